@@ -6,7 +6,7 @@ fp16 [65536 x 1920] activation tensor, group 128.  One "step" = one pass of the
 fused kernel over that tensor (one call of fp_quant_e2_per_group_cuda's HIP
 replacement through the C ABI), input and output resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 N > 1: one rank per GPU over RCCL.  Either the caller starts the ranks
 (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`: WORLD_SIZE is set), or
@@ -52,7 +52,12 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--skip", default="", help="comma-separated secondary legs to leave out (profiling aid): "
                                                "calibration,generation,format_search,other_kernels,steps")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) to DIR/*.npy (see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class Stage:
@@ -156,6 +161,7 @@ class GpuPlatform:
         sp = self.stream.cuda_stream
         ptrs = [(a.data_ptr(), b.data_ptr()) for a, b in zip(xs, outs)]
         counter = [0]
+        self._counter = counter
 
         def step():
             xp, op = ptrs[counter[0] % NBUF]
@@ -165,6 +171,10 @@ class GpuPlatform:
                 _lib.check(st, "fpq_quant_rows")
 
         return step, xs[0].numel(), xs[0]
+
+    def last_output(self):
+        """The tensor the latest step() wrote: the fp16 [ROWS x COLS] result a caller of fpq_quant_rows receives."""
+        return self._keep[1][(self._counter[0] - 1) % NBUF]
 
     def release_hot_path(self):
         self._keep = None
@@ -1004,6 +1014,25 @@ def headline_kernel_label():
     return "rows16_lut_subwave_kernel<16 lanes/group, U=1, HW4: E2M1 levels from the FP4 conversion hardware>"
 
 
+DUMP_ROWS, DUMP_SEED = 8192, 1234    # --dump-outputs: 8192 of the 65536 rows = 63 MB as float32 (the whole output is 503 MB)
+
+
+def dump_rows():
+    """The rows --dump-outputs writes: a fixed, seeded choice, ascending, the same in every run and every build."""
+    import torch
+    return torch.randperm(ROWS, generator=torch.Generator().manual_seed(DUMP_SEED))[:DUMP_ROWS].sort().values
+
+
+def dump_outputs(out_dir, y):
+    """Write what the last timed step handed its caller - the fp16 fake-quantized [ROWS x COLS] tensor `y` - as
+    DIR/quant_e2m1_g128.npy: the rows dump_rows() names (whole groups of 128), converted to float32, which is exact.
+    The inputs are seeded (GpuPlatform.hot_path), so two builds run with the same arguments can be compared value for value."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = dump_rows().to(y.device)
+    np.save(os.path.join(out_dir, "quant_e2m1_g128.npy"), y.index_select(0, rows).float().cpu().numpy())
+
+
 def build_result(args, world, elems, elapsed, kernel_ms, calib, rccl_ranks, data):
     """The contract line (everything the timed region determines)."""
     ms_per_step = elapsed / args.steps * 1e3
@@ -1129,6 +1158,9 @@ def main(argv=None, script=None, platform_factory=GpuPlatform):
         t = torch.tensor([elapsed], device=plat.dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        stage[0] = "dumping the last step's output"
+        dump_outputs(args.dump_outputs, plat.last_output())
 
     def headline(calib):
         return build_result(args, world, elems, elapsed, kernel_ms, calib, rccl_ranks, plat.data)

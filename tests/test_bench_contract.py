@@ -48,6 +48,32 @@ def test_bench_prints_one_contract_line():
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_is_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the seeded row sample of the last timed step's output, as float32, equal to the oracle on the same
+    seeded input (5 timed steps behind 2 warm-up ones over NBUF = 4 buffers: the last step quantized buffer 2)."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    from oracle import fpq_oracle as orc
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+                          "--skip", "calibration,generation,format_search,other_kernels,steps", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+    assert res["steps"] == 5 and res["ms_per_step"] > 0
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["quant_e2m1_g128.npy"] and sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    got = np.load(tmp_path / files[0])
+    assert got.dtype == np.float32 and got.shape == (bench.DUMP_ROWS, bench.COLS)
+    last = (2 + 5 - 1) % bench.NBUF
+    torch.manual_seed(last)
+    x = torch.randn(bench.ROWS, bench.COLS, device="cuda:0").half()[bench.dump_rows().to("cuda:0")].cpu()
+    want = orc.per_group_kernel_sem(x, "e2m1", bench.GROUP).float().numpy()
+    assert np.array_equal(got.view(np.int32), want.view(np.int32))
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_share_the_gpu_over_gloo():
     """`bench.py --gpus 2` with FPQ_BENCH_SHARE_GPU=1: two ranks on the one GPU of a test box, collectives over gloo (RCCL
     refuses two ranks on a device).  Every GPU-side step of the multi-rank line runs for real - the shards, the barrier
