@@ -1,4 +1,4 @@
-// fpq_adaln.h - the complete producer of tr/basic_var.py:263 / :266 for fp16 activations, second generation:
+// fpq_adaln.h - the complete producer of tr/basic_var.py:263 / :266 for rows of up to 2560 channels:
 //     h  = half( fma( LN(x), A, B ) ),   A = half(scale + 1) * s,  B = shift * s      (fp32; LN without affine)
 //     x1 = half( FWHT128( c_h * (h * D) ) )
 //     q  = per-group(128) quant(x1)
@@ -7,7 +7,8 @@
 // What the counters said about the first generation (adaln_rotate_quant16_kernel, profiles/r02_pmc_adaln_before.txt):
 // 41 VALU instructions per element, but the vector pipe only 38 % busy; 134-140 VGPRs = 3 wavefronts per SIMD, each
 // walking its rows strictly load -> reduce -> compute -> store, 42 % of the wavefront-cycles waiting on memory.
-// Latency-bound, not throughput-bound.  Hence:
+// Latency-bound, not throughput-bound.  Hence the second generation (a butterfly form, retired once the third below
+// measured faster):
 //   * a workgroup owns ROWS consecutive rows of ONE batch entry and stages the modulation of that entry - already
 //     folded with the smoothing vector: A, B above - in LDS once; the per-element modulate is one fma instead of
 //     add, mul, add, mul plus two 16-byte modulation loads and their conversions per vector;
@@ -16,11 +17,7 @@
 //   * the rotation's sign vector is folded into the staged modulation, the first butterfly stage reads the packed
 //     halves directly (fwht128_h_n): no sign flips and no fp16 -> fp32 conversions in the row loop;
 //   * the NEXT row's loads are issued before the current row is processed (software prefetch);
-//   * wavefront sums are DPP + v_permlane16/32_swap: no LDS round trip, no address arithmetic;
-//   * straight-line code: the launch picks MAXC = ceil(vectors per row / 64) exactly, so only the LAST vector of a
-//     lane can fall outside the row; it is loaded from a clamped address and zeroed, and its store is the one
-//     exec-masked branch of the row loop.  Vectors go through the stages two at a time (stage-major source order:
-//     two independent dependency chains per wavefront for the in-order issue to interleave).
+//   * wavefront sums are DPP + v_permlane16/32_swap: no LDS round trip, no address arithmetic.
 // (Tried and dropped: scaling by c_h in front of the butterfly, where it would ride on the fp16 -> fp32 widening.
 //  The butterfly of raw fp16 values is nearly always EXACT in fp32 - 11-bit inputs of similar magnitude - while
 //  19-bit inputs are not: rotated values went from <= 1 to 3 fp16 ulp off the fp64 product.)
@@ -73,414 +70,6 @@ __device__ __forceinline__ void wave_sum2_dpp(float& a, float& b) {
 
 typedef _Float16 h2v_t __attribute__((ext_vector_type(2)));
 
-// build-time knobs for A/B experiments (tools/ab_quant.py); the defaults are the measured best
-#ifndef FPQ_ADALN_PREFETCH
-#define FPQ_ADALN_PREFETCH 1
-#endif
-#ifndef FPQ_ADALN_N2
-#define FPQ_ADALN_N2 2
-#endif
-#ifndef FPQ_ADALN_WAVES
-#define FPQ_ADALN_WAVES 0
-#endif
-#if FPQ_ADALN_WAVES > 0
-#define FPQ_ADALN_OCC __attribute__((amdgpu_waves_per_eu(FPQ_ADALN_WAVES, 8)))
-#else
-#define FPQ_ADALN_OCC
-#endif
-
-#ifndef FPQ_ADALN_PREFETCH32
-#define FPQ_ADALN_PREFETCH32 1
-#endif
-#ifndef FPQ_ADALN_X32_WAVES   // fp32 rows of 13 .. 16 groups with the next row prefetched: 130 registers = 3 wavefronts per SIMD; capped at 128 (= 4, with 3 - 5 spilled) measured the same 134 - 138 us: left uncapped
-#define FPQ_ADALN_X32_WAVES 1
-#endif
-
-// MFMA: the rotation on the matrix cores (fpq_rotate_mfma.h: a row of up to 16 groups is one tile; value output only).
-// X32: fp32 rows - the model's case: the residual stream is fp32 under the reference's autocast (tr/var.py:168,209:
-// fp16 Linear output + fp32 position embedding; tr/basic_var.py:264,267: fp32 x + fp16 branch).  A lane then loads
-// 4-float vectors n * 64 + lane of the row (n = 0 .. 2 MAXC - 1, every load a fully coalesced 16 bytes per lane; a
-// 32-bytes-per-lane mapping would leave each load instruction half of every 128-byte line, see fpq_fast32.h): that is
-// half h = lane & 1 of the 8-element chunk 32 n + lane / 2.  Statistics do not care, the modulation planes are kept by
-// halves anyway, and the lane's fp16 results (8 bytes) meet their other half in LDS - straight in the matrix-core
-// operand image, or in a row buffer that is read back in the one-chunk-per-lane order of the butterfly forms.  No
-// cross-lane exchange, no second kernel.
-template <typename Tmod, int MAXC, bool CODES, bool EMIT, bool TOKEN = false, bool X32 = false>
-__global__ __launch_bounds__(kBlock, 1) FPQ_ADALN_OCC void adaln_rq16_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ out,
-                                                           u32x4* __restrict__ h_out, u32x4* __restrict__ y_out,
-                                                           int64_t rows, AdaLnArgs ad, RotArgs r, Lut16Args a, Lut16Tab tab,
-                                                           int rows_per_wg, int wgs_per_batch) {
-  __shared__ __attribute__((aligned(16))) uint16_t lut[kLutLdsEntries];   // static LDS: addresses known at compile time
-  __shared__ u32x4 planes[4 * 64 * 5];                                      // 64 bytes per vector of the row (<= 320 vectors)
-  constexpr bool MOD16 = sizeof(Tmod) == 2;
-  constexpr int W = kBlock / 64;
-  constexpr int RV = X32 ? 2 * MAXC : MAXC;      // 16-byte registers of one row per lane
-  constexpr bool PREFETCH = X32 ? (FPQ_ADALN_PREFETCH32 != 0) : (FPQ_ADALN_PREFETCH != 0);
-  const int vpr = (int)r.vec_per_row;            // host: (MAXC - 1) * 64 < vpr <= MAXC * 64
-  FPQ_PHASE("workgroup_prologue");
-  // four planes of vpr x 16 bytes: A[8v..8v+3], A[8v+4..8v+7], B[8v..8v+3], B[8v+4..8v+7]
-  // (a lane reads 16 bytes of each plane at 16 * v: consecutive lanes, consecutive banks)
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  u32x4* buf = nullptr;
-  if constexpr (X32) {
-    __shared__ u32x4 rowbuf[W][64 * MAXC];   // the modulated row, halves in, whole chunks out
-    buf = rowbuf[wave];
-  }
-  const int64_t b = blockIdx.x / wgs_per_batch;
-  const int chunk = blockIdx.x % wgs_per_batch;
-  const int64_t L = ad.rows_per_batch;
-  const int64_t row0 = b * L + (int64_t)chunk * rows_per_wg;
-  int64_t n_here = L - (int64_t)chunk * rows_per_wg;
-  if (n_here > rows_per_wg) n_here = rows_per_wg;
-  if (row0 + n_here > rows) n_here = rows - row0;
-
-  // vector c of this lane is vector c * 64 + lane of the row; only c = MAXC - 1 can lie outside
-  const bool last_live = (MAXC - 1) * 64 + lane < vpr;
-  int vidx[MAXC];
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c) vidx[c] = c * 64 + lane;
-  if (!last_live) vidx[MAXC - 1] = vpr - 1;      // any valid address: the value is zeroed, the store masked
-
-  // X32: 4-float vector n * 64 + lane; only the last two can lie outside (a whole half-wave at a time: vpr % 16 == 0)
-  int qidx[RV];
-  bool qlive[RV];
-#pragma unroll
-  for (int n = 0; n < RV; ++n) {
-    qidx[n] = n * 64 + lane;
-    qlive[n] = !X32 || qidx[n] < 2 * vpr;
-    if (!qlive[n]) qidx[n] = 2 * vpr - 1;
-  }
-  auto load_row = [&](u32x4 (&dst)[RV], int64_t row) {
-    if constexpr (X32) {
-      const u32x4* p = x + row * (2 * vpr);
-#pragma unroll
-      for (int n = 0; n < RV; ++n) dst[n] = __builtin_nontemporal_load(p + qidx[n]);
-    } else {
-      const u32x4* p = x + row * vpr;
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) dst[c] = __builtin_nontemporal_load(p + vidx[c]);
-    }
-  };
-  u32x4 cur[RV];
-#pragma unroll
-  for (int c = 0; c < RV; ++c) cur[c] = u32x4{0, 0, 0, 0};
-  if (wave < n_here) load_row(cur, row0 + wave);   // requested before the staging below
-
-  // ---- stage the table and the folded modulation of batch entry b ----
-  lut16_stage(lut, tab, a.shift);
-  for (int v = threadIdx.x; v < vpr; v += kBlock) {
-    const int64_t col = (int64_t)v * 8;
-    float sc[8], sh[8];
-    if constexpr (MOD16) {
-      const u32x4 ws = *(const u32x4*)((const _Float16*)ad.scale + b * ad.cols + col);
-      const u32x4 wh = *(const u32x4*)((const _Float16*)ad.shift + b * ad.cols + col);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint32_t s1p = pk_add_f16(ws[k], 0x3C003C00u);   // scale.add(1) is an fp16 op in the reference
-        sc[2 * k] = h2f(s1p & 0xFFFFu);
-        sc[2 * k + 1] = h2f(s1p >> 16);
-        sh[2 * k] = h2f(wh[k] & 0xFFFFu);
-        sh[2 * k + 1] = h2f(wh[k] >> 16);
-      }
-    } else {
-      const u32x4* ap = (const u32x4*)((const float*)ad.scale + b * ad.cols + col);
-      const u32x4* bp = (const u32x4*)((const float*)ad.shift + b * ad.cols + col);
-      const u32x4 a0 = ap[0], a1 = ap[1], b0 = bp[0], b1 = bp[1];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        sc[k] = u2f(a0[k]) + 1.0f;
-        sc[4 + k] = u2f(a1[k]) + 1.0f;
-        sh[k] = u2f(b0[k]);
-        sh[4 + k] = u2f(b1[k]);
-      }
-    }
-    if (r.smooth) {
-      const u32x4* sp = (const u32x4*)(r.smooth + col);
-      const u32x4 s0 = sp[0], s1 = sp[1];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        sc[k] *= u2f(s0[k]);
-        sh[k] *= u2f(s0[k]);
-        sc[4 + k] *= u2f(s1[k]);
-        sh[4 + k] *= u2f(s1[k]);
-      }
-    }
-    // the rotation's sign vector D rides on the modulation: half(-t) == -half(t), so h * D = half(fma(ln, A*D, B*D))
-    const int j0 = (v * 8) & 127;
-    const uint32_t dbits = (r.sign[j0 >> 5] >> (j0 & 31)) & 0xFFu;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const uint32_t flip = ((dbits >> k) & 1u) << 31;
-      sc[k] = u2f(fbits(sc[k]) ^ flip);
-      sh[k] = u2f(fbits(sh[k]) ^ flip);
-    }
-    planes[v] = u32x4{fbits(sc[0]), fbits(sc[1]), fbits(sc[2]), fbits(sc[3])};
-    planes[vpr + v] = u32x4{fbits(sc[4]), fbits(sc[5]), fbits(sc[6]), fbits(sc[7])};
-    planes[2 * vpr + v] = u32x4{fbits(sh[0]), fbits(sh[1]), fbits(sh[2]), fbits(sh[3])};
-    planes[3 * vpr + v] = u32x4{fbits(sh[4]), fbits(sh[5]), fbits(sh[6]), fbits(sh[7])};
-  }
-  __syncthreads();
-
-  const int lg = lane & 15;
-  const uint32_t sb = (r.sign[lg >> 2] >> ((lg & 3) * 8)) & 0xFFu;
-  uint32_t sx[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) sx[k] = (((sb >> (2 * k)) & 1u) << 15) | (((sb >> (2 * k + 1)) & 1u) << 31);
-  const float inv_c = 1.0f / (float)ad.cols;
-  const h2v_t ones = {(_Float16)1.0f, (_Float16)1.0f};
-
-  // One row: `cur` holds it, the wavefront's next row (if any) is requested into `nxt` first (software prefetch).
-  // The row loop below alternates two register sets, so no row is ever copied from register to register.
-  auto do_row = [&](u32x4 (&cur)[RV], u32x4 (&nxt)[RV], int i) {
-    const int64_t row = row0 + i;
-    FPQ_PHASE("prefetch_next_row");
-    if constexpr (PREFETCH) {
-      if (i + W < n_here) load_row(nxt, row + W);      // wave-uniform branch
-    } else {
-      (void)nxt;
-      if (i != wave) load_row(cur, row);               // no prefetch: the row is requested when its turn comes
-    }
-    if constexpr (X32) {
-#pragma unroll
-      for (int n = (RV > 2 ? RV - 2 : 0); n < RV; ++n)
-        if (!qlive[n]) cur[n] = u32x4{0, 0, 0, 0};
-    } else {
-      if (!last_live) cur[MAXC - 1] = u32x4{0, 0, 0, 0};
-    }
-
-    // ---- LayerNorm statistics: sum and sum of squares in one pass over the packed row (v_dot2_f32_f16: exact
-    // products, fp32 accumulation; the zeroed padding vector adds nothing), var = E[x^2] - mean^2.  That
-    // subtraction cancels when |mean| >> sigma: rows with mean^2 >= 64 var (6 of the 24 bits gone; also NaN / Inf
-    // rows) take the centred second pass instead - wave-uniform branch, rare.
-    // fp32 rows: plain sums, the squares are rounded: the centred pass already when mean^2 >= 8 var.
-    FPQ_PHASE("ln_stats");
-    float a1[RV], a2[RV];
-#pragma unroll
-    for (int c = 0; c < RV; ++c) a1[c] = a2[c] = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int c = 0; c < RV; ++c) {
-        const uint32_t xw = cur[c][k];   // NOT __builtin_bit_cast(h2v_t, cur[c][k]): hipcc 7.2 then reads element 0 for every k
-        if constexpr (X32) {
-          const float xf = u2f(xw);
-          a1[c] += xf;
-          a2[c] = __builtin_fmaf(xf, xf, a2[c]);
-        } else {
-          const h2v_t xv = __builtin_bit_cast(h2v_t, xw);
-          a1[c] = __builtin_amdgcn_fdot2(xv, ones, a1[c], false);
-          a2[c] = __builtin_amdgcn_fdot2(xv, xv, a2[c], false);
-        }
-      }
-    float s1 = a1[0], s2 = a2[0];
-#pragma unroll
-    for (int c = 1; c < RV; ++c) {
-      s1 += a1[c];
-      s2 += a2[c];
-    }
-    FPQ_PHASE("ln_reduce_rstd");
-    wave_sum2_dpp(s1, s2);
-    const float mean = s1 * inv_c;
-    float var = __builtin_fmaf(-mean, mean, s2 * inv_c);
-    if (!(mean * mean < (X32 ? 8.0f : 64.0f) * var)) {
-#pragma unroll
-      for (int c = 0; c < RV; ++c) a2[c] = 0.0f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int c = 0; c < RV; ++c) {
-          if constexpr (X32) {
-            const float d0 = u2f(cur[c][k]) - mean;
-            a2[c] = __builtin_fmaf(d0, d0, a2[c]);
-          } else {
-            const float d0 = fma_h_lo(cur[c][k], 1.0f, -mean), d1 = fma_h_hi(cur[c][k], 1.0f, -mean);
-            a2[c] = __builtin_fmaf(d0, d0, a2[c]);
-            a2[c] = __builtin_fmaf(d1, d1, a2[c]);
-          }
-        }
-      if constexpr (X32) {                            // the zeroed padding is not part of the row
-#pragma unroll
-        for (int n = (RV > 2 ? RV - 2 : 0); n < RV; ++n)
-          if (!qlive[n]) a2[n] = 0.0f;
-      } else {
-        if (!last_live) a2[MAXC - 1] = 0.0f;
-      }
-      s2 = a2[0];
-#pragma unroll
-      for (int c = 1; c < RV; ++c) s2 += a2[c];
-      var = wave_sum_dpp(s2) * inv_c;
-    }
-    // rstd = 1 / sqrt(var + eps): v_rsq_f32 (1 ulp) + one Newton step, ~2^-23 relative - four instructions instead of
-    // the IEEE sqrt and division sequences (~25); what it feeds is rounded to fp16
-    const float ve = var + ad.eps;
-    float rstd = __builtin_amdgcn_rsqf(ve);
-    rstd = __builtin_fmaf(rstd * __builtin_fmaf(-ve * rstd, rstd, 1.0f), 0.5f, rstd);
-    const float nm = -mean * rstd;
-
-    // per-token operand output of ONE chunk per lane (the butterfly forms, and groups 16 .. 19 of the hybrid): E4M3 bytes
-    // of the levels (fpq_gemm_fp8.h), 8 per vector, or dense 6-bit codes (fpq_gemm_fp6.h)
-    auto token_codes_out = [&](int c, const u32x4& yv, const RowScale16& s, int v) {
-        uint32_t cb[8];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const uint32_t wk = yv[k];
-          const uint32_t rb = div_pair16(wk, s.inv, s.inv_lo, s.inv, s.inv_lo);
-          const uint32_t u = pk_sub_u16(rb, pk_lshr_u16(rb, 15));
-          cb[2 * k] = lut[(u & 0xFFFFu) >> a.shift];
-          cb[2 * k + 1] = lut[u >> (16 + a.shift)];
-        }
-        if (r.code_bits == 6) {
-          // 8 six-bit codes = 48 bits per lane, rows packed densely: the four lanes of a quad own 24 contiguous
-          // bytes; lane q of the quad takes the (3 - q) upper 16-bit words of its own string and the q + 1 lower
-          // words of its right neighbour's, so that lanes 0..2 each store 8 aligned bytes (cols % 32 == 0: a quad
-          // is live or dead as a whole).
-          const uint64_t own = (uint64_t)(cb[0] | (cb[1] << 6) | (cb[2] << 12) | (cb[3] << 18)) |
-                               ((uint64_t)(cb[4] | (cb[5] << 6) | (cb[6] << 12) | (cb[7] << 18)) << 24);
-          const uint32_t nlo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)own, 0xF9, 0xF, 0xF, false);   // quad_perm [1,2,3,3]
-          const uint32_t nhi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(own >> 32), 0xF9, 0xF, 0xF, false);
-          const uint64_t nb = ((uint64_t)nhi << 32) | nlo;
-          const int qp = lane & 3, sr = 16 * qp;
-          const uint64_t w = (own >> sr) | (nb << (48 - sr));
-          if (qp < 3) {
-            uint8_t* dst = (uint8_t*)out + row * ((int64_t)vpr * 6) + (int64_t)c * (64 * 6) + 24 * (lane >> 2) + 8 * qp;
-            __builtin_nontemporal_store(u32x2{(uint32_t)w, (uint32_t)(w >> 32)}, (u32x2*)dst);
-          }
-        } else {
-          const u32x2 o2 = {cb[0] | (cb[1] << 8) | (cb[2] << 16) | (cb[3] << 24), cb[4] | (cb[5] << 8) | (cb[6] << 16) | (cb[7] << 24)};
-          __builtin_nontemporal_store(o2, (u32x2*)out + row * vpr + v);
-        }
-    };
-    FPQ_PHASE("modulate_to_image");
-    if constexpr (X32) {
-      // ---- fp32 rows: modulate this lane's half-chunks, 8 bytes of fp16 each, into LDS ----
-      const int lane_x = rq_opaque(lane);
-      const int hsel = lane_x & 1, k2 = lane_x >> 1;
-      u32x2* img = (u32x2*)buf;
-#pragma unroll
-      for (int n = 0; n < RV; ++n) {
-        const int v = 32 * n + k2;                       // chunk of the row
-        u32x2 hw2 = {0, 0};
-        if (n < RV) {
-          const u32x4 A = planes[hsel * vpr + v], B = planes[(2 + hsel) * vpr + v];   // beyond the row: in bounds, unused
-          const u32x4 w = cur[n];
-          hw2[0] = f2h2(__builtin_fmaf(__builtin_fmaf(u2f(w[0]), rstd, nm), u2f(A[0]), u2f(B[0])), __builtin_fmaf(__builtin_fmaf(u2f(w[1]), rstd, nm), u2f(A[1]), u2f(B[1])));
-          hw2[1] = f2h2(__builtin_fmaf(__builtin_fmaf(u2f(w[2]), rstd, nm), u2f(A[2]), u2f(B[2])), __builtin_fmaf(__builtin_fmaf(u2f(w[3]), rstd, nm), u2f(A[3]), u2f(B[3])));
-          if (n >= RV - 2 && !qlive[n]) hw2 = u32x2{0, 0};
-        }
-        img[v * 2 + hsel] = hw2;
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-    {
-    // ---- modulate, rotate, quantize: vectors two at a time, stage by stage ----
-    u32x4 ys[TOKEN ? MAXC : 1];   // per-token scale: the rotated row waits here for the row maximum
-    uint32_t mrow = 0;
-    (void)ys;
-    (void)mrow;
-#pragma unroll
-    for (int c0 = 0; c0 < MAXC; c0 += FPQ_ADALN_N2) {
-      constexpr int N2 = FPQ_ADALN_N2;
-      const int n = (MAXC - c0) < N2 ? (MAXC - c0) : N2;
-      u32x4 hw[N2], y[N2], o[N2];
-      float t[N2][8];
-#pragma unroll
-      for (int j = 0; j < n; ++j) {
-        const int v = vidx[c0 + j];
-        if constexpr (X32) {
-          hw[j] = buf[v];                                // the modulated row, written by halves above
-        } else {
-          const u32x4 A0 = planes[v], B0 = planes[2 * vpr + v];
-          const u32x4 A1 = planes[vpr + v], B1 = planes[3 * vpr + v];
-          const u32x4 w = cur[c0 + j];
-          hw[j][0] = f2h2(__builtin_fmaf(fma_h_lo(w[0], rstd, nm), u2f(A0[0]), u2f(B0[0])), __builtin_fmaf(fma_h_hi(w[0], rstd, nm), u2f(A0[1]), u2f(B0[1])));
-          hw[j][1] = f2h2(__builtin_fmaf(fma_h_lo(w[1], rstd, nm), u2f(A0[2]), u2f(B0[2])), __builtin_fmaf(fma_h_hi(w[1], rstd, nm), u2f(A0[3]), u2f(B0[3])));
-          hw[j][2] = f2h2(__builtin_fmaf(fma_h_lo(w[2], rstd, nm), u2f(A1[0]), u2f(B1[0])), __builtin_fmaf(fma_h_hi(w[2], rstd, nm), u2f(A1[1]), u2f(B1[1])));
-          hw[j][3] = f2h2(__builtin_fmaf(fma_h_lo(w[3], rstd, nm), u2f(A1[2]), u2f(B1[2])), __builtin_fmaf(fma_h_hi(w[3], rstd, nm), u2f(A1[3]), u2f(B1[3])));
-        }
-      }
-      if (!last_live && c0 + n == MAXC) hw[n - 1] = u32x4{0, 0, 0, 0};
-      fwht128_h_n<N2>(hw, t, n, lg);                     // hw already carries the rotation's signs
-#pragma unroll
-      for (int j = 0; j < n; ++j)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) y[j][k] = mul2_to_h2(t[j][2 * k], t[j][2 * k + 1], r.c_h);
-      uint32_t m[N2];
-#pragma unroll
-      for (int j = 0; j < n; ++j) m[j] = vec_absmax16(y[j]);
-      if constexpr (TOKEN) {
-#pragma unroll
-        for (int j = 0; j < n; ++j) {
-          const int c = c0 + j;
-          ys[c] = y[j];
-          mrow = mrow > m[j] ? mrow : m[j];
-          if constexpr (EMIT) {
-            if (c < MAXC - 1 || last_live) {
-              const int64_t at = row * vpr + vidx[c];
-              if (h_out) __builtin_nontemporal_store(u32x4{hw[j][0] ^ sx[0], hw[j][1] ^ sx[1], hw[j][2] ^ sx[2], hw[j][3] ^ sx[3]}, h_out + at);
-              if (y_out) __builtin_nontemporal_store(y[j], y_out + at);
-            }
-          }
-        }
-        continue;
-      }
-      row_max_dpp16_n<N2>(m, n);
-      uint32_t cd[N2];
-      RowScale16 s[N2];
-#pragma unroll
-      for (int j = 0; j < n; ++j) s[j] = row_scale16(m[j], a.fpos.gmax, a.inv_gpos);
-#pragma unroll
-      for (int j = 0; j < n; ++j) {
-        if constexpr (CODES) cd[j] = codes_vec16(y[j], lut, a.shift, s[j].inv, s[j].inv_lo);
-        else o[j] = quant_vec16<false>(y[j], lut, a.shift, s[j].inv, s[j].inv_lo, s[j].s16x2, 0.f, 0.f, 0u);
-      }
-#pragma unroll
-      for (int j = 0; j < n; ++j) {
-        const int c = c0 + j;
-        if (c < MAXC - 1 || last_live) {
-          const int64_t at = row * vpr + vidx[c];
-          if constexpr (EMIT) {
-            if (h_out) __builtin_nontemporal_store(u32x4{hw[j][0] ^ sx[0], hw[j][1] ^ sx[1], hw[j][2] ^ sx[2], hw[j][3] ^ sx[3]}, h_out + at);
-            if (y_out) __builtin_nontemporal_store(y[j], y_out + at);
-          }
-          if constexpr (CODES) {
-            ((uint32_t*)out)[at] = cd[j];
-            if (lg == 0) r.code_scales[at >> 4] = (uint16_t)(s[j].s16x2 & 0xFFFFu);
-          } else {
-            __builtin_nontemporal_store(o[j], out + at);
-          }
-        }
-      }
-    }
-    if constexpr (TOKEN) {
-      // fp6_quant_*_per_token_cuda on the rotated row (tr/quant_utils.py:503-534): one scale for the whole row
-      mrow = row_max_dpp<64>(mrow);
-      const RowScale16 s = row_scale16(mrow, a.fpos.gmax, a.inv_gpos);
-      if (r.code_scales && lane == 0) r.code_scales[row] = (uint16_t)(s.s16x2 & 0xFFFFu);
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) {
-        if (c == MAXC - 1 && !last_live) continue;
-        const int v = vidx[c];
-        if constexpr (CODES) {
-          token_codes_out(c, ys[c], s, v);
-        } else {
-          const u32x4 o = quant_vec16<false>(ys[c], lut, a.shift, s.inv, s.inv_lo, s.s16x2, 0.f, 0.f, 0u);
-          __builtin_nontemporal_store(o, out + row * vpr + v);
-        }
-      }
-    }
-    }
-    if constexpr (X32) __builtin_amdgcn_wave_barrier();   // the row buffer is rewritten by the next row
-  };
-  u32x4 alt[RV];
-  if constexpr (PREFETCH) {
-    for (int i = wave; i < n_here; i += 2 * W) {   // no barrier below: wavefronts run their rows independently
-      do_row(cur, alt, i);
-      if (i + W < n_here) do_row(alt, cur, i + W);
-    }
-  } else {
-    for (int i = wave; i < n_here; i += W) do_row(cur, alt, i);
-  }
-}
 // ==================================================================================================================
 // Third generation (round 3): the matrix-core form of the producer, rebuilt around the instruction census of the second
 // one (profiles/r03_adaln_isa_census.txt: 585 vector instructions per row and wavefront at C = 1920 in the row loop +
@@ -553,9 +142,13 @@ struct AdalnTiers {
 #else
 #define FPQ_STAMP(k) do { } while (0)
 #endif
-#ifndef FPQ_ADALN_DB       // 1: two register sets, the next row is requested at the START of the current one (same-process A/B: 95.4 - 97.0 us against 91.9 - 97.6 for the single set, profiles/r03_adaln_ab.txt: not the default)
-#define FPQ_ADALN_DB 0
-#endif
+// X32: fp32 rows - the model's case: the residual stream is fp32 under the reference's autocast (tr/var.py:168,209:
+// fp16 Linear output + fp32 position embedding; tr/basic_var.py:264,267: fp32 x + fp16 branch).  A lane then loads
+// 4-float vectors n * 64 + lane of the row (n = 0 .. 2 MAXC - 1, every load a fully coalesced 16 bytes per lane; a
+// 32-bytes-per-lane mapping would leave each load instruction half of every 128-byte line, see fpq_fast32.h): that is
+// half h = lane & 1 of the 8-element chunk 32 n + lane / 2.  Statistics do not care, the modulation planes are kept by
+// halves anyway, and the lane's fp16 results (8 bytes) meet their other half in LDS, straight in the matrix-core
+// operand image.  No cross-lane exchange, no second kernel.
 // NW: wavefronts per workgroup.  (8 sharing one set of planes - the staging paid once per 8 wavefronts - was measured
 // no faster than 4 and is not built any more, profiles/r03_adaln_partition.txt.)
 // PAIR2 (rows of exactly 8 groups = C 1024, VAR-d16; instantiated with MAXC = 4): TWO consecutive rows of a batch entry
@@ -580,13 +173,8 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
   constexpr int W = NW;
   constexpr int RPU = PAIR2 ? 2 : 1;             // rows per unit of work of a wavefront
   constexpr int RV = X32 ? 2 * MAXC : MAXC;      // 16-byte registers of one row per lane
-#ifdef FPQ_ADALN_PV_TEST   // timing experiment only (wrong results): a smaller LDS footprint
-  constexpr int PV = FPQ_ADALN_PV_TEST;
-#else
   constexpr int PV = TIGHT ? 240 : PAIR2 ? 128 : MAXC * 64;   // vectors per modulation plane (not TIGHT: the padding carries zeros)
-#endif
   constexpr int INS = TIGHT ? kRqOutStride : kRqInStride;
-  constexpr bool DB = FPQ_ADALN_DB && !X32 && !EMIT;
   uint16_t* lut = nullptr;                       // symmetric tables only: at most 2 x 512 buckets (E2M3)
   if constexpr (!HW4 && HW6 == 0) {
     __shared__ __attribute__((aligned(16))) uint16_t lut_s[1024];
@@ -641,16 +229,11 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
   // (`hi_half`), and ONE slot pass - butterfly, maximum, scale, quantize, store - serves both (about 200 of a row's
   // ~700 vector instructions belong to that pass).  Not for the emitting form (tests), the per-token forms (the slot
   // enters the row's scale), fp32 rows (their slot chunk meets in the image).
-  constexpr bool PAIRABLE = MAXC == 5 && !X32 && !EMIT && !TOKEN && !DB;
+  constexpr bool PAIRABLE = MAXC == 5 && !X32 && !EMIT && !TOKEN;
   const bool pair_ok = PAIRABLE && vpr - 256 <= 32;
   const int lane16_hi = ((lane + 32) & 63) * 16;     // the slot chunk's vector index of this lane in a `hi_half` row
   auto load_row = [&](u32x4 (&dst)[RV], int64_t row, bool hi_half = false) {
-#ifdef FPQ_ADALN_NOMEM   // timing experiment: zero-record descriptors - every row load returns zeros, every row store is dropped,
-                         // the instruction stream is unchanged: what the kernel costs without its HBM traffic
-    const __amdgpu_buffer_rsrc_t src = rq_rsrc((const char*)x + row * row_bytes, 0);
-#else
     const __amdgpu_buffer_rsrc_t src = rq_rsrc((const char*)x + row * row_bytes, (PAIR2 && row + 1 < hi ? 2 : 1) * row_bytes);
-#endif
 #pragma unroll
     for (int n = 0; n < RV; ++n) {
       int at = la.lane16 + n * 1024;
@@ -787,8 +370,7 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
     }
   };
 
-  // One row.  `cur` holds it; `next_row` >= 0: that row is requested - DB: into `nxt`, at once; otherwise into `cur`,
-  // once the current row has left it.
+  // One row.  `cur` holds it; `next_row` >= 0: that row is requested into `cur` once the current row has left it.
 #ifdef FPQ_ADALN_STAMPS
   unsigned long long st_sum[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = 0, st_rows = 0, st_first = 0;
   const unsigned long long st_t0 = __builtin_amdgcn_s_memrealtime();   // 100 MHz, one clock for the whole chip
@@ -797,7 +379,7 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
   u32x4 pend = {0, 0, 0, 0};      // PAIRABLE: the parked slot chunk of the pair's first row, and that row
   int64_t pend_row = 0;
   bool cur_hi = false;           // the row in `cur` was loaded with its slot chunk on lanes 32 .. 63
-  auto do_row = [&](u32x4 (&cur)[RV], u32x4 (&nxt)[RV], int64_t row, int64_t next_row) {
+  auto do_row = [&](u32x4 (&cur)[RV], int64_t row, int64_t next_row) {
     const int nrows = (PAIR2 && row + 1 < hi) ? 2 : 1;                 // PAIR2: rows in this unit (a batch entry of odd length ends with one)
     const bool hi_half = PAIRABLE && cur_hi;                           // second row of a pair
     const bool park = PAIRABLE && pair_ok && !hi_half && next_row >= 0;   // first row of a pair: its slot waits for the next row
@@ -807,25 +389,7 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
     if (++st_rows == 1) st_first = __builtin_amdgcn_s_memrealtime();   // the wavefront's first row has arrived
 #endif
     FPQ_STAMP(1);                                   // waiting for the row (and, in this build, the previous row's stores)
-#ifdef FPQ_ADALN_COPYONLY   // experiment: the kernel's memory access pattern alone (rows in, rows out, nothing computed; 2: no staging either)
-    if constexpr (!X32 && !EMIT && !CODES && !TOKEN) {
-      const __amdgpu_buffer_rsrc_t dst = rq_rsrc(out + row * vpr, vpr * 16);
-      u32x4 keep[RV];
-#pragma unroll
-      for (int n = 0; n < RV; ++n) keep[n] = cur[n];
-      if (next_row >= 0) load_row(DB ? nxt : cur, next_row);
-#pragma unroll
-      for (int n = 0; n < RV; ++n) __builtin_amdgcn_raw_buffer_store_b128(keep[n], dst, la.lane16 + n * 1024, 0, kRqNt);
-      return;
-    }
-#endif
-    if constexpr (DB) {
-      FPQ_PHASE("prefetch_next_row");
-      if (next_row >= 0) load_row(nxt, next_row);   // wave-uniform
-    } else {
-      (void)nxt;
-    }
-    // ---- LayerNorm statistics (see the second generation above; padding lanes hold zeros) ----
+    // ---- LayerNorm statistics (padding lanes hold zeros) ----
     FPQ_PHASE("ln_stats");
     float a1[RV], a2[RV];
 #pragma unroll
@@ -860,21 +424,12 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
       }
     }
     FPQ_PHASE("ln_reduce_rstd");
-#ifdef FPQ_ADALN_ABLATE_STATS   // measurement only (wrong results): what the kernel would cost with the row statistics given
-    sum1 = 0.0f;
-    s2 = (float)ad.cols;
-    sum1b = 0.0f;
-    s2b = (float)ad.cols;
-#else
     wave_sum2_dpp(sum1, s2);
-#endif
     const float mean = sum1 * inv_c;
     float var = __builtin_fmaf(-mean, mean, s2 * inv_c);
     float mean_b = 0.0f, var_b = 1.0f;
     if constexpr (PAIR2) {
-#ifndef FPQ_ADALN_ABLATE_STATS
       wave_sum2_dpp(sum1b, s2b);
-#endif
       mean_b = sum1b * inv_c;
       var_b = __builtin_fmaf(-mean_b, mean_b, s2b * inv_c);
       if (!(mean * mean < 64.0f * var) || !(mean_b * mean_b < 64.0f * var_b)) {   // either row: both centred (rare)
@@ -999,10 +554,8 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
         for (int k = 0; k < 4; ++k) hw_slot[k] = lane < 32 ? pend[k] : hw_slot[k];
       }
     }
-    if constexpr (!DB) {
-      FPQ_PHASE("prefetch_next_row");
-      if (next_row >= 0) load_row(cur, next_row, park);   // wave-uniform; lands under the rest of this row
-    }
+    FPQ_PHASE("prefetch_next_row");
+    if (next_row >= 0) load_row(cur, next_row, park);   // wave-uniform; lands under the rest of this row
     if constexpr (PAIRABLE) cur_hi = park;
     __builtin_amdgcn_wave_barrier();
     FPQ_STAMP(3);                                   // modulate (plane reads), image writes, next row requested
@@ -1184,11 +737,7 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
           }
         }
       FPQ_STAMP(6);                                 // divide, level, dequantize
-#ifdef FPQ_ADALN_NOMEM
-      rq_store_tile<TIGHT>(img, yw, rq_rsrc(out + row * vpr, 0), la);
-#else
       rq_store_tile<TIGHT>(img, yw, rq_rsrc(out + row * vpr, nrows * vpr * 16), la);
-#endif
       FPQ_STAMP(7);                                 // output image round trip, stores issued
       FPQ_PHASE("row_end");
       if (MAXC == 5 && do_slot) {
@@ -1219,18 +768,13 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
   };
 
   // ---- the workgroup's rows: wavefront w takes rows lo + w, lo + w + 4, ... ----
-  u32x4 cur[RV], alt[DB ? RV : 1];
+  u32x4 cur[RV];
   int64_t i = lo + RPU * wave;
-#if !defined(FPQ_ADALN_COPYONLY) || FPQ_ADALN_COPYONLY < 2
   StageRaw sraw[NST];
   // fp32 rows (10 - 40 KiB of row requests per workgroup): the modulation's loads go first; fp16 rows: the row first, as in
   // round 3 (ten scale steps cold: fp32 rows 176.3 -> 172.9 us for d30 with the modulation first, fp16 rows
   // 137.1 -> 139.2; profiles/r04_adaln_stage_order.txt)
-#ifdef FPQ_ADALN_ROW_FIRST
-  constexpr bool MOD_FIRST = false;
-#else
   constexpr bool MOD_FIRST = X32;
-#endif
   if constexpr (MOD_FIRST) {
     stage_load(b, sraw);
     __builtin_amdgcn_sched_barrier(0);           // keep the modulation's loads in front of the row's in the instruction stream
@@ -1243,19 +787,11 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
   if constexpr (!HW4 && HW6 == 0) lut16_stage(lut, tab, a.shift);
   stage_store(sraw);
   __syncthreads();
-#else
-  if (i < hi) load_row(cur, i);
-#endif
-  if constexpr (DB) {
-    for (; i < hi; i += 2 * W) {                 // two register sets alternate: no row is copied between registers
-      do_row(cur, alt, i, i + W < hi ? i + W : -1);
-      if (i + W < hi) do_row(alt, cur, i + W, i + 2 * W < hi ? i + 2 * W : -1);
-    }
-  } else if (i < hi) {
+  if (i < hi) {
     // first pass peeled: both edges into the loop then carry "loads, then this row's stores", and the wait for the
     // prefetched row leaves the stores in flight (fpq_rotate_mfma.h, rotate_quant_mfma_kernel)
-    do_row(cur, cur, i, i + RPU * W < hi ? i + RPU * W : -1);
-    for (i += RPU * W; i < hi; i += RPU * W) do_row(cur, cur, i, i + RPU * W < hi ? i + RPU * W : -1);
+    do_row(cur, i, i + RPU * W < hi ? i + RPU * W : -1);
+    for (i += RPU * W; i < hi; i += RPU * W) do_row(cur, i, i + RPU * W < hi ? i + RPU * W : -1);
   }
 #ifdef FPQ_ADALN_STAMPS
   if constexpr (!EMIT) {

@@ -18,8 +18,6 @@
   X(FPQ_NO_HW6, 1)          /* E2M3 / E3M2: keep the bucket table instead of the FP6 conversion hardware */            \
   X(FPQ_NO_FAST32, 1)       /* fp32 rows: IEEE division + closed form instead of approximate-then-verify */            \
   X(FPQ_ADALN_NO_PAIR2, 1)  /* adaLN producer at C = 1024: one row per tile */                                         \
-  X(FPQ_ROT_BUTTERFLY, 1)   /* the butterfly form of the 128-point transform instead of the matrix cores */            \
-  X(FPQ_ADALN_V1, 1)        /* first-generation adaLN kernel */                                                        \
   X(FPQ_ADALN_NO_TIGHT, 1)                                                                                             \
   X(FPQ_NO_WAVE_ROWS, 1)    /* long fp16 rows: one workgroup per row even when a wavefront would hold it */            \
   X(FPQ_GEMM_CFG, 0)        /* FP4 GEMM tiling: 0..2 register-staged, 10 / 20 / 30 LDS-DMA 256x128 / 128x128 / 64x128 */ \
@@ -28,10 +26,7 @@
   X(FPQ_ROT_WGS, 0)         /* rotate_quant: workgroups per generation */                                              \
   X(FPQ_ADALN_ROWS, 0)      /* adaLN producer: rows per workgroup */                                                   \
   X(FPQ_ADALN_TAIL, 0)      /* adaLN producer: rows at the end of the grid cut into finer tiers */                     \
-  X(FPQ_ADALN_GRID, 0)      /* first-generation adaLN kernel: grid cap */                                              \
-  X(FPQ_ADALN_LANES, 0)     /* adaLN producer: 64 (wavefront per row) or 256 (workgroup per row) */                    \
   X(FPQ_BIGTAB_RPB, 0)                                                                                                 \
-  X(FPQ_BIGTAB_U, 0)                                                                                                   \
   X(FPQ_BIGTAB_CAP, 0)
 enum FpqOptId {
 #define FPQ_OPT_ENUM(name, is_flag) OPT_##name,

@@ -141,16 +141,11 @@ __device__ __forceinline__ float fmaf_h_hi(uint32_t w, float b, float c) {
 //     hardware-level form of the producers.
 // Round 2 carried 1/s as inv + inv_lo and rounded x * inv + x * inv_lo straight to fp16 (the exact quotient, 25 cycles of
 // the vector pipe per pair: v_fma_mixlo/hi_f16 cost 8.2 each, tools/probe/valu_issue_cost.hip); this form: 13.
-// -DFPQ_DIV_WITH_LO restores the two-term reciprocal (21.8 cycles per pair) for A/B runs.
+// (The two-term reciprocal measured 21.8 cycles per pair.)
 __device__ __forceinline__ uint32_t div_pair16(uint32_t w, float ih0, float il0, float ih1, float il1) {
-#ifdef FPQ_DIV_WITH_LO
-  const float t0 = mul_h_lo(w, il0), t1 = mul_h_hi(w, il1);
-  return f2h2(fmaf_h_lo(w, ih0, t0), fmaf_h_hi(w, ih1, t1));
-#else
   (void)il0;
   (void)il1;
   return f2h2(mul_h_lo(w, ih0), mul_h_hi(w, ih1));
-#endif
 }
 
 // the two table entries of a packed pair of bucket patterns as ONE packed register: byte offsets straight from the
@@ -516,43 +511,12 @@ inline void lut16_build_host(uint16_t* lut, const Lut16Args& a) {
 // torch: aten/src/ATen/native/cuda/ActivationGeluKernel.cu, GeluCUDAKernelImpl, approximate == tanh (opmath = float):
 //   kBeta = M_SQRT2 * M_2_SQRTPI * 0.5, kKappa = 0.044715; x_cube = x * x * x; inner = kBeta * (x + kKappa * x_cube);
 //   0.5 * x * (1 + tanh(inner))
-// FPQ_GELU_FMA: the compiler that built torch contracts x + kKappa * x_cube into one fma (hipcc's default for HIP sources);
-// this library is built with contraction off, so the fma is spelled out.
-#ifndef FPQ_GELU_FMA
-#define FPQ_GELU_FMA 1
-#endif
-__device__ __forceinline__ float tanh_devlib(float x) {   // __ocml_tanh_f32 (ROCm device library), restated
-  const float y = __builtin_fabsf(x);
-  float z;
-  if (y < 0.625f) {
-    const float y2 = x * x;
-    float p = __builtin_fmaf(y2, -0x1.758e7ap-8f, 0x1.521192p-6f);
-    p = __builtin_fmaf(y2, p, -0x1.b8389cp-5f);
-    p = __builtin_fmaf(y2, p, 0x1.110704p-3f);
-    p = __builtin_fmaf(y2, p, -0x1.555532p-2f);
-    z = __builtin_fmaf(y2, y * p, y);
-  } else {
-    const float t = __builtin_expf(2.0f * y);
-    z = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(t + 1.0f), 1.0f);
-  }
-  return __builtin_copysignf(z, x);
-}
-__device__ __forceinline__ float gelu_tanh_like_torch(float x) {
-  const float kBeta = (float)(1.41421356237309504880 * 1.12837916709551257390 * 0.5), kKappa = 0.044715f;
-  const float x3 = x * x * x;
-#if FPQ_GELU_FMA
-  const float inner = kBeta * __builtin_fmaf(kKappa, x3, x);
-#else
-  const float inner = kBeta * (x + kKappa * x3);
-#endif
-  return 0.5f * x * (1.0f + tanh_devlib(inner));
-}
-
 // The form the epilogue runs (9 vector instructions instead of ~30): gelu(x) = x w, w = (1 + tanh(u)) / 2 = 1 / (1 + 2^m),
 // m = -2 log2(e) u = x (c0 + c1 x^2); `(w - 0.5) + 0.5` snaps w to the grid torch's own 1 + tanh(u) lives on (its tanh is an
 // fp32 number just below 1 for the deep negatives, where 1 + tanh cancels: without the snap the more exact w is up to 2 fp16
 // ulps away from what torch returns on 7 inputs in [-5.2, -4.7]).  tools/probe/gelu_probe.hip runs eight candidate forms over
-// all 65536 fp16 inputs against torch on the GPU (profiles/r05_gelu_probe.txt): the torch-order form above is bit-equal
+// all 65536 fp16 inputs against torch on the GPU (profiles/r05_gelu_probe.txt): the torch-order form (the device library's
+// tanh restated, with the fma torch's compiler contracts) is bit-equal
 // to torch on every input; this one differs on 5 inputs, by one ulp each, NaN exactly where torch has NaN (NaN, -inf).
 __device__ __forceinline__ float gelu_tanh_fast(float x) {
   const float kBeta = (float)(1.41421356237309504880 * 1.12837916709551257390 * 0.5), kKappa = 0.044715f;
@@ -1095,14 +1059,12 @@ __global__ __launch_bounds__(kBlock) void rows16_lut_wave_kernel(const uint16_t*
 // (rotate_utils/rotation_utils.py:69-104, hadamard_utils.py:63-99), so per 128-chunk
 //     x1 = half( c_h * FWHT128(h * D) ),   c_h = half(float32(1/sqrt(128))) = 0.08837890625   (one rounding:
 //          v_fma_mixlo/hi_f16; the butterfly of fp16 inputs is nearly always exact in fp32)
-// Here: h = half(x * s) (s optional), sign flip by xor, 3 butterfly stages inside the lane's
-// 8 values, 4 across the 16 lanes of the group (DPP quad_perm for lane^1, lane^2; ds_swizzle
-// for lane^4, lane^8 - no LDS memory is touched), fp32 throughout, one rounding to fp16, and
-// the result feeds the quantizer of this file without leaving registers.  A dense fp16 GEMM
-// of 2*rows*C^2 FLOPs and a 2 B/elem round trip disappear.
+// The transform runs on the matrix cores (fpq_rotate_mfma.h); the butterfly below (fwht128_h_n) serves what of the adaLN
+// producers' rows does not: the first generation (C > 2560) and the groups beyond a tile in the third (fpq_adaln.h).  A dense fp16 GEMM of 2*rows*C^2 FLOPs and a 2 B/elem round trip
+// disappear.
 //
-// Parity contract: the quant stage is bit-exact for the rotated values this kernel
-// produces (it can emit them); the rotated values are within 1 fp16 ulp of the
+// Parity contract: the quant stage is bit-exact for the rotated values the kernels
+// produce (it can emit them); the rotated values are within 1 fp16 ulp of the
 // fp64-accumulated product (the reference GEMM's own summation order is unspecified).
 // ---------------------------------------------------------------------------------
 struct RotArgs {
@@ -1131,55 +1093,17 @@ __device__ __forceinline__ float xlane_xor2(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));
 }
 
-// FWHT over the 128 values held by 16 lanes x 8 registers; natural (Sylvester) order.
-// The values travel as 4 float pairs (t[j], t[j+4]) so that the butterflies map onto the
+// The butterfly's values travel as 4 float pairs (t[j], t[j+4]) so that the butterflies map onto the
 // packed fp32 ALU (v_pk_add_f32 / v_pk_fma_f32: two results per issue slot).
 typedef float f2_t __attribute__((ext_vector_type(2)));
 
-#ifndef FPQ_FWHT_SWZ
-#define FPQ_FWHT_SWZ 0   // 1: lane ^ 1 / lane ^ 2 exchanges through ds_swizzle (LDS crossbar) instead of DPP moves (VALU)
-#endif
-__device__ __forceinline__ float xlane_xor1s(float v) {
-  return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x80B1));   // quad perm [1,0,3,2]
-}
-__device__ __forceinline__ float xlane_xor2s(float v) {
-  return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x804E));   // quad perm [2,3,0,1]
-}
 __device__ __forceinline__ f2_t xlane2(f2_t v, int which) {
   f2_t r;
   if (which == 1) { r.x = xlane_xor1(v.x); r.y = xlane_xor1(v.y); }
-#if FPQ_FWHT_SWZ
-  else if (which == 2) { r.x = xlane_xor2s(v.x); r.y = xlane_xor2s(v.y); }
-#endif
   else if (which == 2) { r.x = xlane_xor2(v.x); r.y = xlane_xor2(v.y); }
   else if (which == 4) { r.x = xlane_xor4(v.x); r.y = xlane_xor4(v.y); }
   else { r.x = xlane_xor8(v.x); r.y = xlane_xor8(v.y); }
   return r;
-}
-
-__device__ __forceinline__ void fwht128(float (&t)[8], int lane_in_group) {
-  f2_t p[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) p[j] = f2_t{t[j], t[j + 4]};
-  // index bit 0 and bit 1: whole pairs against whole pairs
-  { f2_t a = p[0], b = p[1]; p[0] = a + b; p[1] = a - b; a = p[2]; b = p[3]; p[2] = a + b; p[3] = a - b; }
-  { f2_t a = p[0], b = p[2]; p[0] = a + b; p[2] = a - b; a = p[1]; b = p[3]; p[1] = a + b; p[3] = a - b; }
-  // index bit 2: inside each pair
-#pragma unroll
-  for (int j = 0; j < 4; ++j) p[j] = f2_t{p[j].x + p[j].y, p[j].x - p[j].y};
-  // index bits 3..6 live in the lane number: partner + sign*mine (lower lane a+b, upper lane a-b)
-  const float s1 = (lane_in_group & 1) ? -1.0f : 1.0f, s2 = (lane_in_group & 2) ? -1.0f : 1.0f;
-  const float s4 = (lane_in_group & 4) ? -1.0f : 1.0f, s8 = (lane_in_group & 8) ? -1.0f : 1.0f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) p[j] = __builtin_elementwise_fma(p[j], f2_t{s1, s1}, xlane2(p[j], 1));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) p[j] = __builtin_elementwise_fma(p[j], f2_t{s2, s2}, xlane2(p[j], 2));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) p[j] = __builtin_elementwise_fma(p[j], f2_t{s4, s4}, xlane2(p[j], 4));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) p[j] = __builtin_elementwise_fma(p[j], f2_t{s8, s8}, xlane2(p[j], 8));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { t[j] = p[j].x; t[j + 4] = p[j].y; }
 }
 
 // half(a * b) packed from two fp32 values: the rotated value half(c_h * FWHT(...)).  Two v_mul_f32 and one
@@ -1207,7 +1131,9 @@ __device__ __forceinline__ float fmix_hsh_hi(uint32_t w, float s, uint32_t pw) {
 // source order: N dependency chains for the in-order issue to interleave).  The butterfly stages commute, so the
 // first one is the lane-bit-0 stage, taken straight from the PACKED halves: one DPP move fetches two partner
 // values, and v_fma_mix_f32 widens mine and the partner's while it adds (exact) - no separate fp16 -> fp32
-// conversion exists.  Then the three in-register stages on float pairs, then lane bits 1, 2, 3 as in fwht128.
+// conversion exists.  Then the three in-register stages on float pairs, then lane bits 1, 2, 3: partner + sign * mine
+// (lower lane a + b, upper lane a - b; DPP quad_perm for lane ^ 2, ds_swizzle for lane ^ 4, lane ^ 8 - no LDS memory is
+// touched).
 template <int N>
 __device__ __forceinline__ void fwht128_h_n(const u32x4 (&w)[N], float (&t)[N][8], int n, int lane_in_group) {
   const float s1 = (lane_in_group & 1) ? -1.0f : 1.0f, s2 = (lane_in_group & 2) ? -1.0f : 1.0f;
@@ -1219,11 +1145,7 @@ __device__ __forceinline__ void fwht128_h_n(const u32x4 (&w)[N], float (&t)[N][8
     uint32_t pw[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-#if FPQ_FWHT_SWZ
-      pw[k] = (uint32_t)__builtin_amdgcn_ds_swizzle((int)w[q][k], 0x80B1);
-#else
       pw[k] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[q][k], 0xB1, 0xF, 0xF, true);
-#endif
 #pragma unroll
     for (int k = 0; k < 4; ++k) {   // element 2k, 2k+1 -> pair register (k & 1 ? .. ): t index j pairs with j + 4
       const float lo = fmix_hsh_lo(w[q][k], s1, pw[k]), hi = fmix_hsh_hi(w[q][k], s1, pw[k]);
@@ -1307,93 +1229,6 @@ __device__ __forceinline__ void row_max_dpp16_n(uint32_t (&v)[N], int n) {
     }
 }
 
-template <typename Tin, bool EMIT, int U, bool CODES = false>
-__global__ __launch_bounds__(kBlock) void rotate_quant16_kernel(const void* __restrict__ xv, u32x4* __restrict__ out,
-                                                               u32x4* __restrict__ rot_out, int64_t n_vec,
-                                                               RotArgs r, Lut16Args a, Lut16Tab tab) {
-  __shared__ __attribute__((aligned(16))) uint16_t lut[kLutLdsEntries];   // static: a compile-time LDS address (a dynamic base is not folded into the ds_read offsets)
-  const int lg = threadIdx.x & 15;
-  // this lane's 8 sign bits -> xor masks on packed halves
-  const uint32_t sb = (r.sign[lg >> 2] >> ((lg & 3) * 8)) & 0xFFu;
-  uint32_t sx[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) sx[k] = (((sb >> (2 * k)) & 1u) << 15) | (((sb >> (2 * k + 1)) & 1u) << 31);
-  const int64_t tiles = (n_vec + (int64_t)kBlock * U - 1) / ((int64_t)kBlock * U);
-  bool first = true;
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int64_t v0 = tile * ((int64_t)kBlock * U) + threadIdx.x;
-    u32x4 raw[U];
-    bool live[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      int64_t v = v0 + u * kBlock;
-      live[u] = v < n_vec;
-      u32x4 w = {0, 0, 0, 0};
-      if (live[u]) {
-        if constexpr (sizeof(Tin) == 2) {
-          w = __builtin_nontemporal_load((const u32x4*)xv + v);
-          if (r.smooth) {   // h = half(float(x) * s)
-            const float* sp = r.smooth + (v % r.vec_per_row) * 8;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              w[k] = f2h(h2f(w[k] & 0xFFFFu) * sp[2 * k]) | (f2h(h2f(w[k] >> 16) * sp[2 * k + 1]) << 16);
-          }
-        } else {            // fp32 producer output: h = half(x * s)
-          u32x4 lo = __builtin_nontemporal_load((const u32x4*)xv + 2 * v);
-          u32x4 hi = __builtin_nontemporal_load((const u32x4*)xv + 2 * v + 1);
-          float f[8] = {u2f(lo[0]), u2f(lo[1]), u2f(lo[2]), u2f(lo[3]), u2f(hi[0]), u2f(hi[1]), u2f(hi[2]), u2f(hi[3])};
-          if (r.smooth) {
-            const float* sp = r.smooth + (v % r.vec_per_row) * 8;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) f[i] *= sp[i];
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) w[k] = f2h(f[2 * k]) | (f2h(f[2 * k + 1]) << 16);
-        }
-      }
-      raw[u] = w;
-    }
-    if (first) {
-      lut16_stage(lut, tab, a.shift);
-      __syncthreads();
-      first = false;
-    }
-    // the U vectors of a lane go through the stages together (stage-major: U independent dependency chains)
-    u32x4 ws[U], ys[U];
-    float tt[U][8];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ws[u][k] = raw[u][k] ^ sx[k];
-    fwht128_h_n<U>(ws, tt, U, lg);
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ys[u][k] = mul2_to_h2(tt[u][2 * k], tt[u][2 * k + 1], r.c_h);
-    uint32_t ms[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) ms[u] = vec_absmax16(ys[u]);
-    row_max_dpp16_n<U>(ms, U);
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const u32x4 y = ys[u];
-      if (EMIT && live[u]) __builtin_nontemporal_store(y, rot_out + v0 + u * kBlock);
-      RowScale16 s = row_scale16(ms[u], a.fpos.gmax, a.inv_gpos);
-      if constexpr (CODES) {
-        const uint32_t c = codes_vec16(y, lut, a.shift, s.inv, s.inv_lo);
-        if (live[u]) {
-          const int64_t v = v0 + u * kBlock;
-          ((uint32_t*)out)[v] = c;
-          if (lg == 0) r.code_scales[v >> 4] = (uint16_t)(s.s16x2 & 0xFFFFu);
-        }
-      } else {
-        u32x4 o = quant_vec16<false>(y, lut, a.shift, s.inv, s.inv_lo, s.s16x2, 0.f, 0.f, 0u);
-        if (live[u]) __builtin_nontemporal_store(o, out + v0 + u * kBlock);
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------
 // F1, complete form: the whole producer of tr/basic_var.py:263 / :266 in one launch
 //     h  = half( ((LN(x) * half(scale+1)) + shift) * s )      LN without affine, eps, fp32 math
@@ -1422,26 +1257,22 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
   return v;
 }
 
-// One WAVEFRONT per token row (64 lanes x MAXC vectors of 8 channels, C <= 64*8*MAXC): no LDS
-// traffic and no workgroup barrier after the table is staged; the modulation vectors of the
-// row are requested together with x so that their latency hides behind the two reductions.
-template <int LANES>
+// the sum over the workgroup, which owns the row
 __device__ __forceinline__ float row_sum_f32(float v, float* sh) {
   v = wave_sum_f32(v);
-  if constexpr (LANES == 64) {
-    return v;
-  } else {   // the whole workgroup owns the row
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = sh[0];
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = sh[0];
 #pragma unroll
-    for (int i = 1; i < kBlock / 64; ++i) r += sh[i];
-    return r;
-  }
+  for (int i = 1; i < kBlock / 64; ++i) r += sh[i];
+  return r;
 }
 
-template <typename Tin, typename Tmod, int LANES, int MAXC, bool CODES = false, bool TOKEN = false>
+// Rows of 2688 .. 4096 channels (the adaLN producer of fpq_adaln.h keeps a row inside one wavefront: C <= 2560): the
+// workgroup's 256 lanes x 2 vectors of 8 channels; the modulation vectors of the row are requested together with x so
+// that their latency hides behind the two reductions.
+template <typename Tin, typename Tmod, bool CODES>
 __global__ __launch_bounds__(kBlock) void adaln_rotate_quant16_kernel(const void* __restrict__ xv,
                                                                      u32x4* __restrict__ out, u32x4* __restrict__ h_out,
                                                                      u32x4* __restrict__ y_out, int64_t rows,
@@ -1449,6 +1280,7 @@ __global__ __launch_bounds__(kBlock) void adaln_rotate_quant16_kernel(const void
   __shared__ __attribute__((aligned(16))) uint16_t lut[kLutLdsEntries];   // static: a compile-time LDS address (a dynamic base is not folded into the ds_read offsets)
   __shared__ float shf[kBlock / 64];
   constexpr bool MOD16 = sizeof(Tmod) == 2;
+  constexpr int LANES = kBlock, MAXC = 2;
   const int lane = threadIdx.x & (LANES - 1);
   const int lg = lane & 15;
   const uint32_t sb = (r.sign[lg >> 2] >> ((lg & 3) * 8)) & 0xFFu;
@@ -1509,7 +1341,7 @@ __global__ __launch_bounds__(kBlock) void adaln_rotate_quant16_kernel(const void
 #pragma unroll
     for (int i = 0; i < 8; ++i) s1 += f[c][i];
   }
-  const float mean = row_sum_f32<LANES>(s1, shf) * inv_c;
+  const float mean = row_sum_f32(s1, shf) * inv_c;
   float s2 = 0.0f;
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) {
@@ -1522,12 +1354,8 @@ __global__ __launch_bounds__(kBlock) void adaln_rotate_quant16_kernel(const void
     }
     if (!live) s2 -= 8.0f * mean * mean;   // padding lanes hold zeros: take their (0 - mean)^2 back out
   }
-  const float var = row_sum_f32<LANES>(s2, shf) * inv_c;
+  const float var = row_sum_f32(s2, shf) * inv_c;
   const float rstd = 1.0f / __builtin_sqrtf(var + ad.eps);
-  u32x4 ys[TOKEN ? MAXC : 1];
-  uint32_t mrow = 0;
-  (void)ys;
-  (void)mrow;
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) {
     const int64_t v = (int64_t)c * LANES + lane;
@@ -1594,12 +1422,6 @@ __global__ __launch_bounds__(kBlock) void adaln_rotate_quant16_kernel(const void
 #pragma unroll
     for (int k = 0; k < 4; ++k) y[k] = mul2_to_h2(t[2 * k], t[2 * k + 1], r.c_h);
     if (y_out && live && row_live) __builtin_nontemporal_store(y, y_out + row * vpr + v);
-    if constexpr (TOKEN) {   // per-token scale: keep the rotated row, quantize after the row maximum is known
-      ys[c] = y;
-      const uint32_t mv = vec_absmax16(y);
-      mrow = mrow > mv ? mrow : mv;
-      continue;
-    }
     uint32_t m = row_max_dpp<16>(vec_absmax16(y));
     RowScale16 s = row_scale16(m, a.fpos.gmax, a.inv_gpos);
     if constexpr (CODES) {
@@ -1611,55 +1433,6 @@ __global__ __launch_bounds__(kBlock) void adaln_rotate_quant16_kernel(const void
     } else {
       u32x4 o = quant_vec16<false>(y, lut, a.shift, s.inv, s.inv_lo, s.s16x2, 0.f, 0.f, 0u);
       if (live && row_live) __builtin_nontemporal_store(o, out + row * vpr + v);
-    }
-  }
-  if constexpr (TOKEN) {
-    // fp6_quant_*_per_token_cuda on the rotated row (tr/quant_utils.py:503-534): one scale for the whole row
-    static_assert(!TOKEN || LANES == 64, "the per-token form keeps a row inside one wavefront");
-    mrow = row_max_dpp<64>(mrow);
-    const RowScale16 s = row_scale16(mrow, a.fpos.gmax, a.inv_gpos);
-    if (r.code_scales && lane == 0 && row_live) r.code_scales[row] = (uint16_t)(s.s16x2 & 0xFFFFu);
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      const int64_t v = (int64_t)c * LANES + lane;
-      if (v < vpr && row_live) {
-        if constexpr (CODES) {   // E4M3 bytes of the levels (fpq_gemm_fp8.h), 8 per vector
-          const uint32_t wk0 = ys[c][0], wk1 = ys[c][1], wk2 = ys[c][2], wk3 = ys[c][3];
-          uint32_t cb[8];
-          const uint32_t ws[4] = {wk0, wk1, wk2, wk3};
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const uint32_t wk = ws[k];
-            const uint32_t rb = div_pair16(wk, s.inv, s.inv_lo, s.inv, s.inv_lo);
-            const uint32_t u = pk_sub_u16(rb, pk_lshr_u16(rb, 15));
-            cb[2 * k] = lut[(u & 0xFFFFu) >> a.shift];
-            cb[2 * k + 1] = lut[u >> (16 + a.shift)];
-          }
-          if (r.code_bits == 6) {
-            // 8 six-bit codes = 48 bits per lane, rows packed densely: the four lanes of a quad own 24 contiguous
-            // bytes; lane q of the quad takes the (3 - q) upper 16-bit words of its own string and the q + 1 lower
-            // words of its right neighbour's, so that lanes 0..2 each store 8 aligned bytes (cols % 32 == 0: a quad
-            // is live or dead as a whole).
-            const uint64_t own = (uint64_t)(cb[0] | (cb[1] << 6) | (cb[2] << 12) | (cb[3] << 18)) |
-                                 ((uint64_t)(cb[4] | (cb[5] << 6) | (cb[6] << 12) | (cb[7] << 18)) << 24);
-            const uint32_t nlo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)own, 0xF9, 0xF, 0xF, false);   // quad_perm [1,2,3,3]
-            const uint32_t nhi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(own >> 32), 0xF9, 0xF, 0xF, false);
-            const uint64_t nb = ((uint64_t)nhi << 32) | nlo;
-            const int qp = lane & 3, sr = 16 * qp;
-            const uint64_t w = (own >> sr) | (nb << (48 - sr));
-            if (qp < 3) {
-              uint8_t* dst = (uint8_t*)out + row * (vpr * 6) + (int64_t)c * (LANES * 6) + 24 * (lane >> 2) + 8 * qp;
-              __builtin_nontemporal_store(u32x2{(uint32_t)w, (uint32_t)(w >> 32)}, (u32x2*)dst);
-            }
-          } else {
-            const u32x2 o2 = {cb[0] | (cb[1] << 8) | (cb[2] << 16) | (cb[3] << 24), cb[4] | (cb[5] << 8) | (cb[6] << 16) | (cb[7] << 24)};
-            __builtin_nontemporal_store(o2, (u32x2*)out + row * vpr + v);
-          }
-        } else {
-          u32x4 o = quant_vec16<false>(ys[c], lut, a.shift, s.inv, s.inv_lo, s.s16x2, 0.f, 0.f, 0u);
-          __builtin_nontemporal_store(o, out + row * vpr + v);
-        }
-      }
     }
   }
   }   // row loop

@@ -56,36 +56,13 @@ struct GemmEpi {
 typedef _Float16 fpq_h2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 fpq_h4_t __attribute__((ext_vector_type(4)));
 
-// The four 8-byte stores of a lane (rows t_first .. +3, outputs o .. o+3), or with -DFPQ_GEMM_WIDE_STORES two 16-byte ones: lanes
-// q and q ^ 1 hold neighbouring outputs of the same four rows; the even lane trades its rows 2, 3 for the odd lane's rows 0, 1
-// (one DPP quad_perm [1,0,3,2] per dword) and each then owns eight consecutive outputs of two rows.  outs % 8 == 0 and 4q % 8 == 0
-// on the even lane: both 16-byte pieces are inside the row or both outside; `out` is 16-byte aligned (checked on the host).
-#ifdef FPQ_GEMM_WIDE_STORES
-#define FPQ_GEMM_ROWS_STORE(y_, t_first_, tc_, o_, oc_)                                                             \
-  do {                                                                                                              \
-    const bool odd_ = (lane & 1) != 0;                                                                              \
-    _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_) {                                                              \
-      const u32x2 own_lo_ = __builtin_bit_cast(u32x2, (y_)[j_]), own_hi_ = __builtin_bit_cast(u32x2, (y_)[2 + j_]); \
-      const u32x2 send_ = odd_ ? own_lo_ : own_hi_;                                                                 \
-      u32x2 recv_;                                                                                                  \
-      recv_[0] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)send_[0], 0xB1, 0xF, 0xF, false);                    \
-      recv_[1] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)send_[1], 0xB1, 0xF, 0xF, false);                    \
-      const u32x2 first_ = odd_ ? recv_ : own_lo_, second_ = odd_ ? own_hi_ : recv_;                                \
-      const u32x4 w_ = u32x4{first_[0], first_[1], second_[0], second_[1]};                                         \
-      const int r_ = (odd_ ? 2 : 0) + j_;                                                                           \
-      const int trow_ = odd_ ? (tc_)[2 + j_] : (tc_)[j_];                                                           \
-      if ((t_first_) + r_ < T && (o_) < O)                                                                          \
-        __builtin_nontemporal_store(w_, (u32x4*)(out + (int64_t)trow_ * O + (oc_) - (odd_ ? 4 : 0)));               \
-    }                                                                                                               \
-  } while (0)
-#else
+// The four 8-byte stores of a lane (rows t_first .. +3, outputs o .. o+3)
 #define FPQ_GEMM_ROWS_STORE(y_, t_first_, tc_, o_, oc_)                                                             \
   do {                                                                                                              \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                                \
         if ((t_first_) + i_ < T && (o_) < O)                                                                        \
           __builtin_nontemporal_store(__builtin_bit_cast(u32x2, (y_)[i_]), (u32x2*)(out + (int64_t)(tc_)[i_] * O + (oc_))); \
   } while (0)
-#endif
 
 // (macros, not functions: the kernels carry different target attributes and a callee is only inlined into a kernel
 // with the same ones)
@@ -315,11 +292,7 @@ FPQ_NOPK __device__ __forceinline__ void load_scale_tiles(const _Float16* __rest
       for (int g0 = 0; g0 < G; g0 += GB) {
         _Float16 v[GB];
 #pragma unroll
-#ifdef FPQ_GEMM_SCALE_FAKE   // timing experiment only (wrong results): what the scale tiles' global loads cost the prologue
-        for (int i = 0; i < GB; ++i) v[i] = (_Float16)(1.0f + (float)(r & 1));
-#else
         for (int i = 0; i < GB; ++i) v[i] = src[g0 + i < G ? g0 + i : G - 1];
-#endif
 #pragma unroll
         for (int i = 0; i < GB; ++i)
           if (g0 + i < G) lsa[(g0 + i) * BM + r] = ok ? (float)v[i] : 0.0f;
@@ -331,11 +304,7 @@ FPQ_NOPK __device__ __forceinline__ void load_scale_tiles(const _Float16* __rest
       for (int g0 = 0; g0 < G; g0 += GB) {
         Tsw v[GB];
 #pragma unroll
-#ifdef FPQ_GEMM_SCALE_FAKE
-        for (int i = 0; i < GB; ++i) v[i] = (Tsw)(0.01f + 0.001f * (float)(c & 3));
-#else
         for (int i = 0; i < GB; ++i) v[i] = src[g0 + i < G ? g0 + i : G - 1];
-#endif
 #pragma unroll
         for (int i = 0; i < GB; ++i)
           if (g0 + i < G) lsw[(g0 + i) * BN + c] = ok ? (float)v[i] : 0.0f;
@@ -353,7 +322,7 @@ FPQ_NOPK __device__ __forceinline__ void load_scale_tiles(const _Float16* __rest
 //   * y = half(acc + bias) exactly as the plain epilogue rounds it (the Linear output the reference's GELU sees);
 //   * h = half(gelu(float(y))), gelu_tanh_fast below: within one fp16 ulp of torch's F.gelu(y, approximate="tanh") on every
 //     fp16 input, checked exhaustively (tests/test_gpu_fc1_fused.py; torch's formula in torch's operation order with the
-//     device library's tanh restated, gelu_tanh_like_torch, is bit-equal to torch and three times the instructions);
+//     device library's tanh restated, tools/probe/gelu_probe.hip, is bit-equal to torch and three times the instructions);
 //   * per token row the maxima of the negative and of the positive side over the lane's four outputs, the 16 lanes of the
 //     row (a DPP reduce-scatter) and the two wavefronts that share the group (LDS), one thread per row turns them into the two scales
 //     (row_scale16, dual_poison: the arithmetic of rows16_lut_subwave_kernel<DUAL>), and every lane quantizes its own
@@ -370,12 +339,7 @@ struct GemmFc1 {
   Lut16Tab tab;          // ... and the table itself, by value (as the stand-alone quantizers take it)
 };
 
-// (the GELU itself - gelu_tanh_fast, gelu_tanh_like_torch - lives in fpq_fast16.h: the stand-alone fused quantizer uses it too)
-#ifdef FPQ_FC1_GELU_TORCH_ORDER   // A/B builds: the bit-equal form
-#define FPQ_FC1_GELU gelu_tanh_like_torch
-#else
-#define FPQ_FC1_GELU gelu_tanh_fast
-#endif
+// (the GELU itself - gelu_tanh_fast - lives in fpq_fast16.h: the stand-alone fused quantizer uses it too)
 
 // One step of the maxima's reduce-scatter over the 16 lanes of a DPP row: rows r and r + N / 2 are paired, a lane keeps the
 // one its bit selects and hands the other to its partner (DPP control CTRL), taking the partner's in return: N rows in, N / 2
@@ -635,7 +599,7 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4
       for (int i = 0; i < 4; ++i) {
         float g[NT];
 #pragma unroll
-        for (int n = 0; n < NT; ++n) g[n] = FPQ_FC1_GELU((float)(_Float16)(acc[m][n][i] + b4[n]));
+        for (int n = 0; n < NT; ++n) g[n] = gelu_tanh_fast((float)(_Float16)(acc[m][n][i] + b4[n]));
         const uint32_t w0 = f2h2(g[0], g[1]), w1 = f2h2(g[2], g[3]);
         hw[m][i][0] = w0;
         hw[m][i][1] = w1;

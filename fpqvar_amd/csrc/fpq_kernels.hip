@@ -400,9 +400,6 @@ __global__ __launch_bounds__(kBlock) void rows_negrev_scalar_kernel(const T* __r
 
 #include "fpq_fast16.h"
 #include "fpq_rotate_mfma.h"
-#ifndef FPQ_ROT_BUTTERFLY_BUILD   // 1: the butterfly forms of the rotation everywhere (A/B builds)
-#define FPQ_ROT_BUTTERFLY_BUILD 0
-#endif
 #include "fpq_fast32.h"
 #include "fpq_adaln.h"
 #include "fpq_codes_mx.h"    // the operand-emitting quantizers of the matrix-core GEMMs (the GEMM kernels themselves,
@@ -1098,7 +1095,7 @@ static bool km_image_fits(int64_t rows, int64_t row_bytes) { return rows < (1ll 
 template <typename Tin>
 int launch_rotate_quant(const void* x, void* out, void* rot_out, int64_t rows, int64_t cols, const float* smooth,
                         const uint32_t sign[4], int table_id, hipStream_t st, uint16_t* code_scales = nullptr,
-                        bool km = false /* FP4 codes into a k-major image (include/fpq.h): the matrix-core form only */) {
+                        bool km = false /* FP4 codes into a k-major image (include/fpq.h) */) {
   const Lut16Host& h = lut16_host(table_id, table_id);
   if (!h.tab_valid) return FPQ_ERR_TABLE;
   const Lut16Tab& tab = code_scales ? lut16_mx_codes_e2m1() : h.tab;
@@ -1113,59 +1110,39 @@ int launch_rotate_quant(const void* x, void* out, void* rot_out, int64_t rows, i
   r.c_h = h2f(f2h(1.0f / __builtin_sqrtf(128.0f)));   // torch.tensor(128).sqrt() is float32; autocast makes Q fp16
   r.vec_per_row = cols / 8;
   const int64_t n_vec = rows * (cols / 8);
-  #ifndef FPQ_ROT_U
-#define FPQ_ROT_U 2
-#endif
-  constexpr int U = FPQ_ROT_U;
   const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
-  const int64_t tiles = (n_vec + (int64_t)kBlock * U - 1) / ((int64_t)kBlock * U);
-  const dim3 grid(grid_for(tiles, 1 << 20));
-  // values out: the transform on the matrix cores (fpq_rotate_mfma.h), one 32-group tile per wavefront
-  const bool butterfly = FPQ_ROT_BUTTERFLY_BUILD || fpq_flag(OPT_FPQ_ROT_BUTTERFLY);
-  if (!butterfly) {
-    // Every workgroup the same number of passes over its tiles.  With a bucket table to stage per workgroup the grid is
-    // two generations of the FPQ_ROT_WAVES workgroups a CU holds (3072: 84.2 us against 85.9 for one generation, round 2).
-    // The table-free E2M1 forms have next to no prologue and want SHORT workgroups - the grid drains faster at its end:
-    // values out, 3072 / 7680 / 12288 / 16384 workgroups: 83.2 / 82.2 / 82.1 / 80.3 us (one pass each at [65536 x 1920]);
-    // codes out: 57.3 / 52.8 / 53.0 / 53.6 us (profiles/r03_rotate_grid.txt).  FPQ_ROT_WGS overrides.
-    const bool hw4 = table_id == FPQ_E2M1 && !fpq_flag(OPT_FPQ_NO_HW4);   // E2M1 values or FP4 operands: levels / codes from the conversion hardware
-    const int64_t per_wg = (int64_t)(kBlock / 64) * kRqTileVec;
-    const int64_t wg_tiles = (n_vec + per_wg - 1) / per_wg;
-    const int64_t resident_env = fpq_opt(OPT_FPQ_ROT_WGS, 0);
-    // (with a smoothing vector every workgroup stages it - 7.5 KiB at C = 1920 - so a few passes each: 7680 / 2560)
-    const int64_t resident = resident_env > 0 ? resident_env : !hw4 ? 2 * 256ll * FPQ_ROT_WAVES
-                             : smooth ? (code_scales ? 2560 : 7680) : code_scales ? 8192 : 16384;
-    const int64_t passes = (wg_tiles + resident - 1) / resident;
-    const dim3 mgrid((unsigned)((wg_tiles + passes - 1) / passes));
+  // The transform on the matrix cores (fpq_rotate_mfma.h), one 32-group tile per wavefront.
+  // Every workgroup the same number of passes over its tiles.  With a bucket table to stage per workgroup the grid is
+  // two generations of the FPQ_ROT_WAVES workgroups a CU holds (3072: 84.2 us against 85.9 for one generation, round 2).
+  // The table-free E2M1 forms have next to no prologue and want SHORT workgroups - the grid drains faster at its end:
+  // values out, 3072 / 7680 / 12288 / 16384 workgroups: 83.2 / 82.2 / 82.1 / 80.3 us (one pass each at [65536 x 1920]);
+  // codes out: 57.3 / 52.8 / 53.0 / 53.6 us (profiles/r03_rotate_grid.txt).  FPQ_ROT_WGS overrides.
+  const bool hw4 = table_id == FPQ_E2M1 && !fpq_flag(OPT_FPQ_NO_HW4);   // E2M1 values or FP4 operands: levels / codes from the conversion hardware
+  const int64_t per_wg = (int64_t)(kBlock / 64) * kRqTileVec;
+  const int64_t wg_tiles = (n_vec + per_wg - 1) / per_wg;
+  const int64_t resident_env = fpq_opt(OPT_FPQ_ROT_WGS, 0);
+  // (with a smoothing vector every workgroup stages it - 7.5 KiB at C = 1920 - so a few passes each: 7680 / 2560)
+  const int64_t resident = resident_env > 0 ? resident_env : !hw4 ? 2 * 256ll * FPQ_ROT_WAVES
+                           : smooth ? (code_scales ? 2560 : 7680) : code_scales ? 8192 : 16384;
+  const int64_t passes = (wg_tiles + resident - 1) / resident;
+  const dim3 mgrid((unsigned)((wg_tiles + passes - 1) / passes));
 #define FPQ_ROT_MFMA(EMIT, SMOOTH, ...)                                                                             \
   hipLaunchKernelGGL((rotate_quant_mfma_kernel<Tin, EMIT, SMOOTH, ##__VA_ARGS__>), mgrid, dim3(kBlock), lds, st, x, \
                      (u32x4*)out, (u32x4*)rot_out, n_vec, r, h.args, tab)
-    if (code_scales && hw4) { if (smooth) FPQ_ROT_MFMA(false, true, true, true); else FPQ_ROT_MFMA(false, false, true, true); }
-    else if (code_scales) { if (smooth) FPQ_ROT_MFMA(false, true, true); else FPQ_ROT_MFMA(false, false, true); }
-    else if (rot_out && hw4) { if (smooth) FPQ_ROT_MFMA(true, true, false, true); else FPQ_ROT_MFMA(true, false, false, true); }
-    else if (rot_out) { if (smooth) FPQ_ROT_MFMA(true, true); else FPQ_ROT_MFMA(true, false); }
-    else if (hw4) { if (smooth) FPQ_ROT_MFMA(false, true, false, true); else FPQ_ROT_MFMA(false, false, false, true); }
-    else { if (smooth) FPQ_ROT_MFMA(false, true); else FPQ_ROT_MFMA(false, false); }
+  if (code_scales && hw4) { if (smooth) FPQ_ROT_MFMA(false, true, true, true); else FPQ_ROT_MFMA(false, false, true, true); }
+  else if (code_scales) { if (smooth) FPQ_ROT_MFMA(false, true, true); else FPQ_ROT_MFMA(false, false, true); }
+  else if (rot_out && hw4) { if (smooth) FPQ_ROT_MFMA(true, true, false, true); else FPQ_ROT_MFMA(true, false, false, true); }
+  else if (rot_out) { if (smooth) FPQ_ROT_MFMA(true, true); else FPQ_ROT_MFMA(true, false); }
+  else if (hw4) { if (smooth) FPQ_ROT_MFMA(false, true, false, true); else FPQ_ROT_MFMA(false, false, false, true); }
+  else { if (smooth) FPQ_ROT_MFMA(false, true); else FPQ_ROT_MFMA(false, false); }
 #undef FPQ_ROT_MFMA
-    return check_launch();
-  }
-  if (km) return FPQ_ERR_SHAPE;   // the butterfly forms (a build / experiment switch) write row-major codes only
-  if (code_scales)
-    hipLaunchKernelGGL((rotate_quant16_kernel<Tin, false, U, true>), grid, dim3(kBlock), lds, st, x, (u32x4*)out,
-                       (u32x4*)nullptr, n_vec, r, h.args, tab);
-  else if (rot_out)
-    hipLaunchKernelGGL((rotate_quant16_kernel<Tin, true, U>), grid, dim3(kBlock), lds, st, x, (u32x4*)out,
-                       (u32x4*)rot_out, n_vec, r, h.args, tab);
-  else
-    hipLaunchKernelGGL((rotate_quant16_kernel<Tin, false, U>), grid, dim3(kBlock), lds, st, x, (u32x4*)out,
-                       (u32x4*)nullptr, n_vec, r, h.args, tab);
   return check_launch();
 }
 
 template <typename Tin, typename Tmod>
 int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out, int64_t rows, int64_t cols,
                               const AdaLnArgs& ad, const float* smooth, const uint32_t sign[4], int table_id,
-                              hipStream_t st, int lanes_per_row, uint16_t* code_scales = nullptr,
+                              hipStream_t st, uint16_t* code_scales = nullptr,
                               int token_mode = 0 /*1: per-token values, 2: per-token E4M3 codes, 3: per-token packed 6-bit codes*/,
                               const Lut16Tab* token_code_tab = nullptr,
                               bool km = false /* FP4 / 6-bit codes into a k-major image (include/fpq.h): adaln_mfma_kernel only */) {
@@ -1180,9 +1157,7 @@ int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out
   if (km) {
     const bool fp4_codes = code_scales && !token_mode;
     if (!(fp4_codes || token_mode == 3) || !km_image_fits(rows, token_mode == 3 ? cols / 4 * 3 : cols / 2)) return FPQ_ERR_SHAPE;
-    // the forms that write row-major codes only: rows beyond one wavefront, the first-generation kernel, the butterfly build
-    if (lanes_per_row != 64 || cols / 8 > 64 * 5 || fpq_flag(OPT_FPQ_ADALN_V1) || FPQ_ROT_BUTTERFLY_BUILD || fpq_flag(OPT_FPQ_ROT_BUTTERFLY))
-      return FPQ_ERR_SHAPE;
+    if (cols / 8 > 64 * 5) return FPQ_ERR_SHAPE;   // rows beyond one wavefront: the first generation writes row-major codes only
   }
   r.smooth = smooth;
   for (int i = 0; i < 4; ++i) r.sign[i] = sign[i];
@@ -1190,13 +1165,12 @@ int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out
   r.vec_per_row = cols / 8;
   const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
   {
-    // second generation (fpq_adaln.h): fp16 or fp32 rows of up to 2560 channels, one batch entry per workgroup
+    // fpq_adaln.h: fp16 or fp32 rows of up to 2560 channels, one batch entry per workgroup
     constexpr bool X32 = sizeof(Tin) == 4;
-    if (lanes_per_row == 64 && r.vec_per_row <= 64 * 5 && !fpq_flag(OPT_FPQ_ADALN_V1)) {
+    if (r.vec_per_row <= 64 * 5) {
       if (h.args.shift < 6) return FPQ_ERR_TABLE;   // symmetric tables only (<= 2 x 512 buckets)
       const int64_t L = ad.rows_per_batch;
       const int64_t n_batches = (rows + L - 1) / L;
-      const bool adaln_butterfly = FPQ_ROT_BUTTERFLY_BUILD || fpq_flag(OPT_FPQ_ROT_BUTTERFLY);
       const bool rows_env = fpq_opt_set(OPT_FPQ_ADALN_ROWS);
       // Large launches: chunks of 16 rows (4 per wavefront) amortise the staging of the modulation; small launches (the
       // early scale steps of a generation: 100 .. 3600 rows) are latency-bound and want every CU busy: one row per wavefront
@@ -1211,10 +1185,10 @@ int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out
       // prologue's instructions per row count: 73.3 -> 70.5 us for codes, 89.7 -> 87.1 for E4M3 bytes, 96.2 -> 93.4 for
       // per-token E2M3 values; profiles/r03_adaln_partition.txt)
       const bool issue_bound = !X32 && (code_scales != nullptr || token_mode != 0 || table_id != FPQ_E2M1);
-      int rows_per_wg = rows_env ? fpq_opt(OPT_FPQ_ADALN_ROWS, 0) : (rows >= 8192 ? (adaln_butterfly && rows >= 32768 ? 16 : issue_bound && rows >= 32768 ? 12 : 8) : 4);
+      int rows_per_wg = rows_env ? fpq_opt(OPT_FPQ_ADALN_ROWS, 0) : (rows >= 8192 ? (issue_bound && rows >= 32768 ? 12 : 8) : 4);
       if (rows_per_wg < 1) rows_per_wg = 1;
       // rows of exactly 8 groups (C = 1024): two rows per tile (fpq_adaln.h, PAIR2) - workgroups of an even number of rows
-      const bool pair2 = !adaln_butterfly && !X32 && r.vec_per_row == 128 && token_mode == 0 && !h_out && !y_out &&
+      const bool pair2 = !X32 && r.vec_per_row == 128 && token_mode == 0 && !h_out && !y_out &&
                          !fpq_flag(OPT_FPQ_ADALN_NO_PAIR2);
       if (pair2) rows_per_wg = rows_env ? ((rows_per_wg + 1) & ~1) : (rows >= 8192 ? 16 : 8);
       const int64_t per_batch = (L + rows_per_wg - 1) / rows_per_wg;
@@ -1222,7 +1196,7 @@ int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out
       AdalnTiers tiers = {};
       const int tail_rows = fpq_opt(OPT_FPQ_ADALN_TAIL, 0);
       int64_t nb2 = 0, nb1 = 0;
-      if (!adaln_butterfly && tail_rows > 0 && rows_per_wg > 4) {
+      if (tail_rows > 0 && rows_per_wg > 4) {
         nb2 = (tail_rows + L - 1) / L;                                   // batch entries cut into chunks of 4 rows
         if (rows_per_wg > 8) nb1 = (tail_rows + L - 1) / L;              // ... of 8 rows
         if (nb2 > n_batches) nb2 = n_batches;
@@ -1243,7 +1217,6 @@ int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out
       }
       const int64_t n_wg3 = (int64_t)tiers.batches[0] * tiers.per_batch[0] + nb1 * tiers.per_batch[1] + nb2 * tiers.per_batch[2];
       if (n_wg3 > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
-      const dim3 g2((unsigned)(n_batches * per_batch));         // second generation (butterfly form): flat grid of equal chunks
       const dim3 g3((unsigned)n_wg3);
       const size_t lds2 = 0;   // table, modulation planes and images live in static LDS
       // E2M1 values per group: levels from the FP4 conversion hardware, no table (fpq_adaln.h)
@@ -1256,52 +1229,46 @@ int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out
                      (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab, tiers)
 #define FPQ_ADALN2K(M, CODES, EMIT, TOKEN)                                                                             \
   do {                                                                                                                 \
-    if (!adaln_butterfly) {                                                                                            \
-      if constexpr ((M == 4 || M == 5) && !(CODES) && !(EMIT)) {   /* E2M3 / E3M2 values, rows of 13 .. 20 groups: hardware levels */ \
-        if (hw6 == 1) {                                                                                                \
-          hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 1>), g3,    \
-                             dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,       \
-                             rows, ad, r, h.args, tab, tiers);                                                         \
-          break;                                                                                                       \
-        }                                                                                                              \
-        if (hw6 == 2) {                                                                                                \
-          hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 2>), g3,    \
-                             dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,       \
-                             rows, ad, r, h.args, tab, tiers);                                                         \
-          break;                                                                                                       \
-        }                                                                                                              \
+    if constexpr ((M == 4 || M == 5) && !(CODES) && !(EMIT)) {   /* E2M3 / E3M2 values, rows of 13 .. 20 groups: hardware levels */ \
+      if (hw6 == 1) {                                                                                                  \
+        hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 1>), g3,      \
+                           dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,         \
+                           rows, ad, r, h.args, tab, tiers);                                                           \
+        break;                                                                                                         \
       }                                                                                                                \
-      if constexpr (M == 2 && !X32 && !(EMIT) && !(TOKEN)) {                                                           \
-        if (pair2) {                                                                                                   \
-          if (hw4)                                                                                                     \
-            hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, 4, CODES, false, false, false, true, false, 4, true>), g3,     \
-                               dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,     \
-                               rows, ad, r, h.args, tab, tiers);                                                       \
-          else                                                                                                         \
-            hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, 4, CODES, false, false, false, false, false, 4, true>), g3,    \
-                               dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,     \
-                               rows, ad, r, h.args, tab, tiers);                                                       \
-          break;                                                                                                       \
-        }                                                                                                              \
+      if (hw6 == 2) {                                                                                                  \
+        hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 2>), g3,      \
+                           dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,         \
+                           rows, ad, r, h.args, tab, tiers);                                                           \
+        break;                                                                                                         \
       }                                                                                                                \
-      if constexpr (!(TOKEN)) {                                                                                        \
-        if constexpr (M == 4 && !X32 && !(EMIT) && !(CODES)) {                                                                     \
-          if (hw4 && tight_ok && r.vec_per_row == 240) {   /* VAR-d30: 31 KiB of LDS, five workgroups per CU */        \
-            FPQ_ADALN3(M, CODES, EMIT, TOKEN, true, true);                                                             \
-            break;                                                                                                     \
-          }                                                                                                            \
-        }                                                                                                              \
-        if (hw4) {                                                                                                     \
-          FPQ_ADALN3(M, CODES, EMIT, TOKEN, true, false);                                                              \
-          break;                                                                                                       \
-        }                                                                                                              \
-      }                                                                                                                \
-      FPQ_ADALN3(M, CODES, EMIT, TOKEN, false, false);                                                                 \
-      break;                                                                                                           \
     }                                                                                                                  \
-    hipLaunchKernelGGL((adaln_rq16_kernel<Tmod, M, CODES, EMIT, TOKEN, X32>), g2, dim3(kBlock), lds2, st,              \
-                       (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab,           \
-                       rows_per_wg, (int)per_batch);                                                                   \
+    if constexpr (M == 2 && !X32 && !(EMIT) && !(TOKEN)) {                                                             \
+      if (pair2) {                                                                                                     \
+        if (hw4)                                                                                                       \
+          hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, 4, CODES, false, false, false, true, false, 4, true>), g3,       \
+                             dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,       \
+                             rows, ad, r, h.args, tab, tiers);                                                         \
+        else                                                                                                           \
+          hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, 4, CODES, false, false, false, false, false, 4, true>), g3,      \
+                             dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,       \
+                             rows, ad, r, h.args, tab, tiers);                                                         \
+        break;                                                                                                         \
+      }                                                                                                                \
+    }                                                                                                                  \
+    if constexpr (!(TOKEN)) {                                                                                          \
+      if constexpr (M == 4 && !X32 && !(EMIT) && !(CODES)) {                                                           \
+        if (hw4 && tight_ok && r.vec_per_row == 240) {   /* VAR-d30: 31 KiB of LDS, five workgroups per CU */          \
+          FPQ_ADALN3(M, CODES, EMIT, TOKEN, true, true);                                                               \
+          break;                                                                                                       \
+        }                                                                                                              \
+      }                                                                                                                \
+      if (hw4) {                                                                                                       \
+        FPQ_ADALN3(M, CODES, EMIT, TOKEN, true, false);                                                                \
+        break;                                                                                                         \
+      }                                                                                                                \
+    }                                                                                                                  \
+    FPQ_ADALN3(M, CODES, EMIT, TOKEN, false, false);                                                                   \
   } while (0)
 #ifdef FPQ_ADALN_STAMPS
 #define FPQ_ADALN_EMIT (h_out != nullptr)   /* diagnostic build: y_out alone is the stamp buffer */
@@ -1331,46 +1298,14 @@ int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out
       return check_launch();
     }
   }
-  const int64_t rows_per_wg = kBlock / lanes_per_row;
-  int64_t g64 = (rows + rows_per_wg - 1) / rows_per_wg;
-  const int64_t cap = fpq_opt(OPT_FPQ_ADALN_GRID, 8192);   // every workgroup stages the table once, then walks rows
-  if (g64 > cap) g64 = cap;
-  const dim3 g((unsigned)g64);
-  const int maxc = (int)((r.vec_per_row + lanes_per_row - 1) / lanes_per_row);
-#define FPQ_ADALN(L, M)                                                                                              \
-  do {                                                                                                               \
-    if (code_scales)                                                                                                 \
-      hipLaunchKernelGGL((adaln_rotate_quant16_kernel<Tin, Tmod, L, M, true>), g, dim3(kBlock), lds, st, x,         \
-                         (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab);                       \
-    else                                                                                                             \
-      hipLaunchKernelGGL((adaln_rotate_quant16_kernel<Tin, Tmod, L, M>), g, dim3(kBlock), lds, st, x, (u32x4*)out,  \
-                         (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab);                                    \
-  } while (0)
-  if (token_mode) {   // one wavefront per row only (C <= 2560)
-#define FPQ_ADALN_TOK(M)                                                                                             \
-  do {                                                                                                               \
-    if (token_mode >= 2)                                                                                             \
-      hipLaunchKernelGGL((adaln_rotate_quant16_kernel<Tin, Tmod, 64, M, true, true>), g, dim3(kBlock), lds, st, x,  \
-                         (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab);                       \
-    else                                                                                                             \
-      hipLaunchKernelGGL((adaln_rotate_quant16_kernel<Tin, Tmod, 64, M, false, true>), g, dim3(kBlock), lds, st, x, \
-                         (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab);                       \
-  } while (0)
-    if (lanes_per_row != 64 || maxc > 5) return FPQ_ERR_SHAPE;
-    if (maxc <= 4) FPQ_ADALN_TOK(4);
-    else FPQ_ADALN_TOK(5);
-#undef FPQ_ADALN_TOK
-    return check_launch();
-  }
-  if (lanes_per_row == 256) {
-    if (maxc <= 1) FPQ_ADALN(256, 1);
-    else FPQ_ADALN(256, 2);
-  } else {
-    if (maxc <= 4) FPQ_ADALN(64, 4);
-    else if (maxc <= 5) FPQ_ADALN(64, 5);
-    else FPQ_ADALN(64, 8);
-  }
-#undef FPQ_ADALN
+  // rows beyond one wavefront (2560 < C <= 4096, per group only): the first generation, one workgroup per row
+  const dim3 g((unsigned)(rows < 8192 ? rows : 8192));   // every workgroup stages the table once, then walks rows
+  if (code_scales)
+    hipLaunchKernelGGL((adaln_rotate_quant16_kernel<Tin, Tmod, true>), g, dim3(kBlock), lds, st, x, (u32x4*)out,
+                       (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab);
+  else
+    hipLaunchKernelGGL((adaln_rotate_quant16_kernel<Tin, Tmod, false>), g, dim3(kBlock), lds, st, x, (u32x4*)out,
+                       (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab);
   return check_launch();
 }
 
@@ -1901,8 +1836,7 @@ int fpq_quant_rows_dual(const void* x, void* out, int64_t rows, int64_t cols, in
       rc = launch_fast16<true>(x, out, rows, cols, neg_table, pos_table, st, 1 << 20, flag);
     else {
       const int cap = fpq_opt(OPT_FPQ_BIGTAB_CAP, 16384);   // measured on [65536 x 7680]: 4096 -> 366 us, 16384 -> 348 us, full grid -> 367 us
-      if (fpq_opt(OPT_FPQ_BIGTAB_U, 4) == 8) rc = launch_fast16<true, 8>(x, out, rows, cols, neg_table, pos_table, st, cap, flag);
-      else rc = launch_fast16<true, 4>(x, out, rows, cols, neg_table, pos_table, st, cap, flag);
+      rc = launch_fast16<true, 4>(x, out, rows, cols, neg_table, pos_table, st, cap, flag);
     }
   } else if (!clip_absmax && fast16_block_eligible(x, out, cols, in_dtype, out_dtype)) {
     rc = launch_fast16_block<true>(x, out, rows, cols, neg_table, pos_table, st, flag);
@@ -2032,13 +1966,10 @@ static int adaln_rotate_quant_impl(const void* x, void* out, void* h_out, void* 
   ad.cols = cols;
   // One wavefront per row while the row fits 5 vectors per lane (C <= 2560: no barrier in the row
   // loop; measured 0.180 ms vs 0.199 ms per [65500 x 1920] on MI355X), one workgroup per row beyond.
-  // FPQ_ADALN_LANES / FPQ_ADALN_GRID override the choice for experiments.
-  const int lanes = (fpq_opt_set(OPT_FPQ_ADALN_LANES) && !token_mode) ? fpq_opt(OPT_FPQ_ADALN_LANES, 64) : (cols / 8 <= 64 * 5 ? 64 : 256);
-  const int lpr = (lanes == 64) ? 64 : 256;
-  if (token_mode && lpr != 64) return FPQ_ERR_SHAPE;   // the per-token form keeps a row inside one wavefront: C <= 2560
+  if (token_mode && cols / 8 > 64 * 5) return FPQ_ERR_SHAPE;   // the per-token form keeps a row inside one wavefront: C <= 2560
   hipStream_t st = (hipStream_t)stream;
 #define FPQ_GO(TI, TM) return launch_adaln_rotate_quant<TI, TM>(x, out, h_out, rotated_out, rows, cols, ad, smooth, \
-                                                              sign_mask_host, table_id, st, lpr, (uint16_t*)code_scales, \
+                                                              sign_mask_host, table_id, st, (uint16_t*)code_scales, \
                                                               token_mode, token_code_tab, km)
   if (in_dtype == FPQ_F16 && mod_dtype == FPQ_F16) FPQ_GO(_Float16, _Float16);
   if (in_dtype == FPQ_F16) FPQ_GO(_Float16, float);

@@ -422,13 +422,9 @@ __global__ __launch_bounds__(kBlock, SMOOTH ? FPQ_ROT_WAVES - 1 : FPQ_ROT_WAVES)
     if (smooth_in_lds)
       for (uint32_t i = threadIdx.x; i < vpr32 * 2u; i += kBlock) ((u32x4*)smooth_s)[i] = ((const u32x4*)r.smooth)[i];
   }
-#ifndef FPQ_ROT_PREFETCH16
-#define FPQ_ROT_PREFETCH16 1
-#endif
-#ifndef FPQ_ROT_PREFETCH32   // fp32 input: 32 more registers take the kernel from 8 to 5 wavefronts per SIMD, measured 72 - 75 us against 64 - 65 without
-#define FPQ_ROT_PREFETCH32 0
-#endif
-  constexpr bool PREFETCH = (sizeof(Tin) == 2 ? FPQ_ROT_PREFETCH16 != 0 : FPQ_ROT_PREFETCH32 != 0) && !EMIT;   // the emitting form is for tests and calibration dumps
+  // fp16 input only (fp32 input: 32 more registers take the kernel from 8 to 5 wavefronts per SIMD, measured 72 - 75 us
+  // against 64 - 65 without); the emitting form is for tests and calibration dumps
+  constexpr bool PREFETCH = sizeof(Tin) == 2 && !EMIT;
   constexpr int VW = sizeof(Tin) == 2 ? 1 : 2;           // 16-byte words per input vector
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

@@ -5,7 +5,7 @@ The reference builds a dense block-diagonal Q (15 or 18 identical 128x128 blocks
 ``diag(D) . H128 / sqrt(128)``, D = +-1 drawn with ``torch.manual_seed(42)``) and
 multiplies activations by it with a dense fp16 GEMM on every forward
 (tr/basic_var.py:263,266).  Here Q exists only for the offline weight side and for
-tests; online, ``rotate_quant`` runs the 128-point butterfly inside the quant kernel.
+tests; online, ``rotate_quant`` runs the 128-point transform on the matrix cores inside the quant kernel.
 """
 from __future__ import annotations
 

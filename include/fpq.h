@@ -24,12 +24,14 @@
 extern "C" {
 #endif
 
-#define FPQ_VERSION 125 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
+#define FPQ_VERSION 126 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
                            0.1.3: + fpq_quant_rows_codes_segments, fpq_dequant_rows_codes_segments (round 3);
                            123: + fpq_build_tag (round 4);
                            124: + fpq_set_option, fpq_get_option, fpq_option_name, fpq_gemm_fp4_gelu_dual, fpq_gelu_quant_rows_dual (round 5);
                            125: + k-major operand images: fpq_codes_to_kmajor, fpq_scales_to_kmajor, fpq_gemm_fp4_mx_km, fpq_gemm_fp4_gelu_dual_km,
-                                fpq_gemm_fp6_rows_km, the *_km producers, fpq_gemm_fp4_mx_split (round 5) */
+                                fpq_gemm_fp6_rows_km, the *_km producers, fpq_gemm_fp4_mx_split (round 5);
+                           126: - the switches FPQ_ROT_BUTTERFLY, FPQ_ADALN_V1, FPQ_ADALN_LANES, FPQ_ADALN_GRID, FPQ_BIGTAB_U
+                                (the kernel forms they chose are retired) */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -69,8 +71,9 @@ const char* fpq_strerror(int status);
 const char* fpq_build_tag(void);
 
 /* Experiment switches - tests and the A/B tools only; a deployment never touches them.  Every switch is an int named
- * like the environment variable that initialises it ("FPQ_NO_HW4", "FPQ_GEMM_CFG", ...; fpq_option_name enumerates
- * them).  The environment is read ONCE, by the library's initialiser (a variable that is set and not empty: flags take
+ * like the environment variable that initialises it: the flags FPQ_NO_HW4, FPQ_NO_HW6, FPQ_NO_FAST32, FPQ_ADALN_NO_PAIR2,
+ * FPQ_ADALN_NO_TIGHT, FPQ_NO_WAVE_ROWS and the numbers FPQ_GEMM_CFG, FPQ_GEMM6_CFG, FPQ_GEMM8_CFG, FPQ_ROT_WGS,
+ * FPQ_ADALN_ROWS, FPQ_ADALN_TAIL, FPQ_BIGTAB_RPB, FPQ_BIGTAB_CAP (fpq_option_name enumerates them).  The environment is read ONCE, by the library's initialiser (a variable that is set and not empty: flags take
  * 1 unless the text is "0", numbers take atoi of the text); later changes of the environment are not seen.
  * fpq_set_option changes a switch for every later call in the process (value FPQ_OPTION_DEFAULT = back to the built-in
  * choice); it is a relaxed atomic store - call it between launches, not concurrently with them, if the outcome matters.

@@ -134,10 +134,14 @@ def test_option_table_is_the_only_reader_of_the_environment(lib):
     assert all(("GLOBAL__sub_I" in c or "FpqOptionInit" in c or c.startswith(".plt")) for c in callers), callers
 
 
-def test_options_roundtrip_and_env_is_read_once(lib, monkeypatch):
+def test_option_list_roundtrip_and_env_is_read_once(lib, monkeypatch):
+    """The switches are exactly the ones include/fpq.h lists, each round-trips through fpq_set_option, and the environment
+    is read once, at load."""
     from fpqvar_amd import _lib
     names = _lib.option_names()
-    assert "FPQ_NO_HW4" in names and "FPQ_GEMM_CFG" in names and len(names) == len(set(names)) >= 19
+    assert names == ["FPQ_NO_HW4", "FPQ_NO_HW6", "FPQ_NO_FAST32", "FPQ_ADALN_NO_PAIR2", "FPQ_ADALN_NO_TIGHT", "FPQ_NO_WAVE_ROWS",
+                     "FPQ_GEMM_CFG", "FPQ_GEMM6_CFG", "FPQ_GEMM8_CFG", "FPQ_ROT_WGS", "FPQ_ADALN_ROWS", "FPQ_ADALN_TAIL",
+                     "FPQ_BIGTAB_RPB", "FPQ_BIGTAB_CAP"], names
     assert lib.fpq_option_name(len(names)) is None and lib.fpq_option_name(-1) is None
     for n in names:
         before = _lib.get_option(n)

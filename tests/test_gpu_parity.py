@@ -829,43 +829,6 @@ def test_rotate_quant_tiles(dev, rows, cols, in_dtype):
     assert_bits_equal(o6, orc.per_group_kernel_sem(y.cpu(), "e2m3", 128, out_dtype=torch.float16), "e2m3 after rotate")
 
 
-def test_rotate_butterfly_switch(dev, tmp_path):
-    """FPQ_ROT_BUTTERFLY=1 (read once per process, hence a child process) selects the butterfly form of the transform in
-    both producers: same contract - quantization exact on the rotated values it produced - and rotated values that agree
-    with the matrix-core form up to the last bit of rare elements."""
-    import subprocess
-    import sys
-    from fpqvar_amd import rotation as rot
-    script = (
-        "import sys, torch\n"
-        "sys.path.insert(0, %r)\n"
-        "from fpqvar_amd import rotation as rot\n"
-        "d = torch.load(sys.argv[1])\n"
-        "dev = torch.device('cuda:0')\n"
-        "o, y = rot.rotate_quant(d['x'].to(dev), 'e2m1', return_rotated=True)\n"
-        "oa, ha, ya = rot.adaln_rotate_quant(d['xa'].to(dev), d['scale'].to(dev), d['shift'].to(dev), 'e2m1', return_intermediates=True)\n"
-        "torch.save({'o': o.cpu(), 'y': y.cpu(), 'oa': oa.cpu(), 'ha': ha.cpu(), 'ya': ya.cpu()}, sys.argv[2])\n"
-    ) % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    g = torch.Generator().manual_seed(77)
-    d = {"x": (torch.randn(65, 1920, generator=g) * torch.exp(0.5 * torch.randn(65, 1920, generator=g))).half(),
-         "xa": torch.randn(3, 21, 1920, generator=g).half(),
-         "scale": (torch.randn(3, 1, 1920, generator=g) * 0.3).half(), "shift": (torch.randn(3, 1, 1920, generator=g) * 0.3).half()}
-    fin, fout = str(tmp_path / "in.pt"), str(tmp_path / "out.pt")
-    torch.save(d, fin)
-    env = dict(os.environ, FPQ_ROT_BUTTERFLY="1")
-    subprocess.run([sys.executable, "-c", script, fin, fout], check=True, env=env, timeout=300)
-    b = torch.load(fout)
-    o, y = rot.rotate_quant(d["x"].to(dev), "e2m1", return_rotated=True)
-    oa, ha, ya = rot.adaln_rotate_quant(d["xa"].to(dev), d["scale"].to(dev), d["shift"].to(dev), "e2m1", return_intermediates=True)
-    assert_bits_equal(b["ha"], ha, "modulated rows do not depend on the form of the transform")
-    for name, yb, ym in (("rotate", b["y"], y.cpu()), ("adaln", b["ya"], ya.cpu())):
-        dd = _ulp_diff_f16(yb, ym)
-        assert int(dd.max()) <= 1 and float((dd > 0).float().mean()) < 1e-3, f"{name}: the two forms disagree"
-    assert_bits_equal(b["o"], orc.per_group_kernel_sem(b["y"], "e2m1", 128), "butterfly form: quant of rotated")
-    assert_bits_equal(b["oa"], orc.per_group_kernel_sem(b["ya"].reshape(-1, 1920), "e2m1", 128).view_as(b["oa"]), "butterfly adaLN: quant of rotated")
-    assert_bits_equal(o, orc.per_group_kernel_sem(y.cpu(), "e2m1", 128), "matrix-core form: quant of rotated")
-
-
 @pytest.mark.parametrize("C", (1920, 2304))
 @pytest.mark.parametrize("x_dtype", (torch.float16, torch.float32))
 @pytest.mark.parametrize("table", ("e2m3", "e3m2"))
@@ -1264,6 +1227,35 @@ def test_adaln_rotate_quant_widths(dev, C):
     tok = rot.adaln_rotate_quant_token(x, scale, shift, "e2m3", smooth=s)
     assert_bits_equal(tok, ops.quant_rows(y, "e2m3", C, torch.float16), "per-token quant of the rotated row")
     assert_bits_equal(tok, orc.per_token_kernel_sem(y.cpu(), "e2m3"), "per-token oracle")
+
+
+@pytest.mark.parametrize("mod_dtype", (torch.float16, torch.float32))
+@pytest.mark.parametrize("x_dtype", (torch.float16, torch.float32))
+@pytest.mark.parametrize("C", (2688, 4096))
+def test_adaln_rotate_quant_wide_rows(dev, C, x_dtype, mod_dtype):
+    """Rows of 21 .. 32 groups (2560 < C <= 4096: one workgroup per row, per group only), batch entries of a ragged length:
+    the modulated row equals torch's chain up to rounding; the transform there is the butterfly, so the rotated values
+    agree with the matrix-core form of rotate_quant up to the last bit of rare elements, and the values (E2M1 and a table
+    format) and the FP4 operands are the oracle's quantization of the rotated values produced, bit for bit."""
+    from fpqvar_amd import gemm, rotation as rot
+    g = torch.Generator().manual_seed(C + 7)
+    B, L = 5, 23
+    x = (torch.randn(B, L, C, generator=g) * torch.exp(0.4 * torch.randn(B, L, C, generator=g)) + 0.2).to(x_dtype).to(dev)
+    scale = (torch.randn(B, 1, C, generator=g) * 0.3).to(mod_dtype).to(dev)
+    shift = (torch.randn(B, 1, C, generator=g) * 0.3).to(mod_dtype).to(dev)
+    s = (torch.rand(C, generator=g) * 1.5 + 0.25).to(dev)
+    out, h, y = rot.adaln_rotate_quant(x, scale, shift, "e2m1", smooth=s, return_intermediates=True)
+    assert_bits_equal(rot.adaln_rotate_quant(x, scale, shift, "e2m1", smooth=s), out, "emit vs no-emit")
+    ln = torch.nn.functional.layer_norm(x.float(), (C,), eps=1e-6)
+    h_ref = (ln.mul(scale.add(1)) + shift).mul(s).half()
+    assert float((_ulp_diff_f16(h.cpu(), h_ref.cpu()) > 0).float().mean()) < 5e-3
+    dd = _ulp_diff_f16(y.cpu(), rot.rotate_quant(h, "e2m1", return_rotated=True)[1].cpu())
+    assert int(dd.max()) <= 1 and float((dd > 0).float().mean()) < 1e-3, "rotated: butterfly vs matrix cores"
+    assert_bits_equal(out, orc.per_group_kernel_sem(y.cpu(), "e2m1", 128), "quant of rotated")
+    tab = rot.adaln_rotate_quant(x, scale, shift, "e2m3", smooth=s)
+    assert_bits_equal(tab, orc.per_group_kernel_sem(y.cpu(), "e2m3", 128), "table format: quant of rotated")
+    codes, scales = rot.adaln_rotate_quant_mx(x, scale, shift, smooth=s)
+    assert_bits_equal(gemm.dequantize_mx(codes.view(B * L, -1), scales.view(B * L, -1)).half().view_as(out), out, "operands")
 
 
 @pytest.mark.parametrize("source", ("qkv_view", "separate", "unaligned"))

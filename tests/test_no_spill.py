@@ -16,7 +16,7 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 # the kernels of the hot path: quantizers, producers, KV step, code emitters
-HOT = re.compile(r"rows16_lut|groups32|rows32|rotate_quant_mfma|adaln_mfma|adaln_rq16|kv16_step|rows16_codes|codes128|decode128|gemm_fp4_glds|gemm_fp6_rows|gemm_fp8_rows")
+HOT = re.compile(r"rows16_lut|groups32|rows32|rotate_quant_mfma|adaln_mfma|kv16_step|rows16_codes|codes128|decode128|gemm_fp4_glds|gemm_fp6_rows|gemm_fp8_rows")
 
 
 def _tool(name):

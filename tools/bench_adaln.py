@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """adaln_rotate_quant at the d30 generation shape ([100 x 655 x 1920] fp16), rotating inputs, HIP-event timing.
-usage: bench_adaln.py [C=1920]   env FPQ_ADALN_V1=1: first-generation kernel, FPQ_ADALN_ROWS=n: rows per workgroup"""
+usage: bench_adaln.py [C=1920]   env FPQ_ADALN_ROWS=n: rows per workgroup"""
 import json
 import os
 import sys
@@ -39,6 +39,5 @@ for _ in range(3):
     torch.cuda.synchronize()
     best = min(best, e0.elapsed_time(e1) / 20)
 n = B * L * C
-print(json.dumps({"case": f"adaln_rotate_quant fp16 [{B}x{L}x{C}]", "v1": bool(os.environ.get("FPQ_ADALN_V1")),
-                  "rows_per_wg": os.environ.get("FPQ_ADALN_ROWS", "16"), "ms": round(best, 4),
+print(json.dumps({"case": f"adaln_rotate_quant fp16 [{B}x{L}x{C}]", "rows_per_wg": os.environ.get("FPQ_ADALN_ROWS", "16"), "ms": round(best, 4),
                   "GBps": round(n * 4 / best / 1e6, 1), "frac_of_8TBps": round(n * 4 / best / 1e6 / 8000, 3)}))
