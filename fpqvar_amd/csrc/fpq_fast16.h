@@ -715,6 +715,33 @@ struct KvStepArgs {
   int64_t new_vecs;
 };
 
+// job (a) of kv16_step_qkn_kernel (kv16_step_kernel's own, spelled out there): this workgroup's share of the previous step's rows
+// of one slab, quantized in place
+template <int LPR, int U>
+__device__ __forceinline__ void kv16_quant_job(u32x4* slab, const KvStepArgs& k, const Lut16Args& a, const Lut16Tab& tab, uint16_t* lut) {
+  u32x4* p = slab + k.q_first_vec;
+  const int64_t v0 = (int64_t)blockIdx.x * (kBlock * U) + threadIdx.x;
+  u32x4 raw[U];
+  bool live[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int64_t v = v0 + u * kBlock;
+    live[u] = v < k.q_vecs;     // q_vecs is a multiple of LPR: a row is live or dead as a whole
+    raw[u] = live[u] ? p[v] : u32x4{0, 0, 0, 0};
+  }
+  {
+    lut16_stage(lut, tab, a.shift);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint32_t m = row_max_dpp<LPR>(vec_absmax16(raw[u]));
+    const RowScale16 s = row_scale16(m, a.fpos.gmax, a.inv_gpos);
+    const u32x4 o = quant_vec16<false>(raw[u], lut, a.shift, s.inv, s.inv_lo, s.s16x2, 0.f, 0.f, 0u);
+    if (live[u]) p[v0 + u * kBlock] = o;
+  }
+}
+
 template <int LPR, int U>
 __global__ __launch_bounds__(kBlock) void kv16_step_kernel(KvStepArgs k, Lut16Args a, Lut16Tab tab) {
   __shared__ __attribute__((aligned(16))) uint16_t lut[kLutLdsEntries];   // static: a compile-time LDS address (a dynamic base is not folded into the ds_read offsets)
@@ -755,6 +782,94 @@ __global__ __launch_bounds__(kBlock) void kv16_step_kernel(KvStepArgs k, Lut16Ar
         d[v] = *(const u32x4*)(s + l * k.src_token_pitch + c * 8);
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// KV-cache step of an attention block with attn_l2_norm (tr/basic_var.py:173-183; include/fpq.h fpq_kv_cache_step_qknorm):
+// kv16_step_kernel's two jobs, the copy-in now
+//     y = float(x16) + b32                        (the fp32 bias cat(q_bias, 0, v_bias) promotes the fp16 Linear output)
+//     k = half(y / max(||y||_2, 1e-12))           per (token, head) over the head's 64 channels: F.normalize(k, dim=-1)
+//     v = half(y)
+// and a third job (blockIdx.z == 2) that writes q_out = half(y / max(||y||_2, 1e-12) * s_h), contiguous [batch, n, row_elems]:
+// the whole qkv-to-cache work of a block-step in one launch.  Lanes: consecutive threads own consecutive 16-byte vectors of a
+// token row, so the 64 channels of a head are the 8 vectors of 8 adjacent, 8-aligned lanes (kBlock and row_vec are multiples
+// of 8) - the sum of squares is three DPP steps, every lane of the head ends with the same bits.  A lane past the end reads
+// zeros: a head is live or dead as a whole (new_vecs is a multiple of row_vec).  The norm: a real square root, one real
+// division per head (1 / n), and per element q = y * (1/n) with one residual step, q + (y - q n) (1/n) - the correctly
+// rounded quotient but for rare ties, at three instructions instead of a division each.
+// ---------------------------------------------------------------------------------
+struct KvStepQkn {
+  const uint16_t* q;       // new q: the pitches of new k
+  u32x4* q_out;            // [batch, n_new, row_vec] vectors
+  const float* q_scale;    // [row_elems / 64]: exp(min(scale_mul_1H11, log 100))
+  const float* bias;       // [3 * row_elems] (q, k, v) or nullptr
+  int row_elems;
+};
+
+// sum over the 8 lanes of an 8-aligned lane group (the same bits in every lane: each step adds a value and its mirror image)
+__device__ __forceinline__ float head_sum8(float v) {
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));   // row_half_mirror
+  return v;
+}
+
+template <int LPR, int U>
+__global__ __launch_bounds__(kBlock) void kv16_step_qkn_kernel(KvStepArgs k, KvStepQkn qn, Lut16Args a, Lut16Tab tab) {
+  __shared__ __attribute__((aligned(16))) uint16_t lut[kLutLdsEntries];
+  const int z = blockIdx.z, b = blockIdx.y;   // z: 0 k, 1 v (cache slabs), 2 q
+  if ((int)blockIdx.x < k.q_tiles) {
+    if (z == 2) return;
+    kv16_quant_job<LPR, U>(k.cache + ((int64_t)z * k.batch + b) * k.slab_vec, k, a, tab, lut);
+    return;
+  }
+  const uint16_t* s = (z == 2 ? qn.q : k.src[z]) + (int64_t)b * k.src_batch_pitch;
+  u32x4* d = z == 2 ? qn.q_out + (int64_t)b * k.new_vecs : k.cache + ((int64_t)z * k.batch + b) * k.slab_vec + k.new_first_vec;
+  const float* bias = qn.bias ? qn.bias + (int64_t)(z == 2 ? 0 : z + 1) * qn.row_elems : nullptr;   // bias order: q, k, v
+  const int64_t v0 = (int64_t)((int)blockIdx.x - k.q_tiles) * (kBlock * U) + threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int64_t v = v0 + u * kBlock;
+    const bool live = v < k.new_vecs;
+    const int64_t l = live ? v / k.row_vec : 0;
+    const int c = live ? (int)(v - l * k.row_vec) : 0;
+    const u32x4 raw = live ? *(const u32x4*)(s + l * k.src_token_pitch + c * 8) : u32x4{0, 0, 0, 0};
+    float y[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      y[2 * j] = h2f(raw[j] & 0xFFFFu);
+      y[2 * j + 1] = h2f(raw[j] >> 16);
+    }
+    if (bias) {
+      typedef float f4_t __attribute__((ext_vector_type(4)));
+      const f4_t b0 = *(const f4_t*)(bias + c * 8), b1 = *(const f4_t*)(bias + c * 8 + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        y[j] += b0[j];
+        y[4 + j] += b1[j];
+      }
+    }
+    if (z != 1) {   // uniform
+      float ss = y[0] * y[0];
+#pragma unroll
+      for (int j = 1; j < 8; ++j) ss = __builtin_fmaf(y[j], y[j], ss);
+      ss = head_sum8(ss);
+      float nrm = __builtin_sqrtf(ss);
+      nrm = nrm < 1e-12f ? 1e-12f : nrm;   // clamp_min(eps) (a NaN stays a NaN)
+      const float inv = 1.0f / nrm;
+      const float hs = z == 2 ? qn.q_scale[c >> 3] : 1.0f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float q = y[j] * inv;
+        q = __builtin_fmaf(__builtin_fmaf(-q, nrm, y[j]), inv, q);
+        y[j] = z == 2 ? q * hs : q;
+      }
+    }
+    u32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = f2h2(y[2 * j], y[2 * j + 1]);
+    if (live) d[v] = o;
   }
 }
 

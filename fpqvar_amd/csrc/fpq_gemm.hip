@@ -140,7 +140,8 @@ static int gemm_epilogue(const fpq_gemm_epilogue_t* ep, int64_t tokens, GemmEpi*
 // km: both operands are k-major images (include/fpq.h); only the LDS-DMA kernels read them
 static int gemm_fp4_mx_impl(const uint8_t* a_codes, const void* a_scales, const uint8_t* w_codes, const void* w_scales,
                             int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
-                            const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream, const fpq_gemm_split_t* split = nullptr) {
+                            const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream, const fpq_gemm_split_t* split = nullptr,
+                            const GemmQkNorm* qkn = nullptr) {
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   GemmEpi epi;
   if (int rc = gemm_epilogue(epilogue, tokens, &epi)) return rc;
@@ -213,7 +214,15 @@ static int gemm_fp4_mx_impl(const uint8_t* a_codes, const void* a_scales, const 
       const int64_t n_col = (outs + Cfg::BN - 1) / Cfg::BN, n_row = (tokens + Cfg::BM - 1) / Cfg::BM;                \
       const int64_t n_wg = 8 * ((n_col + 7) / 8) * n_row;                                                            \
       if (n_wg > 0x7FFFFFFF) return FPQ_ERR_SHAPE;                                                                   \
-      if (w_scale_dtype == FPQ_F16)                                                                                  \
+      if (qkn && w_scale_dtype == FPQ_F16)                                                                           \
+        hipLaunchKernelGGL((gemm_fp4_glds_kernel<_Float16, MT, NT, GemmQkNorm>), dim3((unsigned)n_wg), dim3(256), lds, st, \
+                           a_codes, (const _Float16*)a_scales, w_codes, (const _Float16*)w_scales,                   \
+                           (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, *qkn);        \
+      else if (qkn)                                                                                                  \
+        hipLaunchKernelGGL((gemm_fp4_glds_kernel<float, MT, NT, GemmQkNorm>), dim3((unsigned)n_wg), dim3(256), lds, st, \
+                           a_codes, (const _Float16*)a_scales, w_codes, (const float*)w_scales,                      \
+                           (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, *qkn);        \
+      else if (w_scale_dtype == FPQ_F16)                                                                             \
         hipLaunchKernelGGL((gemm_fp4_glds_kernel<_Float16, MT, NT>), dim3((unsigned)n_wg), dim3(256), lds, st,      \
                            a_codes, (const _Float16*)a_scales, w_codes, (const _Float16*)w_scales,                   \
                            (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, GemmNoFc1{});      \
@@ -246,6 +255,16 @@ int fpq_gemm_fp4_mx_split(const uint8_t* a_codes, const void* a_scales, const ui
                           fpq_stream_t stream) {
   if (!split) return FPQ_ERR_ARG;
   return gemm_fp4_mx_impl(a_codes, a_scales, w_codes, w_scales, w_scale_dtype, bias, nullptr, tokens, outs, k, nullptr, kmajor != 0, stream, split);
+}
+int fpq_gemm_fp4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, const uint8_t* w_codes, const void* w_scales,
+                                 int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
+                                 const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream) {
+  // parts q, k, v of heads of 64 columns; the fp32 bias is read four outputs (16 bytes) at a time
+  if (!split || split->n_parts != 3 || split->part_cols <= 0 || split->part_cols % 128 != 0) return FPQ_ERR_ARG;
+  if (!q_head_scale || ((uintptr_t)q_head_scale & 3) != 0 || ((uintptr_t)bias & 15) != 0) return FPQ_ERR_ARG;
+  const GemmQkNorm qkn{bias, q_head_scale};
+  return gemm_fp4_mx_impl(a_codes, a_scales, w_codes, w_scales, w_scale_dtype, nullptr, nullptr, tokens, outs, k, nullptr, kmajor != 0, stream,
+                          split, &qkn);
 }
 int fpq_gemm_fp4_mx_km(const uint8_t* a_image, const void* a_scales, const uint8_t* w_image, const void* w_scales,
                        int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,

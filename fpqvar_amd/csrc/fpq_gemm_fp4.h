@@ -341,6 +341,28 @@ struct GemmFc1 {
 
 // (the GELU itself - gelu_tanh_fast - lives in fpq_fast16.h: the stand-alone fused quantizer uses it too)
 
+// ---------------------------------------------------------------------------------------------------
+// mat_qkv of an attention block with attn_l2_norm (round 6; include/fpq.h fpq_gemm_fp4_mx_split_qknorm), the split epilogue with
+//     y = float(half(acc)) + b32            the fp16 Linear output (mat_qkv has no bias), then the fp32 cat(q_bias, 0, v_bias)
+//     part 0 (q): half(y / max(||y||_2, 1e-12) * s_h)      part 1 (k): half(y / max(||y||_2, 1e-12))      part 2 (v): half(y)
+// per (token, head) over the head's 64 columns (tr/basic_var.py:173-183).  Lanes: a wavefront owns 64 consecutive outputs of a
+// 128-aligned tile, a lane four of them (4q .. 4q + 3, see the dealt weight rows), so a token row's head is the 16 lanes of one DPP
+// row - four in-lane FMAs and four DPP steps per row, no LDS, no barrier.  The quotient: a real square root, one real division per
+// row (1 / n) and per element q = y (1/n) + (y - q n)(1/n) - the correctly rounded quotient but for rare ties.
+struct GemmQkNorm {
+  const float* bias;      // fp32 [3 * part_cols] or nullptr (16-byte aligned)
+  const float* q_scale;   // fp32 [part_cols / 64]: exp(min(scale_mul_1H11, log 100))
+};
+
+// sum over the 16 lanes of a DPP row; every lane ends with the same bits (each step adds a value and its mirror image)
+FPQ_NOPK __device__ __forceinline__ float row_sum16(float v) {
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));   // row_half_mirror
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));   // row_mirror
+  return v;
+}
+
 // One step of the maxima's reduce-scatter over the 16 lanes of a DPP row: rows r and r + N / 2 are paired, a lane keeps the
 // one its bit selects and hands the other to its partner (DPP control CTRL), taking the partner's in return: N rows in, N / 2
 // out, each now the maximum over twice as many lanes.  N == 1: plain exchange-and-max.  Packed pairs, unsigned compare.
@@ -372,14 +394,15 @@ FPQ_NOPK __device__ __forceinline__ uint32_t quant_pair16_dual(uint32_t wk, cons
 // target("no-packed-fp32-ops"): beside MFMAs a packed fp32 op costs as much as two scalar ones and blocks the issue
 // port twice as long (tools/probe/valu_mfma_overlap.hip); with the feature off the compiler emits scalar
 // v_mul_f32 / v_fma_f32 and schedules them - and the MFMA hazard wait states - itself.
-// XE = GemmNoFc1: the plain Linear (+ gate / residual tail); XE = GemmFc1: the fc1 tail above.
+// XE = GemmNoFc1: the plain Linear (+ gate / residual tail); XE = GemmFc1: the fc1 tail above; XE = GemmQkNorm: the split
+// output with the q / k norm above.
 template <typename Tsw, int MT, int NT, typename XE = GemmNoFc1>
 __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4_glds_kernel(const uint8_t* __restrict__ A,
                                                               const _Float16* __restrict__ sa,
                                                               const uint8_t* __restrict__ W, const Tsw* __restrict__ sw,
                                                               const _Float16* __restrict__ bias,
                                                               _Float16* out, int T, int O, int C, GemmEpi epi, XE xe) {
-  constexpr bool FC1 = !__is_same(XE, GemmNoFc1);
+  constexpr bool FC1 = __is_same(XE, GemmFc1), QKN = __is_same(XE, GemmQkNorm);
   constexpr int WR = 2, WC = 2, BM = 16 * MT * WR, BN = 16 * NT * WC, NTHR = 256;
   constexpr int ABLK = BM / 16, BBLK = BN / 16, NBLK = ABLK + BBLK, STAGE = NBLK * 1024;
   static_assert(NBLK % 4 == 0, "blocks are dealt round-robin to the four wavefronts");
@@ -495,6 +518,12 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4
   const int oc = o < O ? o : O - 4;
   fpq_h4_t bias_h = fpq_h4_t{0, 0, 0, 0};
   if (bias) bias_h = *(const fpq_h4_t*)(bias + oc);
+  v4f_t qkn_b = v4f_t{0, 0, 0, 0};   // (QKN) the fp32 bias of the lane's outputs, and s_h of its head in part 0
+  float qkn_s = 1.0f;
+  if constexpr (QKN) {
+    if (xe.bias) qkn_b = *(const v4f_t*)(xe.bias + oc);
+    if (o0 < epi.sp_cols) qkn_s = xe.q_scale[oc >> 6];
+  }
 
   v4f_t acc[MT][NT];
 #pragma unroll
@@ -686,10 +715,35 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4
   for (int m = 0; m < MT; ++m) {
     const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);
     fpq_h4_t y[4];
+    if constexpr (QKN) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+      for (int i = 0; i < 4; ++i) {
+        float yf[NT];
 #pragma unroll
-      for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)(acc[m][n][i] + b4[n]);
+        for (int n = 0; n < NT; ++n) yf[n] = (float)(_Float16)acc[m][n][i] + qkn_b[n];
+        if (part < 2) {   // uniform over the tile
+          float ss = yf[0] * yf[0];
+#pragma unroll
+          for (int n = 1; n < NT; ++n) ss = __builtin_fmaf(yf[n], yf[n], ss);
+          float nrm = __builtin_sqrtf(row_sum16(ss));
+          nrm = nrm < 1e-12f ? 1e-12f : nrm;   // clamp_min(eps) (a NaN stays a NaN)
+          const float inv = 1.0f / nrm;
+#pragma unroll
+          for (int n = 0; n < NT; ++n) {
+            float q = yf[n] * inv;
+            q = __builtin_fmaf(__builtin_fmaf(-q, nrm, yf[n]), inv, q);
+            yf[n] = part == 0 ? q * qkn_s : q;
+          }
+        }
+#pragma unroll
+        for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)yf[n];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)(acc[m][n][i] + b4[n]);
+    }
     int tc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;

@@ -1746,10 +1746,11 @@ int fpq_quant_rows_segments(const fpq_segment_t* segments_device, int n_segments
   return launch_fast32((const Seg32*)segments_device, n_segments, none, max_rows, table_id, out_dtype, (hipStream_t)stream);
 }
 
-int fpq_kv_cache_step(void* cache, int64_t batch, int64_t max_len, int64_t row_elems, int64_t quant_start,
-                      int64_t quant_stop, const void* new_k, const void* new_v, int64_t new_batch_pitch,
-                      int64_t new_token_pitch, int64_t new_start, int64_t n_new, int64_t group, int table_id,
-                      fpq_stream_t stream) {
+// qn: the q / k norm form (fpq_kv_cache_step_qknorm): its pointers checked by the caller, grid z = 3
+static int kv_cache_step_impl(void* cache, int64_t batch, int64_t max_len, int64_t row_elems, int64_t quant_start,
+                              int64_t quant_stop, const void* new_k, const void* new_v, int64_t new_batch_pitch,
+                              int64_t new_token_pitch, int64_t new_start, int64_t n_new, int64_t group, int table_id,
+                              fpq_stream_t stream, const KvStepQkn* qn) {
   if (batch < 0 || max_len < 0 || row_elems <= 0 || n_new < 0) return FPQ_ERR_ARG;
   if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
   if (quant_start < 0 || quant_stop < quant_start || new_start < quant_stop || new_start + n_new > max_len)
@@ -1782,9 +1783,14 @@ int fpq_kv_cache_step(void* cache, int64_t batch, int64_t max_len, int64_t row_e
   const int64_t c_tiles = (k.new_vecs + kBlock * U - 1) / (kBlock * U);
   if (q_tiles + c_tiles > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
   k.q_tiles = (int)q_tiles;
-  const dim3 grid((unsigned)(q_tiles + c_tiles), (unsigned)batch, 2);
+  const dim3 grid((unsigned)(q_tiles + c_tiles), (unsigned)batch, qn ? 3 : 2);
   const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
   hipStream_t st = (hipStream_t)stream;
+  if (qn) {
+    if (group == 64) hipLaunchKernelGGL((kv16_step_qkn_kernel<8, U>), grid, dim3(kBlock), lds, st, k, *qn, h.args, h.tab);
+    else hipLaunchKernelGGL((kv16_step_qkn_kernel<16, U>), grid, dim3(kBlock), lds, st, k, *qn, h.args, h.tab);
+    return check_launch();
+  }
 #define FPQ_KV_CASE(L) \
   case L: hipLaunchKernelGGL((kv16_step_kernel<L, U>), grid, dim3(kBlock), lds, st, k, h.args, h.tab); break;
   switch ((int)(group / 8)) {
@@ -1792,6 +1798,31 @@ int fpq_kv_cache_step(void* cache, int64_t batch, int64_t max_len, int64_t row_e
   }
 #undef FPQ_KV_CASE
   return check_launch();
+}
+
+int fpq_kv_cache_step(void* cache, int64_t batch, int64_t max_len, int64_t row_elems, int64_t quant_start,
+                      int64_t quant_stop, const void* new_k, const void* new_v, int64_t new_batch_pitch,
+                      int64_t new_token_pitch, int64_t new_start, int64_t n_new, int64_t group, int table_id,
+                      fpq_stream_t stream) {
+  return kv_cache_step_impl(cache, batch, max_len, row_elems, quant_start, quant_stop, new_k, new_v, new_batch_pitch, new_token_pitch,
+                            new_start, n_new, group, table_id, stream, nullptr);
+}
+
+int fpq_kv_cache_step_qknorm(void* cache, int64_t batch, int64_t max_len, int64_t row_elems, int64_t quant_start,
+                             int64_t quant_stop, const void* new_q, const void* new_k, const void* new_v, int64_t new_batch_pitch,
+                             int64_t new_token_pitch, int64_t new_start, int64_t n_new, int64_t group, int table_id,
+                             void* q_out, const float* q_head_scale, const float* bias, int64_t head_dim, fpq_stream_t stream) {
+  if (head_dim != 64 || row_elems <= 0 || row_elems % 64 != 0 || (group != 64 && group != 128)) return FPQ_ERR_ARG;
+  if (!q_head_scale || ((uintptr_t)q_head_scale & 3) != 0 || ((uintptr_t)bias & 15) != 0) return FPQ_ERR_ARG;
+  if (n_new > 0 && (!new_q || !q_out || (((uintptr_t)new_q | (uintptr_t)q_out) & 15) != 0)) return FPQ_ERR_ARG;
+  KvStepQkn qn;
+  qn.q = (const uint16_t*)new_q;
+  qn.q_out = (u32x4*)q_out;
+  qn.q_scale = q_head_scale;
+  qn.bias = bias;
+  qn.row_elems = (int)row_elems;
+  return kv_cache_step_impl(cache, batch, max_len, row_elems, quant_start, quant_stop, new_k, new_v, new_batch_pitch, new_token_pitch,
+                            new_start, n_new, group, table_id, stream, &qn);
 }
 
 int fpq_quant_rows_argmin(const void* x, float* out, int64_t rows, int64_t cols, int table_id, int in_dtype,

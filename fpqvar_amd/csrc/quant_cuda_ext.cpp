@@ -375,6 +375,40 @@ void kv_cache_step(const at::Tensor& cache, int64_t quant_start, int64_t quant_s
                           n ? k.stride(1) : 0, new_start, n, (int)group, (int)table_id, current_stream(cache)), "fpq_kv_cache_step");
 }
 
+// the same step for a block with attn_l2_norm (ops.kv_cache_step_qk_norm holds the argument checks' prose); returns the normalized q
+at::Tensor kv_cache_step_qk_norm(const at::Tensor& cache, int64_t quant_start, int64_t quant_stop, const at::Tensor& q, const at::Tensor& k,
+                                 const at::Tensor& v, int64_t new_start, int64_t group, int64_t table_id, const at::Tensor& head_scale,
+                                 const c10::optional<at::Tensor>& bias) {
+  require_gpu(cache, "kv_cache_step_qk_norm");
+  TORCH_CHECK(cache.scalar_type() == at::kHalf && q.scalar_type() == at::kHalf && k.scalar_type() == at::kHalf && v.scalar_type() == at::kHalf,
+              "kv_cache_step_qk_norm: cache, q, k and v must be float16");
+  TORCH_CHECK(cache.dim() == 5 && cache.size(0) == 2 && cache.is_contiguous(), "kv_cache_step_qk_norm: cache must be a contiguous [2, B, max_len, H, c] tensor");
+  const int64_t B = cache.size(1), max_len = cache.size(2), H = cache.size(3), c = cache.size(4);
+  TORCH_CHECK(c == 64, "kv_cache_step_qk_norm: head_dim must be 64, got ", c);
+  TORCH_CHECK(q.sizes() == k.sizes() && k.sizes() == v.sizes() && k.dim() == 4 && k.size(0) == B && k.size(2) == H && k.size(3) == c &&
+              q.device() == cache.device() && k.device() == cache.device() && v.device() == cache.device(),
+              "kv_cache_step_qk_norm: q / k / v must be [B, n, H, c] on the cache's device");
+  const int64_t n = k.size(1);
+  if (n)
+    TORCH_CHECK(k.stride(3) == 1 && k.stride(2) == c && q.strides() == k.strides() && k.strides() == v.strides(),
+                "kv_cache_step_qk_norm: q, k and v must share their strides, with contiguous (H, c) rows");
+  TORCH_CHECK(head_scale.scalar_type() == at::kFloat && head_scale.numel() == H && head_scale.is_contiguous() && head_scale.device() == cache.device(),
+              "kv_cache_step_qk_norm: head_scale must be a contiguous float32 tensor of ", H, " values on the cache's device");
+  const void* b = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->numel() == 3 * H * c && bias->is_contiguous() && bias->device() == cache.device(),
+                "kv_cache_step_qk_norm: bias must be a contiguous float32 tensor of ", 3 * H * c, " values on the cache's device");
+    b = bias->data_ptr();
+  }
+  at::Tensor q_out = at::empty({B, n, H, c}, cache.options());
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(cache.device());
+  check(fpq_kv_cache_step_qknorm(cache.data_ptr(), B, max_len, H * c, quant_start, quant_stop, q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                 n ? k.stride(0) : 0, n ? k.stride(1) : 0, new_start, n, group, (int)table_id, q_out.data_ptr(),
+                                 (const float*)head_scale.data_ptr(), (const float*)b, c, current_stream(cache)),
+        "fpq_kv_cache_step_qknorm");
+  return q_out;
+}
+
 void check_operand(const char* what, const at::Tensor& codes, const at::Tensor& scales, int64_t rows, int64_t row_bytes, int64_t n_scales,
                    const at::Device& dev) {
   TORCH_CHECK(codes.scalar_type() == at::kByte && codes.is_contiguous() && codes.device() == dev, what, ": codes must be a contiguous uint8 tensor on ", dev);
@@ -556,6 +590,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kmajor") = false);
   m.def("kv_cache_step", &kv_cache_step, py::arg("cache"), py::arg("quant_start"), py::arg("quant_stop"), py::arg("k"), py::arg("v"),
         py::arg("new_start"), py::arg("group"), py::arg("table_id"));
+  m.def("kv_cache_step_qk_norm", &kv_cache_step_qk_norm, py::arg("cache"), py::arg("quant_start"), py::arg("quant_stop"), py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("new_start"), py::arg("group"), py::arg("table_id"), py::arg("head_scale"),
+        py::arg("bias") = py::none());
   m.def("linear_fp4", &linear_fp4, py::arg("a_codes"), py::arg("a_scales"), py::arg("w_codes"), py::arg("w_scales"),
         py::arg("bias") = py::none(), py::arg("gate") = py::none(), py::arg("residual") = py::none(), py::arg("outs") = py::none());
   m.def("linear_fp4_gelu_dual", &linear_fp4_gelu_dual, py::arg("a_codes"), py::arg("a_scales"), py::arg("w_codes"), py::arg("w_scales"),

@@ -220,12 +220,17 @@ def linear_fp4(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Ten
 
 
 def linear_fp4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
-                            bias: Optional[torch.Tensor], cache_kv: torch.Tensor, pos: int, seq: int) -> torch.Tensor:
+                            bias: Optional[torch.Tensor], cache_kv: torch.Tensor, pos: int, seq: int,
+                            qk_norm_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """mat_qkv of an attention block with a split output (fpq_gemm_fp4_mx_split): `qkv = linear_fp4(a, w, bias)` for tokens
     [B * seq] and outs = 3 * C, but only q comes back - fp16 [B, seq, C] - while k and v are written straight into the KV cache
     `cache_kv` [2, B, max_len, H, c] (C = H * c) at token positions pos .. pos + seq: what `qkv.view(B, L, 3, H, c).unbind(2)`
     followed by the cache's copy-in (tr/basic_var.py:173-209; kv_cache.IncrementalKVCache.append) leaves there, without the copy.
-    Operands row-major (2-D) or k-major images (3-D) as in linear_fp4."""
+    Operands row-major (2-D) or k-major images (3-D) as in linear_fp4.
+
+    qk_norm_scale: fp32 [H] (kv_cache.qk_norm_head_scale) - the attention block has attn_l2_norm (fpq_gemm_fp4_mx_split_qknorm):
+    y = float(fp16 Linear output) + bias (fp32 [3C] or None: q_bias, 0, v_bias, added after the fp16 rounding), q =
+    F.normalize(y_q) * qk_norm_scale per head, k = F.normalize(y_k) into the cache, v = y_v (tr/basic_var.py:173-183), head_dim 64."""
     from ._lib import GemmSplit
     require_gpu(a_codes, "linear_fp4_qkv_to_cache")
     km = _kmajor_pair("linear_fp4_qkv_to_cache", a_codes, w_codes, 64)
@@ -246,7 +251,19 @@ def linear_fp4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_cod
         raise RuntimeError(f"linear_fp4_qkv_to_cache: {tokens} tokens x {outs} outputs do not fit a cache of [{bsz}, {max_len}, {heads}, {hd}] at {pos} .. {pos + seq}")
     q = torch.empty((bsz, seq, c), dtype=torch.float16, device=dev)
     b = None
-    if bias is not None:
+    if qk_norm_scale is not None:
+        if hd != 64:
+            raise RuntimeError(f"linear_fp4_qkv_to_cache: the q / k norm needs head_dim 64, the cache has {hd}")
+        if qk_norm_scale.dtype != torch.float32 or qk_norm_scale.numel() != heads or qk_norm_scale.device != dev:
+            raise RuntimeError(f"linear_fp4_qkv_to_cache: qk_norm_scale must be a float32 tensor of {heads} values on the operands' device")
+        hs = qk_norm_scale.detach().reshape(-1).contiguous()
+        if bias is not None:
+            if bias.dtype != torch.float32 or bias.numel() != outs or bias.device != dev:
+                raise RuntimeError(f"linear_fp4_qkv_to_cache: with qk_norm_scale the bias must be a float32 tensor of {outs} values on the operands' device")
+            b = bias.detach().reshape(-1).contiguous()
+            if b.data_ptr() % 16:
+                b = b.clone()
+    elif bias is not None:
         if bias.numel() != outs or bias.device != dev:
             raise RuntimeError("linear_fp4_qkv_to_cache: bias must hold one value per output on the operands' device")
         b = bias.detach().to(torch.float16).reshape(-1).contiguous()
@@ -256,7 +273,13 @@ def linear_fp4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_cod
     sp.part_cols, sp.n_parts, sp.rows_per_batch = c, 3, seq
     for p, (t, bstride, row0) in enumerate(((q, seq, 0), (cache_kv[0], max_len, pos), (cache_kv[1], max_len, pos))):
         sp.out[p], sp.row_stride[p], sp.batch_stride[p], sp.row0[p] = t.data_ptr(), c, bstride, row0
-    if tokens:
+    if tokens and qk_norm_scale is not None:
+        with device_guard(dev):
+            check(lib().fpq_gemm_fp4_mx_split_qknorm(a_codes.data_ptr(), a_scales.data_ptr(), w_codes.data_ptr(), w_scales.data_ptr(),
+                                                     dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), tokens, outs, k,
+                                                     ctypes.byref(sp), hs.data_ptr(), 1 if km else 0, stream_ptr(dev)),
+                  "fpq_gemm_fp4_mx_split_qknorm")
+    elif tokens:
         with device_guard(dev):
             check(lib().fpq_gemm_fp4_mx_split(a_codes.data_ptr(), a_scales.data_ptr(), w_codes.data_ptr(), w_scales.data_ptr(),
                                               dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), tokens, outs, k,

@@ -7,11 +7,22 @@ Both are single launches of the fused kernels (8 or 16 lanes own a row).
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
 
 import torch
 
 from . import ops, quant_utils as qu
+
+
+MAX_SCALE_MUL = math.log(100)   # SelfAttention.max_scale_mul (tr/basic_var.py:140), torch.log(torch.tensor(100)).item()
+
+
+def qk_norm_head_scale(scale_mul_1H11: torch.Tensor) -> torch.Tensor:
+    """The per-head multiplier of q in a block with attn_l2_norm: `scale_mul_1H11.clamp_max(max_scale_mul).exp()`
+    (tr/basic_var.py:178) as fp32 [H] - computed once at load time, the argument of IncrementalKVCache.append_qk_norm and of
+    gemm.linear_fp4_qkv_to_cache(..., qk_norm_scale=)."""
+    return scale_mul_1H11.detach().float().clamp_max(MAX_SCALE_MUL).exp().reshape(-1).contiguous()
 
 
 def quantize_kv(t: torch.Tensor, kv_bit: int) -> torch.Tensor:
@@ -127,3 +138,23 @@ class IncrementalKVCache:
         self._prev = self.len
         self.len += n
         return self.k[:, :self.len], self.v[:, :self.len]
+
+    @torch.no_grad()
+    def append_qk_norm(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, head_scale: torch.Tensor,
+                       bias: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """`append` for a block with attn_l2_norm, q / k / v the fp16 [B, n, H, 64] parts of mat_qkv's output WITHOUT its bias
+        (views of one qkv tensor are fine): adds the fp32 bias [3C] (q_bias, 0, v_bias, or None), L2-normalizes k per head on
+        its way into the cache and returns (q normalized and scaled by head_scale - qk_norm_head_scale -, K, V) - one launch
+        (fpq_kv_cache_step_qknorm, include/fpq.h holds the numerics)."""
+        n = k.shape[1]
+        assert self.len + n <= self.k.shape[1], "IncrementalKVCache: max_len exceeded"
+        if self._group not in (64, 128) or self.k.shape[-1] != 64:
+            raise RuntimeError("IncrementalKVCache.append_qk_norm: needs an fp16 cache with head_dim 64 (kv_bit 6 or 4)")
+        if not (q.stride() == k.stride() == v.stride()) or k.stride(3) != 1 or k.stride(2) != k.shape[3] or k.stride(0) % 8 or k.stride(1) % 8 \
+                or q.data_ptr() % 16 or k.data_ptr() % 16 or v.data_ptr() % 16:
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        qn = ops.kv_cache_step_qk_norm(self.kv, self._prev, self.len, q, k, v, self.len, self._group,
+                                       "e2m3" if self.kv_bit == 6 else "e2m1", head_scale, bias)
+        self._prev = self.len
+        self.len += n
+        return qn, self.k[:, :self.len], self.v[:, :self.len]

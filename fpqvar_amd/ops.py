@@ -173,6 +173,42 @@ def kv_cache_step(cache: torch.Tensor, quant_start: int, quant_stop: int, k: tor
                                       TABLE_IDS[table], stream_ptr(cache.device)), "fpq_kv_cache_step")
 
 
+def kv_cache_step_qk_norm(cache: torch.Tensor, quant_start: int, quant_stop: int, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                          new_start: int, group: int, table: str, head_scale: torch.Tensor,
+                          bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fpq_kv_cache_step_qknorm: kv_cache_step for a block with attn_l2_norm (include/fpq.h) - the new k is L2-normalized per head
+    on its way into the cache, and the new q [B, n, H, 64] (the strides of k) comes back normalized and scaled by head_scale
+    (fp32 [H], kv_cache.qk_norm_head_scale), fp16 [B, n, H, 64] contiguous; the optional fp32 bias [3 * H * 64] (q_bias, 0,
+    v_bias) is added to the fp16 q, k, v first.  One launch."""
+    if _native is not None:
+        return _native.kv_cache_step_qk_norm(cache, quant_start, quant_stop, q, k, v, new_start, group, TABLE_IDS[table], head_scale, bias)
+    require_gpu(cache, "kv_cache_step_qk_norm")
+    if cache.dtype != torch.float16 or q.dtype != torch.float16 or k.dtype != torch.float16 or v.dtype != torch.float16:
+        raise RuntimeError("kv_cache_step_qk_norm: cache, q, k and v must be float16")
+    if cache.dim() != 5 or cache.shape[0] != 2 or not cache.is_contiguous():
+        raise RuntimeError("kv_cache_step_qk_norm: cache must be a contiguous [2, B, max_len, H, c] tensor")
+    _, B, max_len, H, c = cache.shape
+    if c != 64:
+        raise RuntimeError(f"kv_cache_step_qk_norm: head_dim must be 64, got {c}")
+    if not (q.shape == k.shape == v.shape) or k.dim() != 4 or k.shape[0] != B or tuple(k.shape[2:]) != (H, c):
+        raise RuntimeError(f"kv_cache_step_qk_norm: q / k / v must be [B, n, H, c] = [{B}, n, {H}, {c}], got {tuple(q.shape)} / {tuple(k.shape)} / {tuple(v.shape)}")
+    n = k.shape[1]
+    if n and (k.stride(3) != 1 or k.stride(2) != c or not (q.stride() == k.stride() == v.stride())):
+        raise RuntimeError("kv_cache_step_qk_norm: q, k and v must share their strides, with contiguous (H, c) rows")
+    if head_scale.dtype != torch.float32 or head_scale.numel() != H or not head_scale.is_contiguous() or head_scale.device != cache.device:
+        raise RuntimeError(f"kv_cache_step_qk_norm: head_scale must be a contiguous float32 tensor of {H} values on the cache's device")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != 3 * H * c or not bias.is_contiguous() or bias.device != cache.device):
+        raise RuntimeError(f"kv_cache_step_qk_norm: bias must be a contiguous float32 tensor of {3 * H * c} values on the cache's device")
+    q_out = torch.empty((B, n, H, c), dtype=torch.float16, device=cache.device)
+    with device_guard(cache.device):
+        check(lib().fpq_kv_cache_step_qknorm(cache.data_ptr(), B, max_len, H * c, quant_start, quant_stop, q.data_ptr(), k.data_ptr(),
+                                             v.data_ptr(), k.stride(0) if n else 0, k.stride(1) if n else 0, new_start, n, group,
+                                             TABLE_IDS[table], q_out.data_ptr(), head_scale.data_ptr(),
+                                             None if bias is None else bias.data_ptr(), c, stream_ptr(cache.device)),
+              "fpq_kv_cache_step_qknorm")
+    return q_out
+
+
 def quant_rows_argmin(x: torch.Tensor, table: str, cols: int, clamp3: bool) -> torch.Tensor:
     """The reference's pure-torch quantizers (argmin lookup, float32 result) in one launch."""
     require_gpu(x, "quant_rows_argmin")

@@ -109,8 +109,8 @@ class GenerationBatch:
 
     def __init__(self, model: str = "d30-256", config: str = "w4a4", depth: Optional[int] = None,
                  batch_rows: Optional[int] = None, device=None, seed: int = 0, fused_fc1: bool = True, sdpa_in_f: bool = False,
-                 kmajor: bool = True, qkv_to_cache: bool = True):
-        assert model in MODELS and config in ("w4a4", "w6a6")
+                 kmajor: bool = True, qkv_to_cache: bool = True, attn_l2_norm: bool = False, qk_norm: str = "fused"):
+        assert model in MODELS and config in ("w4a4", "w6a6") and qk_norm in ("fused", "torch")
         self.model, self.config = model, config
         heads, self.patch_nums, rows = MODELS[model]
         dev = self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -158,6 +158,21 @@ class GenerationBatch:
         self.gneg = torch.tensor([-1.75, -1.5, -1.25, -1.0, -0.75, -0.5, -0.25, 0.0], device=dev)
         self.gpos = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], device=dev)
         self.ineg, self.e2m3p = qu.int_neg_grid.to(dev), qu.e2m3_pos_grid.to(dev)
+        # attn_l2_norm (the released models' setting, tr/basic_var.py:136-140,173-183): per block a scale_mul_1H11 around log 4 with
+        # head 0 above log 100 (its clamp is exercised) and the fp32 bias cat(q_bias, 0, v_bias); attention at scale 1.  Drawn from
+        # a generator of their own: every other tensor is the same with and without the flag.  qk_norm: "fused" - paths F / Q
+        # normalize inside the qkv-to-cache kernels; "torch" - the reference's lines between the existing kernels (A/B, tests).
+        self.attn_l2_norm, self.qk_norm = attn_l2_norm, qk_norm
+        if attn_l2_norm:
+            gn = torch.Generator(device=dev).manual_seed(seed + 7919)
+            self.scale_mul = []
+            for _ in range(self.depth):
+                sm = torch.full((1, heads, 1, 1), 4.0, device=dev).log() + 0.3 * torch.randn(1, heads, 1, 1, device=dev, generator=gn)
+                sm[0, 0] = kv_cache.MAX_SCALE_MUL + 0.5
+                self.scale_mul.append(sm)
+            self.head_scale = [kv_cache.qk_norm_head_scale(sm) for sm in self.scale_mul]
+            self.qkv_bias = [torch.cat((torch.randn(C, device=dev, generator=gn) * 0.1, torch.zeros(C, device=dev),
+                                        torch.randn(C, device=dev, generator=gn) * 0.1)) for _ in range(self.depth)]
 
     # ---- the quantizers of the three paths -------------------------------------------------------------------------
     def r_act(self, t):       # activation quantizer of mat_qkv / proj / fc1, the reference's op sequence
@@ -201,9 +216,18 @@ class GenerationBatch:
         """fc2's quantized input straight out of the fc1 GEMM: GELU(tanh) and the dual E1M2-/E2M1+ quantizer in its epilogue."""
         return gemm.linear_fp4_gelu_dual(*rot.adaln_rotate_quant_mx(t, sc, sh, smooth=self.s_fc1, kmajor=self.kmajor), *self.wop["fc1"])
 
-    def attend(self, q, kc, vc):               # q [B,L,H,c]; kc, vc [B,Ltot,H,c] (flash layout, as the KV runs use)
-        o = Fn.scaled_dot_product_attention(q.transpose(1, 2), kc.transpose(1, 2), vc.transpose(1, 2))
+    def attend(self, q, kc, vc, scale=None):   # q [B,L,H,c]; kc, vc [B,Ltot,H,c] (flash layout, as the KV runs use)
+        if scale is None and self.attn_l2_norm:
+            scale = 1.0
+        o = Fn.scaled_dot_product_attention(q.transpose(1, 2), kc.transpose(1, 2), vc.transpose(1, 2), scale=scale)
         return o.transpose(1, 2).reshape(q.shape[0], q.shape[1], self.C)
+
+    def qk_norm_torch(self, qkv, b):
+        """the reference's lines (tr/basic_var.py:173-183, flash layout) on an fp16 qkv [B, L, 3C] without its bias: fp32 q, k, v"""
+        B, L = qkv.shape[0], qkv.shape[1]
+        q, k, v = (qkv + self.qkv_bias[b]).view(B, L, 3, self.H, self.hd).unbind(2)
+        scale_mul = self.scale_mul[b].clamp_max(kv_cache.MAX_SCALE_MUL).exp().transpose(1, 2)   # 1H11 -> 11H1
+        return Fn.normalize(q, dim=-1).mul(scale_mul), Fn.normalize(k, dim=-1), v
 
     def new_caches(self, path):
         if path == "R":
@@ -222,14 +246,17 @@ class GenerationBatch:
             if path == "R":
                 with torch.autocast("cuda", dtype=torch.float16):
                     x1 = torch.matmul(Fn.layer_norm(x, (C,), eps=1e-6).mul(sc1.add(1)).add_(sh1).mul(self.s_qkv), self.q32)
-                    qkv = Fn.linear(self.r_act(x1), self.wq["qkv"]).view(B, L, 3, H, hd)
-                    q, k, v = qkv.unbind(2)
+                    if self.attn_l2_norm:                      # fp32 q, k, v (the fp32 bias promotes) and an fp32 cache, as the reference
+                        q, k, v = self.qk_norm_torch(Fn.linear(self.r_act(x1), self.wq["qkv"]), b)
+                    else:
+                        q, k, v = Fn.linear(self.r_act(x1), self.wq["qkv"]).view(B, L, 3, H, hd).unbind(2)
+                    cache_dtype = None if self.attn_l2_norm else torch.float16
                     if caches[b] is None:
                         kc, vc = k, v
                     else:                                        # tr/basic_var.py:186-209: whole cache, every step
                         ck, cv = caches[b]
-                        ck = _ref_sym(ck.contiguous(), self.e2m3, None, torch.float16)
-                        cv = _ref_sym(cv.contiguous(), self.e2m3, None, torch.float16)
+                        ck = _ref_sym(ck.contiguous(), self.e2m3, None, cache_dtype)
+                        cv = _ref_sym(cv.contiguous(), self.e2m3, None, cache_dtype)
                         kc, vc = torch.cat((ck, k), dim=1), torch.cat((cv, v), dim=1)
                     caches[b] = (kc, vc)
                     a = Fn.linear(self.r_act(self.attend(q, kc, vc)), self.wq["proj"])
@@ -238,18 +265,28 @@ class GenerationBatch:
                     h = Fn.gelu(Fn.linear(self.r_act(x2), self.wq["fc1"]), approximate="tanh")
                     x = x + Fn.linear(self.r_fc2(h), self.wq["fc2"]).mul(g2)
                 continue
-            if path == "Q" and self.qkv_to_cache:
+            l2 = self.attn_l2_norm
+            if path == "Q" and self.qkv_to_cache and not (l2 and self.qk_norm == "torch"):
                 q = gemm.linear_fp4_qkv_to_cache(*rot.adaln_rotate_quant_mx(x, sc1, sh1, smooth=self.s_qkv, kmajor=self.kmajor), *self.wop["qkv"],
-                                                 None, caches[b].kv, caches[b].len, L).view(B, L, H, hd)
+                                                 self.qkv_bias[b] if l2 else None, caches[b].kv, caches[b].len, L,
+                                                 qk_norm_scale=self.head_scale[b] if l2 else None).view(B, L, H, hd)
                 kc, vc = caches[b].commit_written(L)
             else:
                 if path == "F":
                     qkv = Fn.linear(self.f_producer(x, sc1, sh1, self.s_qkv), self.wq["qkv"])
                 else:
                     qkv = self.q_producer_linear(x, sc1, sh1, self.s_qkv, "qkv")
-                q, k, v = qkv.view(B, L, 3, H, hd).unbind(2)
-                kc, vc = caches[b].append(k, v)
-            a = self.attend(q, kc, vc) if (path == "F" and self.sdpa_in_f) else ops.attention_blhc(q, kc, vc, hd ** -0.5).view(B, L, C)
+                if l2 and self.qk_norm == "torch":
+                    q, k, v = (t.half() for t in self.qk_norm_torch(qkv.view(B, L, 3 * C), b))
+                    kc, vc = caches[b].append(k, v)
+                elif l2:
+                    q, k, v = qkv.view(B, L, 3, H, hd).unbind(2)
+                    q, kc, vc = caches[b].append_qk_norm(q, k, v, self.head_scale[b], self.qkv_bias[b])
+                else:
+                    q, k, v = qkv.view(B, L, 3, H, hd).unbind(2)
+                    kc, vc = caches[b].append(k, v)
+            scale = 1.0 if l2 else hd ** -0.5
+            a = self.attend(q, kc, vc, scale) if (path == "F" and self.sdpa_in_f) else ops.attention_blhc(q, kc, vc, scale).view(B, L, C)
             if path == "F":
                 x = ops.gate_residual(Fn.linear(self.f_act(a), self.wq["proj"]), g1, x)
             else:
@@ -318,7 +355,8 @@ class GenerationBatch:
 
     def describe(self) -> str:
         return (f"VAR-{self.model} transformer part, {self.depth} blocks x {len(self.patch_nums)} steps ({self.max_len} tokens), "
-                f"B={self.B} rows per token (CFG), {self.config.upper()} + FP6 KV cache, random weights")
+                f"B={self.B} rows per token (CFG), {self.config.upper()} + FP6 KV cache, random weights"
+                + (f", attn_l2_norm (q / k norm: {self.qk_norm})" if self.attn_l2_norm else ""))
 
 
 def generation_record(models: Sequence[str] = ("d30-256", "d36-512"), paths: Sequence[str] = PATHS, config: str = "w4a4",

@@ -24,14 +24,15 @@
 extern "C" {
 #endif
 
-#define FPQ_VERSION 126 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
+#define FPQ_VERSION 127 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
                            0.1.3: + fpq_quant_rows_codes_segments, fpq_dequant_rows_codes_segments (round 3);
                            123: + fpq_build_tag (round 4);
                            124: + fpq_set_option, fpq_get_option, fpq_option_name, fpq_gemm_fp4_gelu_dual, fpq_gelu_quant_rows_dual (round 5);
                            125: + k-major operand images: fpq_codes_to_kmajor, fpq_scales_to_kmajor, fpq_gemm_fp4_mx_km, fpq_gemm_fp4_gelu_dual_km,
                                 fpq_gemm_fp6_rows_km, the *_km producers, fpq_gemm_fp4_mx_split (round 5);
                            126: - the switches FPQ_ROT_BUTTERFLY, FPQ_ADALN_V1, FPQ_ADALN_LANES, FPQ_ADALN_GRID, FPQ_BIGTAB_U
-                                (the kernel forms they chose are retired) */
+                                (the kernel forms they chose are retired);
+                           127: + fpq_gemm_fp4_mx_split_qknorm, fpq_kv_cache_step_qknorm (attn_l2_norm) */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -518,6 +519,33 @@ int fpq_gemm_fp4_mx_split(const uint8_t* a_codes, const void* a_scales, const ui
 int fpq_gemm_fp6_rows_km(const uint8_t* a_image, const void* a_scales, int a_scale_dtype, const uint8_t* w_image,
                          const void* w_scales, int w_scale_dtype, const void* bias, void* out, int64_t tokens,
                          int64_t outs, int64_t k, const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream);
+
+/* THE Q / K L2 NORM of an attention block with attn_l2_norm=True (the default of every released VAR model; tr/basic_var.py:160-183):
+ *     qkv = mat_qkv(x) + cat(q_bias, 0, v_bias);  q = F.normalize(q, dim=-1) * exp(min(scale_mul_1H11, log 100));  k = F.normalize(k, dim=-1)
+ * before k enters the KV cache (quant(k / |k|) != quant(k) / |k|: the norm cannot follow the cache's quantization).  Under
+ * autocast(float16) the Linear's output is fp16 and the fp32 bias promotes it, so with y16 the fp16 Linear output, b32 the fp32 bias
+ * [3C] (or none) and s_h the per-head multiplier q_head_scale[h] (fp32, exp(min(scale_mul_1H11[h], log 100)), computed once by
+ * the caller), per (token, head of 64 channels):
+ *     y = float(y16) + b32                               (the bias AFTER the fp16 rounding)
+ *     q_out = half(y_q / max(sqrt(sum y_q^2), 1e-12) * s_h)      k_cache = half(y_k / max(sqrt(sum y_k^2), 1e-12))      v_cache = half(y_v)
+ * q_out and k within one fp16 ulp of the same lines in fp32 torch (a real square root and quotient, another summation order), v bit
+ * for bit; a zero row gives zeros.  The cache's quantization of these entries at the next step is fpq_kv_cache_step's, unchanged.
+ *
+ * fpq_gemm_fp4_mx_split_qknorm: fpq_gemm_fp4_mx_split with that epilogue: n_parts == 3 (q, k, v), part_cols % 128 == 0, heads of 64
+ * columns (part_cols / 64 of them), bias fp32 [3 * part_cols] 16-byte aligned or NULL, q_head_scale fp32 [part_cols / 64].
+ * Anything else: FPQ_ERR_ARG before any launch. */
+int fpq_gemm_fp4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, const uint8_t* w_codes, const void* w_scales,
+                                 int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
+                                 const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream);
+/* fpq_kv_cache_step_qknorm: fpq_kv_cache_step (same arguments, same checks) for an fp16 qkv WITHOUT the norm (path F, or a
+ * mat_qkv that is not split): the new k is normalized and the bias added on its way into the cache, and the same launch writes
+ * q_out - fp16 [batch, n_new, row_elems], contiguous - from new_q (the pitches of new_k).  head_dim == 64, row_elems % 64 == 0,
+ * group 64 or 128; q_head_scale fp32 [row_elems / 64] never NULL; bias fp32 [3 * row_elems] (q, k, v) 16-byte aligned or NULL;
+ * new_q / q_out 16-byte aligned.  Anything else: FPQ_ERR_ARG before any launch. */
+int fpq_kv_cache_step_qknorm(void* cache, int64_t batch, int64_t max_len, int64_t row_elems, int64_t quant_start,
+                             int64_t quant_stop, const void* new_q, const void* new_k, const void* new_v, int64_t new_batch_pitch,
+                             int64_t new_token_pitch, int64_t new_start, int64_t n_new, int64_t group, int table_id,
+                             void* q_out, const float* q_head_scale, const float* bias, int64_t head_dim, fpq_stream_t stream);
 
 /* Inverse of fpq_quant_rows_codes: out = (Tout)((float)table_dedup[code] * (float)scale). */
 int fpq_dequant_rows_codes(const uint8_t* codes, const void* scales, void* out, int64_t rows,

@@ -29,14 +29,17 @@ def main():
     ap.add_argument("--sdpa-in-f", action="store_true", help="path F with torch's SDPA instead of fpq_attention_blhc (as rounds 1 - 4 timed it)")
     ap.add_argument("--row-major-operands", action="store_true", help="Q path: row-major code tensors instead of k-major images (the form of rounds 1 - 4)")
     ap.add_argument("--qkv-copy-in", action="store_true", help="Q path: mat_qkv writes one [tokens, 3 C] tensor and the cache copies k / v in (the form before fpq_gemm_fp4_mx_split)")
+    ap.add_argument("--attn-l2-norm", action="store_true", help="attention blocks with attn_l2_norm (the released models' setting): q / k L2 norm")
+    ap.add_argument("--qk-norm", default="fused", choices=("fused", "torch"),
+                    help="with --attn-l2-norm: the norm inside the qkv-to-cache kernels (fused) or the reference's torch lines between them")
     ap.add_argument("--tuned-gemms", action="store_true", help="torch's own GEMMs with the recorded TunableOp selections (var_block.tuned_torch_gemms)")
     args = ap.parse_args()
     torch.manual_seed(0)
     gb = var_block.GenerationBatch(args.model, args.config, depth=args.depth, batch_rows=args.batch, device="cuda:0",
                                    fused_fc1=not args.unfused_fc1, sdpa_in_f=args.sdpa_in_f, kmajor=not args.row_major_operands,
-                                   qkv_to_cache=not args.qkv_copy_in)
+                                   qkv_to_cache=not args.qkv_copy_in, attn_l2_norm=args.attn_l2_norm, qk_norm=args.qk_norm)
     res = {"workload": gb.describe(), "depth": gb.depth, "batch_rows": gb.B, "fc1_epilogue_fused": gb.fused_fc1, "kmajor_operands": gb.kmajor, "qkv_to_cache": gb.qkv_to_cache,
-           "library": _lib.build_tag()}
+           "attn_l2_norm": gb.attn_l2_norm, "qk_norm": gb.qk_norm, "library": _lib.build_tag()}
     paths = args.paths.split(",")
     import contextlib
     ctx = var_block.tuned_torch_gemms() if args.tuned_gemms else contextlib.nullcontext()
