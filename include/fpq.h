@@ -135,9 +135,13 @@ int fpq_quant_rows(const void* x, void* out, int64_t rows, int64_t cols, int tab
  * the consumer of the KV cache; at inference there is no mask and no dropout (attn_bias is None with KV caching,
  * :159).  q [B, lq, H, 64] and k / v [B, lkv, H, 64] may be views: rows of H * 64 halves contiguous, batch / token
  * pitch in elements (multiples of 8) free (q out of the fused qkv output, k / v out of fpq_kv_cache_step's cache);
- * out [B, lq, H, 64] contiguous; all 16-byte aligned.  fp32 scores and accumulation on the matrix cores, online
- * softmax; agreement with a reference attention is to fp16 tolerance (P is rounded to fp16 before P V, as in flash
- * attention), not bit-exact. */
+ * out [B, lq, H, 64] contiguous; all 16-byte aligned.  Tokens at or past lkv and anything outside the views are never
+ * read: loads past the end clamp to token lkv - 1 and those keys are masked.  fp32 scores and accumulation on the
+ * matrix cores, online softmax, P rounded to fp16 before P V (as in flash attention), not bit-exact.  Against the
+ * float64 ref = softmax(s) v, s = scale q k^T from the fp16 inputs, with A = softmax(s) |v| and Z = sum_j exp(s_j - max s),
+ * every element satisfies (for |scale q.k| <= 100)
+ *     |out - ref| <= (2^-11 + 2^-13) (|ref| + A) + 2^-25 sum_j |v_jc| / Z + 2^-25
+ * (output rounding, P rounding, fp32 arithmetic, fp16-subnormal P and output; derived in tests/attention_model.py). */
 int fpq_attention_blhc(const void* q, const void* k, const void* v, void* out, int64_t batch, int64_t lq, int64_t lkv,
                        int64_t heads, int64_t head_dim, int64_t q_batch_pitch, int64_t q_token_pitch,
                        int64_t kv_batch_pitch, int64_t kv_token_pitch, float scale, fpq_stream_t stream);

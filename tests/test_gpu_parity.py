@@ -11,6 +11,7 @@ import torch
 
 from fpqvar_amd import _lib
 from oracle import fpq_oracle as orc
+from tests import attention_model as am
 from tests.conftest import assert_bits_equal, from_bits
 
 pytestmark = pytest.mark.gpu
@@ -2048,6 +2049,7 @@ def test_attention_over_the_cache_matches_sdpa(dev, B, H, Lq, Lkv):
             assert out.shape == (B, Lq, H, 64) and out.dtype == torch.float16
             err = (out.float() - ref).abs().max().item()
             assert err <= 2e-3 * float(v_view.abs().max()), (scale, err)
+            assert am.ratio(out, am.reference(q_view, k_view, v_view, scale)) <= 1.0, scale   # tests/attention_model.py
 
 
 def test_attention_argument_checks_and_graph_capture(dev):
@@ -2109,3 +2111,4 @@ def test_attention_fuzz_shapes(dev):
         out = ops.attention_blhc(q, k, v, 0.125)
         err = (out.float() - ref).abs().max().item()
         assert err <= 2e-3 * float(v.abs().max()), (B, H, Lq, Lkv, err)
+        assert am.ratio(out, am.reference(q, k, v, 0.125)) <= 1.0, (B, H, Lq, Lkv)
