@@ -369,8 +369,13 @@ int fpq_adaln_rotate_quant_rows_codes_mx(const void* x, uint8_t* codes, void* sc
  * tr/quant_utils.py:765-767 for the W4A4 per-group E2M1 configuration.  a_codes [tokens, k/2],
  * a_scales fp16 [tokens, k/128], w_codes [outs, k/2], w_scales [outs, k/128] in w_scale_dtype,
  * bias fp16 [outs] or NULL, out fp16 [tokens, outs]; k % 128 == 0, outs % 8 == 0.
- * Numerics: does NOT round the de-quantized operands to fp16 first as the reference's fp16 GEMM does;
- * agreement with it is to fp16-GEMM tolerance, not bit-exact. */
+ * Numerics: does NOT round the de-quantized operands to fp16 first as the reference's fp16 GEMM does.  Against the
+ * float64 product of the decoded operands every element is within
+ *     2^-11 |ref| + 2^-25 + (1 + 2^-10) 2^-24 (S + R + |ref|),   S = sum_g |sa sw d_g|,  R = sum_g |exact partial sum after g|
+ * (tests/gemm_model.py derives it), assuming the 128-term dot d_g of E2M1 levels is exact (multiples of 1/4, |d_g| <= 4608).
+ * Per group the LDS-DMA tilings round t = d_g sa and acc = fma(t, sw, acc), the register-staged ones p = sa sw and
+ * acc = fma(d_g, p, acc); out = fp16(acc + bias), nearest-even, overflow to inf, NaN / inf scales propagate as in IEEE
+ * arithmetic.  Each tiling is bit-equal to an fp32 model of exactly those steps. */
 int fpq_gemm_fp4_mx(const uint8_t* a_codes, const void* a_scales, const uint8_t* w_codes, const void* w_scales,
                     int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
                     fpq_stream_t stream);
@@ -387,8 +392,17 @@ int fpq_quant_rows_codes_fp8(const void* x, uint8_t* codes, void* scales, int64_
  * products, fp32 accumulation, nothing but matrix instructions in the K loop: with one scale per row the scales
  * leave the sum); replaces F.linear(act_quant(x), W_q, b) of tr/quant_utils.py:765-767 for per_token activations x
  * per_channel weights.  a_codes [tokens, k], w_codes [outs, k], bias fp16 [outs] or NULL, out fp16 [tokens, outs];
- * k % 128 == 0, outs % 8 == 0, code arrays and out 16-byte aligned.  Tolerance-level agreement with the reference's
- * fp16 GEMM on the de-quantized tensors (as fpq_gemm_fp4_mx). */
+ * k % 128 == 0, outs % 8 == 0, code arrays and out 16-byte aligned.  Numerics (and fpq_gemm_fp6_rows'): acc is chained
+ * through the k / 128 MFMAs, then out = fp16(fl(fl(acc * fl(sr * sc)) + bias)).  Against the float64 product of the decoded
+ * operands every element is within
+ *     2^-11 |ref| + 2^-25 + (1 + 2^-10) (2^-23 R + 2^-24 (2 S + |ref|)),
+ *     S = |sr sc| sum_k |La Lw|,  R = |sr sc| sum_steps (|exact partial sum before the step| + the step's sum_k |La Lw|)
+ * (tests/gemm_model.py).  The rounding of the chained MFMA accumulator is not documented: the bound allows one fp32 ulp
+ * per step, sound for nearest and for truncation, plus 128 * 2^-23 of each step's largest product.  Measured on an MI355X: with
+ * E2M3 codes (what the W6A6 path feeds both kernels) every output is inside the bound and equals a model with one rounding
+ * per step; E2M3 partial sums are exact below 2^18 (K >= 4661 with near-extreme codes of one sign to leave
+ * that range).  With E3M2 or full-range E4M3 codes the matrix core's 128-term dot loses more than that (up to 5.3 times the
+ * bound, already at k = 128): the bound does not hold for those codes (tests/test_gpu_gemm.py holds them to 8 times it). */
 int fpq_gemm_fp8_rows(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,
                       const void* w_scales, int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs,
                       int64_t k, fpq_stream_t stream);

@@ -12,6 +12,7 @@ import torch
 from fpqvar_amd import _lib
 from oracle import fpq_oracle as orc
 from tests import attention_model as am
+from tests import gemm_model as gm
 from tests.conftest import assert_bits_equal, from_bits
 
 pytestmark = pytest.mark.gpu
@@ -1347,11 +1348,13 @@ def test_fp4_gemm(dev, T, O, K):
     err = (y.double() - ref).abs()
     tol = 2.0 ** -10 * ref.abs() + 1e-5 * (a64.abs() @ w64.abs().t()) + 1e-6     # fp16 output rounding + fp32 accumulation
     assert bool((err <= tol).all()), float((err / tol).max())
+    assert gm.ratio(y, gm.reference("fp4", ac, asc, wc, wsc, bias)) <= 1.0      # the derived bound (tests/gemm_model.py)
     # and the reference's own path: fp16 GEMM on the fake-quantized tensors (tr/quant_utils.py:765-767)
     wq16 = qu.fp_quant_e2_per_group_cuda(w, 4, 128).half()
     y_ref = torch.nn.functional.linear(qu.fp_quant_e2_per_group_cuda(x, 4, 128), wq16, bias)
     torch.testing.assert_close(y.float(), y_ref.float(), rtol=2e-2, atol=2e-2 * float(ref.abs().mean()))
     assert gemm.linear_fp4(ac, asc, wc, wsc.half(), None).shape == (T, O)        # fp16 weight scales, no bias
+    assert gm.ratio(gemm.linear_fp4(ac, asc, wc, wsc.half(), None), gm.reference("fp4", ac, asc, wc, wsc.half(), None)) <= 1.0
 
 
 @pytest.mark.parametrize("T,O,K", ((300, 392, 1920), (16384, 8192, 128)))
@@ -1437,6 +1440,7 @@ def test_row_scaled_gemm_tile_configurations_agree(dev, kind, T, O, K, lib_optio
     err = (base[0].double() - ref).abs()
     tol = 2.0 ** -10 * ref.abs() + 1e-5 * (a64.abs() @ w64.abs().t()) + 1e-6     # fp16 output rounding + fp32 accumulation
     assert bool((err <= tol).all()), float((err / tol).max())
+    assert gm.ratio(base[0], gm.reference(kind, *a, *wq, bias)) <= 1.0           # the derived bound (tests/gemm_model.py)
 
 
 @pytest.mark.parametrize("kind", ("fp4", "fp6", "fp8"))
@@ -1468,6 +1472,8 @@ def test_gemm_full_size_row_and_column_permutations(dev, kind):
     err = (y[rows][:, cols].double() - ref).abs()
     tol = 2.0 ** -10 * ref.abs() + 1e-5 * (a64.abs() @ w64.abs().t()) + 1e-6
     assert bool((err <= tol).all()), float((err / tol).max())
+    r = gm.reference(kind, ac[rows].contiguous(), asc[rows].contiguous(), wc[cols].contiguous(), wsc[cols].contiguous(), bias[cols])
+    assert gm.ratio(y[rows][:, cols], r) <= 1.0                                  # the derived bound (tests/gemm_model.py)
 
 
 def test_fp4_linear_module(dev, golden):
@@ -1828,6 +1834,7 @@ def test_fp8_gemm(dev, T, O, K):
     err = (y.double() - ref).abs()
     tol = 2.0 ** -10 * ref.abs() + 1e-5 * (a64.abs() @ w64.abs().t()) + 1e-6     # fp16 output rounding + fp32 accumulation
     assert bool((err <= tol).all()), float((err / tol).max())
+    assert gm.ratio(y, gm.reference("fp8", ac, asc, wc, wsc, bias)) <= 1.0      # the derived bound (tests/gemm_model.py)
     # against the reference's formulation: fake-quantized fp16 tensors through an fp16 GEMM
     import fpqvar_amd.quant_utils as qu
     ref16 = torch.nn.functional.linear(qu.fp6_quant_e2m3_per_token_cuda(x, 6), qu.fp6_quant_e2m3_per_token_cuda(w, 6), bias)
@@ -1888,6 +1895,7 @@ def test_fp6_gemm(dev, T, O, K):
     err = (y.double() - ref).abs()
     tol = 2.0 ** -10 * ref.abs() + 1e-5 * (a64.abs() @ w64.abs().t()) + 1e-6
     assert bool((err <= tol).all()), float((err / tol).max())
+    assert gm.ratio(y, gm.reference("fp6", ac, asc, wc, wsc, bias)) <= 1.0      # the derived bound (tests/gemm_model.py)
     assert float((y.float() - y8.float()).abs().max()) <= 2.0 ** -9 * float(y8.float().abs().max()) + 1e-4
 
 
