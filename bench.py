@@ -6,7 +6,12 @@ fp16 [65536 x 1920] activation tensor, group 128.  One "step" = one pass of the
 fused kernel over that tensor (one call of fp_quant_e2_per_group_cuda's HIP
 replacement through the C ABI), input and output resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--skip LEGS]]
+
+A plain run does what the headline needs and nothing else: it sets up the hot path, warms up, times the K steps, writes
+--dump-outputs and prints the line.  --full then goes on to the secondary measurements, after the timed region (about 50 s
+on one GPU): weight calibration, the sharded format search, the generation batches, and at N = 1 the unfused GPU sequence,
+the other kernels, the ten scale steps of configs 3 / 5 and the CPU baseline.
 
 N > 1: one rank per GPU over RCCL.  Either the caller starts the ranks
 (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`: WORLD_SIZE is set), or
@@ -16,8 +21,8 @@ from --gpus refuses to run.  The path is embarrassingly parallel over 128-elemen
 its own [65536 x 1920] shards with no data-path collective ("scaling": "weak"); the only collectives of the timed
 region are the barrier and the MAX over ranks of the elapsed time.
 
-Prints ONE JSON line (rank 0).  Exit code 0 only when every part ran; a collective that blocks in the secondary
-(weight calibration) measurement is reported in the line AND by exit code 3.
+Prints ONE JSON line (rank 0).  Exit code 0 only when every part ran; a collective that blocks in a secondary
+measurement of --full (weight calibration, say) is reported in the line AND by exit code 3.
 """
 import argparse
 import json
@@ -49,8 +54,11 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--skip", default="", help="comma-separated secondary legs to leave out (profiling aid): "
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the secondary measurements (see the module docstring); off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave out the N = 1 legs (unfused GPU sequence, other kernels, scale steps, CPU baseline)")
+    ap.add_argument("--skip", default="", help="with --full: comma-separated secondary legs to leave out (profiling aid): "
                                                "calibration,generation,format_search,other_kernels,steps")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (rank 0) to DIR/*.npy (see dump_outputs)")
@@ -1164,6 +1172,14 @@ def main(argv=None, script=None, platform_factory=GpuPlatform):
 
     def headline(calib):
         return build_result(args, world, elems, elapsed, kernel_ms, calib, rccl_ranks, plat.data)
+
+    if not args.full:             # a plain run: the headline line and nothing more
+        stage.done.set()
+        if rank == 0:
+            print(json.dumps(headline(None)), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     partial[0] = headline
     skip = set(filter(None, args.skip.split(",")))

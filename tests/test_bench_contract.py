@@ -80,7 +80,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo():
     and the MAX over ranks, the sharded calibration's slab with its in-place all-gather on device memory, the codes
     exchange with its two segment launches; the line says that it is a rehearsal, its numbers are no scaling curve."""
     env = dict(os.environ, FPQ_BENCH_SHARE_GPU="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-1500:])
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -200,7 +200,7 @@ def _rehearse(tmp_path, args, env_extra=None, timeout=300):
 
 
 def test_bench_gpus2_launches_two_ranks_gloo(tmp_path):
-    out = _rehearse(tmp_path, ["--gpus", "2", "--steps", "3", "--warmup", "1"])
+    out = _rehearse(tmp_path, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"])
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -236,7 +236,7 @@ def test_bench_gpus2_launches_two_ranks_gloo(tmp_path):
 def test_bench_gpus8_launches_eight_ranks_gloo(tmp_path):
     """The driver's largest case, rehearsed on CPU: eight ranks, more ranks than the rehearsal's model has layers (some own
     nothing), one line from rank 0."""
-    out = _rehearse(tmp_path, ["--gpus", "8", "--steps", "2", "--warmup", "1"], timeout=600)
+    out = _rehearse(tmp_path, ["--gpus", "8", "--steps", "2", "--warmup", "1", "--full"], timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -251,6 +251,22 @@ def test_bench_gpus8_launches_eight_ranks_gloo(tmp_path):
     assert len(gen) == 6 and all(g["replicas_ok"] == 8 and abs(g["ms_per_batch"] - 17.0) < 1e-6 for g in gen)
 
 
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_is_the_headline_alone(tmp_path, gpus):
+    """Without --full a run sets up, warms up, times the steps and prints the line: no secondary leg runs, neither the N = 1
+    ones (CPU baseline, other kernels, scale steps) nor those at every N (calibration, search, generation)."""
+    out = _rehearse(tmp_path, ["--gpus", str(gpus), "--steps", "3", "--warmup", "1"], timeout=120)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["n_gpus"] == gpus and res["steps"] == 3 and res["warmup"] == 1 and res["value"] > 0 and res["ms_per_step"] > 0
+    assert res["unit"] == "Gelem/s" and res["higher_is_better"] is True and res["dtype"] == "f16" and "roofline" in res
+    secondary = {"weight_calibration", "format_search_sharded", "generation", "unfused_gpu", "other_kernels", "config3_steps",
+                 "config5_steps", "cpu_baseline", "omitted_at_n_gt_1"}
+    assert not secondary & set(res), sorted(secondary & set(res))
+
+
 def test_bench_refuses_a_world_size_that_is_not_gpus(tmp_path):
     out = _rehearse(tmp_path, ["--gpus", "2", "--steps", "1", "--warmup", "0"],
                     {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
@@ -261,7 +277,7 @@ def test_bench_refuses_a_world_size_that_is_not_gpus(tmp_path):
 
 def test_bench_reports_a_blocked_collective_as_failure(tmp_path):
     """A rank that never reaches the all-gather: the line carries the error and the exit code is non-zero."""
-    out = _rehearse(tmp_path, ["--gpus", "2", "--steps", "2", "--warmup", "0"],
+    out = _rehearse(tmp_path, ["--gpus", "2", "--steps", "2", "--warmup", "0", "--full"],
                     {"REHEARSAL_HANG": "1", "REHEARSAL_WATCHDOG_S": "8"}, timeout=240)
     assert out.returncode == 3                 # bench.EXIT_COLLECTIVE_TIMEOUT, restored by the launcher from the line
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -34,16 +34,16 @@ elif [ "$1" = steps ]; then
   done
 else
   # the bench command itself: the line, the same command under --kernel-trace --stats, and the two traffic passes
-  python3 bench.py > $out/bench_n1.json 2> $out/bench_n1.log
+  python3 bench.py --full > $out/bench_n1.json 2> $out/bench_n1.log
   echo "bench ok"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_kt -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --skip generation,format_search,steps > $out/bench_under_rocprof.json 2> $out/bench_kt.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_kt -- python3 bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --skip generation,format_search,steps > $out/bench_under_rocprof.json 2> $out/bench_kt.log
   find $out/bench_kt -name "*kernel_stats.csv" -exec cp {} $out/bench_kernel_stats_full.csv \;
-  { echo "$stampline"; echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --skip generation,format_search,steps (this library's kernels only)"
+  { echo "$stampline"; echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --skip generation,format_search,steps (this library's kernels only)"
     grep -E "^\"Name\"|^\"_ZN12_GLOBAL__N_|^\"void \(anonymous namespace\)::" $out/bench_kernel_stats_full.csv | sed -E 's/^"(_ZN12_GLOBAL__N_[0-9]*[a-z_0-9]*)[^"]*"/"\1"/; s/^"void \(anonymous namespace\)::([a-z_0-9]*<[^>]*>)[^"]*"/"\1"/'; } > $out/bench_kernel_stats.csv
   rm -rf $out/bench_kt $out/bench_kernel_stats_full.csv
   echo "bench kernel trace ok"
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/bench_f -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --skip generation,format_search,steps,other_kernels > /dev/null 2> $out/bench_f.log
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/bench_w -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --skip generation,format_search,steps,other_kernels > /dev/null 2> $out/bench_w.log
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/bench_f -- python3 bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --skip generation,format_search,steps,other_kernels > /dev/null 2> $out/bench_f.log
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/bench_w -- python3 bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --skip generation,format_search,steps,other_kernels > /dev/null 2> $out/bench_w.log
   { echo "$stampline"; python3 tools/pmc_summary.py $out/bench_f rows16_lut_subwave; python3 tools/pmc_summary.py $out/bench_f groups32; } > $out/bench_fetch.txt
   { echo "$stampline"; python3 tools/pmc_summary.py $out/bench_w rows16_lut_subwave; python3 tools/pmc_summary.py $out/bench_w groups32; } > $out/bench_write.txt
   rm -rf $out/bench_f $out/bench_w
