@@ -37,7 +37,28 @@ struct AttnArgs {
 constexpr int kAttnKv = 64;          // keys per staged tile
 constexpr int kAttnTile = kAttnKv * 128;   // bytes of one K (or V) tile
 
-__global__ __launch_bounds__(256, 3) void attn_fwd64_kernel(AttnArgs a) {
+// K / V sources of the kernel body: where the 16-byte chunk ch (channels 8 ch .. 8 ch + 7) of key row kv comes from.  fetch()
+// issues the global loads of a tile's chunks, stage() turns what they returned into the fp16 chunk the LDS image holds - between
+// the two sits a whole iteration, so a decode in stage() is off the loads' latency path.  Everything else (tiles, LDS images,
+// swizzles, the matrix-core part) is the body's own and the same for every source.
+
+// fp16 rows [B, lkv, H, 64] at AttnArgs' pitches (fpq_attention_blhc)
+struct AttnFp16Src {
+  typedef AttnArgs Args;
+  const uint16_t* kbase;
+  const uint16_t* vbase;
+  int64_t token;
+  __device__ __forceinline__ AttnFp16Src(const AttnArgs& a, int b, int h)
+      : kbase(a.k + (int64_t)b * a.kv_batch + h * 64), vbase(a.v + (int64_t)b * a.kv_batch + h * 64), token(a.kv_token) {}
+  __device__ __forceinline__ void fetch(int kv, int ch, u32x4& gk, u32x4& gv) const {
+    gk = *(const u32x4*)(kbase + (int64_t)kv * token + 8 * ch);
+    gv = *(const u32x4*)(vbase + (int64_t)kv * token + 8 * ch);
+  }
+  __device__ __forceinline__ u32x4 stage(const u32x4& g, int, int) const { return g; }
+};
+
+template <class Src>
+__global__ __launch_bounds__(256, 3) void attn_fwd64_kernel(typename Src::Args a) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[4 * kAttnTile];   // [buffer][K | V]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // all query tiles of one (batch, head) on one XCD, next to each other in dispatch order
@@ -61,8 +82,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd64_kernel(AttnArgs a) {
   }
 
   // staging: thread -> (row, 16-byte chunk) of the K and of the V tile, two of each
-  const uint16_t* kbase = a.k + (int64_t)b * a.kv_batch + h * 64;
-  const uint16_t* vbase = a.v + (int64_t)b * a.kv_batch + h * 64;
+  const Src src(a, b, h);
   int st_row[2], st_koff[2], st_voff[2], st_ch[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -79,16 +99,17 @@ __global__ __launch_bounds__(256, 3) void attn_fwd64_kernel(AttnArgs a) {
   _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                  \
     int kv_ = (t) * kAttnKv + st_row[i_];                                                             \
     kv_ = kv_ < a.lkv ? kv_ : a.lkv - 1;                                                              \
-    GK[i_] = *(const u32x4*)(kbase + (int64_t)kv_ * a.kv_token + 8 * st_ch[i_]);                     \
-    GV[i_] = *(const u32x4*)(vbase + (int64_t)kv_ * a.kv_token + 8 * st_ch[i_]);                     \
+    src.fetch(kv_, st_ch[i_], GK[i_], GV[i_]);                                                        \
   }
-#define FPQ_ATTN_STAGE(buf, GK, GV)                                                                   \
+#define FPQ_ATTN_STAGE(buf, t, GK, GV)                                                                \
   _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                  \
-    *(u32x4*)(smem + (buf) * 2 * kAttnTile + st_koff[i_]) = GK[i_];                                   \
-    *(u32x4*)(smem + (buf) * 2 * kAttnTile + kAttnTile + st_voff[i_]) = GV[i_];                       \
+    int kv_ = (t) * kAttnKv + st_row[i_];                                                             \
+    kv_ = kv_ < a.lkv ? kv_ : a.lkv - 1;                 /* the row FETCH read */                     \
+    *(u32x4*)(smem + (buf) * 2 * kAttnTile + st_koff[i_]) = src.stage(GK[i_], kv_, st_ch[i_]);        \
+    *(u32x4*)(smem + (buf) * 2 * kAttnTile + kAttnTile + st_voff[i_]) = src.stage(GV[i_], kv_, st_ch[i_]); \
   }
   FPQ_ATTN_FETCH(0, gk, gv);
-  FPQ_ATTN_STAGE(0, gk, gv);
+  FPQ_ATTN_STAGE(0, 0, gk, gv);
   // Everything issued so far (the Q fragments too) has to have landed before the loop: otherwise the compiler, not
   // knowing how many prefetches are in flight on each path, waits for vmcnt(0) in front of the loop's first MFMAs -
   // i.e. for the prefetch it has just issued - in every iteration.
@@ -191,7 +212,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd64_kernel(AttnArgs a) {
           o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(attn_h8_t, both), pf[u][sst], o[dt], 0, 0, 0);
         }
     }
-    if (more) { FPQ_ATTN_STAGE((t + 1) & 1, gk1, gv1); }
+    if (more) { FPQ_ATTN_STAGE((t + 1) & 1, t + 1, gk1, gv1); }
   };
   for (int t = 0; t < n_tiles; t += 2) {
     iter(t, gk, gv, gk2, gv2);
@@ -216,3 +237,90 @@ __global__ __launch_bounds__(256, 3) void attn_fwd64_kernel(AttnArgs a) {
       }
   }
 }
+
+// ---------------------------------------------------------------------------------
+// The same kernel over a packed KV cache (include/fpq.h, fpq_attention_blhc_kvcodes): keys [0, n_packed) come as codes + fp16
+// scales out of the packed slabs, keys [n_packed, lkv) as fp16 rows at AttnArgs' k / v pointers and pitches (the step's own
+// entries, which attention sees unquantized).  A packed chunk is decoded in stage() to exactly the fp16 value the fake-quantizing
+// cache holds, (half)(level * scale): the level's bits are placed in an fp16 pattern that is level * 2^-14 (sign to bit 15, the
+// E2M3 / E2M1 exponent and mantissa bits to the low end of the fp16 exponent field and the top of the mantissa - a zero
+// exponent field is a subnormal m / 8 (m / 2) in both formats), an fp16 multiply by 2^14 makes that the level exactly, and one
+// fp16 multiply by the scale rounds level * scale once - the same v_pk_mul_f16 the quantizers apply to the same two numbers
+// (quant_vec16), so the decoded cache is bit-identical to the fake-quantized one, ±0 and subnormal scales included.
+// ---------------------------------------------------------------------------------
+struct AttnCodesArgs : AttnArgs {     // AttnArgs' k / v / kv_batch / kv_token describe the fresh rows
+  const uint8_t* codes;               // [2, B, max_len, H, row_bytes]: the K slab, then the V slab
+  const uint16_t* scales;             // [2, B, max_len, H] (E2M3) or [2, B, max_len, H / 2] (E2M1)
+  int64_t codes_slab, scales_slab;    // bytes / scales of one slab: the V slab's offset
+  int64_t max_len;
+  int n_packed;
+};
+
+typedef _Float16 attn_h2_t __attribute__((ext_vector_type(2)));
+
+// eight 6-bit (E2M3) or 4-bit (E2M1) codes of 8 consecutive channels -> their levels * scale as fp16 (channel 2j in the low half
+// of word j)
+template <int BITS>
+__device__ __forceinline__ u32x4 attn_decode8(uint64_t p, uint32_t scale16) {
+  const attn_h2_t two14 = {(_Float16)16384.0f, (_Float16)16384.0f};
+  const attn_h2_t sc = __builtin_bit_cast(attn_h2_t, scale16 | (scale16 << 16));
+  u32x4 o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    uint32_t w;   // the codes of channels 2j (bits 0..) and 2j + 1 (bits 16..)
+    if constexpr (BITS == 6) {
+      const uint32_t x = (uint32_t)(p >> (12 * j));
+      w = (x & 0x3Fu) | ((x << 10) & 0x3F0000u);
+      w = ((w & 0x00200020u) << 10) | ((w & 0x001F001Fu) << 7);
+    } else {
+      const uint32_t x = (uint32_t)(p >> (8 * j));
+      w = (x & 0xFu) | ((x << 12) & 0xF0000u);
+      w = ((w & 0x00080008u) << 12) | ((w & 0x00070007u) << 9);
+    }
+    o[j] = __builtin_bit_cast(uint32_t, (__builtin_bit_cast(attn_h2_t, w) * two14) * sc);
+  }
+  return o;
+}
+
+template <int BITS>
+struct AttnCodesSrc {
+  typedef AttnCodesArgs Args;
+  static constexpr int kRowBytes = BITS == 6 ? 48 : 32;   // 64 channels
+  const uint8_t* kc;                  // codes of (b, token 0, h) in the K slab
+  const uint16_t* ks;                 // its scale
+  int64_t c_token, s_token, c_slab, s_slab;
+  const uint16_t* kbase;
+  const uint16_t* vbase;
+  int64_t token;
+  int n_packed;
+  __device__ __forceinline__ AttnCodesSrc(const AttnCodesArgs& a, int b, int h)
+      : kc(a.codes + ((int64_t)b * a.max_len * a.heads + h) * kRowBytes),
+        ks(a.scales + (BITS == 6 ? (int64_t)b * a.max_len * a.heads + h : (int64_t)b * a.max_len * (a.heads >> 1) + (h >> 1))),
+        c_token((int64_t)a.heads * kRowBytes), s_token(BITS == 6 ? a.heads : a.heads >> 1), c_slab(a.codes_slab), s_slab(a.scales_slab),
+        kbase(a.k + (int64_t)b * a.kv_batch + h * 64), vbase(a.v + (int64_t)b * a.kv_batch + h * 64), token(a.kv_token),
+        n_packed(a.n_packed) {}
+  // packed row: the dwords holding the chunk's codes in [0], [1] (E2M3: 6 bytes at 6 ch, read as the aligned 8 bytes at 6 ch & ~3;
+  // E2M1: 4 bytes at 4 ch), the scale in [2]
+  __device__ __forceinline__ void fetch(int kv, int ch, u32x4& gk, u32x4& gv) const {
+    if (kv < n_packed) {
+      const uint8_t* p = kc + (int64_t)kv * c_token + (BITS == 6 ? ((6 * ch) & ~3) : 4 * ch);
+      const uint16_t* s = ks + (int64_t)kv * s_token;
+      if constexpr (BITS == 6) {
+        const u32x2 wk = *(const u32x2*)p, wv = *(const u32x2*)(p + c_slab);
+        gk = u32x4{wk[0], wk[1], s[0], 0u};
+        gv = u32x4{wv[0], wv[1], s[s_slab], 0u};
+      } else {
+        gk = u32x4{*(const uint32_t*)p, 0u, s[0], 0u};
+        gv = u32x4{*(const uint32_t*)(p + c_slab), 0u, s[s_slab], 0u};
+      }
+    } else {
+      gk = *(const u32x4*)(kbase + (int64_t)(kv - n_packed) * token + 8 * ch);
+      gv = *(const u32x4*)(vbase + (int64_t)(kv - n_packed) * token + 8 * ch);
+    }
+  }
+  __device__ __forceinline__ u32x4 stage(const u32x4& g, int kv, int ch) const {
+    if (kv >= n_packed) return g;
+    const uint64_t p = ((uint64_t)g[1] << 32 | g[0]) >> (BITS == 6 ? 16 * (ch & 1) : 0);
+    return attn_decode8<BITS>(p, g[2]);
+  }
+};

@@ -56,7 +56,55 @@ int fpq_attention_blhc(const void* q, const void* k, const void* v, void* out, i
   const int64_t groups = (batch * heads + 7) / 8;
   const int64_t n_wg = groups * a.q_tiles * 8;
   if (n_wg > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
-  hipLaunchKernelGGL(attn_fwd64_kernel, dim3((unsigned)n_wg), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(attn_fwd64_kernel<AttnFp16Src>, dim3((unsigned)n_wg), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch();
+}
+
+int fpq_attention_blhc_kvcodes(const void* q, const uint8_t* codes, const void* scales, int kv_bit, int64_t max_len, int64_t n_packed,
+                               const void* new_k, const void* new_v, int64_t new_batch_pitch, int64_t new_token_pitch, int64_t n_new,
+                               void* out, int64_t batch, int64_t lq, int64_t heads, int64_t head_dim, int64_t q_batch_pitch,
+                               int64_t q_token_pitch, float scale, fpq_stream_t stream) {
+  if (batch < 0 || lq < 0 || heads <= 0 || max_len < 0 || n_packed < 0 || n_new < 0 || head_dim != 64) return FPQ_ERR_ARG;
+  if ((kv_bit != 6 && kv_bit != 4) || (kv_bit == 4 && heads % 2 != 0) || n_packed > max_len) return FPQ_ERR_ARG;
+  if (batch == 0 || lq == 0) return FPQ_OK;
+  const int64_t lkv = n_packed + n_new;
+  if (lkv == 0 || !(scale > 0.0f) || !q || !out) return FPQ_ERR_ARG;
+  if (n_packed > 0 && (!codes || !scales)) return FPQ_ERR_ARG;
+  if (n_new > 0 && (!new_k || !new_v)) return FPQ_ERR_ARG;
+  if ((((uintptr_t)q | (uintptr_t)out | (uintptr_t)new_k | (uintptr_t)new_v | (uintptr_t)codes | (uintptr_t)scales) & 15) != 0)
+    return FPQ_ERR_ARG;
+  if (q_batch_pitch % 8 != 0 || q_token_pitch % 8 != 0 || new_batch_pitch % 8 != 0 || new_token_pitch % 8 != 0 ||
+      q_batch_pitch < 0 || q_token_pitch < 0 || new_batch_pitch < 0 || new_token_pitch < 0)
+    return FPQ_ERR_ARG;
+  if (lq > 0x7FFFFFFF || lkv > 0x7FFFFFFF || batch * heads > 0x7FFFFFFF) return FPQ_ERR_ARG;
+  AttnCodesArgs a;
+  a.q = (const uint16_t*)q;
+  a.k = (const uint16_t*)new_k;
+  a.v = (const uint16_t*)new_v;
+  a.out = (uint16_t*)out;
+  a.q_batch = q_batch_pitch;
+  a.q_token = q_token_pitch;
+  a.kv_batch = new_batch_pitch;
+  a.kv_token = new_token_pitch;
+  a.batch = (int)batch;
+  a.heads = (int)heads;
+  a.lq = (int)lq;
+  a.lkv = (int)lkv;
+  a.q_tiles = (int)((lq + 127) / 128);
+  a.scale_log2e = scale * 1.4426950408889634f;
+  a.codes = codes;
+  a.scales = (const uint16_t*)scales;
+  a.codes_slab = batch * max_len * heads * (kv_bit == 6 ? 48 : 32);
+  a.scales_slab = batch * max_len * (kv_bit == 6 ? heads : heads / 2);
+  a.max_len = max_len;
+  a.n_packed = (int)n_packed;
+  const int64_t groups = (batch * heads + 7) / 8;
+  const int64_t n_wg = groups * a.q_tiles * 8;
+  if (n_wg > 0x7FFFFFFF) return FPQ_ERR_ARG;
+  if (kv_bit == 6)
+    hipLaunchKernelGGL(attn_fwd64_kernel<AttnCodesSrc<6>>, dim3((unsigned)n_wg), dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(attn_fwd64_kernel<AttnCodesSrc<4>>, dim3((unsigned)n_wg), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch();
 }
 

@@ -405,6 +405,7 @@ __global__ __launch_bounds__(kBlock) void rows_negrev_scalar_kernel(const T* __r
 #include "fpq_codes_mx.h"    // the operand-emitting quantizers of the matrix-core GEMMs (the GEMM kernels themselves,
 #include "fpq_codes_fp8.h"   // fpq_gemm_fp4.h / fp8.h / fp6.h, are compiled in fpq_gemm.hip only: an edit there does not
 #include "fpq_codes_fp6.h"   // rebuild this translation unit)
+#include "fpq_kv_codes.h"    // the packed KV cache's producer (fpq_kv_pack; its consumer is the attention kernel, fpq_gemm.hip)
 
 // ---------------------------------------------------------------------------------
 // L0: literal scan (quant/quant_kernel.cu:25-37), any table of k <= 256 floats.
@@ -2224,6 +2225,41 @@ int fpq_quant_rows_codes_fp6(const void* x, uint8_t* codes, void* scales, int64_
 int fpq_quant_rows_codes_fp6_km(const void* x, uint8_t* image, void* scales, int64_t rows, int64_t cols, int table_id,
                                 int in_dtype, fpq_stream_t stream) {
   return quant_rows_codes_fp6_impl(x, image, scales, rows, cols, table_id, in_dtype, true, stream);
+}
+
+int fpq_kv_pack(uint8_t* codes, void* scales, int kv_bit, int64_t batch, int64_t max_len, int64_t heads, int64_t head_dim, int64_t pos,
+                const void* new_k, const void* new_v, int64_t new_batch_pitch, int64_t new_token_pitch, int64_t n_new,
+                fpq_stream_t stream) {
+  if (batch < 0 || max_len < 0 || heads <= 0 || head_dim != 64 || pos < 0 || n_new < 0 || pos + n_new > max_len) return FPQ_ERR_ARG;
+  if ((kv_bit != 6 && kv_bit != 4) || (kv_bit == 4 && heads % 2 != 0) || batch > 65535 || heads > (1 << 20)) return FPQ_ERR_ARG;
+  if (new_batch_pitch % 8 != 0 || new_token_pitch % 8 != 0 || new_batch_pitch < 0 || new_token_pitch < 0) return FPQ_ERR_ARG;
+  if (batch == 0 || n_new == 0) return FPQ_OK;
+  if (!codes || !scales || !new_k || !new_v) return FPQ_ERR_ARG;
+  if ((((uintptr_t)codes | (uintptr_t)scales | (uintptr_t)new_k | (uintptr_t)new_v) & 15) != 0) return FPQ_ERR_ARG;
+  const int table_id = kv_bit == 6 ? FPQ_E2M3 : FPQ_E2M1;
+  const Lut16Host& h = lut16_host(table_id, table_id);
+  if (!h.tab_valid) return FPQ_ERR_TABLE;
+  constexpr int U = 2;
+  KvPackArgs k;
+  k.src[0] = (const uint16_t*)new_k;
+  k.src[1] = (const uint16_t*)new_v;
+  k.src_batch_pitch = new_batch_pitch;
+  k.src_token_pitch = new_token_pitch;
+  k.codes = codes;
+  k.scales = (uint16_t*)scales;
+  k.codes_slab = batch * max_len * heads * (kv_bit == 6 ? 48 : 32);
+  k.scales_slab = batch * max_len * (kv_bit == 6 ? heads : heads / 2);
+  k.max_len = max_len;
+  k.pos = pos;
+  k.row_vec = (int)(heads * 8);
+  k.new_vecs = n_new * k.row_vec;
+  const int64_t tiles = (k.new_vecs + kBlock * U - 1) / (kBlock * U);
+  if (tiles > 0x7FFFFFFF) return FPQ_ERR_ARG;
+  const dim3 grid((unsigned)tiles, (unsigned)batch, 2);
+  hipStream_t st = (hipStream_t)stream;
+  if (kv_bit == 6) hipLaunchKernelGGL((kv_pack_kernel<6, U>), grid, dim3(kBlock), 0, st, k, h.args, lut16_codes6_e2m3());
+  else hipLaunchKernelGGL((kv_pack_kernel<4, U>), grid, dim3(kBlock), 0, st, k, h.args, lut16_mx_codes_e2m1());
+  return check_launch();
 }
 
 int fpq_absmax(const void* x, int64_t n, int dtype, void* out, fpq_stream_t stream) {

@@ -158,3 +158,119 @@ class IncrementalKVCache:
         self._prev = self.len
         self.len += n
         return qn, self.k[:, :self.len], self.v[:, :self.len]
+
+
+def _e2m3_levels() -> torch.Tensor:
+    """The 64 OCP E2M3 codes' values (sign bit 5, exponent bits 4..3, mantissa bits 2..0), fp32."""
+    c = torch.arange(64)
+    e, m = (c >> 3) & 3, (c & 7).float()
+    mag = torch.where(e == 0, m / 8, (1 + m / 8) * torch.exp2((e - 1).float()))
+    return torch.where(c >= 32, -mag, mag)
+
+
+def _e2m1_levels() -> torch.Tensor:
+    """The 16 OCP E2M1 codes' values (sign bit 3, exponent bits 2..1, mantissa bit 0), fp32."""
+    c = torch.arange(16)
+    e, m = (c >> 1) & 3, (c & 1).float()
+    mag = torch.where(e == 0, m / 2, (1 + m / 2) * torch.exp2((e - 1).float()))
+    return torch.where(c >= 8, -mag, mag)
+
+
+class PackedKVCache:
+    """The KV cache of IncrementalKVCache stored as what it holds: quantization codes + fp16 scales (include/fpq.h, "the packed
+    KV cache") - 50 bytes per (token, head) row of 64 with kv_bit 6 (E2M3 codes, one scale per row), 33 with kv_bit 4 (E2M1
+    nibbles, one scale per 128 elements = two heads), against 128 in fp16.
+
+    A step is two launches (`attend`): attention over the packed entries [0, len) followed by the fresh fp16 k / v of the step
+    (fpq_attention_blhc_kvcodes: the reference attends to the new k / v unquantized), then the pack of k / v into slots
+    [len, len + L) (fpq_kv_pack: the quantization IncrementalKVCache applies to them at the next step).  Every attention output
+    is bit for bit `ops.attention_blhc(q, *IncrementalKVCache.append(k, v), scale)`.
+
+    `staging`: an fp16 [2, B, max_step, H, 64] slab that producers write a step's k / v into (gemm.linear_fp4_qkv_to_cache(...,
+    staging, 0, L); `stage_qk_norm`) before `attend_staged` - one slab serves every block's cache, since a block's fresh entries
+    are packed before the next block runs (new_staging).
+    """
+
+    def __init__(self, batch: int, max_len: int, heads: int, head_dim: int = 64, kv_bit: int = 6, device="cuda",
+                 staging: Optional[torch.Tensor] = None):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"PackedKVCache: expected a GPU device, got {dev} (fpqvar_amd has no CPU path)")
+        if head_dim != 64:
+            raise RuntimeError(f"PackedKVCache: head_dim must be 64, got {head_dim}")
+        if kv_bit not in (4, 6) or (kv_bit == 4 and heads % 2):
+            raise RuntimeError(f"PackedKVCache: kv_bit 6, or kv_bit 4 with an even number of heads (H * 64 % 128 == 0); got {kv_bit}, H = {heads}")
+        if staging is not None and (staging.dtype != torch.float16 or staging.dim() != 5 or staging.shape[0] != 2 or staging.shape[1] != batch
+                                    or tuple(staging.shape[3:]) != (heads, head_dim) or not staging.is_contiguous() or staging.device != dev):
+            raise RuntimeError(f"PackedKVCache: staging must be a contiguous float16 [2, {batch}, max_step, {heads}, {head_dim}] tensor on {dev}")
+        self.kv_bit, self.batch, self.max_len, self.heads = kv_bit, batch, max_len, heads
+        self.codes = torch.empty(2, batch, max_len, heads, 48 if kv_bit == 6 else 32, dtype=torch.uint8, device=dev)
+        self.scales = torch.empty(2, batch, max_len, heads if kv_bit == 6 else heads // 2, dtype=torch.float16, device=dev)
+        self.staging = staging
+        self.len = 0
+
+    @staticmethod
+    def new_staging(batch: int, max_step: int, heads: int, head_dim: int = 64, device="cuda") -> torch.Tensor:
+        """The fp16 [2, B, max_step, H, 64] slab a model's caches share (`staging=`)."""
+        return torch.empty(2, batch, max_step, heads, head_dim, dtype=torch.float16, device=device)
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the packed slabs (codes + scales; a shared staging slab is not counted)."""
+        return self.codes.numel() + 2 * self.scales.numel()
+
+    @torch.no_grad()
+    def attend(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float) -> torch.Tensor:
+        """softmax(q K^T * scale) V over the packed entries and the fresh k / v [B, L, H, 64] (views of a fused qkv output are
+        fine), then k / v packed into slots [len, len + L): out fp16 [B, L, H, 64]."""
+        n = k.shape[1]
+        if self.len + n > self.max_len:
+            raise RuntimeError("PackedKVCache: max_len exceeded")
+        out = ops.attention_blhc_kvcodes(q, self.codes, self.scales, self.kv_bit, self.len, k, v, scale)
+        ops.kv_pack(self.codes, self.scales, self.kv_bit, self.len, k, v)
+        self.len += n
+        return out
+
+    def staged(self, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The views [B, n, H, 64] of the staging slab's first n tokens (k, v)."""
+        if self.staging is None:
+            raise RuntimeError("PackedKVCache: no staging slab (staging=)")
+        if n > self.staging.shape[2]:
+            raise RuntimeError(f"PackedKVCache: {n} tokens do not fit the staging slab's {self.staging.shape[2]}")
+        return self.staging[0, :, :n], self.staging[1, :, :n]
+
+    @torch.no_grad()
+    def attend_staged(self, q: torch.Tensor, n: int, scale: float) -> torch.Tensor:
+        """`attend` on the k / v a producer wrote into the staging slab's first n tokens."""
+        return self.attend(q, *self.staged(n), scale)
+
+    @torch.no_grad()
+    def stage_qk_norm(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, head_scale: torch.Tensor,
+                      bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """IncrementalKVCache.append_qk_norm's producer into the staging slab (fpq_kv_cache_step_qknorm with nothing to quantize):
+        k normalized and v (+ bias) land in the slab's first n tokens, q normalized and scaled comes back; `attend_staged` next."""
+        if self.staging is None:
+            raise RuntimeError("PackedKVCache: no staging slab (staging=)")
+        if not (q.stride() == k.stride() == v.stride()) or k.stride(3) != 1 or k.stride(2) != k.shape[3] or k.stride(0) % 8 or k.stride(1) % 8 \
+                or q.data_ptr() % 16 or k.data_ptr() % 16 or v.data_ptr() % 16:
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        return ops.kv_cache_step_qk_norm(self.staging, 0, 0, q, k, v, 0, 64, "e2m3", head_scale, bias)
+
+    @torch.no_grad()
+    def dequantize(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(K, V) fp16 [B, len, H, 64]: the packed entries decoded as include/fpq.h defines them, (half)(level * scale) - for
+        tests and debugging (torch ops, not a hot path)."""
+        B, H, n = self.batch, self.heads, self.len
+        c = self.codes[:, :, :n].to(torch.int32)
+        if self.kv_bit == 6:   # 3 bytes = 4 codes, little-endian
+            c = c.view(2, B, n, H, 16, 3)
+            w = c[..., 0] | (c[..., 1] << 8) | (c[..., 2] << 16)
+            idx = torch.stack([(w >> (6 * i)) & 63 for i in range(4)], dim=-1).view(2, B, n, H, 64)
+            lv = _e2m3_levels().to(c.device)[idx.long()]
+            sc = self.scales[:, :, :n].float().unsqueeze(-1)
+        else:                  # element 2i in the low nibble of byte i; one scale per two heads
+            idx = torch.stack([c & 15, c >> 4], dim=-1).view(2, B, n, H, 64)
+            lv = _e2m1_levels().to(c.device)[idx.long()]
+            sc = self.scales[:, :, :n].float().repeat_interleave(2, dim=3).unsqueeze(-1)
+        kv = (lv * sc).half()   # the fp32 product of a 4-bit and an 11-bit significand is exact: one rounding
+        return kv[0], kv[1]

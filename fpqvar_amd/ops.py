@@ -147,6 +147,85 @@ def attention_blhc(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: flo
     return out
 
 
+def _kv_codes_layout(codes: torch.Tensor, scales: torch.Tensor, kv_bit: int, what: str) -> Tuple[int, int, int]:
+    """(B, max_len, H) of a packed KV cache (include/fpq.h): codes uint8 [2, B, max_len, H, 48 | 32], scales fp16 [2, B, max_len,
+    H | H / 2], both contiguous on one device."""
+    if kv_bit not in (4, 6):
+        raise RuntimeError(f"{what}: kv_bit must be 4 or 6, got {kv_bit}")
+    rb = 48 if kv_bit == 6 else 32
+    if codes.dtype != torch.uint8 or codes.dim() != 5 or codes.shape[0] != 2 or codes.shape[4] != rb or not codes.is_contiguous():
+        raise RuntimeError(f"{what}: codes must be a contiguous uint8 [2, B, max_len, H, {rb}] tensor, got {codes.dtype} {tuple(codes.shape)}")
+    _, B, max_len, H, _ = codes.shape
+    want = (2, B, max_len, H if kv_bit == 6 else H // 2)
+    if kv_bit == 4 and H % 2:
+        raise RuntimeError(f"{what}: kv_bit 4 needs an even number of heads (one scale per 128 elements), got {H}")
+    if scales.dtype != torch.float16 or tuple(scales.shape) != want or not scales.is_contiguous() or scales.device != codes.device:
+        raise RuntimeError(f"{what}: scales must be a contiguous float16 {list(want)} tensor on the codes' device, got {scales.dtype} {tuple(scales.shape)}")
+    return B, max_len, H
+
+
+def _fresh_rows(k: torch.Tensor, v: torch.Tensor, B: int, H: int, what: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """k / v [B, n, H, 64] fp16 as the C ABI takes them: views kept when their (H, 64) rows are contiguous, their strides shared,
+    pitches multiples of 8 and the base 16-byte aligned; copied otherwise."""
+    if k.dtype != torch.float16 or v.dtype != torch.float16:
+        raise RuntimeError(f"{what}: k and v must be float16")
+    if k.dim() != 4 or k.shape != v.shape or k.shape[0] != B or tuple(k.shape[2:]) != (H, 64):
+        raise RuntimeError(f"{what}: k / v must be [B, n, H, 64] = [{B}, n, {H}, 64], got {tuple(k.shape)} / {tuple(v.shape)}")
+
+    def rows_ok(t):
+        return t.stride(3) == 1 and t.stride(2) == 64 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
+    if k.shape[1] and not (rows_ok(k) and rows_ok(v) and k.stride() == v.stride()):
+        k, v = k.contiguous(), v.contiguous()
+    return k, v
+
+
+def kv_pack(codes: torch.Tensor, scales: torch.Tensor, kv_bit: int, pos: int, k: torch.Tensor, v: torch.Tensor) -> None:
+    """fpq_kv_pack: quantize the fresh fp16 k / v [B, n, H, 64] (views of a fused qkv output are taken as they are) straight into
+    slots [pos, pos + n) of a packed KV cache - codes uint8 [2, B, max_len, H, 48 | 32], scales fp16 [2, B, max_len, H | H / 2]
+    (include/fpq.h) - with fpq_kv_cache_step's decisions (kv_bit 6: E2M3 per row of 64, kv_bit 4: E2M1 per 128).  One launch."""
+    require_gpu(codes, "kv_pack")
+    B, max_len, H = _kv_codes_layout(codes, scales, kv_bit, "kv_pack")
+    if k.device != codes.device or v.device != codes.device:
+        raise RuntimeError("kv_pack: k and v must be on the cache's device")
+    k, v = _fresh_rows(k, v, B, H, "kv_pack")
+    n = k.shape[1]
+    if pos < 0 or pos + n > max_len:
+        raise RuntimeError(f"kv_pack: slots [{pos}, {pos + n}) outside the cache's {max_len}")
+    with device_guard(codes.device):
+        check(lib().fpq_kv_pack(codes.data_ptr(), scales.data_ptr(), kv_bit, B, max_len, H, 64, pos, k.data_ptr(), v.data_ptr(),
+                                k.stride(0) if n else 0, k.stride(1) if n else 0, n, stream_ptr(codes.device)), "fpq_kv_pack")
+
+
+def attention_blhc_kvcodes(q: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, kv_bit: int, n_packed: int,
+                           k: torch.Tensor, v: torch.Tensor, scale: float) -> torch.Tensor:
+    """fpq_attention_blhc_kvcodes: attention_blhc(q, K, V, scale) with K / V = the decoded slots [0, n_packed) of a packed KV cache
+    (kv_pack) followed by the fresh fp16 k / v [B, n, H, 64] - bit for bit what attention_blhc returns on the fake-quantized fp16
+    cache.  q [B, Lq, H, 64] (views with contiguous (H, 64) rows are taken as they are) -> [B, Lq, H, 64]."""
+    require_gpu(q, "attention_blhc_kvcodes")
+    B, max_len, H = _kv_codes_layout(codes, scales, kv_bit, "attention_blhc_kvcodes")
+    if q.dtype != torch.float16 or q.dim() != 4 or q.shape[0] != B or tuple(q.shape[2:]) != (H, 64):
+        raise RuntimeError(f"attention_blhc_kvcodes: q must be float16 [B, Lq, H, 64] = [{B}, Lq, {H}, 64], got {q.dtype} {tuple(q.shape)}")
+    if q.device != codes.device or k.device != codes.device or v.device != codes.device:
+        raise RuntimeError("attention_blhc_kvcodes: q, k, v and the cache must share one device")
+    k, v = _fresh_rows(k, v, B, H, "attention_blhc_kvcodes")
+    n = k.shape[1]
+    if not 0 <= n_packed <= max_len:
+        raise RuntimeError(f"attention_blhc_kvcodes: n_packed {n_packed} outside [0, {max_len}]")
+    Lq = q.shape[1]
+    if n_packed + n == 0 and Lq > 0 and B > 0:
+        raise RuntimeError("attention_blhc_kvcodes: no keys")
+    if Lq and not (q.stride(3) == 1 and q.stride(2) == 64 and q.stride(0) % 8 == 0 and q.stride(1) % 8 == 0 and q.data_ptr() % 16 == 0):
+        q = q.contiguous()
+    out = torch.empty((B, Lq, H, 64), dtype=torch.float16, device=q.device)
+    with device_guard(q.device):
+        check(lib().fpq_attention_blhc_kvcodes(q.data_ptr(), codes.data_ptr(), scales.data_ptr(), kv_bit, max_len, n_packed,
+                                               k.data_ptr() if n else None, v.data_ptr() if n else None,
+                                               k.stride(0) if n else 0, k.stride(1) if n else 0, n, out.data_ptr(), B, Lq, H, 64,
+                                               q.stride(0), q.stride(1), float(scale), stream_ptr(q.device)),
+              "fpq_attention_blhc_kvcodes")
+    return out
+
+
 def kv_cache_step(cache: torch.Tensor, quant_start: int, quant_stop: int, k: torch.Tensor, v: torch.Tensor,
                   new_start: int, group: int, table: str) -> None:
     """fpq_kv_cache_step: quantize tokens [quant_start, quant_stop) of the fp16 cache [2, B, max_len, H, c] in place

@@ -109,8 +109,16 @@ class GenerationBatch:
 
     def __init__(self, model: str = "d30-256", config: str = "w4a4", depth: Optional[int] = None,
                  batch_rows: Optional[int] = None, device=None, seed: int = 0, fused_fc1: bool = True, sdpa_in_f: bool = False,
-                 kmajor: bool = True, qkv_to_cache: bool = True, attn_l2_norm: bool = False, qk_norm: str = "fused"):
+                 kmajor: bool = True, qkv_to_cache: bool = True, attn_l2_norm: bool = False, qk_norm: str = "fused",
+                 kv_storage: str = "fp16"):
         assert model in MODELS and config in ("w4a4", "w6a6") and qk_norm in ("fused", "torch")
+        if kv_storage not in ("fp16", "codes"):
+            raise ValueError(f"kv_storage must be 'fp16' or 'codes', got {kv_storage!r}")
+        if kv_storage == "codes" and sdpa_in_f:
+            raise ValueError("kv_storage='codes' attends with fpq_attention_blhc_kvcodes: not with sdpa_in_f")
+        # "codes": every block's KV cache is a PackedKVCache (FP6 codes + scales, include/fpq.h) - same results, bit for bit, as the
+        # fp16 IncrementalKVCache; paths F and Q only (path R keeps the reference's whole-cache loop)
+        self.kv_storage = kv_storage
         self.model, self.config = model, config
         heads, self.patch_nums, rows = MODELS[model]
         dev = self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -231,11 +239,40 @@ class GenerationBatch:
 
     def new_caches(self, path):
         if path == "R":
+            if self.kv_storage == "codes":
+                raise ValueError("kv_storage='codes' runs on paths F and Q; path R is the reference's own cache loop")
             return [None] * self.depth
+        if self.kv_storage == "codes":   # one staging slab for the step's fresh k / v, shared by every block's cache
+            staging = kv_cache.PackedKVCache.new_staging(self.B, max(p * p for p in self.patch_nums), self.H, self.hd, self.dev)
+            return [kv_cache.PackedKVCache(self.B, self.max_len, self.H, self.hd, 6, self.dev, staging) for _ in range(self.depth)]
         return [kv_cache.IncrementalKVCache(self.B, self.max_len, self.H, self.hd, 6, device=self.dev) for _ in range(self.depth)]
 
     def new_input(self, pn):
         return torch.randn(self.B, pn * pn, self.C, device=self.dev, generator=self.gen).half()
+
+    def attend_codes(self, path, cache, x, b, scale):
+        """The attention half of block b with kv_storage="codes": the same producers as the fp16 cache's lines of `step`, k / v
+        handed to the PackedKVCache as views or through its staging slab; attention over the packed entries + the fresh k / v,
+        then their pack.  Returns [B, L, H, 64]."""
+        B, L, H, hd = self.B, x.shape[1], self.H, self.hd
+        g1, g2, sc1, sc2, sh1, sh2 = self.mods[b]
+        l2 = self.attn_l2_norm
+        if path == "Q" and self.qkv_to_cache and not (l2 and self.qk_norm == "torch"):
+            q = gemm.linear_fp4_qkv_to_cache(*rot.adaln_rotate_quant_mx(x, sc1, sh1, smooth=self.s_qkv, kmajor=self.kmajor), *self.wop["qkv"],
+                                             self.qkv_bias[b] if l2 else None, cache.staging, 0, L,
+                                             qk_norm_scale=self.head_scale[b] if l2 else None).view(B, L, H, hd)
+            return cache.attend_staged(q, L, scale)
+        if path == "F":
+            qkv = Fn.linear(self.f_producer(x, sc1, sh1, self.s_qkv), self.wq["qkv"])
+        else:
+            qkv = self.q_producer_linear(x, sc1, sh1, self.s_qkv, "qkv")
+        if l2 and self.qk_norm == "torch":
+            q, k, v = (t.half() for t in self.qk_norm_torch(qkv.view(B, L, 3 * self.C), b))
+            return cache.attend(q, k, v, scale)
+        q, k, v = qkv.view(B, L, 3, H, hd).unbind(2)
+        if l2:
+            return cache.attend_staged(cache.stage_qk_norm(q, k, v, self.head_scale[b], self.qkv_bias[b]), L, scale)
+        return cache.attend(q, k, v, scale)
 
     # ---- one scale step: `depth` blocks over x [B, pn^2, C] ----------------------------------------------------------
     def step(self, path, caches, x):
@@ -266,7 +303,10 @@ class GenerationBatch:
                     x = x + Fn.linear(self.r_fc2(h), self.wq["fc2"]).mul(g2)
                 continue
             l2 = self.attn_l2_norm
-            if path == "Q" and self.qkv_to_cache and not (l2 and self.qk_norm == "torch"):
+            scale = 1.0 if l2 else hd ** -0.5
+            if self.kv_storage == "codes":
+                a = self.attend_codes(path, caches[b], x, b, scale).view(B, L, C)
+            elif path == "Q" and self.qkv_to_cache and not (l2 and self.qk_norm == "torch"):
                 q = gemm.linear_fp4_qkv_to_cache(*rot.adaln_rotate_quant_mx(x, sc1, sh1, smooth=self.s_qkv, kmajor=self.kmajor), *self.wop["qkv"],
                                                  self.qkv_bias[b] if l2 else None, caches[b].kv, caches[b].len, L,
                                                  qk_norm_scale=self.head_scale[b] if l2 else None).view(B, L, H, hd)
@@ -285,8 +325,8 @@ class GenerationBatch:
                 else:
                     q, k, v = qkv.view(B, L, 3, H, hd).unbind(2)
                     kc, vc = caches[b].append(k, v)
-            scale = 1.0 if l2 else hd ** -0.5
-            a = self.attend(q, kc, vc, scale) if (path == "F" and self.sdpa_in_f) else ops.attention_blhc(q, kc, vc, scale).view(B, L, C)
+            if self.kv_storage != "codes":
+                a = self.attend(q, kc, vc, scale) if (path == "F" and self.sdpa_in_f) else ops.attention_blhc(q, kc, vc, scale).view(B, L, C)
             if path == "F":
                 x = ops.gate_residual(Fn.linear(self.f_act(a), self.wq["proj"]), g1, x)
             else:
@@ -356,7 +396,8 @@ class GenerationBatch:
     def describe(self) -> str:
         return (f"VAR-{self.model} transformer part, {self.depth} blocks x {len(self.patch_nums)} steps ({self.max_len} tokens), "
                 f"B={self.B} rows per token (CFG), {self.config.upper()} + FP6 KV cache, random weights"
-                + (f", attn_l2_norm (q / k norm: {self.qk_norm})" if self.attn_l2_norm else ""))
+                + (f", attn_l2_norm (q / k norm: {self.qk_norm})" if self.attn_l2_norm else "")
+                + (", KV cache stored as FP6 codes + scales (PackedKVCache)" if self.kv_storage == "codes" else ""))
 
 
 def generation_record(models: Sequence[str] = ("d30-256", "d36-512"), paths: Sequence[str] = PATHS, config: str = "w4a4",

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FPQ_VERSION 127 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
+#define FPQ_VERSION 128 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
                            0.1.3: + fpq_quant_rows_codes_segments, fpq_dequant_rows_codes_segments (round 3);
                            123: + fpq_build_tag (round 4);
                            124: + fpq_set_option, fpq_get_option, fpq_option_name, fpq_gemm_fp4_gelu_dual, fpq_gelu_quant_rows_dual (round 5);
@@ -32,7 +32,8 @@ extern "C" {
                                 fpq_gemm_fp6_rows_km, the *_km producers, fpq_gemm_fp4_mx_split (round 5);
                            126: - the switches FPQ_ROT_BUTTERFLY, FPQ_ADALN_V1, FPQ_ADALN_LANES, FPQ_ADALN_GRID, FPQ_BIGTAB_U
                                 (the kernel forms they chose are retired);
-                           127: + fpq_gemm_fp4_mx_split_qknorm, fpq_kv_cache_step_qknorm (attn_l2_norm) */
+                           127: + fpq_gemm_fp4_mx_split_qknorm, fpq_kv_cache_step_qknorm (attn_l2_norm);
+                           128: + the packed KV cache: fpq_kv_pack, fpq_attention_blhc_kvcodes */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -163,6 +164,45 @@ int fpq_kv_cache_step(void* cache, int64_t batch, int64_t max_len, int64_t row_e
                       int64_t quant_stop, const void* new_k, const void* new_v, int64_t new_batch_pitch,
                       int64_t new_token_pitch, int64_t new_start, int64_t n_new, int64_t group, int table_id,
                       fpq_stream_t stream);
+
+/* THE PACKED KV CACHE: the cache fpq_kv_cache_step keeps as fake-quantized fp16, stored as the codes it holds (50 or 33 bytes per
+ * (token, head) row of 64 channels instead of 128).  Layout, per kv_bit:
+ *   kv_bit 6 (FP6-E2M3, one scale per (token, head) row of 64 - fp6_quant_e2m3_per_token_cuda on head_dim 64, group 64):
+ *     codes  uint8 [2 (K, V), batch, max_len, heads, 48]: the row's 64 elements as dense 6-bit OCP E2M3 codes, element j at bits
+ *            6 j .. 6 j + 5 of the row's 48 bytes read as one little-endian number (fpq_quant_rows_codes_fp6's bit format);
+ *     scales fp16  [2, batch, max_len, heads].
+ *   kv_bit 4 (FP4-E2M1, one scale per group of 128 consecutive elements of the flattened cache - fp_quant_e2_per_group_cuda):
+ *     codes  uint8 [2, batch, max_len, heads, 32]: OCP E2M1 nibbles, element 2i in the low nibble of byte i (fpq_quant_rows_codes_mx);
+ *     scales fp16  [2, batch, max_len, heads / 2]: scale g covers heads 2g and 2g + 1 (heads must be even).
+ * An entry decodes to (half)((float)level(code) * (float)scale) - bit for bit the fp16 value fpq_kv_cache_step leaves in the fp16
+ * cache for the same row, signed zeros, all-zero rows and rows with a subnormal fp16 scale included.  The K slab is followed by
+ * the V slab in both arrays; both 16-byte aligned.
+ *
+ * fpq_kv_pack: quantizes the fresh fp16 rows new_k / new_v [batch, n_new, heads, 64] (rows of heads * 64 halves contiguous,
+ * batch / token pitch in elements, multiples of 8, free - views of a fused qkv output need no copy; 16-byte aligned) straight
+ * into the code and scale slots [pos, pos + n_new) of K and V, one launch.  The quantization decisions are fpq_kv_cache_step's
+ * with group 64 / FPQ_E2M3 (kv_bit 6) or group 128 / FPQ_E2M1 (kv_bit 4).  Slots outside [pos, pos + n_new) are not touched;
+ * new_k / new_v must not overlap the codes or scales.  head_dim must be 64, pos + n_new <= max_len, batch <= 65535.
+ *
+ * fpq_attention_blhc_kvcodes: fpq_attention_blhc over lkv = n_packed + n_new keys, bit for bit: keys [0, n_packed) are the
+ * decoded packed entries of slots [0, n_packed), keys [n_packed, lkv) the fp16 rows new_k / new_v [batch, n_new, heads, 64]
+ * (pitches as fpq_kv_pack's; the step's own entries, which attention sees unquantized).  The decode happens between the
+ * global load and the LDS write of fpq_attention_blhc's staging, so tiles, summation order and rounding are that kernel's and
+ * its error bound holds unchanged.  Nothing past slot n_packed of the codes / scales and nothing outside the q / new_k / new_v
+ * views is read.  q, out, head_dim, pitches and scale as in fpq_attention_blhc; new_k / new_v may be NULL when n_new == 0,
+ * codes / scales when n_packed == 0.  out must not overlap any input.
+ *
+ * Both: every argument error (negative sizes, kv_bit not 4 or 6, odd heads with kv_bit 4, head_dim != 64, a range past
+ * max_len, a pitch not a multiple of 8, NULL or unaligned pointers, lkv == 0, scale <= 0) returns FPQ_ERR_ARG before anything
+ * is launched; batch == 0 (and lq == 0, n_new == 0 where the call has nothing to do) returns FPQ_OK.  Nothing is allocated,
+ * the work is ordered on `stream` and can be captured in a graph. */
+int fpq_kv_pack(uint8_t* codes, void* scales, int kv_bit, int64_t batch, int64_t max_len, int64_t heads, int64_t head_dim, int64_t pos,
+                const void* new_k, const void* new_v, int64_t new_batch_pitch, int64_t new_token_pitch, int64_t n_new,
+                fpq_stream_t stream);
+int fpq_attention_blhc_kvcodes(const void* q, const uint8_t* codes, const void* scales, int kv_bit, int64_t max_len, int64_t n_packed,
+                               const void* new_k, const void* new_v, int64_t new_batch_pitch, int64_t new_token_pitch, int64_t n_new,
+                               void* out, int64_t batch, int64_t lq, int64_t heads, int64_t head_dim, int64_t q_batch_pitch,
+                               int64_t q_token_pitch, float scale, fpq_stream_t stream);
 
 /* The reference's pure-torch quantizers ("CPU path", also what QuantizedLinear uses on
  * the GPU for per_channel / per_token FP4, tr/quant_utils.py:699-704,796-807):
