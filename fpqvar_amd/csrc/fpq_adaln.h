@@ -2,7 +2,7 @@
 //     h  = half( fma( LN(x), A, B ) ),   A = half(scale + 1) * s,  B = shift * s      (fp32; LN without affine)
 //     x1 = half( FWHT128( c_h * (h * D) ) )
 //     q  = per-group(128) quant(x1)
-// Included by fpq_kernels.hip after fpq_fast16.h (whose quantizer, butterfly and reductions it uses).
+// Included by fpq_adaln.hip after fpq_fast16.h (whose quantizer, butterfly and reductions it uses) and fpq_rotate_mfma.h.
 //
 // What the counters said about the first generation (adaln_rotate_quant16_kernel, profiles/r02_pmc_adaln_before.txt):
 // 41 VALU instructions per element, but the vector pipe only 38 % busy; 134-140 VGPRs = 3 wavefronts per SIMD, each
@@ -26,6 +26,215 @@
 // is the fuzzy one of SURVEY.md section 7 (tests/test_gpu_parity.py::test_adaln_rotate_quant_fused: h within half an
 // fp16 ulp + 4e-6 relative, rotated values and quantization bit-exact given h).
 #pragma once
+
+// ---------------------------------------------------------------------------------
+// F1, complete form: the whole producer of tr/basic_var.py:263 / :266 in one launch
+//     h  = half( ((LN(x) * half(scale+1)) + shift) * s )      LN without affine, eps, fp32 math
+//     x1 = half( c_h * FWHT128(h * D) )
+//     q  = per-group(128) quant(x1)
+// One workgroup per token row (C <= 4096): the row stays in registers from the first load
+// to the final store; mean / variance by a two-pass block reduction (shuffles + LDS).
+// fp32 op order follows the reference's chain of torch ops (mul, add_, mul - each rounded
+// to fp32, no contraction); LayerNorm's own mean/rstd differ from torch's Welford kernel
+// by fp32 rounding only, so h can differ from torch's by 1 fp16 ulp on rare elements:
+// the contract for this entry point is the fuzzy one of SURVEY.md section 7 (quant stage
+// bit-exact on the rotated values produced here; rotated values within 1 ulp).
+// ---------------------------------------------------------------------------------
+struct AdaLnArgs {
+  const void* scale;      // [batches, cols]  (scale1 / scale2 of the block)
+  const void* shift;      // [batches, cols]
+  int mod_is_f16;         // dtype of scale / shift
+  int64_t rows_per_batch; // L: row r uses batch r / L
+  float eps;
+  int64_t cols;
+};
+
+__device__ __forceinline__ float wave_sum_f32(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// the sum over the workgroup, which owns the row
+__device__ __forceinline__ float row_sum_f32(float v, float* sh) {
+  v = wave_sum_f32(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = sh[0];
+#pragma unroll
+  for (int i = 1; i < kBlock / 64; ++i) r += sh[i];
+  return r;
+}
+
+// Rows of 2688 .. 4096 channels (the adaLN producer of fpq_adaln.h keeps a row inside one wavefront: C <= 2560): the
+// workgroup's 256 lanes x 2 vectors of 8 channels; the modulation vectors of the row are requested together with x so
+// that their latency hides behind the two reductions.
+template <typename Tin, typename Tmod, bool CODES>
+__global__ __launch_bounds__(kBlock) void adaln_rotate_quant16_kernel(const void* __restrict__ xv,
+                                                                     u32x4* __restrict__ out, u32x4* __restrict__ h_out,
+                                                                     u32x4* __restrict__ y_out, int64_t rows,
+                                                                     AdaLnArgs ad, RotArgs r, Lut16Args a, Lut16Tab tab) {
+  __shared__ __attribute__((aligned(16))) uint16_t lut[kLutLdsEntries];   // static: a compile-time LDS address (a dynamic base is not folded into the ds_read offsets)
+  __shared__ float shf[kBlock / 64];
+  constexpr bool MOD16 = sizeof(Tmod) == 2;
+  constexpr int LANES = kBlock, MAXC = 2;
+  const int lane = threadIdx.x & (LANES - 1);
+  const int lg = lane & 15;
+  const uint32_t sb = (r.sign[lg >> 2] >> ((lg & 3) * 8)) & 0xFFu;
+  uint32_t sx[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) sx[k] = (((sb >> (2 * k)) & 1u) << 15) | (((sb >> (2 * k + 1)) & 1u) << 31);
+  {
+    lut16_stage(lut, tab, a.shift);
+    __syncthreads();
+  }
+  const int64_t vpr = r.vec_per_row;
+  const float inv_c = 1.0f / (float)ad.cols;
+  // a workgroup walks rows blockIdx.x*R + sub, (blockIdx.x + gridDim.x)*R + sub, ... (R rows per pass);
+  // the trip count is uniform over the workgroup, rows beyond the end are skipped by `row_live`
+  constexpr int R = kBlock / LANES;
+  for (int64_t base = (int64_t)blockIdx.x * R; base < rows; base += (int64_t)gridDim.x * R) {
+  const int64_t row_raw = base + (threadIdx.x / LANES);
+  const bool row_live = row_raw < rows;
+  const int64_t row = row_live ? row_raw : rows - 1;   // dead wavefronts recompute the last row, stores masked
+  const int64_t b = row / ad.rows_per_batch;
+
+  float f[MAXC][8];
+  constexpr int MV = MOD16 ? 1 : 2;
+  u32x4 m_sc[MAXC][MV], m_sh[MAXC][MV];   // raw modulation vectors, requested together with x
+  float s1 = 0.0f;
+#pragma unroll
+  for (int c = 0; c < MAXC; ++c) {
+    const int64_t v = (int64_t)c * LANES + lane;
+    const bool live = v < vpr;
+    const int64_t col = v * 8;
+    if constexpr (sizeof(Tin) == 2) {
+      u32x4 w = live ? __builtin_nontemporal_load((const u32x4*)xv + row * vpr + v) : u32x4{0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        f[c][2 * k] = h2f(w[k] & 0xFFFFu);
+        f[c][2 * k + 1] = h2f(w[k] >> 16);
+      }
+    } else {
+      u32x4 lo = live ? __builtin_nontemporal_load((const u32x4*)xv + 2 * (row * vpr + v)) : u32x4{0, 0, 0, 0};
+      u32x4 hi = live ? __builtin_nontemporal_load((const u32x4*)xv + 2 * (row * vpr + v) + 1) : u32x4{0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        f[c][k] = u2f(lo[k]);
+        f[c][4 + k] = u2f(hi[k]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < MV; ++j) m_sc[c][j] = m_sh[c][j] = u32x4{0, 0, 0, 0};
+    if (live) {
+      const u32x4* ap = (const u32x4*)((const Tmod*)ad.scale + b * ad.cols + col);
+      const u32x4* bp = (const u32x4*)((const Tmod*)ad.shift + b * ad.cols + col);
+#pragma unroll
+      for (int j = 0; j < MV; ++j) {
+        m_sc[c][j] = ap[j];
+        m_sh[c][j] = bp[j];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s1 += f[c][i];
+  }
+  const float mean = row_sum_f32(s1, shf) * inv_c;
+  float s2 = 0.0f;
+#pragma unroll
+  for (int c = 0; c < MAXC; ++c) {
+    const bool live = (int64_t)c * LANES + lane < vpr;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float d = f[c][i] - mean;
+      f[c][i] = d;
+      s2 = __builtin_fmaf(d, d, s2);
+    }
+    if (!live) s2 -= 8.0f * mean * mean;   // padding lanes hold zeros: take their (0 - mean)^2 back out
+  }
+  const float var = row_sum_f32(s2, shf) * inv_c;
+  const float rstd = 1.0f / __builtin_sqrtf(var + ad.eps);
+#pragma unroll
+  for (int c = 0; c < MAXC; ++c) {
+    const int64_t v = (int64_t)c * LANES + lane;
+    const bool live = v < vpr;
+    float t[8];
+    if (live) {
+      const int64_t col = v * 8;
+      float sc[8], sh[8], sm[8];
+      if constexpr (MOD16) {   // scale.add(1) is an fp16 op in the reference
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint32_t s1p = pk_add_f16(m_sc[c][0][k], 0x3C003C00u);   // scale + 1 as a (packed) fp16 add
+          sc[2 * k] = h2f(s1p & 0xFFFFu);
+          sc[2 * k + 1] = h2f(s1p >> 16);
+          sh[2 * k] = h2f(m_sh[c][0][k] & 0xFFFFu);
+          sh[2 * k + 1] = h2f(m_sh[c][0][k] >> 16);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          sc[k] = u2f(m_sc[c][0][k]) + 1.0f;
+          sc[4 + k] = u2f(m_sc[c][MV - 1][k]) + 1.0f;
+          sh[k] = u2f(m_sh[c][0][k]);
+          sh[4 + k] = u2f(m_sh[c][MV - 1][k]);
+        }
+      }
+      if (r.smooth) {
+        const u32x4* sp = (const u32x4*)(r.smooth + col);
+        u32x4 s0 = sp[0], s1v = sp[1];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          sm[k] = u2f(s0[k]);
+          sm[4 + k] = u2f(s1v[k]);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        float ln = f[c][i] * rstd;
+        float u1 = ln * sc[i];
+        float u2 = u1 + sh[i];
+        if (r.smooth) u2 = u2 * sm[i];
+        t[i] = u2;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) t[i] = 0.0f;
+    }
+    u32x4 hw;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) hw[k] = f2h2(t[2 * k], t[2 * k + 1]);
+    if (h_out && live && row_live) __builtin_nontemporal_store(hw, h_out + row * vpr + v);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[2 * k] = t[2 * k + 1] = 0.0f;
+    {
+      u32x4 ws[1];
+      float tt[1][8];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ws[0][k] = hw[k] ^ sx[k];
+      fwht128_h_n<1>(ws, tt, 1, lg);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) t[k] = tt[0][k];
+    }
+    u32x4 y;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y[k] = mul2_to_h2(t[2 * k], t[2 * k + 1], r.c_h);
+    if (y_out && live && row_live) __builtin_nontemporal_store(y, y_out + row * vpr + v);
+    uint32_t m = row_max_dpp<16>(vec_absmax16(y));
+    RowScale16 s = row_scale16(m, a.fpos.gmax, a.inv_gpos);
+    if constexpr (CODES) {
+      const uint32_t cd = codes_vec16(y, lut, a.shift, s.inv, s.inv_lo);
+      if (live && row_live) {
+        ((uint32_t*)out)[row * vpr + v] = cd;
+        if (lg == 0) r.code_scales[(row * vpr + v) >> 4] = (uint16_t)(s.s16x2 & 0xFFFFu);
+      }
+    } else {
+      u32x4 o = quant_vec16<false>(y, lut, a.shift, s.inv, s.inv_lo, s.s16x2, 0.f, 0.f, 0u);
+      if (live && row_live) __builtin_nontemporal_store(o, out + row * vpr + v);
+    }
+  }
+  }   // row loop
+}
 
 // D = (float)half_lo(w) * b + c   /   (float)half_hi(w) * b + c
 __device__ __forceinline__ float fma_h_lo(uint32_t w, float b, float c) {

@@ -1,0 +1,287 @@
+// fpq_adaln.hip - the adaLN producer (fpq_adaln.h: LayerNorm, modulation, rotation and quantizer in one launch) and its seven
+// C entry points.  A unit of its own because its ~230 kernel forms take longer to compile than the rest of the quantizers
+// together: an edit elsewhere does not recompile them.
+#include "fpq_common.h"
+
+namespace {
+#include "fpq_fast16.h"
+#include "fpq_rotate_mfma.h"
+#include "fpq_adaln.h"
+
+template <typename Tin, typename Tmod>
+int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out, int64_t rows, int64_t cols,
+                              const AdaLnArgs& ad, const float* smooth, const uint32_t sign[4], int table_id,
+                              hipStream_t st, uint16_t* code_scales = nullptr,
+                              int token_mode = 0 /*1: per-token values, 2: per-token E4M3 codes, 3: per-token packed 6-bit codes*/,
+                              const Lut16Tab* token_code_tab = nullptr,
+                              bool km = false /* FP4 / 6-bit codes into a k-major image (include/fpq.h): adaln_mfma_kernel only */) {
+  const Lut16Host& h = lut16_host(table_id, table_id);
+  if (!h.tab_valid) return FPQ_ERR_TABLE;
+  const Lut16Tab& tab = token_mode >= 2 ? *token_code_tab : (code_scales && !token_mode ? lut16_mx_codes_e2m1() : h.tab);
+  RotArgs r;
+  r.code_scales = code_scales;
+  r.code_bits = token_mode == 3 ? 6 : 8;
+  r.km_rows = km ? (uint32_t)rows : 0u;
+  r.km_gpr = fast_div((uint32_t)(cols / 128));
+  if (km) {
+    const bool fp4_codes = code_scales && !token_mode;
+    if (!(fp4_codes || token_mode == 3) || !km_image_fits(rows, token_mode == 3 ? cols / 4 * 3 : cols / 2)) return FPQ_ERR_SHAPE;
+    if (cols / 8 > 64 * 5) return FPQ_ERR_SHAPE;   // rows beyond one wavefront: the first generation writes row-major codes only
+  }
+  r.smooth = smooth;
+  for (int i = 0; i < 4; ++i) r.sign[i] = sign[i];
+  r.c_h = h2f(f2h(1.0f / __builtin_sqrtf(128.0f)));
+  r.vec_per_row = cols / 8;
+  const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
+  {
+    // fpq_adaln.h: fp16 or fp32 rows of up to 2560 channels, one batch entry per workgroup
+    constexpr bool X32 = sizeof(Tin) == 4;
+    if (r.vec_per_row <= 64 * 5) {
+      if (h.args.shift < 6) return FPQ_ERR_TABLE;   // symmetric tables only (<= 2 x 512 buckets)
+      const int64_t L = ad.rows_per_batch;
+      const int64_t n_batches = (rows + L - 1) / L;
+      const bool rows_env = fpq_opt_set(OPT_FPQ_ADALN_ROWS);
+      // Large launches: chunks of 16 rows (4 per wavefront) amortise the staging of the modulation; small launches (the
+      // early scale steps of a generation: 100 .. 3600 rows) are latency-bound and want every CU busy: one row per wavefront
+      // (profiles/r02_small_steps.json; round 4, cold inputs, 4 / 8 / 12 / 16 rows per workgroup over the ten steps of d30 and
+      // d36-512: 4 is the best or within 2 % of it up to 10 000 rows, 8 from 16 900 on - profiles/r04_adaln_rows_sweep.txt).
+      // FPQ_ADALN_ROWS=n: n rows per workgroup everywhere; FPQ_ADALN_TAIL=rows: how many rows at the end of the grid go to
+      // each of two finer tiers (8 and 4 rows per workgroup).  The tiers are OFF by default (0): they never beat a plain grid
+      // of 8 - 12 rows (profiles/r03_adaln_partition.txt); the tier decode stays reachable through the variable and is
+      // covered by tests/test_gpu_parity.py::test_adaln_tail_tiers_switch in a child process.
+      // (third generation, large launches: 8 rows = two per wavefront for the stream-bound forms - E2M1 values out, fp32
+      // rows; 12 for the forms bound by vector issue - operands out or a bucket table, from fp16 rows - where the
+      // prologue's instructions per row count: 73.3 -> 70.5 us for codes, 89.7 -> 87.1 for E4M3 bytes, 96.2 -> 93.4 for
+      // per-token E2M3 values; profiles/r03_adaln_partition.txt)
+      const bool issue_bound = !X32 && (code_scales != nullptr || token_mode != 0 || table_id != FPQ_E2M1);
+      int rows_per_wg = rows_env ? fpq_opt(OPT_FPQ_ADALN_ROWS, 0) : (rows >= 8192 ? (issue_bound && rows >= 32768 ? 12 : 8) : 4);
+      if (rows_per_wg < 1) rows_per_wg = 1;
+      // rows of exactly 8 groups (C = 1024): two rows per tile (fpq_adaln.h, PAIR2) - workgroups of an even number of rows
+      const bool pair2 = !X32 && r.vec_per_row == 128 && token_mode == 0 && !h_out && !y_out &&
+                         !fpq_flag(OPT_FPQ_ADALN_NO_PAIR2);
+      if (pair2) rows_per_wg = rows_env ? ((rows_per_wg + 1) & ~1) : (rows >= 8192 ? 16 : 8);
+      const int64_t per_batch = (L + rows_per_wg - 1) / rows_per_wg;
+      if (n_batches * per_batch > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
+      AdalnTiers tiers = {};
+      const int tail_rows = fpq_opt(OPT_FPQ_ADALN_TAIL, 0);
+      int64_t nb2 = 0, nb1 = 0;
+      if (tail_rows > 0 && rows_per_wg > 4) {
+        nb2 = (tail_rows + L - 1) / L;                                   // batch entries cut into chunks of 4 rows
+        if (rows_per_wg > 8) nb1 = (tail_rows + L - 1) / L;              // ... of 8 rows
+        if (nb2 > n_batches) nb2 = n_batches;
+        if (nb1 > n_batches - nb2) nb1 = n_batches - nb2;
+      }
+      tiers.rows[0] = rows_per_wg;
+      tiers.rows[1] = 8;
+      tiers.rows[2] = 4;
+      for (int t = 0; t < 3; ++t) tiers.per_batch[t] = (int)((L + tiers.rows[t] - 1) / tiers.rows[t]);
+      tiers.batches[0] = (int)(n_batches - nb1 - nb2);
+      tiers.batches[1] = (int)nb1;
+      {
+        const int64_t nb_of[3] = {n_batches - nb1 - nb2, nb1, nb2};
+        for (int t = 0; t < 3; ++t) {   // id / d == (id * ceil(2^32 / d)) >> 32 whenever id * d < 2^32
+          const uint64_t d = (uint64_t)tiers.per_batch[t], ids = (uint64_t)nb_of[t] * d;
+          tiers.magic[t] = (d >= 2 && ids * d < (1ull << 32)) ? (uint32_t)(((1ull << 32) + d - 1) / d) : 0u;
+        }
+      }
+      const int64_t n_wg3 = (int64_t)tiers.batches[0] * tiers.per_batch[0] + nb1 * tiers.per_batch[1] + nb2 * tiers.per_batch[2];
+      if (n_wg3 > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
+      const dim3 g3((unsigned)n_wg3);
+      const size_t lds2 = 0;   // table, modulation planes and images live in static LDS
+      // E2M1 values per group: levels from the FP4 conversion hardware, no table (fpq_adaln.h)
+      const bool hw4 = table_id == FPQ_E2M1 && !token_mode && !fpq_flag(OPT_FPQ_NO_HW4);
+      const bool tight_ok = FPQ_ADALN_TIGHT && !fpq_flag(OPT_FPQ_ADALN_NO_TIGHT);
+      // E2M3 / E3M2 values (per group, or per token: token_mode 1): levels from the FP6 conversion hardware, no table
+      const int hw6 = (token_mode <= 1 && !code_scales && !fpq_flag(OPT_FPQ_NO_HW6)) ? (table_id == FPQ_E2M3 ? 1 : table_id == FPQ_E3M2 ? 2 : 0) : 0;
+#define FPQ_ADALN3(M, CODES, EMIT, TOKEN, HW4, TIGHT)                                                                  \
+  hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, CODES, EMIT, TOKEN, X32, HW4, TIGHT>), g3, dim3(kBlock), lds2, st,    \
+                     (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab, tiers)
+#define FPQ_ADALN2K(M, CODES, EMIT, TOKEN)                                                                             \
+  do {                                                                                                                 \
+    if constexpr ((M == 4 || M == 5) && !(CODES) && !(EMIT)) {   /* E2M3 / E3M2 values, rows of 13 .. 20 groups: hardware levels */ \
+      if (hw6 == 1) {                                                                                                  \
+        hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 1>), g3,      \
+                           dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,         \
+                           rows, ad, r, h.args, tab, tiers);                                                           \
+        break;                                                                                                         \
+      }                                                                                                                \
+      if (hw6 == 2) {                                                                                                  \
+        hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 2>), g3,      \
+                           dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,         \
+                           rows, ad, r, h.args, tab, tiers);                                                           \
+        break;                                                                                                         \
+      }                                                                                                                \
+    }                                                                                                                  \
+    if constexpr (M == 2 && !X32 && !(EMIT) && !(TOKEN)) {                                                             \
+      if (pair2) {                                                                                                     \
+        if (hw4)                                                                                                       \
+          hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, 4, CODES, false, false, false, true, false, 4, true>), g3,       \
+                             dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,       \
+                             rows, ad, r, h.args, tab, tiers);                                                         \
+        else                                                                                                           \
+          hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, 4, CODES, false, false, false, false, false, 4, true>), g3,      \
+                             dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,       \
+                             rows, ad, r, h.args, tab, tiers);                                                         \
+        break;                                                                                                         \
+      }                                                                                                                \
+    }                                                                                                                  \
+    if constexpr (!(TOKEN)) {                                                                                          \
+      if constexpr (M == 4 && !X32 && !(EMIT) && !(CODES)) {                                                           \
+        if (hw4 && tight_ok && r.vec_per_row == 240) {   /* VAR-d30: 31 KiB of LDS, five workgroups per CU */          \
+          FPQ_ADALN3(M, CODES, EMIT, TOKEN, true, true);                                                               \
+          break;                                                                                                       \
+        }                                                                                                              \
+      }                                                                                                                \
+      if (hw4) {                                                                                                       \
+        FPQ_ADALN3(M, CODES, EMIT, TOKEN, true, false);                                                                \
+        break;                                                                                                         \
+      }                                                                                                                \
+    }                                                                                                                  \
+    FPQ_ADALN3(M, CODES, EMIT, TOKEN, false, false);                                                                   \
+  } while (0)
+#ifdef FPQ_ADALN_STAMPS
+#define FPQ_ADALN_EMIT (h_out != nullptr)   /* diagnostic build: y_out alone is the stamp buffer */
+#else
+#define FPQ_ADALN_EMIT (h_out || y_out)
+#endif
+#define FPQ_ADALN2(M)                                                                                                  \
+  do {                                                                                                                 \
+    const bool emit = FPQ_ADALN_EMIT;                                                                                  \
+    if (token_mode >= 2) FPQ_ADALN2K(M, true, false, true);                                                            \
+    else if (token_mode == 1 && emit) FPQ_ADALN2K(M, false, true, true);                                               \
+    else if (token_mode == 1) FPQ_ADALN2K(M, false, false, true);                                                      \
+    else if (code_scales) FPQ_ADALN2K(M, true, false, false);                                                          \
+    else if (emit) FPQ_ADALN2K(M, false, true, false);                                                                 \
+    else FPQ_ADALN2K(M, false, false, false);                                                                          \
+  } while (0)
+      switch ((int)((r.vec_per_row + 63) / 64)) {   // MAXC = ceil(vectors per row / 64), exactly
+        case 1: FPQ_ADALN2(1); break;
+        case 2: FPQ_ADALN2(2); break;
+        case 3: FPQ_ADALN2(3); break;
+        case 4: FPQ_ADALN2(4); break;
+        default: FPQ_ADALN2(5); break;
+      }
+#undef FPQ_ADALN3
+#undef FPQ_ADALN2
+#undef FPQ_ADALN2K
+      return check_launch();
+    }
+  }
+  // rows beyond one wavefront (2560 < C <= 4096, per group only): the first generation, one workgroup per row
+  const dim3 g((unsigned)(rows < 8192 ? rows : 8192));   // every workgroup stages the table once, then walks rows
+  if (code_scales)
+    hipLaunchKernelGGL((adaln_rotate_quant16_kernel<Tin, Tmod, true>), g, dim3(kBlock), lds, st, x, (u32x4*)out,
+                       (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab);
+  else
+    hipLaunchKernelGGL((adaln_rotate_quant16_kernel<Tin, Tmod, false>), g, dim3(kBlock), lds, st, x, (u32x4*)out,
+                       (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab);
+  return check_launch();
+}
+
+}  // namespace
+
+extern "C" {
+
+static int adaln_rotate_quant_impl(const void* x, void* out, void* h_out, void* rotated_out, void* code_scales,
+                                   int64_t rows, int64_t cols, int in_dtype, const void* scale, const void* shift,
+                                   int mod_dtype, int64_t rows_per_batch, float eps, const float* smooth,
+                                   const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream,
+                                   int token_mode = 0, const Lut16Tab* token_code_tab = nullptr, bool km = false) {
+  if (rows < 0 || cols < 0 || rows_per_batch <= 0 || !sign_mask_host) return FPQ_ERR_ARG;
+  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
+  if ((in_dtype != FPQ_F16 && in_dtype != FPQ_F32) || (mod_dtype != FPQ_F16 && mod_dtype != FPQ_F32))
+    return FPQ_ERR_DTYPE;
+  if (cols % 128 != 0 || cols > 4096) return FPQ_ERR_SHAPE;
+  if (rows == 0 || cols == 0) return FPQ_OK;
+  if (!x || !out || !scale || !shift) return FPQ_ERR_ARG;
+  if ((((uintptr_t)x | (uintptr_t)out | (uintptr_t)h_out | (uintptr_t)rotated_out | (uintptr_t)scale |
+        (uintptr_t)shift | (uintptr_t)smooth) & 15) != 0)
+    return FPQ_ERR_ARG;
+  AdaLnArgs ad;
+  ad.scale = scale;
+  ad.shift = shift;
+  ad.mod_is_f16 = mod_dtype == FPQ_F16;
+  ad.rows_per_batch = rows_per_batch;
+  ad.eps = eps;
+  ad.cols = cols;
+  // One wavefront per row while the row fits 5 vectors per lane (C <= 2560: no barrier in the row
+  // loop; measured 0.180 ms vs 0.199 ms per [65500 x 1920] on MI355X), one workgroup per row beyond.
+  if (token_mode && cols / 8 > 64 * 5) return FPQ_ERR_SHAPE;   // the per-token form keeps a row inside one wavefront: C <= 2560
+  hipStream_t st = (hipStream_t)stream;
+#define FPQ_GO(TI, TM) return launch_adaln_rotate_quant<TI, TM>(x, out, h_out, rotated_out, rows, cols, ad, smooth, \
+                                                              sign_mask_host, table_id, st, (uint16_t*)code_scales, \
+                                                              token_mode, token_code_tab, km)
+  if (in_dtype == FPQ_F16 && mod_dtype == FPQ_F16) FPQ_GO(_Float16, _Float16);
+  if (in_dtype == FPQ_F16) FPQ_GO(_Float16, float);
+  if (mod_dtype == FPQ_F16) FPQ_GO(float, _Float16);
+  FPQ_GO(float, float);
+#undef FPQ_GO
+}
+
+int fpq_adaln_rotate_quant_rows(const void* x, void* out, void* h_out, void* rotated_out, int64_t rows, int64_t cols,
+                                int in_dtype, const void* scale, const void* shift, int mod_dtype,
+                                int64_t rows_per_batch, float eps, const float* smooth,
+                                const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
+  return adaln_rotate_quant_impl(x, out, h_out, rotated_out, nullptr, rows, cols, in_dtype, scale, shift, mod_dtype,
+                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream);
+}
+
+int fpq_adaln_rotate_quant_rows_codes_mx(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols,
+                                         int in_dtype, const void* scale, const void* shift, int mod_dtype,
+                                         int64_t rows_per_batch, float eps, const float* smooth,
+                                         const uint32_t* sign_mask_host, fpq_stream_t stream) {
+  if (rows > 0 && cols > 0 && !scales) return FPQ_ERR_ARG;
+  return adaln_rotate_quant_impl(x, codes, nullptr, nullptr, scales, rows, cols, in_dtype, scale, shift, mod_dtype,
+                                 rows_per_batch, eps, smooth, sign_mask_host, FPQ_E2M1, stream);
+}
+int fpq_adaln_rotate_quant_rows_codes_mx_km(const void* x, uint8_t* image, void* scales, int64_t rows, int64_t cols,
+                                            int in_dtype, const void* scale, const void* shift, int mod_dtype,
+                                            int64_t rows_per_batch, float eps, const float* smooth,
+                                            const uint32_t* sign_mask_host, fpq_stream_t stream) {
+  if (rows > 0 && cols > 0 && !scales) return FPQ_ERR_ARG;
+  return adaln_rotate_quant_impl(x, image, nullptr, nullptr, scales, rows, cols, in_dtype, scale, shift, mod_dtype,
+                                 rows_per_batch, eps, smooth, sign_mask_host, FPQ_E2M1, stream, 0, nullptr, true);
+}
+
+int fpq_adaln_rotate_quant_token_rows(const void* x, void* out, void* h_out, void* rotated_out, void* row_scales,
+                                      int64_t rows, int64_t cols, int in_dtype, const void* scale, const void* shift,
+                                      int mod_dtype, int64_t rows_per_batch, float eps, const float* smooth,
+                                      const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
+  if ((((uintptr_t)row_scales) & 1) != 0) return FPQ_ERR_ARG;
+  return adaln_rotate_quant_impl(x, out, h_out, rotated_out, row_scales, rows, cols, in_dtype, scale, shift, mod_dtype,
+                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 1, nullptr);
+}
+
+int fpq_adaln_rotate_quant_token_rows_codes_fp8(const void* x, uint8_t* codes, void* row_scales, int64_t rows, int64_t cols,
+                                                int in_dtype, const void* scale, const void* shift, int mod_dtype,
+                                                int64_t rows_per_batch, float eps, const float* smooth,
+                                                const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
+  if (rows > 0 && cols > 0 && !row_scales) return FPQ_ERR_ARG;
+  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
+  return adaln_rotate_quant_impl(x, codes, nullptr, nullptr, row_scales, rows, cols, in_dtype, scale, shift, mod_dtype,
+                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 2, &lut16_codes8(table_id));
+}
+
+int fpq_adaln_rotate_quant_token_rows_codes_fp6(const void* x, uint8_t* codes, void* row_scales, int64_t rows, int64_t cols,
+                                                int in_dtype, const void* scale, const void* shift, int mod_dtype,
+                                                int64_t rows_per_batch, float eps, const float* smooth,
+                                                const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
+  if (rows > 0 && cols > 0 && !row_scales) return FPQ_ERR_ARG;
+  if (table_id != FPQ_E2M3) return FPQ_ERR_TABLE;
+  if (cols % 32 != 0) return FPQ_ERR_SHAPE;
+  if ((((uintptr_t)codes) & 7) != 0) return FPQ_ERR_ARG;
+  return adaln_rotate_quant_impl(x, codes, nullptr, nullptr, row_scales, rows, cols, in_dtype, scale, shift, mod_dtype,
+                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 3, &lut16_codes6_e2m3());
+}
+int fpq_adaln_rotate_quant_token_rows_codes_fp6_km(const void* x, uint8_t* image, void* row_scales, int64_t rows, int64_t cols,
+                                                   int in_dtype, const void* scale, const void* shift, int mod_dtype,
+                                                   int64_t rows_per_batch, float eps, const float* smooth,
+                                                   const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
+  if (rows > 0 && cols > 0 && !row_scales) return FPQ_ERR_ARG;
+  if (table_id != FPQ_E2M3) return FPQ_ERR_TABLE;
+  if (cols % 128 != 0) return FPQ_ERR_SHAPE;
+  return adaln_rotate_quant_impl(x, image, nullptr, nullptr, row_scales, rows, cols, in_dtype, scale, shift, mod_dtype,
+                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 3, &lut16_codes6_e2m3(), true);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // fpq_attention.h - the consumer of the KV cache: softmax(q k^T * scale) v for head_dim 64 in the layout the
 // reference hands to flash_attn_func (SelfAttention.forward, tr/basic_var.py:173,211: q / k / v are [B, L, H, c]
-// views, no mask and no dropout at inference because KV caching is on, :159).  Included by fpq_kernels.hip.
+// views, no mask and no dropout at inference because KV caching is on, :159).  Included by fpq_gemm.hip.
 //
 // One workgroup = 4 wavefronts = 128 query rows of one (batch, head); every wavefront owns 32 query rows and walks the
 // keys in tiles of 64 that the workgroup stages once (global -> registers -> LDS, double buffered, one barrier per tile).

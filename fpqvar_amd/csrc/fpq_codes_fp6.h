@@ -1,5 +1,5 @@
 // fpq_codes_fp6.h - the operand-emitting quantizers of the row-scaled FP6 GEMM (fpq_gemm_fp6.h): dense 6-bit E2M3 codes + one
-// scale per row.  Included by fpq_kernels.hip only.
+// scale per row.  Included by fpq_rotate.hip only (the code table, lut16_codes6_e2m3: fpq_fast16.h).
 #pragma once
 
 // Fast form for fp16 rows (per-token activations): one wavefront per row, every lane owns whole 32-element
@@ -69,18 +69,6 @@ __global__ __launch_bounds__(kBlock) void rows16_codes6_wave_kernel(const uint16
       }
     }
   }
-}
-
-// level (exactly an E2M3 number, sign included) -> 6-bit code
-__host__ __device__ __forceinline__ uint32_t e2m3_of_level(float q) {
-  const uint32_t sgn = (q < 0.0f) ? 32u : 0u;
-  const float a = q < 0.0f ? -q : q;
-  uint32_t mag;
-  if (a < 1.0f) mag = (uint32_t)(a * 8.0f);                                        // subnormal: m / 8
-  else if (a < 2.0f) mag = (1u << 3) | (uint32_t)((a - 1.0f) * 8.0f);
-  else if (a < 4.0f) mag = (2u << 3) | (uint32_t)((a * 0.5f - 1.0f) * 8.0f);
-  else mag = (3u << 3) | (uint32_t)((a * 0.25f - 1.0f) * 8.0f);
-  return sgn | mag;
 }
 
 // Generic form (fp32 weights, long or unaligned rows): one workgroup per row, a thread packs whole 32-element blocks.

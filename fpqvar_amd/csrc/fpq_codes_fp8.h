@@ -1,5 +1,5 @@
 // fpq_codes_fp8.h - the operand-emitting quantizers of the row-scaled FP8 GEMM (fpq_gemm_fp8.h): one E4M3 byte per element +
-// one scale per row.  Included by fpq_kernels.hip only.
+// one scale per row.  Included by fpq_rotate.hip (the emitters) and fpq_kernels.hip (codes8_vec16, for fpq_kv_pack).
 #pragma once
 
 // Per-row quantization straight to E4M3 bytes + one scale per row (x's dtype): same scale / normalise / rounding

@@ -1,5 +1,6 @@
 // fpq_codes_mx.h - the operand-emitting quantizer of the FP4 matrix-core GEMM (fpq_gemm_fp4.h): per-group(128) E2M1 codes +
-// scales.  Included by fpq_kernels.hip (the quantizers' translation unit) only - the GEMM kernels live in fpq_gemm.hip.
+// scales.  Included by fpq_kernels.hip only (beside codes128_kernel, which its fp32 form uses) - the GEMM kernels live in
+// fpq_gemm.hip.
 #pragma once
 
 typedef float v2f_t __attribute__((ext_vector_type(2)));   // (fpq_gemm_fp4.h has its own: the two headers never meet in one translation unit)

@@ -1,5 +1,6 @@
-// fpq_common.h - format descriptors, dtype traits and the closed-form rounding shared by the two
-// translation units of libfpq_hip.so (fpq_kernels.hip: quantizers; fpq_gemm.hip: matrix-core consumers).
+// fpq_common.h - format descriptors, dtype traits and the closed-form rounding shared by the translation units of
+// libfpq_hip.so (fpq_kernels.hip: row and element quantizers, codes, KV cache; fpq_rotate.hip: online rotation, FP8 / FP6
+// operand emitters; fpq_adaln.hip: the adaLN producer; fpq_gemm.hip: matrix-core consumers and attention).
 // Everything lives in an anonymous namespace: each translation unit gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,7 +10,7 @@
 #include "fpq.h"
 
 // ---------------------------------------------------------------------------------
-// Process-wide experiment switches (include/fpq.h, fpq_set_option).  ONE table of ints for both translation units
+// Process-wide experiment switches (include/fpq.h, fpq_set_option).  ONE table of ints for every translation unit
 // (defined in fpq_kernels.hip), filled from the environment once when the library is loaded and changed afterwards only
 // through fpq_set_option: the launch paths read an int, never the environment.
 // ---------------------------------------------------------------------------------
@@ -41,11 +42,8 @@ static inline bool fpq_flag(int id) { const int v = fpq_opt_raw(id); return v !=
 static inline bool fpq_opt_set(int id) { return fpq_opt_raw(id) != FPQ_OPTION_DEFAULT; }
 static inline int fpq_opt(int id, int dflt) { const int v = fpq_opt_raw(id); return v == FPQ_OPTION_DEFAULT ? dflt : v; }
 
-// Helpers of fpq_kernels.hip that fpq_gemm.hip's fused fc1 epilogue needs too (internal to the library, not exported):
-// the bucket table + arguments of a dual-format quantizer (copied into caller-provided Lut16Args / Lut16Tab objects, whose
-// layout the two translation units share through fpq_fast16.h), and the "any NaN => the whole result is zero" fix-up launch.
-extern "C" __attribute__((visibility("hidden"))) int fpq_internal_dual_lut(int neg_table, int pos_table, void* args_out, size_t args_bytes,
-                                                                           void* tab_out, size_t tab_bytes);
+// A helper of fpq_kernels.hip that fpq_gemm.hip's fused fc1 epilogue needs too (internal to the library, not exported):
+// the "any NaN => the whole result is zero" fix-up launch.
 extern "C" __attribute__((visibility("hidden"))) int fpq_internal_zero_if_flag(void* out, int64_t n_bytes, void* scratch, void* stream);
 
 namespace {
@@ -372,5 +370,20 @@ inline int grid_for(int64_t work_items_of_block, int64_t cap = kMaxBlocks) {
 }
 
 inline int check_launch() { return hipGetLastError() == hipSuccess ? FPQ_OK : FPQ_ERR_LAUNCH; }
+
+// (T)(x / s).  fp16: x and s carry 11-bit significands, so one residual step on x*rcp(s) lands on the
+// correctly rounded quotient (fpq_fast16.h, "exact fp16 division"); where it differs from IEEE
+// (s = 0 or non-finite: 0 / NaN instead of inf / 0) the quantizer maps both to level 0.
+template <typename T>
+__device__ __forceinline__ float div_round(float x, float s) {
+  if constexpr (sizeof(T) == 2) {
+    float inv = (s == 0.0f) ? 0.0f : __builtin_amdgcn_rcpf(s);
+    float y = x * inv;
+    float e = __builtin_fmaf(-y, s, x);
+    return DT<T>::round(__builtin_fmaf(e, inv, y));
+  } else {
+    return x / s;
+  }
+}
 
 }  // namespace

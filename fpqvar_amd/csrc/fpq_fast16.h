@@ -1,5 +1,5 @@
-// fpq_fast16.h - the fp16 -> fp16 hot path (activations, KV cache).  Included by
-// fpq_kernels.hip inside its anonymous namespace, after the generic helpers.
+// fpq_fast16.h - the fp16 -> fp16 hot path (activations, KV cache).  Included by every translation unit inside its
+// anonymous namespace; at its end, the host caches of the bucket tables that the units share.
 //
 // Same results as the generic kernels (rows_subwave_kernel / rows_block_kernel),
 // about a fifth of their VALU work per element:
@@ -76,7 +76,7 @@ __device__ __forceinline__ uint32_t pk_mul_f16(uint32_t a, uint32_t b) {
 }
 
 // two fp32 values -> packed fp16 pair with ONE v_cvt_pk_f16_f32 (round to nearest even).  The
-// asm barrier keeps both values as rounded fp32 numbers first (see f2h in fpq_kernels.hip).
+// asm barrier keeps both values as rounded fp32 numbers first (see f2h in fpq_common.h).
 __device__ __forceinline__ uint32_t f2h2(float lo, float hi) {
   asm volatile("" : "+v"(lo), "+v"(hi));
   typedef float f2c_t __attribute__((ext_vector_type(2)));
@@ -1345,210 +1345,123 @@ __device__ __forceinline__ void row_max_dpp16_n(uint32_t (&v)[N], int n) {
 }
 
 // ---------------------------------------------------------------------------------
-// F1, complete form: the whole producer of tr/basic_var.py:263 / :266 in one launch
-//     h  = half( ((LN(x) * half(scale+1)) + shift) * s )      LN without affine, eps, fp32 math
-//     x1 = half( c_h * FWHT128(h * D) )
-//     q  = per-group(128) quant(x1)
-// One workgroup per token row (C <= 4096): the row stays in registers from the first load
-// to the final store; mean / variance by a two-pass block reduction (shuffles + LDS).
-// fp32 op order follows the reference's chain of torch ops (mul, add_, mul - each rounded
-// to fp32, no contraction); LayerNorm's own mean/rstd differ from torch's Welford kernel
-// by fp32 rounding only, so h can differ from torch's by 1 fp16 ulp on rare elements:
-// the contract for this entry point is the fuzzy one of SURVEY.md section 7 (quant stage
-// bit-exact on the rotated values produced here; rotated values within 1 ulp).
+// Host caches of the bucket tables, shared by every translation unit that launches a table kernel.  Each unit builds its
+// own copy on first use (inline functions in an anonymous namespace: one static per unit).  That is safe: every cache is a
+// deterministic function of the table ids, immutable once built, and lives on the host only - the tables reach the
+// kernels as arguments (no device global is written from the host).
 // ---------------------------------------------------------------------------------
-struct AdaLnArgs {
-  const void* scale;      // [batches, cols]  (scale1 / scale2 of the block)
-  const void* shift;      // [batches, cols]
-  int mod_is_f16;         // dtype of scale / shift
-  int64_t rows_per_batch; // L: row r uses batch r / L
-  float eps;
-  int64_t cols;
+inline int table_shift16(int id) {   // rounding thresholds are multiples of 2^shift in fp16 patterns
+  return id == FPQ_INT_NEG ? 5 : 9 - kTables[id].mbits;
+}
+
+// host cache of prebuilt tables: built once per (neg, pos) pair, immutable afterwards
+struct Lut16Host {
+  Lut16Args args;
+  Lut16Tab tab;                    // the compressed image that travels in the kernel arguments
+  bool tab_valid;                  // false: kernels evaluate the closed form themselves (lut16_fill)
+  uint16_t full[kLutLdsEntries];   // the full image (host side: derived code tables are built from it)
 };
 
-__device__ __forceinline__ float wave_sum_f32(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
+inline const Lut16Host& lut16_host(int neg_id, int pos_id) {
+  static const auto* cache = [] {
+    auto* c = new Lut16Host[FPQ_NUM_TABLES * FPQ_NUM_TABLES];
+    for (int n = 0; n < FPQ_NUM_TABLES; ++n)
+      for (int p = 0; p < FPQ_NUM_TABLES; ++p) {
+        Lut16Host& h = c[n * FPQ_NUM_TABLES + p];
+        h.args.fneg = make_fmt(n);
+        h.args.fpos = make_fmt(p);
+        h.args.inv_gneg = 1.0f / h.args.fneg.gmax;
+        h.args.inv_gpos = 1.0f / h.args.fpos.gmax;
+        h.args.shift = table_shift16(n) < table_shift16(p) ? table_shift16(n) : table_shift16(p);
+        h.args.nan_flag = nullptr;
+        h.args.clip_absmax = nullptr;
+        h.args.clip_strength = 1.0f;
+        h.args.gelu_out = nullptr;
+        for (int i = 0; i < kLutLdsEntries; ++i) h.full[i] = 0;
+        lut16_build_host(h.full, h.args);
+        h.tab_valid = lut16_compress(h.full, h.args.shift, &h.tab);
+      }
+    return c;
+  }();
+  return cache[neg_id * FPQ_NUM_TABLES + pos_id];
 }
 
-// the sum over the workgroup, which owns the row
-__device__ __forceinline__ float row_sum_f32(float v, float* sh) {
-  v = wave_sum_f32(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = sh[0];
-#pragma unroll
-  for (int i = 1; i < kBlock / 64; ++i) r += sh[i];
-  return r;
+// hardware-nibble codes of E2M1 (the FP4 GEMM's operands, fpq_codes_mx.h, and the packed KV cache)
+inline const Lut16Tab& lut16_mx_codes_e2m1() {
+  static const Lut16Tab* tab = [] {
+    auto* t = new Lut16Tab;
+    const Lut16Host& h = lut16_host(FPQ_E2M1, FPQ_E2M1);
+    const int n = 1 << (16 - h.args.shift);
+    uint16_t full[kLutLdsEntries] = {0};
+    for (int i = 0; i < n; ++i) {
+      uint32_t u = (uint32_t)i << h.args.shift;
+      bool neg = (u >> 15) != 0;
+      float qm = quant_mag(h2f(u & 0x7FFFu), 0u, h.args.fpos);
+      // level -> magnitude index 0..7 (host twin of level_index)
+      int li = (qm >= h.args.fpos.kmin) ? (int)((fbits(qm) >> h.args.fpos.mshift) - h.args.fpos.kmin_code_base)
+                                        : (int)(qm * h.args.fpos.inv_step0);
+      full[i] = (uint16_t)(li | ((neg && li != 0) ? 8 : 0));
+    }
+    if (!lut16_compress(full, h.args.shift, t)) abort();   // E2M1: 2 x 128 buckets, always fits
+    return t;
+  }();
+  return *tab;
 }
 
-// Rows of 2688 .. 4096 channels (the adaLN producer of fpq_adaln.h keeps a row inside one wavefront: C <= 2560): the
-// workgroup's 256 lanes x 2 vectors of 8 channels; the modulation vectors of the row are requested together with x so
-// that their latency hides behind the two reductions.
-template <typename Tin, typename Tmod, bool CODES>
-__global__ __launch_bounds__(kBlock) void adaln_rotate_quant16_kernel(const void* __restrict__ xv,
-                                                                     u32x4* __restrict__ out, u32x4* __restrict__ h_out,
-                                                                     u32x4* __restrict__ y_out, int64_t rows,
-                                                                     AdaLnArgs ad, RotArgs r, Lut16Args a, Lut16Tab tab) {
-  __shared__ __attribute__((aligned(16))) uint16_t lut[kLutLdsEntries];   // static: a compile-time LDS address (a dynamic base is not folded into the ds_read offsets)
-  __shared__ float shf[kBlock / 64];
-  constexpr bool MOD16 = sizeof(Tmod) == 2;
-  constexpr int LANES = kBlock, MAXC = 2;
-  const int lane = threadIdx.x & (LANES - 1);
-  const int lg = lane & 15;
-  const uint32_t sb = (r.sign[lg >> 2] >> ((lg & 3) * 8)) & 0xFFu;
-  uint32_t sx[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) sx[k] = (((sb >> (2 * k)) & 1u) << 15) | (((sb >> (2 * k + 1)) & 1u) << 31);
-  {
-    lut16_stage(lut, tab, a.shift);
-    __syncthreads();
-  }
-  const int64_t vpr = r.vec_per_row;
-  const float inv_c = 1.0f / (float)ad.cols;
-  // a workgroup walks rows blockIdx.x*R + sub, (blockIdx.x + gridDim.x)*R + sub, ... (R rows per pass);
-  // the trip count is uniform over the workgroup, rows beyond the end are skipped by `row_live`
-  constexpr int R = kBlock / LANES;
-  for (int64_t base = (int64_t)blockIdx.x * R; base < rows; base += (int64_t)gridDim.x * R) {
-  const int64_t row_raw = base + (threadIdx.x / LANES);
-  const bool row_live = row_raw < rows;
-  const int64_t row = row_live ? row_raw : rows - 1;   // dead wavefronts recompute the last row, stores masked
-  const int64_t b = row / ad.rows_per_batch;
-
-  float f[MAXC][8];
-  constexpr int MV = MOD16 ? 1 : 2;
-  u32x4 m_sc[MAXC][MV], m_sh[MAXC][MV];   // raw modulation vectors, requested together with x
-  float s1 = 0.0f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c) {
-    const int64_t v = (int64_t)c * LANES + lane;
-    const bool live = v < vpr;
-    const int64_t col = v * 8;
-    if constexpr (sizeof(Tin) == 2) {
-      u32x4 w = live ? __builtin_nontemporal_load((const u32x4*)xv + row * vpr + v) : u32x4{0, 0, 0, 0};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        f[c][2 * k] = h2f(w[k] & 0xFFFFu);
-        f[c][2 * k + 1] = h2f(w[k] >> 16);
-      }
-    } else {
-      u32x4 lo = live ? __builtin_nontemporal_load((const u32x4*)xv + 2 * (row * vpr + v)) : u32x4{0, 0, 0, 0};
-      u32x4 hi = live ? __builtin_nontemporal_load((const u32x4*)xv + 2 * (row * vpr + v) + 1) : u32x4{0, 0, 0, 0};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        f[c][k] = u2f(lo[k]);
-        f[c][4 + k] = u2f(hi[k]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < MV; ++j) m_sc[c][j] = m_sh[c][j] = u32x4{0, 0, 0, 0};
-    if (live) {
-      const u32x4* ap = (const u32x4*)((const Tmod*)ad.scale + b * ad.cols + col);
-      const u32x4* bp = (const u32x4*)((const Tmod*)ad.shift + b * ad.cols + col);
-#pragma unroll
-      for (int j = 0; j < MV; ++j) {
-        m_sc[c][j] = ap[j];
-        m_sh[c][j] = bp[j];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s1 += f[c][i];
-  }
-  const float mean = row_sum_f32(s1, shf) * inv_c;
-  float s2 = 0.0f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c) {
-    const bool live = (int64_t)c * LANES + lane < vpr;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float d = f[c][i] - mean;
-      f[c][i] = d;
-      s2 = __builtin_fmaf(d, d, s2);
-    }
-    if (!live) s2 -= 8.0f * mean * mean;   // padding lanes hold zeros: take their (0 - mean)^2 back out
-  }
-  const float var = row_sum_f32(s2, shf) * inv_c;
-  const float rstd = 1.0f / __builtin_sqrtf(var + ad.eps);
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c) {
-    const int64_t v = (int64_t)c * LANES + lane;
-    const bool live = v < vpr;
-    float t[8];
-    if (live) {
-      const int64_t col = v * 8;
-      float sc[8], sh[8], sm[8];
-      if constexpr (MOD16) {   // scale.add(1) is an fp16 op in the reference
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const uint32_t s1p = pk_add_f16(m_sc[c][0][k], 0x3C003C00u);   // scale + 1 as a (packed) fp16 add
-          sc[2 * k] = h2f(s1p & 0xFFFFu);
-          sc[2 * k + 1] = h2f(s1p >> 16);
-          sh[2 * k] = h2f(m_sh[c][0][k] & 0xFFFFu);
-          sh[2 * k + 1] = h2f(m_sh[c][0][k] >> 16);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          sc[k] = u2f(m_sc[c][0][k]) + 1.0f;
-          sc[4 + k] = u2f(m_sc[c][MV - 1][k]) + 1.0f;
-          sh[k] = u2f(m_sh[c][0][k]);
-          sh[4 + k] = u2f(m_sh[c][MV - 1][k]);
-        }
-      }
-      if (r.smooth) {
-        const u32x4* sp = (const u32x4*)(r.smooth + col);
-        u32x4 s0 = sp[0], s1v = sp[1];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          sm[k] = u2f(s0[k]);
-          sm[4 + k] = u2f(s1v[k]);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        float ln = f[c][i] * rstd;
-        float u1 = ln * sc[i];
-        float u2 = u1 + sh[i];
-        if (r.smooth) u2 = u2 * sm[i];
-        t[i] = u2;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) t[i] = 0.0f;
-    }
-    u32x4 hw;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) hw[k] = f2h2(t[2 * k], t[2 * k + 1]);
-    if (h_out && live && row_live) __builtin_nontemporal_store(hw, h_out + row * vpr + v);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) t[2 * k] = t[2 * k + 1] = 0.0f;
-    {
-      u32x4 ws[1];
-      float tt[1][8];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ws[0][k] = hw[k] ^ sx[k];
-      fwht128_h_n<1>(ws, tt, 1, lg);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) t[k] = tt[0][k];
-    }
-    u32x4 y;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) y[k] = mul2_to_h2(t[2 * k], t[2 * k + 1], r.c_h);
-    if (y_out && live && row_live) __builtin_nontemporal_store(y, y_out + row * vpr + v);
-    uint32_t m = row_max_dpp<16>(vec_absmax16(y));
-    RowScale16 s = row_scale16(m, a.fpos.gmax, a.inv_gpos);
-    if constexpr (CODES) {
-      const uint32_t cd = codes_vec16(y, lut, a.shift, s.inv, s.inv_lo);
-      if (live && row_live) {
-        ((uint32_t*)out)[row * vpr + v] = cd;
-        if (lg == 0) r.code_scales[(row * vpr + v) >> 4] = (uint16_t)(s.s16x2 & 0xFFFFu);
-      }
-    } else {
-      u32x4 o = quant_vec16<false>(y, lut, a.shift, s.inv, s.inv_lo, s.s16x2, 0.f, 0.f, 0u);
-      if (live && row_live) __builtin_nontemporal_store(o, out + row * vpr + v);
-    }
-  }
-  }   // row loop
+// level (exactly an E2M3 number, sign included) -> 6-bit code
+__host__ __device__ __forceinline__ uint32_t e2m3_of_level(float q) {
+  const uint32_t sgn = (q < 0.0f) ? 32u : 0u;
+  const float a = q < 0.0f ? -q : q;
+  uint32_t mag;
+  if (a < 1.0f) mag = (uint32_t)(a * 8.0f);                                        // subnormal: m / 8
+  else if (a < 2.0f) mag = (1u << 3) | (uint32_t)((a - 1.0f) * 8.0f);
+  else if (a < 4.0f) mag = (2u << 3) | (uint32_t)((a * 0.5f - 1.0f) * 8.0f);
+  else mag = (3u << 3) | (uint32_t)((a * 0.25f - 1.0f) * 8.0f);
+  return sgn | mag;
 }
+
+// host: OCP E4M3 byte of a value that is exactly representable (every level of the symmetric tables is)
+inline uint8_t e4m3_of(float v) {
+  if (v == 0.0f) return 0;
+  const uint8_t sgn = v < 0.0f ? 0x80 : 0;
+  int e;
+  const float m = frexpf(fabsf(v), &e);        // |v| = m * 2^e, m in [0.5, 1)
+  const int ex = e - 1;                         // |v| = (2m) * 2^(e-1), 2m in [1, 2)
+  const int man = (int)((2.0f * m - 1.0f) * 8.0f);
+  return (uint8_t)(sgn | ((ex + 7) << 3) | man);
+}
+
+// bucket -> E4M3 code tables for the fast fp16 path, one per symmetric table, built once (immutable afterwards)
+inline const Lut16Tab& lut16_codes8(int table_id) {
+  static const Lut16Tab* tabs = [] {
+    auto* t = new Lut16Tab[FPQ_NUM_TABLES]();
+    for (int id = 0; id < FPQ_NUM_TABLES; ++id) {
+      if (!kTables[id].symmetric) continue;
+      const Lut16Host& h = lut16_host(id, id);
+      if (!h.tab_valid) continue;
+      const int n = 1 << (16 - h.args.shift);
+      uint16_t full[kLutLdsEntries] = {0};
+      for (int i = 0; i < n; ++i) full[i] = e4m3_of(h2f(h.full[i]));
+      if (!lut16_compress(full, h.args.shift, &t[id])) abort();   // same structure as the level table it is derived from
+    }
+    return t;
+  }();
+  return tabs[table_id];
+}
+
+// bucket -> 6-bit E2M3 code table (the FP6 operand producers and the packed KV cache), built once (immutable afterwards)
+inline const Lut16Tab& lut16_codes6_e2m3() {
+  static const Lut16Tab* tab = [] {
+    auto* t = new Lut16Tab();
+    const Lut16Host& h = lut16_host(FPQ_E2M3, FPQ_E2M3);
+    const int n = 1 << (16 - h.args.shift);
+    uint16_t full[kLutLdsEntries] = {0};
+    for (int i = 0; i < n; ++i) full[i] = (uint16_t)e2m3_of_level(h2f(h.full[i]));
+    if (!lut16_compress(full, h.args.shift, t)) abort();
+    return t;
+  }();
+  return *tab;
+}
+
+// k-major images are addressed with 32-bit byte offsets (and int buffer ranges) by their producers: the whole image must stay below 2 GiB
+inline bool km_image_fits(int64_t rows, int64_t row_bytes) { return rows < (1ll << 31) && rows * row_bytes < (1ll << 31); }

@@ -1,7 +1,7 @@
 // fpq_fast32.h - fp32 input, rows of 128 elements: the weight-calibration hot path
 // (QuantizedLinear.from_float -> fp_quant_e{1,2,3}_per_group_cuda / fp6_quant_*_per_group_cuda on the fp32 weight,
 // tr/quant_utils.py:828-855; the driver's later var.half() fused as the fp16 output form).
-// Included by fpq_kernels.hip inside its anonymous namespace, after the generic helpers.
+// Included by fpq_kernels.hip inside its anonymous namespace, after fpq_fast16.h.
 //
 // Same results as rows_subwave_kernel<float, Tout, 32, false, U> (IEEE fp32 division + closed form, ~50 VALU ops per
 // element, 8-byte stores for fp16 output), at ~17 VALU ops per element and 16-byte accesses only:

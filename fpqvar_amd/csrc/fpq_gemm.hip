@@ -1,7 +1,7 @@
 // fpq_gemm.hip - the consumers on the far side of the quantizers and of the KV path:
 // FP4 / FP6 / FP8 matrix-core GEMMs on quantizer codes, attention over the cache, the gated residual tail.
-// Second translation unit of libfpq_hip.so; the quantizers (and the code-emitting kernels that live in the
-// fpq_gemm_*.h headers) are compiled in fpq_kernels.hip.
+// One translation unit of libfpq_hip.so; the quantizers and the code-emitting kernels that feed these consumers are compiled in
+// fpq_kernels.hip, fpq_rotate.hip and fpq_adaln.hip.
 #include "fpq_common.h"
 
 namespace {
@@ -340,17 +340,12 @@ static int gemm_fp4_gelu_dual_impl(const uint8_t* a_codes, const void* a_scales,
   if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out | (uintptr_t)gelu_out) & 15) != 0 || ((uintptr_t)bias & 7) != 0 ||
       ((uintptr_t)nan_flag & 7) != 0)
     return FPQ_ERR_ARG;
-  // the dual quantizer's table and arguments, built once by the quantizers' translation unit (immutable afterwards)
-  struct Dual { GemmFc1 xe; int rc; };
-  static const Dual dual = [] {
-    Dual d;
-    d.rc = fpq_internal_dual_lut(FPQ_E1M2_NEG, FPQ_E2M1_POS, &d.xe.a, sizeof(d.xe.a), &d.xe.tab, sizeof(d.xe.tab));
-    d.xe.h_out = nullptr;
-    d.xe.nan_flag = nullptr;
-    return d;
-  }();
-  if (dual.rc != FPQ_OK) return dual.rc;
-  GemmFc1 xe = dual.xe;
+  // the dual quantizer's table and arguments (fpq_fast16.h, lut16_host: built once, immutable afterwards)
+  const Lut16Host& dual = lut16_host(FPQ_E1M2_NEG, FPQ_E2M1_POS);
+  if (!dual.tab_valid) return FPQ_ERR_TABLE;
+  GemmFc1 xe;
+  xe.a = dual.args;
+  xe.tab = dual.tab;
   xe.h_out = (_Float16*)gelu_out;
   xe.nan_flag = (uint32_t*)nan_flag;
   const int G = (int)(k / 128);

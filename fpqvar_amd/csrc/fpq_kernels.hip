@@ -1,4 +1,7 @@
-// fpq_kernels.hip - gfx950 (MI355X) fake-quantization kernels behind include/fpq.h.
+// fpq_kernels.hip - gfx950 (MI355X) fake-quantization kernels behind include/fpq.h: the row and element quantizers, codes and
+// their decode, the KV step and pack, the option table, and their C ABI.  The library's other translation units: fpq_rotate.hip
+// (online rotation, FP8 / FP6 operand emitters), fpq_adaln.hip (the adaLN producer), fpq_gemm.hip (matrix-core consumers,
+// attention) and fpq_build_tag.hip.
 //
 // What the reference computes (PKU-SEC-Lab/FPQVAR, tr/ = models_fp_quant_transform_rotate/):
 //   quant/quant_kernel.cu:25-37        nearest entry of a value table, last index wins ties,
@@ -28,8 +31,8 @@
 #include "fpq_common.h"
 #include <string.h>
 
-// Experiment switches (fpq_common.h, FPQ_OPTION_LIST; include/fpq.h, fpq_set_option): the table both translation units
-// read.  The initialiser below is the ONLY place in the library that touches the environment.
+// Experiment switches (fpq_common.h, FPQ_OPTION_LIST; include/fpq.h, fpq_set_option): the table every translation unit
+// reads.  The initialiser below is the ONLY place in the library that touches the environment.
 int fpq_option_table[FPQ_OPT_COUNT];
 namespace {
 struct FpqOptionDesc { const char* name; int is_flag; };
@@ -291,21 +294,6 @@ __device__ __forceinline__ float negrev_shifted(float xf, float m) {
   return DT<T>::round(((xf <= 0.0f) ? xf : 0.0f) + m);
 }
 
-// (T)(x / s).  fp16: x and s carry 11-bit significands, so one residual step on x*rcp(s) lands on the
-// correctly rounded quotient (fpq_fast16.h, "exact fp16 division"); where it differs from IEEE
-// (s = 0 or non-finite: 0 / NaN instead of inf / 0) the quantizer maps both to level 0.
-template <typename T>
-__device__ __forceinline__ float div_round(float x, float s) {
-  if constexpr (sizeof(T) == 2) {
-    float inv = (s == 0.0f) ? 0.0f : __builtin_amdgcn_rcpf(s);
-    float y = x * inv;
-    float e = __builtin_fmaf(-y, s, x);
-    return DT<T>::round(__builtin_fmaf(e, inv, y));
-  } else {
-    return x / s;
-  }
-}
-
 template <typename T>
 __device__ __forceinline__ float quant_negrev(float xf, float xnr, float m, float snr, float sp, const Fmt& f) {
   float a = div_round<T>(xnr, snr);
@@ -399,12 +387,9 @@ __global__ __launch_bounds__(kBlock) void rows_negrev_scalar_kernel(const T* __r
 }
 
 #include "fpq_fast16.h"
-#include "fpq_rotate_mfma.h"
 #include "fpq_fast32.h"
-#include "fpq_adaln.h"
-#include "fpq_codes_mx.h"    // the operand-emitting quantizers of the matrix-core GEMMs (the GEMM kernels themselves,
-#include "fpq_codes_fp8.h"   // fpq_gemm_fp4.h / fp8.h / fp6.h, are compiled in fpq_gemm.hip only: an edit there does not
-#include "fpq_codes_fp6.h"   // rebuild this translation unit)
+#include "fpq_codes_mx.h"    // the FP4 operand emitter (fpq_quant_rows_codes_mx: it shares codes128_kernel with fpq_quant_rows_codes)
+#include "fpq_codes_fp8.h"   // (codes8_vec16, the 6-bit code lookup of fpq_kv_pack)
 #include "fpq_kv_codes.h"    // the packed KV cache's producer (fpq_kv_pack; its consumer is the attention kernel, fpq_gemm.hip)
 
 // ---------------------------------------------------------------------------------
@@ -953,10 +938,6 @@ int dispatch_rows(const void* x, void* out, int64_t rows, int64_t cols, int in_d
 }
 
 // ---- fast fp16 -> fp16 path (fpq_fast16.h) ------------------------------------------
-inline int table_shift16(int id) {   // rounding thresholds are multiples of 2^shift in fp16 patterns
-  return id == FPQ_INT_NEG ? 5 : 9 - kTables[id].mbits;
-}
-
 inline bool fast16_aligned(const void* x, const void* out, int64_t cols, int in_dtype, int out_dtype) {
   return in_dtype == FPQ_F16 && out_dtype == FPQ_F16 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0 &&
          cols % 8 == 0;
@@ -972,38 +953,6 @@ inline bool fast16_eligible(const void* x, const void* out, int64_t cols, int in
 // long rows: one workgroup per row, at most 8 vectors (64 halves) per lane in registers
 inline bool fast16_block_eligible(const void* x, const void* out, int64_t cols, int in_dtype, int out_dtype) {
   return fast16_aligned(x, out, cols, in_dtype, out_dtype) && cols / 8 <= (int64_t)kBlock * 8;
-}
-
-// host cache of prebuilt tables: built once per (neg, pos) pair, immutable afterwards
-struct Lut16Host {
-  Lut16Args args;
-  Lut16Tab tab;                    // the compressed image that travels in the kernel arguments
-  bool tab_valid;                  // false: kernels evaluate the closed form themselves (lut16_fill)
-  uint16_t full[kLutLdsEntries];   // the full image (host side: derived code tables are built from it)
-};
-
-inline const Lut16Host& lut16_host(int neg_id, int pos_id) {
-  static const auto* cache = [] {
-    auto* c = new Lut16Host[FPQ_NUM_TABLES * FPQ_NUM_TABLES];
-    for (int n = 0; n < FPQ_NUM_TABLES; ++n)
-      for (int p = 0; p < FPQ_NUM_TABLES; ++p) {
-        Lut16Host& h = c[n * FPQ_NUM_TABLES + p];
-        h.args.fneg = make_fmt(n);
-        h.args.fpos = make_fmt(p);
-        h.args.inv_gneg = 1.0f / h.args.fneg.gmax;
-        h.args.inv_gpos = 1.0f / h.args.fpos.gmax;
-        h.args.shift = table_shift16(n) < table_shift16(p) ? table_shift16(n) : table_shift16(p);
-        h.args.nan_flag = nullptr;
-        h.args.clip_absmax = nullptr;
-        h.args.clip_strength = 1.0f;
-        h.args.gelu_out = nullptr;
-        for (int i = 0; i < kLutLdsEntries; ++i) h.full[i] = 0;
-        lut16_build_host(h.full, h.args);
-        h.tab_valid = lut16_compress(h.full, h.args.shift, &h.tab);
-      }
-    return c;
-  }();
-  return cache[neg_id * FPQ_NUM_TABLES + pos_id];
 }
 
 // Defaults measured on MI355X with tools/kbench (cold HBM, 4 rotating 252 MB buffer pairs):
@@ -1086,228 +1035,6 @@ int launch_fast16(const void* x, void* out, int64_t rows, int64_t cols, int neg_
   }
 #undef FPQ_FAST16_CASE
   return FPQ_ERR_SHAPE;
-}
-
-inline const Lut16Tab& lut16_mx_codes_e2m1();
-
-// k-major images are addressed with 32-bit byte offsets (and int buffer ranges) by their producers: the whole image must stay below 2 GiB
-static bool km_image_fits(int64_t rows, int64_t row_bytes) { return rows < (1ll << 31) && rows * row_bytes < (1ll << 31); }
-
-template <typename Tin>
-int launch_rotate_quant(const void* x, void* out, void* rot_out, int64_t rows, int64_t cols, const float* smooth,
-                        const uint32_t sign[4], int table_id, hipStream_t st, uint16_t* code_scales = nullptr,
-                        bool km = false /* FP4 codes into a k-major image (include/fpq.h) */) {
-  const Lut16Host& h = lut16_host(table_id, table_id);
-  if (!h.tab_valid) return FPQ_ERR_TABLE;
-  const Lut16Tab& tab = code_scales ? lut16_mx_codes_e2m1() : h.tab;
-  RotArgs r;
-  r.code_scales = code_scales;
-  r.code_bits = 8;
-  r.km_rows = km ? (uint32_t)rows : 0u;
-  r.km_gpr = fast_div((uint32_t)(cols / 128));
-  if (km && (!code_scales || !km_image_fits(rows, cols / 2))) return FPQ_ERR_SHAPE;
-  r.smooth = smooth;
-  for (int i = 0; i < 4; ++i) r.sign[i] = sign[i];
-  r.c_h = h2f(f2h(1.0f / __builtin_sqrtf(128.0f)));   // torch.tensor(128).sqrt() is float32; autocast makes Q fp16
-  r.vec_per_row = cols / 8;
-  const int64_t n_vec = rows * (cols / 8);
-  const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
-  // The transform on the matrix cores (fpq_rotate_mfma.h), one 32-group tile per wavefront.
-  // Every workgroup the same number of passes over its tiles.  With a bucket table to stage per workgroup the grid is
-  // two generations of the FPQ_ROT_WAVES workgroups a CU holds (3072: 84.2 us against 85.9 for one generation, round 2).
-  // The table-free E2M1 forms have next to no prologue and want SHORT workgroups - the grid drains faster at its end:
-  // values out, 3072 / 7680 / 12288 / 16384 workgroups: 83.2 / 82.2 / 82.1 / 80.3 us (one pass each at [65536 x 1920]);
-  // codes out: 57.3 / 52.8 / 53.0 / 53.6 us (profiles/r03_rotate_grid.txt).  FPQ_ROT_WGS overrides.
-  const bool hw4 = table_id == FPQ_E2M1 && !fpq_flag(OPT_FPQ_NO_HW4);   // E2M1 values or FP4 operands: levels / codes from the conversion hardware
-  const int64_t per_wg = (int64_t)(kBlock / 64) * kRqTileVec;
-  const int64_t wg_tiles = (n_vec + per_wg - 1) / per_wg;
-  const int64_t resident_env = fpq_opt(OPT_FPQ_ROT_WGS, 0);
-  // (with a smoothing vector every workgroup stages it - 7.5 KiB at C = 1920 - so a few passes each: 7680 / 2560)
-  const int64_t resident = resident_env > 0 ? resident_env : !hw4 ? 2 * 256ll * FPQ_ROT_WAVES
-                           : smooth ? (code_scales ? 2560 : 7680) : code_scales ? 8192 : 16384;
-  const int64_t passes = (wg_tiles + resident - 1) / resident;
-  const dim3 mgrid((unsigned)((wg_tiles + passes - 1) / passes));
-#define FPQ_ROT_MFMA(EMIT, SMOOTH, ...)                                                                             \
-  hipLaunchKernelGGL((rotate_quant_mfma_kernel<Tin, EMIT, SMOOTH, ##__VA_ARGS__>), mgrid, dim3(kBlock), lds, st, x, \
-                     (u32x4*)out, (u32x4*)rot_out, n_vec, r, h.args, tab)
-  if (code_scales && hw4) { if (smooth) FPQ_ROT_MFMA(false, true, true, true); else FPQ_ROT_MFMA(false, false, true, true); }
-  else if (code_scales) { if (smooth) FPQ_ROT_MFMA(false, true, true); else FPQ_ROT_MFMA(false, false, true); }
-  else if (rot_out && hw4) { if (smooth) FPQ_ROT_MFMA(true, true, false, true); else FPQ_ROT_MFMA(true, false, false, true); }
-  else if (rot_out) { if (smooth) FPQ_ROT_MFMA(true, true); else FPQ_ROT_MFMA(true, false); }
-  else if (hw4) { if (smooth) FPQ_ROT_MFMA(false, true, false, true); else FPQ_ROT_MFMA(false, false, false, true); }
-  else { if (smooth) FPQ_ROT_MFMA(false, true); else FPQ_ROT_MFMA(false, false); }
-#undef FPQ_ROT_MFMA
-  return check_launch();
-}
-
-template <typename Tin, typename Tmod>
-int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out, int64_t rows, int64_t cols,
-                              const AdaLnArgs& ad, const float* smooth, const uint32_t sign[4], int table_id,
-                              hipStream_t st, uint16_t* code_scales = nullptr,
-                              int token_mode = 0 /*1: per-token values, 2: per-token E4M3 codes, 3: per-token packed 6-bit codes*/,
-                              const Lut16Tab* token_code_tab = nullptr,
-                              bool km = false /* FP4 / 6-bit codes into a k-major image (include/fpq.h): adaln_mfma_kernel only */) {
-  const Lut16Host& h = lut16_host(table_id, table_id);
-  if (!h.tab_valid) return FPQ_ERR_TABLE;
-  const Lut16Tab& tab = token_mode >= 2 ? *token_code_tab : (code_scales && !token_mode ? lut16_mx_codes_e2m1() : h.tab);
-  RotArgs r;
-  r.code_scales = code_scales;
-  r.code_bits = token_mode == 3 ? 6 : 8;
-  r.km_rows = km ? (uint32_t)rows : 0u;
-  r.km_gpr = fast_div((uint32_t)(cols / 128));
-  if (km) {
-    const bool fp4_codes = code_scales && !token_mode;
-    if (!(fp4_codes || token_mode == 3) || !km_image_fits(rows, token_mode == 3 ? cols / 4 * 3 : cols / 2)) return FPQ_ERR_SHAPE;
-    if (cols / 8 > 64 * 5) return FPQ_ERR_SHAPE;   // rows beyond one wavefront: the first generation writes row-major codes only
-  }
-  r.smooth = smooth;
-  for (int i = 0; i < 4; ++i) r.sign[i] = sign[i];
-  r.c_h = h2f(f2h(1.0f / __builtin_sqrtf(128.0f)));
-  r.vec_per_row = cols / 8;
-  const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
-  {
-    // fpq_adaln.h: fp16 or fp32 rows of up to 2560 channels, one batch entry per workgroup
-    constexpr bool X32 = sizeof(Tin) == 4;
-    if (r.vec_per_row <= 64 * 5) {
-      if (h.args.shift < 6) return FPQ_ERR_TABLE;   // symmetric tables only (<= 2 x 512 buckets)
-      const int64_t L = ad.rows_per_batch;
-      const int64_t n_batches = (rows + L - 1) / L;
-      const bool rows_env = fpq_opt_set(OPT_FPQ_ADALN_ROWS);
-      // Large launches: chunks of 16 rows (4 per wavefront) amortise the staging of the modulation; small launches (the
-      // early scale steps of a generation: 100 .. 3600 rows) are latency-bound and want every CU busy: one row per wavefront
-      // (profiles/r02_small_steps.json; round 4, cold inputs, 4 / 8 / 12 / 16 rows per workgroup over the ten steps of d30 and
-      // d36-512: 4 is the best or within 2 % of it up to 10 000 rows, 8 from 16 900 on - profiles/r04_adaln_rows_sweep.txt).
-      // FPQ_ADALN_ROWS=n: n rows per workgroup everywhere; FPQ_ADALN_TAIL=rows: how many rows at the end of the grid go to
-      // each of two finer tiers (8 and 4 rows per workgroup).  The tiers are OFF by default (0): they never beat a plain grid
-      // of 8 - 12 rows (profiles/r03_adaln_partition.txt); the tier decode stays reachable through the variable and is
-      // covered by tests/test_gpu_parity.py::test_adaln_tail_tiers_switch in a child process.
-      // (third generation, large launches: 8 rows = two per wavefront for the stream-bound forms - E2M1 values out, fp32
-      // rows; 12 for the forms bound by vector issue - operands out or a bucket table, from fp16 rows - where the
-      // prologue's instructions per row count: 73.3 -> 70.5 us for codes, 89.7 -> 87.1 for E4M3 bytes, 96.2 -> 93.4 for
-      // per-token E2M3 values; profiles/r03_adaln_partition.txt)
-      const bool issue_bound = !X32 && (code_scales != nullptr || token_mode != 0 || table_id != FPQ_E2M1);
-      int rows_per_wg = rows_env ? fpq_opt(OPT_FPQ_ADALN_ROWS, 0) : (rows >= 8192 ? (issue_bound && rows >= 32768 ? 12 : 8) : 4);
-      if (rows_per_wg < 1) rows_per_wg = 1;
-      // rows of exactly 8 groups (C = 1024): two rows per tile (fpq_adaln.h, PAIR2) - workgroups of an even number of rows
-      const bool pair2 = !X32 && r.vec_per_row == 128 && token_mode == 0 && !h_out && !y_out &&
-                         !fpq_flag(OPT_FPQ_ADALN_NO_PAIR2);
-      if (pair2) rows_per_wg = rows_env ? ((rows_per_wg + 1) & ~1) : (rows >= 8192 ? 16 : 8);
-      const int64_t per_batch = (L + rows_per_wg - 1) / rows_per_wg;
-      if (n_batches * per_batch > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
-      AdalnTiers tiers = {};
-      const int tail_rows = fpq_opt(OPT_FPQ_ADALN_TAIL, 0);
-      int64_t nb2 = 0, nb1 = 0;
-      if (tail_rows > 0 && rows_per_wg > 4) {
-        nb2 = (tail_rows + L - 1) / L;                                   // batch entries cut into chunks of 4 rows
-        if (rows_per_wg > 8) nb1 = (tail_rows + L - 1) / L;              // ... of 8 rows
-        if (nb2 > n_batches) nb2 = n_batches;
-        if (nb1 > n_batches - nb2) nb1 = n_batches - nb2;
-      }
-      tiers.rows[0] = rows_per_wg;
-      tiers.rows[1] = 8;
-      tiers.rows[2] = 4;
-      for (int t = 0; t < 3; ++t) tiers.per_batch[t] = (int)((L + tiers.rows[t] - 1) / tiers.rows[t]);
-      tiers.batches[0] = (int)(n_batches - nb1 - nb2);
-      tiers.batches[1] = (int)nb1;
-      {
-        const int64_t nb_of[3] = {n_batches - nb1 - nb2, nb1, nb2};
-        for (int t = 0; t < 3; ++t) {   // id / d == (id * ceil(2^32 / d)) >> 32 whenever id * d < 2^32
-          const uint64_t d = (uint64_t)tiers.per_batch[t], ids = (uint64_t)nb_of[t] * d;
-          tiers.magic[t] = (d >= 2 && ids * d < (1ull << 32)) ? (uint32_t)(((1ull << 32) + d - 1) / d) : 0u;
-        }
-      }
-      const int64_t n_wg3 = (int64_t)tiers.batches[0] * tiers.per_batch[0] + nb1 * tiers.per_batch[1] + nb2 * tiers.per_batch[2];
-      if (n_wg3 > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
-      const dim3 g3((unsigned)n_wg3);
-      const size_t lds2 = 0;   // table, modulation planes and images live in static LDS
-      // E2M1 values per group: levels from the FP4 conversion hardware, no table (fpq_adaln.h)
-      const bool hw4 = table_id == FPQ_E2M1 && !token_mode && !fpq_flag(OPT_FPQ_NO_HW4);
-      const bool tight_ok = FPQ_ADALN_TIGHT && !fpq_flag(OPT_FPQ_ADALN_NO_TIGHT);
-      // E2M3 / E3M2 values (per group, or per token: token_mode 1): levels from the FP6 conversion hardware, no table
-      const int hw6 = (token_mode <= 1 && !code_scales && !fpq_flag(OPT_FPQ_NO_HW6)) ? (table_id == FPQ_E2M3 ? 1 : table_id == FPQ_E3M2 ? 2 : 0) : 0;
-#define FPQ_ADALN3(M, CODES, EMIT, TOKEN, HW4, TIGHT)                                                                  \
-  hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, CODES, EMIT, TOKEN, X32, HW4, TIGHT>), g3, dim3(kBlock), lds2, st,    \
-                     (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab, tiers)
-#define FPQ_ADALN2K(M, CODES, EMIT, TOKEN)                                                                             \
-  do {                                                                                                                 \
-    if constexpr ((M == 4 || M == 5) && !(CODES) && !(EMIT)) {   /* E2M3 / E3M2 values, rows of 13 .. 20 groups: hardware levels */ \
-      if (hw6 == 1) {                                                                                                  \
-        hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 1>), g3,      \
-                           dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,         \
-                           rows, ad, r, h.args, tab, tiers);                                                           \
-        break;                                                                                                         \
-      }                                                                                                                \
-      if (hw6 == 2) {                                                                                                  \
-        hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 2>), g3,      \
-                           dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,         \
-                           rows, ad, r, h.args, tab, tiers);                                                           \
-        break;                                                                                                         \
-      }                                                                                                                \
-    }                                                                                                                  \
-    if constexpr (M == 2 && !X32 && !(EMIT) && !(TOKEN)) {                                                             \
-      if (pair2) {                                                                                                     \
-        if (hw4)                                                                                                       \
-          hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, 4, CODES, false, false, false, true, false, 4, true>), g3,       \
-                             dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,       \
-                             rows, ad, r, h.args, tab, tiers);                                                         \
-        else                                                                                                           \
-          hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, 4, CODES, false, false, false, false, false, 4, true>), g3,      \
-                             dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,       \
-                             rows, ad, r, h.args, tab, tiers);                                                         \
-        break;                                                                                                         \
-      }                                                                                                                \
-    }                                                                                                                  \
-    if constexpr (!(TOKEN)) {                                                                                          \
-      if constexpr (M == 4 && !X32 && !(EMIT) && !(CODES)) {                                                           \
-        if (hw4 && tight_ok && r.vec_per_row == 240) {   /* VAR-d30: 31 KiB of LDS, five workgroups per CU */          \
-          FPQ_ADALN3(M, CODES, EMIT, TOKEN, true, true);                                                               \
-          break;                                                                                                       \
-        }                                                                                                              \
-      }                                                                                                                \
-      if (hw4) {                                                                                                       \
-        FPQ_ADALN3(M, CODES, EMIT, TOKEN, true, false);                                                                \
-        break;                                                                                                         \
-      }                                                                                                                \
-    }                                                                                                                  \
-    FPQ_ADALN3(M, CODES, EMIT, TOKEN, false, false);                                                                   \
-  } while (0)
-#ifdef FPQ_ADALN_STAMPS
-#define FPQ_ADALN_EMIT (h_out != nullptr)   /* diagnostic build: y_out alone is the stamp buffer */
-#else
-#define FPQ_ADALN_EMIT (h_out || y_out)
-#endif
-#define FPQ_ADALN2(M)                                                                                                  \
-  do {                                                                                                                 \
-    const bool emit = FPQ_ADALN_EMIT;                                                                                  \
-    if (token_mode >= 2) FPQ_ADALN2K(M, true, false, true);                                                            \
-    else if (token_mode == 1 && emit) FPQ_ADALN2K(M, false, true, true);                                               \
-    else if (token_mode == 1) FPQ_ADALN2K(M, false, false, true);                                                      \
-    else if (code_scales) FPQ_ADALN2K(M, true, false, false);                                                          \
-    else if (emit) FPQ_ADALN2K(M, false, true, false);                                                                 \
-    else FPQ_ADALN2K(M, false, false, false);                                                                          \
-  } while (0)
-      switch ((int)((r.vec_per_row + 63) / 64)) {   // MAXC = ceil(vectors per row / 64), exactly
-        case 1: FPQ_ADALN2(1); break;
-        case 2: FPQ_ADALN2(2); break;
-        case 3: FPQ_ADALN2(3); break;
-        case 4: FPQ_ADALN2(4); break;
-        default: FPQ_ADALN2(5); break;
-      }
-#undef FPQ_ADALN3
-#undef FPQ_ADALN2
-#undef FPQ_ADALN2K
-      return check_launch();
-    }
-  }
-  // rows beyond one wavefront (2560 < C <= 4096, per group only): the first generation, one workgroup per row
-  const dim3 g((unsigned)(rows < 8192 ? rows : 8192));   // every workgroup stages the table once, then walks rows
-  if (code_scales)
-    hipLaunchKernelGGL((adaln_rotate_quant16_kernel<Tin, Tmod, true>), g, dim3(kBlock), lds, st, x, (u32x4*)out,
-                       (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab);
-  else
-    hipLaunchKernelGGL((adaln_rotate_quant16_kernel<Tin, Tmod, false>), g, dim3(kBlock), lds, st, x, (u32x4*)out,
-                       (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab);
-  return check_launch();
 }
 
 template <bool DUAL>
@@ -1467,28 +1194,6 @@ int launch_rows32(const void* x, void* out, int64_t rows, int64_t cols, int tabl
 #undef FPQ_R32
 }
 
-// ---- F2: hardware-nibble codes + FP4 MFMA GEMM ---------------------------------------
-inline const Lut16Tab& lut16_mx_codes_e2m1() {
-  static const Lut16Tab* tab = [] {
-    auto* t = new Lut16Tab;
-    const Lut16Host& h = lut16_host(FPQ_E2M1, FPQ_E2M1);
-    const int n = 1 << (16 - h.args.shift);
-    uint16_t full[kLutLdsEntries] = {0};
-    for (int i = 0; i < n; ++i) {
-      uint32_t u = (uint32_t)i << h.args.shift;
-      bool neg = (u >> 15) != 0;
-      float qm = quant_mag(h2f(u & 0x7FFFu), 0u, h.args.fpos);
-      // level -> magnitude index 0..7 (host twin of level_index)
-      int li = (qm >= h.args.fpos.kmin) ? (int)((fbits(qm) >> h.args.fpos.mshift) - h.args.fpos.kmin_code_base)
-                                        : (int)(qm * h.args.fpos.inv_step0);
-      full[i] = (uint16_t)(li | ((neg && li != 0) ? 8 : 0));
-    }
-    if (!lut16_compress(full, h.args.shift, t)) abort();   // E2M1: 2 x 128 buckets, always fits
-    return t;
-  }();
-  return *tab;
-}
-
 }  // namespace
 
 // =================================================================================
@@ -1526,20 +1231,6 @@ int launch_negrev(const void* x, void* out, int64_t rows, int64_t cols, const Fm
 extern "C" {
 
 int fpq_version(void) { return FPQ_VERSION; }
-
-#ifndef FPQ_BUILD_TAG
-#define FPQ_BUILD_TAG "stock"
-#endif
-const char* fpq_build_tag(void) { return FPQ_BUILD_TAG; }
-
-int fpq_internal_dual_lut(int neg_table, int pos_table, void* args_out, size_t args_bytes, void* tab_out, size_t tab_bytes) {
-  if (neg_table < 0 || neg_table >= FPQ_NUM_TABLES || pos_table < 0 || pos_table >= FPQ_NUM_TABLES) return FPQ_ERR_TABLE;
-  const Lut16Host& h = lut16_host(neg_table, pos_table);
-  if (!h.tab_valid || args_bytes != sizeof(Lut16Args) || tab_bytes != sizeof(Lut16Tab)) return FPQ_ERR_TABLE;
-  memcpy(args_out, &h.args, sizeof(Lut16Args));
-  memcpy(tab_out, &h.tab, sizeof(Lut16Tab));
-  return FPQ_OK;
-}
 
 int fpq_internal_zero_if_flag(void* out, int64_t n_bytes, void* scratch, void* stream) {
   hipLaunchKernelGGL(zero_if_flag_kernel, dim3(kFixupBlocks), dim3(kBlock), 0, (hipStream_t)stream, (uint8_t*)out, n_bytes, (uint32_t*)scratch);
@@ -1923,23 +1614,6 @@ int fpq_quant_rows_neg_reverse(const void* x, void* out, int64_t rows, int64_t c
   return launch_negrev<float>(x, out, rows, cols, make_fmt(table_id), (hipStream_t)stream);
 }
 
-static int rotate_quant_impl(const void* x, void* out, void* rotated_out, void* code_scales, int64_t rows, int64_t cols,
-                             int in_dtype, const float* smooth, const uint32_t* sign_mask_host, int table_id,
-                             fpq_stream_t stream, bool km = false) {
-  if (rows < 0 || cols < 0 || !sign_mask_host) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
-  if (cols % 128 != 0) return FPQ_ERR_SHAPE;
-  if (rows == 0 || cols == 0) return FPQ_OK;
-  if (!x || !out) return FPQ_ERR_ARG;
-  if ((((uintptr_t)x | (uintptr_t)out | (uintptr_t)rotated_out | (uintptr_t)smooth) & 15) != 0) return FPQ_ERR_ARG;
-  if (in_dtype == FPQ_F16)
-    return launch_rotate_quant<_Float16>(x, out, rotated_out, rows, cols, smooth, sign_mask_host, table_id,
-                                         (hipStream_t)stream, (uint16_t*)code_scales, km);
-  return launch_rotate_quant<float>(x, out, rotated_out, rows, cols, smooth, sign_mask_host, table_id,
-                                    (hipStream_t)stream, (uint16_t*)code_scales, km);
-}
-
 int fpq_quant_rows_dual_argmin(const void* x, float* out, int64_t rows, int64_t cols, int neg_table, int pos_table,
                                int in_dtype, const void* clip_absmax, float clip_strength, fpq_stream_t stream) {
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
@@ -1956,83 +1630,6 @@ int fpq_quant_rows_dual_argmin(const void* x, float* out, int64_t rows, int64_t 
   dual.clip_strength = clip_strength;
   dual.nan_flag = nullptr;
   return dispatch_rows<true>(x, out, rows, cols, in_dtype, FPQ_F32, dual.fneg, dual, (hipStream_t)stream);
-}
-
-int fpq_rotate_quant_rows(const void* x, void* out, void* rotated_out, int64_t rows, int64_t cols, int in_dtype,
-                          const float* smooth, const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
-  return rotate_quant_impl(x, out, rotated_out, nullptr, rows, cols, in_dtype, smooth, sign_mask_host, table_id, stream);
-}
-
-int fpq_rotate_quant_rows_codes_mx(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
-                                   const float* smooth, const uint32_t* sign_mask_host, fpq_stream_t stream) {
-  if (rows > 0 && cols > 0 && !scales) return FPQ_ERR_ARG;
-  return rotate_quant_impl(x, codes, nullptr, scales, rows, cols, in_dtype, smooth, sign_mask_host, FPQ_E2M1, stream);
-}
-int fpq_rotate_quant_rows_codes_mx_km(const void* x, uint8_t* image, void* scales, int64_t rows, int64_t cols, int in_dtype,
-                                      const float* smooth, const uint32_t* sign_mask_host, fpq_stream_t stream) {
-  if (rows > 0 && cols > 0 && !scales) return FPQ_ERR_ARG;
-  return rotate_quant_impl(x, image, nullptr, scales, rows, cols, in_dtype, smooth, sign_mask_host, FPQ_E2M1, stream, true);
-}
-
-static int adaln_rotate_quant_impl(const void* x, void* out, void* h_out, void* rotated_out, void* code_scales,
-                                   int64_t rows, int64_t cols, int in_dtype, const void* scale, const void* shift,
-                                   int mod_dtype, int64_t rows_per_batch, float eps, const float* smooth,
-                                   const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream,
-                                   int token_mode = 0, const Lut16Tab* token_code_tab = nullptr, bool km = false) {
-  if (rows < 0 || cols < 0 || rows_per_batch <= 0 || !sign_mask_host) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if ((in_dtype != FPQ_F16 && in_dtype != FPQ_F32) || (mod_dtype != FPQ_F16 && mod_dtype != FPQ_F32))
-    return FPQ_ERR_DTYPE;
-  if (cols % 128 != 0 || cols > 4096) return FPQ_ERR_SHAPE;
-  if (rows == 0 || cols == 0) return FPQ_OK;
-  if (!x || !out || !scale || !shift) return FPQ_ERR_ARG;
-  if ((((uintptr_t)x | (uintptr_t)out | (uintptr_t)h_out | (uintptr_t)rotated_out | (uintptr_t)scale |
-        (uintptr_t)shift | (uintptr_t)smooth) & 15) != 0)
-    return FPQ_ERR_ARG;
-  AdaLnArgs ad;
-  ad.scale = scale;
-  ad.shift = shift;
-  ad.mod_is_f16 = mod_dtype == FPQ_F16;
-  ad.rows_per_batch = rows_per_batch;
-  ad.eps = eps;
-  ad.cols = cols;
-  // One wavefront per row while the row fits 5 vectors per lane (C <= 2560: no barrier in the row
-  // loop; measured 0.180 ms vs 0.199 ms per [65500 x 1920] on MI355X), one workgroup per row beyond.
-  if (token_mode && cols / 8 > 64 * 5) return FPQ_ERR_SHAPE;   // the per-token form keeps a row inside one wavefront: C <= 2560
-  hipStream_t st = (hipStream_t)stream;
-#define FPQ_GO(TI, TM) return launch_adaln_rotate_quant<TI, TM>(x, out, h_out, rotated_out, rows, cols, ad, smooth, \
-                                                              sign_mask_host, table_id, st, (uint16_t*)code_scales, \
-                                                              token_mode, token_code_tab, km)
-  if (in_dtype == FPQ_F16 && mod_dtype == FPQ_F16) FPQ_GO(_Float16, _Float16);
-  if (in_dtype == FPQ_F16) FPQ_GO(_Float16, float);
-  if (mod_dtype == FPQ_F16) FPQ_GO(float, _Float16);
-  FPQ_GO(float, float);
-#undef FPQ_GO
-}
-
-int fpq_adaln_rotate_quant_rows(const void* x, void* out, void* h_out, void* rotated_out, int64_t rows, int64_t cols,
-                                int in_dtype, const void* scale, const void* shift, int mod_dtype,
-                                int64_t rows_per_batch, float eps, const float* smooth,
-                                const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
-  return adaln_rotate_quant_impl(x, out, h_out, rotated_out, nullptr, rows, cols, in_dtype, scale, shift, mod_dtype,
-                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream);
-}
-
-int fpq_adaln_rotate_quant_rows_codes_mx(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols,
-                                         int in_dtype, const void* scale, const void* shift, int mod_dtype,
-                                         int64_t rows_per_batch, float eps, const float* smooth,
-                                         const uint32_t* sign_mask_host, fpq_stream_t stream) {
-  if (rows > 0 && cols > 0 && !scales) return FPQ_ERR_ARG;
-  return adaln_rotate_quant_impl(x, codes, nullptr, nullptr, scales, rows, cols, in_dtype, scale, shift, mod_dtype,
-                                 rows_per_batch, eps, smooth, sign_mask_host, FPQ_E2M1, stream);
-}
-int fpq_adaln_rotate_quant_rows_codes_mx_km(const void* x, uint8_t* image, void* scales, int64_t rows, int64_t cols,
-                                            int in_dtype, const void* scale, const void* shift, int mod_dtype,
-                                            int64_t rows_per_batch, float eps, const float* smooth,
-                                            const uint32_t* sign_mask_host, fpq_stream_t stream) {
-  if (rows > 0 && cols > 0 && !scales) return FPQ_ERR_ARG;
-  return adaln_rotate_quant_impl(x, image, nullptr, nullptr, scales, rows, cols, in_dtype, scale, shift, mod_dtype,
-                                 rows_per_batch, eps, smooth, sign_mask_host, FPQ_E2M1, stream, 0, nullptr, true);
 }
 
 static int quant_rows_codes_mx_impl(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
@@ -2066,165 +1663,6 @@ int fpq_quant_rows_codes_mx(const void* x, uint8_t* codes, void* scales, int64_t
 int fpq_quant_rows_codes_mx_km(const void* x, uint8_t* image, void* scales, int64_t rows, int64_t cols, int in_dtype,
                                fpq_stream_t stream) {
   return quant_rows_codes_mx_impl(x, image, scales, rows, cols, in_dtype, true, stream);
-}
-
-// host: OCP E4M3 byte of a value that is exactly representable (every level of the symmetric tables is)
-static uint8_t e4m3_of(float v) {
-  if (v == 0.0f) return 0;
-  const uint8_t sgn = v < 0.0f ? 0x80 : 0;
-  int e;
-  const float m = frexpf(fabsf(v), &e);        // |v| = m * 2^e, m in [0.5, 1)
-  const int ex = e - 1;                         // |v| = (2m) * 2^(e-1), 2m in [1, 2)
-  const int man = (int)((2.0f * m - 1.0f) * 8.0f);
-  return (uint8_t)(sgn | ((ex + 7) << 3) | man);
-}
-
-// bucket -> E4M3 code tables for the fast fp16 path, one per symmetric table, built once (immutable afterwards)
-static const Lut16Tab& lut16_codes8(int table_id) {
-  static const Lut16Tab* tabs = [] {
-    auto* t = new Lut16Tab[FPQ_NUM_TABLES]();
-    for (int id = 0; id < FPQ_NUM_TABLES; ++id) {
-      if (!kTables[id].symmetric) continue;
-      const Lut16Host& h = lut16_host(id, id);
-      if (!h.tab_valid) continue;
-      const int n = 1 << (16 - h.args.shift);
-      uint16_t full[kLutLdsEntries] = {0};
-      for (int i = 0; i < n; ++i) full[i] = e4m3_of(h2f(h.full[i]));
-      if (!lut16_compress(full, h.args.shift, &t[id])) abort();   // same structure as the level table it is derived from
-    }
-    return t;
-  }();
-  return tabs[table_id];
-}
-
-int fpq_quant_rows_codes_fp8(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
-                             int in_dtype, fpq_stream_t stream) {
-  if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
-  if (rows == 0 || cols == 0) return FPQ_OK;
-  if (!x || !codes || !scales) return FPQ_ERR_ARG;
-  if (in_dtype == FPQ_F16 && cols % 8 == 0 && cols <= 4096 && (((uintptr_t)x | (uintptr_t)codes) & 15) == 0 &&
-      lut16_host(table_id, table_id).tab_valid) {
-    const Lut16Host& h = lut16_host(table_id, table_id);
-    const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
-    const int64_t wgs = (rows + kBlock / 64 - 1) / (kBlock / 64);
-    const dim3 gw(grid_for(wgs, 8192));
-    const int maxc = (int)((cols / 8 + 63) / 64);
-    hipStream_t st = (hipStream_t)stream;
-#define FPQ_C8(M) hipLaunchKernelGGL((rows16_codes8_wave_kernel<M>), gw, dim3(kBlock), lds, st, (const uint16_t*)x, codes, \
-                                     (uint16_t*)scales, rows, cols, h.args, lut16_codes8(table_id))
-    if (maxc <= 2) FPQ_C8(2);
-    else if (maxc <= 4) FPQ_C8(4);
-    else FPQ_C8(8);
-#undef FPQ_C8
-    return check_launch();
-  }
-  const dim3 g(grid_for(rows, 65535));
-  if (in_dtype == FPQ_F16)
-    hipLaunchKernelGGL(rows_codes_fp8_kernel<_Float16>, g, dim3(kBlock), 0, (hipStream_t)stream, (const _Float16*)x,
-                       codes, (_Float16*)scales, rows, cols, make_fmt(table_id));
-  else
-    hipLaunchKernelGGL(rows_codes_fp8_kernel<float>, g, dim3(kBlock), 0, (hipStream_t)stream, (const float*)x, codes,
-                       (float*)scales, rows, cols, make_fmt(table_id));
-  return check_launch();
-}
-
-int fpq_adaln_rotate_quant_token_rows(const void* x, void* out, void* h_out, void* rotated_out, void* row_scales,
-                                      int64_t rows, int64_t cols, int in_dtype, const void* scale, const void* shift,
-                                      int mod_dtype, int64_t rows_per_batch, float eps, const float* smooth,
-                                      const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
-  if ((((uintptr_t)row_scales) & 1) != 0) return FPQ_ERR_ARG;
-  return adaln_rotate_quant_impl(x, out, h_out, rotated_out, row_scales, rows, cols, in_dtype, scale, shift, mod_dtype,
-                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 1, nullptr);
-}
-
-int fpq_adaln_rotate_quant_token_rows_codes_fp8(const void* x, uint8_t* codes, void* row_scales, int64_t rows, int64_t cols,
-                                                int in_dtype, const void* scale, const void* shift, int mod_dtype,
-                                                int64_t rows_per_batch, float eps, const float* smooth,
-                                                const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
-  if (rows > 0 && cols > 0 && !row_scales) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  return adaln_rotate_quant_impl(x, codes, nullptr, nullptr, row_scales, rows, cols, in_dtype, scale, shift, mod_dtype,
-                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 2, &lut16_codes8(table_id));
-}
-
-static const Lut16Tab& lut16_codes6_e2m3() {
-  static const Lut16Tab* tab = [] {
-    auto* t = new Lut16Tab();
-    const Lut16Host& h = lut16_host(FPQ_E2M3, FPQ_E2M3);
-    const int n = 1 << (16 - h.args.shift);
-    uint16_t full[kLutLdsEntries] = {0};
-    for (int i = 0; i < n; ++i) full[i] = (uint16_t)e2m3_of_level(h2f(h.full[i]));
-    if (!lut16_compress(full, h.args.shift, t)) abort();
-    return t;
-  }();
-  return *tab;
-}
-
-int fpq_adaln_rotate_quant_token_rows_codes_fp6(const void* x, uint8_t* codes, void* row_scales, int64_t rows, int64_t cols,
-                                                int in_dtype, const void* scale, const void* shift, int mod_dtype,
-                                                int64_t rows_per_batch, float eps, const float* smooth,
-                                                const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
-  if (rows > 0 && cols > 0 && !row_scales) return FPQ_ERR_ARG;
-  if (table_id != FPQ_E2M3) return FPQ_ERR_TABLE;
-  if (cols % 32 != 0) return FPQ_ERR_SHAPE;
-  if ((((uintptr_t)codes) & 7) != 0) return FPQ_ERR_ARG;
-  return adaln_rotate_quant_impl(x, codes, nullptr, nullptr, row_scales, rows, cols, in_dtype, scale, shift, mod_dtype,
-                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 3, &lut16_codes6_e2m3());
-}
-int fpq_adaln_rotate_quant_token_rows_codes_fp6_km(const void* x, uint8_t* image, void* row_scales, int64_t rows, int64_t cols,
-                                                   int in_dtype, const void* scale, const void* shift, int mod_dtype,
-                                                   int64_t rows_per_batch, float eps, const float* smooth,
-                                                   const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
-  if (rows > 0 && cols > 0 && !row_scales) return FPQ_ERR_ARG;
-  if (table_id != FPQ_E2M3) return FPQ_ERR_TABLE;
-  if (cols % 128 != 0) return FPQ_ERR_SHAPE;
-  return adaln_rotate_quant_impl(x, image, nullptr, nullptr, row_scales, rows, cols, in_dtype, scale, shift, mod_dtype,
-                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 3, &lut16_codes6_e2m3(), true);
-}
-
-static int quant_rows_codes_fp6_impl(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
-                                     int in_dtype, bool km, fpq_stream_t stream) {
-  if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (table_id != FPQ_E2M3) return FPQ_ERR_TABLE;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
-  if (cols % 32 != 0 || (km && (cols % 128 != 0 || !km_image_fits(rows, cols / 4 * 3)))) return FPQ_ERR_SHAPE;
-  const uint32_t km_rows = km ? (uint32_t)rows : 0u;
-  if (rows == 0 || cols == 0) return FPQ_OK;
-  if (!x || !codes || !scales) return FPQ_ERR_ARG;
-  if ((((uintptr_t)codes) & 7) != 0) return FPQ_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  if (in_dtype == FPQ_F16 && cols <= 8192 && (((uintptr_t)x) & 15) == 0) {
-    const Lut16Host& h = lut16_host(table_id, table_id);
-    const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
-    const int64_t wgs = (rows + kBlock / 64 - 1) / (kBlock / 64);
-    const dim3 gw(grid_for(wgs, 8192));
-    const int maxc = (int)((cols / 32 + 63) / 64);
-#define FPQ_C6(M) hipLaunchKernelGGL((rows16_codes6_wave_kernel<M>), gw, dim3(kBlock), lds, st, (const uint16_t*)x, codes, \
-                                     (uint16_t*)scales, rows, cols, h.args, lut16_codes6_e2m3(), km_rows)
-    if (maxc <= 1) FPQ_C6(1);
-    else if (maxc <= 2) FPQ_C6(2);
-    else FPQ_C6(4);
-#undef FPQ_C6
-    return check_launch();
-  }
-  const dim3 g(grid_for(rows, 65535));
-  if (in_dtype == FPQ_F16)
-    hipLaunchKernelGGL(rows_codes_fp6_kernel<_Float16>, g, dim3(kBlock), 0, st, (const _Float16*)x, codes,
-                       (_Float16*)scales, rows, cols, make_fmt(table_id), km_rows);
-  else
-    hipLaunchKernelGGL(rows_codes_fp6_kernel<float>, g, dim3(kBlock), 0, st, (const float*)x, codes, (float*)scales, rows,
-                       cols, make_fmt(table_id), km_rows);
-  return check_launch();
-}
-int fpq_quant_rows_codes_fp6(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
-                             int in_dtype, fpq_stream_t stream) {
-  return quant_rows_codes_fp6_impl(x, codes, scales, rows, cols, table_id, in_dtype, false, stream);
-}
-int fpq_quant_rows_codes_fp6_km(const void* x, uint8_t* image, void* scales, int64_t rows, int64_t cols, int table_id,
-                                int in_dtype, fpq_stream_t stream) {
-  return quant_rows_codes_fp6_impl(x, image, scales, rows, cols, table_id, in_dtype, true, stream);
 }
 
 int fpq_kv_pack(uint8_t* codes, void* scales, int kv_bit, int64_t batch, int64_t max_len, int64_t heads, int64_t head_dim, int64_t pos,

@@ -1,0 +1,173 @@
+// fpq_rotate.hip - the online rotation in front of the per-group quantizer (fpq_rotate_quant_rows*, the transform on the
+// matrix cores: fpq_rotate_mfma.h) and the operand emitters of the row-scaled FP8 / FP6 GEMMs (fpq_quant_rows_codes_fp8 /
+// _fp6*: fpq_codes_fp8.h, fpq_codes_fp6.h), with their C ABI.  The FP4 emitter, fpq_quant_rows_codes_mx, stays with the
+// codes of fpq_kernels.hip, whose codes128_kernel its fp32 form launches.
+#include "fpq_common.h"
+
+namespace {
+#include "fpq_fast16.h"
+#include "fpq_rotate_mfma.h"
+#include "fpq_codes_fp8.h"
+#include "fpq_codes_fp6.h"
+
+template <typename Tin>
+int launch_rotate_quant(const void* x, void* out, void* rot_out, int64_t rows, int64_t cols, const float* smooth,
+                        const uint32_t sign[4], int table_id, hipStream_t st, uint16_t* code_scales = nullptr,
+                        bool km = false /* FP4 codes into a k-major image (include/fpq.h) */) {
+  const Lut16Host& h = lut16_host(table_id, table_id);
+  if (!h.tab_valid) return FPQ_ERR_TABLE;
+  const Lut16Tab& tab = code_scales ? lut16_mx_codes_e2m1() : h.tab;
+  RotArgs r;
+  r.code_scales = code_scales;
+  r.code_bits = 8;
+  r.km_rows = km ? (uint32_t)rows : 0u;
+  r.km_gpr = fast_div((uint32_t)(cols / 128));
+  if (km && (!code_scales || !km_image_fits(rows, cols / 2))) return FPQ_ERR_SHAPE;
+  r.smooth = smooth;
+  for (int i = 0; i < 4; ++i) r.sign[i] = sign[i];
+  r.c_h = h2f(f2h(1.0f / __builtin_sqrtf(128.0f)));   // torch.tensor(128).sqrt() is float32; autocast makes Q fp16
+  r.vec_per_row = cols / 8;
+  const int64_t n_vec = rows * (cols / 8);
+  const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
+  // The transform on the matrix cores (fpq_rotate_mfma.h), one 32-group tile per wavefront.
+  // Every workgroup the same number of passes over its tiles.  With a bucket table to stage per workgroup the grid is
+  // two generations of the FPQ_ROT_WAVES workgroups a CU holds (3072: 84.2 us against 85.9 for one generation, round 2).
+  // The table-free E2M1 forms have next to no prologue and want SHORT workgroups - the grid drains faster at its end:
+  // values out, 3072 / 7680 / 12288 / 16384 workgroups: 83.2 / 82.2 / 82.1 / 80.3 us (one pass each at [65536 x 1920]);
+  // codes out: 57.3 / 52.8 / 53.0 / 53.6 us (profiles/r03_rotate_grid.txt).  FPQ_ROT_WGS overrides.
+  const bool hw4 = table_id == FPQ_E2M1 && !fpq_flag(OPT_FPQ_NO_HW4);   // E2M1 values or FP4 operands: levels / codes from the conversion hardware
+  const int64_t per_wg = (int64_t)(kBlock / 64) * kRqTileVec;
+  const int64_t wg_tiles = (n_vec + per_wg - 1) / per_wg;
+  const int64_t resident_env = fpq_opt(OPT_FPQ_ROT_WGS, 0);
+  // (with a smoothing vector every workgroup stages it - 7.5 KiB at C = 1920 - so a few passes each: 7680 / 2560)
+  const int64_t resident = resident_env > 0 ? resident_env : !hw4 ? 2 * 256ll * FPQ_ROT_WAVES
+                           : smooth ? (code_scales ? 2560 : 7680) : code_scales ? 8192 : 16384;
+  const int64_t passes = (wg_tiles + resident - 1) / resident;
+  const dim3 mgrid((unsigned)((wg_tiles + passes - 1) / passes));
+#define FPQ_ROT_MFMA(EMIT, SMOOTH, ...)                                                                             \
+  hipLaunchKernelGGL((rotate_quant_mfma_kernel<Tin, EMIT, SMOOTH, ##__VA_ARGS__>), mgrid, dim3(kBlock), lds, st, x, \
+                     (u32x4*)out, (u32x4*)rot_out, n_vec, r, h.args, tab)
+  if (code_scales && hw4) { if (smooth) FPQ_ROT_MFMA(false, true, true, true); else FPQ_ROT_MFMA(false, false, true, true); }
+  else if (code_scales) { if (smooth) FPQ_ROT_MFMA(false, true, true); else FPQ_ROT_MFMA(false, false, true); }
+  else if (rot_out && hw4) { if (smooth) FPQ_ROT_MFMA(true, true, false, true); else FPQ_ROT_MFMA(true, false, false, true); }
+  else if (rot_out) { if (smooth) FPQ_ROT_MFMA(true, true); else FPQ_ROT_MFMA(true, false); }
+  else if (hw4) { if (smooth) FPQ_ROT_MFMA(false, true, false, true); else FPQ_ROT_MFMA(false, false, false, true); }
+  else { if (smooth) FPQ_ROT_MFMA(false, true); else FPQ_ROT_MFMA(false, false); }
+#undef FPQ_ROT_MFMA
+  return check_launch();
+}
+
+}  // namespace
+
+extern "C" {
+
+static int rotate_quant_impl(const void* x, void* out, void* rotated_out, void* code_scales, int64_t rows, int64_t cols,
+                             int in_dtype, const float* smooth, const uint32_t* sign_mask_host, int table_id,
+                             fpq_stream_t stream, bool km = false) {
+  if (rows < 0 || cols < 0 || !sign_mask_host) return FPQ_ERR_ARG;
+  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
+  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (cols % 128 != 0) return FPQ_ERR_SHAPE;
+  if (rows == 0 || cols == 0) return FPQ_OK;
+  if (!x || !out) return FPQ_ERR_ARG;
+  if ((((uintptr_t)x | (uintptr_t)out | (uintptr_t)rotated_out | (uintptr_t)smooth) & 15) != 0) return FPQ_ERR_ARG;
+  if (in_dtype == FPQ_F16)
+    return launch_rotate_quant<_Float16>(x, out, rotated_out, rows, cols, smooth, sign_mask_host, table_id,
+                                         (hipStream_t)stream, (uint16_t*)code_scales, km);
+  return launch_rotate_quant<float>(x, out, rotated_out, rows, cols, smooth, sign_mask_host, table_id,
+                                    (hipStream_t)stream, (uint16_t*)code_scales, km);
+}
+
+int fpq_rotate_quant_rows(const void* x, void* out, void* rotated_out, int64_t rows, int64_t cols, int in_dtype,
+                          const float* smooth, const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
+  return rotate_quant_impl(x, out, rotated_out, nullptr, rows, cols, in_dtype, smooth, sign_mask_host, table_id, stream);
+}
+
+int fpq_rotate_quant_rows_codes_mx(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
+                                   const float* smooth, const uint32_t* sign_mask_host, fpq_stream_t stream) {
+  if (rows > 0 && cols > 0 && !scales) return FPQ_ERR_ARG;
+  return rotate_quant_impl(x, codes, nullptr, scales, rows, cols, in_dtype, smooth, sign_mask_host, FPQ_E2M1, stream);
+}
+int fpq_rotate_quant_rows_codes_mx_km(const void* x, uint8_t* image, void* scales, int64_t rows, int64_t cols, int in_dtype,
+                                      const float* smooth, const uint32_t* sign_mask_host, fpq_stream_t stream) {
+  if (rows > 0 && cols > 0 && !scales) return FPQ_ERR_ARG;
+  return rotate_quant_impl(x, image, nullptr, scales, rows, cols, in_dtype, smooth, sign_mask_host, FPQ_E2M1, stream, true);
+}
+
+int fpq_quant_rows_codes_fp8(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
+                             int in_dtype, fpq_stream_t stream) {
+  if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
+  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
+  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (rows == 0 || cols == 0) return FPQ_OK;
+  if (!x || !codes || !scales) return FPQ_ERR_ARG;
+  if (in_dtype == FPQ_F16 && cols % 8 == 0 && cols <= 4096 && (((uintptr_t)x | (uintptr_t)codes) & 15) == 0 &&
+      lut16_host(table_id, table_id).tab_valid) {
+    const Lut16Host& h = lut16_host(table_id, table_id);
+    const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
+    const int64_t wgs = (rows + kBlock / 64 - 1) / (kBlock / 64);
+    const dim3 gw(grid_for(wgs, 8192));
+    const int maxc = (int)((cols / 8 + 63) / 64);
+    hipStream_t st = (hipStream_t)stream;
+#define FPQ_C8(M) hipLaunchKernelGGL((rows16_codes8_wave_kernel<M>), gw, dim3(kBlock), lds, st, (const uint16_t*)x, codes, \
+                                     (uint16_t*)scales, rows, cols, h.args, lut16_codes8(table_id))
+    if (maxc <= 2) FPQ_C8(2);
+    else if (maxc <= 4) FPQ_C8(4);
+    else FPQ_C8(8);
+#undef FPQ_C8
+    return check_launch();
+  }
+  const dim3 g(grid_for(rows, 65535));
+  if (in_dtype == FPQ_F16)
+    hipLaunchKernelGGL(rows_codes_fp8_kernel<_Float16>, g, dim3(kBlock), 0, (hipStream_t)stream, (const _Float16*)x,
+                       codes, (_Float16*)scales, rows, cols, make_fmt(table_id));
+  else
+    hipLaunchKernelGGL(rows_codes_fp8_kernel<float>, g, dim3(kBlock), 0, (hipStream_t)stream, (const float*)x, codes,
+                       (float*)scales, rows, cols, make_fmt(table_id));
+  return check_launch();
+}
+
+static int quant_rows_codes_fp6_impl(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
+                                     int in_dtype, bool km, fpq_stream_t stream) {
+  if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
+  if (table_id != FPQ_E2M3) return FPQ_ERR_TABLE;
+  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (cols % 32 != 0 || (km && (cols % 128 != 0 || !km_image_fits(rows, cols / 4 * 3)))) return FPQ_ERR_SHAPE;
+  const uint32_t km_rows = km ? (uint32_t)rows : 0u;
+  if (rows == 0 || cols == 0) return FPQ_OK;
+  if (!x || !codes || !scales) return FPQ_ERR_ARG;
+  if ((((uintptr_t)codes) & 7) != 0) return FPQ_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (in_dtype == FPQ_F16 && cols <= 8192 && (((uintptr_t)x) & 15) == 0) {
+    const Lut16Host& h = lut16_host(table_id, table_id);
+    const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
+    const int64_t wgs = (rows + kBlock / 64 - 1) / (kBlock / 64);
+    const dim3 gw(grid_for(wgs, 8192));
+    const int maxc = (int)((cols / 32 + 63) / 64);
+#define FPQ_C6(M) hipLaunchKernelGGL((rows16_codes6_wave_kernel<M>), gw, dim3(kBlock), lds, st, (const uint16_t*)x, codes, \
+                                     (uint16_t*)scales, rows, cols, h.args, lut16_codes6_e2m3(), km_rows)
+    if (maxc <= 1) FPQ_C6(1);
+    else if (maxc <= 2) FPQ_C6(2);
+    else FPQ_C6(4);
+#undef FPQ_C6
+    return check_launch();
+  }
+  const dim3 g(grid_for(rows, 65535));
+  if (in_dtype == FPQ_F16)
+    hipLaunchKernelGGL(rows_codes_fp6_kernel<_Float16>, g, dim3(kBlock), 0, st, (const _Float16*)x, codes,
+                       (_Float16*)scales, rows, cols, make_fmt(table_id), km_rows);
+  else
+    hipLaunchKernelGGL(rows_codes_fp6_kernel<float>, g, dim3(kBlock), 0, st, (const float*)x, codes, (float*)scales, rows,
+                       cols, make_fmt(table_id), km_rows);
+  return check_launch();
+}
+int fpq_quant_rows_codes_fp6(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
+                             int in_dtype, fpq_stream_t stream) {
+  return quant_rows_codes_fp6_impl(x, codes, scales, rows, cols, table_id, in_dtype, false, stream);
+}
+int fpq_quant_rows_codes_fp6_km(const void* x, uint8_t* image, void* scales, int64_t rows, int64_t cols, int table_id,
+                                int in_dtype, fpq_stream_t stream) {
+  return quant_rows_codes_fp6_impl(x, image, scales, rows, cols, table_id, in_dtype, true, stream);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // fpq_rotate_mfma.h - the online rotate in front of the per-group quantizer with the 128-point Hadamard transform
-// on the matrix cores.  Included by fpq_kernels.hip after fpq_fast16.h.
+// on the matrix cores.  Included by fpq_rotate.hip and fpq_adaln.hip after fpq_fast16.h.
 //
 // Why: the butterfly form (rotate_quant16_kernel) is bound by vector-instruction issue, not by memory
 // (profiles/r02_pmc_rotate_butterfly.txt: 22 VALU instructions per element, 8.5 of them the butterfly, the vector pipe ~80 %

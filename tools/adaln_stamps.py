@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where a wavefront's row time goes in the adaLN producer: needs a library built with -DFPQ_ADALN_STAMPS
-(tools/build_variant.sh stamps -DFPQ_ADALN_STAMPS), whose kernel sums s_memtime differences per phase and wavefront.
+(tools/build_variant.sh --unit fpq_adaln stamps -DFPQ_ADALN_STAMPS), whose kernel sums s_memtime differences per phase and wavefront.
 usage: adaln_stamps.py tools/ab/libstamps.so [fp16|fp32] [B L C] [cold]
 "cold": the stamped launch works on a tensor the caches have not seen (a 512 MiB write in front of it), as a launch of a
 hipGraph over rotating inputs does (bench.generation_steps); default: the 30th launch on the same tensor."""

@@ -125,6 +125,9 @@ def disassembly(elf, kernels):
             ins = f"s_addc_u32 s{m.group(1)}, s{m.group(1)}, @pcrel"
         if ins:
             out[cur].append(ins)
+    for ins in out.values():   # "..." after the last instruction: the zero fill up to the next symbol, which moves with the layout
+        while ins and ins[-1] == "...":
+            ins.pop()
     return out
 
 

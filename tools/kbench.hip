@@ -4,6 +4,7 @@
 // input distributions, then times variants interleaved in one process next to a
 // plain 16-byte copy (the practical HBM ceiling on the same device).
 #include "../fpqvar_amd/csrc/fpq_kernels.hip"
+#include "../fpqvar_amd/csrc/fpq_rotate.hip"   // fpq_rotate_quant_rows
 
 #include <cstdio>
 #include <functional>
