@@ -396,10 +396,29 @@ int fpq_gemm_fp4_gelu_dual_km(const uint8_t* a_image, const void* a_scales, cons
 
 static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,
                               const void* w_scales, int w_scale_dtype, const void* bias, void* out, int64_t tokens,
-                              int64_t outs, int64_t k, const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream) {
+                              int64_t outs, int64_t k, const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream,
+                              const fpq_gemm_split_t* split = nullptr, const GemmQkNorm* qkn = nullptr) {
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   GemmEpi epi;
   if (int rc = gemm_epilogue(epilogue, tokens, &epi)) return rc;
+  if (split) {   // the outputs leave in column parts, each to its own rows (include/fpq.h); every part is held to the header's 8-byte alignment
+    if (epilogue || split->n_parts < 1 || split->n_parts > 3 || split->part_cols <= 0 || split->part_cols % 128 != 0 ||
+        outs != split->n_parts * split->part_cols || split->rows_per_batch < 1 || split->rows_per_batch > 0x7FFFFFFF ||
+        tokens % split->rows_per_batch != 0)
+      return FPQ_ERR_ARG;
+    epi.sp_cols = (int)split->part_cols;
+    epi.sp_rpb = (int)split->rows_per_batch;
+    for (int p = 0; p < split->n_parts; ++p) {
+      if (!split->out[p] || ((uintptr_t)split->out[p] & 7) != 0 || split->row_stride[p] < split->part_cols || split->row_stride[p] % 4 != 0 ||
+          split->batch_stride[p] < 0 || split->row0[p] < 0)
+        return FPQ_ERR_ARG;
+      epi.sp_out[p] = (_Float16*)split->out[p];
+      epi.sp_stride[p] = split->row_stride[p];
+      epi.sp_bstride[p] = split->batch_stride[p];
+      epi.sp_row0[p] = split->row0[p];
+    }
+    out = split->out[0];   // (not written through: every tile belongs to a part)
+  }
   if (km) {
     if (outs + 63 > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
     epi.km_w_rows = (int)((outs + 63) / 64 * 64);
@@ -409,7 +428,7 @@ static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int 
     return FPQ_ERR_DTYPE;
   if (tokens == 0 || outs == 0) return FPQ_OK;
   if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
-  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out) & 15) != 0) return FPQ_ERR_ARG;
+  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (split ? 0 : (uintptr_t)out)) & 15) != 0) return FPQ_ERR_ARG;
   // the LDS-DMA pieces address a tile by a 32-bit lane offset (row inside the tile x row bytes + chunk): the 256-row tile's
   // last row must stay below 2^32 (k above ~22 M would wrap and read wrong rows silently)
   if (255 * (k * 3 / 4) + 128 >= (1ll << 32)) return FPQ_ERR_SHAPE;
@@ -417,15 +436,19 @@ static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int 
   // FPQ_GEMM6_CFG 0: 128 x 128 tiles, 1: 256 x 128 (default for tall problems)
   // 256 x 128 tiles from 4096 tokens on for the wide Linears, from 32768 on for outs < 4096 (tools/gemm_small_steps.py fp6)
   const int cfg6 = fpq_opt_set(OPT_FPQ_GEMM6_CFG) ? fpq_opt(OPT_FPQ_GEMM6_CFG, 0) : (tokens >= 4096 && (outs >= 4096 || tokens >= 32768) ? 1 : 0);
+#define FPQ_GO6X(TA, TW, MT, NT, XE, xe)                                                                            \
+  hipLaunchKernelGGL((gemm_fp6_rows_kernel<TA, TW, MT, NT, XE>), dim3((unsigned)n_wg), dim3(256), Cfg::lds(), st,   \
+                     a_codes, (const TA*)a_scales, w_codes, (const TW*)w_scales, (const _Float16*)bias,              \
+                     (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, xe)
 #define FPQ_GO6(TA, TW, MT, NT)                                                                                     \
   do {                                                                                                               \
     using Cfg = GemmFp6Cfg<MT, NT>;                                                                                  \
     const int64_t n_col = (outs + Cfg::BN - 1) / Cfg::BN, n_row = (tokens + Cfg::BM - 1) / Cfg::BM;                  \
     const int64_t n_wg = 8 * ((n_col + 7) / 8) * n_row;                                                              \
     if (n_wg > 0x7FFFFFFF) return FPQ_ERR_SHAPE;                                                                     \
-    hipLaunchKernelGGL((gemm_fp6_rows_kernel<TA, TW, MT, NT>), dim3((unsigned)n_wg), dim3(256), Cfg::lds(), st,     \
-                       a_codes, (const TA*)a_scales, w_codes, (const TW*)w_scales, (const _Float16*)bias,            \
-                       (_Float16*)out, (int)tokens, (int)outs, (int)k, epi);                                              \
+    if (qkn) FPQ_GO6X(TA, TW, MT, NT, GemmQkNorm, *qkn);                                                             \
+    else if (split) FPQ_GO6X(TA, TW, MT, NT, GemmSplit, GemmSplit{});                                                \
+    else FPQ_GO6X(TA, TW, MT, NT, GemmNoFc1, GemmNoFc1{});                                                           \
   } while (0)
 #define FPQ_GO6T(MT, NT)                                                                                             \
   do {                                                                                                               \
@@ -438,6 +461,7 @@ static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int 
   else FPQ_GO6T(4, 4);
 #undef FPQ_GO6T
 #undef FPQ_GO6
+#undef FPQ_GO6X
   return check_launch();
 }
 int fpq_gemm_fp6_rows_ex(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,
@@ -449,6 +473,24 @@ int fpq_gemm_fp6_rows_km(const uint8_t* a_image, const void* a_scales, int a_sca
                          const void* w_scales, int w_scale_dtype, const void* bias, void* out, int64_t tokens,
                          int64_t outs, int64_t k, const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream) {
   return gemm_fp6_rows_impl(a_image, a_scales, a_scale_dtype, w_image, w_scales, w_scale_dtype, bias, out, tokens, outs, k, epilogue, true, stream);
+}
+
+int fpq_gemm_fp6_rows_split(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes, const void* w_scales,
+                            int w_scale_dtype, const void* bias, int64_t tokens, int64_t outs, int64_t k, const fpq_gemm_split_t* split,
+                            int kmajor, fpq_stream_t stream) {
+  if (!split) return FPQ_ERR_ARG;
+  return gemm_fp6_rows_impl(a_codes, a_scales, a_scale_dtype, w_codes, w_scales, w_scale_dtype, bias, nullptr, tokens, outs, k, nullptr,
+                            kmajor != 0, stream, split);
+}
+int fpq_gemm_fp6_rows_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,
+                                   const void* w_scales, int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
+                                   const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream) {
+  // parts q, k, v of heads of 64 columns; the fp32 bias is read four outputs (16 bytes) at a time
+  if (!split || split->n_parts != 3) return FPQ_ERR_ARG;
+  if (!q_head_scale || ((uintptr_t)q_head_scale & 3) != 0 || ((uintptr_t)bias & 15) != 0) return FPQ_ERR_ARG;
+  const GemmQkNorm qkn{bias, q_head_scale};
+  return gemm_fp6_rows_impl(a_codes, a_scales, a_scale_dtype, w_codes, w_scales, w_scale_dtype, nullptr, nullptr, tokens, outs, k, nullptr,
+                            kmajor != 0, stream, split, &qkn);
 }
 
 // Row-major codes -> k-major image (include/fpq.h): one thread per 16-byte chunk of the image.  seg = bytes of a row per K step of

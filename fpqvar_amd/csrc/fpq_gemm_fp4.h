@@ -46,7 +46,7 @@ struct GemmEpi {
   // K-MAJOR OPERAND IMAGES (include/fpq.h, "k-major operand images"; the FP4 and FP6 LDS-DMA kernels): 0 = row-major codes,
   // else the image rows of the weight side (outs rounded up to 64; the activation side has exactly T).
   int km_w_rows;
-  // SPLIT OUTPUT (include/fpq.h, fpq_gemm_split_t; the FP4 LDS-DMA kernel's plain epilogue): sp_cols != 0: the outputs are sp_cols-wide
+  // SPLIT OUTPUT (include/fpq.h, fpq_gemm_split_t; the FP4 LDS-DMA kernel's plain epilogue, the FP6 kernel's GemmSplit / GemmQkNorm): sp_cols != 0: the outputs are sp_cols-wide
   // column parts with a destination each - token t = b * sp_rpb + l of part p goes to row b * sp_bstride[p] + sp_row0[p] + l of
   // sp_out[p] (sp_stride[p] elements per row).  mat_qkv writes q to its own tensor and k, v straight into the KV cache's slots.
   int sp_cols, sp_rpb;
@@ -362,6 +362,23 @@ FPQ_NOPK __device__ __forceinline__ float row_sum16(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));   // row_mirror
   return v;
 }
+
+// The q / k norm of one (token, head) row, shared by the FP4 and FP6 GEMMs' split epilogues (include/fpq.h, "THE Q / K L2 NORM"):
+// yf_ = a lane's NT consecutive values of the row (float[NT]), the 16 lanes of its DPP row hold the head's 64; q rows (part_ == 0)
+// are scaled by s_h_.  (A macro: as an inlined function the same lines leave the FP4 kernel with its multiplies' operands swapped.)
+#define FPQ_QK_NORM_ROW(yf_, part_, s_h_)                                                                           \
+  do {                                                                                                              \
+    float ss = (yf_)[0] * (yf_)[0];                                                                                 \
+    _Pragma("unroll") for (int n = 1; n < NT; ++n) ss = __builtin_fmaf((yf_)[n], (yf_)[n], ss);                     \
+    float nrm = __builtin_sqrtf(row_sum16(ss));                                                                     \
+    nrm = nrm < 1e-12f ? 1e-12f : nrm;   /* clamp_min(eps) (a NaN stays a NaN) */                                   \
+    const float inv = 1.0f / nrm;                                                                                   \
+    _Pragma("unroll") for (int n = 0; n < NT; ++n) {                                                                \
+      float q = (yf_)[n] * inv;                                                                                     \
+      q = __builtin_fmaf(__builtin_fmaf(-q, nrm, (yf_)[n]), inv, q);                                                \
+      (yf_)[n] = (part_) == 0 ? q * (s_h_) : q;                                                                     \
+    }                                                                                                               \
+  } while (0)
 
 // One step of the maxima's reduce-scatter over the 16 lanes of a DPP row: rows r and r + N / 2 are paired, a lane keeps the
 // one its bit selects and hands the other to its partner (DPP control CTRL), taking the partner's in return: N rows in, N / 2
@@ -721,20 +738,7 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4
         float yf[NT];
 #pragma unroll
         for (int n = 0; n < NT; ++n) yf[n] = (float)(_Float16)acc[m][n][i] + qkn_b[n];
-        if (part < 2) {   // uniform over the tile
-          float ss = yf[0] * yf[0];
-#pragma unroll
-          for (int n = 1; n < NT; ++n) ss = __builtin_fmaf(yf[n], yf[n], ss);
-          float nrm = __builtin_sqrtf(row_sum16(ss));
-          nrm = nrm < 1e-12f ? 1e-12f : nrm;   // clamp_min(eps) (a NaN stays a NaN)
-          const float inv = 1.0f / nrm;
-#pragma unroll
-          for (int n = 0; n < NT; ++n) {
-            float q = yf[n] * inv;
-            q = __builtin_fmaf(__builtin_fmaf(-q, nrm, yf[n]), inv, q);
-            yf[n] = part == 0 ? q * qkn_s : q;
-          }
-        }
+        if (part < 2) FPQ_QK_NORM_ROW(yf, part, qkn_s);   // uniform over the tile
 #pragma unroll
         for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)yf[n];
       }

@@ -40,13 +40,17 @@ __device__ unsigned long long* g_gemm6_stamps;   // [wavefronts][8]: wait for th
 #define FPQ_ST6(k) do { } while (0)
 #endif
 
-template <typename Tsa, typename Tsw, int MT, int NT>
+// XE = GemmNoFc1: the plain epilogue (+ gate / residual tail); XE = GemmSplit: the split output (GemmEpi's sp_* fields);
+// XE = GemmQkNorm: the split output with the q / k norm (fpq_gemm_fp4.h), as in gemm_fp4_glds_kernel.
+struct GemmSplit {};
+template <typename Tsa, typename Tsw, int MT, int NT, typename XE = GemmNoFc1>
 __global__ __launch_bounds__(256, 2) FPQ_NOPK void gemm_fp6_rows_kernel(const uint8_t* __restrict__ A,
                                                                        const Tsa* __restrict__ sa,
                                                                        const uint8_t* __restrict__ W,
                                                                        const Tsw* __restrict__ sw,
                                                                        const _Float16* __restrict__ bias,
-                                                                       _Float16* out, int T, int O, int C, GemmEpi epi) {
+                                                                       _Float16* out, int T, int O, int C, GemmEpi epi, XE xe) {
+  constexpr bool SPLIT = __is_same(XE, GemmSplit), QKN = __is_same(XE, GemmQkNorm);
   constexpr int WR = 2, WC = 2, BM = 16 * MT * WR, BN = 16 * NT * WC;
   static_assert(BM % 32 == 0 && BN % 32 == 0, "tiles are made of 32-row super-blocks");
   constexpr int ASB = BM / 32, BSB = BN / 32, NSB = ASB + BSB, STAGE = NSB * 3072;
@@ -107,6 +111,13 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void gemm_fp6_rows_kernel(const ui
 #define FPQ_GLDS6_ISSUE(s, buf) _Pragma("unroll") for (int i_ = 0; i_ < PIECES; ++i_) FPQ_GLDS6_ONE(s, buf, i_)
   FPQ_GLDS6_ISSUE(0, 0);
   FPQ_GEMM_ROWS_STAGE_SCALES(STAGE);
+  v4f_t qkn_b = v4f_t{0, 0, 0, 0};   // (QKN) the fp32 bias of the lane's four outputs and s_h of the wavefront's head in part 0, requested here
+  float qkn_s = 1.0f;
+  if constexpr (QKN) {
+    const int o = o0 + wn * (16 * NT) + NT * (lane & 15);
+    if (xe.bias) qkn_b = *(const v4f_t*)(xe.bias + (o < O ? o : O - 4));
+    if (o0 < epi.sp_cols) qkn_s = xe.q_scale[(o0 + wn * (16 * NT)) >> 6];
+  }
 
   v4f_t acc[MT][NT];
 #pragma unroll
@@ -168,7 +179,11 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void gemm_fp6_rows_kernel(const ui
   }
 #undef FPQ_GLDS6_ISSUE
 #undef FPQ_GLDS6_ONE
-  FPQ_GEMM_ROWS_EPILOGUE();
+  if constexpr (SPLIT || QKN) {
+    FPQ_GEMM_ROWS_EPILOGUE_SPLIT(QKN, qkn_b, qkn_s);
+  } else {
+    FPQ_GEMM_ROWS_EPILOGUE();
+  }
 #ifdef FPQ_GEMM6_STAMPS
   FPQ_ST6(5);
   if (lane == 0 && g_gemm6_stamps) {

@@ -83,6 +83,60 @@
     }                                                                                                               \
   } while (0)
 
+// The SPLIT forms of the epilogue above (GemmEpi's sp_* fields; include/fpq.h, fpq_gemm_split_t), lanes and rounding unchanged: the
+// tile lies inside one sp_cols-wide column part (sp_cols % 128 == 0) and its rows go to that part's destination, addressed as in
+// gemm_fp4_glds_kernel - one division per tile while a batch entry spans the wavefront's rows, a comparison per row.  No gate, no
+// residual.  QKN_ (a compile-time constant): y16 = half(acc * scales + 0) as the plain epilogue writes it without a bias, then the
+// q / k norm of GemmQkNorm over a token row's head = the 16 lanes of a DPP row (FPQ_QK_NORM_ROW, fpq_gemm_fp4.h), with qkn_b_ the
+// lane's four fp32 bias values and qkn_s_ its head's s_h.
+#define FPQ_GEMM_ROWS_EPILOGUE_SPLIT(QKN_, qkn_b_, qkn_s_)                                                          \
+  do {                                                                                                              \
+    static_assert(NT == 4, "the epilogue packs a lane's NT results of one row into one 8-byte store");              \
+    constexpr int WROWS_ = 16 * MT, WCOLS_ = 16 * NT;                                                               \
+    const int o_ = o0 + wn * WCOLS_ + NT * (lane & 15);                                                             \
+    const int oc_ = o_ < O ? o_ : O - 4;                                                                            \
+    const v4f_t sc_ = *(const v4f_t*)(lsc + wn * WCOLS_ + NT * (lane & 15));                                        \
+    const v4f_t b_ = *(const v4f_t*)(lsb + wn * WCOLS_ + NT * (lane & 15));                                         \
+    const int part_ = o0 / epi.sp_cols;                                                                             \
+    _Float16* const sp_base_ = part_ == 0 ? epi.sp_out[0] : part_ == 1 ? epi.sp_out[1] : epi.sp_out[2];             \
+    const int64_t sp_stride_ = part_ == 0 ? epi.sp_stride[0] : part_ == 1 ? epi.sp_stride[1] : epi.sp_stride[2];    \
+    const int64_t sp_bstride_ = part_ == 0 ? epi.sp_bstride[0] : part_ == 1 ? epi.sp_bstride[1] : epi.sp_bstride[2]; \
+    const int64_t sp_row0_ = part_ == 0 ? epi.sp_row0[0] : part_ == 1 ? epi.sp_row0[1] : epi.sp_row0[2];            \
+    const bool sp_far_ = epi.sp_rpb >= WROWS_;                                                                      \
+    const int first_ = t0 + wm * WROWS_ + 4 * (lane >> 4);                                                          \
+    const int sb0_ = first_ / epi.sp_rpb, sr0_ = first_ - sb0_ * epi.sp_rpb;                                        \
+    const int oc_l_ = oc_ - part_ * epi.sp_cols;                                                                    \
+    _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                                \
+      const int t_first_ = first_ + m * 16;                                                                         \
+      const v4f_t sr_ = *(const v4f_t*)(lsr + wm * WROWS_ + m * 16 + 4 * (lane >> 4));                              \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                               \
+        fpq_h4_t y_;                                                                                                \
+        if constexpr (QKN_) {                                                                                       \
+          float yf_[NT];                                                                                            \
+          _Pragma("unroll") for (int n = 0; n < NT; ++n)                                                            \
+              yf_[n] = (float)(_Float16)(acc[m][n][i] * (sr_[i] * sc_[n]) + 0.0f) + (qkn_b_)[n];                    \
+          if (part_ < 2) FPQ_QK_NORM_ROW(yf_, part_, (qkn_s_));   /* uniform over the tile */                         \
+          _Pragma("unroll") for (int n = 0; n < NT; ++n) y_[n] = (_Float16)yf_[n];                                  \
+        } else {                                                                                                    \
+          _Pragma("unroll") for (int n = 0; n < NT; ++n) y_[n] = (_Float16)(acc[m][n][i] * (sr_[i] * sc_[n]) + b_[n]); \
+        }                                                                                                           \
+        const int off_ = sr0_ + m * 16 + i;                                                                         \
+        int bb_, ll_;                                                                                               \
+        if (sp_far_) {                                                                                              \
+          const int wrap_ = off_ >= epi.sp_rpb ? 1 : 0;                                                             \
+          bb_ = sb0_ + wrap_;                                                                                       \
+          ll_ = off_ - wrap_ * epi.sp_rpb;                                                                          \
+        } else {                                                                                                    \
+          bb_ = (t_first_ + i) / epi.sp_rpb;                                                                        \
+          ll_ = (t_first_ + i) - bb_ * epi.sp_rpb;                                                                  \
+        }                                                                                                           \
+        if (t_first_ + i < T && o_ < O)                                                                             \
+          __builtin_nontemporal_store(__builtin_bit_cast(u32x2, y_),                                                \
+                                      (u32x2*)(sp_base_ + ((int64_t)bb_ * sp_bstride_ + sp_row0_ + ll_) * sp_stride_ + oc_l_)); \
+      }                                                                                                             \
+    }                                                                                                               \
+  } while (0)
+
 FPQ_NOPK __device__ __forceinline__ int fp8_chunk_swz(int r) { return ((r >> 1) & 1) + ((r >> 3) << 2); }
 
 template <typename Tsa, typename Tsw, int MT, int NT>

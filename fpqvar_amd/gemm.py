@@ -219,6 +219,43 @@ def linear_fp4(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Ten
     return out
 
 
+def _qkv_split_args(name: str, cache_kv: torch.Tensor, tokens: int, outs: int, bias: Optional[torch.Tensor], pos: int, seq: int,
+                    qk_norm_scale: Optional[torch.Tensor]):
+    """The destination side of a mat_qkv with a split output, shared by the FP4 and FP6 forms: checks that the problem fits the cache
+    and the bias / head scale rules, allocates q -> (q, fpq_gemm_split_t, bias or None, head scale or None)."""
+    from ._lib import GemmSplit
+    dev = cache_kv.device
+    _, bsz, max_len, heads, hd = cache_kv.shape
+    c = heads * hd
+    if outs != 3 * c or c % 128 != 0 or seq < 1 or tokens != bsz * seq or pos < 0 or pos + seq > max_len:
+        raise RuntimeError(f"{name}: {tokens} tokens x {outs} outputs do not fit a cache of [{bsz}, {max_len}, {heads}, {hd}] at {pos} .. {pos + seq}")
+    q = torch.empty((bsz, seq, c), dtype=torch.float16, device=dev)
+    b = hs = None
+    if qk_norm_scale is not None:
+        if hd != 64:
+            raise RuntimeError(f"{name}: the q / k norm needs head_dim 64, the cache has {hd}")
+        if qk_norm_scale.dtype != torch.float32 or qk_norm_scale.numel() != heads or qk_norm_scale.device != dev:
+            raise RuntimeError(f"{name}: qk_norm_scale must be a float32 tensor of {heads} values on the operands' device")
+        hs = qk_norm_scale.detach().reshape(-1).contiguous()
+        if bias is not None:
+            if bias.dtype != torch.float32 or bias.numel() != outs or bias.device != dev:
+                raise RuntimeError(f"{name}: with qk_norm_scale the bias must be a float32 tensor of {outs} values on the operands' device")
+            b = bias.detach().reshape(-1).contiguous()
+            if b.data_ptr() % 16:
+                b = b.clone()
+    elif bias is not None:
+        if bias.numel() != outs or bias.device != dev:
+            raise RuntimeError(f"{name}: bias must hold one value per output on the operands' device")
+        b = bias.detach().to(torch.float16).reshape(-1).contiguous()
+        if b.data_ptr() % 16:
+            b = b.clone()
+    sp = GemmSplit()
+    sp.part_cols, sp.n_parts, sp.rows_per_batch = c, 3, seq
+    for p, (t, bstride, row0) in enumerate(((q, seq, 0), (cache_kv[0], max_len, pos), (cache_kv[1], max_len, pos))):
+        sp.out[p], sp.row_stride[p], sp.batch_stride[p], sp.row0[p] = t.data_ptr(), c, bstride, row0
+    return q, sp, b, hs
+
+
 def linear_fp4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
                             bias: Optional[torch.Tensor], cache_kv: torch.Tensor, pos: int, seq: int,
                             qk_norm_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -231,7 +268,6 @@ def linear_fp4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_cod
     qk_norm_scale: fp32 [H] (kv_cache.qk_norm_head_scale) - the attention block has attn_l2_norm (fpq_gemm_fp4_mx_split_qknorm):
     y = float(fp16 Linear output) + bias (fp32 [3C] or None: q_bias, 0, v_bias, added after the fp16 rounding), q =
     F.normalize(y_q) * qk_norm_scale per head, k = F.normalize(y_k) into the cache, v = y_v (tr/basic_var.py:173-183), head_dim 64."""
-    from ._lib import GemmSplit
     require_gpu(a_codes, "linear_fp4_qkv_to_cache")
     km = _kmajor_pair("linear_fp4_qkv_to_cache", a_codes, w_codes, 64)
     dev = a_codes.device
@@ -247,32 +283,7 @@ def linear_fp4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_cod
             raise RuntimeError("linear_fp4_qkv_to_cache: operand shapes / activation scale dtype mismatch")
         _check_operand("linear_fp4_qkv_to_cache(activation)", a_codes, a_scales, tokens, k // 2, tokens * (k // 128), dev)
         _check_operand("linear_fp4_qkv_to_cache(weight)", w_codes, w_scales, outs, k // 2, outs * (k // 128), dev)
-    if outs != 3 * c or c % 128 != 0 or seq < 1 or tokens != bsz * seq or pos < 0 or pos + seq > max_len:
-        raise RuntimeError(f"linear_fp4_qkv_to_cache: {tokens} tokens x {outs} outputs do not fit a cache of [{bsz}, {max_len}, {heads}, {hd}] at {pos} .. {pos + seq}")
-    q = torch.empty((bsz, seq, c), dtype=torch.float16, device=dev)
-    b = None
-    if qk_norm_scale is not None:
-        if hd != 64:
-            raise RuntimeError(f"linear_fp4_qkv_to_cache: the q / k norm needs head_dim 64, the cache has {hd}")
-        if qk_norm_scale.dtype != torch.float32 or qk_norm_scale.numel() != heads or qk_norm_scale.device != dev:
-            raise RuntimeError(f"linear_fp4_qkv_to_cache: qk_norm_scale must be a float32 tensor of {heads} values on the operands' device")
-        hs = qk_norm_scale.detach().reshape(-1).contiguous()
-        if bias is not None:
-            if bias.dtype != torch.float32 or bias.numel() != outs or bias.device != dev:
-                raise RuntimeError(f"linear_fp4_qkv_to_cache: with qk_norm_scale the bias must be a float32 tensor of {outs} values on the operands' device")
-            b = bias.detach().reshape(-1).contiguous()
-            if b.data_ptr() % 16:
-                b = b.clone()
-    elif bias is not None:
-        if bias.numel() != outs or bias.device != dev:
-            raise RuntimeError("linear_fp4_qkv_to_cache: bias must hold one value per output on the operands' device")
-        b = bias.detach().to(torch.float16).reshape(-1).contiguous()
-        if b.data_ptr() % 16:
-            b = b.clone()
-    sp = GemmSplit()
-    sp.part_cols, sp.n_parts, sp.rows_per_batch = c, 3, seq
-    for p, (t, bstride, row0) in enumerate(((q, seq, 0), (cache_kv[0], max_len, pos), (cache_kv[1], max_len, pos))):
-        sp.out[p], sp.row_stride[p], sp.batch_stride[p], sp.row0[p] = t.data_ptr(), c, bstride, row0
+    q, sp, b, hs = _qkv_split_args("linear_fp4_qkv_to_cache", cache_kv, tokens, outs, bias, pos, seq, qk_norm_scale)
     if tokens and qk_norm_scale is not None:
         with device_guard(dev):
             check(lib().fpq_gemm_fp4_mx_split_qknorm(a_codes.data_ptr(), a_scales.data_ptr(), w_codes.data_ptr(), w_scales.data_ptr(),
@@ -533,6 +544,46 @@ def linear_fp6(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Ten
                  stream_ptr(a_codes.device)), what)
     del keep
     return out
+
+
+def linear_fp6_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
+                            bias: Optional[torch.Tensor], cache_kv: torch.Tensor, pos: int, seq: int,
+                            qk_norm_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """linear_fp4_qkv_to_cache for the row-scaled FP6 operands of linear_fp6 (fpq_gemm_fp6_rows_split): q comes back - fp16
+    [B, seq, C] - and k, v are written straight into `cache_kv` [2, B, max_len, H, c] at token positions pos .. pos + seq, each value
+    bit for bit the one linear_fp6(a, w, bias) holds there.  Operands row-major (2-D) or k-major images (3-D), scales float16 or
+    float32 as in linear_fp6.  qk_norm_scale (fp32 [H]) and the fp32 bias [3C] it goes with: the q / k norm in the epilogue
+    (fpq_gemm_fp6_rows_split_qknorm), exactly as linear_fp4_qkv_to_cache states it."""
+    name = "linear_fp6_qkv_to_cache"
+    require_gpu(a_codes, name)
+    km = _kmajor_pair(name, a_codes, w_codes, 96)
+    dev = a_codes.device
+    if cache_kv.dim() != 5 or cache_kv.shape[0] != 2 or cache_kv.dtype != torch.float16 or not cache_kv.is_contiguous() or cache_kv.device != dev:
+        raise RuntimeError(f"{name}: cache_kv must be a contiguous float16 [2, B, max_len, H, c] tensor on the operands' device")
+    if km:
+        tokens, outs, k = a_codes.shape[1], w_scales.shape[0], a_codes.shape[0] * 128
+        w_rows, row_bytes = (outs + 63) // 64 * 64, a_codes.shape[0] * 96
+    else:
+        tokens, outs, k = a_codes.shape[0], w_codes.shape[0], a_codes.shape[1] * 4 // 3
+        w_rows, row_bytes = outs, a_codes.shape[1]
+        if w_codes.shape[1] != a_codes.shape[1] or a_codes.shape[1] % 96 != 0:
+            raise RuntimeError(f"{name}: operand shapes mismatch")
+    _check_operand(f"{name}(activation)", a_codes, a_scales, tokens, row_bytes, tokens, dev)
+    _check_operand(f"{name}(weight)", w_codes, w_scales, w_rows, row_bytes, outs, dev)
+    q, sp, b, hs = _qkv_split_args(name, cache_kv, tokens, outs, bias, pos, seq, qk_norm_scale)
+    if tokens and hs is not None:
+        with device_guard(dev):
+            check(lib().fpq_gemm_fp6_rows_split_qknorm(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), w_codes.data_ptr(),
+                                                       w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(),
+                                                       tokens, outs, k, ctypes.byref(sp), hs.data_ptr(), 1 if km else 0, stream_ptr(dev)),
+                  "fpq_gemm_fp6_rows_split_qknorm")
+    elif tokens:
+        with device_guard(dev):
+            check(lib().fpq_gemm_fp6_rows_split(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), w_codes.data_ptr(),
+                                                w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(),
+                                                tokens, outs, k, ctypes.byref(sp), 1 if km else 0, stream_ptr(dev)),
+                  "fpq_gemm_fp6_rows_split")
+    return q
 
 
 class FP6Linear(_ScaledOperandModule):

@@ -131,8 +131,9 @@ class GenerationBatch:
         self.sdpa_in_f = sdpa_in_f                              # path F with torch's SDPA instead of fpq_attention_blhc (rounds 1 - 4 timed it that way)
         self.fused_gelu_quant = fused_fc1                       # path F: GELU + fc2's input quantizer in one pass over the fc1 output
         self.kmajor = kmajor                                    # path Q: operands as k-major images (include/fpq.h): contiguous LDS-DMA pieces
-        # path Q (W4A4): mat_qkv writes k and v straight into the KV cache's slots (fpq_gemm_fp4_mx_split): no copy-in pass
-        self.qkv_to_cache = qkv_to_cache and not self.W6 and hasattr(gemm, "linear_fp4_qkv_to_cache")
+        # path Q: mat_qkv writes k and v straight into the KV cache's slots (fpq_gemm_fp4_mx_split, W6A6: fpq_gemm_fp6_rows_split):
+        # no copy-in pass
+        self.qkv_to_cache = bool(qkv_to_cache)
         C, HID, B = self.C, self.HID, self.B
         g = torch.Generator(device=dev).manual_seed(seed)
         self.gen = g
@@ -215,6 +216,18 @@ class GenerationBatch:
             return gemm.linear_fp6(*rot.adaln_rotate_quant_token(t, sc, sh, "e2m3", smooth=sm, emit="fp6", kmajor=self.kmajor), *self.wop[name])
         return gemm.linear_fp4(*rot.adaln_rotate_quant_mx(t, sc, sh, smooth=sm, kmajor=self.kmajor), *self.wop[name])
 
+    def q_qkv_to_cache(self, x, sc1, sh1, b, cache_kv, pos):
+        """mat_qkv of block b with the split output: q [B, L, H, hd] comes back, k and v land in cache_kv at pos (with attn_l2_norm:
+        normalized in the GEMM's epilogue)"""
+        bias, hs = (self.qkv_bias[b], self.head_scale[b]) if self.attn_l2_norm else (None, None)
+        if self.W6:
+            q = gemm.linear_fp6_qkv_to_cache(*rot.adaln_rotate_quant_token(x, sc1, sh1, "e2m3", smooth=self.s_qkv, emit="fp6", kmajor=self.kmajor),
+                                             *self.wop["qkv"], bias, cache_kv, pos, x.shape[1], qk_norm_scale=hs)
+        else:
+            q = gemm.linear_fp4_qkv_to_cache(*rot.adaln_rotate_quant_mx(x, sc1, sh1, smooth=self.s_qkv, kmajor=self.kmajor), *self.wop["qkv"],
+                                             bias, cache_kv, pos, x.shape[1], qk_norm_scale=hs)
+        return q.view(self.B, x.shape[1], self.H, self.hd)
+
     def q_proj(self, t2d, gate, resid):       # x + proj(a).mul(gamma1), gate and residual applied in the GEMM epilogue
         if self.W6:
             return gemm.linear_fp6(*gemm.quantize_fp6(t2d, kmajor=self.kmajor), *self.wop["proj"], None, gate, resid)
@@ -258,10 +271,7 @@ class GenerationBatch:
         g1, g2, sc1, sc2, sh1, sh2 = self.mods[b]
         l2 = self.attn_l2_norm
         if path == "Q" and self.qkv_to_cache and not (l2 and self.qk_norm == "torch"):
-            q = gemm.linear_fp4_qkv_to_cache(*rot.adaln_rotate_quant_mx(x, sc1, sh1, smooth=self.s_qkv, kmajor=self.kmajor), *self.wop["qkv"],
-                                             self.qkv_bias[b] if l2 else None, cache.staging, 0, L,
-                                             qk_norm_scale=self.head_scale[b] if l2 else None).view(B, L, H, hd)
-            return cache.attend_staged(q, L, scale)
+            return cache.attend_staged(self.q_qkv_to_cache(x, sc1, sh1, b, cache.staging, 0), L, scale)
         if path == "F":
             qkv = Fn.linear(self.f_producer(x, sc1, sh1, self.s_qkv), self.wq["qkv"])
         else:
@@ -307,9 +317,7 @@ class GenerationBatch:
             if self.kv_storage == "codes":
                 a = self.attend_codes(path, caches[b], x, b, scale).view(B, L, C)
             elif path == "Q" and self.qkv_to_cache and not (l2 and self.qk_norm == "torch"):
-                q = gemm.linear_fp4_qkv_to_cache(*rot.adaln_rotate_quant_mx(x, sc1, sh1, smooth=self.s_qkv, kmajor=self.kmajor), *self.wop["qkv"],
-                                                 self.qkv_bias[b] if l2 else None, caches[b].kv, caches[b].len, L,
-                                                 qk_norm_scale=self.head_scale[b] if l2 else None).view(B, L, H, hd)
+                q = self.q_qkv_to_cache(x, sc1, sh1, b, caches[b].kv, caches[b].len)
                 kc, vc = caches[b].commit_written(L)
             else:
                 if path == "F":
@@ -411,7 +419,7 @@ def generation_record(models: Sequence[str] = ("d30-256", "d36-512"), paths: Seq
             rec = {"model": model, "path": path, "config": config, "images_per_batch": gb.B // 2, "what": WHAT[model]}
             if path == "Q":
                 rec["operands"] = "k-major images (include/fpq.h)" if gb.kmajor else "row-major codes"
-                rec["kv_cache"] = ("k, v written into the cache's slots by mat_qkv's GEMM (fpq_gemm_fp4_mx_split), one quantization pass per step"
+                rec["kv_cache"] = (f"k, v written into the cache's slots by mat_qkv's GEMM ({'fpq_gemm_fp6_rows_split' if gb.W6 else 'fpq_gemm_fp4_mx_split'}), one quantization pass per step"
                                    if gb.qkv_to_cache else "one launch per step: quantization pass + copy-in of k, v")
             try:
                 if tuned_gemms:

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FPQ_VERSION 128 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
+#define FPQ_VERSION 129 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
                            0.1.3: + fpq_quant_rows_codes_segments, fpq_dequant_rows_codes_segments (round 3);
                            123: + fpq_build_tag (round 4);
                            124: + fpq_set_option, fpq_get_option, fpq_option_name, fpq_gemm_fp4_gelu_dual, fpq_gelu_quant_rows_dual (round 5);
@@ -33,7 +33,8 @@ extern "C" {
                            126: - the switches FPQ_ROT_BUTTERFLY, FPQ_ADALN_V1, FPQ_ADALN_LANES, FPQ_ADALN_GRID, FPQ_BIGTAB_U
                                 (the kernel forms they chose are retired);
                            127: + fpq_gemm_fp4_mx_split_qknorm, fpq_kv_cache_step_qknorm (attn_l2_norm);
-                           128: + the packed KV cache: fpq_kv_pack, fpq_attention_blhc_kvcodes */
+                           128: + the packed KV cache: fpq_kv_pack, fpq_attention_blhc_kvcodes;
+                           129: + fpq_gemm_fp6_rows_split, fpq_gemm_fp6_rows_split_qknorm (the split output and the q / k norm for W6A6) */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -595,6 +596,22 @@ int fpq_gemm_fp6_rows_km(const uint8_t* a_image, const void* a_scales, int a_sca
 int fpq_gemm_fp4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, const uint8_t* w_codes, const void* w_scales,
                                  int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
                                  const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream);
+/* The FP6 row-scaled GEMM (fpq_gemm_fp6_rows_ex, kmajor = 0 / fpq_gemm_fp6_rows_km, kmajor = 1; operands, scale dtypes and every
+ * check as there, no gate / residual tail) with the SPLIT OUTPUT of fpq_gemm_fp4_mx_split, and with the Q / K L2 NORM above in that
+ * epilogue: the W6A6 mat_qkv.  Without the norm every written value is bit for bit the one fpq_gemm_fp6_rows_ex / _km writes at
+ * that (token, column); with it, y16 is what they write with bias == NULL and q, k, v follow the contract above (the arithmetic of
+ * fpq_gemm_fp4_mx_split_qknorm: on operands that represent the same matrices the two GEMMs write the same bits).
+ * split: n_parts 1..3 (exactly 3 with the norm), part_cols % 128 == 0, outs == n_parts * part_cols, rows_per_batch >= 1 and
+ * tokens % rows_per_batch == 0; EVERY destination out[p] non-NULL and 8-byte aligned, row_stride[p] >= part_cols and % 4 == 0,
+ * batch_stride[p], row0[p] >= 0.  bias: fp16 [outs] or NULL (split); fp32 [3 * part_cols], 16-byte aligned, or NULL (norm);
+ * q_head_scale fp32 [part_cols / 64], never NULL.  Anything else: FPQ_ERR_ARG (FPQ_ERR_SHAPE / FPQ_ERR_DTYPE as fpq_gemm_fp6_rows_ex
+ * uses them) before any launch; tokens == 0: FPQ_OK, nothing launched. */
+int fpq_gemm_fp6_rows_split(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes, const void* w_scales,
+                            int w_scale_dtype, const void* bias, int64_t tokens, int64_t outs, int64_t k, const fpq_gemm_split_t* split,
+                            int kmajor, fpq_stream_t stream);
+int fpq_gemm_fp6_rows_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,
+                                   const void* w_scales, int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
+                                   const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream);
 /* fpq_kv_cache_step_qknorm: fpq_kv_cache_step (same arguments, same checks) for an fp16 qkv WITHOUT the norm (path F, or a
  * mat_qkv that is not split): the new k is normalized and the bias added on its way into the cache, and the same launch writes
  * q_out - fp16 [batch, n_new, row_elems], contiguous - from new_q (the pitches of new_k).  head_dim == 64, row_elems % 64 == 0,

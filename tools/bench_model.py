@@ -28,7 +28,7 @@ def main():
     ap.add_argument("--unfused-fc1", action="store_true", help="Q path: GEMM, GELU and the dual quantizer as three launches")
     ap.add_argument("--sdpa-in-f", action="store_true", help="path F with torch's SDPA instead of fpq_attention_blhc (as rounds 1 - 4 timed it)")
     ap.add_argument("--row-major-operands", action="store_true", help="Q path: row-major code tensors instead of k-major images (the form of rounds 1 - 4)")
-    ap.add_argument("--qkv-copy-in", action="store_true", help="Q path: mat_qkv writes one [tokens, 3 C] tensor and the cache copies k / v in (the form before fpq_gemm_fp4_mx_split)")
+    ap.add_argument("--qkv-copy-in", action="store_true", help="Q path: mat_qkv writes one [tokens, 3 C] tensor and the cache copies k / v in (the form before fpq_gemm_fp4_mx_split / fpq_gemm_fp6_rows_split)")
     ap.add_argument("--attn-l2-norm", action="store_true", help="attention blocks with attn_l2_norm (the released models' setting): q / k L2 norm")
     ap.add_argument("--qk-norm", default="fused", choices=("fused", "torch"),
                     help="with --attn-l2-norm: the norm inside the qkv-to-cache kernels (fused) or the reference's torch lines between them")
