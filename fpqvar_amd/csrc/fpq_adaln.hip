@@ -1,4 +1,4 @@
-// fpq_adaln.hip - the adaLN producer (fpq_adaln.h: LayerNorm, modulation, rotation and quantizer in one launch) and its seven
+// fpq_adaln.hip - the adaLN producer (fpq_adaln.h: LayerNorm, modulation, rotation and quantizer in one launch) and its eight
 // C entry points.  A unit of its own because its ~230 kernel forms take longer to compile than the rest of the quantizers
 // together: an edit elsewhere does not recompile them.
 #include "fpq_common.h"
@@ -282,6 +282,18 @@ int fpq_adaln_rotate_quant_token_rows_codes_fp6_km(const void* x, uint8_t* image
   if (cols % 128 != 0) return FPQ_ERR_SHAPE;
   return adaln_rotate_quant_impl(x, image, nullptr, nullptr, row_scales, rows, cols, in_dtype, scale, shift, mod_dtype,
                                  rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 3, &lut16_codes6_e2m3(), true);
+}
+// the two above with the operand format as an argument: FPQ_E2M3 (FP6) or FPQ_E3M2 (BF6) codes, row-major or the k-major image
+int fpq_adaln_rotate_quant_token_rows_codes_f6(const void* x, uint8_t* codes, void* row_scales, int64_t rows, int64_t cols,
+                                               int in_dtype, const void* scale, const void* shift, int mod_dtype,
+                                               int64_t rows_per_batch, float eps, const float* smooth,
+                                               const uint32_t* sign_mask_host, int table_id, int kmajor, fpq_stream_t stream) {
+  if (table_id != FPQ_E2M3 && table_id != FPQ_E3M2) return FPQ_ERR_TABLE;
+  if (rows > 0 && cols > 0 && !row_scales) return FPQ_ERR_ARG;
+  if (cols % (kmajor ? 128 : 32) != 0) return FPQ_ERR_SHAPE;
+  if ((((uintptr_t)codes) & 7) != 0) return FPQ_ERR_ARG;
+  return adaln_rotate_quant_impl(x, codes, nullptr, nullptr, row_scales, rows, cols, in_dtype, scale, shift, mod_dtype,
+                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 3, &lut16_codes6(table_id), kmajor != 0);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// fpq_codes_fp6.h - the operand-emitting quantizers of the row-scaled FP6 GEMM (fpq_gemm_fp6.h): dense 6-bit E2M3 codes + one
-// scale per row.  Included by fpq_rotate.hip only (the code table, lut16_codes6_e2m3: fpq_fast16.h).
+// fpq_codes_fp6.h - the operand-emitting quantizers of the row-scaled FP6 GEMM (fpq_gemm_fp6.h): dense 6-bit E2M3 (FP6) or E3M2
+// (BF6) codes + one scale per row.  Included by fpq_rotate.hip only (the code tables, lut16_codes6(table_id): fpq_fast16.h).
 #pragma once
 
 // Fast form for fp16 rows (per-token activations): one wavefront per row, every lane owns whole 32-element
@@ -72,7 +72,8 @@ __global__ __launch_bounds__(kBlock) void rows16_codes6_wave_kernel(const uint16
 }
 
 // Generic form (fp32 weights, long or unaligned rows): one workgroup per row, a thread packs whole 32-element blocks.
-template <typename Tin>
+// BF6: the codes of E3M2 levels (f is that table's format) instead of E2M3's.
+template <typename Tin, bool BF6 = false>
 __global__ __launch_bounds__(kBlock) void rows_codes_fp6_kernel(const Tin* __restrict__ x, uint8_t* __restrict__ codes,
                                                                Tin* __restrict__ scales, int64_t rows, int64_t cols, Fmt f,
                                                                uint32_t km_rows) {
@@ -94,7 +95,8 @@ __global__ __launch_bounds__(kBlock) void rows_codes_fp6_kernel(const Tin* __res
         const float xn = div_round<Tin>(load_scalar<Tin>(xr + b * 32 + j), s);
         const uint32_t neg = (xn < 0.0f) ? 1u : 0u;
         const float qm = quant_mag(fabsf(xn), neg, f);
-        const uint32_t code = e2m3_of_level((neg && qm != 0.0f) ? -qm : qm);
+        const float lv = (neg && qm != 0.0f) ? -qm : qm;
+        const uint32_t code = BF6 ? e3m2_of_level(lv) : e2m3_of_level(lv);
         const int bit = 6 * j;
         o[bit >> 5] |= code << (bit & 31);
         if ((bit & 31) > 26) o[(bit >> 5) + 1] |= code >> (32 - (bit & 31));

@@ -1449,19 +1449,36 @@ inline const Lut16Tab& lut16_codes8(int table_id) {
   return tabs[table_id];
 }
 
-// bucket -> 6-bit E2M3 code table (the FP6 operand producers and the packed KV cache), built once (immutable afterwards)
-inline const Lut16Tab& lut16_codes6_e2m3() {
-  static const Lut16Tab* tab = [] {
+// level (exactly an E3M2 number, sign included) -> 6-bit BF6 code: sign, 3 exponent bits (bias 3), 2 mantissa bits; a zero of
+// either sign is code 0
+__host__ __device__ __forceinline__ uint32_t e3m2_of_level(float q) {
+  const uint32_t sgn = (q < 0.0f) ? 32u : 0u;
+  const float a = q < 0.0f ? -q : q;
+  if (a < 0.25f) return sgn | (uint32_t)(a * 16.0f);                               // subnormal: m / 16
+  const uint32_t u = __builtin_bit_cast(uint32_t, a);                              // normal: 2^(e - 3) (1 + m / 4), e = 1 .. 7
+  return sgn | ((((((u >> 23) & 0xFFu) - 124u) << 2) | ((u >> 21) & 3u)) & 31u);   // (& 31: a code never reaches its neighbours' bits)
+}
+
+// bucket -> 6-bit code table of FPQ_E2M3 or FPQ_E3M2 (the FP6 / BF6 operand producers and the packed KV cache), each built once
+// on first use (immutable afterwards)
+inline const Lut16Tab& lut16_codes6(int table_id) {
+  const auto build = [](int id) {
     auto* t = new Lut16Tab();
-    const Lut16Host& h = lut16_host(FPQ_E2M3, FPQ_E2M3);
+    const Lut16Host& h = lut16_host(id, id);
     const int n = 1 << (16 - h.args.shift);
     uint16_t full[kLutLdsEntries] = {0};
-    for (int i = 0; i < n; ++i) full[i] = (uint16_t)e2m3_of_level(h2f(h.full[i]));
-    if (!lut16_compress(full, h.args.shift, t)) abort();
+    for (int i = 0; i < n; ++i) full[i] = (uint16_t)(id == FPQ_E3M2 ? e3m2_of_level(h2f(h.full[i])) : e2m3_of_level(h2f(h.full[i])));
+    if (!lut16_compress(full, h.args.shift, t)) abort();   // same structure as the level table it is derived from
     return t;
-  }();
-  return *tab;
+  };
+  if (table_id == FPQ_E3M2) {
+    static const Lut16Tab* bf6 = build(FPQ_E3M2);
+    return *bf6;
+  }
+  static const Lut16Tab* fp6 = build(FPQ_E2M3);
+  return *fp6;
 }
+inline const Lut16Tab& lut16_codes6_e2m3() { return lut16_codes6(FPQ_E2M3); }
 
 // k-major images are addressed with 32-bit byte offsets (and int buffer ranges) by their producers: the whole image must stay below 2 GiB
 inline bool km_image_fits(int64_t rows, int64_t row_bytes) { return rows < (1ll << 31) && rows * row_bytes < (1ll << 31); }

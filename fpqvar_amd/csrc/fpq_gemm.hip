@@ -397,7 +397,10 @@ int fpq_gemm_fp4_gelu_dual_km(const uint8_t* a_image, const void* a_scales, cons
 static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,
                               const void* w_scales, int w_scale_dtype, const void* bias, void* out, int64_t tokens,
                               int64_t outs, int64_t k, const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream,
-                              const fpq_gemm_split_t* split = nullptr, const GemmQkNorm* qkn = nullptr) {
+                              const fpq_gemm_split_t* split = nullptr, const GemmQkNorm* qkn = nullptr,
+                              int a_table = FPQ_E2M3, int w_table = FPQ_E2M3) {
+  // a_table / w_table: FPQ_E2M3 or FPQ_E3M2 (checked by the fpq_gemm_f6_* entry points) -> the MFMA's format selectors
+  const int fsel = (a_table == FPQ_E3M2 ? 2 : 0) | (w_table == FPQ_E3M2 ? 1 : 0);
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   GemmEpi epi;
   if (int rc = gemm_epilogue(epilogue, tokens, &epi)) return rc;
@@ -426,6 +429,9 @@ static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int 
   if (k % 128 != 0 || outs % 8 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF || k > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
   if ((a_scale_dtype != FPQ_F16 && a_scale_dtype != FPQ_F32) || (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32))
     return FPQ_ERR_DTYPE;
+  // a pair with an E3M2 side is compiled for the scale dtypes the quantizers of activations produce: fp16 activation scales
+  // (fp16 or fp32 weight scales) - all four dtype pairs for all four format pairs would double this unit's compile time
+  if (fsel != 0 && a_scale_dtype != FPQ_F16) return FPQ_ERR_DTYPE;
   if (tokens == 0 || outs == 0) return FPQ_OK;
   if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
   if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (split ? 0 : (uintptr_t)out)) & 15) != 0) return FPQ_ERR_ARG;
@@ -436,32 +442,57 @@ static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int 
   // FPQ_GEMM6_CFG 0: 128 x 128 tiles, 1: 256 x 128 (default for tall problems)
   // 256 x 128 tiles from 4096 tokens on for the wide Linears, from 32768 on for outs < 4096 (tools/gemm_small_steps.py fp6)
   const int cfg6 = fpq_opt_set(OPT_FPQ_GEMM6_CFG) ? fpq_opt(OPT_FPQ_GEMM6_CFG, 0) : (tokens >= 4096 && (outs >= 4096 || tokens >= 32768) ? 1 : 0);
-#define FPQ_GO6X(TA, TW, MT, NT, XE, xe)                                                                            \
-  hipLaunchKernelGGL((gemm_fp6_rows_kernel<TA, TW, MT, NT, XE>), dim3((unsigned)n_wg), dim3(256), Cfg::lds(), st,   \
-                     a_codes, (const TA*)a_scales, w_codes, (const TW*)w_scales, (const _Float16*)bias,              \
-                     (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, xe)
-#define FPQ_GO6(TA, TW, MT, NT)                                                                                     \
+#define FPQ_GO6ARGS(TA, TW, xe)                                                                                     \
+  dim3((unsigned)n_wg), dim3(256), Cfg::lds(), st, a_codes, (const TA*)a_scales, w_codes, (const TW*)w_scales,       \
+      (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, xe
+#define FPQ_GO6X(TA, TW, MT, NT, XE, xe) hipLaunchKernelGGL((gemm_fp6_rows_kernel<TA, TW, MT, NT, XE>), FPQ_GO6ARGS(TA, TW, xe))
+#define FPQ_GO6B(TA, TW, MT, NT, XE, xe, FA, FB)                                                                    \
+  hipLaunchKernelGGL((gemm_fp6_rows_bf6_kernel<TA, TW, MT, NT, XE, FA, FB>), FPQ_GO6ARGS(TA, TW, xe))
+#define FPQ_GO6P(TA, TW, MT, NT)                                                                                    \
+  do {                                                                                                               \
+    if (qkn) FPQ_GO6X(TA, TW, MT, NT, GemmQkNorm, *qkn);                                                             \
+    else if (split) FPQ_GO6X(TA, TW, MT, NT, GemmSplit, GemmSplit{});                                                \
+    else FPQ_GO6X(TA, TW, MT, NT, GemmNoFc1, GemmNoFc1{});                                                           \
+  } while (0)
+#define FPQ_GO6E(TA, TW, MT, NT, FA, FB)                                                                            \
+  do {                                                                                                               \
+    if (qkn) FPQ_GO6B(TA, TW, MT, NT, GemmQkNorm, *qkn, FA, FB);                                                     \
+    else if (split) FPQ_GO6B(TA, TW, MT, NT, GemmSplit, GemmSplit{}, FA, FB);                                        \
+    else FPQ_GO6B(TA, TW, MT, NT, GemmNoFc1, GemmNoFc1{}, FA, FB);                                                   \
+  } while (0)
+#define FPQ_GO6(TA, TW, MT, NT, MORE)                                                                               \
   do {                                                                                                               \
     using Cfg = GemmFp6Cfg<MT, NT>;                                                                                  \
     const int64_t n_col = (outs + Cfg::BN - 1) / Cfg::BN, n_row = (tokens + Cfg::BM - 1) / Cfg::BM;                  \
     const int64_t n_wg = 8 * ((n_col + 7) / 8) * n_row;                                                              \
     if (n_wg > 0x7FFFFFFF) return FPQ_ERR_SHAPE;                                                                     \
-    if (qkn) FPQ_GO6X(TA, TW, MT, NT, GemmQkNorm, *qkn);                                                             \
-    else if (split) FPQ_GO6X(TA, TW, MT, NT, GemmSplit, GemmSplit{});                                                \
-    else FPQ_GO6X(TA, TW, MT, NT, GemmNoFc1, GemmNoFc1{});                                                           \
+    if (fsel == 0) FPQ_GO6P(TA, TW, MT, NT);   /* E2M3 x E2M3; below: activations (A, cbsz) x weights (B, blgp) */  \
+    MORE(TA, TW, MT, NT);                                                                                            \
   } while (0)
+#define FPQ_GO6_NONE(TA, TW, MT, NT)
+#define FPQ_GO6_BF6(TA, TW, MT, NT)                                                                                 \
+  else if (fsel == 2) FPQ_GO6E(TA, TW, MT, NT, 3, 2);                                                                \
+  else if (fsel == 1) FPQ_GO6E(TA, TW, MT, NT, 2, 3);                                                                \
+  else FPQ_GO6E(TA, TW, MT, NT, 3, 3)
+  // (the pairs with a BF6 side exist for fp16 activation scales only - checked above: 60 instantiations instead of 96)
 #define FPQ_GO6T(MT, NT)                                                                                             \
   do {                                                                                                               \
-    if (a_scale_dtype == FPQ_F16 && w_scale_dtype == FPQ_F16) FPQ_GO6(_Float16, _Float16, MT, NT);                   \
-    else if (a_scale_dtype == FPQ_F16) FPQ_GO6(_Float16, float, MT, NT);                                             \
-    else if (w_scale_dtype == FPQ_F16) FPQ_GO6(float, _Float16, MT, NT);                                             \
-    else FPQ_GO6(float, float, MT, NT);                                                                              \
+    if (a_scale_dtype == FPQ_F16 && w_scale_dtype == FPQ_F16) FPQ_GO6(_Float16, _Float16, MT, NT, FPQ_GO6_BF6);      \
+    else if (a_scale_dtype == FPQ_F16) FPQ_GO6(_Float16, float, MT, NT, FPQ_GO6_BF6);                                \
+    else if (w_scale_dtype == FPQ_F16) FPQ_GO6(float, _Float16, MT, NT, FPQ_GO6_NONE);                               \
+    else FPQ_GO6(float, float, MT, NT, FPQ_GO6_NONE);                                                                \
   } while (0)
   if (cfg6 == 1) FPQ_GO6T(8, 4);
   else FPQ_GO6T(4, 4);
 #undef FPQ_GO6T
+#undef FPQ_GO6_BF6
+#undef FPQ_GO6_NONE
 #undef FPQ_GO6
+#undef FPQ_GO6E
+#undef FPQ_GO6P
+#undef FPQ_GO6B
 #undef FPQ_GO6X
+#undef FPQ_GO6ARGS
   return check_launch();
 }
 int fpq_gemm_fp6_rows_ex(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,
@@ -491,6 +522,35 @@ int fpq_gemm_fp6_rows_split_qknorm(const uint8_t* a_codes, const void* a_scales,
   const GemmQkNorm qkn{bias, q_head_scale};
   return gemm_fp6_rows_impl(a_codes, a_scales, a_scale_dtype, w_codes, w_scales, w_scale_dtype, nullptr, nullptr, tokens, outs, k, nullptr,
                             kmajor != 0, stream, split, &qkn);
+}
+
+// The FP6 GEMM with the format of each operand as an argument (include/fpq.h): FPQ_E2M3 or FPQ_E3M2 per side, everything else
+// as the fpq_gemm_fp6_rows_* entry point of the same shape - (FPQ_E2M3, FPQ_E2M3) launches the very kernel that one launches.
+static bool f6_table(int t) { return t == FPQ_E2M3 || t == FPQ_E3M2; }
+int fpq_gemm_f6_rows(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, int a_table, const uint8_t* w_codes,
+                     const void* w_scales, int w_scale_dtype, int w_table, const void* bias, void* out, int64_t tokens, int64_t outs,
+                     int64_t k, const fpq_gemm_epilogue_t* epilogue, int kmajor, fpq_stream_t stream) {
+  if (!f6_table(a_table) || !f6_table(w_table)) return FPQ_ERR_TABLE;
+  return gemm_fp6_rows_impl(a_codes, a_scales, a_scale_dtype, w_codes, w_scales, w_scale_dtype, bias, out, tokens, outs, k, epilogue,
+                            kmajor != 0, stream, nullptr, nullptr, a_table, w_table);
+}
+int fpq_gemm_f6_rows_split(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, int a_table, const uint8_t* w_codes,
+                           const void* w_scales, int w_scale_dtype, int w_table, const void* bias, int64_t tokens, int64_t outs, int64_t k,
+                           const fpq_gemm_split_t* split, int kmajor, fpq_stream_t stream) {
+  if (!f6_table(a_table) || !f6_table(w_table)) return FPQ_ERR_TABLE;
+  if (!split) return FPQ_ERR_ARG;
+  return gemm_fp6_rows_impl(a_codes, a_scales, a_scale_dtype, w_codes, w_scales, w_scale_dtype, bias, nullptr, tokens, outs, k, nullptr,
+                            kmajor != 0, stream, split, nullptr, a_table, w_table);
+}
+int fpq_gemm_f6_rows_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, int a_table, const uint8_t* w_codes,
+                                  const void* w_scales, int w_scale_dtype, int w_table, const float* bias, int64_t tokens, int64_t outs,
+                                  int64_t k, const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream) {
+  if (!f6_table(a_table) || !f6_table(w_table)) return FPQ_ERR_TABLE;
+  if (!split || split->n_parts != 3) return FPQ_ERR_ARG;
+  if (!q_head_scale || ((uintptr_t)q_head_scale & 3) != 0 || ((uintptr_t)bias & 15) != 0) return FPQ_ERR_ARG;
+  const GemmQkNorm qkn{bias, q_head_scale};
+  return gemm_fp6_rows_impl(a_codes, a_scales, a_scale_dtype, w_codes, w_scales, w_scale_dtype, nullptr, nullptr, tokens, outs, k, nullptr,
+                            kmajor != 0, stream, split, &qkn, a_table, w_table);
 }
 
 // Row-major codes -> k-major image (include/fpq.h): one thread per 16-byte chunk of the image.  seg = bytes of a row per K step of

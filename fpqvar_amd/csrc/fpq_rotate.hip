@@ -1,6 +1,6 @@
 // fpq_rotate.hip - the online rotation in front of the per-group quantizer (fpq_rotate_quant_rows*, the transform on the
 // matrix cores: fpq_rotate_mfma.h) and the operand emitters of the row-scaled FP8 / FP6 GEMMs (fpq_quant_rows_codes_fp8 /
-// _fp6*: fpq_codes_fp8.h, fpq_codes_fp6.h), with their C ABI.  The FP4 emitter, fpq_quant_rows_codes_mx, stays with the
+// _fp6* / _f6: fpq_codes_fp8.h, fpq_codes_fp6.h), with their C ABI.  The FP4 emitter, fpq_quant_rows_codes_mx, stays with the
 // codes of fpq_kernels.hip, whose codes128_kernel its fp32 form launches.
 #include "fpq_common.h"
 
@@ -129,8 +129,8 @@ int fpq_quant_rows_codes_fp8(const void* x, uint8_t* codes, void* scales, int64_
 
 static int quant_rows_codes_fp6_impl(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
                                      int in_dtype, bool km, fpq_stream_t stream) {
+  // table_id: FPQ_E2M3 or FPQ_E3M2, checked by the entry points (the _fp6 forms take E2M3 only)
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (table_id != FPQ_E2M3) return FPQ_ERR_TABLE;
   if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
   if (cols % 32 != 0 || (km && (cols % 128 != 0 || !km_image_fits(rows, cols / 4 * 3)))) return FPQ_ERR_SHAPE;
   const uint32_t km_rows = km ? (uint32_t)rows : 0u;
@@ -145,7 +145,7 @@ static int quant_rows_codes_fp6_impl(const void* x, uint8_t* codes, void* scales
     const dim3 gw(grid_for(wgs, 8192));
     const int maxc = (int)((cols / 32 + 63) / 64);
 #define FPQ_C6(M) hipLaunchKernelGGL((rows16_codes6_wave_kernel<M>), gw, dim3(kBlock), lds, st, (const uint16_t*)x, codes, \
-                                     (uint16_t*)scales, rows, cols, h.args, lut16_codes6_e2m3(), km_rows)
+                                     (uint16_t*)scales, rows, cols, h.args, lut16_codes6(table_id), km_rows)
     if (maxc <= 1) FPQ_C6(1);
     else if (maxc <= 2) FPQ_C6(2);
     else FPQ_C6(4);
@@ -153,21 +153,30 @@ static int quant_rows_codes_fp6_impl(const void* x, uint8_t* codes, void* scales
     return check_launch();
   }
   const dim3 g(grid_for(rows, 65535));
-  if (in_dtype == FPQ_F16)
-    hipLaunchKernelGGL(rows_codes_fp6_kernel<_Float16>, g, dim3(kBlock), 0, st, (const _Float16*)x, codes,
-                       (_Float16*)scales, rows, cols, make_fmt(table_id), km_rows);
-  else
-    hipLaunchKernelGGL(rows_codes_fp6_kernel<float>, g, dim3(kBlock), 0, st, (const float*)x, codes, (float*)scales, rows,
-                       cols, make_fmt(table_id), km_rows);
+#define FPQ_C6G(TIN, BF6)                                                                                           \
+  hipLaunchKernelGGL((rows_codes_fp6_kernel<TIN, BF6>), g, dim3(kBlock), 0, st, (const TIN*)x, codes, (TIN*)scales, rows, cols, \
+                     make_fmt(table_id), km_rows)
+  if (table_id == FPQ_E3M2) { if (in_dtype == FPQ_F16) FPQ_C6G(_Float16, true); else FPQ_C6G(float, true); }
+  else { if (in_dtype == FPQ_F16) FPQ_C6G(_Float16, false); else FPQ_C6G(float, false); }
+#undef FPQ_C6G
   return check_launch();
 }
 int fpq_quant_rows_codes_fp6(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
                              int in_dtype, fpq_stream_t stream) {
+  if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
+  if (table_id != FPQ_E2M3) return FPQ_ERR_TABLE;
   return quant_rows_codes_fp6_impl(x, codes, scales, rows, cols, table_id, in_dtype, false, stream);
 }
 int fpq_quant_rows_codes_fp6_km(const void* x, uint8_t* image, void* scales, int64_t rows, int64_t cols, int table_id,
                                 int in_dtype, fpq_stream_t stream) {
+  if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
+  if (table_id != FPQ_E2M3) return FPQ_ERR_TABLE;
   return quant_rows_codes_fp6_impl(x, image, scales, rows, cols, table_id, in_dtype, true, stream);
+}
+int fpq_quant_rows_codes_f6(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id, int in_dtype,
+                            int kmajor, fpq_stream_t stream) {
+  if (table_id != FPQ_E2M3 && table_id != FPQ_E3M2) return FPQ_ERR_TABLE;
+  return quant_rows_codes_fp6_impl(x, codes, scales, rows, cols, table_id, in_dtype, kmajor != 0, stream);
 }
 
 }  // extern "C"

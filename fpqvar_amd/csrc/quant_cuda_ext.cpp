@@ -355,6 +355,25 @@ std::tuple<at::Tensor, at::Tensor> adaln_rotate_quant_token_codes(const at::Tens
   return {codes, scales};
 }
 
+// ... and the dense 6-bit codes of either format (FPQ_E2M3: FP6, FPQ_E3M2: BF6), row-major or the k-major image
+std::tuple<at::Tensor, at::Tensor> adaln_rotate_quant_token_codes_f6(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift,
+                                                                     int64_t table_id, const std::array<uint32_t, 4>& sign_mask,
+                                                                     const c10::optional<at::Tensor>& smooth, double eps, bool kmajor) {
+  const ProducerArgs a = producer_checks("adaln_rotate_quant_token_codes_f6", x, &scale, &shift, smooth, 2560);
+  TORCH_CHECK(table_id == FPQ_E2M3 || table_id == FPQ_E3M2, "adaln_rotate_quant_token_codes_f6: dense 6-bit codes are E2M3 or E3M2");
+  const int64_t rows = a.b * a.l;
+  at::Tensor codes = kmajor ? at::empty({a.c / 128, rows, 96}, x.options().dtype(at::kByte))
+                            : at::empty({rows, a.c * 3 / 4}, x.options().dtype(at::kByte));
+  at::Tensor scales = at::empty({rows}, x.options().dtype(at::kHalf));
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  check(fpq_adaln_rotate_quant_token_rows_codes_f6(x.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c,
+                                                   dtype_id(x.scalar_type(), "adaln_rotate_quant_token_codes_f6"), scale.data_ptr(),
+                                                   shift.data_ptr(), dtype_id(scale.scalar_type(), "adaln_rotate_quant_token_codes_f6"), a.l,
+                                                   (float)eps, a.smooth, sign_mask.data(), (int)table_id, kmajor ? 1 : 0, current_stream(x)),
+        "fpq_adaln_rotate_quant_token_rows_codes_f6");
+  return {codes, scales};
+}
+
 // one step of the incrementally kept KV cache (ops.kv_cache_step holds the argument checks' prose)
 void kv_cache_step(const at::Tensor& cache, int64_t quant_start, int64_t quant_stop, const at::Tensor& k, const at::Tensor& v,
                    int64_t new_start, int64_t group, int64_t table_id) {
@@ -588,6 +607,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adaln_rotate_quant_token_codes", &adaln_rotate_quant_token_codes, py::arg("x"), py::arg("scale"), py::arg("shift"),
         py::arg("table_id"), py::arg("code_bits"), py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6,
         py::arg("kmajor") = false);
+  m.def("adaln_rotate_quant_token_codes_f6", &adaln_rotate_quant_token_codes_f6, py::arg("x"), py::arg("scale"), py::arg("shift"),
+        py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6, py::arg("kmajor") = false);
   m.def("kv_cache_step", &kv_cache_step, py::arg("cache"), py::arg("quant_start"), py::arg("quant_stop"), py::arg("k"), py::arg("v"),
         py::arg("new_start"), py::arg("group"), py::arg("table_id"));
   m.def("kv_cache_step_qk_norm", &kv_cache_step_qk_norm, py::arg("cache"), py::arg("quant_start"), py::arg("quant_stop"), py::arg("q"),

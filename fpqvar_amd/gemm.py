@@ -482,15 +482,29 @@ class FP8Linear(_ScaledOperandModule):
         return linear_fp8(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, gate, residual).view(*lead, self.out_features)
 
 
-# ---- the same with 6-bit packed operands (FP6 E2M3 on both sides: the W6A6 run configuration) ---------------------
-def quantize_fp6(x: torch.Tensor, kmajor: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+# ---- the same with 6-bit packed operands: FP6 E2M3 (the W6A6 run configuration) or BF6 E3M2, chosen per operand ------------
+_F6_TABLES = {"e2m3": "e2m3", "fp6_e2m3": "e2m3", "e3m2": "e3m2", "fp6_e3m2": "e3m2"}
+
+
+def _f6_table(name: str, table: str) -> str:
+    """'e2m3' / 'fp6_e2m3' -> 'e2m3', 'e3m2' / 'fp6_e3m2' -> 'e3m2': the two formats of the dense 6-bit operand form"""
+    try:
+        return _F6_TABLES[table]
+    except (KeyError, TypeError):
+        raise RuntimeError(f"{name}: the 6-bit operand formats are 'e2m3' and 'e3m2', got {table!r}") from None
+
+
+def quantize_fp6(x: torch.Tensor, kmajor: bool = False, table: str = "e2m3") -> Tuple[torch.Tensor, torch.Tensor]:
     """x [..., K] fp16/fp32 (K % 32 == 0) -> (codes uint8 [rows, K * 3 / 4]: dense 6-bit E2M3 codes,
     scales [rows] in x.dtype); e2m3(code) * scale == fp6_quant_e2m3_per_token_cuda(x).
-    kmajor (K % 128 == 0): the codes as the activation side's k-major image [K/128, rows, 96]."""
+    kmajor (K % 128 == 0): the codes as the activation side's k-major image [K/128, rows, 96].
+    table="e3m2": BF6 codes (sign, 3 exponent bits, 2 mantissa bits) in the same packing - fp6_quant_e3m2_per_token_cuda's
+    decisions (fpq_quant_rows_codes_f6)."""
     require_gpu(x, "quantize_fp6")
     if x.dtype not in (torch.float16, torch.float32):
         raise RuntimeError(f"quantize_fp6: x must be float16 or float32, got {x.dtype}")
     from ._lib import TABLE_IDS
+    table = _f6_table("quantize_fp6", table)
     k = x.shape[-1]
     if k % 32 != 0:
         raise RuntimeError("quantize_fp6: the last dimension must be a multiple of 32")
@@ -500,6 +514,11 @@ def quantize_fp6(x: torch.Tensor, kmajor: bool = False) -> Tuple[torch.Tensor, t
         raise RuntimeError("quantize_fp6(kmajor=True): the last dimension must be a multiple of 128")
     codes = torch.empty((k // 128, rows, 96) if kmajor else (rows, k * 3 // 4), dtype=torch.uint8, device=x.device)
     scales = torch.empty((rows,), dtype=x.dtype, device=x.device)
+    if table != "e2m3":
+        with device_guard(x.device):
+            check(lib().fpq_quant_rows_codes_f6(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, k, TABLE_IDS[table],
+                                                dtype_id(x.dtype), 1 if kmajor else 0, stream_ptr(x.device)), "fpq_quant_rows_codes_f6")
+        return codes, scales
     fn = lib().fpq_quant_rows_codes_fp6_km if kmajor else lib().fpq_quant_rows_codes_fp6
     with device_guard(x.device):
         check(fn(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, k, TABLE_IDS["e2m3"], dtype_id(x.dtype),
@@ -507,23 +526,30 @@ def quantize_fp6(x: torch.Tensor, kmajor: bool = False) -> Tuple[torch.Tensor, t
     return codes, scales
 
 
-def dequantize_fp6(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
-    """Reference decoder in torch ops (tests / debugging): fp32 [rows, K]."""
+def dequantize_fp6(codes: torch.Tensor, scales: torch.Tensor, table: str = "e2m3") -> torch.Tensor:
+    """Reference decoder in torch ops (tests / debugging): fp32 [rows, K].  table: the format the codes are in."""
+    table = _f6_table("dequantize_fp6", table)
     b = codes.reshape(codes.shape[0], -1, 3).to(torch.int32)
     word = b[..., 0] | (b[..., 1] << 8) | (b[..., 2] << 16)
     c = torch.stack((word & 63, (word >> 6) & 63, (word >> 12) & 63, (word >> 18) & 63), dim=-1).reshape(codes.shape[0], -1)
-    e, m = (c >> 3) & 3, (c & 7).float()
-    mag = torch.where(e == 0, m / 8.0, (1.0 + m / 8.0) * torch.pow(2.0, (e - 1).float()))
+    if table == "e3m2":   # sign, 3 exponent bits (bias 3), 2 mantissa bits
+        e, m = (c >> 2) & 7, (c & 3).float()
+        mag = torch.where(e == 0, m / 16.0, (1.0 + m / 4.0) * torch.pow(2.0, (e - 3).float()))
+    else:                 # sign, 2 exponent bits (bias 1), 3 mantissa bits
+        e, m = (c >> 3) & 3, (c & 7).float()
+        mag = torch.where(e == 0, m / 8.0, (1.0 + m / 8.0) * torch.pow(2.0, (e - 1).float()))
     val = torch.where((c & 32) != 0, -mag, mag)
     return val * scales.float().unsqueeze(-1)
 
 
 def linear_fp6(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
                bias: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
-               residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+               residual: Optional[torch.Tensor] = None, a_table: str = "e2m3", w_table: str = "e2m3") -> torch.Tensor:
     """fp16 [tokens, outs] = dequant(a) @ dequant(w).T + bias on the FP6 matrix cores (row-scaled operands); optional
-    fused `residual + y.mul(gate)` as in linear_fp4."""
+    fused `residual + y.mul(gate)` as in linear_fp4.  a_table / w_table: the format of the activation / weight codes,
+    "e2m3" (FP6) or "e3m2" (BF6) - the matrix instruction decodes each operand by its own selector (fpq_gemm_f6_rows)."""
     require_gpu(a_codes, "linear_fp6")
+    a_table, w_table = _f6_table("linear_fp6", a_table), _f6_table("linear_fp6", w_table)
     km = _kmajor_pair("linear_fp6", a_codes, w_codes, 96)
     if km:
         tokens, outs, k = a_codes.shape[1], w_scales.shape[0], a_codes.shape[0] * 128
@@ -537,6 +563,15 @@ def linear_fp6(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Ten
     _check_operand("linear_fp6(weight)", w_codes, w_scales, w_rows, row_bytes, outs, a_codes.device)
     ep, keep, out = _epilogue("linear_fp6", tokens, outs, gate, residual, None, a_codes.device)
     b = None if bias is None else bias.detach().to(torch.float16).reshape(-1).contiguous()
+    if (a_table, w_table) != ("e2m3", "e2m3"):
+        from ._lib import TABLE_IDS
+        with device_guard(a_codes.device):
+            check(lib().fpq_gemm_f6_rows(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), TABLE_IDS[a_table],
+                                         w_codes.data_ptr(), w_scales.data_ptr(), dtype_id(w_scales.dtype), TABLE_IDS[w_table],
+                                         None if b is None else b.data_ptr(), out.data_ptr(), tokens, outs, k, ep, 1 if km else 0,
+                                         stream_ptr(a_codes.device)), "fpq_gemm_f6_rows")
+        del keep
+        return out
     fn, what = (lib().fpq_gemm_fp6_rows_km, "fpq_gemm_fp6_rows_km") if km else (lib().fpq_gemm_fp6_rows_ex, "fpq_gemm_fp6_rows_ex")
     with device_guard(a_codes.device):
         check(fn(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), w_codes.data_ptr(), w_scales.data_ptr(),
@@ -548,14 +583,16 @@ def linear_fp6(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Ten
 
 def linear_fp6_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
                             bias: Optional[torch.Tensor], cache_kv: torch.Tensor, pos: int, seq: int,
-                            qk_norm_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                            qk_norm_scale: Optional[torch.Tensor] = None, a_table: str = "e2m3", w_table: str = "e2m3") -> torch.Tensor:
     """linear_fp4_qkv_to_cache for the row-scaled FP6 operands of linear_fp6 (fpq_gemm_fp6_rows_split): q comes back - fp16
     [B, seq, C] - and k, v are written straight into `cache_kv` [2, B, max_len, H, c] at token positions pos .. pos + seq, each value
     bit for bit the one linear_fp6(a, w, bias) holds there.  Operands row-major (2-D) or k-major images (3-D), scales float16 or
     float32 as in linear_fp6.  qk_norm_scale (fp32 [H]) and the fp32 bias [3C] it goes with: the q / k norm in the epilogue
-    (fpq_gemm_fp6_rows_split_qknorm), exactly as linear_fp4_qkv_to_cache states it."""
+    (fpq_gemm_fp6_rows_split_qknorm), exactly as linear_fp4_qkv_to_cache states it.  a_table / w_table: the operands' formats as in
+    linear_fp6 (fpq_gemm_f6_rows_split / _split_qknorm)."""
     name = "linear_fp6_qkv_to_cache"
     require_gpu(a_codes, name)
+    a_table, w_table = _f6_table(name, a_table), _f6_table(name, w_table)
     km = _kmajor_pair(name, a_codes, w_codes, 96)
     dev = a_codes.device
     if cache_kv.dim() != 5 or cache_kv.shape[0] != 2 or cache_kv.dtype != torch.float16 or not cache_kv.is_contiguous() or cache_kv.device != dev:
@@ -571,7 +608,21 @@ def linear_fp6_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_cod
     _check_operand(f"{name}(activation)", a_codes, a_scales, tokens, row_bytes, tokens, dev)
     _check_operand(f"{name}(weight)", w_codes, w_scales, w_rows, row_bytes, outs, dev)
     q, sp, b, hs = _qkv_split_args(name, cache_kv, tokens, outs, bias, pos, seq, qk_norm_scale)
-    if tokens and hs is not None:
+    if tokens and (a_table, w_table) != ("e2m3", "e2m3"):
+        from ._lib import TABLE_IDS
+        ta, tw = TABLE_IDS[a_table], TABLE_IDS[w_table]
+        with device_guard(dev):
+            if hs is not None:
+                check(lib().fpq_gemm_f6_rows_split_qknorm(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), ta, w_codes.data_ptr(),
+                                                          w_scales.data_ptr(), dtype_id(w_scales.dtype), tw, None if b is None else b.data_ptr(),
+                                                          tokens, outs, k, ctypes.byref(sp), hs.data_ptr(), 1 if km else 0, stream_ptr(dev)),
+                      "fpq_gemm_f6_rows_split_qknorm")
+            else:
+                check(lib().fpq_gemm_f6_rows_split(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), ta, w_codes.data_ptr(),
+                                                   w_scales.data_ptr(), dtype_id(w_scales.dtype), tw, None if b is None else b.data_ptr(),
+                                                   tokens, outs, k, ctypes.byref(sp), 1 if km else 0, stream_ptr(dev)),
+                      "fpq_gemm_f6_rows_split")
+    elif tokens and hs is not None:
         with device_guard(dev):
             check(lib().fpq_gemm_fp6_rows_split_qknorm(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), w_codes.data_ptr(),
                                                        w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(),
@@ -587,11 +638,14 @@ def linear_fp6_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_cod
 
 
 class FP6Linear(_ScaledOperandModule):
-    """FP8Linear with 6-bit packed operands, for E2M3 activations x E2M3 weights (run.sh:7): 0.75 byte per weight."""
+    """FP8Linear with 6-bit packed operands: 0.75 byte per weight.  E2M3 activations x E2M3 weights (run.sh:7) by default; `act_table`
+    / `w_table` ("e2m3" or "e3m2") name the format of each side - the matrix instruction decodes them separately, so the
+    mixed pairs of the reference's FP6 format search (quantize_VAR_mixed_fp6_datatype) run on the same kernel."""
 
-    def __init__(self, w_codes, w_scales, bias, in_features, out_features):
+    def __init__(self, w_codes, w_scales, bias, in_features, out_features, act_table: str = "e2m3", w_table: str = "e2m3"):
         super().__init__()
         self.in_features, self.out_features = in_features, out_features
+        self.act_table, self.w_table = _f6_table("FP6Linear", act_table), _f6_table("FP6Linear", w_table)
         self.register_buffer("w_codes", w_codes)
         self.register_buffer("w_scales", w_scales)
         self.register_buffer("bias", bias)
@@ -601,16 +655,27 @@ class FP6Linear(_ScaledOperandModule):
         return self.w_codes.dim() == 3
 
     @classmethod
-    def from_float(cls, module: torch.nn.Linear, kmajor: bool = False):
+    def from_float(cls, module: torch.nn.Linear, kmajor: bool = False, weight_fp_type: str = "fp6_e2m3", act_fp_type: str = "fp6_e2m3"):
         assert isinstance(module, torch.nn.Linear) and module.in_features % 128 == 0 and module.out_features % 8 == 0
-        codes, scales = quantize_fp6(module.weight.detach().float())
+        w_table, act_table = _f6_table("FP6Linear.from_float", weight_fp_type), _f6_table("FP6Linear.from_float", act_fp_type)
+        codes, scales = quantize_fp6(module.weight.detach().float(), table=w_table)
         if kmajor:
             codes = to_kmajor(codes, 6, dealt=True)
         bias = None if module.bias is None else module.bias.detach().to(torch.float16)
-        return cls(codes, scales, bias, module.in_features, module.out_features)
+        return cls(codes, scales, bias, module.in_features, module.out_features, act_table, w_table)
+
+    def extra_repr(self) -> str:
+        return f"{self.in_features}, {self.out_features}, act={self.act_table}, weight={self.w_table}, kmajor={self.kmajor}"
 
     @torch.no_grad()
     def forward(self, x, gate=None, residual=None):
         lead = x.shape[:-1]
-        a_codes, a_scales = quantize_fp6(x.to(torch.float16).reshape(-1, self.in_features), kmajor=self.kmajor)
-        return linear_fp6(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, gate, residual).view(*lead, self.out_features)
+        a_codes, a_scales = quantize_fp6(x.to(torch.float16).reshape(-1, self.in_features), kmajor=self.kmajor, table=self.act_table)
+        return linear_fp6(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, gate, residual, self.act_table,
+                          self.w_table).view(*lead, self.out_features)
+
+    @torch.no_grad()
+    def forward_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor, gate=None, residual=None) -> torch.Tensor:
+        """The same product for an activation that already is in operand form (codes of `act_table`, row-major or the k-major image
+        as the weight is held) - what `rotation.adaln_rotate_quant_token(..., emit="fp6" / "bf6")` emits: fp16 [tokens, out_features]."""
+        return linear_fp6(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, gate, residual, self.act_table, self.w_table)

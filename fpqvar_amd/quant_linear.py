@@ -172,7 +172,7 @@ class QuantizedLinear_fc2(QuantizedLinear):
 def quantize_VAR(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8, a_bit=8, kv_bit=8,
                  act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None, activation_fp_quant=False,
                  weight_fp_quant=False, act_fp_type=None, weight_fp_type=None, fc2_fp_type=None, real_fp4=False,
-                 real_fp6=False, fuse_ffn=False, kmajor_operands=True):
+                 real_fp6=False, fuse_ffn=False, kmajor_operands=True, packed_e3m2=False):
     """tr/quant_utils.py:1095-1167.  The reference matches its own FFN / SelfAttention
     classes; here a module with Linear children ``fc1``+``fc2`` is an FFN and one with
     ``mat_qkv``+``proj`` is a self-attention block.  As in the reference,
@@ -192,7 +192,10 @@ def quantize_VAR(model, weight_quant=None, act_quant=None, quantize_bmm_input=Fa
 
     ``kmajor_operands`` (with ``real_fp4`` / ``real_fp6``'s FP4 / FP6 Linears; default on): weights are held, and activations
     quantized, as k-major operand images (include/fpq.h) - the layout the GEMMs' LDS-DMA engine reads in contiguous 1 KiB
-    pieces; results are bit-identical to the row-major form, the GEMMs 4 - 30 % faster."""
+    pieces; results are bit-identical to the row-major form, the GEMMs 4 - 30 % faster.
+
+    ``packed_e3m2`` (with ``real_fp6``; default off): a layer with an ``fp6_e3m2`` side becomes a ``gemm.FP6Linear`` of its format pair
+    too - 6-bit packed BF6 operands on the FP6 GEMM - instead of a ``gemm.FP8Linear`` with one byte per code."""
     fp4_ok = (real_fp4 and weight_quant == "per_group" and act_quant == "per_group" and w_bit == 4 and a_bit == 4
               and activation_fp_quant and weight_fp_quant and act_fp_type == "fp_e2" and weight_fp_type == "fp_e2")
     if real_fp4 and not fp4_ok:
@@ -215,6 +218,8 @@ def quantize_VAR(model, weight_quant=None, act_quant=None, quantize_bmm_input=Fa
             from .gemm import FP6Linear, FP8Linear
             if weight_fp_type == "fp6_e2m3" and act_fp_type == "fp6_e2m3":
                 return FP6Linear.from_float(lin, kmajor=kmajor_operands)   # 6-bit packed operands
+            if packed_e3m2:   # ... of either format per side
+                return FP6Linear.from_float(lin, kmajor=kmajor_operands, weight_fp_type=weight_fp_type, act_fp_type=act_fp_type)
             return FP8Linear.from_float(lin, weight_fp_type, act_fp_type)   # mixed / E3M2: E4M3-coded levels
         return QuantizedLinear.from_float(lin, **kw)
 
@@ -257,15 +262,34 @@ def _block_index(name: str) -> int:
     return int(name.split(".")[1])
 
 
+_FP6_SYMMETRIC = ("fp6_e2m3", "fp6_e3m2")
+
+
 def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, w_bit=8, a_bit=8, act_quant_sym=None,
                        fc2_act_log2_quant=None, activation_fp_quant=False, weight_fp_quant=False,
-                       ada_lin_formats=None):
+                       ada_lin_formats=None, real_fp6=False, kmajor_operands=True):
     """quantize_VAR with a format pair per (block, layer): ``layer_formats(block_idx, layer)`` returns
     ``(act_fp_type, weight_fp_type)`` for layer in {"fc1", "fc2", "mat_qkv", "proj"}.  ``ada_lin_formats``:
     None leaves the AdaLN Linear in full precision (as tr/ does), a pair quantizes ``ada_lin[1]`` (as the fq/ and
-    rot/ mixed variants do).  Module matching is duck-typed as in quantize_VAR."""
+    rot/ mixed variants do).  Module matching is duck-typed as in quantize_VAR.
+
+    ``real_fp6`` (additive, default off; the W6A6 per_channel / per_token configuration as in quantize_VAR): fc1, mat_qkv, proj and
+    fc2 become ``gemm.FP6Linear`` of their (activation, weight) pair wherever both formats are ``fp6_e2m3`` / ``fp6_e3m2`` and the
+    shape fits the GEMM (in_features % 128 == 0, out_features % 8 == 0) - same quantization decisions, product on the FP6 matrix
+    cores with a format selector per operand; ``ada_lin[1]`` stays a QuantizedLinear.  ``kmajor_operands``: as in quantize_VAR."""
+    fp6_ok = (real_fp6 and weight_quant == "per_channel" and act_quant == "per_token" and w_bit == 6 and a_bit == 6
+              and activation_fp_quant and weight_fp_quant)
+    if real_fp6 and not fp6_ok:
+        raise ValueError("real_fp6 needs weight_quant='per_channel', act_quant='per_token', w_bit = a_bit = 6, fp6 formats")
     common = dict(weight_quant=weight_quant, act_quant=act_quant, w_bit=w_bit, a_bit=a_bit,
                   activation_fp_quant=activation_fp_quant, weight_fp_quant=weight_fp_quant)
+
+    def layer(cls, lin, a, w, **kw):
+        if (fp6_ok and a in _FP6_SYMMETRIC and w in _FP6_SYMMETRIC and lin.in_features % 128 == 0 and lin.out_features % 8 == 0):
+            from .gemm import FP6Linear
+            return FP6Linear.from_float(lin, kmajor=kmajor_operands, weight_fp_type=w, act_fp_type=a)
+        return cls.from_float(lin, act_fp_type=a, weight_fp_type=w, **kw, **common)
+
     for name, m in list(model.named_modules()):
         fc1, fc2 = getattr(m, "fc1", None), getattr(m, "fc2", None)
         qkv, proj = getattr(m, "mat_qkv", None), getattr(m, "proj", None)
@@ -273,16 +297,15 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
         if isinstance(fc1, nn.Linear) and isinstance(fc2, nn.Linear):
             b = _block_index(name)
             a, w = layer_formats(b, "fc1")
-            m.fc1 = QuantizedLinear.from_float(fc1, act_quant_sym=act_quant_sym, act_fp_type=a, weight_fp_type=w, **common)
+            m.fc1 = layer(QuantizedLinear, fc1, a, w, act_quant_sym=act_quant_sym)
             a, w = layer_formats(b, "fc2")
-            m.fc2 = QuantizedLinear_fc2.from_float(fc2, act_quant_sym=False, fc2_act_log2_quant=fc2_act_log2_quant,
-                                                   act_fp_type=a, weight_fp_type=w, **common)
+            m.fc2 = layer(QuantizedLinear_fc2, fc2, a, w, act_quant_sym=False, fc2_act_log2_quant=fc2_act_log2_quant)
         elif isinstance(qkv, nn.Linear) and isinstance(proj, nn.Linear):
             b = _block_index(name)
             a, w = layer_formats(b, "mat_qkv")
-            m.mat_qkv = QuantizedLinear.from_float(qkv, act_quant_sym=act_quant_sym, act_fp_type=a, weight_fp_type=w, **common)
+            m.mat_qkv = layer(QuantizedLinear, qkv, a, w, act_quant_sym=act_quant_sym)
             a, w = layer_formats(b, "proj")
-            m.proj = QuantizedLinear.from_float(proj, act_quant_sym=act_quant_sym, act_fp_type=a, weight_fp_type=w, **common)
+            m.proj = layer(QuantizedLinear, proj, a, w, act_quant_sym=act_quant_sym)
         if ada_lin_formats is not None and isinstance(ada, nn.Sequential) and len(ada) > 1 and isinstance(ada[1], nn.Linear):
             a, w = ada_lin_formats
             ada[1] = QuantizedLinear.from_float(ada[1], act_quant_sym=act_quant_sym, act_fp_type=a, weight_fp_type=w, **common)
@@ -334,9 +357,10 @@ def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None
 def quantize_VAR_mixed_fp6_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,
                                     a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                     activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
-                                    weight_fp_type=None, fc2_fp_type=None):
+                                    weight_fp_type=None, fc2_fp_type=None, real_fp6=False, kmajor_operands=True):
     """models_fp_quant/quant_utils.py:1344-1431: weights always E2M3; activations E3M2 for fc1 and mat_qkv, for fc2
-    E2M3 in blocks 0 and 23 (E3M2 elsewhere), for proj E2M3 in blocks 2-29 (E3M2 in 0, 1); ada_lin[1] E2M3 / E2M3."""
+    E2M3 in blocks 0 and 23 (E3M2 elsewhere), for proj E2M3 in blocks 2-29 (E3M2 in 0, 1); ada_lin[1] E2M3 / E2M3.
+    ``real_fp6`` / ``kmajor_operands``: as in quantize_VAR_mixed - every fc1, fc2, mat_qkv and proj on the FP6 matrix cores."""
     def fmt(b, layer):
         if layer in ("fc1", "mat_qkv"):
             return ("fp6_e3m2", "fp6_e2m3")
@@ -345,4 +369,5 @@ def quantize_VAR_mixed_fp6_datatype(model, weight_quant=None, act_quant=None, qu
         return ("fp6_e2m3" if 2 <= b <= 29 else "fp6_e3m2", "fp6_e2m3")
 
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
-                              activation_fp_quant, weight_fp_quant, ada_lin_formats=("fp6_e2m3", "fp6_e2m3"))
+                              activation_fp_quant, weight_fp_quant, ada_lin_formats=("fp6_e2m3", "fp6_e2m3"),
+                              real_fp6=real_fp6, kmajor_operands=kmajor_operands)

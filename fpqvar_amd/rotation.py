@@ -357,8 +357,9 @@ def adaln_rotate_quant_token(x: torch.Tensor, scale: torch.Tensor, shift: torch.
     """The fused producer for the per-token configurations (W6A6): LayerNorm, modulate, smooth, rotate, then
     fp6_quant_*_per_token_cuda with one scale per token row.  emit="values": fp16 [B, L, C];
     emit="fp8": (codes uint8 [B*L, C], scales fp16 [B*L]) for gemm.linear_fp8; emit="fp6" (table e2m3 only):
-    (dense 6-bit codes uint8 [B*L, C * 3 / 4], scales) for gemm.linear_fp6.  C <= 2560.
-    kmajor (emit="fp6" only): the codes as the activation side's k-major image [C/128, B*L, 96]."""
+    (dense 6-bit codes uint8 [B*L, C * 3 / 4], scales) for gemm.linear_fp6; emit="bf6" (table e3m2 only): the same shapes with BF6
+    E3M2 codes, for gemm.linear_fp6(..., a_table="e3m2").  C <= 2560.
+    kmajor (emit="fp6" / "bf6" only): the codes as the activation side's k-major image [C/128, B*L, 96]."""
     require_gpu(x, "adaln_rotate_quant_token")
     if x.dim() != 3:
         raise RuntimeError("adaln_rotate_quant_token: x must be [B, L, C]")
@@ -369,13 +370,17 @@ def adaln_rotate_quant_token(x: torch.Tensor, scale: torch.Tensor, shift: torch.
         raise RuntimeError("adaln_rotate_quant_token: scale and shift must both be float16 or both float32")
     sc = _mod_rows(scale, bsz, c)
     sh = _mod_rows(shift, bsz, c)
-    if emit not in ("values", "fp8", "fp6"):
+    if emit not in ("values", "fp8", "fp6", "bf6"):
         raise RuntimeError(f"adaln_rotate_quant_token: unknown emit {emit!r}")
     if emit == "fp6" and table != "e2m3":
         raise RuntimeError("adaln_rotate_quant_token: emit='fp6' is the E2M3 operand format")
-    if kmajor and emit != "fp6":
-        raise RuntimeError("adaln_rotate_quant_token: kmajor is a layout of the FP6 operand codes (emit='fp6')")
+    if emit == "bf6" and table != "e3m2":
+        raise RuntimeError("adaln_rotate_quant_token: emit='bf6' is the E3M2 operand format")
+    if kmajor and emit not in ("fp6", "bf6"):
+        raise RuntimeError("adaln_rotate_quant_token: kmajor is a layout of the FP6 operand codes (emit='fp6' / 'bf6')")
     if sc.device == x.device and sh.device == x.device and _native_ok(x, d, smooth, c):
+        if emit == "bf6":
+            return _native.adaln_rotate_quant_token_codes_f6(x, sc, sh, TABLE_IDS[table], _default_mask_tuple(), smooth, float(eps), kmajor)
         if emit == "values":
             return _native.adaln_rotate_quant_token(x, sc, sh, TABLE_IDS[table], _default_mask_tuple(), smooth, float(eps))
         return _native.adaln_rotate_quant_token_codes(x, sc, sh, TABLE_IDS[table], 8 if emit == "fp8" else 6, _default_mask_tuple(),
@@ -385,6 +390,14 @@ def adaln_rotate_quant_token(x: torch.Tensor, scale: torch.Tensor, shift: torch.
     sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
     rows = bsz * seq
     with device_guard(x.device):
+        if emit == "bf6":
+            codes = torch.empty((c // 128, rows, 96) if kmajor else (rows, c * 3 // 4), dtype=torch.uint8, device=x.device)
+            scales = torch.empty((rows,), dtype=torch.float16, device=x.device)
+            check(lib().fpq_adaln_rotate_quant_token_rows_codes_f6(
+                xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c, dtype_id(x.dtype), sc.data_ptr(), sh.data_ptr(),
+                dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, TABLE_IDS[table], 1 if kmajor else 0, stream_ptr(x.device)),
+                "fpq_adaln_rotate_quant_token_rows_codes_f6")
+            return codes, scales
         if emit in ("fp8", "fp6"):
             if emit == "fp6" and table != "e2m3":
                 raise RuntimeError("adaln_rotate_quant_token: emit='fp6' is the E2M3 operand format")

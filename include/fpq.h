@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FPQ_VERSION 129 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
+#define FPQ_VERSION 130 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
                            0.1.3: + fpq_quant_rows_codes_segments, fpq_dequant_rows_codes_segments (round 3);
                            123: + fpq_build_tag (round 4);
                            124: + fpq_set_option, fpq_get_option, fpq_option_name, fpq_gemm_fp4_gelu_dual, fpq_gelu_quant_rows_dual (round 5);
@@ -34,7 +34,9 @@ extern "C" {
                                 (the kernel forms they chose are retired);
                            127: + fpq_gemm_fp4_mx_split_qknorm, fpq_kv_cache_step_qknorm (attn_l2_norm);
                            128: + the packed KV cache: fpq_kv_pack, fpq_attention_blhc_kvcodes;
-                           129: + fpq_gemm_fp6_rows_split, fpq_gemm_fp6_rows_split_qknorm (the split output and the q / k norm for W6A6) */
+                           129: + fpq_gemm_fp6_rows_split, fpq_gemm_fp6_rows_split_qknorm (the split output and the q / k norm for W6A6);
+                           130: + a format per operand on the FP6 matrix-core path (FP6 E2M3 / BF6 E3M2): fpq_quant_rows_codes_f6,
+                                fpq_adaln_rotate_quant_token_rows_codes_f6, fpq_gemm_f6_rows, fpq_gemm_f6_rows_split, fpq_gemm_f6_rows_split_qknorm */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -451,7 +453,8 @@ int fpq_gemm_fp8_rows(const uint8_t* a_codes, const void* a_scales, int a_scale_
 /* The same pair with the operands in the matrix instruction's 6-bit packed form (FP6 E2M3: sign, 2 exponent bits with
  * bias 1, 3 mantissa bits; element j of a row in bits [6j, 6j+6) of the row's little-endian bit string, i.e. dense
  * packing, 3/4 byte per element): 25 % less operand traffic in a kernel bound by exactly that.  table_id must be
- * FPQ_E2M3, cols % 32 == 0 (GEMM: k % 128 == 0); codes: [rows, cols * 3 / 4]; everything else as the FP8 pair. */
+ * FPQ_E2M3 (BF6 E3M2 - sign, 3 exponent bits with bias 3, 2 mantissa bits, same packing - through fpq_quant_rows_codes_f6 /
+ * fpq_gemm_f6_rows below), cols % 32 == 0 (GEMM: k % 128 == 0); codes: [rows, cols * 3 / 4]; everything else as the FP8 pair. */
 int fpq_quant_rows_codes_fp6(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
                              int in_dtype, fpq_stream_t stream);
 int fpq_gemm_fp6_rows(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,
@@ -612,6 +615,47 @@ int fpq_gemm_fp6_rows_split(const uint8_t* a_codes, const void* a_scales, int a_
 int fpq_gemm_fp6_rows_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,
                                    const void* w_scales, int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
                                    const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream);
+/* ---- A format per operand on the FP6 path: FP6 E2M3 or BF6 E3M2 ---------------------------------------------------------------
+ * The matrix instruction decodes each operand by a selector of its own, so the 6-bit path serves all four pairs of the
+ * reference's FP6 format search (E2M3 / E3M2 activations x E2M3 / E3M2 weights).  Both formats use the dense packing of
+ * fpq_quant_rows_codes_fp6 (element j of a row in bits [6j, 6j+6) of the row's little-endian bit string); a code is
+ *     FPQ_E2M3 (FP6): sign, 2 exponent bits (bias 1), 3 mantissa bits: 0, 1/8 .. 7/8, 1 .. 7.5
+ *     FPQ_E3M2 (BF6): sign, 3 exponent bits (bias 3), 2 mantissa bits: 0, 1/16 .. 3/16, 1/4 .. 28
+ * - level for level the reference's tables (tr/quant_utils.py:458-486); a zero level of either sign is code 0.  Row-major codes and
+ * k-major images (fpq_codes_to_kmajor(.., 6, ..)) have the same layout for both formats: only the decoder differs.
+ * table_id / a_table / w_table: FPQ_E2M3 or FPQ_E3M2; anything else is FPQ_ERR_TABLE, decided before any other check and before a
+ * device is touched.  kmajor != 0: the k-major form of the entry point the call otherwise equals.  With FPQ_E2M3 (on both sides)
+ * every call launches exactly what the entry point it extends launches; those keep refusing FPQ_E3M2.
+ *   fpq_quant_rows_codes_f6                      = fpq_quant_rows_codes_fp6 / _fp6_km: the decisions of fpq_quant_rows(.., table_id)
+ *   fpq_adaln_rotate_quant_token_rows_codes_f6   = fpq_adaln_rotate_quant_token_rows_codes_fp6 / _fp6_km
+ *   fpq_gemm_f6_rows                             = fpq_gemm_fp6_rows_ex / fpq_gemm_fp6_rows_km (a: activations, w: weights)
+ *   fpq_gemm_f6_rows_split, .._split_qknorm      = fpq_gemm_fp6_rows_split, fpq_gemm_fp6_rows_split_qknorm
+ * Scale dtypes: (FPQ_E2M3, FPQ_E2M3) takes all four pairs as fpq_gemm_fp6_rows_ex does; a pair with an FPQ_E3M2 side takes fp16
+ * ACTIVATION scales (what the activation quantizers and the adaLN producer write) with fp16 or fp32 weight scales - fp32 activation
+ * scales there are FPQ_ERR_DTYPE (the kernels are not compiled: they would double the compile time of the GEMM unit).
+ * Numerics: the arithmetic and the bound of fpq_gemm_fp8_rows (above).  As stated there, the matrix core's 128-term dot of E3M2
+ * levels loses more than the derived bound allows - measured through the FP8 GEMM: up to 5.3 times - and the project holds those
+ * levels to 8 times the bound (tests/gemm_model.py, WIDE_FP8_MEASURED).  The same levels in the 6-bit operand form get the same
+ * allowance wherever a side holds E3M2 levels (tests/test_gpu_bf6.py); (FPQ_E2M3, FPQ_E2M3) stays within 1.0 times the bound.
+ * Measured on an MI355X in the BF6 form (profiles/r08_bf6_gemm_bound.txt): at most 1.85 times the bound (E3M2 x E3M2 with a bias that
+ * cancels the product), below 1.0 for every mixed pair; bit-equal to fpq_gemm_fp8_rows on the same levels as E4M3 bytes in all but a few
+ * elements - the 6-bit and the 8-bit operand form of a level are rounded alike. */
+int fpq_quant_rows_codes_f6(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id, int in_dtype,
+                            int kmajor, fpq_stream_t stream);
+int fpq_adaln_rotate_quant_token_rows_codes_f6(const void* x, uint8_t* codes, void* row_scales, int64_t rows, int64_t cols,
+                                               int in_dtype, const void* scale, const void* shift, int mod_dtype,
+                                               int64_t rows_per_batch, float eps, const float* smooth,
+                                               const uint32_t* sign_mask_host, int table_id, int kmajor, fpq_stream_t stream);
+int fpq_gemm_f6_rows(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, int a_table, const uint8_t* w_codes,
+                     const void* w_scales, int w_scale_dtype, int w_table, const void* bias, void* out, int64_t tokens, int64_t outs,
+                     int64_t k, const fpq_gemm_epilogue_t* epilogue, int kmajor, fpq_stream_t stream);
+int fpq_gemm_f6_rows_split(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, int a_table, const uint8_t* w_codes,
+                           const void* w_scales, int w_scale_dtype, int w_table, const void* bias, int64_t tokens, int64_t outs, int64_t k,
+                           const fpq_gemm_split_t* split, int kmajor, fpq_stream_t stream);
+int fpq_gemm_f6_rows_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, int a_table, const uint8_t* w_codes,
+                                  const void* w_scales, int w_scale_dtype, int w_table, const float* bias, int64_t tokens, int64_t outs,
+                                  int64_t k, const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream);
+
 /* fpq_kv_cache_step_qknorm: fpq_kv_cache_step (same arguments, same checks) for an fp16 qkv WITHOUT the norm (path F, or a
  * mat_qkv that is not split): the new k is normalized and the bias added on its way into the cache, and the same launch writes
  * q_out - fp16 [batch, n_new, row_elems], contiguous - from new_q (the pitches of new_k).  head_dim == 64, row_elems % 64 == 0,
