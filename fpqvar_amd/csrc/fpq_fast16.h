@@ -1480,5 +1480,26 @@ inline const Lut16Tab& lut16_codes6(int table_id) {
 }
 inline const Lut16Tab& lut16_codes6_e2m3() { return lut16_codes6(FPQ_E2M3); }
 
+// bucket -> 6-bit code table of the per-group A6W4 emitter (fpq_codes_g6.h): the bucket structure of FPQ_E1M2 with the FP6 E2M3
+// codes of its levels (0, 0.25 .. 1.75 are E2M3 numbers) or of FPQ_E3M0 with the BF6 E3M2 codes of its levels (0, 0.25, 0.5, 1 ..
+// 16 are E3M2 numbers); each built once on first use (immutable afterwards)
+inline const Lut16Tab& lut16_codes_g6(int table_id) {
+  const auto build = [](int id) {
+    auto* t = new Lut16Tab();
+    const Lut16Host& h = lut16_host(id, id);
+    const int n = 1 << (16 - h.args.shift);
+    uint16_t full[kLutLdsEntries] = {0};
+    for (int i = 0; i < n; ++i) full[i] = (uint16_t)(id == FPQ_E3M0 ? e3m2_of_level(h2f(h.full[i])) : e2m3_of_level(h2f(h.full[i])));
+    if (!lut16_compress(full, h.args.shift, t)) abort();   // same structure as the level table it is derived from
+    return t;
+  };
+  if (table_id == FPQ_E3M0) {
+    static const Lut16Tab* e3 = build(FPQ_E3M0);
+    return *e3;
+  }
+  static const Lut16Tab* e1 = build(FPQ_E1M2);
+  return *e1;
+}
+
 // k-major images are addressed with 32-bit byte offsets (and int buffer ranges) by their producers: the whole image must stay below 2 GiB
 inline bool km_image_fits(int64_t rows, int64_t row_bytes) { return rows < (1ll << 31) && rows * row_bytes < (1ll << 31); }

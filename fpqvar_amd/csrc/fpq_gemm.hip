@@ -9,6 +9,7 @@ namespace {
 #include "fpq_gemm_fp4.h"
 #include "fpq_gemm_fp8.h"
 #include "fpq_gemm_fp6.h"
+#include "fpq_gemm_a6w4.h"
 #include "fpq_attention.h"
 
 // Per-group scales [rows, groups] (fp16 or fp32) -> the fp32 k-major scale image [groups][image_rows] of the FP4 GEMM (include/fpq.h):
@@ -318,6 +319,53 @@ int fpq_gemm_fp4_mx_km(const uint8_t* a_image, const void* a_scales, const uint8
                        int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
                        const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream) {
   return gemm_fp4_mx_impl(a_image, a_scales, w_image, w_scales, w_scale_dtype, bias, out, tokens, outs, k, epilogue, true, stream);
+}
+
+// 6-bit activation codes (E1M2 levels as FP6 E2M3 codes, E3M0 levels as BF6 E3M2 codes) x the FP4 GEMM's E2M1 weight nibbles
+// (fpq_gemm_a6w4.h, include/fpq.h).  Two LDS-DMA tilings, chosen as fpq_gemm_fp4_mx_ex chooses between the same two
+// (FPQ_GEMM_CFG 20 / 30 forces one); there is no register-staged form: K is limited by the scale tiles as there, and the bias
+// is read four outputs at a time.
+int fpq_gemm_a6w4_mx(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                     int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
+                     const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream) {
+  if (a_table != FPQ_E1M2 && a_table != FPQ_E3M0) return FPQ_ERR_TABLE;
+  if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
+  GemmEpi epi;
+  if (int rc = gemm_epilogue(epilogue, tokens, &epi)) return rc;
+  if (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (k % 128 != 0 || k > 128 * 64 || outs % 8 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
+  if (tokens == 0 || outs == 0) return FPQ_OK;
+  if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
+  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out) & 15) != 0 || ((uintptr_t)bias & 7) != 0 || ((uintptr_t)a_scales & 1) != 0 ||
+      ((uintptr_t)w_scales & (w_scale_dtype == FPQ_F16 ? 1 : 3)) != 0)
+    return FPQ_ERR_ARG;
+  const int G = (int)(k / 128);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t mid_tiles = ((tokens + 127) / 128) * ((outs + 127) / 128);
+  const int want = fpq_opt(OPT_FPQ_GEMM_CFG, 0);
+  const int cfg = (want == 20 || want == 30) ? want : mid_tiles <= 384 ? 30 : 20;
+#define FPQ_A6W4_GO(TW, MT, FA)                                                                                      \
+  hipLaunchKernelGGL((gemm_a6w4_kernel<TW, MT, 4, FA>), dim3((unsigned)n_wg), dim3(256), lds, st, a_codes,            \
+                     (const _Float16*)a_scales, w_codes, (const TW*)w_scales, (const _Float16*)bias, (_Float16*)out,  \
+                     (int)tokens, (int)outs, (int)k, epi)
+#define FPQ_A6W4_TILE(MT)                                                                                            \
+  do {                                                                                                               \
+    using Cfg = GemmA6W4Cfg<MT, 4>;                                                                                  \
+    const size_t lds = Cfg::lds(G);                                                                                  \
+    if (lds > 160 * 1024) return FPQ_ERR_SHAPE;                                                                      \
+    const int64_t n_col = (outs + Cfg::BN - 1) / Cfg::BN, n_row = (tokens + Cfg::BM - 1) / Cfg::BM;                  \
+    const int64_t n_wg = 8 * ((n_col + 7) / 8) * n_row;                                                              \
+    if (n_wg > 0x7FFFFFFF) return FPQ_ERR_SHAPE;                                                                     \
+    if (a_table == FPQ_E1M2 && w_scale_dtype == FPQ_F16) FPQ_A6W4_GO(_Float16, MT, 2);                               \
+    else if (a_table == FPQ_E1M2) FPQ_A6W4_GO(float, MT, 2);                                                         \
+    else if (w_scale_dtype == FPQ_F16) FPQ_A6W4_GO(_Float16, MT, 3);                                                 \
+    else FPQ_A6W4_GO(float, MT, 3);                                                                                  \
+  } while (0)
+  if (cfg == 30) FPQ_A6W4_TILE(2);
+  else FPQ_A6W4_TILE(4);
+#undef FPQ_A6W4_TILE
+#undef FPQ_A6W4_GO
+  return check_launch();
 }
 
 #ifdef FPQ_GEMM6_STAMPS

@@ -390,6 +390,7 @@ __global__ __launch_bounds__(kBlock) void rows_negrev_scalar_kernel(const T* __r
 #include "fpq_fast32.h"
 #include "fpq_codes_mx.h"    // the FP4 operand emitter (fpq_quant_rows_codes_mx: it shares codes128_kernel with fpq_quant_rows_codes)
 #include "fpq_codes_fp8.h"   // (codes8_vec16, the 6-bit code lookup of fpq_kv_pack)
+#include "fpq_codes_g6.h"    // the A6W4 GEMM's activation emitter (fpq_quant_rows_codes_g6)
 #include "fpq_kv_codes.h"    // the packed KV cache's producer (fpq_kv_pack; its consumer is the attention kernel, fpq_gemm.hip)
 
 // ---------------------------------------------------------------------------------
@@ -1663,6 +1664,34 @@ int fpq_quant_rows_codes_mx(const void* x, uint8_t* codes, void* scales, int64_t
 int fpq_quant_rows_codes_mx_km(const void* x, uint8_t* image, void* scales, int64_t rows, int64_t cols, int in_dtype,
                                fpq_stream_t stream) {
   return quant_rows_codes_mx_impl(x, image, scales, rows, cols, in_dtype, true, stream);
+}
+
+// per-group(128) E1M2 / E3M0 quantization to dense 6-bit codes (fpq_codes_g6.h, include/fpq.h)
+int fpq_quant_rows_codes_g6(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id, int in_dtype,
+                            fpq_stream_t stream) {
+  if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
+  if (table_id != FPQ_E1M2 && table_id != FPQ_E3M0) return FPQ_ERR_TABLE;
+  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (cols % 128 != 0) return FPQ_ERR_SHAPE;
+  if (rows == 0 || cols == 0) return FPQ_OK;
+  if (!x || !codes || !scales) return FPQ_ERR_ARG;
+  if ((((uintptr_t)x | (uintptr_t)codes) & 15) != 0 || ((uintptr_t)scales & (in_dtype == FPQ_F16 ? 1 : 3)) != 0) return FPQ_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (in_dtype == FPQ_F16) {
+    const Lut16Host& h = lut16_host(table_id, table_id);
+    if (!h.tab_valid) return FPQ_ERR_TABLE;
+    const int64_t n_vec = rows * (cols / 8);
+    hipLaunchKernelGGL(group6_emit16_kernel, dim3(grid_for((n_vec + kBlock - 1) / kBlock, 16384)), dim3(kBlock), 0, st, (const u32x4*)x,
+                       codes, (uint16_t*)scales, n_vec, h.args, lut16_codes_g6(table_id));
+  } else {
+    const int64_t n_blk = rows * (cols / 32);
+    const dim3 grid(grid_for((n_blk + kBlock - 1) / kBlock, 1 << 20));
+    if (table_id == FPQ_E3M0)
+      hipLaunchKernelGGL((group6_emit_kernel<float, true>), grid, dim3(kBlock), 0, st, (const u32x4*)x, codes, (float*)scales, n_blk, make_fmt(FPQ_E3M0));
+    else
+      hipLaunchKernelGGL((group6_emit_kernel<float, false>), grid, dim3(kBlock), 0, st, (const u32x4*)x, codes, (float*)scales, n_blk, make_fmt(FPQ_E1M2));
+  }
+  return check_launch();
 }
 
 int fpq_kv_pack(uint8_t* codes, void* scales, int kv_bit, int64_t batch, int64_t max_len, int64_t heads, int64_t head_dim, int64_t pos,

@@ -342,6 +342,80 @@ def linear_fp4_gelu_dual(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes:
     return (out, h) if return_gelu else out
 
 
+# ---- A6W4: E1M2 / E3M0 activations as dense 6-bit codes against the FP4 weights (include/fpq.h) ----------------------------
+# The reference's mixed W4A4 model gives fc1 / mat_qkv an E3M0 or E1M2 activation format in most blocks; the matrix instruction
+# decodes a 6-bit activation fragment (E1M2 levels as FP6 E2M3 codes, E3M0 levels as BF6 E3M2 codes) against E2M1 nibbles.
+_G6_TABLES = {"e1m2": "e1m2", "fp_e1": "e1m2", "e3m0": "e3m0", "fp_e3": "e3m0"}
+_G6_CODE_FORMAT = {"e1m2": "e2m3", "e3m0": "e3m2"}   # the 6-bit hardware format that holds the table's levels
+
+
+def _g6_table(name: str, table: str) -> str:
+    try:
+        return _G6_TABLES[table]
+    except (KeyError, TypeError):
+        raise RuntimeError(f"{name}: the per-group 6-bit activation tables are 'e1m2' and 'e3m0', got {table!r}") from None
+
+
+def quantize_g6(x: torch.Tensor, table: str = "e3m0") -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [..., K] fp16/fp32 (K % 128 == 0) -> (codes uint8 [rows, K * 3 / 4]: dense 6-bit codes of the E1M2 / E3M0 levels,
+    scales [rows, K/128] in x.dtype); level(code) * scale == fp_quant_e1_per_group_cuda / fp_quant_e3_per_group_cuda (x, 4, 128)
+    bit for bit (fpq_quant_rows_codes_g6)."""
+    require_gpu(x, "quantize_g6")
+    if x.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError(f"quantize_g6: x must be float16 or float32, got {x.dtype}")
+    from ._lib import TABLE_IDS
+    table = _g6_table("quantize_g6", table)
+    k = x.shape[-1]
+    if k % 128 != 0:
+        raise RuntimeError("quantize_g6: the last dimension must be a multiple of 128")
+    xc = x.contiguous()
+    rows = xc.numel() // k
+    codes = torch.empty((rows, k * 3 // 4), dtype=torch.uint8, device=x.device)
+    scales = torch.empty((rows, k // 128), dtype=x.dtype, device=x.device)
+    with device_guard(x.device):
+        check(lib().fpq_quant_rows_codes_g6(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, k, TABLE_IDS[table],
+                                            dtype_id(x.dtype), stream_ptr(x.device)), "fpq_quant_rows_codes_g6")
+    return codes, scales
+
+
+def dequantize_g6(codes: torch.Tensor, scales: torch.Tensor, table: str = "e3m0") -> torch.Tensor:
+    """Reference decoder in torch ops (tests / debugging): fp32 [rows, K] = level(code) * scale of the code's group."""
+    table = _g6_table("dequantize_g6", table)
+    rows = codes.shape[0]
+    lv = dequantize_fp6(codes, torch.ones(rows, dtype=torch.float32, device=codes.device), _G6_CODE_FORMAT[table])
+    return (lv.view(rows, -1, 128) * scales.float().unsqueeze(-1)).reshape(rows, -1)
+
+
+def linear_a6w4(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor,
+                bias: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
+                residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp16 [tokens, outs] = dequantize_g6(a) @ dequantize_mx(w).T + bias on the matrix cores (fpq_gemm_a6w4_mx): a 6-bit
+    activation fragment of `a_table` ('e1m2' / 'e3m0') against the E2M1 weight nibbles `quantize_mx` emits; gate / residual as
+    in linear_fp4.  Row-major operands only."""
+    require_gpu(a_codes, "linear_a6w4")
+    from ._lib import TABLE_IDS
+    a_table = _g6_table("linear_a6w4", a_table)
+    if a_codes.dim() != 2 or w_codes.dim() != 2:
+        raise RuntimeError("linear_a6w4: row-major operands only (there is no k-major A6W4 form)")
+    tokens, outs, k = a_codes.shape[0], w_codes.shape[0], w_codes.shape[1] * 2
+    if k % 128 != 0 or a_codes.shape[1] * 4 != k * 3 or a_scales.dtype != torch.float16:
+        raise RuntimeError("linear_a6w4: operand shapes / activation scale dtype mismatch")
+    _check_operand("linear_a6w4(activation)", a_codes, a_scales, tokens, k * 3 // 4, tokens * (k // 128), a_codes.device)
+    _check_operand("linear_a6w4(weight)", w_codes, w_scales, outs, k // 2, outs * (k // 128), a_codes.device)
+    ep, keep, out = _epilogue("linear_a6w4", tokens, outs, gate, residual, None, a_codes.device)
+    b = None if bias is None else bias.detach().to(torch.float16).reshape(-1).contiguous()
+    if b is not None and (b.numel() != outs or b.device != a_codes.device):
+        raise RuntimeError(f"linear_a6w4: bias must hold {outs} elements on {a_codes.device}")
+    if b is not None and b.data_ptr() % 8:
+        b = b.clone()
+    with device_guard(a_codes.device):
+        check(lib().fpq_gemm_a6w4_mx(a_codes.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_codes.data_ptr(), w_scales.data_ptr(),
+                                     dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), out.data_ptr(), tokens, outs, k, ep,
+                                     stream_ptr(a_codes.device)), "fpq_gemm_a6w4_mx")
+    del keep
+    return out
+
+
 class FP4Linear(_ScaledOperandModule):
     """Drop-in for QuantizedLinear in the W4A4 per-group `fp_e2` configuration that runs on the FP4
     matrix cores instead of simulating FP4 in fp16: weights are stored as hardware E2M1 codes + one
@@ -350,9 +424,10 @@ class FP4Linear(_ScaledOperandModule):
     Same quantization decisions as the reference (codes * scale == its fake-quantized tensors bit for
     bit); the GEMM itself is more exact than the reference's fp16 GEMM (tolerance-level agreement)."""
 
-    def __init__(self, w_codes, w_scales, bias, in_features, out_features):
+    def __init__(self, w_codes, w_scales, bias, in_features, out_features, act_table: str = "e2m1"):
         super().__init__()
         self.in_features, self.out_features = in_features, out_features
+        self.act_table = act_table   # "e2m1": nibbles on the FP4 GEMM; "e1m2" / "e3m0": 6-bit codes on the A6W4 GEMM, same weight
         self.register_buffer("w_codes", w_codes)
         self.register_buffer("w_scales", w_scales)
         self.register_buffer("bias", bias)
@@ -363,26 +438,49 @@ class FP4Linear(_ScaledOperandModule):
         return self.w_codes.dim() == 3
 
     @classmethod
-    def from_float(cls, module: torch.nn.Linear, kmajor: bool = False):
+    def from_float(cls, module: torch.nn.Linear, kmajor: bool = False, act_fp_type: str = "fp_e2"):
+        """act_fp_type: the activation's per-group format - "fp_e2" (E2M1, the FP4 GEMM) or "fp_e1" / "fp_e3" (E1M2 / E3M0: the
+        A6W4 GEMM on the same stored weight, row-major only)."""
         assert isinstance(module, torch.nn.Linear) and module.in_features % 128 == 0 and module.out_features % 8 == 0
+        if act_fp_type in ("fp_e2", "e2m1"):
+            act_table = "e2m1"
+        else:
+            act_table = _g6_table("FP4Linear.from_float", act_fp_type)
+            if kmajor:
+                raise ValueError(f"FP4Linear.from_float: act_fp_type={act_fp_type!r} runs on the A6W4 GEMM, which has no k-major form "
+                                 "(kmajor=True needs act_fp_type='fp_e2')")
         codes, scales = quantize_mx(module.weight.detach().float())
         if kmajor:
             codes, scales = to_kmajor(codes, 4, dealt=True), to_kmajor_scales(scales, weight_side=True)
         bias = None if module.bias is None else module.bias.detach().to(torch.float16)
-        return cls(codes, scales, bias, module.in_features, module.out_features)
+        return cls(codes, scales, bias, module.in_features, module.out_features, act_table)
+
+    def extra_repr(self) -> str:
+        return f"in_features={self.in_features}, out_features={self.out_features}, act={self.act_table}, w=e2m1"
 
     @torch.no_grad()
     def forward(self, x, gate=None, residual=None):
         """gate / residual: the AdaLN block's `residual + y.mul(gate)` fused into the GEMM (see linear_fp4)."""
         lead = x.shape[:-1]
-        a_codes, a_scales = quantize_mx(x.to(torch.float16).reshape(-1, self.in_features), kmajor=self.kmajor)
+        x2 = x.to(torch.float16).reshape(-1, self.in_features)
+        if self.act_table != "e2m1":
+            a_codes, a_scales = quantize_g6(x2, self.act_table)
+            y = linear_a6w4(a_codes, a_scales, self.act_table, self.w_codes, self.w_scales, self.bias, gate, residual)
+            return y.view(*lead, self.out_features)
+        a_codes, a_scales = quantize_mx(x2, kmajor=self.kmajor)
         y = linear_fp4(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, gate, residual, outs=self.out_features)
         return y.view(*lead, self.out_features)
 
     @torch.no_grad()
-    def forward_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor, gate=None, residual=None) -> torch.Tensor:
+    def forward_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor, gate=None, residual=None, table: Optional[str] = None) -> torch.Tensor:
         """The same product for an activation that already is in operand form - what the fused producers
-        `rotation.rotate_quant_mx` / `rotation.adaln_rotate_quant_mx` emit: fp16 [tokens, out_features]."""
+        `rotation.rotate_quant_mx` / `rotation.adaln_rotate_quant_mx` emit, or `quantize_g6`: fp16 [tokens, out_features].
+        table: the format the codes are in (default: the module's activation format)."""
+        table = self.act_table if table is None else ("e2m1" if table in ("e2m1", "fp_e2") else _g6_table("FP4Linear.forward_operands", table))
+        if table != "e2m1":
+            if self.kmajor:
+                raise RuntimeError("FP4Linear.forward_operands: 6-bit activation codes need a row-major weight (no k-major A6W4 form)")
+            return linear_a6w4(a_codes, a_scales, table, self.w_codes, self.w_scales, self.bias, gate, residual)
         return linear_fp4(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, gate, residual, outs=self.out_features)
 
 

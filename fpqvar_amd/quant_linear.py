@@ -267,7 +267,7 @@ _FP6_SYMMETRIC = ("fp6_e2m3", "fp6_e3m2")
 
 def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, w_bit=8, a_bit=8, act_quant_sym=None,
                        fc2_act_log2_quant=None, activation_fp_quant=False, weight_fp_quant=False,
-                       ada_lin_formats=None, real_fp6=False, kmajor_operands=True):
+                       ada_lin_formats=None, real_fp6=False, kmajor_operands=True, real_fp4=False):
     """quantize_VAR with a format pair per (block, layer): ``layer_formats(block_idx, layer)`` returns
     ``(act_fp_type, weight_fp_type)`` for layer in {"fc1", "fc2", "mat_qkv", "proj"}.  ``ada_lin_formats``:
     None leaves the AdaLN Linear in full precision (as tr/ does), a pair quantizes ``ada_lin[1]`` (as the fq/ and
@@ -276,7 +276,17 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
     ``real_fp6`` (additive, default off; the W6A6 per_channel / per_token configuration as in quantize_VAR): fc1, mat_qkv, proj and
     fc2 become ``gemm.FP6Linear`` of their (activation, weight) pair wherever both formats are ``fp6_e2m3`` / ``fp6_e3m2`` and the
     shape fits the GEMM (in_features % 128 == 0, out_features % 8 == 0) - same quantization decisions, product on the FP6 matrix
-    cores with a format selector per operand; ``ada_lin[1]`` stays a QuantizedLinear.  ``kmajor_operands``: as in quantize_VAR."""
+    cores with a format selector per operand; ``ada_lin[1]`` stays a QuantizedLinear.  ``kmajor_operands``: as in quantize_VAR.
+
+    ``real_fp4`` (additive, default off; the W4A4 per-group configuration as in quantize_VAR): every layer with an ``fp_e2`` weight
+    and an ``fp_e1`` / ``fp_e2`` / ``fp_e3`` activation whose shape fits the GEMM becomes a ``gemm.FP4Linear`` of its activation
+    format - ``fp_e2`` on the FP4 GEMM (k-major with ``kmajor_operands``), ``fp_e1`` / ``fp_e3`` as 6-bit codes on the A6W4 GEMM
+    against the same stored E2M1 weight (row-major: that GEMM has no k-major form).  Every other layer (fc2's dual format,
+    ``ada_lin[1]``, an E1M2 / E3M0 weight) stays the QuantizedLinear it is without the keyword."""
+    fp4_ok = (real_fp4 and weight_quant == "per_group" and act_quant == "per_group" and w_bit == 4 and a_bit == 4
+              and activation_fp_quant and weight_fp_quant)
+    if real_fp4 and not fp4_ok:
+        raise ValueError("real_fp4 needs weight_quant = act_quant = 'per_group', w_bit = a_bit = 4, fp formats on both sides")
     fp6_ok = (real_fp6 and weight_quant == "per_channel" and act_quant == "per_token" and w_bit == 6 and a_bit == 6
               and activation_fp_quant and weight_fp_quant)
     if real_fp6 and not fp6_ok:
@@ -288,6 +298,9 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
         if (fp6_ok and a in _FP6_SYMMETRIC and w in _FP6_SYMMETRIC and lin.in_features % 128 == 0 and lin.out_features % 8 == 0):
             from .gemm import FP6Linear
             return FP6Linear.from_float(lin, kmajor=kmajor_operands, weight_fp_type=w, act_fp_type=a)
+        if (fp4_ok and w == "fp_e2" and a in ("fp_e1", "fp_e2", "fp_e3") and lin.in_features % 128 == 0 and lin.out_features % 8 == 0):
+            from .gemm import FP4Linear
+            return FP4Linear.from_float(lin, kmajor=kmajor_operands and a == "fp_e2", act_fp_type=a)
         return cls.from_float(lin, act_fp_type=a, weight_fp_type=w, **kw, **common)
 
     for name, m in list(model.named_modules()):
@@ -315,10 +328,12 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
 def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,
                                     a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                     activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
-                                    weight_fp_type=None, fc2_fp_type=None):
+                                    weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True):
     """models_fp_quant/quant_utils.py:1256-1341: fc1 is E2M1 in blocks 6-20 and E3M0 elsewhere, mat_qkv E2M1 in
     blocks 0, 24, 25 and E3M0 elsewhere (activations; weights always E2M1); proj, fc2 and ada_lin[1] take the
-    caller's formats."""
+    caller's formats.
+    ``real_fp4`` / ``kmajor_operands``: as in quantize_VAR_mixed - every E2M1-weight fc1 / mat_qkv / proj on the matrix cores,
+    the E3M0 activations as 6-bit codes."""
     fc1_e2, qkv_e2 = set(range(6, 21)), {0, 24, 25}
 
     def fmt(b, layer):
@@ -331,14 +346,17 @@ def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, qu
         return (act_fp_type, weight_fp_type)
 
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
-                              activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type))
+                              activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type),
+                              real_fp4=real_fp4, kmajor_operands=kmajor_operands)
 
 
 def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,
                                         a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                         activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
-                                        weight_fp_type=None, fc2_fp_type=None):
-    """models_fp_quant_rotate/quant_utils.py:982-1066: as the mixed FP4 variant, with mat_qkv E2M1 in blocks 24, 25 only."""
+                                        weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True):
+    """models_fp_quant_rotate/quant_utils.py:982-1066: as the mixed FP4 variant, with mat_qkv E2M1 in blocks 24, 25 only.
+    ``real_fp4`` / ``kmajor_operands``: as in quantize_VAR_mixed - every E2M1-weight fc1 / mat_qkv / proj on the matrix cores,
+    the E3M0 activations as 6-bit codes."""
     fc1_e2, qkv_e2 = set(range(6, 21)), {24, 25}
 
     def fmt(b, layer):
@@ -351,7 +369,8 @@ def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None
         return (act_fp_type, weight_fp_type)
 
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
-                              activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type))
+                              activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type),
+                              real_fp4=real_fp4, kmajor_operands=kmajor_operands)
 
 
 def quantize_VAR_mixed_fp6_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,

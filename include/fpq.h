@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FPQ_VERSION 130 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
+#define FPQ_VERSION 131 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
                            0.1.3: + fpq_quant_rows_codes_segments, fpq_dequant_rows_codes_segments (round 3);
                            123: + fpq_build_tag (round 4);
                            124: + fpq_set_option, fpq_get_option, fpq_option_name, fpq_gemm_fp4_gelu_dual, fpq_gelu_quant_rows_dual (round 5);
@@ -36,7 +36,9 @@ extern "C" {
                            128: + the packed KV cache: fpq_kv_pack, fpq_attention_blhc_kvcodes;
                            129: + fpq_gemm_fp6_rows_split, fpq_gemm_fp6_rows_split_qknorm (the split output and the q / k norm for W6A6);
                            130: + a format per operand on the FP6 matrix-core path (FP6 E2M3 / BF6 E3M2): fpq_quant_rows_codes_f6,
-                                fpq_adaln_rotate_quant_token_rows_codes_f6, fpq_gemm_f6_rows, fpq_gemm_f6_rows_split, fpq_gemm_f6_rows_split_qknorm */
+                                fpq_adaln_rotate_quant_token_rows_codes_f6, fpq_gemm_f6_rows, fpq_gemm_f6_rows_split, fpq_gemm_f6_rows_split_qknorm;
+                           131: + E1M2 / E3M0 activations on the matrix cores against FP4 weights ("A6W4"): fpq_quant_rows_codes_g6,
+                                fpq_gemm_a6w4_mx */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -655,6 +657,46 @@ int fpq_gemm_f6_rows_split(const uint8_t* a_codes, const void* a_scales, int a_s
 int fpq_gemm_f6_rows_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, int a_table, const uint8_t* w_codes,
                                   const void* w_scales, int w_scale_dtype, int w_table, const float* bias, int64_t tokens, int64_t outs,
                                   int64_t k, const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream);
+
+/* ---- A6W4: E1M2 / E3M0 activations x E2M1 weights, per group of 128 ------------------------------------------------------
+ * The reference's mixed W4A4 model (quantize_VAR_mixed_fp4_datatype / quantize_VAR_use_different_datatype) gives fc1 and mat_qkv
+ * an E3M0 or E1M2 ACTIVATION format in most blocks and keeps every weight E2M1.  The matrix instruction decodes only E2M1 from
+ * nibbles, but it takes a format selector per operand and runs 6-bit operands at the FP4 rate; every E1M2 level (0, 0.25 ..
+ * 1.75) is an FP6 E2M3 number and every E3M0 level (0, 0.25, 0.5, 1 .. 16) a BF6 E3M2 number.
+ *
+ * fpq_quant_rows_codes_g6: per-group(128) quantization on table_id = FPQ_E1M2 or FPQ_E3M0 (anything else: FPQ_ERR_TABLE) straight
+ * to dense 6-bit hardware codes - the E2M3 codes of E1M2 levels, the E3M2 codes of E3M0 levels, in the bit format of
+ * fpq_quant_rows_codes_fp6 (element j of a row in bits [6j, 6j + 6) of the row's little-endian bit string) - and one scale per
+ * group in x's dtype.  x: [rows, cols] F16 or F32, cols % 128 == 0; codes: [rows, cols * 3 / 4]; scales: [rows, cols / 128];
+ * x and codes 16-byte aligned.  Same scale / normalise / rounding arithmetic as fpq_quant_rows(table_id, cols = 128): level(code)
+ * * scale (one product in x's dtype) reproduces fp_quant_e1_per_group_cuda / fp_quant_e3_per_group_cuda bit for bit.  A group
+ * whose maximum is not finite is handled as fpq_quant_rows_codes_mx handles it: the maximum itself (+inf, or the NaN) is stored as
+ * the group's scale and every element gets the code of the level the quantizer's table lookup gives it, so level(code) * scale
+ * is again what fpq_quant_rows writes (NaN from 0 * inf or anything * NaN, +-inf where a non-zero level meets an infinite scale):
+ * the non-finite value travels in the SCALE, every code is a valid code.  An all-zero group has scale 0 and code 0 throughout.
+ *
+ * fpq_gemm_a6w4_mx: out[t, o] = fp16(bias[o] + sum_g a_scale[t,g] * w_scale[o,g] * dot_128(level(a)[t,g,:], level(w)[o,g,:])), with
+ * the optional gate / residual tail of fpq_gemm_epilogue_t (NULL: none).  a_codes: 6-bit [tokens, 3 k / 4] of a_table (FPQ_E1M2:
+ * decoded as FP6 E2M3, cbsz = 2; FPQ_E3M0: as BF6 E3M2, cbsz = 3; anything else FPQ_ERR_TABLE), a_scales fp16 [tokens, k / 128];
+ * w_codes / w_scales / w_scale_dtype exactly what fpq_gemm_fp4_mx takes (E2M1 nibbles [outs, k / 2], blgp = 4): one stored FP4
+ * weight serves both GEMMs.  Shape and alignment rules of fpq_gemm_fp4_mx_ex (k % 128 == 0, k <= 8192, outs % 8 == 0, codes and
+ * out 16-byte aligned), checked before any launch; the bias must be 8-byte aligned (there is no register-staged form to fall
+ * back to).  Row-major operands only: no k-major images, no split output, no q / k norm, no fc1 tail.
+ * Numerics: the per-group steps of fpq_gemm_fp4_mx's LDS-DMA tilings - t = fl(d_g sa), acc = fma(t, sw, acc), out = fp16(acc +
+ * bias).  Products of an E3M0 or E1M2 level and an E2M1 level are multiples of 1/8 (|product| <= 96 resp. 10.5), so the exact
+ * 128-term dot d_g has at most 17 significant bits (|d_g| <= 12288) and fits the fp32 accumulator.
+ * MEASURED on an MI355X before anything else (profiles/r09_a6w4_dot.txt): with k = 128, unit scales and no bias, dots that are fp16
+ * numbers - the largest products cancelling beside a few +-1/8, all 15 x 15 level pairs alone and 128-fold, the largest product
+ * beside 127 smallest - come out bit for bit for both formats: the matrix core keeps every product (it does not for full-range
+ * E3M2 x E3M2 codes, see fpq_gemm_f6_rows).  So the contract is fpq_gemm_fp4_mx's, unchanged: against the float64 product of the
+ * decoded operands every element is within 2^-11 |ref| + 2^-25 + (1 + 2^-10) 2^-24 (S + R + |ref|) (allowance 1.0; worst measured
+ * over the shape sweep 1.000 x the bound, the fp16 output rounding), and the output is bit-equal to an fp32 model of those steps
+ * (tests/a6w4_model.py, tests/test_gpu_a6w4.py).  Both tilings (64 x 128 and 128 x 128 tiles) share the K order: bit-equal. */
+int fpq_quant_rows_codes_g6(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id, int in_dtype,
+                            fpq_stream_t stream);
+int fpq_gemm_a6w4_mx(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                     int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
+                     const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream);
 
 /* fpq_kv_cache_step_qknorm: fpq_kv_cache_step (same arguments, same checks) for an fp16 qkv WITHOUT the norm (path F, or a
  * mat_qkv that is not split): the new k is normalized and the bias added on its way into the cache, and the same launch writes
