@@ -23,6 +23,185 @@ __global__ __launch_bounds__(256) void scales_to_kmajor_kernel(const Ts* __restr
     image[i] = r < rows ? (float)scales[r * groups + g] : 0.0f;
   }
 }
+
+// ---- what the GEMM entry points below share: argument descriptors -> the kernels' form, the tile choice, the launch ----------
+
+// validates an optional epilogue descriptor and turns it into the kernels' form
+int gemm_epilogue(const fpq_gemm_epilogue_t* ep, GemmEpi* epi) {
+  *epi = GemmEpi{};
+  epi->rows_per_gate = 1;
+  epi->sp_rpb = 1;
+  if (!ep) return FPQ_OK;
+  if (ep->gate && (ep->rows_per_gate < 1 || ep->rows_per_gate > 0x7FFFFFFF)) return FPQ_ERR_ARG;
+  if ((((uintptr_t)ep->gate | (uintptr_t)ep->residual) & 15) != 0) return FPQ_ERR_ARG;
+  epi->gate = (const _Float16*)ep->gate;
+  epi->resid = (const _Float16*)ep->residual;
+  if (ep->gate) epi->rows_per_gate = (int)ep->rows_per_gate;
+  return FPQ_OK;
+}
+
+// validates a split-output descriptor (include/fpq.h, fpq_gemm_split_t: the outputs leave in column parts, each to its own rows; no
+// gate / residual tail with it) and fills GemmEpi's sp_* fields.  whole_batches: tokens % rows_per_batch == 0 is required too -
+// the one rule on which the two families differ: the FP6 entry points ask for it, the FP4 ones never did.
+int gemm_split(const fpq_gemm_split_t* split, const fpq_gemm_epilogue_t* epilogue, int64_t tokens, int64_t outs, bool whole_batches,
+               GemmEpi* epi) {
+  if (epilogue || split->n_parts < 1 || split->n_parts > 3 || split->part_cols <= 0 || split->part_cols % 128 != 0 ||
+      outs != split->n_parts * split->part_cols || split->rows_per_batch < 1 || split->rows_per_batch > 0x7FFFFFFF ||
+      (whole_batches && tokens % split->rows_per_batch != 0))
+    return FPQ_ERR_ARG;
+  epi->sp_cols = (int)split->part_cols;
+  epi->sp_rpb = (int)split->rows_per_batch;
+  for (int p = 0; p < split->n_parts; ++p) {
+    if (!split->out[p] || ((uintptr_t)split->out[p] & 7) != 0 || split->row_stride[p] < split->part_cols || split->row_stride[p] % 4 != 0 ||
+        split->batch_stride[p] < 0 || split->row0[p] < 0)
+      return FPQ_ERR_ARG;
+    epi->sp_out[p] = (_Float16*)split->out[p];
+    epi->sp_stride[p] = split->row_stride[p];
+    epi->sp_bstride[p] = split->batch_stride[p];
+    epi->sp_row0[p] = split->row0[p];
+  }
+  return FPQ_OK;
+}
+
+// the q / k norm forms' own arguments (include/fpq.h, "THE Q / K L2 NORM"): parts q, k, v of heads of 64 columns; the fp32 bias is
+// read four outputs (16 bytes) at a time
+int gemm_qknorm(const fpq_gemm_split_t* split, const float* bias, const float* q_head_scale, GemmQkNorm* qkn) {
+  if (!split || split->n_parts != 3) return FPQ_ERR_ARG;
+  if (!q_head_scale || ((uintptr_t)q_head_scale & 3) != 0 || ((uintptr_t)bias & 15) != 0) return FPQ_ERR_ARG;
+  *qkn = GemmQkNorm{bias, q_head_scale};
+  return FPQ_OK;
+}
+
+// The tiling of the per-group LDS-DMA kernels (gemm_fp4_glds_kernel, its fc1 form, gemm_a6w4_kernel): 10 / 20 / 30 = 256 x 128,
+// 128 x 128, 64 x 128 tiles.
+// Default: 128 x 128 tiles (three workgroups per CU); 256 x 128 tiles (two per CU) from 4000 of them
+// on (round 4: 2 - 5 % faster at [65536 x 1920] x {1920, 5760, 7680} and from 16 900 tokens on for the wide Linears, 3 - 5 %
+// slower between 1000 and 4000 tiles) while two of them fit a CU's 160 KB of LDS (the scale tiles grow with K: from K = 3840 on
+// only one would, and the smaller tile is 15 % faster there - tools/gemm_k_sweep.py); 64 x 128 tiles while the 128 x 128 ones
+// would fill less than half of the chip's 768 slots (the first scale steps of a generation: 8.4 against 11.4 us at 100 tokens;
+// tools/gemm_small_steps.py).
+// FPQ_GEMM_CFG (experiments, tests) forces one of the tilings the caller has; have_256: whether it has the 256 x 128 one at all,
+// big_fits_twice: whether two of those tiles fit a CU's LDS at this K.
+int gemm_glds_tiling(int64_t tokens, int64_t outs, bool have_256, bool big_fits_twice) {
+  const int want = fpq_opt(OPT_FPQ_GEMM_CFG, 0);
+  if ((want == 10 && have_256) || want == 20 || want == 30) return want;
+  const int64_t big_tiles = ((tokens + 255) / 256) * ((outs + 127) / 128);
+  const int64_t mid_tiles = ((tokens + 127) / 128) * ((outs + 127) / 128);
+  return mid_tiles <= 384 ? 30 : (have_256 && big_tiles >= 4000 && big_fits_twice) ? 10 : 20;
+}
+
+// workgroups of a launch over BM x BN tiles: the column tiles rounded up to the 8 XCDs (the kernels' XCD-aware tile order), or
+// FPQ_ERR_SHAPE when a grid cannot hold them
+int64_t gemm_grid(int64_t tokens, int64_t outs, int BM, int BN) {
+  const int64_t n_col = (outs + BN - 1) / BN, n_row = (tokens + BM - 1) / BM;
+  const int64_t n_wg = 8 * ((n_col + 7) / 8) * n_row;
+  return n_wg > 0x7FFFFFFF ? (int64_t)FPQ_ERR_SHAPE : n_wg;
+}
+
+// the arguments every GEMM kernel takes, as the entry point received (and checked) them
+struct GemmCall {
+  const uint8_t* a_codes;
+  const void* a_scales;
+  const uint8_t* w_codes;
+  const void* w_scales;
+  const void* bias;
+  void* out;
+  int64_t tokens, outs, k;
+  GemmEpi epi;
+  hipStream_t st;
+};
+
+// THE launch: the grid for the kernel's tile, the scale pointers in the kernel's own types, the epilogue's extra argument if it
+// takes one (xe: GemmNoFc1 / GemmFc1 / GemmQkNorm / GemmSplit)
+template <typename Tsa, typename Tsw, typename... XE>
+int gemm_launch(void (*kernel)(const uint8_t*, const Tsa*, const uint8_t*, const Tsw*, const _Float16*, _Float16*, int, int, int, GemmEpi, XE...),
+                int BM, int BN, unsigned threads, size_t lds, const GemmCall& c, XE... xe) {
+  const int64_t n_wg = gemm_grid(c.tokens, c.outs, BM, BN);
+  if (n_wg < 0) return (int)n_wg;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_wg), dim3(threads), lds, c.st, c.a_codes, (const Tsa*)c.a_scales, c.w_codes,
+                     (const Tsw*)c.w_scales, (const _Float16*)c.bias, (_Float16*)c.out, (int)c.tokens, (int)c.outs, (int)c.k, c.epi, xe...);
+  return check_launch();
+}
+
+// a runtime fpq_dtype of scales (FPQ_F16 or FPQ_F32, checked by the caller) -> a value of that type, for a generic lambda to
+// take the type from
+template <typename F>
+int with_scale_type(int dtype, F&& f) {
+  return dtype == FPQ_F16 ? f(_Float16{}) : f(float{});
+}
+template <int N>
+struct Int { static constexpr int value = N; };
+
+constexpr int kTileDoesNotFit = 1;   // (not an FPQ_* code) the tiling's LDS image is too large at this K: the caller tries the next one
+
+// the FP4 LDS-DMA kernel with 32 MT x 128 tiles and epilogue XE; lds: GemmGldsCfg's figure for that epilogue
+template <int MT, typename XE>
+int launch_fp4_glds(const GemmCall& c, int w_scale_dtype, size_t lds, XE xe) {
+  if (lds > 160 * 1024) return kTileDoesNotFit;
+  return with_scale_type(w_scale_dtype, [&](auto tw) {
+    return gemm_launch(gemm_fp4_glds_kernel<decltype(tw), MT, 4, XE>, GemmGldsCfg<MT, 4>::BM, GemmGldsCfg<MT, 4>::BN, 256, lds, c, xe);
+  });
+}
+// the register-staged FP4 kernel
+template <int MT, int NT, int WR, int WC>
+int launch_fp4_staged(const GemmCall& c, int w_scale_dtype) {
+  using Cfg = GemmCfg<MT, NT, WR, WC>;
+  return with_scale_type(w_scale_dtype, [&](auto tw) {
+    return gemm_launch(gemm_fp4_kernel<decltype(tw), MT, NT, WR, WC>, Cfg::BM, Cfg::BN, Cfg::NTHR, Cfg::lds((int)(c.k / 128)), c);
+  });
+}
+// 6-bit activations x FP4 weights, 32 MT x 128 tiles; a_table: FPQ_E1M2 (as FP6 E2M3 codes, cbsz 2) or FPQ_E3M0 (BF6 E3M2, 3)
+template <int MT>
+int launch_a6w4(const GemmCall& c, int a_table, int w_scale_dtype) {
+  using Cfg = GemmA6W4Cfg<MT, 4>;
+  const size_t lds = Cfg::lds((int)(c.k / 128));
+  if (lds > 160 * 1024) return FPQ_ERR_SHAPE;
+  return with_scale_type(w_scale_dtype, [&](auto tw) {
+    if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_kernel<decltype(tw), MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c);
+    return gemm_launch(gemm_a6w4_kernel<decltype(tw), MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c);
+  });
+}
+// the row-scaled FP6 kernel for one epilogue and one format pair (FA, FB: cbsz of the activations, blgp of the weights; 2 = E2M3,
+// 3 = E3M2).  A pair with an E3M2 side is compiled for fp16 activation scales only - what the quantizers of activations produce;
+// all four dtype pairs for all four format pairs would double this unit's compile time (60 instantiations instead of 96) - and
+// gemm_fp6_rows_impl refuses the other combinations before it gets here.
+template <typename Tsa, typename Tsw, int MT, int FA, int FB, typename XE>
+int launch_fp6(const GemmCall& c, XE xe) {
+  using Cfg = GemmFp6Cfg<MT, 4>;
+  if constexpr (FA == 2 && FB == 2)
+    return gemm_launch(gemm_fp6_rows_kernel<Tsa, Tsw, MT, 4, XE>, Cfg::BM, Cfg::BN, 256, Cfg::lds(), c, xe);
+  else if constexpr (__is_same(Tsa, _Float16))
+    return gemm_launch(gemm_fp6_rows_bf6_kernel<Tsa, Tsw, MT, 4, XE, FA, FB>, Cfg::BM, Cfg::BN, 256, Cfg::lds(), c, xe);
+  else
+    return FPQ_ERR_DTYPE;
+}
+// ... from the runtime scale dtypes, operand formats (FPQ_E2M3 / FPQ_E3M2 per side) and epilogue of a call
+template <int MT>
+int dispatch_fp6(const GemmCall& c, int a_scale_dtype, int w_scale_dtype, int a_table, int w_table, bool split, const GemmQkNorm* qkn) {
+  return with_scale_type(a_scale_dtype, [&](auto ta) {
+    return with_scale_type(w_scale_dtype, [&](auto tw) {
+      auto formats = [&](auto fa, auto fb) {
+        using Ta = decltype(ta);
+        using Tw = decltype(tw);
+        constexpr int FA = decltype(fa)::value, FB = decltype(fb)::value;
+        if (qkn) return launch_fp6<Ta, Tw, MT, FA, FB>(c, *qkn);
+        if (split) return launch_fp6<Ta, Tw, MT, FA, FB>(c, GemmSplit{});
+        return launch_fp6<Ta, Tw, MT, FA, FB>(c, GemmNoFc1{});
+      };
+      if (a_table == FPQ_E3M2) return w_table == FPQ_E3M2 ? formats(Int<3>{}, Int<3>{}) : formats(Int<3>{}, Int<2>{});
+      return w_table == FPQ_E3M2 ? formats(Int<2>{}, Int<3>{}) : formats(Int<2>{}, Int<2>{});
+    });
+  });
+}
+template <int MT>
+int dispatch_fp8(const GemmCall& c, int a_scale_dtype, int w_scale_dtype) {
+  using Cfg = GemmFp8Cfg<MT, 4>;
+  return with_scale_type(a_scale_dtype, [&](auto ta) {
+    return with_scale_type(w_scale_dtype, [&](auto tw) {
+      return gemm_launch(gemm_fp8_rows_kernel<decltype(ta), decltype(tw), MT, 4>, Cfg::BM, Cfg::BN, 256, Cfg::lds(), c);
+    });
+  });
+}
 }  // namespace
 
 extern "C" {
@@ -164,28 +343,6 @@ int fpq_gate_residual(const void* y, const void* gate, const void* residual, voi
   return check_launch();
 }
 
-// validates an optional epilogue descriptor and turns it into the kernels' form
-static int gemm_epilogue(const fpq_gemm_epilogue_t* ep, int64_t tokens, GemmEpi* epi) {
-  epi->gate = nullptr;
-  epi->resid = nullptr;
-  epi->rows_per_gate = 1;
-  epi->km_w_rows = 0;
-  epi->sp_cols = 0;
-  epi->sp_rpb = 1;
-  for (int p = 0; p < 3; ++p) {
-    epi->sp_out[p] = nullptr;
-    epi->sp_stride[p] = epi->sp_bstride[p] = epi->sp_row0[p] = 0;
-  }
-  if (!ep) return FPQ_OK;
-  if (ep->gate && (ep->rows_per_gate < 1 || ep->rows_per_gate > 0x7FFFFFFF)) return FPQ_ERR_ARG;
-  if ((((uintptr_t)ep->gate | (uintptr_t)ep->residual) & 15) != 0) return FPQ_ERR_ARG;
-  epi->gate = (const _Float16*)ep->gate;
-  epi->resid = (const _Float16*)ep->residual;
-  if (ep->gate) epi->rows_per_gate = (int)ep->rows_per_gate;
-  (void)tokens;
-  return FPQ_OK;
-}
-
 // km: both operands are k-major images (include/fpq.h); only the LDS-DMA kernels read them
 static int gemm_fp4_mx_impl(const uint8_t* a_codes, const void* a_scales, const uint8_t* w_codes, const void* w_scales,
                             int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
@@ -193,23 +350,12 @@ static int gemm_fp4_mx_impl(const uint8_t* a_codes, const void* a_scales, const 
                             const GemmQkNorm* qkn = nullptr) {
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   GemmEpi epi;
-  if (int rc = gemm_epilogue(epilogue, tokens, &epi)) return rc;
-  if (split) {   // the outputs leave in column parts, each to its own rows (include/fpq.h): the LDS-DMA kernels' plain epilogue only
-    if (epilogue || split->n_parts < 1 || split->n_parts > 3 || split->part_cols <= 0 || split->part_cols % 128 != 0 ||
-        outs != split->n_parts * split->part_cols || split->rows_per_batch < 1 || split->rows_per_batch > 0x7FFFFFFF)
-      return FPQ_ERR_ARG;
-    epi.sp_cols = (int)split->part_cols;
-    epi.sp_rpb = (int)split->rows_per_batch;
-    for (int p = 0; p < split->n_parts; ++p) {
-      if (!split->out[p] || ((uintptr_t)split->out[p] & 7) != 0 || split->row_stride[p] < split->part_cols || split->row_stride[p] % 4 != 0 ||
-          split->batch_stride[p] < 0 || split->row0[p] < 0)
-        return FPQ_ERR_ARG;
-      epi.sp_out[p] = (_Float16*)split->out[p];
-      epi.sp_stride[p] = split->row_stride[p];
-      epi.sp_bstride[p] = split->batch_stride[p];
-      epi.sp_row0[p] = split->row0[p];
-    }
-    if (!out) out = split->out[0];   // (never written: every tile belongs to a part)
+  if (int rc = gemm_epilogue(epilogue, &epi)) return rc;
+  if (split) {   // the LDS-DMA kernels' plain epilogue only
+    if (int rc = gemm_split(split, epilogue, tokens, outs, false, &epi)) return rc;
+    // (never written through: every tile belongs to a part.)  Part 0 thereby meets the 16-byte test of `out` below, which is
+    // stricter than the header's 8 bytes; the FP6 family exempts it.
+    if (!out) out = split->out[0];
   }
   if (km) {   // scales come as fp32 k-major images too (include/fpq.h); their lane offsets are 32-bit: 3 planes of rows * 4 bytes
     if (w_scale_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
@@ -223,75 +369,32 @@ static int gemm_fp4_mx_impl(const uint8_t* a_codes, const void* a_scales, const 
   if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
   if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out) & 15) != 0) return FPQ_ERR_ARG;
   const int G = (int)(k / 128);
-  hipStream_t st = (hipStream_t)stream;
-  // Default: the LDS-DMA kernel with 128 x 128 tiles (three workgroups per CU); 256 x 128 tiles (two per CU) from 4000 of them
-  // on (round 4: 2 - 5 % faster at [65536 x 1920] x {1920, 5760, 7680} and from 16 900 tokens on for the wide Linears, 3 - 5 %
-  // slower between 1000 and 4000 tiles) while two of them fit a CU's 160 KB of LDS (the scale tiles grow with K: from K = 3840 on
-  // only one would, and the smaller tile is 15 % faster there - tools/gemm_k_sweep.py); 64 x 128 tiles while the 128 x 128 ones
-  // would fill less than half of the chip's 768 slots (the first scale steps of a generation: 8.4 against 11.4 us at 100 tokens;
-  // tools/gemm_small_steps.py); the register-staged kernel when the LDS image does not fit (very long K).
-  // FPQ_GEMM_CFG (experiments, tests): 0..2 register-staged tilings, 10 / 20 / 30 LDS-DMA tilings (256x128, 128x128, 64x128).
-    const int64_t big_tiles = ((tokens + 255) / 256) * ((outs + 127) / 128);
-  const int64_t mid_tiles = ((tokens + 127) / 128) * ((outs + 127) / 128);
-  const bool big_fits_twice = 2 * GemmGldsCfg<8, 4>::lds(G) <= 160 * 1024;
-  // (the LDS-DMA kernel reads the bias four outputs at a time: a bias that is not 8-byte aligned goes to the other kernel)
-  int cfg = ((uintptr_t)bias & 7) != 0 ? 0 : fpq_opt_set(OPT_FPQ_GEMM_CFG) ? fpq_opt(OPT_FPQ_GEMM_CFG, 0) : mid_tiles <= 384 ? 30 : (big_tiles >= 4000 && big_fits_twice) ? 10 : 20;
+  // The LDS-DMA kernel in the tiling gemm_glds_tiling chooses; the register-staged kernel when the LDS image does not fit (very
+  // long K), when the bias is not 8-byte aligned (the LDS-DMA kernel reads it four outputs at a time), or when FPQ_GEMM_CFG
+  // names one of its tilings (0..2; experiments, tests) - but it reads row-major codes and writes one tensor.
+  int cfg = gemm_glds_tiling(tokens, outs, true, 2 * GemmGldsCfg<8, 4>::lds(G) <= 160 * 1024);
   if (km || split) {
     if (((uintptr_t)bias & 7) != 0 || outs + 63 > 0x7FFFFFFF) return FPQ_ERR_ARG;
-    if (cfg != 10 && cfg != 20 && cfg != 30) cfg = mid_tiles <= 384 ? 30 : (big_tiles >= 4000 && big_fits_twice) ? 10 : 20;
+  } else if (((uintptr_t)bias & 7) != 0) {
+    cfg = 0;
+  } else if (fpq_opt_set(OPT_FPQ_GEMM_CFG)) {
+    cfg = fpq_opt(OPT_FPQ_GEMM_CFG, 0);
   }
-#define FPQ_GEMM_LAUNCH(MT, NT, WR, WC)                                                                              \
-  do {                                                                                                               \
-    using Cfg = GemmCfg<MT, NT, WR, WC>;                                                                             \
-    const int64_t n_col = (outs + Cfg::BN - 1) / Cfg::BN, n_row = (tokens + Cfg::BM - 1) / Cfg::BM;                  \
-    const int64_t n_wg = 8 * ((n_col + 7) / 8) * n_row;                                                              \
-    if (n_wg > 0x7FFFFFFF) return FPQ_ERR_SHAPE;                                                                     \
-    if (w_scale_dtype == FPQ_F16)                                                                                    \
-      hipLaunchKernelGGL((gemm_fp4_kernel<_Float16, MT, NT, WR, WC>), dim3((unsigned)n_wg), dim3(Cfg::NTHR),        \
-                         Cfg::lds(G), st, a_codes, (const _Float16*)a_scales, w_codes, (const _Float16*)w_scales,   \
-                         (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi);                     \
-    else                                                                                                             \
-      hipLaunchKernelGGL((gemm_fp4_kernel<float, MT, NT, WR, WC>), dim3((unsigned)n_wg), dim3(Cfg::NTHR),           \
-                         Cfg::lds(G), st, a_codes, (const _Float16*)a_scales, w_codes, (const float*)w_scales,      \
-                         (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi);                     \
-  } while (0)
-#define FPQ_GEMM_GLDS(MT, NT)                                                                                        \
-  do {                                                                                                               \
-    using Cfg = GemmGldsCfg<MT, NT>;                                                                                 \
-    const size_t lds = Cfg::lds(G);                                                                                  \
-    if (lds <= 160 * 1024) {                                                                                         \
-      const int64_t n_col = (outs + Cfg::BN - 1) / Cfg::BN, n_row = (tokens + Cfg::BM - 1) / Cfg::BM;                \
-      const int64_t n_wg = 8 * ((n_col + 7) / 8) * n_row;                                                            \
-      if (n_wg > 0x7FFFFFFF) return FPQ_ERR_SHAPE;                                                                   \
-      if (qkn && w_scale_dtype == FPQ_F16)                                                                           \
-        hipLaunchKernelGGL((gemm_fp4_glds_kernel<_Float16, MT, NT, GemmQkNorm>), dim3((unsigned)n_wg), dim3(256), lds, st, \
-                           a_codes, (const _Float16*)a_scales, w_codes, (const _Float16*)w_scales,                   \
-                           (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, *qkn);        \
-      else if (qkn)                                                                                                  \
-        hipLaunchKernelGGL((gemm_fp4_glds_kernel<float, MT, NT, GemmQkNorm>), dim3((unsigned)n_wg), dim3(256), lds, st, \
-                           a_codes, (const _Float16*)a_scales, w_codes, (const float*)w_scales,                      \
-                           (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, *qkn);        \
-      else if (w_scale_dtype == FPQ_F16)                                                                             \
-        hipLaunchKernelGGL((gemm_fp4_glds_kernel<_Float16, MT, NT>), dim3((unsigned)n_wg), dim3(256), lds, st,      \
-                           a_codes, (const _Float16*)a_scales, w_codes, (const _Float16*)w_scales,                   \
-                           (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, GemmNoFc1{});      \
-      else                                                                                                           \
-        hipLaunchKernelGGL((gemm_fp4_glds_kernel<float, MT, NT>), dim3((unsigned)n_wg), dim3(256), lds, st,         \
-                           a_codes, (const _Float16*)a_scales, w_codes, (const float*)w_scales,                      \
-                           (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, GemmNoFc1{});      \
-      return check_launch();                                                                                         \
-    }                                                                                                                \
-  } while (0)
-  if (cfg == 30) FPQ_GEMM_GLDS(2, 4);   // 64 x 128 tiles
-  if (cfg == 10) FPQ_GEMM_GLDS(8, 4);
-  if (cfg == 10 || cfg == 20 || cfg == 30) FPQ_GEMM_GLDS(4, 4);   // (the larger tile's LDS image may not fit where the smaller one's does)
-#undef FPQ_GEMM_GLDS
-  if (km || split) return FPQ_ERR_SHAPE;   // K too long for the LDS-DMA kernel's scale tiles: the register-staged kernels read row-major codes, write one tensor
-  if (cfg == 1) FPQ_GEMM_LAUNCH(2, 4, 4, 2);
-  else if (cfg == 2) FPQ_GEMM_LAUNCH(4, 4, 2, 4);
-  else FPQ_GEMM_LAUNCH(4, 4, 2, 2);
-#undef FPQ_GEMM_LAUNCH
-  return check_launch();
+  const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
+  auto glds = [&](auto mt) {
+    constexpr int MT = decltype(mt)::value;
+    const size_t lds = GemmGldsCfg<MT, 4>::lds(G);
+    return qkn ? launch_fp4_glds<MT>(c, w_scale_dtype, lds, *qkn) : launch_fp4_glds<MT>(c, w_scale_dtype, lds, GemmNoFc1{});
+  };
+  int rc = kTileDoesNotFit;
+  if (cfg == 30) rc = glds(Int<2>{});   // 64 x 128 tiles
+  if (cfg == 10) rc = glds(Int<8>{});
+  if (rc == kTileDoesNotFit && (cfg == 10 || cfg == 20 || cfg == 30)) rc = glds(Int<4>{});   // (the larger tile's LDS image may not fit where the smaller one's does)
+  if (rc != kTileDoesNotFit) return rc;
+  if (km || split) return FPQ_ERR_SHAPE;   // K too long for the LDS-DMA kernel's scale tiles
+  if (cfg == 1) return launch_fp4_staged<2, 4, 4, 2>(c, w_scale_dtype);
+  if (cfg == 2) return launch_fp4_staged<4, 4, 2, 4>(c, w_scale_dtype);
+  return launch_fp4_staged<4, 4, 2, 2>(c, w_scale_dtype);
 }
 
 int fpq_gemm_fp4_mx_ex(const uint8_t* a_codes, const void* a_scales, const uint8_t* w_codes, const void* w_scales,
@@ -308,10 +411,8 @@ int fpq_gemm_fp4_mx_split(const uint8_t* a_codes, const void* a_scales, const ui
 int fpq_gemm_fp4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, const uint8_t* w_codes, const void* w_scales,
                                  int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
                                  const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream) {
-  // parts q, k, v of heads of 64 columns; the fp32 bias is read four outputs (16 bytes) at a time
-  if (!split || split->n_parts != 3 || split->part_cols <= 0 || split->part_cols % 128 != 0) return FPQ_ERR_ARG;
-  if (!q_head_scale || ((uintptr_t)q_head_scale & 3) != 0 || ((uintptr_t)bias & 15) != 0) return FPQ_ERR_ARG;
-  const GemmQkNorm qkn{bias, q_head_scale};
+  GemmQkNorm qkn;
+  if (int rc = gemm_qknorm(split, bias, q_head_scale, &qkn)) return rc;
   return gemm_fp4_mx_impl(a_codes, a_scales, w_codes, w_scales, w_scale_dtype, nullptr, nullptr, tokens, outs, k, nullptr, kmajor != 0, stream,
                           split, &qkn);
 }
@@ -331,7 +432,7 @@ int fpq_gemm_a6w4_mx(const uint8_t* a_codes, const void* a_scales, int a_table, 
   if (a_table != FPQ_E1M2 && a_table != FPQ_E3M0) return FPQ_ERR_TABLE;
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   GemmEpi epi;
-  if (int rc = gemm_epilogue(epilogue, tokens, &epi)) return rc;
+  if (int rc = gemm_epilogue(epilogue, &epi)) return rc;
   if (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
   if (k % 128 != 0 || k > 128 * 64 || outs % 8 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
   if (tokens == 0 || outs == 0) return FPQ_OK;
@@ -339,33 +440,9 @@ int fpq_gemm_a6w4_mx(const uint8_t* a_codes, const void* a_scales, int a_table, 
   if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out) & 15) != 0 || ((uintptr_t)bias & 7) != 0 || ((uintptr_t)a_scales & 1) != 0 ||
       ((uintptr_t)w_scales & (w_scale_dtype == FPQ_F16 ? 1 : 3)) != 0)
     return FPQ_ERR_ARG;
-  const int G = (int)(k / 128);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t mid_tiles = ((tokens + 127) / 128) * ((outs + 127) / 128);
-  const int want = fpq_opt(OPT_FPQ_GEMM_CFG, 0);
-  const int cfg = (want == 20 || want == 30) ? want : mid_tiles <= 384 ? 30 : 20;
-#define FPQ_A6W4_GO(TW, MT, FA)                                                                                      \
-  hipLaunchKernelGGL((gemm_a6w4_kernel<TW, MT, 4, FA>), dim3((unsigned)n_wg), dim3(256), lds, st, a_codes,            \
-                     (const _Float16*)a_scales, w_codes, (const TW*)w_scales, (const _Float16*)bias, (_Float16*)out,  \
-                     (int)tokens, (int)outs, (int)k, epi)
-#define FPQ_A6W4_TILE(MT)                                                                                            \
-  do {                                                                                                               \
-    using Cfg = GemmA6W4Cfg<MT, 4>;                                                                                  \
-    const size_t lds = Cfg::lds(G);                                                                                  \
-    if (lds > 160 * 1024) return FPQ_ERR_SHAPE;                                                                      \
-    const int64_t n_col = (outs + Cfg::BN - 1) / Cfg::BN, n_row = (tokens + Cfg::BM - 1) / Cfg::BM;                  \
-    const int64_t n_wg = 8 * ((n_col + 7) / 8) * n_row;                                                              \
-    if (n_wg > 0x7FFFFFFF) return FPQ_ERR_SHAPE;                                                                     \
-    if (a_table == FPQ_E1M2 && w_scale_dtype == FPQ_F16) FPQ_A6W4_GO(_Float16, MT, 2);                               \
-    else if (a_table == FPQ_E1M2) FPQ_A6W4_GO(float, MT, 2);                                                         \
-    else if (w_scale_dtype == FPQ_F16) FPQ_A6W4_GO(_Float16, MT, 3);                                                 \
-    else FPQ_A6W4_GO(float, MT, 3);                                                                                  \
-  } while (0)
-  if (cfg == 30) FPQ_A6W4_TILE(2);
-  else FPQ_A6W4_TILE(4);
-#undef FPQ_A6W4_TILE
-#undef FPQ_A6W4_GO
-  return check_launch();
+  const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
+  if (gemm_glds_tiling(tokens, outs, false, false) == 30) return launch_a6w4<2>(c, a_table, w_scale_dtype);
+  return launch_a6w4<4>(c, a_table, w_scale_dtype);
 }
 
 #ifdef FPQ_GEMM6_STAMPS
@@ -397,39 +474,21 @@ static int gemm_fp4_gelu_dual_impl(const uint8_t* a_codes, const void* a_scales,
   xe.h_out = (_Float16*)gelu_out;
   xe.nan_flag = (uint32_t*)nan_flag;
   const int G = (int)(k / 128);
-  hipStream_t st = (hipStream_t)stream;
   GemmEpi epi{nullptr, nullptr, 1, km ? (int)outs : 0};   // (outs % 128 == 0: the weight image has exactly outs rows)
   if (km && (w_scale_dtype != FPQ_F32 || tokens >= (1ll << 28) || (((uintptr_t)a_scales | (uintptr_t)w_scales) & 15) != 0)) return FPQ_ERR_ARG;
-  // tile choice as fpq_gemm_fp4_mx_ex (FPQ_GEMM_CFG 10 / 20 / 30 forces one of the three LDS-DMA tilings)
-  const int64_t big_tiles = ((tokens + 255) / 256) * (outs / 128), mid_tiles = ((tokens + 127) / 128) * (outs / 128);
-  const bool big_fits_twice = 2 * GemmGldsCfg<8, 4>::lds_fc1(G, xe.a.shift) <= 160 * 1024;
-  const int want = fpq_opt(OPT_FPQ_GEMM_CFG, 0);
-  const int cfg = (want == 10 || want == 20 || want == 30) ? want : mid_tiles <= 384 ? 30 : (big_tiles >= 4000 && big_fits_twice) ? 10 : 20;
-#define FPQ_GEMM_FC1(MT, NT)                                                                                         \
-  do {                                                                                                               \
-    using Cfg = GemmGldsCfg<MT, NT>;                                                                                 \
-    const size_t lds = Cfg::lds_fc1(G, xe.a.shift);                                                                  \
-    if (lds <= 160 * 1024) {                                                                                         \
-      const int64_t n_col = outs / Cfg::BN, n_row = (tokens + Cfg::BM - 1) / Cfg::BM;                                \
-      const int64_t n_wg = 8 * ((n_col + 7) / 8) * n_row;                                                            \
-      if (n_wg > 0x7FFFFFFF) return FPQ_ERR_SHAPE;                                                                   \
-      if (w_scale_dtype == FPQ_F16)                                                                                  \
-        hipLaunchKernelGGL((gemm_fp4_glds_kernel<_Float16, MT, NT, GemmFc1>), dim3((unsigned)n_wg), dim3(256), lds, st, \
-                           a_codes, (const _Float16*)a_scales, w_codes, (const _Float16*)w_scales,                   \
-                           (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, xe);          \
-      else                                                                                                           \
-        hipLaunchKernelGGL((gemm_fp4_glds_kernel<float, MT, NT, GemmFc1>), dim3((unsigned)n_wg), dim3(256), lds, st, \
-                           a_codes, (const _Float16*)a_scales, w_codes, (const float*)w_scales,                      \
-                           (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, xe);          \
-      if (int rc = check_launch()) return rc;                                                                        \
-      return nan_flag ? fpq_internal_zero_if_flag(out, tokens * outs * 2, nan_flag, stream) : FPQ_OK;                \
-    }                                                                                                                \
-  } while (0)
-  if (cfg == 30) FPQ_GEMM_FC1(2, 4);
-  if (cfg == 10) FPQ_GEMM_FC1(8, 4);
-  FPQ_GEMM_FC1(4, 4);
-#undef FPQ_GEMM_FC1
-  return FPQ_ERR_SHAPE;   // K too long for the LDS-DMA kernel's scale tiles
+  const int cfg = gemm_glds_tiling(tokens, outs, true, 2 * GemmGldsCfg<8, 4>::lds_fc1(G, xe.a.shift) <= 160 * 1024);
+  const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
+  auto glds = [&](auto mt) {
+    constexpr int MT = decltype(mt)::value;
+    return launch_fp4_glds<MT>(c, w_scale_dtype, GemmGldsCfg<MT, 4>::lds_fc1(G, xe.a.shift), xe);
+  };
+  int rc = kTileDoesNotFit;
+  if (cfg == 30) rc = glds(Int<2>{});
+  if (cfg == 10) rc = glds(Int<8>{});
+  if (rc == kTileDoesNotFit) rc = glds(Int<4>{});
+  if (rc == kTileDoesNotFit) return FPQ_ERR_SHAPE;   // K too long for the LDS-DMA kernel's scale tiles
+  if (rc) return rc;
+  return nan_flag ? fpq_internal_zero_if_flag(out, tokens * outs * 2, nan_flag, stream) : FPQ_OK;
 }
 int fpq_gemm_fp4_gelu_dual(const uint8_t* a_codes, const void* a_scales, const uint8_t* w_codes, const void* w_scales,
                            int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs,
@@ -447,27 +506,12 @@ static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int 
                               int64_t outs, int64_t k, const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream,
                               const fpq_gemm_split_t* split = nullptr, const GemmQkNorm* qkn = nullptr,
                               int a_table = FPQ_E2M3, int w_table = FPQ_E2M3) {
-  // a_table / w_table: FPQ_E2M3 or FPQ_E3M2 (checked by the fpq_gemm_f6_* entry points) -> the MFMA's format selectors
-  const int fsel = (a_table == FPQ_E3M2 ? 2 : 0) | (w_table == FPQ_E3M2 ? 1 : 0);
+  // a_table / w_table: FPQ_E2M3 or FPQ_E3M2 (checked by the fpq_gemm_f6_* entry points)
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   GemmEpi epi;
-  if (int rc = gemm_epilogue(epilogue, tokens, &epi)) return rc;
-  if (split) {   // the outputs leave in column parts, each to its own rows (include/fpq.h); every part is held to the header's 8-byte alignment
-    if (epilogue || split->n_parts < 1 || split->n_parts > 3 || split->part_cols <= 0 || split->part_cols % 128 != 0 ||
-        outs != split->n_parts * split->part_cols || split->rows_per_batch < 1 || split->rows_per_batch > 0x7FFFFFFF ||
-        tokens % split->rows_per_batch != 0)
-      return FPQ_ERR_ARG;
-    epi.sp_cols = (int)split->part_cols;
-    epi.sp_rpb = (int)split->rows_per_batch;
-    for (int p = 0; p < split->n_parts; ++p) {
-      if (!split->out[p] || ((uintptr_t)split->out[p] & 7) != 0 || split->row_stride[p] < split->part_cols || split->row_stride[p] % 4 != 0 ||
-          split->batch_stride[p] < 0 || split->row0[p] < 0)
-        return FPQ_ERR_ARG;
-      epi.sp_out[p] = (_Float16*)split->out[p];
-      epi.sp_stride[p] = split->row_stride[p];
-      epi.sp_bstride[p] = split->batch_stride[p];
-      epi.sp_row0[p] = split->row0[p];
-    }
+  if (int rc = gemm_epilogue(epilogue, &epi)) return rc;
+  if (split) {   // every part is held to the header's 8-byte alignment; whole batch entries only (the FP4 family does not ask for that)
+    if (int rc = gemm_split(split, epilogue, tokens, outs, true, &epi)) return rc;
     out = split->out[0];   // (not written through: every tile belongs to a part)
   }
   if (km) {
@@ -477,71 +521,20 @@ static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int 
   if (k % 128 != 0 || outs % 8 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF || k > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
   if ((a_scale_dtype != FPQ_F16 && a_scale_dtype != FPQ_F32) || (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32))
     return FPQ_ERR_DTYPE;
-  // a pair with an E3M2 side is compiled for the scale dtypes the quantizers of activations produce: fp16 activation scales
-  // (fp16 or fp32 weight scales) - all four dtype pairs for all four format pairs would double this unit's compile time
-  if (fsel != 0 && a_scale_dtype != FPQ_F16) return FPQ_ERR_DTYPE;
+  // a pair with an E3M2 side exists for fp16 activation scales only (fp16 or fp32 weight scales; launch_fp6)
+  if ((a_table == FPQ_E3M2 || w_table == FPQ_E3M2) && a_scale_dtype != FPQ_F16) return FPQ_ERR_DTYPE;
   if (tokens == 0 || outs == 0) return FPQ_OK;
   if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
   if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (split ? 0 : (uintptr_t)out)) & 15) != 0) return FPQ_ERR_ARG;
   // the LDS-DMA pieces address a tile by a 32-bit lane offset (row inside the tile x row bytes + chunk): the 256-row tile's
   // last row must stay below 2^32 (k above ~22 M would wrap and read wrong rows silently)
   if (255 * (k * 3 / 4) + 128 >= (1ll << 32)) return FPQ_ERR_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
   // FPQ_GEMM6_CFG 0: 128 x 128 tiles, 1: 256 x 128 (default for tall problems)
   // 256 x 128 tiles from 4096 tokens on for the wide Linears, from 32768 on for outs < 4096 (tools/gemm_small_steps.py fp6)
   const int cfg6 = fpq_opt_set(OPT_FPQ_GEMM6_CFG) ? fpq_opt(OPT_FPQ_GEMM6_CFG, 0) : (tokens >= 4096 && (outs >= 4096 || tokens >= 32768) ? 1 : 0);
-#define FPQ_GO6ARGS(TA, TW, xe)                                                                                     \
-  dim3((unsigned)n_wg), dim3(256), Cfg::lds(), st, a_codes, (const TA*)a_scales, w_codes, (const TW*)w_scales,       \
-      (const _Float16*)bias, (_Float16*)out, (int)tokens, (int)outs, (int)k, epi, xe
-#define FPQ_GO6X(TA, TW, MT, NT, XE, xe) hipLaunchKernelGGL((gemm_fp6_rows_kernel<TA, TW, MT, NT, XE>), FPQ_GO6ARGS(TA, TW, xe))
-#define FPQ_GO6B(TA, TW, MT, NT, XE, xe, FA, FB)                                                                    \
-  hipLaunchKernelGGL((gemm_fp6_rows_bf6_kernel<TA, TW, MT, NT, XE, FA, FB>), FPQ_GO6ARGS(TA, TW, xe))
-#define FPQ_GO6P(TA, TW, MT, NT)                                                                                    \
-  do {                                                                                                               \
-    if (qkn) FPQ_GO6X(TA, TW, MT, NT, GemmQkNorm, *qkn);                                                             \
-    else if (split) FPQ_GO6X(TA, TW, MT, NT, GemmSplit, GemmSplit{});                                                \
-    else FPQ_GO6X(TA, TW, MT, NT, GemmNoFc1, GemmNoFc1{});                                                           \
-  } while (0)
-#define FPQ_GO6E(TA, TW, MT, NT, FA, FB)                                                                            \
-  do {                                                                                                               \
-    if (qkn) FPQ_GO6B(TA, TW, MT, NT, GemmQkNorm, *qkn, FA, FB);                                                     \
-    else if (split) FPQ_GO6B(TA, TW, MT, NT, GemmSplit, GemmSplit{}, FA, FB);                                        \
-    else FPQ_GO6B(TA, TW, MT, NT, GemmNoFc1, GemmNoFc1{}, FA, FB);                                                   \
-  } while (0)
-#define FPQ_GO6(TA, TW, MT, NT, MORE)                                                                               \
-  do {                                                                                                               \
-    using Cfg = GemmFp6Cfg<MT, NT>;                                                                                  \
-    const int64_t n_col = (outs + Cfg::BN - 1) / Cfg::BN, n_row = (tokens + Cfg::BM - 1) / Cfg::BM;                  \
-    const int64_t n_wg = 8 * ((n_col + 7) / 8) * n_row;                                                              \
-    if (n_wg > 0x7FFFFFFF) return FPQ_ERR_SHAPE;                                                                     \
-    if (fsel == 0) FPQ_GO6P(TA, TW, MT, NT);   /* E2M3 x E2M3; below: activations (A, cbsz) x weights (B, blgp) */  \
-    MORE(TA, TW, MT, NT);                                                                                            \
-  } while (0)
-#define FPQ_GO6_NONE(TA, TW, MT, NT)
-#define FPQ_GO6_BF6(TA, TW, MT, NT)                                                                                 \
-  else if (fsel == 2) FPQ_GO6E(TA, TW, MT, NT, 3, 2);                                                                \
-  else if (fsel == 1) FPQ_GO6E(TA, TW, MT, NT, 2, 3);                                                                \
-  else FPQ_GO6E(TA, TW, MT, NT, 3, 3)
-  // (the pairs with a BF6 side exist for fp16 activation scales only - checked above: 60 instantiations instead of 96)
-#define FPQ_GO6T(MT, NT)                                                                                             \
-  do {                                                                                                               \
-    if (a_scale_dtype == FPQ_F16 && w_scale_dtype == FPQ_F16) FPQ_GO6(_Float16, _Float16, MT, NT, FPQ_GO6_BF6);      \
-    else if (a_scale_dtype == FPQ_F16) FPQ_GO6(_Float16, float, MT, NT, FPQ_GO6_BF6);                                \
-    else if (w_scale_dtype == FPQ_F16) FPQ_GO6(float, _Float16, MT, NT, FPQ_GO6_NONE);                               \
-    else FPQ_GO6(float, float, MT, NT, FPQ_GO6_NONE);                                                                \
-  } while (0)
-  if (cfg6 == 1) FPQ_GO6T(8, 4);
-  else FPQ_GO6T(4, 4);
-#undef FPQ_GO6T
-#undef FPQ_GO6_BF6
-#undef FPQ_GO6_NONE
-#undef FPQ_GO6
-#undef FPQ_GO6E
-#undef FPQ_GO6P
-#undef FPQ_GO6B
-#undef FPQ_GO6X
-#undef FPQ_GO6ARGS
-  return check_launch();
+  const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
+  if (cfg6 == 1) return dispatch_fp6<8>(c, a_scale_dtype, w_scale_dtype, a_table, w_table, split != nullptr, qkn);
+  return dispatch_fp6<4>(c, a_scale_dtype, w_scale_dtype, a_table, w_table, split != nullptr, qkn);
 }
 int fpq_gemm_fp6_rows_ex(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,
                          const void* w_scales, int w_scale_dtype, const void* bias, void* out, int64_t tokens,
@@ -564,10 +557,8 @@ int fpq_gemm_fp6_rows_split(const uint8_t* a_codes, const void* a_scales, int a_
 int fpq_gemm_fp6_rows_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,
                                    const void* w_scales, int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
                                    const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream) {
-  // parts q, k, v of heads of 64 columns; the fp32 bias is read four outputs (16 bytes) at a time
-  if (!split || split->n_parts != 3) return FPQ_ERR_ARG;
-  if (!q_head_scale || ((uintptr_t)q_head_scale & 3) != 0 || ((uintptr_t)bias & 15) != 0) return FPQ_ERR_ARG;
-  const GemmQkNorm qkn{bias, q_head_scale};
+  GemmQkNorm qkn;
+  if (int rc = gemm_qknorm(split, bias, q_head_scale, &qkn)) return rc;
   return gemm_fp6_rows_impl(a_codes, a_scales, a_scale_dtype, w_codes, w_scales, w_scale_dtype, nullptr, nullptr, tokens, outs, k, nullptr,
                             kmajor != 0, stream, split, &qkn);
 }
@@ -594,9 +585,8 @@ int fpq_gemm_f6_rows_split_qknorm(const uint8_t* a_codes, const void* a_scales, 
                                   const void* w_scales, int w_scale_dtype, int w_table, const float* bias, int64_t tokens, int64_t outs,
                                   int64_t k, const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream) {
   if (!f6_table(a_table) || !f6_table(w_table)) return FPQ_ERR_TABLE;
-  if (!split || split->n_parts != 3) return FPQ_ERR_ARG;
-  if (!q_head_scale || ((uintptr_t)q_head_scale & 3) != 0 || ((uintptr_t)bias & 15) != 0) return FPQ_ERR_ARG;
-  const GemmQkNorm qkn{bias, q_head_scale};
+  GemmQkNorm qkn;
+  if (int rc = gemm_qknorm(split, bias, q_head_scale, &qkn)) return rc;
   return gemm_fp6_rows_impl(a_codes, a_scales, a_scale_dtype, w_codes, w_scales, w_scale_dtype, nullptr, nullptr, tokens, outs, k, nullptr,
                             kmajor != 0, stream, split, &qkn, a_table, w_table);
 }
@@ -654,7 +644,7 @@ int fpq_gemm_fp8_rows_ex(const uint8_t* a_codes, const void* a_scales, int a_sca
                          int64_t outs, int64_t k, const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream) {
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   GemmEpi epi;
-  if (int rc = gemm_epilogue(epilogue, tokens, &epi)) return rc;
+  if (int rc = gemm_epilogue(epilogue, &epi)) return rc;
   if (k % 128 != 0 || outs % 8 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF || k > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
   if ((a_scale_dtype != FPQ_F16 && a_scale_dtype != FPQ_F32) || (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32))
     return FPQ_ERR_DTYPE;
@@ -662,30 +652,9 @@ int fpq_gemm_fp8_rows_ex(const uint8_t* a_codes, const void* a_scales, int a_sca
   if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
   if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out) & 15) != 0) return FPQ_ERR_ARG;
   if (255 * k + 128 >= (1ll << 32)) return FPQ_ERR_SHAPE;   // 32-bit lane offsets inside a tile, as in fpq_gemm_fp6_rows_ex
-  hipStream_t st = (hipStream_t)stream;
-  const int cfg8 = fpq_opt(OPT_FPQ_GEMM8_CFG, 0);
-#define FPQ_GO8(TA, TW, MT, NT)                                                                                     \
-  do {                                                                                                               \
-    using Cfg = GemmFp8Cfg<MT, NT>;                                                                                  \
-    const int64_t n_col = (outs + Cfg::BN - 1) / Cfg::BN, n_row = (tokens + Cfg::BM - 1) / Cfg::BM;                  \
-    const int64_t n_wg = 8 * ((n_col + 7) / 8) * n_row;                                                              \
-    if (n_wg > 0x7FFFFFFF) return FPQ_ERR_SHAPE;                                                                     \
-    hipLaunchKernelGGL((gemm_fp8_rows_kernel<TA, TW, MT, NT>), dim3((unsigned)n_wg), dim3(256), Cfg::lds(), st,     \
-                       a_codes, (const TA*)a_scales, w_codes, (const TW*)w_scales, (const _Float16*)bias,            \
-                       (_Float16*)out, (int)tokens, (int)outs, (int)k, epi);                                              \
-  } while (0)
-#define FPQ_GO8T(MT, NT)                                                                                             \
-  do {                                                                                                               \
-    if (a_scale_dtype == FPQ_F16 && w_scale_dtype == FPQ_F16) FPQ_GO8(_Float16, _Float16, MT, NT);                   \
-    else if (a_scale_dtype == FPQ_F16) FPQ_GO8(_Float16, float, MT, NT);                                             \
-    else if (w_scale_dtype == FPQ_F16) FPQ_GO8(float, _Float16, MT, NT);                                             \
-    else FPQ_GO8(float, float, MT, NT);                                                                              \
-  } while (0)
-  if (cfg8 == 1) FPQ_GO8T(8, 4);
-  else FPQ_GO8T(4, 4);
-#undef FPQ_GO8T
-#undef FPQ_GO8
-  return check_launch();
+  const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
+  if (fpq_opt(OPT_FPQ_GEMM8_CFG, 0) == 1) return dispatch_fp8<8>(c, a_scale_dtype, w_scale_dtype);
+  return dispatch_fp8<4>(c, a_scale_dtype, w_scale_dtype);
 }
 
 }  // extern "C"

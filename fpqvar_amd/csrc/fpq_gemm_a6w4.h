@@ -175,14 +175,7 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void gemm_a6w4_kernel(const uint8_
   v4f_t b4 = v4f_t{0, 0, 0, 0};
 #pragma unroll
   for (int n = 0; n < NT; ++n) b4[n] = (float)bias_h[n];
-  const bool gate_far = epi.gate && epi.rows_per_gate >= WROWS;
-  int gq0 = 0, gr0 = 0, gq_last = 0;
-  if (epi.gate) {
-    const int first = t0 + wm * WROWS + 4 * (lane >> 4);
-    gq0 = first / epi.rows_per_gate;
-    gr0 = first - gq0 * epi.rows_per_gate;
-    gq_last = (T - 1) / epi.rows_per_gate;
-  }
+  FPQ_GEMM_GATE_SETUP(WROWS);
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);
@@ -194,25 +187,7 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void gemm_a6w4_kernel(const uint8_
     int tc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;
-    if (epi.gate) {
-      fpq_h4_t gt[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int off = gr0 + m * 16 + i;
-        int gq = gate_far ? gq0 + (off >= epi.rows_per_gate ? 1 : 0) : tc[i] / epi.rows_per_gate;
-        gq = gq < gq_last ? gq : gq_last;
-        gt[i] = *(const fpq_h4_t*)(epi.gate + (int64_t)gq * O + oc);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) y[i] = y[i] * gt[i];
-    }
-    if (epi.resid) {
-      fpq_h4_t rs[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) rs[i] = *(const fpq_h4_t*)(epi.resid + (int64_t)tc[i] * O + oc);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) y[i] = rs[i] + y[i];
-    }
+    FPQ_GEMM_GATE_RESID_ROWS(y, tc, m, oc);
     FPQ_GEMM_ROWS_STORE(y, t_first, tc, o, oc);
   }
 }

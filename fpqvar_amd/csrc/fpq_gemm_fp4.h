@@ -64,9 +64,78 @@ typedef _Float16 fpq_h4_t __attribute__((ext_vector_type(4)));
           __builtin_nontemporal_store(__builtin_bit_cast(u32x2, (y_)[i_]), (u32x2*)(out + (int64_t)(tc_)[i_] * O + (oc_))); \
   } while (0)
 
+// The gate / residual tail of the register epilogues (gemm_fp4_glds_kernel, gemm_a6w4_kernel, FPQ_GEMM_ROWS_EPILOGUE), written
+// once.  _SETUP in front of the loop over the tile rows: a gate row that spans at least the wavefront's WROWS_ rows costs ONE
+// division per tile (gq0_, gr0_) and a comparison per row instead of a division per row - 32 of them were a fifth of a tile's
+// vector instructions.  _ROWS for tile row m_: y_ = fpq_h4_t[4] (rows tc_[0..3], clamped to T - 1; outputs oc_ .. oc_ + 3) becomes
+// resid + y_ * gate.  Loads are unconditional on clamped rows.  Names from the kernel: epi, t0, wm, lane, T, O.
+#define FPQ_GEMM_GATE_SETUP(WROWS_)                                                                                 \
+  const bool gate_far_ = epi.gate && epi.rows_per_gate >= (WROWS_);                                                 \
+  int gq0_ = 0, gr0_ = 0, gq_last_ = 0;                                                                             \
+  if (epi.gate) {                                                                                                   \
+    const int gfirst_ = t0 + wm * (WROWS_) + 4 * (lane >> 4);                                                       \
+    gq0_ = gfirst_ / epi.rows_per_gate;                                                                             \
+    gr0_ = gfirst_ - gq0_ * epi.rows_per_gate;                                                                      \
+    gq_last_ = (T - 1) / epi.rows_per_gate;                                                                         \
+  }
+#define FPQ_GEMM_GATE_RESID_ROWS(y_, tc_, m_, oc_)                                                                  \
+  do {                                                                                                              \
+    if (epi.gate) {                                                                                                 \
+      fpq_h4_t gt_[4];                                                                                              \
+      _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                            \
+        const int goff_ = gr0_ + (m_) * 16 + i_;                                                                    \
+        int gq_ = gate_far_ ? gq0_ + (goff_ >= epi.rows_per_gate ? 1 : 0) : (tc_)[i_] / epi.rows_per_gate;          \
+        gq_ = gq_ < gq_last_ ? gq_ : gq_last_;                                                                      \
+        gt_[i_] = *(const fpq_h4_t*)(epi.gate + (int64_t)gq_ * O + (oc_));                                          \
+      }                                                                                                             \
+      _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) (y_)[i_] = (y_)[i_] * gt_[i_];                               \
+    }                                                                                                               \
+    if (epi.resid) {                                                                                                \
+      fpq_h4_t rs_[4];                                                                                              \
+      _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) rs_[i_] = *(const fpq_h4_t*)(epi.resid + (int64_t)(tc_)[i_] * O + (oc_)); \
+      _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) (y_)[i_] = rs_[i_] + (y_)[i_];                               \
+    }                                                                                                               \
+  } while (0)
+
+// The split output (GemmEpi's sp_* fields) of gemm_fp4_glds_kernel and FPQ_GEMM_ROWS_EPILOGUE_SPLIT, written once.  A tile lies
+// inside ONE part (sp_cols % 128 == 0).  _SETUP in front of the loop over the tile rows: the part's destination, and the batch
+// entry / row of the wavefront's first row - one division per tile while a batch entry spans the wavefront's WROWS_ rows.
+// on_: whether the output is split at all (the FP4 kernel's plain epilogue serves both: epi.sp_cols; the split epilogue: true).
+// _STORE: row i_ of tile row m_ (token t_first_ + i_) goes out as one non-temporal 8-byte store; t_ is the token a row that does
+// NOT span a batch entry is divided from - each kernel's own expression (clamped in the FP4 kernel, plain in the row-scaled ones).
+#define FPQ_GEMM_SPLIT_SETUP(WROWS_, on_)                                                                           \
+  const int sp_part_ = (on_) ? o0 / epi.sp_cols : 0;                                                                \
+  _Float16* const sp_base_ = sp_part_ == 0 ? epi.sp_out[0] : sp_part_ == 1 ? epi.sp_out[1] : epi.sp_out[2];         \
+  const int64_t sp_stride_ = sp_part_ == 0 ? epi.sp_stride[0] : sp_part_ == 1 ? epi.sp_stride[1] : epi.sp_stride[2]; \
+  const int64_t sp_bstride_ = sp_part_ == 0 ? epi.sp_bstride[0] : sp_part_ == 1 ? epi.sp_bstride[1] : epi.sp_bstride[2]; \
+  const int64_t sp_row0_ = sp_part_ == 0 ? epi.sp_row0[0] : sp_part_ == 1 ? epi.sp_row0[1] : epi.sp_row0[2];        \
+  const bool sp_far_ = (on_) && epi.sp_rpb >= (WROWS_);                                                             \
+  int sb0_ = 0, sr0_ = 0;                                                                                           \
+  if (on_) {                                                                                                        \
+    const int sfirst_ = t0 + wm * (WROWS_) + 4 * (lane >> 4);                                                       \
+    sb0_ = sfirst_ / epi.sp_rpb;                                                                                    \
+    sr0_ = sfirst_ - sb0_ * epi.sp_rpb;                                                                             \
+  }
+#define FPQ_GEMM_SPLIT_STORE(y_, m_, i_, t_, t_first_, o_, oc_l_)                                                   \
+  do {                                                                                                              \
+    const int soff_ = sr0_ + (m_) * 16 + (i_);                                                                      \
+    int bb_, ll_;                                                                                                   \
+    if (sp_far_) {                                                                                                  \
+      const int wrap_ = soff_ >= epi.sp_rpb ? 1 : 0;                                                                \
+      bb_ = sb0_ + wrap_;                                                                                           \
+      ll_ = soff_ - wrap_ * epi.sp_rpb;                                                                             \
+    } else {                                                                                                        \
+      bb_ = (t_) / epi.sp_rpb;                                                                                      \
+      ll_ = (t_) - bb_ * epi.sp_rpb;                                                                                \
+    }                                                                                                               \
+    if ((t_first_) + (i_) < T && (o_) < O)                                                                          \
+      __builtin_nontemporal_store(__builtin_bit_cast(u32x2, (y_)),                                                  \
+                                  (u32x2*)(sp_base_ + ((int64_t)bb_ * sp_bstride_ + sp_row0_ + ll_) * sp_stride_ + (oc_l_))); \
+  } while (0)
+
 // (macros, not functions: the kernels carry different target attributes and a callee is only inlined into a kernel
 // with the same ones)
-#define FPQ_GEMM_EPI_VEC(y, e, t, o, O)                                                                  \
+#define FPQ_GEMM_EPI_VEC(y, e, t, o, O)                                                                \
   do {                                                                                                   \
     if ((e).gate) {                                                                                      \
       const u32x4 g_ = *(const u32x4*)((e).gate + (int64_t)((t) / (e).rows_per_gate) * (O) + (o));       \
@@ -705,27 +774,8 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4
     }
     return;
   }
-  const bool gate_far = epi.gate && epi.rows_per_gate >= WROWS;
-  int gq0 = 0, gr0 = 0, gq_last = 0;
-  if (epi.gate) {
-    const int first = t0 + wm * WROWS + 4 * (lane >> 4);
-    gq0 = first / epi.rows_per_gate;
-    gr0 = first - gq0 * epi.rows_per_gate;
-    gq_last = (T - 1) / epi.rows_per_gate;
-  }
-  // split output: the tile lies inside ONE part (sp_cols % 128 == 0); its destination, and the batch entry / row of the wavefront's first row
-  const int part = epi.sp_cols ? o0 / epi.sp_cols : 0;
-  _Float16* const sp_base = part == 0 ? epi.sp_out[0] : part == 1 ? epi.sp_out[1] : epi.sp_out[2];
-  const int64_t sp_stride = part == 0 ? epi.sp_stride[0] : part == 1 ? epi.sp_stride[1] : epi.sp_stride[2];
-  const int64_t sp_bstride = part == 0 ? epi.sp_bstride[0] : part == 1 ? epi.sp_bstride[1] : epi.sp_bstride[2];
-  const int64_t sp_row0 = part == 0 ? epi.sp_row0[0] : part == 1 ? epi.sp_row0[1] : epi.sp_row0[2];
-  const bool sp_far = epi.sp_cols && epi.sp_rpb >= WROWS;
-  int sb0 = 0, sr0 = 0;
-  if (epi.sp_cols) {
-    const int first = t0 + wm * WROWS + 4 * (lane >> 4);
-    sb0 = first / epi.sp_rpb;
-    sr0 = first - sb0 * epi.sp_rpb;
-  }
+  FPQ_GEMM_GATE_SETUP(WROWS);
+  FPQ_GEMM_SPLIT_SETUP(WROWS, epi.sp_cols);   // (this epilogue serves the one-tensor output too)
   // (requesting the gate / residual rows one tile row ahead of their use - the compiler may not move a load above a store
   // that could alias it, and the residual may BE the output - was measured: 13 % slower with the fused tail, round 4)
 #pragma unroll
@@ -738,7 +788,7 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4
         float yf[NT];
 #pragma unroll
         for (int n = 0; n < NT; ++n) yf[n] = (float)(_Float16)acc[m][n][i] + qkn_b[n];
-        if (part < 2) FPQ_QK_NORM_ROW(yf, part, qkn_s);   // uniform over the tile
+        if (sp_part_ < 2) FPQ_QK_NORM_ROW(yf, sp_part_, qkn_s);   // uniform over the tile
 #pragma unroll
         for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)yf[n];
       }
@@ -751,44 +801,11 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4
     int tc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;
-    if (epi.gate) {
-      fpq_h4_t gt[4];
+    FPQ_GEMM_GATE_RESID_ROWS(y, tc, m, oc);
+    if (epi.sp_cols) {   // uniform: four 8-byte stores to the part's rows
+      const int oc_l = oc - sp_part_ * epi.sp_cols;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        // a gate row spans at least the wavefront's rows: ONE division per tile (gq0, gr0 below) and a comparison per row,
-        // instead of a division per row - 32 of them were a fifth of a tile's vector instructions
-        const int off = gr0 + m * 16 + i;
-        int gq = gate_far ? gq0 + (off >= epi.rows_per_gate ? 1 : 0) : tc[i] / epi.rows_per_gate;
-        gq = gq < gq_last ? gq : gq_last;
-        gt[i] = *(const fpq_h4_t*)(epi.gate + (int64_t)gq * O + oc);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) y[i] = y[i] * gt[i];
-    }
-    if (epi.resid) {
-      fpq_h4_t rs[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) rs[i] = *(const fpq_h4_t*)(epi.resid + (int64_t)tc[i] * O + oc);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) y[i] = rs[i] + y[i];
-    }
-    if (epi.sp_cols) {   // uniform: four 8-byte stores to the part's rows (one division per tile while a batch entry spans the wavefront's rows)
-      const int oc_l = oc - part * epi.sp_cols;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int off = sr0 + m * 16 + i;
-        int bb, ll;
-        if (sp_far) {
-          const int wrap = off >= epi.sp_rpb ? 1 : 0;
-          bb = sb0 + wrap;
-          ll = off - wrap * epi.sp_rpb;
-        } else {
-          bb = tc[i] / epi.sp_rpb;
-          ll = tc[i] - bb * epi.sp_rpb;
-        }
-        if (t_first + i < T && o < O)
-          __builtin_nontemporal_store(__builtin_bit_cast(u32x2, y[i]), (u32x2*)(sp_base + ((int64_t)bb * sp_bstride + sp_row0 + ll) * sp_stride + oc_l));
-      }
+      for (int i = 0; i < 4; ++i) FPQ_GEMM_SPLIT_STORE(y[i], m, i, tc[i], t_first, o, oc_l);
       continue;
     }
     // (non-temporal: a round of tiles writes as much as an XCD's L2 holds - the operands should stay there; +1-2 %)

@@ -47,15 +47,7 @@
     const int oc_ = o_ < O ? o_ : O - 4;                                                                            \
     const v4f_t sc_ = *(const v4f_t*)(lsc + wn * WCOLS_ + NT * (lane & 15));                                        \
     const v4f_t b_ = *(const v4f_t*)(lsb + wn * WCOLS_ + NT * (lane & 15));                                         \
-    /* a gate row that spans the wavefront's rows: one division per tile and a comparison per row (gemm_fp4_glds_kernel) */ \
-    const bool gate_far_ = epi.gate && epi.rows_per_gate >= WROWS_;                                                 \
-    int gq0_ = 0, gr0_ = 0, gq_last_ = 0;                                                                           \
-    if (epi.gate) {                                                                                                 \
-      const int first_ = t0 + wm * WROWS_ + 4 * (lane >> 4);                                                        \
-      gq0_ = first_ / epi.rows_per_gate;                                                                            \
-      gr0_ = first_ - gq0_ * epi.rows_per_gate;                                                                     \
-      gq_last_ = (T - 1) / epi.rows_per_gate;                                                                       \
-    }                                                                                                               \
+    FPQ_GEMM_GATE_SETUP(WROWS_)                                                                                     \
     _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                                \
       const int t_first_ = t0 + wm * WROWS_ + m * 16 + 4 * (lane >> 4);                                             \
       int tc_[4];                                                                                                   \
@@ -64,21 +56,7 @@
       fpq_h4_t y_[4];                                                                                               \
       _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                 \
           _Pragma("unroll") for (int n = 0; n < 4; ++n) y_[i][n] = (_Float16)(acc[m][n][i] * (sr_[i] * sc_[n]) + b_[n]); \
-      if (epi.gate) {                                                                                               \
-        fpq_h4_t g_[4];                                                                                             \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                             \
-          const int off_ = gr0_ + m * 16 + i;                                                                       \
-          int gq_ = gate_far_ ? gq0_ + (off_ >= epi.rows_per_gate ? 1 : 0) : tc_[i] / epi.rows_per_gate;            \
-          gq_ = gq_ < gq_last_ ? gq_ : gq_last_;                                                                    \
-          g_[i] = *(const fpq_h4_t*)(epi.gate + (int64_t)gq_ * O + oc_);                                            \
-        }                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) y_[i] = y_[i] * g_[i];                                        \
-      }                                                                                                             \
-      if (epi.resid) {                                                                                              \
-        fpq_h4_t r_[4];                                                                                             \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) r_[i] = *(const fpq_h4_t*)(epi.resid + (int64_t)tc_[i] * O + oc_); \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) y_[i] = r_[i] + y_[i];                                        \
-      }                                                                                                             \
+      FPQ_GEMM_GATE_RESID_ROWS(y_, tc_, m, oc_);                                                                    \
       FPQ_GEMM_ROWS_STORE(y_, t_first_, tc_, o_, oc_);                                                              \
     }                                                                                                               \
   } while (0)
@@ -97,17 +75,10 @@
     const int oc_ = o_ < O ? o_ : O - 4;                                                                            \
     const v4f_t sc_ = *(const v4f_t*)(lsc + wn * WCOLS_ + NT * (lane & 15));                                        \
     const v4f_t b_ = *(const v4f_t*)(lsb + wn * WCOLS_ + NT * (lane & 15));                                         \
-    const int part_ = o0 / epi.sp_cols;                                                                             \
-    _Float16* const sp_base_ = part_ == 0 ? epi.sp_out[0] : part_ == 1 ? epi.sp_out[1] : epi.sp_out[2];             \
-    const int64_t sp_stride_ = part_ == 0 ? epi.sp_stride[0] : part_ == 1 ? epi.sp_stride[1] : epi.sp_stride[2];    \
-    const int64_t sp_bstride_ = part_ == 0 ? epi.sp_bstride[0] : part_ == 1 ? epi.sp_bstride[1] : epi.sp_bstride[2]; \
-    const int64_t sp_row0_ = part_ == 0 ? epi.sp_row0[0] : part_ == 1 ? epi.sp_row0[1] : epi.sp_row0[2];            \
-    const bool sp_far_ = epi.sp_rpb >= WROWS_;                                                                      \
-    const int first_ = t0 + wm * WROWS_ + 4 * (lane >> 4);                                                          \
-    const int sb0_ = first_ / epi.sp_rpb, sr0_ = first_ - sb0_ * epi.sp_rpb;                                        \
-    const int oc_l_ = oc_ - part_ * epi.sp_cols;                                                                    \
+    FPQ_GEMM_SPLIT_SETUP(WROWS_, true)                                                                              \
+    const int oc_l_ = oc_ - sp_part_ * epi.sp_cols;                                                                 \
     _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                                \
-      const int t_first_ = first_ + m * 16;                                                                         \
+      const int t_first_ = t0 + wm * WROWS_ + 4 * (lane >> 4) + m * 16;                                             \
       const v4f_t sr_ = *(const v4f_t*)(lsr + wm * WROWS_ + m * 16 + 4 * (lane >> 4));                              \
       _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                               \
         fpq_h4_t y_;                                                                                                \
@@ -115,26 +86,14 @@
           float yf_[NT];                                                                                            \
           _Pragma("unroll") for (int n = 0; n < NT; ++n)                                                            \
               yf_[n] = (float)(_Float16)(acc[m][n][i] * (sr_[i] * sc_[n]) + 0.0f) + (qkn_b_)[n];                    \
-          if (part_ < 2) FPQ_QK_NORM_ROW(yf_, part_, (qkn_s_));   /* uniform over the tile */                         \
+          if (sp_part_ < 2) FPQ_QK_NORM_ROW(yf_, sp_part_, (qkn_s_));   /* uniform over the tile */                   \
           _Pragma("unroll") for (int n = 0; n < NT; ++n) y_[n] = (_Float16)yf_[n];                                  \
         } else {                                                                                                    \
           _Pragma("unroll") for (int n = 0; n < NT; ++n) y_[n] = (_Float16)(acc[m][n][i] * (sr_[i] * sc_[n]) + b_[n]); \
         }                                                                                                           \
-        const int off_ = sr0_ + m * 16 + i;                                                                         \
-        int bb_, ll_;                                                                                               \
-        if (sp_far_) {                                                                                              \
-          const int wrap_ = off_ >= epi.sp_rpb ? 1 : 0;                                                             \
-          bb_ = sb0_ + wrap_;                                                                                       \
-          ll_ = off_ - wrap_ * epi.sp_rpb;                                                                          \
-        } else {                                                                                                    \
-          bb_ = (t_first_ + i) / epi.sp_rpb;                                                                        \
-          ll_ = (t_first_ + i) - bb_ * epi.sp_rpb;                                                                  \
-        }                                                                                                           \
-        if (t_first_ + i < T && o_ < O)                                                                             \
-          __builtin_nontemporal_store(__builtin_bit_cast(u32x2, y_),                                                \
-                                      (u32x2*)(sp_base_ + ((int64_t)bb_ * sp_bstride_ + sp_row0_ + ll_) * sp_stride_ + oc_l_)); \
+        FPQ_GEMM_SPLIT_STORE(y_, m, i, t_first_ + i, t_first_, o_, oc_l_);                                          \
       }                                                                                                             \
-    }                                                                                                               \
+    }                                                                                                          \
   } while (0)
 
 FPQ_NOPK __device__ __forceinline__ int fp8_chunk_swz(int r) { return ((r >> 1) & 1) + ((r >> 3) << 2); }

@@ -187,6 +187,33 @@ def _check_kmajor_fp4(name: str, a_codes, a_scales, w_codes, w_scales, bias, out
     return tokens, outs, groups * 128
 
 
+def _fp4_operands(name: str, a_codes, a_scales, w_codes, w_scales, bias, outs):
+    """An FP4 operand pair, row-major codes (2-D) or k-major images (3-D), checked -> (km, tokens, outs, k); what the compiled
+    binding's fp4_shapes does.  `outs` (or the bias) only matters for images, see _check_kmajor_fp4."""
+    km = _kmajor_pair(name, a_codes, w_codes, 64)
+    if km:
+        return (km, *_check_kmajor_fp4(name, a_codes, a_scales, w_codes, w_scales, bias, outs))
+    tokens, outs, k = a_codes.shape[0], w_codes.shape[0], a_codes.shape[1] * 2
+    if w_codes.shape[1] * 2 != k or a_scales.dtype != torch.float16 or k % 128 != 0:
+        raise RuntimeError(f"{name}: operand shapes / activation scale dtype mismatch")
+    _check_operand(f"{name}(activation)", a_codes, a_scales, tokens, k // 2, tokens * (k // 128), a_codes.device)
+    _check_operand(f"{name}(weight)", w_codes, w_scales, outs, k // 2, outs * (k // 128), a_codes.device)
+    return km, tokens, outs, k
+
+
+def _bias_f16(name: str, bias: Optional[torch.Tensor], outs: Optional[int], device, align: int = 0) -> Optional[torch.Tensor]:
+    """The bias as the kernels read it: a contiguous fp16 vector, or None.  outs: when given, it must hold that many values
+    on `device`; align: when not 0, a copy is made unless the address is a multiple of it."""
+    if bias is None:
+        return None
+    if outs is not None and (bias.numel() != outs or bias.device != device):
+        raise RuntimeError(f"{name}: bias must hold one value per output ({outs}) on {device}")
+    b = bias.detach().to(torch.float16).reshape(-1).contiguous()
+    if align and b.data_ptr() % align:
+        b = b.clone()
+    return b
+
+
 def linear_fp4(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
                bias: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
                residual: Optional[torch.Tensor] = None, outs: Optional[int] = None) -> torch.Tensor:
@@ -196,21 +223,9 @@ def linear_fp4(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Ten
     if _native is not None:   # same checks, same C calls (fpq_gemm_fp4_mx_ex / fpq_gemm_fp4_mx_km)
         return _native.linear_fp4(a_codes, a_scales, w_codes, w_scales, bias, gate, residual, outs)
     require_gpu(a_codes, "linear_fp4")
-    km = _kmajor_pair("linear_fp4", a_codes, w_codes, 64)
-    if km:
-        tokens, outs, k = _check_kmajor_fp4("linear_fp4", a_codes, a_scales, w_codes, w_scales, bias, outs)
-    else:
-        tokens, outs, k = a_codes.shape[0], w_codes.shape[0], a_codes.shape[1] * 2
-        if w_codes.shape[1] * 2 != k:
-            raise RuntimeError("linear_fp4: operand shapes mismatch")
-        if a_scales.dtype != torch.float16 or k % 128 != 0:
-            raise RuntimeError("linear_fp4: operand shapes / activation scale dtype mismatch")
-        _check_operand("linear_fp4(activation)", a_codes, a_scales, tokens, k // 2, tokens * (k // 128), a_codes.device)
-        _check_operand("linear_fp4(weight)", w_codes, w_scales, outs, k // 2, outs * (k // 128), a_codes.device)
+    km, tokens, outs, k = _fp4_operands("linear_fp4", a_codes, a_scales, w_codes, w_scales, bias, outs)
     ep, keep, out = _epilogue("linear_fp4", tokens, outs, gate, residual, None, a_codes.device)
-    b = None if bias is None else bias.detach().to(torch.float16).reshape(-1).contiguous()
-    if km and b is not None and b.data_ptr() % 16:
-        b = b.clone()
+    b = _bias_f16("linear_fp4", bias, None, a_codes.device, 16 if km else 0)
     fn, what = (lib().fpq_gemm_fp4_mx_km, "fpq_gemm_fp4_mx_km") if km else (lib().fpq_gemm_fp4_mx_ex, "fpq_gemm_fp4_mx_ex")
     with device_guard(a_codes.device):
         check(fn(a_codes.data_ptr(), a_scales.data_ptr(), w_codes.data_ptr(), w_scales.data_ptr(), dtype_id(w_scales.dtype),
@@ -243,12 +258,8 @@ def _qkv_split_args(name: str, cache_kv: torch.Tensor, tokens: int, outs: int, b
             b = bias.detach().reshape(-1).contiguous()
             if b.data_ptr() % 16:
                 b = b.clone()
-    elif bias is not None:
-        if bias.numel() != outs or bias.device != dev:
-            raise RuntimeError(f"{name}: bias must hold one value per output on the operands' device")
-        b = bias.detach().to(torch.float16).reshape(-1).contiguous()
-        if b.data_ptr() % 16:
-            b = b.clone()
+    else:
+        b = _bias_f16(name, bias, outs, dev, 16)
     sp = GemmSplit()
     sp.part_cols, sp.n_parts, sp.rows_per_batch = c, 3, seq
     for p, (t, bstride, row0) in enumerate(((q, seq, 0), (cache_kv[0], max_len, pos), (cache_kv[1], max_len, pos))):
@@ -269,20 +280,11 @@ def linear_fp4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_cod
     y = float(fp16 Linear output) + bias (fp32 [3C] or None: q_bias, 0, v_bias, added after the fp16 rounding), q =
     F.normalize(y_q) * qk_norm_scale per head, k = F.normalize(y_k) into the cache, v = y_v (tr/basic_var.py:173-183), head_dim 64."""
     require_gpu(a_codes, "linear_fp4_qkv_to_cache")
-    km = _kmajor_pair("linear_fp4_qkv_to_cache", a_codes, w_codes, 64)
     dev = a_codes.device
     if cache_kv.dim() != 5 or cache_kv.shape[0] != 2 or cache_kv.dtype != torch.float16 or not cache_kv.is_contiguous() or cache_kv.device != dev:
         raise RuntimeError("linear_fp4_qkv_to_cache: cache_kv must be a contiguous float16 [2, B, max_len, H, c] tensor on the operands' device")
-    _, bsz, max_len, heads, hd = cache_kv.shape
-    c = heads * hd
-    if km:
-        tokens, outs, k = _check_kmajor_fp4("linear_fp4_qkv_to_cache", a_codes, a_scales, w_codes, w_scales, bias, 3 * c)
-    else:
-        tokens, outs, k = a_codes.shape[0], w_codes.shape[0], a_codes.shape[1] * 2
-        if w_codes.shape[1] * 2 != k or a_scales.dtype != torch.float16 or k % 128 != 0:
-            raise RuntimeError("linear_fp4_qkv_to_cache: operand shapes / activation scale dtype mismatch")
-        _check_operand("linear_fp4_qkv_to_cache(activation)", a_codes, a_scales, tokens, k // 2, tokens * (k // 128), dev)
-        _check_operand("linear_fp4_qkv_to_cache(weight)", w_codes, w_scales, outs, k // 2, outs * (k // 128), dev)
+    km, tokens, outs, k = _fp4_operands("linear_fp4_qkv_to_cache", a_codes, a_scales, w_codes, w_scales, bias,
+                                        3 * cache_kv.shape[3] * cache_kv.shape[4])
     q, sp, b, hs = _qkv_split_args("linear_fp4_qkv_to_cache", cache_kv, tokens, outs, bias, pos, seq, qk_norm_scale)
     if tokens and qk_norm_scale is not None:
         with device_guard(dev):
@@ -309,27 +311,13 @@ def linear_fp4_gelu_dual(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes:
         out, h = _native.linear_fp4_gelu_dual(a_codes, a_scales, w_codes, w_scales, bias, return_gelu, outs)
         return (out, h) if return_gelu else out
     require_gpu(a_codes, "linear_fp4_gelu_dual")
-    km = _kmajor_pair("linear_fp4_gelu_dual", a_codes, w_codes, 64)
     dev = a_codes.device
-    if km:
-        tokens, outs, k = _check_kmajor_fp4("linear_fp4_gelu_dual", a_codes, a_scales, w_codes, w_scales, bias, outs)
-    else:
-        tokens, outs, k = a_codes.shape[0], w_codes.shape[0], a_codes.shape[1] * 2
-        if w_codes.shape[1] * 2 != k or a_scales.dtype != torch.float16 or k % 128 != 0:
-            raise RuntimeError("linear_fp4_gelu_dual: operand shapes / activation scale dtype mismatch")
-        _check_operand("linear_fp4_gelu_dual(activation)", a_codes, a_scales, tokens, k // 2, tokens * (k // 128), dev)
-        _check_operand("linear_fp4_gelu_dual(weight)", w_codes, w_scales, outs, k // 2, outs * (k // 128), dev)
+    km, tokens, outs, k = _fp4_operands("linear_fp4_gelu_dual", a_codes, a_scales, w_codes, w_scales, bias, outs)
     if outs % 128 != 0:
         raise RuntimeError("linear_fp4_gelu_dual: outs must be a multiple of 128")
     out = torch.empty((tokens, outs), dtype=torch.float16, device=dev)
     h = torch.empty((tokens, outs), dtype=torch.float16, device=dev) if return_gelu else None
-    b = None
-    if bias is not None:
-        if bias.numel() != outs or bias.device != dev:
-            raise RuntimeError("linear_fp4_gelu_dual: bias must hold one value per output on the operands' device")
-        b = bias.detach().to(torch.float16).reshape(-1).contiguous()
-        if b.data_ptr() % 16:
-            b = b.clone()
+    b = _bias_f16("linear_fp4_gelu_dual", bias, outs, dev, 16)
     if tokens and outs:
         from .ops import _nan_scratch
         with device_guard(dev):
@@ -403,11 +391,7 @@ def linear_a6w4(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_c
     _check_operand("linear_a6w4(activation)", a_codes, a_scales, tokens, k * 3 // 4, tokens * (k // 128), a_codes.device)
     _check_operand("linear_a6w4(weight)", w_codes, w_scales, outs, k // 2, outs * (k // 128), a_codes.device)
     ep, keep, out = _epilogue("linear_a6w4", tokens, outs, gate, residual, None, a_codes.device)
-    b = None if bias is None else bias.detach().to(torch.float16).reshape(-1).contiguous()
-    if b is not None and (b.numel() != outs or b.device != a_codes.device):
-        raise RuntimeError(f"linear_a6w4: bias must hold {outs} elements on {a_codes.device}")
-    if b is not None and b.data_ptr() % 8:
-        b = b.clone()
+    b = _bias_f16("linear_a6w4", bias, outs, a_codes.device, 8)
     with device_guard(a_codes.device):
         check(lib().fpq_gemm_a6w4_mx(a_codes.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_codes.data_ptr(), w_scales.data_ptr(),
                                      dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), out.data_ptr(), tokens, outs, k, ep,
@@ -545,7 +529,7 @@ def linear_fp8(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Ten
     _check_operand("linear_fp8(activation)", a_codes, a_scales, tokens, k, tokens, a_codes.device)
     _check_operand("linear_fp8(weight)", w_codes, w_scales, outs, k, outs, a_codes.device)
     ep, keep, out = _epilogue("linear_fp8", tokens, outs, gate, residual, None, a_codes.device)
-    b = None if bias is None else bias.detach().to(torch.float16).reshape(-1).contiguous()
+    b = _bias_f16("linear_fp8", bias, None, a_codes.device)
     with device_guard(a_codes.device):
         check(lib().fpq_gemm_fp8_rows_ex(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), w_codes.data_ptr(),
                                          w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(),
@@ -640,6 +624,39 @@ def dequantize_fp6(codes: torch.Tensor, scales: torch.Tensor, table: str = "e2m3
     return val * scales.float().unsqueeze(-1)
 
 
+def _fp6_operands(name: str, a_codes, a_scales, w_codes, w_scales):
+    """A row-scaled 6-bit operand pair, row-major codes (2-D) or k-major images (3-D), checked -> (km, tokens, outs, k)"""
+    km = _kmajor_pair(name, a_codes, w_codes, 96)
+    if km:
+        tokens, outs, k = a_codes.shape[1], w_scales.shape[0], a_codes.shape[0] * 128
+        w_rows, row_bytes = (outs + 63) // 64 * 64, a_codes.shape[0] * 96
+    else:
+        tokens, outs, k = a_codes.shape[0], w_codes.shape[0], a_codes.shape[1] * 4 // 3
+        w_rows, row_bytes = outs, a_codes.shape[1]
+        if w_codes.shape[1] != a_codes.shape[1]:
+            raise RuntimeError(f"{name}: operand shapes mismatch")
+    _check_operand(f"{name}(activation)", a_codes, a_scales, tokens, row_bytes, tokens, a_codes.device)
+    _check_operand(f"{name}(weight)", w_codes, w_scales, w_rows, row_bytes, outs, a_codes.device)
+    return km, tokens, outs, k
+
+
+def _fp6_gemm(form: str, a_codes, a_scales, a_table: str, w_codes, w_scales, w_table: str, km: bool, *rest) -> None:
+    """One call of the FP6 GEMM's C entry point of `form` ("", "_split" or "_split_qknorm"); rest: its arguments between the
+    weight scales' dtype and the k-major flag.  (E2M3, E2M3) goes to fpq_gemm_fp6_rows_*, any other pair to fpq_gemm_f6_rows*
+    with the two table ids."""
+    a = (a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype))
+    w = (w_codes.data_ptr(), w_scales.data_ptr(), dtype_id(w_scales.dtype))
+    if (a_table, w_table) != ("e2m3", "e2m3"):
+        from ._lib import TABLE_IDS
+        what, args = "fpq_gemm_f6_rows" + form, (*a, TABLE_IDS[a_table], *w, TABLE_IDS[w_table], *rest, 1 if km else 0)
+    elif form:
+        what, args = "fpq_gemm_fp6_rows" + form, (*a, *w, *rest, 1 if km else 0)
+    else:   # the plain E2M3 x E2M3 form has an entry point per layout instead of the flag
+        what, args = "fpq_gemm_fp6_rows_km" if km else "fpq_gemm_fp6_rows_ex", (*a, *w, *rest)
+    with device_guard(a_codes.device):
+        check(getattr(lib(), what)(*args, stream_ptr(a_codes.device)), what)
+
+
 def linear_fp6(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
                bias: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
                residual: Optional[torch.Tensor] = None, a_table: str = "e2m3", w_table: str = "e2m3") -> torch.Tensor:
@@ -648,33 +665,13 @@ def linear_fp6(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Ten
     "e2m3" (FP6) or "e3m2" (BF6) - the matrix instruction decodes each operand by its own selector (fpq_gemm_f6_rows)."""
     require_gpu(a_codes, "linear_fp6")
     a_table, w_table = _f6_table("linear_fp6", a_table), _f6_table("linear_fp6", w_table)
-    km = _kmajor_pair("linear_fp6", a_codes, w_codes, 96)
-    if km:
-        tokens, outs, k = a_codes.shape[1], w_scales.shape[0], a_codes.shape[0] * 128
-        w_rows, row_bytes = (outs + 63) // 64 * 64, a_codes.shape[0] * 96
-    else:
-        tokens, outs, k = a_codes.shape[0], w_codes.shape[0], a_codes.shape[1] * 4 // 3
-        w_rows, row_bytes = outs, a_codes.shape[1]
-        if w_codes.shape[1] != a_codes.shape[1] or a_codes.shape[1] % 3 != 0:
-            raise RuntimeError("linear_fp6: operand shapes mismatch")
-    _check_operand("linear_fp6(activation)", a_codes, a_scales, tokens, row_bytes, tokens, a_codes.device)
-    _check_operand("linear_fp6(weight)", w_codes, w_scales, w_rows, row_bytes, outs, a_codes.device)
+    if a_codes.dim() == 2 and w_codes.dim() == 2 and a_codes.shape[1] % 3 != 0:
+        raise RuntimeError("linear_fp6: operand shapes mismatch")
+    km, tokens, outs, k = _fp6_operands("linear_fp6", a_codes, a_scales, w_codes, w_scales)
     ep, keep, out = _epilogue("linear_fp6", tokens, outs, gate, residual, None, a_codes.device)
-    b = None if bias is None else bias.detach().to(torch.float16).reshape(-1).contiguous()
-    if (a_table, w_table) != ("e2m3", "e2m3"):
-        from ._lib import TABLE_IDS
-        with device_guard(a_codes.device):
-            check(lib().fpq_gemm_f6_rows(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), TABLE_IDS[a_table],
-                                         w_codes.data_ptr(), w_scales.data_ptr(), dtype_id(w_scales.dtype), TABLE_IDS[w_table],
-                                         None if b is None else b.data_ptr(), out.data_ptr(), tokens, outs, k, ep, 1 if km else 0,
-                                         stream_ptr(a_codes.device)), "fpq_gemm_f6_rows")
-        del keep
-        return out
-    fn, what = (lib().fpq_gemm_fp6_rows_km, "fpq_gemm_fp6_rows_km") if km else (lib().fpq_gemm_fp6_rows_ex, "fpq_gemm_fp6_rows_ex")
-    with device_guard(a_codes.device):
-        check(fn(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), w_codes.data_ptr(), w_scales.data_ptr(),
-                 dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), out.data_ptr(), tokens, outs, k, ep,
-                 stream_ptr(a_codes.device)), what)
+    b = _bias_f16("linear_fp6", bias, None, a_codes.device)
+    _fp6_gemm("", a_codes, a_scales, a_table, w_codes, w_scales, w_table, km, None if b is None else b.data_ptr(), out.data_ptr(),
+              tokens, outs, k, ep)
     del keep
     return out
 
@@ -691,47 +688,17 @@ def linear_fp6_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_cod
     name = "linear_fp6_qkv_to_cache"
     require_gpu(a_codes, name)
     a_table, w_table = _f6_table(name, a_table), _f6_table(name, w_table)
-    km = _kmajor_pair(name, a_codes, w_codes, 96)
     dev = a_codes.device
     if cache_kv.dim() != 5 or cache_kv.shape[0] != 2 or cache_kv.dtype != torch.float16 or not cache_kv.is_contiguous() or cache_kv.device != dev:
         raise RuntimeError(f"{name}: cache_kv must be a contiguous float16 [2, B, max_len, H, c] tensor on the operands' device")
-    if km:
-        tokens, outs, k = a_codes.shape[1], w_scales.shape[0], a_codes.shape[0] * 128
-        w_rows, row_bytes = (outs + 63) // 64 * 64, a_codes.shape[0] * 96
-    else:
-        tokens, outs, k = a_codes.shape[0], w_codes.shape[0], a_codes.shape[1] * 4 // 3
-        w_rows, row_bytes = outs, a_codes.shape[1]
-        if w_codes.shape[1] != a_codes.shape[1] or a_codes.shape[1] % 96 != 0:
-            raise RuntimeError(f"{name}: operand shapes mismatch")
-    _check_operand(f"{name}(activation)", a_codes, a_scales, tokens, row_bytes, tokens, dev)
-    _check_operand(f"{name}(weight)", w_codes, w_scales, w_rows, row_bytes, outs, dev)
+    if a_codes.dim() == 2 and w_codes.dim() == 2 and a_codes.shape[1] % 96 != 0:
+        raise RuntimeError(f"{name}: operand shapes mismatch")
+    km, tokens, outs, k = _fp6_operands(name, a_codes, a_scales, w_codes, w_scales)
     q, sp, b, hs = _qkv_split_args(name, cache_kv, tokens, outs, bias, pos, seq, qk_norm_scale)
-    if tokens and (a_table, w_table) != ("e2m3", "e2m3"):
-        from ._lib import TABLE_IDS
-        ta, tw = TABLE_IDS[a_table], TABLE_IDS[w_table]
-        with device_guard(dev):
-            if hs is not None:
-                check(lib().fpq_gemm_f6_rows_split_qknorm(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), ta, w_codes.data_ptr(),
-                                                          w_scales.data_ptr(), dtype_id(w_scales.dtype), tw, None if b is None else b.data_ptr(),
-                                                          tokens, outs, k, ctypes.byref(sp), hs.data_ptr(), 1 if km else 0, stream_ptr(dev)),
-                      "fpq_gemm_f6_rows_split_qknorm")
-            else:
-                check(lib().fpq_gemm_f6_rows_split(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), ta, w_codes.data_ptr(),
-                                                   w_scales.data_ptr(), dtype_id(w_scales.dtype), tw, None if b is None else b.data_ptr(),
-                                                   tokens, outs, k, ctypes.byref(sp), 1 if km else 0, stream_ptr(dev)),
-                      "fpq_gemm_f6_rows_split")
-    elif tokens and hs is not None:
-        with device_guard(dev):
-            check(lib().fpq_gemm_fp6_rows_split_qknorm(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), w_codes.data_ptr(),
-                                                       w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(),
-                                                       tokens, outs, k, ctypes.byref(sp), hs.data_ptr(), 1 if km else 0, stream_ptr(dev)),
-                  "fpq_gemm_fp6_rows_split_qknorm")
-    elif tokens:
-        with device_guard(dev):
-            check(lib().fpq_gemm_fp6_rows_split(a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), w_codes.data_ptr(),
-                                                w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(),
-                                                tokens, outs, k, ctypes.byref(sp), 1 if km else 0, stream_ptr(dev)),
-                  "fpq_gemm_fp6_rows_split")
+    if tokens:
+        norm = () if hs is None else (hs.data_ptr(),)
+        _fp6_gemm("_split" if hs is None else "_split_qknorm", a_codes, a_scales, a_table, w_codes, w_scales, w_table, km,
+                  None if b is None else b.data_ptr(), tokens, outs, k, ctypes.byref(sp), *norm)
     return q
 
 
