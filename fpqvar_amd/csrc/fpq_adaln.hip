@@ -93,89 +93,51 @@ int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out
       const bool tight_ok = FPQ_ADALN_TIGHT && !fpq_flag(OPT_FPQ_ADALN_NO_TIGHT);
       // E2M3 / E3M2 values (per group, or per token: token_mode 1): levels from the FP6 conversion hardware, no table
       const int hw6 = (token_mode <= 1 && !code_scales && !fpq_flag(OPT_FPQ_NO_HW6)) ? (table_id == FPQ_E2M3 ? 1 : table_id == FPQ_E3M2 ? 2 : 0) : 0;
-#define FPQ_ADALN3(M, CODES, EMIT, TOKEN, HW4, TIGHT)                                                                  \
-  hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, CODES, EMIT, TOKEN, X32, HW4, TIGHT>), g3, dim3(kBlock), lds2, st,    \
-                     (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab, tiers)
-#define FPQ_ADALN2K(M, CODES, EMIT, TOKEN)                                                                             \
-  do {                                                                                                                 \
-    if constexpr ((M == 4 || M == 5) && !(CODES) && !(EMIT)) {   /* E2M3 / E3M2 values, rows of 13 .. 20 groups: hardware levels */ \
-      if (hw6 == 1) {                                                                                                  \
-        hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 1>), g3,      \
-                           dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,         \
-                           rows, ad, r, h.args, tab, tiers);                                                           \
-        break;                                                                                                         \
-      }                                                                                                                \
-      if (hw6 == 2) {                                                                                                  \
-        hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 2>), g3,      \
-                           dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,         \
-                           rows, ad, r, h.args, tab, tiers);                                                           \
-        break;                                                                                                         \
-      }                                                                                                                \
-    }                                                                                                                  \
-    if constexpr (M == 2 && !X32 && !(EMIT) && !(TOKEN)) {                                                             \
-      if (pair2) {                                                                                                     \
-        if (hw4)                                                                                                       \
-          hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, 4, CODES, false, false, false, true, false, 4, true>), g3,       \
-                             dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,       \
-                             rows, ad, r, h.args, tab, tiers);                                                         \
-        else                                                                                                           \
-          hipLaunchKernelGGL((adaln_mfma_kernel<Tmod, 4, CODES, false, false, false, false, false, 4, true>), g3,      \
-                             dim3(kBlock), lds2, st, (const u32x4*)x, (u32x4*)out, (u32x4*)h_out, (u32x4*)y_out,       \
-                             rows, ad, r, h.args, tab, tiers);                                                         \
-        break;                                                                                                         \
-      }                                                                                                                \
-    }                                                                                                                  \
-    if constexpr (!(TOKEN)) {                                                                                          \
-      if constexpr (M == 4 && !X32 && !(EMIT) && !(CODES)) {                                                           \
-        if (hw4 && tight_ok && r.vec_per_row == 240) {   /* VAR-d30: 31 KiB of LDS, five workgroups per CU */          \
-          FPQ_ADALN3(M, CODES, EMIT, TOKEN, true, true);                                                               \
-          break;                                                                                                       \
-        }                                                                                                              \
-      }                                                                                                                \
-      if (hw4) {                                                                                                       \
-        FPQ_ADALN3(M, CODES, EMIT, TOKEN, true, false);                                                                \
-        break;                                                                                                         \
-      }                                                                                                                \
-    }                                                                                                                  \
-    FPQ_ADALN3(M, CODES, EMIT, TOKEN, false, false);                                                                   \
-  } while (0)
 #ifdef FPQ_ADALN_STAMPS
 #define FPQ_ADALN_EMIT (h_out != nullptr)   /* diagnostic build: y_out alone is the stamp buffer */
 #else
 #define FPQ_ADALN_EMIT (h_out || y_out)
 #endif
-#define FPQ_ADALN2(M)                                                                                                  \
-  do {                                                                                                                 \
-    const bool emit = FPQ_ADALN_EMIT;                                                                                  \
-    if (token_mode >= 2) FPQ_ADALN2K(M, true, false, true);                                                            \
-    else if (token_mode == 1 && emit) FPQ_ADALN2K(M, false, true, true);                                               \
-    else if (token_mode == 1) FPQ_ADALN2K(M, false, false, true);                                                      \
-    else if (code_scales) FPQ_ADALN2K(M, true, false, false);                                                          \
-    else if (emit) FPQ_ADALN2K(M, false, true, false);                                                                 \
-    else FPQ_ADALN2K(M, false, false, false);                                                                          \
-  } while (0)
-      switch ((int)((r.vec_per_row + 63) / 64)) {   // MAXC = ceil(vectors per row / 64), exactly
-        case 1: FPQ_ADALN2(1); break;
-        case 2: FPQ_ADALN2(2); break;
-        case 3: FPQ_ADALN2(3); break;
-        case 4: FPQ_ADALN2(4); break;
-        default: FPQ_ADALN2(5); break;
-      }
-#undef FPQ_ADALN3
-#undef FPQ_ADALN2
-#undef FPQ_ADALN2K
-      return check_launch();
+      const bool emit = FPQ_ADALN_EMIT;
+      auto go = [&](auto kern) { return launch(kern, g3, lds2, st, x, out, h_out, y_out, rows, ad, r, h.args, tab, tiers); };
+      // the form of adaln_mfma_kernel for rows of up to M x 64 vectors: CODES - operands out; EMIT - h / the rotated rows go out
+      // too; TOKEN - one scale per row
+      auto pick = [&](auto m, auto codes, auto emits, auto token) {
+        constexpr int M = m.value;
+        constexpr bool CODES = codes.value, EMIT = emits.value, TOKEN = token.value;
+        if constexpr ((M == 4 || M == 5) && !CODES && !EMIT) {   // E2M3 / E3M2 values, rows of 13 .. 20 groups: hardware levels
+          if (hw6 == 1) return go(adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 1>);
+          if (hw6 == 2) return go(adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 2>);
+        }
+        if constexpr (M == 2 && !X32 && !EMIT && !TOKEN) {
+          if (pair2)
+            return with_bool(hw4, [&](auto hw) {
+              return go(adaln_mfma_kernel<Tmod, 4, CODES, false, false, false, hw.value, false, 4, true>);
+            });
+        }
+        if constexpr (!TOKEN) {
+          if constexpr (M == 4 && !X32 && !EMIT && !CODES) {
+            if (hw4 && tight_ok && r.vec_per_row == 240)   // VAR-d30: 31 KiB of LDS, five workgroups per CU
+              return go(adaln_mfma_kernel<Tmod, M, CODES, EMIT, TOKEN, X32, true, true>);
+          }
+          if (hw4) return go(adaln_mfma_kernel<Tmod, M, CODES, EMIT, TOKEN, X32, true, false>);
+        }
+        return go(adaln_mfma_kernel<Tmod, M, CODES, EMIT, TOKEN, X32, false, false>);
+      };
+      // MAXC = ceil(vectors per row / 64), exactly: 1 .. 5 (vec_per_row <= 64 * 5 above)
+      return with_int<1, 2, 3, 4, 5>((int)((r.vec_per_row + 63) / 64), [&](auto m) {
+        if (token_mode >= 2) return pick(m, Bool<true>{}, Bool<false>{}, Bool<true>{});
+        if (token_mode == 1) return with_bool(emit, [&](auto e) { return pick(m, Bool<false>{}, e, Bool<true>{}); });
+        if (code_scales) return pick(m, Bool<true>{}, Bool<false>{}, Bool<false>{});
+        return with_bool(emit, [&](auto e) { return pick(m, Bool<false>{}, e, Bool<false>{}); });
+      });
     }
   }
   // rows beyond one wavefront (2560 < C <= 4096, per group only): the first generation, one workgroup per row
   const dim3 g((unsigned)(rows < 8192 ? rows : 8192));   // every workgroup stages the table once, then walks rows
-  if (code_scales)
-    hipLaunchKernelGGL((adaln_rotate_quant16_kernel<Tin, Tmod, true>), g, dim3(kBlock), lds, st, x, (u32x4*)out,
-                       (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab);
-  else
-    hipLaunchKernelGGL((adaln_rotate_quant16_kernel<Tin, Tmod, false>), g, dim3(kBlock), lds, st, x, (u32x4*)out,
-                       (u32x4*)h_out, (u32x4*)y_out, rows, ad, r, h.args, tab);
-  return check_launch();
+  return with_bool(code_scales != nullptr, [&](auto codes) {
+    return launch(adaln_rotate_quant16_kernel<Tin, Tmod, codes.value>, g, lds, st, x, out, h_out, y_out, rows, ad, r, h.args, tab);
+  });
 }
 
 }  // namespace
@@ -188,9 +150,8 @@ static int adaln_rotate_quant_impl(const void* x, void* out, void* h_out, void* 
                                    const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream,
                                    int token_mode = 0, const Lut16Tab* token_code_tab = nullptr, bool km = false) {
   if (rows < 0 || cols < 0 || rows_per_batch <= 0 || !sign_mask_host) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if ((in_dtype != FPQ_F16 && in_dtype != FPQ_F32) || (mod_dtype != FPQ_F16 && mod_dtype != FPQ_F32))
-    return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype) || !is_f16_or_f32(mod_dtype)) return FPQ_ERR_DTYPE;
   if (cols % 128 != 0 || cols > 4096) return FPQ_ERR_SHAPE;
   if (rows == 0 || cols == 0) return FPQ_OK;
   if (!x || !out || !scale || !shift) return FPQ_ERR_ARG;
@@ -208,14 +169,12 @@ static int adaln_rotate_quant_impl(const void* x, void* out, void* h_out, void* 
   // loop; measured 0.180 ms vs 0.199 ms per [65500 x 1920] on MI355X), one workgroup per row beyond.
   if (token_mode && cols / 8 > 64 * 5) return FPQ_ERR_SHAPE;   // the per-token form keeps a row inside one wavefront: C <= 2560
   hipStream_t st = (hipStream_t)stream;
-#define FPQ_GO(TI, TM) return launch_adaln_rotate_quant<TI, TM>(x, out, h_out, rotated_out, rows, cols, ad, smooth, \
-                                                              sign_mask_host, table_id, st, (uint16_t*)code_scales, \
-                                                              token_mode, token_code_tab, km)
-  if (in_dtype == FPQ_F16 && mod_dtype == FPQ_F16) FPQ_GO(_Float16, _Float16);
-  if (in_dtype == FPQ_F16) FPQ_GO(_Float16, float);
-  if (mod_dtype == FPQ_F16) FPQ_GO(float, _Float16);
-  FPQ_GO(float, float);
-#undef FPQ_GO
+  return with_dtype(in_dtype, [&](auto ti) {
+    return with_dtype(mod_dtype, [&](auto tm) {
+      return launch_adaln_rotate_quant<decltype(ti), decltype(tm)>(x, out, h_out, rotated_out, rows, cols, ad, smooth, sign_mask_host,
+                                                                   table_id, st, (uint16_t*)code_scales, token_mode, token_code_tab, km);
+    });
+  });
 }
 
 int fpq_adaln_rotate_quant_rows(const void* x, void* out, void* h_out, void* rotated_out, int64_t rows, int64_t cols,
@@ -257,7 +216,7 @@ int fpq_adaln_rotate_quant_token_rows_codes_fp8(const void* x, uint8_t* codes, v
                                                 int64_t rows_per_batch, float eps, const float* smooth,
                                                 const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream) {
   if (rows > 0 && cols > 0 && !row_scales) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
   return adaln_rotate_quant_impl(x, codes, nullptr, nullptr, row_scales, rows, cols, in_dtype, scale, shift, mod_dtype,
                                  rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 2, &lut16_codes8(table_id));
 }

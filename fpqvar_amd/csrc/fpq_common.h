@@ -4,6 +4,7 @@
 // Everything lives in an anonymous namespace: each translation unit gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -92,6 +93,14 @@ const TableInfo kTables[FPQ_NUM_TABLES] = {
     {"e2m1_pos", 0, 1.0f, 1, 6.0f, 8},  {"int_neg", 0, 32.0f, 5, 32.0f, 33},
     {"e2m3_pos", 0, 1.0f, 3, 7.5f, 32}, {"e2m1_neg", 0, 1.0f, 1, 6.0f, 8},
 };
+// what the entry points ask of their arguments: a table id that fpq_quant_rows and the other one-table forms take; the
+// (x <= 0, x > 0) pairs of the dual-format forms; a floating-point fpq_dtype of rows or scales
+inline bool is_symmetric_table(int id) { return id >= 0 && id < FPQ_NUM_TABLES && kTables[id].symmetric; }
+inline bool is_dual_pair(int neg_id, int pos_id) {
+  return (neg_id == FPQ_E1M2_NEG || neg_id == FPQ_INT_NEG || neg_id == FPQ_E2M1_NEG) &&
+         (pos_id == FPQ_E2M1_POS || pos_id == FPQ_E2M3_POS);
+}
+inline bool is_f16_or_f32(int dtype) { return dtype == FPQ_F16 || dtype == FPQ_F32; }
 
 inline uint32_t f2u(float f) {
   uint32_t u;
@@ -370,6 +379,45 @@ inline int grid_for(int64_t work_items_of_block, int64_t cap = kMaxBlocks) {
 }
 
 inline int check_launch() { return hipGetLastError() == hipSuccess ? FPQ_OK : FPQ_ERR_LAUNCH; }
+
+// THE launch of a producer: workgroups of kBlock lanes, every argument converted to the kernel's own parameter type (a
+// const void* operand to the kernel's pointer), then the launch status.  (The GEMMs' counterpart: fpq_gemm.hip, gemm_launch.)
+template <typename... P, typename... A>
+int launch(void (*kernel)(P...), dim3 grid, size_t lds, hipStream_t st, const A&... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, st, static_cast<P>(args)...);
+  return check_launch();
+}
+
+// workgroups that cover n_vec 16-byte vectors at U of them per lane
+inline int64_t tiles_of(int64_t n_vec, int U) { return (n_vec + (int64_t)kBlock * U - 1) / ((int64_t)kBlock * U); }
+
+// A runtime value -> a value whose TYPE carries it, for a generic lambda to take the template argument from:
+//   with_dtype(d, f): FPQ_F16 / FPQ_F32 (checked by the caller: is_f16_or_f32) -> f(_Float16{}) / f(float{})
+//   with_bool(b, f) -> f(Bool<b>{});  with_int<1, 2, 4>(v, f) -> f(Int<v>{}), FPQ_ERR_SHAPE when v is not in the list
+template <int N>
+struct Int { static constexpr int value = N; };
+template <bool B>
+struct Bool { static constexpr bool value = B; };
+template <typename F>
+int with_dtype(int dtype, F&& f) {
+  return dtype == FPQ_F16 ? f(_Float16{}) : f(float{});
+}
+template <typename F>
+int with_bool(bool b, F&& f) {
+  return b ? f(Bool<true>{}) : f(Bool<false>{});
+}
+template <int... Ns, typename F>
+int with_int(int v, F&& f) {
+  int rc = FPQ_ERR_SHAPE;
+  (void)((v == Ns && (rc = f(Int<Ns>{}), true)) || ...);
+  return rc;
+}
+// the first of the ascending `steps` that holds v (a register budget: vectors per lane), the last one beyond them
+inline int step_for(int64_t v, std::initializer_list<int> steps) {
+  for (int s : steps)
+    if (v <= s) return s;
+  return *(steps.end() - 1);
+}
 
 // (T)(x / s).  fp16: x and s carry 11-bit significands, so one residual step on x*rcp(s) lands on the
 // correctly rounded quotient (fpq_fast16.h, "exact fp16 division"); where it differs from IEEE

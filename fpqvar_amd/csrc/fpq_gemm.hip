@@ -123,22 +123,13 @@ int gemm_launch(void (*kernel)(const uint8_t*, const Tsa*, const uint8_t*, const
   return check_launch();
 }
 
-// a runtime fpq_dtype of scales (FPQ_F16 or FPQ_F32, checked by the caller) -> a value of that type, for a generic lambda to
-// take the type from
-template <typename F>
-int with_scale_type(int dtype, F&& f) {
-  return dtype == FPQ_F16 ? f(_Float16{}) : f(float{});
-}
-template <int N>
-struct Int { static constexpr int value = N; };
-
 constexpr int kTileDoesNotFit = 1;   // (not an FPQ_* code) the tiling's LDS image is too large at this K: the caller tries the next one
 
 // the FP4 LDS-DMA kernel with 32 MT x 128 tiles and epilogue XE; lds: GemmGldsCfg's figure for that epilogue
 template <int MT, typename XE>
 int launch_fp4_glds(const GemmCall& c, int w_scale_dtype, size_t lds, XE xe) {
   if (lds > 160 * 1024) return kTileDoesNotFit;
-  return with_scale_type(w_scale_dtype, [&](auto tw) {
+  return with_dtype(w_scale_dtype, [&](auto tw) {
     return gemm_launch(gemm_fp4_glds_kernel<decltype(tw), MT, 4, XE>, GemmGldsCfg<MT, 4>::BM, GemmGldsCfg<MT, 4>::BN, 256, lds, c, xe);
   });
 }
@@ -146,7 +137,7 @@ int launch_fp4_glds(const GemmCall& c, int w_scale_dtype, size_t lds, XE xe) {
 template <int MT, int NT, int WR, int WC>
 int launch_fp4_staged(const GemmCall& c, int w_scale_dtype) {
   using Cfg = GemmCfg<MT, NT, WR, WC>;
-  return with_scale_type(w_scale_dtype, [&](auto tw) {
+  return with_dtype(w_scale_dtype, [&](auto tw) {
     return gemm_launch(gemm_fp4_kernel<decltype(tw), MT, NT, WR, WC>, Cfg::BM, Cfg::BN, Cfg::NTHR, Cfg::lds((int)(c.k / 128)), c);
   });
 }
@@ -156,7 +147,7 @@ int launch_a6w4(const GemmCall& c, int a_table, int w_scale_dtype) {
   using Cfg = GemmA6W4Cfg<MT, 4>;
   const size_t lds = Cfg::lds((int)(c.k / 128));
   if (lds > 160 * 1024) return FPQ_ERR_SHAPE;
-  return with_scale_type(w_scale_dtype, [&](auto tw) {
+  return with_dtype(w_scale_dtype, [&](auto tw) {
     if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_kernel<decltype(tw), MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c);
     return gemm_launch(gemm_a6w4_kernel<decltype(tw), MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c);
   });
@@ -178,8 +169,8 @@ int launch_fp6(const GemmCall& c, XE xe) {
 // ... from the runtime scale dtypes, operand formats (FPQ_E2M3 / FPQ_E3M2 per side) and epilogue of a call
 template <int MT>
 int dispatch_fp6(const GemmCall& c, int a_scale_dtype, int w_scale_dtype, int a_table, int w_table, bool split, const GemmQkNorm* qkn) {
-  return with_scale_type(a_scale_dtype, [&](auto ta) {
-    return with_scale_type(w_scale_dtype, [&](auto tw) {
+  return with_dtype(a_scale_dtype, [&](auto ta) {
+    return with_dtype(w_scale_dtype, [&](auto tw) {
       auto formats = [&](auto fa, auto fb) {
         using Ta = decltype(ta);
         using Tw = decltype(tw);
@@ -196,8 +187,8 @@ int dispatch_fp6(const GemmCall& c, int a_scale_dtype, int w_scale_dtype, int a_
 template <int MT>
 int dispatch_fp8(const GemmCall& c, int a_scale_dtype, int w_scale_dtype) {
   using Cfg = GemmFp8Cfg<MT, 4>;
-  return with_scale_type(a_scale_dtype, [&](auto ta) {
-    return with_scale_type(w_scale_dtype, [&](auto tw) {
+  return with_dtype(a_scale_dtype, [&](auto ta) {
+    return with_dtype(w_scale_dtype, [&](auto tw) {
       return gemm_launch(gemm_fp8_rows_kernel<decltype(ta), decltype(tw), MT, 4>, Cfg::BM, Cfg::BN, 256, Cfg::lds(), c);
     });
   });

@@ -891,51 +891,28 @@ int launch_rows(const void* x, void* out, int64_t rows, int64_t cols, const Fmt&
     const int64_t n_vec = rows * (cols / V);
     const int lpr = (int)(cols / V);
     constexpr int U = 2;
-    auto go = [&](auto kern) {
-      int64_t blocks = (n_vec + (int64_t)kBlock * U - 1) / ((int64_t)kBlock * U);
-      hipLaunchKernelGGL(kern, dim3(grid_for(blocks, 1 << 20)), dim3(kBlock), 0, st, (const u32x4*)x, out, n_vec,
-                         fs, dual);
-      return check_launch();
-    };
-    if (row_bytes <= 1024 && (lpr & (lpr - 1)) == 0) {
-      switch (lpr) {
-        case 1: return go(rows_subwave_kernel<Tin, Tout, 1, DUAL, U>);
-        case 2: return go(rows_subwave_kernel<Tin, Tout, 2, DUAL, U>);
-        case 4: return go(rows_subwave_kernel<Tin, Tout, 4, DUAL, U>);
-        case 8: return go(rows_subwave_kernel<Tin, Tout, 8, DUAL, U>);
-        case 16: return go(rows_subwave_kernel<Tin, Tout, 16, DUAL, U>);
-        case 32: return go(rows_subwave_kernel<Tin, Tout, 32, DUAL, U>);
-        case 64: return go(rows_subwave_kernel<Tin, Tout, 64, DUAL, U>);
-      }
-    }
+    if (row_bytes <= 1024 && (lpr & (lpr - 1)) == 0)   // 1 .. 64 lanes per row: every power of two is in the list
+      return with_int<1, 2, 4, 8, 16, 32, 64>(lpr, [&](auto l) {
+        return launch(rows_subwave_kernel<Tin, Tout, l.value, DUAL, U>, grid_for(tiles_of(n_vec, U), 1 << 20), 0, st, x, out,
+                      n_vec, fs, dual);
+      });
     // the output row must stay 16-byte (f16 out of f32 in: 8-byte) aligned per vector
-    const int64_t vec_per_row = cols / V;
-    const int g = grid_for(rows, 65535);
-    if (vec_per_row <= (int64_t)kBlock * 2)
-      hipLaunchKernelGGL((rows_block_kernel<Tin, Tout, DUAL, 2>), dim3(g), dim3(kBlock), 0, st, (const Tin*)x,
-                         (Tout*)out, rows, cols, fs, dual);
-    else
-      hipLaunchKernelGGL((rows_block_kernel<Tin, Tout, DUAL, 8>), dim3(g), dim3(kBlock), 0, st, (const Tin*)x,
-                         (Tout*)out, rows, cols, fs, dual);
-    return check_launch();
+    return with_int<2, 8>(cols / V <= (int64_t)kBlock * 2 ? 2 : 8, [&](auto c) {
+      return launch(rows_block_kernel<Tin, Tout, DUAL, c.value>, grid_for(rows, 65535), 0, st, x, out, rows, cols, fs, dual);
+    });
   }
-  hipLaunchKernelGGL((rows_scalar_kernel<Tin, Tout, DUAL>), dim3(grid_for(rows, 65535)), dim3(kBlock), 0, st,
-                     (const Tin*)x, (Tout*)out, rows, cols, fs, dual);
-  return check_launch();
+  return launch(rows_scalar_kernel<Tin, Tout, DUAL>, grid_for(rows, 65535), 0, st, x, out, rows, cols, fs, dual);
 }
 
 template <bool DUAL>
 int dispatch_rows(const void* x, void* out, int64_t rows, int64_t cols, int in_dtype, int out_dtype, const Fmt& fs,
                   const DualArgs& dual, hipStream_t st) {
-  if (in_dtype == FPQ_F16 && out_dtype == FPQ_F16)
-    return launch_rows<_Float16, _Float16, DUAL>(x, out, rows, cols, fs, dual, st);
-  if (in_dtype == FPQ_F32 && out_dtype == FPQ_F32)
-    return launch_rows<float, float, DUAL>(x, out, rows, cols, fs, dual, st);
-  if (in_dtype == FPQ_F32 && out_dtype == FPQ_F16)
-    return launch_rows<float, _Float16, DUAL>(x, out, rows, cols, fs, dual, st);
-  if (in_dtype == FPQ_F16 && out_dtype == FPQ_F32)
-    return launch_rows<_Float16, float, DUAL>(x, out, rows, cols, fs, dual, st);
-  return FPQ_ERR_DTYPE;
+  if (!is_f16_or_f32(in_dtype) || !is_f16_or_f32(out_dtype)) return FPQ_ERR_DTYPE;
+  return with_dtype(in_dtype, [&](auto ti) {
+    return with_dtype(out_dtype, [&](auto to) {
+      return launch_rows<decltype(ti), decltype(to), DUAL>(x, out, rows, cols, fs, dual, st);
+    });
+  });
 }
 
 // ---- fast fp16 -> fp16 path (fpq_fast16.h) ------------------------------------------
@@ -954,6 +931,22 @@ inline bool fast16_eligible(const void* x, const void* out, int64_t cols, int in
 // long rows: one workgroup per row, at most 8 vectors (64 halves) per lane in registers
 inline bool fast16_block_eligible(const void* x, const void* out, int64_t cols, int in_dtype, int out_dtype) {
   return fast16_aligned(x, out, cols, in_dtype, out_dtype) && cols / 8 <= (int64_t)kBlock * 8;
+}
+
+// Buckets of a table pair's image, which every workgroup stages in LDS before its first row (fpq_fast16.h): 128 .. 512 for
+// the 4-bit tables, their pairs and E3M2; 1024 for E2M3 and the pairs with E2M3_POS; 2 x 1024 for the pairs with INT_NEG.
+// kBigTab is where the staging starts to count: 1024 buckets are 2 KiB, a quarter of an 8 KiB tile's own bytes, so from
+// there on (>=) the launches below give a workgroup several tiles or rows per staging, and past it (>) the 8 stores per
+// lane want many tiles per workgroup on a capped grid.
+inline int lut16_buckets(const Lut16Host& h) { return 1 << (16 - h.args.shift); }
+constexpr int kBigTab = 1024;
+
+// A table kernel has two forms: the bucket table travels in the kernel arguments (h.tab_valid), or every workgroup
+// evaluates the closed form itself (fpq_fast16.h, lut16_fill).  kern_of(Bool<TAB>{}) names the kernel; its last argument is
+// the table, and its LDS is static (the bucket table lives there).
+template <typename K, typename... A>
+int launch_tab(const Lut16Host& h, K kern_of, dim3 grid, hipStream_t st, const A&... args) {
+  return with_bool(h.tab_valid, [&](auto tab) { return launch(kern_of(tab), grid, 0, st, args..., h.tab); });
 }
 
 // Defaults measured on MI355X with tools/kbench (cold HBM, 4 rotating 252 MB buffer pairs):
@@ -978,27 +971,19 @@ int launch_fast16(const void* x, void* out, int64_t rows, int64_t cols, int neg_
   const int64_t n_vec = rows * (cols / 8);
   const int lpr = (int)(cols / 8);
   const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
-  const int64_t tiles = (n_vec + (int64_t)kBlock * U - 1) / ((int64_t)kBlock * U);
-  auto go = [&](auto kern_tab, auto kern_fill) {
-    if (h.tab_valid)
-      hipLaunchKernelGGL(kern_tab, dim3(grid_for(tiles, grid_cap)), dim3(kBlock), lds, st, (const u32x4*)x,
-                         (u32x4*)out, n_vec, args, h.tab);
-    else
-      hipLaunchKernelGGL(kern_fill, dim3(grid_for(tiles, grid_cap)), dim3(kBlock), lds, st, (const u32x4*)x,
-                         (u32x4*)out, n_vec, args, h.tab);
-    return check_launch();
-  };
+  const dim3 grid(grid_for(tiles_of(n_vec, U), grid_cap));
   // the headline shape - E2M1, groups of 128 - takes its levels from the FP4 conversion hardware (fpq_fast16.h); FPQ_NO_HW4
   // (read at every call: the exhaustive test sweeps both forms in one process) keeps the bucket table
   if constexpr (DUAL) {
     if (gelu) {          // groups of 128, small tables (fpq_gelu_quant_rows_dual checks): GELU in front of the quantizer, one pass
       if (lpr != 16 || clip_absmax) return FPQ_ERR_SHAPE;
-      return go(rows16_lut_subwave_kernel<16, true, U, true, NTL, NTS, false, false, 0, true>,
-                rows16_lut_subwave_kernel<16, true, U, false, NTL, NTS, false, false, 0, true>);
+      return launch_tab(h, [](auto tab) { return rows16_lut_subwave_kernel<16, true, U, tab.value, NTL, NTS, false, false, 0, true>; },
+                        grid, st, x, out, n_vec, args);
     }
     if (clip_absmax) {   // groups of 128 only (fpq_quant_rows_dual checks): the clamping form of the same kernel
       if (lpr != 16) return FPQ_ERR_SHAPE;
-      return go(rows16_lut_subwave_kernel<16, true, U, true, NTL, NTS, false, true>, rows16_lut_subwave_kernel<16, true, U, false, NTL, NTS, false, true>);
+      return launch_tab(h, [](auto tab) { return rows16_lut_subwave_kernel<16, true, U, tab.value, NTL, NTS, false, true>; },
+                        grid, st, x, out, n_vec, args);
     }
   }
   if constexpr (!DUAL) {
@@ -1007,35 +992,27 @@ int launch_fast16(const void* x, void* out, int64_t rows, int64_t cols, int neg_
       // shape of this chip (profiles/r02_copy_persistent_probe.txt: 0.81 against 0.777 for 8 KiB tiles); same-process
       // A/B against U = 2: 77.0 - 77.5 vs 79.0 - 79.4 us in steady state (profiles/r03_headline_u1.txt)
       constexpr int U1 = FPQ_FAST16_HW4_U;
-      const int64_t tiles1 = (n_vec + (int64_t)kBlock * U1 - 1) / ((int64_t)kBlock * U1);
-      hipLaunchKernelGGL((rows16_lut_subwave_kernel<16, false, U1, true, NTL, NTS, true>), dim3(grid_for(tiles1, grid_cap)),
-                         dim3(kBlock), lds, st, (const u32x4*)x, (u32x4*)out, n_vec, args, h.tab);
-      return check_launch();
+      return launch(rows16_lut_subwave_kernel<16, false, U1, true, NTL, NTS, true>, grid_for(tiles_of(n_vec, U1), grid_cap), lds,
+                    st, x, out, n_vec, args, h.tab);
     }
   }
   if constexpr (!DUAL) {
     // E2M3 / E3M2 per group of 128 and per row of 64 (the KV cache's head rows): levels from the FP6 conversion hardware, four
     // vectors per lane = the 32 values of one conversion, full grid (no table to amortise); FPQ_NO_HW6 keeps the table
-    if ((lpr == 16 || lpr == 8) && neg_id == pos_id && (neg_id == FPQ_E2M3 || neg_id == FPQ_E3M2) && !fpq_flag(OPT_FPQ_NO_HW6)) {
-      const int64_t tiles4 = (n_vec + (int64_t)kBlock * 4 - 1) / ((int64_t)kBlock * 4);
-      const dim3 g4(grid_for(tiles4, 1 << 20));
-#define FPQ_HW6_GO(L, H)                                                                                                         \
-  hipLaunchKernelGGL((rows16_lut_subwave_kernel<L, false, 4, true, NTL, NTS, false, false, H>), g4, dim3(kBlock), lds, st,      \
-                     (const u32x4*)x, (u32x4*)out, n_vec, args, h.tab)
-      if (lpr == 16) { if (neg_id == FPQ_E2M3) FPQ_HW6_GO(16, 1); else FPQ_HW6_GO(16, 2); }
-      else { if (neg_id == FPQ_E2M3) FPQ_HW6_GO(8, 1); else FPQ_HW6_GO(8, 2); }
-#undef FPQ_HW6_GO
-      return check_launch();
-    }
+    if ((lpr == 16 || lpr == 8) && neg_id == pos_id && (neg_id == FPQ_E2M3 || neg_id == FPQ_E3M2) && !fpq_flag(OPT_FPQ_NO_HW6))
+      return with_int<8, 16>(lpr, [&](auto l) {
+        constexpr int L = l.value;
+        return with_int<1, 2>(neg_id == FPQ_E2M3 ? 1 : 2, [&](auto hw) {   // the conversion: 1 E2M3, 2 E3M2
+          return launch(rows16_lut_subwave_kernel<L, false, 4, true, NTL, NTS, false, false, hw.value>,
+                        grid_for(tiles_of(n_vec, 4), 1 << 20), lds, st, x, out, n_vec, args, h.tab);
+        });
+      });
   }
-#define FPQ_FAST16_CASE(L) \
-  case L: return go(rows16_lut_subwave_kernel<L, DUAL, U, true, NTL, NTS>, rows16_lut_subwave_kernel<L, DUAL, U, false, NTL, NTS>);
-  switch (lpr) {
-    FPQ_FAST16_CASE(1) FPQ_FAST16_CASE(2) FPQ_FAST16_CASE(4) FPQ_FAST16_CASE(8)
-    FPQ_FAST16_CASE(16) FPQ_FAST16_CASE(32) FPQ_FAST16_CASE(64)
-  }
-#undef FPQ_FAST16_CASE
-  return FPQ_ERR_SHAPE;
+  return with_int<1, 2, 4, 8, 16, 32, 64>(lpr, [&](auto l) {
+    constexpr int L = l.value;
+    return launch_tab(h, [](auto tab) { return rows16_lut_subwave_kernel<L, DUAL, U, tab.value, NTL, NTS>; }, grid, st, x, out,
+                      n_vec, args);
+  });
 }
 
 template <bool DUAL>
@@ -1045,15 +1022,8 @@ int launch_fast16_pair8(const void* x, void* out, int64_t rows, int neg_id, int 
   Lut16Args args = h.args;
   args.nan_flag = nan_flag;
   const int64_t n_vec = rows * 16;   // rows of 128 halves
-  const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
-  const int64_t tiles = (n_vec + (int64_t)kBlock * 2 - 1) / ((int64_t)kBlock * 2);
-  if (h.tab_valid)
-    hipLaunchKernelGGL((rows16_lut_pair_kernel<8, DUAL, true>), dim3(grid_for(tiles, 1 << 20)), dim3(kBlock), lds, st,
-                       (const u32x4*)x, (u32x4*)out, n_vec, args, h.tab);
-  else
-    hipLaunchKernelGGL((rows16_lut_pair_kernel<8, DUAL, false>), dim3(grid_for(tiles, 1 << 20)), dim3(kBlock), lds, st,
-                       (const u32x4*)x, (u32x4*)out, n_vec, args, h.tab);
-  return check_launch();
+  return launch_tab(h, [](auto tab) { return rows16_lut_pair_kernel<8, DUAL, tab.value>; }, grid_for(tiles_of(n_vec, 2), 1 << 20),
+                    st, x, out, n_vec, args);
 }
 
 template <bool DUAL>
@@ -1072,28 +1042,26 @@ int launch_fast16_block(const void* x, void* out, int64_t rows, int64_t cols, in
     int64_t g = (rows + 3) / 4;
     const int64_t capw = h.tab_valid ? 16384 : 2048;
     if (g > capw) g = capw;
-#define FPQ_WAVE(M) do { if (h.tab_valid) hipLaunchKernelGGL((rows16_lut_wave_kernel<DUAL, M, true>), dim3((unsigned)g), dim3(kBlock), lds, st, (const uint16_t*)x, (uint16_t*)out, rows, cols, args, h.tab); \
-                         else hipLaunchKernelGGL((rows16_lut_wave_kernel<DUAL, M, false>), dim3((unsigned)g), dim3(kBlock), lds, st, (const uint16_t*)x, (uint16_t*)out, rows, cols, args, h.tab); } while (0)
     // rows of four or five vectors per lane on E2M3 / E3M2 (per-token FP6 at C = 1920, 2048, 2304): levels from the FP6
     // conversion hardware, no table (fpq_fast16.h, fp6_levels_hw32); FPQ_NO_HW6 (read at every call) keeps the table
     if constexpr (!DUAL) {
       if ((mc == 4 || mc == 5) && neg_id == pos_id && (neg_id == FPQ_E2M3 || neg_id == FPQ_E3M2) && !fpq_flag(OPT_FPQ_NO_HW6)) {
         int64_t g6 = (rows + 3) / 4;
         if (g6 > (1 << 20)) g6 = 1 << 20;   // nothing to amortise: one pass of four rows per workgroup
-#define FPQ_WAVE6(M, H) hipLaunchKernelGGL((rows16_lut_wave_kernel<false, M, true, H>), dim3((unsigned)g6), dim3(kBlock), lds, st, \
-                                           (const uint16_t*)x, (uint16_t*)out, rows, cols, args, h.tab)
-        if (mc == 4) { if (neg_id == FPQ_E2M3) FPQ_WAVE6(4, 1); else FPQ_WAVE6(4, 2); }
-        else { if (neg_id == FPQ_E2M3) FPQ_WAVE6(5, 1); else FPQ_WAVE6(5, 2); }
-#undef FPQ_WAVE6
-        return check_launch();
+        return with_int<4, 5>(mc, [&](auto m) {
+          constexpr int M = m.value;
+          return with_int<1, 2>(neg_id == FPQ_E2M3 ? 1 : 2, [&](auto hw) {   // the conversion: 1 E2M3, 2 E3M2
+            return launch(rows16_lut_wave_kernel<false, M, true, hw.value>, (unsigned)g6, lds, st, x, out, rows, cols, args,
+                          h.tab);
+          });
+        });
       }
     }
-    if (mc <= 1) FPQ_WAVE(1);
-    else if (mc <= 2) FPQ_WAVE(2);
-    else if (mc <= 4) FPQ_WAVE(4);
-    else FPQ_WAVE(5);
-#undef FPQ_WAVE
-    return check_launch();
+    return with_int<1, 2, 4, 5>(step_for(mc, {1, 2, 4, 5}), [&](auto m) {
+      constexpr int M = m.value;
+      return launch_tab(h, [](auto tab) { return rows16_lut_wave_kernel<DUAL, M, tab.value>; }, (unsigned)g, st, x, out, rows, cols,
+                        args);
+    });
   }
   const int maxc = (int)((vec_per_row + kBlock - 1) / kBlock);
   // enough workgroups to fill the chip several times over, each walking consecutive rows
@@ -1103,34 +1071,21 @@ int launch_fast16_block(const void* x, void* out, int64_t rows, int64_t cols, in
   const int64_t target_wgs = h.tab_valid ? (1 << 20) : 2048;
   int64_t rpb = (rows + target_wgs - 1) / target_wgs;
   if (rpb < 1) rpb = 1;
-  if (h.tab_valid && (1 << (16 - h.args.shift)) >= 1024) {   // 2 x 512 (E2M3: [16384 x 7680] 86.3 -> 83.4 us) or 2 x 1024 buckets to stage: two rows per workgroup
+  if (h.tab_valid && lut16_buckets(h) >= kBigTab) {   // 2 x 512 (E2M3: [16384 x 7680] 86.3 -> 83.4 us) or 2 x 1024 buckets to stage: two rows per workgroup
     rpb = fpq_opt(OPT_FPQ_BIGTAB_RPB, 2);
     if (rpb < 1) rpb = 1;
   }
-  const int64_t grid = (rows + rpb - 1) / rpb;
-  auto go = [&](auto kern_tab, auto kern_fill) {
-    if (h.tab_valid)
-      hipLaunchKernelGGL(kern_tab, dim3((unsigned)grid), dim3(kBlock), lds, st, (const uint16_t*)x, (uint16_t*)out,
-                         rows, cols, rpb, args, h.tab);
-    else
-      hipLaunchKernelGGL(kern_fill, dim3((unsigned)grid), dim3(kBlock), lds, st, (const uint16_t*)x,
-                         (uint16_t*)out, rows, cols, rpb, args, h.tab);
-    return check_launch();
-  };
-  if constexpr (DUAL) {
-    if (gelu) {   // GELU in front of the quantizer (fpq_gelu_quant_rows_dual): one workgroup per row for every row length
-      if (maxc <= 1) return go(rows16_lut_block_kernel<true, 1, true, true>, rows16_lut_block_kernel<true, 1, false, true>);
-      if (maxc <= 2) return go(rows16_lut_block_kernel<true, 2, true, true>, rows16_lut_block_kernel<true, 2, false, true>);
-      if (maxc <= 4) return go(rows16_lut_block_kernel<true, 4, true, true>, rows16_lut_block_kernel<true, 4, false, true>);
-      if (maxc <= 5) return go(rows16_lut_block_kernel<true, 5, true, true>, rows16_lut_block_kernel<true, 5, false, true>);
-      return go(rows16_lut_block_kernel<true, 8, true, true>, rows16_lut_block_kernel<true, 8, false, true>);
+  const dim3 grid((unsigned)((rows + rpb - 1) / rpb));
+  return with_int<1, 2, 4, 5, 8>(step_for(maxc, {1, 2, 4, 5, 8}), [&](auto c) {
+    constexpr int C = c.value;
+    if constexpr (DUAL) {
+      if (gelu)   // GELU in front of the quantizer (fpq_gelu_quant_rows_dual): one workgroup per row for every row length
+        return launch_tab(h, [](auto tab) { return rows16_lut_block_kernel<true, C, tab.value, true>; }, grid, st, x, out, rows,
+                          cols, rpb, args);
     }
-  }
-  if (maxc <= 1) return go(rows16_lut_block_kernel<DUAL, 1, true>, rows16_lut_block_kernel<DUAL, 1, false>);
-  if (maxc <= 2) return go(rows16_lut_block_kernel<DUAL, 2, true>, rows16_lut_block_kernel<DUAL, 2, false>);
-  if (maxc <= 4) return go(rows16_lut_block_kernel<DUAL, 4, true>, rows16_lut_block_kernel<DUAL, 4, false>);
-  if (maxc <= 5) return go(rows16_lut_block_kernel<DUAL, 5, true>, rows16_lut_block_kernel<DUAL, 5, false>);
-  return go(rows16_lut_block_kernel<DUAL, 8, true>, rows16_lut_block_kernel<DUAL, 8, false>);
+    return launch_tab(h, [](auto tab) { return rows16_lut_block_kernel<DUAL, C, tab.value>; }, grid, st, x, out, rows, cols, rpb,
+                      args);
+  });
 }
 
 // ---- fp32 rows of 128 (weights): fpq_fast32.h -------------------------------------------------
@@ -1143,28 +1098,24 @@ inline bool fast32_eligible(const void* x, const void* out, int64_t cols, int in
 inline int launch_fast32(const Seg32* segs, int n_segs, const Seg32& one, int64_t max_rows, int table_id, int out_dtype,
                          hipStream_t st) {
   constexpr int U = 4;
-  const Lut32Args a = lut32_args(table_id);
-  const int64_t tiles = (max_rows * 32 + (int64_t)kBlock * U - 1) / ((int64_t)kBlock * U);
+  const int64_t tiles = tiles_of(max_rows * 32, U);
   if (tiles > 0x7FFFFFFF || n_segs > 65535) return FPQ_ERR_SHAPE;
   const dim3 grid((unsigned)tiles, (unsigned)n_segs);
-  if (out_dtype == FPQ_F16)
-    hipLaunchKernelGGL((groups32_lut_kernel<_Float16, U>), grid, dim3(kBlock), 0, st, segs, one, a);
-  else
-    hipLaunchKernelGGL((groups32_lut_kernel<float, U>), grid, dim3(kBlock), 0, st, segs, one, a);
-  return check_launch();
+  return with_dtype(out_dtype, [&](auto to) {
+    return launch(groups32_lut_kernel<decltype(to), U>, grid, 0, st, segs, one, lut32_args(table_id));
+  });
 }
 
 // fp32 groups of 128 -> codes + fp32 scales: one tensor (segs == nullptr) or a device-resident segment table
 inline int launch_codes32(const CodesSeg32* segs, int n_segs, const CodesSeg32& one, int64_t max_rows, int table_id, bool pack,
                           hipStream_t st) {
   constexpr int U = 4;
-  const Lut32Args a = lut32_args(table_id);
-  const int64_t tiles = (max_rows * 32 + (int64_t)kBlock * U - 1) / ((int64_t)kBlock * U);
+  const int64_t tiles = tiles_of(max_rows * 32, U);
   if (tiles > 0x7FFFFFFF || n_segs > 65535) return FPQ_ERR_SHAPE;
   const dim3 grid((unsigned)tiles, (unsigned)n_segs);
-  if (pack) hipLaunchKernelGGL((groups32_codes_kernel<true, U>), grid, dim3(kBlock), 0, st, segs, one, a);
-  else hipLaunchKernelGGL((groups32_codes_kernel<false, U>), grid, dim3(kBlock), 0, st, segs, one, a);
-  return check_launch();
+  return with_bool(pack, [&](auto pk) {
+    return launch(groups32_codes_kernel<pk.value, U>, grid, 0, st, segs, one, lut32_args(table_id));
+  });
 }
 
 // long fp32 rows (per-channel weights): one wavefront or one workgroup per row (fpq_fast32.h)
@@ -1175,24 +1126,40 @@ inline bool rows32_eligible(const void* x, const void* out, int64_t cols, int in
 
 template <typename Tout>
 int launch_rows32(const void* x, void* out, int64_t rows, int64_t cols, int table_id, hipStream_t st) {
-  const Lut32Args a = lut32_args(table_id);
   const int64_t vpr = cols / 4;
-#define FPQ_R32(L, M)                                                                                              \
-  do {                                                                                                             \
-    const int64_t wgs = (rows + (kBlock / L) - 1) / (kBlock / L);                                                  \
-    hipLaunchKernelGGL((rows32_lut_kernel<Tout, L, M>), dim3(grid_for(wgs, 1 << 16)), dim3(kBlock), 0, st,        \
-                       (const float*)x, (Tout*)out, rows, cols, a);                                               \
-    return check_launch();                                                                                         \
-  } while (0)
-  if (vpr <= 64 * 2) FPQ_R32(64, 2);
-  if (vpr <= 64 * 4) FPQ_R32(64, 4);
-  if (vpr <= 64 * 8) FPQ_R32(64, 8);
-  if (vpr <= 256 * 3) FPQ_R32(256, 3);
-  if (vpr <= 256 * 4) FPQ_R32(256, 4);
-  if (vpr <= 256 * 6) FPQ_R32(256, 6);
-  if (vpr <= 256 * 8) FPQ_R32(256, 8);
-  FPQ_R32(256, 10);
-#undef FPQ_R32
+  auto go = [&](auto lanes, auto m) {   // lanes per row, vectors per lane
+    constexpr int L = lanes.value;
+    const int64_t wgs = (rows + (kBlock / L) - 1) / (kBlock / L);
+    return launch(rows32_lut_kernel<Tout, L, m.value>, grid_for(wgs, 1 << 16), 0, st, x, out, rows, cols, lut32_args(table_id));
+  };
+  if (vpr <= 64 * 2) return go(Int<64>{}, Int<2>{});
+  if (vpr <= 64 * 4) return go(Int<64>{}, Int<4>{});
+  if (vpr <= 64 * 8) return go(Int<64>{}, Int<8>{});
+  if (vpr <= 256 * 3) return go(Int<256>{}, Int<3>{});
+  if (vpr <= 256 * 4) return go(Int<256>{}, Int<4>{});
+  if (vpr <= 256 * 6) return go(Int<256>{}, Int<6>{});
+  if (vpr <= 256 * 8) return go(Int<256>{}, Int<8>{});
+  return go(Int<256>{}, Int<10>{});
+}
+
+template <typename T>
+int launch_negrev(const void* x, void* out, int64_t rows, int64_t cols, const Fmt& fs, hipStream_t st) {
+  constexpr int V = DT<T>::kVec;
+  constexpr int U = 2;
+  const bool aligned = (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
+  const int64_t lpr = cols / V;
+  if (aligned && cols % V == 0 && lpr <= 64 && (lpr & (lpr - 1)) == 0) {   // 1 .. 64 lanes per row: every power of two is in the list
+    const int64_t n_vec = rows * lpr;
+    return with_int<1, 2, 4, 8, 16, 32, 64>((int)lpr, [&](auto l) {
+      return launch(rows_negrev_subwave_kernel<T, l.value, U>, grid_for(tiles_of(n_vec, U), 1 << 20), 0, st, x, out, n_vec, fs);
+    });
+  }
+  return launch(rows_negrev_scalar_kernel<T>, grid_for(rows, 65535), 0, st, x, out, rows, cols, fs);
+}
+
+// the tail of the dual quantizers that were given a NaN flag: any NaN in the input => the whole result is zero
+inline int zero_if_flag(void* out, int64_t n_bytes, void* flag, hipStream_t st) {
+  return launch(zero_if_flag_kernel, kFixupBlocks, 0, st, out, n_bytes, flag);
 }
 
 }  // namespace
@@ -1200,42 +1167,12 @@ int launch_rows32(const void* x, void* out, int64_t rows, int64_t cols, int tabl
 // =================================================================================
 // C ABI
 // =================================================================================
-template <typename T>
-int launch_negrev(const void* x, void* out, int64_t rows, int64_t cols, const Fmt& fs, hipStream_t st) {
-  constexpr int V = DT<T>::kVec;
-  constexpr int U = 2;
-  const bool aligned = (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
-  const int64_t lpr = cols / V;
-  if (aligned && cols % V == 0 && lpr <= 64 && (lpr & (lpr - 1)) == 0) {
-    const int64_t n_vec = rows * lpr;
-    auto go = [&](auto kern) {
-      int64_t blocks = (n_vec + (int64_t)kBlock * U - 1) / ((int64_t)kBlock * U);
-      hipLaunchKernelGGL(kern, dim3(grid_for(blocks, 1 << 20)), dim3(kBlock), 0, st, (const u32x4*)x, (u32x4*)out,
-                         n_vec, fs);
-      return check_launch();
-    };
-    switch ((int)lpr) {
-      case 1: return go(rows_negrev_subwave_kernel<T, 1, U>);
-      case 2: return go(rows_negrev_subwave_kernel<T, 2, U>);
-      case 4: return go(rows_negrev_subwave_kernel<T, 4, U>);
-      case 8: return go(rows_negrev_subwave_kernel<T, 8, U>);
-      case 16: return go(rows_negrev_subwave_kernel<T, 16, U>);
-      case 32: return go(rows_negrev_subwave_kernel<T, 32, U>);
-      case 64: return go(rows_negrev_subwave_kernel<T, 64, U>);
-    }
-  }
-  hipLaunchKernelGGL((rows_negrev_scalar_kernel<T>), dim3(grid_for(rows, 65535)), dim3(kBlock), 0, st, (const T*)x,
-                     (T*)out, rows, cols, fs);
-  return check_launch();
-}
-
 extern "C" {
 
 int fpq_version(void) { return FPQ_VERSION; }
 
 int fpq_internal_zero_if_flag(void* out, int64_t n_bytes, void* scratch, void* stream) {
-  hipLaunchKernelGGL(zero_if_flag_kernel, dim3(kFixupBlocks), dim3(kBlock), 0, (hipStream_t)stream, (uint8_t*)out, n_bytes, (uint32_t*)scratch);
-  return check_launch();
+  return zero_if_flag(out, n_bytes, scratch, (hipStream_t)stream);
 }
 
 int fpq_set_option(const char* name, int value) {
@@ -1311,30 +1248,21 @@ int fpq_quant_nearest(const void* x, const float* table, void* z, int64_t n, int
   if (n == 0) return FPQ_OK;
   if (!x || !table || !z) return FPQ_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  int g = grid_for((n + kBlock - 1) / kBlock);
   if (dtype == FPQ_F32)
-    hipLaunchKernelGGL(nearest_scan_kernel<float>, dim3(grid_for((n / 4 + 2 * kBlock - 1) / (2 * kBlock) + 1, 4096)),
-                       dim3(kBlock), 0, st, (const float*)x, table, (float*)z, n, k, known_tables());
-  else
-    hipLaunchKernelGGL(nearest_scan_kernel<double>, dim3(g), dim3(kBlock), 0, st, (const double*)x, table,
-                       (double*)z, n, k, known_tables());
-  return check_launch();
+    return launch(nearest_scan_kernel<float>, grid_for(tiles_of(n / 4, 2) + 1, 4096), 0, st, x, table, z, n, k, known_tables());
+  return launch(nearest_scan_kernel<double>, grid_for(tiles_of(n, 1)), 0, st, x, table, z, n, k, known_tables());
 }
 
 int fpq_quant_nearest_argmin(const void* x, const float* table, float* z, int64_t n, int k, int dtype,
                              fpq_stream_t stream) {
   if (n < 0) return FPQ_ERR_ARG;
   if (k < 1 || k > 256) return FPQ_ERR_SHAPE;
-  if (dtype != FPQ_F16 && dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_f16_or_f32(dtype)) return FPQ_ERR_DTYPE;
   if (n == 0) return FPQ_OK;
   if (!x || !table || !z) return FPQ_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = grid_for((n + kBlock - 1) / kBlock, 8192);
-  if (dtype == FPQ_F32)
-    hipLaunchKernelGGL(nearest_argmin_kernel<float>, dim3(g), dim3(kBlock), 0, st, (const float*)x, table, z, n, k);
-  else
-    hipLaunchKernelGGL(nearest_argmin_kernel<_Float16>, dim3(g), dim3(kBlock), 0, st, (const _Float16*)x, table, z, n, k);
-  return check_launch();
+  return with_dtype(dtype, [&](auto t) {
+    return launch(nearest_argmin_kernel<decltype(t)>, grid_for(tiles_of(n, 1), 8192), 0, (hipStream_t)stream, x, table, z, n, k);
+  });
 }
 
 int fpq_quant_nearest_builtin(const float* x, float* z, int64_t n, int table_id, fpq_stream_t stream) {
@@ -1343,17 +1271,14 @@ int fpq_quant_nearest_builtin(const float* x, float* z, int64_t n, int table_id,
   if (n == 0) return FPQ_OK;
   if (!x || !z) return FPQ_ERR_ARG;
   int side = kTables[table_id].symmetric ? 0 : ((table_id == FPQ_E1M2_NEG || table_id == FPQ_INT_NEG || table_id == FPQ_E2M1_NEG) ? 1 : 2);
-  hipLaunchKernelGGL(nearest_builtin_kernel, dim3(grid_for((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     (hipStream_t)stream, x, z, n, make_fmt(table_id), side);
-  return check_launch();
+  return launch(nearest_builtin_kernel, grid_for(tiles_of(n, 1)), 0, (hipStream_t)stream, x, z, n, make_fmt(table_id), side);
 }
 
 int fpq_quant_rows(const void* x, void* out, int64_t rows, int64_t cols, int table_id, int in_dtype, int out_dtype,
                    fpq_stream_t stream) {
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if ((in_dtype != FPQ_F16 && in_dtype != FPQ_F32) || (out_dtype != FPQ_F16 && out_dtype != FPQ_F32))
-    return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype) || !is_f16_or_f32(out_dtype)) return FPQ_ERR_DTYPE;
   if (rows == 0 || cols == 0) return FPQ_OK;
   if (!x || !out) return FPQ_ERR_ARG;
   if (fast16_eligible(x, out, cols, in_dtype, out_dtype)) {
@@ -1361,7 +1286,7 @@ int fpq_quant_rows(const void* x, void* out, int64_t rows, int64_t cols, int tab
     // 16384 workgroups, so that at the large shapes every workgroup stages once for two tiles or more - E2M3 g = 128 and
     // KV rows of 64 at [65536 x 1920]: 84.2 -> 80.8 us (caps 10240 .. 24576: 82.3 .. 80.6; U = 4 and U = 1 are slower,
     // profiles/r03_e2m3_grid.txt)
-    const int cap = (1 << (16 - lut16_host(table_id, table_id).args.shift)) >= 1024 ? 16384 : 1 << 20;
+    const int cap = lut16_buckets(lut16_host(table_id, table_id)) >= kBigTab ? 16384 : 1 << 20;
     return launch_fast16<false>(x, out, rows, cols, table_id, table_id, (hipStream_t)stream, cap);
   }
   if (fast16_block_eligible(x, out, cols, in_dtype, out_dtype))
@@ -1371,8 +1296,7 @@ int fpq_quant_rows(const void* x, void* out, int64_t rows, int64_t cols, int tab
     return launch_fast32(nullptr, 1, one, rows, table_id, out_dtype, (hipStream_t)stream);
   }
   if (rows32_eligible(x, out, cols, in_dtype, table_id))
-    return out_dtype == FPQ_F16 ? launch_rows32<_Float16>(x, out, rows, cols, table_id, (hipStream_t)stream)
-                                : launch_rows32<float>(x, out, rows, cols, table_id, (hipStream_t)stream);
+    return with_dtype(out_dtype, [&](auto to) { return launch_rows32<decltype(to)>(x, out, rows, cols, table_id, (hipStream_t)stream); });
   DualArgs dual = {};
   dual.nan_flag = nullptr;
   return dispatch_rows<false>(x, out, rows, cols, in_dtype, out_dtype, make_fmt(table_id), dual,
@@ -1382,8 +1306,8 @@ int fpq_quant_rows(const void* x, void* out, int64_t rows, int64_t cols, int tab
 int fpq_quant_rows_multi(const fpq_segment_t* segments_host, int n_segments, int64_t cols, int table_id, int in_dtype,
                          int out_dtype, fpq_stream_t stream) {
   if (n_segments < 0 || cols < 0 || (n_segments > 0 && !segments_host)) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if ((in_dtype != FPQ_F16 && in_dtype != FPQ_F32) || (out_dtype != FPQ_F16 && out_dtype != FPQ_F32)) return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype) || !is_f16_or_f32(out_dtype)) return FPQ_ERR_DTYPE;
   for (int i = 0; i < n_segments; ++i) {
     if (segments_host[i].rows < 0) return FPQ_ERR_ARG;
     if (segments_host[i].rows > 0 && cols > 0 && (!segments_host[i].x || !segments_host[i].out)) return FPQ_ERR_ARG;
@@ -1414,24 +1338,20 @@ int fpq_quant_rows_multi(const fpq_segment_t* segments_host, int n_segments, int
     m.n_vec[i] = segments_host[i].rows * lpr;
   }
   const Lut16Host& h = lut16_host(table_id, table_id);
-  const int64_t tiles = (max_vec + (int64_t)kBlock * U - 1) / ((int64_t)kBlock * U);
+  const int64_t tiles = tiles_of(max_vec, U);
   if (tiles > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
   const dim3 grid((unsigned)tiles, (unsigned)n_segments);
-#define FPQ_MULTI_CASE(L) \
-  case L: hipLaunchKernelGGL((rows16_lut_multi_kernel<L, U>), grid, dim3(kBlock), 0, st, m, h.args, h.tab); break;
-  switch ((int)lpr) {
-    FPQ_MULTI_CASE(1) FPQ_MULTI_CASE(2) FPQ_MULTI_CASE(4) FPQ_MULTI_CASE(8) FPQ_MULTI_CASE(16) FPQ_MULTI_CASE(32) FPQ_MULTI_CASE(64)
-  }
-#undef FPQ_MULTI_CASE
-  return check_launch();
+  return with_int<1, 2, 4, 8, 16, 32, 64>((int)lpr, [&](auto l) {
+    return launch(rows16_lut_multi_kernel<l.value, U>, grid, 0, st, m, h.args, h.tab);
+  });
 }
 
 int fpq_quant_rows_segments(const fpq_segment_t* segments_device, int n_segments, int64_t max_rows, int64_t cols,
                             int table_id, int in_dtype, int out_dtype, fpq_stream_t stream) {
   static_assert(sizeof(fpq_segment_t) == sizeof(Seg32), "fpq_segment_t and the kernels' Seg32 share one layout");
   if (n_segments < 0 || max_rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if (in_dtype != FPQ_F32 || (out_dtype != FPQ_F16 && out_dtype != FPQ_F32)) return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (in_dtype != FPQ_F32 || !is_f16_or_f32(out_dtype)) return FPQ_ERR_DTYPE;
   if (cols != 128) return FPQ_ERR_SHAPE;
   if (n_segments == 0 || max_rows == 0) return FPQ_OK;
   if (!segments_device || (((uintptr_t)segments_device) & 7) != 0) return FPQ_ERR_ARG;
@@ -1445,7 +1365,7 @@ static int kv_cache_step_impl(void* cache, int64_t batch, int64_t max_len, int64
                               int64_t new_token_pitch, int64_t new_start, int64_t n_new, int64_t group, int table_id,
                               fpq_stream_t stream, const KvStepQkn* qn) {
   if (batch < 0 || max_len < 0 || row_elems <= 0 || n_new < 0) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
   if (quant_start < 0 || quant_stop < quant_start || new_start < quant_stop || new_start + n_new > max_len)
     return FPQ_ERR_ARG;
   if (group != 8 && group != 16 && group != 32 && group != 64 && group != 128 && group != 256 && group != 512)
@@ -1466,31 +1386,26 @@ static int kv_cache_step_impl(void* cache, int64_t batch, int64_t max_len, int64
   k.batch = (int)batch;
   k.q_first_vec = quant_start * k.row_vec;
   k.q_vecs = n_quant * k.row_vec;
-  const int64_t q_tiles = (k.q_vecs + kBlock * U - 1) / (kBlock * U);
+  const int64_t q_tiles = tiles_of(k.q_vecs, U);
   k.src[0] = (const uint16_t*)new_k;
   k.src[1] = (const uint16_t*)new_v;
   k.src_batch_pitch = new_batch_pitch;
   k.src_token_pitch = new_token_pitch;
   k.new_first_vec = new_start * k.row_vec;
   k.new_vecs = n_new * k.row_vec;
-  const int64_t c_tiles = (k.new_vecs + kBlock * U - 1) / (kBlock * U);
+  const int64_t c_tiles = tiles_of(k.new_vecs, U);
   if (q_tiles + c_tiles > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
   k.q_tiles = (int)q_tiles;
   const dim3 grid((unsigned)(q_tiles + c_tiles), (unsigned)batch, qn ? 3 : 2);
   const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
   hipStream_t st = (hipStream_t)stream;
-  if (qn) {
-    if (group == 64) hipLaunchKernelGGL((kv16_step_qkn_kernel<8, U>), grid, dim3(kBlock), lds, st, k, *qn, h.args, h.tab);
-    else hipLaunchKernelGGL((kv16_step_qkn_kernel<16, U>), grid, dim3(kBlock), lds, st, k, *qn, h.args, h.tab);
-    return check_launch();
-  }
-#define FPQ_KV_CASE(L) \
-  case L: hipLaunchKernelGGL((kv16_step_kernel<L, U>), grid, dim3(kBlock), lds, st, k, h.args, h.tab); break;
-  switch ((int)(group / 8)) {
-    FPQ_KV_CASE(1) FPQ_KV_CASE(2) FPQ_KV_CASE(4) FPQ_KV_CASE(8) FPQ_KV_CASE(16) FPQ_KV_CASE(32) FPQ_KV_CASE(64)
-  }
-#undef FPQ_KV_CASE
-  return check_launch();
+  if (qn)   // groups of 64 or 128 (fpq_kv_cache_step_qknorm checks)
+    return with_int<8, 16>((int)(group / 8), [&](auto l) {
+      return launch(kv16_step_qkn_kernel<l.value, U>, grid, lds, st, k, *qn, h.args, h.tab);
+    });
+  return with_int<1, 2, 4, 8, 16, 32, 64>((int)(group / 8), [&](auto l) {
+    return launch(kv16_step_kernel<l.value, U>, grid, lds, st, k, h.args, h.tab);
+  });
 }
 
 int fpq_kv_cache_step(void* cache, int64_t batch, int64_t max_len, int64_t row_elems, int64_t quant_start,
@@ -1521,8 +1436,8 @@ int fpq_kv_cache_step_qknorm(void* cache, int64_t batch, int64_t max_len, int64_
 int fpq_quant_rows_argmin(const void* x, float* out, int64_t rows, int64_t cols, int table_id, int in_dtype,
                           int clamp3, fpq_stream_t stream) {
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
   if (rows == 0 || cols == 0) return FPQ_OK;
   if (!x || !out) return FPQ_ERR_ARG;
   Fmt f = make_fmt(table_id);
@@ -1537,17 +1452,15 @@ int fpq_quant_rows_dual(const void* x, void* out, int64_t rows, int64_t cols, in
                         int in_dtype, int out_dtype, const void* clip_absmax, float clip_strength, void* nan_flag,
                         fpq_stream_t stream) {
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (neg_table != FPQ_E1M2_NEG && neg_table != FPQ_INT_NEG && neg_table != FPQ_E2M1_NEG) return FPQ_ERR_TABLE;
-  if (pos_table != FPQ_E2M1_POS && pos_table != FPQ_E2M3_POS) return FPQ_ERR_TABLE;
-  if ((in_dtype != FPQ_F16 && in_dtype != FPQ_F32) || (out_dtype != FPQ_F16 && out_dtype != FPQ_F32))
-    return FPQ_ERR_DTYPE;
+  if (!is_dual_pair(neg_table, pos_table)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype) || !is_f16_or_f32(out_dtype)) return FPQ_ERR_DTYPE;
   if (rows == 0 || cols == 0) return FPQ_OK;
   if (!x || !out) return FPQ_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   uint32_t* flag = (uint32_t*)nan_flag;
   if (flag && (((uintptr_t)flag) & 7) != 0) return FPQ_ERR_ARG;
   int rc;
-  const bool bigtab = (1 << (16 - lut16_host(neg_table, pos_table).args.shift)) > 1024;
+  const bool bigtab = lut16_buckets(lut16_host(neg_table, pos_table)) > kBigTab;
   if (clip_absmax && clip_strength >= 0.0f && cols == 128 && !bigtab && fast16_eligible(x, out, cols, in_dtype, out_dtype)) {
     // the global clamp on the fast path (fp16 groups of 128, strength >= 0; anything else below, through the generic kernel)
     rc = launch_fast16<true>(x, out, rows, cols, neg_table, pos_table, st, 1 << 20, flag, clip_absmax, clip_strength);
@@ -1556,7 +1469,7 @@ int fpq_quant_rows_dual(const void* x, void* out, int64_t rows, int64_t cols, in
     // evaluates it once, so give each workgroup many tiles (measured: 88 us vs 127 us with a full grid)
     // tables of 2 x 1024 buckets (int_neg / e2m3_pos) cost a workgroup 8 stores per lane to stage: give each
     // workgroup many tiles (capped grid, U = 4); the smaller ones run one tile per workgroup on a full grid
-    if ((1 << (16 - lut16_host(neg_table, pos_table).args.shift)) <= 1024)
+    if (lut16_buckets(lut16_host(neg_table, pos_table)) <= kBigTab)
       rc = launch_fast16<true>(x, out, rows, cols, neg_table, pos_table, st, 1 << 20, flag);
     else {
       const int cap = fpq_opt(OPT_FPQ_BIGTAB_CAP, 16384);   // measured on [65536 x 7680]: 4096 -> 366 us, 16384 -> 348 us, full grid -> 367 us
@@ -1574,16 +1487,13 @@ int fpq_quant_rows_dual(const void* x, void* out, int64_t rows, int64_t cols, in
     rc = dispatch_rows<true>(x, out, rows, cols, in_dtype, out_dtype, dual.fneg, dual, st);
   }
   if (rc != FPQ_OK || !flag) return rc;
-  const int64_t n_bytes = rows * cols * (out_dtype == FPQ_F16 ? 2 : 4);
-  hipLaunchKernelGGL(zero_if_flag_kernel, dim3(kFixupBlocks), dim3(kBlock), 0, st, (uint8_t*)out, n_bytes, flag);
-  return check_launch();
+  return zero_if_flag(out, rows * cols * (out_dtype == FPQ_F16 ? 2 : 4), flag, st);
 }
 
 int fpq_gelu_quant_rows_dual(const void* x, void* out, void* gelu_out, int64_t rows, int64_t cols, int neg_table, int pos_table,
                              void* nan_flag, fpq_stream_t stream) {
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (neg_table != FPQ_E1M2_NEG && neg_table != FPQ_INT_NEG && neg_table != FPQ_E2M1_NEG) return FPQ_ERR_TABLE;
-  if (pos_table != FPQ_E2M1_POS && pos_table != FPQ_E2M3_POS) return FPQ_ERR_TABLE;
+  if (!is_dual_pair(neg_table, pos_table)) return FPQ_ERR_TABLE;
   // groups of 128 (rows inside a wavefront) or rows of at most 16384 elements (one workgroup per row: the per-token forms)
   if (cols <= 0 || cols % 8 != 0 || cols > 8 * 8 * kBlock) return FPQ_ERR_SHAPE;
   if (rows == 0) return FPQ_OK;
@@ -1594,33 +1504,29 @@ int fpq_gelu_quant_rows_dual(const void* x, void* out, void* gelu_out, int64_t r
   int rc;
   if (cols != 128)
     rc = launch_fast16_block<true>(x, out, rows, cols, neg_table, pos_table, st, flag, true, gelu_out);
-  else if ((1 << (16 - lut16_host(neg_table, pos_table).args.shift)) <= 1024)
+  else if (lut16_buckets(lut16_host(neg_table, pos_table)) <= kBigTab)
     rc = launch_fast16<true>(x, out, rows, cols, neg_table, pos_table, st, 1 << 20, flag, nullptr, 1.0f, true, gelu_out);
   else   // int_neg / e2m3_pos: 2 x 1024 buckets to stage per workgroup - many tiles per workgroup, as fpq_quant_rows_dual
     rc = launch_fast16<true, 4>(x, out, rows, cols, neg_table, pos_table, st, fpq_opt(OPT_FPQ_BIGTAB_CAP, 16384), flag, nullptr, 1.0f, true, gelu_out);
-  if (rc != FPQ_OK) return rc;
-  if (!nan_flag) return FPQ_OK;
-  hipLaunchKernelGGL(zero_if_flag_kernel, dim3(kFixupBlocks), dim3(kBlock), 0, st, (uint8_t*)out, rows * cols * 2, (uint32_t*)nan_flag);
-  return check_launch();
+  if (rc != FPQ_OK || !flag) return rc;
+  return zero_if_flag(out, rows * cols * 2, flag, st);
 }
 
 int fpq_quant_rows_neg_reverse(const void* x, void* out, int64_t rows, int64_t cols, int table_id, int dtype,
                                fpq_stream_t stream) {
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if (dtype != FPQ_F16 && dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(dtype)) return FPQ_ERR_DTYPE;
   if (rows == 0 || cols == 0) return FPQ_OK;
   if (!x || !out) return FPQ_ERR_ARG;
-  if (dtype == FPQ_F16) return launch_negrev<_Float16>(x, out, rows, cols, make_fmt(table_id), (hipStream_t)stream);
-  return launch_negrev<float>(x, out, rows, cols, make_fmt(table_id), (hipStream_t)stream);
+  return with_dtype(dtype, [&](auto t) { return launch_negrev<decltype(t)>(x, out, rows, cols, make_fmt(table_id), (hipStream_t)stream); });
 }
 
 int fpq_quant_rows_dual_argmin(const void* x, float* out, int64_t rows, int64_t cols, int neg_table, int pos_table,
                                int in_dtype, const void* clip_absmax, float clip_strength, fpq_stream_t stream) {
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (neg_table != FPQ_E1M2_NEG && neg_table != FPQ_INT_NEG && neg_table != FPQ_E2M1_NEG) return FPQ_ERR_TABLE;
-  if (pos_table != FPQ_E2M1_POS && pos_table != FPQ_E2M3_POS) return FPQ_ERR_TABLE;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_dual_pair(neg_table, pos_table)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
   if (rows == 0 || cols == 0) return FPQ_OK;
   if (!x || !out) return FPQ_ERR_ARG;
   DualArgs dual;
@@ -1636,7 +1542,7 @@ int fpq_quant_rows_dual_argmin(const void* x, float* out, int64_t rows, int64_t 
 static int quant_rows_codes_mx_impl(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
                                     bool km, fpq_stream_t stream) {
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
   if (km && in_dtype != FPQ_F16) return FPQ_ERR_DTYPE;   // fp32 rows (weights): fpq_quant_rows_codes_mx + fpq_codes_to_kmajor
   if (cols % 128 != 0 || (km && !km_image_fits(rows, cols / 2))) return FPQ_ERR_SHAPE;
   if (rows == 0 || cols == 0) return FPQ_OK;
@@ -1647,15 +1553,12 @@ static int quant_rows_codes_mx_impl(const void* x, uint8_t* codes, void* scales,
     const Lut16Host& h = lut16_host(FPQ_E2M1, FPQ_E2M1);
     const int64_t n_vec = rows * (cols / 8);
     const size_t lds = 0;   // the bucket table lives in static LDS (fpq_fast16.h)
-    hipLaunchKernelGGL(rows16_codes_mx_kernel, dim3(grid_for((n_vec + kBlock - 1) / kBlock, 16384)), dim3(kBlock), lds, st,
-                       (const u32x4*)x, (uint32_t*)codes, (uint16_t*)scales, n_vec, h.args, lut16_mx_codes_e2m1(),
-                       km ? (uint32_t)rows : 0u, fast_div((uint32_t)(cols / 128)));
-  } else {
-    const int64_t n_vec = rows * (cols / 4);
-    hipLaunchKernelGGL((codes128_kernel<float, true, true>), dim3(grid_for((n_vec + kBlock - 1) / kBlock, 1 << 20)),
-                       dim3(kBlock), 0, st, (const u32x4*)x, codes, (float*)scales, n_vec, make_fmt(FPQ_E2M1));
+    return launch(rows16_codes_mx_kernel, grid_for(tiles_of(n_vec, 1), 16384), lds, st, x, (uint32_t*)codes, scales, n_vec, h.args,
+                  lut16_mx_codes_e2m1(), km ? (uint32_t)rows : 0u, fast_div((uint32_t)(cols / 128)));
   }
-  return check_launch();
+  const int64_t n_vec = rows * (cols / 4);
+  return launch(codes128_kernel<float, true, true>, grid_for(tiles_of(n_vec, 1), 1 << 20), 0, st, x, codes, scales, n_vec,
+                make_fmt(FPQ_E2M1));
 }
 int fpq_quant_rows_codes_mx(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
                             fpq_stream_t stream) {
@@ -1671,7 +1574,7 @@ int fpq_quant_rows_codes_g6(const void* x, uint8_t* codes, void* scales, int64_t
                             fpq_stream_t stream) {
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
   if (table_id != FPQ_E1M2 && table_id != FPQ_E3M0) return FPQ_ERR_TABLE;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
   if (cols % 128 != 0) return FPQ_ERR_SHAPE;
   if (rows == 0 || cols == 0) return FPQ_OK;
   if (!x || !codes || !scales) return FPQ_ERR_ARG;
@@ -1681,17 +1584,14 @@ int fpq_quant_rows_codes_g6(const void* x, uint8_t* codes, void* scales, int64_t
     const Lut16Host& h = lut16_host(table_id, table_id);
     if (!h.tab_valid) return FPQ_ERR_TABLE;
     const int64_t n_vec = rows * (cols / 8);
-    hipLaunchKernelGGL(group6_emit16_kernel, dim3(grid_for((n_vec + kBlock - 1) / kBlock, 16384)), dim3(kBlock), 0, st, (const u32x4*)x,
-                       codes, (uint16_t*)scales, n_vec, h.args, lut16_codes_g6(table_id));
-  } else {
-    const int64_t n_blk = rows * (cols / 32);
-    const dim3 grid(grid_for((n_blk + kBlock - 1) / kBlock, 1 << 20));
-    if (table_id == FPQ_E3M0)
-      hipLaunchKernelGGL((group6_emit_kernel<float, true>), grid, dim3(kBlock), 0, st, (const u32x4*)x, codes, (float*)scales, n_blk, make_fmt(FPQ_E3M0));
-    else
-      hipLaunchKernelGGL((group6_emit_kernel<float, false>), grid, dim3(kBlock), 0, st, (const u32x4*)x, codes, (float*)scales, n_blk, make_fmt(FPQ_E1M2));
+    return launch(group6_emit16_kernel, grid_for(tiles_of(n_vec, 1), 16384), 0, st, x, codes, scales, n_vec, h.args,
+                  lut16_codes_g6(table_id));
   }
-  return check_launch();
+  const int64_t n_blk = rows * (cols / 32);
+  return with_bool(table_id == FPQ_E3M0, [&](auto e3m0) {   // (the other table: E1M2)
+    return launch(group6_emit_kernel<float, e3m0.value>, grid_for(tiles_of(n_blk, 1), 1 << 20), 0, st, x, codes, scales, n_blk,
+                  make_fmt(table_id));
+  });
 }
 
 int fpq_kv_pack(uint8_t* codes, void* scales, int kv_bit, int64_t batch, int64_t max_len, int64_t heads, int64_t head_dim, int64_t pos,
@@ -1720,64 +1620,48 @@ int fpq_kv_pack(uint8_t* codes, void* scales, int kv_bit, int64_t batch, int64_t
   k.pos = pos;
   k.row_vec = (int)(heads * 8);
   k.new_vecs = n_new * k.row_vec;
-  const int64_t tiles = (k.new_vecs + kBlock * U - 1) / (kBlock * U);
+  const int64_t tiles = tiles_of(k.new_vecs, U);
   if (tiles > 0x7FFFFFFF) return FPQ_ERR_ARG;
   const dim3 grid((unsigned)tiles, (unsigned)batch, 2);
   hipStream_t st = (hipStream_t)stream;
-  if (kv_bit == 6) hipLaunchKernelGGL((kv_pack_kernel<6, U>), grid, dim3(kBlock), 0, st, k, h.args, lut16_codes6_e2m3());
-  else hipLaunchKernelGGL((kv_pack_kernel<4, U>), grid, dim3(kBlock), 0, st, k, h.args, lut16_mx_codes_e2m1());
-  return check_launch();
+  if (kv_bit == 6) return launch(kv_pack_kernel<6, U>, grid, 0, st, k, h.args, lut16_codes6_e2m3());
+  return launch(kv_pack_kernel<4, U>, grid, 0, st, k, h.args, lut16_mx_codes_e2m1());
 }
 
 int fpq_absmax(const void* x, int64_t n, int dtype, void* out, fpq_stream_t stream) {
   if (n < 0 || !out) return FPQ_ERR_ARG;
-  if (dtype != FPQ_F16 && dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_f16_or_f32(dtype)) return FPQ_ERR_DTYPE;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(out, 0, 4, st) != hipSuccess) return FPQ_ERR_LAUNCH;
   if (n == 0) return FPQ_OK;
   if (!x) return FPQ_ERR_ARG;
-  int64_t per_block = (int64_t)kBlock * 16;
-  int g = grid_for((n + per_block - 1) / per_block);
-  if (dtype == FPQ_F16)
-    hipLaunchKernelGGL(absmax_kernel<_Float16>, dim3(g), dim3(kBlock), 0, st, (const _Float16*)x, n, (uint32_t*)out);
-  else
-    hipLaunchKernelGGL(absmax_kernel<float>, dim3(g), dim3(kBlock), 0, st, (const float*)x, n, (uint32_t*)out);
-  return check_launch();
+  return with_dtype(dtype, [&](auto t) { return launch(absmax_kernel<decltype(t)>, grid_for(tiles_of(n, 16)), 0, st, x, n, out); });
 }
 
 int fpq_quant_tensor_argmin(const void* x, float* out, float* scale_out, void* workspace, int64_t n, int table_id,
                             int in_dtype, fpq_stream_t stream) {
   if (n < 0) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
   if (!scale_out || !workspace || (((uintptr_t)workspace | (uintptr_t)scale_out) & 3) != 0) return FPQ_ERR_ARG;
   if (n > 0 && (!x || !out)) return FPQ_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   Fmt f = make_fmt(table_id);
   f.argmin = 1;
-  constexpr int64_t per_block = (int64_t)kBlock * 16;
-  const int g1 = grid_for((n + per_block - 1) / per_block, FPQ_TENSOR_WORKSPACE_BYTES / 4);   // also 1 when n == 0
-  const int V = in_dtype == FPQ_F16 ? 8 : 4;
-  const int g2 = grid_for((n / V + 2 * kBlock - 1) / (2 * kBlock) + 1, 1 << 16);
-  if (in_dtype == FPQ_F16) {
-    hipLaunchKernelGGL(absmax_partials_kernel<_Float16>, dim3(g1), dim3(kBlock), 0, st, (const _Float16*)x, n,
-                       (uint32_t*)workspace);
-    hipLaunchKernelGGL(tensor_argmin_kernel<_Float16>, dim3(g2), dim3(kBlock), 0, st, (const _Float16*)x, out, n,
-                       (const uint32_t*)workspace, g1, scale_out, f);
-  } else {
-    hipLaunchKernelGGL(absmax_partials_kernel<float>, dim3(g1), dim3(kBlock), 0, st, (const float*)x, n,
-                       (uint32_t*)workspace);
-    hipLaunchKernelGGL(tensor_argmin_kernel<float>, dim3(g2), dim3(kBlock), 0, st, (const float*)x, out, n,
-                       (const uint32_t*)workspace, g1, scale_out, f);
-  }
-  return check_launch();
+  const int g1 = grid_for(tiles_of(n, 16), FPQ_TENSOR_WORKSPACE_BYTES / 4);   // also 1 when n == 0
+  return with_dtype(in_dtype, [&](auto t) {
+    using T = decltype(t);
+    const int g2 = grid_for(tiles_of(n / DT<T>::kVec, 2) + 1, 1 << 16);
+    if (int rc = launch(absmax_partials_kernel<T>, g1, 0, st, x, n, workspace)) return rc;
+    return launch(tensor_argmin_kernel<T>, g2, 0, st, x, out, n, workspace, g1, scale_out, f);
+  });
 }
 
 int fpq_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
                          int in_dtype, int pack_nibbles, fpq_stream_t stream) {
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
   if (pack_nibbles && kTables[table_id].n_pos > 8) return FPQ_ERR_SHAPE;  // FP6 codes do not fit a nibble
   if (rows == 0 || cols == 0) return FPQ_OK;
   if (!x || !codes || !scales) return FPQ_ERR_ARG;
@@ -1790,33 +1674,22 @@ int fpq_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t ro
   }
   if (cols == 128 && (((uintptr_t)x | (uintptr_t)codes | (uintptr_t)scales) & 15) == 0) {
     const int64_t n_vec = rows * (in_dtype == FPQ_F16 ? 16 : 32);
-    const int gv = grid_for((n_vec + kBlock - 1) / kBlock, 1 << 20);
-    if (in_dtype == FPQ_F16 && pack_nibbles)
-      hipLaunchKernelGGL((codes128_kernel<_Float16, true>), dim3(gv), dim3(kBlock), 0, st, (const u32x4*)x, codes, (_Float16*)scales, n_vec, f);
-    else if (in_dtype == FPQ_F16)
-      hipLaunchKernelGGL((codes128_kernel<_Float16, false>), dim3(gv), dim3(kBlock), 0, st, (const u32x4*)x, codes, (_Float16*)scales, n_vec, f);
-    else if (pack_nibbles)
-      hipLaunchKernelGGL((codes128_kernel<float, true>), dim3(gv), dim3(kBlock), 0, st, (const u32x4*)x, codes, (float*)scales, n_vec, f);
-    else
-      hipLaunchKernelGGL((codes128_kernel<float, false>), dim3(gv), dim3(kBlock), 0, st, (const u32x4*)x, codes, (float*)scales, n_vec, f);
-    return check_launch();
+    return with_dtype(in_dtype, [&](auto t) {
+      return with_bool(pack_nibbles != 0, [&](auto pk) {
+        return launch(codes128_kernel<decltype(t), pk.value>, grid_for(tiles_of(n_vec, 1), 1 << 20), 0, st, x, codes, scales, n_vec, f);
+      });
+    });
   }
-  int g = grid_for(rows, 65535);
-  if (in_dtype == FPQ_F16)
-    hipLaunchKernelGGL(rows_codes_kernel<_Float16>, dim3(g), dim3(kBlock), 0, st, (const _Float16*)x, codes,
-                       (_Float16*)scales, rows, cols, f, pack_nibbles ? 1 : 0);
-  else
-    hipLaunchKernelGGL(rows_codes_kernel<float>, dim3(g), dim3(kBlock), 0, st, (const float*)x, codes,
-                       (float*)scales, rows, cols, f, pack_nibbles ? 1 : 0);
-  return check_launch();
+  return with_dtype(in_dtype, [&](auto t) {
+    return launch(rows_codes_kernel<decltype(t)>, grid_for(rows, 65535), 0, st, x, codes, scales, rows, cols, f, pack_nibbles ? 1 : 0);
+  });
 }
 
 int fpq_dequant_rows_codes(const uint8_t* codes, const void* scales, void* out, int64_t rows, int64_t cols,
                            int table_id, int scale_dtype, int out_dtype, int pack_nibbles, fpq_stream_t stream) {
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if ((scale_dtype != FPQ_F16 && scale_dtype != FPQ_F32) || (out_dtype != FPQ_F16 && out_dtype != FPQ_F32))
-    return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(scale_dtype) || !is_f16_or_f32(out_dtype)) return FPQ_ERR_DTYPE;
   if (pack_nibbles && kTables[table_id].n_pos > 8) return FPQ_ERR_SHAPE;
   if (rows == 0 || cols == 0) return FPQ_OK;
   if (!codes || !scales || !out) return FPQ_ERR_ARG;
@@ -1826,37 +1699,28 @@ int fpq_dequant_rows_codes(const uint8_t* codes, const void* scales, void* out, 
     const int64_t n_oct = rows * 16;
     const int64_t per_wg = pack_nibbles ? 4 * kBlock : kBlock;   // the nibble form decodes tiles of 4 x 256 octets
     const int gv = grid_for((n_oct + per_wg - 1) / per_wg, 1 << 20);
-#define FPQ_DEC(TS, TO, PK) hipLaunchKernelGGL((decode128_kernel<TS, TO, PK>), dim3(gv), dim3(kBlock), 0, st, codes, (const TS*)scales, (TO*)out, n_oct, f)
-    if (scale_dtype == FPQ_F16 && out_dtype == FPQ_F16) { if (pack_nibbles) FPQ_DEC(_Float16, _Float16, true); else FPQ_DEC(_Float16, _Float16, false); }
-    else if (scale_dtype == FPQ_F16) { if (pack_nibbles) FPQ_DEC(_Float16, float, true); else FPQ_DEC(_Float16, float, false); }
-    else if (out_dtype == FPQ_F16) { if (pack_nibbles) FPQ_DEC(float, _Float16, true); else FPQ_DEC(float, _Float16, false); }
-    else { if (pack_nibbles) FPQ_DEC(float, float, true); else FPQ_DEC(float, float, false); }
-#undef FPQ_DEC
-    return check_launch();
+    return with_dtype(scale_dtype, [&](auto ts) {
+      return with_dtype(out_dtype, [&](auto to) {
+        return with_bool(pack_nibbles != 0, [&](auto pk) {
+          return launch(decode128_kernel<decltype(ts), decltype(to), pk.value>, gv, 0, st, codes, scales, out, n_oct, f);
+        });
+      });
+    });
   }
-  int g = grid_for(rows, 65535);
-  int pk = pack_nibbles ? 1 : 0;
-  if (scale_dtype == FPQ_F16 && out_dtype == FPQ_F16)
-    hipLaunchKernelGGL((rows_decode_kernel<_Float16, _Float16>), dim3(g), dim3(kBlock), 0, st, codes,
-                       (const _Float16*)scales, (_Float16*)out, rows, cols, f, pk);
-  else if (scale_dtype == FPQ_F16 && out_dtype == FPQ_F32)
-    hipLaunchKernelGGL((rows_decode_kernel<_Float16, float>), dim3(g), dim3(kBlock), 0, st, codes,
-                       (const _Float16*)scales, (float*)out, rows, cols, f, pk);
-  else if (scale_dtype == FPQ_F32 && out_dtype == FPQ_F16)
-    hipLaunchKernelGGL((rows_decode_kernel<float, _Float16>), dim3(g), dim3(kBlock), 0, st, codes,
-                       (const float*)scales, (_Float16*)out, rows, cols, f, pk);
-  else
-    hipLaunchKernelGGL((rows_decode_kernel<float, float>), dim3(g), dim3(kBlock), 0, st, codes,
-                       (const float*)scales, (float*)out, rows, cols, f, pk);
-  return check_launch();
+  return with_dtype(scale_dtype, [&](auto ts) {
+    return with_dtype(out_dtype, [&](auto to) {
+      return launch(rows_decode_kernel<decltype(ts), decltype(to)>, grid_for(rows, 65535), 0, st, codes, scales, out, rows, cols, f,
+                    pack_nibbles ? 1 : 0);
+    });
+  });
 }
 
 int fpq_quant_rows_codes_segments(const fpq_codes_segment_t* segments_device, int n_segments, int64_t max_rows,
                                   int64_t cols, int table_id, int in_dtype, int pack_nibbles, fpq_stream_t stream) {
   static_assert(sizeof(fpq_codes_segment_t) == sizeof(CodesSeg), "fpq_codes_segment_t and the kernels' CodesSeg share one layout");
   if (n_segments < 0 || max_rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
   if (cols != 128 || n_segments > 65535) return FPQ_ERR_SHAPE;
   if (pack_nibbles && kTables[table_id].n_pos > 8) return FPQ_ERR_SHAPE;
   if (n_segments == 0 || max_rows == 0) return FPQ_OK;
@@ -1872,11 +1736,9 @@ int fpq_quant_rows_codes_segments(const fpq_codes_segment_t* segments_device, in
   // a few vectors per thread in the largest segment: the grid's y dimension multiplies it by the segment count
   const dim3 grid((unsigned)grid_for((n_vec + 4 * kBlock - 1) / (4 * kBlock), 1 << 16), (unsigned)n_segments);
   const CodesSeg* sg = (const CodesSeg*)segments_device;
-  if (in_dtype == FPQ_F16 && pack_nibbles) hipLaunchKernelGGL((codes128_segments_kernel<_Float16, true>), grid, dim3(kBlock), 0, st, sg, f);
-  else if (in_dtype == FPQ_F16) hipLaunchKernelGGL((codes128_segments_kernel<_Float16, false>), grid, dim3(kBlock), 0, st, sg, f);
-  else if (pack_nibbles) hipLaunchKernelGGL((codes128_segments_kernel<float, true>), grid, dim3(kBlock), 0, st, sg, f);
-  else hipLaunchKernelGGL((codes128_segments_kernel<float, false>), grid, dim3(kBlock), 0, st, sg, f);
-  return check_launch();
+  return with_dtype(in_dtype, [&](auto t) {
+    return with_bool(pack_nibbles != 0, [&](auto pk) { return launch(codes128_segments_kernel<decltype(t), pk.value>, grid, 0, st, sg, f); });
+  });
 }
 
 int fpq_dequant_rows_codes_segments(const fpq_decode_segment_t* segments_device, int n_segments, int64_t max_rows,
@@ -1884,9 +1746,8 @@ int fpq_dequant_rows_codes_segments(const fpq_decode_segment_t* segments_device,
                                     fpq_stream_t stream) {
   static_assert(sizeof(fpq_decode_segment_t) == sizeof(DecodeSeg), "fpq_decode_segment_t and the kernels' DecodeSeg share one layout");
   if (n_segments < 0 || max_rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if ((scale_dtype != FPQ_F16 && scale_dtype != FPQ_F32) || (out_dtype != FPQ_F16 && out_dtype != FPQ_F32))
-    return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(scale_dtype) || !is_f16_or_f32(out_dtype)) return FPQ_ERR_DTYPE;
   if (cols != 128 || n_segments > 65535) return FPQ_ERR_SHAPE;
   if (pack_nibbles && kTables[table_id].n_pos > 8) return FPQ_ERR_SHAPE;
   if (n_segments == 0 || max_rows == 0) return FPQ_OK;
@@ -1896,13 +1757,13 @@ int fpq_dequant_rows_codes_segments(const fpq_decode_segment_t* segments_device,
   const int64_t n_oct = max_rows * 16;
   const dim3 grid((unsigned)grid_for((n_oct + 4 * kBlock - 1) / (4 * kBlock), 1 << 16), (unsigned)n_segments);
   const DecodeSeg* sg = (const DecodeSeg*)segments_device;
-#define FPQ_DECS(TS, TO, PK) hipLaunchKernelGGL((decode128_segments_kernel<TS, TO, PK>), grid, dim3(kBlock), 0, st, sg, f)
-  if (scale_dtype == FPQ_F16 && out_dtype == FPQ_F16) { if (pack_nibbles) FPQ_DECS(_Float16, _Float16, true); else FPQ_DECS(_Float16, _Float16, false); }
-  else if (scale_dtype == FPQ_F16) { if (pack_nibbles) FPQ_DECS(_Float16, float, true); else FPQ_DECS(_Float16, float, false); }
-  else if (out_dtype == FPQ_F16) { if (pack_nibbles) FPQ_DECS(float, _Float16, true); else FPQ_DECS(float, _Float16, false); }
-  else { if (pack_nibbles) FPQ_DECS(float, float, true); else FPQ_DECS(float, float, false); }
-#undef FPQ_DECS
-  return check_launch();
+  return with_dtype(scale_dtype, [&](auto ts) {
+    return with_dtype(out_dtype, [&](auto to) {
+      return with_bool(pack_nibbles != 0, [&](auto pk) {
+        return launch(decode128_segments_kernel<decltype(ts), decltype(to), pk.value>, grid, 0, st, sg, f);
+      });
+    });
+  });
 }
 
 }  // extern "C"

@@ -44,17 +44,18 @@ int launch_rotate_quant(const void* x, void* out, void* rot_out, int64_t rows, i
                            : smooth ? (code_scales ? 2560 : 7680) : code_scales ? 8192 : 16384;
   const int64_t passes = (wg_tiles + resident - 1) / resident;
   const dim3 mgrid((unsigned)((wg_tiles + passes - 1) / passes));
-#define FPQ_ROT_MFMA(EMIT, SMOOTH, ...)                                                                             \
-  hipLaunchKernelGGL((rotate_quant_mfma_kernel<Tin, EMIT, SMOOTH, ##__VA_ARGS__>), mgrid, dim3(kBlock), lds, st, x, \
-                     (u32x4*)out, (u32x4*)rot_out, n_vec, r, h.args, tab)
-  if (code_scales && hw4) { if (smooth) FPQ_ROT_MFMA(false, true, true, true); else FPQ_ROT_MFMA(false, false, true, true); }
-  else if (code_scales) { if (smooth) FPQ_ROT_MFMA(false, true, true); else FPQ_ROT_MFMA(false, false, true); }
-  else if (rot_out && hw4) { if (smooth) FPQ_ROT_MFMA(true, true, false, true); else FPQ_ROT_MFMA(true, false, false, true); }
-  else if (rot_out) { if (smooth) FPQ_ROT_MFMA(true, true); else FPQ_ROT_MFMA(true, false); }
-  else if (hw4) { if (smooth) FPQ_ROT_MFMA(false, true, false, true); else FPQ_ROT_MFMA(false, false, false, true); }
-  else { if (smooth) FPQ_ROT_MFMA(false, true); else FPQ_ROT_MFMA(false, false); }
-#undef FPQ_ROT_MFMA
-  return check_launch();
+  auto go = [&](auto emit, auto codes) {   // EMIT: the rotated rows go out too; CODES: FP4 operands instead of values
+    constexpr bool EMIT = emit.value, CODES = codes.value;
+    return with_bool(smooth != nullptr, [&](auto sm) {
+      constexpr bool SMOOTH = sm.value;
+      return with_bool(hw4, [&](auto hw) {
+        return launch(rotate_quant_mfma_kernel<Tin, EMIT, SMOOTH, CODES, hw.value>, mgrid, lds, st, x, out, rot_out, n_vec, r, h.args, tab);
+      });
+    });
+  };
+  if (code_scales) return go(Bool<false>{}, Bool<true>{});
+  if (rot_out) return go(Bool<true>{}, Bool<false>{});
+  return go(Bool<false>{}, Bool<false>{});
 }
 
 }  // namespace
@@ -65,17 +66,16 @@ static int rotate_quant_impl(const void* x, void* out, void* rotated_out, void* 
                              int in_dtype, const float* smooth, const uint32_t* sign_mask_host, int table_id,
                              fpq_stream_t stream, bool km = false) {
   if (rows < 0 || cols < 0 || !sign_mask_host) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
   if (cols % 128 != 0) return FPQ_ERR_SHAPE;
   if (rows == 0 || cols == 0) return FPQ_OK;
   if (!x || !out) return FPQ_ERR_ARG;
   if ((((uintptr_t)x | (uintptr_t)out | (uintptr_t)rotated_out | (uintptr_t)smooth) & 15) != 0) return FPQ_ERR_ARG;
-  if (in_dtype == FPQ_F16)
-    return launch_rotate_quant<_Float16>(x, out, rotated_out, rows, cols, smooth, sign_mask_host, table_id,
-                                         (hipStream_t)stream, (uint16_t*)code_scales, km);
-  return launch_rotate_quant<float>(x, out, rotated_out, rows, cols, smooth, sign_mask_host, table_id,
-                                    (hipStream_t)stream, (uint16_t*)code_scales, km);
+  return with_dtype(in_dtype, [&](auto t) {
+    return launch_rotate_quant<decltype(t)>(x, out, rotated_out, rows, cols, smooth, sign_mask_host, table_id, (hipStream_t)stream,
+                                            (uint16_t*)code_scales, km);
+  });
 }
 
 int fpq_rotate_quant_rows(const void* x, void* out, void* rotated_out, int64_t rows, int64_t cols, int in_dtype,
@@ -97,10 +97,11 @@ int fpq_rotate_quant_rows_codes_mx_km(const void* x, uint8_t* image, void* scale
 int fpq_quant_rows_codes_fp8(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
                              int in_dtype, fpq_stream_t stream) {
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (table_id < 0 || table_id >= FPQ_NUM_TABLES || !kTables[table_id].symmetric) return FPQ_ERR_TABLE;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
   if (rows == 0 || cols == 0) return FPQ_OK;
   if (!x || !codes || !scales) return FPQ_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
   if (in_dtype == FPQ_F16 && cols % 8 == 0 && cols <= 4096 && (((uintptr_t)x | (uintptr_t)codes) & 15) == 0 &&
       lut16_host(table_id, table_id).tab_valid) {
     const Lut16Host& h = lut16_host(table_id, table_id);
@@ -108,30 +109,20 @@ int fpq_quant_rows_codes_fp8(const void* x, uint8_t* codes, void* scales, int64_
     const int64_t wgs = (rows + kBlock / 64 - 1) / (kBlock / 64);
     const dim3 gw(grid_for(wgs, 8192));
     const int maxc = (int)((cols / 8 + 63) / 64);
-    hipStream_t st = (hipStream_t)stream;
-#define FPQ_C8(M) hipLaunchKernelGGL((rows16_codes8_wave_kernel<M>), gw, dim3(kBlock), lds, st, (const uint16_t*)x, codes, \
-                                     (uint16_t*)scales, rows, cols, h.args, lut16_codes8(table_id))
-    if (maxc <= 2) FPQ_C8(2);
-    else if (maxc <= 4) FPQ_C8(4);
-    else FPQ_C8(8);
-#undef FPQ_C8
-    return check_launch();
+    return with_int<2, 4, 8>(step_for(maxc, {2, 4, 8}), [&](auto m) {
+      return launch(rows16_codes8_wave_kernel<m.value>, gw, lds, st, x, codes, scales, rows, cols, h.args, lut16_codes8(table_id));
+    });
   }
-  const dim3 g(grid_for(rows, 65535));
-  if (in_dtype == FPQ_F16)
-    hipLaunchKernelGGL(rows_codes_fp8_kernel<_Float16>, g, dim3(kBlock), 0, (hipStream_t)stream, (const _Float16*)x,
-                       codes, (_Float16*)scales, rows, cols, make_fmt(table_id));
-  else
-    hipLaunchKernelGGL(rows_codes_fp8_kernel<float>, g, dim3(kBlock), 0, (hipStream_t)stream, (const float*)x, codes,
-                       (float*)scales, rows, cols, make_fmt(table_id));
-  return check_launch();
+  return with_dtype(in_dtype, [&](auto t) {
+    return launch(rows_codes_fp8_kernel<decltype(t)>, grid_for(rows, 65535), 0, st, x, codes, scales, rows, cols, make_fmt(table_id));
+  });
 }
 
 static int quant_rows_codes_fp6_impl(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
                                      int in_dtype, bool km, fpq_stream_t stream) {
   // table_id: FPQ_E2M3 or FPQ_E3M2, checked by the entry points (the _fp6 forms take E2M3 only)
   if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
-  if (in_dtype != FPQ_F16 && in_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
   if (cols % 32 != 0 || (km && (cols % 128 != 0 || !km_image_fits(rows, cols / 4 * 3)))) return FPQ_ERR_SHAPE;
   const uint32_t km_rows = km ? (uint32_t)rows : 0u;
   if (rows == 0 || cols == 0) return FPQ_OK;
@@ -144,22 +135,16 @@ static int quant_rows_codes_fp6_impl(const void* x, uint8_t* codes, void* scales
     const int64_t wgs = (rows + kBlock / 64 - 1) / (kBlock / 64);
     const dim3 gw(grid_for(wgs, 8192));
     const int maxc = (int)((cols / 32 + 63) / 64);
-#define FPQ_C6(M) hipLaunchKernelGGL((rows16_codes6_wave_kernel<M>), gw, dim3(kBlock), lds, st, (const uint16_t*)x, codes, \
-                                     (uint16_t*)scales, rows, cols, h.args, lut16_codes6(table_id), km_rows)
-    if (maxc <= 1) FPQ_C6(1);
-    else if (maxc <= 2) FPQ_C6(2);
-    else FPQ_C6(4);
-#undef FPQ_C6
-    return check_launch();
+    return with_int<1, 2, 4>(step_for(maxc, {1, 2, 4}), [&](auto m) {
+      return launch(rows16_codes6_wave_kernel<m.value>, gw, lds, st, x, codes, scales, rows, cols, h.args, lut16_codes6(table_id), km_rows);
+    });
   }
-  const dim3 g(grid_for(rows, 65535));
-#define FPQ_C6G(TIN, BF6)                                                                                           \
-  hipLaunchKernelGGL((rows_codes_fp6_kernel<TIN, BF6>), g, dim3(kBlock), 0, st, (const TIN*)x, codes, (TIN*)scales, rows, cols, \
-                     make_fmt(table_id), km_rows)
-  if (table_id == FPQ_E3M2) { if (in_dtype == FPQ_F16) FPQ_C6G(_Float16, true); else FPQ_C6G(float, true); }
-  else { if (in_dtype == FPQ_F16) FPQ_C6G(_Float16, false); else FPQ_C6G(float, false); }
-#undef FPQ_C6G
-  return check_launch();
+  return with_dtype(in_dtype, [&](auto t) {
+    return with_bool(table_id == FPQ_E3M2, [&](auto bf6) {
+      return launch(rows_codes_fp6_kernel<decltype(t), bf6.value>, grid_for(rows, 65535), 0, st, x, codes, scales, rows, cols,
+                    make_fmt(table_id), km_rows);
+    });
+  });
 }
 int fpq_quant_rows_codes_fp6(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,
                              int in_dtype, fpq_stream_t stream) {
