@@ -72,7 +72,7 @@ int gemm_qknorm(const fpq_gemm_split_t* split, const float* bias, const float* q
   return FPQ_OK;
 }
 
-// The tiling of the per-group LDS-DMA kernels (gemm_fp4_glds_kernel, its fc1 form, gemm_a6w4_kernel): 10 / 20 / 30 = 256 x 128,
+// The tiling of the per-group LDS-DMA kernels (gemm_fp4_glds_kernel, gemm_a6w4_kernel, their fc1 forms): 10 / 20 / 30 = 256 x 128,
 // 128 x 128, 64 x 128 tiles.
 // Default: 128 x 128 tiles (three workgroups per CU); 256 x 128 tiles (two per CU) from 4000 of them
 // on (round 4: 2 - 5 % faster at [65536 x 1920] x {1920, 5760, 7680} and from 16 900 tokens on for the wide Linears, 3 - 5 %
@@ -141,15 +141,21 @@ int launch_fp4_staged(const GemmCall& c, int w_scale_dtype) {
     return gemm_launch(gemm_fp4_kernel<decltype(tw), MT, NT, WR, WC>, Cfg::BM, Cfg::BN, Cfg::NTHR, Cfg::lds((int)(c.k / 128)), c);
   });
 }
-// 6-bit activations x FP4 weights, 32 MT x 128 tiles; a_table: FPQ_E1M2 (as FP6 E2M3 codes, cbsz 2) or FPQ_E3M0 (BF6 E3M2, 3)
-template <int MT>
-int launch_a6w4(const GemmCall& c, int a_table, int w_scale_dtype) {
+// 6-bit activations x FP4 weights, 32 MT x 128 tiles and epilogue XE (GemmNoFc1: the plain kernel; GemmFc1: its fc1 form); a_table:
+// FPQ_E1M2 (as FP6 E2M3 codes, cbsz 2) or FPQ_E3M0 (BF6 E3M2, 3); lds: GemmA6W4Cfg's figure for that epilogue
+template <int MT, typename XE>
+int launch_a6w4(const GemmCall& c, int a_table, int w_scale_dtype, size_t lds, XE xe) {
   using Cfg = GemmA6W4Cfg<MT, 4>;
-  const size_t lds = Cfg::lds((int)(c.k / 128));
   if (lds > 160 * 1024) return FPQ_ERR_SHAPE;
   return with_dtype(w_scale_dtype, [&](auto tw) {
-    if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_kernel<decltype(tw), MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c);
-    return gemm_launch(gemm_a6w4_kernel<decltype(tw), MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c);
+    using Tw = decltype(tw);
+    if constexpr (__is_same(XE, GemmFc1)) {
+      if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_fc1_kernel<Tw, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+      return gemm_launch(gemm_a6w4_fc1_kernel<Tw, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+    } else {
+      if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_kernel<Tw, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c);
+      return gemm_launch(gemm_a6w4_kernel<Tw, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c);
+    }
   });
 }
 // the row-scaled FP6 kernel for one epilogue and one format pair (FA, FB: cbsz of the activations, blgp of the weights; 2 = E2M3,
@@ -432,8 +438,9 @@ int fpq_gemm_a6w4_mx(const uint8_t* a_codes, const void* a_scales, int a_table, 
       ((uintptr_t)w_scales & (w_scale_dtype == FPQ_F16 ? 1 : 3)) != 0)
     return FPQ_ERR_ARG;
   const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
-  if (gemm_glds_tiling(tokens, outs, false, false) == 30) return launch_a6w4<2>(c, a_table, w_scale_dtype);
-  return launch_a6w4<4>(c, a_table, w_scale_dtype);
+  const int G = (int)(k / 128);
+  if (gemm_glds_tiling(tokens, outs, false, false) == 30) return launch_a6w4<2>(c, a_table, w_scale_dtype, GemmA6W4Cfg<2, 4>::lds(G), GemmNoFc1{});
+  return launch_a6w4<4>(c, a_table, w_scale_dtype, GemmA6W4Cfg<4, 4>::lds(G), GemmNoFc1{});
 }
 
 #ifdef FPQ_GEMM6_STAMPS
@@ -490,6 +497,43 @@ int fpq_gemm_fp4_gelu_dual_km(const uint8_t* a_image, const void* a_scales, cons
                               int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs,
                               int64_t k, void* nan_flag, fpq_stream_t stream) {
   return gemm_fp4_gelu_dual_impl(a_image, a_scales, w_image, w_scales, w_scale_dtype, bias, out, gelu_out, tokens, outs, k, nan_flag, true, stream);
+}
+
+// fc1 with a 6-bit activation: the fc1 tail of fpq_gemm_fp4_gelu_dual in the A6W4 GEMM's epilogue (gemm_a6w4_fc1_kernel); operands
+// and tilings of fpq_gemm_a6w4_mx, tail, gelu_out, nan_flag and fix-up launch of fpq_gemm_fp4_gelu_dual
+int fpq_gemm_a6w4_gelu_dual(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                            int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs, int64_t k,
+                            void* nan_flag, fpq_stream_t stream) {
+  if (a_table != FPQ_E1M2 && a_table != FPQ_E3M0) return FPQ_ERR_TABLE;
+  const Lut16Host& dual = lut16_host(FPQ_E1M2_NEG, FPQ_E2M1_POS);   // host arithmetic only: the table travels in the kernel's arguments
+  if (!dual.tab_valid) return FPQ_ERR_TABLE;
+  if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
+  if (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  // outs % 128: an output tile is one quantization group wide.  The LDS image of the 128-row tiling is the larger of the two, so
+  // it stands for both (about 105 KiB at k = 8192: the k limit is the tighter one today)
+  if (k % 128 != 0 || k > 128 * 64 || outs % 128 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF ||
+      GemmA6W4Cfg<4, 4>::lds_fc1((int)(k / 128), dual.args.shift) > 160 * 1024)
+    return FPQ_ERR_SHAPE;
+  if (tokens == 0 || outs == 0) return FPQ_OK;
+  if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
+  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out | (uintptr_t)gelu_out) & 15) != 0 || ((uintptr_t)bias & 7) != 0 ||
+      ((uintptr_t)nan_flag & 7) != 0 || ((uintptr_t)a_scales & 1) != 0 || ((uintptr_t)w_scales & (w_scale_dtype == FPQ_F16 ? 1 : 3)) != 0)
+    return FPQ_ERR_ARG;
+  GemmFc1 xe;
+  xe.a = dual.args;
+  xe.tab = dual.tab;
+  xe.h_out = (_Float16*)gelu_out;
+  xe.nan_flag = (uint32_t*)nan_flag;
+  const int G = (int)(k / 128);
+  GemmEpi epi{};
+  epi.rows_per_gate = 1;
+  epi.sp_rpb = 1;
+  const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
+  const int rc = gemm_glds_tiling(tokens, outs, false, false) == 30
+                     ? launch_a6w4<2>(c, a_table, w_scale_dtype, GemmA6W4Cfg<2, 4>::lds_fc1(G, xe.a.shift), xe)
+                     : launch_a6w4<4>(c, a_table, w_scale_dtype, GemmA6W4Cfg<4, 4>::lds_fc1(G, xe.a.shift), xe);
+  if (rc) return rc;
+  return nan_flag ? fpq_internal_zero_if_flag(out, tokens * outs * 2, nan_flag, stream) : FPQ_OK;
 }
 
 static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,

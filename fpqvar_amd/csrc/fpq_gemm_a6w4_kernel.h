@@ -1,0 +1,195 @@
+// fpq_gemm_a6w4_kernel.h - the text of the A6W4 GEMM kernel.  NOT a header of its own: fpq_gemm_a6w4.h includes it once per kernel
+// it defines, with
+//   FPQ_A6W4_KERNEL   the kernel's name
+//   FPQ_A6W4_FC1      0: the plain epilogue (+ gate / residual tail); 1: the fc1 tail (FPQ_GEMM_FC1_TAIL, fpq_gemm_fp4.h) - the kernel
+//                     takes a GemmFc1 behind the GemmEpi and stages the dual quantizer's bucket table behind the scale tiles
+// (one text, compiled under two names, as fpq_gemm_fp6_kernel.h is: the plain kernel keeps the symbol and, instruction for
+// instruction, the machine code it had before the fc1 form existed - profiles/r12_a6w4_fc1_isa.txt)
+template <typename Tsw, int MT, int NT, int FA>
+__global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_A6W4_KERNEL(const uint8_t* __restrict__ A, const _Float16* __restrict__ sa,
+                                                                   const uint8_t* __restrict__ W, const Tsw* __restrict__ sw,
+                                                                   const _Float16* __restrict__ bias, _Float16* out, int T, int O, int C,
+                                                                   GemmEpi epi
+#if FPQ_A6W4_FC1
+                                                                   , GemmFc1 xe
+#endif
+                                                                   ) {
+  static_assert(FA == 2 || FA == 3, "activation format: 2 = FP6 E2M3 (E1M2 levels), 3 = BF6 E3M2 (E3M0 levels)");
+  static_assert(NT == 4, "the epilogue packs a lane's NT results of one row into one 8-byte store");
+  constexpr int WR = 2, WC = 2, BM = 16 * MT * WR, BN = 16 * NT * WC, NTHR = 256;
+  static_assert(BM % 64 == 0, "whole super-blocks; load_scale_tiles wants the A / W boundary wavefront-uniform");
+  constexpr int ASB = BM / 32, APC = 3 * ASB, WBLK = BN / 16, NPC = APC + WBLK;   // pieces of A, blocks of W, pieces of a stage
+  constexpr int ABYTES = APC * 1024, STAGE = NPC * 1024;
+  constexpr int PIECES = (NPC + 3) / 4;
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int G = C >> 7, a_row_bytes = (C >> 2) * 3, w_row_bytes = C >> 1;
+  float* lsa = (float*)(smem + 2 * STAGE);   // [G][BM]
+  const int Gp = (G + 3) & ~3;
+  float* lsw = lsa + Gp * BM;                // [G][BN]
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int n_col = (O + BN - 1) / BN, n_row = (T + BM - 1) / BM;
+  const int cpx = (n_col + 7) >> 3;
+  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
+  const int col_blk = xcd * cpx + local % cpx, row_blk = local / cpx;
+  if (col_blk >= n_col || row_blk >= n_row) return;   // uniform over the workgroup
+  const int t0 = row_blk * BM, o0 = col_blk * BN;
+
+  // LDS-DMA sources: a uniform base per operand + a 32-bit lane offset that never changes (see gemm_fp4_glds_kernel); rows past
+  // the end of a tensor are clamped to its last row - their products land where the epilogue never stores
+  const uint8_t* const a_base_g = A + (int64_t)t0 * a_row_bytes;
+  const uint8_t* const w_base_g = W + (int64_t)o0 * w_row_bytes;
+  uint32_t voff[PIECES];
+#pragma unroll
+  for (int i = 0; i < PIECES; ++i) {
+    const int piece = wave + 4 * i;
+    if (piece < APC) {                                // super-block piece / 3, part piece % 3 (fpq_gemm_fp6_kernel.h)
+      const int sb = piece / 3, ci = (piece % 3) * 64 + lane;
+      const int r = ci / 6, pc = ci - 6 * r;          // row inside the super-block, physical chunk
+      int c = pc - fp6_rot(r);
+      c = c < 0 ? c + 6 : c;                          // logical chunk this lane fetches
+      const int t = t0 + sb * 32 + r;
+      voff[i] = (uint32_t)((t < T ? t : T - 1) - t0) * (uint32_t)a_row_bytes + (uint32_t)(c * 16);
+    } else {                                          // a 16-row block of nibbles, rows dealt over the wavefront's NT tiles
+      const int wb = piece - APC, q = lane >> 2, kb = (lane & 3) ^ glds_chunk_perm(q);
+      const int o = o0 + (wb / NT) * (16 * NT) + NT * q + wb % NT;
+      voff[i] = (uint32_t)((o < O ? o : O - 1) - o0) * (uint32_t)w_row_bytes + (uint32_t)(kb * 16);
+    }
+  }
+#define FPQ_A6W4_ISSUE(g, buf)                                                                                      \
+  _Pragma("unroll") for (int i_ = 0; i_ < PIECES; ++i_) {                                                           \
+    const int piece_ = wave + 4 * i_;                                                                               \
+    if (piece_ < NPC)   /* wavefront-uniform */                                                                     \
+      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                                 \
+                   :                                                                                                \
+                   : "v"(voff[i_]), "s"(piece_ < APC ? a_base_g + (g) * 96 : w_base_g + (g) * 64),                  \
+                     "s"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + (buf) * STAGE +     \
+                                                                                       piece_ * 1024))             \
+                   : "m0");                                                                                         \
+  }
+  FPQ_A6W4_ISSUE(0, 0);
+  load_scale_tiles<Tsw, BM, BN, NTHR>(sa, sw, lsa, lsw, t0, o0, T, O, G, tid);
+  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), the builtin: the compiler's scoreboard forgets the scale loads (gemm_fp4_glds_kernel)
+#if FPQ_A6W4_FC1
+  // the dual quantizer's bucket table, behind the scale tiles; visible after the first barrier of the main loop
+  uint16_t* lut = (uint16_t*)(lsw + Gp * BN);
+  lut16_stage(lut, xe.tab, xe.a.shift);
+#endif
+
+  constexpr int WROWS = 16 * MT, WCOLS = 16 * NT;
+  const int o = o0 + wn * WCOLS + NT * (lane & 15);
+  const int oc = o < O ? o : O - 4;
+  fpq_h4_t bias_h = fpq_h4_t{0, 0, 0, 0};
+  if (bias) bias_h = *(const fpq_h4_t*)(bias + oc);
+
+  v4f_t acc[MT][NT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[m][n] = v4f_t{0, 0, 0, 0};
+
+  // the A fragment: three 8-byte pieces inside a 16-row half of a super-block; the W fragment: row lane & 15, chunk lane >> 4
+  const int fr = lane & 15, kblk = lane >> 4;
+  int foff[3];
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    const int b = kblk * 24 + 8 * t;
+    int pc = (b >> 4) + fp6_rot(fr);
+    pc = pc >= 6 ? pc - 6 : pc;
+    foff[t] = wm * MT * 1536 + fr * 96 + pc * 16 + (b & 15);
+  }
+  const int b_off = ABYTES + wn * NT * 1024 + (fr << 6) + (((kblk ^ glds_chunk_perm(fr)) & 3) << 4);
+  const int sa_off = wm * MT * 16 + 4 * kblk, sw_off = wn * NT * 16 + NT * fr;   // outputs 4q .. 4q+3: tile n holds 4q + n
+
+  for (int g = 0; g < G; ++g) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the compiler does not see the LDS-DMA loads
+    FPQ_SYNC();   // stage g has landed; stage g^1's readers are done
+    if (g + 1 < G) { FPQ_A6W4_ISSUE(g + 1, (g + 1) & 1); }
+    const uint8_t* st = smem + (g & 1) * STAGE;
+    // the software pipeline of gemm_fp4_glds_kernel: the reads of tile row m+1, the NT MFMAs of row m, the scale-and-accumulate
+    // of row m-1
+    u32x4 bq[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) bq[n] = *(const u32x4*)(st + b_off + n * 1024);
+    const v4f_t sw1 = *(const v4f_t*)(lsw + g * BN + sw_off);
+    u32x2 aq0 = FPQ_LDS_READ64(st + foff[0]), aq1 = FPQ_LDS_READ64(st + foff[1]), aq2 = FPQ_LDS_READ64(st + foff[2]);
+    v4f_t sa4 = *(const v4f_t*)(lsa + g * BM + sa_off);
+    v4f_t d_prev[NT], sa4_prev = sa4;
+#pragma unroll
+    for (int n = 0; n < NT; ++n) d_prev[n] = v4f_t{0, 0, 0, 0};
+#pragma unroll
+    for (int m = 0; m <= MT; ++m) {
+      u32x2 an0 = aq0, an1 = aq1, an2 = aq2;
+      v4f_t sa4_n = sa4;
+      if (m + 1 < MT) {
+        const uint8_t* p = st + (m + 1) * 1536;
+        an0 = FPQ_LDS_READ64(p + foff[0]);
+        an1 = FPQ_LDS_READ64(p + foff[1]);
+        an2 = FPQ_LDS_READ64(p + foff[2]);
+        sa4_n = *(const v4f_t*)(lsa + g * BM + sa_off + (m + 1) * 16);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      v4f_t d[NT];
+      if (m < MT) {
+        const v8i_t af = v8i_t{(int)aq0[0], (int)aq0[1], (int)aq1[0], (int)aq1[1], (int)aq2[0], (int)aq2[1], 0, 0};
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+          const v8i_t bf = v8i_t{(int)bq[n][0], (int)bq[n][1], (int)bq[n][2], (int)bq[n][3], 0, 0, 0, 0};
+          // cbsz = FA decodes the 6-bit activation fragment, blgp = 4 the E2M1 nibbles; literal zero scales: the unscaled instruction
+          d[n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf, v4f_t{0, 0, 0, 0}, FA, 4, 0, 0, 0, 0);
+        }
+      }
+      if (m > 0) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float t = d_prev[n][i] * sa4_prev[i];
+            acc[m - 1][n][i] = __builtin_fmaf(t, sw1[n], acc[m - 1][n][i]);
+          }
+      }
+      if (m > 0 && m < MT) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (m < MT) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n) d_prev[n] = d[n];
+        sa4_prev = sa4;
+      }
+      aq0 = an0;
+      aq1 = an1;
+      aq2 = an2;
+      sa4 = sa4_n;
+    }
+  }
+#undef FPQ_A6W4_ISSUE
+
+  // epilogue from the registers, as gemm_fp4_glds_kernel's plain one: + bias, one rounding to fp16, gate / residual, 8-byte stores
+  v4f_t b4 = v4f_t{0, 0, 0, 0};
+#pragma unroll
+  for (int n = 0; n < NT; ++n) b4[n] = (float)bias_h[n];
+#if FPQ_A6W4_FC1
+  FPQ_GEMM_FC1_TAIL(STAGE);   // (this form has no gate / residual tail: epi is not read)
+#else
+  FPQ_GEMM_GATE_SETUP(WROWS);
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);
+    fpq_h4_t y[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)(acc[m][n][i] + b4[n]);
+    int tc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;
+    FPQ_GEMM_GATE_RESID_ROWS(y, tc, m, oc);
+    FPQ_GEMM_ROWS_STORE(y, t_first, tc, o, oc);
+  }
+#endif
+}

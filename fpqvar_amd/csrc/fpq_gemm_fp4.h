@@ -477,6 +477,84 @@ FPQ_NOPK __device__ __forceinline__ uint32_t quant_pair16_dual(uint32_t wk, cons
   return pk_mul_f16(lut_pair16(lut, u, shift), sc);
 }
 
+// THE fc1 tail (see the comment above GemmFc1) of the register epilogues with 128-wide tiles - gemm_fp4_glds_kernel<.., GemmFc1>,
+// gemm_a6w4_fc1_kernel - written once; it ends the kernel (every store is in it).  Row r of the tile = wm * WROWS + m * 16 +
+// 4 * (lane >> 4) + i.  STAGE_: the bytes of one stage buffer of the kernel's two-stage ring; the exchange and the row scales go
+// into buffer (G & 1), the one the last K group does not read.  Names from the kernel: smem, G, BM, MT, NT, WROWS, acc, b4, xe
+// (GemmFc1), lut (the staged bucket table), t0, wm, wn, lane, tid, T, O, o, oc, out.
+//   * The two maxima of a row travel as ONE packed key, both halves compared unsigned: low half = the unsigned maximum of the fp16
+//     patterns (the most negative value, or a negative NaN), high half = their signed maximum with the sign bit flipped (the
+//     largest positive value, or a positive NaN) - dual_max_acc of fpq_fast16.h, finished by the row's thread further down.
+//   * Maxima over the 16 lanes that share a row: a reduce-scatter (the NR rows of a lane are halved four times, each step one DPP
+//     exchange per surviving row: 30 exchanges for 32 rows, where reducing every row over all lanes takes 128) - afterwards lane
+//     j of a DPP row holds the finished keys of NR / 16 rows (one row per lane pair for NR = 8), row index = the lane's bits,
+//     highest first, then the position in `key`.
+//   * The NaN flag is raised with the builtin: atomicOr() is a header function without the kernels' target attribute - it would
+//     become a call.
+#define FPQ_GEMM_FC1_TAIL(STAGE_)                                                                                   \
+  do {                                                                                                              \
+    uint32_t* xch = (uint32_t*)(smem + (G & 1) * (STAGE_));  /* [2 (wn)][BM]: packed (max|h| over h < 0) | (max h over h > 0) << 16 */ \
+    u32x4* rsc = (u32x4*)(xch + 2 * BM);                     /* [BM]: {1 / s_neg, 1 / s_pos, s_neg x 2, s_pos x 2} */ \
+    static_assert(2 * BM * 4 + BM * 16 <= (STAGE_), "exchange + row scales fit the idle stage buffer");             \
+    uint32_t hw[MT][4][2];                                                                                          \
+    constexpr int NR = 4 * MT;                                                                                      \
+    uint32_t key[NR];                                                                                               \
+    _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                                \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                               \
+        float g[NT];                                                                                                \
+        _Pragma("unroll") for (int n = 0; n < NT; ++n) g[n] = gelu_tanh_fast((float)(_Float16)(acc[m][n][i] + b4[n])); \
+        const uint32_t w0 = f2h2(g[0], g[1]), w1 = f2h2(g[2], g[3]);                                                \
+        hw[m][i][0] = w0;                                                                                           \
+        hw[m][i][1] = w1;                                                                                           \
+        const uint32_t un = pk_max_u16(w0, w1), sg = pk_max_i16(w0, w1) ^ 0x80008000u;                              \
+        key[4 * m + i] = pk_max_u16(__builtin_amdgcn_perm(sg, un, 0x05040100u), __builtin_amdgcn_perm(sg, un, 0x07060302u)); \
+      }                                                                                                             \
+      if (xe.h_out) {                                                                                               \
+        const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);                                             \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                               \
+          if (t_first + i < T && o < O)                                                                             \
+            __builtin_nontemporal_store(u32x2{hw[m][i][0], hw[m][i][1]}, (u32x2*)(xe.h_out + (int64_t)(t_first + i) * O + oc)); \
+      }                                                                                                             \
+    }                                                                                                               \
+    {                                                                                                               \
+      const int j = lane & 15;                                                                                      \
+      pk_max_scatter_step<NR, 0x128>(key, (j & 8) != 0);                               /* row_ror:8       partner j ^ 8 */ \
+      pk_max_scatter_step<(NR >= 2 ? NR / 2 : 1), 0x141>(key, (j & 4) != 0);           /* row_half_mirror partner 7 - (j & 7) */ \
+      pk_max_scatter_step<(NR >= 4 ? NR / 4 : 1), 0x4E>(key, (j & 2) != 0);            /* quad_perm [2,3,0,1] */    \
+      pk_max_scatter_step<(NR >= 8 ? NR / 8 : 1), 0xB1>(key, (j & 1) != 0);            /* quad_perm [1,0,3,2] */    \
+      constexpr int NF = NR >= 16 ? NR / 16 : 1;                                       /* finished rows per lane */ \
+      constexpr int HALVINGS = NR >= 16 ? 4 : 3;                                       /* NR = 8: the last step is a plain exchange */ \
+      const int rho0 = (HALVINGS == 4 ? j : (j >> 1)) * NF;                            /* row m * 4 + i of key[0] */ \
+      uint32_t* dst = xch + wn * BM + wm * WROWS + (rho0 >> 2) * 16 + 4 * (lane >> 4) + (rho0 & 3);                 \
+      if constexpr (NF == 2) *(u32x2*)dst = u32x2{key[0], key[1]};                     /* rows i, i + 1 of one tile row block */ \
+      else dst[0] = key[0];                                                                                         \
+    }                                                                                                               \
+    FPQ_SYNC();                                                                                                     \
+    if (tid < BM) {   /* one thread per token row: the group's two scales */                                        \
+      const uint32_t k = pk_max_u16(xch[tid], xch[BM + tid]);                          /* the two wavefronts that share the group */ \
+      const uint32_t un = k & 0xFFFFu, sgv = (k >> 16) ^ 0x8000u;                                                   \
+      const uint32_t mn = (un & 0x8000u) ? (un & 0x7FFFu) : 0u, mp = (sgv & 0x8000u) ? 0u : sgv;   /* dual_max_finish */ \
+      if ((mn > 0x7C00u || mp > 0x7C00u) && xe.nan_flag && t0 + tid < T)   /* a NaN in this group */                \
+        __hip_atomic_fetch_or(xe.nan_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                         \
+      RowScale16 sn = row_scale16(mn, xe.a.fneg.gmax, xe.a.inv_gneg), sp = row_scale16(mp, xe.a.fpos.gmax, xe.a.inv_gpos); \
+      dual_poison(sn, sp);                                                                                          \
+      rsc[tid] = u32x4{fbits16(sn.inv), fbits16(sp.inv), sn.s16x2, sp.s16x2};                                       \
+    }                                                                                                               \
+    FPQ_SYNC();                                                                                                     \
+    _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                                \
+      const int r_first = wm * WROWS + m * 16 + 4 * (lane >> 4);                                                    \
+      u32x2 q[4];                                                                                                   \
+      int tq[4];                                                                                                    \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                               \
+        const u32x4 sc = rsc[r_first + i];                                                                          \
+        q[i][0] = quant_pair16_dual(hw[m][i][0], lut, xe.a.shift, u2f(sc[0]), sc[2], u2f(sc[1]), sc[3]);            \
+        q[i][1] = quant_pair16_dual(hw[m][i][1], lut, xe.a.shift, u2f(sc[0]), sc[2], u2f(sc[1]), sc[3]);            \
+        tq[i] = t0 + r_first + i;                                                                                   \
+      }                                                                                                             \
+      FPQ_GEMM_ROWS_STORE(q, t0 + r_first, tq, o, oc);                                                              \
+    }                                                                                                               \
+  } while (0)
+
 // target("no-packed-fp32-ops"): beside MFMAs a packed fp32 op costs as much as two scalar ones and blocks the issue
 // port twice as long (tools/probe/valu_mfma_overlap.hip); with the feature off the compiler emits scalar
 // v_mul_f32 / v_fma_f32 and schedules them - and the MFMA hazard wait states - itself.
@@ -698,80 +776,7 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4
 #pragma unroll
   for (int n = 0; n < NT; ++n) b4[n] = (float)bias_h[n];
   if constexpr (FC1) {
-    // (see the comment above GemmFc1)  Row r of the tile = wm * WROWS + m * 16 + 4 * (lane >> 4) + i.
-    uint32_t* xch = (uint32_t*)(smem + (G & 1) * STAGE);     // [2 (wn)][BM]: packed (max|h| over h < 0) | (max h over h > 0) << 16
-    u32x4* rsc = (u32x4*)(xch + 2 * BM);                     // [BM]: {1 / s_neg, 1 / s_pos, s_neg x 2, s_pos x 2}
-    static_assert(2 * BM * 4 + BM * 16 <= STAGE, "exchange + row scales fit the idle stage buffer");
-    uint32_t hw[MT][4][2];
-    // The two maxima of a row as ONE packed key, both halves compared unsigned: low half = the unsigned maximum of the fp16
-    // patterns (the most negative value, or a negative NaN), high half = their signed maximum with the sign bit flipped (the
-    // largest positive value, or a positive NaN) - dual_max_acc of fpq_fast16.h, finished by the row's thread further down.
-    constexpr int NR = 4 * MT;
-    uint32_t key[NR];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float g[NT];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) g[n] = gelu_tanh_fast((float)(_Float16)(acc[m][n][i] + b4[n]));
-        const uint32_t w0 = f2h2(g[0], g[1]), w1 = f2h2(g[2], g[3]);
-        hw[m][i][0] = w0;
-        hw[m][i][1] = w1;
-        const uint32_t un = pk_max_u16(w0, w1), sg = pk_max_i16(w0, w1) ^ 0x80008000u;
-        key[4 * m + i] = pk_max_u16(__builtin_amdgcn_perm(sg, un, 0x05040100u), __builtin_amdgcn_perm(sg, un, 0x07060302u));
-      }
-      if (xe.h_out) {
-        const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (t_first + i < T && o < O)
-            __builtin_nontemporal_store(u32x2{hw[m][i][0], hw[m][i][1]}, (u32x2*)(xe.h_out + (int64_t)(t_first + i) * O + oc));
-      }
-    }
-    {
-      // maxima over the 16 lanes that share a row: a reduce-scatter (the NR rows of a lane are halved four times, each step
-      // one DPP exchange per surviving row: 30 exchanges for 32 rows, where reducing every row over all lanes takes 128) -
-      // afterwards lane j of a DPP row holds the finished keys of NR / 16 rows (one row per lane pair for NR = 8), row index
-      // = the lane's bits, highest first, then the position in `key`
-      const int j = lane & 15;
-      pk_max_scatter_step<NR, 0x128>(key, (j & 8) != 0);                               // row_ror:8       partner j ^ 8
-      pk_max_scatter_step<(NR >= 2 ? NR / 2 : 1), 0x141>(key, (j & 4) != 0);           // row_half_mirror partner 7 - (j & 7)
-      pk_max_scatter_step<(NR >= 4 ? NR / 4 : 1), 0x4E>(key, (j & 2) != 0);            // quad_perm [2,3,0,1]
-      pk_max_scatter_step<(NR >= 8 ? NR / 8 : 1), 0xB1>(key, (j & 1) != 0);            // quad_perm [1,0,3,2]
-      constexpr int NF = NR >= 16 ? NR / 16 : 1;                                       // finished rows per lane
-      constexpr int HALVINGS = NR >= 16 ? 4 : 3;                                       // NR = 8: the last step is a plain exchange
-      const int rho0 = (HALVINGS == 4 ? j : (j >> 1)) * NF;                            // row m * 4 + i of key[0]
-      uint32_t* dst = xch + wn * BM + wm * WROWS + (rho0 >> 2) * 16 + 4 * (lane >> 4) + (rho0 & 3);
-      if constexpr (NF == 2) *(u32x2*)dst = u32x2{key[0], key[1]};                     // rows i, i + 1 of one tile row block
-      else dst[0] = key[0];
-    }
-    FPQ_SYNC();
-    if (tid < BM) {   // one thread per token row: the group's two scales
-      const uint32_t k = pk_max_u16(xch[tid], xch[BM + tid]);                          // the two wavefronts that share the group
-      const uint32_t un = k & 0xFFFFu, sgv = (k >> 16) ^ 0x8000u;
-      const uint32_t mn = (un & 0x8000u) ? (un & 0x7FFFu) : 0u, mp = (sgv & 0x8000u) ? 0u : sgv;   // dual_max_finish
-      if ((mn > 0x7C00u || mp > 0x7C00u) && xe.nan_flag && t0 + tid < T)   // a NaN in this group (the builtin: atomicOr() is a header function without this kernel's target attribute - it would become a call)
-        __hip_atomic_fetch_or(xe.nan_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      RowScale16 sn = row_scale16(mn, xe.a.fneg.gmax, xe.a.inv_gneg), sp = row_scale16(mp, xe.a.fpos.gmax, xe.a.inv_gpos);
-      dual_poison(sn, sp);
-      rsc[tid] = u32x4{fbits16(sn.inv), fbits16(sp.inv), sn.s16x2, sp.s16x2};
-    }
-    FPQ_SYNC();
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      const int r_first = wm * WROWS + m * 16 + 4 * (lane >> 4);
-      u32x2 q[4];
-      int tq[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const u32x4 sc = rsc[r_first + i];
-        q[i][0] = quant_pair16_dual(hw[m][i][0], lut, xe.a.shift, u2f(sc[0]), sc[2], u2f(sc[1]), sc[3]);
-        q[i][1] = quant_pair16_dual(hw[m][i][1], lut, xe.a.shift, u2f(sc[0]), sc[2], u2f(sc[1]), sc[3]);
-        tq[i] = t0 + r_first + i;
-      }
-      FPQ_GEMM_ROWS_STORE(q, t0 + r_first, tq, o, oc);
-    }
+    FPQ_GEMM_FC1_TAIL(STAGE);
     return;
   }
   FPQ_GEMM_GATE_SETUP(WROWS);

@@ -374,6 +374,18 @@ def dequantize_g6(codes: torch.Tensor, scales: torch.Tensor, table: str = "e3m0"
     return (lv.view(rows, -1, 128) * scales.float().unsqueeze(-1)).reshape(rows, -1)
 
 
+def _a6w4_operands(name: str, a_codes, a_scales, w_codes, w_scales):
+    """An A6W4 operand pair (6-bit activation codes, FP4 weight nibbles; row-major), checked -> (tokens, outs, k)"""
+    if a_codes.dim() != 2 or w_codes.dim() != 2:
+        raise RuntimeError(f"{name}: row-major operands only (there is no k-major A6W4 form)")
+    tokens, outs, k = a_codes.shape[0], w_codes.shape[0], w_codes.shape[1] * 2
+    if k % 128 != 0 or a_codes.shape[1] * 4 != k * 3 or a_scales.dtype != torch.float16:
+        raise RuntimeError(f"{name}: operand shapes / activation scale dtype mismatch")
+    _check_operand(f"{name}(activation)", a_codes, a_scales, tokens, k * 3 // 4, tokens * (k // 128), a_codes.device)
+    _check_operand(f"{name}(weight)", w_codes, w_scales, outs, k // 2, outs * (k // 128), a_codes.device)
+    return tokens, outs, k
+
+
 def linear_a6w4(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor,
                 bias: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -383,13 +395,7 @@ def linear_a6w4(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_c
     require_gpu(a_codes, "linear_a6w4")
     from ._lib import TABLE_IDS
     a_table = _g6_table("linear_a6w4", a_table)
-    if a_codes.dim() != 2 or w_codes.dim() != 2:
-        raise RuntimeError("linear_a6w4: row-major operands only (there is no k-major A6W4 form)")
-    tokens, outs, k = a_codes.shape[0], w_codes.shape[0], w_codes.shape[1] * 2
-    if k % 128 != 0 or a_codes.shape[1] * 4 != k * 3 or a_scales.dtype != torch.float16:
-        raise RuntimeError("linear_a6w4: operand shapes / activation scale dtype mismatch")
-    _check_operand("linear_a6w4(activation)", a_codes, a_scales, tokens, k * 3 // 4, tokens * (k // 128), a_codes.device)
-    _check_operand("linear_a6w4(weight)", w_codes, w_scales, outs, k // 2, outs * (k // 128), a_codes.device)
+    tokens, outs, k = _a6w4_operands("linear_a6w4", a_codes, a_scales, w_codes, w_scales)
     ep, keep, out = _epilogue("linear_a6w4", tokens, outs, gate, residual, None, a_codes.device)
     b = _bias_f16("linear_a6w4", bias, outs, a_codes.device, 8)
     with device_guard(a_codes.device):
@@ -398,6 +404,33 @@ def linear_a6w4(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_c
                                      stream_ptr(a_codes.device)), "fpq_gemm_a6w4_mx")
     del keep
     return out
+
+
+def linear_a6w4_gelu_dual(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor,
+                          bias: Optional[torch.Tensor] = None, return_gelu: bool = False):
+    """linear_fp4_gelu_dual for a 6-bit activation (fpq_gemm_a6w4_gelu_dual): fc1 of the FFN up to fc2's GEMM in one launch (+ the
+    NaN fix-up launch) - `fp_quant_e1m2_neg_e2m1_pos_per_group_cuda(F.gelu(linear_a6w4(a, a_table, w, bias), approximate="tanh"),
+    4, 128)` as the epilogue of the A6W4 GEMM: fp16 [tokens, outs], outs % 128 == 0.  Row-major operands only.  return_gelu: also
+    the GELU values the quantizer saw - the same function of the fp16 Linear output as linear_fp4_gelu_dual's, bit for bit."""
+    require_gpu(a_codes, "linear_a6w4_gelu_dual")
+    from ._lib import TABLE_IDS
+    a_table = _g6_table("linear_a6w4_gelu_dual", a_table)
+    dev = a_codes.device
+    tokens, outs, k = _a6w4_operands("linear_a6w4_gelu_dual", a_codes, a_scales, w_codes, w_scales)
+    if outs % 128 != 0:
+        raise RuntimeError("linear_a6w4_gelu_dual: outs must be a multiple of 128")
+    out = torch.empty((tokens, outs), dtype=torch.float16, device=dev)
+    h = torch.empty((tokens, outs), dtype=torch.float16, device=dev) if return_gelu else None
+    b = _bias_f16("linear_a6w4_gelu_dual", bias, outs, dev, 8)
+    if tokens and outs:
+        from .ops import _nan_scratch
+        with device_guard(dev):
+            flag = _nan_scratch(dev)
+            check(lib().fpq_gemm_a6w4_gelu_dual(a_codes.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_codes.data_ptr(),
+                                                w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(),
+                                                out.data_ptr(), None if h is None else h.data_ptr(), tokens, outs, k, flag.data_ptr(),
+                                                stream_ptr(dev)), "fpq_gemm_a6w4_gelu_dual")
+    return (out, h) if return_gelu else out
 
 
 class FP4Linear(_ScaledOperandModule):
@@ -473,16 +506,27 @@ class FP4LinearGeluDual(FP4Linear):
     quantizer (`fp_e1m2_neg_e2m1_pos`, tr/quant_utils.py:415-452,991) in the GEMM's epilogue: `forward(x)` returns what
     `fc2.act_quant(act(fc1(x)))` returns in the reference's FFN.forward (tr/basic_var.py:120-121) - the module that follows
     must neither apply the activation nor quantize again (`quant_linear.quantize_VAR(..., real_fp4=True, fuse_ffn=True)` swaps
-    the FFN's `act` for an identity and switches fc2's input quantizer off)."""
+    the FFN's `act` for an identity and switches fc2's input quantizer off).  With an E1M2 / E3M0 activation format
+    (`from_float(..., act_fp_type="fp_e1" / "fp_e3")`, row-major) the same tail runs in the A6W4 GEMM (`linear_a6w4_gelu_dual`)."""
 
     @torch.no_grad()
     def forward(self, x):
         lead = x.shape[:-1]
-        a_codes, a_scales = quantize_mx(x.to(torch.float16).reshape(-1, self.in_features), kmajor=self.kmajor)
+        x2 = x.to(torch.float16).reshape(-1, self.in_features)
+        if self.act_table != "e2m1":   # 6-bit codes on the A6W4 GEMM, whose fc1 form has the same tail
+            a_codes, a_scales = quantize_g6(x2, self.act_table)
+            return linear_a6w4_gelu_dual(a_codes, a_scales, self.act_table, self.w_codes, self.w_scales, self.bias).view(*lead, self.out_features)
+        a_codes, a_scales = quantize_mx(x2, kmajor=self.kmajor)
         return linear_fp4_gelu_dual(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, outs=self.out_features).view(*lead, self.out_features)
 
     @torch.no_grad()
-    def forward_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor) -> torch.Tensor:
+    def forward_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor, table: Optional[str] = None) -> torch.Tensor:
+        """table: the format the codes are in (default: the module's activation format), as in FP4Linear.forward_operands"""
+        table = self.act_table if table is None else ("e2m1" if table in ("e2m1", "fp_e2") else _g6_table("FP4LinearGeluDual.forward_operands", table))
+        if table != "e2m1":
+            if self.kmajor:
+                raise RuntimeError("FP4LinearGeluDual.forward_operands: 6-bit activation codes need a row-major weight (no k-major A6W4 form)")
+            return linear_a6w4_gelu_dual(a_codes, a_scales, table, self.w_codes, self.w_scales, self.bias)
         return linear_fp4_gelu_dual(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, outs=self.out_features)
 
 

@@ -267,7 +267,7 @@ _FP6_SYMMETRIC = ("fp6_e2m3", "fp6_e3m2")
 
 def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, w_bit=8, a_bit=8, act_quant_sym=None,
                        fc2_act_log2_quant=None, activation_fp_quant=False, weight_fp_quant=False,
-                       ada_lin_formats=None, real_fp6=False, kmajor_operands=True, real_fp4=False):
+                       ada_lin_formats=None, real_fp6=False, kmajor_operands=True, real_fp4=False, fuse_ffn=False):
     """quantize_VAR with a format pair per (block, layer): ``layer_formats(block_idx, layer)`` returns
     ``(act_fp_type, weight_fp_type)`` for layer in {"fc1", "fc2", "mat_qkv", "proj"}.  ``ada_lin_formats``:
     None leaves the AdaLN Linear in full precision (as tr/ does), a pair quantizes ``ada_lin[1]`` (as the fq/ and
@@ -282,7 +282,15 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
     and an ``fp_e1`` / ``fp_e2`` / ``fp_e3`` activation whose shape fits the GEMM becomes a ``gemm.FP4Linear`` of its activation
     format - ``fp_e2`` on the FP4 GEMM (k-major with ``kmajor_operands``), ``fp_e1`` / ``fp_e3`` as 6-bit codes on the A6W4 GEMM
     against the same stored E2M1 weight (row-major: that GEMM has no k-major form).  Every other layer (fc2's dual format,
-    ``ada_lin[1]``, an E1M2 / E3M0 weight) stays the QuantizedLinear it is without the keyword."""
+    ``ada_lin[1]``, an E1M2 / E3M0 weight) stays the QuantizedLinear it is without the keyword.
+
+    ``fuse_ffn`` (additive, default off): quantize_VAR's rules, per FFN - the FFN's ``act`` must be GELU(tanh).  With ``real_fp4``,
+    where fc1 qualifies for ``gemm.FP4Linear`` with out_features % 128 == 0 and the block's fc2 activation format is
+    ``fp_e1m2_neg_e2m1_pos``: fc1 becomes ``gemm.FP4LinearGeluDual`` of its activation format (GELU and fc2's input quantizer in the
+    epilogue of the FP4 GEMM for ``fp_e2``, of the A6W4 GEMM for ``fp_e1`` / ``fp_e3``), ``act`` an identity and fc2's input quantizer
+    is switched off.  Otherwise, where ``GeluThenFc2Quant`` covers (act_quant, fc2's activation format): ``act`` becomes that
+    one-pass module.  An FFN neither applies to raises quantize_VAR's ValueError - when the walk reaches it: the model is converted
+    in place (as in quantize_VAR), so the modules in front of that FFN are already replaced and the model is not to be used."""
     fp4_ok = (real_fp4 and weight_quant == "per_group" and act_quant == "per_group" and w_bit == 4 and a_bit == 4
               and activation_fp_quant and weight_fp_quant)
     if real_fp4 and not fp4_ok:
@@ -310,9 +318,30 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
         if isinstance(fc1, nn.Linear) and isinstance(fc2, nn.Linear):
             b = _block_index(name)
             a, w = layer_formats(b, "fc1")
-            m.fc1 = layer(QuantizedLinear, fc1, a, w, act_quant_sym=act_quant_sym)
-            a, w = layer_formats(b, "fc2")
-            m.fc2 = layer(QuantizedLinear_fc2, fc2, a, w, act_quant_sym=False, fc2_act_log2_quant=fc2_act_log2_quant)
+            a2, w2 = layer_formats(b, "fc2")
+            act = getattr(m, "act", None)
+            gelu_tanh = isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "tanh"
+            in_gemm = (fuse_ffn and gelu_tanh and fp4_ok and w == "fp_e2" and a in ("fp_e1", "fp_e2", "fp_e3")
+                       and a2 == "fp_e1m2_neg_e2m1_pos" and fc1.in_features % 128 == 0 and fc1.out_features % 128 == 0)
+            one_pass = (fuse_ffn and gelu_tanh and not in_gemm and activation_fp_quant and (act_quant, a2) in GeluThenFc2Quant.FUSED
+                        and fc1.out_features % (128 if act_quant == "per_group" else 8) == 0)
+            if fuse_ffn and not (in_gemm or one_pass):
+                raise ValueError("fuse_ffn needs an FFN with act = GELU(approximate='tanh') and a dual-format fc2_fp_type "
+                                 "(fp_e1m2_neg_e2m1_pos / fp4_afpq per group, fp6_int_neg_e2m3_pos per group or per token)")
+            if in_gemm:
+                from .gemm import FP4LinearGeluDual
+                m.fc1 = FP4LinearGeluDual.from_float(fc1, kmajor=kmajor_operands and a == "fp_e2", act_fp_type=a)
+            else:
+                m.fc1 = layer(QuantizedLinear, fc1, a, w, act_quant_sym=act_quant_sym)
+            m.fc2 = layer(QuantizedLinear_fc2, fc2, a2, w2, act_quant_sym=False, fc2_act_log2_quant=fc2_act_log2_quant)
+            if in_gemm:
+                m.act = nn.Identity()
+                m.fc2.act_quant = lambda t: t                      # its input arrives quantized from fc1's epilogue
+                m.fc2.act_quant_name = "in fc1's epilogue"
+            elif one_pass:
+                m.act = GeluThenFc2Quant(act_quant, a2, a_bit)
+                m.fc2.act_quant = lambda t: t                      # ... from the activation module in front of it
+                m.fc2.act_quant_name = "behind the GELU (one pass)"
         elif isinstance(qkv, nn.Linear) and isinstance(proj, nn.Linear):
             b = _block_index(name)
             a, w = layer_formats(b, "mat_qkv")
@@ -328,12 +357,13 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
 def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,
                                     a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                     activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
-                                    weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True):
+                                    weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True, fuse_ffn=False):
     """models_fp_quant/quant_utils.py:1256-1341: fc1 is E2M1 in blocks 6-20 and E3M0 elsewhere, mat_qkv E2M1 in
     blocks 0, 24, 25 and E3M0 elsewhere (activations; weights always E2M1); proj, fc2 and ada_lin[1] take the
     caller's formats.
     ``real_fp4`` / ``kmajor_operands``: as in quantize_VAR_mixed - every E2M1-weight fc1 / mat_qkv / proj on the matrix cores,
-    the E3M0 activations as 6-bit codes."""
+    the E3M0 activations as 6-bit codes.  ``fuse_ffn``: as in quantize_VAR_mixed - with ``real_fp4`` and ``fc2_fp_type`` =
+    ``fp_e1m2_neg_e2m1_pos`` every fc1 runs its GELU and fc2's input quantizer in its GEMM's epilogue."""
     fc1_e2, qkv_e2 = set(range(6, 21)), {0, 24, 25}
 
     def fmt(b, layer):
@@ -347,16 +377,17 @@ def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, qu
 
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
                               activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type),
-                              real_fp4=real_fp4, kmajor_operands=kmajor_operands)
+                              real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn)
 
 
 def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,
                                         a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                         activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
-                                        weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True):
+                                        weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True, fuse_ffn=False):
     """models_fp_quant_rotate/quant_utils.py:982-1066: as the mixed FP4 variant, with mat_qkv E2M1 in blocks 24, 25 only.
     ``real_fp4`` / ``kmajor_operands``: as in quantize_VAR_mixed - every E2M1-weight fc1 / mat_qkv / proj on the matrix cores,
-    the E3M0 activations as 6-bit codes."""
+    the E3M0 activations as 6-bit codes.  ``fuse_ffn``: as in quantize_VAR_mixed - with ``real_fp4`` and ``fc2_fp_type`` =
+    ``fp_e1m2_neg_e2m1_pos`` every fc1 runs its GELU and fc2's input quantizer in its GEMM's epilogue."""
     fc1_e2, qkv_e2 = set(range(6, 21)), {24, 25}
 
     def fmt(b, layer):
@@ -370,7 +401,7 @@ def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None
 
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
                               activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type),
-                              real_fp4=real_fp4, kmajor_operands=kmajor_operands)
+                              real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn)
 
 
 def quantize_VAR_mixed_fp6_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FPQ_VERSION 131 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
+#define FPQ_VERSION 132 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
                            0.1.3: + fpq_quant_rows_codes_segments, fpq_dequant_rows_codes_segments (round 3);
                            123: + fpq_build_tag (round 4);
                            124: + fpq_set_option, fpq_get_option, fpq_option_name, fpq_gemm_fp4_gelu_dual, fpq_gelu_quant_rows_dual (round 5);
@@ -38,7 +38,8 @@ extern "C" {
                            130: + a format per operand on the FP6 matrix-core path (FP6 E2M3 / BF6 E3M2): fpq_quant_rows_codes_f6,
                                 fpq_adaln_rotate_quant_token_rows_codes_f6, fpq_gemm_f6_rows, fpq_gemm_f6_rows_split, fpq_gemm_f6_rows_split_qknorm;
                            131: + E1M2 / E3M0 activations on the matrix cores against FP4 weights ("A6W4"): fpq_quant_rows_codes_g6,
-                                fpq_gemm_a6w4_mx */
+                                fpq_gemm_a6w4_mx;
+                           132: + the fc1 tail (GELU + fc2's dual-format input quantizer) in the A6W4 GEMM: fpq_gemm_a6w4_gelu_dual */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -681,7 +682,7 @@ int fpq_gemm_f6_rows_split_qknorm(const uint8_t* a_codes, const void* a_scales, 
  * w_codes / w_scales / w_scale_dtype exactly what fpq_gemm_fp4_mx takes (E2M1 nibbles [outs, k / 2], blgp = 4): one stored FP4
  * weight serves both GEMMs.  Shape and alignment rules of fpq_gemm_fp4_mx_ex (k % 128 == 0, k <= 8192, outs % 8 == 0, codes and
  * out 16-byte aligned), checked before any launch; the bias must be 8-byte aligned (there is no register-staged form to fall
- * back to).  Row-major operands only: no k-major images, no split output, no q / k norm, no fc1 tail.
+ * back to).  Row-major operands only: no k-major images, no split output, no q / k norm; the fc1 tail: fpq_gemm_a6w4_gelu_dual.
  * Numerics: the per-group steps of fpq_gemm_fp4_mx's LDS-DMA tilings - t = fl(d_g sa), acc = fma(t, sw, acc), out = fp16(acc +
  * bias).  Products of an E3M0 or E1M2 level and an E2M1 level are multiples of 1/8 (|product| <= 96 resp. 10.5), so the exact
  * 128-term dot d_g has at most 17 significant bits (|d_g| <= 12288) and fits the fp32 accumulator.
@@ -697,6 +698,21 @@ int fpq_quant_rows_codes_g6(const void* x, uint8_t* codes, void* scales, int64_t
 int fpq_gemm_a6w4_mx(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
                      int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
                      const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream);
+/* fpq_gemm_a6w4_gelu_dual: fpq_gemm_fp4_gelu_dual for a 6-bit activation - fc1 of the FFN, its GELU(tanh) and fc2's dual E1M2- /
+ * E2M1+ per-group(128) input quantizer in ONE launch (+ the NaN fix-up launch): out = fp16 [tokens, outs] =
+ * fp_quant_e1m2_neg_e2m1_pos_per_group_cuda(gelu_tanh(y), 4, 128) with y the fp16 [tokens, outs] that fpq_gemm_a6w4_mx writes for
+ * the same operands and bias, bit for bit.  Operands (a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, bias) exactly
+ * fpq_gemm_a6w4_mx's, row-major; the tail, gelu_out (NULL, or fp16 [tokens, outs], 16-byte aligned: the GELU values the quantizer
+ * saw), nan_flag (NULL, or the 8-byte zeroed scratch of fpq_quant_rows_dual: a NaN in any live row makes the whole result +0 and
+ * the scratch is zero again afterwards) exactly fpq_gemm_fp4_gelu_dual's - the same GELU of the same fp16 value and the same
+ * quantizer arithmetic, so the two entry points agree bit for bit wherever their Linear outputs do.
+ * Checks, in this order, before any launch: a_table (FPQ_ERR_TABLE), negative sizes (FPQ_ERR_ARG), w_scale_dtype (FPQ_ERR_DTYPE),
+ * shape (FPQ_ERR_SHAPE: k % 128, k > 8192, outs % 128 - an output tile is one quantization group -, tokens or outs above 2^31 - 1,
+ * an LDS image above 160 KiB), tokens == 0 or outs == 0 (FPQ_OK), then NULL pointers / alignment (FPQ_ERR_ARG; codes, out and
+ * gelu_out 16 bytes, bias and nan_flag 8).  Tilings as fpq_gemm_a6w4_mx (FPQ_GEMM_CFG 20 / 30 forces one); both give the same bits. */
+int fpq_gemm_a6w4_gelu_dual(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes,
+                            const void* w_scales, int w_scale_dtype, const void* bias, void* out, void* gelu_out,
+                            int64_t tokens, int64_t outs, int64_t k, void* nan_flag, fpq_stream_t stream);
 
 /* fpq_kv_cache_step_qknorm: fpq_kv_cache_step (same arguments, same checks) for an fp16 qkv WITHOUT the norm (path F, or a
  * mat_qkv that is not split): the new k is normalized and the bias added on its way into the cache, and the same launch writes
