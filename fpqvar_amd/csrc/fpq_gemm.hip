@@ -142,11 +142,21 @@ int launch_fp4_staged(const GemmCall& c, int w_scale_dtype) {
   });
 }
 // 6-bit activations x FP4 weights, 32 MT x 128 tiles and epilogue XE (GemmNoFc1: the plain kernel; GemmFc1: its fc1 form); a_table:
-// FPQ_E1M2 (as FP6 E2M3 codes, cbsz 2) or FPQ_E3M0 (BF6 E3M2, 3); lds: GemmA6W4Cfg's figure for that epilogue
+// FPQ_E1M2 (as FP6 E2M3 codes, cbsz 2) or FPQ_E3M0 (BF6 E3M2, 3); lds: GemmA6W4Cfg's figure for that epilogue.  km: the operands are
+// k-major images (c.epi.km_w_rows set, fp32 scale images: the entry points have checked w_scale_dtype)
 template <int MT, typename XE>
-int launch_a6w4(const GemmCall& c, int a_table, int w_scale_dtype, size_t lds, XE xe) {
+int launch_a6w4(const GemmCall& c, int a_table, int w_scale_dtype, size_t lds, XE xe, bool km = false) {
   using Cfg = GemmA6W4Cfg<MT, 4>;
   if (lds > 160 * 1024) return FPQ_ERR_SHAPE;
+  if (km) {
+    if constexpr (__is_same(XE, GemmFc1)) {
+      if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_fc1_km_kernel<float, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+      return gemm_launch(gemm_a6w4_fc1_km_kernel<float, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+    } else {
+      if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_km_kernel<float, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c);
+      return gemm_launch(gemm_a6w4_km_kernel<float, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c);
+    }
+  }
   return with_dtype(w_scale_dtype, [&](auto tw) {
     using Tw = decltype(tw);
     if constexpr (__is_same(XE, GemmFc1)) {
@@ -423,24 +433,41 @@ int fpq_gemm_fp4_mx_km(const uint8_t* a_image, const void* a_scales, const uint8
 // (fpq_gemm_a6w4.h, include/fpq.h).  Two LDS-DMA tilings, chosen as fpq_gemm_fp4_mx_ex chooses between the same two
 // (FPQ_GEMM_CFG 20 / 30 forces one); there is no register-staged form: K is limited by the scale tiles as there, and the bias
 // is read four outputs at a time.
-int fpq_gemm_a6w4_mx(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
-                     int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
-                     const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream) {
+// km: both operands and both scale tensors are k-major images (include/fpq.h; gemm_a6w4_km_kernel) - the FP4 km rules of
+// gemm_fp4_mx_impl beside the row-major checks: fp32 scale images, 16-byte aligned, tokens and outs below 2^28 (32-bit lane
+// offsets into three planes of the scale images)
+static int gemm_a6w4_mx_impl(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                             int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
+                             const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream) {
   if (a_table != FPQ_E1M2 && a_table != FPQ_E3M0) return FPQ_ERR_TABLE;
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   GemmEpi epi;
   if (int rc = gemm_epilogue(epilogue, &epi)) return rc;
-  if (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (km ? w_scale_dtype != FPQ_F32 : (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32)) return FPQ_ERR_DTYPE;
   if (k % 128 != 0 || k > 128 * 64 || outs % 8 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
+  if (km && (tokens >= (1ll << 28) || outs >= (1ll << 28))) return FPQ_ERR_SHAPE;
   if (tokens == 0 || outs == 0) return FPQ_OK;
   if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
-  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out) & 15) != 0 || ((uintptr_t)bias & 7) != 0 || ((uintptr_t)a_scales & 1) != 0 ||
-      ((uintptr_t)w_scales & (w_scale_dtype == FPQ_F16 ? 1 : 3)) != 0)
+  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out) & 15) != 0 || ((uintptr_t)bias & 7) != 0) return FPQ_ERR_ARG;
+  if (km ? (((uintptr_t)a_scales | (uintptr_t)w_scales) & 15) != 0
+         : ((uintptr_t)a_scales & 1) != 0 || ((uintptr_t)w_scales & (w_scale_dtype == FPQ_F16 ? 1 : 3)) != 0)
     return FPQ_ERR_ARG;
+  if (km) epi.km_w_rows = (int)((outs + 63) / 64 * 64);
   const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
   const int G = (int)(k / 128);
-  if (gemm_glds_tiling(tokens, outs, false, false) == 30) return launch_a6w4<2>(c, a_table, w_scale_dtype, GemmA6W4Cfg<2, 4>::lds(G), GemmNoFc1{});
-  return launch_a6w4<4>(c, a_table, w_scale_dtype, GemmA6W4Cfg<4, 4>::lds(G), GemmNoFc1{});
+  if (gemm_glds_tiling(tokens, outs, false, false) == 30)
+    return launch_a6w4<2>(c, a_table, w_scale_dtype, GemmA6W4Cfg<2, 4>::lds(G), GemmNoFc1{}, km);
+  return launch_a6w4<4>(c, a_table, w_scale_dtype, GemmA6W4Cfg<4, 4>::lds(G), GemmNoFc1{}, km);
+}
+int fpq_gemm_a6w4_mx(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                     int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
+                     const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream) {
+  return gemm_a6w4_mx_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, bias, out, tokens, outs, k, epilogue, false, stream);
+}
+int fpq_gemm_a6w4_mx_km(const uint8_t* a_image, const void* a_scales, int a_table, const uint8_t* w_image, const void* w_scales,
+                        int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
+                        const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream) {
+  return gemm_a6w4_mx_impl(a_image, a_scales, a_table, w_image, w_scales, w_scale_dtype, bias, out, tokens, outs, k, epilogue, true, stream);
 }
 
 #ifdef FPQ_GEMM6_STAMPS
@@ -500,24 +527,29 @@ int fpq_gemm_fp4_gelu_dual_km(const uint8_t* a_image, const void* a_scales, cons
 }
 
 // fc1 with a 6-bit activation: the fc1 tail of fpq_gemm_fp4_gelu_dual in the A6W4 GEMM's epilogue (gemm_a6w4_fc1_kernel); operands
-// and tilings of fpq_gemm_a6w4_mx, tail, gelu_out, nan_flag and fix-up launch of fpq_gemm_fp4_gelu_dual
-int fpq_gemm_a6w4_gelu_dual(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
-                            int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs, int64_t k,
-                            void* nan_flag, fpq_stream_t stream) {
+// and tilings of fpq_gemm_a6w4_mx, tail, gelu_out, nan_flag and fix-up launch of fpq_gemm_fp4_gelu_dual; km as in gemm_a6w4_mx_impl
+// (outs % 128 == 0: the weight image has exactly outs rows)
+static int gemm_a6w4_gelu_dual_impl(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                                    int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs, int64_t k,
+                                    void* nan_flag, bool km, fpq_stream_t stream) {
   if (a_table != FPQ_E1M2 && a_table != FPQ_E3M0) return FPQ_ERR_TABLE;
   const Lut16Host& dual = lut16_host(FPQ_E1M2_NEG, FPQ_E2M1_POS);   // host arithmetic only: the table travels in the kernel's arguments
   if (!dual.tab_valid) return FPQ_ERR_TABLE;
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
-  if (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  if (km ? w_scale_dtype != FPQ_F32 : (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32)) return FPQ_ERR_DTYPE;
   // outs % 128: an output tile is one quantization group wide.  The LDS image of the 128-row tiling is the larger of the two, so
   // it stands for both (about 105 KiB at k = 8192: the k limit is the tighter one today)
   if (k % 128 != 0 || k > 128 * 64 || outs % 128 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF ||
       GemmA6W4Cfg<4, 4>::lds_fc1((int)(k / 128), dual.args.shift) > 160 * 1024)
     return FPQ_ERR_SHAPE;
+  if (km && (tokens >= (1ll << 28) || outs >= (1ll << 28))) return FPQ_ERR_SHAPE;
   if (tokens == 0 || outs == 0) return FPQ_OK;
   if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
   if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out | (uintptr_t)gelu_out) & 15) != 0 || ((uintptr_t)bias & 7) != 0 ||
-      ((uintptr_t)nan_flag & 7) != 0 || ((uintptr_t)a_scales & 1) != 0 || ((uintptr_t)w_scales & (w_scale_dtype == FPQ_F16 ? 1 : 3)) != 0)
+      ((uintptr_t)nan_flag & 7) != 0)
+    return FPQ_ERR_ARG;
+  if (km ? (((uintptr_t)a_scales | (uintptr_t)w_scales) & 15) != 0
+         : ((uintptr_t)a_scales & 1) != 0 || ((uintptr_t)w_scales & (w_scale_dtype == FPQ_F16 ? 1 : 3)) != 0)
     return FPQ_ERR_ARG;
   GemmFc1 xe;
   xe.a = dual.args;
@@ -528,12 +560,25 @@ int fpq_gemm_a6w4_gelu_dual(const uint8_t* a_codes, const void* a_scales, int a_
   GemmEpi epi{};
   epi.rows_per_gate = 1;
   epi.sp_rpb = 1;
+  if (km) epi.km_w_rows = (int)outs;
   const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
   const int rc = gemm_glds_tiling(tokens, outs, false, false) == 30
-                     ? launch_a6w4<2>(c, a_table, w_scale_dtype, GemmA6W4Cfg<2, 4>::lds_fc1(G, xe.a.shift), xe)
-                     : launch_a6w4<4>(c, a_table, w_scale_dtype, GemmA6W4Cfg<4, 4>::lds_fc1(G, xe.a.shift), xe);
+                     ? launch_a6w4<2>(c, a_table, w_scale_dtype, GemmA6W4Cfg<2, 4>::lds_fc1(G, xe.a.shift), xe, km)
+                     : launch_a6w4<4>(c, a_table, w_scale_dtype, GemmA6W4Cfg<4, 4>::lds_fc1(G, xe.a.shift), xe, km);
   if (rc) return rc;
   return nan_flag ? fpq_internal_zero_if_flag(out, tokens * outs * 2, nan_flag, stream) : FPQ_OK;
+}
+int fpq_gemm_a6w4_gelu_dual(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                            int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs, int64_t k,
+                            void* nan_flag, fpq_stream_t stream) {
+  return gemm_a6w4_gelu_dual_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, bias, out, gelu_out, tokens, outs, k, nan_flag,
+                                  false, stream);
+}
+int fpq_gemm_a6w4_gelu_dual_km(const uint8_t* a_image, const void* a_scales, int a_table, const uint8_t* w_image, const void* w_scales,
+                               int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs, int64_t k,
+                               void* nan_flag, fpq_stream_t stream) {
+  return gemm_a6w4_gelu_dual_impl(a_image, a_scales, a_table, w_image, w_scales, w_scale_dtype, bias, out, gelu_out, tokens, outs, k, nan_flag,
+                                  true, stream);
 }
 
 static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,

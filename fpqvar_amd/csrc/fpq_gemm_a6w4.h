@@ -21,6 +21,10 @@
 // gemm_fp4_glds_kernel (FPQ_GEMM_FC1_TAIL, fpq_gemm_fp4.h: same 128-wide, 128-aligned tiles, same lane-to-output mapping, same
 // two-stage ring whose idle buffer takes the maxima exchange), so fc2's input is bit-equal to the stand-alone quantizer on the
 // same GELU values whichever GEMM computed fc1.
+// Each form also on K-MAJOR IMAGES (FPQ_A6W4_KM; include/fpq.h): gemm_a6w4_km_kernel, gemm_a6w4_fc1_km_kernel - the activation
+// side's 6-bit image, the FP4 GEMM's dealt weight image and both fp32 scale images, so that one stored k-major FP4 weight
+// serves both GEMMs as the row-major one does.  Same main loop, same epilogues, same bits.
+#define FPQ_A6W4_KM 0
 #define FPQ_A6W4_KERNEL gemm_a6w4_kernel
 #define FPQ_A6W4_FC1 0
 #include "fpq_gemm_a6w4_kernel.h"
@@ -31,6 +35,19 @@
 #include "fpq_gemm_a6w4_kernel.h"
 #undef FPQ_A6W4_KERNEL
 #undef FPQ_A6W4_FC1
+#undef FPQ_A6W4_KM
+#define FPQ_A6W4_KM 1
+#define FPQ_A6W4_KERNEL gemm_a6w4_km_kernel
+#define FPQ_A6W4_FC1 0
+#include "fpq_gemm_a6w4_kernel.h"
+#undef FPQ_A6W4_KERNEL
+#undef FPQ_A6W4_FC1
+#define FPQ_A6W4_KERNEL gemm_a6w4_fc1_km_kernel
+#define FPQ_A6W4_FC1 1
+#include "fpq_gemm_a6w4_kernel.h"
+#undef FPQ_A6W4_KERNEL
+#undef FPQ_A6W4_FC1
+#undef FPQ_A6W4_KM
 
 template <int MT, int NT>
 struct GemmA6W4Cfg {

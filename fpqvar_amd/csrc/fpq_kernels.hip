@@ -1594,6 +1594,23 @@ int fpq_quant_rows_codes_g6(const void* x, uint8_t* codes, void* scales, int64_t
   });
 }
 
+// the same quantization of fp16 rows straight into the A6W4 GEMM's k-major images (group6_km_emit16_kernel, include/fpq.h)
+int fpq_a6w4_quant_rows_codes_km(const void* x, uint8_t* image, void* scales, int64_t rows, int64_t cols, int table_id, int in_dtype,
+                               fpq_stream_t stream) {
+  if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
+  if (table_id != FPQ_E1M2 && table_id != FPQ_E3M0) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype) || in_dtype != FPQ_F16) return FPQ_ERR_DTYPE;   // fp32 rows: fpq_quant_rows_codes_g6 + fpq_codes_to_kmajor
+  if (cols % 128 != 0 || !km_image_fits(rows, cols / 4 * 3)) return FPQ_ERR_SHAPE;
+  if (rows == 0 || cols == 0) return FPQ_OK;
+  if (!x || !image || !scales) return FPQ_ERR_ARG;
+  if ((((uintptr_t)x | (uintptr_t)image | (uintptr_t)scales) & 15) != 0) return FPQ_ERR_ARG;
+  const Lut16Host& h = lut16_host(table_id, table_id);
+  if (!h.tab_valid) return FPQ_ERR_TABLE;
+  const int64_t units = (rows + 15) / 16 * (cols / 128);
+  return launch(group6_km_emit16_kernel, grid_for(units, 16384), 0, (hipStream_t)stream, x, image, scales, h.args, lut16_codes_g6(table_id),
+                (uint32_t)rows, fast_div((uint32_t)(cols / 128)));
+}
+
 int fpq_kv_pack(uint8_t* codes, void* scales, int kv_bit, int64_t batch, int64_t max_len, int64_t heads, int64_t head_dim, int64_t pos,
                 const void* new_k, const void* new_v, int64_t new_batch_pitch, int64_t new_token_pitch, int64_t n_new,
                 fpq_stream_t stream) {

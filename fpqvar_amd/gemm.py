@@ -6,6 +6,7 @@ the product runs on MI355X's block-scaled FP4 matrix cores (`fpq_gemm_fp4_mx`).
 """
 from __future__ import annotations
 
+from functools import partial
 from typing import Optional, Tuple
 
 import torch
@@ -344,10 +345,12 @@ def _g6_table(name: str, table: str) -> str:
         raise RuntimeError(f"{name}: the per-group 6-bit activation tables are 'e1m2' and 'e3m0', got {table!r}") from None
 
 
-def quantize_g6(x: torch.Tensor, table: str = "e3m0") -> Tuple[torch.Tensor, torch.Tensor]:
+def quantize_g6(x: torch.Tensor, table: str = "e3m0", kmajor: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """x [..., K] fp16/fp32 (K % 128 == 0) -> (codes uint8 [rows, K * 3 / 4]: dense 6-bit codes of the E1M2 / E3M0 levels,
     scales [rows, K/128] in x.dtype); level(code) * scale == fp_quant_e1_per_group_cuda / fp_quant_e3_per_group_cuda (x, 4, 128)
-    bit for bit (fpq_quant_rows_codes_g6)."""
+    bit for bit (fpq_quant_rows_codes_g6).
+    kmajor: the activation side's k-major images instead (fpq_a6w4_quant_rows_codes_km) - codes [K/128, rows, 96] and scales fp32
+    [K/128, rows rounded up to 4], what linear_a6w4_km takes."""
     require_gpu(x, "quantize_g6")
     if x.dtype not in (torch.float16, torch.float32):
         raise RuntimeError(f"quantize_g6: x must be float16 or float32, got {x.dtype}")
@@ -356,13 +359,16 @@ def quantize_g6(x: torch.Tensor, table: str = "e3m0") -> Tuple[torch.Tensor, tor
     k = x.shape[-1]
     if k % 128 != 0:
         raise RuntimeError("quantize_g6: the last dimension must be a multiple of 128")
+    if kmajor and x.dtype == torch.float32:   # the image-writing emitter takes fp16 rows (activations); fp32 rows: two steps
+        codes, scales = quantize_g6(x, table)
+        return to_kmajor(codes, 6), to_kmajor_scales(scales)
     xc = x.contiguous()
     rows = xc.numel() // k
-    codes = torch.empty((rows, k * 3 // 4), dtype=torch.uint8, device=x.device)
-    scales = torch.empty((rows, k // 128), dtype=x.dtype, device=x.device)
+    codes = torch.empty((k // 128, rows, 96) if kmajor else (rows, k * 3 // 4), dtype=torch.uint8, device=x.device)
+    scales = kmajor_mx_scales(rows, k, x.device) if kmajor else torch.empty((rows, k // 128), dtype=x.dtype, device=x.device)
+    fn, what = (lib().fpq_a6w4_quant_rows_codes_km, "fpq_a6w4_quant_rows_codes_km") if kmajor else (lib().fpq_quant_rows_codes_g6, "fpq_quant_rows_codes_g6")
     with device_guard(x.device):
-        check(lib().fpq_quant_rows_codes_g6(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, k, TABLE_IDS[table],
-                                            dtype_id(x.dtype), stream_ptr(x.device)), "fpq_quant_rows_codes_g6")
+        check(fn(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, k, TABLE_IDS[table], dtype_id(x.dtype), stream_ptr(x.device)), what)
     return codes, scales
 
 
@@ -377,7 +383,7 @@ def dequantize_g6(codes: torch.Tensor, scales: torch.Tensor, table: str = "e3m0"
 def _a6w4_operands(name: str, a_codes, a_scales, w_codes, w_scales):
     """An A6W4 operand pair (6-bit activation codes, FP4 weight nibbles; row-major), checked -> (tokens, outs, k)"""
     if a_codes.dim() != 2 or w_codes.dim() != 2:
-        raise RuntimeError(f"{name}: row-major operands only (there is no k-major A6W4 form)")
+        raise RuntimeError(f"{name}: row-major operands only (k-major images: {name}_km)")
     tokens, outs, k = a_codes.shape[0], w_codes.shape[0], w_codes.shape[1] * 2
     if k % 128 != 0 or a_codes.shape[1] * 4 != k * 3 or a_scales.dtype != torch.float16:
         raise RuntimeError(f"{name}: operand shapes / activation scale dtype mismatch")
@@ -433,6 +439,63 @@ def linear_a6w4_gelu_dual(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table
     return (out, h) if return_gelu else out
 
 
+def _a6w4_km_operands(name: str, a_image, a_scales, w_image, w_scales, bias, outs):
+    """An A6W4 operand pair as k-major images (6-bit activation image [G, tokens, 96], the FP4 GEMM's dealt weight image
+    [G, rows64, 64], both fp32 scale images), checked -> (tokens, outs, k); `outs` as in _check_kmajor_fp4"""
+    if a_image.dim() != 3 or w_image.dim() != 3:
+        raise RuntimeError(f"{name}: both operands must be k-major images (3-D); row-major codes go to {name[:-3]}")
+    if a_image.shape[2] != 96 or w_image.shape[2] != 64 or a_image.shape[0] != w_image.shape[0] or w_image.shape[1] % 64 != 0:
+        raise RuntimeError(f"{name}: k-major images must be [K/128, tokens, 96] (activation) and [K/128, rows, 64] (weight) with the same K "
+                           "and a weight image of a multiple of 64 rows")
+    return _check_kmajor_fp4(name, a_image, a_scales, w_image, w_scales, bias, outs)
+
+
+def linear_a6w4_km(a_image: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_image: torch.Tensor, w_scales: torch.Tensor,
+                   bias: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
+                   residual: Optional[torch.Tensor] = None, outs: Optional[int] = None) -> torch.Tensor:
+    """linear_a6w4 on k-major images (fpq_gemm_a6w4_mx_km), bit for bit the same result: the activation as `quantize_g6(x, table,
+    kmajor=True)` emits it, the weight exactly as a k-major FP4Linear holds it (`to_kmajor(codes, 4, dealt=True)`,
+    `to_kmajor_scales(scales, weight_side=True)`).  outs: the Linear's width when it is neither the bias's length nor the weight
+    image's row count (a multiple of 64), as in linear_fp4."""
+    require_gpu(a_image, "linear_a6w4_km")
+    from ._lib import TABLE_IDS
+    a_table = _g6_table("linear_a6w4_km", a_table)
+    tokens, outs, k = _a6w4_km_operands("linear_a6w4_km", a_image, a_scales, w_image, w_scales, bias, outs)
+    ep, keep, out = _epilogue("linear_a6w4_km", tokens, outs, gate, residual, None, a_image.device)
+    b = _bias_f16("linear_a6w4_km", bias, outs, a_image.device, 8)
+    with device_guard(a_image.device):
+        check(lib().fpq_gemm_a6w4_mx_km(a_image.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_image.data_ptr(), w_scales.data_ptr(),
+                                        dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), out.data_ptr(), tokens, outs, k, ep,
+                                        stream_ptr(a_image.device)), "fpq_gemm_a6w4_mx_km")
+    del keep
+    return out
+
+
+def linear_a6w4_gelu_dual_km(a_image: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_image: torch.Tensor, w_scales: torch.Tensor,
+                             bias: Optional[torch.Tensor] = None, return_gelu: bool = False, outs: Optional[int] = None):
+    """linear_a6w4_gelu_dual on k-major images (fpq_gemm_a6w4_gelu_dual_km), bit for bit the same result; operands as in
+    linear_a6w4_km, return_gelu as in linear_a6w4_gelu_dual."""
+    require_gpu(a_image, "linear_a6w4_gelu_dual_km")
+    from ._lib import TABLE_IDS
+    a_table = _g6_table("linear_a6w4_gelu_dual_km", a_table)
+    dev = a_image.device
+    tokens, outs, k = _a6w4_km_operands("linear_a6w4_gelu_dual_km", a_image, a_scales, w_image, w_scales, bias, outs)
+    if outs % 128 != 0:
+        raise RuntimeError("linear_a6w4_gelu_dual_km: outs must be a multiple of 128")
+    out = torch.empty((tokens, outs), dtype=torch.float16, device=dev)
+    h = torch.empty((tokens, outs), dtype=torch.float16, device=dev) if return_gelu else None
+    b = _bias_f16("linear_a6w4_gelu_dual_km", bias, outs, dev, 8)
+    if tokens and outs:
+        from .ops import _nan_scratch
+        with device_guard(dev):
+            flag = _nan_scratch(dev)
+            check(lib().fpq_gemm_a6w4_gelu_dual_km(a_image.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_image.data_ptr(),
+                                                   w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(),
+                                                   out.data_ptr(), None if h is None else h.data_ptr(), tokens, outs, k, flag.data_ptr(),
+                                                   stream_ptr(dev)), "fpq_gemm_a6w4_gelu_dual_km")
+    return (out, h) if return_gelu else out
+
+
 class FP4Linear(_ScaledOperandModule):
     """Drop-in for QuantizedLinear in the W4A4 per-group `fp_e2` configuration that runs on the FP4
     matrix cores instead of simulating FP4 in fp16: weights are stored as hardware E2M1 codes + one
@@ -455,17 +518,18 @@ class FP4Linear(_ScaledOperandModule):
         return self.w_codes.dim() == 3
 
     @classmethod
-    def from_float(cls, module: torch.nn.Linear, kmajor: bool = False, act_fp_type: str = "fp_e2"):
+    def from_float(cls, module: torch.nn.Linear, kmajor: bool = False, act_fp_type: str = "fp_e2", a6w4_kmajor: bool = False):
         """act_fp_type: the activation's per-group format - "fp_e2" (E2M1, the FP4 GEMM) or "fp_e1" / "fp_e3" (E1M2 / E3M0: the
-        A6W4 GEMM on the same stored weight, row-major only)."""
+        A6W4 GEMM on the same stored weight - row-major unless a6w4_kmajor, which lets kmajor=True hold the FP4 GEMM's k-major
+        weight images for it and run quantize_g6(kmajor=True) + linear_a6w4_km)."""
         assert isinstance(module, torch.nn.Linear) and module.in_features % 128 == 0 and module.out_features % 8 == 0
         if act_fp_type in ("fp_e2", "e2m1"):
             act_table = "e2m1"
         else:
             act_table = _g6_table("FP4Linear.from_float", act_fp_type)
-            if kmajor:
+            if kmajor and not a6w4_kmajor:
                 raise ValueError(f"FP4Linear.from_float: act_fp_type={act_fp_type!r} runs on the A6W4 GEMM, which has no k-major form "
-                                 "(kmajor=True needs act_fp_type='fp_e2')")
+                                 "unless a6w4_kmajor=True asks for it (kmajor=True alone needs act_fp_type='fp_e2')")
         codes, scales = quantize_mx(module.weight.detach().float())
         if kmajor:
             codes, scales = to_kmajor(codes, 4, dealt=True), to_kmajor_scales(scales, weight_side=True)
@@ -481,8 +545,11 @@ class FP4Linear(_ScaledOperandModule):
         lead = x.shape[:-1]
         x2 = x.to(torch.float16).reshape(-1, self.in_features)
         if self.act_table != "e2m1":
-            a_codes, a_scales = quantize_g6(x2, self.act_table)
-            y = linear_a6w4(a_codes, a_scales, self.act_table, self.w_codes, self.w_scales, self.bias, gate, residual)
+            a_codes, a_scales = quantize_g6(x2, self.act_table, kmajor=self.kmajor)
+            if self.kmajor:
+                y = linear_a6w4_km(a_codes, a_scales, self.act_table, self.w_codes, self.w_scales, self.bias, gate, residual, outs=self.out_features)
+            else:
+                y = linear_a6w4(a_codes, a_scales, self.act_table, self.w_codes, self.w_scales, self.bias, gate, residual)
             return y.view(*lead, self.out_features)
         a_codes, a_scales = quantize_mx(x2, kmajor=self.kmajor)
         y = linear_fp4(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, gate, residual, outs=self.out_features)
@@ -496,7 +563,10 @@ class FP4Linear(_ScaledOperandModule):
         table = self.act_table if table is None else ("e2m1" if table in ("e2m1", "fp_e2") else _g6_table("FP4Linear.forward_operands", table))
         if table != "e2m1":
             if self.kmajor:
-                raise RuntimeError("FP4Linear.forward_operands: 6-bit activation codes need a row-major weight (no k-major A6W4 form)")
+                if a_codes.dim() != 3:
+                    raise RuntimeError("FP4Linear.forward_operands: the weight is a k-major image - 6-bit activation codes must come as "
+                                       "the k-major images of quantize_g6(kmajor=True), not as row-major codes")
+                return linear_a6w4_km(a_codes, a_scales, table, self.w_codes, self.w_scales, self.bias, gate, residual, outs=self.out_features)
             return linear_a6w4(a_codes, a_scales, table, self.w_codes, self.w_scales, self.bias, gate, residual)
         return linear_fp4(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, gate, residual, outs=self.out_features)
 
@@ -507,15 +577,17 @@ class FP4LinearGeluDual(FP4Linear):
     `fc2.act_quant(act(fc1(x)))` returns in the reference's FFN.forward (tr/basic_var.py:120-121) - the module that follows
     must neither apply the activation nor quantize again (`quant_linear.quantize_VAR(..., real_fp4=True, fuse_ffn=True)` swaps
     the FFN's `act` for an identity and switches fc2's input quantizer off).  With an E1M2 / E3M0 activation format
-    (`from_float(..., act_fp_type="fp_e1" / "fp_e3")`, row-major) the same tail runs in the A6W4 GEMM (`linear_a6w4_gelu_dual`)."""
+    (`from_float(..., act_fp_type="fp_e1" / "fp_e3")`; row-major, or k-major with `a6w4_kmajor=True`) the same tail runs in the A6W4
+    GEMM (`linear_a6w4_gelu_dual` / `linear_a6w4_gelu_dual_km`)."""
 
     @torch.no_grad()
     def forward(self, x):
         lead = x.shape[:-1]
         x2 = x.to(torch.float16).reshape(-1, self.in_features)
         if self.act_table != "e2m1":   # 6-bit codes on the A6W4 GEMM, whose fc1 form has the same tail
-            a_codes, a_scales = quantize_g6(x2, self.act_table)
-            return linear_a6w4_gelu_dual(a_codes, a_scales, self.act_table, self.w_codes, self.w_scales, self.bias).view(*lead, self.out_features)
+            a_codes, a_scales = quantize_g6(x2, self.act_table, kmajor=self.kmajor)
+            fc1 = partial(linear_a6w4_gelu_dual_km, outs=self.out_features) if self.kmajor else linear_a6w4_gelu_dual
+            return fc1(a_codes, a_scales, self.act_table, self.w_codes, self.w_scales, self.bias).view(*lead, self.out_features)
         a_codes, a_scales = quantize_mx(x2, kmajor=self.kmajor)
         return linear_fp4_gelu_dual(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, outs=self.out_features).view(*lead, self.out_features)
 
@@ -525,7 +597,10 @@ class FP4LinearGeluDual(FP4Linear):
         table = self.act_table if table is None else ("e2m1" if table in ("e2m1", "fp_e2") else _g6_table("FP4LinearGeluDual.forward_operands", table))
         if table != "e2m1":
             if self.kmajor:
-                raise RuntimeError("FP4LinearGeluDual.forward_operands: 6-bit activation codes need a row-major weight (no k-major A6W4 form)")
+                if a_codes.dim() != 3:
+                    raise RuntimeError("FP4LinearGeluDual.forward_operands: the weight is a k-major image - 6-bit activation codes must "
+                                       "come as the k-major images of quantize_g6(kmajor=True), not as row-major codes")
+                return linear_a6w4_gelu_dual_km(a_codes, a_scales, table, self.w_codes, self.w_scales, self.bias, outs=self.out_features)
             return linear_a6w4_gelu_dual(a_codes, a_scales, table, self.w_codes, self.w_scales, self.bias)
         return linear_fp4_gelu_dual(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, outs=self.out_features)
 

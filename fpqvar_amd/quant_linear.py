@@ -267,7 +267,7 @@ _FP6_SYMMETRIC = ("fp6_e2m3", "fp6_e3m2")
 
 def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, w_bit=8, a_bit=8, act_quant_sym=None,
                        fc2_act_log2_quant=None, activation_fp_quant=False, weight_fp_quant=False,
-                       ada_lin_formats=None, real_fp6=False, kmajor_operands=True, real_fp4=False, fuse_ffn=False):
+                       ada_lin_formats=None, real_fp6=False, kmajor_operands=True, real_fp4=False, fuse_ffn=False, a6w4_kmajor=False):
     """quantize_VAR with a format pair per (block, layer): ``layer_formats(block_idx, layer)`` returns
     ``(act_fp_type, weight_fp_type)`` for layer in {"fc1", "fc2", "mat_qkv", "proj"}.  ``ada_lin_formats``:
     None leaves the AdaLN Linear in full precision (as tr/ does), a pair quantizes ``ada_lin[1]`` (as the fq/ and
@@ -281,8 +281,12 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
     ``real_fp4`` (additive, default off; the W4A4 per-group configuration as in quantize_VAR): every layer with an ``fp_e2`` weight
     and an ``fp_e1`` / ``fp_e2`` / ``fp_e3`` activation whose shape fits the GEMM becomes a ``gemm.FP4Linear`` of its activation
     format - ``fp_e2`` on the FP4 GEMM (k-major with ``kmajor_operands``), ``fp_e1`` / ``fp_e3`` as 6-bit codes on the A6W4 GEMM
-    against the same stored E2M1 weight (row-major: that GEMM has no k-major form).  Every other layer (fc2's dual format,
+    against the same stored E2M1 weight (row-major unless ``a6w4_kmajor``).  Every other layer (fc2's dual format,
     ``ada_lin[1]``, an E1M2 / E3M0 weight) stays the QuantizedLinear it is without the keyword.
+
+    ``a6w4_kmajor`` (additive, default off; with ``real_fp4`` and ``kmajor_operands``): the ``fp_e1`` / ``fp_e3`` layers hold the FP4
+    GEMM's k-major weight images too and run the A6W4 GEMM's k-major form (``gemm.linear_a6w4_km``) - one weight layout in the
+    model, the same bits.
 
     ``fuse_ffn`` (additive, default off): quantize_VAR's rules, per FFN - the FFN's ``act`` must be GELU(tanh).  With ``real_fp4``,
     where fc1 qualifies for ``gemm.FP4Linear`` with out_features % 128 == 0 and the block's fc2 activation format is
@@ -302,13 +306,18 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
     common = dict(weight_quant=weight_quant, act_quant=act_quant, w_bit=w_bit, a_bit=a_bit,
                   activation_fp_quant=activation_fp_quant, weight_fp_quant=weight_fp_quant)
 
+    def fp4_layer(cls, lin, a):   # a gemm.FP4Linear / FP4LinearGeluDual of activation format a
+        if a != "fp_e2" and kmajor_operands and a6w4_kmajor:
+            return cls.from_float(lin, kmajor=True, act_fp_type=a, a6w4_kmajor=True)
+        return cls.from_float(lin, kmajor=kmajor_operands and a == "fp_e2", act_fp_type=a)
+
     def layer(cls, lin, a, w, **kw):
         if (fp6_ok and a in _FP6_SYMMETRIC and w in _FP6_SYMMETRIC and lin.in_features % 128 == 0 and lin.out_features % 8 == 0):
             from .gemm import FP6Linear
             return FP6Linear.from_float(lin, kmajor=kmajor_operands, weight_fp_type=w, act_fp_type=a)
         if (fp4_ok and w == "fp_e2" and a in ("fp_e1", "fp_e2", "fp_e3") and lin.in_features % 128 == 0 and lin.out_features % 8 == 0):
             from .gemm import FP4Linear
-            return FP4Linear.from_float(lin, kmajor=kmajor_operands and a == "fp_e2", act_fp_type=a)
+            return fp4_layer(FP4Linear, lin, a)
         return cls.from_float(lin, act_fp_type=a, weight_fp_type=w, **kw, **common)
 
     for name, m in list(model.named_modules()):
@@ -330,7 +339,7 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
                                  "(fp_e1m2_neg_e2m1_pos / fp4_afpq per group, fp6_int_neg_e2m3_pos per group or per token)")
             if in_gemm:
                 from .gemm import FP4LinearGeluDual
-                m.fc1 = FP4LinearGeluDual.from_float(fc1, kmajor=kmajor_operands and a == "fp_e2", act_fp_type=a)
+                m.fc1 = fp4_layer(FP4LinearGeluDual, fc1, a)
             else:
                 m.fc1 = layer(QuantizedLinear, fc1, a, w, act_quant_sym=act_quant_sym)
             m.fc2 = layer(QuantizedLinear_fc2, fc2, a2, w2, act_quant_sym=False, fc2_act_log2_quant=fc2_act_log2_quant)
@@ -357,13 +366,15 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
 def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,
                                     a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                     activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
-                                    weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True, fuse_ffn=False):
+                                    weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True, fuse_ffn=False,
+                                    a6w4_kmajor=False):
     """models_fp_quant/quant_utils.py:1256-1341: fc1 is E2M1 in blocks 6-20 and E3M0 elsewhere, mat_qkv E2M1 in
     blocks 0, 24, 25 and E3M0 elsewhere (activations; weights always E2M1); proj, fc2 and ada_lin[1] take the
     caller's formats.
     ``real_fp4`` / ``kmajor_operands``: as in quantize_VAR_mixed - every E2M1-weight fc1 / mat_qkv / proj on the matrix cores,
     the E3M0 activations as 6-bit codes.  ``fuse_ffn``: as in quantize_VAR_mixed - with ``real_fp4`` and ``fc2_fp_type`` =
-    ``fp_e1m2_neg_e2m1_pos`` every fc1 runs its GELU and fc2's input quantizer in its GEMM's epilogue."""
+    ``fp_e1m2_neg_e2m1_pos`` every fc1 runs its GELU and fc2's input quantizer in its GEMM's epilogue.  ``a6w4_kmajor``: as in
+    quantize_VAR_mixed - the E3M0-activation layers on k-major images too."""
     fc1_e2, qkv_e2 = set(range(6, 21)), {0, 24, 25}
 
     def fmt(b, layer):
@@ -377,17 +388,19 @@ def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, qu
 
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
                               activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type),
-                              real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn)
+                              real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn, a6w4_kmajor=a6w4_kmajor)
 
 
 def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,
                                         a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                         activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
-                                        weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True, fuse_ffn=False):
+                                        weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True, fuse_ffn=False,
+                                        a6w4_kmajor=False):
     """models_fp_quant_rotate/quant_utils.py:982-1066: as the mixed FP4 variant, with mat_qkv E2M1 in blocks 24, 25 only.
     ``real_fp4`` / ``kmajor_operands``: as in quantize_VAR_mixed - every E2M1-weight fc1 / mat_qkv / proj on the matrix cores,
     the E3M0 activations as 6-bit codes.  ``fuse_ffn``: as in quantize_VAR_mixed - with ``real_fp4`` and ``fc2_fp_type`` =
-    ``fp_e1m2_neg_e2m1_pos`` every fc1 runs its GELU and fc2's input quantizer in its GEMM's epilogue."""
+    ``fp_e1m2_neg_e2m1_pos`` every fc1 runs its GELU and fc2's input quantizer in its GEMM's epilogue.  ``a6w4_kmajor``: as in
+    quantize_VAR_mixed - the E3M0-activation layers on k-major images too."""
     fc1_e2, qkv_e2 = set(range(6, 21)), {24, 25}
 
     def fmt(b, layer):
@@ -401,7 +414,7 @@ def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None
 
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
                               activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type),
-                              real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn)
+                              real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn, a6w4_kmajor=a6w4_kmajor)
 
 
 def quantize_VAR_mixed_fp6_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FPQ_VERSION 132 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
+#define FPQ_VERSION 133 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
                            0.1.3: + fpq_quant_rows_codes_segments, fpq_dequant_rows_codes_segments (round 3);
                            123: + fpq_build_tag (round 4);
                            124: + fpq_set_option, fpq_get_option, fpq_option_name, fpq_gemm_fp4_gelu_dual, fpq_gelu_quant_rows_dual (round 5);
@@ -39,7 +39,8 @@ extern "C" {
                                 fpq_adaln_rotate_quant_token_rows_codes_f6, fpq_gemm_f6_rows, fpq_gemm_f6_rows_split, fpq_gemm_f6_rows_split_qknorm;
                            131: + E1M2 / E3M0 activations on the matrix cores against FP4 weights ("A6W4"): fpq_quant_rows_codes_g6,
                                 fpq_gemm_a6w4_mx;
-                           132: + the fc1 tail (GELU + fc2's dual-format input quantizer) in the A6W4 GEMM: fpq_gemm_a6w4_gelu_dual */
+                           132: + the fc1 tail (GELU + fc2's dual-format input quantizer) in the A6W4 GEMM: fpq_gemm_a6w4_gelu_dual;
+                           133: + the A6W4 path on k-major images: fpq_a6w4_quant_rows_codes_km, fpq_gemm_a6w4_mx_km, fpq_gemm_a6w4_gelu_dual_km */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -682,7 +683,8 @@ int fpq_gemm_f6_rows_split_qknorm(const uint8_t* a_codes, const void* a_scales, 
  * w_codes / w_scales / w_scale_dtype exactly what fpq_gemm_fp4_mx takes (E2M1 nibbles [outs, k / 2], blgp = 4): one stored FP4
  * weight serves both GEMMs.  Shape and alignment rules of fpq_gemm_fp4_mx_ex (k % 128 == 0, k <= 8192, outs % 8 == 0, codes and
  * out 16-byte aligned), checked before any launch; the bias must be 8-byte aligned (there is no register-staged form to fall
- * back to).  Row-major operands only: no k-major images, no split output, no q / k norm; the fc1 tail: fpq_gemm_a6w4_gelu_dual.
+ * back to).  Row-major operands; k-major images: fpq_gemm_a6w4_mx_km below.  No split output, no q / k norm; the fc1 tail:
+ * fpq_gemm_a6w4_gelu_dual.
  * Numerics: the per-group steps of fpq_gemm_fp4_mx's LDS-DMA tilings - t = fl(d_g sa), acc = fma(t, sw, acc), out = fp16(acc +
  * bias).  Products of an E3M0 or E1M2 level and an E2M1 level are multiples of 1/8 (|product| <= 96 resp. 10.5), so the exact
  * 128-term dot d_g has at most 17 significant bits (|d_g| <= 12288) and fits the fp32 accumulator.
@@ -702,7 +704,7 @@ int fpq_gemm_a6w4_mx(const uint8_t* a_codes, const void* a_scales, int a_table, 
  * E2M1+ per-group(128) input quantizer in ONE launch (+ the NaN fix-up launch): out = fp16 [tokens, outs] =
  * fp_quant_e1m2_neg_e2m1_pos_per_group_cuda(gelu_tanh(y), 4, 128) with y the fp16 [tokens, outs] that fpq_gemm_a6w4_mx writes for
  * the same operands and bias, bit for bit.  Operands (a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, bias) exactly
- * fpq_gemm_a6w4_mx's, row-major; the tail, gelu_out (NULL, or fp16 [tokens, outs], 16-byte aligned: the GELU values the quantizer
+ * fpq_gemm_a6w4_mx's, row-major; (k-major images: fpq_gemm_a6w4_gelu_dual_km below); the tail, gelu_out (NULL, or fp16 [tokens, outs], 16-byte aligned: the GELU values the quantizer
  * saw), nan_flag (NULL, or the 8-byte zeroed scratch of fpq_quant_rows_dual: a NaN in any live row makes the whole result +0 and
  * the scratch is zero again afterwards) exactly fpq_gemm_fp4_gelu_dual's - the same GELU of the same fp16 value and the same
  * quantizer arithmetic, so the two entry points agree bit for bit wherever their Linear outputs do.
@@ -713,6 +715,34 @@ int fpq_gemm_a6w4_mx(const uint8_t* a_codes, const void* a_scales, int a_table, 
 int fpq_gemm_a6w4_gelu_dual(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes,
                             const void* w_scales, int w_scale_dtype, const void* bias, void* out, void* gelu_out,
                             int64_t tokens, int64_t outs, int64_t k, void* nan_flag, fpq_stream_t stream);
+
+/* THE A6W4 PATH ON K-MAJOR IMAGES ("K-MAJOR OPERAND IMAGES" above) - same arithmetic, same results bit for bit as the three row-major
+ * entry points (tests/test_gpu_a6w4_km.py):
+ *   activation codes   the activation side's 6-bit image [k / 128][rows][96] (chunk order c = (p - ((j >> 3) & 1)) mod 6, no row
+ *                      padding): what fpq_codes_to_kmajor(code_bits = 6, dealt = 0) makes of fpq_quant_rows_codes_g6's codes
+ *   activation scales  the fp32 k-major scale image [k / 128][rows rounded up to 4], padding 0
+ *   weights            exactly what fpq_gemm_fp4_mx_km takes: the dealt 4-bit image (rows rounded up to 64) and the fp32 weight-side
+ *                      scale image - one stored k-major FP4 weight serves both GEMMs, as the row-major one does
+ * fpq_a6w4_quant_rows_codes_km: fpq_quant_rows_codes_g6 writing the two activation images directly (padding rows of the scale image
+ * are not written).  fp16 rows only (fp32 rows: fpq_quant_rows_codes_g6 + fpq_codes_to_kmajor + fpq_scales_to_kmajor).  Checks, in
+ * this order: negative sizes (FPQ_ERR_ARG), table_id (FPQ_ERR_TABLE), in_dtype other than FPQ_F16 (FPQ_ERR_DTYPE), cols % 128 or an
+ * image of 2 GiB or more (FPQ_ERR_SHAPE), rows == 0 or cols == 0 (FPQ_OK), then NULL pointers / x, image or scales not 16-byte
+ * aligned (FPQ_ERR_ARG).
+ * fpq_gemm_a6w4_mx_km / fpq_gemm_a6w4_gelu_dual_km: fpq_gemm_a6w4_mx / fpq_gemm_a6w4_gelu_dual on those images; bias, out, epilogue,
+ * gelu_out, nan_flag unchanged.  Checks, in this order, before any launch: a_table (FPQ_ERR_TABLE), negative sizes (FPQ_ERR_ARG),
+ * [_mx_km: the epilogue descriptor (FPQ_ERR_ARG)], w_scale_dtype other than FPQ_F32 (FPQ_ERR_DTYPE: the scale images are fp32), shape
+ * (FPQ_ERR_SHAPE: the row-major entry point's rules - k % 128, k > 8192, outs % 8 resp. outs % 128, an LDS image above 160 KiB -, then
+ * tokens or outs at or above 2^28: the scale images are addressed by 32-bit lane offsets), tokens == 0 or outs == 0 (FPQ_OK), then
+ * NULL pointers / alignment (FPQ_ERR_ARG; images, out and gelu_out 16 bytes, bias and nan_flag 8, both scale images 16).  The weight
+ * image has outs rounded up to 64 rows.  Tilings as fpq_gemm_a6w4_mx (FPQ_GEMM_CFG 20 / 30 forces one); both give the same bits. */
+int fpq_a6w4_quant_rows_codes_km(const void* x, uint8_t* image, void* scales, int64_t rows, int64_t cols, int table_id, int in_dtype,
+                               fpq_stream_t stream);
+int fpq_gemm_a6w4_mx_km(const uint8_t* a_image, const void* a_scales, int a_table, const uint8_t* w_image, const void* w_scales,
+                        int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
+                        const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream);
+int fpq_gemm_a6w4_gelu_dual_km(const uint8_t* a_image, const void* a_scales, int a_table, const uint8_t* w_image,
+                               const void* w_scales, int w_scale_dtype, const void* bias, void* out, void* gelu_out,
+                               int64_t tokens, int64_t outs, int64_t k, void* nan_flag, fpq_stream_t stream);
 
 /* fpq_kv_cache_step_qknorm: fpq_kv_cache_step (same arguments, same checks) for an fp16 qkv WITHOUT the norm (path F, or a
  * mat_qkv that is not split): the new k is normalized and the bias added on its way into the cache, and the same launch writes
