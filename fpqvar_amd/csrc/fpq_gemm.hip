@@ -143,30 +143,47 @@ int launch_fp4_staged(const GemmCall& c, int w_scale_dtype) {
 }
 // 6-bit activations x FP4 weights, 32 MT x 128 tiles and epilogue XE (GemmNoFc1: the plain kernel; GemmFc1: its fc1 form); a_table:
 // FPQ_E1M2 (as FP6 E2M3 codes, cbsz 2) or FPQ_E3M0 (BF6 E3M2, 3); lds: GemmA6W4Cfg's figure for that epilogue.  km: the operands are
-// k-major images (c.epi.km_w_rows set, fp32 scale images: the entry points have checked w_scale_dtype)
+// k-major images (c.epi.km_w_rows set, fp32 scale images: the entry points have checked w_scale_dtype).
+// GemmSplit: the split output (c.epi's sp_* fields set; the kernel takes no further argument), GemmQkNorm: the split output with the
+// q / k norm - both compiled for fp32 weight scales only (fpq_gemm_a6w4.h)
 template <int MT, typename XE>
 int launch_a6w4(const GemmCall& c, int a_table, int w_scale_dtype, size_t lds, XE xe, bool km = false) {
   using Cfg = GemmA6W4Cfg<MT, 4>;
   if (lds > 160 * 1024) return FPQ_ERR_SHAPE;
-  if (km) {
-    if constexpr (__is_same(XE, GemmFc1)) {
-      if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_fc1_km_kernel<float, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
-      return gemm_launch(gemm_a6w4_fc1_km_kernel<float, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
-    } else {
-      if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_km_kernel<float, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c);
-      return gemm_launch(gemm_a6w4_km_kernel<float, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c);
+  if constexpr (__is_same(XE, GemmSplit) || __is_same(XE, GemmQkNorm)) {
+    if (w_scale_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+    auto format = [&](auto fa) {
+      constexpr int FA = decltype(fa)::value;
+      if constexpr (__is_same(XE, GemmQkNorm)) {
+        if (km) return gemm_launch(gemm_a6w4_qkn_km_kernel<float, MT, 4, FA>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+        return gemm_launch(gemm_a6w4_qkn_kernel<float, MT, 4, FA>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+      } else {
+        if (km) return gemm_launch(gemm_a6w4_split_km_kernel<float, MT, 4, FA>, Cfg::BM, Cfg::BN, 256, lds, c);
+        return gemm_launch(gemm_a6w4_split_kernel<float, MT, 4, FA>, Cfg::BM, Cfg::BN, 256, lds, c);
+      }
+    };
+    return a_table == FPQ_E1M2 ? format(Int<2>{}) : format(Int<3>{});
+  } else {
+    if (km) {
+      if constexpr (__is_same(XE, GemmFc1)) {
+        if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_fc1_km_kernel<float, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+        return gemm_launch(gemm_a6w4_fc1_km_kernel<float, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+      } else {
+        if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_km_kernel<float, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c);
+        return gemm_launch(gemm_a6w4_km_kernel<float, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c);
+      }
     }
+    return with_dtype(w_scale_dtype, [&](auto tw) {
+      using Tw = decltype(tw);
+      if constexpr (__is_same(XE, GemmFc1)) {
+        if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_fc1_kernel<Tw, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+        return gemm_launch(gemm_a6w4_fc1_kernel<Tw, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+      } else {
+        if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_kernel<Tw, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c);
+        return gemm_launch(gemm_a6w4_kernel<Tw, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c);
+      }
+    });
   }
-  return with_dtype(w_scale_dtype, [&](auto tw) {
-    using Tw = decltype(tw);
-    if constexpr (__is_same(XE, GemmFc1)) {
-      if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_fc1_kernel<Tw, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
-      return gemm_launch(gemm_a6w4_fc1_kernel<Tw, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
-    } else {
-      if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_kernel<Tw, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c);
-      return gemm_launch(gemm_a6w4_kernel<Tw, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c);
-    }
-  });
 }
 // the row-scaled FP6 kernel for one epilogue and one format pair (FA, FB: cbsz of the activations, blgp of the weights; 2 = E2M3,
 // 3 = E3M2).  A pair with an E3M2 side is compiled for fp16 activation scales only - what the quantizers of activations produce;
@@ -436,28 +453,41 @@ int fpq_gemm_fp4_mx_km(const uint8_t* a_image, const void* a_scales, const uint8
 // km: both operands and both scale tensors are k-major images (include/fpq.h; gemm_a6w4_km_kernel) - the FP4 km rules of
 // gemm_fp4_mx_impl beside the row-major checks: fp32 scale images, 16-byte aligned, tokens and outs below 2^28 (32-bit lane
 // offsets into three planes of the scale images)
+// split / qkn: the split output (fpq_gemm_a6w4_mx_split: the FP6 family's rules - whole batch entries, every part 8-byte aligned) and
+// the q / k norm in front of it; the descriptor is checked where gemm_fp4_mx_impl checks it, behind the sizes and in front of the
+// dtype; those kernels exist for fp32 weight scales only
 static int gemm_a6w4_mx_impl(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
                              int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
-                             const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream) {
+                             const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream, const fpq_gemm_split_t* split = nullptr,
+                             const GemmQkNorm* qkn = nullptr) {
   if (a_table != FPQ_E1M2 && a_table != FPQ_E3M0) return FPQ_ERR_TABLE;
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   GemmEpi epi;
   if (int rc = gemm_epilogue(epilogue, &epi)) return rc;
-  if (km ? w_scale_dtype != FPQ_F32 : (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32)) return FPQ_ERR_DTYPE;
+  if (split) {
+    if (int rc = gemm_split(split, epilogue, tokens, outs, true, &epi)) return rc;
+    out = split->out[0];   // (not written through: every tile belongs to a part)
+  }
+  if ((km || split) ? w_scale_dtype != FPQ_F32 : (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32)) return FPQ_ERR_DTYPE;
   if (k % 128 != 0 || k > 128 * 64 || outs % 8 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
   if (km && (tokens >= (1ll << 28) || outs >= (1ll << 28))) return FPQ_ERR_SHAPE;
   if (tokens == 0 || outs == 0) return FPQ_OK;
   if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
-  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out) & 15) != 0 || ((uintptr_t)bias & 7) != 0) return FPQ_ERR_ARG;
+  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (split ? 0 : (uintptr_t)out)) & 15) != 0 || ((uintptr_t)bias & 7) != 0) return FPQ_ERR_ARG;
   if (km ? (((uintptr_t)a_scales | (uintptr_t)w_scales) & 15) != 0
          : ((uintptr_t)a_scales & 1) != 0 || ((uintptr_t)w_scales & (w_scale_dtype == FPQ_F16 ? 1 : 3)) != 0)
     return FPQ_ERR_ARG;
   if (km) epi.km_w_rows = (int)((outs + 63) / 64 * 64);
   const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
   const int G = (int)(k / 128);
-  if (gemm_glds_tiling(tokens, outs, false, false) == 30)
-    return launch_a6w4<2>(c, a_table, w_scale_dtype, GemmA6W4Cfg<2, 4>::lds(G), GemmNoFc1{}, km);
-  return launch_a6w4<4>(c, a_table, w_scale_dtype, GemmA6W4Cfg<4, 4>::lds(G), GemmNoFc1{}, km);
+  auto tile = [&](auto mt) {
+    constexpr int MT = decltype(mt)::value;
+    const size_t lds = GemmA6W4Cfg<MT, 4>::lds(G);
+    if (qkn) return launch_a6w4<MT>(c, a_table, w_scale_dtype, lds, *qkn, km);
+    if (split) return launch_a6w4<MT>(c, a_table, w_scale_dtype, lds, GemmSplit{}, km);
+    return launch_a6w4<MT>(c, a_table, w_scale_dtype, lds, GemmNoFc1{}, km);
+  };
+  return gemm_glds_tiling(tokens, outs, false, false) == 30 ? tile(Int<2>{}) : tile(Int<4>{});
 }
 int fpq_gemm_a6w4_mx(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
                      int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
@@ -468,6 +498,25 @@ int fpq_gemm_a6w4_mx_km(const uint8_t* a_image, const void* a_scales, int a_tabl
                         int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
                         const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream) {
   return gemm_a6w4_mx_impl(a_image, a_scales, a_table, w_image, w_scales, w_scale_dtype, bias, out, tokens, outs, k, epilogue, true, stream);
+}
+// mat_qkv on the A6W4 GEMM: the split output, and the q / k norm in that epilogue (include/fpq.h); kmajor chooses between the operands
+// of the two entry points above.  The table goes first, as in every A6W4 entry point.
+int fpq_gemm_a6w4_mx_split(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                           int w_scale_dtype, const void* bias, int64_t tokens, int64_t outs, int64_t k, const fpq_gemm_split_t* split,
+                           int kmajor, fpq_stream_t stream) {
+  if (a_table != FPQ_E1M2 && a_table != FPQ_E3M0) return FPQ_ERR_TABLE;
+  if (!split) return FPQ_ERR_ARG;
+  return gemm_a6w4_mx_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, bias, nullptr, tokens, outs, k, nullptr, kmajor != 0,
+                           stream, split);
+}
+int fpq_gemm_a6w4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                                  int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
+                                  const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream) {
+  if (a_table != FPQ_E1M2 && a_table != FPQ_E3M0) return FPQ_ERR_TABLE;
+  GemmQkNorm qkn;
+  if (int rc = gemm_qknorm(split, bias, q_head_scale, &qkn)) return rc;
+  return gemm_a6w4_mx_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, nullptr, nullptr, tokens, outs, k, nullptr, kmajor != 0,
+                           stream, split, &qkn);
 }
 
 #ifdef FPQ_GEMM6_STAMPS

@@ -24,6 +24,12 @@
 // Each form also on K-MAJOR IMAGES (FPQ_A6W4_KM; include/fpq.h): gemm_a6w4_km_kernel, gemm_a6w4_fc1_km_kernel - the activation
 // side's 6-bit image, the FP4 GEMM's dealt weight image and both fp32 scale images, so that one stored k-major FP4 weight
 // serves both GEMMs as the row-major one does.  Same main loop, same epilogues, same bits.
+// mat_qkv's two output forms (FPQ_A6W4_OUT; include/fpq.h, fpq_gemm_a6w4_mx_split / _split_qknorm), row-major and on k-major images:
+// gemm_a6w4_split_kernel / gemm_a6w4_split_km_kernel write the plain epilogue's values to the parts' own destinations,
+// gemm_a6w4_qkn_kernel / gemm_a6w4_qkn_km_kernel with the q / k L2 norm in front.  Only the register epilogue differs.  They are
+// instantiated for fp32 weight scales only - what quantize_mx and FP4Linear hold, and what the km kernels take anyway; the entry
+// points refuse fp16 ones (FPQ_ERR_DTYPE): 16 kernels instead of 24 in a unit whose compile time is the build's longest but one.
+#define FPQ_A6W4_OUT 0
 #define FPQ_A6W4_KM 0
 #define FPQ_A6W4_KERNEL gemm_a6w4_kernel
 #define FPQ_A6W4_FC1 0
@@ -46,6 +52,31 @@
 #define FPQ_A6W4_FC1 1
 #include "fpq_gemm_a6w4_kernel.h"
 #undef FPQ_A6W4_KERNEL
+#undef FPQ_A6W4_FC1
+#define FPQ_A6W4_FC1 0
+#undef FPQ_A6W4_OUT
+#define FPQ_A6W4_KERNEL gemm_a6w4_split_km_kernel
+#define FPQ_A6W4_OUT 1
+#include "fpq_gemm_a6w4_kernel.h"
+#undef FPQ_A6W4_KERNEL
+#undef FPQ_A6W4_OUT
+#define FPQ_A6W4_KERNEL gemm_a6w4_qkn_km_kernel
+#define FPQ_A6W4_OUT 2
+#include "fpq_gemm_a6w4_kernel.h"
+#undef FPQ_A6W4_KERNEL
+#undef FPQ_A6W4_KM
+#define FPQ_A6W4_KM 0
+#undef FPQ_A6W4_OUT
+#define FPQ_A6W4_KERNEL gemm_a6w4_split_kernel
+#define FPQ_A6W4_OUT 1
+#include "fpq_gemm_a6w4_kernel.h"
+#undef FPQ_A6W4_KERNEL
+#undef FPQ_A6W4_OUT
+#define FPQ_A6W4_KERNEL gemm_a6w4_qkn_kernel
+#define FPQ_A6W4_OUT 2
+#include "fpq_gemm_a6w4_kernel.h"
+#undef FPQ_A6W4_KERNEL
+#undef FPQ_A6W4_OUT
 #undef FPQ_A6W4_FC1
 #undef FPQ_A6W4_KM
 

@@ -3,6 +3,10 @@
 //   FPQ_A6W4_KERNEL   the kernel's name
 //   FPQ_A6W4_FC1      0: the plain epilogue (+ gate / residual tail); 1: the fc1 tail (FPQ_GEMM_FC1_TAIL, fpq_gemm_fp4.h) - the kernel
 //                     takes a GemmFc1 behind the GemmEpi and stages the dual quantizer's bucket table behind the scale tiles
+//   FPQ_A6W4_OUT      (FPQ_A6W4_FC1 == 0 only) 0: one [T, O] tensor; 1: the SPLIT OUTPUT of GemmEpi's sp_* fields (mat_qkv: q to its own
+//                     tensor, k and v into the KV cache's slots), the plain epilogue's values bit for bit, no gate / residual tail;
+//                     2: the split output with the Q / K L2 NORM in front of it (FPQ_QK_NORM_ROW, fpq_gemm_fp4.h) - the kernel takes
+//                     a GemmQkNorm behind the GemmEpi, its fp32 bias replaces the fp16 one
 //   FPQ_A6W4_KM       0: row-major codes and scales; 1: K-MAJOR IMAGES (include/fpq.h) - A is the activation side's 6-bit image
 //                     [G][T][96] (the FP6 kernel's km addressing), W the dealt 4-bit image [G][km_w_rows][64] and sa / sw the fp32
 //                     scale images [G][T rounded up to 4] / [G][km_w_rows] (the FP4 kernel's): every piece of a stage is 1 KiB
@@ -21,6 +25,8 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_A6W4_KERNEL(const uint8_t
                                                                    GemmEpi epi
 #if FPQ_A6W4_FC1
                                                                    , GemmFc1 xe
+#elif FPQ_A6W4_OUT == 2
+                                                                   , GemmQkNorm xe
 #endif
                                                                    ) {
   static_assert(FA == 2 || FA == 3, "activation format: 2 = FP6 E2M3 (E1M2 levels), 3 = BF6 E3M2 (E3M0 levels)");
@@ -146,8 +152,16 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_A6W4_KERNEL(const uint8_t
   constexpr int WROWS = 16 * MT, WCOLS = 16 * NT;
   const int o = o0 + wn * WCOLS + NT * (lane & 15);
   const int oc = o < O ? o : O - 4;
+#if !FPQ_A6W4_FC1 && FPQ_A6W4_OUT == 2
+  // the fp32 bias of the lane's outputs and s_h of its head in part 0, as gemm_fp4_glds_kernel reads them (the fp16 bias is NULL here)
+  v4f_t qkn_b = v4f_t{0, 0, 0, 0};
+  float qkn_s = 1.0f;
+  if (xe.bias) qkn_b = *(const v4f_t*)(xe.bias + oc);
+  if (o0 < epi.sp_cols) qkn_s = xe.q_scale[oc >> 6];
+#else
   fpq_h4_t bias_h = fpq_h4_t{0, 0, 0, 0};
   if (bias) bias_h = *(const fpq_h4_t*)(bias + oc);
+#endif
 
   v4f_t acc[MT][NT];
 #pragma unroll
@@ -238,11 +252,44 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_A6W4_KERNEL(const uint8_t
 #undef FPQ_A6W4_TSA
 
   // epilogue from the registers, as gemm_fp4_glds_kernel's plain one: + bias, one rounding to fp16, gate / residual, 8-byte stores
+#if FPQ_A6W4_FC1 || FPQ_A6W4_OUT != 2
   v4f_t b4 = v4f_t{0, 0, 0, 0};
 #pragma unroll
   for (int n = 0; n < NT; ++n) b4[n] = (float)bias_h[n];
+#endif
 #if FPQ_A6W4_FC1
   FPQ_GEMM_FC1_TAIL(STAGE);   // (this form has no gate / residual tail: epi is not read)
+#elif FPQ_A6W4_OUT
+  // the split output, as gemm_fp4_glds_kernel stores it (same tile, same lane-to-output mapping: a lane's four values of row i are four
+  // consecutive columns of one part, a token row's head of 64 columns is the 16 lanes of a DPP row); no gate / residual tail
+  FPQ_GEMM_SPLIT_SETUP(WROWS, true);
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);
+    fpq_h4_t y[4];
+#if FPQ_A6W4_OUT == 2
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float yf[NT];
+#pragma unroll
+      for (int n = 0; n < NT; ++n) yf[n] = (float)(_Float16)acc[m][n][i] + qkn_b[n];
+      if (sp_part_ < 2) FPQ_QK_NORM_ROW(yf, sp_part_, qkn_s);   // uniform over the tile
+#pragma unroll
+      for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)yf[n];
+    }
+#else
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)(acc[m][n][i] + b4[n]);
+#endif
+    int tc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;
+    const int oc_l = oc - sp_part_ * epi.sp_cols;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) FPQ_GEMM_SPLIT_STORE(y[i], m, i, tc[i], t_first, o, oc_l);
+  }
 #else
   FPQ_GEMM_GATE_SETUP(WROWS);
 #pragma unroll

@@ -496,6 +496,48 @@ def linear_a6w4_gelu_dual_km(a_image: torch.Tensor, a_scales: torch.Tensor, a_ta
     return (out, h) if return_gelu else out
 
 
+def linear_a6w4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor,
+                             bias: Optional[torch.Tensor], cache_kv: torch.Tensor, pos: int, seq: int,
+                             qk_norm_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """linear_fp4_qkv_to_cache for a 6-bit activation (fpq_gemm_a6w4_mx_split / fpq_gemm_a6w4_mx_split_qknorm): mat_qkv of an attention
+    block whose activation format is E1M2 / E3M0 - `qkv = linear_a6w4(a, a_table, w, bias)` for tokens [B * seq] and outs = 3 * C, but
+    only q comes back, fp16 [B, seq, C], while k and v are written straight into `cache_kv` [2, B, max_len, H, c] at token positions
+    pos .. pos + seq, bit for bit what the plain GEMM and the cache's copy-in leave there.  Operands row-major (2-D, as linear_a6w4
+    takes them) or k-major images (3-D, as linear_a6w4_km takes them), both of the same kind; fp32 weight scales (what quantize_mx
+    gives an fp32 weight and FP4Linear holds) - these forms are not compiled for fp16 ones.
+    qk_norm_scale, and the fp32 bias that goes with it: as in linear_fp4_qkv_to_cache."""
+    require_gpu(a_codes, "linear_a6w4_qkv_to_cache")
+    from ._lib import TABLE_IDS
+    name = "linear_a6w4_qkv_to_cache"
+    a_table = _g6_table(name, a_table)
+    dev = a_codes.device
+    if cache_kv.dim() != 5 or cache_kv.shape[0] != 2 or cache_kv.dtype != torch.float16 or not cache_kv.is_contiguous() or cache_kv.device != dev:
+        raise RuntimeError(f"{name}: cache_kv must be a contiguous float16 [2, B, max_len, H, c] tensor on the operands' device")
+    if a_codes.dim() == 3 and w_codes.dim() == 3:
+        km = True
+        tokens, outs, k = _a6w4_km_operands(name, a_codes, a_scales, w_codes, w_scales, None, 3 * cache_kv.shape[3] * cache_kv.shape[4])
+    elif a_codes.dim() == 2 and w_codes.dim() == 2:
+        km = False
+        tokens, outs, k = _a6w4_operands(name, a_codes, a_scales, w_codes, w_scales)
+    else:
+        raise RuntimeError(f"{name}: both operands must be row-major codes (2-D) or both k-major images (3-D)")
+    if w_scales.dtype != torch.float32:
+        raise RuntimeError(f"{name}: the weight scales must be float32, got {w_scales.dtype}")
+    q, sp, b, hs = _qkv_split_args(name, cache_kv, tokens, outs, bias, pos, seq, qk_norm_scale)
+    if tokens and qk_norm_scale is not None:
+        with device_guard(dev):
+            check(lib().fpq_gemm_a6w4_mx_split_qknorm(a_codes.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_codes.data_ptr(),
+                                                      w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(),
+                                                      tokens, outs, k, ctypes.byref(sp), hs.data_ptr(), 1 if km else 0, stream_ptr(dev)),
+                  "fpq_gemm_a6w4_mx_split_qknorm")
+    elif tokens:
+        with device_guard(dev):
+            check(lib().fpq_gemm_a6w4_mx_split(a_codes.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_codes.data_ptr(),
+                                               w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), tokens, outs,
+                                               k, ctypes.byref(sp), 1 if km else 0, stream_ptr(dev)), "fpq_gemm_a6w4_mx_split")
+    return q
+
+
 class FP4Linear(_ScaledOperandModule):
     """Drop-in for QuantizedLinear in the W4A4 per-group `fp_e2` configuration that runs on the FP4
     matrix cores instead of simulating FP4 in fp16: weights are stored as hardware E2M1 codes + one
@@ -554,6 +596,32 @@ class FP4Linear(_ScaledOperandModule):
         a_codes, a_scales = quantize_mx(x2, kmajor=self.kmajor)
         y = linear_fp4(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, gate, residual, outs=self.out_features)
         return y.view(*lead, self.out_features)
+
+    @torch.no_grad()
+    def qkv_to_cache(self, x, cache_kv: torch.Tensor, pos: int, seq: int, qk_norm_scale: Optional[torch.Tensor] = None,
+                     bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mat_qkv with a split output: `forward(x)` for x [B, seq, in_features] and out_features = 3 * C, but only q comes back
+        ([B, seq, C]) while k and v go straight into `cache_kv` [2, B, max_len, H, c] at pos .. pos + seq.  x is quantized in the
+        module's own activation format and layout, and the product runs on the GEMM that format has (linear_fp4_qkv_to_cache for
+        E2M1, linear_a6w4_qkv_to_cache for E1M2 / E3M0): one call drives every mat_qkv of a mixed-format model.
+        Without qk_norm_scale the module's fp16 bias is added and `bias` must be None.  With qk_norm_scale (fp32 [H]: the block has
+        attn_l2_norm) `bias` is the fp32 cat(q_bias, 0, v_bias) [3 * C] or None, added after the fp16 rounding, and the module itself
+        must have no bias (mat_qkv has none in the reference)."""
+        if qk_norm_scale is None:
+            if bias is not None:
+                raise RuntimeError("FP4Linear.qkv_to_cache: `bias` is the fp32 bias of the q / k norm form - without qk_norm_scale the "
+                                   "module's own bias is used")
+            bias = self.bias
+        elif self.bias is not None:
+            raise RuntimeError("FP4Linear.qkv_to_cache: with qk_norm_scale the Linear itself must have no bias (pass cat(q_bias, 0, v_bias) "
+                               "as `bias`)")
+        x2 = x.to(torch.float16).reshape(-1, self.in_features)
+        if self.act_table != "e2m1":
+            a_codes, a_scales = quantize_g6(x2, self.act_table, kmajor=self.kmajor)
+            return linear_a6w4_qkv_to_cache(a_codes, a_scales, self.act_table, self.w_codes, self.w_scales, bias, cache_kv, pos, seq,
+                                            qk_norm_scale)
+        a_codes, a_scales = quantize_mx(x2, kmajor=self.kmajor)
+        return linear_fp4_qkv_to_cache(a_codes, a_scales, self.w_codes, self.w_scales, bias, cache_kv, pos, seq, qk_norm_scale)
 
     @torch.no_grad()
     def forward_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor, gate=None, residual=None, table: Optional[str] = None) -> torch.Tensor:

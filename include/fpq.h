@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FPQ_VERSION 133 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
+#define FPQ_VERSION 134 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
                            0.1.3: + fpq_quant_rows_codes_segments, fpq_dequant_rows_codes_segments (round 3);
                            123: + fpq_build_tag (round 4);
                            124: + fpq_set_option, fpq_get_option, fpq_option_name, fpq_gemm_fp4_gelu_dual, fpq_gelu_quant_rows_dual (round 5);
@@ -40,7 +40,8 @@ extern "C" {
                            131: + E1M2 / E3M0 activations on the matrix cores against FP4 weights ("A6W4"): fpq_quant_rows_codes_g6,
                                 fpq_gemm_a6w4_mx;
                            132: + the fc1 tail (GELU + fc2's dual-format input quantizer) in the A6W4 GEMM: fpq_gemm_a6w4_gelu_dual;
-                           133: + the A6W4 path on k-major images: fpq_a6w4_quant_rows_codes_km, fpq_gemm_a6w4_mx_km, fpq_gemm_a6w4_gelu_dual_km */
+                           133: + the A6W4 path on k-major images: fpq_a6w4_quant_rows_codes_km, fpq_gemm_a6w4_mx_km, fpq_gemm_a6w4_gelu_dual_km;
+                           134: + the split output and the q / k norm in the A6W4 GEMM: fpq_gemm_a6w4_mx_split, fpq_gemm_a6w4_mx_split_qknorm */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -683,8 +684,8 @@ int fpq_gemm_f6_rows_split_qknorm(const uint8_t* a_codes, const void* a_scales, 
  * w_codes / w_scales / w_scale_dtype exactly what fpq_gemm_fp4_mx takes (E2M1 nibbles [outs, k / 2], blgp = 4): one stored FP4
  * weight serves both GEMMs.  Shape and alignment rules of fpq_gemm_fp4_mx_ex (k % 128 == 0, k <= 8192, outs % 8 == 0, codes and
  * out 16-byte aligned), checked before any launch; the bias must be 8-byte aligned (there is no register-staged form to fall
- * back to).  Row-major operands; k-major images: fpq_gemm_a6w4_mx_km below.  No split output, no q / k norm; the fc1 tail:
- * fpq_gemm_a6w4_gelu_dual.
+ * back to).  Row-major operands; k-major images: fpq_gemm_a6w4_mx_km below.  The split output and the q / k norm:
+ * fpq_gemm_a6w4_mx_split / fpq_gemm_a6w4_mx_split_qknorm below; the fc1 tail: fpq_gemm_a6w4_gelu_dual.
  * Numerics: the per-group steps of fpq_gemm_fp4_mx's LDS-DMA tilings - t = fl(d_g sa), acc = fma(t, sw, acc), out = fp16(acc +
  * bias).  Products of an E3M0 or E1M2 level and an E2M1 level are multiples of 1/8 (|product| <= 96 resp. 10.5), so the exact
  * 128-term dot d_g has at most 17 significant bits (|d_g| <= 12288) and fits the fp32 accumulator.
@@ -743,6 +744,31 @@ int fpq_gemm_a6w4_mx_km(const uint8_t* a_image, const void* a_scales, int a_tabl
 int fpq_gemm_a6w4_gelu_dual_km(const uint8_t* a_image, const void* a_scales, int a_table, const uint8_t* w_image,
                                const void* w_scales, int w_scale_dtype, const void* bias, void* out, void* gelu_out,
                                int64_t tokens, int64_t outs, int64_t k, void* nan_flag, fpq_stream_t stream);
+
+/* MAT_QKV ON THE A6W4 GEMM: fpq_gemm_a6w4_mx (kmajor = 0) / fpq_gemm_a6w4_mx_km (kmajor = 1) - exactly that entry point's operands
+ * and every one of its operand and scale checks, no gate / residual tail - with the SPLIT OUTPUT of fpq_gemm_fp4_mx_split, and
+ * with the Q / K L2 NORM above in that epilogue (the mixed W4A4 model's mat_qkv has an E3M0 activation in almost every block).
+ * Without the norm every written value is bit for bit the one fpq_gemm_a6w4_mx / _km writes at that (token, column); with it, y16
+ * is what they write with bias == NULL and q, k, v follow "THE Q / K L2 NORM" (the arithmetic of fpq_gemm_fp4_mx_split_qknorm:
+ * q and k within one fp16 ulp of the fp32 lines, v bit for bit).  Row-major and k-major operands, and both tilings, give the same bits.
+ * w_scale_dtype: FPQ_F32 ONLY, row-major operands included - these forms are not compiled for fp16 weight scales (what
+ * fpq_quant_rows_codes_mx writes for an fp32 weight, and what the k-major scale images are, is fp32): FPQ_F16 is FPQ_ERR_DTYPE.
+ * split: the FP6 family's rules (fpq_gemm_fp6_rows_split) - n_parts 1..3 (exactly 3 with the norm), part_cols % 128 == 0,
+ * outs == n_parts * part_cols, rows_per_batch >= 1 and tokens % rows_per_batch == 0; EVERY destination out[p] non-NULL and 8-byte
+ * aligned, row_stride[p] >= part_cols and % 4 == 0, batch_stride[p], row0[p] >= 0.  bias: fp16 [outs], 8-byte aligned, or NULL
+ * (split); fp32 [3 * part_cols], 16-byte aligned, or NULL (norm); q_head_scale fp32 [part_cols / 64], never NULL.
+ * Checks, in this order, before any launch: a_table (FPQ_ERR_TABLE); split == NULL [_qknorm: or n_parts != 3, q_head_scale NULL or
+ * not 4-byte aligned, bias not 16-byte aligned] (FPQ_ERR_ARG); negative sizes (FPQ_ERR_ARG); the split descriptor (FPQ_ERR_ARG);
+ * w_scale_dtype other than FPQ_F32 (FPQ_ERR_DTYPE); shape (FPQ_ERR_SHAPE: k % 128, k > 8192, tokens or outs above 2^31 - 1, with
+ * kmajor tokens or outs at or above 2^28, an LDS image above 160 KiB); tokens == 0 (FPQ_OK, nothing launched); then NULL pointers /
+ * alignment (FPQ_ERR_ARG; codes or images 16 bytes, the fp16 bias 8, with kmajor both scale images 16).
+ * Tilings as fpq_gemm_a6w4_mx (FPQ_GEMM_CFG 20 / 30 forces one). */
+int fpq_gemm_a6w4_mx_split(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                           int w_scale_dtype, const void* bias, int64_t tokens, int64_t outs, int64_t k, const fpq_gemm_split_t* split,
+                           int kmajor, fpq_stream_t stream);
+int fpq_gemm_a6w4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                                  int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
+                                  const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream);
 
 /* fpq_kv_cache_step_qknorm: fpq_kv_cache_step (same arguments, same checks) for an fp16 qkv WITHOUT the norm (path F, or a
  * mat_qkv that is not split): the new k is normalized and the bias added on its way into the cache, and the same launch writes
