@@ -6,20 +6,20 @@ the product runs on MI355X's block-scaled FP4 matrix cores (`fpq_gemm_fp4_mx`).
 """
 from __future__ import annotations
 
-from functools import partial
-from typing import Optional, Tuple
+import ctypes
+import os
+from typing import NamedTuple, Optional, Tuple, Union
 
 import torch
 
-import ctypes
-
-from ._lib import GemmEpilogue, check, dtype_id, lib, require_gpu, stream_ptr, device_guard
+from . import ops
+from ._lib import TABLE_IDS, GemmEpilogue, GemmSplit, check, dtype_id, lib, require_gpu, stream_ptr, device_guard
 
 try:   # the compiled binding (csrc/quant_cuda_ext.cpp)
     from . import _native
 except ImportError:   # pragma: no cover - build() always produces it
     _native = None
-if __import__("os").environ.get("FPQ_NO_NATIVE") == "1":   # the A/B tools time variant builds of the library through ctypes (_lib.use_variant)
+if os.environ.get("FPQ_NO_NATIVE") == "1":   # the A/B tools time variant builds of the library through ctypes (_lib.use_variant)
     _native = None
 
 E2M1_LEVELS = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
@@ -109,27 +109,91 @@ def _kmajor_pair(name: str, a: torch.Tensor, w: torch.Tensor, seg: int) -> bool:
     raise RuntimeError(f"{name}: both operands must be row-major codes (2-D) or both k-major images (3-D)")
 
 
+# ---- the per-group family: E2M1 nibbles on the FP4 GEMM; E1M2 / E3M0 as dense 6-bit codes on the A6W4 GEMM (include/fpq.h) --------
+# Per-group scales (one per 128 elements) on both sides, the same E2M1 weight whatever the activation's format.  The reference's
+# mixed W4A4 model gives fc1 / mat_qkv an E3M0 or E1M2 activation format in most blocks; the matrix instruction decodes a 6-bit
+# activation fragment (E1M2 levels as FP6 E2M3 codes, E3M0 levels as BF6 E3M2 codes) against E2M1 nibbles.
+#
+# One row per activation format holds everything the Python side knows about it; `_per_group_operands` checks an operand pair,
+# `_per_group_gemm` is the one place that names a GEMM entry point of the family, and the public Linears below are the three
+# bodies (`_linear`, `_linear_gelu_dual`, `_linear_qkv_to_cache`) under their own names.  A new format is a row; a new form of
+# the GEMM is a form name in `_per_group_gemm` and a body.
+#
+# What differs between the public functions, and stays as it is (rows of the table or arguments of the bodies, not decisions
+# scattered in them):
+#  - linear_fp4 and linear_fp4_gelu_dual hand the whole call to the compiled binding when it is loaded, before any check here;
+#  - the bias: linear_fp4 checks no size and copies for alignment (16 bytes) only beside images (`loose_bias`); every other plain /
+#    fc1 form checks that it holds `outs` values and copies to `bias_align` (16 FP4, 8 A6W4); the split forms check it and align
+#    to 16, and their q / k norm form takes an fp32 bias of 3C instead (_qkv_split_args);
+#  - row-major activation scales are fp16, scale images are fp32 of the padded shapes; weight scales fp16 or fp32, except that the
+#    A6W4 split forms are compiled for fp32 ones only (`split_w_f32`);
+#  - linear_a6w4 / _gelu_dual take row-major codes only and their _km twins images only (`layouts`); the others go by rank;
+#  - the split forms take `outs` from the cache, not from the bias;
+#  - the fc1 forms skip the launch when tokens == 0 or outs == 0, the split forms when tokens == 0, the plain forms never;
+#  - the order of refusals: GPU, table, (cache), operands, (weight scale dtype), then the form's own arguments.
+class _Format(NamedTuple):
+    seg: int                   # bytes of activation codes per 128 elements
+    gemm: str                  # the GEMM's C entry point family
+    plain: str                 # what the plain row-major entry point adds to "<family>_mx" (the FP4 one with an epilogue is _ex)
+    table: Tuple[int, ...]     # the table id that follows a_scales in every call of the family, or nothing
+    quant: str                 # the quantizer's C entry points: row-major codes,
+    quant_km: str              # k-major images
+    quantizer: str             # the public quantizer, for its messages
+    bias_align: int
+    split_w_f32: bool
+
+
+_FORMATS = {
+    "e2m1": _Format(64, "fpq_gemm_fp4", "_ex", (), "fpq_quant_rows_codes_mx", "fpq_quant_rows_codes_mx_km", "quantize_mx", 16, False),
+    "e1m2": _Format(96, "fpq_gemm_a6w4", "", (TABLE_IDS["e1m2"],), "fpq_quant_rows_codes_g6", "fpq_a6w4_quant_rows_codes_km", "quantize_g6", 8, True),
+    "e3m0": _Format(96, "fpq_gemm_a6w4", "", (TABLE_IDS["e3m0"],), "fpq_quant_rows_codes_g6", "fpq_a6w4_quant_rows_codes_km", "quantize_g6", 8, True),
+}
+_G6_TABLES = {"e1m2": "e1m2", "fp_e1": "e1m2", "e3m0": "e3m0", "fp_e3": "e3m0"}
+_G6_CODE_FORMAT = {"e1m2": "e2m3", "e3m0": "e3m2"}   # the 6-bit hardware format that holds the table's levels
+
+
+def _g6_table(name: str, table: str) -> str:
+    try:
+        return _G6_TABLES[table]
+    except (KeyError, TypeError):
+        raise RuntimeError(f"{name}: the per-group 6-bit activation tables are 'e1m2' and 'e3m0', got {table!r}") from None
+
+
+def _g6_format(name: str, table: str) -> _Format:
+    """The row of the 6-bit table a caller of the A6W4 functions named.  The shared bodies below take `fmt` as a row (the FP4
+    functions and the modules pass one) or as such a name, which they resolve where the A6W4 functions have always refused a
+    wrong one: after the GPU check, before the operands."""
+    return _FORMATS[_g6_table(name, table)]
+
+
+def _quantize_per_group(name: str, fmt: Union[_Format, str], x: torch.Tensor, kmajor: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """quantize_mx / quantize_g6: x [..., K] -> (codes, scales) of `fmt`, row-major or as the activation side's k-major images"""
+    require_gpu(x, name)
+    if x.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError(f"{name}: x must be float16 or float32, got {x.dtype}")
+    if not isinstance(fmt, _Format):
+        fmt = _g6_format(name, fmt)
+    k = x.shape[-1]
+    if k % 128 != 0:
+        raise RuntimeError(f"{name}: the last dimension must be a multiple of 128")
+    if kmajor and x.dtype == torch.float32:   # the image-writing quantizers take fp16 rows (activations); fp32 rows: two steps
+        codes, scales = _quantize_per_group(name, fmt, x, False)
+        return to_kmajor(codes, 4 if fmt.seg == 64 else 6), to_kmajor_scales(scales)
+    xc, dev = x.contiguous(), x.device
+    rows = xc.numel() // k
+    codes = torch.empty((k // 128, rows, fmt.seg) if kmajor else (rows, k // 128 * fmt.seg), dtype=torch.uint8, device=dev)
+    scales = kmajor_mx_scales(rows, k, dev) if kmajor else torch.empty((rows, k // 128), dtype=x.dtype, device=dev)
+    what = fmt.quant_km if kmajor else fmt.quant
+    with device_guard(dev):
+        check(getattr(lib(), what)(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, k, *fmt.table, dtype_id(x.dtype),
+                                   stream_ptr(dev)), what)
+    return codes, scales
+
+
 def quantize_mx(x: torch.Tensor, kmajor: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """x [..., K] fp16/fp32 (K % 128 == 0) -> (codes uint8 [rows, K/2], scales [rows, K/128] in x.dtype).
     kmajor: the activation side's k-major images - codes [K/128, rows, 64] and scales fp32 [K/128, rows rounded up to 4]."""
-    require_gpu(x, "quantize_mx")
-    if x.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError(f"quantize_mx: x must be float16 or float32, got {x.dtype}")
-    k = x.shape[-1]
-    if k % 128 != 0:
-        raise RuntimeError("quantize_mx: the last dimension must be a multiple of 128")
-    if kmajor and x.dtype == torch.float32:   # the image-writing quantizer takes fp16 rows (activations); fp32 rows: two steps
-        codes, scales = quantize_mx(x)
-        return to_kmajor(codes, 4), to_kmajor_scales(scales)
-    xc = x.contiguous()
-    rows = xc.numel() // k
-    codes = torch.empty((k // 128, rows, 64) if kmajor else (rows, k // 2), dtype=torch.uint8, device=x.device)
-    scales = kmajor_mx_scales(rows, k, x.device) if kmajor else torch.empty((rows, k // 128), dtype=x.dtype, device=x.device)
-    fn = lib().fpq_quant_rows_codes_mx_km if kmajor else lib().fpq_quant_rows_codes_mx
-    with device_guard(x.device):
-        check(fn(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, k, dtype_id(x.dtype), stream_ptr(x.device)),
-              "fpq_quant_rows_codes_mx_km" if kmajor else "fpq_quant_rows_codes_mx")
-    return codes, scales
+    return _quantize_per_group("quantize_mx", _FORMATS["e2m1"], x, kmajor)
 
 
 def dequantize_mx(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
@@ -138,6 +202,23 @@ def dequantize_mx(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
     lo, hi = (codes & 0xF).long(), (codes >> 4).long()
     q = torch.stack((lv[lo], lv[hi]), dim=-1).reshape(codes.shape[0], -1)
     return (q.view(codes.shape[0], -1, 128) * scales.float().unsqueeze(-1)).reshape(codes.shape[0], -1)
+
+
+def quantize_g6(x: torch.Tensor, table: str = "e3m0", kmajor: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [..., K] fp16/fp32 (K % 128 == 0) -> (codes uint8 [rows, K * 3 / 4]: dense 6-bit codes of the E1M2 / E3M0 levels,
+    scales [rows, K/128] in x.dtype); level(code) * scale == fp_quant_e1_per_group_cuda / fp_quant_e3_per_group_cuda (x, 4, 128)
+    bit for bit (fpq_quant_rows_codes_g6).
+    kmajor: the activation side's k-major images instead (fpq_a6w4_quant_rows_codes_km) - codes [K/128, rows, 96] and scales fp32
+    [K/128, rows rounded up to 4], what linear_a6w4_km takes."""
+    return _quantize_per_group("quantize_g6", table, x, kmajor)
+
+
+def dequantize_g6(codes: torch.Tensor, scales: torch.Tensor, table: str = "e3m0") -> torch.Tensor:
+    """Reference decoder in torch ops (tests / debugging): fp32 [rows, K] = level(code) * scale of the code's group."""
+    table = _g6_table("dequantize_g6", table)
+    rows = codes.shape[0]
+    lv = dequantize_fp6(codes, torch.ones(rows, dtype=torch.float32, device=codes.device), _G6_CODE_FORMAT[table])
+    return (lv.view(rows, -1, 128) * scales.float().unsqueeze(-1)).reshape(rows, -1)
 
 
 class _ScaledOperandModule(torch.nn.Module):
@@ -169,7 +250,6 @@ def _check_operand(what: str, codes: torch.Tensor, scales: torch.Tensor, rows: i
         raise RuntimeError(f"{what}: {scales.numel()} scales, expected {n_scales}")
 
 
-
 def _check_kmajor_fp4(name: str, a_codes, a_scales, w_codes, w_scales, bias, outs):
     """shapes of a k-major FP4 operand pair -> (tokens, outs, k); `outs` (or the bias) names the Linear's width when it is not
     the weight image's row count (a multiple of 64)"""
@@ -188,18 +268,47 @@ def _check_kmajor_fp4(name: str, a_codes, a_scales, w_codes, w_scales, bias, out
     return tokens, outs, groups * 128
 
 
-def _fp4_operands(name: str, a_codes, a_scales, w_codes, w_scales, bias, outs):
-    """An FP4 operand pair, row-major codes (2-D) or k-major images (3-D), checked -> (km, tokens, outs, k); what the compiled
-    binding's fp4_shapes does.  `outs` (or the bias) only matters for images, see _check_kmajor_fp4."""
-    km = _kmajor_pair(name, a_codes, w_codes, 64)
+def _per_group_operands(name: str, fmt: _Format, a, a_scales, w, w_scales, bias, outs, layouts: str = "rank"):
+    """An operand pair of the per-group family - activation codes of `fmt`, E2M1 weight nibbles - checked -> (km, tokens, outs, k);
+    what the compiled binding's fp4_shapes does for E2M1.  layouts: "rank" - row-major codes (2-D) or k-major images (3-D, with
+    their fp32 scale images), told by the operands' rank; "rows" / "images" - the public function takes that layout only.
+    `outs` (or the bias) only matters for images, see _check_kmajor_fp4."""
+    a_rank, w_rank = a.dim(), w.dim()
+    km = a_rank == 3 and w_rank == 3
+    if layouts == "rows" and (a_rank != 2 or w_rank != 2):
+        raise RuntimeError(f"{name}: row-major operands only (k-major images: {name}_km)")
+    if layouts == "images" and not km:
+        raise RuntimeError(f"{name}: both operands must be k-major images (3-D); row-major codes go to {name[:-3]}")
     if km:
-        return (km, *_check_kmajor_fp4(name, a_codes, a_scales, w_codes, w_scales, bias, outs))
-    tokens, outs, k = a_codes.shape[0], w_codes.shape[0], a_codes.shape[1] * 2
-    if w_codes.shape[1] * 2 != k or a_scales.dtype != torch.float16 or k % 128 != 0:
+        if a.shape[2] != fmt.seg or w.shape[2] != 64 or a.shape[0] != w.shape[0] or w.shape[1] % 64 != 0:
+            shapes = "[K/128, rows, 64]" if fmt.seg == 64 else "[K/128, tokens, 96] (activation) and [K/128, rows, 64] (weight)"
+            raise RuntimeError(f"{name}: k-major images must be {shapes} with the same K and a weight image of a multiple of 64 rows")
+        return (True, *_check_kmajor_fp4(name, a, a_scales, w, w_scales, bias, outs))
+    if a_rank != 2 or w_rank != 2:
+        raise RuntimeError(f"{name}: both operands must be row-major codes (2-D) or both k-major images (3-D)")
+    tokens, outs, k = a.shape[0], w.shape[0], w.shape[1] * 2
+    if k % 128 != 0 or a.shape[1] != k // 128 * fmt.seg or a_scales.dtype != torch.float16:
         raise RuntimeError(f"{name}: operand shapes / activation scale dtype mismatch")
-    _check_operand(f"{name}(activation)", a_codes, a_scales, tokens, k // 2, tokens * (k // 128), a_codes.device)
-    _check_operand(f"{name}(weight)", w_codes, w_scales, outs, k // 2, outs * (k // 128), a_codes.device)
-    return km, tokens, outs, k
+    dev = a.device
+    _check_operand(f"{name}(activation)", a, a_scales, tokens, a.shape[1], tokens * (k // 128), dev)
+    _check_operand(f"{name}(weight)", w, w_scales, outs, k // 2, outs * (k // 128), dev)
+    return False, tokens, outs, k
+
+
+def _per_group_gemm(form: str, fmt: _Format, km: bool, a, a_scales, w, w_scales, *rest) -> None:
+    """One call of the family's C entry point of `form`: "" (plain, with the optional gate / residual tail), "gelu_dual" (fc1),
+    "split" or "split_qknorm" (mat_qkv into the cache); rest: its arguments between the weight scales' dtype and the stream - or,
+    for the split forms, which take the layout as a flag, the k-major flag before it."""
+    if form in ("split", "split_qknorm"):
+        what, rest = f"{fmt.gemm}_mx_{form}", (*rest, 1 if km else 0)
+    elif form:   # an entry point per layout
+        what = f"{fmt.gemm}_{form}_km" if km else f"{fmt.gemm}_{form}"
+    else:
+        what = fmt.gemm + "_mx_km" if km else fmt.gemm + "_mx" + fmt.plain
+    dev = a.device
+    with device_guard(dev):
+        check(getattr(lib(), what)(a.data_ptr(), a_scales.data_ptr(), *fmt.table, w.data_ptr(), w_scales.data_ptr(), dtype_id(w_scales.dtype),
+                                   *rest, stream_ptr(dev)), what)
 
 
 def _bias_f16(name: str, bias: Optional[torch.Tensor], outs: Optional[int], device, align: int = 0) -> Optional[torch.Tensor]:
@@ -215,31 +324,52 @@ def _bias_f16(name: str, bias: Optional[torch.Tensor], outs: Optional[int], devi
     return b
 
 
-def linear_fp4(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
-               bias: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
-               residual: Optional[torch.Tensor] = None, outs: Optional[int] = None) -> torch.Tensor:
-    """fp16 [tokens, outs] = dequant(a) @ dequant(w).T + bias on the FP4 matrix cores; with gate / residual the
-    AdaLN block's `residual + y.mul(gate)` (tr/basic_var.py:264) is applied in the epilogue, bit-identical to the two
-    torch ops on the plain result."""
-    if _native is not None:   # same checks, same C calls (fpq_gemm_fp4_mx_ex / fpq_gemm_fp4_mx_km)
-        return _native.linear_fp4(a_codes, a_scales, w_codes, w_scales, bias, gate, residual, outs)
-    require_gpu(a_codes, "linear_fp4")
-    km, tokens, outs, k = _fp4_operands("linear_fp4", a_codes, a_scales, w_codes, w_scales, bias, outs)
-    ep, keep, out = _epilogue("linear_fp4", tokens, outs, gate, residual, None, a_codes.device)
-    b = _bias_f16("linear_fp4", bias, None, a_codes.device, 16 if km else 0)
-    fn, what = (lib().fpq_gemm_fp4_mx_km, "fpq_gemm_fp4_mx_km") if km else (lib().fpq_gemm_fp4_mx_ex, "fpq_gemm_fp4_mx_ex")
-    with device_guard(a_codes.device):
-        check(fn(a_codes.data_ptr(), a_scales.data_ptr(), w_codes.data_ptr(), w_scales.data_ptr(), dtype_id(w_scales.dtype),
-                 None if b is None else b.data_ptr(), out.data_ptr(), tokens, outs, k, ep, stream_ptr(a_codes.device)), what)
+def _linear(name: str, fmt, layouts: str, a, a_scales, w, w_scales, bias, gate, residual, outs, loose_bias: bool = False) -> torch.Tensor:
+    """The plain Linear with its optional gate / residual tail: linear_fp4, linear_a6w4, linear_a6w4_km"""
+    require_gpu(a, name)
+    if not isinstance(fmt, _Format):
+        fmt = _g6_format(name, fmt)
+    dev = a.device
+    km, tokens, outs, k = _per_group_operands(name, fmt, a, a_scales, w, w_scales, bias, outs, layouts)
+    ep, keep, out = _epilogue(name, tokens, outs, gate, residual, None, dev)
+    if loose_bias:
+        b = _bias_f16(name, bias, None, dev, fmt.bias_align if km else 0)
+    else:
+        b = _bias_f16(name, bias, outs, dev, fmt.bias_align)
+    _per_group_gemm("", fmt, km, a, a_scales, w, w_scales, None if b is None else b.data_ptr(), out.data_ptr(), tokens, outs, k, ep)
     del keep
     return out
+
+
+def _linear_gelu_dual(name: str, fmt, layouts: str, a, a_scales, w, w_scales, bias, return_gelu: bool, outs):
+    """fc1 with the GELU and the dual quantizer in the epilogue: linear_fp4_gelu_dual, linear_a6w4_gelu_dual, linear_a6w4_gelu_dual_km"""
+    require_gpu(a, name)
+    if not isinstance(fmt, _Format):
+        fmt = _g6_format(name, fmt)
+    dev = a.device
+    km, tokens, outs, k = _per_group_operands(name, fmt, a, a_scales, w, w_scales, bias, outs, layouts)
+    if outs % 128 != 0:
+        raise RuntimeError(f"{name}: outs must be a multiple of 128")
+    out = torch.empty((tokens, outs), dtype=torch.float16, device=dev)
+    h = torch.empty((tokens, outs), dtype=torch.float16, device=dev) if return_gelu else None
+    b = _bias_f16(name, bias, outs, dev, fmt.bias_align)
+    if tokens and outs:
+        with device_guard(dev):
+            flag = ops._nan_scratch(dev)
+        _per_group_gemm("gelu_dual", fmt, km, a, a_scales, w, w_scales, None if b is None else b.data_ptr(), out.data_ptr(),
+                        None if h is None else h.data_ptr(), tokens, outs, k, flag.data_ptr())
+    return (out, h) if return_gelu else out
+
+
+def _check_cache_kv(name: str, cache_kv: torch.Tensor, device) -> None:
+    if cache_kv.dim() != 5 or cache_kv.shape[0] != 2 or cache_kv.dtype != torch.float16 or not cache_kv.is_contiguous() or cache_kv.device != device:
+        raise RuntimeError(f"{name}: cache_kv must be a contiguous float16 [2, B, max_len, H, c] tensor on the operands' device")
 
 
 def _qkv_split_args(name: str, cache_kv: torch.Tensor, tokens: int, outs: int, bias: Optional[torch.Tensor], pos: int, seq: int,
                     qk_norm_scale: Optional[torch.Tensor]):
     """The destination side of a mat_qkv with a split output, shared by the FP4 and FP6 forms: checks that the problem fits the cache
     and the bias / head scale rules, allocates q -> (q, fpq_gemm_split_t, bias or None, head scale or None)."""
-    from ._lib import GemmSplit
     dev = cache_kv.device
     _, bsz, max_len, heads, hd = cache_kv.shape
     c = heads * hd
@@ -268,6 +398,34 @@ def _qkv_split_args(name: str, cache_kv: torch.Tensor, tokens: int, outs: int, b
     return q, sp, b, hs
 
 
+def _linear_qkv_to_cache(name: str, fmt, a, a_scales, w, w_scales, bias, cache_kv, pos: int, seq: int, qk_norm_scale) -> torch.Tensor:
+    """mat_qkv with q returned and k, v written into the cache: linear_fp4_qkv_to_cache, linear_a6w4_qkv_to_cache"""
+    require_gpu(a, name)
+    if not isinstance(fmt, _Format):
+        fmt = _g6_format(name, fmt)
+    _check_cache_kv(name, cache_kv, a.device)
+    km, tokens, outs, k = _per_group_operands(name, fmt, a, a_scales, w, w_scales, None, 3 * cache_kv.shape[3] * cache_kv.shape[4])
+    if fmt.split_w_f32 and w_scales.dtype != torch.float32:
+        raise RuntimeError(f"{name}: the weight scales must be float32, got {w_scales.dtype}")
+    q, sp, b, hs = _qkv_split_args(name, cache_kv, tokens, outs, bias, pos, seq, qk_norm_scale)
+    if tokens:
+        norm = () if hs is None else (hs.data_ptr(),)
+        _per_group_gemm("split" if hs is None else "split_qknorm", fmt, km, a, a_scales, w, w_scales, None if b is None else b.data_ptr(),
+                        tokens, outs, k, ctypes.byref(sp), *norm)
+    return q
+
+
+def linear_fp4(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
+               bias: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
+               residual: Optional[torch.Tensor] = None, outs: Optional[int] = None) -> torch.Tensor:
+    """fp16 [tokens, outs] = dequant(a) @ dequant(w).T + bias on the FP4 matrix cores; with gate / residual the
+    AdaLN block's `residual + y.mul(gate)` (tr/basic_var.py:264) is applied in the epilogue, bit-identical to the two
+    torch ops on the plain result."""
+    if _native is not None:   # same checks, same C calls (fpq_gemm_fp4_mx_ex / fpq_gemm_fp4_mx_km)
+        return _native.linear_fp4(a_codes, a_scales, w_codes, w_scales, bias, gate, residual, outs)
+    return _linear("linear_fp4", _FORMATS["e2m1"], "rank", a_codes, a_scales, w_codes, w_scales, bias, gate, residual, outs, True)
+
+
 def linear_fp4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
                             bias: Optional[torch.Tensor], cache_kv: torch.Tensor, pos: int, seq: int,
                             qk_norm_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -280,25 +438,8 @@ def linear_fp4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_cod
     qk_norm_scale: fp32 [H] (kv_cache.qk_norm_head_scale) - the attention block has attn_l2_norm (fpq_gemm_fp4_mx_split_qknorm):
     y = float(fp16 Linear output) + bias (fp32 [3C] or None: q_bias, 0, v_bias, added after the fp16 rounding), q =
     F.normalize(y_q) * qk_norm_scale per head, k = F.normalize(y_k) into the cache, v = y_v (tr/basic_var.py:173-183), head_dim 64."""
-    require_gpu(a_codes, "linear_fp4_qkv_to_cache")
-    dev = a_codes.device
-    if cache_kv.dim() != 5 or cache_kv.shape[0] != 2 or cache_kv.dtype != torch.float16 or not cache_kv.is_contiguous() or cache_kv.device != dev:
-        raise RuntimeError("linear_fp4_qkv_to_cache: cache_kv must be a contiguous float16 [2, B, max_len, H, c] tensor on the operands' device")
-    km, tokens, outs, k = _fp4_operands("linear_fp4_qkv_to_cache", a_codes, a_scales, w_codes, w_scales, bias,
-                                        3 * cache_kv.shape[3] * cache_kv.shape[4])
-    q, sp, b, hs = _qkv_split_args("linear_fp4_qkv_to_cache", cache_kv, tokens, outs, bias, pos, seq, qk_norm_scale)
-    if tokens and qk_norm_scale is not None:
-        with device_guard(dev):
-            check(lib().fpq_gemm_fp4_mx_split_qknorm(a_codes.data_ptr(), a_scales.data_ptr(), w_codes.data_ptr(), w_scales.data_ptr(),
-                                                     dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), tokens, outs, k,
-                                                     ctypes.byref(sp), hs.data_ptr(), 1 if km else 0, stream_ptr(dev)),
-                  "fpq_gemm_fp4_mx_split_qknorm")
-    elif tokens:
-        with device_guard(dev):
-            check(lib().fpq_gemm_fp4_mx_split(a_codes.data_ptr(), a_scales.data_ptr(), w_codes.data_ptr(), w_scales.data_ptr(),
-                                              dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), tokens, outs, k,
-                                              ctypes.byref(sp), 1 if km else 0, stream_ptr(dev)), "fpq_gemm_fp4_mx_split")
-    return q
+    return _linear_qkv_to_cache("linear_fp4_qkv_to_cache", _FORMATS["e2m1"], a_codes, a_scales, w_codes, w_scales, bias, cache_kv, pos, seq,
+                                qk_norm_scale)
 
 
 def linear_fp4_gelu_dual(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
@@ -311,85 +452,7 @@ def linear_fp4_gelu_dual(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes:
     if _native is not None:   # same checks, same C calls, the binding's own NaN scratch
         out, h = _native.linear_fp4_gelu_dual(a_codes, a_scales, w_codes, w_scales, bias, return_gelu, outs)
         return (out, h) if return_gelu else out
-    require_gpu(a_codes, "linear_fp4_gelu_dual")
-    dev = a_codes.device
-    km, tokens, outs, k = _fp4_operands("linear_fp4_gelu_dual", a_codes, a_scales, w_codes, w_scales, bias, outs)
-    if outs % 128 != 0:
-        raise RuntimeError("linear_fp4_gelu_dual: outs must be a multiple of 128")
-    out = torch.empty((tokens, outs), dtype=torch.float16, device=dev)
-    h = torch.empty((tokens, outs), dtype=torch.float16, device=dev) if return_gelu else None
-    b = _bias_f16("linear_fp4_gelu_dual", bias, outs, dev, 16)
-    if tokens and outs:
-        from .ops import _nan_scratch
-        with device_guard(dev):
-            flag = _nan_scratch(dev)
-            fn = lib().fpq_gemm_fp4_gelu_dual_km if km else lib().fpq_gemm_fp4_gelu_dual
-            check(fn(a_codes.data_ptr(), a_scales.data_ptr(), w_codes.data_ptr(), w_scales.data_ptr(),
-                     dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), out.data_ptr(),
-                     None if h is None else h.data_ptr(), tokens, outs, k, flag.data_ptr(),
-                     stream_ptr(dev)), "fpq_gemm_fp4_gelu_dual_km" if km else "fpq_gemm_fp4_gelu_dual")
-    return (out, h) if return_gelu else out
-
-
-# ---- A6W4: E1M2 / E3M0 activations as dense 6-bit codes against the FP4 weights (include/fpq.h) ----------------------------
-# The reference's mixed W4A4 model gives fc1 / mat_qkv an E3M0 or E1M2 activation format in most blocks; the matrix instruction
-# decodes a 6-bit activation fragment (E1M2 levels as FP6 E2M3 codes, E3M0 levels as BF6 E3M2 codes) against E2M1 nibbles.
-_G6_TABLES = {"e1m2": "e1m2", "fp_e1": "e1m2", "e3m0": "e3m0", "fp_e3": "e3m0"}
-_G6_CODE_FORMAT = {"e1m2": "e2m3", "e3m0": "e3m2"}   # the 6-bit hardware format that holds the table's levels
-
-
-def _g6_table(name: str, table: str) -> str:
-    try:
-        return _G6_TABLES[table]
-    except (KeyError, TypeError):
-        raise RuntimeError(f"{name}: the per-group 6-bit activation tables are 'e1m2' and 'e3m0', got {table!r}") from None
-
-
-def quantize_g6(x: torch.Tensor, table: str = "e3m0", kmajor: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
-    """x [..., K] fp16/fp32 (K % 128 == 0) -> (codes uint8 [rows, K * 3 / 4]: dense 6-bit codes of the E1M2 / E3M0 levels,
-    scales [rows, K/128] in x.dtype); level(code) * scale == fp_quant_e1_per_group_cuda / fp_quant_e3_per_group_cuda (x, 4, 128)
-    bit for bit (fpq_quant_rows_codes_g6).
-    kmajor: the activation side's k-major images instead (fpq_a6w4_quant_rows_codes_km) - codes [K/128, rows, 96] and scales fp32
-    [K/128, rows rounded up to 4], what linear_a6w4_km takes."""
-    require_gpu(x, "quantize_g6")
-    if x.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError(f"quantize_g6: x must be float16 or float32, got {x.dtype}")
-    from ._lib import TABLE_IDS
-    table = _g6_table("quantize_g6", table)
-    k = x.shape[-1]
-    if k % 128 != 0:
-        raise RuntimeError("quantize_g6: the last dimension must be a multiple of 128")
-    if kmajor and x.dtype == torch.float32:   # the image-writing emitter takes fp16 rows (activations); fp32 rows: two steps
-        codes, scales = quantize_g6(x, table)
-        return to_kmajor(codes, 6), to_kmajor_scales(scales)
-    xc = x.contiguous()
-    rows = xc.numel() // k
-    codes = torch.empty((k // 128, rows, 96) if kmajor else (rows, k * 3 // 4), dtype=torch.uint8, device=x.device)
-    scales = kmajor_mx_scales(rows, k, x.device) if kmajor else torch.empty((rows, k // 128), dtype=x.dtype, device=x.device)
-    fn, what = (lib().fpq_a6w4_quant_rows_codes_km, "fpq_a6w4_quant_rows_codes_km") if kmajor else (lib().fpq_quant_rows_codes_g6, "fpq_quant_rows_codes_g6")
-    with device_guard(x.device):
-        check(fn(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, k, TABLE_IDS[table], dtype_id(x.dtype), stream_ptr(x.device)), what)
-    return codes, scales
-
-
-def dequantize_g6(codes: torch.Tensor, scales: torch.Tensor, table: str = "e3m0") -> torch.Tensor:
-    """Reference decoder in torch ops (tests / debugging): fp32 [rows, K] = level(code) * scale of the code's group."""
-    table = _g6_table("dequantize_g6", table)
-    rows = codes.shape[0]
-    lv = dequantize_fp6(codes, torch.ones(rows, dtype=torch.float32, device=codes.device), _G6_CODE_FORMAT[table])
-    return (lv.view(rows, -1, 128) * scales.float().unsqueeze(-1)).reshape(rows, -1)
-
-
-def _a6w4_operands(name: str, a_codes, a_scales, w_codes, w_scales):
-    """An A6W4 operand pair (6-bit activation codes, FP4 weight nibbles; row-major), checked -> (tokens, outs, k)"""
-    if a_codes.dim() != 2 or w_codes.dim() != 2:
-        raise RuntimeError(f"{name}: row-major operands only (k-major images: {name}_km)")
-    tokens, outs, k = a_codes.shape[0], w_codes.shape[0], w_codes.shape[1] * 2
-    if k % 128 != 0 or a_codes.shape[1] * 4 != k * 3 or a_scales.dtype != torch.float16:
-        raise RuntimeError(f"{name}: operand shapes / activation scale dtype mismatch")
-    _check_operand(f"{name}(activation)", a_codes, a_scales, tokens, k * 3 // 4, tokens * (k // 128), a_codes.device)
-    _check_operand(f"{name}(weight)", w_codes, w_scales, outs, k // 2, outs * (k // 128), a_codes.device)
-    return tokens, outs, k
+    return _linear_gelu_dual("linear_fp4_gelu_dual", _FORMATS["e2m1"], "rank", a_codes, a_scales, w_codes, w_scales, bias, return_gelu, outs)
 
 
 def linear_a6w4(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor,
@@ -398,18 +461,7 @@ def linear_a6w4(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_c
     """fp16 [tokens, outs] = dequantize_g6(a) @ dequantize_mx(w).T + bias on the matrix cores (fpq_gemm_a6w4_mx): a 6-bit
     activation fragment of `a_table` ('e1m2' / 'e3m0') against the E2M1 weight nibbles `quantize_mx` emits; gate / residual as
     in linear_fp4.  Row-major operands only."""
-    require_gpu(a_codes, "linear_a6w4")
-    from ._lib import TABLE_IDS
-    a_table = _g6_table("linear_a6w4", a_table)
-    tokens, outs, k = _a6w4_operands("linear_a6w4", a_codes, a_scales, w_codes, w_scales)
-    ep, keep, out = _epilogue("linear_a6w4", tokens, outs, gate, residual, None, a_codes.device)
-    b = _bias_f16("linear_a6w4", bias, outs, a_codes.device, 8)
-    with device_guard(a_codes.device):
-        check(lib().fpq_gemm_a6w4_mx(a_codes.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_codes.data_ptr(), w_scales.data_ptr(),
-                                     dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), out.data_ptr(), tokens, outs, k, ep,
-                                     stream_ptr(a_codes.device)), "fpq_gemm_a6w4_mx")
-    del keep
-    return out
+    return _linear("linear_a6w4", a_table, "rows", a_codes, a_scales, w_codes, w_scales, bias, gate, residual, None)
 
 
 def linear_a6w4_gelu_dual(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor,
@@ -418,36 +470,7 @@ def linear_a6w4_gelu_dual(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table
     NaN fix-up launch) - `fp_quant_e1m2_neg_e2m1_pos_per_group_cuda(F.gelu(linear_a6w4(a, a_table, w, bias), approximate="tanh"),
     4, 128)` as the epilogue of the A6W4 GEMM: fp16 [tokens, outs], outs % 128 == 0.  Row-major operands only.  return_gelu: also
     the GELU values the quantizer saw - the same function of the fp16 Linear output as linear_fp4_gelu_dual's, bit for bit."""
-    require_gpu(a_codes, "linear_a6w4_gelu_dual")
-    from ._lib import TABLE_IDS
-    a_table = _g6_table("linear_a6w4_gelu_dual", a_table)
-    dev = a_codes.device
-    tokens, outs, k = _a6w4_operands("linear_a6w4_gelu_dual", a_codes, a_scales, w_codes, w_scales)
-    if outs % 128 != 0:
-        raise RuntimeError("linear_a6w4_gelu_dual: outs must be a multiple of 128")
-    out = torch.empty((tokens, outs), dtype=torch.float16, device=dev)
-    h = torch.empty((tokens, outs), dtype=torch.float16, device=dev) if return_gelu else None
-    b = _bias_f16("linear_a6w4_gelu_dual", bias, outs, dev, 8)
-    if tokens and outs:
-        from .ops import _nan_scratch
-        with device_guard(dev):
-            flag = _nan_scratch(dev)
-            check(lib().fpq_gemm_a6w4_gelu_dual(a_codes.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_codes.data_ptr(),
-                                                w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(),
-                                                out.data_ptr(), None if h is None else h.data_ptr(), tokens, outs, k, flag.data_ptr(),
-                                                stream_ptr(dev)), "fpq_gemm_a6w4_gelu_dual")
-    return (out, h) if return_gelu else out
-
-
-def _a6w4_km_operands(name: str, a_image, a_scales, w_image, w_scales, bias, outs):
-    """An A6W4 operand pair as k-major images (6-bit activation image [G, tokens, 96], the FP4 GEMM's dealt weight image
-    [G, rows64, 64], both fp32 scale images), checked -> (tokens, outs, k); `outs` as in _check_kmajor_fp4"""
-    if a_image.dim() != 3 or w_image.dim() != 3:
-        raise RuntimeError(f"{name}: both operands must be k-major images (3-D); row-major codes go to {name[:-3]}")
-    if a_image.shape[2] != 96 or w_image.shape[2] != 64 or a_image.shape[0] != w_image.shape[0] or w_image.shape[1] % 64 != 0:
-        raise RuntimeError(f"{name}: k-major images must be [K/128, tokens, 96] (activation) and [K/128, rows, 64] (weight) with the same K "
-                           "and a weight image of a multiple of 64 rows")
-    return _check_kmajor_fp4(name, a_image, a_scales, w_image, w_scales, bias, outs)
+    return _linear_gelu_dual("linear_a6w4_gelu_dual", a_table, "rows", a_codes, a_scales, w_codes, w_scales, bias, return_gelu, None)
 
 
 def linear_a6w4_km(a_image: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_image: torch.Tensor, w_scales: torch.Tensor,
@@ -457,43 +480,14 @@ def linear_a6w4_km(a_image: torch.Tensor, a_scales: torch.Tensor, a_table: str, 
     kmajor=True)` emits it, the weight exactly as a k-major FP4Linear holds it (`to_kmajor(codes, 4, dealt=True)`,
     `to_kmajor_scales(scales, weight_side=True)`).  outs: the Linear's width when it is neither the bias's length nor the weight
     image's row count (a multiple of 64), as in linear_fp4."""
-    require_gpu(a_image, "linear_a6w4_km")
-    from ._lib import TABLE_IDS
-    a_table = _g6_table("linear_a6w4_km", a_table)
-    tokens, outs, k = _a6w4_km_operands("linear_a6w4_km", a_image, a_scales, w_image, w_scales, bias, outs)
-    ep, keep, out = _epilogue("linear_a6w4_km", tokens, outs, gate, residual, None, a_image.device)
-    b = _bias_f16("linear_a6w4_km", bias, outs, a_image.device, 8)
-    with device_guard(a_image.device):
-        check(lib().fpq_gemm_a6w4_mx_km(a_image.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_image.data_ptr(), w_scales.data_ptr(),
-                                        dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), out.data_ptr(), tokens, outs, k, ep,
-                                        stream_ptr(a_image.device)), "fpq_gemm_a6w4_mx_km")
-    del keep
-    return out
+    return _linear("linear_a6w4_km", a_table, "images", a_image, a_scales, w_image, w_scales, bias, gate, residual, outs)
 
 
 def linear_a6w4_gelu_dual_km(a_image: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_image: torch.Tensor, w_scales: torch.Tensor,
                              bias: Optional[torch.Tensor] = None, return_gelu: bool = False, outs: Optional[int] = None):
     """linear_a6w4_gelu_dual on k-major images (fpq_gemm_a6w4_gelu_dual_km), bit for bit the same result; operands as in
     linear_a6w4_km, return_gelu as in linear_a6w4_gelu_dual."""
-    require_gpu(a_image, "linear_a6w4_gelu_dual_km")
-    from ._lib import TABLE_IDS
-    a_table = _g6_table("linear_a6w4_gelu_dual_km", a_table)
-    dev = a_image.device
-    tokens, outs, k = _a6w4_km_operands("linear_a6w4_gelu_dual_km", a_image, a_scales, w_image, w_scales, bias, outs)
-    if outs % 128 != 0:
-        raise RuntimeError("linear_a6w4_gelu_dual_km: outs must be a multiple of 128")
-    out = torch.empty((tokens, outs), dtype=torch.float16, device=dev)
-    h = torch.empty((tokens, outs), dtype=torch.float16, device=dev) if return_gelu else None
-    b = _bias_f16("linear_a6w4_gelu_dual_km", bias, outs, dev, 8)
-    if tokens and outs:
-        from .ops import _nan_scratch
-        with device_guard(dev):
-            flag = _nan_scratch(dev)
-            check(lib().fpq_gemm_a6w4_gelu_dual_km(a_image.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_image.data_ptr(),
-                                                   w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(),
-                                                   out.data_ptr(), None if h is None else h.data_ptr(), tokens, outs, k, flag.data_ptr(),
-                                                   stream_ptr(dev)), "fpq_gemm_a6w4_gelu_dual_km")
-    return (out, h) if return_gelu else out
+    return _linear_gelu_dual("linear_a6w4_gelu_dual_km", a_table, "images", a_image, a_scales, w_image, w_scales, bias, return_gelu, outs)
 
 
 def linear_a6w4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor,
@@ -506,36 +500,13 @@ def linear_a6w4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, a_ta
     takes them) or k-major images (3-D, as linear_a6w4_km takes them), both of the same kind; fp32 weight scales (what quantize_mx
     gives an fp32 weight and FP4Linear holds) - these forms are not compiled for fp16 ones.
     qk_norm_scale, and the fp32 bias that goes with it: as in linear_fp4_qkv_to_cache."""
-    require_gpu(a_codes, "linear_a6w4_qkv_to_cache")
-    from ._lib import TABLE_IDS
-    name = "linear_a6w4_qkv_to_cache"
-    a_table = _g6_table(name, a_table)
-    dev = a_codes.device
-    if cache_kv.dim() != 5 or cache_kv.shape[0] != 2 or cache_kv.dtype != torch.float16 or not cache_kv.is_contiguous() or cache_kv.device != dev:
-        raise RuntimeError(f"{name}: cache_kv must be a contiguous float16 [2, B, max_len, H, c] tensor on the operands' device")
-    if a_codes.dim() == 3 and w_codes.dim() == 3:
-        km = True
-        tokens, outs, k = _a6w4_km_operands(name, a_codes, a_scales, w_codes, w_scales, None, 3 * cache_kv.shape[3] * cache_kv.shape[4])
-    elif a_codes.dim() == 2 and w_codes.dim() == 2:
-        km = False
-        tokens, outs, k = _a6w4_operands(name, a_codes, a_scales, w_codes, w_scales)
-    else:
-        raise RuntimeError(f"{name}: both operands must be row-major codes (2-D) or both k-major images (3-D)")
-    if w_scales.dtype != torch.float32:
-        raise RuntimeError(f"{name}: the weight scales must be float32, got {w_scales.dtype}")
-    q, sp, b, hs = _qkv_split_args(name, cache_kv, tokens, outs, bias, pos, seq, qk_norm_scale)
-    if tokens and qk_norm_scale is not None:
-        with device_guard(dev):
-            check(lib().fpq_gemm_a6w4_mx_split_qknorm(a_codes.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_codes.data_ptr(),
-                                                      w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(),
-                                                      tokens, outs, k, ctypes.byref(sp), hs.data_ptr(), 1 if km else 0, stream_ptr(dev)),
-                  "fpq_gemm_a6w4_mx_split_qknorm")
-    elif tokens:
-        with device_guard(dev):
-            check(lib().fpq_gemm_a6w4_mx_split(a_codes.data_ptr(), a_scales.data_ptr(), TABLE_IDS[a_table], w_codes.data_ptr(),
-                                               w_scales.data_ptr(), dtype_id(w_scales.dtype), None if b is None else b.data_ptr(), tokens, outs,
-                                               k, ctypes.byref(sp), 1 if km else 0, stream_ptr(dev)), "fpq_gemm_a6w4_mx_split")
-    return q
+    return _linear_qkv_to_cache("linear_a6w4_qkv_to_cache", a_table, a_codes, a_scales, w_codes, w_scales, bias, cache_kv, pos, seq, qk_norm_scale)
+
+
+# form -> the public function for E2M1 operands, for 6-bit row-major codes and for 6-bit k-major images
+_FORMS = {"plain": (linear_fp4, linear_a6w4, linear_a6w4_km),
+          "gelu_dual": (linear_fp4_gelu_dual, linear_a6w4_gelu_dual, linear_a6w4_gelu_dual_km),
+          "qkv_to_cache": (linear_fp4_qkv_to_cache, linear_a6w4_qkv_to_cache, linear_a6w4_qkv_to_cache)}
 
 
 class FP4Linear(_ScaledOperandModule):
@@ -581,21 +552,35 @@ class FP4Linear(_ScaledOperandModule):
     def extra_repr(self) -> str:
         return f"in_features={self.in_features}, out_features={self.out_features}, act={self.act_table}, w=e2m1"
 
+    def _quantize(self, x) -> Tuple[torch.Tensor, torch.Tensor]:
+        """x [..., in_features] -> (codes, scales) in the module's own activation format and layout"""
+        fmt = _FORMATS[self.act_table]
+        return _quantize_per_group(fmt.quantizer, fmt, x.to(torch.float16).reshape(-1, self.in_features), self.kmajor)
+
+    def _run(self, form: str, table: Optional[str], a_codes, a_scales, *rest):
+        """`form` of the product (a key of _FORMS) on operands whose codes are in `table` (None: the module's activation format) ->
+        what the public function of that format and of the weight's layout returns; rest: its arguments from the bias up to `outs`."""
+        if table is None:
+            table = self.act_table
+        elif table in ("e2m1", "fp_e2"):
+            table = "e2m1"
+        else:
+            table = _g6_table(f"{type(self).__name__}.forward_operands", table)
+        fp4, rows, images = _FORMS[form]
+        outs = () if form == "qkv_to_cache" else (self.out_features,)   # the last argument; mat_qkv's width is the cache's
+        if table == "e2m1":   # the public functions: they hand the call to the compiled binding when it is loaded
+            return fp4(a_codes, a_scales, self.w_codes, self.w_scales, *rest, *outs)
+        if not self.kmajor:
+            return rows(a_codes, a_scales, table, self.w_codes, self.w_scales, *rest)
+        if a_codes.dim() != 3:
+            raise RuntimeError(f"{type(self).__name__}.forward_operands: the weight is a k-major image - 6-bit activation codes must come as "
+                               "the k-major images of quantize_g6(kmajor=True), not as row-major codes")
+        return images(a_codes, a_scales, table, self.w_codes, self.w_scales, *rest, *outs)
+
     @torch.no_grad()
     def forward(self, x, gate=None, residual=None):
         """gate / residual: the AdaLN block's `residual + y.mul(gate)` fused into the GEMM (see linear_fp4)."""
-        lead = x.shape[:-1]
-        x2 = x.to(torch.float16).reshape(-1, self.in_features)
-        if self.act_table != "e2m1":
-            a_codes, a_scales = quantize_g6(x2, self.act_table, kmajor=self.kmajor)
-            if self.kmajor:
-                y = linear_a6w4_km(a_codes, a_scales, self.act_table, self.w_codes, self.w_scales, self.bias, gate, residual, outs=self.out_features)
-            else:
-                y = linear_a6w4(a_codes, a_scales, self.act_table, self.w_codes, self.w_scales, self.bias, gate, residual)
-            return y.view(*lead, self.out_features)
-        a_codes, a_scales = quantize_mx(x2, kmajor=self.kmajor)
-        y = linear_fp4(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, gate, residual, outs=self.out_features)
-        return y.view(*lead, self.out_features)
+        return self._run("plain", None, *self._quantize(x), self.bias, gate, residual).view(*x.shape[:-1], self.out_features)
 
     @torch.no_grad()
     def qkv_to_cache(self, x, cache_kv: torch.Tensor, pos: int, seq: int, qk_norm_scale: Optional[torch.Tensor] = None,
@@ -615,28 +600,14 @@ class FP4Linear(_ScaledOperandModule):
         elif self.bias is not None:
             raise RuntimeError("FP4Linear.qkv_to_cache: with qk_norm_scale the Linear itself must have no bias (pass cat(q_bias, 0, v_bias) "
                                "as `bias`)")
-        x2 = x.to(torch.float16).reshape(-1, self.in_features)
-        if self.act_table != "e2m1":
-            a_codes, a_scales = quantize_g6(x2, self.act_table, kmajor=self.kmajor)
-            return linear_a6w4_qkv_to_cache(a_codes, a_scales, self.act_table, self.w_codes, self.w_scales, bias, cache_kv, pos, seq,
-                                            qk_norm_scale)
-        a_codes, a_scales = quantize_mx(x2, kmajor=self.kmajor)
-        return linear_fp4_qkv_to_cache(a_codes, a_scales, self.w_codes, self.w_scales, bias, cache_kv, pos, seq, qk_norm_scale)
+        return self._run("qkv_to_cache", None, *self._quantize(x), bias, cache_kv, pos, seq, qk_norm_scale)
 
     @torch.no_grad()
     def forward_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor, gate=None, residual=None, table: Optional[str] = None) -> torch.Tensor:
         """The same product for an activation that already is in operand form - what the fused producers
         `rotation.rotate_quant_mx` / `rotation.adaln_rotate_quant_mx` emit, or `quantize_g6`: fp16 [tokens, out_features].
         table: the format the codes are in (default: the module's activation format)."""
-        table = self.act_table if table is None else ("e2m1" if table in ("e2m1", "fp_e2") else _g6_table("FP4Linear.forward_operands", table))
-        if table != "e2m1":
-            if self.kmajor:
-                if a_codes.dim() != 3:
-                    raise RuntimeError("FP4Linear.forward_operands: the weight is a k-major image - 6-bit activation codes must come as "
-                                       "the k-major images of quantize_g6(kmajor=True), not as row-major codes")
-                return linear_a6w4_km(a_codes, a_scales, table, self.w_codes, self.w_scales, self.bias, gate, residual, outs=self.out_features)
-            return linear_a6w4(a_codes, a_scales, table, self.w_codes, self.w_scales, self.bias, gate, residual)
-        return linear_fp4(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, gate, residual, outs=self.out_features)
+        return self._run("plain", table, a_codes, a_scales, self.bias, gate, residual)
 
 
 class FP4LinearGeluDual(FP4Linear):
@@ -650,27 +621,12 @@ class FP4LinearGeluDual(FP4Linear):
 
     @torch.no_grad()
     def forward(self, x):
-        lead = x.shape[:-1]
-        x2 = x.to(torch.float16).reshape(-1, self.in_features)
-        if self.act_table != "e2m1":   # 6-bit codes on the A6W4 GEMM, whose fc1 form has the same tail
-            a_codes, a_scales = quantize_g6(x2, self.act_table, kmajor=self.kmajor)
-            fc1 = partial(linear_a6w4_gelu_dual_km, outs=self.out_features) if self.kmajor else linear_a6w4_gelu_dual
-            return fc1(a_codes, a_scales, self.act_table, self.w_codes, self.w_scales, self.bias).view(*lead, self.out_features)
-        a_codes, a_scales = quantize_mx(x2, kmajor=self.kmajor)
-        return linear_fp4_gelu_dual(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, outs=self.out_features).view(*lead, self.out_features)
+        return self._run("gelu_dual", None, *self._quantize(x), self.bias, False).view(*x.shape[:-1], self.out_features)
 
     @torch.no_grad()
     def forward_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor, table: Optional[str] = None) -> torch.Tensor:
         """table: the format the codes are in (default: the module's activation format), as in FP4Linear.forward_operands"""
-        table = self.act_table if table is None else ("e2m1" if table in ("e2m1", "fp_e2") else _g6_table("FP4LinearGeluDual.forward_operands", table))
-        if table != "e2m1":
-            if self.kmajor:
-                if a_codes.dim() != 3:
-                    raise RuntimeError("FP4LinearGeluDual.forward_operands: the weight is a k-major image - 6-bit activation codes must "
-                                       "come as the k-major images of quantize_g6(kmajor=True), not as row-major codes")
-                return linear_a6w4_gelu_dual_km(a_codes, a_scales, table, self.w_codes, self.w_scales, self.bias, outs=self.out_features)
-            return linear_a6w4_gelu_dual(a_codes, a_scales, table, self.w_codes, self.w_scales, self.bias)
-        return linear_fp4_gelu_dual(a_codes, a_scales, self.w_codes, self.w_scales, self.bias, outs=self.out_features)
+        return self._run("gelu_dual", table, a_codes, a_scales, self.bias, False)
 
 
 # ---- per-token activations x per-channel weights (W6A6): one scale per row, FP8-coded levels ---------------------
@@ -684,7 +640,6 @@ def quantize_fp8(x: torch.Tensor, table: str = "e2m3") -> Tuple[torch.Tensor, to
     require_gpu(x, "quantize_fp8")
     if x.dtype not in (torch.float16, torch.float32):
         raise RuntimeError(f"quantize_fp8: x must be float16 or float32, got {x.dtype}")
-    from ._lib import TABLE_IDS
     k = x.shape[-1]
     xc = x.contiguous()
     rows = xc.numel() // k
@@ -772,7 +727,6 @@ def quantize_fp6(x: torch.Tensor, kmajor: bool = False, table: str = "e2m3") -> 
     require_gpu(x, "quantize_fp6")
     if x.dtype not in (torch.float16, torch.float32):
         raise RuntimeError(f"quantize_fp6: x must be float16 or float32, got {x.dtype}")
-    from ._lib import TABLE_IDS
     table = _f6_table("quantize_fp6", table)
     k = x.shape[-1]
     if k % 32 != 0:
@@ -834,8 +788,7 @@ def _fp6_gemm(form: str, a_codes, a_scales, a_table: str, w_codes, w_scales, w_t
     a = (a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype))
     w = (w_codes.data_ptr(), w_scales.data_ptr(), dtype_id(w_scales.dtype))
     if (a_table, w_table) != ("e2m3", "e2m3"):
-        from ._lib import TABLE_IDS
-        what, args = "fpq_gemm_f6_rows" + form, (*a, TABLE_IDS[a_table], *w, TABLE_IDS[w_table], *rest, 1 if km else 0)
+            what, args = "fpq_gemm_f6_rows" + form, (*a, TABLE_IDS[a_table], *w, TABLE_IDS[w_table], *rest, 1 if km else 0)
     elif form:
         what, args = "fpq_gemm_fp6_rows" + form, (*a, *w, *rest, 1 if km else 0)
     else:   # the plain E2M3 x E2M3 form has an entry point per layout instead of the flag
@@ -875,9 +828,7 @@ def linear_fp6_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, w_cod
     name = "linear_fp6_qkv_to_cache"
     require_gpu(a_codes, name)
     a_table, w_table = _f6_table(name, a_table), _f6_table(name, w_table)
-    dev = a_codes.device
-    if cache_kv.dim() != 5 or cache_kv.shape[0] != 2 or cache_kv.dtype != torch.float16 or not cache_kv.is_contiguous() or cache_kv.device != dev:
-        raise RuntimeError(f"{name}: cache_kv must be a contiguous float16 [2, B, max_len, H, c] tensor on the operands' device")
+    _check_cache_kv(name, cache_kv, a_codes.device)
     if a_codes.dim() == 2 and w_codes.dim() == 2 and a_codes.shape[1] % 96 != 0:
         raise RuntimeError(f"{name}: operand shapes mismatch")
     km, tokens, outs, k = _fp6_operands(name, a_codes, a_scales, w_codes, w_scales)
