@@ -181,6 +181,13 @@ _SIGS = {
                                            _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_void_p]),
     "fpq_gemm_a6w4_mx_split_qknorm": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p,
                                                   _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    # the rotate and adaLN producers emitting the A6W4 GEMM's activation operands (table, layout: arguments)
+    "fpq_a6w4_rotate_quant_rows_codes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
+                                                     _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int, _c.c_void_p]),
+    "fpq_a6w4_adaln_rotate_quant_rows_codes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64,
+                                                           _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64,
+                                                           _c.c_float, _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int,
+                                                           _c.c_void_p]),
     "fpq_gemm_f6_rows":(_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
                                      _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_void_p]),
     "fpq_gemm_f6_rows_split": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,

@@ -367,7 +367,9 @@ struct AdalnTiers {
 // 0.53 of 8 TB/s at [32768 x 1024] (profiles/r03_survey_shapes.txt).
 // HW6 (1: E2M3, 2: E3M2; value output, rows of at most 16 groups): the levels of a lane's 32 outputs from the FP6 conversion
 // hardware (fpq_fast16.h, fp6_levels_hw32) - per group and per token alike; no table is staged.
-template <typename Tmod, int MAXC, bool CODES, bool EMIT, bool TOKEN, bool X32, bool HW4, bool TIGHT = false, int NW = 4, bool PAIR2 = false, int HW6 = 0>
+// G6 (CODES, per group, table E1M2 / E3M0): the A6W4 GEMM's activation operands (fpq_gemm_a6w4.h) - dense 6-bit codes, 96 bytes
+// per group, through the bucket -> code table lut16_codes_g6 + one scale per group; row-major or the k-major images (r.km_rows).
+template <typename Tmod, int MAXC, bool CODES, bool EMIT, bool TOKEN, bool X32, bool HW4, bool TIGHT = false, int NW = 4, bool PAIR2 = false, int HW6 = 0, bool G6 = false>
 __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ? 5 : 4) void adaln_mfma_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ out,
                                                               u32x4* __restrict__ h_out, u32x4* __restrict__ y_out,
                                                               int64_t rows, AdaLnArgs ad, RotArgs r, Lut16Args a,
@@ -379,6 +381,7 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
   constexpr bool MOD16 = sizeof(Tmod) == 2;
   static_assert(NW == 4, "four wavefronts per workgroup");
   static_assert(!PAIR2 || (MAXC == 4 && !X32 && !EMIT && !TOKEN && !TIGHT), "two rows per tile: fp16 rows of 8 groups, per group");
+  static_assert(!G6 || (CODES && !EMIT && !TOKEN && !HW4 && !TIGHT && !PAIR2 && HW6 == 0), "6-bit group operands: the plain table form");
   constexpr int W = NW;
   constexpr int RPU = PAIR2 ? 2 : 1;             // rows per unit of work of a wavefront
   constexpr int RV = X32 ? 2 * MAXC : MAXC;      // 16-byte registers of one row per lane
@@ -438,7 +441,9 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
   // (`hi_half`), and ONE slot pass - butterfly, maximum, scale, quantize, store - serves both (about 200 of a row's
   // ~700 vector instructions belong to that pass).  Not for the emitting form (tests), the per-token forms (the slot
   // enters the row's scale), fp32 rows (their slot chunk meets in the image).
-  constexpr bool PAIRABLE = MAXC == 5 && !X32 && !EMIT && !TOKEN;
+  // (nor the 6-bit group operands, G6: the second row of a pair sums its LayerNorm statistics with the slot chunk on other lanes -
+  // another fp32 rounding order than the emitting form's, whose rotated rows that form's contract quantizes byte for byte)
+  constexpr bool PAIRABLE = MAXC == 5 && !X32 && !EMIT && !TOKEN && !G6;
   const bool pair_ok = PAIRABLE && vpr - 256 <= 32;
   const int lane16_hi = ((lane + 32) & 63) * 16;     // the slot chunk's vector index of this lane in a `hi_half` row
   auto load_row = [&](u32x4 (&dst)[RV], int64_t row, bool hi_half = false) {
@@ -830,6 +835,27 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
     const int64_t slot_row = (paired && lane < 32) ? pend_row : row;
     const int64_t slot_at = slot_row * vpr + 256 + slot_idx;
     const bool slot_live = do_slot && 256 + slot_idx < vpr;
+    // MAXC == 5, dense 6-bit codes: the 8 codes `cb` of chunk 256 + idx of row `srow` (groups 16 .. 19).  48 bits per lane, rows packed
+    // densely: the four lanes of a quad own 24 contiguous bytes; lane q of the quad takes the (3 - q) upper 16-bit words of its own
+    // string and the q + 1 lower words of its right neighbour's, so that lanes 0..2 each store 8 aligned bytes (cols % 32 == 0: a quad is
+    // live or dead as a whole).  k-major: the same 8 bytes of the row, at byte wb: K step wb / 96, chunk (wb % 96) / 16 of the image.
+    auto slot_store6 = [&](const uint32_t (&cb)[8], int64_t srow, int idx) {
+      const uint64_t own = (uint64_t)(cb[0] | (cb[1] << 6) | (cb[2] << 12) | (cb[3] << 18)) |
+                           ((uint64_t)(cb[4] | (cb[5] << 6) | (cb[6] << 12) | (cb[7] << 18)) << 24);
+      const uint32_t nlo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)own, 0xF9, 0xF, 0xF, false);   // quad_perm [1,2,3,3]
+      const uint32_t nhi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(own >> 32), 0xF9, 0xF, 0xF, false);
+      const uint64_t nb = ((uint64_t)nhi << 32) | nlo;
+      const int qp = idx & 3, sr = 16 * qp;
+      const uint64_t w6 = (own >> sr) | (nb << (48 - sr));
+      if (qp < 3) {
+        uint8_t* dst = (uint8_t*)out + srow * ((int64_t)vpr * 6) + (int64_t)4 * (64 * 6) + 24 * (idx >> 2) + 8 * qp;
+        if (r.km_rows) {
+          const uint32_t wb = 1536u + 24u * ((uint32_t)idx >> 2) + 8u * (uint32_t)qp, w = wb % 96u;
+          dst = (uint8_t*)out + km6_off((uint32_t)srow, wb / 96u, w >> 4, r.km_rows) + (w & 15u);
+        }
+        __builtin_nontemporal_store(u32x2{(uint32_t)w6, (uint32_t)(w6 >> 32)}, (u32x2*)dst);
+      }
+    };
     if constexpr (CODES && TOKEN) {   // per-token operands: E4M3 bytes or dense 6-bit codes, the row scale is out already
       if (r.code_bits == 6) {
         // row-major: the row's 6 vpr bytes behind its start; k-major (include/fpq.h): chunk ch of the row = chunk ch % 6 of K step ch / 6
@@ -853,28 +879,44 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
             cb[2 * k + 1] = lut[u >> (16 + a.shift)];
           }
           if (r.code_bits == 6) {
-            // 8 six-bit codes = 48 bits per lane, rows packed densely: the four lanes of a quad own 24 contiguous bytes;
-            // lane q of the quad takes the (3 - q) upper 16-bit words of its own string and the q + 1 lower words of its
-            // right neighbour's, so that lanes 0..2 each store 8 aligned bytes (cols % 32 == 0: a quad is live or dead
-            // as a whole)
-            const uint64_t own = (uint64_t)(cb[0] | (cb[1] << 6) | (cb[2] << 12) | (cb[3] << 18)) |
-                                 ((uint64_t)(cb[4] | (cb[5] << 6) | (cb[6] << 12) | (cb[7] << 18)) << 24);
-            const uint32_t nlo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)own, 0xF9, 0xF, 0xF, false);   // quad_perm [1,2,3,3]
-            const uint32_t nhi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(own >> 32), 0xF9, 0xF, 0xF, false);
-            const uint64_t nb = ((uint64_t)nhi << 32) | nlo;
-            const int qp = lane & 3, sr = 16 * qp;
-            const uint64_t w6 = (own >> sr) | (nb << (48 - sr));
-            if (qp < 3) {
-              uint8_t* dst = (uint8_t*)out + row * ((int64_t)vpr * 6) + (int64_t)4 * (64 * 6) + 24 * (lane >> 2) + 8 * qp;
-              if (r.km_rows) {   // the same 8 bytes of the row, at byte wb: K step wb / 96, chunk (wb % 96) / 16 of the k-major image
-                const uint32_t wb = 1536u + 24u * ((uint32_t)lane >> 2) + 8u * (uint32_t)qp, w = wb % 96u;
-                dst = (uint8_t*)out + km6_off((uint32_t)row, wb / 96u, w >> 4, r.km_rows) + (w & 15u);
-              }
-              __builtin_nontemporal_store(u32x2{(uint32_t)w6, (uint32_t)(w6 >> 32)}, (u32x2*)dst);
-            }
+            slot_store6(cb, row, lane);
           } else {
             const u32x2 o2 = {cb[0] | (cb[1] << 8) | (cb[2] << 16) | (cb[3] << 24), cb[4] | (cb[5] << 8) | (cb[6] << 16) | (cb[7] << 24)};
             __builtin_nontemporal_store(o2, (u32x2*)out + slot_at);
+          }
+        }
+      }
+    } else if constexpr (CODES && G6) {   // A6W4 operands: 96 bytes of 6-bit codes + one scale per group (fpq_gemm_a6w4.h)
+      // row-major: the row's 6 vpr bytes behind its start, the tile's groups the first 96 x 16 of them; k-major: chunk ch of the
+      // tile = chunk ch % 6 of group ch / 6 (include/fpq.h).  Scales as in the FP4 branch below.
+      const uint32_t gpr = (uint32_t)vpr >> 4;
+      const __amdgpu_buffer_rsrc_t d6 = r.km_rows ? rq_rsrc(out, (int)(r.km_rows * gpr * 96u)) : rq_rsrc((const uint8_t*)out + row * ((int64_t)vpr * 6), vpr * 6);
+      const uint32_t tpad = (r.km_rows + 3u) & ~3u;
+      const __amdgpu_buffer_rsrc_t sdst = r.km_rows ? rq_rsrc(r.code_scales, (int)(tpad * gpr * 4u)) : rq_rsrc(r.code_scales + row * (vpr >> 4), (vpr >> 4) * 2);
+      rq_store_codes6((u32x4*)img, yw, s, lut, a.shift, d6, lane, [&](int ch) -> uint32_t {
+        if (!r.km_rows) return (uint32_t)ch * 16u;
+        const uint32_t g = (uint32_t)ch / 6u;
+        return g < gpr ? km6_off((uint32_t)row, g, (uint32_t)ch - 6u * g, r.km_rows) : 0xFFFFFFFFu;
+      });
+      rq_store_scale(s, sdst, rq_opaque(lane), [&](int u_) -> uint32_t {
+        if (!r.km_rows) return (uint32_t)u_ * 2u;
+        return (uint32_t)u_ < gpr ? ((((uint32_t)u_ * tpad + (uint32_t)row) * 4u) | 0x80000000u) : 0xFFFFFFFFu;
+      });
+      if constexpr (MAXC == 5) {
+        if (slot_live) {   // (wave-uniform do_slot inside; cols % 128 == 0: a quad is live or dead as a whole)
+          uint32_t cb[8];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const uint32_t rb = div_pair16(y1[k], s1.inv, s1.inv_lo, s1.inv, s1.inv_lo);
+            const uint32_t u = pk_sub_u16(rb, pk_lshr_u16(rb, 15));
+            cb[2 * k] = lut[(u & 0xFFFFu) >> a.shift];
+            cb[2 * k + 1] = lut[u >> (16 + a.shift)];
+          }
+          slot_store6(cb, slot_row, slot_idx);   // (this form pairs no rows: slot_row == row, slot_idx == lane)
+          if ((lane & 15) == 0) {
+            const uint16_t sc16 = (uint16_t)(s1.s16x2 & 0xFFFFu);
+            if (r.km_rows) ((float*)r.code_scales)[(int64_t)(16u + ((uint32_t)slot_idx >> 4)) * tpad + slot_row] = (float)__builtin_bit_cast(_Float16, sc16);
+            else r.code_scales[slot_at >> 4] = sc16;
           }
         }
       }

@@ -1,4 +1,4 @@
-// fpq_adaln.hip - the adaLN producer (fpq_adaln.h: LayerNorm, modulation, rotation and quantizer in one launch) and its eight
+// fpq_adaln.hip - the adaLN producer (fpq_adaln.h: LayerNorm, modulation, rotation and quantizer in one launch) and its nine
 // C entry points.  A unit of its own because its ~230 kernel forms take longer to compile than the rest of the quantizers
 // together: an edit elsewhere does not recompile them.
 #include "fpq_common.h"
@@ -14,18 +14,21 @@ int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out
                               hipStream_t st, uint16_t* code_scales = nullptr,
                               int token_mode = 0 /*1: per-token values, 2: per-token E4M3 codes, 3: per-token packed 6-bit codes*/,
                               const Lut16Tab* token_code_tab = nullptr,
-                              bool km = false /* FP4 / 6-bit codes into a k-major image (include/fpq.h): adaln_mfma_kernel only */) {
+                              bool km = false /* FP4 / 6-bit codes into a k-major image (include/fpq.h): adaln_mfma_kernel only */,
+                              bool g6 = false /* per group, code_scales: the A6W4 GEMM's 6-bit codes of table_id (E1M2 / E3M0) instead of
+                                                 FP4; adaln_mfma_kernel only */) {
   const Lut16Host& h = lut16_host(table_id, table_id);
   if (!h.tab_valid) return FPQ_ERR_TABLE;
-  const Lut16Tab& tab = token_mode >= 2 ? *token_code_tab : (code_scales && !token_mode ? lut16_mx_codes_e2m1() : h.tab);
+  if (g6 && (cols / 8 > 64 * 5 || !code_scales || token_mode)) return FPQ_ERR_SHAPE;
+  const Lut16Tab& tab = token_mode >= 2 ? *token_code_tab : g6 ? lut16_codes_g6(table_id) : (code_scales && !token_mode ? lut16_mx_codes_e2m1() : h.tab);
   RotArgs r;
   r.code_scales = code_scales;
-  r.code_bits = token_mode == 3 ? 6 : 8;
+  r.code_bits = (token_mode == 3 || g6) ? 6 : 8;
   r.km_rows = km ? (uint32_t)rows : 0u;
   r.km_gpr = fast_div((uint32_t)(cols / 128));
   if (km) {
     const bool fp4_codes = code_scales && !token_mode;
-    if (!(fp4_codes || token_mode == 3) || !km_image_fits(rows, token_mode == 3 ? cols / 4 * 3 : cols / 2)) return FPQ_ERR_SHAPE;
+    if (!(fp4_codes || token_mode == 3) || !km_image_fits(rows, (token_mode == 3 || g6) ? cols / 4 * 3 : cols / 2)) return FPQ_ERR_SHAPE;
     if (cols / 8 > 64 * 5) return FPQ_ERR_SHAPE;   // rows beyond one wavefront: the first generation writes row-major codes only
   }
   r.smooth = smooth;
@@ -57,7 +60,7 @@ int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out
       int rows_per_wg = rows_env ? fpq_opt(OPT_FPQ_ADALN_ROWS, 0) : (rows >= 8192 ? (issue_bound && rows >= 32768 ? 12 : 8) : 4);
       if (rows_per_wg < 1) rows_per_wg = 1;
       // rows of exactly 8 groups (C = 1024): two rows per tile (fpq_adaln.h, PAIR2) - workgroups of an even number of rows
-      const bool pair2 = !X32 && r.vec_per_row == 128 && token_mode == 0 && !h_out && !y_out &&
+      const bool pair2 = !X32 && r.vec_per_row == 128 && token_mode == 0 && !h_out && !y_out && !g6 &&
                          !fpq_flag(OPT_FPQ_ADALN_NO_PAIR2);
       if (pair2) rows_per_wg = rows_env ? ((rows_per_wg + 1) & ~1) : (rows >= 8192 ? 16 : 8);
       const int64_t per_batch = (L + rows_per_wg - 1) / rows_per_wg;
@@ -109,6 +112,9 @@ int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out
           if (hw6 == 1) return go(adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 1>);
           if (hw6 == 2) return go(adaln_mfma_kernel<Tmod, M, false, false, TOKEN, X32, false, false, 4, false, 2>);
         }
+        if constexpr (CODES && !EMIT && !TOKEN) {   // 6-bit group operands: one form per row length, modulation and row dtype
+          if (g6) return go(adaln_mfma_kernel<Tmod, M, true, false, false, X32, false, false, 4, false, 0, true>);
+        }
         if constexpr (M == 2 && !X32 && !EMIT && !TOKEN) {
           if (pair2)
             return with_bool(hw4, [&](auto hw) {
@@ -148,7 +154,7 @@ static int adaln_rotate_quant_impl(const void* x, void* out, void* h_out, void* 
                                    int64_t rows, int64_t cols, int in_dtype, const void* scale, const void* shift,
                                    int mod_dtype, int64_t rows_per_batch, float eps, const float* smooth,
                                    const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream,
-                                   int token_mode = 0, const Lut16Tab* token_code_tab = nullptr, bool km = false) {
+                                   int token_mode = 0, const Lut16Tab* token_code_tab = nullptr, bool km = false, bool g6 = false) {
   if (rows < 0 || cols < 0 || rows_per_batch <= 0 || !sign_mask_host) return FPQ_ERR_ARG;
   if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
   if (!is_f16_or_f32(in_dtype) || !is_f16_or_f32(mod_dtype)) return FPQ_ERR_DTYPE;
@@ -172,7 +178,7 @@ static int adaln_rotate_quant_impl(const void* x, void* out, void* h_out, void* 
   return with_dtype(in_dtype, [&](auto ti) {
     return with_dtype(mod_dtype, [&](auto tm) {
       return launch_adaln_rotate_quant<decltype(ti), decltype(tm)>(x, out, h_out, rotated_out, rows, cols, ad, smooth, sign_mask_host,
-                                                                   table_id, st, (uint16_t*)code_scales, token_mode, token_code_tab, km);
+                                                                   table_id, st, (uint16_t*)code_scales, token_mode, token_code_tab, km, g6);
     });
   });
 }
@@ -253,6 +259,24 @@ int fpq_adaln_rotate_quant_token_rows_codes_f6(const void* x, uint8_t* codes, vo
   if ((((uintptr_t)codes) & 7) != 0) return FPQ_ERR_ARG;
   return adaln_rotate_quant_impl(x, codes, nullptr, nullptr, row_scales, rows, cols, in_dtype, scale, shift, mod_dtype,
                                  rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 3, &lut16_codes6(table_id), kmajor != 0);
+}
+
+
+// the A6W4 GEMM's activation operands (include/fpq.h): what fpq_quant_rows_codes_g6 / fpq_a6w4_quant_rows_codes_km make of the
+// rotated rows of fpq_adaln_rotate_quant_rows; the matrix-core kernel only (cols <= 2560)
+int fpq_a6w4_adaln_rotate_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
+                                           const void* scale, const void* shift, int mod_dtype, int64_t rows_per_batch, float eps,
+                                           const float* smooth, const uint32_t* sign_mask_host, int table_id, int kmajor,
+                                           fpq_stream_t stream) {
+  if (rows < 0 || cols < 0 || rows_per_batch <= 0 || !sign_mask_host) return FPQ_ERR_ARG;
+  if (table_id != FPQ_E1M2 && table_id != FPQ_E3M0) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype) || !is_f16_or_f32(mod_dtype)) return FPQ_ERR_DTYPE;
+  if (cols % 128 != 0 || cols > 2560 || (kmajor && !km_image_fits(rows, cols / 4 * 3))) return FPQ_ERR_SHAPE;
+  if (rows == 0 || cols == 0) return FPQ_OK;
+  if (!x || !codes || !scales || !scale || !shift) return FPQ_ERR_ARG;
+  if ((((uintptr_t)codes | (uintptr_t)scales) & 15) != 0) return FPQ_ERR_ARG;   // (x, scale, shift, smooth: checked below)
+  return adaln_rotate_quant_impl(x, codes, nullptr, nullptr, scales, rows, cols, in_dtype, scale, shift, mod_dtype,
+                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 0, nullptr, kmajor != 0, true);
 }
 
 }  // extern "C"

@@ -13,16 +13,17 @@ namespace {
 template <typename Tin>
 int launch_rotate_quant(const void* x, void* out, void* rot_out, int64_t rows, int64_t cols, const float* smooth,
                         const uint32_t sign[4], int table_id, hipStream_t st, uint16_t* code_scales = nullptr,
-                        bool km = false /* FP4 codes into a k-major image (include/fpq.h) */) {
+                        bool km = false /* codes into a k-major image (include/fpq.h) */,
+                        bool g6 = false /* code_scales: the A6W4 GEMM's 6-bit codes of table_id (E1M2 / E3M0) instead of FP4 */) {
   const Lut16Host& h = lut16_host(table_id, table_id);
   if (!h.tab_valid) return FPQ_ERR_TABLE;
-  const Lut16Tab& tab = code_scales ? lut16_mx_codes_e2m1() : h.tab;
+  const Lut16Tab& tab = g6 ? lut16_codes_g6(table_id) : code_scales ? lut16_mx_codes_e2m1() : h.tab;
   RotArgs r;
   r.code_scales = code_scales;
-  r.code_bits = 8;
+  r.code_bits = g6 ? 6 : 8;
   r.km_rows = km ? (uint32_t)rows : 0u;
   r.km_gpr = fast_div((uint32_t)(cols / 128));
-  if (km && (!code_scales || !km_image_fits(rows, cols / 2))) return FPQ_ERR_SHAPE;
+  if (km && (!code_scales || !km_image_fits(rows, g6 ? cols / 4 * 3 : cols / 2))) return FPQ_ERR_SHAPE;
   r.smooth = smooth;
   for (int i = 0; i < 4; ++i) r.sign[i] = sign[i];
   r.c_h = h2f(f2h(1.0f / __builtin_sqrtf(128.0f)));   // torch.tensor(128).sqrt() is float32; autocast makes Q fp16
@@ -53,6 +54,10 @@ int launch_rotate_quant(const void* x, void* out, void* rot_out, int64_t rows, i
       });
     });
   };
+  if (g6)   // (never E2M1: a table form)
+    return with_bool(smooth != nullptr, [&](auto sm) {
+      return launch(rotate_quant_mfma_kernel<Tin, false, sm.value, true, false, true>, mgrid, lds, st, x, out, rot_out, n_vec, r, h.args, tab);
+    });
   if (code_scales) return go(Bool<false>{}, Bool<true>{});
   if (rot_out) return go(Bool<true>{}, Bool<false>{});
   return go(Bool<false>{}, Bool<false>{});
@@ -64,7 +69,7 @@ extern "C" {
 
 static int rotate_quant_impl(const void* x, void* out, void* rotated_out, void* code_scales, int64_t rows, int64_t cols,
                              int in_dtype, const float* smooth, const uint32_t* sign_mask_host, int table_id,
-                             fpq_stream_t stream, bool km = false) {
+                             fpq_stream_t stream, bool km = false, bool g6 = false) {
   if (rows < 0 || cols < 0 || !sign_mask_host) return FPQ_ERR_ARG;
   if (!is_symmetric_table(table_id)) return FPQ_ERR_TABLE;
   if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
@@ -74,7 +79,7 @@ static int rotate_quant_impl(const void* x, void* out, void* rotated_out, void* 
   if ((((uintptr_t)x | (uintptr_t)out | (uintptr_t)rotated_out | (uintptr_t)smooth) & 15) != 0) return FPQ_ERR_ARG;
   return with_dtype(in_dtype, [&](auto t) {
     return launch_rotate_quant<decltype(t)>(x, out, rotated_out, rows, cols, smooth, sign_mask_host, table_id, (hipStream_t)stream,
-                                            (uint16_t*)code_scales, km);
+                                            (uint16_t*)code_scales, km, g6);
   });
 }
 
@@ -92,6 +97,19 @@ int fpq_rotate_quant_rows_codes_mx_km(const void* x, uint8_t* image, void* scale
                                       const float* smooth, const uint32_t* sign_mask_host, fpq_stream_t stream) {
   if (rows > 0 && cols > 0 && !scales) return FPQ_ERR_ARG;
   return rotate_quant_impl(x, image, nullptr, scales, rows, cols, in_dtype, smooth, sign_mask_host, FPQ_E2M1, stream, true);
+}
+
+// the A6W4 GEMM's activation operands (include/fpq.h): what fpq_quant_rows_codes_g6 / fpq_a6w4_quant_rows_codes_km make of the rotated rows
+int fpq_a6w4_rotate_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
+                                     const float* smooth, const uint32_t* sign_mask_host, int table_id, int kmajor, fpq_stream_t stream) {
+  if (rows < 0 || cols < 0 || !sign_mask_host) return FPQ_ERR_ARG;
+  if (table_id != FPQ_E1M2 && table_id != FPQ_E3M0) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
+  if (cols % 128 != 0 || (kmajor && !km_image_fits(rows, cols / 4 * 3))) return FPQ_ERR_SHAPE;
+  if (rows == 0 || cols == 0) return FPQ_OK;
+  if (!x || !codes || !scales) return FPQ_ERR_ARG;
+  if ((((uintptr_t)x | (uintptr_t)codes | (uintptr_t)scales | (uintptr_t)smooth) & 15) != 0) return FPQ_ERR_ARG;
+  return rotate_quant_impl(x, codes, nullptr, scales, rows, cols, in_dtype, smooth, sign_mask_host, table_id, stream, kmajor != 0, true);
 }
 
 int fpq_quant_rows_codes_fp8(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,

@@ -398,12 +398,15 @@ __device__ __forceinline__ void rq_store_codes6(u32x4* buf, const uint32_t (&yw)
 // HW4 (E2M1 values or FP4 operands): levels / codes from the FP4 conversion hardware (fpq_fast16.h) - no table lookups
 // SMOOTH (the GALT vector applied in front of the rotation: 32 more floats per lane and tile in flight) takes 5 wavefronts
 // per SIMD = 96 registers: at 80 it spilled 3 - 8 of them (tests/test_no_spill.py reads every kernel's metadata).
-template <typename Tin, bool EMIT, bool SMOOTH, bool CODES = false, bool HW4 = false>
+// G6 (CODES, table E1M2 / E3M0): the A6W4 GEMM's activation operands instead (fpq_gemm_a6w4.h) - dense 6-bit codes, 96 bytes per
+// group, from the staged bucket -> code table lut16_codes_g6, + one scale per group; row-major or the k-major images (r.km_rows)
+template <typename Tin, bool EMIT, bool SMOOTH, bool CODES = false, bool HW4 = false, bool G6 = false>
 __global__ __launch_bounds__(kBlock, SMOOTH ? FPQ_ROT_WAVES - 1 : FPQ_ROT_WAVES) void rotate_quant_mfma_kernel(const void* __restrict__ xv,
                                                                                  u32x4* __restrict__ out,
                                                                                  u32x4* __restrict__ rot_out,
                                                                                  int64_t n_vec, RotArgs r, Lut16Args a,
                                                                                  Lut16Tab tab) {
+  static_assert(!G6 || (CODES && !HW4 && !EMIT), "6-bit group operands: a table form of the code output");
   uint16_t* lut = nullptr;
   if constexpr (!HW4) {
     __shared__ __attribute__((aligned(16))) uint16_t lut_s[kLutLdsEntries];
@@ -556,7 +559,17 @@ __global__ __launch_bounds__(kBlock, SMOOTH ? FPQ_ROT_WAVES - 1 : FPQ_ROT_WAVES)
         const uint32_t gi = (uint32_t)(base_vec >> 4) + (uint32_t)u, t = fast_div_q(gi, r.km_gpr);
         return (int64_t)gi * 16 < n_vec ? ((((gi - t * r.km_gpr.d) * tpad + t) * 4u) | 0x80000000u) : 0xFFFFFFFFu;
       };
-      if constexpr (HW4)
+      if constexpr (G6) {
+        // 96 bytes per group: the tile's 16 groups are 1.5 KiB in a row behind group base_vec / 16 (row-major), or - k-major - chunk
+        // ch of the tile is chunk ch % 6 of group ch / 6 of the tile, each group with its own (row, group) slot; dead groups dropped
+        const __amdgpu_buffer_rsrc_t d6 = r.km_rows ? rq_rsrc(out, (int)(r.km_rows * r.km_gpr.d * 96u)) : rq_rsrc((const uint8_t*)out + (base_vec >> 4) * 96, rem * 6);
+        rq_store_codes6(buf, yw, s, lut, a.shift, d6, lane, [&](int ch) -> uint32_t {
+          if (!r.km_rows) return (uint32_t)ch * 16u;
+          const uint32_t u = (uint32_t)ch / 6u, gi = (uint32_t)(base_vec >> 4) + u, t = fast_div_q(gi, r.km_gpr);
+          return (int64_t)gi * 16 < n_vec ? km6_off(t, gi - t * r.km_gpr.d, (uint32_t)ch - 6u * u, r.km_rows) : 0xFFFFFFFFu;
+        });
+        rq_store_scale(s, sdst, rq_opaque(lane), soff);
+      } else if constexpr (HW4)
         rq_store_codes_hw(img, yw, s, cdst, sdst, rq_opaque(lane), coff, soff);
       else
         rq_store_codes(buf, yw, s, lut, a.shift, cdst, sdst, lane, coff, soff);

@@ -592,15 +592,48 @@ class FP4Linear(_ScaledOperandModule):
         Without qk_norm_scale the module's fp16 bias is added and `bias` must be None.  With qk_norm_scale (fp32 [H]: the block has
         attn_l2_norm) `bias` is the fp32 cat(q_bias, 0, v_bias) [3 * C] or None, added after the fp16 rounding, and the module itself
         must have no bias (mat_qkv has none in the reference)."""
+        bias = self._qkv_bias("qkv_to_cache", qk_norm_scale, bias)
+        return self._run("qkv_to_cache", None, *self._quantize(x), bias, cache_kv, pos, seq, qk_norm_scale)
+
+    def _qkv_bias(self, name: str, qk_norm_scale, bias):
+        """the bias of the split mat_qkv: the module's own without the q / k norm, the caller's fp32 one with it"""
         if qk_norm_scale is None:
             if bias is not None:
-                raise RuntimeError("FP4Linear.qkv_to_cache: `bias` is the fp32 bias of the q / k norm form - without qk_norm_scale the "
+                raise RuntimeError(f"FP4Linear.{name}: `bias` is the fp32 bias of the q / k norm form - without qk_norm_scale the "
                                    "module's own bias is used")
-            bias = self.bias
-        elif self.bias is not None:
-            raise RuntimeError("FP4Linear.qkv_to_cache: with qk_norm_scale the Linear itself must have no bias (pass cat(q_bias, 0, v_bias) "
+            return self.bias
+        if self.bias is not None:
+            raise RuntimeError(f"FP4Linear.{name}: with qk_norm_scale the Linear itself must have no bias (pass cat(q_bias, 0, v_bias) "
                                "as `bias`)")
-        return self._run("qkv_to_cache", None, *self._quantize(x), bias, cache_kv, pos, seq, qk_norm_scale)
+        return bias
+
+    @torch.no_grad()
+    def qkv_to_cache_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor, cache_kv: torch.Tensor, pos: int, seq: int,
+                              qk_norm_scale: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`qkv_to_cache` for an activation that already is in operand form (the module's own format and layout: what
+        `adaln_operands` / `rotate_operands` return): producer -> split GEMM -> cache without the activation in HBM as fp16."""
+        return self._run("qkv_to_cache", None, a_codes, a_scales, self._qkv_bias("qkv_to_cache_operands", qk_norm_scale, bias), cache_kv, pos, seq, qk_norm_scale)
+
+    @torch.no_grad()
+    def adaln_operands(self, x, scale, shift, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
+                       eps: float = 1e-6) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The block's producer in front of this Linear - LayerNorm, adaLN modulate, smooth, rotate, per-group quantize of x [B, L,
+        in_features] - in one launch, emitting (codes, scales) in the module's own activation format and layout
+        (`rotation.adaln_rotate_quant_mx` for E2M1, `rotation.adaln_rotate_quant_g6` for E1M2 / E3M0; k-major iff the weight is):
+        ready for `forward_operands` / `qkv_to_cache_operands`.  One call in front of every mat_qkv and fc1 of a mixed-format model."""
+        from . import rotation
+        if self.act_table == "e2m1":
+            return rotation.adaln_rotate_quant_mx(x, scale, shift, d=d, smooth=smooth, eps=eps, kmajor=self.kmajor)
+        return rotation.adaln_rotate_quant_g6(x, scale, shift, self.act_table, d=d, smooth=smooth, eps=eps, kmajor=self.kmajor)
+
+    @torch.no_grad()
+    def rotate_operands(self, x, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`adaln_operands` without the LayerNorm and the modulation: smooth, rotate, per-group quantize of x [..., in_features]
+        (`rotation.rotate_quant_mx` / `rotation.rotate_quant_g6`)."""
+        from . import rotation
+        if self.act_table == "e2m1":
+            return rotation.rotate_quant_mx(x, d=d, smooth=smooth, kmajor=self.kmajor)
+        return rotation.rotate_quant_g6(x, self.act_table, d=d, smooth=smooth, kmajor=self.kmajor)
 
     @torch.no_grad()
     def forward_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor, gate=None, residual=None, table: Optional[str] = None) -> torch.Tensor:

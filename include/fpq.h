@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FPQ_VERSION 134 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
+#define FPQ_VERSION 135 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
                            0.1.3: + fpq_quant_rows_codes_segments, fpq_dequant_rows_codes_segments (round 3);
                            123: + fpq_build_tag (round 4);
                            124: + fpq_set_option, fpq_get_option, fpq_option_name, fpq_gemm_fp4_gelu_dual, fpq_gelu_quant_rows_dual (round 5);
@@ -41,7 +41,9 @@ extern "C" {
                                 fpq_gemm_a6w4_mx;
                            132: + the fc1 tail (GELU + fc2's dual-format input quantizer) in the A6W4 GEMM: fpq_gemm_a6w4_gelu_dual;
                            133: + the A6W4 path on k-major images: fpq_a6w4_quant_rows_codes_km, fpq_gemm_a6w4_mx_km, fpq_gemm_a6w4_gelu_dual_km;
-                           134: + the split output and the q / k norm in the A6W4 GEMM: fpq_gemm_a6w4_mx_split, fpq_gemm_a6w4_mx_split_qknorm */
+                           134: + the split output and the q / k norm in the A6W4 GEMM: fpq_gemm_a6w4_mx_split, fpq_gemm_a6w4_mx_split_qknorm;
+                           135: + the rotate and adaLN producers emitting the A6W4 GEMM's activation operands: fpq_a6w4_rotate_quant_rows_codes,
+                                fpq_a6w4_adaln_rotate_quant_rows_codes */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -769,6 +771,31 @@ int fpq_gemm_a6w4_mx_split(const uint8_t* a_codes, const void* a_scales, int a_t
 int fpq_gemm_a6w4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
                                   int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
                                   const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream);
+
+/* THE PRODUCERS IN FRONT OF THE A6W4 GEMM: the online rotation and the adaLN producer emitting its activation operands in one launch,
+ * as fpq_rotate_quant_rows_codes_mx[_km] / fpq_adaln_rotate_quant_rows_codes_mx[_km] do for the FP4 GEMM - the activation never exists
+ * in HBM as fp16 between the block's LayerNorm and its matrix product (the mixed W4A4 model's mat_qkv and fc1 have an E3M0 activation
+ * in almost every block).  x, rows, cols, in_dtype, smooth, sign_mask_host [, scale, shift, mod_dtype, rows_per_batch, eps]: exactly
+ * the arguments of fpq_rotate_quant_rows / fpq_adaln_rotate_quant_rows.  table_id: FPQ_E1M2 or FPQ_E3M0.
+ *   kmajor = 0: codes [rows, cols * 3 / 4] (the bit format of fpq_quant_rows_codes_g6), scales fp16 [rows, cols / 128]
+ *   kmajor = 1: the activation side's 6-bit image [cols / 128][rows][96] and the fp32 scale image [cols / 128][rows rounded up to 4]
+ *               (padding rows not written) - exactly what fpq_gemm_a6w4_mx_km, fpq_gemm_a6w4_gelu_dual_km and the split forms take
+ * CONTRACT: let y be the fp16 rotated rows that fpq_rotate_quant_rows / fpq_adaln_rotate_quant_rows write to rotated_out for the same
+ * arguments.  Then codes and scales are byte for byte what fpq_quant_rows_codes_g6(y) writes (kmajor = 0) or what
+ * fpq_a6w4_quant_rows_codes_km(y) writes (kmajor = 1; padding rows of the scale image excluded).  Hence level(code) * scale equals the
+ * `out` of the values form with the same table_id, bit for bit; non-finite groups follow fpq_quant_rows_codes_g6's rule (the maximum
+ * itself is the scale, every code is a valid code, an all-zero group has scale 0 and code 0).
+ * fpq_a6w4_adaln_rotate_quant_rows_codes runs on the matrix-core kernel only: cols <= 2560 (beyond: FPQ_ERR_SHAPE).
+ * Checks, in this order, before any launch: negative sizes, rows_per_batch <= 0 or sign_mask_host == NULL (FPQ_ERR_ARG); table_id
+ * (FPQ_ERR_TABLE); in_dtype / mod_dtype other than FPQ_F16 / FPQ_F32 (FPQ_ERR_DTYPE); cols % 128, [adaLN: cols > 2560,] with kmajor an
+ * image of 2 GiB or more (FPQ_ERR_SHAPE); rows == 0 or cols == 0 (FPQ_OK, nothing launched); then NULL x / codes / scales [/ scale /
+ * shift] or x, codes, scales, smooth [, scale, shift] not 16-byte aligned (FPQ_ERR_ARG). */
+int fpq_a6w4_rotate_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
+                                     const float* smooth, const uint32_t* sign_mask_host, int table_id, int kmajor, fpq_stream_t stream);
+int fpq_a6w4_adaln_rotate_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
+                                           const void* scale, const void* shift, int mod_dtype, int64_t rows_per_batch, float eps,
+                                           const float* smooth, const uint32_t* sign_mask_host, int table_id, int kmajor,
+                                           fpq_stream_t stream);
 
 /* fpq_kv_cache_step_qknorm: fpq_kv_cache_step (same arguments, same checks) for an fp16 qkv WITHOUT the norm (path F, or a
  * mat_qkv that is not split): the new k is normalized and the bias added on its way into the cache, and the same launch writes
