@@ -23,8 +23,16 @@
 //  19-bit inputs are not: rotated values went from <= 1 to 3 fp16 ulp off the fp64 product.)
 // LayerNorm statistics: one pass (E[x^2] - mean^2) with a centred second pass for rows where that cancels; fp32
 // rounding of the folded modulate differs from torch's three separate ops by a few 2^-24 - the parity contract of this entry point
-// is the fuzzy one of SURVEY.md section 7 (tests/test_gpu_parity.py::test_adaln_rotate_quant_fused: h within half an
-// fp16 ulp + 4e-6 relative, rotated values and quantization bit-exact given h).
+// is the fuzzy one of SURVEY.md section 7: h within tests/adaln_model.py::bound of the float64 value (half an fp16 ulp + the
+// fp32 terms derived there from this source: the sums' depth, the one-pass variance's 1 + min(rho^2, 64 | 8) amplification, the
+// modulate's roundings), quantization bit-exact given the rotated row, every non-emitting form bit for bit the emitting one.
+// tests/test_gpu_adaln.py holds both kernels to it on rows at the switch to the centred pass, high-mean, constant, var ~ eps, 1e4,
+// inf and NaN rows.  Measured worst err / bound on an MI355X: adaln_mfma_kernel fp16 rows 0.999, fp32 rows 0.999,
+// adaln_rotate_quant16_kernel 0.999.  The rotated row of adaln_mfma_kernel is rotate_quant(h) bit for bit: the tile and the slot
+// (groups 16 .. 19) go through the same matrix-core transform; the wide kernel uses fp32 butterflies: one fp16 ulp off on ~1e-6
+// of the elements, as close to the float64 product as the matrix cores' (test_emitting_form_rotates_and_quantizes_as_rotate_quant).
+// The two forms that sum a second row's statistics in another order (PAIR2, the paired slot): 2 of 12 212 groups not bit-equal
+// to the emitting form (both on a row just under the switch), 0 of 5 392 on gauss and log-normal rows.
 #pragma once
 
 // ---------------------------------------------------------------------------------
@@ -144,13 +152,16 @@ __global__ __launch_bounds__(kBlock) void adaln_rotate_quant16_kernel(const void
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) {
     const bool live = (int64_t)c * LANES + lane < vpr;
+    float p = 0.0f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       float d = f[c][i] - mean;
       f[c][i] = d;
-      s2 = __builtin_fmaf(d, d, s2);
+      p = __builtin_fmaf(d, d, p);
     }
-    if (!live) s2 -= 8.0f * mean * mean;   // padding lanes hold zeros: take their (0 - mean)^2 back out
+    // the zero padding is not part of the row: its (0 - mean)^2 never enters the sum (added and taken back out, the
+    // 8 mean^2 per padding vector left their rounding behind - a variance off by 1e-2 at |mean| / std = 1000)
+    if (live) s2 += p;
   }
   const float var = row_sum_f32(s2, shf) * inv_c;
   const float rstd = 1.0f / __builtin_sqrtf(var + ad.eps);
@@ -438,7 +449,7 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
   // Rows of 17 / 18 groups (d36: C = 2304): the one or two groups beyond the tile fill at most half of the 64-lane slot
   // that transforms them as butterflies.  A wavefront therefore pairs its rows: the first row of a pair parks its
   // modulated slot chunk (lanes 0 .. 31), the second row is loaded and modulated with its slot chunk on lanes 32 .. 63
-  // (`hi_half`), and ONE slot pass - butterfly, maximum, scale, quantize, store - serves both (about 200 of a row's
+  // (`hi_half`), and ONE slot pass - transform, maximum, scale, quantize, store - serves both (about 200 of a row's
   // ~700 vector instructions belong to that pass).  Not for the emitting form (tests), the per-token forms (the slot
   // enters the row's scale), fp32 rows (their slot chunk meets in the image).
   // (nor the 6-bit group operands, G6: the second row of a pair sums its LayerNorm statistics with the slot chunk on other lanes -
@@ -704,7 +715,7 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
     FPQ_PHASE("modulate_to_image");
     const __amdgpu_buffer_rsrc_t h_dst = rq_rsrc(EMIT && h_out ? (const char*)(h_out + row * vpr) : nullptr, EMIT && h_out ? vpr * 16 : 0);
     const float rstd_a = rstd, nm_a = nm;
-    u32x4 hw_slot = {0, 0, 0, 0};   // MAXC == 5: chunk 256 + lane of the row (groups 16 .. 19), transformed as butterflies
+    u32x4 hw_slot = {0, 0, 0, 0};   // MAXC == 5: chunk 256 + lane of the row (groups 16 .. 19), transformed after the tile
     if constexpr (X32) {
       auto half_chunk = [&](int n) {
         const u32x4 A = *(const u32x4*)(pl + pl_x + n * 512), B = *(const u32x4*)(pl + pl_x + n * 512 + 2 * PV * 16);
@@ -791,16 +802,25 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
       const uint32_t lo16 = m & 0xFFFFu, hi16 = m >> 16;
       m = lo16 > hi16 ? lo16 : hi16;
     }
-    // ---- groups 16 .. 19 (d36: C = 2304 = 18 groups): one chunk per lane, the transform as butterflies (a second tile
-    // would run its epilogue for 64 lanes to serve 8 - 16 of them); quantized after the tile ----
+    // ---- groups 16 .. 19 (d36: C = 2304 = 18 groups): one chunk per lane (a second tile would run its epilogue for 64 lanes
+    // to serve 8 - 16 of them; only the transform itself takes the tile's route); quantized after the tile ----
     u32x4 y1 = {0, 0, 0, 0};
     uint32_t m1 = 0;
     if (MAXC == 5 && do_slot) {   // wave-uniform (always true unless this row's chunk is parked for its pair)
-      const u32x4 hwa[1] = {hw_slot};
-      float t1[1][8];
-      fwht128_h_n<1>(hwa, t1, 1, lane & 15);
+      // The slot goes through the same matrix-core transform as the tile (its chunks are vector `lane` of a tile image: chunk
+      // lane % 16 of group lane / 16; groups 4 .. 15 still hold the tile's operands, their outputs are not read) and comes
+      // back chunk per lane through the output image: the rotated row is rotate_quant(h) bit for bit in EVERY group.  (As fp32
+      // butterflies groups 16 .. 19 were one fp16 ulp off the matrix cores' on ~1e-6 of the elements.)
+      *(u32x4*)(img + la.in_w) = hw_slot;
+      __builtin_amdgcn_wave_barrier();
+      uint32_t ys[8][2];
+      hadamard128_mfma(img, la.in_r, ha, r.c_h, ys);
+      __builtin_amdgcn_wave_barrier();
 #pragma unroll
-      for (int k = 0; k < 4; ++k) y1[k] = mul2_to_h2(t1[0][2 * k], t1[0][2 * k + 1], r.c_h);
+      for (int c = 0; c < 8; ++c) *(u32x2*)(img + la.out_w + 32 * c) = u32x2{ys[c][0], ys[c][1]};   // (all lanes: a predicate for
+      __builtin_amdgcn_wave_barrier();                                                              //  groups 0 .. 3 measured slower)
+      y1 = *(const u32x4*)(img + la.out_r);
+      __builtin_amdgcn_wave_barrier();
       m1 = vec_absmax16(y1);
     }
     RowScale16 s, s1;

@@ -81,6 +81,23 @@ def main():
     cases["adaln_token_e2m3_x32"] = lambda: rot.adaln_rotate_quant_token(x32(), scale, shift, "e2m3", smooth=s)
     cases["adaln_codes_mx_x32"] = lambda: rot.adaln_rotate_quant_mx(x32(), scale, shift, smooth=s)
     cases["adaln_codes_mx"] = lambda: rot.adaln_rotate_quant_mx(x16()[:B * L].view(B, L, C), scale, shift, smooth=s)
+    # rows of 21 .. 32 groups (one workgroup per row): a padded and a full width, fp16 and fp32 rows
+    for cw in (2688, 4096):
+        scw = (torch.randn(8, 1, cw, device=dev, generator=g) * 0.3).half()
+        sw = torch.rand(cw, device=dev, generator=g) + 0.5
+        for dt, tag in ((torch.float16, ""), (torch.float32, "_x32")):
+            xw = rotating([torch.randn(8, 1024, cw, device=dev, generator=g).to(dt) for _ in range(4)])
+            cases[f"adaln_wide_{cw}{tag}"] = lambda xw=xw, scw=scw, sw=sw: rot.adaln_rotate_quant(xw(), scw, scw, "e2m1", smooth=sw)
+    # rows of 18 groups (VAR-d36, C = 2304: groups 16, 17 are the slot chunk of adaln_mfma_kernel), the model's [44800 x 2304]
+    B5, L5, C5 = 64, 700, 2304
+    sc5 = (torch.randn(B5, 1, C5, device=dev, generator=g) * 0.3).half()
+    s5 = torch.rand(C5, device=dev, generator=g) + 0.5
+    x5h = rotating([torch.randn(B5, L5, C5, device=dev, generator=g).half() for _ in range(3)])
+    x5f = rotating([torch.randn(B5, L5, C5, device=dev, generator=g) for _ in range(3)])
+    cases["adaln_2304"] = lambda: rot.adaln_rotate_quant(x5h(), sc5, sc5, "e2m1", smooth=s5)
+    cases["adaln_2304_x32"] = lambda: rot.adaln_rotate_quant(x5f(), sc5, sc5, "e2m1", smooth=s5)
+    cases["adaln_2304_mx_x32"] = lambda: rot.adaln_rotate_quant_mx(x5f(), sc5, sc5, smooth=s5)
+    cases["adaln_2304_token_fp6_x32"] = lambda: rot.adaln_rotate_quant_token(x5f(), sc5, sc5, "e2m3", smooth=s5, emit="fp6")
     big = None
 
     def fc2():
