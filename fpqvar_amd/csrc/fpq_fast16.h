@@ -858,11 +858,12 @@ __global__ __launch_bounds__(kBlock) void kv16_step_qkn_kernel(KvStepArgs k, KvS
       float nrm = __builtin_sqrtf(ss);
       nrm = nrm < 1e-12f ? 1e-12f : nrm;   // clamp_min(eps) (a NaN stays a NaN)
       const float inv = 1.0f / nrm;
+      const float nrm_r = nrm < __builtin_inff() ? nrm : 0.0f;   // inf / NaN norm: the residual step adds y * 0
       const float hs = z == 2 ? qn.q_scale[c >> 3] : 1.0f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float q = y[j] * inv;
-        q = __builtin_fmaf(__builtin_fmaf(-q, nrm, y[j]), inv, q);
+        q = __builtin_fmaf(__builtin_fmaf(-q, nrm_r, y[j]), inv, q);
         y[j] = z == 2 ? q * hs : q;
       }
     }

@@ -442,9 +442,10 @@ FPQ_NOPK __device__ __forceinline__ float row_sum16(float v) {
     float nrm = __builtin_sqrtf(row_sum16(ss));                                                                     \
     nrm = nrm < 1e-12f ? 1e-12f : nrm;   /* clamp_min(eps) (a NaN stays a NaN) */                                   \
     const float inv = 1.0f / nrm;                                                                                   \
+    const float nrm_r = nrm < __builtin_inff() ? nrm : 0.0f;   /* inf / NaN norm: the residual step adds y * 0 */   \
     _Pragma("unroll") for (int n = 0; n < NT; ++n) {                                                                \
       float q = (yf_)[n] * inv;                                                                                     \
-      q = __builtin_fmaf(__builtin_fmaf(-q, nrm, (yf_)[n]), inv, q);                                                \
+      q = __builtin_fmaf(__builtin_fmaf(-q, nrm_r, (yf_)[n]), inv, q);                                              \
       (yf_)[n] = (part_) == 0 ? q * (s_h_) : q;                                                                     \
     }                                                                                                               \
   } while (0)

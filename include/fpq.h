@@ -597,8 +597,13 @@ int fpq_gemm_fp6_rows_km(const uint8_t* a_image, const void* a_scales, int a_sca
  * the caller), per (token, head of 64 channels):
  *     y = float(y16) + b32                               (the bias AFTER the fp16 rounding)
  *     q_out = half(y_q / max(sqrt(sum y_q^2), 1e-12) * s_h)      k_cache = half(y_k / max(sqrt(sum y_k^2), 1e-12))      v_cache = half(y_v)
- * q_out and k within one fp16 ulp of the same lines in fp32 torch (a real square root and quotient, another summation order), v bit
- * for bit; a zero row gives zeros.  The cache's quantization of these entries at the next step is fpq_kv_cache_step's, unchanged.
+ * With r the same lines in exact arithmetic on y16 and b32, every finite element of q_out and k is within
+ *     0.5 ulp16(|r|) (1 + 2^-12) + 16 * 2^-24 |r|            (ulp16 floored at 2^-24: subnormal results included)
+ * of r - fp32 throughout (a real square root and quotient), one fp16 rounding at the end; the derivation is the docstring of
+ * tests/qknorm_model.py bound(), for sum y^2 < 2^120.  v bit for bit; a zero row gives zeros.  NON-FINITE ROWS follow the
+ * reference's fp32 lines element for element: a NaN anywhere in a head makes its 64 outputs NaN; a head with +-inf and no NaN
+ * gets NaN at the inf elements and (signed) zeros at the others; |r| >= 65520 is +-inf.  The cache's quantization of these entries
+ * at the next step is fpq_kv_cache_step's, unchanged.
  *
  * fpq_gemm_fp4_mx_split_qknorm: fpq_gemm_fp4_mx_split with that epilogue: n_parts == 3 (q, k, v), part_cols % 128 == 0, heads of 64
  * columns (part_cols / 64 of them), bias fp32 [3 * part_cols] 16-byte aligned or NULL, q_head_scale fp32 [part_cols / 64].
@@ -752,7 +757,7 @@ int fpq_gemm_a6w4_gelu_dual_km(const uint8_t* a_image, const void* a_scales, int
  * with the Q / K L2 NORM above in that epilogue (the mixed W4A4 model's mat_qkv has an E3M0 activation in almost every block).
  * Without the norm every written value is bit for bit the one fpq_gemm_a6w4_mx / _km writes at that (token, column); with it, y16
  * is what they write with bias == NULL and q, k, v follow "THE Q / K L2 NORM" (the arithmetic of fpq_gemm_fp4_mx_split_qknorm:
- * q and k within one fp16 ulp of the fp32 lines, v bit for bit).  Row-major and k-major operands, and both tilings, give the same bits.
+ * q and k within that section's bound, its non-finite rule, v bit for bit).  Row-major and k-major operands, and both tilings, give the same bits.
  * w_scale_dtype: FPQ_F32 ONLY, row-major operands included - these forms are not compiled for fp16 weight scales (what
  * fpq_quant_rows_codes_mx writes for an fp32 weight, and what the k-major scale images are, is fp32): FPQ_F16 is FPQ_ERR_DTYPE.
  * split: the FP6 family's rules (fpq_gemm_fp6_rows_split) - n_parts 1..3 (exactly 3 with the norm), part_cols % 128 == 0,
