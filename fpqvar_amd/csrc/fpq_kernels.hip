@@ -648,6 +648,110 @@ __global__ __launch_bounds__(kBlock) void tensor_argmin_kernel(const T* __restri
 }
 
 // ---------------------------------------------------------------------------------
+// The format search's loss (fpq_sqerr_rows_weighted): out[p] = sum_r w[r] sum_c (ref[r, c] - y[p][r, c])^2 for P <= 4
+// planes y[p] against ONE reference, everything in fp32.  Two launches, no memset, no atomics, the same bits every call:
+// (1) the matrices are one stream of 16-byte vectors (cols is a multiple of a vector, so a vector lies in one row);
+//     vector v belongs to lane v % (grid x 256), which walks v, v + grid x 256, ... and carries its (row, column) along
+//     by the host's (step_rows, step_cols) - one 32-bit division per lane, none in the loop.  A lane loads the reference
+//     vector ONCE and every plane's vector against it: (1 + P) matrices move, not 2 P.  Wide and narrow matrices deal
+//     alike: [20 x 5760] fp16 is 14400 vectors on 57 workgroups, [70001 x 8] is 70001 on 274.
+// (2) one workgroup sums the <= kSqerrMaxBlocks partials of every plane (L2-resident) in a fixed order.
+// The additions a term passes through, in order (tests/sqerr_model.py restates them; include/fpq.h carries the bound):
+//     V = 8 (fp16) or 4 (fp32) in its vector (s += d d), then x w[row], n_it = ceil(vectors / (grid x 256)) in the lane
+//     (acc += w s), 6 in the wavefront's butterfly, 3 over the workgroup's four wavefronts; in (2) at most
+//     kSqerrMaxBlocks / 256 = 8 in a lane, 6 in the butterfly, 3 over the wavefronts:   D = V + n_it + 26,
+//     and c = 3 roundings besides them (the difference, the square, the weight).
+// ---------------------------------------------------------------------------------
+constexpr int kSqerrMaxPlanes = 4;
+constexpr int kSqerrMaxBlocks = FPQ_SQERR_WORKSPACE_BYTES / (4 * kSqerrMaxPlanes);
+static_assert(kSqerrMaxBlocks == kMaxBlocks, "the workspace holds one partial per plane and resident workgroup");
+
+struct SqerrDeal {
+  int64_t n_vec;        // rows x cols / V
+  int64_t row_vec;      // cols / V
+  int64_t step_rows;    // (grid x 256) / row_vec
+  int64_t step_cols;    // (grid x 256) % row_vec
+};
+
+__device__ __forceinline__ float lanes_sum64(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);   // both partners add the same pair: every lane ends with the same bits
+  return v;
+}
+
+template <typename T, int P>
+__global__ __launch_bounds__(kBlock) void sqerr_partials_kernel(const u32x4* __restrict__ ref, const u32x4* __restrict__ y,
+                                                               const float* __restrict__ w, float* __restrict__ partials,
+                                                               SqerrDeal d) {
+  __shared__ float sh[P][kBlock / 64];
+  constexpr int V = DT<T>::kVec;
+  const uint32_t v0 = blockIdx.x * kBlock + threadIdx.x;     // < kSqerrMaxBlocks x 256 = 2^19
+  int64_t row = 0, col = v0;
+  if (d.row_vec <= (int64_t)v0) {
+    row = v0 / (uint32_t)d.row_vec;
+    col = v0 - (uint32_t)row * (uint32_t)d.row_vec;
+  }
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  float acc[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) acc[p] = 0.0f;
+  for (int64_t v = v0; v < d.n_vec; v += stride) {
+    const u32x4 r = __builtin_nontemporal_load(ref + v);
+    u32x4 q[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) q[p] = __builtin_nontemporal_load(y + p * d.n_vec + v);
+    const float wr = w[row];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      float s = 0.0f;
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        const float e = DT<T>::get(r, i) - DT<T>::get(q[p], i);
+        s += e * e;
+      }
+      acc[p] += wr * s;
+    }
+    row += d.step_rows;
+    col += d.step_cols;
+    if (col >= d.row_vec) {
+      col -= d.row_vec;
+      ++row;
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const float s = lanes_sum64(acc[p]);
+    if ((threadIdx.x & 63) == 0) sh[p][threadIdx.x >> 6] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < P) {
+    float s = sh[threadIdx.x][0];
+#pragma unroll
+    for (int i = 1; i < kBlock / 64; ++i) s += sh[threadIdx.x][i];
+    partials[threadIdx.x * gridDim.x + blockIdx.x] = s;
+  }
+}
+
+// one workgroup: out[p] = the n_partials partials of plane p, lane i taking i, i + 256, ... in order (none: 0)
+__global__ __launch_bounds__(kBlock) void sqerr_finish_kernel(const float* __restrict__ partials, int n_partials, int planes,
+                                                             float* __restrict__ out) {
+  __shared__ float sh[kSqerrMaxPlanes][kBlock / 64];
+  for (int p = 0; p < planes; ++p) {
+    float s = 0.0f;
+    for (int i = threadIdx.x; i < n_partials; i += kBlock) s += partials[p * n_partials + i];
+    s = lanes_sum64(s);
+    if ((threadIdx.x & 63) == 0) sh[p][threadIdx.x >> 6] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < planes) {
+    float s = sh[threadIdx.x][0];
+#pragma unroll
+    for (int i = 1; i < kBlock / 64; ++i) s += sh[threadIdx.x][i];
+    out[threadIdx.x] = s;
+  }
+}
+
+// ---------------------------------------------------------------------------------
 // Codewords: one workgroup per row (any cols); code = index in the sorted
 // de-duplicated symmetric table.
 // ---------------------------------------------------------------------------------
@@ -1672,6 +1776,35 @@ int fpq_quant_tensor_argmin(const void* x, float* out, float* scale_out, void* w
     if (int rc = launch(absmax_partials_kernel<T>, g1, 0, st, x, n, workspace)) return rc;
     return launch(tensor_argmin_kernel<T>, g2, 0, st, x, out, n, workspace, g1, scale_out, f);
   });
+}
+
+int fpq_sqerr_rows_weighted(const void* ref, const void* y, const float* row_weight, float* out, void* workspace,
+                            int64_t rows, int64_t cols, int planes, int dtype, fpq_stream_t stream) {
+  if (!ref || !y || !row_weight || !out || !workspace || rows < 0 || cols < 0 || planes < 1 || planes > kSqerrMaxPlanes)
+    return FPQ_ERR_ARG;
+  if (!is_f16_or_f32(dtype)) return FPQ_ERR_DTYPE;
+  const int64_t V = dtype == FPQ_F16 ? 8 : 4;
+  if (cols == 0 || cols % V != 0 || rows > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
+  if (rows > 0 && cols / V > INT64_MAX / (rows * kSqerrMaxPlanes)) return FPQ_ERR_SHAPE;   // the planes' vectors are counted in 63 bits
+  if ((((uintptr_t)ref | (uintptr_t)y | (uintptr_t)row_weight) & 15) != 0 || (((uintptr_t)out | (uintptr_t)workspace) & 3) != 0)
+    return FPQ_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  SqerrDeal d;
+  d.row_vec = cols / V;
+  d.n_vec = rows * d.row_vec;
+  const int g1 = rows == 0 ? 0 : grid_for(tiles_of(d.n_vec, 1), kSqerrMaxBlocks);
+  if (g1 > 0) {
+    d.step_rows = (int64_t)g1 * kBlock / d.row_vec;
+    d.step_cols = (int64_t)g1 * kBlock % d.row_vec;
+    const int rc = with_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      return with_int<1, 2, 3, 4>(planes, [&](auto p) {
+        return launch(sqerr_partials_kernel<T, p.value>, g1, 0, st, ref, y, row_weight, workspace, d);
+      });
+    });
+    if (rc != FPQ_OK) return rc;
+  }
+  return launch(sqerr_finish_kernel, 1, 0, st, workspace, g1, planes, out);   // rows == 0: no partials, `planes` zeros
 }
 
 int fpq_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id,

@@ -611,6 +611,40 @@ std::tuple<at::Tensor, c10::optional<at::Tensor>> gelu_quant_rows_dual(const at:
   return {out, h};
 }
 
+// the format search's loss of up to four candidates against one reference: ops.sqerr_rows_weighted
+at::Tensor sqerr_rows_weighted(const at::Tensor& ref, const at::Tensor& y, const at::Tensor& row_weight, c10::optional<at::Tensor> out) {
+  require_gpu(ref, "sqerr_rows_weighted(ref)");
+  require_gpu(y, "sqerr_rows_weighted(y)");
+  require_gpu(row_weight, "sqerr_rows_weighted(row_weight)");
+  TORCH_CHECK((ref.scalar_type() == at::kHalf || ref.scalar_type() == at::kFloat) && y.scalar_type() == ref.scalar_type(),
+              "sqerr_rows_weighted: ref and y must both be float16 or both float32, got ", ref.scalar_type(), " and ", y.scalar_type());
+  TORCH_CHECK(ref.dim() == 2 && (y.dim() == 2 || y.dim() == 3) && y.size(-2) == ref.size(0) && y.size(-1) == ref.size(1),
+              "sqerr_rows_weighted: ref must be [rows, cols] and y [rows, cols] or [P, rows, cols], got ", ref.sizes(), " and ", y.sizes());
+  const int64_t planes = y.dim() == 2 ? 1 : y.size(0), rows = ref.size(0), cols = ref.size(1);
+  TORCH_CHECK(row_weight.scalar_type() == at::kFloat && row_weight.numel() == rows && row_weight.device() == ref.device() &&
+                  y.device() == ref.device(),
+              "sqerr_rows_weighted: row_weight must be float32 [rows] on ref's device, y on it too");
+  TORCH_CHECK(ref.is_contiguous() && y.is_contiguous() && row_weight.is_contiguous(), "sqerr_rows_weighted: ref, y and row_weight must be contiguous");
+  at::Tensor o;
+  if (out.has_value()) {
+    o = *out;
+    TORCH_CHECK(o.scalar_type() == at::kFloat && o.numel() == planes && o.is_contiguous() && o.device() == ref.device(),
+                "sqerr_rows_weighted: out must be a contiguous float32 view of ", planes, " elements on ref's device");
+  } else {
+    o = at::empty({planes}, ref.options().dtype(at::kFloat));
+  }
+  const at::Tensor ws = at::empty({FPQ_SQERR_WORKSPACE_BYTES / 4}, ref.options().dtype(at::kFloat));
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(ref.device());
+  // no rows: empty tensors have a NULL address, the entry point wants pointers - the workspace stands in (never read)
+  const void* pr = rows ? ref.data_ptr() : ws.data_ptr();
+  const void* py = rows ? y.data_ptr() : ws.data_ptr();
+  const void* pw = rows ? row_weight.data_ptr() : ws.data_ptr();
+  check(fpq_sqerr_rows_weighted(pr, py, (const float*)pw, (float*)o.data_ptr(), ws.data_ptr(), rows, cols,
+                                (int)planes, dtype_id(ref.scalar_type(), "sqerr_rows_weighted"), current_stream(ref)),
+        "fpq_sqerr_rows_weighted");
+  return o;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -660,6 +694,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias") = py::none(), py::arg("return_gelu") = false, py::arg("outs") = py::none());
   m.def("gelu_quant_rows_dual", &gelu_quant_rows_dual, py::arg("y"), py::arg("neg_table_id"), py::arg("pos_table_id"), py::arg("cols") = 128,
         py::arg("nan_rule") = true, py::arg("return_gelu") = false);
+  m.def("sqerr_rows_weighted", &sqerr_rows_weighted, py::arg("ref"), py::arg("y"), py::arg("row_weight"), py::arg("out") = py::none());
   m.def("fp6_quant_per_token_contig", &fp6_quant_per_token_contig, py::arg("x"), py::arg("n_bits"), py::arg("table_id"));
   m.def("fp6_quant_int_neg_e2m3_pos_per_token_contig", &fp6_quant_int_neg_e2m3_pos_per_token_contig, py::arg("x"), py::arg("n_bits"));
 }

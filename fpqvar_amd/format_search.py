@@ -8,11 +8,12 @@ all-gather of (loss, w_fmt, a_fmt) per block.
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
 
+from . import ops
 from . import quant_utils as qu
 
 # the reference's candidate sets
@@ -31,10 +32,61 @@ def quantizer(fmt: str) -> Callable[[torch.Tensor], torch.Tensor]:
     return table[fmt]
 
 
+def sample_row_weights(rows_per_sample: Sequence[int], outs: int, device) -> torch.Tensor:
+    """float32 [sum rows]: 1 / (rows_j * outs) repeated rows_j times - the weight of a row of sample j, so that
+    sum_j mean_j(e^2) = sum over rows of (the row's squared error) * (the row's weight).  Built on the host and copied once:
+    the same bits as the vector the batched form of search_layer builds inline on the device."""
+    rows = [int(r) for r in rows_per_sample]
+    per_sample = torch.tensor([1.0 / (r * outs) for r in rows], dtype=torch.float32)
+    return torch.repeat_interleave(per_sample, torch.tensor(rows, dtype=torch.int64)).to(device)
+
+
+def pick_winner(losses_2d_host, formats: Sequence[str]) -> Tuple[str, str]:
+    """(weight format, activation format) of the smallest entry of losses[w index][a index] (a host tensor or nested
+    sequences); ties go to the smaller weight index, then the smaller activation index."""
+    nf = len(formats)
+    keys = [(i, j) for i in range(nf) for j in range(nf)]
+    i, j = min(keys, key=lambda k: (float(losses_2d_host[k[0]][k[1]]), k[0], k[1]))
+    return formats[i], formats[j]
+
+
+_ROW_WEIGHTS: Dict[tuple, torch.Tensor] = {}
+
+
+def _row_weights_on_device(rows: Sequence[int], outs: int, device) -> torch.Tensor:
+    """sample_row_weights on the device without a synchronising copy: the blocks of a search share one calibration set, so
+    the vector is kept per (sample sizes, outs, device); a new one travels from pinned memory, asynchronously."""
+    key = (tuple(rows), outs, str(device))
+    t = _ROW_WEIGHTS.get(key)
+    if t is None:
+        if len(_ROW_WEIGHTS) >= 8:
+            _ROW_WEIGHTS.clear()
+        t = _ROW_WEIGHTS[key] = sample_row_weights(rows, outs, "cpu").pin_memory().to(device, non_blocking=True)
+    return t
+
+
+def _search_layer_fused(xs: Sequence[torch.Tensor], w: torch.Tensor, formats: Sequence[str], quant: Callable[[str], Callable],
+                        losses_out: torch.Tensor) -> None:
+    """The batched arithmetic with the loss in one fused pass per weight format: the activation formats' quantized rows
+    stacked along the row axis, ONE GEMM per weight format, the product kept in w's dtype, and one
+    ops.sqerr_rows_weighted call (the reference product read once for all activation formats) into row i of losses_out."""
+    nf = len(formats)
+    c, outs = w.shape[-1], w.shape[0]
+    rows = [x.numel() // c for x in xs]
+    x_all = torch.cat([x.reshape(-1, c) for x in xs])
+    w_row = _row_weights_on_device(rows, outs, w.device)
+    ref = x_all.to(w.dtype) @ w.t()
+    xq = torch.cat([quant(af)(x_all).to(w.dtype) for af in formats])                 # [nf * rows, C]: one launch per format
+    for i, wf in enumerate(formats):
+        wq = quant(wf)(w).to(w.dtype)
+        y = (xq @ wq.t()).view(nf, x_all.shape[0], outs)
+        ops.sqerr_rows_weighted(ref, y, w_row, out=losses_out[i])
+
+
 @torch.no_grad()
 def search_layer(xs: Sequence[torch.Tensor], w: torch.Tensor, formats: Sequence[str] = FP6_FORMATS,
-                 quant: Callable[[str], Callable] = quantizer, batched: Optional[bool] = None
-                 ) -> Tuple[str, str, Dict[Tuple[str, str], float]]:
+                 quant: Callable[[str], Callable] = quantizer, batched: Optional[bool] = None, fused: bool = False,
+                 losses_out: Optional[torch.Tensor] = None) -> Optional[Tuple[str, str, Dict[Tuple[str, str], float]]]:
     """(best weight format, best activation format, {(w_fmt, a_fmt): summed MSE}).
 
     The reference walks the calibration samples one by one for every (w_fmt, a_fmt) pair: per sample one quantizer call
@@ -50,11 +102,36 @@ def search_layer(xs: Sequence[torch.Tensor], w: torch.Tensor, formats: Sequence[
     an injected `quant` is not assumed to be: batched=None (default) means "batched for the built-in quantizers, the
     loop for anything injected", and a caller who knows his quantizer to be row-local passes batched=True.
     Both forms quantize x in ITS dtype (the reference calls the quantizer on the dumped activation as it is), cast to
-    the weight's dtype for the GEMM, and subtract in float32."""
+    the weight's dtype for the GEMM, and subtract in float32.
+
+    fused=True (batched only, CUDA tensors, an fp16 or fp32 weight, at most four formats): the same operands, but the
+    products stay in w's dtype and the five elementwise passes per pair become one ops.sqerr_rows_weighted pass per WEIGHT
+    format (fpq_sqerr_rows_weighted: fp32 difference, square and sums in a fixed order).  With losses_out (a device
+    [nf, nf] float32 tensor) the losses are left there, nothing is read back and None is returned; without it, one `.cpu()`
+    and the same triple as the other forms.  The default (fused=False) is unchanged."""
     nf = len(formats)
     if batched is None:
         batched = quant is quantizer
-    if not batched:
+    if fused or losses_out is not None:
+        if not fused:
+            raise RuntimeError("search_layer: losses_out is an argument of the fused form (fused=True)")
+        if not batched:
+            raise RuntimeError("search_layer(fused=True) requires the batched form (batched=True, a row-local quantizer)")
+        if not w.is_cuda or not all(x.is_cuda for x in xs):
+            raise RuntimeError("search_layer(fused=True) requires CUDA tensors (the fused loss is a GPU kernel, there is no CPU path)")
+        if w.dtype not in (torch.float16, torch.float32):
+            raise RuntimeError(f"search_layer(fused=True) requires a float16 or float32 weight, got {w.dtype}")
+        if not 1 <= nf <= 4:
+            raise RuntimeError(f"search_layer(fused=True) takes 1 to 4 formats (the planes of one fused pass), got {nf}")
+        out = losses_out if losses_out is not None else torch.empty(nf, nf, dtype=torch.float32, device=w.device)
+        if out.shape != (nf, nf) or out.dtype != torch.float32 or out.device != w.device or not out.is_contiguous():
+            raise RuntimeError(f"search_layer(fused=True): losses_out must be a contiguous float32 [{nf}, {nf}] tensor on the weight's device")
+        _search_layer_fused(xs, w, formats, quant, out)
+        if losses_out is not None:
+            return None
+        host = out.cpu()                                                               # the layer's one synchronisation
+        losses = {(wf, af): float(host[i, j]) for i, wf in enumerate(formats) for j, af in enumerate(formats)}
+    elif not batched:
         losses: Dict[Tuple[str, str], float] = {}
         refs = [x.to(w.dtype) @ w.t() for x in xs]
         for wf in formats:
@@ -83,22 +160,28 @@ def search_layer(xs: Sequence[torch.Tensor], w: torch.Tensor, formats: Sequence[
                 out[i, j] = torch.dot((d * d).sum(dim=1), w_row)
         host = out.cpu()                                                               # the layer's one synchronisation
         losses = {(wf, af): float(host[i, j]) for i, wf in enumerate(formats) for j, af in enumerate(formats)}
-    best = min(losses, key=lambda k: (losses[k], formats.index(k[0]), formats.index(k[1])))
-    return best[0], best[1], losses
+    wf, af = pick_winner([[losses[(a, b)] for b in formats] for a in formats], formats)
+    return wf, af, losses
 
 
-def search_blocks_sharded(n_blocks: int, evaluate: Callable[[int], Tuple[str, str, float]],
-                          formats: Sequence[str] = FP6_FORMATS, group=None) -> List[Tuple[str, str, float]]:
-    """Block b is evaluated on rank b % world; every rank gets all results.
-    `evaluate(b)` returns (w_fmt, a_fmt, loss).  The collective is one all-gather of
-    n_blocks x (loss, w index, a index) float32 triples."""
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    per_rank = (n_blocks + world - 1) // world
-    buf = torch.full((per_rank, 3), -1.0, dtype=torch.float32)
-    for slot, b in enumerate(range(rank, n_blocks, world)):
-        wf, af, loss = evaluate(b)
-        buf[slot] = torch.tensor([loss, formats.index(wf), formats.index(af)], dtype=torch.float32)
+@torch.no_grad()
+def search_layers_fused(layers: Iterable[Tuple[Sequence[torch.Tensor], torch.Tensor]], formats: Sequence[str] = FP6_FORMATS,
+                        quant: Callable[[str], Callable] = quantizer) -> torch.Tensor:
+    """search_layer(fused=True) over an iterable of (xs, w): float32 [L, nf, nf] on the device, nothing read back and no
+    synchronisation inside - the caller's one `.cpu()` serves every layer."""
+    nf = len(formats)
+    tables = []
+    for xs, w in layers:
+        t = torch.empty(nf, nf, dtype=torch.float32, device=w.device)
+        search_layer(xs, w, formats, quant, batched=True, fused=True, losses_out=t)
+        tables.append(t)
+    if not tables:
+        return torch.empty(0, nf, nf, dtype=torch.float32)
+    return torch.stack(tables)
+
+
+def _gather_triples(buf: torch.Tensor, n_blocks: int, formats: Sequence[str], group, world: int) -> List[Tuple[str, str, float]]:
+    """This rank's (loss, w index, a index) rows -> every block's (w_fmt, a_fmt, loss) on every rank: one all-gather."""
     if world == 1:
         gathered = [buf]
     else:
@@ -113,3 +196,35 @@ def search_blocks_sharded(n_blocks: int, evaluate: Callable[[int], Tuple[str, st
             loss, wi, ai = gathered[r][slot].tolist()
             out[b] = (formats[int(wi)], formats[int(ai)], loss)
     return out  # type: ignore[return-value]
+
+
+def search_blocks_sharded(n_blocks: int, evaluate: Callable[[int], Tuple[str, str, float]],
+                          formats: Sequence[str] = FP6_FORMATS, group=None) -> List[Tuple[str, str, float]]:
+    """Block b is evaluated on rank b % world; every rank gets all results.
+    `evaluate(b)` returns (w_fmt, a_fmt, loss).  The collective is one all-gather of
+    n_blocks x (loss, w index, a index) float32 triples."""
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    per_rank = (n_blocks + world - 1) // world
+    buf = torch.full((per_rank, 3), -1.0, dtype=torch.float32)
+    for slot, b in enumerate(range(rank, n_blocks, world)):
+        wf, af, loss = evaluate(b)
+        buf[slot] = torch.tensor([loss, formats.index(wf), formats.index(af)], dtype=torch.float32)
+    return _gather_triples(buf, n_blocks, formats, group, world)
+
+
+def search_blocks_sharded_fused(n_blocks: int, layer_of: Callable[[int], Tuple[Sequence[torch.Tensor], torch.Tensor]],
+                                formats: Sequence[str] = FP6_FORMATS, group=None) -> List[Tuple[str, str, float]]:
+    """search_blocks_sharded on the fused form: `layer_of(b)` returns block b's (xs, w); this rank's blocks (b % world ==
+    rank) go through search_layers_fused, their losses are read back ONCE, the winners are picked on the host, and the
+    same all-gather of triples follows."""
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    per_rank = (n_blocks + world - 1) // world
+    buf = torch.full((per_rank, 3), -1.0, dtype=torch.float32)
+    host = search_layers_fused((layer_of(b) for b in range(rank, n_blocks, world)), formats).cpu()
+    for slot in range(host.shape[0]):
+        wf, af = pick_winner(host[slot], formats)
+        i, j = formats.index(wf), formats.index(af)
+        buf[slot] = torch.tensor([float(host[slot, i, j]), i, j], dtype=torch.float32)
+    return _gather_triples(buf, n_blocks, formats, group, world)

@@ -340,6 +340,38 @@ def quant_tensor_argmin(x: torch.Tensor, table: str) -> Tuple[torch.Tensor, torc
     return out, scale.reshape(())
 
 
+def sqerr_rows_weighted(ref: torch.Tensor, y: torch.Tensor, row_weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[p] = sum_r row_weight[r] * sum_c (ref[r, c] - y[p][r, c])^2 in fp32 (fpq_sqerr_rows_weighted): the format search's
+    loss of up to four candidates against one reference, ref read once.  ref [rows, cols] and y [rows, cols] or [P, rows, cols]
+    float16 or float32 (the same), contiguous; row_weight float32 [rows], finite and positive; out: a contiguous float32 view
+    of P elements (a row of a loss table), allocated when None.  Deterministic; no synchronisation."""
+    if _native is not None:
+        return _native.sqerr_rows_weighted(ref, y, row_weight, out)
+    for t, what in ((ref, "ref"), (y, "y"), (row_weight, "row_weight")):
+        require_gpu(t, f"sqerr_rows_weighted({what})")
+    if ref.dtype not in (torch.float16, torch.float32) or y.dtype != ref.dtype:
+        raise RuntimeError(f"sqerr_rows_weighted: ref and y must both be float16 or both float32, got {ref.dtype} and {y.dtype}")
+    if ref.dim() != 2 or y.dim() not in (2, 3) or tuple(y.shape[-2:]) != tuple(ref.shape):
+        raise RuntimeError(f"sqerr_rows_weighted: ref must be [rows, cols] and y [rows, cols] or [P, rows, cols], got {tuple(ref.shape)} and {tuple(y.shape)}")
+    planes = 1 if y.dim() == 2 else y.shape[0]
+    rows, cols = ref.shape
+    if row_weight.dtype != torch.float32 or row_weight.numel() != rows or row_weight.device != ref.device or y.device != ref.device:
+        raise RuntimeError("sqerr_rows_weighted: row_weight must be float32 [rows] on ref's device, y on it too")
+    if not (ref.is_contiguous() and y.is_contiguous() and row_weight.is_contiguous()):
+        raise RuntimeError("sqerr_rows_weighted: ref, y and row_weight must be contiguous")
+    if out is None:
+        out = torch.empty(planes, dtype=torch.float32, device=ref.device)
+    elif out.dtype != torch.float32 or out.numel() != planes or not out.is_contiguous() or out.device != ref.device:
+        raise RuntimeError(f"sqerr_rows_weighted: out must be a contiguous float32 view of {planes} elements on ref's device")
+    ws = torch.empty(_lib.SQERR_WORKSPACE_BYTES // 4, dtype=torch.float32, device=ref.device)
+    # no rows: torch gives empty tensors a NULL address, the entry point wants pointers - the workspace stands in (never read)
+    pr, py, pw = (ref.data_ptr(), y.data_ptr(), row_weight.data_ptr()) if rows else (ws.data_ptr(),) * 3
+    with device_guard(ref.device):
+        check(lib().fpq_sqerr_rows_weighted(pr, py, pw, out.data_ptr(), ws.data_ptr(), rows, cols,
+                                            planes, dtype_id(ref.dtype), stream_ptr(ref.device)), "fpq_sqerr_rows_weighted")
+    return out
+
+
 def absmax(x: torch.Tensor) -> torch.Tensor:
     """0-dim max|x| in x's dtype (NaN-propagating)."""
     require_gpu(x, "absmax")

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FPQ_VERSION 135 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
+#define FPQ_VERSION 136 /* 0.1.2: + fpq_quant_tensor_argmin, fpq_quant_rows_segments, fpq_quant_rows_multi (round 2);
                            0.1.3: + fpq_quant_rows_codes_segments, fpq_dequant_rows_codes_segments (round 3);
                            123: + fpq_build_tag (round 4);
                            124: + fpq_set_option, fpq_get_option, fpq_option_name, fpq_gemm_fp4_gelu_dual, fpq_gelu_quant_rows_dual (round 5);
@@ -43,7 +43,8 @@ extern "C" {
                            133: + the A6W4 path on k-major images: fpq_a6w4_quant_rows_codes_km, fpq_gemm_a6w4_mx_km, fpq_gemm_a6w4_gelu_dual_km;
                            134: + the split output and the q / k norm in the A6W4 GEMM: fpq_gemm_a6w4_mx_split, fpq_gemm_a6w4_mx_split_qknorm;
                            135: + the rotate and adaLN producers emitting the A6W4 GEMM's activation operands: fpq_a6w4_rotate_quant_rows_codes,
-                                fpq_a6w4_adaln_rotate_quant_rows_codes */
+                                fpq_a6w4_adaln_rotate_quant_rows_codes;
+                           136: + the format search's loss in one pass: fpq_sqerr_rows_weighted */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -382,6 +383,37 @@ int fpq_quant_rows_multi(const fpq_segment_t* segments_host, int n_segments, int
 #define FPQ_TENSOR_WORKSPACE_BYTES 8192
 int fpq_quant_tensor_argmin(const void* x, float* out, float* scale_out, void* workspace, int64_t n, int table_id,
                             int in_dtype, fpq_stream_t stream);
+
+/* The loss of the per-layer format search (search/search_fp6_format.py:589-608 and its FP4 twin: per sample
+ * mean((x_j W^T - q_a(x_j) q_w(W)^T)^2), summed over the samples) for up to four candidates against one reference:
+ *   out[p] = sum_r row_weight[r] * sum_c (f32(ref[r, c]) - f32(y[p][r, c]))^2          p < planes
+ * ref: [rows, cols]; y: [planes, rows, cols] contiguous; both `dtype` (FPQ_F16 or FPQ_F32); row_weight: [rows] float32,
+ * FINITE AND POSITIVE (1 / (rows_j * cols) of the row's sample); out: `planes` float32, overwritten, not accumulated;
+ * 1 <= planes <= 4.  A workgroup reads its part of ref once and every plane against it: 1 + planes matrices move.
+ * The subtraction, the square and every sum are fp32; nothing is rounded to fp16.
+ * workspace: FPQ_SQERR_WORKSPACE_BYTES of device scratch (one partial per plane and workgroup, the grid is capped at
+ * FPQ_SQERR_WORKSPACE_BYTES / 16 workgroups).  No memset, no atomics: the same inputs give the same bits on every call
+ * whatever the workspace held.  Two launches (partials, then one workgroup sums them in a fixed order); no host
+ * synchronisation, allocation or copy - legal inside a stream capture.
+ * Checked before anything is enqueued, in this order:
+ *   a NULL pointer, rows < 0, cols < 0, planes outside 1 .. 4                                     FPQ_ERR_ARG
+ *   dtype other than FPQ_F16 / FPQ_F32                                                           FPQ_ERR_DTYPE
+ *   cols == 0, cols % 8 != 0 (F16) or cols % 4 != 0 (F32), rows > 2^31 - 1
+ *     (or planes x rows x cols beyond 63 bits)                                                   FPQ_ERR_SHAPE
+ *   ref, y or row_weight not 16-byte aligned (out, workspace: 4-byte)                             FPQ_ERR_ARG
+ * rows == 0 stores `planes` zeros (one launch) and succeeds.
+ * Accuracy: every term is non-negative and every weight positive, so against the exact sum S of the stored inputs
+ *   |out[p] - S| <= (D + c) 2^-24 S,    D = V + n_it + 26,  c = 3
+ * V = 8 (F16) / 4 (F32) additions inside a 16-byte vector, n_it = ceil(n_vec / (min(ceil(n_vec / 256), 2048) * 256))
+ * additions in a lane (n_vec = rows cols / V), 6 + 3 in the workgroup, 8 + 6 + 3 over the partials; c = the roundings of the
+ * difference, the square and the weight.  [13600 x 5760] F16: n_it = 19, (D + c) 2^-24 = 3.4e-6.  F32 inputs whose squares or
+ * weighted squares go subnormal add at most 2^-149 per element and per vector (F16 inputs cannot: the smallest non-zero
+ * difference squared is 2^-48).
+ * Non-finite inputs behave as the fp32 expression does: out[p] is NaN if any difference of plane p is NaN (a NaN input, or
+ * inf - inf), otherwise +inf if any difference (or an fp32 square) is infinite; the other planes are not touched by it. */
+#define FPQ_SQERR_WORKSPACE_BYTES 32768
+int fpq_sqerr_rows_weighted(const void* ref, const void* y, const float* row_weight, float* out, void* workspace,
+                            int64_t rows, int64_t cols, int planes, int dtype, fpq_stream_t stream);
 
 /* Codeword output (build-defined; the reference's kernel never emits codes,
  * quant_kernel.cu:18,49).  code = index into the sorted, de-duplicated table
