@@ -22,7 +22,7 @@
   X(FPQ_ADALN_NO_PAIR2, 1)  /* adaLN producer at C = 1024: one row per tile */                                         \
   X(FPQ_ADALN_NO_TIGHT, 1)                                                                                             \
   X(FPQ_NO_WAVE_ROWS, 1)    /* long fp16 rows: one workgroup per row even when a wavefront would hold it */            \
-  X(FPQ_GEMM_CFG, 0)        /* FP4 GEMM tiling: 0..2 register-staged, 10 / 20 / 30 LDS-DMA 256x128 / 128x128 / 64x128 */ \
+  X(FPQ_GEMM_CFG, 0)        /* FP4 GEMM tiling: 0..2 register-staged, 10 / 20 / 30 LDS-DMA 256x128 / 128x128 / 64x128, 40 64x128 deep ring */ \
   X(FPQ_GEMM6_CFG, 0)       /* FP6 GEMM tiling: 0 128x128, 1 256x128 */                                                 \
   X(FPQ_GEMM8_CFG, 0)       /* FP8 GEMM tiling: 0 128x128, 1 256x128 */                                                 \
   X(FPQ_ROT_WGS, 0)         /* rotate_quant: workgroups per generation */                                              \

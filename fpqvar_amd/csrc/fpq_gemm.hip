@@ -73,18 +73,23 @@ int gemm_qknorm(const fpq_gemm_split_t* split, const float* bias, const float* q
 }
 
 // The tiling of the per-group LDS-DMA kernels (gemm_fp4_glds_kernel, gemm_a6w4_kernel, their fc1 forms): 10 / 20 / 30 = 256 x 128,
-// 128 x 128, 64 x 128 tiles.
+// 128 x 128, 64 x 128 tiles behind a two-stage ring.
 // Default: 128 x 128 tiles (three workgroups per CU); 256 x 128 tiles (two per CU) from 4000 of them
 // on (round 4: 2 - 5 % faster at [65536 x 1920] x {1920, 5760, 7680} and from 16 900 tokens on for the wide Linears, 3 - 5 %
 // slower between 1000 and 4000 tiles) while two of them fit a CU's 160 KB of LDS (the scale tiles grow with K: from K = 3840 on
 // only one would, and the smaller tile is 15 % faster there - tools/gemm_k_sweep.py); 64 x 128 tiles while the 128 x 128 ones
 // would fill less than half of the chip's 768 slots (the first scale steps of a generation: 8.4 against 11.4 us at 100 tokens;
 // tools/gemm_small_steps.py).
+// 40 = gemm_fp4_ring_kernel, the 64 x 128 tile behind a deep stage ring (fpq_gemm_fp4.h): the FP4 GEMM has it (have_ring), the
+// A6W4 GEMM does not - for it 40 means "not set".  The default NEVER chooses it: measured against 30 and the default at every
+// row count of d30's and d36-512's scale steps (K = 1920, 2304; k-major, both orders, against a 30-vs-30 spread of 0.2 us) it
+// wins at no tile count and no outs - 0.2 us slower while a grid has at most one tile per CU, 1.2 x beyond
+// (profiles/gemm_fp4_ring_small_steps.txt) - so there is no rule for it beside the tile-count rule below.
 // FPQ_GEMM_CFG (experiments, tests) forces one of the tilings the caller has; have_256: whether it has the 256 x 128 one at all,
 // big_fits_twice: whether two of those tiles fit a CU's LDS at this K.
-int gemm_glds_tiling(int64_t tokens, int64_t outs, bool have_256, bool big_fits_twice) {
+int gemm_glds_tiling(int64_t tokens, int64_t outs, bool have_256, bool big_fits_twice, bool have_ring = false) {
   const int want = fpq_opt(OPT_FPQ_GEMM_CFG, 0);
-  if ((want == 10 && have_256) || want == 20 || want == 30) return want;
+  if ((want == 10 && have_256) || want == 20 || want == 30 || (want == 40 && have_ring)) return want;
   const int64_t big_tiles = ((tokens + 255) / 256) * ((outs + 127) / 128);
   const int64_t mid_tiles = ((tokens + 127) / 128) * ((outs + 127) / 128);
   return mid_tiles <= 384 ? 30 : (have_256 && big_tiles >= 4000 && big_fits_twice) ? 10 : 20;
@@ -132,6 +137,27 @@ int launch_fp4_glds(const GemmCall& c, int w_scale_dtype, size_t lds, XE xe) {
   return with_dtype(w_scale_dtype, [&](auto tw) {
     return gemm_launch(gemm_fp4_glds_kernel<decltype(tw), MT, 4, XE>, GemmGldsCfg<MT, 4>::BM, GemmGldsCfg<MT, 4>::BN, 256, lds, c, xe);
   });
+}
+// the FP4 deep-ring kernel (64 x 128 tiles, FPQ_GEMM_CFG 40) with epilogue XE; lds: GemmRingCfg's figure for that epilogue
+template <typename XE>
+int launch_fp4_ring(const GemmCall& c, int w_scale_dtype, size_t lds, XE xe) {
+  if (lds > 160 * 1024) return kTileDoesNotFit;
+  return with_dtype(w_scale_dtype, [&](auto tw) {
+    return gemm_launch(gemm_fp4_ring_kernel<decltype(tw), XE>, GemmRingCfg::BM, GemmRingCfg::BN, 256, lds, c, xe);
+  });
+}
+// THE tiling of an FP4 LDS-DMA call - the Linear (fc1_shift < 0; plain, split or q / k norm) or the fc1 form (fc1_shift = the dual
+// quantizer's table shift: its bucket table lies behind the scale tiles) - for the launch and for fpq_gemm_fp4_tiling alike:
+// gemm_glds_tiling's choice, then the fall-through where that tiling's LDS image does not fit a CU's 160 KiB at this K (the ring
+// to the 64 x 128 tile, that and the 256 x 128 one to 128 x 128).  -> 10 / 20 / 30 / 40, or kTileDoesNotFit when nothing fits.
+int gemm_fp4_plan(int64_t tokens, int64_t outs, int G, int fc1_shift) {
+  const size_t table = fc1_shift < 0 ? 0 : (size_t)2 << (16 - fc1_shift), cap = 160 * 1024;
+  int cfg = gemm_glds_tiling(tokens, outs, true, 2 * (GemmGldsCfg<8, 4>::lds(G) + table) <= cap, true);
+  if (cfg == 40 && GemmRingCfg::lds(G) + table > cap) cfg = 30;
+  if (cfg == 30 && GemmGldsCfg<2, 4>::lds(G) + table > cap) cfg = 20;
+  if (cfg == 10 && GemmGldsCfg<8, 4>::lds(G) + table > cap) cfg = 20;
+  if (cfg == 20 && GemmGldsCfg<4, 4>::lds(G) + table > cap) return kTileDoesNotFit;
+  return cfg;
 }
 // the register-staged FP4 kernel
 template <int MT, int NT, int WR, int WC>
@@ -393,16 +419,19 @@ static int gemm_fp4_mx_impl(const uint8_t* a_codes, const void* a_scales, const 
   if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
   if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out) & 15) != 0) return FPQ_ERR_ARG;
   const int G = (int)(k / 128);
-  // The LDS-DMA kernel in the tiling gemm_glds_tiling chooses; the register-staged kernel when the LDS image does not fit (very
-  // long K), when the bias is not 8-byte aligned (the LDS-DMA kernel reads it four outputs at a time), or when FPQ_GEMM_CFG
-  // names one of its tilings (0..2; experiments, tests) - but it reads row-major codes and writes one tensor.
-  int cfg = gemm_glds_tiling(tokens, outs, true, 2 * GemmGldsCfg<8, 4>::lds(G) <= 160 * 1024);
+  // The LDS-DMA kernel in the tiling gemm_fp4_plan chooses; the register-staged kernel when no LDS image fits (very long K),
+  // when the bias is not 8-byte aligned (the LDS-DMA kernels read it four outputs at a time), or when FPQ_GEMM_CFG names
+  // anything but an LDS-DMA tiling (0..2 are the register-staged kernel's own; experiments, tests) - but it reads row-major codes
+  // and writes one tensor.
+  int cfg = gemm_fp4_plan(tokens, outs, G, -1);
+  if (cfg == kTileDoesNotFit) cfg = 0;
   if (km || split) {
     if (((uintptr_t)bias & 7) != 0 || outs + 63 > 0x7FFFFFFF) return FPQ_ERR_ARG;
   } else if (((uintptr_t)bias & 7) != 0) {
     cfg = 0;
   } else if (fpq_opt_set(OPT_FPQ_GEMM_CFG)) {
-    cfg = fpq_opt(OPT_FPQ_GEMM_CFG, 0);
+    const int want = fpq_opt(OPT_FPQ_GEMM_CFG, 0);
+    if (want != 10 && want != 20 && want != 30 && want != 40) cfg = want;   // (a forced LDS-DMA tiling is in the plan already)
   }
   const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
   auto glds = [&](auto mt) {
@@ -410,11 +439,10 @@ static int gemm_fp4_mx_impl(const uint8_t* a_codes, const void* a_scales, const 
     const size_t lds = GemmGldsCfg<MT, 4>::lds(G);
     return qkn ? launch_fp4_glds<MT>(c, w_scale_dtype, lds, *qkn) : launch_fp4_glds<MT>(c, w_scale_dtype, lds, GemmNoFc1{});
   };
-  int rc = kTileDoesNotFit;
-  if (cfg == 30) rc = glds(Int<2>{});   // 64 x 128 tiles
-  if (cfg == 10) rc = glds(Int<8>{});
-  if (rc == kTileDoesNotFit && (cfg == 10 || cfg == 20 || cfg == 30)) rc = glds(Int<4>{});   // (the larger tile's LDS image may not fit where the smaller one's does)
-  if (rc != kTileDoesNotFit) return rc;
+  if (cfg == 40) return qkn ? launch_fp4_ring(c, w_scale_dtype, GemmRingCfg::lds(G), *qkn) : launch_fp4_ring(c, w_scale_dtype, GemmRingCfg::lds(G), GemmNoFc1{});
+  if (cfg == 30) return glds(Int<2>{});   // 64 x 128 tiles
+  if (cfg == 10) return glds(Int<8>{});
+  if (cfg == 20) return glds(Int<4>{});
   if (km || split) return FPQ_ERR_SHAPE;   // K too long for the LDS-DMA kernel's scale tiles
   if (cfg == 1) return launch_fp4_staged<2, 4, 4, 2>(c, w_scale_dtype);
   if (cfg == 2) return launch_fp4_staged<4, 4, 2, 4>(c, w_scale_dtype);
@@ -550,16 +578,17 @@ static int gemm_fp4_gelu_dual_impl(const uint8_t* a_codes, const void* a_scales,
   const int G = (int)(k / 128);
   GemmEpi epi{nullptr, nullptr, 1, km ? (int)outs : 0};   // (outs % 128 == 0: the weight image has exactly outs rows)
   if (km && (w_scale_dtype != FPQ_F32 || tokens >= (1ll << 28) || (((uintptr_t)a_scales | (uintptr_t)w_scales) & 15) != 0)) return FPQ_ERR_ARG;
-  const int cfg = gemm_glds_tiling(tokens, outs, true, 2 * GemmGldsCfg<8, 4>::lds_fc1(G, xe.a.shift) <= 160 * 1024);
+  const int cfg = gemm_fp4_plan(tokens, outs, G, xe.a.shift);
   const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
   auto glds = [&](auto mt) {
     constexpr int MT = decltype(mt)::value;
     return launch_fp4_glds<MT>(c, w_scale_dtype, GemmGldsCfg<MT, 4>::lds_fc1(G, xe.a.shift), xe);
   };
   int rc = kTileDoesNotFit;
+  if (cfg == 40) rc = launch_fp4_ring(c, w_scale_dtype, GemmRingCfg::lds_fc1(G, xe.a.shift), xe);
   if (cfg == 30) rc = glds(Int<2>{});
   if (cfg == 10) rc = glds(Int<8>{});
-  if (rc == kTileDoesNotFit) rc = glds(Int<4>{});
+  if (cfg == 20) rc = glds(Int<4>{});
   if (rc == kTileDoesNotFit) return FPQ_ERR_SHAPE;   // K too long for the LDS-DMA kernel's scale tiles
   if (rc) return rc;
   return nan_flag ? fpq_internal_zero_if_flag(out, tokens * outs * 2, nan_flag, stream) : FPQ_OK;
@@ -568,6 +597,21 @@ int fpq_gemm_fp4_gelu_dual(const uint8_t* a_codes, const void* a_scales, const u
                            int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs,
                            int64_t k, void* nan_flag, fpq_stream_t stream) {
   return gemm_fp4_gelu_dual_impl(a_codes, a_scales, w_codes, w_scales, w_scale_dtype, bias, out, gelu_out, tokens, outs, k, nan_flag, false, stream);
+}
+// which tiling a call would run (include/fpq.h): the entry points' shape checks, then gemm_fp4_plan - host arithmetic only
+int fpq_gemm_fp4_tiling(int64_t tokens, int64_t outs, int64_t k, int form) {
+  if (tokens < 0 || outs < 0 || k < 0 || (form != 0 && form != 1)) return FPQ_ERR_ARG;
+  if (k % 128 != 0 || k > 128 * 64 || outs % (form == 1 ? 128 : 8) != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
+  if (tokens == 0 || outs == 0) return FPQ_OK;   // nothing is launched
+  if (k == 0) return FPQ_ERR_ARG;
+  int shift = -1;
+  if (form == 1) {
+    const Lut16Host& dual = lut16_host(FPQ_E1M2_NEG, FPQ_E2M1_POS);
+    if (!dual.tab_valid) return FPQ_ERR_TABLE;
+    shift = dual.args.shift;
+  }
+  const int cfg = gemm_fp4_plan(tokens, outs, (int)(k / 128), shift);
+  return cfg == kTileDoesNotFit ? FPQ_ERR_SHAPE : cfg;
 }
 int fpq_gemm_fp4_gelu_dual_km(const uint8_t* a_image, const void* a_scales, const uint8_t* w_image, const void* w_scales,
                               int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs,

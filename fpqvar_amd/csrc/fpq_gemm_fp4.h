@@ -822,6 +822,291 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4
 #undef FPQ_GLDS_ISSUE
 #undef FPQ_GLDS_WAIT
 
+// ---------------------------------------------------------------------------------------------------
+// The deep-ring small-M form of gemm_fp4_glds_kernel<.., 2, 4> (FPQ_GEMM_CFG 40): the same 64 x 128 tile, LDS block image, dealt
+// weight rows, XCD tile order, clamped lane offsets, per-group arithmetic (t = d * sa; acc = fma(t, sw, acc), g ascending) and
+// register epilogues - every output is bit-equal to FPQ_GEMM_CFG 30.  What differs is the staging.  The loop above is
+// `wait vmcnt(0) -> barrier -> request group g + 1 -> multiply group g`: one group in flight, a tile pays G dependent trips to
+// memory, and at the first scale steps (30 - 240 workgroups on 256 CUs) no second workgroup hides them.  Here:
+//   * a ring of S = FPQ_GEMM_RING_STAGES stage buffers, group g in buffer g % S;
+//   * the first min(S - 1, G) groups requested up front, behind everything else the prologue puts into the memory queue (the
+//     k-major scale pieces, the row-major scale loads and their visible wait, the bias) - the queue retires in order, so the
+//     wait for group 0 covers all of it, and a visible wait in front of the ring cannot drain it;
+//   * iteration g: `wait -> barrier -> request group g + S - 1 -> multiply group g`.  The request goes to buffer (g - 1) % S, last
+//     read in iteration g - 1, behind the barrier every reader of it has passed (write after read); buffer g % S is read behind
+//     the wait of the wavefronts that requested it and that same barrier (read after write);
+//   * the wait is COUNTED: in front of it groups g .. min(G, g + S - 1) - 1 are outstanding, so min(G - 1 - g, S - 2) groups may
+//     stay in flight - s_waitcnt vmcnt(PIECES * (S - 2)) in the steady loop (which always requests: g + S - 1 < G), and PIECES *
+//     (G - 1 - g), ..., PIECES, 0 over the last S - 1 groups, which request nothing (no piece of a group >= G is ever issued: a
+//     k-major plane past G is past the allocation) - a uniform switch in a loop of its own (FPQ_RING_TAIL_WAIT).
+// A visible load younger than the ring (none is left in the loops) could only make a wait stricter, never laxer.
+// The fc1 tail's scratch stays `(G & 1) * STAGE`: S is even, so buffer G & 1 is not the last group's, (G - 1) % S - the parities
+// differ; every request has landed (the last wait is vmcnt(0)) and every other buffer's readers are behind the last barrier.
+// LDS: S stages + the scale tiles (+ the bucket table): 12 S + 12 KiB at K = 1920, 12 S + 48 KiB at K = 8192 - with S = 8 one
+// workgroup per CU (108 / 144 KiB), with S = 4 two (60 / 96 KiB).
+// MEASURED (profiles/gemm_fp4_ring_small_steps.txt): it pays nowhere at the models' shapes.  With at most one tile per CU it is
+// 0.2 / 0.4 / 0.7 us SLOWER than cfg 30's 7.8 - 8.1 us at K = 1920 with S = 4 / 6 / 8, past that 1.2 x (S = 4) to 2 x (S = 6, 8:
+// one workgroup per CU) slower.  The flat 8 us are a 3.4 us floor (K = 128) + 0.33 us per group, and that step does not move with
+// the depth of the ring: it is the lone wavefront's own chain per group (three LDS-DMA issues, fragment reads, eight MFMAs with
+// their scale stage, the barrier), not a trip to memory.  S = 4 is the least slow of the three and is what ships; the default
+// tiling never chooses 40 (gemm_glds_tiling, fpq_gemm.hip).
+#ifndef FPQ_GEMM_RING_STAGES
+#define FPQ_GEMM_RING_STAGES 4   // {4, 6, 8} measured: profiles/gemm_fp4_ring_small_steps.txt
+#endif
+template <int N>
+FPQ_NOPK __device__ __forceinline__ void glds_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+template <typename Tsw, typename XE = GemmNoFc1>
+__global__ __launch_bounds__(256, 3) FPQ_NOPK void gemm_fp4_ring_kernel(const uint8_t* __restrict__ A,
+                                                              const _Float16* __restrict__ sa,
+                                                              const uint8_t* __restrict__ W, const Tsw* __restrict__ sw,
+                                                              const _Float16* __restrict__ bias,
+                                                              _Float16* out, int T, int O, int C, GemmEpi epi, XE xe) {
+  constexpr bool FC1 = __is_same(XE, GemmFc1), QKN = __is_same(XE, GemmQkNorm);
+  constexpr int S = FPQ_GEMM_RING_STAGES, MT = 2, NT = 4;
+  constexpr int WR = 2, WC = 2, BM = 16 * MT * WR, BN = 16 * NT * WC, NTHR = 256;
+  constexpr int ABLK = BM / 16, BBLK = BN / 16, NBLK = ABLK + BBLK, STAGE = NBLK * 1024;
+  constexpr int PIECES = NBLK / 4;   // LDS-DMA pieces per wavefront and stage
+  static_assert(S >= 4 && S % 2 == 0, "an even ring: the fc1 tail's scratch, buffer G & 1, is never the last group's");
+  static_assert(PIECES * (S - 2) <= 63, "vmcnt is a 6-bit counter");
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int G = C >> 7, row_bytes = C >> 1;
+  float* lsa = (float*)(smem + S * STAGE);   // [G][BM]
+  const int Gp = (G + 3) & ~3;
+  float* lsw = lsa + Gp * BM;                // [G][BN]
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int n_col = (O + BN - 1) / BN, n_row = (T + BM - 1) / BM;
+  const int cpx = (n_col + 7) >> 3;
+  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
+  const int col_blk = xcd * cpx + local % cpx, row_blk = local / cpx;
+  if (col_blk >= n_col || row_blk >= n_row) return;   // uniform over the workgroup
+  const int t0 = row_blk * BM, o0 = col_blk * BN;
+
+  // LDS-DMA sources: gemm_fp4_glds_kernel's (uniform base per operand, 32-bit lane offset clamped to the tensor's last row)
+  const bool km = epi.km_w_rows != 0;
+  const int row_stride = km ? 64 : row_bytes;
+  const int64_t a_step = km ? (int64_t)T * 64 : 64, w_step = km ? (int64_t)epi.km_w_rows * 64 : 64;
+  const uint8_t* const gbase[2] = {A + (int64_t)t0 * row_stride, W + (int64_t)o0 * row_stride};
+  uint32_t voff[PIECES];
+  {
+    const int q = lane >> 2, kb = km ? (lane & 3) : (lane & 3) ^ glds_chunk_perm(q);
+    const int w_rows = km ? epi.km_w_rows : O;
+#pragma unroll
+    for (int i = 0; i < PIECES; ++i) {
+      const int blk = wave + 4 * i;
+      if (blk < ABLK) {
+        const int t = t0 + blk * 16 + q;
+        voff[i] = (uint32_t)((t < T ? t : T - 1) - t0) * (uint32_t)row_stride + (uint32_t)(kb * 16);
+      } else {
+        const int wb = blk - ABLK;
+        const int o = km ? o0 + wb * 16 + q : o0 + (wb / NT) * (16 * NT) + NT * q + wb % NT;
+        voff[i] = (uint32_t)((o < w_rows ? o : w_rows - 1) - o0) * (uint32_t)row_stride + (uint32_t)(kb * 16);
+      }
+    }
+  }
+  static_assert(ABLK % 4 == 0, "a wavefront's pieces i < ABLK / 4 are rows of A, the rest rows of W");
+#define FPQ_RING_ISSUE(g, buf)                                                                                      \
+  _Pragma("unroll") for (int i_ = 0; i_ < PIECES; ++i_)                                                             \
+      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                                 \
+                   :                                                                                                \
+                   : "v"(voff[i_]), "s"(gbase[i_ < ABLK / 4 ? 0 : 1] + (g) * (i_ < ABLK / 4 ? a_step : w_step)),    \
+                     "s"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + (buf) * STAGE +     \
+                                                                                       (wave + 4 * i_) * 1024))    \
+                   : "m0")
+
+  if (km) {
+    // the k-major scale images by LDS-DMA (gemm_fp4_glds_kernel's block), IN FRONT of the ring: a wavefront has 0 .. n pieces of
+    // them, so they cannot be counted - being older than group 0, its wait covers them
+    constexpr int APG = 256 / BM, LPG_A = BM / 4;
+    const int Tpad = (T + 3) & ~3, n_a = (G + APG - 1) / APG, n_w = (G + 1) >> 1;
+    const float* sa_km = (const float*)sa;
+    const float* sw_km = (const float*)sw;
+    for (int p = wave; p < n_a + n_w; p += 4) {
+      const bool is_a = p < n_a;
+      const int g0 = is_a ? p * APG : (p - n_a) * 2;
+      const int sub = is_a ? lane / LPG_A : lane >> 5, l4 = is_a ? lane % LPG_A : lane & 31;
+      const int grp = g0 + sub < G ? g0 + sub : G - 1;
+      const int rows = is_a ? Tpad : epi.km_w_rows, r0 = is_a ? t0 : o0;
+      int r4 = r0 + 4 * l4;
+      r4 = r4 < rows - 4 ? r4 : rows - 4;
+      const uint32_t vo = (uint32_t)(((grp - g0) * rows + (r4 - r0)) * 4);
+      const float* sbase = (is_a ? sa_km : sw_km) + ((int64_t)g0 * rows + r0);
+      const uint32_t dst = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(is_a ? lsa + g0 * BM : lsw + g0 * BN);
+      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(vo), "s"(sbase), "s"(dst) : "m0");
+    }
+  } else {
+    load_scale_tiles<Tsw, BM, BN, NTHR>(sa, sw, lsa, lsw, t0, o0, T, O, G, tid);
+    // the wait the compiler sees (gemm_fp4_glds_kernel: it has to stand in this branch); the ring is requested behind it
+    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+  }
+  // the tile's bias, the q / k norm's fp32 bias and head scale: in front of the ring too
+  constexpr int WROWS = 16 * MT, WCOLS = 16 * NT;
+  const int o = o0 + wn * WCOLS + NT * (lane & 15);
+  const int oc = o < O ? o : O - 4;
+  fpq_h4_t bias_h = fpq_h4_t{0, 0, 0, 0};
+  if (bias) bias_h = *(const fpq_h4_t*)(bias + oc);
+  v4f_t qkn_b = v4f_t{0, 0, 0, 0};
+  float qkn_s = 1.0f;
+  if constexpr (QKN) {
+    if (xe.bias) qkn_b = *(const v4f_t*)(xe.bias + oc);
+    if (o0 < epi.sp_cols) qkn_s = xe.q_scale[oc >> 6];
+  }
+  // the ring's first min(S - 1, G) groups
+#pragma unroll
+  for (int i = 0; i < S - 1; ++i)
+    if (i < G) { FPQ_RING_ISSUE(i, i); }   // uniform
+
+  uint16_t* lut = nullptr;
+  if constexpr (FC1) {   // the dual quantizer's bucket table, behind the scale tiles; visible after the first barrier of the main loop
+    lut = (uint16_t*)(lsw + Gp * BN);
+    lut16_stage(lut, xe.tab, xe.a.shift);
+  }
+
+  v4f_t acc[MT][NT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[m][n] = v4f_t{0, 0, 0, 0};
+
+  const int frag_off = ((lane & 15) << 6) + ((((lane >> 4) ^ glds_chunk_perm(lane & 15)) & 3) << 4);
+  const int a_off = wm * MT * 1024 + frag_off, b_off = (ABLK + wn * NT) * 1024 + frag_off;
+  const int sa_off = wm * MT * 16 + 4 * (lane >> 4), sw_off = wn * NT * 16 + NT * (lane & 15);
+
+  // group g_ from stage buffer st_: gemm_fp4_glds_kernel's software pipeline over the tile rows, operation for operation
+#define FPQ_RING_GROUP(g_, st_)                                                                                     \
+  do {                                                                                                              \
+    u32x4 bq[NT];                                                                                                   \
+    _Pragma("unroll") for (int n = 0; n < NT; ++n) bq[n] = *(const u32x4*)((st_) + b_off + n * 1024);               \
+    const v4f_t sw1 = *(const v4f_t*)(lsw + (g_) * BN + sw_off);                                                    \
+    u32x4 aq = *(const u32x4*)((st_) + a_off);                                                                      \
+    v4f_t sa4 = *(const v4f_t*)(lsa + (g_) * BM + sa_off);                                                          \
+    v4f_t d_prev[NT], sa4_prev = sa4;                                                                               \
+    _Pragma("unroll") for (int n = 0; n < NT; ++n) d_prev[n] = v4f_t{0, 0, 0, 0};                                   \
+    _Pragma("unroll") for (int m = 0; m <= MT; ++m) {                                                               \
+      u32x4 aq_n = aq;                                                                                              \
+      v4f_t sa4_n = sa4;                                                                                            \
+      if (m + 1 < MT) {                                                                                             \
+        aq_n = *(const u32x4*)((st_) + a_off + (m + 1) * 1024);                                                     \
+        sa4_n = *(const v4f_t*)(lsa + (g_) * BM + sa_off + (m + 1) * 16);                                           \
+      }                                                                                                             \
+      __builtin_amdgcn_sched_barrier(0);                                                                            \
+      v4f_t d[NT];                                                                                                  \
+      if (m < MT) {                                                                                                 \
+        const v8i_t af = v8i_t{(int)aq[0], (int)aq[1], (int)aq[2], (int)aq[3], 0, 0, 0, 0};                         \
+        _Pragma("unroll") for (int n = 0; n < NT; ++n) {                                                            \
+          const v8i_t bf = v8i_t{(int)bq[n][0], (int)bq[n][1], (int)bq[n][2], (int)bq[n][3], 0, 0, 0, 0};           \
+          d[n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf, v4f_t{0, 0, 0, 0}, 4, 4, 0, 0, 0, 0);     \
+        }                                                                                                           \
+      }                                                                                                             \
+      if (m > 0) {                                                                                                  \
+        _Pragma("unroll") for (int n = 0; n < NT; ++n)                                                              \
+          _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                           \
+            const float t = d_prev[n][i] * sa4_prev[i];                                                             \
+            acc[m - 1][n][i] = __builtin_fmaf(t, sw1[n], acc[m - 1][n][i]);                                         \
+          }                                                                                                         \
+      }                                                                                                             \
+      if (m > 0 && m < MT) {                                                                                        \
+        _Pragma("unroll") for (int n = 0; n < NT; ++n) {                                                            \
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                        \
+          __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);                                                        \
+        }                                                                                                           \
+      }                                                                                                             \
+      __builtin_amdgcn_sched_barrier(0);                                                                            \
+      if (m < MT) {                                                                                                 \
+        _Pragma("unroll") for (int n = 0; n < NT; ++n) d_prev[n] = d[n];                                            \
+        sa4_prev = sa4;                                                                                             \
+      }                                                                                                             \
+      aq = aq_n;                                                                                                    \
+      sa4 = sa4_n;                                                                                                  \
+    }                                                                                                               \
+  } while (0)
+  // the last S - 1 groups' waits: rem_ = G - 1 - g groups are behind group g in the queue, all of them may stay in flight
+  // (counts past S - 2 never occur: they repeat the steady one)
+#define FPQ_RING_TAIL_WAIT(rem_)                                                                                    \
+  switch (rem_) {                                                                                                   \
+    case 0: glds_wait_vm<0>(); break;   /* the last group: everything has landed */                                 \
+    case 1: glds_wait_vm<PIECES * (1 < S - 2 ? 1 : S - 2)>(); break;                                                \
+    case 2: glds_wait_vm<PIECES * (2 < S - 2 ? 2 : S - 2)>(); break;                                                \
+    case 3: glds_wait_vm<PIECES * (3 < S - 2 ? 3 : S - 2)>(); break;                                                \
+    case 4: glds_wait_vm<PIECES * (4 < S - 2 ? 4 : S - 2)>(); break;                                                \
+    case 5: glds_wait_vm<PIECES * (5 < S - 2 ? 5 : S - 2)>(); break;                                                \
+    default: glds_wait_vm<PIECES * (S - 2)>(); break;                                                               \
+  }
+  static_assert(S - 2 <= 6, "FPQ_RING_TAIL_WAIT spells the counts out up to S - 2 = 6");
+
+  int g = 0, rb = 0;   // rb = g % S: the buffer group g is read from; the request of iteration g goes to the one before it
+  for (; g + S - 1 < G; ++g) {   // the steady state: S - 2 groups stay in flight across the barrier
+    glds_wait_vm<PIECES * (S - 2)>();
+    FPQ_SYNC();   // group g has landed for every wavefront; buffer (g - 1) % S's readers are done
+    const int wb = rb == 0 ? S - 1 : rb - 1;
+    FPQ_RING_ISSUE(g + S - 1, wb);
+    const uint8_t* st = smem + rb * STAGE;
+    FPQ_RING_GROUP(g, st);
+    rb = rb + 1 == S ? 0 : rb + 1;
+  }
+  for (; g < G; ++g) {   // the drain: nothing is requested any more
+    FPQ_RING_TAIL_WAIT(G - 1 - g);
+    FPQ_SYNC();
+    const uint8_t* st = smem + rb * STAGE;
+    FPQ_RING_GROUP(g, st);
+    rb = rb + 1 == S ? 0 : rb + 1;
+  }
+
+  // the register epilogues of gemm_fp4_glds_kernel
+  v4f_t b4 = v4f_t{0, 0, 0, 0};
+#pragma unroll
+  for (int n = 0; n < NT; ++n) b4[n] = (float)bias_h[n];
+  if constexpr (FC1) {
+    FPQ_GEMM_FC1_TAIL(STAGE);
+    return;
+  }
+  FPQ_GEMM_GATE_SETUP(WROWS);
+  FPQ_GEMM_SPLIT_SETUP(WROWS, epi.sp_cols);
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);
+    fpq_h4_t y[4];
+    if constexpr (QKN) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float yf[NT];
+#pragma unroll
+        for (int n = 0; n < NT; ++n) yf[n] = (float)(_Float16)acc[m][n][i] + qkn_b[n];
+        if (sp_part_ < 2) FPQ_QK_NORM_ROW(yf, sp_part_, qkn_s);   // uniform over the tile
+#pragma unroll
+        for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)yf[n];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)(acc[m][n][i] + b4[n]);
+    }
+    int tc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;
+    FPQ_GEMM_GATE_RESID_ROWS(y, tc, m, oc);
+    if (epi.sp_cols) {
+      const int oc_l = oc - sp_part_ * epi.sp_cols;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) FPQ_GEMM_SPLIT_STORE(y[i], m, i, tc[i], t_first, o, oc_l);
+      continue;
+    }
+    FPQ_GEMM_ROWS_STORE(y, t_first, tc, o, oc);
+  }
+}
+#undef FPQ_RING_ISSUE
+#undef FPQ_RING_GROUP
+#undef FPQ_RING_TAIL_WAIT
+
+// the ring kernel's tile and LDS figure: S stages + the scale tiles, groups rounded up to four
+struct GemmRingCfg {
+  static constexpr int BM = 64, BN = 128, S = FPQ_GEMM_RING_STAGES;
+  static size_t lds(int G) { return (size_t)S * (BM + BN) * 64 + (size_t)((G + 3) & ~3) * (BM + BN) * 4; }
+  static size_t lds_fc1(int G, int shift) { return lds(G) + ((size_t)2 << (16 - shift)); }
+};
+
 template <int MT, int NT>
 struct GemmGldsCfg {
   static constexpr int BM = 32 * MT, BN = 32 * NT;

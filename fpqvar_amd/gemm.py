@@ -455,6 +455,17 @@ def linear_fp4_gelu_dual(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes:
     return _linear_gelu_dual("linear_fp4_gelu_dual", _FORMATS["e2m1"], "rank", a_codes, a_scales, w_codes, w_scales, bias, return_gelu, outs)
 
 
+def fp4_tiling(tokens: int, outs: int, k: int, form: str = "linear") -> int:
+    """The FPQ_GEMM_CFG code (10 / 20 / 30 / 40) of the LDS-DMA tiling a linear_fp4 / linear_fp4_qkv_to_cache call (form "linear")
+    or a linear_fp4_gelu_dual call (form "fc1") of these sizes runs under the current FPQ_GEMM_CFG (fpq_gemm_fp4_tiling; 0 when
+    tokens or outs is zero).  Host arithmetic only; raises for a shape the GEMM refuses."""
+    if form not in ("linear", "fc1"):
+        raise ValueError(f"fp4_tiling: form {form!r} (linear | fc1)")
+    rc = lib().fpq_gemm_fp4_tiling(int(tokens), int(outs), int(k), 1 if form == "fc1" else 0)
+    check(min(rc, 0), "fpq_gemm_fp4_tiling")
+    return rc
+
+
 def linear_a6w4(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor,
                 bias: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -44,7 +44,9 @@ extern "C" {
                            134: + the split output and the q / k norm in the A6W4 GEMM: fpq_gemm_a6w4_mx_split, fpq_gemm_a6w4_mx_split_qknorm;
                            135: + the rotate and adaLN producers emitting the A6W4 GEMM's activation operands: fpq_a6w4_rotate_quant_rows_codes,
                                 fpq_a6w4_adaln_rotate_quant_rows_codes;
-                           136: + the format search's loss in one pass: fpq_sqerr_rows_weighted */
+                           136: + the format search's loss in one pass: fpq_sqerr_rows_weighted;
+                           (136 still: + FPQ_GEMM_CFG 40, the FP4 GEMM's deep-ring small-M tiling, and fpq_gemm_fp4_tiling - an addition that changes no
+                                existing entry point; a caller that wants the query looks the symbol up) */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -578,6 +580,19 @@ int fpq_gemm_fp4_mx_km(const uint8_t* a_image, const void* a_scales, const uint8
 int fpq_gemm_fp4_gelu_dual_km(const uint8_t* a_image, const void* a_scales, const uint8_t* w_image, const void* w_scales,
                               int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs,
                               int64_t k, void* nan_flag, fpq_stream_t stream);
+/* WHICH TILING AN FP4 GEMM CALL RUNS.  The FP4 LDS-DMA kernels come in four tilings, named by the values of the switch
+ * FPQ_GEMM_CFG that force them: 10 / 20 / 30 = 256 x 128, 128 x 128, 64 x 128 tiles behind a two-stage ring, 40 = the 64 x 128 tile
+ * behind a deep ring of stage buffers whose loads span the loop's barrier (for the first scale steps, where a tile's time is its
+ * chain of trips to memory).  All four share the per-group arithmetic and give the same bits.  (FPQ_GEMM_CFG 0..2 name the
+ * register-staged kernel's tilings, which only a row-major one-tensor call honours; the A6W4 entry points have 20 and 30 and
+ * treat every other value as "not set".)
+ * fpq_gemm_fp4_tiling: the code - 10, 20, 30 or 40 - of the LDS-DMA tiling that a call of fpq_gemm_fp4_mx / _ex / _km / _split /
+ * _split_qknorm (form 0) or of fpq_gemm_fp4_gelu_dual / _km (form 1: the LDS image carries the dual quantizer's bucket table too)
+ * with these sizes and an 8-byte aligned bias runs under the current value of the switch, the fall-through to a smaller image where
+ * the chosen one exceeds a CU's 160 KiB of LDS included.  Host arithmetic only: no GPU call, nothing launched.  Shapes the entry
+ * points refuse give their code: negative sizes or another form FPQ_ERR_ARG; k % 128, k > 8192, outs % 8 (form 1: outs % 128),
+ * tokens or outs above 2^31 - 1 FPQ_ERR_SHAPE; tokens == 0 or outs == 0 FPQ_OK (nothing would be launched); k == 0 FPQ_ERR_ARG. */
+int fpq_gemm_fp4_tiling(int64_t tokens, int64_t outs, int64_t k, int form);
 /* The activation producers writing the k-major images directly (same arguments as the forms without _km; image:
  * rows * cols / 2 bytes (FP4) or rows * cols * 3 / 4 (FP6), below 2 GiB, 16-byte aligned; cols % 128 == 0).  The FP4
  * producers' `scales` is the fp32 k-major scale image [cols / 128][rows rounded up to 4] (padding rows are not written);
