@@ -1,0 +1,76 @@
+// fpq_gemm_launch.h - what the GEMM entry points of fpq_gemm.hip and fpq_gemm_w6.hip share on the host: the epilogue descriptor ->
+// the kernels' form, the tile choice of the per-group LDS-DMA kernels, the launch.  Included inside the unit's anonymous namespace,
+// behind fpq_gemm_fp4.h (GemmEpi).
+#pragma once
+
+// ---- what the GEMM entry points below share: argument descriptors -> the kernels' form, the tile choice, the launch ----------
+
+// validates an optional epilogue descriptor and turns it into the kernels' form
+int gemm_epilogue(const fpq_gemm_epilogue_t* ep, GemmEpi* epi) {
+  *epi = GemmEpi{};
+  epi->rows_per_gate = 1;
+  epi->sp_rpb = 1;
+  if (!ep) return FPQ_OK;
+  if (ep->gate && (ep->rows_per_gate < 1 || ep->rows_per_gate > 0x7FFFFFFF)) return FPQ_ERR_ARG;
+  if ((((uintptr_t)ep->gate | (uintptr_t)ep->residual) & 15) != 0) return FPQ_ERR_ARG;
+  epi->gate = (const _Float16*)ep->gate;
+  epi->resid = (const _Float16*)ep->residual;
+  if (ep->gate) epi->rows_per_gate = (int)ep->rows_per_gate;
+  return FPQ_OK;
+}
+
+// The tiling of the per-group LDS-DMA kernels (gemm_fp4_glds_kernel, gemm_a6w4_kernel, their fc1 forms): 10 / 20 / 30 = 256 x 128,
+// 128 x 128, 64 x 128 tiles behind a two-stage ring.
+// Default: 128 x 128 tiles (three workgroups per CU); 256 x 128 tiles (two per CU) from 4000 of them
+// on (round 4: 2 - 5 % faster at [65536 x 1920] x {1920, 5760, 7680} and from 16 900 tokens on for the wide Linears, 3 - 5 %
+// slower between 1000 and 4000 tiles) while two of them fit a CU's 160 KB of LDS (the scale tiles grow with K: from K = 3840 on
+// only one would, and the smaller tile is 15 % faster there - tools/gemm_k_sweep.py); 64 x 128 tiles while the 128 x 128 ones
+// would fill less than half of the chip's 768 slots (the first scale steps of a generation: 8.4 against 11.4 us at 100 tokens;
+// tools/gemm_small_steps.py).
+// 40 = gemm_fp4_ring_kernel, the 64 x 128 tile behind a deep stage ring (fpq_gemm_fp4.h): the FP4 GEMM has it (have_ring), the
+// A6W4 GEMM does not - for it 40 means "not set".  The default NEVER chooses it: measured against 30 and the default at every
+// row count of d30's and d36-512's scale steps (K = 1920, 2304; k-major, both orders, against a 30-vs-30 spread of 0.2 us) it
+// wins at no tile count and no outs - 0.2 us slower while a grid has at most one tile per CU, 1.2 x beyond
+// (profiles/gemm_fp4_ring_small_steps.txt) - so there is no rule for it beside the tile-count rule below.
+// FPQ_GEMM_CFG (experiments, tests) forces one of the tilings the caller has; have_256: whether it has the 256 x 128 one at all,
+// big_fits_twice: whether two of those tiles fit a CU's LDS at this K.
+int gemm_glds_tiling(int64_t tokens, int64_t outs, bool have_256, bool big_fits_twice, bool have_ring = false) {
+  const int want = fpq_opt(OPT_FPQ_GEMM_CFG, 0);
+  if ((want == 10 && have_256) || want == 20 || want == 30 || (want == 40 && have_ring)) return want;
+  const int64_t big_tiles = ((tokens + 255) / 256) * ((outs + 127) / 128);
+  const int64_t mid_tiles = ((tokens + 127) / 128) * ((outs + 127) / 128);
+  return mid_tiles <= 384 ? 30 : (have_256 && big_tiles >= 4000 && big_fits_twice) ? 10 : 20;
+}
+
+// workgroups of a launch over BM x BN tiles: the column tiles rounded up to the 8 XCDs (the kernels' XCD-aware tile order), or
+// FPQ_ERR_SHAPE when a grid cannot hold them
+int64_t gemm_grid(int64_t tokens, int64_t outs, int BM, int BN) {
+  const int64_t n_col = (outs + BN - 1) / BN, n_row = (tokens + BM - 1) / BM;
+  const int64_t n_wg = 8 * ((n_col + 7) / 8) * n_row;
+  return n_wg > 0x7FFFFFFF ? (int64_t)FPQ_ERR_SHAPE : n_wg;
+}
+
+// the arguments every GEMM kernel takes, as the entry point received (and checked) them
+struct GemmCall {
+  const uint8_t* a_codes;
+  const void* a_scales;
+  const uint8_t* w_codes;
+  const void* w_scales;
+  const void* bias;
+  void* out;
+  int64_t tokens, outs, k;
+  GemmEpi epi;
+  hipStream_t st;
+};
+
+// THE launch: the grid for the kernel's tile, the scale pointers in the kernel's own types, the epilogue's extra argument if it
+// takes one (xe: GemmNoFc1 / GemmFc1 / GemmQkNorm / GemmSplit)
+template <typename Tsa, typename Tsw, typename... XE>
+int gemm_launch(void (*kernel)(const uint8_t*, const Tsa*, const uint8_t*, const Tsw*, const _Float16*, _Float16*, int, int, int, GemmEpi, XE...),
+                int BM, int BN, unsigned threads, size_t lds, const GemmCall& c, XE... xe) {
+  const int64_t n_wg = gemm_grid(c.tokens, c.outs, BM, BN);
+  if (n_wg < 0) return (int)n_wg;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_wg), dim3(threads), lds, c.st, c.a_codes, (const Tsa*)c.a_scales, c.w_codes,
+                     (const Tsw*)c.w_scales, (const _Float16*)c.bias, (_Float16*)c.out, (int)c.tokens, (int)c.outs, (int)c.k, c.epi, xe...);
+  return check_launch();
+}

@@ -557,6 +557,55 @@ at::Tensor linear_fp4(const at::Tensor& a_codes, const at::Tensor& a_scales, con
   return out;
 }
 
+// fp16 [tokens, outs] = dequant(a) @ dequant(w).T + bias with an E1M2 / E3M0 WEIGHT held as dense 6-bit codes [outs, 3 K / 4] and fp32
+// group scales, against an activation of any FP4 table (a_table_id FPQ_E2M1: nibbles [tokens, K / 2]; FPQ_E1M2 / FPQ_E3M0: 6-bit codes
+// [tokens, 3 K / 4]; fp16 scales): gemm.linear_w6's call of fpq_gemm_w6_mx, row-major operands, the gate / residual tail of linear_fp4.
+at::Tensor linear_w6(const at::Tensor& a_codes, const at::Tensor& a_scales, int64_t a_table_id, const at::Tensor& w_codes,
+                     const at::Tensor& w_scales, int64_t w_table_id, const c10::optional<at::Tensor>& bias,
+                     const c10::optional<at::Tensor>& gate, const c10::optional<at::Tensor>& residual) {
+  require_gpu(a_codes, "linear_w6");
+  TORCH_CHECK(a_table_id == FPQ_E2M1 || a_table_id == FPQ_E1M2 || a_table_id == FPQ_E3M0, "linear_w6: the activation tables are E2M1, E1M2 and E3M0");
+  TORCH_CHECK(w_table_id == FPQ_E1M2 || w_table_id == FPQ_E3M0, "linear_w6: the 6-bit weight tables are E1M2 and E3M0");
+  TORCH_CHECK(a_codes.dim() == 2 && w_codes.dim() == 2, "linear_w6: row-major operands only");
+  const int64_t a_seg = a_table_id == FPQ_E2M1 ? 64 : 96;
+  const int64_t tokens = a_codes.size(0), outs = w_codes.size(0), k = w_codes.size(1) / 96 * 128;
+  TORCH_CHECK(w_codes.size(1) % 96 == 0 && a_codes.size(1) == k / 128 * a_seg && a_scales.scalar_type() == at::kHalf,
+              "linear_w6: operand shapes / activation scale dtype mismatch");
+  TORCH_CHECK(w_scales.scalar_type() == at::kFloat, "linear_w6: the weight scales must be float32");
+  const at::Device dev = a_codes.device();
+  check_operand("linear_w6(activation)", a_codes, a_scales, tokens, a_codes.size(1), tokens * (k / 128), dev);
+  check_operand("linear_w6(weight)", w_codes, w_scales, outs, w_codes.size(1), outs * (k / 128), dev);
+  fpq_gemm_epilogue_t ep{nullptr, nullptr, 1};
+  at::Tensor g, r, b;
+  at::Tensor out = at::empty({tokens, outs}, a_codes.options().dtype(at::kHalf));
+  if (tokens == 0 || outs == 0) return out;
+  auto aligned = [](const at::Tensor& t) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0 ? t : t.clone(); };
+  if (gate.has_value()) {
+    g = gate->reshape({-1, outs});
+    TORCH_CHECK(g.scalar_type() == at::kHalf && g.size(0) > 0 && tokens % g.size(0) == 0 && g.device() == dev,
+                "linear_w6: gate must be float16 [B, outs] with tokens % B == 0");
+    g = aligned(g.contiguous());
+    ep.gate = g.data_ptr();
+    ep.rows_per_gate = std::max<int64_t>(tokens / g.size(0), 1);
+  }
+  if (residual.has_value()) {
+    r = residual->reshape({-1, outs});
+    TORCH_CHECK(r.scalar_type() == at::kHalf && r.size(0) == tokens && r.device() == dev, "linear_w6: residual must be float16 with ", tokens, " rows of ", outs);
+    r = aligned(r.contiguous());
+    ep.residual = r.data_ptr();
+  }
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->numel() == outs && bias->device() == dev, "linear_w6: bias must hold one value per output on the operands' device");
+    b = aligned(bias->detach().to(at::kHalf).reshape({-1}).contiguous());
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+  check(fpq_gemm_w6_mx((const uint8_t*)a_codes.data_ptr(), a_scales.data_ptr(), (int)a_table_id, (const uint8_t*)w_codes.data_ptr(),
+                       w_scales.data_ptr(), FPQ_F32, (int)w_table_id, b.defined() ? b.data_ptr() : nullptr, out.data_ptr(), tokens, outs, k,
+                       (gate.has_value() || residual.has_value()) ? &ep : nullptr, current_stream(a_codes)),
+        "fpq_gemm_w6_mx");
+  return out;
+}
+
 // fc1 with the FFN's GELU and fc2's dual-format input quantizer in the GEMM's epilogue (tr/basic_var.py:120-121,
 // tr/quant_utils.py:415-452,991): gemm.linear_fp4_gelu_dual.  Returns (out, gelu values or an undefined tensor).
 std::tuple<at::Tensor, c10::optional<at::Tensor>> linear_fp4_gelu_dual(const at::Tensor& a_codes, const at::Tensor& a_scales, const at::Tensor& w_codes,
@@ -690,6 +739,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias") = py::none());
   m.def("linear_fp4", &linear_fp4, py::arg("a_codes"), py::arg("a_scales"), py::arg("w_codes"), py::arg("w_scales"),
         py::arg("bias") = py::none(), py::arg("gate") = py::none(), py::arg("residual") = py::none(), py::arg("outs") = py::none());
+  m.def("linear_w6", &linear_w6, py::arg("a_codes"), py::arg("a_scales"), py::arg("a_table_id"), py::arg("w_codes"), py::arg("w_scales"),
+        py::arg("w_table_id"), py::arg("bias") = py::none(), py::arg("gate") = py::none(), py::arg("residual") = py::none());
   m.def("linear_fp4_gelu_dual", &linear_fp4_gelu_dual, py::arg("a_codes"), py::arg("a_scales"), py::arg("w_codes"), py::arg("w_scales"),
         py::arg("bias") = py::none(), py::arg("return_gelu") = false, py::arg("outs") = py::none());
   m.def("gelu_quant_rows_dual", &gelu_quant_rows_dual, py::arg("y"), py::arg("neg_table_id"), py::arg("pos_table_id"), py::arg("cols") = 128,

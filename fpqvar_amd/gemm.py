@@ -141,6 +141,8 @@ class _Format(NamedTuple):
     quantizer: str             # the public quantizer, for its messages
     bias_align: int
     split_w_f32: bool
+    w_seg: int = 64            # bytes of weight codes per 128 elements: 64 = E2M1 nibbles, 96 = dense 6-bit codes (linear_w6)
+    w_table: Tuple[int, ...] = ()   # the weight's table id, which follows the weight scales' dtype in a call of the W6 family
 
 
 _FORMATS = {
@@ -148,6 +150,9 @@ _FORMATS = {
     "e1m2": _Format(96, "fpq_gemm_a6w4", "", (TABLE_IDS["e1m2"],), "fpq_quant_rows_codes_g6", "fpq_a6w4_quant_rows_codes_km", "quantize_g6", 8, True),
     "e3m0": _Format(96, "fpq_gemm_a6w4", "", (TABLE_IDS["e3m0"],), "fpq_quant_rows_codes_g6", "fpq_a6w4_quant_rows_codes_km", "quantize_g6", 8, True),
 }
+# E1M2 / E3M0 WEIGHTS as 6-bit codes (fpq_gemm_w6_mx; row-major, plain form only): a row per (activation, weight) pair
+_W6_FORMATS = {(a, w): _FORMATS[a]._replace(gemm="fpq_gemm_w6", plain="", table=(TABLE_IDS[a],), bias_align=8, w_seg=96, w_table=(TABLE_IDS[w],))
+               for a in ("e2m1", "e1m2", "e3m0") for w in ("e1m2", "e3m0")}
 _G6_TABLES = {"e1m2": "e1m2", "fp_e1": "e1m2", "e3m0": "e3m0", "fp_e3": "e3m0"}
 _G6_CODE_FORMAT = {"e1m2": "e2m3", "e3m0": "e3m2"}   # the 6-bit hardware format that holds the table's levels
 
@@ -275,6 +280,8 @@ def _per_group_operands(name: str, fmt: _Format, a, a_scales, w, w_scales, bias,
     `outs` (or the bias) only matters for images, see _check_kmajor_fp4."""
     a_rank, w_rank = a.dim(), w.dim()
     km = a_rank == 3 and w_rank == 3
+    if fmt.w_seg != 64 and (a_rank != 2 or w_rank != 2):
+        raise RuntimeError(f"{name}: row-major operands only (a 6-bit weight has no k-major form)")
     if layouts == "rows" and (a_rank != 2 or w_rank != 2):
         raise RuntimeError(f"{name}: row-major operands only (k-major images: {name}_km)")
     if layouts == "images" and not km:
@@ -286,12 +293,12 @@ def _per_group_operands(name: str, fmt: _Format, a, a_scales, w, w_scales, bias,
         return (True, *_check_kmajor_fp4(name, a, a_scales, w, w_scales, bias, outs))
     if a_rank != 2 or w_rank != 2:
         raise RuntimeError(f"{name}: both operands must be row-major codes (2-D) or both k-major images (3-D)")
-    tokens, outs, k = a.shape[0], w.shape[0], w.shape[1] * 2
-    if k % 128 != 0 or a.shape[1] != k // 128 * fmt.seg or a_scales.dtype != torch.float16:
+    tokens, outs, k = a.shape[0], w.shape[0], w.shape[1] * 128 // fmt.w_seg
+    if k % 128 != 0 or w.shape[1] != k // 128 * fmt.w_seg or a.shape[1] != k // 128 * fmt.seg or a_scales.dtype != torch.float16:
         raise RuntimeError(f"{name}: operand shapes / activation scale dtype mismatch")
     dev = a.device
     _check_operand(f"{name}(activation)", a, a_scales, tokens, a.shape[1], tokens * (k // 128), dev)
-    _check_operand(f"{name}(weight)", w, w_scales, outs, k // 2, outs * (k // 128), dev)
+    _check_operand(f"{name}(weight)", w, w_scales, outs, w.shape[1], outs * (k // 128), dev)
     return False, tokens, outs, k
 
 
@@ -308,7 +315,7 @@ def _per_group_gemm(form: str, fmt: _Format, km: bool, a, a_scales, w, w_scales,
     dev = a.device
     with device_guard(dev):
         check(getattr(lib(), what)(a.data_ptr(), a_scales.data_ptr(), *fmt.table, w.data_ptr(), w_scales.data_ptr(), dtype_id(w_scales.dtype),
-                                   *rest, stream_ptr(dev)), what)
+                                   *fmt.w_table, *rest, stream_ptr(dev)), what)
 
 
 def _bias_f16(name: str, bias: Optional[torch.Tensor], outs: Optional[int], device, align: int = 0) -> Optional[torch.Tensor]:
@@ -325,7 +332,7 @@ def _bias_f16(name: str, bias: Optional[torch.Tensor], outs: Optional[int], devi
 
 
 def _linear(name: str, fmt, layouts: str, a, a_scales, w, w_scales, bias, gate, residual, outs, loose_bias: bool = False) -> torch.Tensor:
-    """The plain Linear with its optional gate / residual tail: linear_fp4, linear_a6w4, linear_a6w4_km"""
+    """The plain Linear with its optional gate / residual tail: linear_fp4, linear_a6w4, linear_a6w4_km, linear_w6"""
     require_gpu(a, name)
     if not isinstance(fmt, _Format):
         fmt = _g6_format(name, fmt)
@@ -514,6 +521,23 @@ def linear_a6w4_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, a_ta
     return _linear_qkv_to_cache("linear_a6w4_qkv_to_cache", a_table, a_codes, a_scales, w_codes, w_scales, bias, cache_kv, pos, seq, qk_norm_scale)
 
 
+def linear_w6(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor, w_table: str,
+              bias: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+              outs: Optional[int] = None) -> torch.Tensor:
+    """fp16 [tokens, outs] = dequantize(a) @ dequantize_g6(w, w_table).T + bias on the matrix cores (fpq_gemm_w6_mx): an E1M2 / E3M0
+    WEIGHT as the dense 6-bit codes and fp32 group scales of `quantize_g6(weight.float(), w_table)`, against an activation in any of
+    the three FP4 formats - a_table "e2m1": the nibbles and fp16 scales of quantize_mx; "e1m2" / "e3m0": the 6-bit codes of quantize_g6.
+    Row-major operands only.  gate / residual: the AdaLN block's tail as in linear_fp4.  outs: the weight's row count, when given."""
+    require_gpu(a_codes, "linear_w6")
+    a_table = "e2m1" if a_table in ("e2m1", "fp_e2") else _g6_table("linear_w6", a_table)
+    fmt = _W6_FORMATS[a_table, _g6_table("linear_w6", w_table)]
+    if w_scales.dtype != torch.float32:
+        raise RuntimeError("linear_w6: the weight scales must be float32 (what quantize_g6 writes for an fp32 weight)")
+    if outs is not None and w_codes.dim() == 2 and outs != w_codes.shape[0]:
+        raise RuntimeError(f"linear_w6: outs = {outs}, but the weight has {w_codes.shape[0]} rows")
+    return _linear("linear_w6", fmt, "rows", a_codes, a_scales, w_codes, w_scales, bias, gate, residual, None)
+
+
 # form -> the public function for E2M1 operands, for 6-bit row-major codes and for 6-bit k-major images
 _FORMS = {"plain": (linear_fp4, linear_a6w4, linear_a6w4_km),
           "gelu_dual": (linear_fp4_gelu_dual, linear_a6w4_gelu_dual, linear_a6w4_gelu_dual_km),
@@ -528,10 +552,11 @@ class FP4Linear(_ScaledOperandModule):
     Same quantization decisions as the reference (codes * scale == its fake-quantized tensors bit for
     bit); the GEMM itself is more exact than the reference's fp16 GEMM (tolerance-level agreement)."""
 
-    def __init__(self, w_codes, w_scales, bias, in_features, out_features, act_table: str = "e2m1"):
+    def __init__(self, w_codes, w_scales, bias, in_features, out_features, act_table: str = "e2m1", w_table: str = "e2m1"):
         super().__init__()
         self.in_features, self.out_features = in_features, out_features
         self.act_table = act_table   # "e2m1": nibbles on the FP4 GEMM; "e1m2" / "e3m0": 6-bit codes on the A6W4 GEMM, same weight
+        self.w_table = w_table       # "e2m1": nibbles; "e1m2" / "e3m0": 6-bit codes on the W6 GEMM (linear_w6), any activation format
         self.register_buffer("w_codes", w_codes)
         self.register_buffer("w_scales", w_scales)
         self.register_buffer("bias", bias)
@@ -542,11 +567,28 @@ class FP4Linear(_ScaledOperandModule):
         return self.w_codes.dim() == 3
 
     @classmethod
-    def from_float(cls, module: torch.nn.Linear, kmajor: bool = False, act_fp_type: str = "fp_e2", a6w4_kmajor: bool = False):
+    def from_float(cls, module: torch.nn.Linear, kmajor: bool = False, act_fp_type: str = "fp_e2", a6w4_kmajor: bool = False,
+                   weight_fp_type: str = "fp_e2"):
         """act_fp_type: the activation's per-group format - "fp_e2" (E2M1, the FP4 GEMM) or "fp_e1" / "fp_e3" (E1M2 / E3M0: the
         A6W4 GEMM on the same stored weight - row-major unless a6w4_kmajor, which lets kmajor=True hold the FP4 GEMM's k-major
-        weight images for it and run quantize_g6(kmajor=True) + linear_a6w4_km)."""
+        weight images for it and run quantize_g6(kmajor=True) + linear_a6w4_km).
+        weight_fp_type: the weight's per-group format - "fp_e2" (E2M1 nibbles, as above) or "fp_e1" / "fp_e3": the weight is held as
+        the 6-bit codes and fp32 scales of quantize_g6(weight.float(), table) and the product runs on linear_w6 for any of the three
+        activation formats (an E2M1 activation as quantize_mx's row-major nibbles).  Row-major, plain form only: kmajor /
+        a6w4_kmajor, qkv_to_cache* and FP4LinearGeluDual raise ValueError."""
         assert isinstance(module, torch.nn.Linear) and module.in_features % 128 == 0 and module.out_features % 8 == 0
+        if weight_fp_type not in ("fp_e2", "e2m1"):
+            w_table = _G6_TABLES.get(weight_fp_type) if isinstance(weight_fp_type, str) else None
+            if w_table is None:
+                raise ValueError(f"FP4Linear.from_float: weight_fp_type must be 'fp_e2', 'fp_e1' or 'fp_e3', got {weight_fp_type!r}")
+            if kmajor or a6w4_kmajor:
+                raise ValueError(f"FP4Linear.from_float: weight_fp_type={weight_fp_type!r} runs on the W6 GEMM, which has no k-major form")
+            if issubclass(cls, FP4LinearGeluDual):
+                raise ValueError(f"FP4LinearGeluDual.from_float: weight_fp_type={weight_fp_type!r} runs on the W6 GEMM, which has no fc1 tail")
+            act_table = "e2m1" if act_fp_type in ("fp_e2", "e2m1") else _g6_table("FP4Linear.from_float", act_fp_type)
+            codes, scales = quantize_g6(module.weight.detach().float(), w_table)
+            bias = None if module.bias is None else module.bias.detach().to(torch.float16)
+            return cls(codes, scales, bias, module.in_features, module.out_features, act_table, w_table)
         if act_fp_type in ("fp_e2", "e2m1"):
             act_table = "e2m1"
         else:
@@ -561,7 +603,7 @@ class FP4Linear(_ScaledOperandModule):
         return cls(codes, scales, bias, module.in_features, module.out_features, act_table)
 
     def extra_repr(self) -> str:
-        return f"in_features={self.in_features}, out_features={self.out_features}, act={self.act_table}, w=e2m1"
+        return f"in_features={self.in_features}, out_features={self.out_features}, act={self.act_table}, w={self.w_table}"
 
     def _quantize(self, x) -> Tuple[torch.Tensor, torch.Tensor]:
         """x [..., in_features] -> (codes, scales) in the module's own activation format and layout"""
@@ -577,6 +619,11 @@ class FP4Linear(_ScaledOperandModule):
             table = "e2m1"
         else:
             table = _g6_table(f"{type(self).__name__}.forward_operands", table)
+        if self.w_table != "e2m1":   # a 6-bit weight: the plain form on the W6 GEMM, row-major
+            if form != "plain":
+                raise ValueError(f"{type(self).__name__}: a {self.w_table} weight runs on the W6 GEMM, which has the plain form only "
+                                 f"(no {form} form)")
+            return linear_w6(a_codes, a_scales, table, self.w_codes, self.w_scales, self.w_table, *rest)
         fp4, rows, images = _FORMS[form]
         outs = () if form == "qkv_to_cache" else (self.out_features,)   # the last argument; mat_qkv's width is the cache's
         if table == "e2m1":   # the public functions: they hand the call to the compiled binding when it is loaded
@@ -603,8 +650,13 @@ class FP4Linear(_ScaledOperandModule):
         Without qk_norm_scale the module's fp16 bias is added and `bias` must be None.  With qk_norm_scale (fp32 [H]: the block has
         attn_l2_norm) `bias` is the fp32 cat(q_bias, 0, v_bias) [3 * C] or None, added after the fp16 rounding, and the module itself
         must have no bias (mat_qkv has none in the reference)."""
+        self._no_w6("qkv_to_cache")
         bias = self._qkv_bias("qkv_to_cache", qk_norm_scale, bias)
         return self._run("qkv_to_cache", None, *self._quantize(x), bias, cache_kv, pos, seq, qk_norm_scale)
+
+    def _no_w6(self, form: str) -> None:
+        if self.w_table != "e2m1":
+            raise ValueError(f"{type(self).__name__}.{form}: a {self.w_table} weight runs on the W6 GEMM, which has the plain form only")
 
     def _qkv_bias(self, name: str, qk_norm_scale, bias):
         """the bias of the split mat_qkv: the module's own without the q / k norm, the caller's fp32 one with it"""
@@ -623,6 +675,7 @@ class FP4Linear(_ScaledOperandModule):
                               qk_norm_scale: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`qkv_to_cache` for an activation that already is in operand form (the module's own format and layout: what
         `adaln_operands` / `rotate_operands` return): producer -> split GEMM -> cache without the activation in HBM as fp16."""
+        self._no_w6("qkv_to_cache_operands")
         return self._run("qkv_to_cache", None, a_codes, a_scales, self._qkv_bias("qkv_to_cache_operands", qk_norm_scale, bias), cache_kv, pos, seq, qk_norm_scale)
 
     @torch.no_grad()
@@ -665,11 +718,13 @@ class FP4LinearGeluDual(FP4Linear):
 
     @torch.no_grad()
     def forward(self, x):
+        self._no_w6("forward")
         return self._run("gelu_dual", None, *self._quantize(x), self.bias, False).view(*x.shape[:-1], self.out_features)
 
     @torch.no_grad()
     def forward_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor, table: Optional[str] = None) -> torch.Tensor:
         """table: the format the codes are in (default: the module's activation format), as in FP4Linear.forward_operands"""
+        self._no_w6("forward_operands")
         return self._run("gelu_dual", table, a_codes, a_scales, self.bias, False)
 
 

@@ -267,7 +267,8 @@ _FP6_SYMMETRIC = ("fp6_e2m3", "fp6_e3m2")
 
 def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, w_bit=8, a_bit=8, act_quant_sym=None,
                        fc2_act_log2_quant=None, activation_fp_quant=False, weight_fp_quant=False,
-                       ada_lin_formats=None, real_fp6=False, kmajor_operands=True, real_fp4=False, fuse_ffn=False, a6w4_kmajor=False):
+                       ada_lin_formats=None, real_fp6=False, kmajor_operands=True, real_fp4=False, fuse_ffn=False, a6w4_kmajor=False,
+                       w6_weights=False):
     """quantize_VAR with a format pair per (block, layer): ``layer_formats(block_idx, layer)`` returns
     ``(act_fp_type, weight_fp_type)`` for layer in {"fc1", "fc2", "mat_qkv", "proj"}.  ``ada_lin_formats``:
     None leaves the AdaLN Linear in full precision (as tr/ does), a pair quantizes ``ada_lin[1]`` (as the fq/ and
@@ -283,6 +284,13 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
     format - ``fp_e2`` on the FP4 GEMM (k-major with ``kmajor_operands``), ``fp_e1`` / ``fp_e3`` as 6-bit codes on the A6W4 GEMM
     against the same stored E2M1 weight (row-major unless ``a6w4_kmajor``).  Every other layer (fc2's dual format,
     ``ada_lin[1]``, an E1M2 / E3M0 weight) stays the QuantizedLinear it is without the keyword.
+
+    ``w6_weights`` (additive, default off; with ``real_fp4``, else ValueError): fc1, mat_qkv and proj with an ``fp_e1`` / ``fp_e3``
+    WEIGHT and an ``fp_e1`` / ``fp_e2`` / ``fp_e3`` activation whose shape fits the GEMM become a ``gemm.FP4Linear`` of that pair too -
+    the weight as 6-bit codes on the W6 GEMM (``gemm.linear_w6``; row-major, whatever ``kmajor_operands`` / ``a6w4_kmajor`` say).
+    All six pairs: each one's 128-term dot came out exact on the matrix core (profiles/w6_dot.txt), so none is left behind as a
+    QuantizedLinear for its numerics.  fc2 and ``ada_lin[1]`` are as without the keyword; an FFN whose fc1 has such a weight has no
+    in-GEMM tail: with ``fuse_ffn`` it takes the one-pass ``GeluThenFc2Quant`` route, or raises as below.
 
     ``a6w4_kmajor`` (additive, default off; with ``real_fp4`` and ``kmajor_operands``): the ``fp_e1`` / ``fp_e3`` layers hold the FP4
     GEMM's k-major weight images too and run the A6W4 GEMM's k-major form (``gemm.linear_a6w4_km``) - one weight layout in the
@@ -303,6 +311,8 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
               and activation_fp_quant and weight_fp_quant)
     if real_fp6 and not fp6_ok:
         raise ValueError("real_fp6 needs weight_quant='per_channel', act_quant='per_token', w_bit = a_bit = 6, fp6 formats")
+    if w6_weights and not real_fp4:
+        raise ValueError("w6_weights needs real_fp4")
     common = dict(weight_quant=weight_quant, act_quant=act_quant, w_bit=w_bit, a_bit=a_bit,
                   activation_fp_quant=activation_fp_quant, weight_fp_quant=weight_fp_quant)
 
@@ -311,13 +321,17 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
             return cls.from_float(lin, kmajor=True, act_fp_type=a, a6w4_kmajor=True)
         return cls.from_float(lin, kmajor=kmajor_operands and a == "fp_e2", act_fp_type=a)
 
-    def layer(cls, lin, a, w, **kw):
+    def layer(cls, lin, a, w, w6=False, **kw):   # w6: the layer is one of those w6_weights covers (fc1, mat_qkv, proj)
         if (fp6_ok and a in _FP6_SYMMETRIC and w in _FP6_SYMMETRIC and lin.in_features % 128 == 0 and lin.out_features % 8 == 0):
             from .gemm import FP6Linear
             return FP6Linear.from_float(lin, kmajor=kmajor_operands, weight_fp_type=w, act_fp_type=a)
         if (fp4_ok and w == "fp_e2" and a in ("fp_e1", "fp_e2", "fp_e3") and lin.in_features % 128 == 0 and lin.out_features % 8 == 0):
             from .gemm import FP4Linear
             return fp4_layer(FP4Linear, lin, a)
+        if (fp4_ok and w6 and w6_weights and w in ("fp_e1", "fp_e3") and a in ("fp_e1", "fp_e2", "fp_e3") and lin.in_features % 128 == 0
+                and lin.out_features % 8 == 0):
+            from .gemm import FP4Linear
+            return FP4Linear.from_float(lin, act_fp_type=a, weight_fp_type=w)
         return cls.from_float(lin, act_fp_type=a, weight_fp_type=w, **kw, **common)
 
     for name, m in list(model.named_modules()):
@@ -341,7 +355,7 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
                 from .gemm import FP4LinearGeluDual
                 m.fc1 = fp4_layer(FP4LinearGeluDual, fc1, a)
             else:
-                m.fc1 = layer(QuantizedLinear, fc1, a, w, act_quant_sym=act_quant_sym)
+                m.fc1 = layer(QuantizedLinear, fc1, a, w, w6=True, act_quant_sym=act_quant_sym)
             m.fc2 = layer(QuantizedLinear_fc2, fc2, a2, w2, act_quant_sym=False, fc2_act_log2_quant=fc2_act_log2_quant)
             if in_gemm:
                 m.act = nn.Identity()
@@ -354,9 +368,9 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
         elif isinstance(qkv, nn.Linear) and isinstance(proj, nn.Linear):
             b = _block_index(name)
             a, w = layer_formats(b, "mat_qkv")
-            m.mat_qkv = layer(QuantizedLinear, qkv, a, w, act_quant_sym=act_quant_sym)
+            m.mat_qkv = layer(QuantizedLinear, qkv, a, w, w6=True, act_quant_sym=act_quant_sym)
             a, w = layer_formats(b, "proj")
-            m.proj = layer(QuantizedLinear, proj, a, w, act_quant_sym=act_quant_sym)
+            m.proj = layer(QuantizedLinear, proj, a, w, w6=True, act_quant_sym=act_quant_sym)
         if ada_lin_formats is not None and isinstance(ada, nn.Sequential) and len(ada) > 1 and isinstance(ada[1], nn.Linear):
             a, w = ada_lin_formats
             ada[1] = QuantizedLinear.from_float(ada[1], act_quant_sym=act_quant_sym, act_fp_type=a, weight_fp_type=w, **common)
@@ -367,14 +381,15 @@ def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, qu
                                     a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                     activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
                                     weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True, fuse_ffn=False,
-                                    a6w4_kmajor=False):
+                                    a6w4_kmajor=False, w6_weights=False):
     """models_fp_quant/quant_utils.py:1256-1341: fc1 is E2M1 in blocks 6-20 and E3M0 elsewhere, mat_qkv E2M1 in
     blocks 0, 24, 25 and E3M0 elsewhere (activations; weights always E2M1); proj, fc2 and ada_lin[1] take the
     caller's formats.
     ``real_fp4`` / ``kmajor_operands``: as in quantize_VAR_mixed - every E2M1-weight fc1 / mat_qkv / proj on the matrix cores,
     the E3M0 activations as 6-bit codes.  ``fuse_ffn``: as in quantize_VAR_mixed - with ``real_fp4`` and ``fc2_fp_type`` =
     ``fp_e1m2_neg_e2m1_pos`` every fc1 runs its GELU and fc2's input quantizer in its GEMM's epilogue.  ``a6w4_kmajor``: as in
-    quantize_VAR_mixed - the E3M0-activation layers on k-major images too."""
+    quantize_VAR_mixed - the E3M0-activation layers on k-major images too.  ``w6_weights``: as in quantize_VAR_mixed - a proj whose
+    ``weight_fp_type`` is ``fp_e1`` / ``fp_e3`` on the W6 GEMM."""
     fc1_e2, qkv_e2 = set(range(6, 21)), {0, 24, 25}
 
     def fmt(b, layer):
@@ -388,19 +403,21 @@ def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, qu
 
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
                               activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type),
-                              real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn, a6w4_kmajor=a6w4_kmajor)
+                              real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn, a6w4_kmajor=a6w4_kmajor,
+                              w6_weights=w6_weights)
 
 
 def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,
                                         a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                         activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
                                         weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True, fuse_ffn=False,
-                                        a6w4_kmajor=False):
+                                        a6w4_kmajor=False, w6_weights=False):
     """models_fp_quant_rotate/quant_utils.py:982-1066: as the mixed FP4 variant, with mat_qkv E2M1 in blocks 24, 25 only.
     ``real_fp4`` / ``kmajor_operands``: as in quantize_VAR_mixed - every E2M1-weight fc1 / mat_qkv / proj on the matrix cores,
     the E3M0 activations as 6-bit codes.  ``fuse_ffn``: as in quantize_VAR_mixed - with ``real_fp4`` and ``fc2_fp_type`` =
     ``fp_e1m2_neg_e2m1_pos`` every fc1 runs its GELU and fc2's input quantizer in its GEMM's epilogue.  ``a6w4_kmajor``: as in
-    quantize_VAR_mixed - the E3M0-activation layers on k-major images too."""
+    quantize_VAR_mixed - the E3M0-activation layers on k-major images too.  ``w6_weights``: as in quantize_VAR_mixed - a proj whose
+    ``weight_fp_type`` is ``fp_e1`` / ``fp_e3`` on the W6 GEMM."""
     fc1_e2, qkv_e2 = set(range(6, 21)), {24, 25}
 
     def fmt(b, layer):
@@ -414,7 +431,8 @@ def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None
 
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
                               activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type),
-                              real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn, a6w4_kmajor=a6w4_kmajor)
+                              real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn, a6w4_kmajor=a6w4_kmajor,
+                              w6_weights=w6_weights)
 
 
 def quantize_VAR_mixed_fp6_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,

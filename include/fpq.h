@@ -46,7 +46,9 @@ extern "C" {
                                 fpq_a6w4_adaln_rotate_quant_rows_codes;
                            136: + the format search's loss in one pass: fpq_sqerr_rows_weighted;
                            (136 still: + FPQ_GEMM_CFG 40, the FP4 GEMM's deep-ring small-M tiling, and fpq_gemm_fp4_tiling - an addition that changes no
-                                existing entry point; a caller that wants the query looks the symbol up) */
+                                existing entry point; a caller that wants the query looks the symbol up;
+                                 + fpq_gemm_w6_mx, E1M2 / E3M0 WEIGHTS on the matrix cores as 6-bit codes against any FP4 activation format - again an
+                                addition only, and the number stays because tests/test_format_search_fused_host.py pins it: look the symbol up) */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -823,6 +825,34 @@ int fpq_gemm_a6w4_mx_split(const uint8_t* a_codes, const void* a_scales, int a_t
 int fpq_gemm_a6w4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
                                   int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
                                   const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream);
+
+/* ---- W6: E1M2 / E3M0 WEIGHTS as 6-bit codes x an E2M1 / E1M2 / E3M0 activation, per group of 128 --------------------------------
+ * The FP4 format search chooses a weight format per layer among E1M2, E2M1 and E3M0; fpq_gemm_fp4_mx and fpq_gemm_a6w4_mx run the
+ * E2M1 weights.  fpq_gemm_w6_mx runs the other two: out[t, o] = fp16(bias[o] + sum_g a_scale[t,g] * w_scale[o,g] * dot_128(level(a)[t,g,:],
+ * level(w)[o,g,:])), with the optional gate / residual tail of fpq_gemm_epilogue_t (NULL: none).
+ *   w_codes   dense 6-bit codes [outs, 3 k / 4] of w_table - FPQ_E1M2 (decoded as FP6 E2M3, blgp = 2) or FPQ_E3M0 (as BF6 E3M2, blgp = 3) -
+ *             and w_scales fp32 [outs, k / 128]: exactly what fpq_quant_rows_codes_g6 writes for an fp32 weight.  w_scale_dtype: FPQ_F32
+ *             ONLY - the kernels are not compiled for fp16 weight scales (FPQ_F16 is FPQ_ERR_DTYPE, as in the A6W4 split forms).
+ *   a_codes   of a_table: FPQ_E2M1 - nibbles [tokens, k / 2] as fpq_quant_rows_codes_mx writes them (cbsz = 4); FPQ_E1M2 / FPQ_E3M0 - 6-bit
+ *             codes [tokens, 3 k / 4] as fpq_quant_rows_codes_g6 writes them (cbsz = 2 / 3); a_scales fp16 [tokens, k / 128] in all three.
+ * Row-major operands only (no k-major, fc1-tail or split-output form).
+ * Checks, in this order, before any launch (fpq_gemm_a6w4_mx's order): a_table, w_table (FPQ_ERR_TABLE); negative sizes (FPQ_ERR_ARG); the
+ * epilogue descriptor (FPQ_ERR_ARG); w_scale_dtype other than FPQ_F32 (FPQ_ERR_DTYPE); shape (FPQ_ERR_SHAPE: k % 128, k > 8192, outs % 8,
+ * tokens or outs above 2^31 - 1, an LDS image above 160 KiB); tokens == 0 or outs == 0 (FPQ_OK, nothing launched); then NULL pointers /
+ * alignment (FPQ_ERR_ARG; codes and out 16 bytes, bias 8, scales their dtype).  Two tilings (64 x 128 and 128 x 128 tiles, the K order of
+ * both the same: bit-equal), chosen as fpq_gemm_a6w4_mx chooses; FPQ_GEMM_CFG 20 / 30 forces one.
+ * Numerics: the per-group steps of fpq_gemm_a6w4_mx - t = fl(d_g sa), acc = fma(t, sw, acc), out = fp16(acc + bias).  Per pair
+ * (activation x weight), products are multiples of / at most: E2M1 x E1M2 1/8, 10.5; E2M1 x E3M0 1/8, 96; E1M2 x E1M2 1/16, 3.0625; E1M2 x
+ * E3M0 and E3M0 x E1M2 1/16, 28; E3M0 x E3M0 1/16, 256 - the exact 128-term dot has at most 20 significant bits and fits fp32.
+ * MEASURED on an MI355X before anything else (profiles/w6_dot.txt): with k = 128, unit scales and no bias, dots that are fp16 numbers -
+ * the four constructions of fpq_gemm_a6w4_mx's measurement, for a weight table - come out bit for bit for ALL SIX pairs in both tilings
+ * (72 runs, none differs; E3M0 x E3M0 included, unlike full-range E3M2 x E3M2 codes: fpq_gemm_f6_rows).  So for every pair the contract is
+ * fpq_gemm_fp4_mx's, unchanged: against the float64 product of the decoded operands every element is within 2^-11 |ref| + 2^-25 +
+ * (1 + 2^-10) 2^-24 (S + R + |ref|) (allowance 1.0; worst measured over the shape sweep 1.000 x the bound, the fp16 output rounding), and
+ * the output is bit-equal to an fp32 model of those steps (tests/w6_model.py, tests/test_gpu_w6.py). */
+int fpq_gemm_w6_mx(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                   int w_scale_dtype, int w_table, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
+                   const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream);
 
 /* THE PRODUCERS IN FRONT OF THE A6W4 GEMM: the online rotation and the adaLN producer emitting its activation operands in one launch,
  * as fpq_rotate_quant_rows_codes_mx[_km] / fpq_adaln_rotate_quant_rows_codes_mx[_km] do for the FP4 GEMM - the activation never exists
