@@ -1,6 +1,6 @@
-// fpq_gemm_launch.h - what the GEMM entry points of fpq_gemm.hip and fpq_gemm_w6.hip share on the host: the epilogue descriptor ->
-// the kernels' form, the tile choice of the per-group LDS-DMA kernels, the launch.  Included inside the unit's anonymous namespace,
-// behind fpq_gemm_fp4.h (GemmEpi).
+// fpq_gemm_launch.h - what the GEMM entry points of fpq_gemm.hip and fpq_gemm_w6.hip share on the host: the
+// epilogue, split-output and q / k norm descriptors -> the kernels' form, the tile choice of the per-group LDS-DMA kernels, the
+// launch.  Included inside the unit's anonymous namespace, behind fpq_gemm_fp4.h (GemmEpi, GemmQkNorm).
 #pragma once
 
 // ---- what the GEMM entry points below share: argument descriptors -> the kernels' form, the tile choice, the launch ----------
@@ -16,6 +16,38 @@ int gemm_epilogue(const fpq_gemm_epilogue_t* ep, GemmEpi* epi) {
   epi->gate = (const _Float16*)ep->gate;
   epi->resid = (const _Float16*)ep->residual;
   if (ep->gate) epi->rows_per_gate = (int)ep->rows_per_gate;
+  return FPQ_OK;
+}
+
+// validates a split-output descriptor (include/fpq.h, fpq_gemm_split_t: the outputs leave in column parts, each to its own rows; no
+// gate / residual tail with it) and fills GemmEpi's sp_* fields.  whole_batches: tokens % rows_per_batch == 0 is required too -
+// the one rule on which the two families differ: the FP6 entry points ask for it, the FP4 ones never did.
+int gemm_split(const fpq_gemm_split_t* split, const fpq_gemm_epilogue_t* epilogue, int64_t tokens, int64_t outs, bool whole_batches,
+               GemmEpi* epi) {
+  if (epilogue || split->n_parts < 1 || split->n_parts > 3 || split->part_cols <= 0 || split->part_cols % 128 != 0 ||
+      outs != split->n_parts * split->part_cols || split->rows_per_batch < 1 || split->rows_per_batch > 0x7FFFFFFF ||
+      (whole_batches && tokens % split->rows_per_batch != 0))
+    return FPQ_ERR_ARG;
+  epi->sp_cols = (int)split->part_cols;
+  epi->sp_rpb = (int)split->rows_per_batch;
+  for (int p = 0; p < split->n_parts; ++p) {
+    if (!split->out[p] || ((uintptr_t)split->out[p] & 7) != 0 || split->row_stride[p] < split->part_cols || split->row_stride[p] % 4 != 0 ||
+        split->batch_stride[p] < 0 || split->row0[p] < 0)
+      return FPQ_ERR_ARG;
+    epi->sp_out[p] = (_Float16*)split->out[p];
+    epi->sp_stride[p] = split->row_stride[p];
+    epi->sp_bstride[p] = split->batch_stride[p];
+    epi->sp_row0[p] = split->row0[p];
+  }
+  return FPQ_OK;
+}
+
+// the q / k norm forms' own arguments (include/fpq.h, "THE Q / K L2 NORM"): parts q, k, v of heads of 64 columns; the fp32 bias is
+// read four outputs (16 bytes) at a time
+int gemm_qknorm(const fpq_gemm_split_t* split, const float* bias, const float* q_head_scale, GemmQkNorm* qkn) {
+  if (!split || split->n_parts != 3) return FPQ_ERR_ARG;
+  if (!q_head_scale || ((uintptr_t)q_head_scale & 3) != 0 || ((uintptr_t)bias & 15) != 0) return FPQ_ERR_ARG;
+  *qkn = GemmQkNorm{bias, q_head_scale};
   return FPQ_OK;
 }
 

@@ -19,205 +19,42 @@
 // Row-major operands, fp16 activation scales; instantiated for fp32 weight scales only (what quantize_g6 writes for a weight).
 #pragma once
 
-template <typename Tsw, int MT, int NT, int FA, int FW>
-__global__ __launch_bounds__(256, 2) FPQ_NOPK void gemm_w6_kernel(const uint8_t* __restrict__ A, const _Float16* __restrict__ sa,
-                                                                  const uint8_t* __restrict__ W, const Tsw* __restrict__ sw,
-                                                                  const _Float16* __restrict__ bias, _Float16* out, int T, int O, int C,
-                                                                  GemmEpi epi) {
-  static_assert(FA == 4 || FA == 2 || FA == 3, "activation format: 4 = FP4 E2M1, 2 = FP6 E2M3 (E1M2 levels), 3 = BF6 E3M2 (E3M0 levels)");
-  static_assert(FW == 2 || FW == 3, "weight format: 2 = FP6 E2M3 (E1M2 levels), 3 = BF6 E3M2 (E3M0 levels)");
-  static_assert(NT == 4, "the epilogue packs a lane's NT results of one row into one 8-byte store");
-  constexpr bool A4 = FA == 4;
-  constexpr int WR = 2, WC = 2, BM = 16 * MT * WR, BN = 16 * NT * WC, NTHR = 256;
-  static_assert(BM % 64 == 0 && BN % 32 == 0, "whole super-blocks; load_scale_tiles wants the A / W boundary wavefront-uniform");
-  constexpr int A_SEG = A4 ? 64 : 96, A_TILE = 16 * A_SEG;                  // bytes of a row per group, of a 16-row tile
-  constexpr int APC = BM * A_SEG / 1024, WPC = 3 * (BN / 32), NPC = APC + WPC;   // pieces of A, of W, of a stage
-  constexpr int ABYTES = APC * 1024, STAGE = NPC * 1024;
-  constexpr int PIECES = (NPC + 3) / 4;
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int G = C >> 7, a_row_bytes = A4 ? C >> 1 : (C >> 2) * 3, w_row_bytes = (C >> 2) * 3;
-  float* lsa = (float*)(smem + 2 * STAGE);   // [G][BM]
-  const int Gp = (G + 3) & ~3;
-  float* lsw = lsa + Gp * BM;                // [G][BN]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int n_col = (O + BN - 1) / BN, n_row = (T + BM - 1) / BM;
-  const int cpx = (n_col + 7) >> 3;
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int col_blk = xcd * cpx + local % cpx, row_blk = local / cpx;
-  if (col_blk >= n_col || row_blk >= n_row) return;   // uniform over the workgroup
-  const int t0 = row_blk * BM, o0 = col_blk * BN;
+// The kernel's text is fpq_gemm_w6_kernel.h, compiled under four names (as fpq_gemm_a6w4.h compiles fpq_gemm_a6w4_kernel.h): only
+// the register epilogue and the extra kernel argument differ.
+//   gemm_w6_kernel        the plain Linear (+ gate / residual tail);
+//   gemm_w6_fc1_kernel    fc1 with the FFN's GELU(tanh) and fc2's dual-format input quantizer in the epilogue - the fc1 tail of
+//                         gemm_fp4_glds_kernel / gemm_a6w4_fc1_kernel (FPQ_GEMM_FC1_TAIL: same 128-wide, 128-aligned tiles, same
+//                         lane-to-output mapping, same two-stage ring whose idle buffer takes the maxima exchange), so fc2's input is
+//                         bit-equal to the stand-alone quantizer on the same GELU values whichever GEMM computed fc1;
+//   gemm_w6_split_kernel  mat_qkv's split output (include/fpq.h, fpq_gemm_w6_mx_split): the plain epilogue's values to the parts' own
+//                         destinations;
+//   gemm_w6_qkn_kernel    the split output with the q / k L2 norm in front (fpq_gemm_w6_mx_split_qknorm).
+// Each for the same twelve (FA, FW, MT), fp32 weight scales: 48 kernels, none above 157 registers.  No k-major form.
+#define FPQ_W6_KERNEL gemm_w6_kernel
+#define FPQ_W6_FC1 0
+#define FPQ_W6_OUT 0
+#include "fpq_gemm_w6_kernel.h"
+#undef FPQ_W6_KERNEL
+#undef FPQ_W6_FC1
+#define FPQ_W6_KERNEL gemm_w6_fc1_kernel
+#define FPQ_W6_FC1 1
+#include "fpq_gemm_w6_kernel.h"
+#undef FPQ_W6_KERNEL
+#undef FPQ_W6_FC1
+#undef FPQ_W6_OUT
+#define FPQ_W6_FC1 0
+#define FPQ_W6_KERNEL gemm_w6_split_kernel
+#define FPQ_W6_OUT 1
+#include "fpq_gemm_w6_kernel.h"
+#undef FPQ_W6_KERNEL
+#undef FPQ_W6_OUT
+#define FPQ_W6_KERNEL gemm_w6_qkn_kernel
+#define FPQ_W6_OUT 2
+#include "fpq_gemm_w6_kernel.h"
+#undef FPQ_W6_KERNEL
+#undef FPQ_W6_OUT
+#undef FPQ_W6_FC1
 
-  // LDS-DMA sources: a uniform base per operand + a 32-bit lane offset that never changes (see gemm_fp4_glds_kernel); rows past
-  // the end of a tensor are clamped to its last row - their products land where the epilogue never stores
-  const uint8_t* const a_base_g = A + (int64_t)t0 * a_row_bytes;
-  const uint8_t* const w_base_g = W + (int64_t)o0 * w_row_bytes;
-  uint32_t voff[PIECES];
-#pragma unroll
-  for (int i = 0; i < PIECES; ++i) {
-    const int piece = wave + 4 * i;
-    if (piece < APC) {
-      if constexpr (A4) {                               // a 16-row block of nibbles, natural row order (gemm_fp4_glds_kernel)
-        const int q = lane >> 2, kb = (lane & 3) ^ glds_chunk_perm(q);
-        const int t = t0 + piece * 16 + q;
-        voff[i] = (uint32_t)((t < T ? t : T - 1) - t0) * (uint32_t)a_row_bytes + (uint32_t)(kb * 16);
-      } else {                                          // super-block piece / 3, part piece % 3 (fpq_gemm_fp6_kernel.h)
-        const int sb = piece / 3, ci = (piece % 3) * 64 + lane;
-        const int r = ci / 6, pc = ci - 6 * r;          // row inside the super-block, physical chunk
-        int c = pc - fp6_rot(r);
-        c = c < 0 ? c + 6 : c;                          // logical chunk this lane fetches
-        const int t = t0 + sb * 32 + r;
-        voff[i] = (uint32_t)((t < T ? t : T - 1) - t0) * (uint32_t)a_row_bytes + (uint32_t)(c * 16);
-      }
-    } else {                                            // the weight side's super-blocks, rows dealt over the wavefront's NT tiles
-      const int wp = piece - APC, sb = wp / 3, ci = (wp % 3) * 64 + lane;
-      const int r = ci / 6, pc = ci - 6 * r;
-      int c = pc - fp6_rot(r);
-      c = c < 0 ? c + 6 : c;
-      const int ti = 2 * sb + (r >> 4);                 // 16-row tile of the weight side
-      const int o = o0 + (ti / NT) * (16 * NT) + NT * (r & 15) + ti % NT;
-      voff[i] = (uint32_t)((o < O ? o : O - 1) - o0) * (uint32_t)w_row_bytes + (uint32_t)(c * 16);
-    }
-  }
-#define FPQ_W6_ISSUE(g, buf)                                                                                        \
-  _Pragma("unroll") for (int i_ = 0; i_ < PIECES; ++i_) {                                                           \
-    const int piece_ = wave + 4 * i_;                                                                               \
-    if (piece_ < NPC)   /* wavefront-uniform */                                                                     \
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                                 \
-                   :                                                                                                \
-                   : "v"(voff[i_]), "s"(piece_ < APC ? a_base_g + (g) * A_SEG : w_base_g + (g) * 96),               \
-                     "s"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + (buf) * STAGE +     \
-                                                                                       piece_ * 1024))             \
-                   : "m0");                                                                                         \
-  }
-  FPQ_W6_ISSUE(0, 0);
-  load_scale_tiles<Tsw, BM, BN, NTHR>(sa, sw, lsa, lsw, t0, o0, T, O, G, tid);
-  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), the builtin: the compiler's scoreboard forgets the scale loads (gemm_fp4_glds_kernel)
-
-  constexpr int WROWS = 16 * MT, WCOLS = 16 * NT;
-  const int o = o0 + wn * WCOLS + NT * (lane & 15);
-  const int oc = o < O ? o : O - 4;
-  fpq_h4_t bias_h = fpq_h4_t{0, 0, 0, 0};
-  if (bias) bias_h = *(const fpq_h4_t*)(bias + oc);
-
-  v4f_t acc[MT][NT];
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int n = 0; n < NT; ++n) acc[m][n] = v4f_t{0, 0, 0, 0};
-
-  // a 6-bit fragment: three 8-byte pieces inside a 16-row half of a super-block; a nibble fragment: row lane & 15, chunk lane >> 4
-  const int fr = lane & 15, kblk = lane >> 4;
-  int foff[3];
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const int b = kblk * 24 + 8 * t;
-    int pc = (b >> 4) + fp6_rot(fr);
-    pc = pc >= 6 ? pc - 6 : pc;
-    foff[t] = fr * 96 + pc * 16 + (b & 15);
-  }
-  const int a_off = wm * MT * A_TILE + (A4 ? (fr << 6) + (((kblk ^ glds_chunk_perm(fr)) & 3) << 4) : 0);
-  const int b_off = ABYTES + wn * NT * 1536;
-  const int sa_off = wm * MT * 16 + 4 * kblk, sw_off = wn * NT * 16 + NT * fr;   // outputs 4q .. 4q+3: tile n holds 4q + n
-  // the activation fragment of the 16-row tile at p_ (= stage + tile row * A_TILE)
-#define FPQ_W6_READ_A(dst_, p_)                                                                                     \
-  do {                                                                                                              \
-    if constexpr (A4) {                                                                                             \
-      const u32x4 q_ = *(const u32x4*)((p_) + a_off);                                                               \
-      dst_ = v8i_t{(int)q_[0], (int)q_[1], (int)q_[2], (int)q_[3], 0, 0, 0, 0};                                     \
-    } else {                                                                                                        \
-      const u32x2 q0_ = FPQ_LDS_READ64((p_) + a_off + foff[0]), q1_ = FPQ_LDS_READ64((p_) + a_off + foff[1]),       \
-                  q2_ = FPQ_LDS_READ64((p_) + a_off + foff[2]);                                                     \
-      dst_ = v8i_t{(int)q0_[0], (int)q0_[1], (int)q1_[0], (int)q1_[1], (int)q2_[0], (int)q2_[1], 0, 0};             \
-    }                                                                                                               \
-  } while (0)
-
-  for (int g = 0; g < G; ++g) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the compiler does not see the LDS-DMA loads
-    FPQ_SYNC();   // stage g has landed; stage g^1's readers are done
-    if (g + 1 < G) { FPQ_W6_ISSUE(g + 1, (g + 1) & 1); }
-    const uint8_t* st = smem + (g & 1) * STAGE;
-    // the software pipeline of gemm_fp4_glds_kernel: the reads of tile row m+1, the NT MFMAs of row m, the scale-and-accumulate
-    // of row m-1
-    v8i_t bf[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-      const uint8_t* p = st + b_off + n * 1536;
-      const u32x2 q0 = FPQ_LDS_READ64(p + foff[0]), q1 = FPQ_LDS_READ64(p + foff[1]), q2 = FPQ_LDS_READ64(p + foff[2]);
-      bf[n] = v8i_t{(int)q0[0], (int)q0[1], (int)q1[0], (int)q1[1], (int)q2[0], (int)q2[1], 0, 0};
-    }
-    const v4f_t sw1 = *(const v4f_t*)(lsw + g * BN + sw_off);
-    v8i_t af;
-    FPQ_W6_READ_A(af, st);
-    v4f_t sa4 = *(const v4f_t*)(lsa + g * BM + sa_off);
-    v4f_t d_prev[NT], sa4_prev = sa4;
-#pragma unroll
-    for (int n = 0; n < NT; ++n) d_prev[n] = v4f_t{0, 0, 0, 0};
-#pragma unroll
-    for (int m = 0; m <= MT; ++m) {
-      v8i_t af_n = af;
-      v4f_t sa4_n = sa4;
-      if (m + 1 < MT) {
-        FPQ_W6_READ_A(af_n, st + (m + 1) * A_TILE);
-        sa4_n = *(const v4f_t*)(lsa + g * BM + sa_off + (m + 1) * 16);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      v4f_t d[NT];
-      if (m < MT) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-          // cbsz = FA decodes the activation fragment, blgp = FW the 6-bit weight fragment; literal zero scales: the unscaled instruction
-          d[n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf[n], v4f_t{0, 0, 0, 0}, FA, FW, 0, 0, 0, 0);
-      }
-      if (m > 0) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float t = d_prev[n][i] * sa4_prev[i];
-            acc[m - 1][n][i] = __builtin_fmaf(t, sw1[n], acc[m - 1][n][i]);
-          }
-      }
-      if (m > 0 && m < MT) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (m < MT) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n) d_prev[n] = d[n];
-        sa4_prev = sa4;
-      }
-      af = af_n;
-      sa4 = sa4_n;
-    }
-  }
-#undef FPQ_W6_READ_A
-#undef FPQ_W6_ISSUE
-
-  // epilogue from the registers, as gemm_a6w4_kernel's plain one: + bias, one rounding to fp16, gate / residual, 8-byte stores
-  v4f_t b4 = v4f_t{0, 0, 0, 0};
-#pragma unroll
-  for (int n = 0; n < NT; ++n) b4[n] = (float)bias_h[n];
-  FPQ_GEMM_GATE_SETUP(WROWS);
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);
-    fpq_h4_t y[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)(acc[m][n][i] + b4[n]);
-    int tc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;
-    FPQ_GEMM_GATE_RESID_ROWS(y, tc, m, oc);
-    FPQ_GEMM_ROWS_STORE(y, t_first, tc, o, oc);
-  }
-}
 
 template <int MT, int NT>
 struct GemmW6Cfg {
@@ -226,4 +63,5 @@ struct GemmW6Cfg {
   static size_t lds(int G, bool a4) {
     return 2 * ((size_t)BM * (a4 ? 64 : 96) + (size_t)BN * 96) + (size_t)((G + 3) & ~3) * (BM + BN) * 4;
   }
+  static size_t lds_fc1(int G, bool a4, int shift) { return lds(G, a4) + ((size_t)2 << (16 - shift)); }   // + the dual quantizer's bucket table
 };

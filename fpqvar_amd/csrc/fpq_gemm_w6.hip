@@ -1,6 +1,7 @@
 // fpq_gemm_w6.hip - the per-group(128) GEMM with a 6-bit WEIGHT fragment (E1M2 / E3M0 weights against E2M1, E1M2 or E3M0
-// activations; include/fpq.h, fpq_gemm_w6.h).  One translation unit of libfpq_hip.so, beside fpq_gemm.hip: twelve kernels
-// (three activation formats x two weight formats x two tilings) that compile while that unit does.
+// activations; include/fpq.h, fpq_gemm_w6.h).  One translation unit of libfpq_hip.so, beside fpq_gemm.hip: 48 kernels (three
+// activation formats x two weight formats x two tilings, in four forms: plain, fc1 tail, split output, split output with the q / k
+// norm) that compile while that unit does - about 20 s against fpq_gemm.hip's 55 and fpq_adaln.hip's 85, so they stay one unit.
 #include "fpq_common.h"
 
 namespace {
@@ -23,6 +24,59 @@ int launch_w6(const GemmCall& c, int a_table, int w_table) {
   };
   auto weight = [&](auto fa) { return w_table == FPQ_E1M2 ? formats(fa, Int<2>{}) : formats(fa, Int<3>{}); };
   return a_table == FPQ_E2M1 ? weight(Int<4>{}) : a_table == FPQ_E1M2 ? weight(Int<2>{}) : weight(Int<3>{});
+}
+// 32 MT x 128 tiles and epilogue XE - GemmFc1: the fc1 tail; GemmSplit: the split output (c.epi's sp_* fields set; the kernel takes
+// no further argument); GemmQkNorm: the split output with the q / k norm.  Tables as in launch_w6 (the entry point
+// has checked them and the fp32 weight scales); lds: GemmW6Cfg's figure for that epilogue.
+template <int MT, typename XE>
+int launch_w6_form(const GemmCall& c, int a_table, int w_table, size_t lds, XE xe) {
+  using Cfg = GemmW6Cfg<MT, 4>;
+  if (lds > 160 * 1024) return FPQ_ERR_SHAPE;
+  auto formats = [&](auto fa, auto fw) {
+    constexpr int FA = decltype(fa)::value, FW = decltype(fw)::value;
+    if constexpr (__is_same(XE, GemmFc1))
+      return gemm_launch(gemm_w6_fc1_kernel<float, MT, 4, FA, FW>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+    else if constexpr (__is_same(XE, GemmQkNorm))
+      return gemm_launch(gemm_w6_qkn_kernel<float, MT, 4, FA, FW>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+    else
+      return gemm_launch(gemm_w6_split_kernel<float, MT, 4, FA, FW>, Cfg::BM, Cfg::BN, 256, lds, c);
+  };
+  auto weight = [&](auto fa) { return w_table == FPQ_E1M2 ? formats(fa, Int<2>{}) : formats(fa, Int<3>{}); };
+  return a_table == FPQ_E2M1 ? weight(Int<4>{}) : a_table == FPQ_E1M2 ? weight(Int<2>{}) : weight(Int<3>{});
+}
+
+// mat_qkv on the W6 GEMM: fpq_gemm_w6_mx's checks in its order, the split descriptor where gemm_a6w4_mx_impl checks it (behind the
+// sizes, in front of the dtype); out's alignment is not checked - every tile belongs to a part
+int gemm_w6_split_impl(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                       int w_scale_dtype, int w_table, const void* bias, int64_t tokens, int64_t outs, int64_t k,
+                       const fpq_gemm_split_t* split, const GemmQkNorm* qkn, fpq_stream_t stream) {
+  if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
+  GemmEpi epi;
+  if (int rc = gemm_epilogue(nullptr, &epi)) return rc;
+  if (int rc = gemm_split(split, nullptr, tokens, outs, true, &epi)) return rc;
+  if (w_scale_dtype != FPQ_F32) return FPQ_ERR_DTYPE;   // the kernels exist for fp32 weight scales only (fpq_gemm_w6.h)
+  if (k % 128 != 0 || k > 128 * 64 || outs % 8 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF ||
+      GemmW6Cfg<4, 4>::lds((int)(k / 128), false) > 160 * 1024)
+    return FPQ_ERR_SHAPE;
+  if (tokens == 0 || outs == 0) return FPQ_OK;
+  if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales) return FPQ_ERR_ARG;
+  if ((((uintptr_t)a_codes | (uintptr_t)w_codes) & 15) != 0 || ((uintptr_t)bias & 7) != 0) return FPQ_ERR_ARG;
+  if (((uintptr_t)a_scales & 1) != 0 || ((uintptr_t)w_scales & 3) != 0) return FPQ_ERR_ARG;
+  // out: the first part's tensor (not written through)
+  const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, split->out[0], tokens, outs, k, epi, (hipStream_t)stream};
+  const int G = (int)(k / 128);
+  const bool a4 = a_table == FPQ_E2M1;
+  auto tile = [&](auto mt) {
+    constexpr int MT = decltype(mt)::value;
+    const size_t lds = GemmW6Cfg<MT, 4>::lds(G, a4);
+    if (qkn) return launch_w6_form<MT>(c, a_table, w_table, lds, *qkn);
+    return launch_w6_form<MT>(c, a_table, w_table, lds, GemmSplit{});
+  };
+  return gemm_glds_tiling(tokens, outs, false, false) == 30 ? tile(Int<2>{}) : tile(Int<4>{});
+}
+
+bool w6_tables(int a_table, int w_table) {
+  return (a_table == FPQ_E2M1 || a_table == FPQ_E1M2 || a_table == FPQ_E3M0) && (w_table == FPQ_E1M2 || w_table == FPQ_E3M0);
 }
 }  // namespace
 
@@ -50,6 +104,65 @@ int fpq_gemm_w6_mx(const uint8_t* a_codes, const void* a_scales, int a_table, co
   if (((uintptr_t)a_scales & 1) != 0 || ((uintptr_t)w_scales & 3) != 0) return FPQ_ERR_ARG;
   const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
   return gemm_glds_tiling(tokens, outs, false, false) == 30 ? launch_w6<2>(c, a_table, w_table) : launch_w6<4>(c, a_table, w_table);
+}
+
+// fc1 with a 6-bit weight: the fc1 tail of fpq_gemm_fp4_gelu_dual / fpq_gemm_a6w4_gelu_dual in the W6 GEMM's epilogue
+// (gemm_w6_fc1_kernel); operands, refusal order and tilings of fpq_gemm_w6_mx; tail, gelu_out, nan_flag and fix-up launch of
+// fpq_gemm_a6w4_gelu_dual
+int fpq_gemm_w6_gelu_dual(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                          int w_scale_dtype, int w_table, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs,
+                          int64_t k, void* nan_flag, fpq_stream_t stream) {
+  if (!w6_tables(a_table, w_table)) return FPQ_ERR_TABLE;
+  const Lut16Host& dual = lut16_host(FPQ_E1M2_NEG, FPQ_E2M1_POS);   // host arithmetic only: the table travels in the kernel's arguments
+  if (!dual.tab_valid) return FPQ_ERR_TABLE;
+  if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
+  if (w_scale_dtype != FPQ_F32) return FPQ_ERR_DTYPE;   // the kernels exist for fp32 weight scales only (fpq_gemm_w6.h)
+  // outs % 128: an output tile is one quantization group wide.  The LDS image of the 128-row tiling with a 6-bit activation is the
+  // largest of the four, so it stands for all (about 116 KiB at k = 8192: the k limit is the tighter one today)
+  if (k % 128 != 0 || k > 128 * 64 || outs % 128 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF ||
+      GemmW6Cfg<4, 4>::lds_fc1((int)(k / 128), false, dual.args.shift) > 160 * 1024)
+    return FPQ_ERR_SHAPE;
+  if (tokens == 0 || outs == 0) return FPQ_OK;
+  if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
+  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out | (uintptr_t)gelu_out) & 15) != 0 || ((uintptr_t)bias & 7) != 0 ||
+      ((uintptr_t)nan_flag & 7) != 0)
+    return FPQ_ERR_ARG;
+  if (((uintptr_t)a_scales & 1) != 0 || ((uintptr_t)w_scales & 3) != 0) return FPQ_ERR_ARG;
+  GemmFc1 xe;
+  xe.a = dual.args;
+  xe.tab = dual.tab;
+  xe.h_out = (_Float16*)gelu_out;
+  xe.nan_flag = (uint32_t*)nan_flag;
+  const int G = (int)(k / 128);
+  const bool a4 = a_table == FPQ_E2M1;
+  GemmEpi epi;
+  if (int rc = gemm_epilogue(nullptr, &epi)) return rc;
+  const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
+  const int rc = gemm_glds_tiling(tokens, outs, false, false) == 30
+                     ? launch_w6_form<2>(c, a_table, w_table, GemmW6Cfg<2, 4>::lds_fc1(G, a4, xe.a.shift), xe)
+                     : launch_w6_form<4>(c, a_table, w_table, GemmW6Cfg<4, 4>::lds_fc1(G, a4, xe.a.shift), xe);
+  if (rc) return rc;
+  return nan_flag ? fpq_internal_zero_if_flag(out, tokens * outs * 2, nan_flag, stream) : FPQ_OK;
+}
+
+// mat_qkv on the W6 GEMM: the split output, and the q / k norm in that epilogue (include/fpq.h).  The tables go first, as in every W6
+// entry point.  Row-major operands: there is no kmajor argument.
+int fpq_gemm_w6_mx_split(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                         int w_scale_dtype, int w_table, const void* bias, int64_t tokens, int64_t outs, int64_t k,
+                         const fpq_gemm_split_t* split, fpq_stream_t stream) {
+  if (!w6_tables(a_table, w_table)) return FPQ_ERR_TABLE;
+  if (!split) return FPQ_ERR_ARG;
+  return gemm_w6_split_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, w_table, bias, tokens, outs, k, split, nullptr,
+                            stream);
+}
+int fpq_gemm_w6_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                                int w_scale_dtype, int w_table, const float* bias, int64_t tokens, int64_t outs, int64_t k,
+                                const fpq_gemm_split_t* split, const float* q_head_scale, fpq_stream_t stream) {
+  if (!w6_tables(a_table, w_table)) return FPQ_ERR_TABLE;
+  GemmQkNorm qkn;
+  if (int rc = gemm_qknorm(split, bias, q_head_scale, &qkn)) return rc;
+  return gemm_w6_split_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, w_table, nullptr, tokens, outs, k, split, &qkn,
+                            stream);
 }
 
 }  // extern "C"

@@ -150,8 +150,10 @@ _FORMATS = {
     "e1m2": _Format(96, "fpq_gemm_a6w4", "", (TABLE_IDS["e1m2"],), "fpq_quant_rows_codes_g6", "fpq_a6w4_quant_rows_codes_km", "quantize_g6", 8, True),
     "e3m0": _Format(96, "fpq_gemm_a6w4", "", (TABLE_IDS["e3m0"],), "fpq_quant_rows_codes_g6", "fpq_a6w4_quant_rows_codes_km", "quantize_g6", 8, True),
 }
-# E1M2 / E3M0 WEIGHTS as 6-bit codes (fpq_gemm_w6_mx; row-major, plain form only): a row per (activation, weight) pair
-_W6_FORMATS = {(a, w): _FORMATS[a]._replace(gemm="fpq_gemm_w6", plain="", table=(TABLE_IDS[a],), bias_align=8, w_seg=96, w_table=(TABLE_IDS[w],))
+# E1M2 / E3M0 WEIGHTS as 6-bit codes (fpq_gemm_w6_mx, _gelu_dual, _mx_split, _mx_split_qknorm; row-major only, fp32 weight scales
+# only): a row per (activation, weight) pair
+_W6_FORMATS = {(a, w): _FORMATS[a]._replace(gemm="fpq_gemm_w6", plain="", table=(TABLE_IDS[a],), bias_align=8, split_w_f32=True, w_seg=96,
+                                            w_table=(TABLE_IDS[w],))
                for a in ("e2m1", "e1m2", "e3m0") for w in ("e1m2", "e3m0")}
 _G6_TABLES = {"e1m2": "e1m2", "fp_e1": "e1m2", "e3m0": "e3m0", "fp_e3": "e3m0"}
 _G6_CODE_FORMAT = {"e1m2": "e2m3", "e3m0": "e3m2"}   # the 6-bit hardware format that holds the table's levels
@@ -305,9 +307,9 @@ def _per_group_operands(name: str, fmt: _Format, a, a_scales, w, w_scales, bias,
 def _per_group_gemm(form: str, fmt: _Format, km: bool, a, a_scales, w, w_scales, *rest) -> None:
     """One call of the family's C entry point of `form`: "" (plain, with the optional gate / residual tail), "gelu_dual" (fc1),
     "split" or "split_qknorm" (mat_qkv into the cache); rest: its arguments between the weight scales' dtype and the stream - or,
-    for the split forms, which take the layout as a flag, the k-major flag before it."""
+    for the split forms, which take the layout as a flag, the k-major flag before it (the W6 family has no k-major form, and no flag)."""
     if form in ("split", "split_qknorm"):
-        what, rest = f"{fmt.gemm}_mx_{form}", (*rest, 1 if km else 0)
+        what, rest = f"{fmt.gemm}_mx_{form}", (*rest, 1 if km else 0) if fmt.w_seg == 64 else rest
     elif form:   # an entry point per layout
         what = f"{fmt.gemm}_{form}_km" if km else f"{fmt.gemm}_{form}"
     else:
@@ -349,7 +351,8 @@ def _linear(name: str, fmt, layouts: str, a, a_scales, w, w_scales, bias, gate, 
 
 
 def _linear_gelu_dual(name: str, fmt, layouts: str, a, a_scales, w, w_scales, bias, return_gelu: bool, outs):
-    """fc1 with the GELU and the dual quantizer in the epilogue: linear_fp4_gelu_dual, linear_a6w4_gelu_dual, linear_a6w4_gelu_dual_km"""
+    """fc1 with the GELU and the dual quantizer in the epilogue: linear_fp4_gelu_dual, linear_a6w4_gelu_dual, linear_a6w4_gelu_dual_km,
+    linear_w6_gelu_dual"""
     require_gpu(a, name)
     if not isinstance(fmt, _Format):
         fmt = _g6_format(name, fmt)
@@ -406,7 +409,7 @@ def _qkv_split_args(name: str, cache_kv: torch.Tensor, tokens: int, outs: int, b
 
 
 def _linear_qkv_to_cache(name: str, fmt, a, a_scales, w, w_scales, bias, cache_kv, pos: int, seq: int, qk_norm_scale) -> torch.Tensor:
-    """mat_qkv with q returned and k, v written into the cache: linear_fp4_qkv_to_cache, linear_a6w4_qkv_to_cache"""
+    """mat_qkv with q returned and k, v written into the cache: linear_fp4_qkv_to_cache, linear_a6w4_qkv_to_cache, linear_w6_qkv_to_cache"""
     require_gpu(a, name)
     if not isinstance(fmt, _Format):
         fmt = _g6_format(name, fmt)
@@ -529,19 +532,52 @@ def linear_w6(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_cod
     the three FP4 formats - a_table "e2m1": the nibbles and fp16 scales of quantize_mx; "e1m2" / "e3m0": the 6-bit codes of quantize_g6.
     Row-major operands only.  gate / residual: the AdaLN block's tail as in linear_fp4.  outs: the weight's row count, when given."""
     require_gpu(a_codes, "linear_w6")
-    a_table = "e2m1" if a_table in ("e2m1", "fp_e2") else _g6_table("linear_w6", a_table)
-    fmt = _W6_FORMATS[a_table, _g6_table("linear_w6", w_table)]
-    if w_scales.dtype != torch.float32:
-        raise RuntimeError("linear_w6: the weight scales must be float32 (what quantize_g6 writes for an fp32 weight)")
+    fmt = _w6_format("linear_w6", a_table, w_table, w_scales)
     if outs is not None and w_codes.dim() == 2 and outs != w_codes.shape[0]:
         raise RuntimeError(f"linear_w6: outs = {outs}, but the weight has {w_codes.shape[0]} rows")
     return _linear("linear_w6", fmt, "rows", a_codes, a_scales, w_codes, w_scales, bias, gate, residual, None)
+
+
+def _w6_format(name: str, a_table: str, w_table: str, w_scales: torch.Tensor) -> _Format:
+    """the row of an (activation, weight) pair of the W6 family, and its one weight scale dtype"""
+    a_table = "e2m1" if a_table in ("e2m1", "fp_e2") else _g6_table(name, a_table)
+    fmt = _W6_FORMATS[a_table, _g6_table(name, w_table)]
+    if w_scales.dtype != torch.float32:
+        raise RuntimeError(f"{name}: the weight scales must be float32 (what quantize_g6 writes for an fp32 weight)")
+    return fmt
+
+
+def linear_w6_gelu_dual(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor, w_table: str,
+                        bias: Optional[torch.Tensor] = None, return_gelu: bool = False):
+    """linear_a6w4_gelu_dual for a 6-bit WEIGHT (fpq_gemm_w6_gelu_dual): fc1 of the FFN up to fc2's GEMM in one launch (+ the NaN fix-up
+    launch) - `fp_quant_e1m2_neg_e2m1_pos_per_group_cuda(F.gelu(linear_w6(a, a_table, w, w_table, bias), approximate="tanh"), 4, 128)` as
+    the epilogue of the W6 GEMM: fp16 [tokens, outs], outs % 128 == 0.  Operands as linear_w6 takes them: row-major only, float32
+    weight scales.  return_gelu: also the GELU values the quantizer saw - the same function of the fp16 Linear output as
+    linear_fp4_gelu_dual's, bit for bit."""
+    require_gpu(a_codes, "linear_w6_gelu_dual")
+    fmt = _w6_format("linear_w6_gelu_dual", a_table, w_table, w_scales)
+    return _linear_gelu_dual("linear_w6_gelu_dual", fmt, "rows", a_codes, a_scales, w_codes, w_scales, bias, return_gelu, None)
+
+
+def linear_w6_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor,
+                           w_table: str, bias: Optional[torch.Tensor], cache_kv: torch.Tensor, pos: int, seq: int,
+                           qk_norm_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """linear_a6w4_qkv_to_cache for a 6-bit WEIGHT (fpq_gemm_w6_mx_split / fpq_gemm_w6_mx_split_qknorm): mat_qkv of an attention block
+    whose weight format is E1M2 / E3M0 - `qkv = linear_w6(a, a_table, w, w_table, bias)` for tokens [B * seq] and outs = 3 * C, but only
+    q comes back, fp16 [B, seq, C], while k and v are written straight into `cache_kv` [2, B, max_len, H, c] at token positions
+    pos .. pos + seq, bit for bit what the plain GEMM and the cache's copy-in leave there.  Operands as linear_w6 takes them: row-major
+    only, float32 weight scales.  qk_norm_scale, and the fp32 bias that goes with it: as in linear_fp4_qkv_to_cache."""
+    require_gpu(a_codes, "linear_w6_qkv_to_cache")
+    fmt = _w6_format("linear_w6_qkv_to_cache", a_table, w_table, w_scales)
+    return _linear_qkv_to_cache("linear_w6_qkv_to_cache", fmt, a_codes, a_scales, w_codes, w_scales, bias, cache_kv, pos, seq, qk_norm_scale)
 
 
 # form -> the public function for E2M1 operands, for 6-bit row-major codes and for 6-bit k-major images
 _FORMS = {"plain": (linear_fp4, linear_a6w4, linear_a6w4_km),
           "gelu_dual": (linear_fp4_gelu_dual, linear_a6w4_gelu_dual, linear_a6w4_gelu_dual_km),
           "qkv_to_cache": (linear_fp4_qkv_to_cache, linear_a6w4_qkv_to_cache, linear_a6w4_qkv_to_cache)}
+# form -> the public function for a 6-bit weight (row-major; the forms beside "plain" need the module's w6_forms)
+_W6_FORMS = {"plain": linear_w6, "gelu_dual": linear_w6_gelu_dual, "qkv_to_cache": linear_w6_qkv_to_cache}
 
 
 class FP4Linear(_ScaledOperandModule):
@@ -552,11 +588,13 @@ class FP4Linear(_ScaledOperandModule):
     Same quantization decisions as the reference (codes * scale == its fake-quantized tensors bit for
     bit); the GEMM itself is more exact than the reference's fp16 GEMM (tolerance-level agreement)."""
 
-    def __init__(self, w_codes, w_scales, bias, in_features, out_features, act_table: str = "e2m1", w_table: str = "e2m1"):
+    def __init__(self, w_codes, w_scales, bias, in_features, out_features, act_table: str = "e2m1", w_table: str = "e2m1",
+                 w6_forms: bool = False):
         super().__init__()
         self.in_features, self.out_features = in_features, out_features
         self.act_table = act_table   # "e2m1": nibbles on the FP4 GEMM; "e1m2" / "e3m0": 6-bit codes on the A6W4 GEMM, same weight
         self.w_table = w_table       # "e2m1": nibbles; "e1m2" / "e3m0": 6-bit codes on the W6 GEMM (linear_w6), any activation format
+        self.w6_forms = bool(w6_forms)   # a 6-bit weight also runs the W6 GEMM's fc1 tail and split output (else: the plain form only)
         self.register_buffer("w_codes", w_codes)
         self.register_buffer("w_scales", w_scales)
         self.register_buffer("bias", bias)
@@ -568,14 +606,17 @@ class FP4Linear(_ScaledOperandModule):
 
     @classmethod
     def from_float(cls, module: torch.nn.Linear, kmajor: bool = False, act_fp_type: str = "fp_e2", a6w4_kmajor: bool = False,
-                   weight_fp_type: str = "fp_e2"):
+                   weight_fp_type: str = "fp_e2", w6_forms: bool = False):
         """act_fp_type: the activation's per-group format - "fp_e2" (E2M1, the FP4 GEMM) or "fp_e1" / "fp_e3" (E1M2 / E3M0: the
         A6W4 GEMM on the same stored weight - row-major unless a6w4_kmajor, which lets kmajor=True hold the FP4 GEMM's k-major
         weight images for it and run quantize_g6(kmajor=True) + linear_a6w4_km).
         weight_fp_type: the weight's per-group format - "fp_e2" (E2M1 nibbles, as above) or "fp_e1" / "fp_e3": the weight is held as
         the 6-bit codes and fp32 scales of quantize_g6(weight.float(), table) and the product runs on linear_w6 for any of the three
         activation formats (an E2M1 activation as quantize_mx's row-major nibbles).  Row-major, plain form only: kmajor /
-        a6w4_kmajor, qkv_to_cache* and FP4LinearGeluDual raise ValueError."""
+        a6w4_kmajor, qkv_to_cache* and FP4LinearGeluDual raise ValueError.
+        w6_forms (with a 6-bit weight; an E2M1 weight ignores it): the module also runs the W6 GEMM's fc1 tail and split output -
+        FP4LinearGeluDual constructs (linear_w6_gelu_dual) and qkv_to_cache* work (linear_w6_qkv_to_cache).  Still row-major only:
+        kmajor / a6w4_kmajor raise as before."""
         assert isinstance(module, torch.nn.Linear) and module.in_features % 128 == 0 and module.out_features % 8 == 0
         if weight_fp_type not in ("fp_e2", "e2m1"):
             w_table = _G6_TABLES.get(weight_fp_type) if isinstance(weight_fp_type, str) else None
@@ -583,12 +624,12 @@ class FP4Linear(_ScaledOperandModule):
                 raise ValueError(f"FP4Linear.from_float: weight_fp_type must be 'fp_e2', 'fp_e1' or 'fp_e3', got {weight_fp_type!r}")
             if kmajor or a6w4_kmajor:
                 raise ValueError(f"FP4Linear.from_float: weight_fp_type={weight_fp_type!r} runs on the W6 GEMM, which has no k-major form")
-            if issubclass(cls, FP4LinearGeluDual):
+            if issubclass(cls, FP4LinearGeluDual) and not w6_forms:
                 raise ValueError(f"FP4LinearGeluDual.from_float: weight_fp_type={weight_fp_type!r} runs on the W6 GEMM, which has no fc1 tail")
             act_table = "e2m1" if act_fp_type in ("fp_e2", "e2m1") else _g6_table("FP4Linear.from_float", act_fp_type)
             codes, scales = quantize_g6(module.weight.detach().float(), w_table)
             bias = None if module.bias is None else module.bias.detach().to(torch.float16)
-            return cls(codes, scales, bias, module.in_features, module.out_features, act_table, w_table)
+            return cls(codes, scales, bias, module.in_features, module.out_features, act_table, w_table, w6_forms=w6_forms)
         if act_fp_type in ("fp_e2", "e2m1"):
             act_table = "e2m1"
         else:
@@ -619,11 +660,11 @@ class FP4Linear(_ScaledOperandModule):
             table = "e2m1"
         else:
             table = _g6_table(f"{type(self).__name__}.forward_operands", table)
-        if self.w_table != "e2m1":   # a 6-bit weight: the plain form on the W6 GEMM, row-major
-            if form != "plain":
+        if self.w_table != "e2m1":   # a 6-bit weight: the W6 GEMM, row-major; the forms beside the plain one with w6_forms only
+            if form != "plain" and not self.w6_forms:
                 raise ValueError(f"{type(self).__name__}: a {self.w_table} weight runs on the W6 GEMM, which has the plain form only "
                                  f"(no {form} form)")
-            return linear_w6(a_codes, a_scales, table, self.w_codes, self.w_scales, self.w_table, *rest)
+            return _W6_FORMS[form](a_codes, a_scales, table, self.w_codes, self.w_scales, self.w_table, *rest)
         fp4, rows, images = _FORMS[form]
         outs = () if form == "qkv_to_cache" else (self.out_features,)   # the last argument; mat_qkv's width is the cache's
         if table == "e2m1":   # the public functions: they hand the call to the compiled binding when it is loaded
@@ -655,7 +696,7 @@ class FP4Linear(_ScaledOperandModule):
         return self._run("qkv_to_cache", None, *self._quantize(x), bias, cache_kv, pos, seq, qk_norm_scale)
 
     def _no_w6(self, form: str) -> None:
-        if self.w_table != "e2m1":
+        if self.w_table != "e2m1" and not self.w6_forms:
             raise ValueError(f"{type(self).__name__}.{form}: a {self.w_table} weight runs on the W6 GEMM, which has the plain form only")
 
     def _qkv_bias(self, name: str, qk_norm_scale, bias):
@@ -714,7 +755,8 @@ class FP4LinearGeluDual(FP4Linear):
     must neither apply the activation nor quantize again (`quant_linear.quantize_VAR(..., real_fp4=True, fuse_ffn=True)` swaps
     the FFN's `act` for an identity and switches fc2's input quantizer off).  With an E1M2 / E3M0 activation format
     (`from_float(..., act_fp_type="fp_e1" / "fp_e3")`; row-major, or k-major with `a6w4_kmajor=True`) the same tail runs in the A6W4
-    GEMM (`linear_a6w4_gelu_dual` / `linear_a6w4_gelu_dual_km`)."""
+    GEMM (`linear_a6w4_gelu_dual` / `linear_a6w4_gelu_dual_km`), and with an E1M2 / E3M0 weight format and `w6_forms=True` in the W6 GEMM
+    (`linear_w6_gelu_dual`, row-major)."""
 
     @torch.no_grad()
     def forward(self, x):

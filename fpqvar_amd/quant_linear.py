@@ -268,7 +268,7 @@ _FP6_SYMMETRIC = ("fp6_e2m3", "fp6_e3m2")
 def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, w_bit=8, a_bit=8, act_quant_sym=None,
                        fc2_act_log2_quant=None, activation_fp_quant=False, weight_fp_quant=False,
                        ada_lin_formats=None, real_fp6=False, kmajor_operands=True, real_fp4=False, fuse_ffn=False, a6w4_kmajor=False,
-                       w6_weights=False):
+                       w6_weights=False, w6_forms=False):
     """quantize_VAR with a format pair per (block, layer): ``layer_formats(block_idx, layer)`` returns
     ``(act_fp_type, weight_fp_type)`` for layer in {"fc1", "fc2", "mat_qkv", "proj"}.  ``ada_lin_formats``:
     None leaves the AdaLN Linear in full precision (as tr/ does), a pair quantizes ``ada_lin[1]`` (as the fq/ and
@@ -290,7 +290,14 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
     the weight as 6-bit codes on the W6 GEMM (``gemm.linear_w6``; row-major, whatever ``kmajor_operands`` / ``a6w4_kmajor`` say).
     All six pairs: each one's 128-term dot came out exact on the matrix core (profiles/w6_dot.txt), so none is left behind as a
     QuantizedLinear for its numerics.  fc2 and ``ada_lin[1]`` are as without the keyword; an FFN whose fc1 has such a weight has no
-    in-GEMM tail: with ``fuse_ffn`` it takes the one-pass ``GeluThenFc2Quant`` route, or raises as below.
+    in-GEMM tail without ``w6_forms``: with ``fuse_ffn`` it takes the one-pass ``GeluThenFc2Quant`` route, or raises as below.
+
+    ``w6_forms`` (additive, default off; with ``w6_weights``, else ValueError): those ``gemm.FP4Linear`` are built with
+    ``w6_forms=True``, so a mat_qkv with a 6-bit weight has ``qkv_to_cache`` / ``qkv_to_cache_operands`` (the W6 GEMM's split output,
+    q / k norm included), and with ``fuse_ffn`` an FFN whose fc1 has such a weight and meets the conditions below gets the in-GEMM tail
+    too: fc1 becomes ``gemm.FP4LinearGeluDual`` on the W6 GEMM (``gemm.linear_w6_gelu_dual``), ``act`` an identity and fc2's input
+    quantizer is switched off - one launch where the ``GeluThenFc2Quant`` route takes three.  k-major operands remain unbuilt for a
+    6-bit weight.
 
     ``a6w4_kmajor`` (additive, default off; with ``real_fp4`` and ``kmajor_operands``): the ``fp_e1`` / ``fp_e3`` layers hold the FP4
     GEMM's k-major weight images too and run the A6W4 GEMM's k-major form (``gemm.linear_a6w4_km``) - one weight layout in the
@@ -313,6 +320,9 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
         raise ValueError("real_fp6 needs weight_quant='per_channel', act_quant='per_token', w_bit = a_bit = 6, fp6 formats")
     if w6_weights and not real_fp4:
         raise ValueError("w6_weights needs real_fp4")
+    if w6_forms and not w6_weights:
+        raise ValueError("w6_forms needs w6_weights")
+    w6_kw = {"w6_forms": True} if w6_forms else {}   # (passed only when on: the keyword list without it is today's)
     common = dict(weight_quant=weight_quant, act_quant=act_quant, w_bit=w_bit, a_bit=a_bit,
                   activation_fp_quant=activation_fp_quant, weight_fp_quant=weight_fp_quant)
 
@@ -331,7 +341,7 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
         if (fp4_ok and w6 and w6_weights and w in ("fp_e1", "fp_e3") and a in ("fp_e1", "fp_e2", "fp_e3") and lin.in_features % 128 == 0
                 and lin.out_features % 8 == 0):
             from .gemm import FP4Linear
-            return FP4Linear.from_float(lin, act_fp_type=a, weight_fp_type=w)
+            return FP4Linear.from_float(lin, act_fp_type=a, weight_fp_type=w, **w6_kw)
         return cls.from_float(lin, act_fp_type=a, weight_fp_type=w, **kw, **common)
 
     for name, m in list(model.named_modules()):
@@ -344,7 +354,8 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
             a2, w2 = layer_formats(b, "fc2")
             act = getattr(m, "act", None)
             gelu_tanh = isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "tanh"
-            in_gemm = (fuse_ffn and gelu_tanh and fp4_ok and w == "fp_e2" and a in ("fp_e1", "fp_e2", "fp_e3")
+            w6_tail = w6_forms and w in ("fp_e1", "fp_e3")   # the W6 GEMM's fc1 tail stands in for the FP4 / A6W4 GEMM's
+            in_gemm = (fuse_ffn and gelu_tanh and fp4_ok and (w == "fp_e2" or w6_tail) and a in ("fp_e1", "fp_e2", "fp_e3")
                        and a2 == "fp_e1m2_neg_e2m1_pos" and fc1.in_features % 128 == 0 and fc1.out_features % 128 == 0)
             one_pass = (fuse_ffn and gelu_tanh and not in_gemm and activation_fp_quant and (act_quant, a2) in GeluThenFc2Quant.FUSED
                         and fc1.out_features % (128 if act_quant == "per_group" else 8) == 0)
@@ -353,7 +364,10 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
                                  "(fp_e1m2_neg_e2m1_pos / fp4_afpq per group, fp6_int_neg_e2m3_pos per group or per token)")
             if in_gemm:
                 from .gemm import FP4LinearGeluDual
-                m.fc1 = fp4_layer(FP4LinearGeluDual, fc1, a)
+                if w6_tail:
+                    m.fc1 = FP4LinearGeluDual.from_float(fc1, act_fp_type=a, weight_fp_type=w, w6_forms=True)
+                else:
+                    m.fc1 = fp4_layer(FP4LinearGeluDual, fc1, a)
             else:
                 m.fc1 = layer(QuantizedLinear, fc1, a, w, w6=True, act_quant_sym=act_quant_sym)
             m.fc2 = layer(QuantizedLinear_fc2, fc2, a2, w2, act_quant_sym=False, fc2_act_log2_quant=fc2_act_log2_quant)
@@ -381,7 +395,7 @@ def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, qu
                                     a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                     activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
                                     weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True, fuse_ffn=False,
-                                    a6w4_kmajor=False, w6_weights=False):
+                                    a6w4_kmajor=False, w6_weights=False, w6_forms=False):
     """models_fp_quant/quant_utils.py:1256-1341: fc1 is E2M1 in blocks 6-20 and E3M0 elsewhere, mat_qkv E2M1 in
     blocks 0, 24, 25 and E3M0 elsewhere (activations; weights always E2M1); proj, fc2 and ada_lin[1] take the
     caller's formats.
@@ -389,7 +403,7 @@ def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, qu
     the E3M0 activations as 6-bit codes.  ``fuse_ffn``: as in quantize_VAR_mixed - with ``real_fp4`` and ``fc2_fp_type`` =
     ``fp_e1m2_neg_e2m1_pos`` every fc1 runs its GELU and fc2's input quantizer in its GEMM's epilogue.  ``a6w4_kmajor``: as in
     quantize_VAR_mixed - the E3M0-activation layers on k-major images too.  ``w6_weights``: as in quantize_VAR_mixed - a proj whose
-    ``weight_fp_type`` is ``fp_e1`` / ``fp_e3`` on the W6 GEMM."""
+    ``weight_fp_type`` is ``fp_e1`` / ``fp_e3`` on the W6 GEMM; ``w6_forms``: passed through as well."""
     fc1_e2, qkv_e2 = set(range(6, 21)), {0, 24, 25}
 
     def fmt(b, layer):
@@ -404,20 +418,20 @@ def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, qu
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
                               activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type),
                               real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn, a6w4_kmajor=a6w4_kmajor,
-                              w6_weights=w6_weights)
+                              w6_weights=w6_weights, w6_forms=w6_forms)
 
 
 def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,
                                         a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                         activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
                                         weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True, fuse_ffn=False,
-                                        a6w4_kmajor=False, w6_weights=False):
+                                        a6w4_kmajor=False, w6_weights=False, w6_forms=False):
     """models_fp_quant_rotate/quant_utils.py:982-1066: as the mixed FP4 variant, with mat_qkv E2M1 in blocks 24, 25 only.
     ``real_fp4`` / ``kmajor_operands``: as in quantize_VAR_mixed - every E2M1-weight fc1 / mat_qkv / proj on the matrix cores,
     the E3M0 activations as 6-bit codes.  ``fuse_ffn``: as in quantize_VAR_mixed - with ``real_fp4`` and ``fc2_fp_type`` =
     ``fp_e1m2_neg_e2m1_pos`` every fc1 runs its GELU and fc2's input quantizer in its GEMM's epilogue.  ``a6w4_kmajor``: as in
     quantize_VAR_mixed - the E3M0-activation layers on k-major images too.  ``w6_weights``: as in quantize_VAR_mixed - a proj whose
-    ``weight_fp_type`` is ``fp_e1`` / ``fp_e3`` on the W6 GEMM."""
+    ``weight_fp_type`` is ``fp_e1`` / ``fp_e3`` on the W6 GEMM; ``w6_forms``: passed through as well."""
     fc1_e2, qkv_e2 = set(range(6, 21)), {24, 25}
 
     def fmt(b, layer):
@@ -432,7 +446,7 @@ def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
                               activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type),
                               real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn, a6w4_kmajor=a6w4_kmajor,
-                              w6_weights=w6_weights)
+                              w6_weights=w6_weights, w6_forms=w6_forms)
 
 
 def quantize_VAR_mixed_fp6_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,

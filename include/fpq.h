@@ -835,7 +835,8 @@ int fpq_gemm_a6w4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, 
  *             ONLY - the kernels are not compiled for fp16 weight scales (FPQ_F16 is FPQ_ERR_DTYPE, as in the A6W4 split forms).
  *   a_codes   of a_table: FPQ_E2M1 - nibbles [tokens, k / 2] as fpq_quant_rows_codes_mx writes them (cbsz = 4); FPQ_E1M2 / FPQ_E3M0 - 6-bit
  *             codes [tokens, 3 k / 4] as fpq_quant_rows_codes_g6 writes them (cbsz = 2 / 3); a_scales fp16 [tokens, k / 128] in all three.
- * Row-major operands only (no k-major, fc1-tail or split-output form).
+ * Row-major operands only (there is no k-major form; the fc1 tail and the split output: fpq_gemm_w6_gelu_dual, fpq_gemm_w6_mx_split /
+ * _split_qknorm below).
  * Checks, in this order, before any launch (fpq_gemm_a6w4_mx's order): a_table, w_table (FPQ_ERR_TABLE); negative sizes (FPQ_ERR_ARG); the
  * epilogue descriptor (FPQ_ERR_ARG); w_scale_dtype other than FPQ_F32 (FPQ_ERR_DTYPE); shape (FPQ_ERR_SHAPE: k % 128, k > 8192, outs % 8,
  * tokens or outs above 2^31 - 1, an LDS image above 160 KiB); tokens == 0 or outs == 0 (FPQ_OK, nothing launched); then NULL pointers /
@@ -853,6 +854,38 @@ int fpq_gemm_a6w4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, 
 int fpq_gemm_w6_mx(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
                    int w_scale_dtype, int w_table, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
                    const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream);
+/* fpq_gemm_w6_gelu_dual: fpq_gemm_a6w4_gelu_dual for a 6-bit weight - fc1 of the FFN, its GELU(tanh) and fc2's dual E1M2- / E2M1+
+ * per-group(128) input quantizer in ONE launch (+ the NaN fix-up launch): out = fp16 [tokens, outs] =
+ * fp_quant_e1m2_neg_e2m1_pos_per_group_cuda(gelu_tanh(y), 4, 128) with y the fp16 [tokens, outs] that fpq_gemm_w6_mx writes for the same
+ * operands and bias, bit for bit.  Operands (a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, w_table, bias) exactly
+ * fpq_gemm_w6_mx's; the tail, gelu_out (NULL, or fp16 [tokens, outs], 16-byte aligned: the GELU values the quantizer saw) and nan_flag
+ * (NULL, or the 8-byte zeroed scratch of fpq_quant_rows_dual) exactly fpq_gemm_fp4_gelu_dual's - the same GELU of the same fp16 value
+ * and the same quantizer arithmetic, so the three fc1 entry points agree bit for bit wherever their Linear outputs do.
+ * Checks, in this order, before any launch: a_table, w_table (FPQ_ERR_TABLE), negative sizes (FPQ_ERR_ARG), w_scale_dtype other than
+ * FPQ_F32 (FPQ_ERR_DTYPE), shape (FPQ_ERR_SHAPE: k % 128, k > 8192, outs % 128 - an output tile is one quantization group -, tokens or
+ * outs above 2^31 - 1, an LDS image above 160 KiB), tokens == 0 or outs == 0 (FPQ_OK), then NULL pointers / alignment (FPQ_ERR_ARG; codes,
+ * out and gelu_out 16 bytes, bias and nan_flag 8, scales their dtype).  Tilings as fpq_gemm_w6_mx; both give the same bits. */
+int fpq_gemm_w6_gelu_dual(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                          int w_scale_dtype, int w_table, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs,
+                          int64_t k, void* nan_flag, fpq_stream_t stream);
+/* MAT_QKV ON THE W6 GEMM: fpq_gemm_w6_mx's operands and every one of its operand and scale checks, no gate / residual tail, with the
+ * SPLIT OUTPUT of fpq_gemm_fp4_mx_split, and with the Q / K L2 NORM above in that epilogue - fpq_gemm_a6w4_mx_split / _split_qknorm for
+ * a 6-bit weight.  Without the norm every written value is bit for bit the one fpq_gemm_w6_mx writes at that (token, column); with it,
+ * y16 is what it writes with bias == NULL and q, k, v follow "THE Q / K L2 NORM" (the arithmetic of fpq_gemm_fp4_mx_split_qknorm: q and k
+ * within that section's bound, its non-finite rule, v bit for bit).  Row-major operands only: there is no kmajor argument.  split, bias,
+ * q_head_scale: the rules of fpq_gemm_a6w4_mx_split (whole batch entries; every destination 8-byte aligned).
+ * Checks, in this order, before any launch: a_table, w_table (FPQ_ERR_TABLE); split == NULL [_qknorm: or n_parts != 3, q_head_scale NULL
+ * or not 4-byte aligned, bias not 16-byte aligned] (FPQ_ERR_ARG); negative sizes (FPQ_ERR_ARG); the split descriptor (FPQ_ERR_ARG);
+ * w_scale_dtype other than FPQ_F32 (FPQ_ERR_DTYPE); shape (FPQ_ERR_SHAPE: k % 128, k > 8192, outs % 8, tokens or outs above 2^31 - 1, an
+ * LDS image above 160 KiB); tokens == 0 (FPQ_OK, nothing launched); then NULL pointers / alignment (FPQ_ERR_ARG; codes 16 bytes, the fp16
+ * bias 8, scales their dtype).  Tilings as fpq_gemm_w6_mx (FPQ_GEMM_CFG 20 / 30 forces one); both give the same bits.
+ * FPQ_VERSION is unchanged by these three: look the symbols up. */
+int fpq_gemm_w6_mx_split(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                         int w_scale_dtype, int w_table, const void* bias, int64_t tokens, int64_t outs, int64_t k,
+                         const fpq_gemm_split_t* split, fpq_stream_t stream);
+int fpq_gemm_w6_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                                int w_scale_dtype, int w_table, const float* bias, int64_t tokens, int64_t outs, int64_t k,
+                                const fpq_gemm_split_t* split, const float* q_head_scale, fpq_stream_t stream);
 
 /* THE PRODUCERS IN FRONT OF THE A6W4 GEMM: the online rotation and the adaLN producer emitting its activation operands in one launch,
  * as fpq_rotate_quant_rows_codes_mx[_km] / fpq_adaln_rotate_quant_rows_codes_mx[_km] do for the FP4 GEMM - the activation never exists
