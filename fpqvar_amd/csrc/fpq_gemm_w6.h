@@ -16,11 +16,12 @@
 //     and the register epilogue (+ gate / residual tail) are gemm_a6w4_kernel's: the same fp32 model (include/fpq.h).
 // A stage is BM / 16 (FA = 4) or 3 BM / 32 activation pieces + 3 BN / 32 weight pieces of 1 KiB, dealt round-robin over the four
 // wavefronts (16 / 20 / 18 / 24 pieces: a short last round is a wavefront-uniform test); two stages, one barrier per group.
-// Row-major operands, fp16 activation scales; instantiated for fp32 weight scales only (what quantize_g6 writes for a weight).
+// Row-major operands with fp16 activation scales, or k-major images with fp32 scale images (FPQ_W6_KM below); instantiated for
+// fp32 weight scales only (what quantize_g6 writes for a weight).
 #pragma once
 
-// The kernel's text is fpq_gemm_w6_kernel.h, compiled under four names (as fpq_gemm_a6w4.h compiles fpq_gemm_a6w4_kernel.h): only
-// the register epilogue and the extra kernel argument differ.
+// The kernel's text is fpq_gemm_w6_kernel.h, compiled under four names per operand layout (as fpq_gemm_a6w4.h compiles
+// fpq_gemm_a6w4_kernel.h): only the register epilogue and the extra kernel argument differ.
 //   gemm_w6_kernel        the plain Linear (+ gate / residual tail);
 //   gemm_w6_fc1_kernel    fc1 with the FFN's GELU(tanh) and fc2's dual-format input quantizer in the epilogue - the fc1 tail of
 //                         gemm_fp4_glds_kernel / gemm_a6w4_fc1_kernel (FPQ_GEMM_FC1_TAIL: same 128-wide, 128-aligned tiles, same
@@ -29,31 +30,71 @@
 //   gemm_w6_split_kernel  mat_qkv's split output (include/fpq.h, fpq_gemm_w6_mx_split): the plain epilogue's values to the parts' own
 //                         destinations;
 //   gemm_w6_qkn_kernel    the split output with the q / k L2 norm in front (fpq_gemm_w6_mx_split_qknorm).
-// Each for the same twelve (FA, FW, MT), fp32 weight scales: 48 kernels, none above 157 registers.  No k-major form.
+// Each for the same twelve (FA, FW, MT), fp32 weight scales: 48 kernels, none above 157 registers.
+// Each form also on K-MAJOR IMAGES (FPQ_W6_KM; include/fpq.h): gemm_w6_km_kernel, gemm_w6_fc1_km_kernel, gemm_w6_split_km_kernel,
+// gemm_w6_qkn_km_kernel, another 48 - the activation side's 4-bit (FA = 4) or 6-bit image, the dealt 6-bit weight image an FP6Linear
+// holds, and both fp32 scale images.  Only the LDS-DMA sources and the scale-tile load differ: same LDS image, same main loop, same
+// epilogues, same bits.
+#define FPQ_W6_KM 0
 #define FPQ_W6_KERNEL gemm_w6_kernel
 #define FPQ_W6_FC1 0
 #define FPQ_W6_OUT 0
 #include "fpq_gemm_w6_kernel.h"
 #undef FPQ_W6_KERNEL
 #undef FPQ_W6_FC1
+#undef FPQ_W6_OUT
 #define FPQ_W6_KERNEL gemm_w6_fc1_kernel
 #define FPQ_W6_FC1 1
+#define FPQ_W6_OUT 0
 #include "fpq_gemm_w6_kernel.h"
 #undef FPQ_W6_KERNEL
 #undef FPQ_W6_FC1
 #undef FPQ_W6_OUT
-#define FPQ_W6_FC1 0
 #define FPQ_W6_KERNEL gemm_w6_split_kernel
+#define FPQ_W6_FC1 0
 #define FPQ_W6_OUT 1
 #include "fpq_gemm_w6_kernel.h"
 #undef FPQ_W6_KERNEL
+#undef FPQ_W6_FC1
 #undef FPQ_W6_OUT
 #define FPQ_W6_KERNEL gemm_w6_qkn_kernel
+#define FPQ_W6_FC1 0
 #define FPQ_W6_OUT 2
 #include "fpq_gemm_w6_kernel.h"
 #undef FPQ_W6_KERNEL
-#undef FPQ_W6_OUT
 #undef FPQ_W6_FC1
+#undef FPQ_W6_OUT
+#undef FPQ_W6_KM
+#define FPQ_W6_KM 1
+#define FPQ_W6_KERNEL gemm_w6_km_kernel
+#define FPQ_W6_FC1 0
+#define FPQ_W6_OUT 0
+#include "fpq_gemm_w6_kernel.h"
+#undef FPQ_W6_KERNEL
+#undef FPQ_W6_FC1
+#undef FPQ_W6_OUT
+#define FPQ_W6_KERNEL gemm_w6_fc1_km_kernel
+#define FPQ_W6_FC1 1
+#define FPQ_W6_OUT 0
+#include "fpq_gemm_w6_kernel.h"
+#undef FPQ_W6_KERNEL
+#undef FPQ_W6_FC1
+#undef FPQ_W6_OUT
+#define FPQ_W6_KERNEL gemm_w6_split_km_kernel
+#define FPQ_W6_FC1 0
+#define FPQ_W6_OUT 1
+#include "fpq_gemm_w6_kernel.h"
+#undef FPQ_W6_KERNEL
+#undef FPQ_W6_FC1
+#undef FPQ_W6_OUT
+#define FPQ_W6_KERNEL gemm_w6_qkn_km_kernel
+#define FPQ_W6_FC1 0
+#define FPQ_W6_OUT 2
+#include "fpq_gemm_w6_kernel.h"
+#undef FPQ_W6_KERNEL
+#undef FPQ_W6_FC1
+#undef FPQ_W6_OUT
+#undef FPQ_W6_KM
 
 
 template <int MT, int NT>

@@ -7,11 +7,21 @@
 //                   tensor, k and v into the KV cache's slots), the plain epilogue's values bit for bit, no gate / residual tail;
 //                   2: the split output with the Q / K L2 NORM in front of it (FPQ_QK_NORM_ROW, fpq_gemm_fp4.h) - the kernel takes a
 //                   GemmQkNorm behind the GemmEpi, its fp32 bias replaces the fp16 one
-// (one text, compiled under several names, as fpq_gemm_a6w4_kernel.h is: only the register epilogue and the extra argument differ;
-// gemm_w6_kernel keeps its symbols and, instruction for instruction, the machine code it had before the other forms existed -
-// profiles/w6_forms_isa.txt)
+//   FPQ_W6_KM       0: row-major codes and scales; 1: K-MAJOR IMAGES (include/fpq.h) - A is the activation side's 4-bit image
+//                   [G][T][64] (FA = 4: the FP4 kernel's km addressing) or 6-bit image [G][T][96] (FA = 2 / 3: gemm_a6w4_km_kernel's), W
+//                   the dealt 6-bit image [G][km_w_rows][96] (the FP6 kernel's) and sa / sw the fp32 scale images [G][T rounded up to 4] /
+//                   [G][km_w_rows]: every piece of a stage is 1 KiB (a super-block 3 KiB) contiguous, and the scale tiles come in by
+//                   LDS-DMA too.  Tsw = float only; epi.km_w_rows = outs rounded up to 64.
+// (one text, compiled under several names, as fpq_gemm_a6w4_kernel.h is: only the register epilogue and the extra argument differ -
+// with FPQ_W6_KM only the LDS-DMA sources and the scale-tile load; the row-major kernels keep their symbols and, instruction for
+// instruction, the machine code they had before the other forms existed - profiles/w6_forms_isa.txt, w6_km_isa.txt)
+#if FPQ_W6_KM
+#define FPQ_W6_TSA float
+#else
+#define FPQ_W6_TSA _Float16
+#endif
 template <typename Tsw, int MT, int NT, int FA, int FW>
-__global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* __restrict__ A, const _Float16* __restrict__ sa,
+__global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* __restrict__ A, const FPQ_W6_TSA* __restrict__ sa,
                                                                  const uint8_t* __restrict__ W, const Tsw* __restrict__ sw,
                                                                  const _Float16* __restrict__ bias, _Float16* out, int T, int O, int C,
                                                                  GemmEpi epi
@@ -47,6 +57,70 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
 
   // LDS-DMA sources: a uniform base per operand + a 32-bit lane offset that never changes (see gemm_fp4_glds_kernel); rows past
   // the end of a tensor are clamped to its last row - their products land where the epilogue never stores
+#if FPQ_W6_KM
+  static_assert(__is_same(Tsw, float), "the k-major scale images are fp32");
+  // plane g of an image holds every row's 64 / 96 bytes of group g, chunks in the LDS image's order (no glds_chunk_perm, no fp6_rot
+  // here), weight rows in dealt order and padded to km_w_rows: the lane fetches the physical chunk of its image row
+  // (gemm_fp4_glds_kernel, gemm_a6w4_km_kernel, fpq_gemm_fp6_kernel.h)
+  const int64_t a_step = (int64_t)T * A_SEG, w_step = (int64_t)epi.km_w_rows * 96;
+  (void)a_row_bytes, (void)w_row_bytes;
+  const uint8_t* const a_base_g = A + (int64_t)t0 * A_SEG;
+  const uint8_t* const w_base_g = W + (int64_t)o0 * 96;
+  uint32_t voff[PIECES];
+#pragma unroll
+  for (int i = 0; i < PIECES; ++i) {
+    const int piece = wave + 4 * i;
+    if (piece < APC) {
+      if constexpr (A4) {                               // a 16-row block of the 4-bit image
+        const int t = t0 + piece * 16 + (lane >> 2);
+        voff[i] = (uint32_t)((t < T ? t : T - 1) - t0) * 64u + (uint32_t)((lane & 3) * 16);
+      } else {                                          // super-block piece / 3, part piece % 3 of the 6-bit image
+        const int sb = piece / 3, ci = (piece % 3) * 64 + lane;
+        const int r = ci / 6, pc = ci - 6 * r;          // row inside the super-block, physical chunk
+        const int t = t0 + sb * 32 + r;
+        voff[i] = (uint32_t)((t < T ? t : T - 1) - t0) * 96u + (uint32_t)(pc * 16);
+      }
+    } else {                                            // the weight side's super-blocks: the dealing is in the image
+      const int wp = piece - APC, sb = wp / 3, ci = (wp % 3) * 64 + lane;
+      const int r = ci / 6, pc = ci - 6 * r;
+      const int o = o0 + sb * 32 + r;                   // image row
+      voff[i] = (uint32_t)((o < epi.km_w_rows ? o : epi.km_w_rows - 1) - o0) * 96u + (uint32_t)(pc * 16);
+    }
+  }
+#define FPQ_W6_ISSUE(g, buf)                                                                                        \
+  _Pragma("unroll") for (int i_ = 0; i_ < PIECES; ++i_) {                                                           \
+    const int piece_ = wave + 4 * i_;                                                                               \
+    if (piece_ < NPC)   /* wavefront-uniform */                                                                     \
+      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                                 \
+                   :                                                                                                \
+                   : "v"(voff[i_]), "s"(piece_ < APC ? a_base_g + (g) * a_step : w_base_g + (g) * w_step),          \
+                     "s"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + (buf) * STAGE +     \
+                                                                                       piece_ * 1024))             \
+                   : "m0");                                                                                         \
+  }
+  FPQ_W6_ISSUE(0, 0);
+  {
+    // the scale tiles by LDS-DMA, gemm_a6w4_km_kernel's block (gemm_fp4_glds_kernel's `if (km)`): a group's scales of the tile are
+    // 4 BM (4 BN) contiguous bytes = one row of lsa (lsw); 256 / BM groups per activation piece, two per weight piece, a last
+    // piece's surplus groups re-read the last one (their LDS rows are the padding up to Gp); rows clamped to the image's last four.
+    // The main loop's first vmcnt(0) covers them - the compiler has issued no load of its own that it would have to wait for.
+    constexpr int APG = 256 / BM, LPG_A = BM / 4;
+    const int Tpad = (T + 3) & ~3, n_a = (G + APG - 1) / APG, n_w = (G + 1) >> 1;
+    for (int p = wave; p < n_a + n_w; p += 4) {
+      const bool is_a = p < n_a;
+      const int g0 = is_a ? p * APG : (p - n_a) * 2;
+      const int sub = is_a ? lane / LPG_A : lane >> 5, l4 = is_a ? lane % LPG_A : lane & 31;
+      const int grp = g0 + sub < G ? g0 + sub : G - 1;
+      const int rows = is_a ? Tpad : epi.km_w_rows, r0 = is_a ? t0 : o0;
+      int r4 = r0 + 4 * l4;
+      r4 = r4 < rows - 4 ? r4 : rows - 4;
+      const uint32_t vo = (uint32_t)(((grp - g0) * rows + (r4 - r0)) * 4);
+      const float* sbase = (is_a ? sa : sw) + ((int64_t)g0 * rows + r0);
+      const uint32_t dst = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(is_a ? lsa + g0 * BM : lsw + g0 * BN);
+      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(vo), "s"(sbase), "s"(dst) : "m0");
+    }
+  }
+#else
   const uint8_t* const a_base_g = A + (int64_t)t0 * a_row_bytes;
   const uint8_t* const w_base_g = W + (int64_t)o0 * w_row_bytes;
   uint32_t voff[PIECES];
@@ -90,6 +164,7 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
   FPQ_W6_ISSUE(0, 0);
   load_scale_tiles<Tsw, BM, BN, NTHR>(sa, sw, lsa, lsw, t0, o0, T, O, G, tid);
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), the builtin: the compiler's scoreboard forgets the scale loads (gemm_fp4_glds_kernel)
+#endif
 #if FPQ_W6_FC1
   // the dual quantizer's bucket table, behind the scale tiles; visible after the first barrier of the main loop
   uint16_t* lut = (uint16_t*)(lsw + Gp * BN);
@@ -207,6 +282,7 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
   }
 #undef FPQ_W6_READ_A
 #undef FPQ_W6_ISSUE
+#undef FPQ_W6_TSA
 
   // epilogue from the registers, as gemm_a6w4_kernel's: + bias, one rounding to fp16, then the form's own tail, 8-byte stores
 #if FPQ_W6_FC1 || FPQ_W6_OUT != 2

@@ -150,8 +150,8 @@ _FORMATS = {
     "e1m2": _Format(96, "fpq_gemm_a6w4", "", (TABLE_IDS["e1m2"],), "fpq_quant_rows_codes_g6", "fpq_a6w4_quant_rows_codes_km", "quantize_g6", 8, True),
     "e3m0": _Format(96, "fpq_gemm_a6w4", "", (TABLE_IDS["e3m0"],), "fpq_quant_rows_codes_g6", "fpq_a6w4_quant_rows_codes_km", "quantize_g6", 8, True),
 }
-# E1M2 / E3M0 WEIGHTS as 6-bit codes (fpq_gemm_w6_mx, _gelu_dual, _mx_split, _mx_split_qknorm; row-major only, fp32 weight scales
-# only): a row per (activation, weight) pair
+# E1M2 / E3M0 WEIGHTS as 6-bit codes (fpq_gemm_w6_mx, _gelu_dual, _mx_split, _mx_split_qknorm, each with a _km twin for k-major
+# images; fp32 weight scales only): a row per (activation, weight) pair
 _W6_FORMATS = {(a, w): _FORMATS[a]._replace(gemm="fpq_gemm_w6", plain="", table=(TABLE_IDS[a],), bias_align=8, split_w_f32=True, w_seg=96,
                                             w_table=(TABLE_IDS[w],))
                for a in ("e2m1", "e1m2", "e3m0") for w in ("e1m2", "e3m0")}
@@ -282,15 +282,16 @@ def _per_group_operands(name: str, fmt: _Format, a, a_scales, w, w_scales, bias,
     `outs` (or the bias) only matters for images, see _check_kmajor_fp4."""
     a_rank, w_rank = a.dim(), w.dim()
     km = a_rank == 3 and w_rank == 3
-    if fmt.w_seg != 64 and (a_rank != 2 or w_rank != 2):
-        raise RuntimeError(f"{name}: row-major operands only (a 6-bit weight has no k-major form)")
+    if fmt.w_seg != 64 and layouts != "images" and (a_rank != 2 or w_rank != 2):
+        raise RuntimeError(f"{name}: row-major operands only (k-major images of a 6-bit weight: the _km functions)")
     if layouts == "rows" and (a_rank != 2 or w_rank != 2):
         raise RuntimeError(f"{name}: row-major operands only (k-major images: {name}_km)")
     if layouts == "images" and not km:
         raise RuntimeError(f"{name}: both operands must be k-major images (3-D); row-major codes go to {name[:-3]}")
     if km:
-        if a.shape[2] != fmt.seg or w.shape[2] != 64 or a.shape[0] != w.shape[0] or w.shape[1] % 64 != 0:
-            shapes = "[K/128, rows, 64]" if fmt.seg == 64 else "[K/128, tokens, 96] (activation) and [K/128, rows, 64] (weight)"
+        if a.shape[2] != fmt.seg or w.shape[2] != fmt.w_seg or a.shape[0] != w.shape[0] or w.shape[1] % 64 != 0:
+            shapes = ("[K/128, rows, 64]" if fmt.seg == fmt.w_seg == 64 else
+                      f"[K/128, tokens, {fmt.seg}] (activation) and [K/128, rows, {fmt.w_seg}] (weight)")
             raise RuntimeError(f"{name}: k-major images must be {shapes} with the same K and a weight image of a multiple of 64 rows")
         return (True, *_check_kmajor_fp4(name, a, a_scales, w, w_scales, bias, outs))
     if a_rank != 2 or w_rank != 2:
@@ -307,9 +308,13 @@ def _per_group_operands(name: str, fmt: _Format, a, a_scales, w, w_scales, bias,
 def _per_group_gemm(form: str, fmt: _Format, km: bool, a, a_scales, w, w_scales, *rest) -> None:
     """One call of the family's C entry point of `form`: "" (plain, with the optional gate / residual tail), "gelu_dual" (fc1),
     "split" or "split_qknorm" (mat_qkv into the cache); rest: its arguments between the weight scales' dtype and the stream - or,
-    for the split forms, which take the layout as a flag, the k-major flag before it (the W6 family has no k-major form, and no flag)."""
+    for the split forms, which take the layout as a flag, the k-major flag before it (the W6 family has no flag: its split forms
+    have an entry point per layout too)."""
     if form in ("split", "split_qknorm"):
-        what, rest = f"{fmt.gemm}_mx_{form}", (*rest, 1 if km else 0) if fmt.w_seg == 64 else rest
+        if fmt.w_seg == 64:
+            what, rest = f"{fmt.gemm}_mx_{form}", (*rest, 1 if km else 0)
+        else:
+            what = f"{fmt.gemm}_mx_{form}_km" if km else f"{fmt.gemm}_mx_{form}"
     elif form:   # an entry point per layout
         what = f"{fmt.gemm}_{form}_km" if km else f"{fmt.gemm}_{form}"
     else:
@@ -334,7 +339,7 @@ def _bias_f16(name: str, bias: Optional[torch.Tensor], outs: Optional[int], devi
 
 
 def _linear(name: str, fmt, layouts: str, a, a_scales, w, w_scales, bias, gate, residual, outs, loose_bias: bool = False) -> torch.Tensor:
-    """The plain Linear with its optional gate / residual tail: linear_fp4, linear_a6w4, linear_a6w4_km, linear_w6"""
+    """The plain Linear with its optional gate / residual tail: linear_fp4, linear_a6w4, linear_a6w4_km, linear_w6, linear_w6_km"""
     require_gpu(a, name)
     if not isinstance(fmt, _Format):
         fmt = _g6_format(name, fmt)
@@ -352,7 +357,7 @@ def _linear(name: str, fmt, layouts: str, a, a_scales, w, w_scales, bias, gate, 
 
 def _linear_gelu_dual(name: str, fmt, layouts: str, a, a_scales, w, w_scales, bias, return_gelu: bool, outs):
     """fc1 with the GELU and the dual quantizer in the epilogue: linear_fp4_gelu_dual, linear_a6w4_gelu_dual, linear_a6w4_gelu_dual_km,
-    linear_w6_gelu_dual"""
+    linear_w6_gelu_dual, linear_w6_gelu_dual_km"""
     require_gpu(a, name)
     if not isinstance(fmt, _Format):
         fmt = _g6_format(name, fmt)
@@ -408,13 +413,15 @@ def _qkv_split_args(name: str, cache_kv: torch.Tensor, tokens: int, outs: int, b
     return q, sp, b, hs
 
 
-def _linear_qkv_to_cache(name: str, fmt, a, a_scales, w, w_scales, bias, cache_kv, pos: int, seq: int, qk_norm_scale) -> torch.Tensor:
-    """mat_qkv with q returned and k, v written into the cache: linear_fp4_qkv_to_cache, linear_a6w4_qkv_to_cache, linear_w6_qkv_to_cache"""
+def _linear_qkv_to_cache(name: str, fmt, a, a_scales, w, w_scales, bias, cache_kv, pos: int, seq: int, qk_norm_scale,
+                         layouts: str = "rank") -> torch.Tensor:
+    """mat_qkv with q returned and k, v written into the cache: linear_fp4_qkv_to_cache, linear_a6w4_qkv_to_cache, linear_w6_qkv_to_cache,
+    linear_w6_qkv_to_cache_km"""
     require_gpu(a, name)
     if not isinstance(fmt, _Format):
         fmt = _g6_format(name, fmt)
     _check_cache_kv(name, cache_kv, a.device)
-    km, tokens, outs, k = _per_group_operands(name, fmt, a, a_scales, w, w_scales, None, 3 * cache_kv.shape[3] * cache_kv.shape[4])
+    km, tokens, outs, k = _per_group_operands(name, fmt, a, a_scales, w, w_scales, None, 3 * cache_kv.shape[3] * cache_kv.shape[4], layouts)
     if fmt.split_w_f32 and w_scales.dtype != torch.float32:
         raise RuntimeError(f"{name}: the weight scales must be float32, got {w_scales.dtype}")
     q, sp, b, hs = _qkv_split_args(name, cache_kv, tokens, outs, bias, pos, seq, qk_norm_scale)
@@ -530,7 +537,8 @@ def linear_w6(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_cod
     """fp16 [tokens, outs] = dequantize(a) @ dequantize_g6(w, w_table).T + bias on the matrix cores (fpq_gemm_w6_mx): an E1M2 / E3M0
     WEIGHT as the dense 6-bit codes and fp32 group scales of `quantize_g6(weight.float(), w_table)`, against an activation in any of
     the three FP4 formats - a_table "e2m1": the nibbles and fp16 scales of quantize_mx; "e1m2" / "e3m0": the 6-bit codes of quantize_g6.
-    Row-major operands only.  gate / residual: the AdaLN block's tail as in linear_fp4.  outs: the weight's row count, when given."""
+    Row-major operands only (k-major images: linear_w6_km).  gate / residual: the AdaLN block's tail as in linear_fp4.  outs: the
+    weight's row count, when given."""
     require_gpu(a_codes, "linear_w6")
     fmt = _w6_format("linear_w6", a_table, w_table, w_scales)
     if outs is not None and w_codes.dim() == 2 and outs != w_codes.shape[0]:
@@ -551,8 +559,8 @@ def linear_w6_gelu_dual(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: 
                         bias: Optional[torch.Tensor] = None, return_gelu: bool = False):
     """linear_a6w4_gelu_dual for a 6-bit WEIGHT (fpq_gemm_w6_gelu_dual): fc1 of the FFN up to fc2's GEMM in one launch (+ the NaN fix-up
     launch) - `fp_quant_e1m2_neg_e2m1_pos_per_group_cuda(F.gelu(linear_w6(a, a_table, w, w_table, bias), approximate="tanh"), 4, 128)` as
-    the epilogue of the W6 GEMM: fp16 [tokens, outs], outs % 128 == 0.  Operands as linear_w6 takes them: row-major only, float32
-    weight scales.  return_gelu: also the GELU values the quantizer saw - the same function of the fp16 Linear output as
+    the epilogue of the W6 GEMM: fp16 [tokens, outs], outs % 128 == 0.  Operands as linear_w6 takes them: row-major only (k-major
+    images: linear_w6_gelu_dual_km), float32 weight scales.  return_gelu: also the GELU values the quantizer saw - the same function of the fp16 Linear output as
     linear_fp4_gelu_dual's, bit for bit."""
     require_gpu(a_codes, "linear_w6_gelu_dual")
     fmt = _w6_format("linear_w6_gelu_dual", a_table, w_table, w_scales)
@@ -566,18 +574,54 @@ def linear_w6_qkv_to_cache(a_codes: torch.Tensor, a_scales: torch.Tensor, a_tabl
     whose weight format is E1M2 / E3M0 - `qkv = linear_w6(a, a_table, w, w_table, bias)` for tokens [B * seq] and outs = 3 * C, but only
     q comes back, fp16 [B, seq, C], while k and v are written straight into `cache_kv` [2, B, max_len, H, c] at token positions
     pos .. pos + seq, bit for bit what the plain GEMM and the cache's copy-in leave there.  Operands as linear_w6 takes them: row-major
-    only, float32 weight scales.  qk_norm_scale, and the fp32 bias that goes with it: as in linear_fp4_qkv_to_cache."""
+    only (k-major images: linear_w6_qkv_to_cache_km), float32 weight scales.  qk_norm_scale, and the fp32 bias that goes with it: as in
+    linear_fp4_qkv_to_cache."""
     require_gpu(a_codes, "linear_w6_qkv_to_cache")
     fmt = _w6_format("linear_w6_qkv_to_cache", a_table, w_table, w_scales)
     return _linear_qkv_to_cache("linear_w6_qkv_to_cache", fmt, a_codes, a_scales, w_codes, w_scales, bias, cache_kv, pos, seq, qk_norm_scale)
+
+
+def linear_w6_km(a_image: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_image: torch.Tensor, w_scales: torch.Tensor, w_table: str,
+                 bias: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                 outs: Optional[int] = None) -> torch.Tensor:
+    """linear_w6 on k-major images (fpq_gemm_w6_mx_km), bit for bit the same result: the activation as the `kmajor=True` quantizer of
+    its format emits it - a_table "e2m1": `quantize_mx(x, kmajor=True)`, codes [K/128, tokens, 64]; "e1m2" / "e3m0": `quantize_g6(x, table,
+    kmajor=True)`, codes [K/128, tokens, 96]; scales fp32 [K/128, tokens rounded up to 4] in all three - and the weight as
+    `to_kmajor(codes, 6, dealt=True)` [K/128, outs rounded up to 64, 96] with `to_kmajor_scales(scales, weight_side=True)` of
+    `quantize_g6(weight.float(), w_table)`.  outs: the Linear's width when it is neither the bias's length nor the weight image's row
+    count (a multiple of 64), as in linear_fp4."""
+    require_gpu(a_image, "linear_w6_km")
+    fmt = _w6_format("linear_w6_km", a_table, w_table, w_scales)
+    return _linear("linear_w6_km", fmt, "images", a_image, a_scales, w_image, w_scales, bias, gate, residual, outs)
+
+
+def linear_w6_gelu_dual_km(a_image: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_image: torch.Tensor, w_scales: torch.Tensor,
+                           w_table: str, bias: Optional[torch.Tensor] = None, return_gelu: bool = False, outs: Optional[int] = None):
+    """linear_w6_gelu_dual on k-major images (fpq_gemm_w6_gelu_dual_km), bit for bit the same result; operands as in linear_w6_km,
+    return_gelu as in linear_w6_gelu_dual."""
+    require_gpu(a_image, "linear_w6_gelu_dual_km")
+    fmt = _w6_format("linear_w6_gelu_dual_km", a_table, w_table, w_scales)
+    return _linear_gelu_dual("linear_w6_gelu_dual_km", fmt, "images", a_image, a_scales, w_image, w_scales, bias, return_gelu, outs)
+
+
+def linear_w6_qkv_to_cache_km(a_image: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_image: torch.Tensor, w_scales: torch.Tensor,
+                              w_table: str, bias: Optional[torch.Tensor], cache_kv: torch.Tensor, pos: int, seq: int,
+                              qk_norm_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """linear_w6_qkv_to_cache on k-major images (fpq_gemm_w6_mx_split_km / fpq_gemm_w6_mx_split_qknorm_km), bit for bit the same q and
+    cache entries; operands as in linear_w6_km (the width is the cache's: 3 * H * c, whose weight image has exactly that many rows)."""
+    require_gpu(a_image, "linear_w6_qkv_to_cache_km")
+    fmt = _w6_format("linear_w6_qkv_to_cache_km", a_table, w_table, w_scales)
+    return _linear_qkv_to_cache("linear_w6_qkv_to_cache_km", fmt, a_image, a_scales, w_image, w_scales, bias, cache_kv, pos, seq,
+                                qk_norm_scale, "images")
 
 
 # form -> the public function for E2M1 operands, for 6-bit row-major codes and for 6-bit k-major images
 _FORMS = {"plain": (linear_fp4, linear_a6w4, linear_a6w4_km),
           "gelu_dual": (linear_fp4_gelu_dual, linear_a6w4_gelu_dual, linear_a6w4_gelu_dual_km),
           "qkv_to_cache": (linear_fp4_qkv_to_cache, linear_a6w4_qkv_to_cache, linear_a6w4_qkv_to_cache)}
-# form -> the public function for a 6-bit weight (row-major; the forms beside "plain" need the module's w6_forms)
-_W6_FORMS = {"plain": linear_w6, "gelu_dual": linear_w6_gelu_dual, "qkv_to_cache": linear_w6_qkv_to_cache}
+# form -> the public function for a 6-bit weight, row-major and on k-major images (the forms beside "plain" need the module's w6_forms)
+_W6_FORMS = {"plain": (linear_w6, linear_w6_km), "gelu_dual": (linear_w6_gelu_dual, linear_w6_gelu_dual_km),
+             "qkv_to_cache": (linear_w6_qkv_to_cache, linear_w6_qkv_to_cache_km)}
 
 
 class FP4Linear(_ScaledOperandModule):
@@ -606,7 +650,7 @@ class FP4Linear(_ScaledOperandModule):
 
     @classmethod
     def from_float(cls, module: torch.nn.Linear, kmajor: bool = False, act_fp_type: str = "fp_e2", a6w4_kmajor: bool = False,
-                   weight_fp_type: str = "fp_e2", w6_forms: bool = False):
+                   weight_fp_type: str = "fp_e2", w6_forms: bool = False, w6_kmajor: bool = False):
         """act_fp_type: the activation's per-group format - "fp_e2" (E2M1, the FP4 GEMM) or "fp_e1" / "fp_e3" (E1M2 / E3M0: the
         A6W4 GEMM on the same stored weight - row-major unless a6w4_kmajor, which lets kmajor=True hold the FP4 GEMM's k-major
         weight images for it and run quantize_g6(kmajor=True) + linear_a6w4_km).
@@ -615,19 +659,27 @@ class FP4Linear(_ScaledOperandModule):
         activation formats (an E2M1 activation as quantize_mx's row-major nibbles).  Row-major, plain form only: kmajor /
         a6w4_kmajor, qkv_to_cache* and FP4LinearGeluDual raise ValueError.
         w6_forms (with a 6-bit weight; an E2M1 weight ignores it): the module also runs the W6 GEMM's fc1 tail and split output -
-        FP4LinearGeluDual constructs (linear_w6_gelu_dual) and qkv_to_cache* work (linear_w6_qkv_to_cache).  Still row-major only:
-        kmajor / a6w4_kmajor raise as before."""
+        FP4LinearGeluDual constructs (linear_w6_gelu_dual) and qkv_to_cache* work (linear_w6_qkv_to_cache).  Row-major unless
+        w6_kmajor: kmajor / a6w4_kmajor raise as before.
+        w6_kmajor (with a 6-bit weight and kmajor=True; alone it changes nothing, and an E2M1 weight ignores it): the module holds the
+        dealt 6-bit weight image `to_kmajor(codes, 6, dealt=True)` and `to_kmajor_scales(scales, weight_side=True)`, quantizes its
+        activation with the kmajor=True quantizer of its format and runs the W6 GEMM's k-major forms (linear_w6_km,
+        linear_w6_gelu_dual_km, linear_w6_qkv_to_cache_km) - the same bits as the row-major module."""
         assert isinstance(module, torch.nn.Linear) and module.in_features % 128 == 0 and module.out_features % 8 == 0
         if weight_fp_type not in ("fp_e2", "e2m1"):
             w_table = _G6_TABLES.get(weight_fp_type) if isinstance(weight_fp_type, str) else None
             if w_table is None:
                 raise ValueError(f"FP4Linear.from_float: weight_fp_type must be 'fp_e2', 'fp_e1' or 'fp_e3', got {weight_fp_type!r}")
-            if kmajor or a6w4_kmajor:
-                raise ValueError(f"FP4Linear.from_float: weight_fp_type={weight_fp_type!r} runs on the W6 GEMM, which has no k-major form")
+            km6 = bool(kmajor and w6_kmajor)
+            if (kmajor or a6w4_kmajor) and not km6:
+                raise ValueError(f"FP4Linear.from_float: weight_fp_type={weight_fp_type!r} runs on the W6 GEMM, which has no k-major form "
+                                 "unless w6_kmajor=True asks for it (together with kmajor=True)")
             if issubclass(cls, FP4LinearGeluDual) and not w6_forms:
                 raise ValueError(f"FP4LinearGeluDual.from_float: weight_fp_type={weight_fp_type!r} runs on the W6 GEMM, which has no fc1 tail")
             act_table = "e2m1" if act_fp_type in ("fp_e2", "e2m1") else _g6_table("FP4Linear.from_float", act_fp_type)
             codes, scales = quantize_g6(module.weight.detach().float(), w_table)
+            if km6:
+                codes, scales = to_kmajor(codes, 6, dealt=True), to_kmajor_scales(scales, weight_side=True)
             bias = None if module.bias is None else module.bias.detach().to(torch.float16)
             return cls(codes, scales, bias, module.in_features, module.out_features, act_table, w_table, w6_forms=w6_forms)
         if act_fp_type in ("fp_e2", "e2m1"):
@@ -660,11 +712,15 @@ class FP4Linear(_ScaledOperandModule):
             table = "e2m1"
         else:
             table = _g6_table(f"{type(self).__name__}.forward_operands", table)
-        if self.w_table != "e2m1":   # a 6-bit weight: the W6 GEMM, row-major; the forms beside the plain one with w6_forms only
+        if self.w_table != "e2m1":   # a 6-bit weight: the W6 GEMM, in the weight's layout; the forms beside the plain one with w6_forms only
             if form != "plain" and not self.w6_forms:
                 raise ValueError(f"{type(self).__name__}: a {self.w_table} weight runs on the W6 GEMM, which has the plain form only "
                                  f"(no {form} form)")
-            return _W6_FORMS[form](a_codes, a_scales, table, self.w_codes, self.w_scales, self.w_table, *rest)
+            rows, images = _W6_FORMS[form]
+            if not self.kmajor:
+                return rows(a_codes, a_scales, table, self.w_codes, self.w_scales, self.w_table, *rest)
+            outs = () if form == "qkv_to_cache" else (self.out_features,)
+            return images(a_codes, a_scales, table, self.w_codes, self.w_scales, self.w_table, *rest, *outs)
         fp4, rows, images = _FORMS[form]
         outs = () if form == "qkv_to_cache" else (self.out_features,)   # the last argument; mat_qkv's width is the cache's
         if table == "e2m1":   # the public functions: they hand the call to the compiled binding when it is loaded
@@ -756,7 +812,7 @@ class FP4LinearGeluDual(FP4Linear):
     the FFN's `act` for an identity and switches fc2's input quantizer off).  With an E1M2 / E3M0 activation format
     (`from_float(..., act_fp_type="fp_e1" / "fp_e3")`; row-major, or k-major with `a6w4_kmajor=True`) the same tail runs in the A6W4
     GEMM (`linear_a6w4_gelu_dual` / `linear_a6w4_gelu_dual_km`), and with an E1M2 / E3M0 weight format and `w6_forms=True` in the W6 GEMM
-    (`linear_w6_gelu_dual`, row-major)."""
+    (`linear_w6_gelu_dual`; `linear_w6_gelu_dual_km` with `kmajor=True, w6_kmajor=True`)."""
 
     @torch.no_grad()
     def forward(self, x):

@@ -268,7 +268,7 @@ _FP6_SYMMETRIC = ("fp6_e2m3", "fp6_e3m2")
 def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, w_bit=8, a_bit=8, act_quant_sym=None,
                        fc2_act_log2_quant=None, activation_fp_quant=False, weight_fp_quant=False,
                        ada_lin_formats=None, real_fp6=False, kmajor_operands=True, real_fp4=False, fuse_ffn=False, a6w4_kmajor=False,
-                       w6_weights=False, w6_forms=False):
+                       w6_weights=False, w6_forms=False, w6_kmajor=False):
     """quantize_VAR with a format pair per (block, layer): ``layer_formats(block_idx, layer)`` returns
     ``(act_fp_type, weight_fp_type)`` for layer in {"fc1", "fc2", "mat_qkv", "proj"}.  ``ada_lin_formats``:
     None leaves the AdaLN Linear in full precision (as tr/ does), a pair quantizes ``ada_lin[1]`` (as the fq/ and
@@ -287,7 +287,7 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
 
     ``w6_weights`` (additive, default off; with ``real_fp4``, else ValueError): fc1, mat_qkv and proj with an ``fp_e1`` / ``fp_e3``
     WEIGHT and an ``fp_e1`` / ``fp_e2`` / ``fp_e3`` activation whose shape fits the GEMM become a ``gemm.FP4Linear`` of that pair too -
-    the weight as 6-bit codes on the W6 GEMM (``gemm.linear_w6``; row-major, whatever ``kmajor_operands`` / ``a6w4_kmajor`` say).
+    the weight as 6-bit codes on the W6 GEMM (``gemm.linear_w6``; row-major, whatever ``kmajor_operands`` / ``a6w4_kmajor`` say, unless ``w6_kmajor``).
     All six pairs: each one's 128-term dot came out exact on the matrix core (profiles/w6_dot.txt), so none is left behind as a
     QuantizedLinear for its numerics.  fc2 and ``ada_lin[1]`` are as without the keyword; an FFN whose fc1 has such a weight has no
     in-GEMM tail without ``w6_forms``: with ``fuse_ffn`` it takes the one-pass ``GeluThenFc2Quant`` route, or raises as below.
@@ -296,8 +296,13 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
     ``w6_forms=True``, so a mat_qkv with a 6-bit weight has ``qkv_to_cache`` / ``qkv_to_cache_operands`` (the W6 GEMM's split output,
     q / k norm included), and with ``fuse_ffn`` an FFN whose fc1 has such a weight and meets the conditions below gets the in-GEMM tail
     too: fc1 becomes ``gemm.FP4LinearGeluDual`` on the W6 GEMM (``gemm.linear_w6_gelu_dual``), ``act`` an identity and fc2's input
-    quantizer is switched off - one launch where the ``GeluThenFc2Quant`` route takes three.  k-major operands remain unbuilt for a
-    6-bit weight.
+    quantizer is switched off - one launch where the ``GeluThenFc2Quant`` route takes three.  Row-major unless ``w6_kmajor``.
+
+    ``w6_kmajor`` (additive, default off; with ``w6_weights``, else ValueError; inert when ``kmajor_operands`` is off, as
+    ``a6w4_kmajor`` is): the 6-bit-weight fc1 / mat_qkv / proj are built with ``kmajor=True, w6_kmajor=True`` - they hold the dealt
+    6-bit weight image and the fp32 weight-side scale image, quantize their activation into the k-major images of its format and run
+    the W6 GEMM's k-major forms (``gemm.linear_w6_km``, ``linear_w6_gelu_dual_km``, ``linear_w6_qkv_to_cache_km``): the same bits.
+    With ``a6w4_kmajor`` as well, every matrix-core layer of a 3 x 3 model is on one layout.
 
     ``a6w4_kmajor`` (additive, default off; with ``real_fp4`` and ``kmajor_operands``): the ``fp_e1`` / ``fp_e3`` layers hold the FP4
     GEMM's k-major weight images too and run the A6W4 GEMM's k-major form (``gemm.linear_a6w4_km``) - one weight layout in the
@@ -322,7 +327,11 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
         raise ValueError("w6_weights needs real_fp4")
     if w6_forms and not w6_weights:
         raise ValueError("w6_forms needs w6_weights")
+    if w6_kmajor and not w6_weights:
+        raise ValueError("w6_kmajor needs w6_weights")
     w6_kw = {"w6_forms": True} if w6_forms else {}   # (passed only when on: the keyword list without it is today's)
+    if w6_kmajor and kmajor_operands:
+        w6_kw.update(kmajor=True, w6_kmajor=True)
     common = dict(weight_quant=weight_quant, act_quant=act_quant, w_bit=w_bit, a_bit=a_bit,
                   activation_fp_quant=activation_fp_quant, weight_fp_quant=weight_fp_quant)
 
@@ -365,7 +374,7 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
             if in_gemm:
                 from .gemm import FP4LinearGeluDual
                 if w6_tail:
-                    m.fc1 = FP4LinearGeluDual.from_float(fc1, act_fp_type=a, weight_fp_type=w, w6_forms=True)
+                    m.fc1 = FP4LinearGeluDual.from_float(fc1, act_fp_type=a, weight_fp_type=w, **w6_kw)
                 else:
                     m.fc1 = fp4_layer(FP4LinearGeluDual, fc1, a)
             else:
@@ -395,7 +404,7 @@ def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, qu
                                     a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                     activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
                                     weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True, fuse_ffn=False,
-                                    a6w4_kmajor=False, w6_weights=False, w6_forms=False):
+                                    a6w4_kmajor=False, w6_weights=False, w6_forms=False, w6_kmajor=False):
     """models_fp_quant/quant_utils.py:1256-1341: fc1 is E2M1 in blocks 6-20 and E3M0 elsewhere, mat_qkv E2M1 in
     blocks 0, 24, 25 and E3M0 elsewhere (activations; weights always E2M1); proj, fc2 and ada_lin[1] take the
     caller's formats.
@@ -403,7 +412,7 @@ def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, qu
     the E3M0 activations as 6-bit codes.  ``fuse_ffn``: as in quantize_VAR_mixed - with ``real_fp4`` and ``fc2_fp_type`` =
     ``fp_e1m2_neg_e2m1_pos`` every fc1 runs its GELU and fc2's input quantizer in its GEMM's epilogue.  ``a6w4_kmajor``: as in
     quantize_VAR_mixed - the E3M0-activation layers on k-major images too.  ``w6_weights``: as in quantize_VAR_mixed - a proj whose
-    ``weight_fp_type`` is ``fp_e1`` / ``fp_e3`` on the W6 GEMM; ``w6_forms``: passed through as well."""
+    ``weight_fp_type`` is ``fp_e1`` / ``fp_e3`` on the W6 GEMM; ``w6_forms`` / ``w6_kmajor``: passed through as well."""
     fc1_e2, qkv_e2 = set(range(6, 21)), {0, 24, 25}
 
     def fmt(b, layer):
@@ -418,20 +427,20 @@ def quantize_VAR_mixed_fp4_datatype(model, weight_quant=None, act_quant=None, qu
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
                               activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type),
                               real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn, a6w4_kmajor=a6w4_kmajor,
-                              w6_weights=w6_weights, w6_forms=w6_forms)
+                              w6_weights=w6_weights, w6_forms=w6_forms, w6_kmajor=w6_kmajor)
 
 
 def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,
                                         a_bit=8, kv_bit=8, act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None,
                                         activation_fp_quant=False, weight_fp_quant=False, act_fp_type=None,
                                         weight_fp_type=None, fc2_fp_type=None, real_fp4=False, kmajor_operands=True, fuse_ffn=False,
-                                        a6w4_kmajor=False, w6_weights=False, w6_forms=False):
+                                        a6w4_kmajor=False, w6_weights=False, w6_forms=False, w6_kmajor=False):
     """models_fp_quant_rotate/quant_utils.py:982-1066: as the mixed FP4 variant, with mat_qkv E2M1 in blocks 24, 25 only.
     ``real_fp4`` / ``kmajor_operands``: as in quantize_VAR_mixed - every E2M1-weight fc1 / mat_qkv / proj on the matrix cores,
     the E3M0 activations as 6-bit codes.  ``fuse_ffn``: as in quantize_VAR_mixed - with ``real_fp4`` and ``fc2_fp_type`` =
     ``fp_e1m2_neg_e2m1_pos`` every fc1 runs its GELU and fc2's input quantizer in its GEMM's epilogue.  ``a6w4_kmajor``: as in
     quantize_VAR_mixed - the E3M0-activation layers on k-major images too.  ``w6_weights``: as in quantize_VAR_mixed - a proj whose
-    ``weight_fp_type`` is ``fp_e1`` / ``fp_e3`` on the W6 GEMM; ``w6_forms``: passed through as well."""
+    ``weight_fp_type`` is ``fp_e1`` / ``fp_e3`` on the W6 GEMM; ``w6_forms`` / ``w6_kmajor``: passed through as well."""
     fc1_e2, qkv_e2 = set(range(6, 21)), {24, 25}
 
     def fmt(b, layer):
@@ -446,7 +455,7 @@ def quantize_VAR_use_different_datatype(model, weight_quant=None, act_quant=None
     return quantize_VAR_mixed(model, fmt, weight_quant, act_quant, w_bit, a_bit, act_quant_sym, fc2_act_log2_quant,
                               activation_fp_quant, weight_fp_quant, ada_lin_formats=(act_fp_type, weight_fp_type),
                               real_fp4=real_fp4, kmajor_operands=kmajor_operands, fuse_ffn=fuse_ffn, a6w4_kmajor=a6w4_kmajor,
-                              w6_weights=w6_weights, w6_forms=w6_forms)
+                              w6_weights=w6_weights, w6_forms=w6_forms, w6_kmajor=w6_kmajor)
 
 
 def quantize_VAR_mixed_fp6_datatype(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8,

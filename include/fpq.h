@@ -48,7 +48,8 @@ extern "C" {
                            (136 still: + FPQ_GEMM_CFG 40, the FP4 GEMM's deep-ring small-M tiling, and fpq_gemm_fp4_tiling - an addition that changes no
                                 existing entry point; a caller that wants the query looks the symbol up;
                                  + fpq_gemm_w6_mx, E1M2 / E3M0 WEIGHTS on the matrix cores as 6-bit codes against any FP4 activation format - again an
-                                addition only, and the number stays because tests/test_format_search_fused_host.py pins it: look the symbol up) */
+                                addition only, and the number stays because tests/test_format_search_fused_host.py pins it: look the symbol up;
+                                 + its fc1 tail and split output, and all four forms on k-major images (fpq_gemm_w6_*_km): additions again) */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -835,8 +836,8 @@ int fpq_gemm_a6w4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, 
  *             ONLY - the kernels are not compiled for fp16 weight scales (FPQ_F16 is FPQ_ERR_DTYPE, as in the A6W4 split forms).
  *   a_codes   of a_table: FPQ_E2M1 - nibbles [tokens, k / 2] as fpq_quant_rows_codes_mx writes them (cbsz = 4); FPQ_E1M2 / FPQ_E3M0 - 6-bit
  *             codes [tokens, 3 k / 4] as fpq_quant_rows_codes_g6 writes them (cbsz = 2 / 3); a_scales fp16 [tokens, k / 128] in all three.
- * Row-major operands only (there is no k-major form; the fc1 tail and the split output: fpq_gemm_w6_gelu_dual, fpq_gemm_w6_mx_split /
- * _split_qknorm below).
+ * Row-major operands here; the fc1 tail and the split output: fpq_gemm_w6_gelu_dual, fpq_gemm_w6_mx_split / _split_qknorm below; every
+ * form on k-major images: the _km twins behind them ("THE W6 GEMM ON K-MAJOR IMAGES").
  * Checks, in this order, before any launch (fpq_gemm_a6w4_mx's order): a_table, w_table (FPQ_ERR_TABLE); negative sizes (FPQ_ERR_ARG); the
  * epilogue descriptor (FPQ_ERR_ARG); w_scale_dtype other than FPQ_F32 (FPQ_ERR_DTYPE); shape (FPQ_ERR_SHAPE: k % 128, k > 8192, outs % 8,
  * tokens or outs above 2^31 - 1, an LDS image above 160 KiB); tokens == 0 or outs == 0 (FPQ_OK, nothing launched); then NULL pointers /
@@ -872,7 +873,8 @@ int fpq_gemm_w6_gelu_dual(const uint8_t* a_codes, const void* a_scales, int a_ta
  * SPLIT OUTPUT of fpq_gemm_fp4_mx_split, and with the Q / K L2 NORM above in that epilogue - fpq_gemm_a6w4_mx_split / _split_qknorm for
  * a 6-bit weight.  Without the norm every written value is bit for bit the one fpq_gemm_w6_mx writes at that (token, column); with it,
  * y16 is what it writes with bias == NULL and q, k, v follow "THE Q / K L2 NORM" (the arithmetic of fpq_gemm_fp4_mx_split_qknorm: q and k
- * within that section's bound, its non-finite rule, v bit for bit).  Row-major operands only: there is no kmajor argument.  split, bias,
+ * within that section's bound, its non-finite rule, v bit for bit).  Row-major operands: there is no kmajor argument (k-major images
+ * have entry points of their own, fpq_gemm_w6_mx_split_km / _split_qknorm_km below).  split, bias,
  * q_head_scale: the rules of fpq_gemm_a6w4_mx_split (whole batch entries; every destination 8-byte aligned).
  * Checks, in this order, before any launch: a_table, w_table (FPQ_ERR_TABLE); split == NULL [_qknorm: or n_parts != 3, q_head_scale NULL
  * or not 4-byte aligned, bias not 16-byte aligned] (FPQ_ERR_ARG); negative sizes (FPQ_ERR_ARG); the split descriptor (FPQ_ERR_ARG);
@@ -886,6 +888,36 @@ int fpq_gemm_w6_mx_split(const uint8_t* a_codes, const void* a_scales, int a_tab
 int fpq_gemm_w6_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
                                 int w_scale_dtype, int w_table, const float* bias, int64_t tokens, int64_t outs, int64_t k,
                                 const fpq_gemm_split_t* split, const float* q_head_scale, fpq_stream_t stream);
+
+/* THE W6 GEMM ON K-MAJOR IMAGES ("K-MAJOR OPERAND IMAGES" above): the four entry points above with every operand as the image the other
+ * matrix-core GEMMs run on by default - same arithmetic, same tilings, same results bit for bit as their row-major twins
+ * (tests/test_gpu_w6_km.py); the argument lists are the twins', so there is no kmajor flag on either.
+ *   a_image    of a_table: FPQ_E2M1 - the activation side's 4-bit image [k / 128][tokens][64], what fpq_quant_rows_codes_mx_km and the
+ *              *_mx_km producers write (fpq_gemm_fp4_mx_km's activation operand); FPQ_E1M2 / FPQ_E3M0 - the activation side's 6-bit image
+ *              [k / 128][tokens][96], what fpq_a6w4_quant_rows_codes_km and the A6W4 producers with kmajor = 1 write
+ *              (fpq_gemm_a6w4_mx_km's activation operand)
+ *   a_scales   the fp32 k-major scale image [k / 128][tokens rounded up to 4], padding 0, in all three formats
+ *   w_image    the dealt 6-bit image [k / 128][outs rounded up to 64][96]: fpq_codes_to_kmajor(code_bits = 6, dealt = 1) of
+ *              fpq_quant_rows_codes_g6's codes - the layout of fpq_gemm_fp6_rows_km's weight operand
+ *   w_scales   the fp32 weight-side scale image [k / 128][outs rounded up to 64]: fpq_scales_to_kmajor(weight_side = 1).  w_scale_dtype:
+ *              FPQ_F32 only
+ * bias, out, epilogue, gelu_out, nan_flag, split, q_head_scale: unchanged.  Checks: each row-major twin's, in its documented order, with
+ * the k-major rules where fpq_gemm_a6w4_mx_km has them - w_scale_dtype other than FPQ_F32 is FPQ_ERR_DTYPE as before; behind the shape
+ * rules, tokens or outs at or above 2^28 (FPQ_ERR_SHAPE: the scale images are addressed by 32-bit lane offsets); behind the empty-problem
+ * return (FPQ_OK), NULL pointers, then alignment (FPQ_ERR_ARG): both images 16 bytes (out, gelu_out, bias, nan_flag as in the twin) and
+ * BOTH scale images 16 bytes.  FPQ_VERSION is unchanged by these four: look the symbols up. */
+int fpq_gemm_w6_mx_km(const uint8_t* a_image, const void* a_scales, int a_table, const uint8_t* w_image, const void* w_scales,
+                      int w_scale_dtype, int w_table, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
+                      const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream);
+int fpq_gemm_w6_gelu_dual_km(const uint8_t* a_image, const void* a_scales, int a_table, const uint8_t* w_image, const void* w_scales,
+                             int w_scale_dtype, int w_table, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs,
+                             int64_t k, void* nan_flag, fpq_stream_t stream);
+int fpq_gemm_w6_mx_split_km(const uint8_t* a_image, const void* a_scales, int a_table, const uint8_t* w_image, const void* w_scales,
+                            int w_scale_dtype, int w_table, const void* bias, int64_t tokens, int64_t outs, int64_t k,
+                            const fpq_gemm_split_t* split, fpq_stream_t stream);
+int fpq_gemm_w6_mx_split_qknorm_km(const uint8_t* a_image, const void* a_scales, int a_table, const uint8_t* w_image, const void* w_scales,
+                                   int w_scale_dtype, int w_table, const float* bias, int64_t tokens, int64_t outs, int64_t k,
+                                   const fpq_gemm_split_t* split, const float* q_head_scale, fpq_stream_t stream);
 
 /* THE PRODUCERS IN FRONT OF THE A6W4 GEMM: the online rotation and the adaLN producer emitting its activation operands in one launch,
  * as fpq_rotate_quant_rows_codes_mx[_km] / fpq_adaln_rotate_quant_rows_codes_mx[_km] do for the FP4 GEMM - the activation never exists
