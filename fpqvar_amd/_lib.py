@@ -211,6 +211,16 @@ _SIGS = {
                                                            _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64,
                                                            _c.c_float, _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int,
                                                            _c.c_void_p]),
+    # per-group(128) quantization on the full FP6 tables to dense 6-bit codes (table, dtype, layout: arguments)
+    "fpq_gf6_quant_rows_codes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int,
+                                             _c.c_void_p]),
+    # the fc1 tail with its dual pair and the layout as arguments: the twin's list, then neg table, pos table, kmajor
+    "fpq_gemm_a6w4_gelu_dual_pair": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                                 _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                                 _c.c_void_p]),
+    "fpq_gemm_w6_gelu_dual_pair": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p,
+                                               _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int,
+                                               _c.c_int, _c.c_void_p]),
     "fpq_gemm_f6_rows":(_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
                                      _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_void_p]),
     "fpq_gemm_f6_rows_split": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,

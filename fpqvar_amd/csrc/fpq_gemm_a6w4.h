@@ -24,6 +24,8 @@
 // Each form also on K-MAJOR IMAGES (FPQ_A6W4_KM; include/fpq.h): gemm_a6w4_km_kernel, gemm_a6w4_fc1_km_kernel - the activation
 // side's 6-bit image, the FP4 GEMM's dealt weight image and both fp32 scale images, so that one stored k-major FP4 weight
 // serves both GEMMs as the row-major one does.  Same main loop, same epilogues, same bits.
+// gemm_a6w4_fc1x_kernel / gemm_a6w4_fc1x_km_kernel (FPQ_A6W4_FC1 == 2): the fc1 kernels with the tail of a dual pair that has no global
+// clamp (fpq_gemm_a6w4_gelu_dual_pair with INT- / E2M3+): a NaN stays out of its group's maxima.  The fc1 kernels themselves are untouched.
 // mat_qkv's two output forms (FPQ_A6W4_OUT; include/fpq.h, fpq_gemm_a6w4_mx_split / _split_qknorm), row-major and on k-major images:
 // gemm_a6w4_split_kernel / gemm_a6w4_split_km_kernel write the plain epilogue's values to the parts' own destinations,
 // gemm_a6w4_qkn_kernel / gemm_a6w4_qkn_km_kernel with the q / k L2 norm in front.  Only the register epilogue differs.  They are
@@ -41,6 +43,11 @@
 #include "fpq_gemm_a6w4_kernel.h"
 #undef FPQ_A6W4_KERNEL
 #undef FPQ_A6W4_FC1
+#define FPQ_A6W4_KERNEL gemm_a6w4_fc1x_kernel
+#define FPQ_A6W4_FC1 2
+#include "fpq_gemm_a6w4_kernel.h"
+#undef FPQ_A6W4_KERNEL
+#undef FPQ_A6W4_FC1
 #undef FPQ_A6W4_KM
 #define FPQ_A6W4_KM 1
 #define FPQ_A6W4_KERNEL gemm_a6w4_km_kernel
@@ -50,6 +57,11 @@
 #undef FPQ_A6W4_FC1
 #define FPQ_A6W4_KERNEL gemm_a6w4_fc1_km_kernel
 #define FPQ_A6W4_FC1 1
+#include "fpq_gemm_a6w4_kernel.h"
+#undef FPQ_A6W4_KERNEL
+#undef FPQ_A6W4_FC1
+#define FPQ_A6W4_KERNEL gemm_a6w4_fc1x_km_kernel
+#define FPQ_A6W4_FC1 2
 #include "fpq_gemm_a6w4_kernel.h"
 #undef FPQ_A6W4_KERNEL
 #undef FPQ_A6W4_FC1

@@ -1,7 +1,7 @@
 // fpq_gemm_a6w4_kernel.h - the text of the A6W4 GEMM kernel.  NOT a header of its own: fpq_gemm_a6w4.h includes it once per kernel
 // it defines, with
 //   FPQ_A6W4_KERNEL   the kernel's name
-//   FPQ_A6W4_FC1      0: the plain epilogue (+ gate / residual tail); 1: the fc1 tail (FPQ_GEMM_FC1_TAIL, fpq_gemm_fp4.h) - the kernel
+//   FPQ_A6W4_FC1      0: the plain epilogue (+ gate / residual tail); 1 / 2: the fc1 tail (FPQ_GEMM_FC1_TAIL, fpq_gemm_fp4.h; 2: its NaN-excluding form, FPQ_GEMM_FC1_TAIL_X) - the kernel
 //                     takes a GemmFc1 behind the GemmEpi and stages the dual quantizer's bucket table behind the scale tiles
 //   FPQ_A6W4_OUT      (FPQ_A6W4_FC1 == 0 only) 0: one [T, O] tensor; 1: the SPLIT OUTPUT of GemmEpi's sp_* fields (mat_qkv: q to its own
 //                     tensor, k and v into the KV cache's slots), the plain epilogue's values bit for bit, no gate / residual tail;
@@ -258,7 +258,11 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_A6W4_KERNEL(const uint8_t
   for (int n = 0; n < NT; ++n) b4[n] = (float)bias_h[n];
 #endif
 #if FPQ_A6W4_FC1
+#if FPQ_A6W4_FC1 == 2
+  FPQ_GEMM_FC1_TAIL_X(STAGE, true);   // the dual pair without a global clamp: a NaN stays out of the maxima
+#else
   FPQ_GEMM_FC1_TAIL(STAGE);   // (this form has no gate / residual tail: epi is not read)
+#endif
 #elif FPQ_A6W4_OUT
   // the split output, as gemm_fp4_glds_kernel stores it (same tile, same lane-to-output mapping: a lane's four values of row i are four
   // consecutive columns of one part, a token row's head of 64 columns is the 16 lanes of a DPP row); no gate / residual tail

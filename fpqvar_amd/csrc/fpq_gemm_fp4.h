@@ -407,6 +407,7 @@ struct GemmFc1 {
   Lut16Args a;           // the (e1m2_neg, e2m1_pos) bucket table's arguments ...
   Lut16Tab tab;          // ... and the table itself, by value (as the stand-alone quantizers take it)
 };
+struct GemmFc1X : GemmFc1 {};   // host side only: selects the kernels whose tail keeps a NaN out of the maxima (FPQ_GEMM_FC1_TAIL_X)
 
 // (the GELU itself - gelu_tanh_fast - lives in fpq_fast16.h: the stand-alone fused quantizer uses it too)
 
@@ -466,6 +467,11 @@ FPQ_NOPK __device__ __forceinline__ void pk_max_scatter_step(uint32_t* key, bool
   }
 }
 
+// a packed fp16 pair with its NaN halves cleared to +0 (vec_absmax16_dual's mask: 0xFFFF where |pattern| > 0x7C00)
+FPQ_NOPK __device__ __forceinline__ uint32_t pk_nan_to_zero16(uint32_t w) {
+  return w & ~pk_ashr_i16(pk_sub_u16(0x7C007C00u, w & 0x7FFF7FFFu), 15);
+}
+
 // one packed pair of quant_vec16<DUAL> (fpq_fast16.h): each half takes the reciprocal and the scale of its sign's side
 FPQ_NOPK __device__ __forceinline__ uint32_t quant_pair16_dual(uint32_t wk, const uint16_t* lut, int shift, float ih_n, uint32_t s2_n,
                                                                float ih_p, uint32_t s2_p) {
@@ -492,7 +498,12 @@ FPQ_NOPK __device__ __forceinline__ uint32_t quant_pair16_dual(uint32_t wk, cons
 //     highest first, then the position in `key`.
 //   * The NaN flag is raised with the builtin: atomicOr() is a header function without the kernels' target attribute - it would
 //     become a call.
-#define FPQ_GEMM_FC1_TAIL(STAGE_)                                                                                   \
+//   * NANX_ (a compile-time constant; the kernels with it are instantiations of their own): the dual pair has NO global clamp (INT- /
+//     E2M3+, fp6_quant_int_neg_e2m3_pos_per_group_cuda), so a NaN must stay out of its group's two maxima - vec_absmax16_dual's
+//     rule, "NaN belongs to neither" - instead of riding in the key as the largest value of its side: the NaN halves are cleared in
+//     the values the key is made of (never in hw, which is quantized and stored), three instructions per packed pair.
+#define FPQ_GEMM_FC1_TAIL(STAGE_) FPQ_GEMM_FC1_TAIL_X(STAGE_, false)
+#define FPQ_GEMM_FC1_TAIL_X(STAGE_, NANX_)                                                                          \
   do {                                                                                                              \
     uint32_t* xch = (uint32_t*)(smem + (G & 1) * (STAGE_));  /* [2 (wn)][BM]: packed (max|h| over h < 0) | (max h over h > 0) << 16 */ \
     u32x4* rsc = (u32x4*)(xch + 2 * BM);                     /* [BM]: {1 / s_neg, 1 / s_pos, s_neg x 2, s_pos x 2} */ \
@@ -507,7 +518,8 @@ FPQ_NOPK __device__ __forceinline__ uint32_t quant_pair16_dual(uint32_t wk, cons
         const uint32_t w0 = f2h2(g[0], g[1]), w1 = f2h2(g[2], g[3]);                                                \
         hw[m][i][0] = w0;                                                                                           \
         hw[m][i][1] = w1;                                                                                           \
-        const uint32_t un = pk_max_u16(w0, w1), sg = pk_max_i16(w0, w1) ^ 0x80008000u;                              \
+        const uint32_t k0 = (NANX_) ? pk_nan_to_zero16(w0) : w0, k1 = (NANX_) ? pk_nan_to_zero16(w1) : w1;          \
+        const uint32_t un = pk_max_u16(k0, k1), sg = pk_max_i16(k0, k1) ^ 0x80008000u;                              \
         key[4 * m + i] = pk_max_u16(__builtin_amdgcn_perm(sg, un, 0x05040100u), __builtin_amdgcn_perm(sg, un, 0x07060302u)); \
       }                                                                                                             \
       if (xe.h_out) {                                                                                               \

@@ -31,6 +31,8 @@
 //                         destinations;
 //   gemm_w6_qkn_kernel    the split output with the q / k L2 norm in front (fpq_gemm_w6_mx_split_qknorm).
 // Each for the same twelve (FA, FW, MT), fp32 weight scales: 48 kernels, none above 157 registers.
+//   gemm_w6_fc1x_kernel   (FPQ_W6_FC1 == 2; and gemm_w6_fc1x_km_kernel) the fc1 kernel with the tail of a dual pair that has no global clamp
+//                         (fpq_gemm_w6_gelu_dual_pair with INT- / E2M3+): a NaN stays out of its group's maxima
 // Each form also on K-MAJOR IMAGES (FPQ_W6_KM; include/fpq.h): gemm_w6_km_kernel, gemm_w6_fc1_km_kernel, gemm_w6_split_km_kernel,
 // gemm_w6_qkn_km_kernel, another 48 - the activation side's 4-bit (FA = 4) or 6-bit image, the dealt 6-bit weight image an FP6Linear
 // holds, and both fp32 scale images.  Only the LDS-DMA sources and the scale-tile load differ: same LDS image, same main loop, same
@@ -45,6 +47,13 @@
 #undef FPQ_W6_OUT
 #define FPQ_W6_KERNEL gemm_w6_fc1_kernel
 #define FPQ_W6_FC1 1
+#define FPQ_W6_OUT 0
+#include "fpq_gemm_w6_kernel.h"
+#undef FPQ_W6_KERNEL
+#undef FPQ_W6_FC1
+#undef FPQ_W6_OUT
+#define FPQ_W6_KERNEL gemm_w6_fc1x_kernel
+#define FPQ_W6_FC1 2
 #define FPQ_W6_OUT 0
 #include "fpq_gemm_w6_kernel.h"
 #undef FPQ_W6_KERNEL
@@ -75,6 +84,13 @@
 #undef FPQ_W6_OUT
 #define FPQ_W6_KERNEL gemm_w6_fc1_km_kernel
 #define FPQ_W6_FC1 1
+#define FPQ_W6_OUT 0
+#include "fpq_gemm_w6_kernel.h"
+#undef FPQ_W6_KERNEL
+#undef FPQ_W6_FC1
+#undef FPQ_W6_OUT
+#define FPQ_W6_KERNEL gemm_w6_fc1x_km_kernel
+#define FPQ_W6_FC1 2
 #define FPQ_W6_OUT 0
 #include "fpq_gemm_w6_kernel.h"
 #undef FPQ_W6_KERNEL

@@ -40,6 +40,10 @@ int launch_w6_form(const GemmCall& c, int a_table, int w_table, size_t lds, XE x
     if constexpr (__is_same(XE, GemmFc1)) {
       if (km) return gemm_launch(gemm_w6_fc1_km_kernel<float, MT, 4, FA, FW>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
       return gemm_launch(gemm_w6_fc1_kernel<float, MT, 4, FA, FW>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
+    } else if constexpr (__is_same(XE, GemmFc1X)) {   // the tail of a dual pair without a global clamp
+      const GemmFc1& x1 = xe;
+      if (km) return gemm_launch(gemm_w6_fc1x_km_kernel<float, MT, 4, FA, FW>, Cfg::BM, Cfg::BN, 256, lds, c, x1);
+      return gemm_launch(gemm_w6_fc1x_kernel<float, MT, 4, FA, FW>, Cfg::BM, Cfg::BN, 256, lds, c, x1);
     } else if constexpr (__is_same(XE, GemmQkNorm)) {
       if (km) return gemm_launch(gemm_w6_qkn_km_kernel<float, MT, 4, FA, FW>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
       return gemm_launch(gemm_w6_qkn_kernel<float, MT, 4, FA, FW>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
@@ -97,9 +101,14 @@ int gemm_w6_mx_impl(const uint8_t* a_codes, const void* a_scales, int a_table, c
 // fpq_gemm_a6w4_gelu_dual; km as there (outs % 128 == 0: the weight image has exactly outs rows)
 int gemm_w6_gelu_dual_impl(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
                            int w_scale_dtype, int w_table, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs,
-                           int64_t k, void* nan_flag, bool km, fpq_stream_t stream) {
+                           int64_t k, void* nan_flag, bool km, fpq_stream_t stream, int neg_table = FPQ_E1M2_NEG,
+                           int pos_table = FPQ_E2M1_POS) {
   if (!w6_tables(a_table, w_table)) return FPQ_ERR_TABLE;
-  const Lut16Host& dual = lut16_host(FPQ_E1M2_NEG, FPQ_E2M1_POS);   // host arithmetic only: the table travels in the kernel's arguments
+  // the tail's dual pair (fpq_gemm_w6_gelu_dual_pair): fc2's 4-bit format with the reference's global clamp (the NaN flag), or its
+  // 6-bit one, which has no clamp - the flag is not raised and nothing is zeroed
+  const bool fp6_pair = neg_table == FPQ_INT_NEG && pos_table == FPQ_E2M3_POS;
+  if (!fp6_pair && !(neg_table == FPQ_E1M2_NEG && pos_table == FPQ_E2M1_POS)) return FPQ_ERR_TABLE;
+  const Lut16Host& dual = lut16_host(neg_table, pos_table);   // host arithmetic only: the table travels in the kernel's arguments
   if (!dual.tab_valid) return FPQ_ERR_TABLE;
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   if (w_scale_dtype != FPQ_F32) return FPQ_ERR_DTYPE;   // the kernels exist for fp32 weight scales only (fpq_gemm_w6.h)
@@ -119,6 +128,7 @@ int gemm_w6_gelu_dual_impl(const uint8_t* a_codes, const void* a_scales, int a_t
   xe.a = dual.args;
   xe.tab = dual.tab;
   xe.h_out = (_Float16*)gelu_out;
+  if (fp6_pair) nan_flag = nullptr;
   xe.nan_flag = (uint32_t*)nan_flag;
   const int G = (int)(k / 128);
   const bool a4 = a_table == FPQ_E2M1;
@@ -126,9 +136,14 @@ int gemm_w6_gelu_dual_impl(const uint8_t* a_codes, const void* a_scales, int a_t
   if (int rc = gemm_epilogue(nullptr, &epi)) return rc;
   if (km) epi.km_w_rows = (int)outs;
   const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
-  const int rc = gemm_glds_tiling(tokens, outs, false, false) == 30
-                     ? launch_w6_form<2>(c, a_table, w_table, GemmW6Cfg<2, 4>::lds_fc1(G, a4, xe.a.shift), xe, km)
-                     : launch_w6_form<4>(c, a_table, w_table, GemmW6Cfg<4, 4>::lds_fc1(G, a4, xe.a.shift), xe, km);
+  auto run = [&](const auto& x) {   // (the table's size comes from the pair: 2^(16 - shift) entries behind the scale tiles)
+    return gemm_glds_tiling(tokens, outs, false, false) == 30
+               ? launch_w6_form<2>(c, a_table, w_table, GemmW6Cfg<2, 4>::lds_fc1(G, a4, x.a.shift), x, km)
+               : launch_w6_form<4>(c, a_table, w_table, GemmW6Cfg<4, 4>::lds_fc1(G, a4, x.a.shift), x, km);
+  };
+  GemmFc1X xx;
+  static_cast<GemmFc1&>(xx) = xe;
+  const int rc = fp6_pair ? run(xx) : run(xe);
   if (rc) return rc;
   return nan_flag ? fpq_internal_zero_if_flag(out, tokens * outs * 2, nan_flag, stream) : FPQ_OK;
 }
@@ -212,6 +227,13 @@ int fpq_gemm_w6_gelu_dual_km(const uint8_t* a_image, const void* a_scales, int a
                              int64_t k, void* nan_flag, fpq_stream_t stream) {
   return gemm_w6_gelu_dual_impl(a_image, a_scales, a_table, w_image, w_scales, w_scale_dtype, w_table, bias, out, gelu_out, tokens, outs, k,
                                 nan_flag, true, stream);
+}
+// the same with the tail's dual pair and the layout as arguments (include/fpq.h, GF6)
+int fpq_gemm_w6_gelu_dual_pair(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                               int w_scale_dtype, int w_table, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs,
+                               int64_t k, void* nan_flag, int neg_table, int pos_table, int kmajor, fpq_stream_t stream) {
+  return gemm_w6_gelu_dual_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, w_table, bias, out, gelu_out, tokens, outs, k,
+                                nan_flag, kmajor != 0, stream, neg_table, pos_table);
 }
 
 // mat_qkv on the W6 GEMM: the split output, and the q / k norm in that epilogue (include/fpq.h)

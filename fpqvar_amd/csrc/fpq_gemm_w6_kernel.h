@@ -1,7 +1,7 @@
 // fpq_gemm_w6_kernel.h - the text of the W6 GEMM kernel.  NOT a header of its own: fpq_gemm_w6.h includes it once per kernel it
 // defines, with
 //   FPQ_W6_KERNEL   the kernel's name
-//   FPQ_W6_FC1      0: the plain epilogue (+ gate / residual tail); 1: the fc1 tail (FPQ_GEMM_FC1_TAIL, fpq_gemm_fp4.h) - the kernel
+//   FPQ_W6_FC1      0: the plain epilogue (+ gate / residual tail); 1 / 2: the fc1 tail (FPQ_GEMM_FC1_TAIL, fpq_gemm_fp4.h; 2: its NaN-excluding form, FPQ_GEMM_FC1_TAIL_X) - the kernel
 //                   takes a GemmFc1 behind the GemmEpi and stages the dual quantizer's bucket table behind the scale tiles
 //   FPQ_W6_OUT      (FPQ_W6_FC1 == 0 only) 0: one [T, O] tensor; 1: the SPLIT OUTPUT of GemmEpi's sp_* fields (mat_qkv: q to its own
 //                   tensor, k and v into the KV cache's slots), the plain epilogue's values bit for bit, no gate / residual tail;
@@ -293,7 +293,11 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
 #if FPQ_W6_FC1
   // the maxima exchange goes into stage buffer G & 1, which the last K group does not read (and nothing was loaded into after
   // the group before it was read: the last issue fills buffer (G - 1) & 1); this form has no gate / residual tail: epi is not read
+#if FPQ_W6_FC1 == 2
+  FPQ_GEMM_FC1_TAIL_X(STAGE, true);   // the dual pair without a global clamp: a NaN stays out of the maxima
+#else
   FPQ_GEMM_FC1_TAIL(STAGE);
+#endif
 #elif FPQ_W6_OUT
   // the split output, as gemm_a6w4_split_kernel stores it (same tile, same lane-to-output mapping: a lane's four values of row i are
   // four consecutive columns of one part, a token row's head of 64 columns is the 16 lanes of a DPP row); no gate / residual tail

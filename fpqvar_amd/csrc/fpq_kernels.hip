@@ -1715,6 +1715,39 @@ int fpq_a6w4_quant_rows_codes_km(const void* x, uint8_t* image, void* scales, in
                 (uint32_t)rows, fast_div((uint32_t)(cols / 128)));
 }
 
+// per-group(128) quantization on the FULL FP6 tables (E2M3 / E3M2) to dense 6-bit codes, row-major or as the k-major images
+// (include/fpq.h).  No kernel of its own: the emitters of fpq_codes_g6.h take their table as data - the fast forms the bucket ->
+// code table (lut16_codes6: 1024 buckets for E2M3, inside what they stage), the generic form the closed form of make_fmt.
+int fpq_gf6_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id, int in_dtype,
+                             int kmajor, fpq_stream_t stream) {
+  if (table_id != FPQ_E2M3 && table_id != FPQ_E3M2) return FPQ_ERR_TABLE;
+  if (rows < 0 || cols < 0) return FPQ_ERR_ARG;
+  if (!is_f16_or_f32(in_dtype) || (kmajor && in_dtype != FPQ_F16)) return FPQ_ERR_DTYPE;   // fp32 rows as images: row-major + fpq_codes_to_kmajor
+  if (cols % 128 != 0 || (kmajor && !km_image_fits(rows, cols / 4 * 3))) return FPQ_ERR_SHAPE;
+  if (rows == 0 || cols == 0) return FPQ_OK;
+  if (!x || !codes || !scales) return FPQ_ERR_ARG;
+  if ((((uintptr_t)x | (uintptr_t)codes) & 15) != 0) return FPQ_ERR_ARG;
+  if (((uintptr_t)scales & (kmajor ? 15 : in_dtype == FPQ_F16 ? 1 : 3)) != 0) return FPQ_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (in_dtype == FPQ_F16) {
+    const Lut16Host& h = lut16_host(table_id, table_id);
+    if (!h.tab_valid) return FPQ_ERR_TABLE;
+    if (kmajor) {
+      const int64_t units = (rows + 15) / 16 * (cols / 128);
+      return launch(group6_km_emit16_kernel, grid_for(units, 16384), 0, st, x, codes, scales, h.args, lut16_codes6(table_id),
+                    (uint32_t)rows, fast_div((uint32_t)(cols / 128)));
+    }
+    const int64_t n_vec = rows * (cols / 8);
+    return launch(group6_emit16_kernel, grid_for(tiles_of(n_vec, 1), 16384), 0, st, x, codes, scales, n_vec, h.args,
+                  lut16_codes6(table_id));
+  }
+  const int64_t n_blk = rows * (cols / 32);
+  return with_bool(table_id == FPQ_E3M2, [&](auto bf6) {   // (the other table: E2M3)
+    return launch(group6_emit_kernel<float, bf6.value>, grid_for(tiles_of(n_blk, 1), 1 << 20), 0, st, x, codes, scales, n_blk,
+                  make_fmt(table_id));
+  });
+}
+
 int fpq_kv_pack(uint8_t* codes, void* scales, int kv_bit, int64_t batch, int64_t max_len, int64_t heads, int64_t head_dim, int64_t pos,
                 const void* new_k, const void* new_v, int64_t new_batch_pitch, int64_t new_token_pitch, int64_t n_new,
                 fpq_stream_t stream) {

@@ -143,12 +143,20 @@ class _Format(NamedTuple):
     split_w_f32: bool
     w_seg: int = 64            # bytes of weight codes per 128 elements: 64 = E2M1 nibbles, 96 = dense 6-bit codes (linear_w6)
     w_table: Tuple[int, ...] = ()   # the weight's table id, which follows the weight scales' dtype in a call of the W6 family
+    quant_table: Optional[Tuple[int, ...]] = None   # the quantizer's table id where it is not `table` (a full FP6 table: `table` names the decode)
+    quant_flag: bool = False   # the quantizer takes the layout as a flag before the stream (one entry point for both layouts)
 
 
 _FORMATS = {
     "e2m1": _Format(64, "fpq_gemm_fp4", "_ex", (), "fpq_quant_rows_codes_mx", "fpq_quant_rows_codes_mx_km", "quantize_mx", 16, False),
     "e1m2": _Format(96, "fpq_gemm_a6w4", "", (TABLE_IDS["e1m2"],), "fpq_quant_rows_codes_g6", "fpq_a6w4_quant_rows_codes_km", "quantize_g6", 8, True),
     "e3m0": _Format(96, "fpq_gemm_a6w4", "", (TABLE_IDS["e3m0"],), "fpq_quant_rows_codes_g6", "fpq_a6w4_quant_rows_codes_km", "quantize_g6", 8, True),
+    # the FULL FP6 tables per group (quantize_gf6; the Linears: linear_g6*): the A6W4 kernels decode any E2M3 codes under the selector
+    # id of E1M2 and any E3M2 codes under that of E3M0 (include/fpq.h, GF6), so the id that follows a_scales is the DECODE format's
+    "e2m3": _Format(96, "fpq_gemm_a6w4", "", (TABLE_IDS["e1m2"],), "fpq_gf6_quant_rows_codes", "fpq_gf6_quant_rows_codes", "quantize_gf6", 8, True,
+                    quant_table=(TABLE_IDS["e2m3"],), quant_flag=True),
+    "e3m2": _Format(96, "fpq_gemm_a6w4", "", (TABLE_IDS["e3m0"],), "fpq_gf6_quant_rows_codes", "fpq_gf6_quant_rows_codes", "quantize_gf6", 8, True,
+                    quant_table=(TABLE_IDS["e3m2"],), quant_flag=True),
 }
 # E1M2 / E3M0 WEIGHTS as 6-bit codes (fpq_gemm_w6_mx, _gelu_dual, _mx_split, _mx_split_qknorm, each with a _km twin for k-major
 # images; fp32 weight scales only): a row per (activation, weight) pair
@@ -192,8 +200,9 @@ def _quantize_per_group(name: str, fmt: Union[_Format, str], x: torch.Tensor, km
     scales = kmajor_mx_scales(rows, k, dev) if kmajor else torch.empty((rows, k // 128), dtype=x.dtype, device=dev)
     what = fmt.quant_km if kmajor else fmt.quant
     with device_guard(dev):
-        check(getattr(lib(), what)(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, k, *fmt.table, dtype_id(x.dtype),
-                                   stream_ptr(dev)), what)
+        check(getattr(lib(), what)(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, k,
+                                   *(fmt.table if fmt.quant_table is None else fmt.quant_table), dtype_id(x.dtype),
+                                   *((1 if kmajor else 0,) if fmt.quant_flag else ()), stream_ptr(dev)), what)
     return codes, scales
 
 
@@ -315,6 +324,8 @@ def _per_group_gemm(form: str, fmt: _Format, km: bool, a, a_scales, w, w_scales,
             what, rest = f"{fmt.gemm}_mx_{form}", (*rest, 1 if km else 0)
         else:
             what = f"{fmt.gemm}_mx_{form}_km" if km else f"{fmt.gemm}_mx_{form}"
+    elif form == "gelu_dual_pair":   # the fc1 tail with its dual pair as an argument: one entry point, the layout a flag behind the pair
+        what, rest = f"{fmt.gemm}_gelu_dual_pair", (*rest, 1 if km else 0)
     elif form:   # an entry point per layout
         what = f"{fmt.gemm}_{form}_km" if km else f"{fmt.gemm}_{form}"
     else:
@@ -355,9 +366,10 @@ def _linear(name: str, fmt, layouts: str, a, a_scales, w, w_scales, bias, gate, 
     return out
 
 
-def _linear_gelu_dual(name: str, fmt, layouts: str, a, a_scales, w, w_scales, bias, return_gelu: bool, outs):
+def _linear_gelu_dual(name: str, fmt, layouts: str, a, a_scales, w, w_scales, bias, return_gelu: bool, outs,
+                      pair: Optional[Tuple[int, int]] = None):
     """fc1 with the GELU and the dual quantizer in the epilogue: linear_fp4_gelu_dual, linear_a6w4_gelu_dual, linear_a6w4_gelu_dual_km,
-    linear_w6_gelu_dual, linear_w6_gelu_dual_km"""
+    linear_w6_gelu_dual, linear_w6_gelu_dual_km; with `pair` (the dual quantizer's table ids) linear_g6_gelu_dual"""
     require_gpu(a, name)
     if not isinstance(fmt, _Format):
         fmt = _g6_format(name, fmt)
@@ -371,8 +383,9 @@ def _linear_gelu_dual(name: str, fmt, layouts: str, a, a_scales, w, w_scales, bi
     if tokens and outs:
         with device_guard(dev):
             flag = ops._nan_scratch(dev)
-        _per_group_gemm("gelu_dual", fmt, km, a, a_scales, w, w_scales, None if b is None else b.data_ptr(), out.data_ptr(),
-                        None if h is None else h.data_ptr(), tokens, outs, k, flag.data_ptr())
+        _per_group_gemm("gelu_dual" if pair is None else "gelu_dual_pair", fmt, km, a, a_scales, w, w_scales,
+                        None if b is None else b.data_ptr(), out.data_ptr(), None if h is None else h.data_ptr(), tokens, outs, k,
+                        flag.data_ptr(), *(pair or ()))
     return (out, h) if return_gelu else out
 
 
@@ -823,6 +836,233 @@ class FP4LinearGeluDual(FP4Linear):
     def forward_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor, table: Optional[str] = None) -> torch.Tensor:
         """table: the format the codes are in (default: the module's activation format), as in FP4Linear.forward_operands"""
         self._no_w6("forward_operands")
+        return self._run("gelu_dual", table, a_codes, a_scales, self.bias, False)
+
+
+# ---- GF6: full-range FP6 (E2M3 / E3M2) operands with per-group scales - the reference's per-group W6A6, W4A6 and W6A4 ---------
+# No GEMM of its own (include/fpq.h, GF6): the A6W4 and W6 kernels decode ANY E2M3 codes under the selector id of E1M2 and any E3M2
+# codes under that of E3M0, so a pair with a full FP6 side is a row whose table ids name the hardware decode.  `linear_g6*` accept
+# every pair with at least one e2m3 / e3m2 side and route to the A6W4 family when the weight is E2M1 and to the W6 family
+# otherwise; quantize_g6, linear_a6w4* and linear_w6* keep refusing the full tables.
+_GF6_TABLES = {"e2m3": "e2m3", "fp6_e2m3": "e2m3", "e3m2": "e3m2", "fp6_e3m2": "e3m2", "e2m1": "e2m1", "fp_e2": "e2m1",
+               "e1m2": "e1m2", "fp_e1": "e1m2", "e3m0": "e3m0", "fp_e3": "e3m0"}
+_GF6_FULL = ("e2m3", "e3m2")
+_GF6_DECODE = {"e2m1": "e2m1", "e1m2": "e1m2", "e3m0": "e3m0", "e2m3": "e1m2", "e3m2": "e3m0"}   # the selector id's table
+_GF6_CODE_FORMAT = {"e1m2": "e2m3", "e3m0": "e3m2", "e2m3": "e2m3", "e3m2": "e3m2"}             # the 6-bit format the codes are in
+# a row per (activation, weight) pair with a 6-bit weight and at least one full FP6 side (fpq_gemm_w6_*; fp32 weight scales only);
+# the pairs with an E2M1 weight are the rows "e2m3" / "e3m2" of _FORMATS (fpq_gemm_a6w4_*)
+_GF6_W6_FORMATS = {(a, w): _FORMATS[a]._replace(gemm="fpq_gemm_w6", plain="", table=(TABLE_IDS[_GF6_DECODE[a]],), bias_align=8, split_w_f32=True,
+                                                w_seg=96, w_table=(TABLE_IDS[_GF6_DECODE[w]],))
+                   for a in ("e2m1", "e1m2", "e3m0", "e2m3", "e3m2") for w in ("e1m2", "e3m0", "e2m3", "e3m2")
+                   if a in _GF6_FULL or w in _GF6_FULL}
+# the fc1 tail's dual pair -> (neg table id, pos table id): fc2's per-group input format - the 6-bit configuration's INT- / E2M3+ (no
+# global clamp: a NaN stays in its group; kernels of their own) or the 4-bit E1M2- / E2M1+ of the mixed W4A6 / W6A4 models
+_GF6_FC2_PAIRS = {("int_neg", "e2m3_pos"): (TABLE_IDS["int_neg"], TABLE_IDS["e2m3_pos"]),
+                  ("e1m2_neg", "e2m1_pos"): (TABLE_IDS["e1m2_neg"], TABLE_IDS["e2m1_pos"])}
+# Pairs linear_g6* refuse for their numerics: both operands decoded as BF6 E3M2 with a full-range side.  The matrix core does not keep
+# every product of such a dot (profiles/gf6_dot.txt) and over the shape sweep the error reaches 290 - 660 x the GEMM bound, far past
+# the 8 x the project grants E3M2 levels on this instruction (profiles/gf6_gemm_bound.txt).  They stay fake-quantized layers.
+GF6_REFUSED_PAIRS = frozenset({("e3m0", "e3m2"), ("e3m2", "e3m0"), ("e3m2", "e3m2")})
+_GF6_FC2_NAMES = {"fp6_int_neg_e2m3_pos": ("int_neg", "e2m3_pos"), "fp_e1m2_neg_e2m1_pos": ("e1m2_neg", "e2m1_pos")}
+
+
+def _gf6_table(name: str, table: str, full_only: bool = False) -> str:
+    try:
+        t = _GF6_TABLES[table]
+    except (KeyError, TypeError):
+        t = None
+    if t is None or (full_only and t not in _GF6_FULL):
+        want = "'e2m3' and 'e3m2'" if full_only else "'e2m3', 'e3m2', 'e2m1', 'e1m2' and 'e3m0'"
+        raise RuntimeError(f"{name}: the per-group formats here are {want}, got {table!r}")
+    return t
+
+
+def _gf6_owner(a: str, w: str) -> str:
+    """the function that owns a pair without a full FP6 side"""
+    return "linear_fp4" if (a, w) == ("e2m1", "e2m1") else "linear_a6w4" if w == "e2m1" else "linear_w6"
+
+
+def _gf6_format(name: str, a_table: str, w_table: str, a: torch.Tensor, w: torch.Tensor, w_scales: torch.Tensor) -> Tuple[_Format, str]:
+    """the row of an (activation, weight) pair with at least one full FP6 side, and the layout word of _per_group_operands (the
+    operands' rank decides: both 2-D, row-major codes; both 3-D, k-major images)"""
+    at, wt = _gf6_table(name, a_table), _gf6_table(name, w_table)
+    if at not in _GF6_FULL and wt not in _GF6_FULL:
+        raise RuntimeError(f"{name}: the pair ({at}, {wt}) has no e2m3 / e3m2 side - it belongs to {_gf6_owner(at, wt)}")
+    if (at, wt) in GF6_REFUSED_PAIRS:
+        raise RuntimeError(f"{name}: the pair ({at}, {wt}) is not run on the matrix cores - with both operands decoded as BF6 E3M2 the "
+                           "instruction drops small products and the error passes the GEMM contract's allowance "
+                           "(profiles/gf6_gemm_bound.txt, profiles/gf6_dot.txt)")
+    if (a.dim(), w.dim()) not in ((2, 2), (3, 3)):
+        raise RuntimeError(f"{name}: both operands must be row-major codes (2-D) or both k-major images (3-D)")
+    if wt == "e2m1":
+        return _FORMATS[at], "rank"
+    if w_scales.dtype != torch.float32:
+        raise RuntimeError(f"{name}: the scales of a 6-bit weight must be float32 (what quantize_gf6 / quantize_g6 write for an fp32 weight)")
+    return _GF6_W6_FORMATS[at, wt], "images" if a.dim() == 3 else "rows"
+
+
+def quantize_gf6(x: torch.Tensor, table: str = "e2m3", kmajor: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [..., K] fp16/fp32 (K % 128 == 0) -> (codes uint8 [rows, K * 3 / 4]: dense 6-bit codes of the FULL E2M3 / E3M2 table,
+    scales [rows, K/128] in x.dtype), one scale per group of 128 (fpq_gf6_quant_rows_codes): half(level(code) * scale) ==
+    fp6_quant_e2m3_per_group_cuda / fp6_quant_e3m2_per_group_cuda (x, 6, 128) bit for bit.
+    kmajor: the activation side's k-major images instead - codes [K/128, rows, 96] and scales fp32 [K/128, rows rounded up to 4]."""
+    require_gpu(x, "quantize_gf6")
+    return _quantize_per_group("quantize_gf6", _FORMATS[_gf6_table("quantize_gf6", table, full_only=True)], x, kmajor)
+
+
+def dequantize_gf6(codes: torch.Tensor, scales: torch.Tensor, table: str = "e2m3") -> torch.Tensor:
+    """Reference decoder in torch ops (tests / debugging): fp32 [rows, K] = level(code) * scale of the code's group, for row-major
+    6-bit codes of any per-group table ('e2m3' / 'e3m2', and 'e1m2' / 'e3m0' as quantize_g6 codes them)."""
+    table = _gf6_table("dequantize_gf6", table)
+    if table == "e2m1":
+        raise RuntimeError("dequantize_gf6: E2M1 operands are nibbles - dequantize_mx decodes them")
+    rows = codes.shape[0]
+    lv = dequantize_fp6(codes, torch.ones(rows, dtype=torch.float32, device=codes.device), _GF6_CODE_FORMAT[table])
+    return (lv.view(rows, -1, 128) * scales.float().unsqueeze(-1)).reshape(rows, -1)
+
+
+def linear_g6(a: torch.Tensor, a_scales: torch.Tensor, a_table: str, w: torch.Tensor, w_scales: torch.Tensor, w_table: str,
+              bias: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+              outs: Optional[int] = None) -> torch.Tensor:
+    """fp16 [tokens, outs] = dequantize(a) @ dequantize(w).T + bias on the matrix cores for a per-group pair with at least one
+    full FP6 side ('e2m3' / 'e3m2'; the other side any per-group format): operands as quantize_gf6 / quantize_g6 / quantize_mx emit
+    them, row-major (2-D) or k-major images (3-D: the weight `to_kmajor(codes, bits, dealt=True)` with `to_kmajor_scales(scales,
+    weight_side=True)`), told by rank.  An E2M1 weight runs on fpq_gemm_a6w4_mx[_km], a 6-bit weight (float32 scales) on
+    fpq_gemm_w6_mx[_km].  gate / residual: the AdaLN block's tail as in linear_fp4.  outs: the Linear's width for images whose
+    row count is padded, as in linear_fp4.  Numerics per pair: include/fpq.h (GF6) and profiles/gf6_dot.txt."""
+    require_gpu(a, "linear_g6")
+    fmt, layouts = _gf6_format("linear_g6", a_table, w_table, a, w, w_scales)
+    if outs is not None and w.dim() == 2 and outs != w.shape[0]:
+        raise RuntimeError(f"linear_g6: outs = {outs}, but the weight has {w.shape[0]} rows")
+    return _linear("linear_g6", fmt, layouts, a, a_scales, w, w_scales, bias, gate, residual, outs)
+
+
+def linear_g6_qkv_to_cache(a: torch.Tensor, a_scales: torch.Tensor, a_table: str, w: torch.Tensor, w_scales: torch.Tensor, w_table: str,
+                           bias: Optional[torch.Tensor], cache_kv: torch.Tensor, pos: int, seq: int,
+                           qk_norm_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mat_qkv with a split output for the pairs of linear_g6 (fpq_gemm_a6w4_mx_split[_qknorm] for an E2M1 weight,
+    fpq_gemm_w6_mx_split[_qknorm][_km] for a 6-bit one): `qkv = linear_g6(...)` for tokens [B * seq] and outs = 3 * C, but only q
+    comes back, fp16 [B, seq, C], while k and v are written straight into `cache_kv` [2, B, max_len, H, c] at pos .. pos + seq.
+    Operands row-major or k-major by rank; float32 weight scales.  qk_norm_scale and its fp32 bias: as in linear_fp4_qkv_to_cache."""
+    require_gpu(a, "linear_g6_qkv_to_cache")
+    fmt, layouts = _gf6_format("linear_g6_qkv_to_cache", a_table, w_table, a, w, w_scales)
+    return _linear_qkv_to_cache("linear_g6_qkv_to_cache", fmt, a, a_scales, w, w_scales, bias, cache_kv, pos, seq, qk_norm_scale, layouts)
+
+
+def _gf6_fc2_pair(name: str, fc2_pair) -> Tuple[str, str]:
+    pair = _GF6_FC2_NAMES.get(fc2_pair, fc2_pair) if isinstance(fc2_pair, str) else fc2_pair
+    try:
+        pair = tuple(pair)
+    except TypeError:
+        pair = None
+    if pair not in _GF6_FC2_PAIRS:
+        raise RuntimeError(f"{name}: fc2_pair must be ('int_neg', 'e2m3_pos') / 'fp6_int_neg_e2m3_pos' or ('e1m2_neg', 'e2m1_pos') / "
+                           f"'fp_e1m2_neg_e2m1_pos', got {fc2_pair!r}")
+    return pair
+
+
+def linear_g6_gelu_dual(a: torch.Tensor, a_scales: torch.Tensor, a_table: str, w: torch.Tensor, w_scales: torch.Tensor, w_table: str,
+                        bias: Optional[torch.Tensor] = None, fc2_pair=("int_neg", "e2m3_pos"), return_gelu: bool = False,
+                        outs: Optional[int] = None):
+    """fc1 of the FFN up to fc2's GEMM in one launch for the pairs of linear_g6 (fpq_gemm_a6w4_gelu_dual_pair for an E2M1 weight,
+    fpq_gemm_w6_gelu_dual_pair for a 6-bit one): fp16 [tokens, outs] = fc2's per-group(128) dual input quantizer applied to
+    F.gelu(linear_g6(...), approximate="tanh"), outs % 128 == 0.  fc2_pair ('int_neg', 'e2m3_pos') - the per-group 6-bit
+    configuration's `fp6_quant_int_neg_e2m3_pos_per_group_cuda(h, 6, 128)`, which has no global clamp: a NaN stays in its group - or
+    ('e1m2_neg', 'e2m1_pos'): `fp_quant_e1m2_neg_e2m1_pos_per_group_cuda(h, 4, 128)` as linear_a6w4_gelu_dual / linear_w6_gelu_dual
+    compute it (+ the NaN fix-up launch).  Operands row-major or k-major by rank; return_gelu: also the GELU values the quantizer saw."""
+    require_gpu(a, "linear_g6_gelu_dual")
+    fmt, layouts = _gf6_format("linear_g6_gelu_dual", a_table, w_table, a, w, w_scales)
+    pair = _GF6_FC2_PAIRS[_gf6_fc2_pair("linear_g6_gelu_dual", fc2_pair)]
+    return _linear_gelu_dual("linear_g6_gelu_dual", fmt, layouts, a, a_scales, w, w_scales, bias, return_gelu, outs, pair)
+
+
+def _quantize_any(name: str, table: str, x: torch.Tensor, kmajor: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x -> (codes, scales) in the per-group format `table` (a canonical name), by the quantizer that owns it"""
+    return _quantize_per_group(_FORMATS[table].quantizer, _FORMATS[table], x, kmajor)
+
+
+class FP6GroupLinear(FP4Linear):
+    """FP4Linear for the per-group pairs with a full FP6 side (the reference's per-group W6A6, W4A6, W6A4): the weight is held as
+    the codes and fp32 group scales of its format's quantizer (quantize_gf6 for 'e2m3' / 'e3m2', quantize_g6 for 'e1m2' / 'e3m0',
+    quantize_mx for 'e2m1'), row-major or as dealt k-major images; the activation is quantized on the fly in its own format and
+    the product is linear_g6.  Same buffers (w_codes, w_scales, bias) as its parent."""
+
+    def __init__(self, w_codes, w_scales, bias, in_features, out_features, act_table: str = "e2m3", w_table: str = "e2m3"):
+        super().__init__(w_codes, w_scales, bias, in_features, out_features, act_table, w_table, w6_forms=True)
+
+    @classmethod
+    def from_float(cls, module: torch.nn.Linear, weight_fp_type: str = "fp6_e2m3", act_fp_type: str = "fp6_e2m3", kmajor: bool = False):
+        """weight_fp_type / act_fp_type: the reference's names - "fp6_e2m3", "fp6_e3m2", "fp_e1", "fp_e2", "fp_e3" - at least one of
+        them an fp6 one.  kmajor: hold the weight as the dealt k-major image and its fp32 scale image; activations become images too."""
+        name = f"{cls.__name__}.from_float"
+        assert isinstance(module, torch.nn.Linear) and module.in_features % 128 == 0 and module.out_features % 8 == 0
+        try:
+            at, wt = _gf6_table(name, act_fp_type), _gf6_table(name, weight_fp_type)
+        except RuntimeError as e:
+            raise ValueError(str(e)) from None
+        if at not in _GF6_FULL and wt not in _GF6_FULL:
+            raise ValueError(f"{name}: the pair ({at}, {wt}) has no fp6_e2m3 / fp6_e3m2 side - it belongs to FP4Linear")
+        codes, scales = _quantize_any(name, wt, module.weight.detach().float())
+        if kmajor:
+            codes, scales = to_kmajor(codes, 4 if wt == "e2m1" else 6, dealt=True), to_kmajor_scales(scales, weight_side=True)
+        bias = None if module.bias is None else module.bias.detach().to(torch.float16)
+        return cls(codes, scales, bias, module.in_features, module.out_features, at, wt)
+
+    def _run(self, form: str, table: Optional[str], a_codes, a_scales, *rest):
+        table = self.act_table if table is None else _gf6_table(f"{type(self).__name__}.forward_operands", table)
+        if form == "plain":
+            return linear_g6(a_codes, a_scales, table, self.w_codes, self.w_scales, self.w_table, *rest, self.out_features)
+        if form == "qkv_to_cache":
+            return linear_g6_qkv_to_cache(a_codes, a_scales, table, self.w_codes, self.w_scales, self.w_table, *rest)
+        raise ValueError(f"{type(self).__name__}: no {form} form")
+
+    def _no_w6(self, form: str) -> None:   # every form exists for every pair here
+        return None
+
+    def adaln_operands(self, *args, **kw):
+        raise NotImplementedError("FP6GroupLinear: the fused producers do not emit full FP6 group operands - quantize the activation "
+                                  "with forward() or quantize_gf6()")
+
+    rotate_operands = adaln_operands
+
+
+class FP6GroupLinearGeluDual(FP6GroupLinear):
+    """FP4LinearGeluDual for the pairs of FP6GroupLinear: fc1 with the FFN's GELU(tanh) and fc2's per-group dual input quantizer in
+    the GEMM's epilogue (linear_g6_gelu_dual) - `forward(x)` returns what `fc2.act_quant(act(fc1(x)))` returns; the module that
+    follows must neither apply the activation nor quantize again.  fc2_pair: ('int_neg', 'e2m3_pos') or ('e1m2_neg', 'e2m1_pos')."""
+
+    def __init__(self, w_codes, w_scales, bias, in_features, out_features, act_table: str = "e2m3", w_table: str = "e2m3",
+                 fc2_pair=("int_neg", "e2m3_pos")):
+        super().__init__(w_codes, w_scales, bias, in_features, out_features, act_table, w_table)
+        self.fc2_pair = _gf6_fc2_pair("FP6GroupLinearGeluDual", fc2_pair)
+
+    @classmethod
+    def from_float(cls, module: torch.nn.Linear, weight_fp_type: str = "fp6_e2m3", act_fp_type: str = "fp6_e2m3", kmajor: bool = False,
+                   fc2_fp_type="fp6_int_neg_e2m3_pos"):
+        """fc2_fp_type: "fp6_int_neg_e2m3_pos" or "fp_e1m2_neg_e2m1_pos" (or the pair of table names); the rest as FP6GroupLinear"""
+        assert module.out_features % 128 == 0
+        try:
+            pair = _gf6_fc2_pair("FP6GroupLinearGeluDual.from_float", fc2_fp_type)
+        except RuntimeError as e:
+            raise ValueError(str(e)) from None
+        m = super().from_float(module, weight_fp_type, act_fp_type, kmajor)
+        m.fc2_pair = pair
+        return m
+
+    def _run(self, form: str, table: Optional[str], a_codes, a_scales, *rest):
+        if form != "gelu_dual":
+            return super()._run(form, table, a_codes, a_scales, *rest)
+        table = self.act_table if table is None else _gf6_table(f"{type(self).__name__}.forward_operands", table)
+        bias, return_gelu = rest
+        return linear_g6_gelu_dual(a_codes, a_scales, table, self.w_codes, self.w_scales, self.w_table, bias, self.fc2_pair, return_gelu,
+                                   self.out_features)
+
+    @torch.no_grad()
+    def forward(self, x):
+        return self._run("gelu_dual", None, *self._quantize(x), self.bias, False).view(*x.shape[:-1], self.out_features)
+
+    @torch.no_grad()
+    def forward_operands(self, a_codes: torch.Tensor, a_scales: torch.Tensor, table: Optional[str] = None) -> torch.Tensor:
         return self._run("gelu_dual", table, a_codes, a_scales, self.bias, False)
 
 

@@ -172,7 +172,7 @@ class QuantizedLinear_fc2(QuantizedLinear):
 def quantize_VAR(model, weight_quant=None, act_quant=None, quantize_bmm_input=False, w_bit=8, a_bit=8, kv_bit=8,
                  act_quant_sym=None, fc2_act_log2_quant=None, quant_kv=None, activation_fp_quant=False,
                  weight_fp_quant=False, act_fp_type=None, weight_fp_type=None, fc2_fp_type=None, real_fp4=False,
-                 real_fp6=False, fuse_ffn=False, kmajor_operands=True, packed_e3m2=False):
+                 real_fp6=False, fuse_ffn=False, kmajor_operands=True, packed_e3m2=False, group_fp6=False):
     """tr/quant_utils.py:1095-1167.  The reference matches its own FFN / SelfAttention
     classes; here a module with Linear children ``fc1``+``fc2`` is an FFN and one with
     ``mat_qkv``+``proj`` is a self-attention block.  As in the reference,
@@ -195,7 +195,17 @@ def quantize_VAR(model, weight_quant=None, act_quant=None, quantize_bmm_input=Fa
     pieces; results are bit-identical to the row-major form, the GEMMs 4 - 30 % faster.
 
     ``packed_e3m2`` (with ``real_fp6``; default off): a layer with an ``fp6_e3m2`` side becomes a ``gemm.FP6Linear`` of its format pair
-    too - 6-bit packed BF6 operands on the FP6 GEMM - instead of a ``gemm.FP8Linear`` with one byte per code."""
+    too - 6-bit packed BF6 operands on the FP6 GEMM - instead of a ``gemm.FP8Linear`` with one byte per code.
+
+    ``group_fp6`` (additive, default off; needs weight_quant = act_quant = "per_group", bit widths 6 / 6, 4 / 6 or 6 / 4 and FP
+    formats on both sides, else ValueError): fc1, mat_qkv and proj whose format pair has an ``fp6_e2m3`` / ``fp6_e3m2`` side (the
+    other side any of ``fp6_e2m3``, ``fp6_e3m2``, ``fp_e1``, ``fp_e2``, ``fp_e3``) become ``gemm.FP6GroupLinear`` of that pair - full
+    FP6 codes with per-group scales on the A6W4 / W6 GEMMs (``gemm.linear_g6``), k-major with ``kmajor_operands``.  The three pairs
+    whose operands are both decoded as BF6 E3M2 with a full-range side (``gemm.GF6_REFUSED_PAIRS``) stay QuantizedLinear: the
+    matrix core does not hold them inside the GEMM contract.  With ``fuse_ffn`` and ``fc2_fp_type`` ``fp6_int_neg_e2m3_pos`` or
+    ``fp_e1m2_neg_e2m1_pos`` fc1 becomes ``gemm.FP6GroupLinearGeluDual`` (GELU and fc2's quantizer in the GEMM's epilogue) under the
+    conditions of the ``real_fp4`` branch.  fc2 and ``ada_lin`` are as without it."""
+    g6_ok = _group_fp6_ok(group_fp6, weight_quant, act_quant, w_bit, a_bit, activation_fp_quant, weight_fp_quant)
     fp4_ok = (real_fp4 and weight_quant == "per_group" and act_quant == "per_group" and w_bit == 4 and a_bit == 4
               and activation_fp_quant and weight_fp_quant and act_fp_type == "fp_e2" and weight_fp_type == "fp_e2")
     if real_fp4 and not fp4_ok:
@@ -211,6 +221,9 @@ def quantize_VAR(model, weight_quant=None, act_quant=None, quantize_bmm_input=Fa
                   activation_fp_quant=activation_fp_quant, weight_fp_quant=weight_fp_quant,
                   weight_fp_type=weight_fp_type)
     def plain(lin, **kw):
+        if g6_ok and _group_fp6_pair(lin, act_fp_type, weight_fp_type):
+            from .gemm import FP6GroupLinear
+            return FP6GroupLinear.from_float(lin, weight_fp_type, act_fp_type, kmajor=kmajor_operands)
         if fp4_ok and lin.in_features % 128 == 0 and lin.out_features % 8 == 0:
             from .gemm import FP4Linear
             return FP4Linear.from_float(lin, kmajor=kmajor_operands)
@@ -231,6 +244,9 @@ def quantize_VAR(model, weight_quant=None, act_quant=None, quantize_bmm_input=Fa
             gelu_tanh = isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "tanh"
             in_gemm = (fuse_ffn and gelu_tanh and fp4_ok and fc2_fp_type == "fp_e1m2_neg_e2m1_pos"
                        and fc1.in_features % 128 == 0 and fc1.out_features % 128 == 0)
+            g6_tail = (fuse_ffn and gelu_tanh and g6_ok and fc2_fp_type in _GROUP_FP6_FC2
+                       and _group_fp6_pair(fc1, act_fp_type, weight_fp_type, tail=True))
+            in_gemm = in_gemm or g6_tail
             one_pass = (fuse_ffn and gelu_tanh and not in_gemm and activation_fp_quant and (act_quant, fc2_fp_type) in GeluThenFc2Quant.FUSED
                         and fc1.out_features % (128 if act_quant == "per_group" else 8) == 0)
             if fuse_ffn and not (in_gemm or one_pass):
@@ -239,8 +255,11 @@ def quantize_VAR(model, weight_quant=None, act_quant=None, quantize_bmm_input=Fa
             m.fc2 = QuantizedLinear_fc2.from_float(fc2, act_quant_sym=False, fc2_act_log2_quant=fc2_act_log2_quant,
                                                    act_fp_type=fc2_fp_type, **common)
             if in_gemm:
-                from .gemm import FP4LinearGeluDual
-                m.fc1 = FP4LinearGeluDual.from_float(fc1, kmajor=kmajor_operands)
+                from .gemm import FP4LinearGeluDual, FP6GroupLinearGeluDual
+                if g6_tail:
+                    m.fc1 = FP6GroupLinearGeluDual.from_float(fc1, weight_fp_type, act_fp_type, kmajor=kmajor_operands, fc2_fp_type=fc2_fp_type)
+                else:
+                    m.fc1 = FP4LinearGeluDual.from_float(fc1, kmajor=kmajor_operands)
                 m.act = nn.Identity()
                 m.fc2.act_quant = lambda t: t                      # its input arrives quantized from fc1's epilogue
                 m.fc2.act_quant_name = "in fc1's epilogue"
@@ -256,6 +275,30 @@ def quantize_VAR(model, weight_quant=None, act_quant=None, quantize_bmm_input=Fa
     return model
 
 
+# ---- group_fp6: the per-group 6-bit configuration (and W4A6 / W6A4) on the matrix cores ---------------------------------------
+_GROUP_FP6_FULL = ("fp6_e2m3", "fp6_e3m2")
+_GROUP_FP6_FORMATS = _GROUP_FP6_FULL + ("fp_e1", "fp_e2", "fp_e3")
+_GROUP_FP6_FC2 = ("fp6_int_neg_e2m3_pos", "fp_e1m2_neg_e2m1_pos")   # the fc2 formats of the GEMMs' fc1 tail (gemm._GF6_FC2_PAIRS)
+
+
+def _group_fp6_ok(group_fp6, weight_quant, act_quant, w_bit, a_bit, activation_fp_quant, weight_fp_quant) -> bool:
+    ok = (group_fp6 and weight_quant == "per_group" and act_quant == "per_group" and (w_bit, a_bit) in ((6, 6), (4, 6), (6, 4))
+          and activation_fp_quant and weight_fp_quant)
+    if group_fp6 and not ok:
+        raise ValueError("group_fp6 needs weight_quant = act_quant = 'per_group', (w_bit, a_bit) = (6, 6), (4, 6) or (6, 4), "
+                         "fp formats on both sides")
+    return bool(ok)
+
+
+def _group_fp6_pair(lin, a, w, tail: bool = False) -> bool:
+    """the layer is one gemm.FP6GroupLinear runs: a per-group pair with at least one fp6 side that linear_g6 accepts, a shape the GEMM
+    takes (tail: the fc1 form, whose output tile is one quantization group)"""
+    from .gemm import GF6_REFUSED_PAIRS, _GF6_TABLES
+    return (a in _GROUP_FP6_FORMATS and w in _GROUP_FP6_FORMATS and (a in _GROUP_FP6_FULL or w in _GROUP_FP6_FULL)
+            and (_GF6_TABLES[a], _GF6_TABLES[w]) not in GF6_REFUSED_PAIRS
+            and lin.in_features % 128 == 0 and lin.out_features % (128 if tail else 8) == 0)
+
+
 # ---- per-block mixed formats (the older variants' quantize_VAR_* functions, as data) --------------------------
 def _block_index(name: str) -> int:
     """'blocks.<i>.ffn' -> i, as the reference does (int(name.split('.')[1]))."""
@@ -268,7 +311,7 @@ _FP6_SYMMETRIC = ("fp6_e2m3", "fp6_e3m2")
 def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, w_bit=8, a_bit=8, act_quant_sym=None,
                        fc2_act_log2_quant=None, activation_fp_quant=False, weight_fp_quant=False,
                        ada_lin_formats=None, real_fp6=False, kmajor_operands=True, real_fp4=False, fuse_ffn=False, a6w4_kmajor=False,
-                       w6_weights=False, w6_forms=False, w6_kmajor=False):
+                       w6_weights=False, w6_forms=False, w6_kmajor=False, group_fp6=False):
     """quantize_VAR with a format pair per (block, layer): ``layer_formats(block_idx, layer)`` returns
     ``(act_fp_type, weight_fp_type)`` for layer in {"fc1", "fc2", "mat_qkv", "proj"}.  ``ada_lin_formats``:
     None leaves the AdaLN Linear in full precision (as tr/ does), a pair quantizes ``ada_lin[1]`` (as the fq/ and
@@ -314,7 +357,13 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
     epilogue of the FP4 GEMM for ``fp_e2``, of the A6W4 GEMM for ``fp_e1`` / ``fp_e3``), ``act`` an identity and fc2's input quantizer
     is switched off.  Otherwise, where ``GeluThenFc2Quant`` covers (act_quant, fc2's activation format): ``act`` becomes that
     one-pass module.  An FFN neither applies to raises quantize_VAR's ValueError - when the walk reaches it: the model is converted
-    in place (as in quantize_VAR), so the modules in front of that FFN are already replaced and the model is not to be used."""
+    in place (as in quantize_VAR), so the modules in front of that FFN are already replaced and the model is not to be used.
+
+    ``group_fp6`` (additive, default off): as in quantize_VAR, per layer - fc1, mat_qkv and proj whose pair has an ``fp6_e2m3`` /
+    ``fp6_e3m2`` side become ``gemm.FP6GroupLinear``; a pure FP4 pair goes where ``real_fp4`` sends it; with ``fuse_ffn`` and a block
+    whose fc2 activation format is ``fp6_int_neg_e2m3_pos`` or ``fp_e1m2_neg_e2m1_pos`` such an fc1 becomes
+    ``gemm.FP6GroupLinearGeluDual``.  fc2 and ``ada_lin[1]`` are as without the keyword."""
+    g6_ok = _group_fp6_ok(group_fp6, weight_quant, act_quant, w_bit, a_bit, activation_fp_quant, weight_fp_quant)
     fp4_ok = (real_fp4 and weight_quant == "per_group" and act_quant == "per_group" and w_bit == 4 and a_bit == 4
               and activation_fp_quant and weight_fp_quant)
     if real_fp4 and not fp4_ok:
@@ -340,7 +389,10 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
             return cls.from_float(lin, kmajor=True, act_fp_type=a, a6w4_kmajor=True)
         return cls.from_float(lin, kmajor=kmajor_operands and a == "fp_e2", act_fp_type=a)
 
-    def layer(cls, lin, a, w, w6=False, **kw):   # w6: the layer is one of those w6_weights covers (fc1, mat_qkv, proj)
+    def layer(cls, lin, a, w, w6=False, **kw):   # w6: the layer is one of those w6_weights / group_fp6 cover (fc1, mat_qkv, proj)
+        if g6_ok and w6 and _group_fp6_pair(lin, a, w):
+            from .gemm import FP6GroupLinear
+            return FP6GroupLinear.from_float(lin, w, a, kmajor=kmajor_operands)
         if (fp6_ok and a in _FP6_SYMMETRIC and w in _FP6_SYMMETRIC and lin.in_features % 128 == 0 and lin.out_features % 8 == 0):
             from .gemm import FP6Linear
             return FP6Linear.from_float(lin, kmajor=kmajor_operands, weight_fp_type=w, act_fp_type=a)
@@ -366,14 +418,18 @@ def quantize_VAR_mixed(model, layer_formats, weight_quant=None, act_quant=None, 
             w6_tail = w6_forms and w in ("fp_e1", "fp_e3")   # the W6 GEMM's fc1 tail stands in for the FP4 / A6W4 GEMM's
             in_gemm = (fuse_ffn and gelu_tanh and fp4_ok and (w == "fp_e2" or w6_tail) and a in ("fp_e1", "fp_e2", "fp_e3")
                        and a2 == "fp_e1m2_neg_e2m1_pos" and fc1.in_features % 128 == 0 and fc1.out_features % 128 == 0)
+            g6_tail = fuse_ffn and gelu_tanh and g6_ok and a2 in _GROUP_FP6_FC2 and _group_fp6_pair(fc1, a, w, tail=True)
+            in_gemm = in_gemm or g6_tail
             one_pass = (fuse_ffn and gelu_tanh and not in_gemm and activation_fp_quant and (act_quant, a2) in GeluThenFc2Quant.FUSED
                         and fc1.out_features % (128 if act_quant == "per_group" else 8) == 0)
             if fuse_ffn and not (in_gemm or one_pass):
                 raise ValueError("fuse_ffn needs an FFN with act = GELU(approximate='tanh') and a dual-format fc2_fp_type "
                                  "(fp_e1m2_neg_e2m1_pos / fp4_afpq per group, fp6_int_neg_e2m3_pos per group or per token)")
             if in_gemm:
-                from .gemm import FP4LinearGeluDual
-                if w6_tail:
+                from .gemm import FP4LinearGeluDual, FP6GroupLinearGeluDual
+                if g6_tail:
+                    m.fc1 = FP6GroupLinearGeluDual.from_float(fc1, w, a, kmajor=kmajor_operands, fc2_fp_type=a2)
+                elif w6_tail:
                     m.fc1 = FP4LinearGeluDual.from_float(fc1, act_fp_type=a, weight_fp_type=w, **w6_kw)
                 else:
                     m.fc1 = fp4_layer(FP4LinearGeluDual, fc1, a)

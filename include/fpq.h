@@ -919,6 +919,69 @@ int fpq_gemm_w6_mx_split_qknorm_km(const uint8_t* a_image, const void* a_scales,
                                    int w_scale_dtype, int w_table, const float* bias, int64_t tokens, int64_t outs, int64_t k,
                                    const fpq_gemm_split_t* split, const float* q_head_scale, fpq_stream_t stream);
 
+/* ---- GF6: FULL-RANGE FP6 (E2M3 / E3M2) operands with per-group(128) scales, on the A6W4 and W6 GEMMs ----------------------------
+ * The reference's per-group 6-bit configuration (--w_bit 6 --a_bit 6, per_group on both sides: fp6_quant_e2m3_per_group_cuda /
+ * fp6_quant_e3m2_per_group_cuda) and its mixed siblings W4A6 / W6A4.  No GEMM of its own: in fpq_gemm_a6w4_* and fpq_gemm_w6_* the
+ * table argument of a 6-bit operand names the HARDWARE DECODE - FPQ_E1M2 selects FP6 E2M3 (cbsz / blgp = 2), FPQ_E3M0 selects BF6
+ * E3M2 (3) - and those kernels never look at which of the 64 codes occur: full-range E2M3 codes are valid operands under FPQ_E1M2
+ * and full-range E3M2 codes under FPQ_E3M0, in every form and both layouts.  FPQ_E2M3 / FPQ_E3M2 themselves stay refused there.
+ *
+ * fpq_gf6_quant_rows_codes: the per-group(128) quantizer on table_id = FPQ_E2M3 or FPQ_E3M2 (anything else: FPQ_ERR_TABLE, decided
+ * first) straight to dense 6-bit hardware codes in the bit format of fpq_quant_rows_codes_fp6 / _g6, one scale per group, with the
+ * quantization decisions of fpq_quant_rows(table_id, cols = 128).
+ *   kmajor = 0: x [rows, cols] F16 or F32 -> codes [rows, cols * 3 / 4], scales [rows, cols / 128] in x's dtype
+ *   kmajor = 1: x F16 only (F32: FPQ_ERR_DTYPE; use kmajor = 0 + fpq_codes_to_kmajor + fpq_scales_to_kmajor) -> the activation
+ *               side's 6-bit image [cols / 128][rows][96] and the fp32 scale image [cols / 128][rows rounded up to 4] of
+ *               fpq_a6w4_quant_rows_codes_km (padding rows of the scale image are not written)
+ * For fp16 x, half(level(code) * scale) equals fp6_quant_e2m3_per_group_cuda / fp6_quant_e3m2_per_group_cuda(x, 6, 128) bit for
+ * bit; for fp32 x the fp32 product cast to fp16 does (the reference's .to(float16)).  Non-finite and all-zero groups follow
+ * fpq_quant_rows_codes_g6's rule: the non-finite maximum travels in the SCALE, every code is a valid code, an all-zero group has
+ * scale 0 and code 0 throughout.  Checks, in this order: table_id (FPQ_ERR_TABLE), negative sizes (FPQ_ERR_ARG), in_dtype
+ * (FPQ_ERR_DTYPE), cols % 128 or - with kmajor - an image of 2 GiB or more (FPQ_ERR_SHAPE), rows == 0 or cols == 0 (FPQ_OK), then
+ * NULL pointers / alignment (FPQ_ERR_ARG; x and codes 16 bytes, scales their dtype, the scale image 16).  It launches the
+ * kernels behind fpq_quant_rows_codes_g6 / fpq_a6w4_quant_rows_codes_km with the full tables as data.
+ *
+ * NUMERICS of full-range operands on the two GEMMs (the steps are unchanged: t = fl(d_g sa), acc = fma(t, sw, acc), out = fp16(acc +
+ * bias)).  Per pair (activation x weight) the products are multiples of / at most: E2M3 x E2M1 2^-4, 45; E3M2 x E2M1 2^-5, 168;
+ * E2M3 x E1M2 2^-5, 13.125; E2M3 x E3M0 2^-5, 120; E3M2 x E1M2 2^-6, 49; E2M3 x E2M3 2^-6, 56.25; E3M0 x E3M2 2^-6, 448; E2M3 x E3M2
+ * 2^-7, 210; E3M2 x E3M2 2^-8, 784 (a pair and its mirror image alike) - so the exact 128-term dot has at most 22 significant bits and
+ * fits fp32, but for E3M2 x E3M2 (25).  MEASURED on an MI355X before anything else (profiles/gf6_dot.txt; tools/gf6_dot.py): with
+ * k = 128, unit scales and no bias, dots that are fp16 numbers - the largest products cancelling beside a few smallest ones, every
+ * level pair alone and 128-fold, the largest product beside 127 small ones - come out bit for bit in both tilings for THIRTEEN of the
+ * sixteen pairs, E2M3 x E3M2 (22 bits) among them.  For those the contract is fpq_gemm_fp4_mx's, unchanged: allowance 1.0 x the bound
+ * (worst measured over the shape sweep 1.000, the fp16 output rounding), bit-equal to the fp32 model of those steps, both tilings
+ * and both layouts bit-equal (tests/gf6_model.py, tests/test_gpu_gf6.py).  The three pairs whose operands are BOTH decoded as BF6
+ * E3M2 with a full-range side - E3M0 x E3M2, E3M2 x E3M0, E3M2 x E3M2 - are not exact (the cancelling construction loses 8 steps of
+ * the smallest product, although two of them fit fp32 on paper; E3M0 x E3M0 is exact, profiles/w6_dot.txt) and over the shape sweep
+ * reach 290, 380 and 660 x the bound (profiles/gf6_gemm_bound.txt), far past the 8 x this project grants E3M2 levels on the
+ * instruction elsewhere: the C entry points run them like any other codes, the Python layer (gemm.linear_g6*) refuses them.
+ * THE FC1 TAIL with full-range codes: fpq_gemm_a6w4_gelu_dual_pair / fpq_gemm_w6_gelu_dual_pair below, for fc2's 4-bit dual pair
+ * and for the 6-bit configuration's own (INT- / E2M3+). */
+int fpq_gf6_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id, int in_dtype,
+                             int kmajor, fpq_stream_t stream);
+
+/* THE FC1 TAIL WITH ITS DUAL PAIR AS AN ARGUMENT: fpq_gemm_a6w4_gelu_dual[_km] / fpq_gemm_w6_gelu_dual[_km] with the two tables of fc2's
+ * per-group(128) input quantizer (neg_table, pos_table) and the layout (kmajor: 0 row-major operands, else the k-major images of the
+ * _km twin) as arguments.  Accepted pairs - anything else FPQ_ERR_TABLE, checked beside the operand tables, before every other check:
+ *   (FPQ_E1M2_NEG, FPQ_E2M1_POS)  the 4-bit format: the same launch as the existing entry points, bit for bit, nan_flag included
+ *   (FPQ_INT_NEG, FPQ_E2M3_POS)   fc2's format in the per-group 6-bit configuration: out = fp6_quant_int_neg_e2m3_pos_per_group_cuda(
+ *                                 gelu_tanh(y), 6, 128) with y the fp16 Linear output of the plain form - bit for bit what
+ *                                 fpq_quant_rows_dual / fpq_gelu_quant_rows_dual write for that pair WITHOUT a flag.  This format has no
+ *                                 global clamp: a NaN stays out of its group's two maxima (it "belongs to neither side") and comes out
+ *                                 as the table's level for a NaN pattern times the scale, the other 127 values are quantized as ever;
+ *                                 a +-inf makes its side's scale infinite and, as in the stand-alone kernels, the whole group NaN.
+ *                                 nan_flag is checked for alignment like the twin's and otherwise ignored: nothing is raised or zeroed.
+ * gelu_out and every other argument, check and tiling: the twins', in the twins' order.  The bucket table behind the scale tiles is
+ * sized from the pair (1 KiB for the 4-bit pair, 4 KiB - 2 x 1024 buckets - for the 6-bit one) and counted in the 160 KiB refusal.
+ * The 6-bit pair runs kernels of its own (gemm_a6w4_fc1x[_km]_kernel, gemm_w6_fc1x[_km]_kernel: the fc1 kernels with the NaN halves
+ * cleared in the values the tail's packed maxima are made of); the kernels behind the existing entry points are untouched. */
+int fpq_gemm_a6w4_gelu_dual_pair(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                                 int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs, int64_t k,
+                                 void* nan_flag, int neg_table, int pos_table, int kmajor, fpq_stream_t stream);
+int fpq_gemm_w6_gelu_dual_pair(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                               int w_scale_dtype, int w_table, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs,
+                               int64_t k, void* nan_flag, int neg_table, int pos_table, int kmajor, fpq_stream_t stream);
+
 /* THE PRODUCERS IN FRONT OF THE A6W4 GEMM: the online rotation and the adaLN producer emitting its activation operands in one launch,
  * as fpq_rotate_quant_rows_codes_mx[_km] / fpq_adaln_rotate_quant_rows_codes_mx[_km] do for the FP4 GEMM - the activation never exists
  * in HBM as fp16 between the block's LayerNorm and its matrix product (the mixed W4A4 model's mat_qkv and fc1 have an E3M0 activation
