@@ -378,7 +378,7 @@ struct AdalnTiers {
 // 0.53 of 8 TB/s at [32768 x 1024] (profiles/r03_survey_shapes.txt).
 // HW6 (1: E2M3, 2: E3M2; value output, rows of at most 16 groups): the levels of a lane's 32 outputs from the FP6 conversion
 // hardware (fpq_fast16.h, fp6_levels_hw32) - per group and per token alike; no table is staged.
-// G6 (CODES, per group, table E1M2 / E3M0): the A6W4 GEMM's activation operands (fpq_gemm_a6w4.h) - dense 6-bit codes, 96 bytes
+// G6 (CODES, per group, table E1M2 / E3M0): the A6W4 GEMM's activation operands (fpq_gemm_g6.h) - dense 6-bit codes, 96 bytes
 // per group, through the bucket -> code table lut16_codes_g6 + one scale per group; row-major or the k-major images (r.km_rows).
 template <typename Tmod, int MAXC, bool CODES, bool EMIT, bool TOKEN, bool X32, bool HW4, bool TIGHT = false, int NW = 4, bool PAIR2 = false, int HW6 = 0, bool G6 = false>
 __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ? 5 : 4) void adaln_mfma_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ out,
@@ -906,7 +906,7 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
           }
         }
       }
-    } else if constexpr (CODES && G6) {   // A6W4 operands: 96 bytes of 6-bit codes + one scale per group (fpq_gemm_a6w4.h)
+    } else if constexpr (CODES && G6) {   // A6W4 operands: 96 bytes of 6-bit codes + one scale per group (fpq_gemm_g6.h)
       // row-major: the row's 6 vpr bytes behind its start, the tile's groups the first 96 x 16 of them; k-major: chunk ch of the
       // tile = chunk ch % 6 of group ch / 6 (include/fpq.h).  Scales as in the FP4 branch below.
       const uint32_t gpr = (uint32_t)vpr >> 4;

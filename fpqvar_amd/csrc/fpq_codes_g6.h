@@ -1,4 +1,4 @@
-// fpq_codes_g6.h - the operand-emitting quantizer of the A6W4 GEMM (fpq_gemm_a6w4.h): per-group(128) quantization on the E1M2 or
+// fpq_codes_g6.h - the operand-emitting quantizer of the A6W4 GEMM (fpq_gemm_g6.h): per-group(128) quantization on the E1M2 or
 // E3M0 table straight to dense 6-bit hardware codes (E1M2 levels as FP6 E2M3 codes, E3M0 levels as BF6 E3M2 codes) + one scale per
 // group.  Included by fpq_kernels.hip only, behind fpq_codes_fp8.h (codes8_vec16); the code tables: lut16_codes_g6, fpq_fast16.h.
 #pragma once

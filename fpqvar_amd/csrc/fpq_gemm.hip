@@ -9,7 +9,6 @@ namespace {
 #include "fpq_gemm_fp4.h"
 #include "fpq_gemm_fp8.h"
 #include "fpq_gemm_fp6.h"
-#include "fpq_gemm_a6w4.h"
 #include "fpq_attention.h"
 
 // Per-group scales [rows, groups] (fp16 or fp32) -> the fp32 k-major scale image [groups][image_rows] of the FP4 GEMM (include/fpq.h):
@@ -66,58 +65,6 @@ int launch_fp4_staged(const GemmCall& c, int w_scale_dtype) {
   return with_dtype(w_scale_dtype, [&](auto tw) {
     return gemm_launch(gemm_fp4_kernel<decltype(tw), MT, NT, WR, WC>, Cfg::BM, Cfg::BN, Cfg::NTHR, Cfg::lds((int)(c.k / 128)), c);
   });
-}
-// 6-bit activations x FP4 weights, 32 MT x 128 tiles and epilogue XE (GemmNoFc1: the plain kernel; GemmFc1: its fc1 form); a_table:
-// FPQ_E1M2 (as FP6 E2M3 codes, cbsz 2) or FPQ_E3M0 (BF6 E3M2, 3); lds: GemmA6W4Cfg's figure for that epilogue.  km: the operands are
-// k-major images (c.epi.km_w_rows set, fp32 scale images: the entry points have checked w_scale_dtype).
-// GemmSplit: the split output (c.epi's sp_* fields set; the kernel takes no further argument), GemmQkNorm: the split output with the
-// q / k norm - both compiled for fp32 weight scales only (fpq_gemm_a6w4.h)
-template <int MT, typename XE>
-int launch_a6w4(const GemmCall& c, int a_table, int w_scale_dtype, size_t lds, XE xe, bool km = false) {
-  using Cfg = GemmA6W4Cfg<MT, 4>;
-  if (lds > 160 * 1024) return FPQ_ERR_SHAPE;
-  if constexpr (__is_same(XE, GemmSplit) || __is_same(XE, GemmQkNorm)) {
-    if (w_scale_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
-    auto format = [&](auto fa) {
-      constexpr int FA = decltype(fa)::value;
-      if constexpr (__is_same(XE, GemmQkNorm)) {
-        if (km) return gemm_launch(gemm_a6w4_qkn_km_kernel<float, MT, 4, FA>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
-        return gemm_launch(gemm_a6w4_qkn_kernel<float, MT, 4, FA>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
-      } else {
-        if (km) return gemm_launch(gemm_a6w4_split_km_kernel<float, MT, 4, FA>, Cfg::BM, Cfg::BN, 256, lds, c);
-        return gemm_launch(gemm_a6w4_split_kernel<float, MT, 4, FA>, Cfg::BM, Cfg::BN, 256, lds, c);
-      }
-    };
-    return a_table == FPQ_E1M2 ? format(Int<2>{}) : format(Int<3>{});
-  } else {
-    if (km) {
-      if constexpr (__is_same(XE, GemmFc1)) {
-        if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_fc1_km_kernel<float, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
-        return gemm_launch(gemm_a6w4_fc1_km_kernel<float, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
-      } else if constexpr (__is_same(XE, GemmFc1X)) {
-        const GemmFc1& x1 = xe;
-        if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_fc1x_km_kernel<float, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c, x1);
-        return gemm_launch(gemm_a6w4_fc1x_km_kernel<float, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c, x1);
-      } else {
-        if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_km_kernel<float, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c);
-        return gemm_launch(gemm_a6w4_km_kernel<float, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c);
-      }
-    }
-    return with_dtype(w_scale_dtype, [&](auto tw) {
-      using Tw = decltype(tw);
-      if constexpr (__is_same(XE, GemmFc1)) {
-        if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_fc1_kernel<Tw, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
-        return gemm_launch(gemm_a6w4_fc1_kernel<Tw, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c, xe);
-      } else if constexpr (__is_same(XE, GemmFc1X)) {
-        const GemmFc1& x1 = xe;
-        if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_fc1x_kernel<Tw, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c, x1);
-        return gemm_launch(gemm_a6w4_fc1x_kernel<Tw, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c, x1);
-      } else {
-        if (a_table == FPQ_E1M2) return gemm_launch(gemm_a6w4_kernel<Tw, MT, 4, 2>, Cfg::BM, Cfg::BN, 256, lds, c);
-        return gemm_launch(gemm_a6w4_kernel<Tw, MT, 4, 3>, Cfg::BM, Cfg::BN, 256, lds, c);
-      }
-    });
-  }
 }
 // the row-scaled FP6 kernel for one epilogue and one format pair (FA, FB: cbsz of the activations, blgp of the weights; 2 = E2M3,
 // 3 = E3M2).  A pair with an E3M2 side is compiled for fp16 activation scales only - what the quantizers of activations produce;
@@ -382,79 +329,6 @@ int fpq_gemm_fp4_mx_km(const uint8_t* a_image, const void* a_scales, const uint8
   return gemm_fp4_mx_impl(a_image, a_scales, w_image, w_scales, w_scale_dtype, bias, out, tokens, outs, k, epilogue, true, stream);
 }
 
-// 6-bit activation codes (E1M2 levels as FP6 E2M3 codes, E3M0 levels as BF6 E3M2 codes) x the FP4 GEMM's E2M1 weight nibbles
-// (fpq_gemm_a6w4.h, include/fpq.h).  Two LDS-DMA tilings, chosen as fpq_gemm_fp4_mx_ex chooses between the same two
-// (FPQ_GEMM_CFG 20 / 30 forces one); there is no register-staged form: K is limited by the scale tiles as there, and the bias
-// is read four outputs at a time.
-// km: both operands and both scale tensors are k-major images (include/fpq.h; gemm_a6w4_km_kernel) - the FP4 km rules of
-// gemm_fp4_mx_impl beside the row-major checks: fp32 scale images, 16-byte aligned, tokens and outs below 2^28 (32-bit lane
-// offsets into three planes of the scale images)
-// split / qkn: the split output (fpq_gemm_a6w4_mx_split: the FP6 family's rules - whole batch entries, every part 8-byte aligned) and
-// the q / k norm in front of it; the descriptor is checked where gemm_fp4_mx_impl checks it, behind the sizes and in front of the
-// dtype; those kernels exist for fp32 weight scales only
-static int gemm_a6w4_mx_impl(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
-                             int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
-                             const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream, const fpq_gemm_split_t* split = nullptr,
-                             const GemmQkNorm* qkn = nullptr) {
-  if (a_table != FPQ_E1M2 && a_table != FPQ_E3M0) return FPQ_ERR_TABLE;
-  if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
-  GemmEpi epi;
-  if (int rc = gemm_epilogue(epilogue, &epi)) return rc;
-  if (split) {
-    if (int rc = gemm_split(split, epilogue, tokens, outs, true, &epi)) return rc;
-    out = split->out[0];   // (not written through: every tile belongs to a part)
-  }
-  if ((km || split) ? w_scale_dtype != FPQ_F32 : (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32)) return FPQ_ERR_DTYPE;
-  if (k % 128 != 0 || k > 128 * 64 || outs % 8 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
-  if (km && (tokens >= (1ll << 28) || outs >= (1ll << 28))) return FPQ_ERR_SHAPE;
-  if (tokens == 0 || outs == 0) return FPQ_OK;
-  if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
-  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (split ? 0 : (uintptr_t)out)) & 15) != 0 || ((uintptr_t)bias & 7) != 0) return FPQ_ERR_ARG;
-  if (km ? (((uintptr_t)a_scales | (uintptr_t)w_scales) & 15) != 0
-         : ((uintptr_t)a_scales & 1) != 0 || ((uintptr_t)w_scales & (w_scale_dtype == FPQ_F16 ? 1 : 3)) != 0)
-    return FPQ_ERR_ARG;
-  if (km) epi.km_w_rows = (int)((outs + 63) / 64 * 64);
-  const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
-  const int G = (int)(k / 128);
-  auto tile = [&](auto mt) {
-    constexpr int MT = decltype(mt)::value;
-    const size_t lds = GemmA6W4Cfg<MT, 4>::lds(G);
-    if (qkn) return launch_a6w4<MT>(c, a_table, w_scale_dtype, lds, *qkn, km);
-    if (split) return launch_a6w4<MT>(c, a_table, w_scale_dtype, lds, GemmSplit{}, km);
-    return launch_a6w4<MT>(c, a_table, w_scale_dtype, lds, GemmNoFc1{}, km);
-  };
-  return gemm_glds_tiling(tokens, outs, false, false) == 30 ? tile(Int<2>{}) : tile(Int<4>{});
-}
-int fpq_gemm_a6w4_mx(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
-                     int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
-                     const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream) {
-  return gemm_a6w4_mx_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, bias, out, tokens, outs, k, epilogue, false, stream);
-}
-int fpq_gemm_a6w4_mx_km(const uint8_t* a_image, const void* a_scales, int a_table, const uint8_t* w_image, const void* w_scales,
-                        int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
-                        const fpq_gemm_epilogue_t* epilogue, fpq_stream_t stream) {
-  return gemm_a6w4_mx_impl(a_image, a_scales, a_table, w_image, w_scales, w_scale_dtype, bias, out, tokens, outs, k, epilogue, true, stream);
-}
-// mat_qkv on the A6W4 GEMM: the split output, and the q / k norm in that epilogue (include/fpq.h); kmajor chooses between the operands
-// of the two entry points above.  The table goes first, as in every A6W4 entry point.
-int fpq_gemm_a6w4_mx_split(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
-                           int w_scale_dtype, const void* bias, int64_t tokens, int64_t outs, int64_t k, const fpq_gemm_split_t* split,
-                           int kmajor, fpq_stream_t stream) {
-  if (a_table != FPQ_E1M2 && a_table != FPQ_E3M0) return FPQ_ERR_TABLE;
-  if (!split) return FPQ_ERR_ARG;
-  return gemm_a6w4_mx_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, bias, nullptr, tokens, outs, k, nullptr, kmajor != 0,
-                           stream, split);
-}
-int fpq_gemm_a6w4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
-                                  int w_scale_dtype, const float* bias, int64_t tokens, int64_t outs, int64_t k,
-                                  const fpq_gemm_split_t* split, const float* q_head_scale, int kmajor, fpq_stream_t stream) {
-  if (a_table != FPQ_E1M2 && a_table != FPQ_E3M0) return FPQ_ERR_TABLE;
-  GemmQkNorm qkn;
-  if (int rc = gemm_qknorm(split, bias, q_head_scale, &qkn)) return rc;
-  return gemm_a6w4_mx_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, nullptr, nullptr, tokens, outs, k, nullptr, kmajor != 0,
-                           stream, split, &qkn);
-}
-
 #ifdef FPQ_GEMM6_STAMPS
 // diagnostic builds only: where the FP6 GEMM's wavefronts put their per-phase stamp sums ([wavefronts][8] uint64, zeroed by the caller)
 int fpq_debug_gemm6_stamp_buffer(void* device_buffer) {
@@ -525,80 +399,6 @@ int fpq_gemm_fp4_gelu_dual_km(const uint8_t* a_image, const void* a_scales, cons
                               int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs,
                               int64_t k, void* nan_flag, fpq_stream_t stream) {
   return gemm_fp4_gelu_dual_impl(a_image, a_scales, w_image, w_scales, w_scale_dtype, bias, out, gelu_out, tokens, outs, k, nan_flag, true, stream);
-}
-
-// fc1 with a 6-bit activation: the fc1 tail of fpq_gemm_fp4_gelu_dual in the A6W4 GEMM's epilogue (gemm_a6w4_fc1_kernel); operands
-// and tilings of fpq_gemm_a6w4_mx, tail, gelu_out, nan_flag and fix-up launch of fpq_gemm_fp4_gelu_dual; km as in gemm_a6w4_mx_impl
-// (outs % 128 == 0: the weight image has exactly outs rows)
-static int gemm_a6w4_gelu_dual_impl(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
-                                    int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs, int64_t k,
-                                    void* nan_flag, bool km, fpq_stream_t stream, int neg_table = FPQ_E1M2_NEG,
-                                    int pos_table = FPQ_E2M1_POS) {
-  if (a_table != FPQ_E1M2 && a_table != FPQ_E3M0) return FPQ_ERR_TABLE;
-  // the tail's dual pair (fpq_gemm_a6w4_gelu_dual_pair): fc2's 4-bit format with the reference's global clamp (the NaN flag), or its
-  // 6-bit one, which has no clamp - the flag is not raised and nothing is zeroed
-  const bool fp6_pair = neg_table == FPQ_INT_NEG && pos_table == FPQ_E2M3_POS;
-  if (!fp6_pair && !(neg_table == FPQ_E1M2_NEG && pos_table == FPQ_E2M1_POS)) return FPQ_ERR_TABLE;
-  const Lut16Host& dual = lut16_host(neg_table, pos_table);   // host arithmetic only: the table travels in the kernel's arguments
-  if (!dual.tab_valid) return FPQ_ERR_TABLE;
-  if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
-  if (km ? w_scale_dtype != FPQ_F32 : (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32)) return FPQ_ERR_DTYPE;
-  // outs % 128: an output tile is one quantization group wide.  The LDS image of the 128-row tiling is the larger of the two, so
-  // it stands for both (about 105 KiB at k = 8192: the k limit is the tighter one today)
-  if (k % 128 != 0 || k > 128 * 64 || outs % 128 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF ||
-      GemmA6W4Cfg<4, 4>::lds_fc1((int)(k / 128), dual.args.shift) > 160 * 1024)
-    return FPQ_ERR_SHAPE;
-  if (km && (tokens >= (1ll << 28) || outs >= (1ll << 28))) return FPQ_ERR_SHAPE;
-  if (tokens == 0 || outs == 0) return FPQ_OK;
-  if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
-  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out | (uintptr_t)gelu_out) & 15) != 0 || ((uintptr_t)bias & 7) != 0 ||
-      ((uintptr_t)nan_flag & 7) != 0)
-    return FPQ_ERR_ARG;
-  if (km ? (((uintptr_t)a_scales | (uintptr_t)w_scales) & 15) != 0
-         : ((uintptr_t)a_scales & 1) != 0 || ((uintptr_t)w_scales & (w_scale_dtype == FPQ_F16 ? 1 : 3)) != 0)
-    return FPQ_ERR_ARG;
-  GemmFc1 xe;
-  xe.a = dual.args;
-  xe.tab = dual.tab;
-  xe.h_out = (_Float16*)gelu_out;
-  if (fp6_pair) nan_flag = nullptr;
-  xe.nan_flag = (uint32_t*)nan_flag;
-  const int G = (int)(k / 128);
-  GemmEpi epi{};
-  epi.rows_per_gate = 1;
-  epi.sp_rpb = 1;
-  if (km) epi.km_w_rows = (int)outs;
-  const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
-  auto run = [&](const auto& x) {   // (the table's size comes from the pair: 2^(16 - shift) entries behind the scale tiles)
-    return gemm_glds_tiling(tokens, outs, false, false) == 30
-               ? launch_a6w4<2>(c, a_table, w_scale_dtype, GemmA6W4Cfg<2, 4>::lds_fc1(G, x.a.shift), x, km)
-               : launch_a6w4<4>(c, a_table, w_scale_dtype, GemmA6W4Cfg<4, 4>::lds_fc1(G, x.a.shift), x, km);
-  };
-  GemmFc1X xx;
-  static_cast<GemmFc1&>(xx) = xe;
-  const int rc = fp6_pair ? run(xx) : run(xe);
-  if (rc) return rc;
-  return nan_flag ? fpq_internal_zero_if_flag(out, tokens * outs * 2, nan_flag, stream) : FPQ_OK;
-}
-int fpq_gemm_a6w4_gelu_dual(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
-                            int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs, int64_t k,
-                            void* nan_flag, fpq_stream_t stream) {
-  return gemm_a6w4_gelu_dual_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, bias, out, gelu_out, tokens, outs, k, nan_flag,
-                                  false, stream);
-}
-int fpq_gemm_a6w4_gelu_dual_km(const uint8_t* a_image, const void* a_scales, int a_table, const uint8_t* w_image, const void* w_scales,
-                               int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs, int64_t k,
-                               void* nan_flag, fpq_stream_t stream) {
-  return gemm_a6w4_gelu_dual_impl(a_image, a_scales, a_table, w_image, w_scales, w_scale_dtype, bias, out, gelu_out, tokens, outs, k, nan_flag,
-                                  true, stream);
-}
-
-// the same with the tail's dual pair and the layout as arguments (include/fpq.h, GF6)
-int fpq_gemm_a6w4_gelu_dual_pair(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
-                                 int w_scale_dtype, const void* bias, void* out, void* gelu_out, int64_t tokens, int64_t outs, int64_t k,
-                                 void* nan_flag, int neg_table, int pos_table, int kmajor, fpq_stream_t stream) {
-  return gemm_a6w4_gelu_dual_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, bias, out, gelu_out, tokens, outs, k, nan_flag,
-                                  kmajor != 0, stream, neg_table, pos_table);
 }
 
 static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, const uint8_t* w_codes,

@@ -1,48 +1,80 @@
-// fpq_gemm_w6_kernel.h - the text of the W6 GEMM kernel.  NOT a header of its own: fpq_gemm_w6.h includes it once per kernel it
-// defines, with
-//   FPQ_W6_KERNEL   the kernel's name
-//   FPQ_W6_FC1      0: the plain epilogue (+ gate / residual tail); 1 / 2: the fc1 tail (FPQ_GEMM_FC1_TAIL, fpq_gemm_fp4.h; 2: its NaN-excluding form, FPQ_GEMM_FC1_TAIL_X) - the kernel
-//                   takes a GemmFc1 behind the GemmEpi and stages the dual quantizer's bucket table behind the scale tiles
-//   FPQ_W6_OUT      (FPQ_W6_FC1 == 0 only) 0: one [T, O] tensor; 1: the SPLIT OUTPUT of GemmEpi's sp_* fields (mat_qkv: q to its own
+// fpq_gemm_g6_kernel.h - the text of the per-group(128) GEMM kernel with a 6-bit side: the "A6W4" kernels (6-bit activation codes
+// against E2M1 weight nibbles) and the "W6" kernels (a 6-bit weight against an E2M1, E1M2 or E3M0 activation) are this one text.
+// NOT a header of its own: fpq_gemm_g6.h includes it once per kernel it defines, with
+//   FPQ_G6_KERNEL   the kernel's name
+//   FPQ_G6_FC1      0: the plain epilogue (+ gate / residual tail); 1 / 2: the fc1 tail (FPQ_GEMM_FC1_TAIL, fpq_gemm_fp4.h; 2: its
+//                   NaN-excluding form, FPQ_GEMM_FC1_TAIL_X) - the kernel takes a GemmFc1 behind the GemmEpi and stages the dual
+//                   quantizer's bucket table behind the scale tiles
+//   FPQ_G6_OUT      (FPQ_G6_FC1 == 0 only) 0: one [T, O] tensor; 1: the SPLIT OUTPUT of GemmEpi's sp_* fields (mat_qkv: q to its own
 //                   tensor, k and v into the KV cache's slots), the plain epilogue's values bit for bit, no gate / residual tail;
 //                   2: the split output with the Q / K L2 NORM in front of it (FPQ_QK_NORM_ROW, fpq_gemm_fp4.h) - the kernel takes a
 //                   GemmQkNorm behind the GemmEpi, its fp32 bias replaces the fp16 one
-//   FPQ_W6_KM       0: row-major codes and scales; 1: K-MAJOR IMAGES (include/fpq.h) - A is the activation side's 4-bit image
-//                   [G][T][64] (FA = 4: the FP4 kernel's km addressing) or 6-bit image [G][T][96] (FA = 2 / 3: gemm_a6w4_km_kernel's), W
-//                   the dealt 6-bit image [G][km_w_rows][96] (the FP6 kernel's) and sa / sw the fp32 scale images [G][T rounded up to 4] /
-//                   [G][km_w_rows]: every piece of a stage is 1 KiB (a super-block 3 KiB) contiguous, and the scale tiles come in by
-//                   LDS-DMA too.  Tsw = float only; epi.km_w_rows = outs rounded up to 64.
-// (one text, compiled under several names, as fpq_gemm_a6w4_kernel.h is: only the register epilogue and the extra argument differ -
-// with FPQ_W6_KM only the LDS-DMA sources and the scale-tile load; the row-major kernels keep their symbols and, instruction for
-// instruction, the machine code they had before the other forms existed - profiles/w6_forms_isa.txt, w6_km_isa.txt)
-#if FPQ_W6_KM
-#define FPQ_W6_TSA float
-#else
-#define FPQ_W6_TSA _Float16
+//   FPQ_G6_KM       0: row-major codes and scales (fp16 activation scales); 1: K-MAJOR IMAGES (include/fpq.h) - per side the 4-bit
+//                   image [G][rows][64] or the 6-bit image [G][rows][96], the weight's rows dealt and padded to epi.km_w_rows (outs
+//                   rounded up to 64), and sa / sw the fp32 scale images [G][T rounded up to 4] / [G][km_w_rows]: every piece of a
+//                   stage is 1 KiB contiguous, and the scale tiles come in by LDS-DMA too.  Tsw = float only.
+//   FPQ_G6_W4       1: the weight format is fixed to E2M1 (FW = 4) and the template takes <Tsw, MT, NT, FA> - the A6W4 kernels'
+//                   signature, so their symbols are what they were; 0: <Tsw, MT, NT, FA, FW>, FW = 2 / 3
+// An absent parameter is 0, and the text #undefs all five at its end: an instantiation is the name, the non-zero parameters and
+// the #include.
+// Either side's tile of a stage and fragment of a lane (32 consecutive k of k-block lane >> 4) come in one of two forms, chosen
+// at compile time per side (A4, W4):
+//   * nibbles (FA = 4 / FW = 4): gemm_fp4_glds_kernel's 16-row, 1 KiB blocks - glds_chunk_perm, one ds_read_b128 per fragment;
+//   * 6-bit codes (2 / 3), activation side: the FP6 kernel's 32-row, 3 KiB super-blocks (fpq_gemm_fp6_kernel.h) - fp6_rot, three
+//     ds_read_b64 per fragment; first used against nibbles by the A6W4 kernel;
+//   * 6-bit codes, weight side: the FP6 kernel's weight super-blocks, rows dealt over a wavefront's NT tiles; first used by the W6
+//     kernel.  (A nibble weight block is dealt the same way.)
+// The tile walk, the LDS-DMA issue, the scale tiles, the software-pipelined main loop and the register epilogues do not depend on
+// the forms.  Every kernel's machine code is, instruction for instruction, what the two families' separate texts gave:
+// profiles/g6_merge_isa.txt.
+#ifndef FPQ_G6_FC1
+#define FPQ_G6_FC1 0
 #endif
+#ifndef FPQ_G6_OUT
+#define FPQ_G6_OUT 0
+#endif
+#ifndef FPQ_G6_KM
+#define FPQ_G6_KM 0
+#endif
+#ifndef FPQ_G6_W4
+#define FPQ_G6_W4 0
+#endif
+#if FPQ_G6_KM
+#define FPQ_G6_TSA float
+#else
+#define FPQ_G6_TSA _Float16
+#endif
+#if FPQ_G6_W4
+template <typename Tsw, int MT, int NT, int FA>
+#else
 template <typename Tsw, int MT, int NT, int FA, int FW>
-__global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* __restrict__ A, const FPQ_W6_TSA* __restrict__ sa,
+#endif
+__global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_G6_KERNEL(const uint8_t* __restrict__ A, const FPQ_G6_TSA* __restrict__ sa,
                                                                  const uint8_t* __restrict__ W, const Tsw* __restrict__ sw,
                                                                  const _Float16* __restrict__ bias, _Float16* out, int T, int O, int C,
                                                                  GemmEpi epi
-#if FPQ_W6_FC1
+#if FPQ_G6_FC1
                                                                  , GemmFc1 xe
-#elif FPQ_W6_OUT == 2
+#elif FPQ_G6_OUT == 2
                                                                  , GemmQkNorm xe
 #endif
                                                                  ) {
+#if FPQ_G6_W4
+  constexpr int FW = 4;
+#endif
   static_assert(FA == 4 || FA == 2 || FA == 3, "activation format: 4 = FP4 E2M1, 2 = FP6 E2M3 (E1M2 levels), 3 = BF6 E3M2 (E3M0 levels)");
-  static_assert(FW == 2 || FW == 3, "weight format: 2 = FP6 E2M3 (E1M2 levels), 3 = BF6 E3M2 (E3M0 levels)");
+  static_assert(FW == 4 || FW == 2 || FW == 3, "weight format: 4 = FP4 E2M1, 2 = FP6 E2M3 (E1M2 levels), 3 = BF6 E3M2 (E3M0 levels)");
+  static_assert(FA != 4 || FW != 4, "one side is 6-bit: the E2M1 x E2M1 product is gemm_fp4_glds_kernel's");
   static_assert(NT == 4, "the epilogue packs a lane's NT results of one row into one 8-byte store");
-  constexpr bool A4 = FA == 4;
+  constexpr bool A4 = FA == 4, W4 = FW == 4;
   constexpr int WR = 2, WC = 2, BM = 16 * MT * WR, BN = 16 * NT * WC, NTHR = 256;
   static_assert(BM % 64 == 0 && BN % 32 == 0, "whole super-blocks; load_scale_tiles wants the A / W boundary wavefront-uniform");
-  constexpr int A_SEG = A4 ? 64 : 96, A_TILE = 16 * A_SEG;                  // bytes of a row per group, of a 16-row tile
-  constexpr int APC = BM * A_SEG / 1024, WPC = 3 * (BN / 32), NPC = APC + WPC;   // pieces of A, of W, of a stage
+  constexpr int A_SEG = A4 ? 64 : 96, W_SEG = W4 ? 64 : 96, A_TILE = 16 * A_SEG, W_TILE = 16 * W_SEG;   // bytes of a row per group, of a 16-row tile
+  constexpr int APC = BM * A_SEG / 1024, WPC = BN * W_SEG / 1024, NPC = APC + WPC;                     // pieces of A, of W, of a stage
   constexpr int ABYTES = APC * 1024, STAGE = NPC * 1024;
   constexpr int PIECES = (NPC + 3) / 4;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int G = C >> 7, a_row_bytes = A4 ? C >> 1 : (C >> 2) * 3, w_row_bytes = (C >> 2) * 3;
+  const int G = C >> 7, a_row_bytes = A4 ? C >> 1 : (C >> 2) * 3, w_row_bytes = W4 ? C >> 1 : (C >> 2) * 3;
   float* lsa = (float*)(smem + 2 * STAGE);   // [G][BM]
   const int Gp = (G + 3) & ~3;
   float* lsw = lsa + Gp * BM;                // [G][BN]
@@ -57,15 +89,15 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
 
   // LDS-DMA sources: a uniform base per operand + a 32-bit lane offset that never changes (see gemm_fp4_glds_kernel); rows past
   // the end of a tensor are clamped to its last row - their products land where the epilogue never stores
-#if FPQ_W6_KM
+#if FPQ_G6_KM
   static_assert(__is_same(Tsw, float), "the k-major scale images are fp32");
   // plane g of an image holds every row's 64 / 96 bytes of group g, chunks in the LDS image's order (no glds_chunk_perm, no fp6_rot
   // here), weight rows in dealt order and padded to km_w_rows: the lane fetches the physical chunk of its image row
-  // (gemm_fp4_glds_kernel, gemm_a6w4_km_kernel, fpq_gemm_fp6_kernel.h)
-  const int64_t a_step = (int64_t)T * A_SEG, w_step = (int64_t)epi.km_w_rows * 96;
+  // (gemm_fp4_glds_kernel, fpq_gemm_fp6_kernel.h)
+  const int64_t a_step = (int64_t)T * A_SEG, w_step = (int64_t)epi.km_w_rows * W_SEG;
   (void)a_row_bytes, (void)w_row_bytes;
   const uint8_t* const a_base_g = A + (int64_t)t0 * A_SEG;
-  const uint8_t* const w_base_g = W + (int64_t)o0 * 96;
+  const uint8_t* const w_base_g = W + (int64_t)o0 * W_SEG;
   uint32_t voff[PIECES];
 #pragma unroll
   for (int i = 0; i < PIECES; ++i) {
@@ -80,14 +112,17 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
         const int t = t0 + sb * 32 + r;
         voff[i] = (uint32_t)((t < T ? t : T - 1) - t0) * 96u + (uint32_t)(pc * 16);
       }
-    } else {                                            // the weight side's super-blocks: the dealing is in the image
+    } else if constexpr (W4) {                          // the weight side, image row o: the dealing is in the image
+      const int o = o0 + (piece - APC) * 16 + (lane >> 2);
+      voff[i] = (uint32_t)((o < epi.km_w_rows ? o : epi.km_w_rows - 1) - o0) * 64u + (uint32_t)((lane & 3) * 16);
+    } else {
       const int wp = piece - APC, sb = wp / 3, ci = (wp % 3) * 64 + lane;
       const int r = ci / 6, pc = ci - 6 * r;
-      const int o = o0 + sb * 32 + r;                   // image row
+      const int o = o0 + sb * 32 + r;
       voff[i] = (uint32_t)((o < epi.km_w_rows ? o : epi.km_w_rows - 1) - o0) * 96u + (uint32_t)(pc * 16);
     }
   }
-#define FPQ_W6_ISSUE(g, buf)                                                                                        \
+#define FPQ_G6_ISSUE(g, buf)                                                                                        \
   _Pragma("unroll") for (int i_ = 0; i_ < PIECES; ++i_) {                                                           \
     const int piece_ = wave + 4 * i_;                                                                               \
     if (piece_ < NPC)   /* wavefront-uniform */                                                                     \
@@ -98,9 +133,9 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
                                                                                        piece_ * 1024))             \
                    : "m0");                                                                                         \
   }
-  FPQ_W6_ISSUE(0, 0);
+  FPQ_G6_ISSUE(0, 0);
   {
-    // the scale tiles by LDS-DMA, gemm_a6w4_km_kernel's block (gemm_fp4_glds_kernel's `if (km)`): a group's scales of the tile are
+    // the scale tiles by LDS-DMA, gemm_fp4_glds_kernel's `if (km)` block: a group's scales of the tile are
     // 4 BM (4 BN) contiguous bytes = one row of lsa (lsw); 256 / BM groups per activation piece, two per weight piece, a last
     // piece's surplus groups re-read the last one (their LDS rows are the padding up to Gp); rows clamped to the image's last four.
     // The main loop's first vmcnt(0) covers them - the compiler has issued no load of its own that it would have to wait for.
@@ -140,7 +175,11 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
         const int t = t0 + sb * 32 + r;
         voff[i] = (uint32_t)((t < T ? t : T - 1) - t0) * (uint32_t)a_row_bytes + (uint32_t)(c * 16);
       }
-    } else {                                            // the weight side's super-blocks, rows dealt over the wavefront's NT tiles
+    } else if constexpr (W4) {                          // the weight side, rows dealt over the wavefront's NT tiles: a 16-row block
+      const int wb = piece - APC, q = lane >> 2, kb = (lane & 3) ^ glds_chunk_perm(q);
+      const int o = o0 + (wb / NT) * (16 * NT) + NT * q + wb % NT;
+      voff[i] = (uint32_t)((o < O ? o : O - 1) - o0) * (uint32_t)w_row_bytes + (uint32_t)(kb * 16);
+    } else {                                            // ... a super-block
       const int wp = piece - APC, sb = wp / 3, ci = (wp % 3) * 64 + lane;
       const int r = ci / 6, pc = ci - 6 * r;
       int c = pc - fp6_rot(r);
@@ -150,22 +189,22 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
       voff[i] = (uint32_t)((o < O ? o : O - 1) - o0) * (uint32_t)w_row_bytes + (uint32_t)(c * 16);
     }
   }
-#define FPQ_W6_ISSUE(g, buf)                                                                                        \
+#define FPQ_G6_ISSUE(g, buf)                                                                                        \
   _Pragma("unroll") for (int i_ = 0; i_ < PIECES; ++i_) {                                                           \
     const int piece_ = wave + 4 * i_;                                                                               \
     if (piece_ < NPC)   /* wavefront-uniform */                                                                     \
       asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                                 \
                    :                                                                                                \
-                   : "v"(voff[i_]), "s"(piece_ < APC ? a_base_g + (g) * A_SEG : w_base_g + (g) * 96),               \
+                   : "v"(voff[i_]), "s"(piece_ < APC ? a_base_g + (g) * A_SEG : w_base_g + (g) * W_SEG),            \
                      "s"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + (buf) * STAGE +     \
                                                                                        piece_ * 1024))             \
                    : "m0");                                                                                         \
   }
-  FPQ_W6_ISSUE(0, 0);
+  FPQ_G6_ISSUE(0, 0);
   load_scale_tiles<Tsw, BM, BN, NTHR>(sa, sw, lsa, lsw, t0, o0, T, O, G, tid);
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), the builtin: the compiler's scoreboard forgets the scale loads (gemm_fp4_glds_kernel)
 #endif
-#if FPQ_W6_FC1
+#if FPQ_G6_FC1
   // the dual quantizer's bucket table, behind the scale tiles; visible after the first barrier of the main loop
   uint16_t* lut = (uint16_t*)(lsw + Gp * BN);
   lut16_stage(lut, xe.tab, xe.a.shift);
@@ -174,8 +213,8 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
   constexpr int WROWS = 16 * MT, WCOLS = 16 * NT;
   const int o = o0 + wn * WCOLS + NT * (lane & 15);
   const int oc = o < O ? o : O - 4;
-#if !FPQ_W6_FC1 && FPQ_W6_OUT == 2
-  // the fp32 bias of the lane's outputs and s_h of its head in part 0, as gemm_a6w4_qkn_kernel reads them (the fp16 bias is NULL here)
+#if !FPQ_G6_FC1 && FPQ_G6_OUT == 2
+  // the fp32 bias of the lane's outputs and s_h of its head in part 0, as gemm_fp4_glds_kernel reads them (the fp16 bias is NULL here)
   v4f_t qkn_b = v4f_t{0, 0, 0, 0};
   float qkn_s = 1.0f;
   if (xe.bias) qkn_b = *(const v4f_t*)(xe.bias + oc);
@@ -191,7 +230,9 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
 #pragma unroll
     for (int n = 0; n < NT; ++n) acc[m][n] = v4f_t{0, 0, 0, 0};
 
-  // a 6-bit fragment: three 8-byte pieces inside a 16-row half of a super-block; a nibble fragment: row lane & 15, chunk lane >> 4
+  // a 6-bit fragment: three 8-byte pieces inside a 16-row half of a super-block (foff); a nibble fragment: row lane & 15, chunk
+  // lane >> 4 of a 16-row block (nib_off).  With nibble weights foff[] addresses the activation fragment alone and carries the
+  // wavefront's activation base (one add less per read); otherwise it addresses the weight fragment too and the base stays in a_off.
   const int fr = lane & 15, kblk = lane >> 4;
   int foff[3];
 #pragma unroll
@@ -199,20 +240,22 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
     const int b = kblk * 24 + 8 * t;
     int pc = (b >> 4) + fp6_rot(fr);
     pc = pc >= 6 ? pc - 6 : pc;
-    foff[t] = fr * 96 + pc * 16 + (b & 15);
+    foff[t] = (W4 ? wm * MT * A_TILE : 0) + fr * 96 + pc * 16 + (b & 15);
   }
-  const int a_off = wm * MT * A_TILE + (A4 ? (fr << 6) + (((kblk ^ glds_chunk_perm(fr)) & 3) << 4) : 0);
-  const int b_off = ABYTES + wn * NT * 1536;
+#define FPQ_G6_NIB_OFF ((fr << 6) + (((kblk ^ glds_chunk_perm(fr)) & 3) << 4))
+  const int a_off = (W4 ? 0 : wm * MT * A_TILE) + (A4 ? FPQ_G6_NIB_OFF : 0);
+  const int b_off = ABYTES + wn * NT * W_TILE + (W4 ? FPQ_G6_NIB_OFF : 0);
+#undef FPQ_G6_NIB_OFF
   const int sa_off = wm * MT * 16 + 4 * kblk, sw_off = wn * NT * 16 + NT * fr;   // outputs 4q .. 4q+3: tile n holds 4q + n
-  // the activation fragment of the 16-row tile at p_ (= stage + tile row * A_TILE)
-#define FPQ_W6_READ_A(dst_, p_)                                                                                     \
+  // the fragment of the 16-row tile at p_ (= stage + the side's offset + the tile's): one ds_read_b128 of nibbles or three ds_read_b64
+#define FPQ_G6_READ(dst_, nibbles_, p_)                                                                             \
   do {                                                                                                              \
-    if constexpr (A4) {                                                                                             \
-      const u32x4 q_ = *(const u32x4*)((p_) + a_off);                                                               \
+    if constexpr (nibbles_) {                                                                                       \
+      const u32x4 q_ = *(const u32x4*)(p_);                                                                         \
       dst_ = v8i_t{(int)q_[0], (int)q_[1], (int)q_[2], (int)q_[3], 0, 0, 0, 0};                                     \
     } else {                                                                                                        \
-      const u32x2 q0_ = FPQ_LDS_READ64((p_) + a_off + foff[0]), q1_ = FPQ_LDS_READ64((p_) + a_off + foff[1]),       \
-                  q2_ = FPQ_LDS_READ64((p_) + a_off + foff[2]);                                                     \
+      const u32x2 q0_ = FPQ_LDS_READ64((p_) + foff[0]), q1_ = FPQ_LDS_READ64((p_) + foff[1]),                       \
+                  q2_ = FPQ_LDS_READ64((p_) + foff[2]);                                                             \
       dst_ = v8i_t{(int)q0_[0], (int)q0_[1], (int)q1_[0], (int)q1_[1], (int)q2_[0], (int)q2_[1], 0, 0};             \
     }                                                                                                               \
   } while (0)
@@ -220,20 +263,16 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
   for (int g = 0; g < G; ++g) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the compiler does not see the LDS-DMA loads
     FPQ_SYNC();   // stage g has landed; stage g^1's readers are done
-    if (g + 1 < G) { FPQ_W6_ISSUE(g + 1, (g + 1) & 1); }
+    if (g + 1 < G) { FPQ_G6_ISSUE(g + 1, (g + 1) & 1); }
     const uint8_t* st = smem + (g & 1) * STAGE;
     // the software pipeline of gemm_fp4_glds_kernel: the reads of tile row m+1, the NT MFMAs of row m, the scale-and-accumulate
     // of row m-1
     v8i_t bf[NT];
 #pragma unroll
-    for (int n = 0; n < NT; ++n) {
-      const uint8_t* p = st + b_off + n * 1536;
-      const u32x2 q0 = FPQ_LDS_READ64(p + foff[0]), q1 = FPQ_LDS_READ64(p + foff[1]), q2 = FPQ_LDS_READ64(p + foff[2]);
-      bf[n] = v8i_t{(int)q0[0], (int)q0[1], (int)q1[0], (int)q1[1], (int)q2[0], (int)q2[1], 0, 0};
-    }
+    for (int n = 0; n < NT; ++n) FPQ_G6_READ(bf[n], W4, st + b_off + n * W_TILE);
     const v4f_t sw1 = *(const v4f_t*)(lsw + g * BN + sw_off);
     v8i_t af;
-    FPQ_W6_READ_A(af, st);
+    FPQ_G6_READ(af, A4, st + a_off);
     v4f_t sa4 = *(const v4f_t*)(lsa + g * BM + sa_off);
     v4f_t d_prev[NT], sa4_prev = sa4;
 #pragma unroll
@@ -243,7 +282,7 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
       v8i_t af_n = af;
       v4f_t sa4_n = sa4;
       if (m + 1 < MT) {
-        FPQ_W6_READ_A(af_n, st + (m + 1) * A_TILE);
+        FPQ_G6_READ(af_n, A4, st + (m + 1) * A_TILE + a_off);
         sa4_n = *(const v4f_t*)(lsa + g * BM + sa_off + (m + 1) * 16);
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -251,7 +290,7 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
       if (m < MT) {
 #pragma unroll
         for (int n = 0; n < NT; ++n)
-          // cbsz = FA decodes the activation fragment, blgp = FW the 6-bit weight fragment; literal zero scales: the unscaled instruction
+          // cbsz = FA decodes the activation fragment, blgp = FW the weight fragment; literal zero scales: the unscaled instruction
           d[n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf[n], v4f_t{0, 0, 0, 0}, FA, FW, 0, 0, 0, 0);
       }
       if (m > 0) {
@@ -280,33 +319,33 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
       sa4 = sa4_n;
     }
   }
-#undef FPQ_W6_READ_A
-#undef FPQ_W6_ISSUE
-#undef FPQ_W6_TSA
+#undef FPQ_G6_READ
+#undef FPQ_G6_ISSUE
+#undef FPQ_G6_TSA
 
-  // epilogue from the registers, as gemm_a6w4_kernel's: + bias, one rounding to fp16, then the form's own tail, 8-byte stores
-#if FPQ_W6_FC1 || FPQ_W6_OUT != 2
+  // epilogue from the registers, as gemm_fp4_glds_kernel's: + bias, one rounding to fp16, then the form's own tail, 8-byte stores
+#if FPQ_G6_FC1 || FPQ_G6_OUT != 2
   v4f_t b4 = v4f_t{0, 0, 0, 0};
 #pragma unroll
   for (int n = 0; n < NT; ++n) b4[n] = (float)bias_h[n];
 #endif
-#if FPQ_W6_FC1
+#if FPQ_G6_FC1
   // the maxima exchange goes into stage buffer G & 1, which the last K group does not read (and nothing was loaded into after
   // the group before it was read: the last issue fills buffer (G - 1) & 1); this form has no gate / residual tail: epi is not read
-#if FPQ_W6_FC1 == 2
+#if FPQ_G6_FC1 == 2
   FPQ_GEMM_FC1_TAIL_X(STAGE, true);   // the dual pair without a global clamp: a NaN stays out of the maxima
 #else
   FPQ_GEMM_FC1_TAIL(STAGE);
 #endif
-#elif FPQ_W6_OUT
-  // the split output, as gemm_a6w4_split_kernel stores it (same tile, same lane-to-output mapping: a lane's four values of row i are
+#elif FPQ_G6_OUT
+  // the split output, as gemm_fp4_glds_kernel stores it (same tile, same lane-to-output mapping: a lane's four values of row i are
   // four consecutive columns of one part, a token row's head of 64 columns is the 16 lanes of a DPP row); no gate / residual tail
   FPQ_GEMM_SPLIT_SETUP(WROWS, true);
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);
     fpq_h4_t y[4];
-#if FPQ_W6_OUT == 2
+#if FPQ_G6_OUT == 2
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       float yf[NT];
@@ -347,3 +386,8 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_W6_KERNEL(const uint8_t* 
   }
 #endif
 }
+#undef FPQ_G6_KERNEL
+#undef FPQ_G6_FC1
+#undef FPQ_G6_OUT
+#undef FPQ_G6_KM
+#undef FPQ_G6_W4

@@ -1,4 +1,4 @@
-// fpq_gemm_launch.h - what the GEMM entry points of fpq_gemm.hip and fpq_gemm_w6.hip share on the host: the
+// fpq_gemm_launch.h - what the GEMM entry points of fpq_gemm.hip and fpq_gemm_g6.hip share on the host: the
 // epilogue, split-output and q / k norm descriptors -> the kernels' form, the tile choice of the per-group LDS-DMA kernels, the
 // launch.  Included inside the unit's anonymous namespace, behind fpq_gemm_fp4.h (GemmEpi, GemmQkNorm).
 #pragma once

@@ -398,7 +398,7 @@ __device__ __forceinline__ void rq_store_codes6(u32x4* buf, const uint32_t (&yw)
 // HW4 (E2M1 values or FP4 operands): levels / codes from the FP4 conversion hardware (fpq_fast16.h) - no table lookups
 // SMOOTH (the GALT vector applied in front of the rotation: 32 more floats per lane and tile in flight) takes 5 wavefronts
 // per SIMD = 96 registers: at 80 it spilled 3 - 8 of them (tests/test_no_spill.py reads every kernel's metadata).
-// G6 (CODES, table E1M2 / E3M0): the A6W4 GEMM's activation operands instead (fpq_gemm_a6w4.h) - dense 6-bit codes, 96 bytes per
+// G6 (CODES, table E1M2 / E3M0): the A6W4 GEMM's activation operands instead (fpq_gemm_g6.h) - dense 6-bit codes, 96 bytes per
 // group, from the staged bucket -> code table lut16_codes_g6, + one scale per group; row-major or the k-major images (r.km_rows)
 template <typename Tin, bool EMIT, bool SMOOTH, bool CODES = false, bool HW4 = false, bool G6 = false>
 __global__ __launch_bounds__(kBlock, SMOOTH ? FPQ_ROT_WAVES - 1 : FPQ_ROT_WAVES) void rotate_quant_mfma_kernel(const void* __restrict__ xv,

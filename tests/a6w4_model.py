@@ -1,4 +1,4 @@
-"""What the A6W4 GEMM (fpqvar_amd/csrc/fpq_gemm_a6w4.h: E1M2 / E3M0 activations as dense 6-bit codes against E2M1 weight nibbles,
+"""What the A6W4 GEMM (fpqvar_amd/csrc/fpq_gemm_g6.h: E1M2 / E3M0 activations as dense 6-bit codes against E2M1 weight nibbles,
 per-group(128) scales on both sides) must compute, in the terms of tests/gemm_model.py.
 
 Shared by tests/test_a6w4_host.py (CPU) and tests/test_gpu_a6w4.py (the kernel).

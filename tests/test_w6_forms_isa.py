@@ -1,5 +1,5 @@
 """CPU-only: the gfx950 code of every gemm_w6_fc1_kernel, gemm_w6_split_kernel and gemm_w6_qkn_kernel instantiation in libfpq_hip.so
-(fpq_gemm_w6.h: the W6 GEMM's fc1 tail, split output and split output with the q / k norm - three activation formats x two weight
+(fpq_gemm_g6.h: the W6 GEMM's fc1 tail, split output and split output with the q / k norm - three activation formats x two weight
 formats x two tilings each), read from the library's code objects the way tests/test_w6_isa.py reads the plain kernel's.  All 36
 fit: none is routed to the smaller tiling.  The test is about registers, LDS and the matrix instruction - nothing else."""
 import re

@@ -1,4 +1,4 @@
-"""CPU-only: the gfx950 code of every gemm_w6_kernel instantiation in libfpq_hip.so (fpq_gemm_w6.h: three activation formats x two
+"""CPU-only: the gfx950 code of every gemm_w6_kernel instantiation in libfpq_hip.so (fpq_gemm_g6.h: three activation formats x two
 weight formats x two tilings), read from the library's code objects the way tests/test_gemm_ring_isa.py reads them: no spill, no
 scratch, dynamic LDS only; every matrix instruction is the f8f6f4 MFMA with the instantiation's format selectors."""
 import re

@@ -1,5 +1,5 @@
 """CPU-only: the gfx950 code of every gemm_w6_km_kernel, gemm_w6_fc1_km_kernel, gemm_w6_split_km_kernel and gemm_w6_qkn_km_kernel
-instantiation in libfpq_hip.so (fpq_gemm_w6.h: the W6 GEMM's four forms on k-major images - three activation formats x two weight
+instantiation in libfpq_hip.so (fpq_gemm_g6.h: the W6 GEMM's four forms on k-major images - three activation formats x two weight
 formats x two tilings each), read from the library's code objects the way tests/test_w6_forms_isa.py reads the row-major forms'.
 All 48 fit: none is routed to the smaller tiling.  The test is about registers, LDS and the matrix instruction - nothing else."""
 import re

@@ -1,4 +1,4 @@
-"""What the W6 GEMM (fpqvar_amd/csrc/fpq_gemm_w6.h: E1M2 / E3M0 WEIGHTS as dense 6-bit codes against an E2M1, E1M2 or E3M0
+"""What the W6 GEMM (fpqvar_amd/csrc/fpq_gemm_g6.h: E1M2 / E3M0 WEIGHTS as dense 6-bit codes against an E2M1, E1M2 or E3M0
 activation, per-group(128) scales on both sides) must compute, in the terms of tests/gemm_model.py and tests/a6w4_model.py.
 
 Shared by tests/test_w6_host.py (CPU) and tests/test_gpu_w6.py (the kernel).
