@@ -211,6 +211,13 @@ _SIGS = {
                                                            _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64,
                                                            _c.c_float, _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int,
                                                            _c.c_void_p]),
+    # the same two producers on the full FP6 tables (E2M3 / E3M2): the twins' argument lists
+    "fpq_gf6_rotate_quant_rows_codes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
+                                                    _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int, _c.c_void_p]),
+    "fpq_gf6_adaln_rotate_quant_rows_codes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64,
+                                                          _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64,
+                                                          _c.c_float, _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int,
+                                                          _c.c_void_p]),
     # per-group(128) quantization on the full FP6 tables to dense 6-bit codes (table, dtype, layout: arguments)
     "fpq_gf6_quant_rows_codes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int,
                                              _c.c_void_p]),

@@ -1,4 +1,4 @@
-// fpq_adaln.hip - the adaLN producer (fpq_adaln.h: LayerNorm, modulation, rotation and quantizer in one launch) and its nine
+// fpq_adaln.hip - the adaLN producer (fpq_adaln.h: LayerNorm, modulation, rotation and quantizer in one launch) and its ten
 // C entry points.  A unit of its own because its ~230 kernel forms take longer to compile than the rest of the quantizers
 // together: an edit elsewhere does not recompile them.
 #include "fpq_common.h"
@@ -15,12 +15,15 @@ int launch_adaln_rotate_quant(const void* x, void* out, void* h_out, void* y_out
                               int token_mode = 0 /*1: per-token values, 2: per-token E4M3 codes, 3: per-token packed 6-bit codes*/,
                               const Lut16Tab* token_code_tab = nullptr,
                               bool km = false /* FP4 / 6-bit codes into a k-major image (include/fpq.h): adaln_mfma_kernel only */,
-                              bool g6 = false /* per group, code_scales: the A6W4 GEMM's 6-bit codes of table_id (E1M2 / E3M0) instead of
-                                                 FP4; adaln_mfma_kernel only */) {
+                              bool g6 = false /* per group, code_scales: dense 6-bit group codes of table_id instead of FP4 - the A6W4
+                                                 GEMM's (E1M2 / E3M0) or the full tables' (E2M3 / E3M2); adaln_mfma_kernel only */) {
   const Lut16Host& h = lut16_host(table_id, table_id);
   if (!h.tab_valid) return FPQ_ERR_TABLE;
   if (g6 && (cols / 8 > 64 * 5 || !code_scales || token_mode)) return FPQ_ERR_SHAPE;
-  const Lut16Tab& tab = token_mode >= 2 ? *token_code_tab : g6 ? lut16_codes_g6(table_id) : (code_scales && !token_mode ? lut16_mx_codes_e2m1() : h.tab);
+  const bool full6 = table_id == FPQ_E2M3 || table_id == FPQ_E3M2;   // the table fpq_gf6_quant_rows_codes stages
+  const Lut16Tab& tab = token_mode >= 2 ? *token_code_tab
+                        : g6 ? (full6 ? lut16_codes6(table_id) : lut16_codes_g6(table_id))
+                             : (code_scales && !token_mode ? lut16_mx_codes_e2m1() : h.tab);
   RotArgs r;
   r.code_scales = code_scales;
   r.code_bits = (token_mode == 3 || g6) ? 6 : 8;
@@ -270,6 +273,22 @@ int fpq_a6w4_adaln_rotate_quant_rows_codes(const void* x, uint8_t* codes, void* 
                                            fpq_stream_t stream) {
   if (rows < 0 || cols < 0 || rows_per_batch <= 0 || !sign_mask_host) return FPQ_ERR_ARG;
   if (table_id != FPQ_E1M2 && table_id != FPQ_E3M0) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype) || !is_f16_or_f32(mod_dtype)) return FPQ_ERR_DTYPE;
+  if (cols % 128 != 0 || cols > 2560 || (kmajor && !km_image_fits(rows, cols / 4 * 3))) return FPQ_ERR_SHAPE;
+  if (rows == 0 || cols == 0) return FPQ_OK;
+  if (!x || !codes || !scales || !scale || !shift) return FPQ_ERR_ARG;
+  if ((((uintptr_t)codes | (uintptr_t)scales) & 15) != 0) return FPQ_ERR_ARG;   // (x, scale, shift, smooth: checked below)
+  return adaln_rotate_quant_impl(x, codes, nullptr, nullptr, scales, rows, cols, in_dtype, scale, shift, mod_dtype,
+                                 rows_per_batch, eps, smooth, sign_mask_host, table_id, stream, 0, nullptr, kmajor != 0, true);
+}
+
+// the same on the FULL FP6 tables (include/fpq.h, GF6): what fpq_gf6_quant_rows_codes makes of the rotated rows
+int fpq_gf6_adaln_rotate_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
+                                          const void* scale, const void* shift, int mod_dtype, int64_t rows_per_batch, float eps,
+                                          const float* smooth, const uint32_t* sign_mask_host, int table_id, int kmajor,
+                                          fpq_stream_t stream) {
+  if (rows < 0 || cols < 0 || rows_per_batch <= 0 || !sign_mask_host) return FPQ_ERR_ARG;
+  if (table_id != FPQ_E2M3 && table_id != FPQ_E3M2) return FPQ_ERR_TABLE;
   if (!is_f16_or_f32(in_dtype) || !is_f16_or_f32(mod_dtype)) return FPQ_ERR_DTYPE;
   if (cols % 128 != 0 || cols > 2560 || (kmajor && !km_image_fits(rows, cols / 4 * 3))) return FPQ_ERR_SHAPE;
   if (rows == 0 || cols == 0) return FPQ_OK;

@@ -14,10 +14,12 @@ template <typename Tin>
 int launch_rotate_quant(const void* x, void* out, void* rot_out, int64_t rows, int64_t cols, const float* smooth,
                         const uint32_t sign[4], int table_id, hipStream_t st, uint16_t* code_scales = nullptr,
                         bool km = false /* codes into a k-major image (include/fpq.h) */,
-                        bool g6 = false /* code_scales: the A6W4 GEMM's 6-bit codes of table_id (E1M2 / E3M0) instead of FP4 */) {
+                        bool g6 = false /* code_scales: dense 6-bit group codes of table_id instead of FP4 - the A6W4 GEMM's (E1M2 /
+                                           E3M0) or the full tables' (E2M3 / E3M2: fpq_gf6_rotate_quant_rows_codes) */) {
   const Lut16Host& h = lut16_host(table_id, table_id);
   if (!h.tab_valid) return FPQ_ERR_TABLE;
-  const Lut16Tab& tab = g6 ? lut16_codes_g6(table_id) : code_scales ? lut16_mx_codes_e2m1() : h.tab;
+  const bool full6 = table_id == FPQ_E2M3 || table_id == FPQ_E3M2;   // the table fpq_gf6_quant_rows_codes stages
+  const Lut16Tab& tab = g6 ? (full6 ? lut16_codes6(table_id) : lut16_codes_g6(table_id)) : code_scales ? lut16_mx_codes_e2m1() : h.tab;
   RotArgs r;
   r.code_scales = code_scales;
   r.code_bits = g6 ? 6 : 8;
@@ -37,12 +39,17 @@ int launch_rotate_quant(const void* x, void* out, void* rot_out, int64_t rows, i
   // values out, 3072 / 7680 / 12288 / 16384 workgroups: 83.2 / 82.2 / 82.1 / 80.3 us (one pass each at [65536 x 1920]);
   // codes out: 57.3 / 52.8 / 53.0 / 53.6 us (profiles/r03_rotate_grid.txt).  FPQ_ROT_WGS overrides.
   const bool hw4 = table_id == FPQ_E2M1 && !fpq_flag(OPT_FPQ_NO_HW4);   // E2M1 values or FP4 operands: levels / codes from the conversion hardware
+  // 6-bit group operands of the full tables: codes from the FP6 conversion hardware (rq_store_codes6_hw), table-free like the E2M1 forms
+  const bool hw6 = g6 && full6 && h.args.shift >= 6 /* its rare table path: <= 2 x 512 buckets */ && !fpq_flag(OPT_FPQ_NO_HW6);
   const int64_t per_wg = (int64_t)(kBlock / 64) * kRqTileVec;
   const int64_t wg_tiles = (n_vec + per_wg - 1) / per_wg;
   const int64_t resident_env = fpq_opt(OPT_FPQ_ROT_WGS, 0);
-  // (with a smoothing vector every workgroup stages it - 7.5 KiB at C = 1920 - so a few passes each: 7680 / 2560)
-  const int64_t resident = resident_env > 0 ? resident_env : !hw4 ? 2 * 256ll * FPQ_ROT_WAVES
-                           : smooth ? (code_scales ? 2560 : 7680) : code_scales ? 8192 : 16384;
+  // (with a smoothing vector every workgroup stages it - 7.5 KiB at C = 1920 - so a few passes each: 7680 / 2560; the 6-bit codes
+  // into a k-major image are the exception - at [65536 x 1920 / 2304] 8192 workgroups take 82.5 - 147.5 us where 2560 take 92.0 -
+  // 168.5 and the table form 92.1 - 168.0, fp16 and fp32 rows alike; row-major codes keep 2560: 67.0 against 71.8 us on fp16 rows -
+  // profiles/gf6_producers_ab.txt, the --grid section)
+  const int64_t resident = resident_env > 0 ? resident_env : !(hw4 || hw6) ? 2 * 256ll * FPQ_ROT_WAVES
+                           : smooth ? (code_scales ? (hw6 && km ? 8192 : 2560) : 7680) : code_scales ? 8192 : 16384;
   const int64_t passes = (wg_tiles + resident - 1) / resident;
   const dim3 mgrid((unsigned)((wg_tiles + passes - 1) / passes));
   auto go = [&](auto emit, auto codes) {   // EMIT: the rotated rows go out too; CODES: FP4 operands instead of values
@@ -54,8 +61,12 @@ int launch_rotate_quant(const void* x, void* out, void* rot_out, int64_t rows, i
       });
     });
   };
-  if (g6)   // (never E2M1: a table form)
+  if (g6)   // (never E2M1; E1M2 / E3M0 and FPQ_NO_HW6: the table form)
     return with_bool(smooth != nullptr, [&](auto sm) {
+      if (hw6 && table_id == FPQ_E2M3)
+        return launch(rotate_quant_mfma_kernel<Tin, false, sm.value, true, false, true, 1>, mgrid, lds, st, x, out, rot_out, n_vec, r, h.args, tab);
+      if (hw6)
+        return launch(rotate_quant_mfma_kernel<Tin, false, sm.value, true, false, true, 2>, mgrid, lds, st, x, out, rot_out, n_vec, r, h.args, tab);
       return launch(rotate_quant_mfma_kernel<Tin, false, sm.value, true, false, true>, mgrid, lds, st, x, out, rot_out, n_vec, r, h.args, tab);
     });
   if (code_scales) return go(Bool<false>{}, Bool<true>{});
@@ -104,6 +115,19 @@ int fpq_a6w4_rotate_quant_rows_codes(const void* x, uint8_t* codes, void* scales
                                      const float* smooth, const uint32_t* sign_mask_host, int table_id, int kmajor, fpq_stream_t stream) {
   if (rows < 0 || cols < 0 || !sign_mask_host) return FPQ_ERR_ARG;
   if (table_id != FPQ_E1M2 && table_id != FPQ_E3M0) return FPQ_ERR_TABLE;
+  if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
+  if (cols % 128 != 0 || (kmajor && !km_image_fits(rows, cols / 4 * 3))) return FPQ_ERR_SHAPE;
+  if (rows == 0 || cols == 0) return FPQ_OK;
+  if (!x || !codes || !scales) return FPQ_ERR_ARG;
+  if ((((uintptr_t)x | (uintptr_t)codes | (uintptr_t)scales | (uintptr_t)smooth) & 15) != 0) return FPQ_ERR_ARG;
+  return rotate_quant_impl(x, codes, nullptr, scales, rows, cols, in_dtype, smooth, sign_mask_host, table_id, stream, kmajor != 0, true);
+}
+
+// the same on the FULL FP6 tables (include/fpq.h, GF6): what fpq_gf6_quant_rows_codes makes of the rotated rows
+int fpq_gf6_rotate_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
+                                    const float* smooth, const uint32_t* sign_mask_host, int table_id, int kmajor, fpq_stream_t stream) {
+  if (rows < 0 || cols < 0 || !sign_mask_host) return FPQ_ERR_ARG;
+  if (table_id != FPQ_E2M3 && table_id != FPQ_E3M2) return FPQ_ERR_TABLE;
   if (!is_f16_or_f32(in_dtype)) return FPQ_ERR_DTYPE;
   if (cols % 128 != 0 || (kmajor && !km_image_fits(rows, cols / 4 * 3))) return FPQ_ERR_SHAPE;
   if (rows == 0 || cols == 0) return FPQ_OK;

@@ -389,6 +389,86 @@ __device__ __forceinline__ void rq_store_codes6(u32x4* buf, const uint32_t (&yw)
   __builtin_amdgcn_wave_barrier();
 }
 
+// entry i of the table image lut16_stage expands `tab` to, read straight from the by-value table (the kernel's arguments): for
+// rare paths of the kernels that stage no table
+__device__ __forceinline__ uint32_t lut16_arg_entry(const Lut16Tab& tab, int shift, uint32_t i) {
+  if (tab.n_pos == 0xFFFFu) return tab.e[i];
+  const uint32_t nh = 1u << (15 - shift), nan0 = 0x7C00u >> shift;
+  const bool neg = i >= nh;
+  const uint32_t j = neg ? i - nh : i;
+  const uint32_t np = neg ? tab.n_neg : tab.n_pos, base = neg ? tab.n_pos : 0u;
+  return j < np ? tab.e[base + j] : (j < nan0 ? (neg ? tab.fill_neg : tab.fill_pos) : 0u);
+}
+
+// rq_store_codes6 for the full tables E2M3 / E3M2 (BF6) with the codes taken from the FP6 conversion hardware (fpq_fast16.h,
+// fp6_levels_hw32): no table, no staging barrier, no lookups.  v_cvt_scalef32_2xpk16_{fp6,bf6}_f32 interleaves its two source
+// tuples - code 2 i from a[i], code 2 i + 1 from b[i] - and packs the 32 codes densely, code k at bits 6 k .. 6 k + 5 of its six
+// result dwords: with a[2 c + rr] / b[2 c + rr] the low / high halves of the quotient pair of yw[c][rr], bits 24 c .. 24 c + 23 are
+// the lane's piece c exactly as rq_store_codes6 packs it.  Byte for byte the table form's output:
+//   * ties: the conversion rounds to nearest even, the table (the reference's scan) to the larger value - the + 2^-17 of
+//     fp6_levels_hw32, which moves nothing else;
+//   * quotients in (-step / 2, 0) come out as -0 (0b100000) where the table has code 0: cleared per 24-bit piece (a field's sign
+//     bit survives only beside a non-zero magnitude: magnitude + 0b011111 carries into bit 5, never beyond);
+//   * a group whose scale is not finite has NaN quotients, which the conversion saturates: the wavefront then (rare, wave-uniform)
+//     expands the table of the kernel's arguments into its own image behind the tile's 1.5 KiB of codes - <= 2 x 512 buckets, 2 KiB
+//     of the 3 KiB left: shift >= 6, which the launch checks - and runs the table form itself: whatever the host table holds.
+constexpr int kRqCodes6Bytes = 16 * 96;
+template <bool BF6, typename OffFn>
+__device__ __forceinline__ void rq_store_codes6_hw(u32x4* buf, const uint32_t (&yw)[8][2], const RowScale16& s, const Lut16Tab& tab,
+                                                   int shift, __amdgpu_buffer_rsrc_t dst, int lane, OffFn off) {
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(!(s.sf < __builtin_inff())) != 0, 0)) {
+    uint16_t* lut = (uint16_t*)((char*)buf + kRqCodes6Bytes);
+    const int n_tab = 1 << (16 - shift), n_fit = (kRqImageBytes - kRqCodes6Bytes) / 2, n = n_tab < n_fit ? n_tab : n_fit;
+#pragma unroll 1
+    for (int i = rq_opaque(lane); i < n; i += 64) lut[i] = (uint16_t)lut16_arg_entry(tab, shift, (uint32_t)i);
+    __builtin_amdgcn_wave_barrier();
+    rq_store_codes6(buf, yw, s, lut, shift, dst, lane, off);
+    return;
+  }
+  uint32_t p[8];   // the lane's eight pieces: four codes in bits 0 .. 23 (the bits above are not written)
+  {
+    fp6_f16v_t a, b;
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) {
+        const uint32_t rb = div_pair16(yw[c][rr], s.inv, s.inv_lo, s.inv, s.inv_lo);
+        a[2 * c + rr] = fmaf_h_lo(rb, 1.0f, 0x1p-17f);
+        b[2 * c + rr] = fmaf_h_hi(rb, 1.0f, 0x1p-17f);
+      }
+    fp6_u6v_t d;
+    if constexpr (BF6)
+      asm("v_cvt_scalef32_2xpk16_bf6_f32 %0, %1, %2, 1.0" : "=&v"(d) : "v"(a), "v"(b));   // early clobber: a multi-pass instruction
+    else
+      asm("v_cvt_scalef32_2xpk16_fp6_f32 %0, %1, %2, 1.0" : "=&v"(d) : "v"(a), "v"(b));
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      p[4 * k] = d[3 * k];
+      p[4 * k + 1] = __builtin_amdgcn_alignbit(d[3 * k + 1], d[3 * k], 24);
+      p[4 * k + 2] = __builtin_amdgcn_alignbit(d[3 * k + 2], d[3 * k + 1], 16);
+      p[4 * k + 3] = d[3 * k + 2] >> 8;
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) p[c] &= ((p[c] & 0x7DF7DFu) + 0x7DF7DFu) | 0x7DF7DFu;   // -0 -> 0, field by field
+  }
+  lane = rq_opaque(lane);
+  const int g = lane & 15, quarter = lane >> 4;
+  const bool odd = (quarter & 1) != 0;
+  uint8_t* b8 = (uint8_t*)buf;
+  const int base = g * 96 + 3 * quarter;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const int at = base + 12 * c;                               // odd quarters sit at odd addresses
+    b8[odd ? at : at + 2] = (uint8_t)(odd ? p[c] : p[c] >> 16);
+    *(uint16_t*)(b8 + (odd ? at + 1 : at)) = (uint16_t)(odd ? p[c] >> 8 : p[c]);
+  }
+  __builtin_amdgcn_wave_barrier();
+  lane = rq_opaque(lane);
+  rq_store_code_chunk(buf[lane], dst, off(lane));   // chunk `lane` of the tile's 96: row-major lane * 16
+  if (lane < 32) rq_store_code_chunk(buf[64 + lane], dst, off(64 + lane));   // chunk 64 + lane: row-major 1024 + lane * 16
+  __builtin_amdgcn_wave_barrier();
+}
+
 #ifndef FPQ_ROT_WAVES
 #define FPQ_ROT_WAVES 6
 #endif
@@ -399,16 +479,21 @@ __device__ __forceinline__ void rq_store_codes6(u32x4* buf, const uint32_t (&yw)
 // SMOOTH (the GALT vector applied in front of the rotation: 32 more floats per lane and tile in flight) takes 5 wavefronts
 // per SIMD = 96 registers: at 80 it spilled 3 - 8 of them (tests/test_no_spill.py reads every kernel's metadata).
 // G6 (CODES, table E1M2 / E3M0): the A6W4 GEMM's activation operands instead (fpq_gemm_g6.h) - dense 6-bit codes, 96 bytes per
-// group, from the staged bucket -> code table lut16_codes_g6, + one scale per group; row-major or the k-major images (r.km_rows)
-template <typename Tin, bool EMIT, bool SMOOTH, bool CODES = false, bool HW4 = false, bool G6 = false>
+// group, from the staged bucket -> code table lut16_codes_g6, + one scale per group; row-major or the k-major images (r.km_rows).
+// The full tables E2M3 / E3M2 run the same form on lut16_codes6 (fpq_gf6_rotate_quant_rows_codes), or
+// HW6 (G6; 1: E2M3, 2: E3M2): their codes from the FP6 conversion hardware (rq_store_codes6_hw) - no table is staged, `tab` is
+// read on the non-finite path only
+template <typename Tin, bool EMIT, bool SMOOTH, bool CODES = false, bool HW4 = false, bool G6 = false, int HW6 = 0>
 __global__ __launch_bounds__(kBlock, SMOOTH ? FPQ_ROT_WAVES - 1 : FPQ_ROT_WAVES) void rotate_quant_mfma_kernel(const void* __restrict__ xv,
                                                                                  u32x4* __restrict__ out,
                                                                                  u32x4* __restrict__ rot_out,
                                                                                  int64_t n_vec, RotArgs r, Lut16Args a,
                                                                                  Lut16Tab tab) {
   static_assert(!G6 || (CODES && !HW4 && !EMIT), "6-bit group operands: a table form of the code output");
+  static_assert(HW6 == 0 || G6, "FP6 conversion hardware: the 6-bit group operands of the full tables");
+  constexpr bool TABLE = !HW4 && HW6 == 0;   // a bucket table is staged
   uint16_t* lut = nullptr;
-  if constexpr (!HW4) {
+  if constexpr (TABLE) {
     __shared__ __attribute__((aligned(16))) uint16_t lut_s[kLutLdsEntries];
     lut = lut_s;
   }
@@ -451,8 +536,8 @@ __global__ __launch_bounds__(kBlock, SMOOTH ? FPQ_ROT_WAVES - 1 : FPQ_ROT_WAVES)
 
   RqRaw<Tin> raw;
   if (PREFETCH) rq_load_tile<Tin>(in_rsrc(tile), lane, raw);
-  if constexpr (!HW4) lut16_stage(lut, tab, a.shift);
-  if constexpr (!HW4 || SMOOTH) __syncthreads();   // the table / the smoothing vector (workgroup-wide, once); everything below is private to the wavefront
+  if constexpr (TABLE) lut16_stage(lut, tab, a.shift);
+  if constexpr (TABLE || SMOOTH) __syncthreads();   // the table / the smoothing vector (workgroup-wide, once); everything below is private to the wavefront
   const HadOperand ha = had_operand(lane);
   // column chunk of vector (tile, i, lane) = (tile * 256 + i * 64 + lane) mod vpr: the tile's part once per pass in the
   // scalar unit's width, the rest in 32 bits
@@ -563,11 +648,15 @@ __global__ __launch_bounds__(kBlock, SMOOTH ? FPQ_ROT_WAVES - 1 : FPQ_ROT_WAVES)
         // 96 bytes per group: the tile's 16 groups are 1.5 KiB in a row behind group base_vec / 16 (row-major), or - k-major - chunk
         // ch of the tile is chunk ch % 6 of group ch / 6 of the tile, each group with its own (row, group) slot; dead groups dropped
         const __amdgpu_buffer_rsrc_t d6 = r.km_rows ? rq_rsrc(out, (int)(r.km_rows * r.km_gpr.d * 96u)) : rq_rsrc((const uint8_t*)out + (base_vec >> 4) * 96, rem * 6);
-        rq_store_codes6(buf, yw, s, lut, a.shift, d6, lane, [&](int ch) -> uint32_t {
+        const auto off6 = [&](int ch) -> uint32_t {
           if (!r.km_rows) return (uint32_t)ch * 16u;
           const uint32_t u = (uint32_t)ch / 6u, gi = (uint32_t)(base_vec >> 4) + u, t = fast_div_q(gi, r.km_gpr);
           return (int64_t)gi * 16 < n_vec ? km6_off(t, gi - t * r.km_gpr.d, (uint32_t)ch - 6u * u, r.km_rows) : 0xFFFFFFFFu;
-        });
+        };
+        if constexpr (HW6 != 0)
+          rq_store_codes6_hw<HW6 == 2>(buf, yw, s, tab, a.shift, d6, lane, off6);
+        else
+          rq_store_codes6(buf, yw, s, lut, a.shift, d6, lane, off6);
         rq_store_scale(s, sdst, rq_opaque(lane), soff);
       } else if constexpr (HW4)
         rq_store_codes_hw(img, yw, s, cdst, sdst, rq_opaque(lane), coff, soff);

@@ -357,6 +357,38 @@ std::tuple<at::Tensor, at::Tensor> adaln_rotate_quant_g6(const at::Tensor& x, co
   return {codes, scales};
 }
 
+// the same pair on the full FP6 tables (table_id FPQ_E2M3 / FPQ_E3M2): the operands fpq_gf6_quant_rows_codes makes of the rotated rows,
+// in the same shapes
+std::tuple<at::Tensor, at::Tensor> rotate_quant_gf6(const at::Tensor& x, int64_t table_id, const std::array<uint32_t, 4>& sign_mask,
+                                                    const c10::optional<at::Tensor>& smooth, bool kmajor) {
+  const ProducerArgs a = producer_checks("rotate_quant_gf6", x, nullptr, nullptr, smooth, 1 << 30);
+  const int64_t rows = a.l;
+  at::Tensor codes = g6_codes_tensor(x, rows, a.c, kmajor);
+  at::Tensor scales = mx_scales_tensor(x, rows, a.c, kmajor);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  check(fpq_gf6_rotate_quant_rows_codes(x.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c,
+                                        dtype_id(x.scalar_type(), "rotate_quant_gf6"), a.smooth, sign_mask.data(), (int)table_id,
+                                        kmajor ? 1 : 0, current_stream(x)),
+        "fpq_gf6_rotate_quant_rows_codes");
+  return {codes, scales};
+}
+
+std::tuple<at::Tensor, at::Tensor> adaln_rotate_quant_gf6(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift,
+                                                          int64_t table_id, const std::array<uint32_t, 4>& sign_mask,
+                                                          const c10::optional<at::Tensor>& smooth, double eps, bool kmajor) {
+  const ProducerArgs a = producer_checks("adaln_rotate_quant_gf6", x, &scale, &shift, smooth, 2560);
+  const int64_t rows = a.b * a.l;
+  at::Tensor codes = g6_codes_tensor(x, rows, a.c, kmajor);
+  at::Tensor scales = mx_scales_tensor(x, rows, a.c, kmajor);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  check(fpq_gf6_adaln_rotate_quant_rows_codes(x.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c,
+                                              dtype_id(x.scalar_type(), "adaln_rotate_quant_gf6"), scale.data_ptr(), shift.data_ptr(),
+                                              dtype_id(scale.scalar_type(), "adaln_rotate_quant_gf6"), a.l, (float)eps, a.smooth,
+                                              sign_mask.data(), (int)table_id, kmajor ? 1 : 0, current_stream(x)),
+        "fpq_gf6_adaln_rotate_quant_rows_codes");
+  return {codes, scales};
+}
+
 // per-token configurations (W6A6): values, or the operands of the row-scaled GEMMs - code_bits 8: E4M3 bytes, 6: dense E2M3
 at::Tensor adaln_rotate_quant_token(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift, int64_t table_id,
                                     const std::array<uint32_t, 4>& sign_mask, const c10::optional<at::Tensor>& smooth, double eps) {
@@ -724,6 +756,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rotate_quant_g6", &rotate_quant_g6, py::arg("x"), py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none(),
         py::arg("kmajor") = false);
   m.def("adaln_rotate_quant_g6", &adaln_rotate_quant_g6, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("table_id"),
+        py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6, py::arg("kmajor") = false);
+  m.def("rotate_quant_gf6", &rotate_quant_gf6, py::arg("x"), py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none(),
+        py::arg("kmajor") = false);
+  m.def("adaln_rotate_quant_gf6", &adaln_rotate_quant_gf6, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("table_id"),
         py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6, py::arg("kmajor") = false);
   m.def("adaln_rotate_quant_token", &adaln_rotate_quant_token, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("table_id"),
         py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6);

@@ -1019,11 +1019,23 @@ class FP6GroupLinear(FP4Linear):
     def _no_w6(self, form: str) -> None:   # every form exists for every pair here
         return None
 
-    def adaln_operands(self, *args, **kw):
-        raise NotImplementedError("FP6GroupLinear: the fused producers do not emit full FP6 group operands - quantize the activation "
-                                  "with forward() or quantize_gf6()")
+    @torch.no_grad()
+    def adaln_operands(self, x, scale, shift, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
+                       eps: float = 1e-6) -> Tuple[torch.Tensor, torch.Tensor]:
+        """FP4Linear.adaln_operands; an 'e2m3' / 'e3m2' activation comes from `rotation.adaln_rotate_quant_gf6` (byte for byte
+        quantize_gf6 of the rotated rows), any other format from the parent's producer; k-major iff the weight is an image."""
+        if self.act_table not in _GF6_FULL:
+            return super().adaln_operands(x, scale, shift, d=d, smooth=smooth, eps=eps)
+        from . import rotation
+        return rotation.adaln_rotate_quant_gf6(x, scale, shift, self.act_table, d=d, smooth=smooth, eps=eps, kmajor=self.kmajor)
 
-    rotate_operands = adaln_operands
+    @torch.no_grad()
+    def rotate_operands(self, x, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """FP4Linear.rotate_operands; an 'e2m3' / 'e3m2' activation comes from `rotation.rotate_quant_gf6`."""
+        if self.act_table not in _GF6_FULL:
+            return super().rotate_operands(x, d=d, smooth=smooth)
+        from . import rotation
+        return rotation.rotate_quant_gf6(x, self.act_table, d=d, smooth=smooth, kmajor=self.kmajor)
 
 
 class FP6GroupLinearGeluDual(FP6GroupLinear):

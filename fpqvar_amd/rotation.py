@@ -415,6 +415,70 @@ def adaln_rotate_quant_g6(x: torch.Tensor, scale: torch.Tensor, shift: torch.Ten
     return codes, scales
 
 
+def _gf6_table_id(name: str, table: str) -> int:
+    from .gemm import _gf6_table
+    return TABLE_IDS[_gf6_table(name, table, full_only=True)]
+
+
+def rotate_quant_gf6(x: torch.Tensor, table: str = "e2m3", d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
+                     kmajor: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """rotate_quant(x, table) for the full FP6 tables "e2m3" / "e3m2" (or "fp6_e2m3" / "fp6_e3m2") emitting per-group operands instead
+    of values: (dense 6-bit codes uint8 [rows, C * 3 / 4], scales fp16 [rows, C/128]) - byte for byte gemm.quantize_gf6 of the rotated
+    rows, so level(code) * scale == rotate_quant(x, table) bit for bit.  The operands of gemm.linear_g6* / FP6GroupLinear.
+    kmajor: the activation side's k-major images (include/fpq.h) - codes [C/128, rows, 96], scales fp32 [C/128, rows rounded up to 4]."""
+    require_gpu(x, "rotate_quant_gf6")
+    if x.dtype not in (torch.float16, torch.float32) or x.shape[-1] % 128 != 0:
+        raise RuntimeError("rotate_quant_gf6: x must be float16/float32 with a last dimension that is a multiple of 128")
+    tid = _gf6_table_id("rotate_quant_gf6", table)
+    c = x.shape[-1]
+    rows = x.numel() // c
+    if _native_ok(x, d, smooth, c):
+        return _native.rotate_quant_gf6(x, tid, _default_mask_tuple(), smooth, kmajor)
+    mask = _mask_arg(d)
+    xc = x if x.is_contiguous() else x.contiguous()
+    sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
+    codes = torch.empty((c // 128, rows, 96) if kmajor else (rows, c * 3 // 4), dtype=torch.uint8, device=x.device)
+    scales = _kmajor_mx_scales(rows, c, x.device) if kmajor else torch.empty((rows, c // 128), dtype=torch.float16, device=x.device)
+    with device_guard(x.device):
+        check(lib().fpq_gf6_rotate_quant_rows_codes(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c, dtype_id(x.dtype),
+                                                    sm_ptr, mask, tid, 1 if kmajor else 0, stream_ptr(x.device)),
+              "fpq_gf6_rotate_quant_rows_codes")
+    return codes, scales
+
+
+def adaln_rotate_quant_gf6(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, table: str = "e2m3",
+                           d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                           kmajor: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """adaln_rotate_quant(x, scale, shift, table) for the full FP6 tables "e2m3" / "e3m2" emitting per-group operands:
+    (dense 6-bit codes uint8 [B*L, C * 3 / 4], scales fp16 [B*L, C/128]) - byte for byte gemm.quantize_gf6 of the rotated rows.  C <= 2560.
+    kmajor: the k-major images - codes [C/128, B*L, 96], scales fp32 [C/128, B*L rounded up to 4]."""
+    require_gpu(x, "adaln_rotate_quant_gf6")
+    if x.dim() != 3:
+        raise RuntimeError("adaln_rotate_quant_gf6: x must be [B, L, C]")
+    bsz, seq, c = x.shape
+    if c % 128 != 0 or c > 2560:
+        raise RuntimeError("adaln_rotate_quant_gf6: C must be a multiple of 128 and at most 2560")
+    if scale.dtype != shift.dtype or scale.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError("adaln_rotate_quant_gf6: scale and shift must both be float16 or both float32")
+    tid = _gf6_table_id("adaln_rotate_quant_gf6", table)
+    sc = _mod_rows(scale, bsz, c)
+    sh = _mod_rows(shift, bsz, c)
+    if sc.device == x.device and sh.device == x.device and _native_ok(x, d, smooth, c):
+        return _native.adaln_rotate_quant_gf6(x, sc, sh, tid, _default_mask_tuple(), smooth, float(eps), kmajor)
+    mask = _mask_arg(d)
+    xc = x if x.is_contiguous() else x.contiguous()
+    sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
+    rows = bsz * seq
+    codes = torch.empty((c // 128, rows, 96) if kmajor else (rows, c * 3 // 4), dtype=torch.uint8, device=x.device)
+    scales = _kmajor_mx_scales(rows, c, x.device) if kmajor else torch.empty((rows, c // 128), dtype=torch.float16, device=x.device)
+    with device_guard(x.device):
+        check(lib().fpq_gf6_adaln_rotate_quant_rows_codes(
+            xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c, dtype_id(x.dtype), sc.data_ptr(), sh.data_ptr(),
+            dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, tid, 1 if kmajor else 0, stream_ptr(x.device)),
+            "fpq_gf6_adaln_rotate_quant_rows_codes")
+    return codes, scales
+
+
 def adaln_rotate_quant_token(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, table: str = "e2m3",
                              d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None, eps: float = 1e-6,
                              emit: str = "values", kmajor: bool = False):

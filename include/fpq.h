@@ -49,7 +49,9 @@ extern "C" {
                                 existing entry point; a caller that wants the query looks the symbol up;
                                  + fpq_gemm_w6_mx, E1M2 / E3M0 WEIGHTS on the matrix cores as 6-bit codes against any FP4 activation format - again an
                                 addition only, and the number stays because tests/test_format_search_fused_host.py pins it: look the symbol up;
-                                 + its fc1 tail and split output, and all four forms on k-major images (fpq_gemm_w6_*_km): additions again) */
+                                 + its fc1 tail and split output, and all four forms on k-major images (fpq_gemm_w6_*_km): additions again;
+                                 + the rotate and adaLN producers on the full FP6 tables: fpq_gf6_rotate_quant_rows_codes,
+                                fpq_gf6_adaln_rotate_quant_rows_codes - additions again) */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -1006,6 +1008,35 @@ int fpq_a6w4_adaln_rotate_quant_rows_codes(const void* x, uint8_t* codes, void* 
                                            const void* scale, const void* shift, int mod_dtype, int64_t rows_per_batch, float eps,
                                            const float* smooth, const uint32_t* sign_mask_host, int table_id, int kmajor,
                                            fpq_stream_t stream);
+
+/* THE SAME PRODUCERS ON THE FULL FP6 TABLES (GF6 above): the online rotation and the adaLN producer emitting per-group(128) full-range
+ * E2M3 / E3M2 operands in one launch - the activation of a per-group W6A6 / W4A6 mat_qkv or fc1 no longer exists in HBM as fp16 between
+ * the block's LayerNorm and its matrix product.  Every argument is its fpq_a6w4_* twin's, in the twin's order; table_id: FPQ_E2M3 or
+ * FPQ_E3M2 (the fpq_a6w4_* names keep refusing these two, and these refuse FPQ_E1M2 / FPQ_E3M0 / FPQ_E2M1).
+ *   kmajor = 0: codes [rows, cols * 3 / 4] (the bit format of fpq_gf6_quant_rows_codes), scales fp16 [rows, cols / 128]
+ *   kmajor = 1: the activation side's 6-bit image [cols / 128][rows][96] and the fp32 scale image [cols / 128][rows rounded up to 4]
+ *               (padding rows not written) - what fpq_gemm_a6w4_*_km / fpq_gemm_w6_*_km take under the decode id of the format
+ * CONTRACT: let y be the fp16 rotated rows that fpq_rotate_quant_rows / fpq_adaln_rotate_quant_rows write to rotated_out for the same
+ * arguments and table_id.  Then codes and scales are byte for byte what fpq_gf6_quant_rows_codes(y, ..., table_id, FPQ_F16, kmajor)
+ * writes (padding rows of the scale image excluded), non-finite and all-zero groups included.  Hence level(code) * scale equals the
+ * `out` of the values form, bit for bit.
+ * The adaLN entry point has no kernel of its own: the 6-bit group form of the adaLN kernel stages whatever bucket -> code table it is
+ * handed, here the table fpq_gf6_quant_rows_codes stages (2 x 512 buckets for E2M3, 2 KiB per workgroup).  The rotate entry point
+ * takes its codes from the FP6 conversion hardware instead (v_cvt_scalef32_2xpk16_{fp6,bf6}_f32: no table, no staging barrier, the
+ * short-workgroup grid of the table-free E2M1 forms) - the same bytes, checked against the table form in tests/test_gpu_gf6_producers.py;
+ * the switch FPQ_NO_HW6 = 1 keeps the staged table there too, on the kernel of fpq_a6w4_rotate_quant_rows_codes.
+ * fpq_gf6_adaln_rotate_quant_rows_codes runs on the matrix-core kernel only: cols <= 2560 (beyond: FPQ_ERR_SHAPE).
+ * Checks, in this order, before any launch: negative sizes, rows_per_batch <= 0 or sign_mask_host == NULL (FPQ_ERR_ARG); table_id
+ * (FPQ_ERR_TABLE); in_dtype / mod_dtype other than FPQ_F16 / FPQ_F32 (FPQ_ERR_DTYPE); cols % 128, [adaLN: cols > 2560,] with kmajor an
+ * image of 2 GiB or more (FPQ_ERR_SHAPE); rows == 0 or cols == 0 (FPQ_OK, nothing launched); then NULL x / codes / scales [/ scale /
+ * shift] or x, codes, scales, smooth [, scale, shift] not 16-byte aligned (FPQ_ERR_ARG).
+ * Additions that change no existing entry point: FPQ_VERSION stays, a caller looks the symbols up. */
+int fpq_gf6_rotate_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
+                                    const float* smooth, const uint32_t* sign_mask_host, int table_id, int kmajor, fpq_stream_t stream);
+int fpq_gf6_adaln_rotate_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
+                                          const void* scale, const void* shift, int mod_dtype, int64_t rows_per_batch, float eps,
+                                          const float* smooth, const uint32_t* sign_mask_host, int table_id, int kmajor,
+                                          fpq_stream_t stream);
 
 /* fpq_kv_cache_step_qknorm: fpq_kv_cache_step (same arguments, same checks) for an fp16 qkv WITHOUT the norm (path F, or a
  * mat_qkv that is not split): the new k is normalized and the bias added on its way into the cache, and the same launch writes
