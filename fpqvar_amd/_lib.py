@@ -218,6 +218,22 @@ _SIGS = {
                                                           _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64,
                                                           _c.c_float, _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int,
                                                           _c.c_void_p]),
+    # the adaLN producers with the gated residual in front folded in: the twin's list behind (y, gate, x_out), residual in x's place
+    "fpq_resid_adaln_rotate_quant_rows": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                                      _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                                      _c.c_int64, _c.c_float, _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_void_p]),
+    "fpq_resid_adaln_rotate_quant_rows_codes_mx": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                                               _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                                               _c.c_int, _c.c_int64, _c.c_float, _c.c_void_p, _c.POINTER(_c.c_uint32),
+                                                               _c.c_int, _c.c_void_p]),
+    "fpq_resid_adaln_rotate_quant_token_rows": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                                            _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int, _c.c_void_p,
+                                                            _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_void_p,
+                                                            _c.POINTER(_c.c_uint32), _c.c_int, _c.c_void_p]),
+    "fpq_resid_adaln_rotate_quant_token_rows_codes_f6": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                                                     _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int, _c.c_void_p,
+                                                                     _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_void_p,
+                                                                     _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int, _c.c_void_p]),
     # per-group(128) quantization on the full FP6 tables to dense 6-bit codes (table, dtype, layout: arguments)
     "fpq_gf6_quant_rows_codes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int,
                                              _c.c_void_p]),

@@ -380,11 +380,26 @@ struct AdalnTiers {
 // hardware (fpq_fast16.h, fp6_levels_hw32) - per group and per token alike; no table is staged.
 // G6 (CODES, per group, table E1M2 / E3M0): the A6W4 GEMM's activation operands (fpq_gemm_g6.h) - dense 6-bit codes, 96 bytes
 // per group, through the bucket -> code table lut16_codes_g6 + one scale per group; row-major or the k-major images (r.km_rows).
-template <typename Tmod, int MAXC, bool CODES, bool EMIT, bool TOKEN, bool X32, bool HW4, bool TIGHT = false, int NW = 4, bool PAIR2 = false, int HW6 = 0, bool G6 = false>
+// RESID (fpq_resid_adaln.hip): the gated residual that runs in front of the producer, x = x + y.mul(gate), folded into the row load.
+// A lane requests the y vectors (fp16) and the gate vectors of its batch entry (fp16 [batches, cols]) at the column offsets of its row
+// vectors (y with them, a row ahead, where the registers allow: PRE_Y below); when the row is taken up, the registers that held it receive
+//     fp16 rows:  half(x + half(y * gate))         one packed multiply, one packed add: gate_residual_kernel's two instructions
+//     fp32 rows:  x + float(half(y * gate))        torch's x32 + y16.mul(gate16)
+// and go out to x_out at the offsets they were loaded from (x_out may be x itself: one wavefront reads a row, then writes it).
+// Loads beyond the row return zeros in all three streams and 0 + 0 * 0 = 0: the padding stays what every phase below expects.  All of it
+// happens before the first statistic, so the rest of the kernel is the twin's on the new row - in every variant, bit for bit.
+// The pointers travel behind the tiers (AdalnTiersResid): the forms without the flag keep their argument block and their machine code.
+struct AdalnTiersResid : AdalnTiers {
+  const void* y;      // [rows, cols] fp16
+  const void* gate;   // [batches, cols] fp16
+  void* x_out;        // [rows, cols], the rows' dtype
+};
+
+template <typename Tmod, int MAXC, bool CODES, bool EMIT, bool TOKEN, bool X32, bool HW4, bool TIGHT = false, int NW = 4, bool PAIR2 = false, int HW6 = 0, bool G6 = false, bool RESID = false>
 __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ? 5 : 4) void adaln_mfma_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ out,
                                                               u32x4* __restrict__ h_out, u32x4* __restrict__ y_out,
                                                               int64_t rows, AdaLnArgs ad, RotArgs r, Lut16Args a,
-                                                              Lut16Tab tab, AdalnTiers tiers) {
+                                                              Lut16Tab tab, std::conditional_t<RESID, AdalnTiersResid, AdalnTiers> tiers) {
   static_assert(MAXC >= 1 && MAXC <= 5, "rows of at most 20 groups");
   static_assert(!HW4 || !TOKEN, "hardware E2M1 levels / codes: per group only");
   static_assert(HW6 == 0 || (!HW4 && !CODES && !PAIR2), "hardware FP6 levels: value outputs");
@@ -393,6 +408,7 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
   static_assert(NW == 4, "four wavefronts per workgroup");
   static_assert(!PAIR2 || (MAXC == 4 && !X32 && !EMIT && !TOKEN && !TIGHT), "two rows per tile: fp16 rows of 8 groups, per group");
   static_assert(!G6 || (CODES && !EMIT && !TOKEN && !HW4 && !TIGHT && !PAIR2 && HW6 == 0), "6-bit group operands: the plain table form");
+  static_assert(!RESID || !G6, "the gated residual in front: not built for the 6-bit group operands");
   constexpr int W = NW;
   constexpr int RPU = PAIR2 ? 2 : 1;             // rows per unit of work of a wavefront
   constexpr int RV = X32 ? 2 * MAXC : MAXC;      // 16-byte registers of one row per lane
@@ -457,6 +473,57 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
   constexpr bool PAIRABLE = MAXC == 5 && !X32 && !EMIT && !TOKEN && !G6;
   const bool pair_ok = PAIRABLE && vpr - 256 <= 32;
   const int lane16_hi = ((lane + 32) & 63) * 16;     // the slot chunk's vector index of this lane in a `hi_half` row
+  // RESID: the y and gate vectors that belong to the row vectors in flight (fp32 rows: 4 channels per row vector = 8 bytes of each).
+  // PRE_Y: y is requested with the row, a row ahead, and waits in registers through the previous row's second half - wherever the
+  // registers of the twin's occupancy class allow it.  Otherwise y is requested when the row is taken up, as the gate vectors always
+  // are (they are the batch entry's: L2 hits after the entry's first row).
+  typedef std::conditional_t<X32, u32x2, u32x4> resid_vec_t;
+  resid_vec_t ry[RESID ? RV : 1], rg[RESID ? RV : 1];
+  // (Not in TIGHT - 96 registers - nor on rows of 17 .. 20 groups from fp16 rows or in the emitting form: with y a row ahead those spill.)
+  // PARK (rows of 17 .. 20 groups into operands through a bucket table: the forms that have no scalar register left): the three
+  // addresses wait in vector registers, which these forms have to spare once y is not a row ahead, and come back through
+  // v_readfirstlane where a row's buffer resources are formed.  (Every lane holds the same value; they are set behind the staging,
+  // before any row asks for them.)  The forms it is for - 1 to 7 scalar spills each without it, profiles/resid_adaln_isa.txt - are
+  // MAXC 5, CODES, no hardware levels, either modulation dtype: fp16 rows into FP4 operands (FPQ_NO_HW4), fp32 rows into FP4
+  // operands (FPQ_NO_HW4) and fp32 rows into per-token 6-bit codes; the fourth of the family (fp16 rows, per token) rides along.  Drop
+  // PARK when a compiler no longer spills there: tests/test_resid_adaln_isa.py says so either way.
+  constexpr bool PARK = RESID && MAXC == 5 && CODES && !HW4;
+  constexpr bool PRE_Y = RESID && !TIGHT && !PARK && !(MAXC == 5 && (!X32 || EMIT));
+  const char *resid_y = nullptr, *resid_g = nullptr, *resid_x = nullptr;   // (copies: the argument block itself stays out of the closures)
+  uint32_t parked[PARK ? 6 : 1];
+  if constexpr (RESID && !PARK) {
+    resid_y = (const char*)tiers.y;
+    resid_g = (const char*)tiers.gate + b * (vpr * 16);
+    resid_x = (const char*)tiers.x_out;
+  }
+  auto resid_ptr = [&](int i) -> const char* {   // 0: y, 1: the batch entry's gate row, 2: x_out
+    if constexpr (PARK)
+      return (const char*)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)parked[2 * i]) |
+                           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)parked[2 * i + 1]) << 32));
+    else
+      return i == 0 ? resid_y : i == 1 ? resid_g : resid_x;
+  };
+  auto load_resid = [&](auto want_y, auto want_g, int64_t row, bool hi_half) {
+    if constexpr (RESID) {
+      const int nr = (PAIR2 && row + 1 < hi) ? 2 : 1;
+      constexpr int YS = X32 ? 1 : 0;   // a row of y has the bytes of an fp16 row: row_bytes, halved on fp32 rows
+      const __amdgpu_buffer_rsrc_t ys = rq_rsrc(resid_ptr(0) + ((row * row_bytes) >> YS), (nr * row_bytes) >> YS);
+      const __amdgpu_buffer_rsrc_t gs = rq_rsrc(resid_ptr(1), row_bytes >> YS);
+#pragma unroll
+      for (int n = 0; n < RV; ++n) {
+        if constexpr (X32) {
+          if constexpr (want_y.value) ry[n] = __builtin_amdgcn_raw_buffer_load_b64(ys, lane * 8 + n * 512, 0, kRqNt);
+          if constexpr (want_g.value) rg[n] = __builtin_amdgcn_raw_buffer_load_b64(gs, lane * 8 + n * 512, 0, 0);
+        } else {
+          int at = la.lane16 + n * 1024;
+          if (PAIRABLE && n == 4 && hi_half) at = lane16_hi + 4096;
+          if constexpr (want_y.value) ry[n] = __builtin_amdgcn_raw_buffer_load_b128(ys, at, 0, kRqNt);
+          // PAIR2: the unit's second row (chunks 2, 3) takes the same gate vectors; without a second row they stay beyond the range
+          if constexpr (want_g.value) rg[n] = __builtin_amdgcn_raw_buffer_load_b128(gs, (PAIR2 && nr == 2) ? (at & 2047) : at, 0, 0);
+        }
+      }
+    }
+  };
   auto load_row = [&](u32x4 (&dst)[RV], int64_t row, bool hi_half = false) {
     const __amdgpu_buffer_rsrc_t src = rq_rsrc((const char*)x + row * row_bytes, (PAIR2 && row + 1 < hi ? 2 : 1) * row_bytes);
 #pragma unroll
@@ -465,6 +532,7 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
       if (PAIRABLE && n == 4 && hi_half) at = lane16_hi + 4096;   // lanes 0 .. 31 then point beyond the row: zeros
       dst[n] = __builtin_amdgcn_raw_buffer_load_b128(src, at, 0, kRqNt);
     }
+    if constexpr (PRE_Y) load_resid(Bool<true>{}, Bool<false>{}, row, hi_half);
   };
 
   // the rotation's signs of this lane's chunk (16-byte vector: chunk lane % 16; fp32 rows: half lane & 1 of chunk
@@ -614,6 +682,27 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
     if (++st_rows == 1) st_first = __builtin_amdgcn_s_memrealtime();   // the wavefront's first row has arrived
 #endif
     FPQ_STAMP(1);                                   // waiting for the row (and, in this build, the previous row's stores)
+    // RESID: the row that has arrived becomes x + y * gate, in the registers it arrived in, and goes out to x_out
+    if constexpr (RESID) {
+      load_resid(Bool<!PRE_Y>{}, Bool<true>{}, row, hi_half);
+      const __amdgpu_buffer_rsrc_t xd = rq_rsrc(resid_ptr(2) + row * row_bytes, nrows * row_bytes);
+#pragma unroll
+      for (int n = 0; n < RV; ++n) {
+        if constexpr (X32) {
+          const uint32_t p0 = pk_mul_f16(ry[n][0], rg[n][0]), p1 = pk_mul_f16(ry[n][1], rg[n][1]);
+          cur[n][0] = fbits(u2f(cur[n][0]) + h2f(p0 & 0xFFFFu));
+          cur[n][1] = fbits(u2f(cur[n][1]) + h2f(p0 >> 16));
+          cur[n][2] = fbits(u2f(cur[n][2]) + h2f(p1 & 0xFFFFu));
+          cur[n][3] = fbits(u2f(cur[n][3]) + h2f(p1 >> 16));
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) cur[n][k] = pk_add_f16(cur[n][k], pk_mul_f16(ry[n][k], rg[n][k]));
+        }
+        int at = la.lane16 + n * 1024;
+        if (PAIRABLE && n == 4 && hi_half) at = lane16_hi + 4096;
+        __builtin_amdgcn_raw_buffer_store_b128(cur[n], xd, at, 0, 0);   // (the next launch reads it: not non-temporal)
+      }
+    }
     // ---- LayerNorm statistics (padding lanes hold zeros) ----
     FPQ_PHASE("ln_stats");
     float a1[RV], a2[RV];
@@ -1058,6 +1147,15 @@ __global__ __launch_bounds__(64 * NW, (EMIT || (X32 && MAXC == 5)) ? 3 : TIGHT ?
   if constexpr (!HW4 && HW6 == 0) lut16_stage(lut, tab, a.shift);
   stage_store(sraw);
   __syncthreads();
+  if constexpr (PARK) {   // (behind the staging, which holds the table in scalar registers; no row has asked for them yet)
+    const uint64_t a3[3] = {(uint64_t)tiers.y, (uint64_t)((const char*)tiers.gate + b * (vpr * 16)), (uint64_t)tiers.x_out};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      parked[2 * i] = (uint32_t)a3[i];
+      parked[2 * i + 1] = (uint32_t)(a3[i] >> 32);
+      asm volatile("" : "+v"(parked[2 * i]), "+v"(parked[2 * i + 1]));
+    }
+  }
   if (i < hi) {
     // first pass peeled: both edges into the loop then carry "loads, then this row's stores", and the wait for the
     // prefetched row leaves the stores in flight (fpq_rotate_mfma.h, rotate_quant_mfma_kernel)

@@ -442,6 +442,96 @@ std::tuple<at::Tensor, at::Tensor> adaln_rotate_quant_token_codes_f6(const at::T
   return {codes, scales};
 }
 
+// ---- the same producers with the gated residual in front folded in (include/fpq.h, fpq_resid_adaln_*): x_new = residual + y.mul(gate)
+// goes to x_out - a fresh tensor, or `residual` itself (inplace) - and comes back in front of what the twin returns ----
+static at::Tensor resid_checks(const char* what, const at::Tensor& y, const at::Tensor& gate, const at::Tensor& residual,
+                               const ProducerArgs& a, bool inplace) {
+  TORCH_CHECK(a.c <= 2560, what, ": C must be a multiple of 128 and at most 2560");
+  TORCH_CHECK(y.scalar_type() == at::kHalf && gate.scalar_type() == at::kHalf, what, ": y and gate must be float16");
+  TORCH_CHECK(y.sizes() == residual.sizes(), what, ": y must have the shape of residual");
+  TORCH_CHECK(y.is_contiguous() && gate.is_contiguous() && gate.numel() == a.b * a.c && y.device() == residual.device() &&
+              gate.device() == residual.device(), what, " (native): contiguous y and [B, C] gate rows on residual's device");
+  if (inplace) {   // include/fpq.h: x_out (here the residual) must not overlap y
+    const char *y0 = (const char*)y.data_ptr(), *r0 = (const char*)residual.data_ptr();
+    TORCH_CHECK(!(y0 < r0 + residual.nbytes() && r0 < y0 + y.nbytes()), what, ": inplace=True writes x_new over residual, which must not overlap y");
+  }
+  return inplace ? residual : at::empty_like(residual);
+}
+
+std::tuple<at::Tensor, at::Tensor> resid_adaln_rotate_quant(const at::Tensor& y, const at::Tensor& gate, const at::Tensor& residual,
+                                                            const at::Tensor& scale, const at::Tensor& shift, int64_t table_id,
+                                                            const std::array<uint32_t, 4>& sign_mask,
+                                                            const c10::optional<at::Tensor>& smooth, double eps, bool inplace) {
+  const ProducerArgs a = producer_checks("resid_adaln_rotate_quant", residual, &scale, &shift, smooth, 2560);
+  at::Tensor x_new = resid_checks("resid_adaln_rotate_quant", y, gate, residual, a, inplace);
+  at::Tensor out = at::empty(residual.sizes(), residual.options().dtype(at::kHalf));
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(residual.device());
+  check(fpq_resid_adaln_rotate_quant_rows(y.data_ptr(), gate.data_ptr(), x_new.data_ptr(), residual.data_ptr(), out.data_ptr(), nullptr,
+                                          nullptr, a.b * a.l, a.c, dtype_id(residual.scalar_type(), "resid_adaln_rotate_quant"),
+                                          scale.data_ptr(), shift.data_ptr(), dtype_id(scale.scalar_type(), "resid_adaln_rotate_quant"), a.l,
+                                          (float)eps, a.smooth, sign_mask.data(), (int)table_id, current_stream(residual)),
+        "fpq_resid_adaln_rotate_quant_rows");
+  return {x_new, out};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> resid_adaln_rotate_quant_mx(const at::Tensor& y, const at::Tensor& gate,
+                                                                           const at::Tensor& residual, const at::Tensor& scale,
+                                                                           const at::Tensor& shift, const std::array<uint32_t, 4>& sign_mask,
+                                                                           const c10::optional<at::Tensor>& smooth, double eps, bool kmajor,
+                                                                           bool inplace) {
+  const ProducerArgs a = producer_checks("resid_adaln_rotate_quant_mx", residual, &scale, &shift, smooth, 2560);
+  at::Tensor x_new = resid_checks("resid_adaln_rotate_quant_mx", y, gate, residual, a, inplace);
+  const int64_t rows = a.b * a.l;
+  at::Tensor codes = mx_codes_tensor(residual, rows, a.c, kmajor);
+  at::Tensor scales = mx_scales_tensor(residual, rows, a.c, kmajor);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(residual.device());
+  check(fpq_resid_adaln_rotate_quant_rows_codes_mx(y.data_ptr(), gate.data_ptr(), x_new.data_ptr(), residual.data_ptr(),
+                                                   (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c,
+                                                   dtype_id(residual.scalar_type(), "resid_adaln_rotate_quant_mx"), scale.data_ptr(),
+                                                   shift.data_ptr(), dtype_id(scale.scalar_type(), "resid_adaln_rotate_quant_mx"), a.l,
+                                                   (float)eps, a.smooth, sign_mask.data(), kmajor ? 1 : 0, current_stream(residual)),
+        "fpq_resid_adaln_rotate_quant_rows_codes_mx");
+  return {x_new, codes, scales};
+}
+
+std::tuple<at::Tensor, at::Tensor> resid_adaln_rotate_quant_token(const at::Tensor& y, const at::Tensor& gate, const at::Tensor& residual,
+                                                                  const at::Tensor& scale, const at::Tensor& shift, int64_t table_id,
+                                                                  const std::array<uint32_t, 4>& sign_mask,
+                                                                  const c10::optional<at::Tensor>& smooth, double eps, bool inplace) {
+  const ProducerArgs a = producer_checks("resid_adaln_rotate_quant_token", residual, &scale, &shift, smooth, 2560);
+  at::Tensor x_new = resid_checks("resid_adaln_rotate_quant_token", y, gate, residual, a, inplace);
+  at::Tensor out = at::empty(residual.sizes(), residual.options().dtype(at::kHalf));
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(residual.device());
+  check(fpq_resid_adaln_rotate_quant_token_rows(y.data_ptr(), gate.data_ptr(), x_new.data_ptr(), residual.data_ptr(), out.data_ptr(),
+                                                nullptr, nullptr, nullptr, a.b * a.l, a.c,
+                                                dtype_id(residual.scalar_type(), "resid_adaln_rotate_quant_token"), scale.data_ptr(),
+                                                shift.data_ptr(), dtype_id(scale.scalar_type(), "resid_adaln_rotate_quant_token"), a.l,
+                                                (float)eps, a.smooth, sign_mask.data(), (int)table_id, current_stream(residual)),
+        "fpq_resid_adaln_rotate_quant_token_rows");
+  return {x_new, out};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> resid_adaln_rotate_quant_token_codes_f6(
+    const at::Tensor& y, const at::Tensor& gate, const at::Tensor& residual, const at::Tensor& scale, const at::Tensor& shift,
+    int64_t table_id, const std::array<uint32_t, 4>& sign_mask, const c10::optional<at::Tensor>& smooth, double eps, bool kmajor,
+    bool inplace) {
+  const ProducerArgs a = producer_checks("resid_adaln_rotate_quant_token_codes_f6", residual, &scale, &shift, smooth, 2560);
+  TORCH_CHECK(table_id == FPQ_E2M3 || table_id == FPQ_E3M2, "resid_adaln_rotate_quant_token_codes_f6: dense 6-bit codes are E2M3 or E3M2");
+  at::Tensor x_new = resid_checks("resid_adaln_rotate_quant_token_codes_f6", y, gate, residual, a, inplace);
+  const int64_t rows = a.b * a.l;
+  at::Tensor codes = kmajor ? at::empty({a.c / 128, rows, 96}, residual.options().dtype(at::kByte))
+                            : at::empty({rows, a.c * 3 / 4}, residual.options().dtype(at::kByte));
+  at::Tensor scales = at::empty({rows}, residual.options().dtype(at::kHalf));
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(residual.device());
+  check(fpq_resid_adaln_rotate_quant_token_rows_codes_f6(
+            y.data_ptr(), gate.data_ptr(), x_new.data_ptr(), residual.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c,
+            dtype_id(residual.scalar_type(), "resid_adaln_rotate_quant_token_codes_f6"), scale.data_ptr(), shift.data_ptr(),
+            dtype_id(scale.scalar_type(), "resid_adaln_rotate_quant_token_codes_f6"), a.l, (float)eps, a.smooth, sign_mask.data(),
+            (int)table_id, kmajor ? 1 : 0, current_stream(residual)),
+        "fpq_resid_adaln_rotate_quant_token_rows_codes_f6");
+  return {x_new, codes, scales};
+}
+
 // one step of the incrementally kept KV cache (ops.kv_cache_step holds the argument checks' prose)
 void kv_cache_step(const at::Tensor& cache, int64_t quant_start, int64_t quant_stop, const at::Tensor& k, const at::Tensor& v,
                    int64_t new_start, int64_t group, int64_t table_id) {
@@ -773,6 +863,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv_cache_step_qk_norm", &kv_cache_step_qk_norm, py::arg("cache"), py::arg("quant_start"), py::arg("quant_stop"), py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("new_start"), py::arg("group"), py::arg("table_id"), py::arg("head_scale"),
         py::arg("bias") = py::none());
+  m.def("resid_adaln_rotate_quant", &resid_adaln_rotate_quant, py::arg("y"), py::arg("gate"), py::arg("residual"), py::arg("scale"),
+        py::arg("shift"), py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6,
+        py::arg("inplace") = false);
+  m.def("resid_adaln_rotate_quant_mx", &resid_adaln_rotate_quant_mx, py::arg("y"), py::arg("gate"), py::arg("residual"), py::arg("scale"),
+        py::arg("shift"), py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6, py::arg("kmajor") = false,
+        py::arg("inplace") = false);
+  m.def("resid_adaln_rotate_quant_token", &resid_adaln_rotate_quant_token, py::arg("y"), py::arg("gate"), py::arg("residual"),
+        py::arg("scale"), py::arg("shift"), py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6,
+        py::arg("inplace") = false);
+  m.def("resid_adaln_rotate_quant_token_codes_f6", &resid_adaln_rotate_quant_token_codes_f6, py::arg("y"), py::arg("gate"),
+        py::arg("residual"), py::arg("scale"), py::arg("shift"), py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none(),
+        py::arg("eps") = 1e-6, py::arg("kmajor") = false, py::arg("inplace") = false);
   m.def("linear_fp4", &linear_fp4, py::arg("a_codes"), py::arg("a_scales"), py::arg("w_codes"), py::arg("w_scales"),
         py::arg("bias") = py::none(), py::arg("gate") = py::none(), py::arg("residual") = py::none(), py::arg("outs") = py::none());
   m.def("linear_w6", &linear_w6, py::arg("a_codes"), py::arg("a_scales"), py::arg("a_table_id"), py::arg("w_codes"), py::arg("w_scales"),

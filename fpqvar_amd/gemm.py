@@ -790,12 +790,21 @@ class FP4Linear(_ScaledOperandModule):
 
     @torch.no_grad()
     def adaln_operands(self, x, scale, shift, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
-                       eps: float = 1e-6) -> Tuple[torch.Tensor, torch.Tensor]:
+                       eps: float = 1e-6, pending: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         """The block's producer in front of this Linear - LayerNorm, adaLN modulate, smooth, rotate, per-group quantize of x [B, L,
         in_features] - in one launch, emitting (codes, scales) in the module's own activation format and layout
         (`rotation.adaln_rotate_quant_mx` for E2M1, `rotation.adaln_rotate_quant_g6` for E1M2 / E3M0; k-major iff the weight is):
-        ready for `forward_operands` / `qkv_to_cache_operands`.  One call in front of every mat_qkv and fc1 of a mixed-format model."""
+        ready for `forward_operands` / `qkv_to_cache_operands`.  One call in front of every mat_qkv and fc1 of a mixed-format model.
+        pending = (y, gate): a gated residual x + y.mul(gate) that has not been applied to x yet - what `ops.gate_residual(y, gate, x)`
+        would compute - is applied by the same launch (`rotation.resid_adaln_rotate_quant_mx`, E2M1 activations, in_features <= 2560):
+        returns (x_new, codes, scales), x_new and the operands bit for bit those of the two calls."""
         from . import rotation
+        if pending is not None:
+            if self.act_table != "e2m1":
+                raise RuntimeError(f"{type(self).__name__}.adaln_operands: pending= needs an 'e2m1' activation (the 6-bit group producers "
+                                   f"have no fused form), this module's is {self.act_table!r}")
+            y, gate = pending
+            return rotation.resid_adaln_rotate_quant_mx(y, gate, x, scale, shift, d=d, smooth=smooth, eps=eps, kmajor=self.kmajor)
         if self.act_table == "e2m1":
             return rotation.adaln_rotate_quant_mx(x, scale, shift, d=d, smooth=smooth, eps=eps, kmajor=self.kmajor)
         return rotation.adaln_rotate_quant_g6(x, scale, shift, self.act_table, d=d, smooth=smooth, eps=eps, kmajor=self.kmajor)
@@ -1021,9 +1030,11 @@ class FP6GroupLinear(FP4Linear):
 
     @torch.no_grad()
     def adaln_operands(self, x, scale, shift, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
-                       eps: float = 1e-6) -> Tuple[torch.Tensor, torch.Tensor]:
+                       eps: float = 1e-6, pending: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         """FP4Linear.adaln_operands; an 'e2m3' / 'e3m2' activation comes from `rotation.adaln_rotate_quant_gf6` (byte for byte
         quantize_gf6 of the rotated rows), any other format from the parent's producer; k-major iff the weight is an image."""
+        if pending is not None:   # (the parent refuses every activation format but 'e2m1')
+            return super().adaln_operands(x, scale, shift, d=d, smooth=smooth, eps=eps, pending=pending)
         if self.act_table not in _GF6_FULL:
             return super().adaln_operands(x, scale, shift, d=d, smooth=smooth, eps=eps)
         from . import rotation

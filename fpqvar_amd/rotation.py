@@ -582,3 +582,140 @@ def adaln_rotate_quant(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor
             dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, TABLE_IDS[table], stream_ptr(x.device)),
             "fpq_adaln_rotate_quant_rows")
     return (out, h, y) if return_intermediates else out
+
+
+# ---- the same producers with the gated residual in front of them folded in (include/fpq.h, fpq_resid_adaln_*) ----
+# x_new = residual + y.mul(gate), then the twin on x_new, in one launch.  x_new is bit for bit torch's residual + y.mul(gate) (on fp16
+# rows also ops.gate_residual); every other output is byte for byte what the twin returns for x_new.
+
+def _resid_args(name: str, y: torch.Tensor, gate: torch.Tensor, residual: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
+                inplace: bool):
+    """The checks the three functions share; returns (B, L, C, gate rows, scale rows, shift rows)."""
+    require_gpu(residual, name)
+    if residual.dim() != 3:
+        raise RuntimeError(f"{name}: residual must be [B, L, C]")
+    if residual.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError(f"{name}: residual must be float16 or float32, got {residual.dtype}")
+    bsz, seq, c = residual.shape
+    if c % 128 != 0 or c > 2560:
+        raise RuntimeError(f"{name}: C must be a multiple of 128 and at most 2560")
+    if y.dtype is not torch.float16 or gate.dtype is not torch.float16:
+        raise RuntimeError(f"{name}: y and gate must be float16, got {y.dtype} and {gate.dtype}")
+    if tuple(y.shape) != tuple(residual.shape):
+        raise RuntimeError(f"{name}: y {tuple(y.shape)} must have the shape of residual {tuple(residual.shape)}")
+    if gate.numel() != bsz * c or gate.shape[-1] != c:
+        raise RuntimeError(f"{name}: gate {tuple(gate.shape)} must be [B, 1, C] (or [B, C]) for residual {tuple(residual.shape)}")
+    if scale.dtype != shift.dtype or scale.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError(f"{name}: scale and shift must both be float16 or both float32")
+    if scale.numel() != bsz * c or shift.numel() != bsz * c:
+        raise RuntimeError(f"{name}: scale and shift must be [B, 1, C] (or [B, C]) for residual {tuple(residual.shape)}")
+    if y.device != residual.device or gate.device != residual.device:
+        raise RuntimeError(f"{name}: y and gate must be on the GPU of residual")
+    if inplace and not residual.is_contiguous():
+        raise RuntimeError(f"{name}: inplace=True needs a contiguous residual")
+    if inplace and y.is_contiguous():   # include/fpq.h: x_out must not overlap y (a copy of a non-contiguous y cannot)
+        y0, r0 = y.data_ptr(), residual.data_ptr()
+        if y0 < r0 + residual.numel() * residual.element_size() and r0 < y0 + y.numel() * y.element_size():
+            raise RuntimeError(f"{name}: inplace=True writes x_new over residual, which must not overlap y")
+    return bsz, seq, c, _mod_rows(gate, bsz, c), _mod_rows(scale, bsz, c), _mod_rows(shift, bsz, c)
+
+
+def _resid_native_ok(y, residual, sc, sh, d, smooth, c) -> bool:
+    return (y.is_contiguous() and sc.device == residual.device and sh.device == residual.device and _native_ok(residual, d, smooth, c))
+
+
+def resid_adaln_rotate_quant(y: torch.Tensor, gate: torch.Tensor, residual: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
+                             table: str = "e2m1", d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
+                             eps: float = 1e-6, return_intermediates: bool = False, inplace: bool = False):
+    """x_new = residual + y.mul(gate); adaln_rotate_quant(x_new, scale, shift, table, ...) - one launch.
+
+    y: [B, L, C] fp16; gate: [B, 1, C] (or [B, C]) fp16; residual: [B, L, C] fp16 or fp32, C <= 2560.  Returns (x_new, out), or
+    (x_new, out, h, rotated) with return_intermediates.  inplace: x_new is written over residual (and is that tensor)."""
+    name = "resid_adaln_rotate_quant"
+    bsz, seq, c, gt, sc, sh = _resid_args(name, y, gate, residual, scale, shift, inplace)
+    if not return_intermediates and _resid_native_ok(y, residual, sc, sh, d, smooth, c):
+        return _native.resid_adaln_rotate_quant(y, gt, residual, sc, sh, TABLE_IDS[table], _default_mask_tuple(), smooth, float(eps), inplace)
+    mask = _mask_arg(d)
+    rc = residual if residual.is_contiguous() else residual.contiguous()
+    yc = y if y.is_contiguous() else y.contiguous()
+    sm, sm_ptr = _smooth_ptr(smooth, c, residual.device)
+    x_new = rc if inplace else torch.empty_like(rc)
+    out = torch.empty(residual.shape, dtype=torch.float16, device=residual.device)
+    h = torch.empty_like(out) if return_intermediates else None
+    rot = torch.empty_like(out) if return_intermediates else None
+    with device_guard(residual.device):
+        check(lib().fpq_resid_adaln_rotate_quant_rows(
+            yc.data_ptr(), gt.data_ptr(), x_new.data_ptr(), rc.data_ptr(), out.data_ptr(), h.data_ptr() if h is not None else None,
+            rot.data_ptr() if rot is not None else None, bsz * seq, c, dtype_id(residual.dtype), sc.data_ptr(), sh.data_ptr(),
+            dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, TABLE_IDS[table], stream_ptr(residual.device)),
+            "fpq_resid_adaln_rotate_quant_rows")
+    return (x_new, out, h, rot) if return_intermediates else (x_new, out)
+
+
+def resid_adaln_rotate_quant_mx(y: torch.Tensor, gate: torch.Tensor, residual: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
+                                d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                                kmajor: bool = False, inplace: bool = False):
+    """x_new = residual + y.mul(gate); adaln_rotate_quant_mx(x_new, scale, shift, ...) - one launch.  Returns (x_new, codes, scales) in
+    the twin's shapes (kmajor: the k-major images).  C <= 2560.  inplace: x_new is written over residual."""
+    name = "resid_adaln_rotate_quant_mx"
+    bsz, seq, c, gt, sc, sh = _resid_args(name, y, gate, residual, scale, shift, inplace)
+    if _resid_native_ok(y, residual, sc, sh, d, smooth, c):
+        return _native.resid_adaln_rotate_quant_mx(y, gt, residual, sc, sh, _default_mask_tuple(), smooth, float(eps), kmajor, inplace)
+    mask = _mask_arg(d)
+    rc = residual if residual.is_contiguous() else residual.contiguous()
+    yc = y if y.is_contiguous() else y.contiguous()
+    sm, sm_ptr = _smooth_ptr(smooth, c, residual.device)
+    x_new = rc if inplace else torch.empty_like(rc)
+    rows = bsz * seq
+    codes = torch.empty((c // 128, rows, 64) if kmajor else (rows, c // 2), dtype=torch.uint8, device=residual.device)
+    scales = (_kmajor_mx_scales(rows, c, residual.device) if kmajor
+              else torch.empty((rows, c // 128), dtype=torch.float16, device=residual.device))
+    with device_guard(residual.device):
+        check(lib().fpq_resid_adaln_rotate_quant_rows_codes_mx(
+            yc.data_ptr(), gt.data_ptr(), x_new.data_ptr(), rc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c,
+            dtype_id(residual.dtype), sc.data_ptr(), sh.data_ptr(), dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask,
+            1 if kmajor else 0, stream_ptr(residual.device)), "fpq_resid_adaln_rotate_quant_rows_codes_mx")
+    return x_new, codes, scales
+
+
+def resid_adaln_rotate_quant_token(y: torch.Tensor, gate: torch.Tensor, residual: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
+                                   table: str = "e2m3", d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
+                                   eps: float = 1e-6, emit: str = "values", kmajor: bool = False, inplace: bool = False):
+    """x_new = residual + y.mul(gate); adaln_rotate_quant_token(x_new, scale, shift, table, ...) - one launch.
+    emit="values": (x_new, fp16 [B, L, C]); emit="fp6": (x_new, dense 6-bit codes, row scales) in the format of `table` ("e2m3": FP6,
+    "e3m2": BF6), row-major or (kmajor) the activation side's k-major image.  The FP8 form has no fused twin.  C <= 2560."""
+    name = "resid_adaln_rotate_quant_token"
+    bsz, seq, c, gt, sc, sh = _resid_args(name, y, gate, residual, scale, shift, inplace)
+    if emit not in ("values", "fp6"):
+        raise RuntimeError(f"{name}: emit must be 'values' or 'fp6', got {emit!r}")
+    if emit == "fp6" and table not in ("e2m3", "e3m2"):
+        raise RuntimeError(f"{name}: emit='fp6' writes E2M3 or E3M2 codes, got table {table!r}")
+    if kmajor and emit != "fp6":
+        raise RuntimeError(f"{name}: kmajor is a layout of the 6-bit operand codes (emit='fp6')")
+    if _resid_native_ok(y, residual, sc, sh, d, smooth, c):
+        if emit == "values":
+            return _native.resid_adaln_rotate_quant_token(y, gt, residual, sc, sh, TABLE_IDS[table], _default_mask_tuple(), smooth,
+                                                          float(eps), inplace)
+        return _native.resid_adaln_rotate_quant_token_codes_f6(y, gt, residual, sc, sh, TABLE_IDS[table], _default_mask_tuple(), smooth,
+                                                               float(eps), kmajor, inplace)
+    mask = _mask_arg(d)
+    rc = residual if residual.is_contiguous() else residual.contiguous()
+    yc = y if y.is_contiguous() else y.contiguous()
+    sm, sm_ptr = _smooth_ptr(smooth, c, residual.device)
+    x_new = rc if inplace else torch.empty_like(rc)
+    rows = bsz * seq
+    with device_guard(residual.device):
+        if emit == "fp6":
+            codes = torch.empty((c // 128, rows, 96) if kmajor else (rows, c * 3 // 4), dtype=torch.uint8, device=residual.device)
+            scales = torch.empty((rows,), dtype=torch.float16, device=residual.device)
+            check(lib().fpq_resid_adaln_rotate_quant_token_rows_codes_f6(
+                yc.data_ptr(), gt.data_ptr(), x_new.data_ptr(), rc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c,
+                dtype_id(residual.dtype), sc.data_ptr(), sh.data_ptr(), dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask,
+                TABLE_IDS[table], 1 if kmajor else 0, stream_ptr(residual.device)), "fpq_resid_adaln_rotate_quant_token_rows_codes_f6")
+            return x_new, codes, scales
+        out = torch.empty(residual.shape, dtype=torch.float16, device=residual.device)
+        check(lib().fpq_resid_adaln_rotate_quant_token_rows(
+            yc.data_ptr(), gt.data_ptr(), x_new.data_ptr(), rc.data_ptr(), out.data_ptr(), None, None, None, rows, c,
+            dtype_id(residual.dtype), sc.data_ptr(), sh.data_ptr(), dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, TABLE_IDS[table],
+            stream_ptr(residual.device)), "fpq_resid_adaln_rotate_quant_token_rows")
+    return x_new, out

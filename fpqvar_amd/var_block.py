@@ -110,7 +110,7 @@ class GenerationBatch:
     def __init__(self, model: str = "d30-256", config: str = "w4a4", depth: Optional[int] = None,
                  batch_rows: Optional[int] = None, device=None, seed: int = 0, fused_fc1: bool = True, sdpa_in_f: bool = False,
                  kmajor: bool = True, qkv_to_cache: bool = True, attn_l2_norm: bool = False, qk_norm: str = "fused",
-                 kv_storage: str = "fp16"):
+                 kv_storage: str = "fp16", fuse_residual: bool = False):
         assert model in MODELS and config in ("w4a4", "w6a6") and qk_norm in ("fused", "torch")
         if kv_storage not in ("fp16", "codes"):
             raise ValueError(f"kv_storage must be 'fp16' or 'codes', got {kv_storage!r}")
@@ -134,6 +134,10 @@ class GenerationBatch:
         # path Q: mat_qkv writes k and v straight into the KV cache's slots (fpq_gemm_fp4_mx_split, W6A6: fpq_gemm_fp6_rows_split):
         # no copy-in pass
         self.qkv_to_cache = bool(qkv_to_cache)
+        # every x = x + y.mul(gamma) whose y comes out of a torch GEMM (path F: proj's and fc2's tail, path Q: fc2's) is applied by the
+        # adaLN producer that follows it (rotation.resid_adaln_rotate_quant*) instead of a launch of its own; the last block of a
+        # step ends with the plain gate_residual.  Same results, bit for bit.  Off by default.
+        self.fuse_residual = bool(fuse_residual)
         C, HID, B = self.C, self.HID, self.B
         g = torch.Generator(device=dev).manual_seed(seed)
         self.gen = g
@@ -211,20 +215,37 @@ class GenerationBatch:
             return rot.adaln_rotate_quant_token(t, sc, sh, "e2m3", smooth=sm)
         return rot.adaln_rotate_quant(t, sc, sh, "e2m1", smooth=sm)
 
-    def q_producer_linear(self, t, sc, sh, sm, name):
+    def resid_producer(self, path, pend, x, sc, sh, sm):
+        """fuse_residual: the pending x + y.mul(gate), pend = (y, gate), and the producer behind it in one launch.  Returns
+        (x_new, what the path's producer returns for x_new): path F - the quantized values, path Q - (codes, scales)."""
+        y, gate = pend
+        if path == "F":
+            if self.W6:
+                return rot.resid_adaln_rotate_quant_token(y, gate, x, sc, sh, "e2m3", smooth=sm)
+            return rot.resid_adaln_rotate_quant(y, gate, x, sc, sh, "e2m1", smooth=sm)
         if self.W6:
-            return gemm.linear_fp6(*rot.adaln_rotate_quant_token(t, sc, sh, "e2m3", smooth=sm, emit="fp6", kmajor=self.kmajor), *self.wop[name])
-        return gemm.linear_fp4(*rot.adaln_rotate_quant_mx(t, sc, sh, smooth=sm, kmajor=self.kmajor), *self.wop[name])
+            x_new, *operands = rot.resid_adaln_rotate_quant_token(y, gate, x, sc, sh, "e2m3", smooth=sm, emit="fp6", kmajor=self.kmajor)
+        else:
+            x_new, *operands = rot.resid_adaln_rotate_quant_mx(y, gate, x, sc, sh, smooth=sm, kmajor=self.kmajor)
+        return x_new, tuple(operands)
 
-    def q_qkv_to_cache(self, x, sc1, sh1, b, cache_kv, pos):
+    def q_producer_linear(self, t, sc, sh, sm, name, operands=None):
+        """operands: the producer's output when it has run already (fuse_residual)"""
+        if self.W6:
+            return gemm.linear_fp6(*(operands or rot.adaln_rotate_quant_token(t, sc, sh, "e2m3", smooth=sm, emit="fp6", kmajor=self.kmajor)),
+                                   *self.wop[name])
+        return gemm.linear_fp4(*(operands or rot.adaln_rotate_quant_mx(t, sc, sh, smooth=sm, kmajor=self.kmajor)), *self.wop[name])
+
+    def q_qkv_to_cache(self, x, sc1, sh1, b, cache_kv, pos, operands=None):
         """mat_qkv of block b with the split output: q [B, L, H, hd] comes back, k and v land in cache_kv at pos (with attn_l2_norm:
         normalized in the GEMM's epilogue)"""
         bias, hs = (self.qkv_bias[b], self.head_scale[b]) if self.attn_l2_norm else (None, None)
         if self.W6:
-            q = gemm.linear_fp6_qkv_to_cache(*rot.adaln_rotate_quant_token(x, sc1, sh1, "e2m3", smooth=self.s_qkv, emit="fp6", kmajor=self.kmajor),
+            q = gemm.linear_fp6_qkv_to_cache(*(operands or rot.adaln_rotate_quant_token(x, sc1, sh1, "e2m3", smooth=self.s_qkv, emit="fp6",
+                                                                                        kmajor=self.kmajor)),
                                              *self.wop["qkv"], bias, cache_kv, pos, x.shape[1], qk_norm_scale=hs)
         else:
-            q = gemm.linear_fp4_qkv_to_cache(*rot.adaln_rotate_quant_mx(x, sc1, sh1, smooth=self.s_qkv, kmajor=self.kmajor), *self.wop["qkv"],
+            q = gemm.linear_fp4_qkv_to_cache(*(operands or rot.adaln_rotate_quant_mx(x, sc1, sh1, smooth=self.s_qkv, kmajor=self.kmajor)), *self.wop["qkv"],
                                              bias, cache_kv, pos, x.shape[1], qk_norm_scale=hs)
         return q.view(self.B, x.shape[1], self.H, self.hd)
 
@@ -233,9 +254,9 @@ class GenerationBatch:
             return gemm.linear_fp6(*gemm.quantize_fp6(t2d, kmajor=self.kmajor), *self.wop["proj"], None, gate, resid)
         return gemm.linear_fp4(*gemm.quantize_mx(t2d, kmajor=self.kmajor), *self.wop["proj"], None, gate, resid)
 
-    def q_fc1_gelu_dual(self, t, sc, sh):
+    def q_fc1_gelu_dual(self, t, sc, sh, operands=None):
         """fc2's quantized input straight out of the fc1 GEMM: GELU(tanh) and the dual E1M2-/E2M1+ quantizer in its epilogue."""
-        return gemm.linear_fp4_gelu_dual(*rot.adaln_rotate_quant_mx(t, sc, sh, smooth=self.s_fc1, kmajor=self.kmajor), *self.wop["fc1"])
+        return gemm.linear_fp4_gelu_dual(*(operands or rot.adaln_rotate_quant_mx(t, sc, sh, smooth=self.s_fc1, kmajor=self.kmajor)), *self.wop["fc1"])
 
     def attend(self, q, kc, vc, scale=None):   # q [B,L,H,c]; kc, vc [B,Ltot,H,c] (flash layout, as the KV runs use)
         if scale is None and self.attn_l2_norm:
@@ -263,19 +284,19 @@ class GenerationBatch:
     def new_input(self, pn):
         return torch.randn(self.B, pn * pn, self.C, device=self.dev, generator=self.gen).half()
 
-    def attend_codes(self, path, cache, x, b, scale):
+    def attend_codes(self, path, cache, x, b, scale, prod=None):
         """The attention half of block b with kv_storage="codes": the same producers as the fp16 cache's lines of `step`, k / v
         handed to the PackedKVCache as views or through its staging slab; attention over the packed entries + the fresh k / v,
-        then their pack.  Returns [B, L, H, 64]."""
+        then their pack.  Returns [B, L, H, 64].  prod: the first producer's output when it has run already (fuse_residual)."""
         B, L, H, hd = self.B, x.shape[1], self.H, self.hd
         g1, g2, sc1, sc2, sh1, sh2 = self.mods[b]
         l2 = self.attn_l2_norm
         if path == "Q" and self.qkv_to_cache and not (l2 and self.qk_norm == "torch"):
-            return cache.attend_staged(self.q_qkv_to_cache(x, sc1, sh1, b, cache.staging, 0), L, scale)
+            return cache.attend_staged(self.q_qkv_to_cache(x, sc1, sh1, b, cache.staging, 0, prod), L, scale)
         if path == "F":
-            qkv = Fn.linear(self.f_producer(x, sc1, sh1, self.s_qkv), self.wq["qkv"])
+            qkv = Fn.linear(self.f_producer(x, sc1, sh1, self.s_qkv) if prod is None else prod, self.wq["qkv"])
         else:
-            qkv = self.q_producer_linear(x, sc1, sh1, self.s_qkv, "qkv")
+            qkv = self.q_producer_linear(x, sc1, sh1, self.s_qkv, "qkv", prod)
         if l2 and self.qk_norm == "torch":
             q, k, v = (t.half() for t in self.qk_norm_torch(qkv.view(B, L, 3 * self.C), b))
             return cache.attend(q, k, v, scale)
@@ -288,6 +309,7 @@ class GenerationBatch:
     def step(self, path, caches, x):
         B, C, H, hd, HID = self.B, self.C, self.H, self.hd, self.HID
         L = x.shape[1]
+        pend = None   # fuse_residual: (y, gate) of an x = x + y.mul(gate) that the next producer applies
         for b in range(self.depth):
             g1, g2, sc1, sc2, sh1, sh2 = self.mods[b]
             if path == "R":
@@ -314,16 +336,20 @@ class GenerationBatch:
                 continue
             l2 = self.attn_l2_norm
             scale = 1.0 if l2 else hd ** -0.5
+            prod = None
+            if pend is not None:   # the previous block's fc2 tail, applied by this block's first producer
+                x, prod = self.resid_producer(path, pend, x, sc1, sh1, self.s_qkv)
+                pend = None
             if self.kv_storage == "codes":
-                a = self.attend_codes(path, caches[b], x, b, scale).view(B, L, C)
+                a = self.attend_codes(path, caches[b], x, b, scale, prod).view(B, L, C)
             elif path == "Q" and self.qkv_to_cache and not (l2 and self.qk_norm == "torch"):
-                q = self.q_qkv_to_cache(x, sc1, sh1, b, caches[b].kv, caches[b].len)
+                q = self.q_qkv_to_cache(x, sc1, sh1, b, caches[b].kv, caches[b].len, prod)
                 kc, vc = caches[b].commit_written(L)
             else:
                 if path == "F":
-                    qkv = Fn.linear(self.f_producer(x, sc1, sh1, self.s_qkv), self.wq["qkv"])
+                    qkv = Fn.linear(self.f_producer(x, sc1, sh1, self.s_qkv) if prod is None else prod, self.wq["qkv"])
                 else:
-                    qkv = self.q_producer_linear(x, sc1, sh1, self.s_qkv, "qkv")
+                    qkv = self.q_producer_linear(x, sc1, sh1, self.s_qkv, "qkv", prod)
                 if l2 and self.qk_norm == "torch":
                     q, k, v = (t.half() for t in self.qk_norm_torch(qkv.view(B, L, 3 * C), b))
                     kc, vc = caches[b].append(k, v)
@@ -336,16 +362,23 @@ class GenerationBatch:
             if self.kv_storage != "codes":
                 a = self.attend(q, kc, vc, scale) if (path == "F" and self.sdpa_in_f) else ops.attention_blhc(q, kc, vc, scale).view(B, L, C)
             if path == "F":
-                x = ops.gate_residual(Fn.linear(self.f_act(a), self.wq["proj"]), g1, x)
+                proj = Fn.linear(self.f_act(a), self.wq["proj"])
+                if self.fuse_residual:   # proj's tail, applied by the fc1 producer
+                    x, h2 = self.resid_producer(path, (proj, g1), x, sc2, sh2, self.s_fc1)
+                else:
+                    x = ops.gate_residual(proj, g1, x)
+                    h2 = self.f_producer(x, sc2, sh2, self.s_fc1)
+                hq = self.act_then_fc2_quant(Fn.linear(h2, self.wq["fc1"]))
             else:
                 x = self.q_proj(a.view(B * L, C), g1, x).view(B, L, C)
-            if path == "F":
-                hq = self.act_then_fc2_quant(Fn.linear(self.f_producer(x, sc2, sh2, self.s_fc1), self.wq["fc1"]))
-            elif self.fused_fc1:
-                hq = self.q_fc1_gelu_dual(x, sc2, sh2).view(B, L, HID)
+                if self.fused_fc1:
+                    hq = self.q_fc1_gelu_dual(x, sc2, sh2).view(B, L, HID)
+                else:
+                    hq = self.act_then_fc2_quant(self.q_producer_linear(x, sc2, sh2, self.s_fc1, "fc1").view(B, L, HID))
+            if self.fuse_residual and b + 1 < self.depth:
+                pend = (Fn.linear(hq, self.wq["fc2"]), g2)
             else:
-                hq = self.act_then_fc2_quant(self.q_producer_linear(x, sc2, sh2, self.s_fc1, "fc1").view(B, L, HID))
-            x = ops.gate_residual(Fn.linear(hq, self.wq["fc2"]), g2, x)
+                x = ops.gate_residual(Fn.linear(hq, self.wq["fc2"]), g2, x)
         return x
 
     # ---- timing ----------------------------------------------------------------------------------------------------

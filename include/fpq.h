@@ -51,7 +51,9 @@ extern "C" {
                                 addition only, and the number stays because tests/test_format_search_fused_host.py pins it: look the symbol up;
                                  + its fc1 tail and split output, and all four forms on k-major images (fpq_gemm_w6_*_km): additions again;
                                  + the rotate and adaLN producers on the full FP6 tables: fpq_gf6_rotate_quant_rows_codes,
-                                fpq_gf6_adaln_rotate_quant_rows_codes - additions again) */
+                                fpq_gf6_adaln_rotate_quant_rows_codes - additions again;
+                                 + the gated residual folded into the adaLN producer behind it: fpq_resid_adaln_rotate_quant_rows, _rows_codes_mx,
+                                _token_rows, _token_rows_codes_f6 - additions again) */
 
 typedef void* fpq_stream_t; /* hipStream_t */
 
@@ -1037,6 +1039,41 @@ int fpq_gf6_adaln_rotate_quant_rows_codes(const void* x, uint8_t* codes, void* s
                                           const void* scale, const void* shift, int mod_dtype, int64_t rows_per_batch, float eps,
                                           const float* smooth, const uint32_t* sign_mask_host, int table_id, int kmajor,
                                           fpq_stream_t stream);
+
+/* THE GATED RESIDUAL FOLDED INTO THE adaLN PRODUCER THAT FOLLOWS IT.  In a block every x = x + y.mul(gate) whose y comes out of a GEMM that
+ * has no epilogue of ours is followed by an adaLN producer that reads the row just written.  These four run both in one launch:
+ *     x_new = residual + y.mul(gate)          written to x_out, [rows, cols] of in_dtype
+ *     ...   = the twin entry point on x_new   (fpq_adaln_rotate_quant_rows, _rows_codes_mx[_km], _token_rows, _token_rows_codes_f6)
+ * y: fp16 [rows, cols]; gate: fp16 [rows / rows_per_batch, cols], one row per batch entry as scale and shift; residual: the twin's x.
+ * Every other argument is the twin's, in the twin's order; kmajor selects the twin's _km form where it has one.
+ * CONTRACT (bit equality, no tolerance): x_out is what torch computes on the GPU for residual + y.mul(gate) - fp16 rows:
+ * half(residual + half(y * gate)), which is also fpq_gate_residual's result; fp32 rows: residual + float(half(y * gate)) - and every
+ * other output is byte for byte what the twin writes when handed x_out as its x.  The same kernel variant runs as for the twin (they
+ * share one dispatch), under the same switches.
+ * ALIASING: x_out may be exactly `residual` (an in-place residual stream: a row is read and written by one wavefront, and read first).
+ * x_out must not overlap y, and must not overlap residual in any other way.
+ * Checks: the twin's own come first, in the twin's order (rows == 0 or cols == 0 among them: FPQ_OK, nothing launched); then y, gate or
+ * x_out NULL (FPQ_ERR_ARG); y, gate or x_out not 16-byte aligned (FPQ_ERR_ARG); cols > 2560 (FPQ_ERR_SHAPE: the kernel for wider rows
+ * has no fused form).  The 6-bit group forms (_g6, _gf6) and the FP8 form have no fused twin.
+ * Additions that change no existing entry point: FPQ_VERSION stays, a caller looks the symbols up. */
+int fpq_resid_adaln_rotate_quant_rows(const void* y, const void* gate, void* x_out, const void* residual, void* out, void* h_out,
+                                      void* rotated_out, int64_t rows, int64_t cols, int in_dtype, const void* scale,
+                                      const void* shift, int mod_dtype, int64_t rows_per_batch, float eps, const float* smooth,
+                                      const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream);
+int fpq_resid_adaln_rotate_quant_rows_codes_mx(const void* y, const void* gate, void* x_out, const void* residual, uint8_t* codes,
+                                               void* scales, int64_t rows, int64_t cols, int in_dtype, const void* scale,
+                                               const void* shift, int mod_dtype, int64_t rows_per_batch, float eps,
+                                               const float* smooth, const uint32_t* sign_mask_host, int kmajor, fpq_stream_t stream);
+int fpq_resid_adaln_rotate_quant_token_rows(const void* y, const void* gate, void* x_out, const void* residual, void* out,
+                                            void* h_out, void* rotated_out, void* row_scales, int64_t rows, int64_t cols,
+                                            int in_dtype, const void* scale, const void* shift, int mod_dtype,
+                                            int64_t rows_per_batch, float eps, const float* smooth,
+                                            const uint32_t* sign_mask_host, int table_id, fpq_stream_t stream);
+int fpq_resid_adaln_rotate_quant_token_rows_codes_f6(const void* y, const void* gate, void* x_out, const void* residual,
+                                                     uint8_t* codes, void* row_scales, int64_t rows, int64_t cols, int in_dtype,
+                                                     const void* scale, const void* shift, int mod_dtype, int64_t rows_per_batch,
+                                                     float eps, const float* smooth, const uint32_t* sign_mask_host, int table_id,
+                                                     int kmajor, fpq_stream_t stream);
 
 /* fpq_kv_cache_step_qknorm: fpq_kv_cache_step (same arguments, same checks) for an fp16 qkv WITHOUT the norm (path F, or a
  * mat_qkv that is not split): the new k is normalized and the bias added on its way into the cache, and the same launch writes

@@ -34,15 +34,18 @@ def main():
                     help="with --attn-l2-norm: the norm inside the qkv-to-cache kernels (fused) or the reference's torch lines between them")
     ap.add_argument("--kv-codes", action="store_true",
                     help="paths F / Q: every block's KV cache as FP6 codes + scales (kv_cache.PackedKVCache; kv_storage='codes')")
+    ap.add_argument("--fuse-residual", action="store_true",
+                    help="paths F / Q: every gated residual behind a torch GEMM is applied by the adaLN producer that follows it "
+                         "(rotation.resid_adaln_rotate_quant*; GenerationBatch(fuse_residual=True)) - same results, fewer launches")
     ap.add_argument("--tuned-gemms", action="store_true", help="torch's own GEMMs with the recorded TunableOp selections (var_block.tuned_torch_gemms)")
     args = ap.parse_args()
     torch.manual_seed(0)
     gb = var_block.GenerationBatch(args.model, args.config, depth=args.depth, batch_rows=args.batch, device="cuda:0",
                                    fused_fc1=not args.unfused_fc1, sdpa_in_f=args.sdpa_in_f, kmajor=not args.row_major_operands,
                                    qkv_to_cache=not args.qkv_copy_in, attn_l2_norm=args.attn_l2_norm, qk_norm=args.qk_norm,
-                                   kv_storage="codes" if args.kv_codes else "fp16")
+                                   kv_storage="codes" if args.kv_codes else "fp16", fuse_residual=args.fuse_residual)
     res = {"workload": gb.describe(), "depth": gb.depth, "batch_rows": gb.B, "fc1_epilogue_fused": gb.fused_fc1, "kmajor_operands": gb.kmajor, "qkv_to_cache": gb.qkv_to_cache,
-           "attn_l2_norm": gb.attn_l2_norm, "qk_norm": gb.qk_norm, "kv_storage": gb.kv_storage, "library": _lib.build_tag()}
+           "attn_l2_norm": gb.attn_l2_norm, "qk_norm": gb.qk_norm, "kv_storage": gb.kv_storage, "fuse_residual": gb.fuse_residual, "library": _lib.build_tag()}
     paths = args.paths.split(",")
     import contextlib
     ctx = var_block.tuned_torch_gemms() if args.tuned_gemms else contextlib.nullcontext()
