@@ -8,6 +8,9 @@
 //   quant(x, y) -> (z, idx)                                   quant/quant.cpp:27-29
 //   the reference-named per-group / per-token / dual functions  tr/quant_utils.py:265-282,313-330,361-378,415-452,503-646
 //   quant_rows / quant_rows_dual                               the generic forms fpqvar_amd.ops wraps
+//   producer                                                   the hot calls of rotation.py's twelve rotate / adaLN producers: one body,
+//                                                              one row of PRODUCER_FORMS per C entry point
+//   kv_cache_step*, linear_fp4*, linear_w6, gelu_quant_rows_dual, sqerr_rows_weighted   the same for ops.py / gemm.py
 // PyTorch is plumbing here (tensors in, tensors out, device memory, streams); no kernel and no arithmetic lives in this
 // file.  fpqvar_amd.quant_utils / quant_cuda bind these when the module is built and fall back to the ctypes path
 // otherwise (same C entry points either way; tests cover both).
@@ -197,55 +200,46 @@ at::Tensor fp6_quant_int_neg_e2m3_pos_per_token_contig(const at::Tensor& x, int6
   return quant_rows_dual(x, FPQ_INT_NEG, FPQ_E2M3_POS, x.size(-1), c10::nullopt, c10::nullopt);
 }
 
-// ---- the fused producers (tr/basic_var.py:263,266 + tr/quant_utils.py:765), value output, contiguous arguments: the hot
-// calls of a generation step; everything else (intermediates, operand outputs, odd layouts) stays with rotation.py ----
-at::Tensor rotate_quant(const at::Tensor& x, int64_t table_id, const std::array<uint32_t, 4>& sign_mask, const c10::optional<at::Tensor>& smooth) {
-  require_gpu(x, "rotate_quant");
-  TORCH_CHECK(x.scalar_type() == at::kHalf || x.scalar_type() == at::kFloat, "rotate_quant: x must be float16 or float32, got ", x.scalar_type());
-  TORCH_CHECK(x.dim() >= 1 && x.size(-1) % 128 == 0, "rotate_quant: the last dimension must be a multiple of 128");
-  const int64_t c = x.size(-1);
-  const at::Tensor xc = x.is_contiguous() ? x : x.contiguous();
-  const float* sm = nullptr;
-  if (smooth.has_value()) {
-    TORCH_CHECK(smooth->scalar_type() == at::kFloat && smooth->is_contiguous() && smooth->numel() == c && smooth->device() == x.device(),
-                "rotate_quant (native): smooth must be a contiguous float32 [C] tensor on x's device");
-    sm = (const float*)smooth->data_ptr();
-  }
-  at::Tensor out = at::empty(x.sizes(), x.options().dtype(at::kHalf));
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  check(fpq_rotate_quant_rows(xc.data_ptr(), out.data_ptr(), nullptr, x.numel() / c, c, dtype_id(x.scalar_type(), "rotate_quant"), sm,
-                              sign_mask.data(), (int)table_id, current_stream(x)), "fpq_rotate_quant_rows");
-  return out;
-}
 
-at::Tensor adaln_rotate_quant(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift, int64_t table_id,
-                              const std::array<uint32_t, 4>& sign_mask, const c10::optional<at::Tensor>& smooth, double eps) {
-  require_gpu(x, "adaln_rotate_quant");
-  TORCH_CHECK(x.dim() == 3, "adaln_rotate_quant: x must be [B, L, C]");
-  TORCH_CHECK(x.scalar_type() == at::kHalf || x.scalar_type() == at::kFloat, "adaln_rotate_quant: x must be float16 or float32, got ", x.scalar_type());
-  const int64_t b = x.size(0), l = x.size(1), c = x.size(2);
-  TORCH_CHECK(c % 128 == 0 && c <= 4096, "adaln_rotate_quant: C must be a multiple of 128 and at most 4096");
-  TORCH_CHECK(scale.scalar_type() == shift.scalar_type() && (scale.scalar_type() == at::kHalf || scale.scalar_type() == at::kFloat),
-              "adaln_rotate_quant: scale and shift must both be float16 or both float32");
-  TORCH_CHECK(x.is_contiguous() && scale.is_contiguous() && shift.is_contiguous() && scale.numel() == b * c && shift.numel() == b * c &&
-              scale.device() == x.device() && shift.device() == x.device(),
-              "adaln_rotate_quant (native): contiguous x and [B, C] modulation rows on x's device");
-  const float* sm = nullptr;
-  if (smooth.has_value()) {
-    TORCH_CHECK(smooth->scalar_type() == at::kFloat && smooth->is_contiguous() && smooth->numel() == c && smooth->device() == x.device(),
-                "adaln_rotate_quant (native): smooth must be a contiguous float32 [C] tensor on x's device");
-    sm = (const float*)smooth->data_ptr();
-  }
-  at::Tensor out = at::empty(x.sizes(), x.options().dtype(at::kHalf));
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  check(fpq_adaln_rotate_quant_rows(x.data_ptr(), out.data_ptr(), nullptr, nullptr, b * l, c, dtype_id(x.scalar_type(), "adaln_rotate_quant"),
-                                    scale.data_ptr(), shift.data_ptr(), dtype_id(scale.scalar_type(), "adaln_rotate_quant"), l, (float)eps, sm,
-                                    sign_mask.data(), (int)table_id, current_stream(x)), "fpq_adaln_rotate_quant_rows");
-  return out;
-}
+// ---- the row producers (tr/basic_var.py:263,266 + tr/quant_utils.py:765): rotate / adaLN + rotate / gated
+// residual + adaLN + rotate, then the quantizer, emitting values or what the matrix-core GEMMs consume.  ONE body for the usual
+// arguments of all of them (contiguous tensors, the default sign vector's mask, a float32 [C] smooth); everything else (intermediates,
+// odd layouts, a sign vector of the caller's) stays with rotation.py, which holds the public functions and names the form. ----
+enum Front { ROWS, ADALN, RESID };            // x [..., C]; x [B, L, C] with [B, C] modulation rows; the same with (y, gate) in front
+enum Out { VALUES, GROUP_CODES, ROW_CODES };  // fp16 of x's shape; codes + a scale per 128 elements; codes + a scale per row
+enum Form { ROTATE, ROTATE_MX, ROTATE_G6, ROTATE_GF6, ADALN_VALUES, ADALN_MX, ADALN_G6, ADALN_GF6, TOKEN, TOKEN_FP8, TOKEN_FP6, TOKEN_F6,
+            RESID_VALUES, RESID_MX, RESID_TOKEN, RESID_TOKEN_F6, N_FORMS };
+struct ProducerForm {
+  const char* entry;      // the C entry point (include/fpq.h), by which rotation.py finds the form's number
+  const char* entry_km;   // its twin that writes k-major images, where that is an entry point of its own
+  bool km_flag;           // ... or the layout is an `int kmajor` of `entry`
+  Front front;
+  Out out;
+  int seg;                // bytes of codes per 128 elements: 64 FP4 nibbles, 96 dense 6-bit codes, 128 E4M3 bytes
+  int64_t max_c;
+};
+const ProducerForm PRODUCER_FORMS[N_FORMS] = {
+    {"fpq_rotate_quant_rows", nullptr, false, ROWS, VALUES, 0, 1 << 30},
+    {"fpq_rotate_quant_rows_codes_mx", "fpq_rotate_quant_rows_codes_mx_km", false, ROWS, GROUP_CODES, 64, 1 << 30},
+    {"fpq_a6w4_rotate_quant_rows_codes", nullptr, true, ROWS, GROUP_CODES, 96, 1 << 30},        // table_id FPQ_E1M2 / FPQ_E3M0
+    {"fpq_gf6_rotate_quant_rows_codes", nullptr, true, ROWS, GROUP_CODES, 96, 1 << 30},         // table_id FPQ_E2M3 / FPQ_E3M2
+    {"fpq_adaln_rotate_quant_rows", nullptr, false, ADALN, VALUES, 0, 4096},
+    {"fpq_adaln_rotate_quant_rows_codes_mx", "fpq_adaln_rotate_quant_rows_codes_mx_km", false, ADALN, GROUP_CODES, 64, 4096},
+    {"fpq_a6w4_adaln_rotate_quant_rows_codes", nullptr, true, ADALN, GROUP_CODES, 96, 2560},
+    {"fpq_gf6_adaln_rotate_quant_rows_codes", nullptr, true, ADALN, GROUP_CODES, 96, 2560},
+    // per-token configurations (W6A6): values, or the operands of the row-scaled GEMMs
+    {"fpq_adaln_rotate_quant_token_rows", nullptr, false, ADALN, VALUES, 0, 2560},
+    {"fpq_adaln_rotate_quant_token_rows_codes_fp8", nullptr, false, ADALN, ROW_CODES, 128, 2560},
+    {"fpq_adaln_rotate_quant_token_rows_codes_fp6", "fpq_adaln_rotate_quant_token_rows_codes_fp6_km", false, ADALN, ROW_CODES, 96, 2560},   // E2M3
+    {"fpq_adaln_rotate_quant_token_rows_codes_f6", nullptr, true, ADALN, ROW_CODES, 96, 2560},   // either format (FPQ_E2M3: FP6, FPQ_E3M2: BF6)
+    // the gated residual in front folded in (fpq_resid_adaln_*): x_new = residual + y.mul(gate) goes to x_out - a fresh tensor, or
+    // `residual` itself (inplace) - and comes back in front of what the twin returns
+    {"fpq_resid_adaln_rotate_quant_rows", nullptr, false, RESID, VALUES, 0, 2560},
+    {"fpq_resid_adaln_rotate_quant_rows_codes_mx", nullptr, true, RESID, GROUP_CODES, 64, 2560},
+    {"fpq_resid_adaln_rotate_quant_token_rows", nullptr, false, RESID, VALUES, 0, 2560},
+    {"fpq_resid_adaln_rotate_quant_token_rows_codes_f6", nullptr, true, RESID, ROW_CODES, 96, 2560},
+};
 
-// ---- the "Q" path: the same producers emitting what the matrix-core GEMMs consume, the KV-cache step and the FP4 GEMM
-// (rotation.py / gemm.py / ops.py hold the general forms and dispatch here for the usual arguments) ----
 struct ProducerArgs {
   int64_t b, l, c;
   const float* smooth;
@@ -278,175 +272,8 @@ ProducerArgs producer_checks(const char* what, const at::Tensor& x, const at::Te
   return a;
 }
 
-// FP4 operand codes: row-major [rows, C / 2], or (kmajor) the activation side's k-major image [C / 128, rows, 64] (include/fpq.h)
-static at::Tensor mx_codes_tensor(const at::Tensor& x, int64_t rows, int64_t c, bool kmajor) {
-  return kmajor ? at::empty({c / 128, rows, 64}, x.options().dtype(at::kByte)) : at::empty({rows, c / 2}, x.options().dtype(at::kByte));
-}
-// ... and their scales: fp16 [rows, C / 128], or (kmajor) the fp32 k-major scale image [C / 128, rows rounded up to 4], padding zeroed
-static at::Tensor mx_scales_tensor(const at::Tensor& x, int64_t rows, int64_t c, bool kmajor) {
-  if (!kmajor) return at::empty({rows, c / 128}, x.options().dtype(at::kHalf));
-  const int64_t pad = (rows + 3) / 4 * 4;
-  at::Tensor t = at::empty({c / 128, pad}, x.options().dtype(at::kFloat));
-  if (pad != rows) t.narrow(1, rows, pad - rows).zero_();
-  return t;
-}
-
-std::tuple<at::Tensor, at::Tensor> rotate_quant_mx(const at::Tensor& x, const std::array<uint32_t, 4>& sign_mask,
-                                                   const c10::optional<at::Tensor>& smooth, bool kmajor) {
-  const ProducerArgs a = producer_checks("rotate_quant_mx", x, nullptr, nullptr, smooth, 1 << 30);
-  const int64_t rows = a.l;
-  at::Tensor codes = mx_codes_tensor(x, rows, a.c, kmajor);
-  at::Tensor scales = mx_scales_tensor(x, rows, a.c, kmajor);
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  check((kmajor ? fpq_rotate_quant_rows_codes_mx_km : fpq_rotate_quant_rows_codes_mx)(
-            x.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c, dtype_id(x.scalar_type(), "rotate_quant_mx"), a.smooth,
-            sign_mask.data(), current_stream(x)),
-        kmajor ? "fpq_rotate_quant_rows_codes_mx_km" : "fpq_rotate_quant_rows_codes_mx");
-  return {codes, scales};
-}
-
-std::tuple<at::Tensor, at::Tensor> adaln_rotate_quant_mx(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift,
-                                                         const std::array<uint32_t, 4>& sign_mask,
-                                                         const c10::optional<at::Tensor>& smooth, double eps, bool kmajor) {
-  const ProducerArgs a = producer_checks("adaln_rotate_quant_mx", x, &scale, &shift, smooth, 4096);
-  const int64_t rows = a.b * a.l;
-  at::Tensor codes = mx_codes_tensor(x, rows, a.c, kmajor);
-  at::Tensor scales = mx_scales_tensor(x, rows, a.c, kmajor);
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  check((kmajor ? fpq_adaln_rotate_quant_rows_codes_mx_km : fpq_adaln_rotate_quant_rows_codes_mx)(
-            x.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c, dtype_id(x.scalar_type(), "adaln_rotate_quant_mx"),
-            scale.data_ptr(), shift.data_ptr(), dtype_id(scale.scalar_type(), "adaln_rotate_quant_mx"), a.l, (float)eps, a.smooth,
-            sign_mask.data(), current_stream(x)),
-        kmajor ? "fpq_adaln_rotate_quant_rows_codes_mx_km" : "fpq_adaln_rotate_quant_rows_codes_mx");
-  return {codes, scales};
-}
-
-// the same pair emitting the A6W4 GEMM's activation operands (table_id FPQ_E1M2 / FPQ_E3M0): dense 6-bit codes [rows, 3 C / 4] + fp16
-// scales, or (kmajor) the 6-bit image [C / 128, rows, 96] + the fp32 scale image
-static at::Tensor g6_codes_tensor(const at::Tensor& x, int64_t rows, int64_t c, bool kmajor) {
-  return kmajor ? at::empty({c / 128, rows, 96}, x.options().dtype(at::kByte)) : at::empty({rows, c / 4 * 3}, x.options().dtype(at::kByte));
-}
-
-std::tuple<at::Tensor, at::Tensor> rotate_quant_g6(const at::Tensor& x, int64_t table_id, const std::array<uint32_t, 4>& sign_mask,
-                                                   const c10::optional<at::Tensor>& smooth, bool kmajor) {
-  const ProducerArgs a = producer_checks("rotate_quant_g6", x, nullptr, nullptr, smooth, 1 << 30);
-  const int64_t rows = a.l;
-  at::Tensor codes = g6_codes_tensor(x, rows, a.c, kmajor);
-  at::Tensor scales = mx_scales_tensor(x, rows, a.c, kmajor);
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  check(fpq_a6w4_rotate_quant_rows_codes(x.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c,
-                                         dtype_id(x.scalar_type(), "rotate_quant_g6"), a.smooth, sign_mask.data(), (int)table_id,
-                                         kmajor ? 1 : 0, current_stream(x)),
-        "fpq_a6w4_rotate_quant_rows_codes");
-  return {codes, scales};
-}
-
-std::tuple<at::Tensor, at::Tensor> adaln_rotate_quant_g6(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift,
-                                                         int64_t table_id, const std::array<uint32_t, 4>& sign_mask,
-                                                         const c10::optional<at::Tensor>& smooth, double eps, bool kmajor) {
-  const ProducerArgs a = producer_checks("adaln_rotate_quant_g6", x, &scale, &shift, smooth, 2560);
-  const int64_t rows = a.b * a.l;
-  at::Tensor codes = g6_codes_tensor(x, rows, a.c, kmajor);
-  at::Tensor scales = mx_scales_tensor(x, rows, a.c, kmajor);
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  check(fpq_a6w4_adaln_rotate_quant_rows_codes(x.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c,
-                                               dtype_id(x.scalar_type(), "adaln_rotate_quant_g6"), scale.data_ptr(), shift.data_ptr(),
-                                               dtype_id(scale.scalar_type(), "adaln_rotate_quant_g6"), a.l, (float)eps, a.smooth,
-                                               sign_mask.data(), (int)table_id, kmajor ? 1 : 0, current_stream(x)),
-        "fpq_a6w4_adaln_rotate_quant_rows_codes");
-  return {codes, scales};
-}
-
-// the same pair on the full FP6 tables (table_id FPQ_E2M3 / FPQ_E3M2): the operands fpq_gf6_quant_rows_codes makes of the rotated rows,
-// in the same shapes
-std::tuple<at::Tensor, at::Tensor> rotate_quant_gf6(const at::Tensor& x, int64_t table_id, const std::array<uint32_t, 4>& sign_mask,
-                                                    const c10::optional<at::Tensor>& smooth, bool kmajor) {
-  const ProducerArgs a = producer_checks("rotate_quant_gf6", x, nullptr, nullptr, smooth, 1 << 30);
-  const int64_t rows = a.l;
-  at::Tensor codes = g6_codes_tensor(x, rows, a.c, kmajor);
-  at::Tensor scales = mx_scales_tensor(x, rows, a.c, kmajor);
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  check(fpq_gf6_rotate_quant_rows_codes(x.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c,
-                                        dtype_id(x.scalar_type(), "rotate_quant_gf6"), a.smooth, sign_mask.data(), (int)table_id,
-                                        kmajor ? 1 : 0, current_stream(x)),
-        "fpq_gf6_rotate_quant_rows_codes");
-  return {codes, scales};
-}
-
-std::tuple<at::Tensor, at::Tensor> adaln_rotate_quant_gf6(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift,
-                                                          int64_t table_id, const std::array<uint32_t, 4>& sign_mask,
-                                                          const c10::optional<at::Tensor>& smooth, double eps, bool kmajor) {
-  const ProducerArgs a = producer_checks("adaln_rotate_quant_gf6", x, &scale, &shift, smooth, 2560);
-  const int64_t rows = a.b * a.l;
-  at::Tensor codes = g6_codes_tensor(x, rows, a.c, kmajor);
-  at::Tensor scales = mx_scales_tensor(x, rows, a.c, kmajor);
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  check(fpq_gf6_adaln_rotate_quant_rows_codes(x.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c,
-                                              dtype_id(x.scalar_type(), "adaln_rotate_quant_gf6"), scale.data_ptr(), shift.data_ptr(),
-                                              dtype_id(scale.scalar_type(), "adaln_rotate_quant_gf6"), a.l, (float)eps, a.smooth,
-                                              sign_mask.data(), (int)table_id, kmajor ? 1 : 0, current_stream(x)),
-        "fpq_gf6_adaln_rotate_quant_rows_codes");
-  return {codes, scales};
-}
-
-// per-token configurations (W6A6): values, or the operands of the row-scaled GEMMs - code_bits 8: E4M3 bytes, 6: dense E2M3
-at::Tensor adaln_rotate_quant_token(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift, int64_t table_id,
-                                    const std::array<uint32_t, 4>& sign_mask, const c10::optional<at::Tensor>& smooth, double eps) {
-  const ProducerArgs a = producer_checks("adaln_rotate_quant_token", x, &scale, &shift, smooth, 2560);
-  at::Tensor out = at::empty(x.sizes(), x.options().dtype(at::kHalf));
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  check(fpq_adaln_rotate_quant_token_rows(x.data_ptr(), out.data_ptr(), nullptr, nullptr, nullptr, a.b * a.l, a.c,
-                                          dtype_id(x.scalar_type(), "adaln_rotate_quant_token"), scale.data_ptr(), shift.data_ptr(),
-                                          dtype_id(scale.scalar_type(), "adaln_rotate_quant_token"), a.l, (float)eps, a.smooth,
-                                          sign_mask.data(), (int)table_id, current_stream(x)), "fpq_adaln_rotate_quant_token_rows");
-  return out;
-}
-
-std::tuple<at::Tensor, at::Tensor> adaln_rotate_quant_token_codes(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift,
-                                                                  int64_t table_id, int64_t code_bits,
-                                                                  const std::array<uint32_t, 4>& sign_mask,
-                                                                  const c10::optional<at::Tensor>& smooth, double eps, bool kmajor) {
-  const ProducerArgs a = producer_checks("adaln_rotate_quant_token_codes", x, &scale, &shift, smooth, 2560);
-  TORCH_CHECK(code_bits == 8 || (code_bits == 6 && table_id == FPQ_E2M3), "adaln_rotate_quant_token_codes: E4M3 bytes (8) or dense E2M3 codes (6)");
-  TORCH_CHECK(!kmajor || code_bits == 6, "adaln_rotate_quant_token_codes: kmajor is a layout of the dense 6-bit codes");
-  const int64_t rows = a.b * a.l;
-  at::Tensor codes = kmajor ? at::empty({a.c / 128, rows, 96}, x.options().dtype(at::kByte))   // the activation side's k-major image (include/fpq.h)
-                            : at::empty({rows, code_bits == 8 ? a.c : a.c * 3 / 4}, x.options().dtype(at::kByte));
-  at::Tensor scales = at::empty({rows}, x.options().dtype(at::kHalf));
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  const auto fn = code_bits == 8 ? fpq_adaln_rotate_quant_token_rows_codes_fp8
-                  : kmajor       ? fpq_adaln_rotate_quant_token_rows_codes_fp6_km
-                                 : fpq_adaln_rotate_quant_token_rows_codes_fp6;
-  check(fn(x.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c, dtype_id(x.scalar_type(), "adaln_rotate_quant_token_codes"),
-           scale.data_ptr(), shift.data_ptr(), dtype_id(scale.scalar_type(), "adaln_rotate_quant_token_codes"), a.l, (float)eps, a.smooth,
-           sign_mask.data(), (int)table_id, current_stream(x)), "fpq_adaln_rotate_quant_token_rows_codes");
-  return {codes, scales};
-}
-
-// ... and the dense 6-bit codes of either format (FPQ_E2M3: FP6, FPQ_E3M2: BF6), row-major or the k-major image
-std::tuple<at::Tensor, at::Tensor> adaln_rotate_quant_token_codes_f6(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift,
-                                                                     int64_t table_id, const std::array<uint32_t, 4>& sign_mask,
-                                                                     const c10::optional<at::Tensor>& smooth, double eps, bool kmajor) {
-  const ProducerArgs a = producer_checks("adaln_rotate_quant_token_codes_f6", x, &scale, &shift, smooth, 2560);
-  TORCH_CHECK(table_id == FPQ_E2M3 || table_id == FPQ_E3M2, "adaln_rotate_quant_token_codes_f6: dense 6-bit codes are E2M3 or E3M2");
-  const int64_t rows = a.b * a.l;
-  at::Tensor codes = kmajor ? at::empty({a.c / 128, rows, 96}, x.options().dtype(at::kByte))
-                            : at::empty({rows, a.c * 3 / 4}, x.options().dtype(at::kByte));
-  at::Tensor scales = at::empty({rows}, x.options().dtype(at::kHalf));
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  check(fpq_adaln_rotate_quant_token_rows_codes_f6(x.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c,
-                                                   dtype_id(x.scalar_type(), "adaln_rotate_quant_token_codes_f6"), scale.data_ptr(),
-                                                   shift.data_ptr(), dtype_id(scale.scalar_type(), "adaln_rotate_quant_token_codes_f6"), a.l,
-                                                   (float)eps, a.smooth, sign_mask.data(), (int)table_id, kmajor ? 1 : 0, current_stream(x)),
-        "fpq_adaln_rotate_quant_token_rows_codes_f6");
-  return {codes, scales};
-}
-
-// ---- the same producers with the gated residual in front folded in (include/fpq.h, fpq_resid_adaln_*): x_new = residual + y.mul(gate)
-// goes to x_out - a fresh tensor, or `residual` itself (inplace) - and comes back in front of what the twin returns ----
 static at::Tensor resid_checks(const char* what, const at::Tensor& y, const at::Tensor& gate, const at::Tensor& residual,
                                const ProducerArgs& a, bool inplace) {
-  TORCH_CHECK(a.c <= 2560, what, ": C must be a multiple of 128 and at most 2560");
   TORCH_CHECK(y.scalar_type() == at::kHalf && gate.scalar_type() == at::kHalf, what, ": y and gate must be float16");
   TORCH_CHECK(y.sizes() == residual.sizes(), what, ": y must have the shape of residual");
   TORCH_CHECK(y.is_contiguous() && gate.is_contiguous() && gate.numel() == a.b * a.c && y.device() == residual.device() &&
@@ -458,78 +285,96 @@ static at::Tensor resid_checks(const char* what, const at::Tensor& y, const at::
   return inplace ? residual : at::empty_like(residual);
 }
 
-std::tuple<at::Tensor, at::Tensor> resid_adaln_rotate_quant(const at::Tensor& y, const at::Tensor& gate, const at::Tensor& residual,
-                                                            const at::Tensor& scale, const at::Tensor& shift, int64_t table_id,
-                                                            const std::array<uint32_t, 4>& sign_mask,
-                                                            const c10::optional<at::Tensor>& smooth, double eps, bool inplace) {
-  const ProducerArgs a = producer_checks("resid_adaln_rotate_quant", residual, &scale, &shift, smooth, 2560);
-  at::Tensor x_new = resid_checks("resid_adaln_rotate_quant", y, gate, residual, a, inplace);
-  at::Tensor out = at::empty(residual.sizes(), residual.options().dtype(at::kHalf));
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(residual.device());
-  check(fpq_resid_adaln_rotate_quant_rows(y.data_ptr(), gate.data_ptr(), x_new.data_ptr(), residual.data_ptr(), out.data_ptr(), nullptr,
-                                          nullptr, a.b * a.l, a.c, dtype_id(residual.scalar_type(), "resid_adaln_rotate_quant"),
-                                          scale.data_ptr(), shift.data_ptr(), dtype_id(scale.scalar_type(), "resid_adaln_rotate_quant"), a.l,
-                                          (float)eps, a.smooth, sign_mask.data(), (int)table_id, current_stream(residual)),
-        "fpq_resid_adaln_rotate_quant_rows");
-  return {x_new, out};
+// operand codes: row-major [rows, C / 128 * seg], or (kmajor) the activation side's k-major image [C / 128, rows, seg] (include/fpq.h)
+static at::Tensor codes_tensor(const at::Tensor& x, int64_t rows, int64_t c, int64_t seg, bool kmajor) {
+  return kmajor ? at::empty({c / 128, rows, seg}, x.options().dtype(at::kByte)) : at::empty({rows, c / 128 * seg}, x.options().dtype(at::kByte));
+}
+// ... and their per-group scales: fp16 [rows, C / 128], or (kmajor) the fp32 k-major scale image [C / 128, rows rounded up to 4], padding zeroed
+static at::Tensor group_scales_tensor(const at::Tensor& x, int64_t rows, int64_t c, bool kmajor) {
+  if (!kmajor) return at::empty({rows, c / 128}, x.options().dtype(at::kHalf));
+  const int64_t pad = (rows + 3) / 4 * 4;
+  at::Tensor t = at::empty({c / 128, pad}, x.options().dtype(at::kFloat));
+  if (pad != rows) t.narrow(1, rows, pad - rows).zero_();
+  return t;
 }
 
-std::tuple<at::Tensor, at::Tensor, at::Tensor> resid_adaln_rotate_quant_mx(const at::Tensor& y, const at::Tensor& gate,
-                                                                           const at::Tensor& residual, const at::Tensor& scale,
-                                                                           const at::Tensor& shift, const std::array<uint32_t, 4>& sign_mask,
-                                                                           const c10::optional<at::Tensor>& smooth, double eps, bool kmajor,
-                                                                           bool inplace) {
-  const ProducerArgs a = producer_checks("resid_adaln_rotate_quant_mx", residual, &scale, &shift, smooth, 2560);
-  at::Tensor x_new = resid_checks("resid_adaln_rotate_quant_mx", y, gate, residual, a, inplace);
-  const int64_t rows = a.b * a.l;
-  at::Tensor codes = mx_codes_tensor(residual, rows, a.c, kmajor);
-  at::Tensor scales = mx_scales_tensor(residual, rows, a.c, kmajor);
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(residual.device());
-  check(fpq_resid_adaln_rotate_quant_rows_codes_mx(y.data_ptr(), gate.data_ptr(), x_new.data_ptr(), residual.data_ptr(),
-                                                   (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c,
-                                                   dtype_id(residual.scalar_type(), "resid_adaln_rotate_quant_mx"), scale.data_ptr(),
-                                                   shift.data_ptr(), dtype_id(scale.scalar_type(), "resid_adaln_rotate_quant_mx"), a.l,
-                                                   (float)eps, a.smooth, sign_mask.data(), kmajor ? 1 : 0, current_stream(residual)),
-        "fpq_resid_adaln_rotate_quant_rows_codes_mx");
-  return {x_new, codes, scales};
+// `what`: the public producer, for the messages.  x: the rows (RESID: the residual); y, gate: RESID only; scale, shift: not ROWS.
+// table_id, eps, kmajor, inplace: ignored by the forms without them.  Returns what the public function does: a tensor, or a tuple.
+py::object producer(const py::str& name, int64_t form, const at::Tensor& x, const c10::optional<at::Tensor>& y,
+                    const c10::optional<at::Tensor>& gate, const c10::optional<at::Tensor>& scale, const c10::optional<at::Tensor>& shift,
+                    int64_t table_id, const std::array<uint32_t, 4>& sign_mask, const c10::optional<at::Tensor>& smooth, double eps,
+                    bool kmajor, bool inplace) {
+  const char* what = PyUnicode_AsUTF8(name.ptr());   // the str's own buffer: nothing is copied on the hot call
+  if (!what) throw py::error_already_set();
+  TORCH_CHECK(form >= 0 && form < N_FORMS, what, " (native): no producer form ", form);
+  const ProducerForm& f = PRODUCER_FORMS[form];
+  TORCH_CHECK((scale.has_value() && shift.has_value()) == (f.front != ROWS) && (y.has_value() && gate.has_value()) == (f.front == RESID),
+              what, " (native): ", f.entry, " does not take these tensors");
+  TORCH_CHECK(!kmajor || f.entry_km || f.km_flag, what, ": ", f.entry, " writes no k-major image");
+  const ProducerArgs a = producer_checks(what, x, f.front != ROWS ? &*scale : nullptr, f.front != ROWS ? &*shift : nullptr, smooth, f.max_c);
+  TORCH_CHECK(form != TOKEN_FP6 || table_id == FPQ_E2M3, what, ": ", f.entry, " writes dense E2M3 codes");
+  TORCH_CHECK((form != TOKEN_F6 && form != RESID_TOKEN_F6) || table_id == FPQ_E2M3 || table_id == FPQ_E3M2, what,
+              ": dense 6-bit codes are E2M3 or E3M2");
+  at::Tensor x_new, o0, o1;
+  if (f.front == RESID) x_new = resid_checks(what, *y, *gate, x, a, inplace);
+  const int64_t rows = a.b * a.l, c = a.c;
+  if (f.out == VALUES) {
+    o0 = at::empty(x.sizes(), x.options().dtype(at::kHalf));
+  } else {
+    o0 = codes_tensor(x, rows, c, f.seg, kmajor);
+    o1 = f.out == ROW_CODES ? at::empty({rows}, x.options().dtype(at::kHalf)) : group_scales_tensor(x, rows, c, kmajor);
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  // the arguments the entry points share, in the order they take them
+  const void *xp = x.data_ptr(), *yp = nullptr, *gp = nullptr, *sc = nullptr, *sh = nullptr;
+  void *xn = nullptr, *out = o0.data_ptr(), *scales = f.out == VALUES ? nullptr : o1.data_ptr();
+  uint8_t* codes = (uint8_t*)out;
+  int md = 0;
+  if (f.front != ROWS) sc = scale->data_ptr(), sh = shift->data_ptr(), md = dtype_id(scale->scalar_type(), what);
+  if (f.front == RESID) yp = y->data_ptr(), gp = gate->data_ptr(), xn = x_new.data_ptr();
+  const int dt = dtype_id(x.scalar_type(), what), tid = (int)table_id, km = kmajor ? 1 : 0;
+  const int64_t l = a.l;
+  const float e = (float)eps, *sm = a.smooth;
+  const uint32_t* mk = sign_mask.data();
+  const fpq_stream_t st = current_stream(x);
+  int status = 0;
+  switch (form) {
+    case ROTATE: status = fpq_rotate_quant_rows(xp, out, nullptr, rows, c, dt, sm, mk, tid, st); break;
+    case ROTATE_MX: status = (kmajor ? fpq_rotate_quant_rows_codes_mx_km : fpq_rotate_quant_rows_codes_mx)(xp, codes, scales, rows, c, dt, sm, mk, st); break;
+    case ROTATE_G6: status = fpq_a6w4_rotate_quant_rows_codes(xp, codes, scales, rows, c, dt, sm, mk, tid, km, st); break;
+    case ROTATE_GF6: status = fpq_gf6_rotate_quant_rows_codes(xp, codes, scales, rows, c, dt, sm, mk, tid, km, st); break;
+    case ADALN_VALUES: status = fpq_adaln_rotate_quant_rows(xp, out, nullptr, nullptr, rows, c, dt, sc, sh, md, l, e, sm, mk, tid, st); break;
+    case ADALN_MX:
+      status = (kmajor ? fpq_adaln_rotate_quant_rows_codes_mx_km : fpq_adaln_rotate_quant_rows_codes_mx)(xp, codes, scales, rows, c, dt, sc, sh, md, l, e, sm, mk, st);
+      break;
+    case ADALN_G6: status = fpq_a6w4_adaln_rotate_quant_rows_codes(xp, codes, scales, rows, c, dt, sc, sh, md, l, e, sm, mk, tid, km, st); break;
+    case ADALN_GF6: status = fpq_gf6_adaln_rotate_quant_rows_codes(xp, codes, scales, rows, c, dt, sc, sh, md, l, e, sm, mk, tid, km, st); break;
+    case TOKEN: status = fpq_adaln_rotate_quant_token_rows(xp, out, nullptr, nullptr, nullptr, rows, c, dt, sc, sh, md, l, e, sm, mk, tid, st); break;
+    case TOKEN_FP8: status = fpq_adaln_rotate_quant_token_rows_codes_fp8(xp, codes, scales, rows, c, dt, sc, sh, md, l, e, sm, mk, tid, st); break;
+    case TOKEN_FP6:
+      status = (kmajor ? fpq_adaln_rotate_quant_token_rows_codes_fp6_km : fpq_adaln_rotate_quant_token_rows_codes_fp6)(
+          xp, codes, scales, rows, c, dt, sc, sh, md, l, e, sm, mk, tid, st);
+      break;
+    case TOKEN_F6: status = fpq_adaln_rotate_quant_token_rows_codes_f6(xp, codes, scales, rows, c, dt, sc, sh, md, l, e, sm, mk, tid, km, st); break;
+    case RESID_VALUES: status = fpq_resid_adaln_rotate_quant_rows(yp, gp, xn, xp, out, nullptr, nullptr, rows, c, dt, sc, sh, md, l, e, sm, mk, tid, st); break;
+    case RESID_MX: status = fpq_resid_adaln_rotate_quant_rows_codes_mx(yp, gp, xn, xp, codes, scales, rows, c, dt, sc, sh, md, l, e, sm, mk, km, st); break;
+    case RESID_TOKEN:
+      status = fpq_resid_adaln_rotate_quant_token_rows(yp, gp, xn, xp, out, nullptr, nullptr, nullptr, rows, c, dt, sc, sh, md, l, e, sm, mk, tid, st);
+      break;
+    case RESID_TOKEN_F6:
+      status = fpq_resid_adaln_rotate_quant_token_rows_codes_f6(yp, gp, xn, xp, codes, scales, rows, c, dt, sc, sh, md, l, e, sm, mk, tid, km, st);
+      break;
+  }
+  check(status, kmajor && f.entry_km ? f.entry_km : f.entry);
+  if (f.front == RESID) return f.out == VALUES ? py::make_tuple(x_new, o0) : py::make_tuple(x_new, o0, o1);
+  if (f.out == VALUES) return py::cast(o0);
+  return py::make_tuple(o0, o1);
 }
 
-std::tuple<at::Tensor, at::Tensor> resid_adaln_rotate_quant_token(const at::Tensor& y, const at::Tensor& gate, const at::Tensor& residual,
-                                                                  const at::Tensor& scale, const at::Tensor& shift, int64_t table_id,
-                                                                  const std::array<uint32_t, 4>& sign_mask,
-                                                                  const c10::optional<at::Tensor>& smooth, double eps, bool inplace) {
-  const ProducerArgs a = producer_checks("resid_adaln_rotate_quant_token", residual, &scale, &shift, smooth, 2560);
-  at::Tensor x_new = resid_checks("resid_adaln_rotate_quant_token", y, gate, residual, a, inplace);
-  at::Tensor out = at::empty(residual.sizes(), residual.options().dtype(at::kHalf));
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(residual.device());
-  check(fpq_resid_adaln_rotate_quant_token_rows(y.data_ptr(), gate.data_ptr(), x_new.data_ptr(), residual.data_ptr(), out.data_ptr(),
-                                                nullptr, nullptr, nullptr, a.b * a.l, a.c,
-                                                dtype_id(residual.scalar_type(), "resid_adaln_rotate_quant_token"), scale.data_ptr(),
-                                                shift.data_ptr(), dtype_id(scale.scalar_type(), "resid_adaln_rotate_quant_token"), a.l,
-                                                (float)eps, a.smooth, sign_mask.data(), (int)table_id, current_stream(residual)),
-        "fpq_resid_adaln_rotate_quant_token_rows");
-  return {x_new, out};
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor> resid_adaln_rotate_quant_token_codes_f6(
-    const at::Tensor& y, const at::Tensor& gate, const at::Tensor& residual, const at::Tensor& scale, const at::Tensor& shift,
-    int64_t table_id, const std::array<uint32_t, 4>& sign_mask, const c10::optional<at::Tensor>& smooth, double eps, bool kmajor,
-    bool inplace) {
-  const ProducerArgs a = producer_checks("resid_adaln_rotate_quant_token_codes_f6", residual, &scale, &shift, smooth, 2560);
-  TORCH_CHECK(table_id == FPQ_E2M3 || table_id == FPQ_E3M2, "resid_adaln_rotate_quant_token_codes_f6: dense 6-bit codes are E2M3 or E3M2");
-  at::Tensor x_new = resid_checks("resid_adaln_rotate_quant_token_codes_f6", y, gate, residual, a, inplace);
-  const int64_t rows = a.b * a.l;
-  at::Tensor codes = kmajor ? at::empty({a.c / 128, rows, 96}, residual.options().dtype(at::kByte))
-                            : at::empty({rows, a.c * 3 / 4}, residual.options().dtype(at::kByte));
-  at::Tensor scales = at::empty({rows}, residual.options().dtype(at::kHalf));
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(residual.device());
-  check(fpq_resid_adaln_rotate_quant_token_rows_codes_f6(
-            y.data_ptr(), gate.data_ptr(), x_new.data_ptr(), residual.data_ptr(), (uint8_t*)codes.data_ptr(), scales.data_ptr(), rows, a.c,
-            dtype_id(residual.scalar_type(), "resid_adaln_rotate_quant_token_codes_f6"), scale.data_ptr(), shift.data_ptr(),
-            dtype_id(scale.scalar_type(), "resid_adaln_rotate_quant_token_codes_f6"), a.l, (float)eps, a.smooth, sign_mask.data(),
-            (int)table_id, kmajor ? 1 : 0, current_stream(residual)),
-        "fpq_resid_adaln_rotate_quant_token_rows_codes_f6");
-  return {x_new, codes, scales};
+py::tuple producer_entry_points() {
+  py::tuple t((size_t)N_FORMS);
+  for (int i = 0; i < N_FORMS; ++i) t[i] = PRODUCER_FORMS[i].entry;
+  return t;
 }
 
 // one step of the incrementally kept KV cache (ops.kv_cache_step holds the argument checks' prose)
@@ -837,44 +682,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fp6_quant_e3m2_per_group_cuda", &fp6_quant_e3m2_per_group_cuda, py::arg("x"), py::arg("n_bits"), py::arg("group_size") = 128);
   m.def("fp6_quant_int_neg_e2m3_pos_per_group_cuda", &fp6_quant_int_neg_e2m3_pos_per_group_cuda, py::arg("x"), py::arg("n_bits"),
         py::arg("group_size") = 128);
-  m.def("rotate_quant", &rotate_quant, py::arg("x"), py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none());
-  m.def("adaln_rotate_quant", &adaln_rotate_quant, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("table_id"),
-        py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6);
-  m.def("rotate_quant_mx", &rotate_quant_mx, py::arg("x"), py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("kmajor") = false);
-  m.def("adaln_rotate_quant_mx", &adaln_rotate_quant_mx, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("sign_mask"),
-        py::arg("smooth") = py::none(), py::arg("eps") = 1e-6, py::arg("kmajor") = false);
-  m.def("rotate_quant_g6", &rotate_quant_g6, py::arg("x"), py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none(),
-        py::arg("kmajor") = false);
-  m.def("adaln_rotate_quant_g6", &adaln_rotate_quant_g6, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("table_id"),
-        py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6, py::arg("kmajor") = false);
-  m.def("rotate_quant_gf6", &rotate_quant_gf6, py::arg("x"), py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none(),
-        py::arg("kmajor") = false);
-  m.def("adaln_rotate_quant_gf6", &adaln_rotate_quant_gf6, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("table_id"),
-        py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6, py::arg("kmajor") = false);
-  m.def("adaln_rotate_quant_token", &adaln_rotate_quant_token, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("table_id"),
-        py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6);
-  m.def("adaln_rotate_quant_token_codes", &adaln_rotate_quant_token_codes, py::arg("x"), py::arg("scale"), py::arg("shift"),
-        py::arg("table_id"), py::arg("code_bits"), py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6,
-        py::arg("kmajor") = false);
-  m.def("adaln_rotate_quant_token_codes_f6", &adaln_rotate_quant_token_codes_f6, py::arg("x"), py::arg("scale"), py::arg("shift"),
-        py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6, py::arg("kmajor") = false);
-  m.def("kv_cache_step", &kv_cache_step, py::arg("cache"), py::arg("quant_start"), py::arg("quant_stop"), py::arg("k"), py::arg("v"),
+  m.def("producer", &producer, py::arg("what"), py::arg("form"), py::arg("x"), py::arg("y"), py::arg("gate"), py::arg("scale"),
+        py::arg("shift"), py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth"), py::arg("eps"), py::arg("kmajor"), py::arg("inplace"));
+  m.attr("PRODUCER_ENTRY_POINTS") = producer_entry_points();   // a form's number is the index of its C entry point here
+  m.def("kv_cache_step", &kv_cache_step,py::arg("cache"), py::arg("quant_start"), py::arg("quant_stop"), py::arg("k"), py::arg("v"),
         py::arg("new_start"), py::arg("group"), py::arg("table_id"));
   m.def("kv_cache_step_qk_norm", &kv_cache_step_qk_norm, py::arg("cache"), py::arg("quant_start"), py::arg("quant_stop"), py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("new_start"), py::arg("group"), py::arg("table_id"), py::arg("head_scale"),
         py::arg("bias") = py::none());
-  m.def("resid_adaln_rotate_quant", &resid_adaln_rotate_quant, py::arg("y"), py::arg("gate"), py::arg("residual"), py::arg("scale"),
-        py::arg("shift"), py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6,
-        py::arg("inplace") = false);
-  m.def("resid_adaln_rotate_quant_mx", &resid_adaln_rotate_quant_mx, py::arg("y"), py::arg("gate"), py::arg("residual"), py::arg("scale"),
-        py::arg("shift"), py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6, py::arg("kmajor") = false,
-        py::arg("inplace") = false);
-  m.def("resid_adaln_rotate_quant_token", &resid_adaln_rotate_quant_token, py::arg("y"), py::arg("gate"), py::arg("residual"),
-        py::arg("scale"), py::arg("shift"), py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none(), py::arg("eps") = 1e-6,
-        py::arg("inplace") = false);
-  m.def("resid_adaln_rotate_quant_token_codes_f6", &resid_adaln_rotate_quant_token_codes_f6, py::arg("y"), py::arg("gate"),
-        py::arg("residual"), py::arg("scale"), py::arg("shift"), py::arg("table_id"), py::arg("sign_mask"), py::arg("smooth") = py::none(),
-        py::arg("eps") = 1e-6, py::arg("kmajor") = false, py::arg("inplace") = false);
   m.def("linear_fp4", &linear_fp4, py::arg("a_codes"), py::arg("a_scales"), py::arg("w_codes"), py::arg("w_scales"),
         py::arg("bias") = py::none(), py::arg("gate") = py::none(), py::arg("residual") = py::none(), py::arg("outs") = py::none());
   m.def("linear_w6", &linear_w6, py::arg("a_codes"), py::arg("a_scales"), py::arg("a_table_id"), py::arg("w_codes"), py::arg("w_scales"),

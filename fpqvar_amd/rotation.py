@@ -10,11 +10,12 @@ tests; online, ``rotate_quant`` runs the 128-point transform on the matrix cores
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple, Union
 
 import torch
 
 from ._lib import TABLE_IDS, check, dtype_id, lib, require_gpu, stream_ptr, device_guard
+from .gemm import _g6_table, _gf6_table, kmajor_mx_scales
 
 
 def sign_vector(size: int = 128, seed: int = 42) -> torch.Tensor:
@@ -219,13 +220,6 @@ if __import__("os").environ.get("FPQ_NO_NATIVE") == "1":   # the A/B tools time 
     _native = None
 
 
-def _native_ok(x, d, smooth, c) -> bool:
-    """The compiled fast path takes the usual arguments only: default sign vector, contiguous x, float32 [C] smooth."""
-    return _native is not None and d is None and x.is_cuda and x.is_contiguous() and (
-        smooth is None or (smooth.dtype is torch.float32 and smooth.dim() == 1 and smooth.shape[0] == c and
-                           smooth.device == x.device and smooth.is_contiguous()))
-
-
 def _default_mask_tuple():
     global _DEFAULT_MASK_TUPLE
     if _DEFAULT_MASK_TUPLE is None:
@@ -242,32 +236,6 @@ def _mask_arg(d: Optional[torch.Tensor]):
             _DEFAULT_MASK = (ctypes.c_uint32 * 4)(*sign_mask(sign_vector(128, 42)))   # read-only to the library: shared
         return _DEFAULT_MASK
     return (ctypes.c_uint32 * 4)(*sign_mask(d.cpu()))
-
-
-def rotate_quant(x: torch.Tensor, table: str = "e2m1", d: Optional[torch.Tensor] = None,
-                 smooth: Optional[torch.Tensor] = None, return_rotated: bool = False):
-    """out = fp_quant_*_per_group_cuda( half(x*smooth) @ half(Q_block) , 128 ) in one launch.
-
-    x: [..., C] fp16 or fp32 on the GPU, C % 128 == 0.  Returns fp16 (and the rotated
-    fp16 tensor when return_rotated)."""
-    require_gpu(x, "rotate_quant")
-    if x.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError(f"rotate_quant: x must be float16 or float32, got {x.dtype}")
-    c = x.shape[-1]
-    if c % 128 != 0:
-        raise RuntimeError("rotate_quant: the last dimension must be a multiple of 128")
-    if not return_rotated and _native_ok(x, d, smooth, c):
-        return _native.rotate_quant(x, TABLE_IDS[table], _default_mask_tuple(), smooth)
-    mask = _mask_arg(d)
-    xc = x if x.is_contiguous() else x.contiguous()
-    sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
-    out = torch.empty(x.shape, dtype=torch.float16, device=x.device)
-    rot = torch.empty_like(out) if return_rotated else None
-    with device_guard(x.device):
-        check(lib().fpq_rotate_quant_rows(xc.data_ptr(), out.data_ptr(), rot.data_ptr() if rot is not None else None,
-                                          x.numel() // c, c, dtype_id(x.dtype), sm_ptr, mask, TABLE_IDS[table],
-                                          stream_ptr(x.device)), "fpq_rotate_quant_rows")
-    return (out, rot) if return_rotated else out
 
 
 def _mod_rows(t: torch.Tensor, bsz: int, c: int) -> torch.Tensor:
@@ -291,9 +259,144 @@ def _smooth_ptr(smooth, c, device):
     return sm, sm.data_ptr()
 
 
-def _kmajor_mx_scales(rows: int, c: int, device) -> torch.Tensor:
-    from .gemm import kmajor_mx_scales
-    return kmajor_mx_scales(rows, c, device)
+def _g6_table_id(name: str, table: str) -> int:
+    return TABLE_IDS[_g6_table(name, table)]
+
+
+def _gf6_table_id(name: str, table: str) -> int:
+    return TABLE_IDS[_gf6_table(name, table, full_only=True)]
+
+
+# ---- the row producers: rotate / adaLN + rotate / gated residual + adaLN + rotate, then the quantizer (include/fpq.h) -------------
+# One row per C entry point holds everything the host side knows about it.  The twelve public functions below are their own
+# signatures, docstrings and the refusals that are theirs alone (an emit, a table); behind them `_rotate`, `_adaln_args` and
+# `_resid_args` are the three sets of shared argument checks, `_outputs` the one place that shapes an output tensor and `_produce` the
+# one call path: the compiled binding for the usual arguments, else ctypes, ending in the one `check(lib().X(...), "X")`.  A new
+# operand format is a row (here and in csrc/quant_cuda_ext.cpp's PRODUCER_FORMS) and a public function of a few lines.  The hot call
+# is public function -> checks -> `_produce` -> binding: positional all the way, nothing built but the tuple the checks return.
+#
+# Every entry point takes (x | y, gate, x_out, residual), its `slots` output pointers, rows, C, x's dtype, (scale, shift, their
+# dtype, rows per batch, eps) behind an adaLN front, smooth, the sign mask, then what the row says: a table id, an `int kmajor`.
+class _Family(NamedTuple):
+    form: int                          # the entry point's number in the compiled binding (the index in _native.PRODUCER_ENTRY_POINTS)
+    entry: str                         # the C entry point
+    km: Union[None, str, bool] = None  # k-major images: None - not written; a name - by a twin entry point; True - an `int kmajor` argument
+    table: bool = True                 # a table id follows the sign mask ...
+    tables: Optional[Callable[[str, str], int]] = None   # ... of these only: (function, table) -> id or a refusal; None: any of TABLE_IDS
+    max_c: Optional[int] = None        # the width cap
+    seg: int = 0                       # bytes of codes per 128 elements (64 FP4 nibbles, 96 dense 6-bit codes, 128 E4M3 bytes); 0: fp16 values
+    row_scales: bool = False           # one fp16 scale per row, not one per 128 elements
+    slots: int = 2                     # output pointers: the outputs, then NULL for each intermediate that was not asked for
+
+
+_FORMS = tuple(_native.PRODUCER_ENTRY_POINTS) if _native is not None else ()
+
+
+def _family(entry: str, **kw) -> _Family:
+    return _Family(_FORMS.index(entry) if entry in _FORMS else -1, entry, **kw)
+
+
+_ROTATE = _family("fpq_rotate_quant_rows")
+_ROTATE_MX = _family("fpq_rotate_quant_rows_codes_mx", km="fpq_rotate_quant_rows_codes_mx_km", table=False, seg=64)
+_ROTATE_G6 = _family("fpq_a6w4_rotate_quant_rows_codes", km=True, tables=_g6_table_id, seg=96)
+_ROTATE_GF6 = _family("fpq_gf6_rotate_quant_rows_codes", km=True, tables=_gf6_table_id, seg=96)
+_ADALN = _family("fpq_adaln_rotate_quant_rows", max_c=4096, slots=3)
+_ADALN_MX = _family("fpq_adaln_rotate_quant_rows_codes_mx", km="fpq_adaln_rotate_quant_rows_codes_mx_km", table=False, max_c=4096, seg=64)
+_ADALN_G6 = _family("fpq_a6w4_adaln_rotate_quant_rows_codes", km=True, tables=_g6_table_id, max_c=2560, seg=96)
+_ADALN_GF6 = _family("fpq_gf6_adaln_rotate_quant_rows_codes", km=True, tables=_gf6_table_id, max_c=2560, seg=96)
+_TOKEN = {"values": _family("fpq_adaln_rotate_quant_token_rows", max_c=2560, slots=4),
+          "fp8": _family("fpq_adaln_rotate_quant_token_rows_codes_fp8", max_c=2560, seg=128, row_scales=True),
+          "fp6": _family("fpq_adaln_rotate_quant_token_rows_codes_fp6", km="fpq_adaln_rotate_quant_token_rows_codes_fp6_km", max_c=2560, seg=96,
+                         row_scales=True),
+          "bf6": _family("fpq_adaln_rotate_quant_token_rows_codes_f6", km=True, max_c=2560, seg=96, row_scales=True)}
+_RESID = _family("fpq_resid_adaln_rotate_quant_rows", max_c=2560, slots=3)
+_RESID_MX = _family("fpq_resid_adaln_rotate_quant_rows_codes_mx", km=True, table=False, max_c=2560, seg=64)
+_RESID_TOKEN = {"values": _family("fpq_resid_adaln_rotate_quant_token_rows", max_c=2560, slots=4),
+                "fp6": _family("fpq_resid_adaln_rotate_quant_token_rows_codes_f6", km=True, max_c=2560, seg=96, row_scales=True)}
+
+
+def _outputs(fam: _Family, x: torch.Tensor, rows: int, c: int, kmajor: bool, extra: int):
+    """What a producer writes: fp16 values of x's shape (and `extra` intermediates of that shape), or operand codes - row-major
+    [rows, C/128 * seg], k-major [C/128, rows, seg] - with their scales: fp16 per row; per group fp16 [rows, C/128] or the fp32 scale
+    image [C/128, rows rounded up to 4] with its padding zeroed."""
+    if not fam.seg:
+        out = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+        return [out] + [torch.empty_like(out) for _ in range(extra)] if extra else [out]
+    codes = torch.empty((c // 128, rows, fam.seg) if kmajor else (rows, c // 128 * fam.seg), dtype=torch.uint8, device=x.device)
+    if fam.row_scales:
+        return [codes, torch.empty((rows,), dtype=torch.float16, device=x.device)]
+    return [codes, kmajor_mx_scales(rows, c, x.device) if kmajor else torch.empty((rows, c // 128), dtype=torch.float16, device=x.device)]
+
+
+def _produce(name: str, fam: _Family, x: torch.Tensor, c: int, tid: int, d, smooth, kmajor=False, extra: int = 0, sc=None, sh=None,
+             seq: int = 0, eps: float = 0.0, y=None, gt=None, inplace: bool = False):
+    """The one call of a checked producer.  x: the rows (behind a gated residual: the residual); sc, sh: the modulation rows of an
+    adaLN front; y, gt: the gated residual's other two tensors.  The compiled binding takes the usual arguments - default sign
+    vector, contiguous x (and y), float32 [C] smooth, no intermediates - everything else goes through ctypes; both end in `fam.entry`.
+    Returns the outputs (behind a gated residual x_new first): one tensor as itself, more as a tuple."""
+    if _native is not None and d is None and not extra and x.is_cuda and x.is_contiguous() and (
+            smooth is None or (smooth.dtype is torch.float32 and smooth.dim() == 1 and smooth.shape[0] == c and
+                               smooth.device == x.device and smooth.is_contiguous())) and (
+            sc is None or (sc.device == x.device and sh.device == x.device)) and (y is None or y.is_contiguous()):
+        return _native.producer(name, fam.form, x, y, gt, sc, sh, tid, _DEFAULT_MASK_TUPLE or _default_mask_tuple(), smooth, float(eps),
+                                kmajor, inplace)
+    mask = _mask_arg(d)
+    xc = x if x.is_contiguous() else x.contiguous()
+    head, first = (xc.data_ptr(),), []
+    if y is not None:
+        yc = y if y.is_contiguous() else y.contiguous()
+        first = [xc if inplace else torch.empty_like(xc)]
+        head = (yc.data_ptr(), gt.data_ptr(), first[0].data_ptr(), xc.data_ptr())
+    sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
+    rows = x.numel() // c
+    outs = _outputs(fam, x, rows, c, kmajor, extra)
+    entry = fam.km if kmajor and isinstance(fam.km, str) else fam.entry
+    with device_guard(x.device):
+        check(getattr(lib(), entry)(
+            *head, *map(torch.Tensor.data_ptr, outs), *[None] * (fam.slots - len(outs)), rows, c, dtype_id(x.dtype),
+            *((sc.data_ptr(), sh.data_ptr(), dtype_id(sc.dtype), seq, float(eps)) if sc is not None else ()), sm_ptr, mask,
+            *((tid,) if fam.table else ()), *((1 if kmajor else 0,) if fam.km is True else ()), stream_ptr(x.device)), entry)
+    outs = first + outs
+    return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+def _rotate(name: str, fam: _Family, x: torch.Tensor, table, d, smooth, kmajor=False, extra: int = 0):
+    """The producers of plain rows, x [..., C]: their checks, then the call."""
+    require_gpu(x, name)
+    c = x.shape[-1]
+    if fam is _ROTATE:
+        if x.dtype not in (torch.float16, torch.float32):
+            raise RuntimeError(f"{name}: x must be float16 or float32, got {x.dtype}")
+        if c % 128 != 0:
+            raise RuntimeError(f"{name}: the last dimension must be a multiple of 128")
+    elif x.dtype not in (torch.float16, torch.float32) or c % 128 != 0:
+        raise RuntimeError(f"{name}: x must be float16/float32 with a last dimension that is a multiple of 128")
+    tid = fam.tables(name, table) if fam.tables else TABLE_IDS[table] if fam.table else 0
+    return _produce(name, fam, x, c, tid, d, smooth, kmajor, extra)
+
+
+def _adaln_args(name: str, fam: _Family, x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, table):
+    """The checks of the producers with an adaLN front, x [B, L, C]; returns (C, L, scale rows, shift rows, the table id where the
+    family takes few tables - it is refused here - or None)."""
+    require_gpu(x, name)
+    if x.dim() != 3:
+        raise RuntimeError(f"{name}: x must be [B, L, C]")
+    bsz, seq, c = x.shape
+    if c % 128 != 0 or c > fam.max_c:
+        raise RuntimeError(f"{name}: C must be a multiple of 128 and at most {fam.max_c}")
+    if scale.dtype != shift.dtype or scale.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError(f"{name}: scale and shift must both be float16 or both float32")
+    tid = fam.tables(name, table) if fam.tables else None
+    return c, seq, _mod_rows(scale, bsz, c), _mod_rows(shift, bsz, c), tid
+
+
+def rotate_quant(x: torch.Tensor, table: str = "e2m1", d: Optional[torch.Tensor] = None,
+                 smooth: Optional[torch.Tensor] = None, return_rotated: bool = False):
+    """out = fp_quant_*_per_group_cuda( half(x*smooth) @ half(Q_block) , 128 ) in one launch.
+
+    x: [..., C] fp16 or fp32 on the GPU, C % 128 == 0.  Returns fp16 (and the rotated
+    fp16 tensor when return_rotated)."""
+    return _rotate("rotate_quant", _ROTATE, x, table, d, smooth, extra=1 if return_rotated else 0)
 
 
 def rotate_quant_mx(x: torch.Tensor, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
@@ -301,23 +404,7 @@ def rotate_quant_mx(x: torch.Tensor, d: Optional[torch.Tensor] = None, smooth: O
     """rotate_quant(x, "e2m1") emitting the FP4 GEMM's operands instead of values:
     (codes uint8 [rows, C/2], scales fp16 [rows, C/128]); level(code) * scale == rotate_quant(x) bit for bit.
     kmajor: the activation side's k-major images (include/fpq.h) - codes [C/128, rows, 64], scales fp32 [C/128, rows rounded up to 4]."""
-    require_gpu(x, "rotate_quant_mx")
-    if x.dtype not in (torch.float16, torch.float32) or x.shape[-1] % 128 != 0:
-        raise RuntimeError("rotate_quant_mx: x must be float16/float32 with a last dimension that is a multiple of 128")
-    c = x.shape[-1]
-    rows = x.numel() // c
-    if _native_ok(x, d, smooth, c):
-        return _native.rotate_quant_mx(x, _default_mask_tuple(), smooth, kmajor)
-    mask = _mask_arg(d)
-    xc = x if x.is_contiguous() else x.contiguous()
-    sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
-    codes = torch.empty((c // 128, rows, 64) if kmajor else (rows, c // 2), dtype=torch.uint8, device=x.device)
-    scales = _kmajor_mx_scales(rows, c, x.device) if kmajor else torch.empty((rows, c // 128), dtype=torch.float16, device=x.device)
-    fn = lib().fpq_rotate_quant_rows_codes_mx_km if kmajor else lib().fpq_rotate_quant_rows_codes_mx
-    with device_guard(x.device):
-        check(fn(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c, dtype_id(x.dtype), sm_ptr, mask, stream_ptr(x.device)),
-              "fpq_rotate_quant_rows_codes_mx_km" if kmajor else "fpq_rotate_quant_rows_codes_mx")
-    return codes, scales
+    return _rotate("rotate_quant_mx", _ROTATE_MX, x, None, d, smooth, kmajor)
 
 
 def adaln_rotate_quant_mx(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, d: Optional[torch.Tensor] = None,
@@ -325,35 +412,9 @@ def adaln_rotate_quant_mx(x: torch.Tensor, scale: torch.Tensor, shift: torch.Ten
                           ) -> Tuple[torch.Tensor, torch.Tensor]:
     """adaln_rotate_quant(x, scale, shift, "e2m1") emitting (codes uint8 [B*L, C/2], scales fp16 [B*L, C/128]).
     kmajor (C <= 2560): the activation side's k-major images - codes [C/128, B*L, 64], scales fp32 [C/128, B*L rounded up to 4]."""
-    require_gpu(x, "adaln_rotate_quant_mx")
-    if x.dim() != 3:
-        raise RuntimeError("adaln_rotate_quant_mx: x must be [B, L, C]")
-    bsz, seq, c = x.shape
-    if c % 128 != 0 or c > 4096:
-        raise RuntimeError("adaln_rotate_quant_mx: C must be a multiple of 128 and at most 4096")
-    if scale.dtype != shift.dtype or scale.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError("adaln_rotate_quant_mx: scale and shift must both be float16 or both float32")
-    sc = _mod_rows(scale, bsz, c)
-    sh = _mod_rows(shift, bsz, c)
-    if sc.device == x.device and sh.device == x.device and _native_ok(x, d, smooth, c):
-        return _native.adaln_rotate_quant_mx(x, sc, sh, _default_mask_tuple(), smooth, float(eps), kmajor)
-    mask = _mask_arg(d)
-    xc = x if x.is_contiguous() else x.contiguous()
-    sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
-    codes = torch.empty((c // 128, bsz * seq, 64) if kmajor else (bsz * seq, c // 2), dtype=torch.uint8, device=x.device)
-    scales = (_kmajor_mx_scales(bsz * seq, c, x.device) if kmajor
-              else torch.empty((bsz * seq, c // 128), dtype=torch.float16, device=x.device))
-    fn = lib().fpq_adaln_rotate_quant_rows_codes_mx_km if kmajor else lib().fpq_adaln_rotate_quant_rows_codes_mx
-    with device_guard(x.device):
-        check(fn(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), bsz * seq, c, dtype_id(x.dtype), sc.data_ptr(),
-                 sh.data_ptr(), dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, stream_ptr(x.device)),
-              "fpq_adaln_rotate_quant_rows_codes_mx_km" if kmajor else "fpq_adaln_rotate_quant_rows_codes_mx")
-    return codes, scales
-
-
-def _g6_table_id(name: str, table: str) -> int:
-    from .gemm import _g6_table
-    return TABLE_IDS[_g6_table(name, table)]
+    name = "adaln_rotate_quant_mx"
+    c, seq, sc, sh, _ = _adaln_args(name, _ADALN_MX, x, scale, shift, None)
+    return _produce(name, _ADALN_MX, x, c, 0, d, smooth, kmajor, 0, sc, sh, seq, eps)
 
 
 def rotate_quant_g6(x: torch.Tensor, table: str = "e3m0", d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
@@ -362,24 +423,7 @@ def rotate_quant_g6(x: torch.Tensor, table: str = "e3m0", d: Optional[torch.Tens
     (dense 6-bit codes uint8 [rows, C * 3 / 4], scales fp16 [rows, C/128]) - byte for byte gemm.quantize_g6 of the rotated rows, so
     level(code) * scale == rotate_quant(x, table) bit for bit.
     kmajor: the activation side's k-major images (include/fpq.h) - codes [C/128, rows, 96], scales fp32 [C/128, rows rounded up to 4]."""
-    require_gpu(x, "rotate_quant_g6")
-    if x.dtype not in (torch.float16, torch.float32) or x.shape[-1] % 128 != 0:
-        raise RuntimeError("rotate_quant_g6: x must be float16/float32 with a last dimension that is a multiple of 128")
-    tid = _g6_table_id("rotate_quant_g6", table)
-    c = x.shape[-1]
-    rows = x.numel() // c
-    if _native_ok(x, d, smooth, c):
-        return _native.rotate_quant_g6(x, tid, _default_mask_tuple(), smooth, kmajor)
-    mask = _mask_arg(d)
-    xc = x if x.is_contiguous() else x.contiguous()
-    sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
-    codes = torch.empty((c // 128, rows, 96) if kmajor else (rows, c * 3 // 4), dtype=torch.uint8, device=x.device)
-    scales = _kmajor_mx_scales(rows, c, x.device) if kmajor else torch.empty((rows, c // 128), dtype=torch.float16, device=x.device)
-    with device_guard(x.device):
-        check(lib().fpq_a6w4_rotate_quant_rows_codes(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c, dtype_id(x.dtype),
-                                                     sm_ptr, mask, tid, 1 if kmajor else 0, stream_ptr(x.device)),
-              "fpq_a6w4_rotate_quant_rows_codes")
-    return codes, scales
+    return _rotate("rotate_quant_g6", _ROTATE_G6, x, table, d, smooth, kmajor)
 
 
 def adaln_rotate_quant_g6(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, table: str = "e3m0",
@@ -388,36 +432,9 @@ def adaln_rotate_quant_g6(x: torch.Tensor, scale: torch.Tensor, shift: torch.Ten
     """adaln_rotate_quant(x, scale, shift, table) for table "e1m2" / "e3m0" emitting the A6W4 GEMM's activation operands:
     (dense 6-bit codes uint8 [B*L, C * 3 / 4], scales fp16 [B*L, C/128]) - byte for byte gemm.quantize_g6 of the rotated rows.  C <= 2560.
     kmajor: the k-major images - codes [C/128, B*L, 96], scales fp32 [C/128, B*L rounded up to 4]."""
-    require_gpu(x, "adaln_rotate_quant_g6")
-    if x.dim() != 3:
-        raise RuntimeError("adaln_rotate_quant_g6: x must be [B, L, C]")
-    bsz, seq, c = x.shape
-    if c % 128 != 0 or c > 2560:
-        raise RuntimeError("adaln_rotate_quant_g6: C must be a multiple of 128 and at most 2560")
-    if scale.dtype != shift.dtype or scale.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError("adaln_rotate_quant_g6: scale and shift must both be float16 or both float32")
-    tid = _g6_table_id("adaln_rotate_quant_g6", table)
-    sc = _mod_rows(scale, bsz, c)
-    sh = _mod_rows(shift, bsz, c)
-    if sc.device == x.device and sh.device == x.device and _native_ok(x, d, smooth, c):
-        return _native.adaln_rotate_quant_g6(x, sc, sh, tid, _default_mask_tuple(), smooth, float(eps), kmajor)
-    mask = _mask_arg(d)
-    xc = x if x.is_contiguous() else x.contiguous()
-    sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
-    rows = bsz * seq
-    codes = torch.empty((c // 128, rows, 96) if kmajor else (rows, c * 3 // 4), dtype=torch.uint8, device=x.device)
-    scales = _kmajor_mx_scales(rows, c, x.device) if kmajor else torch.empty((rows, c // 128), dtype=torch.float16, device=x.device)
-    with device_guard(x.device):
-        check(lib().fpq_a6w4_adaln_rotate_quant_rows_codes(
-            xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c, dtype_id(x.dtype), sc.data_ptr(), sh.data_ptr(),
-            dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, tid, 1 if kmajor else 0, stream_ptr(x.device)),
-            "fpq_a6w4_adaln_rotate_quant_rows_codes")
-    return codes, scales
-
-
-def _gf6_table_id(name: str, table: str) -> int:
-    from .gemm import _gf6_table
-    return TABLE_IDS[_gf6_table(name, table, full_only=True)]
+    name = "adaln_rotate_quant_g6"
+    c, seq, sc, sh, tid = _adaln_args(name, _ADALN_G6, x, scale, shift, table)
+    return _produce(name, _ADALN_G6, x, c, tid, d, smooth, kmajor, 0, sc, sh, seq, eps)
 
 
 def rotate_quant_gf6(x: torch.Tensor, table: str = "e2m3", d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
@@ -426,24 +443,7 @@ def rotate_quant_gf6(x: torch.Tensor, table: str = "e2m3", d: Optional[torch.Ten
     of values: (dense 6-bit codes uint8 [rows, C * 3 / 4], scales fp16 [rows, C/128]) - byte for byte gemm.quantize_gf6 of the rotated
     rows, so level(code) * scale == rotate_quant(x, table) bit for bit.  The operands of gemm.linear_g6* / FP6GroupLinear.
     kmajor: the activation side's k-major images (include/fpq.h) - codes [C/128, rows, 96], scales fp32 [C/128, rows rounded up to 4]."""
-    require_gpu(x, "rotate_quant_gf6")
-    if x.dtype not in (torch.float16, torch.float32) or x.shape[-1] % 128 != 0:
-        raise RuntimeError("rotate_quant_gf6: x must be float16/float32 with a last dimension that is a multiple of 128")
-    tid = _gf6_table_id("rotate_quant_gf6", table)
-    c = x.shape[-1]
-    rows = x.numel() // c
-    if _native_ok(x, d, smooth, c):
-        return _native.rotate_quant_gf6(x, tid, _default_mask_tuple(), smooth, kmajor)
-    mask = _mask_arg(d)
-    xc = x if x.is_contiguous() else x.contiguous()
-    sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
-    codes = torch.empty((c // 128, rows, 96) if kmajor else (rows, c * 3 // 4), dtype=torch.uint8, device=x.device)
-    scales = _kmajor_mx_scales(rows, c, x.device) if kmajor else torch.empty((rows, c // 128), dtype=torch.float16, device=x.device)
-    with device_guard(x.device):
-        check(lib().fpq_gf6_rotate_quant_rows_codes(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c, dtype_id(x.dtype),
-                                                    sm_ptr, mask, tid, 1 if kmajor else 0, stream_ptr(x.device)),
-              "fpq_gf6_rotate_quant_rows_codes")
-    return codes, scales
+    return _rotate("rotate_quant_gf6", _ROTATE_GF6, x, table, d, smooth, kmajor)
 
 
 def adaln_rotate_quant_gf6(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, table: str = "e2m3",
@@ -452,31 +452,9 @@ def adaln_rotate_quant_gf6(x: torch.Tensor, scale: torch.Tensor, shift: torch.Te
     """adaln_rotate_quant(x, scale, shift, table) for the full FP6 tables "e2m3" / "e3m2" emitting per-group operands:
     (dense 6-bit codes uint8 [B*L, C * 3 / 4], scales fp16 [B*L, C/128]) - byte for byte gemm.quantize_gf6 of the rotated rows.  C <= 2560.
     kmajor: the k-major images - codes [C/128, B*L, 96], scales fp32 [C/128, B*L rounded up to 4]."""
-    require_gpu(x, "adaln_rotate_quant_gf6")
-    if x.dim() != 3:
-        raise RuntimeError("adaln_rotate_quant_gf6: x must be [B, L, C]")
-    bsz, seq, c = x.shape
-    if c % 128 != 0 or c > 2560:
-        raise RuntimeError("adaln_rotate_quant_gf6: C must be a multiple of 128 and at most 2560")
-    if scale.dtype != shift.dtype or scale.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError("adaln_rotate_quant_gf6: scale and shift must both be float16 or both float32")
-    tid = _gf6_table_id("adaln_rotate_quant_gf6", table)
-    sc = _mod_rows(scale, bsz, c)
-    sh = _mod_rows(shift, bsz, c)
-    if sc.device == x.device and sh.device == x.device and _native_ok(x, d, smooth, c):
-        return _native.adaln_rotate_quant_gf6(x, sc, sh, tid, _default_mask_tuple(), smooth, float(eps), kmajor)
-    mask = _mask_arg(d)
-    xc = x if x.is_contiguous() else x.contiguous()
-    sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
-    rows = bsz * seq
-    codes = torch.empty((c // 128, rows, 96) if kmajor else (rows, c * 3 // 4), dtype=torch.uint8, device=x.device)
-    scales = _kmajor_mx_scales(rows, c, x.device) if kmajor else torch.empty((rows, c // 128), dtype=torch.float16, device=x.device)
-    with device_guard(x.device):
-        check(lib().fpq_gf6_adaln_rotate_quant_rows_codes(
-            xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c, dtype_id(x.dtype), sc.data_ptr(), sh.data_ptr(),
-            dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, tid, 1 if kmajor else 0, stream_ptr(x.device)),
-            "fpq_gf6_adaln_rotate_quant_rows_codes")
-    return codes, scales
+    name = "adaln_rotate_quant_gf6"
+    c, seq, sc, sh, tid = _adaln_args(name, _ADALN_GF6, x, scale, shift, table)
+    return _produce(name, _ADALN_GF6, x, c, tid, d, smooth, kmajor, 0, sc, sh, seq, eps)
 
 
 def adaln_rotate_quant_token(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, table: str = "e2m3",
@@ -488,65 +466,17 @@ def adaln_rotate_quant_token(x: torch.Tensor, scale: torch.Tensor, shift: torch.
     (dense 6-bit codes uint8 [B*L, C * 3 / 4], scales) for gemm.linear_fp6; emit="bf6" (table e3m2 only): the same shapes with BF6
     E3M2 codes, for gemm.linear_fp6(..., a_table="e3m2").  C <= 2560.
     kmajor (emit="fp6" / "bf6" only): the codes as the activation side's k-major image [C/128, B*L, 96]."""
-    require_gpu(x, "adaln_rotate_quant_token")
-    if x.dim() != 3:
-        raise RuntimeError("adaln_rotate_quant_token: x must be [B, L, C]")
-    bsz, seq, c = x.shape
-    if c % 128 != 0 or c > 2560:
-        raise RuntimeError("adaln_rotate_quant_token: C must be a multiple of 128 and at most 2560")
-    if scale.dtype != shift.dtype or scale.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError("adaln_rotate_quant_token: scale and shift must both be float16 or both float32")
-    sc = _mod_rows(scale, bsz, c)
-    sh = _mod_rows(shift, bsz, c)
-    if emit not in ("values", "fp8", "fp6", "bf6"):
-        raise RuntimeError(f"adaln_rotate_quant_token: unknown emit {emit!r}")
+    name = "adaln_rotate_quant_token"
+    c, seq, sc, sh, _ = _adaln_args(name, _TOKEN["values"], x, scale, shift, table)
+    if emit not in _TOKEN:
+        raise RuntimeError(f"{name}: unknown emit {emit!r}")
     if emit == "fp6" and table != "e2m3":
-        raise RuntimeError("adaln_rotate_quant_token: emit='fp6' is the E2M3 operand format")
+        raise RuntimeError(f"{name}: emit='fp6' is the E2M3 operand format")
     if emit == "bf6" and table != "e3m2":
-        raise RuntimeError("adaln_rotate_quant_token: emit='bf6' is the E3M2 operand format")
+        raise RuntimeError(f"{name}: emit='bf6' is the E3M2 operand format")
     if kmajor and emit not in ("fp6", "bf6"):
-        raise RuntimeError("adaln_rotate_quant_token: kmajor is a layout of the FP6 operand codes (emit='fp6' / 'bf6')")
-    if sc.device == x.device and sh.device == x.device and _native_ok(x, d, smooth, c):
-        if emit == "bf6":
-            return _native.adaln_rotate_quant_token_codes_f6(x, sc, sh, TABLE_IDS[table], _default_mask_tuple(), smooth, float(eps), kmajor)
-        if emit == "values":
-            return _native.adaln_rotate_quant_token(x, sc, sh, TABLE_IDS[table], _default_mask_tuple(), smooth, float(eps))
-        return _native.adaln_rotate_quant_token_codes(x, sc, sh, TABLE_IDS[table], 8 if emit == "fp8" else 6, _default_mask_tuple(),
-                                                      smooth, float(eps), kmajor)
-    mask = _mask_arg(d)
-    xc = x if x.is_contiguous() else x.contiguous()
-    sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
-    rows = bsz * seq
-    with device_guard(x.device):
-        if emit == "bf6":
-            codes = torch.empty((c // 128, rows, 96) if kmajor else (rows, c * 3 // 4), dtype=torch.uint8, device=x.device)
-            scales = torch.empty((rows,), dtype=torch.float16, device=x.device)
-            check(lib().fpq_adaln_rotate_quant_token_rows_codes_f6(
-                xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c, dtype_id(x.dtype), sc.data_ptr(), sh.data_ptr(),
-                dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, TABLE_IDS[table], 1 if kmajor else 0, stream_ptr(x.device)),
-                "fpq_adaln_rotate_quant_token_rows_codes_f6")
-            return codes, scales
-        if emit in ("fp8", "fp6"):
-            if emit == "fp6" and table != "e2m3":
-                raise RuntimeError("adaln_rotate_quant_token: emit='fp6' is the E2M3 operand format")
-            codes = torch.empty((c // 128, rows, 96) if kmajor else (rows, c if emit == "fp8" else c * 3 // 4), dtype=torch.uint8,
-                                device=x.device)
-            scales = torch.empty((rows,), dtype=torch.float16, device=x.device)
-            fn = (lib().fpq_adaln_rotate_quant_token_rows_codes_fp8 if emit == "fp8"
-                  else lib().fpq_adaln_rotate_quant_token_rows_codes_fp6_km if kmajor
-                  else lib().fpq_adaln_rotate_quant_token_rows_codes_fp6)
-            check(fn(xc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c, dtype_id(x.dtype), sc.data_ptr(), sh.data_ptr(),
-                     dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, TABLE_IDS[table], stream_ptr(x.device)),
-                  "fpq_adaln_rotate_quant_token_rows_codes_" + emit)
-            return codes, scales
-        if emit != "values":
-            raise RuntimeError(f"adaln_rotate_quant_token: unknown emit {emit!r}")
-        out = torch.empty(x.shape, dtype=torch.float16, device=x.device)
-        check(lib().fpq_adaln_rotate_quant_token_rows(
-            xc.data_ptr(), out.data_ptr(), None, None, None, rows, c, dtype_id(x.dtype), sc.data_ptr(), sh.data_ptr(),
-            dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, TABLE_IDS[table], stream_ptr(x.device)),
-            "fpq_adaln_rotate_quant_token_rows")
-    return out
+        raise RuntimeError(f"{name}: kmajor is a layout of the FP6 operand codes (emit='fp6' / 'bf6')")
+    return _produce(name, _TOKEN[emit], x, c, TABLE_IDS[table], d, smooth, kmajor, 0, sc, sh, seq, eps)
 
 
 def adaln_rotate_quant(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, table: str = "e2m1",
@@ -557,31 +487,9 @@ def adaln_rotate_quant(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor
 
     x: [B, L, C] fp16/fp32 on the GPU; scale, shift: [B, 1, C] (or [B, C]), both fp16 or both fp32.
     Returns fp16 [B, L, C] (plus h and the rotated tensor when return_intermediates)."""
-    require_gpu(x, "adaln_rotate_quant")
-    if x.dim() != 3:
-        raise RuntimeError("adaln_rotate_quant: x must be [B, L, C]")
-    bsz, seq, c = x.shape
-    if c % 128 != 0 or c > 4096:
-        raise RuntimeError("adaln_rotate_quant: C must be a multiple of 128 and at most 4096")
-    if scale.dtype != shift.dtype or scale.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError("adaln_rotate_quant: scale and shift must both be float16 or both float32")
-    sc = _mod_rows(scale, bsz, c)
-    sh = _mod_rows(shift, bsz, c)
-    if not return_intermediates and sc.device == x.device and sh.device == x.device and _native_ok(x, d, smooth, c):
-        return _native.adaln_rotate_quant(x, sc, sh, TABLE_IDS[table], _default_mask_tuple(), smooth, float(eps))
-    mask = _mask_arg(d)
-    xc = x if x.is_contiguous() else x.contiguous()
-    sm, sm_ptr = _smooth_ptr(smooth, c, x.device)
-    out = torch.empty(x.shape, dtype=torch.float16, device=x.device)
-    h = torch.empty_like(out) if return_intermediates else None
-    y = torch.empty_like(out) if return_intermediates else None
-    with device_guard(x.device):
-        check(lib().fpq_adaln_rotate_quant_rows(
-            xc.data_ptr(), out.data_ptr(), h.data_ptr() if h is not None else None,
-            y.data_ptr() if y is not None else None, bsz * seq, c, dtype_id(x.dtype), sc.data_ptr(), sh.data_ptr(),
-            dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, TABLE_IDS[table], stream_ptr(x.device)),
-            "fpq_adaln_rotate_quant_rows")
-    return (out, h, y) if return_intermediates else out
+    name = "adaln_rotate_quant"
+    c, seq, sc, sh, _ = _adaln_args(name, _ADALN, x, scale, shift, table)
+    return _produce(name, _ADALN, x, c, TABLE_IDS[table], d, smooth, False, 2 if return_intermediates else 0, sc, sh, seq, eps)
 
 
 # ---- the same producers with the gated residual in front of them folded in (include/fpq.h, fpq_resid_adaln_*) ----
@@ -590,7 +498,7 @@ def adaln_rotate_quant(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor
 
 def _resid_args(name: str, y: torch.Tensor, gate: torch.Tensor, residual: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
                 inplace: bool):
-    """The checks the three functions share; returns (B, L, C, gate rows, scale rows, shift rows)."""
+    """The checks the three functions share; returns (C, L, gate rows, scale rows, shift rows)."""
     require_gpu(residual, name)
     if residual.dim() != 3:
         raise RuntimeError(f"{name}: residual must be [B, L, C]")
@@ -617,11 +525,7 @@ def _resid_args(name: str, y: torch.Tensor, gate: torch.Tensor, residual: torch.
         y0, r0 = y.data_ptr(), residual.data_ptr()
         if y0 < r0 + residual.numel() * residual.element_size() and r0 < y0 + y.numel() * y.element_size():
             raise RuntimeError(f"{name}: inplace=True writes x_new over residual, which must not overlap y")
-    return bsz, seq, c, _mod_rows(gate, bsz, c), _mod_rows(scale, bsz, c), _mod_rows(shift, bsz, c)
-
-
-def _resid_native_ok(y, residual, sc, sh, d, smooth, c) -> bool:
-    return (y.is_contiguous() and sc.device == residual.device and sh.device == residual.device and _native_ok(residual, d, smooth, c))
+    return c, seq, _mod_rows(gate, bsz, c), _mod_rows(scale, bsz, c), _mod_rows(shift, bsz, c)
 
 
 def resid_adaln_rotate_quant(y: torch.Tensor, gate: torch.Tensor, residual: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
@@ -632,24 +536,9 @@ def resid_adaln_rotate_quant(y: torch.Tensor, gate: torch.Tensor, residual: torc
     y: [B, L, C] fp16; gate: [B, 1, C] (or [B, C]) fp16; residual: [B, L, C] fp16 or fp32, C <= 2560.  Returns (x_new, out), or
     (x_new, out, h, rotated) with return_intermediates.  inplace: x_new is written over residual (and is that tensor)."""
     name = "resid_adaln_rotate_quant"
-    bsz, seq, c, gt, sc, sh = _resid_args(name, y, gate, residual, scale, shift, inplace)
-    if not return_intermediates and _resid_native_ok(y, residual, sc, sh, d, smooth, c):
-        return _native.resid_adaln_rotate_quant(y, gt, residual, sc, sh, TABLE_IDS[table], _default_mask_tuple(), smooth, float(eps), inplace)
-    mask = _mask_arg(d)
-    rc = residual if residual.is_contiguous() else residual.contiguous()
-    yc = y if y.is_contiguous() else y.contiguous()
-    sm, sm_ptr = _smooth_ptr(smooth, c, residual.device)
-    x_new = rc if inplace else torch.empty_like(rc)
-    out = torch.empty(residual.shape, dtype=torch.float16, device=residual.device)
-    h = torch.empty_like(out) if return_intermediates else None
-    rot = torch.empty_like(out) if return_intermediates else None
-    with device_guard(residual.device):
-        check(lib().fpq_resid_adaln_rotate_quant_rows(
-            yc.data_ptr(), gt.data_ptr(), x_new.data_ptr(), rc.data_ptr(), out.data_ptr(), h.data_ptr() if h is not None else None,
-            rot.data_ptr() if rot is not None else None, bsz * seq, c, dtype_id(residual.dtype), sc.data_ptr(), sh.data_ptr(),
-            dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, TABLE_IDS[table], stream_ptr(residual.device)),
-            "fpq_resid_adaln_rotate_quant_rows")
-    return (x_new, out, h, rot) if return_intermediates else (x_new, out)
+    c, seq, gt, sc, sh = _resid_args(name, y, gate, residual, scale, shift, inplace)
+    return _produce(name, _RESID, residual, c, TABLE_IDS[table], d, smooth, False, 2 if return_intermediates else 0, sc, sh, seq, eps,
+                    y, gt, inplace)
 
 
 def resid_adaln_rotate_quant_mx(y: torch.Tensor, gate: torch.Tensor, residual: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
@@ -658,24 +547,8 @@ def resid_adaln_rotate_quant_mx(y: torch.Tensor, gate: torch.Tensor, residual: t
     """x_new = residual + y.mul(gate); adaln_rotate_quant_mx(x_new, scale, shift, ...) - one launch.  Returns (x_new, codes, scales) in
     the twin's shapes (kmajor: the k-major images).  C <= 2560.  inplace: x_new is written over residual."""
     name = "resid_adaln_rotate_quant_mx"
-    bsz, seq, c, gt, sc, sh = _resid_args(name, y, gate, residual, scale, shift, inplace)
-    if _resid_native_ok(y, residual, sc, sh, d, smooth, c):
-        return _native.resid_adaln_rotate_quant_mx(y, gt, residual, sc, sh, _default_mask_tuple(), smooth, float(eps), kmajor, inplace)
-    mask = _mask_arg(d)
-    rc = residual if residual.is_contiguous() else residual.contiguous()
-    yc = y if y.is_contiguous() else y.contiguous()
-    sm, sm_ptr = _smooth_ptr(smooth, c, residual.device)
-    x_new = rc if inplace else torch.empty_like(rc)
-    rows = bsz * seq
-    codes = torch.empty((c // 128, rows, 64) if kmajor else (rows, c // 2), dtype=torch.uint8, device=residual.device)
-    scales = (_kmajor_mx_scales(rows, c, residual.device) if kmajor
-              else torch.empty((rows, c // 128), dtype=torch.float16, device=residual.device))
-    with device_guard(residual.device):
-        check(lib().fpq_resid_adaln_rotate_quant_rows_codes_mx(
-            yc.data_ptr(), gt.data_ptr(), x_new.data_ptr(), rc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c,
-            dtype_id(residual.dtype), sc.data_ptr(), sh.data_ptr(), dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask,
-            1 if kmajor else 0, stream_ptr(residual.device)), "fpq_resid_adaln_rotate_quant_rows_codes_mx")
-    return x_new, codes, scales
+    c, seq, gt, sc, sh = _resid_args(name, y, gate, residual, scale, shift, inplace)
+    return _produce(name, _RESID_MX, residual, c, 0, d, smooth, kmajor, 0, sc, sh, seq, eps, y, gt, inplace)
 
 
 def resid_adaln_rotate_quant_token(y: torch.Tensor, gate: torch.Tensor, residual: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
@@ -685,37 +558,12 @@ def resid_adaln_rotate_quant_token(y: torch.Tensor, gate: torch.Tensor, residual
     emit="values": (x_new, fp16 [B, L, C]); emit="fp6": (x_new, dense 6-bit codes, row scales) in the format of `table` ("e2m3": FP6,
     "e3m2": BF6), row-major or (kmajor) the activation side's k-major image.  The FP8 form has no fused twin.  C <= 2560."""
     name = "resid_adaln_rotate_quant_token"
-    bsz, seq, c, gt, sc, sh = _resid_args(name, y, gate, residual, scale, shift, inplace)
-    if emit not in ("values", "fp6"):
+    c, seq, gt, sc, sh = _resid_args(name, y, gate, residual, scale, shift, inplace)
+    if emit not in _RESID_TOKEN:
         raise RuntimeError(f"{name}: emit must be 'values' or 'fp6', got {emit!r}")
     if emit == "fp6" and table not in ("e2m3", "e3m2"):
         raise RuntimeError(f"{name}: emit='fp6' writes E2M3 or E3M2 codes, got table {table!r}")
     if kmajor and emit != "fp6":
         raise RuntimeError(f"{name}: kmajor is a layout of the 6-bit operand codes (emit='fp6')")
-    if _resid_native_ok(y, residual, sc, sh, d, smooth, c):
-        if emit == "values":
-            return _native.resid_adaln_rotate_quant_token(y, gt, residual, sc, sh, TABLE_IDS[table], _default_mask_tuple(), smooth,
-                                                          float(eps), inplace)
-        return _native.resid_adaln_rotate_quant_token_codes_f6(y, gt, residual, sc, sh, TABLE_IDS[table], _default_mask_tuple(), smooth,
-                                                               float(eps), kmajor, inplace)
-    mask = _mask_arg(d)
-    rc = residual if residual.is_contiguous() else residual.contiguous()
-    yc = y if y.is_contiguous() else y.contiguous()
-    sm, sm_ptr = _smooth_ptr(smooth, c, residual.device)
-    x_new = rc if inplace else torch.empty_like(rc)
-    rows = bsz * seq
-    with device_guard(residual.device):
-        if emit == "fp6":
-            codes = torch.empty((c // 128, rows, 96) if kmajor else (rows, c * 3 // 4), dtype=torch.uint8, device=residual.device)
-            scales = torch.empty((rows,), dtype=torch.float16, device=residual.device)
-            check(lib().fpq_resid_adaln_rotate_quant_token_rows_codes_f6(
-                yc.data_ptr(), gt.data_ptr(), x_new.data_ptr(), rc.data_ptr(), codes.data_ptr(), scales.data_ptr(), rows, c,
-                dtype_id(residual.dtype), sc.data_ptr(), sh.data_ptr(), dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask,
-                TABLE_IDS[table], 1 if kmajor else 0, stream_ptr(residual.device)), "fpq_resid_adaln_rotate_quant_token_rows_codes_f6")
-            return x_new, codes, scales
-        out = torch.empty(residual.shape, dtype=torch.float16, device=residual.device)
-        check(lib().fpq_resid_adaln_rotate_quant_token_rows(
-            yc.data_ptr(), gt.data_ptr(), x_new.data_ptr(), rc.data_ptr(), out.data_ptr(), None, None, None, rows, c,
-            dtype_id(residual.dtype), sc.data_ptr(), sh.data_ptr(), dtype_id(sc.dtype), seq, float(eps), sm_ptr, mask, TABLE_IDS[table],
-            stream_ptr(residual.device)), "fpq_resid_adaln_rotate_quant_token_rows")
-    return x_new, out
+    return _produce(name, _RESID_TOKEN[emit], residual, c, TABLE_IDS[table], d, smooth, kmajor, 0, sc, sh, seq, eps, y, gt, inplace)
+

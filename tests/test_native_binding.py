@@ -30,9 +30,12 @@ def test_native_module_is_built_and_bound():
     assert quant_cuda.fp6_quant_int_neg_e2m3_pos_per_group_cuda is _native.fp6_quant_int_neg_e2m3_pos_per_group_cuda
     for n in quant_cuda.FP_QUANT_NAMES:
         assert getattr(quant_cuda, n) is getattr(qu, n), n
-    for n in ("rotate_quant_mx", "adaln_rotate_quant_mx", "adaln_rotate_quant_token", "adaln_rotate_quant_token_codes",
-              "kv_cache_step", "linear_fp4"):
+    for n in ("producer", "kv_cache_step", "linear_fp4"):
         assert callable(getattr(_native, n)), n
+    # the one body behind rotation.py's producers names a C entry point per form, the four this test used to look up by function among them
+    for n in ("fpq_rotate_quant_rows_codes_mx", "fpq_adaln_rotate_quant_rows_codes_mx", "fpq_adaln_rotate_quant_token_rows",
+              "fpq_adaln_rotate_quant_token_rows_codes_fp8", "fpq_adaln_rotate_quant_token_rows_codes_fp6"):
+        assert n in _native.PRODUCER_ENTRY_POINTS, n
     assert qu.fp_quant_e2_per_group_cuda is _native.fp_quant_e2_per_group_cuda
     assert qu.fp_quant_e1m2_neg_e2m1_pos_per_group_cuda is _native.fp_quant_e1m2_neg_e2m1_pos_per_group_cuda
     # no CPU path in the compiled module either
