@@ -56,6 +56,11 @@ struct GemmEpi {
 typedef _Float16 fpq_h2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 fpq_h4_t __attribute__((ext_vector_type(4)));
 
+// b4: the lane's fp16 bias (bias_h, FPQ_GEMM_LANE_BIAS) widened where the register epilogues and the fc1 tail add it
+#define FPQ_GEMM_BIAS_F32()                                                                                         \
+  v4f_t b4 = v4f_t{0, 0, 0, 0};                                                                                     \
+  _Pragma("unroll") for (int n = 0; n < NT; ++n) b4[n] = (float)bias_h[n]
+
 // The four 8-byte stores of a lane (rows t_first .. +3, outputs o .. o+3)
 #define FPQ_GEMM_ROWS_STORE(y_, t_first_, tc_, o_, oc_)                                                             \
   do {                                                                                                              \
@@ -487,7 +492,7 @@ FPQ_NOPK __device__ __forceinline__ uint32_t quant_pair16_dual(uint32_t wk, cons
 // THE fc1 tail (see the comment above GemmFc1) of the register epilogues with 128-wide tiles - gemm_fp4_glds_kernel<.., GemmFc1>,
 // gemm_a6w4_fc1_kernel - written once; it ends the kernel (every store is in it).  Row r of the tile = wm * WROWS + m * 16 +
 // 4 * (lane >> 4) + i.  STAGE_: the bytes of one stage buffer of the kernel's two-stage ring; the exchange and the row scales go
-// into buffer (G & 1), the one the last K group does not read.  Names from the kernel: smem, G, BM, MT, NT, WROWS, acc, b4, xe
+// into buffer (G & 1), the one the last K group does not read.  Names from the kernel: smem, G, BM, MT, NT, WROWS, acc, bias_h, xe
 // (GemmFc1), lut (the staged bucket table), t0, wm, wn, lane, tid, T, O, o, oc, out.
 //   * The two maxima of a row travel as ONE packed key, both halves compared unsigned: low half = the unsigned maximum of the fp16
 //     patterns (the most negative value, or a negative NaN), high half = their signed maximum with the sign bit flipped (the
@@ -505,6 +510,7 @@ FPQ_NOPK __device__ __forceinline__ uint32_t quant_pair16_dual(uint32_t wk, cons
 #define FPQ_GEMM_FC1_TAIL(STAGE_) FPQ_GEMM_FC1_TAIL_X(STAGE_, false)
 #define FPQ_GEMM_FC1_TAIL_X(STAGE_, NANX_)                                                                          \
   do {                                                                                                              \
+    FPQ_GEMM_BIAS_F32();                                                                                            \
     uint32_t* xch = (uint32_t*)(smem + (G & 1) * (STAGE_));  /* [2 (wn)][BM]: packed (max|h| over h < 0) | (max h over h > 0) << 16 */ \
     u32x4* rsc = (u32x4*)(xch + 2 * BM);                     /* [BM]: {1 / s_neg, 1 / s_pos, s_neg x 2, s_pos x 2} */ \
     static_assert(2 * BM * 4 + BM * 16 <= (STAGE_), "exchange + row scales fit the idle stage buffer");             \
@@ -568,6 +574,246 @@ FPQ_NOPK __device__ __forceinline__ uint32_t quant_pair16_dual(uint32_t wk, cons
     }                                                                                                               \
   } while (0)
 
+// ---------------------------------------------------------------------------------------------------
+// THE STAGES OF THE PER-GROUP(128) LDS-DMA KERNELS - gemm_fp4_glds_kernel and gemm_fp4_ring_kernel below, and the text of the
+// kernels with a 6-bit side (fpq_gemm_g6_kernel.h) - written once.  Macros, like the tails above: a body shared through an
+// inlined function has twice come out as other machine code (the note at FPQ_QK_NORM_ROW, profiles/r08_bf6_isa.txt); as macros
+// every kernel is, instruction for instruction, what its own copy of these lines gave (profiles/gemm_shared_stages_isa.txt).
+// What a kernel keeps: its template head, name and launch bounds, the LDS-DMA lane offsets and the issue of a stage, the
+// staging schedule (two stages or the ring), the row-major scale tiles with their visible wait, and the call of the fc1 tail.
+
+// The tile walk (the row-scaled FP6 / FP8 kernels walk the same way): lane, wavefront (uniform, in a scalar register) and its
+// place wm x wn among the 2 x 2 of the workgroup, then the XCD-aware tile order - workgroups are dealt round-robin over the 8
+// XCDs, each with its own 4 MiB L2: XCD k owns a contiguous band of `cpx` column tiles and walks all row tiles of that band, so
+// its slice of W stays L2-resident and an A tile is re-used by cpx consecutive workgroups.  Defines tid, lane, wave, wm, wn, t0, o0.
+#define FPQ_GEMM_TILE_WALK(BM_, BN_)                                                                                \
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);                    \
+  const int wm = wave >> 1, wn = wave & 1;                                                                          \
+  const int n_col = (O + (BN_) - 1) / (BN_), n_row = (T + (BM_) - 1) / (BM_);                                       \
+  const int cpx = (n_col + 7) >> 3;                                                                                 \
+  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;                                                          \
+  const int col_blk = xcd * cpx + local % cpx, row_blk = local / cpx;                                               \
+  if (col_blk >= n_col || row_blk >= n_row) return;   /* uniform over the workgroup */                              \
+  const int t0 = row_blk * (BM_), o0 = col_blk * (BN_)
+
+// One LDS-DMA instruction: 64 lanes x 16 bytes from (uniform 64-bit base_ + the lane's 32-bit voff_) to the 1 KiB at lds_.
+// Spelled in assembly - the compiler folds base + offset into a loop-invariant per-lane pointer and adds a group's step to each
+// with a 64-bit vector addition - and WITHOUT a memory clobber (with one, -4 % instead of +3 %: it pins every LDS read of the
+// group behind it; the loads write the stage nobody reads, and the barriers order them).  The compiler does not see these loads:
+// the wait for them is spelled out in front of the barrier that hands a stage to its readers, FPQ_GLDS_WAIT (vmcnt(0); the ring
+// counts, glds_wait_vm).
+#define FPQ_GLDS_LOAD(voff_, base_, lds_)                                                                           \
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                                     \
+               :                                                                                                    \
+               : "v"(voff_), "s"(base_), "s"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(lds_)) \
+               : "m0")
+#define FPQ_GLDS_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+
+// K-MAJOR SCALE IMAGES (include/fpq.h) -> the scale tiles: sa_ / sw_ are fp32 planes [G][rows rounded up to 4] (activations) and
+// [G][km_w_rows] (weights, natural output order) - the tile's scales of a group are 4 BM (4 BN) contiguous bytes, exactly one
+// row of lsa (lsw): they come in by LDS-DMA like the codes, 256 / BM groups per 1 KiB activation piece and two per weight piece,
+// no register round trip, no conversion, no ds_write.  (Row-major fp16 / fp32 scales cost 90 strided load instructions + as many
+// LDS writes per tile: 8 % of the kernel, profiles/r05_kmajor_ab.txt.)  Pieces dealt round-robin over the four wavefronts; a last
+// piece's surplus groups re-read the last one (their LDS rows are the padding up to Gp); rows clamped to the image's last four.
+// A wavefront has 0 .. n of these pieces, so they cannot be counted: they are requested in front of every stage, and the main
+// loop's first wait covers them - the compiler has issued no load of its own that it would have to wait for.
+// Names from the kernel: BM, BN, G, T, t0, o0, lane, wave, epi, lsa, lsw.
+#define FPQ_GEMM_KM_SCALE_TILES(sa_, sw_)                                                                           \
+  do {                                                                                                              \
+    constexpr int APG = 256 / BM, LPG_A = BM / 4;          /* groups per piece, lanes per group (activation side) */ \
+    const int Tpad = (T + 3) & ~3, n_a = (G + APG - 1) / APG, n_w = (G + 1) >> 1;                                   \
+    const float* sa_km = (const float*)(sa_);                                                                       \
+    const float* sw_km = (const float*)(sw_);                                                                       \
+    for (int p = wave; p < n_a + n_w; p += 4) {                                                                     \
+      const bool is_a = p < n_a;                                                                                    \
+      const int g0 = is_a ? p * APG : (p - n_a) * 2;                                                                \
+      const int sub = is_a ? lane / LPG_A : lane >> 5, l4 = is_a ? lane % LPG_A : lane & 31;                        \
+      const int grp = g0 + sub < G ? g0 + sub : G - 1;                                                              \
+      const int rows = is_a ? Tpad : epi.km_w_rows, r0 = is_a ? t0 : o0;                                            \
+      int r4 = r0 + 4 * l4;                                                                                         \
+      r4 = r4 < rows - 4 ? r4 : rows - 4;                                                                           \
+      const uint32_t vo = (uint32_t)(((grp - g0) * rows + (r4 - r0)) * 4);                                          \
+      const float* sbase = (is_a ? sa_km : sw_km) + ((int64_t)g0 * rows + r0);                                      \
+      FPQ_GLDS_LOAD(vo, sbase, is_a ? lsa + g0 * BM : lsw + g0 * BN);                                               \
+    }                                                                                                               \
+  } while (0)
+
+// What a lane's epilogue reads from memory, requested in the prologue and not between the last MFMA and the stores: the fp16
+// bias of its four consecutive outputs o .. o + 3 (see the dealt weight rows; oc = o clamped into the tensor) and, QKN_, the q / k
+// norm's fp32 bias and s_h of its head in part 0 (qkn_bias_, qkn_scale_: GemmQkNorm's fields).  Defines WROWS, WCOLS, o, oc,
+// bias_h, qkn_b, qkn_s.
+#define FPQ_GEMM_LANE_BIAS(QKN_, qkn_bias_, qkn_scale_)                                                             \
+  constexpr int WROWS = 16 * MT, WCOLS = 16 * NT;                                                                   \
+  const int o = o0 + wn * WCOLS + NT * (lane & 15);                                                                 \
+  const int oc = o < O ? o : O - 4;                                                                                 \
+  fpq_h4_t bias_h = fpq_h4_t{0, 0, 0, 0};                                                                           \
+  if (bias) bias_h = *(const fpq_h4_t*)(bias + oc);                                                                 \
+  v4f_t qkn_b = v4f_t{0, 0, 0, 0};                                                                                  \
+  float qkn_s = 1.0f;                                                                                               \
+  if constexpr (QKN_) {                                                                                             \
+    if (qkn_bias_) qkn_b = *(const v4f_t*)((qkn_bias_) + oc);                                                       \
+    if (o0 < epi.sp_cols) qkn_s = (qkn_scale_)[oc >> 6];                                                            \
+  }
+
+// a nibble fragment (32 consecutive k of one row): one ds_read_b128 at p_, the upper half of the MFMA operand unused
+#define FPQ_GEMM_READ_NIB(dst_, p_)                                                                                 \
+  do {                                                                                                              \
+    const u32x4 q_ = *(const u32x4*)(p_);                                                                           \
+    dst_ = v8i_t{(int)q_[0], (int)q_[1], (int)q_[2], (int)q_[3], 0, 0, 0, 0};                                       \
+  } while (0)
+
+// K group g_ from the stage at st_: acc[m][n] += (d * sa) * sw over the wavefront's MT x NT tiles, d = one MFMA of 128 k.
+// READ_A_ / READ_B_ (dst, stage, byte offset of the 16-row tile in the wavefront's part of the stage) read a side's fragment -
+// the kernel's own: FPQ_GEMM_READ_NIB or three ds_read_b64 of 6-bit codes, and the ORDER in which the stage, the tile's offset
+// and the lane's are added, which the machine code follows (profiles/gemm_shared_stages_isa.txt); A_TILE_ / W_TILE_ are the
+// bytes from tile to tile; FA_ / FW_ the MFMA's format selectors (cbsz decodes the activation fragment, blgp the weight
+// fragment); literal zero scale operands select the unscaled instruction (x 1.0; tools/probe/mfma_fp4_probe.hip).
+// Names from the kernel: MT, NT, BM, BN, lsa, lsw, sa_off, sw_off, acc.
+// Software pipeline over the tile rows: the ds_reads of row m+1 are issued first, then the NT MFMAs of row m, then the
+// scale-and-accumulate of row m-1 - VALU work that does not depend on the MFMAs in flight, so no hazard wait states are needed
+// and 8 of each MFMA's 16 cycles of vector issue are hidden behind it.  (Left to itself the compiler issues each row's reads
+// right before their use and the VALU right behind its own MFMAs, with s_nops in between.)  Issue order inside a row: one MFMA,
+// then the 8 VALU ops of one finished tile, NT times - an in-order wavefront that issues its MFMAs back to back just waits for
+// the matrix pipe with its VALU idle.
+#define FPQ_GEMM_GROUP(g_, st_, READ_A_, READ_B_, A_TILE_, W_TILE_, FA_, FW_)                                       \
+  do {                                                                                                              \
+    v8i_t bf[NT];                                                                                                   \
+    _Pragma("unroll") for (int n = 0; n < NT; ++n) READ_B_(bf[n], st_, n * (W_TILE_));                              \
+    const v4f_t sw1 = *(const v4f_t*)(lsw + (g_) * BN + sw_off);                                                    \
+    v8i_t af;                                                                                                       \
+    READ_A_(af, st_, 0);                                                                                            \
+    v4f_t sa4 = *(const v4f_t*)(lsa + (g_) * BM + sa_off);                                                          \
+    v4f_t d_prev[NT], sa4_prev = sa4;                                                                               \
+    _Pragma("unroll") for (int n = 0; n < NT; ++n) d_prev[n] = v4f_t{0, 0, 0, 0};                                   \
+    _Pragma("unroll") for (int m = 0; m <= MT; ++m) {                                                               \
+      v8i_t af_n = af;                                                                                              \
+      v4f_t sa4_n = sa4;                                                                                            \
+      if (m + 1 < MT) {                                                                                             \
+        READ_A_(af_n, st_, (m + 1) * (A_TILE_));                                                                    \
+        sa4_n = *(const v4f_t*)(lsa + (g_) * BM + sa_off + (m + 1) * 16);                                           \
+      }                                                                                                             \
+      __builtin_amdgcn_sched_barrier(0);                                                                            \
+      v4f_t d[NT];                                                                                                  \
+      if (m < MT) {                                                                                                 \
+        _Pragma("unroll") for (int n = 0; n < NT; ++n)                                                              \
+          d[n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf[n], v4f_t{0, 0, 0, 0}, FA_, FW_, 0, 0, 0, 0); \
+      }                                                                                                             \
+      if (m > 0) {                                                                                                  \
+        _Pragma("unroll") for (int n = 0; n < NT; ++n)                                                              \
+          _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                           \
+            const float t = d_prev[n][i] * sa4_prev[i];                                                             \
+            acc[m - 1][n][i] = __builtin_fmaf(t, sw1[n], acc[m - 1][n][i]);                                         \
+          }                                                                                                         \
+      }                                                                                                             \
+      if (m > 0 && m < MT) {                                                                                        \
+        _Pragma("unroll") for (int n = 0; n < NT; ++n) {                                                            \
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                        \
+          __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);                                                        \
+        }                                                                                                           \
+      }                                                                                                             \
+      __builtin_amdgcn_sched_barrier(0);                                                                            \
+      if (m < MT) {                                                                                                 \
+        _Pragma("unroll") for (int n = 0; n < NT; ++n) d_prev[n] = d[n];                                            \
+        sa4_prev = sa4;                                                                                             \
+      }                                                                                                             \
+      af = af_n;                                                                                                    \
+      sa4 = sa4_n;                                                                                                  \
+    }                                                                                                               \
+  } while (0)
+
+// The epilogue from the registers (round 4): a lane's results of row i in the NT tiles are four consecutive outputs -> + bias,
+// one rounding to fp16 (QKN_: the q / k norm of the row's head instead, FPQ_QK_NORM_ROW), gate / residual (GATE_, a constant:
+// whether the form has that tail), one 8-byte store; 16 lanes write 128 contiguous bytes.  split_: whether the output is split
+// (FPQ_GEMM_SPLIT_SETUP's on_: epi.sp_cols where one kernel serves both outputs, or a constant).  Rounds 1-3 turned the tile
+// through LDS for 16-byte row stores (64 x (add, convert, ds_write_b16), two barriers, the re-read: ~330 of the ~2850 vector
+// instructions of a wavefront's tile at K = 1920).  outs % 8 == 0 and o % 4 == 0: o < O means o + 4 <= O.
+// Loads are unconditional on clamped addresses (a lane past the edge reads what a neighbour reads and stores nothing): a load
+// inside a divergent branch is waited for inside it.  Requesting the gate / residual rows one tile row ahead of their use - the
+// compiler may not move a load above a store that could alias it, and the residual may BE the output - was measured: 13 % slower
+// with the fused tail (round 4).  The one-tensor stores are non-temporal: a round of tiles writes as much as an XCD's L2 holds -
+// the operands should stay there; +1-2 %.  Names from the kernel: MT, NT, WROWS, acc, bias_h, qkn_b, qkn_s, o, oc, t0, o0, wm,
+// lane, T, O, out, epi.
+#define FPQ_GEMM_REG_EPILOGUE(QKN_, GATE_, split_)                                                                  \
+  do {                                                                                                              \
+    FPQ_GEMM_BIAS_F32();                                                                                            \
+    FPQ_GEMM_GATE_SETUP(WROWS);                                                                                     \
+    FPQ_GEMM_SPLIT_SETUP(WROWS, split_);                                                                            \
+    _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                                \
+      const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);                                               \
+      fpq_h4_t y[4];                                                                                                \
+      if constexpr (QKN_) {                                                                                         \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                             \
+          float yf[NT];                                                                                             \
+          _Pragma("unroll") for (int n = 0; n < NT; ++n) yf[n] = (float)(_Float16)acc[m][n][i] + qkn_b[n];          \
+          if (sp_part_ < 2) FPQ_QK_NORM_ROW(yf, sp_part_, qkn_s);   /* uniform over the tile */                     \
+          _Pragma("unroll") for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)yf[n];                                 \
+        }                                                                                                           \
+      } else {                                                                                                      \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                               \
+          _Pragma("unroll") for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)(acc[m][n][i] + b4[n]);                \
+      }                                                                                                             \
+      int tc[4];                                                                                                    \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;                  \
+      if constexpr (GATE_) FPQ_GEMM_GATE_RESID_ROWS(y, tc, m, oc);                                                  \
+      if (split_) {   /* uniform: four 8-byte stores to the part's rows */                                          \
+        const int oc_l = oc - sp_part_ * epi.sp_cols;                                                               \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) FPQ_GEMM_SPLIT_STORE(y[i], m, i, tc[i], t_first, o, oc_l);    \
+        continue;                                                                                                   \
+      }                                                                                                             \
+      FPQ_GEMM_ROWS_STORE(y, t_first, tc, o, oc);                                                                   \
+    }                                                                                                               \
+  } while (0)
+
+// What the two FP4 kernels below (nibbles on both sides, row-major or k-major at run time) share beyond that.
+// _SOURCES: the LDS-DMA sources of a wavefront's pieces (block = wave + 4 * i of the stage), group 0.
+// The weight rows are DEALT over a wavefront's NT = 4 blocks (round 4): row q of block n holds output 4*q + n of the
+// wavefront's 64, so the lane that holds column q of the NT result tiles holds four CONSECUTIVE outputs 4*q .. 4*q + 3
+// and the epilogue stores 8 bytes per lane, 128 contiguous bytes per 16 lanes, straight from the accumulators.
+// Addressing (round 4): a UNIFORM 64-bit base per operand (the tile's first row) + a 32-bit lane offset (row inside the
+// tile, clamped to the tensor's last row, and 16-byte chunk) that never changes: the step from group to group (64 bytes)
+// is scalar arithmetic and the load takes scalar base + vector offset (FPQ_GLDS_LOAD).  Rows past the end of a tensor are
+// clamped to its last row: their products land where the epilogue never stores.
+// K-major images (epi.km_w_rows != 0): plane g holds every row's 64 bytes of group g, [G][rows][64], the 16-byte chunks of a row
+// already in the LDS image's order and the weight rows in dealt order - a piece is 1 KiB CONTIGUOUS (8 whole 128-byte lines)
+// instead of 16 rows' half lines row_bytes apart: 70 against 105 cycles to issue, profiles/r05_lds_dma_issue.txt.
+// Names from the kernel: A, W, T, O, epi, row_bytes, t0, o0, lane, wave, NT, ABLK, PIECES.  Defines km, a_step, w_step, gbase, voff.
+#define FPQ_FP4_GLDS_SOURCES()                                                                                      \
+  static_assert(NT == 4, "the epilogue packs a lane's NT results of one row into one 8-byte store");               \
+  static_assert(ABLK % 4 == 0, "a wavefront's pieces i < ABLK / 4 are rows of A, the rest rows of W");              \
+  const bool km = epi.km_w_rows != 0;                                                                               \
+  const int row_stride = km ? 64 : row_bytes;                                                                       \
+  const int64_t a_step = km ? (int64_t)T * 64 : 64, w_step = km ? (int64_t)epi.km_w_rows * 64 : 64;                 \
+  const uint8_t* const gbase[2] = {A + (int64_t)t0 * row_stride, W + (int64_t)o0 * row_stride};                     \
+  uint32_t voff[PIECES];                                                                                            \
+  {                                                                                                                 \
+    const int q = lane >> 2, kb = km ? (lane & 3) : (lane & 3) ^ glds_chunk_perm(q);                                \
+    const int w_rows = km ? epi.km_w_rows : O;                                                                      \
+    _Pragma("unroll") for (int i = 0; i < PIECES; ++i) {                                                            \
+      const int blk = wave + 4 * i;                                                                                 \
+      if (blk < ABLK) {                                                                                             \
+        const int t = t0 + blk * 16 + q;                                                                            \
+        voff[i] = (uint32_t)((t < T ? t : T - 1) - t0) * (uint32_t)row_stride + (uint32_t)(kb * 16);                \
+      } else {                                                                                                      \
+        const int wb = blk - ABLK;                                                                                  \
+        const int o = km ? o0 + wb * 16 + q : o0 + (wb / NT) * (16 * NT) + NT * q + wb % NT;                        \
+        voff[i] = (uint32_t)((o < w_rows ? o : w_rows - 1) - o0) * (uint32_t)row_stride + (uint32_t)(kb * 16);      \
+      }                                                                                                             \
+    }                                                                                                               \
+  }
+// group g's pieces of this wavefront into stage buffer buf
+#define FPQ_FP4_GLDS_ISSUE(g, buf)                                                                                  \
+  _Pragma("unroll") for (int i_ = 0; i_ < PIECES; ++i_)                                                             \
+      FPQ_GLDS_LOAD(voff[i_], gbase[i_ < ABLK / 4 ? 0 : 1] + (g) * (i_ < ABLK / 4 ? a_step : w_step),               \
+                    smem + (buf) * STAGE + (wave + 4 * i_) * 1024)
+// the fragment read offsets inside a stage (row lane & 15, chunk lane >> 4 of a 16-row block) and inside the scale tiles
+// (outputs 4q .. 4q+3: tile n holds 4q + n)
+#define FPQ_FP4_FRAG_OFFSETS()                                                                                      \
+  const int frag_off = ((lane & 15) << 6) + ((((lane >> 4) ^ glds_chunk_perm(lane & 15)) & 3) << 4);                \
+  const int a_off = wm * MT * 1024 + frag_off, b_off = (ABLK + wn * NT) * 1024 + frag_off;                          \
+  const int sa_off = wm * MT * 16 + 4 * (lane >> 4), sw_off = wn * NT * 16 + NT * (lane & 15)
+#define FPQ_FP4_READ_A(dst_, st_, tile_) FPQ_GEMM_READ_NIB(dst_, (st_) + a_off + (tile_))
+#define FPQ_FP4_READ_W(dst_, st_, tile_) FPQ_GEMM_READ_NIB(dst_, (st_) + b_off + (tile_))
+
 // target("no-packed-fp32-ops"): beside MFMAs a packed fp32 op costs as much as two scalar ones and blocks the issue
 // port twice as long (tools/probe/valu_mfma_overlap.hip); with the feature off the compiler emits scalar
 // v_mul_f32 / v_fma_f32 and schedules them - and the MFMA hazard wait states - itself.
@@ -589,89 +835,16 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4
   float* lsa = (float*)(smem + 2 * STAGE);   // [G][BM]
   const int Gp = (G + 3) & ~3;               // the scale tiles' LDS-DMA pieces cover up to four groups each: room for a whole last piece
   float* lsw = lsa + Gp * BM;                // [G][BN]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int n_col = (O + BN - 1) / BN, n_row = (T + BM - 1) / BM;
-  const int cpx = (n_col + 7) >> 3;
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int col_blk = xcd * cpx + local % cpx, row_blk = local / cpx;
-  if (col_blk >= n_col || row_blk >= n_row) return;   // uniform over the workgroup
-  const int t0 = row_blk * BM, o0 = col_blk * BN;
+  FPQ_GEMM_TILE_WALK(BM, BN);
 
-  // LDS-DMA sources of this wavefront's pieces (block = wave + 4*i of the stage), group 0.
-  // The weight rows are DEALT over a wavefront's NT = 4 blocks (round 4): row q of block n holds output 4*q + n of the
-  // wavefront's 64, so the lane that holds column q of the NT result tiles holds four CONSECUTIVE outputs 4*q .. 4*q + 3
-  // and the epilogue stores 8 bytes per lane, 128 contiguous bytes per 16 lanes, straight from the accumulators.
-  static_assert(NT == 4, "the epilogue packs a lane's NT results of one row into one 8-byte store");
-  // Addressing (round 4): a UNIFORM 64-bit base per operand (the tile's first row) + a 32-bit lane offset (row inside the
-  // tile, clamped to the tensor's last row, and 16-byte chunk) that never changes: the step from group to group (64 bytes)
-  // is scalar arithmetic and the load takes scalar base + vector offset.  Spelled in assembly - the compiler folds
-  // base + offset into a loop-invariant per-lane pointer and adds the group's 64 bytes to each with a 64-bit vector
-  // addition - and WITHOUT a memory clobber (with one, -4 % instead of +3 %: it pins every LDS read of the group behind it;
-  // the loads write the stage nobody reads, and the barriers order them).  The compiler does not see these loads: the wait
-  // for them is spelled out in front of the barrier that hands a stage to its readers (FPQ_GLDS_WAIT).
   // Issuing a stage's pieces between the MFMAs of the previous one instead of in front of them: 2.5 x slower (measured).
   // A persistent form (one workgroup per resident slot looping over its tiles, the next tile's stage 0 and scale tiles
   // requested in front of the current tile's stores): 5 - 10 % slower than one workgroup per tile (measured, round 4).
-  // K-major images (epi.km_w_rows != 0): plane g holds every row's 64 bytes of group g, [G][rows][64], the 16-byte chunks of a row
-  // already in the LDS image's order and the weight rows in dealt order - a piece is 1 KiB CONTIGUOUS (8 whole 128-byte lines)
-  // instead of 16 rows' half lines row_bytes apart: 70 against 105 cycles to issue, profiles/r05_lds_dma_issue.txt.
-  const bool km = epi.km_w_rows != 0;
-  const int row_stride = km ? 64 : row_bytes;
-  const int64_t a_step = km ? (int64_t)T * 64 : 64, w_step = km ? (int64_t)epi.km_w_rows * 64 : 64;
-  const uint8_t* const gbase[2] = {A + (int64_t)t0 * row_stride, W + (int64_t)o0 * row_stride};
-  uint32_t voff[PIECES];
-  {
-    const int q = lane >> 2, kb = km ? (lane & 3) : (lane & 3) ^ glds_chunk_perm(q);
-    const int w_rows = km ? epi.km_w_rows : O;
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-      const int blk = wave + 4 * i;
-      if (blk < ABLK) {
-        const int t = t0 + blk * 16 + q;
-        voff[i] = (uint32_t)((t < T ? t : T - 1) - t0) * (uint32_t)row_stride + (uint32_t)(kb * 16);
-      } else {
-        const int wb = blk - ABLK;
-        const int o = km ? o0 + wb * 16 + q : o0 + (wb / NT) * (16 * NT) + NT * q + wb % NT;
-        voff[i] = (uint32_t)((o < w_rows ? o : w_rows - 1) - o0) * (uint32_t)row_stride + (uint32_t)(kb * 16);
-      }
-    }
-  }
-  static_assert(ABLK % 4 == 0, "a wavefront's pieces i < ABLK / 4 are rows of A, the rest rows of W");
-#define FPQ_GLDS_ISSUE(g, buf)                                                                                      \
-  _Pragma("unroll") for (int i_ = 0; i_ < PIECES; ++i_)                                                             \
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                                 \
-                   :                                                                                                \
-                   : "v"(voff[i_]), "s"(gbase[i_ < ABLK / 4 ? 0 : 1] + (g) * (i_ < ABLK / 4 ? a_step : w_step)),                                   \
-                     "s"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + (buf) * STAGE +     \
-                                                                                       (wave + 4 * i_) * 1024))    \
-                   : "m0")
-#define FPQ_GLDS_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-  FPQ_GLDS_ISSUE(0, 0);
+  FPQ_FP4_GLDS_SOURCES();
+  FPQ_FP4_GLDS_ISSUE(0, 0);
 
   if (km) {
-    // K-MAJOR SCALE IMAGES (include/fpq.h): fp32 planes [G][rows rounded up to 4] (activations) and [G][km_w_rows] (weights, natural
-    // output order) - the tile's scales of a group are 4 BM (4 BN) contiguous bytes, exactly one row of lsa (lsw): they come
-    // in by LDS-DMA like the codes, 256 / BM (two) groups per 1 KiB piece, no register round trip, no conversion, no ds_write.
-    // Row-major fp16 / fp32 scales cost 90 strided load instructions + as many LDS writes per tile: 8 % of the kernel
-    // (profiles/r05_kmajor_ab.txt).  Pieces dealt round-robin over the four wavefronts; the main loop's first wait covers them.
-    constexpr int APG = 256 / BM, LPG_A = BM / 4;          // groups per piece, lanes per group (activation side)
-    const int Tpad = (T + 3) & ~3, n_a = (G + APG - 1) / APG, n_w = (G + 1) >> 1;
-    const float* sa_km = (const float*)sa;
-    const float* sw_km = (const float*)sw;
-    for (int p = wave; p < n_a + n_w; p += 4) {
-      const bool is_a = p < n_a;
-      const int g0 = is_a ? p * APG : (p - n_a) * 2;
-      const int sub = is_a ? lane / LPG_A : lane >> 5, l4 = is_a ? lane % LPG_A : lane & 31;
-      const int grp = g0 + sub < G ? g0 + sub : G - 1;       // (a last piece's surplus groups re-read the last one; their LDS rows are padding)
-      const int rows = is_a ? Tpad : epi.km_w_rows, r0 = is_a ? t0 : o0;
-      int r4 = r0 + 4 * l4;
-      r4 = r4 < rows - 4 ? r4 : rows - 4;
-      const uint32_t vo = (uint32_t)(((grp - g0) * rows + (r4 - r0)) * 4);
-      const float* sbase = (is_a ? sa_km : sw_km) + ((int64_t)g0 * rows + r0);
-      const uint32_t dst = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(is_a ? lsa + g0 * BM : lsw + g0 * BN);
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(vo), "s"(sbase), "s"(dst) : "m0");
-    }
+    FPQ_GEMM_KM_SCALE_TILES(sa, sw);
   } else {
     load_scale_tiles<Tsw, BM, BN, NTHR>(sa, sw, lsa, lsw, t0, o0, T, O, G, tid);
     // A wait the COMPILER sees (the builtin, not assembly): its scoreboard still carries the scale loads above, whose last
@@ -687,152 +860,28 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4
     lut16_stage(lut, xe.tab, xe.a.shift);
   }
 
-
-  // the tile's bias (four consecutive outputs per lane, see the epilogue) is requested here, not between the last MFMA and
-  // the stores
-  constexpr int WROWS = 16 * MT, WCOLS = 16 * NT;
-  const int o = o0 + wn * WCOLS + NT * (lane & 15);
-  const int oc = o < O ? o : O - 4;
-  fpq_h4_t bias_h = fpq_h4_t{0, 0, 0, 0};
-  if (bias) bias_h = *(const fpq_h4_t*)(bias + oc);
-  v4f_t qkn_b = v4f_t{0, 0, 0, 0};   // (QKN) the fp32 bias of the lane's outputs, and s_h of its head in part 0
-  float qkn_s = 1.0f;
-  if constexpr (QKN) {
-    if (xe.bias) qkn_b = *(const v4f_t*)(xe.bias + oc);
-    if (o0 < epi.sp_cols) qkn_s = xe.q_scale[oc >> 6];
-  }
+  FPQ_GEMM_LANE_BIAS(QKN, xe.bias, xe.q_scale);
 
   v4f_t acc[MT][NT];
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
     for (int n = 0; n < NT; ++n) acc[m][n] = v4f_t{0, 0, 0, 0};
-
-  // fragment read offset inside a block: row lane & 15, chunk lane >> 4
-  const int frag_off = ((lane & 15) << 6) + ((((lane >> 4) ^ glds_chunk_perm(lane & 15)) & 3) << 4);
-  const int a_off = wm * MT * 1024 + frag_off, b_off = (ABLK + wn * NT) * 1024 + frag_off;
-  const int sa_off = wm * MT * 16 + 4 * (lane >> 4), sw_off = wn * NT * 16 + NT * (lane & 15);   // outputs 4q .. 4q+3: tile n holds 4q + n
+  FPQ_FP4_FRAG_OFFSETS();
 
   for (int g = 0; g < G; ++g) {
     FPQ_GLDS_WAIT();
     FPQ_SYNC();   // stage g has landed; stage g^1's readers are done
-    if (g + 1 < G) { FPQ_GLDS_ISSUE(g + 1, (g + 1) & 1); }
+    if (g + 1 < G) { FPQ_FP4_GLDS_ISSUE(g + 1, (g + 1) & 1); }
     const uint8_t* st = smem + (g & 1) * STAGE;
-    // Software pipeline over the tile rows: the ds_reads of row m+1 are issued first, then the NT MFMAs of row m,
-    // then the scale-and-accumulate of row m-1 - VALU work that does not depend on the MFMAs in flight, so no
-    // hazard wait states are needed and 8 of each MFMA's 16 cycles of vector issue are hidden behind it.
-    // (Left to itself the compiler issues each row's reads right before their use and the VALU right behind its
-    // own MFMAs, with s_nops in between.)
-    u32x4 bq[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) bq[n] = *(const u32x4*)(st + b_off + n * 1024);
-    const v4f_t sw1 = *(const v4f_t*)(lsw + g * BN + sw_off);
-    u32x4 aq = *(const u32x4*)(st + a_off);
-    v4f_t sa4 = *(const v4f_t*)(lsa + g * BM + sa_off);
-    v4f_t d_prev[NT], sa4_prev = sa4;
-#pragma unroll
-    for (int n = 0; n < NT; ++n) d_prev[n] = v4f_t{0, 0, 0, 0};
-#pragma unroll
-    for (int m = 0; m <= MT; ++m) {
-      u32x4 aq_n = aq;
-      v4f_t sa4_n = sa4;
-      if (m + 1 < MT) {
-        aq_n = *(const u32x4*)(st + a_off + (m + 1) * 1024);
-        sa4_n = *(const v4f_t*)(lsa + g * BM + sa_off + (m + 1) * 16);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      v4f_t d[NT];
-      if (m < MT) {
-        const v8i_t af = v8i_t{(int)aq[0], (int)aq[1], (int)aq[2], (int)aq[3], 0, 0, 0, 0};
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-          const v8i_t bf = v8i_t{(int)bq[n][0], (int)bq[n][1], (int)bq[n][2], (int)bq[n][3], 0, 0, 0, 0};
-          // literal zero scale operands select the unscaled instruction (x 1.0; tools/probe/mfma_fp4_probe.hip)
-          d[n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf, v4f_t{0, 0, 0, 0}, 4, 4, 0, 0, 0, 0);
-        }
-      }
-      if (m > 0) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float t = d_prev[n][i] * sa4_prev[i];
-            acc[m - 1][n][i] = __builtin_fmaf(t, sw1[n], acc[m - 1][n][i]);
-          }
-      }
-      if (m > 0 && m < MT) {
-        // issue order inside the row: one MFMA, then the 8 VALU ops of one finished tile, NT times - an in-order
-        // wavefront that issues its MFMAs back to back just waits for the matrix pipe with its VALU idle
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (m < MT) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n) d_prev[n] = d[n];
-        sa4_prev = sa4;
-      }
-      aq = aq_n;
-      sa4 = sa4_n;
-    }
+    FPQ_GEMM_GROUP(g, st, FPQ_FP4_READ_A, FPQ_FP4_READ_W, 1024, 1024, 4, 4);
   }
-  // epilogue, from the registers (round 4): a lane's results of row i in the NT tiles are four consecutive outputs -> + bias,
-  // one rounding to fp16, gate / residual, one 8-byte store; 16 lanes write 128 contiguous bytes.  Rounds 1-3 turned the
-  // tile through LDS for 16-byte row stores (64 x (add, convert, ds_write_b16), two barriers, the re-read: ~330 of the
-  // ~2850 vector instructions of a wavefront's tile at K = 1920).  outs % 8 == 0 and o % 4 == 0: o < O means o + 4 <= O.
-  // Loads are unconditional on clamped addresses (a lane past the edge reads what a neighbour reads and stores nothing):
-  // a load inside a divergent branch is waited for inside it.
-  v4f_t b4 = v4f_t{0, 0, 0, 0};
-#pragma unroll
-  for (int n = 0; n < NT; ++n) b4[n] = (float)bias_h[n];
   if constexpr (FC1) {
     FPQ_GEMM_FC1_TAIL(STAGE);
     return;
   }
-  FPQ_GEMM_GATE_SETUP(WROWS);
-  FPQ_GEMM_SPLIT_SETUP(WROWS, epi.sp_cols);   // (this epilogue serves the one-tensor output too)
-  // (requesting the gate / residual rows one tile row ahead of their use - the compiler may not move a load above a store
-  // that could alias it, and the residual may BE the output - was measured: 13 % slower with the fused tail, round 4)
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);
-    fpq_h4_t y[4];
-    if constexpr (QKN) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float yf[NT];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) yf[n] = (float)(_Float16)acc[m][n][i] + qkn_b[n];
-        if (sp_part_ < 2) FPQ_QK_NORM_ROW(yf, sp_part_, qkn_s);   // uniform over the tile
-#pragma unroll
-        for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)yf[n];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)(acc[m][n][i] + b4[n]);
-    }
-    int tc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;
-    FPQ_GEMM_GATE_RESID_ROWS(y, tc, m, oc);
-    if (epi.sp_cols) {   // uniform: four 8-byte stores to the part's rows
-      const int oc_l = oc - sp_part_ * epi.sp_cols;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) FPQ_GEMM_SPLIT_STORE(y[i], m, i, tc[i], t_first, o, oc_l);
-      continue;
-    }
-    // (non-temporal: a round of tiles writes as much as an XCD's L2 holds - the operands should stay there; +1-2 %)
-    FPQ_GEMM_ROWS_STORE(y, t_first, tc, o, oc);
-  }
+  FPQ_GEMM_REG_EPILOGUE(QKN, true, epi.sp_cols);   // (this epilogue serves the one-tensor output too)
 }
-
-#undef FPQ_GLDS_ISSUE
-#undef FPQ_GLDS_WAIT
 
 // ---------------------------------------------------------------------------------------------------
 // The deep-ring small-M form of gemm_fp4_glds_kernel<.., 2, 4> (FPQ_GEMM_CFG 40): the same 64 x 128 tile, LDS block image, dealt
@@ -886,88 +935,23 @@ __global__ __launch_bounds__(256, 3) FPQ_NOPK void gemm_fp4_ring_kernel(const ui
   float* lsa = (float*)(smem + S * STAGE);   // [G][BM]
   const int Gp = (G + 3) & ~3;
   float* lsw = lsa + Gp * BM;                // [G][BN]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int n_col = (O + BN - 1) / BN, n_row = (T + BM - 1) / BM;
-  const int cpx = (n_col + 7) >> 3;
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int col_blk = xcd * cpx + local % cpx, row_blk = local / cpx;
-  if (col_blk >= n_col || row_blk >= n_row) return;   // uniform over the workgroup
-  const int t0 = row_blk * BM, o0 = col_blk * BN;
-
-  // LDS-DMA sources: gemm_fp4_glds_kernel's (uniform base per operand, 32-bit lane offset clamped to the tensor's last row)
-  const bool km = epi.km_w_rows != 0;
-  const int row_stride = km ? 64 : row_bytes;
-  const int64_t a_step = km ? (int64_t)T * 64 : 64, w_step = km ? (int64_t)epi.km_w_rows * 64 : 64;
-  const uint8_t* const gbase[2] = {A + (int64_t)t0 * row_stride, W + (int64_t)o0 * row_stride};
-  uint32_t voff[PIECES];
-  {
-    const int q = lane >> 2, kb = km ? (lane & 3) : (lane & 3) ^ glds_chunk_perm(q);
-    const int w_rows = km ? epi.km_w_rows : O;
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-      const int blk = wave + 4 * i;
-      if (blk < ABLK) {
-        const int t = t0 + blk * 16 + q;
-        voff[i] = (uint32_t)((t < T ? t : T - 1) - t0) * (uint32_t)row_stride + (uint32_t)(kb * 16);
-      } else {
-        const int wb = blk - ABLK;
-        const int o = km ? o0 + wb * 16 + q : o0 + (wb / NT) * (16 * NT) + NT * q + wb % NT;
-        voff[i] = (uint32_t)((o < w_rows ? o : w_rows - 1) - o0) * (uint32_t)row_stride + (uint32_t)(kb * 16);
-      }
-    }
-  }
-  static_assert(ABLK % 4 == 0, "a wavefront's pieces i < ABLK / 4 are rows of A, the rest rows of W");
-#define FPQ_RING_ISSUE(g, buf)                                                                                      \
-  _Pragma("unroll") for (int i_ = 0; i_ < PIECES; ++i_)                                                             \
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                                 \
-                   :                                                                                                \
-                   : "v"(voff[i_]), "s"(gbase[i_ < ABLK / 4 ? 0 : 1] + (g) * (i_ < ABLK / 4 ? a_step : w_step)),    \
-                     "s"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + (buf) * STAGE +     \
-                                                                                       (wave + 4 * i_) * 1024))    \
-                   : "m0")
+  FPQ_GEMM_TILE_WALK(BM, BN);
+  FPQ_FP4_GLDS_SOURCES();
 
   if (km) {
-    // the k-major scale images by LDS-DMA (gemm_fp4_glds_kernel's block), IN FRONT of the ring: a wavefront has 0 .. n pieces of
-    // them, so they cannot be counted - being older than group 0, its wait covers them
-    constexpr int APG = 256 / BM, LPG_A = BM / 4;
-    const int Tpad = (T + 3) & ~3, n_a = (G + APG - 1) / APG, n_w = (G + 1) >> 1;
-    const float* sa_km = (const float*)sa;
-    const float* sw_km = (const float*)sw;
-    for (int p = wave; p < n_a + n_w; p += 4) {
-      const bool is_a = p < n_a;
-      const int g0 = is_a ? p * APG : (p - n_a) * 2;
-      const int sub = is_a ? lane / LPG_A : lane >> 5, l4 = is_a ? lane % LPG_A : lane & 31;
-      const int grp = g0 + sub < G ? g0 + sub : G - 1;
-      const int rows = is_a ? Tpad : epi.km_w_rows, r0 = is_a ? t0 : o0;
-      int r4 = r0 + 4 * l4;
-      r4 = r4 < rows - 4 ? r4 : rows - 4;
-      const uint32_t vo = (uint32_t)(((grp - g0) * rows + (r4 - r0)) * 4);
-      const float* sbase = (is_a ? sa_km : sw_km) + ((int64_t)g0 * rows + r0);
-      const uint32_t dst = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(is_a ? lsa + g0 * BM : lsw + g0 * BN);
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(vo), "s"(sbase), "s"(dst) : "m0");
-    }
+    // the k-major scale images IN FRONT of the ring: being older than group 0, its wait covers them
+    FPQ_GEMM_KM_SCALE_TILES(sa, sw);
   } else {
     load_scale_tiles<Tsw, BM, BN, NTHR>(sa, sw, lsa, lsw, t0, o0, T, O, G, tid);
     // the wait the compiler sees (gemm_fp4_glds_kernel: it has to stand in this branch); the ring is requested behind it
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
   }
   // the tile's bias, the q / k norm's fp32 bias and head scale: in front of the ring too
-  constexpr int WROWS = 16 * MT, WCOLS = 16 * NT;
-  const int o = o0 + wn * WCOLS + NT * (lane & 15);
-  const int oc = o < O ? o : O - 4;
-  fpq_h4_t bias_h = fpq_h4_t{0, 0, 0, 0};
-  if (bias) bias_h = *(const fpq_h4_t*)(bias + oc);
-  v4f_t qkn_b = v4f_t{0, 0, 0, 0};
-  float qkn_s = 1.0f;
-  if constexpr (QKN) {
-    if (xe.bias) qkn_b = *(const v4f_t*)(xe.bias + oc);
-    if (o0 < epi.sp_cols) qkn_s = xe.q_scale[oc >> 6];
-  }
+  FPQ_GEMM_LANE_BIAS(QKN, xe.bias, xe.q_scale);
   // the ring's first min(S - 1, G) groups
 #pragma unroll
   for (int i = 0; i < S - 1; ++i)
-    if (i < G) { FPQ_RING_ISSUE(i, i); }   // uniform
+    if (i < G) { FPQ_FP4_GLDS_ISSUE(i, i); }   // uniform
 
   uint16_t* lut = nullptr;
   if constexpr (FC1) {   // the dual quantizer's bucket table, behind the scale tiles; visible after the first barrier of the main loop
@@ -980,59 +964,8 @@ __global__ __launch_bounds__(256, 3) FPQ_NOPK void gemm_fp4_ring_kernel(const ui
   for (int m = 0; m < MT; ++m)
 #pragma unroll
     for (int n = 0; n < NT; ++n) acc[m][n] = v4f_t{0, 0, 0, 0};
+  FPQ_FP4_FRAG_OFFSETS();
 
-  const int frag_off = ((lane & 15) << 6) + ((((lane >> 4) ^ glds_chunk_perm(lane & 15)) & 3) << 4);
-  const int a_off = wm * MT * 1024 + frag_off, b_off = (ABLK + wn * NT) * 1024 + frag_off;
-  const int sa_off = wm * MT * 16 + 4 * (lane >> 4), sw_off = wn * NT * 16 + NT * (lane & 15);
-
-  // group g_ from stage buffer st_: gemm_fp4_glds_kernel's software pipeline over the tile rows, operation for operation
-#define FPQ_RING_GROUP(g_, st_)                                                                                     \
-  do {                                                                                                              \
-    u32x4 bq[NT];                                                                                                   \
-    _Pragma("unroll") for (int n = 0; n < NT; ++n) bq[n] = *(const u32x4*)((st_) + b_off + n * 1024);               \
-    const v4f_t sw1 = *(const v4f_t*)(lsw + (g_) * BN + sw_off);                                                    \
-    u32x4 aq = *(const u32x4*)((st_) + a_off);                                                                      \
-    v4f_t sa4 = *(const v4f_t*)(lsa + (g_) * BM + sa_off);                                                          \
-    v4f_t d_prev[NT], sa4_prev = sa4;                                                                               \
-    _Pragma("unroll") for (int n = 0; n < NT; ++n) d_prev[n] = v4f_t{0, 0, 0, 0};                                   \
-    _Pragma("unroll") for (int m = 0; m <= MT; ++m) {                                                               \
-      u32x4 aq_n = aq;                                                                                              \
-      v4f_t sa4_n = sa4;                                                                                            \
-      if (m + 1 < MT) {                                                                                             \
-        aq_n = *(const u32x4*)((st_) + a_off + (m + 1) * 1024);                                                     \
-        sa4_n = *(const v4f_t*)(lsa + (g_) * BM + sa_off + (m + 1) * 16);                                           \
-      }                                                                                                             \
-      __builtin_amdgcn_sched_barrier(0);                                                                            \
-      v4f_t d[NT];                                                                                                  \
-      if (m < MT) {                                                                                                 \
-        const v8i_t af = v8i_t{(int)aq[0], (int)aq[1], (int)aq[2], (int)aq[3], 0, 0, 0, 0};                         \
-        _Pragma("unroll") for (int n = 0; n < NT; ++n) {                                                            \
-          const v8i_t bf = v8i_t{(int)bq[n][0], (int)bq[n][1], (int)bq[n][2], (int)bq[n][3], 0, 0, 0, 0};           \
-          d[n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf, v4f_t{0, 0, 0, 0}, 4, 4, 0, 0, 0, 0);     \
-        }                                                                                                           \
-      }                                                                                                             \
-      if (m > 0) {                                                                                                  \
-        _Pragma("unroll") for (int n = 0; n < NT; ++n)                                                              \
-          _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                           \
-            const float t = d_prev[n][i] * sa4_prev[i];                                                             \
-            acc[m - 1][n][i] = __builtin_fmaf(t, sw1[n], acc[m - 1][n][i]);                                         \
-          }                                                                                                         \
-      }                                                                                                             \
-      if (m > 0 && m < MT) {                                                                                        \
-        _Pragma("unroll") for (int n = 0; n < NT; ++n) {                                                            \
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                        \
-          __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);                                                        \
-        }                                                                                                           \
-      }                                                                                                             \
-      __builtin_amdgcn_sched_barrier(0);                                                                            \
-      if (m < MT) {                                                                                                 \
-        _Pragma("unroll") for (int n = 0; n < NT; ++n) d_prev[n] = d[n];                                            \
-        sa4_prev = sa4;                                                                                             \
-      }                                                                                                             \
-      aq = aq_n;                                                                                                    \
-      sa4 = sa4_n;                                                                                                  \
-    }                                                                                                               \
-  } while (0)
   // the last S - 1 groups' waits: rem_ = G - 1 - g groups are behind group g in the queue, all of them may stay in flight
   // (counts past S - 2 never occur: they repeat the steady one)
 #define FPQ_RING_TAIL_WAIT(rem_)                                                                                    \
@@ -1052,65 +985,31 @@ __global__ __launch_bounds__(256, 3) FPQ_NOPK void gemm_fp4_ring_kernel(const ui
     glds_wait_vm<PIECES * (S - 2)>();
     FPQ_SYNC();   // group g has landed for every wavefront; buffer (g - 1) % S's readers are done
     const int wb = rb == 0 ? S - 1 : rb - 1;
-    FPQ_RING_ISSUE(g + S - 1, wb);
+    FPQ_FP4_GLDS_ISSUE(g + S - 1, wb);
     const uint8_t* st = smem + rb * STAGE;
-    FPQ_RING_GROUP(g, st);
+    FPQ_GEMM_GROUP(g, st, FPQ_FP4_READ_A, FPQ_FP4_READ_W, 1024, 1024, 4, 4);
     rb = rb + 1 == S ? 0 : rb + 1;
   }
   for (; g < G; ++g) {   // the drain: nothing is requested any more
     FPQ_RING_TAIL_WAIT(G - 1 - g);
     FPQ_SYNC();
     const uint8_t* st = smem + rb * STAGE;
-    FPQ_RING_GROUP(g, st);
+    FPQ_GEMM_GROUP(g, st, FPQ_FP4_READ_A, FPQ_FP4_READ_W, 1024, 1024, 4, 4);
     rb = rb + 1 == S ? 0 : rb + 1;
   }
+#undef FPQ_RING_TAIL_WAIT
 
-  // the register epilogues of gemm_fp4_glds_kernel
-  v4f_t b4 = v4f_t{0, 0, 0, 0};
-#pragma unroll
-  for (int n = 0; n < NT; ++n) b4[n] = (float)bias_h[n];
   if constexpr (FC1) {
     FPQ_GEMM_FC1_TAIL(STAGE);
     return;
   }
-  FPQ_GEMM_GATE_SETUP(WROWS);
-  FPQ_GEMM_SPLIT_SETUP(WROWS, epi.sp_cols);
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);
-    fpq_h4_t y[4];
-    if constexpr (QKN) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float yf[NT];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) yf[n] = (float)(_Float16)acc[m][n][i] + qkn_b[n];
-        if (sp_part_ < 2) FPQ_QK_NORM_ROW(yf, sp_part_, qkn_s);   // uniform over the tile
-#pragma unroll
-        for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)yf[n];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)(acc[m][n][i] + b4[n]);
-    }
-    int tc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;
-    FPQ_GEMM_GATE_RESID_ROWS(y, tc, m, oc);
-    if (epi.sp_cols) {
-      const int oc_l = oc - sp_part_ * epi.sp_cols;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) FPQ_GEMM_SPLIT_STORE(y[i], m, i, tc[i], t_first, o, oc_l);
-      continue;
-    }
-    FPQ_GEMM_ROWS_STORE(y, t_first, tc, o, oc);
-  }
+  FPQ_GEMM_REG_EPILOGUE(QKN, true, epi.sp_cols);
 }
-#undef FPQ_RING_ISSUE
-#undef FPQ_RING_GROUP
-#undef FPQ_RING_TAIL_WAIT
+#undef FPQ_FP4_GLDS_SOURCES
+#undef FPQ_FP4_GLDS_ISSUE
+#undef FPQ_FP4_FRAG_OFFSETS
+#undef FPQ_FP4_READ_A
+#undef FPQ_FP4_READ_W
 
 // the ring kernel's tile and LDS figure: S stages + the scale tiles, groups rounded up to four
 struct GemmRingCfg {

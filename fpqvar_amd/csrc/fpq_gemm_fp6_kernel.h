@@ -27,14 +27,7 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_GEMM6_KERNEL(const uint8_
   constexpr int PIECES = NPIECE / 4;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int steps = C >> 7, row_bytes = (C >> 2) * 3;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int n_col = (O + BN - 1) / BN, n_row = (T + BM - 1) / BM;
-  const int cpx = (n_col + 7) >> 3;
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int col_blk = xcd * cpx + local % cpx, row_blk = local / cpx;
-  if (col_blk >= n_col || row_blk >= n_row) return;   // uniform over the workgroup
-  const int t0 = row_blk * BM, o0 = col_blk * BN;
+  FPQ_GEMM_TILE_WALK(BM, BN);   // fpq_gemm_fp4.h
 #ifdef FPQ_GEMM6_STAMPS
   unsigned long long st6_sum[6] = {0, 0, 0, 0, 0, 0};
   unsigned long long st6_last = __builtin_amdgcn_s_memtime();
@@ -113,7 +106,7 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_GEMM6_KERNEL(const uint8_
   // requesting tile row m + 1's fragment before the MFMAs of row m (no gain: the SIMD's second wavefront covers it).
   FPQ_ST6(4);
   for (int s = 0; s < steps; ++s) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the compiler does not see the LDS-DMA loads
+    FPQ_GLDS_WAIT();   // the compiler does not see the LDS-DMA loads
     FPQ_ST6(0);
     FPQ_SYNC();   // stage s has landed; the other buffer's readers are done
     FPQ_ST6(1);

@@ -112,14 +112,7 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 1 : 2)) FPQ_NOPK void gemm_fp8
   constexpr int PIECES = NPIECE / 4;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int steps = C >> 7;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int n_col = (O + BN - 1) / BN, n_row = (T + BM - 1) / BM;
-  const int cpx = (n_col + 7) >> 3;
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int col_blk = xcd * cpx + local % cpx, row_blk = local / cpx;
-  if (col_blk >= n_col || row_blk >= n_row) return;   // uniform over the workgroup
-  const int t0 = row_blk * BM, o0 = col_blk * BN;
+  FPQ_GEMM_TILE_WALK(BM, BN);   // fpq_gemm_fp4.h
 
   // LDS-DMA sources: scalar base per operand + 32-bit lane offset, in assembly with explicit waits (as in gemm_fp4_glds_kernel)
   const uint8_t* const gbase[2] = {A + (int64_t)t0 * C, W + (int64_t)o0 * C};
@@ -164,7 +157,7 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 1 : 2)) FPQ_NOPK void gemm_fp8
   const int a_base = wm * MT * 2048, b_base = (ABLK + wn * NT) * 2048;
 
   for (int s = 0; s < steps; ++s) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the compiler does not see the LDS-DMA loads above
+    FPQ_GLDS_WAIT();   // the compiler does not see the LDS-DMA loads above
     FPQ_SYNC();   // stage s has landed; the other buffer's readers are done
     if (s + 1 < steps) { FPQ_GLDS8_ISSUE(s + 1, (s + 1) & 1); }
     const uint8_t* st = smem + (s & 1) * STAGE;

@@ -24,9 +24,12 @@
 //     ds_read_b64 per fragment; first used against nibbles by the A6W4 kernel;
 //   * 6-bit codes, weight side: the FP6 kernel's weight super-blocks, rows dealt over a wavefront's NT tiles; first used by the W6
 //     kernel.  (A nibble weight block is dealt the same way.)
-// The tile walk, the LDS-DMA issue, the scale tiles, the software-pipelined main loop and the register epilogues do not depend on
-// the forms.  Every kernel's machine code is, instruction for instruction, what the two families' separate texts gave:
-// profiles/g6_merge_isa.txt.
+// The tile walk, the k-major scale tiles, the lane's bias loads, the software pipeline over a K group and the register epilogues do
+// not depend on the forms and are not written here: they are the stages this text shares with gemm_fp4_glds_kernel and
+// gemm_fp4_ring_kernel (fpq_gemm_fp4.h, "THE STAGES OF THE PER-GROUP(128) LDS-DMA KERNELS").  What is this text's own: the lane
+// offsets and the issue of a stage in the two forms, the fragment readers, and the choice of tail.  Every kernel's machine code
+// is, instruction for instruction, what the two families' separate texts gave (profiles/g6_merge_isa.txt) and what this text gave
+// with its own copy of the shared stages (profiles/gemm_shared_stages_isa.txt).
 #ifndef FPQ_G6_FC1
 #define FPQ_G6_FC1 0
 #endif
@@ -78,14 +81,7 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_G6_KERNEL(const uint8_t* 
   float* lsa = (float*)(smem + 2 * STAGE);   // [G][BM]
   const int Gp = (G + 3) & ~3;
   float* lsw = lsa + Gp * BM;                // [G][BN]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int n_col = (O + BN - 1) / BN, n_row = (T + BM - 1) / BM;
-  const int cpx = (n_col + 7) >> 3;
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int col_blk = xcd * cpx + local % cpx, row_blk = local / cpx;
-  if (col_blk >= n_col || row_blk >= n_row) return;   // uniform over the workgroup
-  const int t0 = row_blk * BM, o0 = col_blk * BN;
+  FPQ_GEMM_TILE_WALK(BM, BN);
 
   // LDS-DMA sources: a uniform base per operand + a 32-bit lane offset that never changes (see gemm_fp4_glds_kernel); rows past
   // the end of a tensor are clamped to its last row - their products land where the epilogue never stores
@@ -122,40 +118,8 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_G6_KERNEL(const uint8_t* 
       voff[i] = (uint32_t)((o < epi.km_w_rows ? o : epi.km_w_rows - 1) - o0) * 96u + (uint32_t)(pc * 16);
     }
   }
-#define FPQ_G6_ISSUE(g, buf)                                                                                        \
-  _Pragma("unroll") for (int i_ = 0; i_ < PIECES; ++i_) {                                                           \
-    const int piece_ = wave + 4 * i_;                                                                               \
-    if (piece_ < NPC)   /* wavefront-uniform */                                                                     \
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                                 \
-                   :                                                                                                \
-                   : "v"(voff[i_]), "s"(piece_ < APC ? a_base_g + (g) * a_step : w_base_g + (g) * w_step),          \
-                     "s"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + (buf) * STAGE +     \
-                                                                                       piece_ * 1024))             \
-                   : "m0");                                                                                         \
-  }
-  FPQ_G6_ISSUE(0, 0);
-  {
-    // the scale tiles by LDS-DMA, gemm_fp4_glds_kernel's `if (km)` block: a group's scales of the tile are
-    // 4 BM (4 BN) contiguous bytes = one row of lsa (lsw); 256 / BM groups per activation piece, two per weight piece, a last
-    // piece's surplus groups re-read the last one (their LDS rows are the padding up to Gp); rows clamped to the image's last four.
-    // The main loop's first vmcnt(0) covers them - the compiler has issued no load of its own that it would have to wait for.
-    constexpr int APG = 256 / BM, LPG_A = BM / 4;
-    const int Tpad = (T + 3) & ~3, n_a = (G + APG - 1) / APG, n_w = (G + 1) >> 1;
-    for (int p = wave; p < n_a + n_w; p += 4) {
-      const bool is_a = p < n_a;
-      const int g0 = is_a ? p * APG : (p - n_a) * 2;
-      const int sub = is_a ? lane / LPG_A : lane >> 5, l4 = is_a ? lane % LPG_A : lane & 31;
-      const int grp = g0 + sub < G ? g0 + sub : G - 1;
-      const int rows = is_a ? Tpad : epi.km_w_rows, r0 = is_a ? t0 : o0;
-      int r4 = r0 + 4 * l4;
-      r4 = r4 < rows - 4 ? r4 : rows - 4;
-      const uint32_t vo = (uint32_t)(((grp - g0) * rows + (r4 - r0)) * 4);
-      const float* sbase = (is_a ? sa : sw) + ((int64_t)g0 * rows + r0);
-      const uint32_t dst = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(is_a ? lsa + g0 * BM : lsw + g0 * BN);
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(vo), "s"(sbase), "s"(dst) : "m0");
-    }
-  }
 #else
+  constexpr int a_step = A_SEG, w_step = W_SEG;   // row-major: a group is the next A_SEG / W_SEG bytes of every row
   const uint8_t* const a_base_g = A + (int64_t)t0 * a_row_bytes;
   const uint8_t* const w_base_g = W + (int64_t)o0 * w_row_bytes;
   uint32_t voff[PIECES];
@@ -189,18 +153,18 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_G6_KERNEL(const uint8_t* 
       voff[i] = (uint32_t)((o < O ? o : O - 1) - o0) * (uint32_t)w_row_bytes + (uint32_t)(c * 16);
     }
   }
+#endif
 #define FPQ_G6_ISSUE(g, buf)                                                                                        \
   _Pragma("unroll") for (int i_ = 0; i_ < PIECES; ++i_) {                                                           \
     const int piece_ = wave + 4 * i_;                                                                               \
     if (piece_ < NPC)   /* wavefront-uniform */                                                                     \
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                                 \
-                   :                                                                                                \
-                   : "v"(voff[i_]), "s"(piece_ < APC ? a_base_g + (g) * A_SEG : w_base_g + (g) * W_SEG),            \
-                     "s"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + (buf) * STAGE +     \
-                                                                                       piece_ * 1024))             \
-                   : "m0");                                                                                         \
+      FPQ_GLDS_LOAD(voff[i_], piece_ < APC ? a_base_g + (g) * a_step : w_base_g + (g) * w_step,                     \
+                    smem + (buf) * STAGE + piece_ * 1024);                                                          \
   }
   FPQ_G6_ISSUE(0, 0);
+#if FPQ_G6_KM
+  FPQ_GEMM_KM_SCALE_TILES(sa, sw);
+#else
   load_scale_tiles<Tsw, BM, BN, NTHR>(sa, sw, lsa, lsw, t0, o0, T, O, G, tid);
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), the builtin: the compiler's scoreboard forgets the scale loads (gemm_fp4_glds_kernel)
 #endif
@@ -210,18 +174,11 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_G6_KERNEL(const uint8_t* 
   lut16_stage(lut, xe.tab, xe.a.shift);
 #endif
 
-  constexpr int WROWS = 16 * MT, WCOLS = 16 * NT;
-  const int o = o0 + wn * WCOLS + NT * (lane & 15);
-  const int oc = o < O ? o : O - 4;
+  // (OUT == 2: the fp16 bias is NULL, the q / k norm's fp32 bias replaces it)
 #if !FPQ_G6_FC1 && FPQ_G6_OUT == 2
-  // the fp32 bias of the lane's outputs and s_h of its head in part 0, as gemm_fp4_glds_kernel reads them (the fp16 bias is NULL here)
-  v4f_t qkn_b = v4f_t{0, 0, 0, 0};
-  float qkn_s = 1.0f;
-  if (xe.bias) qkn_b = *(const v4f_t*)(xe.bias + oc);
-  if (o0 < epi.sp_cols) qkn_s = xe.q_scale[oc >> 6];
+  FPQ_GEMM_LANE_BIAS(true, xe.bias, xe.q_scale);
 #else
-  fpq_h4_t bias_h = fpq_h4_t{0, 0, 0, 0};
-  if (bias) bias_h = *(const fpq_h4_t*)(bias + oc);
+  FPQ_GEMM_LANE_BIAS(false, (const float*)nullptr, (const float*)nullptr);
 #endif
 
   v4f_t acc[MT][NT];
@@ -251,139 +208,40 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_G6_KERNEL(const uint8_t* 
 #define FPQ_G6_READ(dst_, nibbles_, p_)                                                                             \
   do {                                                                                                              \
     if constexpr (nibbles_) {                                                                                       \
-      const u32x4 q_ = *(const u32x4*)(p_);                                                                         \
-      dst_ = v8i_t{(int)q_[0], (int)q_[1], (int)q_[2], (int)q_[3], 0, 0, 0, 0};                                     \
+      FPQ_GEMM_READ_NIB(dst_, p_);                                                                                  \
     } else {                                                                                                        \
       const u32x2 q0_ = FPQ_LDS_READ64((p_) + foff[0]), q1_ = FPQ_LDS_READ64((p_) + foff[1]),                       \
                   q2_ = FPQ_LDS_READ64((p_) + foff[2]);                                                             \
       dst_ = v8i_t{(int)q0_[0], (int)q0_[1], (int)q1_[0], (int)q1_[1], (int)q2_[0], (int)q2_[1], 0, 0};             \
     }                                                                                                               \
   } while (0)
+#define FPQ_G6_READ_A(dst_, st_, tile_) FPQ_G6_READ(dst_, A4, (st_) + (tile_) + a_off)
+#define FPQ_G6_READ_W(dst_, st_, tile_) FPQ_G6_READ(dst_, W4, (st_) + b_off + (tile_))
 
-  for (int g = 0; g < G; ++g) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the compiler does not see the LDS-DMA loads
+  for (int g = 0; g < G; ++g) {   // the two-stage schedule of gemm_fp4_glds_kernel
+    FPQ_GLDS_WAIT();
     FPQ_SYNC();   // stage g has landed; stage g^1's readers are done
     if (g + 1 < G) { FPQ_G6_ISSUE(g + 1, (g + 1) & 1); }
     const uint8_t* st = smem + (g & 1) * STAGE;
-    // the software pipeline of gemm_fp4_glds_kernel: the reads of tile row m+1, the NT MFMAs of row m, the scale-and-accumulate
-    // of row m-1
-    v8i_t bf[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) FPQ_G6_READ(bf[n], W4, st + b_off + n * W_TILE);
-    const v4f_t sw1 = *(const v4f_t*)(lsw + g * BN + sw_off);
-    v8i_t af;
-    FPQ_G6_READ(af, A4, st + a_off);
-    v4f_t sa4 = *(const v4f_t*)(lsa + g * BM + sa_off);
-    v4f_t d_prev[NT], sa4_prev = sa4;
-#pragma unroll
-    for (int n = 0; n < NT; ++n) d_prev[n] = v4f_t{0, 0, 0, 0};
-#pragma unroll
-    for (int m = 0; m <= MT; ++m) {
-      v8i_t af_n = af;
-      v4f_t sa4_n = sa4;
-      if (m + 1 < MT) {
-        FPQ_G6_READ(af_n, A4, st + (m + 1) * A_TILE + a_off);
-        sa4_n = *(const v4f_t*)(lsa + g * BM + sa_off + (m + 1) * 16);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      v4f_t d[NT];
-      if (m < MT) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-          // cbsz = FA decodes the activation fragment, blgp = FW the weight fragment; literal zero scales: the unscaled instruction
-          d[n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf[n], v4f_t{0, 0, 0, 0}, FA, FW, 0, 0, 0, 0);
-      }
-      if (m > 0) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float t = d_prev[n][i] * sa4_prev[i];
-            acc[m - 1][n][i] = __builtin_fmaf(t, sw1[n], acc[m - 1][n][i]);
-          }
-      }
-      if (m > 0 && m < MT) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (m < MT) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n) d_prev[n] = d[n];
-        sa4_prev = sa4;
-      }
-      af = af_n;
-      sa4 = sa4_n;
-    }
+    FPQ_GEMM_GROUP(g, st, FPQ_G6_READ_A, FPQ_G6_READ_W, A_TILE, W_TILE, FA, FW);
   }
 #undef FPQ_G6_READ
+#undef FPQ_G6_READ_A
+#undef FPQ_G6_READ_W
 #undef FPQ_G6_ISSUE
 #undef FPQ_G6_TSA
 
-  // epilogue from the registers, as gemm_fp4_glds_kernel's: + bias, one rounding to fp16, then the form's own tail, 8-byte stores
-#if FPQ_G6_FC1 || FPQ_G6_OUT != 2
-  v4f_t b4 = v4f_t{0, 0, 0, 0};
-#pragma unroll
-  for (int n = 0; n < NT; ++n) b4[n] = (float)bias_h[n];
-#endif
-#if FPQ_G6_FC1
-  // the maxima exchange goes into stage buffer G & 1, which the last K group does not read (and nothing was loaded into after
-  // the group before it was read: the last issue fills buffer (G - 1) & 1); this form has no gate / residual tail: epi is not read
+  // the register epilogue: the fc1 tail (the maxima exchange goes into stage buffer G & 1, which the last K group does not read
+  // and nothing was loaded into after the group before it was read: the last issue fills buffer (G - 1) & 1; no gate / residual
+  // tail: epi is not read), the split output (no gate / residual tail either), or the one tensor with the gate / residual tail
 #if FPQ_G6_FC1 == 2
   FPQ_GEMM_FC1_TAIL_X(STAGE, true);   // the dual pair without a global clamp: a NaN stays out of the maxima
-#else
+#elif FPQ_G6_FC1
   FPQ_GEMM_FC1_TAIL(STAGE);
-#endif
 #elif FPQ_G6_OUT
-  // the split output, as gemm_fp4_glds_kernel stores it (same tile, same lane-to-output mapping: a lane's four values of row i are
-  // four consecutive columns of one part, a token row's head of 64 columns is the 16 lanes of a DPP row); no gate / residual tail
-  FPQ_GEMM_SPLIT_SETUP(WROWS, true);
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);
-    fpq_h4_t y[4];
-#if FPQ_G6_OUT == 2
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float yf[NT];
-#pragma unroll
-      for (int n = 0; n < NT; ++n) yf[n] = (float)(_Float16)acc[m][n][i] + qkn_b[n];
-      if (sp_part_ < 2) FPQ_QK_NORM_ROW(yf, sp_part_, qkn_s);   // uniform over the tile
-#pragma unroll
-      for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)yf[n];
-    }
+  FPQ_GEMM_REG_EPILOGUE(FPQ_G6_OUT == 2, false, true);   // (q / k norm, gate / residual tail, split output)
 #else
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)(acc[m][n][i] + b4[n]);
-#endif
-    int tc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;
-    const int oc_l = oc - sp_part_ * epi.sp_cols;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) FPQ_GEMM_SPLIT_STORE(y[i], m, i, tc[i], t_first, o, oc_l);
-  }
-#else
-  FPQ_GEMM_GATE_SETUP(WROWS);
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);
-    fpq_h4_t y[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)(acc[m][n][i] + b4[n]);
-    int tc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;
-    FPQ_GEMM_GATE_RESID_ROWS(y, tc, m, oc);
-    FPQ_GEMM_ROWS_STORE(y, t_first, tc, o, oc);
-  }
+  FPQ_GEMM_REG_EPILOGUE(false, true, false);
 #endif
 }
 #undef FPQ_G6_KERNEL
