@@ -251,6 +251,19 @@ _SIGS = {
     "fpq_gemm_f6_rows_split_qknorm": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
                                                   _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int,
                                                   _c.c_void_p]),
+    # the squared-error forms of the four GEMM families: the plain entry point's list up to bias, then ref, ref_dtype, row_weight,
+    # loss_out, workspace, tokens, outs, k, stream
+    "fpq_gemm_sqerr_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int64]),
+    "fpq_gemm_fp4_sqerr": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                       _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p]),
+    "fpq_gemm_a6w4_sqerr": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                        _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p]),
+    "fpq_gemm_w6_sqerr": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p,
+                                      _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64,
+                                      _c.c_void_p]),
+    "fpq_gemm_f6_rows_sqerr": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
+                                           _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
+                                           _c.c_int64, _c.c_int64, _c.c_void_p]),
     "fpq_dequant_rows_codes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
                                            _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
     "fpq_quant_rows_codes_segments": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int,

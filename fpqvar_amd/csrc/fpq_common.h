@@ -46,6 +46,9 @@ static inline int fpq_opt(int id, int dflt) { const int v = fpq_opt_raw(id); ret
 // A helper of fpq_kernels.hip that fpq_gemm.hip's fused fc1 epilogue needs too (internal to the library, not exported):
 // the "any NaN => the whole result is zero" fix-up launch.
 extern "C" __attribute__((visibility("hidden"))) int fpq_internal_zero_if_flag(void* out, int64_t n_bytes, void* scratch, void* stream);
+// ... and one the GEMMs' squared-error tail needs (fpq_gemm_fp4.h, GemmSqErr): sqerr_finish_kernel on one plane - one workgroup,
+// *out = the n_partials fp32 partials added in its fixed order (none: 0)
+extern "C" __attribute__((visibility("hidden"))) int fpq_internal_sqerr_finish(const float* partials, int n_partials, float* out, void* stream);
 
 namespace {
 

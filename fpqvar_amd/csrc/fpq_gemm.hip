@@ -73,7 +73,12 @@ int launch_fp4_staged(const GemmCall& c, int w_scale_dtype) {
 template <typename Tsa, typename Tsw, int MT, int FA, int FB, typename XE>
 int launch_fp6(const GemmCall& c, XE xe) {
   using Cfg = GemmFp6Cfg<MT, 4>;
-  if constexpr (FA == 2 && FB == 2)
+  if constexpr (__is_same(XE, GemmSqErr)) {   // the squared-error tail: one name for all four pairs, the same scale dtypes per pair
+    if constexpr ((FA == 2 && FB == 2) || __is_same(Tsa, _Float16))
+      return gemm_launch(gemm_f6_rows_sqerr_kernel<Tsa, Tsw, MT, 4, XE, FA, FB>, Cfg::BM, Cfg::BN, 256, Cfg::lds(), c, xe);
+    else
+      return FPQ_ERR_DTYPE;
+  } else if constexpr (FA == 2 && FB == 2)
     return gemm_launch(gemm_fp6_rows_kernel<Tsa, Tsw, MT, 4, XE>, Cfg::BM, Cfg::BN, 256, Cfg::lds(), c, xe);
   else if constexpr (__is_same(Tsa, _Float16))
     return gemm_launch(gemm_fp6_rows_bf6_kernel<Tsa, Tsw, MT, 4, XE, FA, FB>, Cfg::BM, Cfg::BN, 256, Cfg::lds(), c, xe);
@@ -82,13 +87,15 @@ int launch_fp6(const GemmCall& c, XE xe) {
 }
 // ... from the runtime scale dtypes, operand formats (FPQ_E2M3 / FPQ_E3M2 per side) and epilogue of a call
 template <int MT>
-int dispatch_fp6(const GemmCall& c, int a_scale_dtype, int w_scale_dtype, int a_table, int w_table, bool split, const GemmQkNorm* qkn) {
+int dispatch_fp6(const GemmCall& c, int a_scale_dtype, int w_scale_dtype, int a_table, int w_table, bool split, const GemmQkNorm* qkn,
+                 const GemmSqErr* sqx = nullptr) {
   return with_dtype(a_scale_dtype, [&](auto ta) {
     return with_dtype(w_scale_dtype, [&](auto tw) {
       auto formats = [&](auto fa, auto fb) {
         using Ta = decltype(ta);
         using Tw = decltype(tw);
         constexpr int FA = decltype(fa)::value, FB = decltype(fb)::value;
+        if (sqx) return launch_fp6<Ta, Tw, MT, FA, FB>(c, *sqx);
         if (qkn) return launch_fp6<Ta, Tw, MT, FA, FB>(c, *qkn);
         if (split) return launch_fp6<Ta, Tw, MT, FA, FB>(c, GemmSplit{});
         return launch_fp6<Ta, Tw, MT, FA, FB>(c, GemmNoFc1{});
@@ -252,7 +259,9 @@ int fpq_gate_residual(const void* y, const void* gate, const void* residual, voi
 static int gemm_fp4_mx_impl(const uint8_t* a_codes, const void* a_scales, const uint8_t* w_codes, const void* w_scales,
                             int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
                             const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream, const fpq_gemm_split_t* split = nullptr,
-                            const GemmQkNorm* qkn = nullptr) {
+                            const GemmQkNorm* qkn = nullptr, const GemmSqErrCall* sq = nullptr) {
+  // sq: the squared-error form (include/fpq.h, fpq_gemm_fp4_sqerr; row-major, no epilogue, no split): `out` is not looked at, the
+  // form's own checks follow the family's, the LDS-DMA kernels only (as km / split), then the finish launch
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   GemmEpi epi;
   if (int rc = gemm_epilogue(epilogue, &epi)) return rc;
@@ -270,9 +279,14 @@ static int gemm_fp4_mx_impl(const uint8_t* a_codes, const void* a_scales, const 
   }
   if (w_scale_dtype != FPQ_F16 && w_scale_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
   if (k % 128 != 0 || k > 128 * 64 || outs % 8 != 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF) return FPQ_ERR_SHAPE;
-  if (tokens == 0 || outs == 0) return FPQ_OK;
-  if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
-  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)out) & 15) != 0) return FPQ_ERR_ARG;
+  GemmSqErr sqx{};
+  if (tokens == 0 || outs == 0) {
+    if (!sq) return FPQ_OK;
+    if (int rc = gemm_sqerr_args(*sq, true, &sqx)) return rc;
+    return gemm_sqerr_finish(*sq, 0, 0, 64, stream);
+  }
+  if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || (!sq && !out)) return FPQ_ERR_ARG;
+  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (sq ? 0 : (uintptr_t)out)) & 15) != 0) return FPQ_ERR_ARG;
   const int G = (int)(k / 128);
   // The LDS-DMA kernel in the tiling gemm_fp4_plan chooses; the register-staged kernel when no LDS image fits (very long K),
   // when the bias is not 8-byte aligned (the LDS-DMA kernels read it four outputs at a time), or when FPQ_GEMM_CFG names
@@ -280,7 +294,8 @@ static int gemm_fp4_mx_impl(const uint8_t* a_codes, const void* a_scales, const 
   // and writes one tensor.
   int cfg = gemm_fp4_plan(tokens, outs, G, -1);
   if (cfg == kTileDoesNotFit) cfg = 0;
-  if (km || split) {
+  if (cfg == 40 && sq) cfg = 30;   // the ring has no squared-error form: its tile behind the two-stage ring (the same bits)
+  if (km || split || sq) {
     if (((uintptr_t)bias & 7) != 0 || outs + 63 > 0x7FFFFFFF) return FPQ_ERR_ARG;
   } else if (((uintptr_t)bias & 7) != 0) {
     cfg = 0;
@@ -288,17 +303,23 @@ static int gemm_fp4_mx_impl(const uint8_t* a_codes, const void* a_scales, const 
     const int want = fpq_opt(OPT_FPQ_GEMM_CFG, 0);
     if (want != 10 && want != 20 && want != 30 && want != 40) cfg = want;   // (a forced LDS-DMA tiling is in the plan already)
   }
+  if (sq)
+    if (int rc = gemm_sqerr_args(*sq, false, &sqx)) return rc;
   const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
   auto glds = [&](auto mt) {
     constexpr int MT = decltype(mt)::value;
     const size_t lds = GemmGldsCfg<MT, 4>::lds(G);
+    if (sq) {
+      if (int rc = launch_fp4_glds<MT>(c, w_scale_dtype, lds, sqx)) return rc;   // (kTileDoesNotFit: gemm_fp4_plan has ruled it out)
+      return gemm_sqerr_finish(*sq, tokens, outs, GemmGldsCfg<MT, 4>::BM, stream);
+    }
     return qkn ? launch_fp4_glds<MT>(c, w_scale_dtype, lds, *qkn) : launch_fp4_glds<MT>(c, w_scale_dtype, lds, GemmNoFc1{});
   };
   if (cfg == 40) return qkn ? launch_fp4_ring(c, w_scale_dtype, GemmRingCfg::lds(G), *qkn) : launch_fp4_ring(c, w_scale_dtype, GemmRingCfg::lds(G), GemmNoFc1{});
   if (cfg == 30) return glds(Int<2>{});   // 64 x 128 tiles
   if (cfg == 10) return glds(Int<8>{});
   if (cfg == 20) return glds(Int<4>{});
-  if (km || split) return FPQ_ERR_SHAPE;   // K too long for the LDS-DMA kernel's scale tiles
+  if (km || split || sq) return FPQ_ERR_SHAPE;   // K too long for the LDS-DMA kernel's scale tiles
   if (cfg == 1) return launch_fp4_staged<2, 4, 4, 2>(c, w_scale_dtype);
   if (cfg == 2) return launch_fp4_staged<4, 4, 2, 4>(c, w_scale_dtype);
   return launch_fp4_staged<4, 4, 2, 2>(c, w_scale_dtype);
@@ -322,6 +343,17 @@ int fpq_gemm_fp4_mx_split_qknorm(const uint8_t* a_codes, const void* a_scales, c
   if (int rc = gemm_qknorm(split, bias, q_head_scale, &qkn)) return rc;
   return gemm_fp4_mx_impl(a_codes, a_scales, w_codes, w_scales, w_scale_dtype, nullptr, nullptr, tokens, outs, k, nullptr, kmajor != 0, stream,
                           split, &qkn);
+}
+int64_t fpq_gemm_sqerr_workspace_bytes(int64_t tokens, int64_t outs) {
+  if (tokens < 0 || outs < 0 || tokens > 0x7FFFFFFF || outs > 0x7FFFFFFF) return FPQ_ERR_ARG;
+  return gemm_sqerr_workspace_bytes(tokens, outs);
+}
+int fpq_gemm_fp4_sqerr(const uint8_t* a_codes, const void* a_scales, const uint8_t* w_codes, const void* w_scales, int w_scale_dtype,
+                       const void* bias, const void* ref, int ref_dtype, const float* row_weight, float* loss_out, void* workspace,
+                       int64_t tokens, int64_t outs, int64_t k, fpq_stream_t stream) {
+  const GemmSqErrCall sq{ref, ref_dtype, row_weight, loss_out, workspace};
+  return gemm_fp4_mx_impl(a_codes, a_scales, w_codes, w_scales, w_scale_dtype, bias, nullptr, tokens, outs, k, nullptr, false, stream,
+                          nullptr, nullptr, &sq);
 }
 int fpq_gemm_fp4_mx_km(const uint8_t* a_image, const void* a_scales, const uint8_t* w_image, const void* w_scales,
                        int w_scale_dtype, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
@@ -405,7 +437,9 @@ static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int 
                               const void* w_scales, int w_scale_dtype, const void* bias, void* out, int64_t tokens,
                               int64_t outs, int64_t k, const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream,
                               const fpq_gemm_split_t* split = nullptr, const GemmQkNorm* qkn = nullptr,
-                              int a_table = FPQ_E2M3, int w_table = FPQ_E2M3) {
+                              int a_table = FPQ_E2M3, int w_table = FPQ_E2M3, const GemmSqErrCall* sq = nullptr) {
+  // sq: the squared-error form (include/fpq.h, fpq_gemm_f6_rows_sqerr; row-major, no epilogue, no split): `out` is not looked at,
+  // the form's own checks follow the family's, then the finish launch
   // a_table / w_table: FPQ_E2M3 or FPQ_E3M2 (checked by the fpq_gemm_f6_* entry points)
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   GemmEpi epi;
@@ -423,9 +457,14 @@ static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int 
     return FPQ_ERR_DTYPE;
   // a pair with an E3M2 side exists for fp16 activation scales only (fp16 or fp32 weight scales; launch_fp6)
   if ((a_table == FPQ_E3M2 || w_table == FPQ_E3M2) && a_scale_dtype != FPQ_F16) return FPQ_ERR_DTYPE;
-  if (tokens == 0 || outs == 0) return FPQ_OK;
-  if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
-  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (split ? 0 : (uintptr_t)out)) & 15) != 0) return FPQ_ERR_ARG;
+  GemmSqErr sqx{};
+  if (tokens == 0 || outs == 0) {
+    if (!sq) return FPQ_OK;
+    if (int rc = gemm_sqerr_args(*sq, true, &sqx)) return rc;
+    return gemm_sqerr_finish(*sq, 0, 0, 128, stream);
+  }
+  if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || (!sq && !out)) return FPQ_ERR_ARG;
+  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (split || sq ? 0 : (uintptr_t)out)) & 15) != 0) return FPQ_ERR_ARG;
   // the LDS-DMA pieces address a tile by a 32-bit lane offset (row inside the tile x row bytes + chunk): the 256-row tile's
   // last row must stay below 2^32 (k above ~22 M would wrap and read wrong rows silently)
   if (255 * (k * 3 / 4) + 128 >= (1ll << 32)) return FPQ_ERR_SHAPE;
@@ -433,6 +472,13 @@ static int gemm_fp6_rows_impl(const uint8_t* a_codes, const void* a_scales, int 
   // 256 x 128 tiles from 4096 tokens on for the wide Linears, from 32768 on for outs < 4096 (tools/gemm_small_steps.py fp6)
   const int cfg6 = fpq_opt_set(OPT_FPQ_GEMM6_CFG) ? fpq_opt(OPT_FPQ_GEMM6_CFG, 0) : (tokens >= 4096 && (outs >= 4096 || tokens >= 32768) ? 1 : 0);
   const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
+  if (sq) {
+    if (int rc = gemm_sqerr_args(*sq, false, &sqx)) return rc;
+    if (int rc = cfg6 == 1 ? dispatch_fp6<8>(c, a_scale_dtype, w_scale_dtype, a_table, w_table, false, nullptr, &sqx)
+                           : dispatch_fp6<4>(c, a_scale_dtype, w_scale_dtype, a_table, w_table, false, nullptr, &sqx))
+      return rc;
+    return gemm_sqerr_finish(*sq, tokens, outs, cfg6 == 1 ? 256 : 128, stream);
+  }
   if (cfg6 == 1) return dispatch_fp6<8>(c, a_scale_dtype, w_scale_dtype, a_table, w_table, split != nullptr, qkn);
   return dispatch_fp6<4>(c, a_scale_dtype, w_scale_dtype, a_table, w_table, split != nullptr, qkn);
 }
@@ -472,6 +518,15 @@ int fpq_gemm_f6_rows(const uint8_t* a_codes, const void* a_scales, int a_scale_d
   if (!f6_table(a_table) || !f6_table(w_table)) return FPQ_ERR_TABLE;
   return gemm_fp6_rows_impl(a_codes, a_scales, a_scale_dtype, w_codes, w_scales, w_scale_dtype, bias, out, tokens, outs, k, epilogue,
                             kmajor != 0, stream, nullptr, nullptr, a_table, w_table);
+}
+int fpq_gemm_f6_rows_sqerr(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, int a_table, const uint8_t* w_codes,
+                           const void* w_scales, int w_scale_dtype, int w_table, const void* bias, const void* ref, int ref_dtype,
+                           const float* row_weight, float* loss_out, void* workspace, int64_t tokens, int64_t outs, int64_t k,
+                           fpq_stream_t stream) {
+  if (!f6_table(a_table) || !f6_table(w_table)) return FPQ_ERR_TABLE;
+  const GemmSqErrCall sq{ref, ref_dtype, row_weight, loss_out, workspace};
+  return gemm_fp6_rows_impl(a_codes, a_scales, a_scale_dtype, w_codes, w_scales, w_scale_dtype, bias, nullptr, tokens, outs, k, nullptr,
+                            false, stream, nullptr, nullptr, a_table, w_table, &sq);
 }
 int fpq_gemm_f6_rows_split(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, int a_table, const uint8_t* w_codes,
                            const void* w_scales, int w_scale_dtype, int w_table, const void* bias, int64_t tokens, int64_t outs, int64_t k,

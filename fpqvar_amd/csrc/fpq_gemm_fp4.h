@@ -764,6 +764,91 @@ FPQ_NOPK __device__ __forceinline__ uint32_t quant_pair16_dual(uint32_t wk, cons
     }                                                                                                               \
   } while (0)
 
+// ---------------------------------------------------------------------------------------------------
+// THE SQUARED-ERROR TAIL (include/fpq.h, fpq_gemm_*_sqerr; the format search's loss): the register epilogues' y16 - bit for bit
+// what the plain form stores - is not stored; the workgroup leaves ONE fp32,
+//     partial[tile] = sum over the tile's rows t < T of  w[t] * sum over its outputs o < O of (f32(ref[t, o]) - f32(y16[t, o]))^2,
+// and a second launch (sqerr_finish_kernel, fpq_kernels.hip) adds the tiles' partials in a fixed order.  No atomics, no memset:
+// every partial the finish reads was written by this launch, so the workspace's old content never shows.
+// Written once for the per-group kernels (FPQ_GEMM_SQERR_EPILOGUE: gemm_fp4_glds_kernel<.., GemmSqErr>, gemm_a6w4_sqerr_kernel,
+// gemm_w6_sqerr_kernel) and the row-scaled one (FPQ_GEMM_ROWS_EPILOGUE_SQERR, fpq_gemm_fp8.h: gemm_f6_rows_sqerr_kernel).
+// The additions a term passes through, in order (tests/gemm_sqerr_model.py restates them; include/fpq.h carries the bound):
+//     4 in the lane's four outputs of a row (s += e e, the first to 0), 4 MT over the lane's rows (acc += w s, the first to 0),
+//     6 in the wavefront's butterfly (lane ^ 32 .. lane ^ 1: both partners add the same pair), 3 over the four wavefronts; in
+//     the finish ceil(tiles / 256) in a lane, 6 and 3 again:   D = 4 MT + ceil(tiles / 256) + 22,
+// and c = 3 roundings besides them (the difference, the square, the weight).  No fused multiply-add (-ffp-contract=off).
+// Edges: a row t >= T or a column group o >= O holds a clamped duplicate (perhaps non-finite) - it is SELECTED away, never
+// multiplied by zero.  The ref / weight loads are unconditional on clamped addresses, as the stores' neighbours above are, and
+// stand behind the main loop: a load the compiler sees in the prologue puts vmcnt waits into the loop.
+struct GemmSqErr {
+  const void* ref;        // [T, O] fp16 or fp32 (ref_f32), 16-byte aligned
+  const float* row_w;     // fp32 [T]
+  float* partials;        // one fp32 per tile: index row_blk * n_col + col_blk of the launch's tiling
+  int ref_f32;
+};
+
+// rows tc_[0..3] (t_first_ + i clamped to T - 1), outputs oc_ .. oc_ + 3 (o_ clamped to O - 4) of y_ = fpq_h4_t[4] into se_acc.
+// Names from the kernel: xe (GemmSqErr), T, O.
+#define FPQ_GEMM_SQERR_ROWS(y_, t_first_, tc_, o_, oc_)                                                             \
+  do {                                                                                                              \
+    float rw_[4], rf_[4][4];                                                                                        \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) rw_[i_] = xe.row_w[(tc_)[i_]];                                 \
+    if (xe.ref_f32) {   /* uniform */                                                                               \
+      v4f_t r32_[4];                                                                                                \
+      _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) r32_[i_] = *(const v4f_t*)((const float*)xe.ref + (int64_t)(tc_)[i_] * O + (oc_)); \
+      _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                              \
+        _Pragma("unroll") for (int n_ = 0; n_ < 4; ++n_) rf_[i_][n_] = r32_[i_][n_];                                \
+    } else {                                                                                                        \
+      fpq_h4_t r16_[4];                                                                                             \
+      _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) r16_[i_] = *(const fpq_h4_t*)((const _Float16*)xe.ref + (int64_t)(tc_)[i_] * O + (oc_)); \
+      _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                              \
+        _Pragma("unroll") for (int n_ = 0; n_ < 4; ++n_) rf_[i_][n_] = (float)r16_[i_][n_];                         \
+    }                                                                                                               \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                              \
+      float s_ = 0.0f;                                                                                              \
+      _Pragma("unroll") for (int n_ = 0; n_ < 4; ++n_) {                                                            \
+        const float e_ = rf_[i_][n_] - (float)(y_)[i_][n_];                                                         \
+        s_ += e_ * e_;                                                                                              \
+      }                                                                                                             \
+      const float ws_ = rw_[i_] * s_;                                                                               \
+      se_acc += ((t_first_) + i_ < T && (o_) < O) ? ws_ : 0.0f;                                                     \
+    }                                                                                                               \
+  } while (0)
+// se_acc over the wavefront (the butterfly of lanes_sum64, fpq_kernels.hip, spelled with the builtin: __shfl_xor is a header
+// function without the kernels' target attribute - it would become a call), the four wavefronts in order through scratch_ (16
+// bytes of LDS nobody reads any more: the stage buffer the last K group did not use), one store per workgroup.
+// Names from the kernel: xe, lane, wave, tid, row_blk, col_blk, n_col.
+#define FPQ_GEMM_SQERR_FINISH(scratch_)                                                                             \
+  do {                                                                                                              \
+    float v_ = se_acc;                                                                                              \
+    _Pragma("unroll") for (int m_ = 32; m_ >= 1; m_ >>= 1)                                                          \
+      v_ += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ m_) << 2, __builtin_bit_cast(int, v_))); \
+    float* xw_ = (float*)(scratch_);                                                                                \
+    if (lane == 0) xw_[wave] = v_;                                                                                  \
+    FPQ_SYNC();                                                                                                     \
+    if (tid == 0) {                                                                                                 \
+      float s_ = xw_[0];                                                                                            \
+      _Pragma("unroll") for (int i_ = 1; i_ < 4; ++i_) s_ += xw_[i_];                                               \
+      xe.partials[row_blk * n_col + col_blk] = s_;                                                                  \
+    }                                                                                                               \
+  } while (0)
+// the per-group kernels' epilogue with this tail: y as FPQ_GEMM_REG_EPILOGUE's plain branch rounds it.  Names as there.
+#define FPQ_GEMM_SQERR_EPILOGUE(scratch_)                                                                           \
+  do {                                                                                                              \
+    FPQ_GEMM_BIAS_F32();                                                                                            \
+    float se_acc = 0.0f;                                                                                            \
+    _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                                \
+      const int t_first = t0 + wm * WROWS + m * 16 + 4 * (lane >> 4);                                               \
+      fpq_h4_t y[4];                                                                                                \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                 \
+        _Pragma("unroll") for (int n = 0; n < NT; ++n) y[i][n] = (_Float16)(acc[m][n][i] + b4[n]);                  \
+      int tc[4];                                                                                                    \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) tc[i] = t_first + i < T ? t_first + i : T - 1;                  \
+      FPQ_GEMM_SQERR_ROWS(y, t_first, tc, o, oc);                                                                   \
+    }                                                                                                               \
+    FPQ_GEMM_SQERR_FINISH(scratch_);                                                                                \
+  } while (0)
+
 // What the two FP4 kernels below (nibbles on both sides, row-major or k-major at run time) share beyond that.
 // _SOURCES: the LDS-DMA sources of a wavefront's pieces (block = wave + 4 * i of the stage), group 0.
 // The weight rows are DEALT over a wavefront's NT = 4 blocks (round 4): row q of block n holds output 4*q + n of the
@@ -818,7 +903,7 @@ FPQ_NOPK __device__ __forceinline__ uint32_t quant_pair16_dual(uint32_t wk, cons
 // port twice as long (tools/probe/valu_mfma_overlap.hip); with the feature off the compiler emits scalar
 // v_mul_f32 / v_fma_f32 and schedules them - and the MFMA hazard wait states - itself.
 // XE = GemmNoFc1: the plain Linear (+ gate / residual tail); XE = GemmFc1: the fc1 tail above; XE = GemmQkNorm: the split
-// output with the q / k norm above.
+// output with the q / k norm above; XE = GemmSqErr: the squared-error tail above (row-major operands, no output tensor).
 template <typename Tsw, int MT, int NT, typename XE = GemmNoFc1>
 __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4_glds_kernel(const uint8_t* __restrict__ A,
                                                               const _Float16* __restrict__ sa,
@@ -878,6 +963,10 @@ __global__ __launch_bounds__(256, (MT * NT > 16 ? 2 : 3)) FPQ_NOPK void gemm_fp4
   }
   if constexpr (FC1) {
     FPQ_GEMM_FC1_TAIL(STAGE);
+    return;
+  }
+  if constexpr (__is_same(XE, GemmSqErr)) {   // the loss against xe.ref instead of the output; buffer G & 1: the fc1 tail's idle one
+    FPQ_GEMM_SQERR_EPILOGUE(smem + (G & 1) * STAGE);
     return;
   }
   FPQ_GEMM_REG_EPILOGUE(QKN, true, epi.sp_cols);   // (this epilogue serves the one-tensor output too)

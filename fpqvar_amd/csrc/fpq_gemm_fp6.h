@@ -67,6 +67,17 @@ struct GemmSplit {};
 #undef FPQ_GEMM6_KERNEL
 #undef FPQ_GEMM6_FA
 #undef FPQ_GEMM6_FB
+// the squared-error tail (XE = GemmSqErr only; include/fpq.h, fpq_gemm_f6_rows_sqerr), any format pair: a name of its own, so
+// that the two above keep exactly the instantiations they had
+#define FPQ_GEMM6_TEMPLATE template <typename Tsa, typename Tsw, int MT, int NT, typename XE, int FA, int FB>
+#define FPQ_GEMM6_KERNEL gemm_f6_rows_sqerr_kernel
+#define FPQ_GEMM6_FA FA
+#define FPQ_GEMM6_FB FB
+#include "fpq_gemm_fp6_kernel.h"
+#undef FPQ_GEMM6_TEMPLATE
+#undef FPQ_GEMM6_KERNEL
+#undef FPQ_GEMM6_FA
+#undef FPQ_GEMM6_FB
 
 template <int MT, int NT>
 struct GemmFp6Cfg {

@@ -9,7 +9,8 @@
 // inlined function did not: profiles/r08_bf6_isa.txt)
 //
 // XE = GemmNoFc1: the plain epilogue (+ gate / residual tail); XE = GemmSplit: the split output (GemmEpi's sp_* fields);
-// XE = GemmQkNorm: the split output with the q / k norm (fpq_gemm_fp4.h), as in gemm_fp4_glds_kernel.
+// XE = GemmQkNorm: the split output with the q / k norm (fpq_gemm_fp4.h), as in gemm_fp4_glds_kernel; XE = GemmSqErr: the
+// squared-error tail (fpq_gemm_fp4.h) - compiled under a third name, gemm_f6_rows_sqerr_kernel, for all four format pairs.
 FPQ_GEMM6_TEMPLATE
 __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_GEMM6_KERNEL(const uint8_t* __restrict__ A,
                                                                    const Tsa* __restrict__ sa,
@@ -140,7 +141,9 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_GEMM6_KERNEL(const uint8_
   }
 #undef FPQ_GLDS6_ISSUE
 #undef FPQ_GLDS6_ONE
-  if constexpr (SPLIT || QKN) {
+  if constexpr (__is_same(XE, GemmSqErr)) {   // scratch: the stage buffer the last K step did not read
+    FPQ_GEMM_ROWS_EPILOGUE_SQERR(smem + (steps & 1) * STAGE);
+  } else if constexpr (SPLIT || QKN) {
     FPQ_GEMM_ROWS_EPILOGUE_SPLIT(QKN, qkn_b, qkn_s);
   } else {
     FPQ_GEMM_ROWS_EPILOGUE();

@@ -96,6 +96,30 @@
     }                                                                                                          \
   } while (0)
 
+// The SQUARED-ERROR TAIL of the row-scaled GEMMs (fpq_gemm_fp4.h, GemmSqErr): FPQ_GEMM_ROWS_EPILOGUE's y16, lanes and rounding,
+// no gate / residual, no store - the tile's weighted squared error against xe.ref instead (FPQ_GEMM_SQERR_ROWS / _FINISH).
+#define FPQ_GEMM_ROWS_EPILOGUE_SQERR(scratch_)                                                                      \
+  do {                                                                                                              \
+    static_assert(NT == 4, "a lane's NT results of one row are four consecutive outputs");                         \
+    constexpr int WROWS_ = 16 * MT, WCOLS_ = 16 * NT;                                                               \
+    const int o_ = o0 + wn * WCOLS_ + NT * (lane & 15);                                                             \
+    const int oc_ = o_ < O ? o_ : O - 4;                                                                            \
+    const v4f_t sc_ = *(const v4f_t*)(lsc + wn * WCOLS_ + NT * (lane & 15));                                        \
+    const v4f_t b_ = *(const v4f_t*)(lsb + wn * WCOLS_ + NT * (lane & 15));                                         \
+    float se_acc = 0.0f;                                                                                            \
+    _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                                \
+      const int t_first_ = t0 + wm * WROWS_ + m * 16 + 4 * (lane >> 4);                                             \
+      int tc_[4];                                                                                                   \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) tc_[i] = t_first_ + i < T ? t_first_ + i : T - 1;               \
+      const v4f_t sr_ = *(const v4f_t*)(lsr + wm * WROWS_ + m * 16 + 4 * (lane >> 4));                              \
+      fpq_h4_t y_[4];                                                                                               \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                 \
+          _Pragma("unroll") for (int n = 0; n < 4; ++n) y_[i][n] = (_Float16)(acc[m][n][i] * (sr_[i] * sc_[n]) + b_[n]); \
+      FPQ_GEMM_SQERR_ROWS(y_, t_first_, tc_, o_, oc_);                                                              \
+    }                                                                                                               \
+    FPQ_GEMM_SQERR_FINISH(scratch_);                                                                                \
+  } while (0)
+
 FPQ_NOPK __device__ __forceinline__ int fp8_chunk_swz(int r) { return ((r >> 1) & 1) + ((r >> 3) << 2); }
 
 template <typename Tsa, typename Tsw, int MT, int NT>

@@ -31,6 +31,9 @@
 //   gemm_*_split_kernel  mat_qkv's split output (include/fpq.h, fpq_gemm_*_mx_split): the plain epilogue's values to the parts' own
 //                        destinations;
 //   gemm_*_qkn_kernel    the split output with the q / k L2 norm in front (fpq_gemm_*_mx_split_qknorm).
+// A sixth form on row-major operands only, counted apart (8 A6W4 kernels, 12 W6 ones):
+//   gemm_*_sqerr_kernel  no output tensor: the format search's loss of the plain form's values against a reference
+//                        (fpq_gemm_*_sqerr; the squared-error tail of fpq_gemm_fp4.h).
 // Only the register epilogue and the extra kernel argument differ between the forms.  launch_g6 (fpq_gemm_g6.hip) instantiates
 // them per (FA, FW, MT) for fp32 weight scales - what quantize_mx, quantize_g6 and the Linears hold, and what the images take
 // anyway - and the row-major A6W4 plain, fc1 and fc1x kernels for fp16 ones too: 52 A6W4 kernels and 120 W6 ones, none above
@@ -55,6 +58,10 @@
 #define FPQ_G6_W4 1
 #define FPQ_G6_KERNEL gemm_a6w4_qkn_kernel
 #define FPQ_G6_OUT 2
+#include "fpq_gemm_g6_kernel.h"
+#define FPQ_G6_W4 1
+#define FPQ_G6_KERNEL gemm_a6w4_sqerr_kernel
+#define FPQ_G6_OUT 3
 #include "fpq_gemm_g6_kernel.h"
 #define FPQ_G6_W4 1
 #define FPQ_G6_KM 1
@@ -95,6 +102,9 @@
 #include "fpq_gemm_g6_kernel.h"
 #define FPQ_G6_KERNEL gemm_w6_qkn_kernel
 #define FPQ_G6_OUT 2
+#include "fpq_gemm_g6_kernel.h"
+#define FPQ_G6_KERNEL gemm_w6_sqerr_kernel
+#define FPQ_G6_OUT 3
 #include "fpq_gemm_g6_kernel.h"
 #define FPQ_G6_KM 1
 #define FPQ_G6_KERNEL gemm_w6_km_kernel

@@ -2,7 +2,8 @@
 // against E2M1 weights, and "W6", E1M2 / E3M0 weights against E2M1, E1M2 or E3M0 activations.  One translation unit of
 // libfpq_hip.so, beside fpq_gemm.hip: 172 kernels of one text (52 A6W4, 120 W6: formats x two tilings, in five forms - plain, fc1
 // tail, its NaN-excluding twin, split output, split output with the q / k norm - each on row-major operands and on k-major
-// images) that compile while fpq_gemm.hip and fpq_adaln.hip, the build's longest unit, do.
+// images) that compile while fpq_gemm.hip and fpq_adaln.hip, the build's longest unit, do - and, counted apart, the 20 kernels of
+// the squared-error form (8 A6W4, 12 W6; row-major only).
 #include "fpq_common.h"
 
 namespace {
@@ -41,7 +42,7 @@ int launch_g6(const GemmCall& c, int a_table, int w_table, int w_scale_dtype, si
     if constexpr (__is_same(XE, GemmFc1X)) {
       const GemmFc1& x1 = xe;
       return gemm_launch(kernel, Cfg::BM, Cfg::BN, 256, lds, c, x1);
-    } else if constexpr (__is_same(XE, GemmFc1) || __is_same(XE, GemmQkNorm)) {
+    } else if constexpr (__is_same(XE, GemmFc1) || __is_same(XE, GemmQkNorm) || __is_same(XE, GemmSqErr)) {
       return gemm_launch(kernel, Cfg::BM, Cfg::BN, 256, lds, c, xe);
     } else {
       return gemm_launch(kernel, Cfg::BM, Cfg::BN, 256, lds, c);
@@ -60,7 +61,10 @@ int launch_g6(const GemmCall& c, int a_table, int w_table, int w_scale_dtype, si
       if (km) return go(a6w4_km_<float, MT, 4, FA>);             \
     return go(a6w4_<Tw, MT, 4, FA>);                             \
   }
-    if constexpr (__is_same(XE, GemmFc1)) {
+    if constexpr (__is_same(XE, GemmSqErr)) {   // row-major only (km is refused by the caller: there is no such entry point)
+      if constexpr (FW != 4) return go(gemm_w6_sqerr_kernel<float, MT, 4, FA, FW>);
+      else return go(gemm_a6w4_sqerr_kernel<Tw, MT, 4, FA>);
+    } else if constexpr (__is_same(XE, GemmFc1)) {
       FPQ_G6_PICK(gemm_a6w4_fc1_kernel, gemm_a6w4_fc1_km_kernel, gemm_w6_fc1_kernel, gemm_w6_fc1_km_kernel)
     } else if constexpr (__is_same(XE, GemmFc1X)) {
       FPQ_G6_PICK(gemm_a6w4_fc1x_kernel, gemm_a6w4_fc1x_km_kernel, gemm_w6_fc1x_kernel, gemm_w6_fc1x_km_kernel)
@@ -107,7 +111,9 @@ bool g6_w_scale_dtype(int w_scale_dtype, bool f16_form) { return w_scale_dtype =
 int gemm_g6_mx_impl(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
                     int w_scale_dtype, int w_table, bool a6w4, const void* bias, void* out, int64_t tokens, int64_t outs, int64_t k,
                     const fpq_gemm_epilogue_t* epilogue, bool km, fpq_stream_t stream, const fpq_gemm_split_t* split = nullptr,
-                    const GemmQkNorm* qkn = nullptr) {
+                    const GemmQkNorm* qkn = nullptr, const GemmSqErrCall* sq = nullptr) {
+  // sq: the squared-error form (include/fpq.h, fpq_gemm_a6w4_sqerr / fpq_gemm_w6_sqerr; row-major, no epilogue, no split): `out` is
+  // not looked at, the form's own checks follow the family's, then the finish launch
   if (!g6_tables(a_table, w_table, a6w4)) return FPQ_ERR_TABLE;
   if (tokens < 0 || outs < 0 || k < 0) return FPQ_ERR_ARG;
   GemmEpi epi;
@@ -125,15 +131,26 @@ int gemm_g6_mx_impl(const uint8_t* a_codes, const void* a_scales, int a_table, c
       (!a6w4 && GemmG6Cfg<4, 4>::lds(G, 96, w_seg) > 160 * 1024))
     return FPQ_ERR_SHAPE;
   if (km && !g6_km_sizes(tokens, outs)) return FPQ_ERR_SHAPE;
-  if (tokens == 0 || outs == 0) return FPQ_OK;
-  if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || !out) return FPQ_ERR_ARG;
-  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (split ? 0 : (uintptr_t)out)) & 15) != 0 || ((uintptr_t)bias & 7) != 0) return FPQ_ERR_ARG;
+  GemmSqErr sqx{};
+  if (tokens == 0 || outs == 0) {
+    if (!sq) return FPQ_OK;
+    if (int rc = gemm_sqerr_args(*sq, true, &sqx)) return rc;
+    return gemm_sqerr_finish(*sq, 0, 0, 64, stream);
+  }
+  if (k == 0 || !a_codes || !a_scales || !w_codes || !w_scales || (!sq && !out)) return FPQ_ERR_ARG;
+  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (split || sq ? 0 : (uintptr_t)out)) & 15) != 0 || ((uintptr_t)bias & 7) != 0) return FPQ_ERR_ARG;
   if (!g6_scales_aligned(a_scales, w_scales, w_scale_dtype, km)) return FPQ_ERR_ARG;
+  if (sq)
+    if (int rc = gemm_sqerr_args(*sq, false, &sqx)) return rc;
   if (km) epi.km_w_rows = (int)((outs + 63) / 64 * 64);   // (split: outs = n_parts * part_cols, part_cols % 128 == 0 - exactly outs)
   const GemmCall c{a_codes, a_scales, w_codes, w_scales, bias, out, tokens, outs, k, epi, (hipStream_t)stream};
   auto tile = [&](auto mt) {
     constexpr int MT = decltype(mt)::value;
     const size_t lds = GemmG6Cfg<MT, 4>::lds(G, a_seg, w_seg);
+    if (sq) {
+      if (int rc = launch_g6<MT>(c, a_table, w_table, w_scale_dtype, lds, sqx, false)) return rc;
+      return gemm_sqerr_finish(*sq, tokens, outs, GemmG6Cfg<MT, 4>::BM, stream);
+    }
     if (qkn) return launch_g6<MT>(c, a_table, w_table, w_scale_dtype, lds, *qkn, km);
     if (split) return launch_g6<MT>(c, a_table, w_table, w_scale_dtype, lds, GemmSplit{}, km);
     return launch_g6<MT>(c, a_table, w_table, w_scale_dtype, lds, GemmNoFc1{}, km);
@@ -257,6 +274,23 @@ int fpq_gemm_a6w4_gelu_dual_pair(const uint8_t* a_codes, const void* a_scales, i
                                  void* nan_flag, int neg_table, int pos_table, int kmajor, fpq_stream_t stream) {
   return gemm_g6_gelu_dual_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, FPQ_E2M1, true, bias, out, gelu_out, tokens, outs,
                                 k, nan_flag, kmajor != 0, stream, neg_table, pos_table);
+}
+
+// the squared-error forms of the two families (include/fpq.h, "THE SQUARED-ERROR FORMS"): the plain row-major Linear's checks, no
+// output tensor, no epilogue
+int fpq_gemm_a6w4_sqerr(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                        int w_scale_dtype, const void* bias, const void* ref, int ref_dtype, const float* row_weight, float* loss_out,
+                        void* workspace, int64_t tokens, int64_t outs, int64_t k, fpq_stream_t stream) {
+  const GemmSqErrCall sq{ref, ref_dtype, row_weight, loss_out, workspace};
+  return gemm_g6_mx_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, FPQ_E2M1, true, bias, nullptr, tokens, outs, k, nullptr,
+                         false, stream, nullptr, nullptr, &sq);
+}
+int fpq_gemm_w6_sqerr(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                      int w_scale_dtype, int w_table, const void* bias, const void* ref, int ref_dtype, const float* row_weight,
+                      float* loss_out, void* workspace, int64_t tokens, int64_t outs, int64_t k, fpq_stream_t stream) {
+  const GemmSqErrCall sq{ref, ref_dtype, row_weight, loss_out, workspace};
+  return gemm_g6_mx_impl(a_codes, a_scales, a_table, w_codes, w_scales, w_scale_dtype, w_table, false, bias, nullptr, tokens, outs, k, nullptr,
+                         false, stream, nullptr, nullptr, &sq);
 }
 
 // ---- W6 (include/fpq.h): a weight table; fp32 weight scales only; every form has a _km twin with the same argument list, no kmajor

@@ -8,7 +8,9 @@
 //   FPQ_G6_OUT      (FPQ_G6_FC1 == 0 only) 0: one [T, O] tensor; 1: the SPLIT OUTPUT of GemmEpi's sp_* fields (mat_qkv: q to its own
 //                   tensor, k and v into the KV cache's slots), the plain epilogue's values bit for bit, no gate / residual tail;
 //                   2: the split output with the Q / K L2 NORM in front of it (FPQ_QK_NORM_ROW, fpq_gemm_fp4.h) - the kernel takes a
-//                   GemmQkNorm behind the GemmEpi, its fp32 bias replaces the fp16 one
+//                   GemmQkNorm behind the GemmEpi, its fp32 bias replaces the fp16 one;
+//                   3: NO output - the SQUARED-ERROR TAIL (FPQ_GEMM_SQERR_EPILOGUE, fpq_gemm_fp4.h): the plain epilogue's values
+//                   against a reference, one fp32 partial per tile - the kernel takes a GemmSqErr behind the GemmEpi (row-major only)
 //   FPQ_G6_KM       0: row-major codes and scales (fp16 activation scales); 1: K-MAJOR IMAGES (include/fpq.h) - per side the 4-bit
 //                   image [G][rows][64] or the 6-bit image [G][rows][96], the weight's rows dealt and padded to epi.km_w_rows (outs
 //                   rounded up to 64), and sa / sw the fp32 scale images [G][T rounded up to 4] / [G][km_w_rows]: every piece of a
@@ -60,6 +62,8 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_G6_KERNEL(const uint8_t* 
                                                                  , GemmFc1 xe
 #elif FPQ_G6_OUT == 2
                                                                  , GemmQkNorm xe
+#elif FPQ_G6_OUT == 3
+                                                                 , GemmSqErr xe
 #endif
                                                                  ) {
 #if FPQ_G6_W4
@@ -238,6 +242,8 @@ __global__ __launch_bounds__(256, 2) FPQ_NOPK void FPQ_G6_KERNEL(const uint8_t* 
   FPQ_GEMM_FC1_TAIL_X(STAGE, true);   // the dual pair without a global clamp: a NaN stays out of the maxima
 #elif FPQ_G6_FC1
   FPQ_GEMM_FC1_TAIL(STAGE);
+#elif FPQ_G6_OUT == 3
+  FPQ_GEMM_SQERR_EPILOGUE(smem + (G & 1) * STAGE);   // (scratch: the idle stage buffer, as the fc1 tail's)
 #elif FPQ_G6_OUT
   FPQ_GEMM_REG_EPILOGUE(FPQ_G6_OUT == 2, false, true);   // (q / k norm, gate / residual tail, split output)
 #else

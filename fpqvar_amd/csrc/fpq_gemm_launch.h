@@ -82,6 +82,35 @@ int64_t gemm_grid(int64_t tokens, int64_t outs, int BM, int BN) {
   return n_wg > 0x7FFFFFFF ? (int64_t)FPQ_ERR_SHAPE : n_wg;
 }
 
+// ---- the squared-error forms (include/fpq.h, fpq_gemm_*_sqerr; fpq_gemm_fp4.h, GemmSqErr) -------------------------------------
+// the form's own arguments as its entry point received them
+struct GemmSqErrCall {
+  const void* ref;
+  int ref_dtype;
+  const float* row_weight;
+  float* loss_out;
+  void* workspace;
+};
+// one fp32 partial per tile of the smallest tiling any family launches (64 x 128), at least one
+int64_t gemm_sqerr_workspace_bytes(int64_t tokens, int64_t outs) {
+  const int64_t tiles = ((tokens + 63) / 64) * ((outs + 127) / 128);
+  return 4 * (tiles < 1 ? 1 : tiles);
+}
+// The form's checks, BEHIND the family's own: a NULL or misaligned pointer, then the reference's dtype.  An empty problem
+// (empty: tokens == 0 or outs == 0) reads neither ref nor row_weight - their pointers are not looked at.
+int gemm_sqerr_args(const GemmSqErrCall& s, bool empty, GemmSqErr* xe) {
+  if (!s.loss_out || !s.workspace || (((uintptr_t)s.loss_out | (uintptr_t)s.workspace) & 3) != 0) return FPQ_ERR_ARG;
+  if (!empty && (!s.ref || !s.row_weight || (((uintptr_t)s.ref | (uintptr_t)s.row_weight) & 15) != 0)) return FPQ_ERR_ARG;
+  if (s.ref_dtype != FPQ_F16 && s.ref_dtype != FPQ_F32) return FPQ_ERR_DTYPE;
+  *xe = GemmSqErr{s.ref, s.row_weight, (float*)s.workspace, s.ref_dtype == FPQ_F32 ? 1 : 0};
+  return FPQ_OK;
+}
+// the second launch: the partials of the BM x 128 tiles the first one wrote (an empty problem: none, and 0.0f is stored)
+int gemm_sqerr_finish(const GemmSqErrCall& s, int64_t tokens, int64_t outs, int BM, fpq_stream_t stream) {
+  const int64_t tiles = ((tokens + BM - 1) / BM) * ((outs + 127) / 128);   // <= the launch's grid, which fits 31 bits
+  return fpq_internal_sqerr_finish((const float*)s.workspace, (int)tiles, s.loss_out, stream);
+}
+
 // the arguments every GEMM kernel takes, as the entry point received (and checked) them
 struct GemmCall {
   const uint8_t* a_codes;

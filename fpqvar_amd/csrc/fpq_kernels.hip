@@ -1278,6 +1278,9 @@ int fpq_version(void) { return FPQ_VERSION; }
 int fpq_internal_zero_if_flag(void* out, int64_t n_bytes, void* scratch, void* stream) {
   return zero_if_flag(out, n_bytes, scratch, (hipStream_t)stream);
 }
+int fpq_internal_sqerr_finish(const float* partials, int n_partials, float* out, void* stream) {
+  return launch(sqerr_finish_kernel, 1, 0, (hipStream_t)stream, partials, n_partials, 1, out);
+}
 
 int fpq_set_option(const char* name, int value) {
   const int i = option_index(name);

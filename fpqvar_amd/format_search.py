@@ -83,10 +83,69 @@ def _search_layer_fused(xs: Sequence[torch.Tensor], w: torch.Tensor, formats: Se
         ops.sqerr_rows_weighted(ref, y, w_row, out=losses_out[i])
 
 
+def _mc_operand(fmt: str, t: torch.Tensor, weight: bool):
+    """A search format's matrix-core operand of t [rows, C] - the codes and scales the deployed Linears multiply:
+      fp_e2                  quantize_mx: E2M1 nibbles, a scale per group of 128
+      fp_e1 / fp_e3          quantize_g6: dense 6-bit codes of the E1M2 / E3M0 levels, a scale per group
+      fp6_e2m3 / fp6_e3m2    quantize_fp6(table=): dense 6-bit codes, a scale per token / per output channel
+    Every operand is quantized in its own dtype, as the search's fake-quantizers see it, so both forms of the search judge the
+    same codes - except an fp_e1 / fp_e3 WEIGHT, which is quantized from its fp32 copy as FP4Linear.from_float(weight_fp_type=)
+    builds it: the W6 GEMM takes fp32 group scales only.  For an fp32 weight that is the same thing; for an fp16 weight the
+    scales are not rounded to fp16, a few level decisions near a midpoint fall the other way, and at a small layer that alone
+    moves a loss by up to 1.5e-3 relative (tests/test_gpu_format_search_mc.py; 5e-5 at a d30 mat_qkv layer)."""
+    from . import gemm
+    if fmt == "fp_e2":
+        return gemm.quantize_mx(t)
+    if fmt in ("fp_e1", "fp_e3"):
+        return gemm.quantize_g6(t.float() if weight else t, fmt)
+    return gemm.quantize_fp6(t, table=fmt)
+
+
+def _mc_loss(wf: str, af: str, w_op, a_op, ref: torch.Tensor, w_row: torch.Tensor, out: torch.Tensor) -> None:
+    """One GEMM-with-loss call of the pair's family (gemm.linear_*_sqerr) into the one-element view `out`"""
+    from . import gemm
+    if wf in FP6_FORMATS:                                   # (the pair is FP6 x FP6: _search_layer_mc has checked it)
+        gemm.linear_fp6_sqerr(*a_op, *w_op, ref, w_row, out=out, a_table=af, w_table=wf)
+    elif wf != "fp_e2":
+        gemm.linear_w6_sqerr(*a_op, af, *w_op, wf, ref, w_row, out=out)
+    elif af != "fp_e2":
+        gemm.linear_a6w4_sqerr(*a_op, af, *w_op, ref, w_row, out=out)
+    else:
+        gemm.linear_fp4_sqerr(*a_op, *w_op, ref, w_row, out=out)
+
+
+def _search_layer_mc(xs: Sequence[torch.Tensor], w: torch.Tensor, formats: Sequence[str], losses_out: torch.Tensor) -> None:
+    """The fused form with every candidate product on the matrix cores and its loss in that GEMM's epilogue: activations
+    quantized to operand codes once per activation format, the weight once per weight format, the reference product one torch
+    GEMM in w's dtype as in _search_layer_fused, then ONE call per pair into losses_out[i, j] - no candidate product is written
+    to memory, nothing is read back."""
+    per_group = all(f in FP4_FORMATS for f in formats)
+    if not per_group and not all(f in FP6_FORMATS for f in formats):
+        raise RuntimeError(f"search_layer(matrix_cores=True) takes the FP4 formats {FP4_FORMATS} or the FP6 formats {FP6_FORMATS}, "
+                           f"not a mix and nothing else, got {tuple(formats)}")
+    if any(x.dtype != torch.float16 for x in xs):
+        raise RuntimeError("search_layer(matrix_cores=True) requires float16 activations (the GEMMs' activation scales are float16)")
+    c, outs = w.shape[-1], w.shape[0]
+    if c % 128 != 0:
+        raise RuntimeError(f"search_layer(matrix_cores=True) requires K % 128 == 0 (the matrix instruction's K step), got K = {c}")
+    if outs % 8 != 0:
+        raise RuntimeError(f"search_layer(matrix_cores=True) requires outs % 8 == 0, got {outs}")
+    rows = [x.numel() // c for x in xs]
+    x_all = torch.cat([x.reshape(-1, c) for x in xs])
+    w_row = _row_weights_on_device(rows, outs, w.device)
+    ref = x_all.to(w.dtype) @ w.t()
+    a_ops = [_mc_operand(af, x_all, False) for af in formats]
+    for i, wf in enumerate(formats):
+        w_op = _mc_operand(wf, w, True)
+        for j, af in enumerate(formats):
+            _mc_loss(wf, af, w_op, a_ops[j], ref, w_row, losses_out[i, j])
+
+
 @torch.no_grad()
 def search_layer(xs: Sequence[torch.Tensor], w: torch.Tensor, formats: Sequence[str] = FP6_FORMATS,
                  quant: Callable[[str], Callable] = quantizer, batched: Optional[bool] = None, fused: bool = False,
-                 losses_out: Optional[torch.Tensor] = None) -> Optional[Tuple[str, str, Dict[Tuple[str, str], float]]]:
+                 losses_out: Optional[torch.Tensor] = None,
+                 matrix_cores: bool = False) -> Optional[Tuple[str, str, Dict[Tuple[str, str], float]]]:
     """(best weight format, best activation format, {(w_fmt, a_fmt): summed MSE}).
 
     The reference walks the calibration samples one by one for every (w_fmt, a_fmt) pair: per sample one quantizer call
@@ -108,10 +167,24 @@ def search_layer(xs: Sequence[torch.Tensor], w: torch.Tensor, formats: Sequence[
     products stay in w's dtype and the five elementwise passes per pair become one ops.sqerr_rows_weighted pass per WEIGHT
     format (fpq_sqerr_rows_weighted: fp32 difference, square and sums in a fixed order).  With losses_out (a device
     [nf, nf] float32 tensor) the losses are left there, nothing is read back and None is returned; without it, one `.cpu()`
-    and the same triple as the other forms.  The default (fused=False) is unchanged."""
+    and the same triple as the other forms.  The default (fused=False) is unchanged.
+
+    matrix_cores=True (with fused=True; the built-in formats only - an injected `quant` is refused; float16 activations, K a
+    multiple of 128, outs a multiple of 8): every candidate product runs on the matrix-core GEMM the deployed model runs for that
+    pair - fp_e2 x fp_e2 on the FP4 GEMM, an fp_e1 / fp_e3 activation against fp_e2 weights on the A6W4 GEMM, fp_e1 / fp_e3
+    weights on the W6 GEMM, the FP6 pairs on the row-scaled FP6 GEMM - with the loss in that GEMM's epilogue
+    (gemm.linear_*_sqerr): operands quantized once per format, one call per pair, no candidate product written to memory.  The
+    search then judges a pair by the product the quantized model computes (exact products of the levels, fp32 accumulation, one
+    rounding to fp16) instead of an fp16 GEMM of fake-quantized tensors; the two agree to the search's tolerance between
+    evaluation orders, not bit for bit.  Off by default."""
     nf = len(formats)
     if batched is None:
         batched = quant is quantizer
+    if matrix_cores:
+        if not fused:
+            raise RuntimeError("search_layer: matrix_cores=True is a variant of the fused form (fused=True)")
+        if quant is not quantizer:
+            raise RuntimeError("search_layer(matrix_cores=True) runs the built-in formats' own operand quantizers: an injected `quant` is refused")
     if fused or losses_out is not None:
         if not fused:
             raise RuntimeError("search_layer: losses_out is an argument of the fused form (fused=True)")
@@ -126,7 +199,10 @@ def search_layer(xs: Sequence[torch.Tensor], w: torch.Tensor, formats: Sequence[
         out = losses_out if losses_out is not None else torch.empty(nf, nf, dtype=torch.float32, device=w.device)
         if out.shape != (nf, nf) or out.dtype != torch.float32 or out.device != w.device or not out.is_contiguous():
             raise RuntimeError(f"search_layer(fused=True): losses_out must be a contiguous float32 [{nf}, {nf}] tensor on the weight's device")
-        _search_layer_fused(xs, w, formats, quant, out)
+        if matrix_cores:
+            _search_layer_mc(xs, w, formats, out)
+        else:
+            _search_layer_fused(xs, w, formats, quant, out)
         if losses_out is not None:
             return None
         host = out.cpu()                                                               # the layer's one synchronisation
@@ -166,14 +242,14 @@ def search_layer(xs: Sequence[torch.Tensor], w: torch.Tensor, formats: Sequence[
 
 @torch.no_grad()
 def search_layers_fused(layers: Iterable[Tuple[Sequence[torch.Tensor], torch.Tensor]], formats: Sequence[str] = FP6_FORMATS,
-                        quant: Callable[[str], Callable] = quantizer) -> torch.Tensor:
+                        quant: Callable[[str], Callable] = quantizer, matrix_cores: bool = False) -> torch.Tensor:
     """search_layer(fused=True) over an iterable of (xs, w): float32 [L, nf, nf] on the device, nothing read back and no
-    synchronisation inside - the caller's one `.cpu()` serves every layer."""
+    synchronisation inside - the caller's one `.cpu()` serves every layer.  matrix_cores: as in search_layer."""
     nf = len(formats)
     tables = []
     for xs, w in layers:
         t = torch.empty(nf, nf, dtype=torch.float32, device=w.device)
-        search_layer(xs, w, formats, quant, batched=True, fused=True, losses_out=t)
+        search_layer(xs, w, formats, quant, batched=True, fused=True, losses_out=t, matrix_cores=matrix_cores)
         tables.append(t)
     if not tables:
         return torch.empty(0, nf, nf, dtype=torch.float32)
@@ -214,15 +290,15 @@ def search_blocks_sharded(n_blocks: int, evaluate: Callable[[int], Tuple[str, st
 
 
 def search_blocks_sharded_fused(n_blocks: int, layer_of: Callable[[int], Tuple[Sequence[torch.Tensor], torch.Tensor]],
-                                formats: Sequence[str] = FP6_FORMATS, group=None) -> List[Tuple[str, str, float]]:
+                                formats: Sequence[str] = FP6_FORMATS, group=None, matrix_cores: bool = False) -> List[Tuple[str, str, float]]:
     """search_blocks_sharded on the fused form: `layer_of(b)` returns block b's (xs, w); this rank's blocks (b % world ==
     rank) go through search_layers_fused, their losses are read back ONCE, the winners are picked on the host, and the
-    same all-gather of triples follows."""
+    same all-gather of triples follows.  matrix_cores: as in search_layer."""
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     per_rank = (n_blocks + world - 1) // world
     buf = torch.full((per_rank, 3), -1.0, dtype=torch.float32)
-    host = search_layers_fused((layer_of(b) for b in range(rank, n_blocks, world)), formats).cpu()
+    host = search_layers_fused((layer_of(b) for b in range(rank, n_blocks, world)), formats, matrix_cores=matrix_cores).cpu()
     for slot in range(host.shape[0]):
         wf, af = pick_winner(host[slot], formats)
         i, j = formats.index(wf), formats.index(af)

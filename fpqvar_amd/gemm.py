@@ -316,7 +316,7 @@ def _per_group_operands(name: str, fmt: _Format, a, a_scales, w, w_scales, bias,
 
 def _per_group_gemm(form: str, fmt: _Format, km: bool, a, a_scales, w, w_scales, *rest) -> None:
     """One call of the family's C entry point of `form`: "" (plain, with the optional gate / residual tail), "gelu_dual" (fc1),
-    "split" or "split_qknorm" (mat_qkv into the cache); rest: its arguments between the weight scales' dtype and the stream - or,
+    "split" or "split_qknorm" (mat_qkv into the cache), "sqerr" (the loss against a reference, row-major only); rest: its arguments between the weight scales' dtype and the stream - or,
     for the split forms, which take the layout as a flag, the k-major flag before it (the W6 family has no flag: its split forms
     have an entry point per layout too)."""
     if form in ("split", "split_qknorm"):
@@ -443,6 +443,76 @@ def _linear_qkv_to_cache(name: str, fmt, a, a_scales, w, w_scales, bias, cache_k
         _per_group_gemm("split" if hs is None else "split_qknorm", fmt, km, a, a_scales, w, w_scales, None if b is None else b.data_ptr(),
                         tokens, outs, k, ctypes.byref(sp), *norm)
     return q
+
+
+def sqerr_workspace_bytes(tokens: int, outs: int) -> int:
+    """bytes of device scratch a linear_*_sqerr call of these sizes needs (fpq_gemm_sqerr_workspace_bytes)"""
+    n = lib().fpq_gemm_sqerr_workspace_bytes(int(tokens), int(outs))
+    check(min(n, 0), "fpq_gemm_sqerr_workspace_bytes")
+    return n
+
+
+def _sqerr_args(name: str, tokens: int, outs: int, device, ref, row_weight, out, workspace):
+    """The squared-error forms' own arguments, checked behind the family's operands -> (ref pointer, its dtype id, weight pointer,
+    out, workspace).  The workspace is torch's (the caching allocator hands the same block back call after call, in stream order),
+    as ops.sqerr_rows_weighted's is, unless the caller passes one."""
+    if ref.dtype not in (torch.float16, torch.float32) or tuple(ref.shape) != (tokens, outs) or not ref.is_contiguous() or ref.device != device:
+        raise RuntimeError(f"{name}: ref must be a contiguous float16 / float32 [{tokens}, {outs}] tensor on {device}")
+    if row_weight.dtype != torch.float32 or row_weight.numel() != tokens or not row_weight.is_contiguous() or row_weight.device != device:
+        raise RuntimeError(f"{name}: row_weight must be a contiguous float32 tensor of {tokens} values on {device}")
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=device)
+    elif out.dtype != torch.float32 or out.numel() != 1 or out.device != device:
+        raise RuntimeError(f"{name}: out must be a float32 view of one element on {device}")
+    need = sqerr_workspace_bytes(tokens, outs)
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=device)
+    elif workspace.dtype != torch.float32 or workspace.numel() * 4 < need or not workspace.is_contiguous() or workspace.device != device:
+        raise RuntimeError(f"{name}: workspace must be a contiguous float32 tensor of at least {need // 4} elements on {device}")
+    return ref.data_ptr(), dtype_id(ref.dtype), row_weight.data_ptr(), out, workspace
+
+
+def _linear_sqerr(name: str, fmt, a, a_scales, w, w_scales, ref, row_weight, out, bias, workspace) -> torch.Tensor:
+    """The plain Linear's product with the loss against `ref` in the GEMM's epilogue and no output tensor: linear_fp4_sqerr,
+    linear_a6w4_sqerr, linear_w6_sqerr"""
+    require_gpu(a, name)
+    if not isinstance(fmt, _Format):
+        fmt = _g6_format(name, fmt)
+    dev = a.device
+    _, tokens, outs, k = _per_group_operands(name, fmt, a, a_scales, w, w_scales, bias, None, "rows")
+    b = _bias_f16(name, bias, outs, dev, fmt.bias_align)
+    pr, rdt, pw, out, ws = _sqerr_args(name, tokens, outs, dev, ref, row_weight, out, workspace)
+    _per_group_gemm("sqerr", fmt, False, a, a_scales, w, w_scales, None if b is None else b.data_ptr(), pr, rdt, pw, out.data_ptr(),
+                    ws.data_ptr(), tokens, outs, k)
+    return out
+
+
+def linear_fp4_sqerr(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor, ref: torch.Tensor,
+                     row_weight: torch.Tensor, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                     workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The format search's loss of a candidate pair, computed where its product is (fpq_gemm_fp4_sqerr): a one-element float32
+    tensor, sum_t row_weight[t] sum_o (ref[t, o] - y[t, o])^2 in fp32 with y = linear_fp4(a, w, bias) bit for bit - which is never
+    written.  Row-major operands; ref [tokens, outs] float16 or float32; row_weight float32 [tokens], finite and positive; out: a
+    float32 view of one element (an entry of a loss table), allocated when None; workspace: float32 scratch of
+    sqerr_workspace_bytes(tokens, outs), allocated when None.  Deterministic; no synchronisation."""
+    return _linear_sqerr("linear_fp4_sqerr", _FORMATS["e2m1"], a_codes, a_scales, w_codes, w_scales, ref, row_weight, out, bias, workspace)
+
+
+def linear_a6w4_sqerr(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor,
+                      ref: torch.Tensor, row_weight: torch.Tensor, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                      workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """linear_fp4_sqerr for a 6-bit activation against the E2M1 weight (fpq_gemm_a6w4_sqerr): the loss of y = linear_a6w4(a, a_table,
+    w, bias) against ref."""
+    return _linear_sqerr("linear_a6w4_sqerr", a_table, a_codes, a_scales, w_codes, w_scales, ref, row_weight, out, bias, workspace)
+
+
+def linear_w6_sqerr(a_codes: torch.Tensor, a_scales: torch.Tensor, a_table: str, w_codes: torch.Tensor, w_scales: torch.Tensor, w_table: str,
+                    ref: torch.Tensor, row_weight: torch.Tensor, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """linear_fp4_sqerr for a 6-bit WEIGHT (fpq_gemm_w6_sqerr): the loss of y = linear_w6(a, a_table, w, w_table, bias) against ref."""
+    require_gpu(a_codes, "linear_w6_sqerr")
+    fmt = _w6_format("linear_w6_sqerr", a_table, w_table, w_scales)
+    return _linear_sqerr("linear_w6_sqerr", fmt, a_codes, a_scales, w_codes, w_scales, ref, row_weight, out, bias, workspace)
 
 
 def linear_fp4(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor,
@@ -1273,6 +1343,29 @@ def linear_fp6(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Ten
     _fp6_gemm("", a_codes, a_scales, a_table, w_codes, w_scales, w_table, km, None if b is None else b.data_ptr(), out.data_ptr(),
               tokens, outs, k, ep)
     del keep
+    return out
+
+
+def linear_fp6_sqerr(a_codes: torch.Tensor, a_scales: torch.Tensor, w_codes: torch.Tensor, w_scales: torch.Tensor, ref: torch.Tensor,
+                     row_weight: torch.Tensor, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                     a_table: str = "e2m3", w_table: str = "e2m3", workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """linear_fp4_sqerr for the row-scaled 6-bit operands of linear_fp6 (fpq_gemm_f6_rows_sqerr): the loss of y = linear_fp6(a, w,
+    bias, a_table=, w_table=) against ref, y never written.  Row-major operands only."""
+    name = "linear_fp6_sqerr"
+    require_gpu(a_codes, name)
+    a_table, w_table = _f6_table(name, a_table), _f6_table(name, w_table)
+    if a_codes.dim() != 2 or w_codes.dim() != 2:
+        raise RuntimeError(f"{name}: row-major operands only")
+    if a_codes.shape[1] % 3 != 0:
+        raise RuntimeError(f"{name}: operand shapes mismatch")
+    _, tokens, outs, k = _fp6_operands(name, a_codes, a_scales, w_codes, w_scales)
+    b = _bias_f16(name, bias, None, a_codes.device)
+    pr, rdt, pw, out, ws = _sqerr_args(name, tokens, outs, a_codes.device, ref, row_weight, out, workspace)
+    args = (a_codes.data_ptr(), a_scales.data_ptr(), dtype_id(a_scales.dtype), TABLE_IDS[a_table], w_codes.data_ptr(), w_scales.data_ptr(),
+            dtype_id(w_scales.dtype), TABLE_IDS[w_table], None if b is None else b.data_ptr(), pr, rdt, pw, out.data_ptr(), ws.data_ptr(),
+            tokens, outs, k)
+    with device_guard(a_codes.device):
+        check(lib().fpq_gemm_f6_rows_sqerr(*args, stream_ptr(a_codes.device)), "fpq_gemm_f6_rows_sqerr")
     return out
 
 

@@ -1075,6 +1075,57 @@ int fpq_resid_adaln_rotate_quant_token_rows_codes_f6(const void* y, const void* 
                                                      float eps, const float* smooth, const uint32_t* sign_mask_host, int table_id,
                                                      int kmajor, fpq_stream_t stream);
 
+/* THE SQUARED-ERROR FORMS OF THE MATRIX-CORE GEMMS (the format search's loss, computed where the product is).  Each computes the
+ * product as its family's plain row-major entry point does - fpq_gemm_fp4_mx, fpq_gemm_a6w4_mx, fpq_gemm_w6_mx, fpq_gemm_f6_rows
+ * (kmajor = 0), no gate / residual tail - but writes no output tensor.  Its result is one float:
+ *     y16[t, o] = bit for bit what that entry point stores for the same operands and bias
+ *     *loss_out = sum_t row_weight[t] * sum_o ( f32(ref[t, o]) - f32(y16[t, o]) )^2
+ * i.e. fpq_sqerr_rows_weighted(ref, y16, row_weight) with one plane, without y16's trip through memory.
+ * Arguments: the family's plain entry point up to `bias`, then
+ *   ref         [tokens, outs] contiguous, `ref_dtype` FPQ_F16 or FPQ_F32, 16-byte aligned
+ *   row_weight  float32 [tokens], FINITE AND POSITIVE, 16-byte aligned
+ *   loss_out    one float32, overwritten (not accumulated), 4-byte aligned
+ *   workspace   at least fpq_gemm_sqerr_workspace_bytes(tokens, outs) bytes of device scratch, 4-byte aligned: 4 bytes per
+ *               64 x 128 tile, the smallest tiling any family launches, and never less than 4 (a negative or > 2^31 - 1 size: FPQ_ERR_ARG)
+ *   tokens, outs, k, stream.
+ * The operands are row-major codes and scales; k-major images are not taken by these four.  Each launch uses the tiling the family's rule picks for the plain form
+ * (FPQ_GEMM_CFG 20 / 30, for the FP4 family 10 too, and FPQ_GEMM6_CFG force one as there); the FP4 family's deep ring (40) and its
+ * register-staged kernels have no such form: 40 runs the 64 x 128 tile (30, the same bits), and what only the register-staged
+ * kernel serves - a bias that is not 8-byte aligned (FPQ_ERR_ARG), a K whose scale tiles fit no LDS image (FPQ_ERR_SHAPE) - is refused.
+ * Two launches: the GEMM, whose workgroups leave one fp32 partial per tile (the differences, squares and sums in fp32, the
+ * wavefronts' butterfly, the four wavefronts in order), and one workgroup that adds the partials in a fixed order
+ * (fpq_sqerr_rows_weighted's second kernel).  No atomics, no memset: the same inputs give the same bits on every call whatever
+ * the workspace held; no host synchronisation, allocation or copy - legal inside a stream capture.
+ * Checks, before anything is enqueued: the family's own come first, in the family's order and with its codes (`out` is not
+ * among them); then loss_out or workspace NULL or not 4-byte aligned, ref or row_weight NULL or not 16-byte aligned
+ * (FPQ_ERR_ARG); then ref_dtype (FPQ_ERR_DTYPE).  tokens == 0 or outs == 0 - where the family returns FPQ_OK - stores 0.0f with
+ * one launch and returns FPQ_OK; ref and row_weight are not looked at then.
+ * Accuracy: every term is non-negative and every weight positive, so against the exact sum S of the stored ref, y16 and weights
+ *   |*loss_out - S| <= ((1 + 2^-24)^(D + c) - 1) S,    D = 4 MT + ceil(tiles / 256) + 22,  c = 3
+ * MT = the tile's rows / 32 (2, 4 or 8: a lane holds 4 MT rows), tiles = ceil(tokens / (32 MT)) ceil(outs / 128).  The chain: 4
+ * additions over a lane's four outputs of a row, 4 MT over its rows, 6 + 3 in the workgroup, ceil(tiles / 256) + 6 + 3 over the
+ * partials; c = the roundings of the difference, the square and the weight.  [13600 x 5760] at 128-row tiles: D + c = 60,
+ * 3.6e-6.  FPQ_F16 ref: nothing goes subnormal (the smallest non-zero difference squared is 2^-48), a zero loss is met exactly;
+ * FPQ_F32 ref adds at most 2^-149 per element and per row of a lane.
+ * Non-finite inputs behave as the fp32 expression does (fpq_sqerr_rows_weighted): the loss is NaN if any counted difference is
+ * NaN, otherwise +inf if any is infinite.  Rows t >= tokens and columns o >= outs of an edge tile are not counted, whatever the
+ * clamped duplicates in their place hold.
+ * Additions that change no existing entry point: FPQ_VERSION stays, a caller looks the symbols up. */
+int64_t fpq_gemm_sqerr_workspace_bytes(int64_t tokens, int64_t outs);
+int fpq_gemm_fp4_sqerr(const uint8_t* a_codes, const void* a_scales, const uint8_t* w_codes, const void* w_scales, int w_scale_dtype,
+                       const void* bias, const void* ref, int ref_dtype, const float* row_weight, float* loss_out, void* workspace,
+                       int64_t tokens, int64_t outs, int64_t k, fpq_stream_t stream);
+int fpq_gemm_a6w4_sqerr(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                        int w_scale_dtype, const void* bias, const void* ref, int ref_dtype, const float* row_weight, float* loss_out,
+                        void* workspace, int64_t tokens, int64_t outs, int64_t k, fpq_stream_t stream);
+int fpq_gemm_w6_sqerr(const uint8_t* a_codes, const void* a_scales, int a_table, const uint8_t* w_codes, const void* w_scales,
+                      int w_scale_dtype, int w_table, const void* bias, const void* ref, int ref_dtype, const float* row_weight,
+                      float* loss_out, void* workspace, int64_t tokens, int64_t outs, int64_t k, fpq_stream_t stream);
+int fpq_gemm_f6_rows_sqerr(const uint8_t* a_codes, const void* a_scales, int a_scale_dtype, int a_table, const uint8_t* w_codes,
+                           const void* w_scales, int w_scale_dtype, int w_table, const void* bias, const void* ref, int ref_dtype,
+                           const float* row_weight, float* loss_out, void* workspace, int64_t tokens, int64_t outs, int64_t k,
+                           fpq_stream_t stream);
+
 /* fpq_kv_cache_step_qknorm: fpq_kv_cache_step (same arguments, same checks) for an fp16 qkv WITHOUT the norm (path F, or a
  * mat_qkv that is not split): the new k is normalized and the bias added on its way into the cache, and the same launch writes
  * q_out - fp16 [batch, n_new, row_elems], contiguous - from new_q (the pitches of new_k).  head_dim == 64, row_elems % 64 == 0,
