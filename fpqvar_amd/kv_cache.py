@@ -15,6 +15,7 @@ import torch
 from . import ops, quant_utils as qu
 
 
+KV_TABLE = {6: "e2m3", 4: "e2m1"}   # the quantizer table of a kv_bit
 MAX_SCALE_MUL = math.log(100)   # SelfAttention.max_scale_mul (tr/basic_var.py:140), torch.log(torch.tensor(100)).item()
 
 
@@ -42,11 +43,8 @@ def quantize_kv_pair(k: torch.Tensor, v: torch.Tensor, kv_bit: int) -> Tuple[tor
         if kv_bit == 6:
             qu._require_viewable(k)
             qu._require_viewable(v)
-            a, b = ops.quant_rows_multi([k, v], "e2m3", k.shape[-1], torch.float16) if k.shape[-1] == v.shape[-1] else \
-                (quantize_kv(k, 6), quantize_kv(v, 6))
-        else:
-            a, b = ops.quant_rows_multi([k, v], "e2m1", 128)
-        return a, b
+        if kv_bit == 4 or k.shape[-1] == v.shape[-1]:
+            return tuple(ops.quant_rows_multi([k, v], KV_TABLE[kv_bit], k.shape[-1] if kv_bit == 6 else 128))
     return quantize_kv(k, kv_bit), quantize_kv(v, kv_bit)
 
 
@@ -83,13 +81,20 @@ class IncrementalKVCache:
     Layout: flash layout [B, L, H, c] (`dim_cat` = 1), as the reference's published KV runs use; with
     kv_bit 4 a 128-group then never straddles tokens as long as H*c is a multiple of 128.
     Buffers are allocated once for `max_len` tokens; `append` returns views of the filled prefix.
+
+    One step of a block, the protocol PackedKVCache shares (each returns the attention output, fp16 [B, L, H, c]):
+      slots(n)                                          (slab [2, B, *, H, c], first token): where a producer writes the step's k / v
+      attend(q, k, v, scale)                            fresh k / v handed over: `append`, then attention
+      attend_written(q, n, scale)                       k / v already sit in slots(n): `commit_written`, then attention
+      attend_qk_norm(q, k, v, head_scale, bias, scale)  the fused q / k norm on an fp16 qkv: `append_qk_norm`, then attention
+    `attention`: the function (q, K, V, scale) that attends; None: ops.attention_blhc, off the cache views.
     """
 
     def __init__(self, batch: int, max_len: int, heads: int, head_dim: int, kv_bit: int,
-                 dtype=torch.float16, device="cuda"):
+                 dtype=torch.float16, device="cuda", attention=None):
         assert kv_bit in (4, 6)
         assert kv_bit == 6 or (heads * head_dim) % 128 == 0
-        self.kv_bit = kv_bit
+        self.kv_bit, self._table, self._attention = kv_bit, KV_TABLE[kv_bit], attention
         self.kv = torch.empty(2, batch, max_len, heads, head_dim, dtype=dtype, device=device)   # K and V in one slab
         self.k, self.v = self.kv[0], self.kv[1]
         self.len = 0
@@ -104,14 +109,21 @@ class IncrementalKVCache:
         split output, gemm.linear_fp4_qkv_to_cache(..., cache.kv, cache.len, n)): quantizes the previous step's entries - one launch,
         nothing copied - and returns the same views."""
         assert self.len + n <= self.k.shape[1], "IncrementalKVCache: max_len exceeded"
-        if self.len > self._prev:
-            a, b = self._prev, self.len
-            if self._group is not None:
-                empty = self.kv[0, :, :0]
-                ops.kv_cache_step(self.kv, a, b, empty, empty, self.len, self._group, "e2m3" if self.kv_bit == 6 else "e2m1")
-            else:
-                self.k[:, a:b].copy_(quantize_kv(self.k[:, a:b].contiguous(), self.kv_bit))
-                self.v[:, a:b].copy_(quantize_kv(self.v[:, a:b].contiguous(), self.kv_bit))
+        if self._group is None:
+            self._quantize_previous()
+        elif self.len > self._prev:
+            empty = self.kv[0, :, :0]
+            ops.kv_cache_step(self.kv, self._prev, self.len, empty, empty, self.len, self._group, self._table)
+        return self._advance(n)
+
+    def _quantize_previous(self) -> None:
+        """Without the fused kernel: what the reference's quantize-the-cache does NEW work on, the previous step's entries."""
+        a, b = self._prev, self.len
+        if b > a:
+            self.k[:, a:b].copy_(quantize_kv(self.k[:, a:b].contiguous(), self.kv_bit))
+            self.v[:, a:b].copy_(quantize_kv(self.v[:, a:b].contiguous(), self.kv_bit))
+
+    def _advance(self, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
         self._prev = self.len
         self.len += n
         return self.k[:, :self.len], self.v[:, :self.len]
@@ -123,21 +135,13 @@ class IncrementalKVCache:
         quantized now, the new ones as they are - what the reference's quantize-then-concatenate produces."""
         n = k.shape[1]
         assert self.len + n <= self.k.shape[1], "IncrementalKVCache: max_len exceeded"
-        fused = (self._group is not None and k.dtype == torch.float16 and v.dtype == torch.float16
-                 and k.stride() == v.stride() and k.stride(3) == 1 and k.stride(2) == k.shape[3]
-                 and k.stride(0) % 8 == 0 and k.stride(1) % 8 == 0 and k.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0)
-        if fused:
-            ops.kv_cache_step(self.kv, self._prev, self.len, k, v, self.len, self._group, "e2m3" if self.kv_bit == 6 else "e2m1")
+        if self._group is not None and k.dtype == v.dtype == torch.float16 and ops.rows_viewable(k, v):
+            ops.kv_cache_step(self.kv, self._prev, self.len, k, v, self.len, self._group, self._table)
         else:
-            if self.len > self._prev:             # what the reference's quantize-the-cache does NEW work on
-                a, b = self._prev, self.len
-                self.k[:, a:b].copy_(quantize_kv(self.k[:, a:b].contiguous(), self.kv_bit))
-                self.v[:, a:b].copy_(quantize_kv(self.v[:, a:b].contiguous(), self.kv_bit))
+            self._quantize_previous()
             self.k[:, self.len:self.len + n].copy_(k)
             self.v[:, self.len:self.len + n].copy_(v)
-        self._prev = self.len
-        self.len += n
-        return self.k[:, :self.len], self.v[:, :self.len]
+        return self._advance(n)
 
     @torch.no_grad()
     def append_qk_norm(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, head_scale: torch.Tensor,
@@ -150,14 +154,26 @@ class IncrementalKVCache:
         assert self.len + n <= self.k.shape[1], "IncrementalKVCache: max_len exceeded"
         if self._group not in (64, 128) or self.k.shape[-1] != 64:
             raise RuntimeError("IncrementalKVCache.append_qk_norm: needs an fp16 cache with head_dim 64 (kv_bit 6 or 4)")
-        if not (q.stride() == k.stride() == v.stride()) or k.stride(3) != 1 or k.stride(2) != k.shape[3] or k.stride(0) % 8 or k.stride(1) % 8 \
-                or q.data_ptr() % 16 or k.data_ptr() % 16 or v.data_ptr() % 16:
+        if not ops.rows_viewable(q, k, v):
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        qn = ops.kv_cache_step_qk_norm(self.kv, self._prev, self.len, q, k, v, self.len, self._group,
-                                       "e2m3" if self.kv_bit == 6 else "e2m1", head_scale, bias)
-        self._prev = self.len
-        self.len += n
-        return qn, self.k[:, :self.len], self.v[:, :self.len]
+        qn = ops.kv_cache_step_qk_norm(self.kv, self._prev, self.len, q, k, v, self.len, self._group, self._table, head_scale, bias)
+        return (qn, *self._advance(n))
+
+    def slots(self, n: int) -> Tuple[torch.Tensor, int]:
+        assert self.len + n <= self.k.shape[1], "IncrementalKVCache: max_len exceeded"
+        return self.kv, self.len
+
+    def _attend(self, q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, scale: float) -> torch.Tensor:
+        return (self._attention or ops.attention_blhc)(q, K, V, scale)
+
+    def attend(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float) -> torch.Tensor:
+        return self._attend(q, *self.append(k, v), scale)
+
+    def attend_written(self, q: torch.Tensor, n: int, scale: float) -> torch.Tensor:
+        return self._attend(q, *self.commit_written(n), scale)
+
+    def attend_qk_norm(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, head_scale: torch.Tensor, bias: Optional[torch.Tensor], scale: float):
+        return self._attend(*self.append_qk_norm(q, k, v, head_scale, bias), scale)
 
 
 def _e2m3_levels() -> torch.Tensor:
@@ -189,6 +205,9 @@ class PackedKVCache:
     `staging`: an fp16 [2, B, max_step, H, 64] slab that producers write a step's k / v into (gemm.linear_fp4_qkv_to_cache(...,
     staging, 0, L); `stage_qk_norm`) before `attend_staged` - one slab serves every block's cache, since a block's fresh entries
     are packed before the next block runs (new_staging).
+
+    The step protocol is IncrementalKVCache's: `slots(n)` = (staging, 0), `attend`, `attend_written` = `attend_staged`,
+    `attend_qk_norm` = `stage_qk_norm` + `attend_staged`.
     """
 
     def __init__(self, batch: int, max_len: int, heads: int, head_dim: int = 64, kv_bit: int = 6, device="cuda",
@@ -251,10 +270,18 @@ class PackedKVCache:
         k normalized and v (+ bias) land in the slab's first n tokens, q normalized and scaled comes back; `attend_staged` next."""
         if self.staging is None:
             raise RuntimeError("PackedKVCache: no staging slab (staging=)")
-        if not (q.stride() == k.stride() == v.stride()) or k.stride(3) != 1 or k.stride(2) != k.shape[3] or k.stride(0) % 8 or k.stride(1) % 8 \
-                or q.data_ptr() % 16 or k.data_ptr() % 16 or v.data_ptr() % 16:
+        if not ops.rows_viewable(q, k, v):
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         return ops.kv_cache_step_qk_norm(self.staging, 0, 0, q, k, v, 0, 64, "e2m3", head_scale, bias)
+
+    def slots(self, n: int) -> Tuple[torch.Tensor, int]:
+        self.staged(n)   # its refusals
+        return self.staging, 0
+
+    attend_written = attend_staged
+
+    def attend_qk_norm(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, head_scale: torch.Tensor, bias: Optional[torch.Tensor], scale: float):
+        return self.attend_staged(self.stage_qk_norm(q, k, v, head_scale, bias), k.shape[1], scale)
 
     @torch.no_grad()
     def dequantize(self) -> Tuple[torch.Tensor, torch.Tensor]:

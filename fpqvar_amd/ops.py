@@ -118,6 +118,14 @@ def gate_residual(y: torch.Tensor, gate: torch.Tensor, residual: torch.Tensor) -
     return out.view(y.shape)
 
 
+def rows_viewable(*ts: torch.Tensor) -> bool:
+    """Whether the C ABI takes fp16 [B, n, H, c] tensors as the views they are: contiguous (H, c) rows, batch and token pitches that
+    are multiples of 8, 16-byte aligned bases and - several tensors - shared strides.  Empty tensors pass: nothing of them is read."""
+    t = ts[0]
+    return t.numel() == 0 or (t.stride(3) == 1 and t.stride(2) == t.shape[3] and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0
+                              and all(u.stride() == t.stride() and u.data_ptr() % 16 == 0 for u in ts))
+
+
 def attention_blhc(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float) -> torch.Tensor:
     """fpq_attention_blhc: softmax(q k^T * scale) v for fp16 q [B, Lq, H, 64], k / v [B, Lkv, H, 64] (views with
     contiguous (H, 64) rows are taken as they are) -> [B, Lq, H, 64]; flash_attn_func(q, k, v, softmax_scale=scale)."""
@@ -132,12 +140,8 @@ def attention_blhc(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: flo
         raise RuntimeError("attention_blhc: head_dim must be 64")
     if Lkv == 0 and Lq > 0 and B > 0:
         raise RuntimeError("attention_blhc: no keys")
-
-    def rows_ok(t):
-        return t.shape[1] == 0 or t.shape[0] == 0 or (t.stride(3) == 1 and t.stride(2) == c and t.stride(0) % 8 == 0
-                                                      and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0)
-    q = q if rows_ok(q) else q.contiguous()
-    if not (rows_ok(k) and rows_ok(v) and k.stride() == v.stride()):
+    q = q if rows_viewable(q) else q.contiguous()
+    if not rows_viewable(k, v):
         k, v = k.contiguous(), v.contiguous()
     out = torch.empty((B, Lq, H, c), dtype=torch.float16, device=q.device)
     with device_guard(q.device):
@@ -165,18 +169,12 @@ def _kv_codes_layout(codes: torch.Tensor, scales: torch.Tensor, kv_bit: int, wha
 
 
 def _fresh_rows(k: torch.Tensor, v: torch.Tensor, B: int, H: int, what: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    """k / v [B, n, H, 64] fp16 as the C ABI takes them: views kept when their (H, 64) rows are contiguous, their strides shared,
-    pitches multiples of 8 and the base 16-byte aligned; copied otherwise."""
+    """k / v [B, n, H, 64] fp16 as the C ABI takes them: views kept when `rows_viewable`, copied otherwise."""
     if k.dtype != torch.float16 or v.dtype != torch.float16:
         raise RuntimeError(f"{what}: k and v must be float16")
     if k.dim() != 4 or k.shape != v.shape or k.shape[0] != B or tuple(k.shape[2:]) != (H, 64):
         raise RuntimeError(f"{what}: k / v must be [B, n, H, 64] = [{B}, n, {H}, 64], got {tuple(k.shape)} / {tuple(v.shape)}")
-
-    def rows_ok(t):
-        return t.stride(3) == 1 and t.stride(2) == 64 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
-    if k.shape[1] and not (rows_ok(k) and rows_ok(v) and k.stride() == v.stride()):
-        k, v = k.contiguous(), v.contiguous()
-    return k, v
+    return (k, v) if rows_viewable(k, v) else (k.contiguous(), v.contiguous())
 
 
 def kv_pack(codes: torch.Tensor, scales: torch.Tensor, kv_bit: int, pos: int, k: torch.Tensor, v: torch.Tensor) -> None:
@@ -214,8 +212,7 @@ def attention_blhc_kvcodes(q: torch.Tensor, codes: torch.Tensor, scales: torch.T
     Lq = q.shape[1]
     if n_packed + n == 0 and Lq > 0 and B > 0:
         raise RuntimeError("attention_blhc_kvcodes: no keys")
-    if Lq and not (q.stride(3) == 1 and q.stride(2) == 64 and q.stride(0) % 8 == 0 and q.stride(1) % 8 == 0 and q.data_ptr() % 16 == 0):
-        q = q.contiguous()
+    q = q if rows_viewable(q) else q.contiguous()
     out = torch.empty((B, Lq, H, 64), dtype=torch.float16, device=q.device)
     with device_guard(q.device):
         check(lib().fpq_attention_blhc_kvcodes(q.data_ptr(), codes.data_ptr(), scales.data_ptr(), kv_bit, max_len, n_packed,
@@ -226,21 +223,31 @@ def attention_blhc_kvcodes(q: torch.Tensor, codes: torch.Tensor, scales: torch.T
     return out
 
 
+def _kv_step_layout(name: str, cache: torch.Tensor, *qkv: torch.Tensor, head_dim: Optional[int] = None) -> Tuple[int, int, int, int, int]:
+    """The checks kv_cache_step ((k, v)) and kv_cache_step_qk_norm ((q, k, v)) share: (B, max_len, H, c, n) of the fp16 cache
+    [2, B, max_len, H, c] and the new [B, n, H, c] tensors."""
+    what = ("q", "k", "v")[-len(qkv):]
+    require_gpu(cache, name)
+    if cache.dtype != torch.float16 or any(t.dtype != torch.float16 for t in qkv):
+        raise RuntimeError(f"{name}: cache, {', '.join(what[:-1])} and v must be float16")
+    if cache.dim() != 5 or cache.shape[0] != 2 or not cache.is_contiguous():
+        raise RuntimeError(f"{name}: cache must be a contiguous [2, B, max_len, H, c] tensor")
+    _, B, max_len, H, c = cache.shape
+    if head_dim is not None and c != head_dim:
+        raise RuntimeError(f"{name}: head_dim must be {head_dim}, got {c}")
+    k = qkv[-1]
+    if any(t.shape != k.shape for t in qkv) or k.dim() != 4 or k.shape[0] != B or tuple(k.shape[2:]) != (H, c):
+        raise RuntimeError(f"{name}: {' / '.join(what)} must be [B, n, H, c] = [{B}, n, {H}, {c}], got {' / '.join(str(tuple(t.shape)) for t in qkv)}")
+    return B, max_len, H, c, k.shape[1]
+
+
 def kv_cache_step(cache: torch.Tensor, quant_start: int, quant_stop: int, k: torch.Tensor, v: torch.Tensor,
                   new_start: int, group: int, table: str) -> None:
     """fpq_kv_cache_step: quantize tokens [quant_start, quant_stop) of the fp16 cache [2, B, max_len, H, c] in place
     and copy the new k / v [B, n, H, c] (rows contiguous, any batch / token stride) to tokens new_start.."""
     if _native is not None:   # same checks, same C call, a third of the host time
         return _native.kv_cache_step(cache, quant_start, quant_stop, k, v, new_start, group, TABLE_IDS[table])
-    require_gpu(cache, "kv_cache_step")
-    if cache.dtype != torch.float16 or k.dtype != torch.float16 or v.dtype != torch.float16:
-        raise RuntimeError("kv_cache_step: cache, k and v must be float16")
-    if cache.dim() != 5 or cache.shape[0] != 2 or not cache.is_contiguous():
-        raise RuntimeError("kv_cache_step: cache must be a contiguous [2, B, max_len, H, c] tensor")
-    _, B, max_len, H, c = cache.shape
-    if k.shape != v.shape or k.dim() != 4 or k.shape[0] != B or tuple(k.shape[2:]) != (H, c):
-        raise RuntimeError(f"kv_cache_step: k / v must be [B, n, H, c] = [{B}, n, {H}, {c}], got {tuple(k.shape)} / {tuple(v.shape)}")
-    n = k.shape[1]
+    B, max_len, H, c, n = _kv_step_layout("kv_cache_step", cache, k, v)
     for t in (k, v):
         if n and (t.stride(3) != 1 or t.stride(2) != c):
             raise RuntimeError("kv_cache_step: the (H, c) rows of k / v must be contiguous")
@@ -261,17 +268,7 @@ def kv_cache_step_qk_norm(cache: torch.Tensor, quant_start: int, quant_stop: int
     v_bias) is added to the fp16 q, k, v first.  One launch."""
     if _native is not None:
         return _native.kv_cache_step_qk_norm(cache, quant_start, quant_stop, q, k, v, new_start, group, TABLE_IDS[table], head_scale, bias)
-    require_gpu(cache, "kv_cache_step_qk_norm")
-    if cache.dtype != torch.float16 or q.dtype != torch.float16 or k.dtype != torch.float16 or v.dtype != torch.float16:
-        raise RuntimeError("kv_cache_step_qk_norm: cache, q, k and v must be float16")
-    if cache.dim() != 5 or cache.shape[0] != 2 or not cache.is_contiguous():
-        raise RuntimeError("kv_cache_step_qk_norm: cache must be a contiguous [2, B, max_len, H, c] tensor")
-    _, B, max_len, H, c = cache.shape
-    if c != 64:
-        raise RuntimeError(f"kv_cache_step_qk_norm: head_dim must be 64, got {c}")
-    if not (q.shape == k.shape == v.shape) or k.dim() != 4 or k.shape[0] != B or tuple(k.shape[2:]) != (H, c):
-        raise RuntimeError(f"kv_cache_step_qk_norm: q / k / v must be [B, n, H, c] = [{B}, n, {H}, {c}], got {tuple(q.shape)} / {tuple(k.shape)} / {tuple(v.shape)}")
-    n = k.shape[1]
+    B, max_len, H, c, n = _kv_step_layout("kv_cache_step_qk_norm", cache, q, k, v, head_dim=64)
     if n and (k.stride(3) != 1 or k.stride(2) != c or not (q.stride() == k.stride() == v.stride())):
         raise RuntimeError("kv_cache_step_qk_norm: q, k and v must share their strides, with contiguous (H, c) rows")
     if head_scale.dtype != torch.float32 or head_scale.numel() != H or not head_scale.is_contiguous() or head_scale.device != cache.device:

@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import os
 import time
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -104,6 +105,48 @@ def _ref_dual(x, gneg, gpos, group=128, clip=True):
     return (qa.view(xs.shape) * sn + qb.view(xs.shape) * sp).view(shape).to(x.dtype)
 
 
+def _mx_weight(w, km):
+    c, sc = gemm.quantize_mx(w)
+    return (gemm.to_kmajor(c, 4, dealt=True), gemm.to_kmajor_scales(sc, weight_side=True)) if km else (c, sc)
+
+
+def _fp6_weight(w, km):
+    c, sc = gemm.quantize_fp6(w)
+    return (gemm.to_kmajor(c, 6, dealt=True), sc) if km else (c, sc)
+
+
+# What differs between the two runs, one row per config; a GenerationBatch picks its row once (`self.row`).  Every entry reaches
+# quant_utils / rotation / gemm through the module at call time.  r_*: (batch, t), the reference's op sequence (path R); the producers:
+# (x, scale, shift, sm=smooth[, km=kmajor]), their gated-residual forms with (y, gate) in front; linear_gelu_dual: fc1 with GELU and
+# fc2's quantizer in the GEMM epilogue, where the config has one.
+ROWS = {
+    "w4a4": SimpleNamespace(
+        r_act=lambda gb, t: _ref_sym(t, gb.e2m1, 128), r_fc2=lambda gb, t: _ref_dual(t, gb.gneg, gb.gpos),
+        act=lambda t: qu.fp_quant_e2_per_group_cuda(t, 4, 128),
+        fc2=lambda t: qu.fp_quant_e1m2_neg_e2m1_pos_per_group_cuda(t, 4, 128),
+        gelu_fc2=lambda y: qu.gelu_fp_quant_e1m2_neg_e2m1_pos_per_group_cuda(y, 4, 128),
+        values=lambda *a, sm: rot.adaln_rotate_quant(*a, "e2m1", smooth=sm),
+        operands=lambda *a, sm, km: rot.adaln_rotate_quant_mx(*a, smooth=sm, kmajor=km),
+        resid_values=lambda *a, sm: rot.resid_adaln_rotate_quant(*a, "e2m1", smooth=sm),
+        resid_operands=lambda *a, sm, km: rot.resid_adaln_rotate_quant_mx(*a, smooth=sm, kmajor=km),
+        quantize=lambda t, km: gemm.quantize_mx(t, kmajor=km), linear=lambda *a: gemm.linear_fp4(*a),
+        linear_split=lambda *a, **kw: gemm.linear_fp4_qkv_to_cache(*a, **kw), linear_gelu_dual=lambda *a: gemm.linear_fp4_gelu_dual(*a),
+        weight=lambda w: qu.fp_quant_e2_per_group_cuda(w, 4, 128).half(), weight_operands=_mx_weight),
+    "w6a6": SimpleNamespace(
+        r_act=lambda gb, t: _ref_sym(t, gb.e2m3, None, torch.float16), r_fc2=lambda gb, t: _ref_dual(t, gb.ineg, gb.e2m3p, None, clip=False),
+        act=lambda t: qu.fp6_quant_e2m3_per_token_cuda(t, 6),
+        fc2=lambda t: qu.fp6_quant_int_neg_e2m3_pos_per_token_cuda(t, 6),
+        gelu_fc2=lambda y: qu.gelu_fp6_quant_int_neg_e2m3_pos_per_token_cuda(y, 6),
+        values=lambda *a, sm: rot.adaln_rotate_quant_token(*a, "e2m3", smooth=sm),
+        operands=lambda *a, sm, km: rot.adaln_rotate_quant_token(*a, "e2m3", smooth=sm, emit="fp6", kmajor=km),
+        resid_values=lambda *a, sm: rot.resid_adaln_rotate_quant_token(*a, "e2m3", smooth=sm),
+        resid_operands=lambda *a, sm, km: rot.resid_adaln_rotate_quant_token(*a, "e2m3", smooth=sm, emit="fp6", kmajor=km),
+        quantize=lambda t, km: gemm.quantize_fp6(t, kmajor=km), linear=lambda *a: gemm.linear_fp6(*a),
+        linear_split=lambda *a, **kw: gemm.linear_fp6_qkv_to_cache(*a, **kw), linear_gelu_dual=None,
+        weight=lambda w: qu.fp6_quant_e2m3_per_token_cuda(w, 6), weight_operands=_fp6_weight),
+}
+
+
 class GenerationBatch:
     """Weights, modulation vectors and the step function of one model-shaped batch on `device`."""
 
@@ -126,8 +169,8 @@ class GenerationBatch:
         self.HID, self.B, self.depth = 4 * self.C, batch_rows or rows, depth or heads
         self.hd = self.C // self.H
         self.max_len = sum(p * p for p in self.patch_nums)
-        self.W6 = config == "w6a6"
-        self.fused_fc1 = fused_fc1 and not self.W6 and hasattr(gemm, "linear_fp4_gelu_dual")
+        self.W6, self.row = config == "w6a6", ROWS[config]
+        self.fused_fc1 = fused_fc1 and self.row.linear_gelu_dual is not None
         self.sdpa_in_f = sdpa_in_f                              # path F with torch's SDPA instead of fpq_attention_blhc (rounds 1 - 4 timed it that way)
         self.fused_gelu_quant = fused_fc1                       # path F: GELU + fc2's input quantizer in one pass over the fc1 output
         self.kmajor = kmajor                                    # path Q: operands as k-major images (include/fpq.h): contiguous LDS-DMA pieces
@@ -154,16 +197,8 @@ class GenerationBatch:
 
         w32 = {"qkv": lin_w(3 * C, C, self.s_qkv, True), "proj": lin_w(C, C), "fc1": lin_w(HID, C, self.s_fc1, True),
                "fc2": lin_w(C, HID)}
-        if self.W6:
-            self.wq = {n: qu.fp6_quant_e2m3_per_token_cuda(w, 6) for n, w in w32.items()}
-            self.wop = {n: gemm.quantize_fp6(w32[n]) for n in ("qkv", "proj", "fc1")}   # operands of the row-scaled GEMMs
-            if kmajor:
-                self.wop = {n: (gemm.to_kmajor(c, 6, dealt=True), sc) for n, (c, sc) in self.wop.items()}
-        else:
-            self.wq = {n: qu.fp_quant_e2_per_group_cuda(w, 4, 128).half() for n, w in w32.items()}
-            self.wop = {n: gemm.quantize_mx(w32[n]) for n in ("qkv", "proj", "fc1")}
-            if kmajor:
-                self.wop = {n: (gemm.to_kmajor(c, 4, dealt=True), gemm.to_kmajor_scales(sc, weight_side=True)) for n, (c, sc) in self.wop.items()}
+        self.wq = {n: self.row.weight(w) for n, w in w32.items()}
+        self.wop = {n: self.row.weight_operands(w32[n], kmajor) for n in ("qkv", "proj", "fc1")}   # operands of the matrix-core GEMMs
         del w32
         self.mods = [[(torch.randn(B, 1, C, device=dev, generator=g) * 0.2).half() for _ in range(6)] for _ in range(self.depth)]
         self.e2m1 = qu.fp4_e2m1_grid.to(dev)
@@ -187,76 +222,36 @@ class GenerationBatch:
             self.qkv_bias = [torch.cat((torch.randn(C, device=dev, generator=gn) * 0.1, torch.zeros(C, device=dev),
                                         torch.randn(C, device=dev, generator=gn) * 0.1)) for _ in range(self.depth)]
 
-    # ---- the quantizers of the three paths -------------------------------------------------------------------------
-    def r_act(self, t):       # activation quantizer of mat_qkv / proj / fc1, the reference's op sequence
-        return _ref_sym(t, self.e2m3, None, torch.float16) if self.W6 else _ref_sym(t, self.e2m1, 128)
-
-    def r_fc2(self, t):       # fc2's dual-format input quantizer, the reference's op sequence
-        if self.W6:
-            return _ref_dual(t, self.ineg, self.e2m3p, None, clip=False)
-        return _ref_dual(t, self.gneg, self.gpos)
-
-    def f_act(self, t):
-        return qu.fp6_quant_e2m3_per_token_cuda(t, 6) if self.W6 else qu.fp_quant_e2_per_group_cuda(t, 4, 128)
-
-    def f_fc2(self, t):
-        return qu.fp6_quant_int_neg_e2m3_pos_per_token_cuda(t, 6) if self.W6 else qu.fp_quant_e1m2_neg_e2m1_pos_per_group_cuda(t, 4, 128)
-
+    # ---- the quantizers and Linears of paths F and Q, through the config's row --------------------------------------------------
     def act_then_fc2_quant(self, y):
         """`fc2.act_quant(act(y))` for an fc1 output y: one pass (GELU in front of the dual quantizer) or GELU, then the quantizer."""
-        if not self.fused_gelu_quant:
-            return self.f_fc2(Fn.gelu(y, approximate="tanh"))
-        if self.W6:
-            return qu.gelu_fp6_quant_int_neg_e2m3_pos_per_token_cuda(y, 6)
-        return qu.gelu_fp_quant_e1m2_neg_e2m1_pos_per_group_cuda(y, 4, 128)
+        return self.row.gelu_fc2(y) if self.fused_gelu_quant else self.row.fc2(Fn.gelu(y, approximate="tanh"))
 
-    def f_producer(self, t, sc, sh, sm):
-        if self.W6:
-            return rot.adaln_rotate_quant_token(t, sc, sh, "e2m3", smooth=sm)
-        return rot.adaln_rotate_quant(t, sc, sh, "e2m1", smooth=sm)
+    def q_operands(self, t, sc, sh, sm):
+        return self.row.operands(t, sc, sh, sm=sm, km=self.kmajor)
 
     def resid_producer(self, path, pend, x, sc, sh, sm):
         """fuse_residual: the pending x + y.mul(gate), pend = (y, gate), and the producer behind it in one launch.  Returns
         (x_new, what the path's producer returns for x_new): path F - the quantized values, path Q - (codes, scales)."""
-        y, gate = pend
         if path == "F":
-            if self.W6:
-                return rot.resid_adaln_rotate_quant_token(y, gate, x, sc, sh, "e2m3", smooth=sm)
-            return rot.resid_adaln_rotate_quant(y, gate, x, sc, sh, "e2m1", smooth=sm)
-        if self.W6:
-            x_new, *operands = rot.resid_adaln_rotate_quant_token(y, gate, x, sc, sh, "e2m3", smooth=sm, emit="fp6", kmajor=self.kmajor)
-        else:
-            x_new, *operands = rot.resid_adaln_rotate_quant_mx(y, gate, x, sc, sh, smooth=sm, kmajor=self.kmajor)
+            return self.row.resid_values(*pend, x, sc, sh, sm=sm)
+        x_new, *operands = self.row.resid_operands(*pend, x, sc, sh, sm=sm, km=self.kmajor)
         return x_new, tuple(operands)
 
     def q_producer_linear(self, t, sc, sh, sm, name, operands=None):
         """operands: the producer's output when it has run already (fuse_residual)"""
-        if self.W6:
-            return gemm.linear_fp6(*(operands or rot.adaln_rotate_quant_token(t, sc, sh, "e2m3", smooth=sm, emit="fp6", kmajor=self.kmajor)),
-                                   *self.wop[name])
-        return gemm.linear_fp4(*(operands or rot.adaln_rotate_quant_mx(t, sc, sh, smooth=sm, kmajor=self.kmajor)), *self.wop[name])
+        return self.row.linear(*(operands or self.q_operands(t, sc, sh, sm)), *self.wop[name])
 
     def q_qkv_to_cache(self, x, sc1, sh1, b, cache_kv, pos, operands=None):
         """mat_qkv of block b with the split output: q [B, L, H, hd] comes back, k and v land in cache_kv at pos (with attn_l2_norm:
         normalized in the GEMM's epilogue)"""
         bias, hs = (self.qkv_bias[b], self.head_scale[b]) if self.attn_l2_norm else (None, None)
-        if self.W6:
-            q = gemm.linear_fp6_qkv_to_cache(*(operands or rot.adaln_rotate_quant_token(x, sc1, sh1, "e2m3", smooth=self.s_qkv, emit="fp6",
-                                                                                        kmajor=self.kmajor)),
-                                             *self.wop["qkv"], bias, cache_kv, pos, x.shape[1], qk_norm_scale=hs)
-        else:
-            q = gemm.linear_fp4_qkv_to_cache(*(operands or rot.adaln_rotate_quant_mx(x, sc1, sh1, smooth=self.s_qkv, kmajor=self.kmajor)), *self.wop["qkv"],
-                                             bias, cache_kv, pos, x.shape[1], qk_norm_scale=hs)
+        q = self.row.linear_split(*(operands or self.q_operands(x, sc1, sh1, self.s_qkv)), *self.wop["qkv"], bias, cache_kv, pos, x.shape[1],
+                                  qk_norm_scale=hs)
         return q.view(self.B, x.shape[1], self.H, self.hd)
 
     def q_proj(self, t2d, gate, resid):       # x + proj(a).mul(gamma1), gate and residual applied in the GEMM epilogue
-        if self.W6:
-            return gemm.linear_fp6(*gemm.quantize_fp6(t2d, kmajor=self.kmajor), *self.wop["proj"], None, gate, resid)
-        return gemm.linear_fp4(*gemm.quantize_mx(t2d, kmajor=self.kmajor), *self.wop["proj"], None, gate, resid)
-
-    def q_fc1_gelu_dual(self, t, sc, sh, operands=None):
-        """fc2's quantized input straight out of the fc1 GEMM: GELU(tanh) and the dual E1M2-/E2M1+ quantizer in its epilogue."""
-        return gemm.linear_fp4_gelu_dual(*(operands or rot.adaln_rotate_quant_mx(t, sc, sh, smooth=self.s_fc1, kmajor=self.kmajor)), *self.wop["fc1"])
+        return self.row.linear(*self.row.quantize(t2d, self.kmajor), *self.wop["proj"], None, gate, resid)
 
     def attend(self, q, kc, vc, scale=None):   # q [B,L,H,c]; kc, vc [B,Ltot,H,c] (flash layout, as the KV runs use)
         if scale is None and self.attn_l2_norm:
@@ -272,6 +267,7 @@ class GenerationBatch:
         return Fn.normalize(q, dim=-1).mul(scale_mul), Fn.normalize(k, dim=-1), v
 
     def new_caches(self, path):
+        """One cache per block; both classes offer the step protocol that `attention_half` runs against (kv_cache.py)."""
         if path == "R":
             if self.kv_storage == "codes":
                 raise ValueError("kv_storage='codes' runs on paths F and Q; path R is the reference's own cache loop")
@@ -279,31 +275,29 @@ class GenerationBatch:
         if self.kv_storage == "codes":   # one staging slab for the step's fresh k / v, shared by every block's cache
             staging = kv_cache.PackedKVCache.new_staging(self.B, max(p * p for p in self.patch_nums), self.H, self.hd, self.dev)
             return [kv_cache.PackedKVCache(self.B, self.max_len, self.H, self.hd, 6, self.dev, staging) for _ in range(self.depth)]
-        return [kv_cache.IncrementalKVCache(self.B, self.max_len, self.H, self.hd, 6, device=self.dev) for _ in range(self.depth)]
+        sdpa = (lambda q, k, v, scale: self.attend(q, k, v, scale).view(q.shape)) if path == "F" and self.sdpa_in_f else None
+        return [kv_cache.IncrementalKVCache(self.B, self.max_len, self.H, self.hd, 6, device=self.dev, attention=sdpa) for _ in range(self.depth)]
 
     def new_input(self, pn):
         return torch.randn(self.B, pn * pn, self.C, device=self.dev, generator=self.gen).half()
 
-    def attend_codes(self, path, cache, x, b, scale, prod=None):
-        """The attention half of block b with kv_storage="codes": the same producers as the fp16 cache's lines of `step`, k / v
-        handed to the PackedKVCache as views or through its staging slab; attention over the packed entries + the fresh k / v,
-        then their pack.  Returns [B, L, H, 64].  prod: the first producer's output when it has run already (fuse_residual)."""
+    def attention_half(self, path, cache, x, b, scale, prod=None):
+        """The attention half of block b against the cache's step protocol: mat_qkv writes k / v into the cache's slots (path Q with
+        the split output), or a plain mat_qkv and k / v handed over - as they are, through the fused q / k norm, or after the
+        reference's torch lines.  Returns [B, L, H, 64].  prod: the first producer's output when it has run already (fuse_residual)."""
         B, L, H, hd = self.B, x.shape[1], self.H, self.hd
         g1, g2, sc1, sc2, sh1, sh2 = self.mods[b]
         l2 = self.attn_l2_norm
         if path == "Q" and self.qkv_to_cache and not (l2 and self.qk_norm == "torch"):
-            return cache.attend_staged(self.q_qkv_to_cache(x, sc1, sh1, b, cache.staging, 0, prod), L, scale)
+            return cache.attend_written(self.q_qkv_to_cache(x, sc1, sh1, b, *cache.slots(L), prod), L, scale)
         if path == "F":
-            qkv = Fn.linear(self.f_producer(x, sc1, sh1, self.s_qkv) if prod is None else prod, self.wq["qkv"])
+            qkv = Fn.linear(self.row.values(x, sc1, sh1, sm=self.s_qkv) if prod is None else prod, self.wq["qkv"])
         else:
             qkv = self.q_producer_linear(x, sc1, sh1, self.s_qkv, "qkv", prod)
         if l2 and self.qk_norm == "torch":
-            q, k, v = (t.half() for t in self.qk_norm_torch(qkv.view(B, L, 3 * self.C), b))
-            return cache.attend(q, k, v, scale)
+            return cache.attend(*(t.half() for t in self.qk_norm_torch(qkv.view(B, L, 3 * self.C), b)), scale)
         q, k, v = qkv.view(B, L, 3, H, hd).unbind(2)
-        if l2:
-            return cache.attend_staged(cache.stage_qk_norm(q, k, v, self.head_scale[b], self.qkv_bias[b]), L, scale)
-        return cache.attend(q, k, v, scale)
+        return cache.attend_qk_norm(q, k, v, self.head_scale[b], self.qkv_bias[b], scale) if l2 else cache.attend(q, k, v, scale)
 
     # ---- one scale step: `depth` blocks over x [B, pn^2, C] ----------------------------------------------------------
     def step(self, path, caches, x):
@@ -316,9 +310,9 @@ class GenerationBatch:
                 with torch.autocast("cuda", dtype=torch.float16):
                     x1 = torch.matmul(Fn.layer_norm(x, (C,), eps=1e-6).mul(sc1.add(1)).add_(sh1).mul(self.s_qkv), self.q32)
                     if self.attn_l2_norm:                      # fp32 q, k, v (the fp32 bias promotes) and an fp32 cache, as the reference
-                        q, k, v = self.qk_norm_torch(Fn.linear(self.r_act(x1), self.wq["qkv"]), b)
+                        q, k, v = self.qk_norm_torch(Fn.linear(self.row.r_act(self, x1), self.wq["qkv"]), b)
                     else:
-                        q, k, v = Fn.linear(self.r_act(x1), self.wq["qkv"]).view(B, L, 3, H, hd).unbind(2)
+                        q, k, v = Fn.linear(self.row.r_act(self, x1), self.wq["qkv"]).view(B, L, 3, H, hd).unbind(2)
                     cache_dtype = None if self.attn_l2_norm else torch.float16
                     if caches[b] is None:
                         kc, vc = k, v
@@ -328,51 +322,30 @@ class GenerationBatch:
                         cv = _ref_sym(cv.contiguous(), self.e2m3, None, cache_dtype)
                         kc, vc = torch.cat((ck, k), dim=1), torch.cat((cv, v), dim=1)
                     caches[b] = (kc, vc)
-                    a = Fn.linear(self.r_act(self.attend(q, kc, vc)), self.wq["proj"])
+                    a = Fn.linear(self.row.r_act(self, self.attend(q, kc, vc)), self.wq["proj"])
                     x = x + a.mul(g1)
                     x2 = torch.matmul(Fn.layer_norm(x, (C,), eps=1e-6).mul(sc2.add(1)).add_(sh2).mul(self.s_fc1), self.q32)
-                    h = Fn.gelu(Fn.linear(self.r_act(x2), self.wq["fc1"]), approximate="tanh")
-                    x = x + Fn.linear(self.r_fc2(h), self.wq["fc2"]).mul(g2)
+                    h = Fn.gelu(Fn.linear(self.row.r_act(self, x2), self.wq["fc1"]), approximate="tanh")
+                    x = x + Fn.linear(self.row.r_fc2(self, h), self.wq["fc2"]).mul(g2)
                 continue
-            l2 = self.attn_l2_norm
-            scale = 1.0 if l2 else hd ** -0.5
+            scale = 1.0 if self.attn_l2_norm else hd ** -0.5
             prod = None
             if pend is not None:   # the previous block's fc2 tail, applied by this block's first producer
                 x, prod = self.resid_producer(path, pend, x, sc1, sh1, self.s_qkv)
                 pend = None
-            if self.kv_storage == "codes":
-                a = self.attend_codes(path, caches[b], x, b, scale, prod).view(B, L, C)
-            elif path == "Q" and self.qkv_to_cache and not (l2 and self.qk_norm == "torch"):
-                q = self.q_qkv_to_cache(x, sc1, sh1, b, caches[b].kv, caches[b].len, prod)
-                kc, vc = caches[b].commit_written(L)
-            else:
-                if path == "F":
-                    qkv = Fn.linear(self.f_producer(x, sc1, sh1, self.s_qkv) if prod is None else prod, self.wq["qkv"])
-                else:
-                    qkv = self.q_producer_linear(x, sc1, sh1, self.s_qkv, "qkv", prod)
-                if l2 and self.qk_norm == "torch":
-                    q, k, v = (t.half() for t in self.qk_norm_torch(qkv.view(B, L, 3 * C), b))
-                    kc, vc = caches[b].append(k, v)
-                elif l2:
-                    q, k, v = qkv.view(B, L, 3, H, hd).unbind(2)
-                    q, kc, vc = caches[b].append_qk_norm(q, k, v, self.head_scale[b], self.qkv_bias[b])
-                else:
-                    q, k, v = qkv.view(B, L, 3, H, hd).unbind(2)
-                    kc, vc = caches[b].append(k, v)
-            if self.kv_storage != "codes":
-                a = self.attend(q, kc, vc, scale) if (path == "F" and self.sdpa_in_f) else ops.attention_blhc(q, kc, vc, scale).view(B, L, C)
+            a = self.attention_half(path, caches[b], x, b, scale, prod).view(B, L, C)
             if path == "F":
-                proj = Fn.linear(self.f_act(a), self.wq["proj"])
+                proj = Fn.linear(self.row.act(a), self.wq["proj"])
                 if self.fuse_residual:   # proj's tail, applied by the fc1 producer
                     x, h2 = self.resid_producer(path, (proj, g1), x, sc2, sh2, self.s_fc1)
                 else:
                     x = ops.gate_residual(proj, g1, x)
-                    h2 = self.f_producer(x, sc2, sh2, self.s_fc1)
+                    h2 = self.row.values(x, sc2, sh2, sm=self.s_fc1)
                 hq = self.act_then_fc2_quant(Fn.linear(h2, self.wq["fc1"]))
             else:
                 x = self.q_proj(a.view(B * L, C), g1, x).view(B, L, C)
-                if self.fused_fc1:
-                    hq = self.q_fc1_gelu_dual(x, sc2, sh2).view(B, L, HID)
+                if self.fused_fc1:   # fc2's quantized input straight out of the fc1 GEMM
+                    hq = self.row.linear_gelu_dual(*self.q_operands(x, sc2, sh2, self.s_fc1), *self.wop["fc1"]).view(B, L, HID)
                 else:
                     hq = self.act_then_fc2_quant(self.q_producer_linear(x, sc2, sh2, self.s_fc1, "fc1").view(B, L, HID))
             if self.fuse_residual and b + 1 < self.depth:
