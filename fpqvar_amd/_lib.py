@@ -237,6 +237,11 @@ _SIGS = {
     # per-group(128) quantization on the full FP6 tables to dense 6-bit codes (table, dtype, layout: arguments)
     "fpq_gf6_quant_rows_codes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int,
                                              _c.c_void_p]),
+    # packed-file codewords <-> weight operands (packed.PackedWeight.operands / from_operands): sizes, cols, table, kmajor
+    "fpq_packed_to_operands": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64,
+                                           _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p]),
+    "fpq_operands_to_packed": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64,
+                                           _c.c_int, _c.c_int, _c.c_void_p]),
     # the fc1 tail with its dual pair and the layout as arguments: the twin's list, then neg table, pos table, kmajor
     "fpq_gemm_a6w4_gelu_dual_pair": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
                                                  _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,

@@ -362,6 +362,9 @@ __device__ __forceinline__ uint32_t fast_div_q(uint32_t n, const FastDiv& f) {
 // the permutations of the GEMMs' LDS images (fpq_gemm_fp4.h glds_chunk_perm, fpq_gemm_fp6.h fp6_rot), restated for the producers
 __host__ __device__ __forceinline__ uint32_t km4_perm(uint32_t row) { return (0x78u >> (((row & 15u) >> 2) << 1)) & 3u; }
 __host__ __device__ __forceinline__ uint32_t km6_rot(uint32_t row) { return (row >> 3) & 1u; }
+// the weight side's "dealt" row order (include/fpq.h): the tensor row that slot j of an image plane holds, and the slot of a row
+__host__ __device__ __forceinline__ int64_t km_dealt_row(int64_t j) { return (j & ~(int64_t)63) + 4 * (j & 15) + ((j >> 4) & 3); }
+__host__ __device__ __forceinline__ int64_t km_dealt_slot(int64_t row) { return (row & ~(int64_t)63) + ((row & 3) << 4) + ((row >> 2) & 15); }
 // FP4 (64 bytes per row and group): byte offset of logical chunk c (0..3) of group g of row t in an image of `rows` rows
 __device__ __forceinline__ uint32_t km4_off(uint32_t t, uint32_t g, uint32_t c, uint32_t rows) {
   return ((g * rows + t) << 6) + ((c ^ km4_perm(t)) << 4);

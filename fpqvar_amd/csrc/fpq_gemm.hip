@@ -559,7 +559,7 @@ __global__ __launch_bounds__(256) void codes_to_kmajor_kernel(const u32x4* __res
     const int64_t j = sj % image_rows;
     const int s = (int)(sj / image_rows);
     const int c = seg == 64 ? (pc ^ glds_chunk_perm((int)(j & 15))) : (pc - fp6_rot((int)(j & 31)) + 6) % 6;
-    const int64_t row = dealt ? (j & ~(int64_t)63) + 4 * (j & 15) + ((j >> 4) & 3) : j;
+    const int64_t row = dealt ? km_dealt_row(j) : j;
     u32x4 v = u32x4{0, 0, 0, 0};
     if (row < rows) v = codes[(row * steps + s) * cps + c];
     image[i] = v;

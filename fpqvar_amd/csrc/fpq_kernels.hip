@@ -391,6 +391,7 @@ __global__ __launch_bounds__(kBlock) void rows_negrev_scalar_kernel(const T* __r
 #include "fpq_codes_mx.h"    // the FP4 operand emitter (fpq_quant_rows_codes_mx: it shares codes128_kernel with fpq_quant_rows_codes)
 #include "fpq_codes_fp8.h"   // (codes8_vec16, the 6-bit code lookup of fpq_kv_pack)
 #include "fpq_codes_g6.h"    // the A6W4 GEMM's activation emitter (fpq_quant_rows_codes_g6)
+#include "fpq_packed_operands.h"   // packed-file codewords <-> weight operands (fpq_packed_to_operands, fpq_operands_to_packed)
 #include "fpq_kv_codes.h"    // the packed KV cache's producer (fpq_kv_pack; its consumer is the attention kernel, fpq_gemm.hip)
 
 // ---------------------------------------------------------------------------------
@@ -1749,6 +1750,43 @@ int fpq_gf6_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_
     return launch(group6_emit_kernel<float, bf6.value>, grid_for(tiles_of(n_blk, 1), 1 << 20), 0, st, x, codes, scales, n_blk,
                   make_fmt(table_id));
   });
+}
+
+// the packed file's codewords -> a GEMM's weight operand, and back (include/fpq.h; fpq_packed_operands.h): one launch each
+int fpq_packed_to_operands(const uint8_t* codes, const void* scales, int scale_dtype, uint8_t* w_codes, float* w_scales, int64_t outs,
+                           int64_t k, int64_t cols, int table_id, int kmajor, fpq_stream_t stream) {
+  PoCall c;
+  if (int rc = po_check(outs, k, cols, table_id, kmajor, scale_dtype, &c)) return rc;
+  if (outs == 0 || k == 0) return FPQ_OK;
+  const bool grouped = cols == 128;   // per channel: the scale vector is not part of the operand
+  if (!codes || !w_codes || (grouped && (!scales || !w_scales))) return FPQ_ERR_ARG;
+  if (!po_aligned16(codes, w_codes, grouped ? scales : nullptr, grouped ? w_scales : nullptr)) return FPQ_ERR_ARG;
+  const dim3 grid(grid_for(tiles_of(c.units, 1), 1 << 16));
+  return with_dtype(scale_dtype, [&](auto ts) {
+    using Ts = decltype(ts);
+    const Ts* sc = grouped ? (const Ts*)scales : nullptr;
+    float* wsc = grouped ? w_scales : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    if (c.mode == kPo44) return launch(packed_to_operands_kernel<kPo44, Ts>, grid, 0, st, codes, sc, w_codes, wsc, outs, c.steps, c.image_rows, c.sh);
+    if (c.mode == kPo46) return launch(packed_to_operands_kernel<kPo46, Ts>, grid, 0, st, codes, sc, w_codes, wsc, outs, c.steps, c.image_rows, c.sh);
+    return launch(packed_to_operands_kernel<kPo66, Ts>, grid, 0, st, codes, sc, w_codes, wsc, outs, c.steps, c.image_rows, c.sh);
+  });
+}
+int fpq_operands_to_packed(const uint8_t* w_codes, const float* w_scales, uint8_t* codes, float* scales, int64_t outs, int64_t k,
+                           int64_t cols, int table_id, int kmajor, fpq_stream_t stream) {
+  PoCall c;
+  if (int rc = po_check(outs, k, cols, table_id, kmajor, FPQ_F32, &c)) return rc;
+  if (outs == 0 || k == 0) return FPQ_OK;
+  const bool grouped = cols == 128;
+  if (!codes || !w_codes || (grouped && (!scales || !w_scales))) return FPQ_ERR_ARG;
+  if (!po_aligned16(codes, w_codes, grouped ? scales : nullptr, grouped ? w_scales : nullptr)) return FPQ_ERR_ARG;
+  const dim3 grid(grid_for(tiles_of(outs * c.steps * (c.mode == kPo66 ? 2 : 4), 1), 1 << 16));
+  const float* wsc = grouped ? w_scales : nullptr;
+  float* sc = grouped ? scales : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  if (c.mode == kPo44) return launch(operands_to_packed_kernel<kPo44>, grid, 0, st, w_codes, wsc, codes, sc, outs, c.steps, c.image_rows, c.sh);
+  if (c.mode == kPo46) return launch(operands_to_packed_kernel<kPo46>, grid, 0, st, w_codes, wsc, codes, sc, outs, c.steps, c.image_rows, c.sh);
+  return launch(operands_to_packed_kernel<kPo66>, grid, 0, st, w_codes, wsc, codes, sc, outs, c.steps, c.image_rows, c.sh);
 }
 
 int fpq_kv_pack(uint8_t* codes, void* scales, int kv_bit, int64_t batch, int64_t max_len, int64_t heads, int64_t head_dim, int64_t pos,

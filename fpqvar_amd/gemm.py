@@ -252,6 +252,73 @@ class _ScaledOperandModule(torch.nn.Module):
         return self
 
 
+    # ---- the packed form (packed.PackedWeight) and the other layout -------------------------------------------------------
+    def _packed_cols(self) -> int:
+        """the quantization row of the held weight: 128 with per-group scales, in_features with one scale per output channel"""
+        return 128 if self.w_scales.dim() == 2 else self.in_features
+
+    def to_packed(self, **header):
+        """The held weight as a packed.PackedWeight (fpq_operands_to_packed): `operands(self.kmajor)` of the result returns the
+        module's w_codes / w_scales.  header: out_dtype, rotate_block, rotate_seed, smooth."""
+        from .packed import PackedWeight
+        return PackedWeight.from_operands(self.w_codes, self.w_scales, self.w_table, (self.out_features, self.in_features),
+                                          self._packed_cols(), bias=self.bias, **header)
+
+    @classmethod
+    def from_packed(cls, packed, **kwargs):
+        """from_float for a packed.PackedWeight instead of an nn.Linear: the same keyword arguments but weight_fp_type - the table
+        is the packed weight's - and the same ValueErrors; the buffers come from `packed.operands(kmajor)`, one launch."""
+        if "weight_fp_type" in kwargs:
+            raise TypeError(f"{cls.__name__}.from_packed: the weight format is the packed weight's ({packed.table}), not an argument")
+        if len(packed.shape) != 2:
+            raise ValueError(f"{cls.__name__}.from_packed: a Linear's weight is 2-D, the packed one has shape {tuple(packed.shape)}")
+        stub = torch.nn.Linear(packed.shape[1], packed.shape[0], bias=False, device="meta")   # shapes only: no weight to read
+        stub.packed_weight = packed
+        return cls.from_float(stub, weight_fp_type=packed.table, **kwargs)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        """w_codes of the other rank than the module holds (row-major codes for a k-major module, or the reverse) are converted,
+        together with w_scales, through the packed form - two launches (fpq_operands_to_packed, fpq_packed_to_operands); on the CPU
+        they are left as they are and the usual size mismatch is reported."""
+        codes, scales = state_dict.get(prefix + "w_codes"), state_dict.get(prefix + "w_scales")
+        if (isinstance(codes, torch.Tensor) and isinstance(scales, torch.Tensor) and codes.is_cuda and scales.is_cuda
+                and codes.dim() != self.w_codes.dim() and codes.dim() in (2, 3) and hasattr(self, "w_table")):
+            from .packed import PackedWeight
+            try:
+                p = PackedWeight.from_operands(codes, scales, self.w_table, (self.out_features, self.in_features), self._packed_cols())
+                state_dict[prefix + "w_codes"], state_dict[prefix + "w_scales"] = p.operands(self.w_codes.dim() == 3)
+            except RuntimeError:
+                pass   # not this module's weight in the other layout: the size mismatch below says so
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+
+def _weight_operands(name: str, module: torch.nn.Linear, table: str, kmajor: bool, per_channel: bool = False):
+    """(w_codes, w_scales, bias) of a matrix-core Linear built from `module`: quantized from module.weight.float() by the format's
+    quantizer (and converted to the dealt k-major images), or - with a packed.PackedWeight attached as module.packed_weight
+    (packed.attach) - taken from it in one launch without reading module.weight.  name: "<class>.from_float"."""
+    cols = module.in_features if per_channel else 128
+    packed = getattr(module, "packed_weight", None)
+    if packed is not None:
+        if packed.table != table or packed.cols != cols or tuple(packed.shape) != (module.out_features, module.in_features):
+            raise ValueError(f"{name}: the attached packed weight is {packed.table} {tuple(packed.shape)} in rows of {packed.cols}, "
+                             f"the layer asks for {table} {(module.out_features, module.in_features)} in rows of {cols}")
+        codes, scales = packed.operands(kmajor)
+        if per_channel and scales.dim() == 2:   # in_features == 128: rows of 128 are channels too, the operand came with its scales
+            scales = (scales[0] if kmajor else scales.reshape(-1))[:module.out_features].contiguous()
+        bias = packed.bias if packed.bias is not None else module.bias
+    else:
+        w = module.weight.detach().float()
+        if per_channel:
+            codes, scales = quantize_fp6(w, table=table)
+        else:
+            codes, scales = _quantize_any(name, table, w)
+        if kmajor:
+            codes = to_kmajor(codes, 4 if table == "e2m1" else 6, dealt=True)
+            scales = scales if per_channel else to_kmajor_scales(scales, weight_side=True)
+        bias = module.bias
+    return codes, scales, None if bias is None else bias.detach().to(torch.float16)
+
+
 def _check_operand(what: str, codes: torch.Tensor, scales: torch.Tensor, rows: int, row_bytes: int, n_scales: int,
                    device) -> None:
     """Shapes, dtypes and placement of a (codes, scales) operand BEFORE the kernel sees the pointers: a truncated or
@@ -760,10 +827,7 @@ class FP4Linear(_ScaledOperandModule):
             if issubclass(cls, FP4LinearGeluDual) and not w6_forms:
                 raise ValueError(f"FP4LinearGeluDual.from_float: weight_fp_type={weight_fp_type!r} runs on the W6 GEMM, which has no fc1 tail")
             act_table = "e2m1" if act_fp_type in ("fp_e2", "e2m1") else _g6_table("FP4Linear.from_float", act_fp_type)
-            codes, scales = quantize_g6(module.weight.detach().float(), w_table)
-            if km6:
-                codes, scales = to_kmajor(codes, 6, dealt=True), to_kmajor_scales(scales, weight_side=True)
-            bias = None if module.bias is None else module.bias.detach().to(torch.float16)
+            codes, scales, bias = _weight_operands(f"{cls.__name__}.from_float", module, w_table, km6)
             return cls(codes, scales, bias, module.in_features, module.out_features, act_table, w_table, w6_forms=w6_forms)
         if act_fp_type in ("fp_e2", "e2m1"):
             act_table = "e2m1"
@@ -772,10 +836,7 @@ class FP4Linear(_ScaledOperandModule):
             if kmajor and not a6w4_kmajor:
                 raise ValueError(f"FP4Linear.from_float: act_fp_type={act_fp_type!r} runs on the A6W4 GEMM, which has no k-major form "
                                  "unless a6w4_kmajor=True asks for it (kmajor=True alone needs act_fp_type='fp_e2')")
-        codes, scales = quantize_mx(module.weight.detach().float())
-        if kmajor:
-            codes, scales = to_kmajor(codes, 4, dealt=True), to_kmajor_scales(scales, weight_side=True)
-        bias = None if module.bias is None else module.bias.detach().to(torch.float16)
+        codes, scales, bias = _weight_operands(f"{cls.__name__}.from_float", module, "e2m1", kmajor)
         return cls(codes, scales, bias, module.in_features, module.out_features, act_table)
 
     def extra_repr(self) -> str:
@@ -1081,10 +1142,7 @@ class FP6GroupLinear(FP4Linear):
             raise ValueError(str(e)) from None
         if at not in _GF6_FULL and wt not in _GF6_FULL:
             raise ValueError(f"{name}: the pair ({at}, {wt}) has no fp6_e2m3 / fp6_e3m2 side - it belongs to FP4Linear")
-        codes, scales = _quantize_any(name, wt, module.weight.detach().float())
-        if kmajor:
-            codes, scales = to_kmajor(codes, 4 if wt == "e2m1" else 6, dealt=True), to_kmajor_scales(scales, weight_side=True)
-        bias = None if module.bias is None else module.bias.detach().to(torch.float16)
+        codes, scales, bias = _weight_operands(name, module, wt, kmajor)
         return cls(codes, scales, bias, module.in_features, module.out_features, at, wt)
 
     def _run(self, form: str, table: Optional[str], a_codes, a_scales, *rest):
@@ -1225,6 +1283,9 @@ class FP8Linear(_ScaledOperandModule):
     @classmethod
     def from_float(cls, module: torch.nn.Linear, weight_fp_type: str = "fp6_e2m3", act_fp_type: str = "fp6_e2m3"):
         assert isinstance(module, torch.nn.Linear) and module.in_features % 128 == 0 and module.out_features % 8 == 0
+        if getattr(module, "packed_weight", None) is not None:
+            raise ValueError("FP8Linear.from_float: a packed weight has no E4M3-coded form - quantize_VAR(..., real_fp6=True, "
+                             "packed_e3m2=True) builds this layer as a gemm.FP6Linear, which takes it")
         codes, scales = quantize_fp8(module.weight.detach().float(), weight_fp_type)
         bias = None if module.bias is None else module.bias.detach().to(torch.float16)
         return cls(codes, scales, bias, module.in_features, module.out_features, act_fp_type)
@@ -1414,10 +1475,7 @@ class FP6Linear(_ScaledOperandModule):
     def from_float(cls, module: torch.nn.Linear, kmajor: bool = False, weight_fp_type: str = "fp6_e2m3", act_fp_type: str = "fp6_e2m3"):
         assert isinstance(module, torch.nn.Linear) and module.in_features % 128 == 0 and module.out_features % 8 == 0
         w_table, act_table = _f6_table("FP6Linear.from_float", weight_fp_type), _f6_table("FP6Linear.from_float", act_fp_type)
-        codes, scales = quantize_fp6(module.weight.detach().float(), table=w_table)
-        if kmajor:
-            codes = to_kmajor(codes, 6, dealt=True)
-        bias = None if module.bias is None else module.bias.detach().to(torch.float16)
+        codes, scales, bias = _weight_operands(f"{cls.__name__}.from_float", module, w_table, kmajor, per_channel=True)
         return cls(codes, scales, bias, module.in_features, module.out_features, act_table, w_table)
 
     def extra_repr(self) -> str:

@@ -72,6 +72,26 @@ def _quantize_weight(w, weight_quant, weight_fp_quant, weight_fp_type, w_bit):
     raise ValueError(f"Invalid weight_quant: {weight_quant}")
 
 
+def _packed_weight(cls_name, module, packed, weight_quant, weight_fp_quant, weight_fp_type, w_bit):
+    """What _quantize_weight returns, from the packed.PackedWeight attached to `module` (packed.attach): its de-quantized tensor,
+    bit-equal to the quantizer's output on the weight it was calibrated from.  The packed format must be the one the arguments
+    ask for."""
+    from .packed import FP4_TABLES, TABLE_OF_FP_TYPE
+    if not weight_fp_quant or weight_quant not in ("per_channel", "per_group"):
+        raise NotImplementedError("INT weight quantizers are out of scope (SURVEY.md section 2 row 4)")
+    table = TABLE_OF_FP_TYPE.get(weight_fp_type)
+    if table is None:
+        raise ValueError("Unsupported fp_type.")
+    cols = _GROUP if weight_quant == "per_group" else module.in_features
+    if (packed.table != table or packed.cols != cols or w_bit != (4 if table in FP4_TABLES else 6)
+            or tuple(packed.shape) != (module.out_features, module.in_features)):
+        raise ValueError(f"{cls_name}.from_float: the attached packed weight is {packed.table} {tuple(packed.shape)} in rows of "
+                         f"{packed.cols}, the layer asks for {table} ({w_bit} bits) {(module.out_features, module.in_features)} in rows of {cols}")
+    # the reference's FP6 quantizers return float16 whatever they are given (`.to(torch.float16)`), its FP4 ones the input's dtype -
+    # which calibrate_packed recorded as the packed weight's out_dtype
+    return packed.dequantize(None if table in FP4_TABLES else torch.float16)
+
+
 class GeluThenFc2Quant(nn.Module):
     """Stands in for an FFN's `act` (GELU, approximate="tanh") when fc2's dual-format input quantizer is fused behind it:
     `forward(y)` = `fc2.act_quant(F.gelu(y, approximate="tanh"))` in ONE pass over the fc1 output (quant_utils.gelu_*), for the
@@ -148,7 +168,11 @@ class QuantizedLinear(nn.Module):
                   quantize_output=quantize_output, w_bit=w_bit, a_bit=a_bit, act_quant_sym=act_quant_sym,
                   fc2_act_log2_quant=fc2_act_log2_quant, activation_fp_quant=activation_fp_quant,
                   weight_fp_quant=weight_fp_quant, act_fp_type=act_fp_type, weight_fp_type=weight_fp_type)
-        new.weight = _quantize_weight(module.weight.detach(), weight_quant, weight_fp_quant, weight_fp_type, w_bit)
+        packed = getattr(module, "packed_weight", None)
+        if packed is None:
+            new.weight = _quantize_weight(module.weight.detach(), weight_quant, weight_fp_quant, weight_fp_type, w_bit)
+        else:   # packed.attach: the fake-quantized weight is the packed one's, module.weight is not read
+            new.weight = _packed_weight(cls.__name__, module, packed, weight_quant, weight_fp_quant, weight_fp_type, w_bit)
         new.weight_quant_name = weight_quant
         if module.bias is not None:
             new.bias = module.bias

@@ -964,6 +964,36 @@ int fpq_gemm_w6_mx_split_qknorm_km(const uint8_t* a_image, const void* a_scales,
 int fpq_gf6_quant_rows_codes(const void* x, uint8_t* codes, void* scales, int64_t rows, int64_t cols, int table_id, int in_dtype,
                              int kmajor, fpq_stream_t stream);
 
+/* ---- PACKED WEIGHTS <-> WEIGHT OPERANDS (fpqvar_amd/packed.py; csrc/fpq_packed_operands.h) -------------------------------------
+ * A packed file stores, per weight, the INDEX of each element's level in the sorted, de-duplicated value table; the matrix-core GEMMs
+ * take the level's HARDWARE CODE.  The two differ by a fixed map per field and a layout - no arithmetic on values, no second
+ * quantization decision - and each direction is ONE launch, padding included.
+ *   packed side   codes: FP4 tables (FPQ_E2M1, FPQ_E1M2, FPQ_E3M0) two index nibbles per byte, element 2i in the low nibble,
+ *                 [outs, k / 2]; FP6 tables (FPQ_E2M3, FPQ_E3M2) four 6-bit indices per three bytes, the little-endian bit string
+ *                 of fpq_quant_rows_codes_fp6 (packed.pack6), [outs, k * 3 / 4].  scales: one per quantization row - [outs, k / 128]
+ *                 with cols == 128, [outs] with cols == k; scale_dtype FPQ_F16 or FPQ_F32 (forward), fp32 (inverse).
+ *   operand side  FPQ_E2M1: OCP E2M1 nibbles, [outs, k / 2] (fpq_gemm_fp4_mx's w_codes).  FPQ_E1M2: its levels as FP6 E2M3 codes,
+ *                 FPQ_E3M0: as BF6 E3M2 codes, FPQ_E2M3 / FPQ_E3M2: sign-magnitude 6-bit codes - all dense, [outs, k * 3 / 4], the
+ *                 form of fpq_quant_rows_codes_g6.  A zero level is code 0 in every format.  Scales always fp32.
+ *   the map       index i, zero index Z (7 or 31): magnitude |i - Z|, sign set below Z; code = sign bit | magnitude (E2M1, E2M3,
+ *                 E3M2), | magnitude << 1 (E1M2 in E2M3), | magnitude << 2 (E3M0 in E3M2).  The index no table has (nibble 15, field
+ *                 63) -> code 0.  Inverse: magnitude = (code >> shift) & Z, index = Z -/+ magnitude: a negative zero gives Z, a code
+ *                 that is no level of the table some index in 0 .. 2 Z.
+ *   kmajor == 0   row-major w_codes and, per group, w_scales float [outs, k / 128]
+ *   kmajor == 1   the dealt weight image [k / 128][outs rounded up to 64][64 | 96], byte for byte fpq_codes_to_kmajor(.., dealt = 1) of
+ *                 the row-major codes, and per group the fp32 weight-side scale image of fpq_scales_to_kmajor(.., weight_side = 1);
+ *                 the padding rows of both are WRITTEN (zero) by the same launch - the caller need not clear anything.
+ *   cols == k     (per channel; FP6 tables only, unless k == 128) the scale vector is not part of the operand layout: scales and
+ *                 w_scales are ignored, pass NULL.
+ * Checks, in this order, before any launch: table_id outside the five tables (FPQ_ERR_TABLE); negative outs / k / cols
+ * (FPQ_ERR_ARG); scale_dtype (FPQ_ERR_DTYPE; the inverse has none); k % 128 != 0, cols neither 128 nor k, cols == k != 128 with an FP4
+ * table, or an operand image (rows rounded up to 64, in either layout) of 2 GiB or more (FPQ_ERR_SHAPE); outs == 0 or k == 0
+ * (FPQ_OK); NULL pointers or pointers not 16-byte aligned (FPQ_ERR_ARG; the two scale pointers only with cols == 128). */
+int fpq_packed_to_operands(const uint8_t* codes, const void* scales, int scale_dtype, uint8_t* w_codes, float* w_scales,
+                           int64_t outs, int64_t k, int64_t cols, int table_id, int kmajor, fpq_stream_t stream);
+int fpq_operands_to_packed(const uint8_t* w_codes, const float* w_scales, uint8_t* codes, float* scales,
+                           int64_t outs, int64_t k, int64_t cols, int table_id, int kmajor, fpq_stream_t stream);
+
 /* THE FC1 TAIL WITH ITS DUAL PAIR AS AN ARGUMENT: fpq_gemm_a6w4_gelu_dual[_km] / fpq_gemm_w6_gelu_dual[_km] with the two tables of fc2's
  * per-group(128) input quantizer (neg_table, pos_table) and the layout (kmajor: 0 row-major operands, else the k-major images of the
  * _km twin) as arguments.  Accepted pairs - anything else FPQ_ERR_TABLE, checked beside the operand tables, before every other check:
