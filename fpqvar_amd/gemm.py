@@ -941,10 +941,18 @@ class FP4Linear(_ScaledOperandModule):
         return rotation.adaln_rotate_quant_g6(x, scale, shift, self.act_table, d=d, smooth=smooth, eps=eps, kmajor=self.kmajor)
 
     @torch.no_grad()
-    def rotate_operands(self, x, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def rotate_operands(self, x, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
+                        full_width: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """`adaln_operands` without the LayerNorm and the modulation: smooth, rotate, per-group quantize of x [..., in_features]
-        (`rotation.rotate_quant_mx` / `rotation.rotate_quant_g6`)."""
+        (`rotation.rotate_quant_mx` / `rotation.rotate_quant_g6`).
+        full_width: the full-width rotation of `rotate_model(block_rotate=False)` instead of the 128-block form
+        (`rotation.rotate_quant_full_mx`; d: in_features signs) - E2M1 activations only."""
         from . import rotation
+        if full_width:
+            if self.act_table != "e2m1":
+                raise NotImplementedError(f"rotate_operands(full_width=True): the fused full-width rotation emits E2M1 (FP4) operands only, "
+                                          f"not {self.act_table!r} - 6-bit operand forms are outside the full-width producer's scope")
+            return rotation.rotate_quant_full_mx(x, d=d, smooth=smooth, kmajor=self.kmajor)
         if self.act_table == "e2m1":
             return rotation.rotate_quant_mx(x, d=d, smooth=smooth, kmajor=self.kmajor)
         return rotation.rotate_quant_g6(x, self.act_table, d=d, smooth=smooth, kmajor=self.kmajor)

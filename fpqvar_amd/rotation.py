@@ -146,6 +146,13 @@ def sign_mask(d: torch.Tensor) -> Tuple[int, int, int, int]:
     return tuple(sum(b << k for k, b in enumerate(bits[32 * w:32 * w + 32])) for w in range(4))
 
 
+def full_sign_words(d: torch.Tensor) -> Tuple[int, ...]:
+    """The C signs of the full-width rotation -> C / 32 x uint32, bit j set <=> d[j] == -1 (C % 32 == 0)."""
+    assert d.numel() % 32 == 0
+    bits = (d.reshape(-1) < 0).to(torch.int64).tolist()
+    return tuple(sum(b << k for k, b in enumerate(bits[32 * w:32 * w + 32])) for w in range(len(bits) // 32))
+
+
 def rotate_weight(w: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
     """Offline weight side: W <- W . Q in float64, back to W's dtype (rotation_utils.py:129-154)."""
     return (w.to(torch.float64) @ q.to(w.device, torch.float64)).to(w.dtype)
@@ -181,8 +188,8 @@ def rotate_model(model, device, block_rotate: bool = True) -> None:
     """The reference's offline weight rotation for every block, mat_qkv and fc1 (rotation_utils.py:211-240):
     block_rotate=True - the run scripts' mode - with the block-diagonal Q (128-wide blocks, seed 42);
     block_rotate=False with the full-width randomized Hadamard matrix of size model.C (had60 x 2^5 for 1920, had36 x 2^6
-    for 2304).  The ONLINE side of the full-width mode is a dense x . Q (no 128-block structure for the fused
-    kernel to exploit), exactly as in the reference."""
+    for 2304).  The ONLINE side of the full-width mode is `rotate_quant_full` / `rotate_quant_full_mx`: one launch that runs
+    x . Q as the two small products hadK . X . Sylvester(C / K) on the matrix cores and quantizes the rotated row."""
     if block_rotate:
         q = block_random_hadamard_matrix(total_size=model.C, block_size=128, device=device, seed=42)
     else:
@@ -238,6 +245,20 @@ def _mask_arg(d: Optional[torch.Tensor]):
     return (ctypes.c_uint32 * 4)(*sign_mask(d.cpu()))
 
 
+_DEFAULT_FULL_WORDS = {}
+
+
+def _full_words_arg(d: Optional[torch.Tensor], c: int):
+    """The C sign bits of the full-width rotation as the C ABI takes them (C / 32 words); the default D (seed 42, C long) once per width."""
+    if d is None:
+        if c not in _DEFAULT_FULL_WORDS:
+            _DEFAULT_FULL_WORDS[c] = (ctypes.c_uint32 * (c // 32))(*full_sign_words(sign_vector(c, 42)))   # read-only to the library: shared
+        return _DEFAULT_FULL_WORDS[c]
+    if d.numel() != c:
+        raise RuntimeError(f"the full-width rotation takes one sign per channel: {c}, got {d.numel()}")
+    return (ctypes.c_uint32 * (c // 32))(*full_sign_words(d.cpu()))
+
+
 def _mod_rows(t: torch.Tensor, bsz: int, c: int) -> torch.Tensor:
     """[B, 1, C] / [B, C] modulation tensor as B contiguous rows (no tensor op when it already is)."""
     if t.is_contiguous() and t.numel() == bsz * c:
@@ -287,6 +308,7 @@ class _Family(NamedTuple):
     seg: int = 0                       # bytes of codes per 128 elements (64 FP4 nibbles, 96 dense 6-bit codes, 128 E4M3 bytes); 0: fp16 values
     row_scales: bool = False           # one fp16 scale per row, not one per 128 elements
     slots: int = 2                     # output pointers: the outputs, then NULL for each intermediate that was not asked for
+    full: bool = False                 # the full-width rotation: C / 32 sign words, not the 128-bit mask; ctypes only (no compiled form)
 
 
 _FORMS = tuple(_native.PRODUCER_ENTRY_POINTS) if _native is not None else ()
@@ -309,6 +331,9 @@ _TOKEN = {"values": _family("fpq_adaln_rotate_quant_token_rows", max_c=2560, slo
           "fp6": _family("fpq_adaln_rotate_quant_token_rows_codes_fp6", km="fpq_adaln_rotate_quant_token_rows_codes_fp6_km", max_c=2560, seg=96,
                          row_scales=True),
           "bf6": _family("fpq_adaln_rotate_quant_token_rows_codes_f6", km=True, max_c=2560, seg=96, row_scales=True)}
+_FULL = _family("fpq_fullrot_quant_rows", full=True)
+_FULL_MX = _family("fpq_fullrot_quant_rows_codes_mx", km=True, table=False, seg=64, full=True)
+FULL_WIDTHS = (1920, 2304)             # the widths the library builds (include/fpq.h, fpq_fullrot_quant_rows)
 _RESID = _family("fpq_resid_adaln_rotate_quant_rows", max_c=2560, slots=3)
 _RESID_MX = _family("fpq_resid_adaln_rotate_quant_rows_codes_mx", km=True, table=False, max_c=2560, seg=64)
 _RESID_TOKEN = {"values": _family("fpq_resid_adaln_rotate_quant_token_rows", max_c=2560, slots=4),
@@ -334,13 +359,13 @@ def _produce(name: str, fam: _Family, x: torch.Tensor, c: int, tid: int, d, smoo
     adaLN front; y, gt: the gated residual's other two tensors.  The compiled binding takes the usual arguments - default sign
     vector, contiguous x (and y), float32 [C] smooth, no intermediates - everything else goes through ctypes; both end in `fam.entry`.
     Returns the outputs (behind a gated residual x_new first): one tensor as itself, more as a tuple."""
-    if _native is not None and d is None and not extra and x.is_cuda and x.is_contiguous() and (
+    if _native is not None and fam.form >= 0 and not fam.full and d is None and not extra and x.is_cuda and x.is_contiguous() and (
             smooth is None or (smooth.dtype is torch.float32 and smooth.dim() == 1 and smooth.shape[0] == c and
                                smooth.device == x.device and smooth.is_contiguous())) and (
             sc is None or (sc.device == x.device and sh.device == x.device)) and (y is None or y.is_contiguous()):
         return _native.producer(name, fam.form, x, y, gt, sc, sh, tid, _DEFAULT_MASK_TUPLE or _default_mask_tuple(), smooth, float(eps),
                                 kmajor, inplace)
-    mask = _mask_arg(d)
+    mask = _full_words_arg(d, c) if fam.full else _mask_arg(d)
     xc = x if x.is_contiguous() else x.contiguous()
     head, first = (xc.data_ptr(),), []
     if y is not None:
@@ -405,6 +430,33 @@ def rotate_quant_mx(x: torch.Tensor, d: Optional[torch.Tensor] = None, smooth: O
     (codes uint8 [rows, C/2], scales fp16 [rows, C/128]); level(code) * scale == rotate_quant(x) bit for bit.
     kmajor: the activation side's k-major images (include/fpq.h) - codes [C/128, rows, 64], scales fp32 [C/128, rows rounded up to 4]."""
     return _rotate("rotate_quant_mx", _ROTATE_MX, x, None, d, smooth, kmajor)
+
+
+def _rotate_full(name: str, fam: _Family, x: torch.Tensor, table, d, smooth, kmajor=False, extra: int = 0):
+    require_gpu(x, name)
+    c = x.shape[-1]
+    if x.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError(f"{name}: x must be float16 or float32, got {x.dtype}")
+    if c not in FULL_WIDTHS:
+        raise RuntimeError(f"{name}: the full-width rotation is built for the widths {FULL_WIDTHS}, got {c}")
+    return _produce(name, fam, x, c, TABLE_IDS[table] if fam.table else 0, d, smooth, kmajor, extra)
+
+
+def rotate_quant_full(x: torch.Tensor, table: str = "e2m1", d: Optional[torch.Tensor] = None,
+                      smooth: Optional[torch.Tensor] = None, return_rotated: bool = False):
+    """out = fp_quant_*_per_group_cuda( half(x*smooth) @ half(Q) , 128 ) in one launch, Q = get_orthogonal_matrix(C) - the
+    FULL-WIDTH randomized Hadamard matrix (the reference's `--rotate` without `--block_rotate`; rotate_model(block_rotate=False)
+    is the weight side).  x: [..., C] fp16 or fp32 on the GPU, C in FULL_WIDTHS; d: the C signs (default sign_vector(C, 42)).
+    Returns fp16 (and the rotated fp16 tensor when return_rotated)."""
+    return _rotate_full("rotate_quant_full", _FULL, x, table, d, smooth, extra=1 if return_rotated else 0)
+
+
+def rotate_quant_full_mx(x: torch.Tensor, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
+                         kmajor: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """rotate_quant_full(x, "e2m1") emitting the FP4 GEMM's operands instead of values, byte for byte gemm.quantize_mx of the rotated
+    rows: (codes uint8 [rows, C/2], scales fp16 [rows, C/128]), or (kmajor) the k-major images - codes [C/128, rows, 64], scales
+    fp32 [C/128, rows rounded up to 4]."""
+    return _rotate_full("rotate_quant_full_mx", _FULL_MX, x, None, d, smooth, kmajor)
 
 
 def adaln_rotate_quant_mx(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, d: Optional[torch.Tensor] = None,

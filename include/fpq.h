@@ -1198,6 +1198,38 @@ int fpq_dequant_rows_codes_segments(const fpq_decode_segment_t* segments_device,
                                     int64_t cols, int table_id, int scale_dtype, int out_dtype, int pack_nibbles,
                                     fpq_stream_t stream);
 
+/* FULL-WIDTH online rotation fused in front of the per-group(128) quantizer: the online side of the reference's `--rotate`
+ * without `--block_rotate` (rotate_utils/rotation_utils.py:57-63: Q = diag(D) . H_cols^T / sqrt(cols), H_cols = hadK (x)
+ * Sylvester(cols / K)), where
+ *     x1 = torch.matmul(producer.mul(s), Q)            tr/basic_var.py:263,266 (fp16 autocast): a dense [rows x cols] . [cols x cols]
+ *     q  = fp_quant_e{1,2,3}_per_group_cuda(x1, 4, 128) / fp6_quant_*_per_group_cuda
+ * becomes one launch:  h = half(x * s);  y = half(c_h * sum_j +-h_j) with the signs of diag(D) . H_cols^T and
+ * c_h = float(half(float32(1 / sqrt(cols)))), the one magnitude of half(float32(Q));  out = per-group(128) quant(y).
+ * Both Hadamard factors run on the matrix cores, 2 cols (K + cols / K) FLOP per row (csrc/fpq_fullrot.h).
+ * Built widths: cols == 1920 (had60 x 2^5) and cols == 2304 (had36 x 2^6).  EVERY other width - the powers of two, 1280 and 1536
+ * included - is FPQ_ERR_SHAPE.
+ * x: [rows, cols] F16 or F32; smooth: device float[cols] or NULL;
+ * sign_words_host: HOST pointer to cols / 32 x uint32, bit j set <=> D[j] == -1, D the cols-long vector of seed 42 (NOT the 128
+ * signs of the block form tiled);
+ * out: fp16 [rows, cols]; rotated_out: NULL, or fp16 [rows, cols] receiving y; table_id: every symmetric table.
+ * Parity: out == fpq_quant_rows(y) bit for bit.  y: the +-h_j are summed in fp32 on the matrix cores (the intermediate between
+ * the two factors enters the second as three bf16 pieces that add up to it exactly), at most cols / K + 3 K - 1 roundings of
+ * partial sums:  |y - exact| <= 1/2 fp16 ulp (1 + 2^-11) + (cols / K + 3 K - 1) 2^-24 c_h sum|h_j|  (tests/fullrot_model.py).
+ * A non-finite input poisons its whole row, as in the reference (the dense Q has no zero entry); y is +-inf exactly where the
+ * exact product overflows fp16 or is infinite, with its sign.
+ * Checks, in this order, before any launch: rows < 0, cols < 0 or sign_words_host NULL (FPQ_ERR_ARG); table_id (FPQ_ERR_TABLE);
+ * in_dtype (FPQ_ERR_DTYPE); cols not a built width or rows >= 2^31 (FPQ_ERR_SHAPE); rows == 0 -> FPQ_OK, nothing is launched;
+ * x or out NULL, a pointer not 16-byte aligned (FPQ_ERR_ARG). */
+int fpq_fullrot_quant_rows(const void* x, void* out, void* rotated_out, int64_t rows, int64_t cols, int in_dtype,
+                           const float* smooth, const uint32_t* sign_words_host, int table_id, fpq_stream_t stream);
+/* The same launch emitting the FP4 GEMM's activation operands: what fpq_quant_rows_codes_mx (kmajor == 0: codes uint8 [rows,
+ * cols / 2], scales fp16 [rows, cols / 128]) or fpq_quant_rows_codes_mx_km (kmajor != 0: the k-major images, codes [cols / 128,
+ * rows, 64], scales fp32 [cols / 128, rows rounded up to 4] - the padding is the caller's) writes for y, byte for byte; F32 rows
+ * are taken in both layouts.  Checks: scales NULL with rows > 0 and a built width (FPQ_ERR_ARG), then those of
+ * fpq_fullrot_quant_rows (the table is FPQ_E2M1; FPQ_ERR_SHAPE also for a k-major image of 2 GiB or more). */
+int fpq_fullrot_quant_rows_codes_mx(const void* x, void* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
+                                    const float* smooth, const uint32_t* sign_words_host, int kmajor, fpq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
