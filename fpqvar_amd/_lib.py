@@ -248,6 +248,14 @@ _SIGS = {
                                            _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_void_p]),
     "fpq_fullrot_quant_rows_codes_mx": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
                                                     _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_void_p]),
+    # the same with LayerNorm + modulate in front (rotation.adaln_rotate_quant_full*): x, outputs (values: out, h, rotated), rows, cols,
+    # dtype, scale, shift, their dtype, rows per batch, eps, smooth, cols / 32 sign words, then a table id / `int kmajor`
+    "fpq_fullrot_adaln_quant_rows": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
+                                                 _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_void_p,
+                                                 _c.POINTER(_c.c_uint32), _c.c_int, _c.c_void_p]),
+    "fpq_fullrot_adaln_quant_rows_codes_mx": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
+                                                          _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_void_p,
+                                                          _c.POINTER(_c.c_uint32), _c.c_int, _c.c_void_p]),
     # the fc1 tail with its dual pair and the layout as arguments: the twin's list, then neg table, pos table, kmajor
     "fpq_gemm_a6w4_gelu_dual_pair": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
                                                  _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,

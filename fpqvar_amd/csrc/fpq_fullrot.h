@@ -25,8 +25,8 @@
 //      out == fpq_quant_rows(y) / fpq_quant_rows_codes_mx[_km](y) by construction.
 // Numerics: +-1 operands; every rounding is an fp32 rounding of a partial sum inside an MFMA (at most m - 1 in stage 1, 3 K - 1 in
 // stage 2: K segments x three pieces), one of the product with c_h, one to fp16: tests/fullrot_model.py carries the bound.
-// Built widths: kFullRotWidths.  The transform (fullrot_transform_row) is a device function of its own: a full-width adaLN producer
-// would call it behind its LayerNorm.
+// Built widths: kFullRotWidths.  The transform (fullrot_transform_row), the table staging (fr_stage_tables) and the quantizer tail
+// (fr_quant_image) are device functions of their own: the full-width adaLN producer (fpq_fulladaln.h) calls them behind its LayerNorm.
 #pragma once
 
 typedef __bf16 fr_bf8_t __attribute__((ext_vector_type(8)));
@@ -259,7 +259,67 @@ __device__ __forceinline__ void fullrot_transform_row(const FrRow<K, M>& h, cons
   else body(Bool<false>{});
 }
 
-// MODE 0: values out; 1: values + the rotated rows; 2: E2M1 operand codes + group scales (`out`: the codes, the staged table the code table)
+// The tables every wavefront of a workgroup reads, staged once (two barriers): hadK's operands, the quantizer's bucket table, and
+// the xor masks of the signs per operand and lane (`sign_s`: the sign words on their way there).
+template <int K, int M>
+__device__ __forceinline__ void fr_stage_tables(const FullRotArgs& r, const Lut16Args& a, const Lut16Tab& tab, uint16_t* lut, uint32_t* sign_s,
+                                                u32x4* had_s, u32x4* sgn_s) {
+  using G = FrGeom<K, M>;
+  for (int n = threadIdx.x; n < G::KT * 2 * 64; n += kBlock) had_s[n] = ((const u32x4*)fr_had_table<K>().w)[n];
+  // the sign words travel by value in the kernel arguments: a lane-indexed read is a load from the argument segment, as lut16_stage's
+  if ((int)threadIdx.x < G::SIGNW) sign_s[threadIdx.x] = (int)threadIdx.x < G::C / 32 ? r.sign[threadIdx.x] : 0u;   // zero for the zero segments
+  lut16_stage(lut, tab, a.shift);
+  __syncthreads();
+  for (int n = threadIdx.x; n < G::KT * G::KS * 64; n += kBlock) {   // the xor masks of operand n / 64 and lane n % 64
+    const uint32_t sbyte = ((const uint8_t*)sign_s)[fr_col0<M>(n / 64 / G::KS, n / 64 % G::KS, n % 64) >> 3];
+    u32x4 m;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) m[k] = (((sbyte >> (2 * k)) & 1u) << 15) | (((sbyte >> (2 * k + 1)) & 1u) << 31);
+    sgn_s[n] = m;
+  }
+  __syncthreads();   // the tables and the signs (workgroup-wide, once); everything behind it is private to the wavefront
+}
+
+// The stand-alone quantizer's lane code on the wavefront's row image: vector v of the row = ko v / (m / 8), chunk v % (m / 8).
+// MODE 0: values out; 1: values + the rotated rows (ROT_MAYBE: `rot_out` may be null); 2: E2M1 operand codes + group scales
+// (`outv`: the codes, `lut` staged from the code table)
+template <int K, int M, int MODE, bool ROT_MAYBE = false>
+__device__ __forceinline__ void fr_quant_image(const char* img, const uint16_t* lut, int lane, int64_t row, void* __restrict__ outv,
+                                               u32x4* __restrict__ rot_out, const FullRotArgs& r, const Lut16Args& a) {
+  using G = FrGeom<K, M>;
+#pragma unroll 1   // (unrolled, the passes' quantizer chains interleave and the C = 2304 code form runs out of registers)
+  for (int pv = 0; pv < G::NPASS; ++pv) {
+    const int v = pv * 64 + lane;
+    const bool live = v < G::VPR;   // a group (16 vectors, 16 lanes) is live or dead as a whole
+    const int at = live ? (v / (M / 8)) * G::STRIDE + (v % (M / 8)) * 16 : 0;
+    u32x4 w = *(const u32x4*)(img + at);
+    if (!live) w = u32x4{0, 0, 0, 0};
+    const uint32_t m = row_max_dpp<16>(vec_absmax16(w));
+    const RowScale16 s = row_scale16(m, a.fpos.gmax, a.inv_gpos);
+    if constexpr (MODE == 2) {
+      const uint32_t codes = codes_vec16(w, lut, a.shift, s.inv, s.inv_lo);
+      const uint32_t g = (uint32_t)v >> 4, l16 = (uint32_t)v & 15u, t = (uint32_t)row;
+      if (live) {
+        if (r.km_rows) {   // the k-major images (include/fpq.h), as rows16_codes_mx_kernel writes them
+          if (l16 == 0) ((float*)r.code_scales)[(int64_t)g * ((r.km_rows + 3u) & ~3u) + t] = (float)__builtin_bit_cast(_Float16, (uint16_t)(s.s16x2 & 0xFFFFu));
+          ((uint32_t*)outv)[(km4_off(t, g, l16 >> 2, r.km_rows) >> 2) + (l16 & 3u)] = codes;
+        } else {
+          if (l16 == 0) r.code_scales[row * (G::C / 128) + g] = (uint16_t)(s.s16x2 & 0xFFFFu);
+          __builtin_nontemporal_store(codes, (uint32_t*)outv + row * G::VPR + v);
+        }
+      }
+    } else {
+      const u32x4 o = quant_vec16<false>(w, lut, a.shift, s.inv, s.inv_lo, s.s16x2, 0.f, 0.f, 0u);
+      if (live) {
+        __builtin_nontemporal_store(o, (u32x4*)outv + row * G::VPR + v);
+        if constexpr (MODE == 1)
+          if (!ROT_MAYBE || rot_out) __builtin_nontemporal_store(w, rot_out + row * G::VPR + v);
+      }
+    }
+  }
+}
+
+// MODE: fr_quant_image's
 template <int K, int M, typename Tin, bool SMOOTH, int MODE>
 __global__ __launch_bounds__(kBlock, kFrWaves) void fullrot_quant_kernel(const void* __restrict__ xv, void* __restrict__ outv,
                                                                          u32x4* __restrict__ rot_out, int64_t rows, FullRotArgs r,
@@ -281,19 +341,7 @@ __global__ __launch_bounds__(kBlock, kFrWaves) void fullrot_quant_kernel(const v
   constexpr bool PREFETCH = G::KT * G::KS * 4 <= 16;
   FrRow<K, M> h;
   if (row < rows) fr_load_row<K, M, Tin, SMOOTH>(row_rsrc(row), smooth, lane, h);   // in flight while the tables are staged
-  for (int n = threadIdx.x; n < G::KT * 2 * 64; n += kBlock) had_s[n] = ((const u32x4*)fr_had_table<K>().w)[n];
-  // the sign words travel by value in the kernel arguments: a lane-indexed read is a load from the argument segment, as lut16_stage's
-  if ((int)threadIdx.x < G::SIGNW) sign_s[threadIdx.x] = (int)threadIdx.x < G::C / 32 ? r.sign[threadIdx.x] : 0u;   // zero for the zero segments
-  lut16_stage(lut, tab, a.shift);
-  __syncthreads();
-  for (int n = threadIdx.x; n < G::KT * G::KS * 64; n += kBlock) {   // the xor masks of operand n / 64 and lane n % 64
-    const uint32_t sbyte = ((const uint8_t*)sign_s)[fr_col0<M>(n / 64 / G::KS, n / 64 % G::KS, n % 64) >> 3];
-    u32x4 m;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) m[k] = (((sbyte >> (2 * k)) & 1u) << 15) | (((sbyte >> (2 * k + 1)) & 1u) << 31);
-    sgn_s[n] = m;
-  }
-  __syncthreads();   // the tables and the signs (workgroup-wide, once); everything below is private to the wavefront
+  fr_stage_tables<K, M>(r, a, tab, lut, sign_s, had_s, sgn_s);
   char* img = img_s[wave];
   const FrLane lc = fr_lane_consts(lane);
   while (row < rows) {
@@ -301,38 +349,30 @@ __global__ __launch_bounds__(kBlock, kFrWaves) void fullrot_quant_kernel(const v
     __builtin_amdgcn_wave_barrier();
     const int64_t next = row + step;
     if (PREFETCH && next < rows) fr_load_row<K, M, Tin, SMOOTH>(row_rsrc(next), smooth, lane, h);   // in flight under the quantizer
-    // the stand-alone quantizer's lane code on the row image: vector v of the row = ko v / (m / 8), chunk v % (m / 8)
-#pragma unroll 1   // (unrolled, the passes' quantizer chains interleave and the C = 2304 code form runs out of registers)
-    for (int pv = 0; pv < G::NPASS; ++pv) {
-      const int v = pv * 64 + lane;
-      const bool live = v < G::VPR;   // a group (16 vectors, 16 lanes) is live or dead as a whole
-      const int at = live ? (v / (M / 8)) * G::STRIDE + (v % (M / 8)) * 16 : 0;
-      u32x4 w = *(const u32x4*)(img + at);
-      if (!live) w = u32x4{0, 0, 0, 0};
-      const uint32_t m = row_max_dpp<16>(vec_absmax16(w));
-      const RowScale16 s = row_scale16(m, a.fpos.gmax, a.inv_gpos);
-      if constexpr (MODE == 2) {
-        const uint32_t codes = codes_vec16(w, lut, a.shift, s.inv, s.inv_lo);
-        const uint32_t g = (uint32_t)v >> 4, l16 = (uint32_t)v & 15u, t = (uint32_t)row;
-        if (live) {
-          if (r.km_rows) {   // the k-major images (include/fpq.h), as rows16_codes_mx_kernel writes them
-            if (l16 == 0) ((float*)r.code_scales)[(int64_t)g * ((r.km_rows + 3u) & ~3u) + t] = (float)__builtin_bit_cast(_Float16, (uint16_t)(s.s16x2 & 0xFFFFu));
-            ((uint32_t*)outv)[(km4_off(t, g, l16 >> 2, r.km_rows) >> 2) + (l16 & 3u)] = codes;
-          } else {
-            if (l16 == 0) r.code_scales[row * (G::C / 128) + g] = (uint16_t)(s.s16x2 & 0xFFFFu);
-            __builtin_nontemporal_store(codes, (uint32_t*)outv + row * G::VPR + v);
-          }
-        }
-      } else {
-        const u32x4 o = quant_vec16<false>(w, lut, a.shift, s.inv, s.inv_lo, s.s16x2, 0.f, 0.f, 0u);
-        if (live) {
-          __builtin_nontemporal_store(o, (u32x4*)outv + row * G::VPR + v);
-          if constexpr (MODE == 1) __builtin_nontemporal_store(w, rot_out + row * G::VPR + v);
-        }
-      }
-    }
+    fr_quant_image<K, M, MODE>(img, lut, lane, row, outv, rot_out, r, a);
     __builtin_amdgcn_wave_barrier();   // the image is rewritten by the next row
     row = next;
     if (!PREFETCH && row < rows) fr_load_row<K, M, Tin, SMOOTH>(row_rsrc(row), smooth, lane, h);
   }
+}
+
+// ---- the host side both launchers share ----
+// Persistent wavefronts, one row each at a time: the grid is what the chip holds resident - kFrCUs x kFrWaves workgroups of 4
+// wavefronts (the launch bounds' occupancy; LDS: 4 row images + the table, ~25 KiB per workgroup) - or one wavefront per row.
+inline int fullrot_grid(int64_t rows) { return grid_for((rows + kBlock / 64 - 1) / (kBlock / 64), (int64_t)kFrCUs * kFrWaves); }
+
+inline bool fullrot_width_built(int64_t cols) {
+  for (int c : kFullRotWidths)
+    if (cols == c) return true;
+  return false;
+}
+
+inline FullRotArgs fullrot_args(int cols, int64_t rows, const float* smooth, const uint32_t* sign_words, uint16_t* code_scales, bool km) {
+  FullRotArgs r;
+  r.smooth = smooth;
+  r.code_scales = code_scales;
+  r.km_rows = km ? (uint32_t)rows : 0u;
+  r.c_h = h2f(f2h(1.0f / __builtin_sqrtf((float)cols)));   // torch.tensor(C).sqrt() is float32; autocast makes Q fp16
+  for (int i = 0; i < kFrMaxSignWords; ++i) r.sign[i] = i < cols / 32 ? sign_words[i] : 0u;
+  return r;
 }

@@ -7,22 +7,13 @@ namespace {
 #include "fpq_rotate_mfma.h"   // the operand vector types, rq_rsrc
 #include "fpq_fullrot.h"
 
-// Persistent wavefronts, one row each at a time: the grid is what the chip holds resident - kFrCUs x kFrWaves workgroups of 4
-// wavefronts (the launch bounds' occupancy; LDS: 4 row images + the table, ~25 KiB per workgroup) - or one wavefront per row.
-inline int fullrot_grid(int64_t rows) { return grid_for((rows + kBlock / 64 - 1) / (kBlock / 64), (int64_t)kFrCUs * kFrWaves); }
-
 template <int K, int M, typename Tin>
 int launch_fullrot(const void* x, void* out, void* rot_out, int64_t rows, const float* smooth, const uint32_t* sign_words, int table_id,
                    hipStream_t st, uint16_t* code_scales, bool km) {
   const Lut16Host& h = lut16_host(table_id, table_id);
   if (!h.tab_valid) return FPQ_ERR_TABLE;
   const Lut16Tab& tab = code_scales ? lut16_mx_codes_e2m1() : h.tab;
-  FullRotArgs r;
-  r.smooth = smooth;
-  r.code_scales = code_scales;
-  r.km_rows = km ? (uint32_t)rows : 0u;
-  r.c_h = h2f(f2h(1.0f / __builtin_sqrtf((float)(K * M))));   // torch.tensor(C).sqrt() is float32; autocast makes Q fp16
-  for (int i = 0; i < kFrMaxSignWords; ++i) r.sign[i] = i < K * M / 32 ? sign_words[i] : 0u;
+  const FullRotArgs r = fullrot_args(K * M, rows, smooth, sign_words, code_scales, km);
   const dim3 grid(fullrot_grid(rows));
   return with_bool(smooth != nullptr, [&](auto sm) {
     constexpr bool SMOOTH = sm.value;
@@ -30,12 +21,6 @@ int launch_fullrot(const void* x, void* out, void* rot_out, int64_t rows, const 
     if (rot_out) return launch(fullrot_quant_kernel<K, M, Tin, SMOOTH, 1>, grid, 0, st, x, out, rot_out, rows, r, h.args, tab);
     return launch(fullrot_quant_kernel<K, M, Tin, SMOOTH, 0>, grid, 0, st, x, out, rot_out, rows, r, h.args, tab);
   });
-}
-
-inline bool fullrot_width_built(int64_t cols) {
-  for (int c : kFullRotWidths)
-    if (cols == c) return true;
-  return false;
 }
 
 }  // namespace

@@ -921,15 +921,25 @@ class FP4Linear(_ScaledOperandModule):
 
     @torch.no_grad()
     def adaln_operands(self, x, scale, shift, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
-                       eps: float = 1e-6, pending: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+                       eps: float = 1e-6, pending: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, full_width: bool = False):
         """The block's producer in front of this Linear - LayerNorm, adaLN modulate, smooth, rotate, per-group quantize of x [B, L,
         in_features] - in one launch, emitting (codes, scales) in the module's own activation format and layout
         (`rotation.adaln_rotate_quant_mx` for E2M1, `rotation.adaln_rotate_quant_g6` for E1M2 / E3M0; k-major iff the weight is):
         ready for `forward_operands` / `qkv_to_cache_operands`.  One call in front of every mat_qkv and fc1 of a mixed-format model.
         pending = (y, gate): a gated residual x + y.mul(gate) that has not been applied to x yet - what `ops.gate_residual(y, gate, x)`
         would compute - is applied by the same launch (`rotation.resid_adaln_rotate_quant_mx`, E2M1 activations, in_features <= 2560):
-        returns (x_new, codes, scales), x_new and the operands bit for bit those of the two calls."""
+        returns (x_new, codes, scales), x_new and the operands bit for bit those of the two calls.
+        full_width: the full-width rotation of `rotate_model(block_rotate=False)` instead of the 128-block form
+        (`rotation.adaln_rotate_quant_full_mx`; d: in_features signs) - E2M1 activations only, no pending=."""
         from . import rotation
+        if full_width:
+            if self.act_table != "e2m1":
+                raise NotImplementedError(f"adaln_operands(full_width=True): the fused full-width rotation emits E2M1 (FP4) operands only, "
+                                          f"not {self.act_table!r} - 6-bit operand forms are outside the full-width producer's scope")
+            if pending is not None:
+                raise NotImplementedError("adaln_operands(full_width=True): pending= has no full-width form (the gated residual is not "
+                                          "fused into the full-width producer) - apply ops.gate_residual first")
+            return rotation.adaln_rotate_quant_full_mx(x, scale, shift, d=d, smooth=smooth, eps=eps, kmajor=self.kmajor)
         if pending is not None:
             if self.act_table != "e2m1":
                 raise RuntimeError(f"{type(self).__name__}.adaln_operands: pending= needs an 'e2m1' activation (the 6-bit group producers "
@@ -1166,11 +1176,12 @@ class FP6GroupLinear(FP4Linear):
 
     @torch.no_grad()
     def adaln_operands(self, x, scale, shift, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
-                       eps: float = 1e-6, pending: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+                       eps: float = 1e-6, pending: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, full_width: bool = False):
         """FP4Linear.adaln_operands; an 'e2m3' / 'e3m2' activation comes from `rotation.adaln_rotate_quant_gf6` (byte for byte
-        quantize_gf6 of the rotated rows), any other format from the parent's producer; k-major iff the weight is an image."""
-        if pending is not None:   # (the parent refuses every activation format but 'e2m1')
-            return super().adaln_operands(x, scale, shift, d=d, smooth=smooth, eps=eps, pending=pending)
+        quantize_gf6 of the rotated rows), any other format from the parent's producer; k-major iff the weight is an image.
+        full_width goes to the parent, which owns the one format that has a full-width producer ('e2m1') and refuses the others."""
+        if pending is not None or full_width:   # (the parent refuses every activation format but 'e2m1')
+            return super().adaln_operands(x, scale, shift, d=d, smooth=smooth, eps=eps, pending=pending, full_width=full_width)
         if self.act_table not in _GF6_FULL:
             return super().adaln_operands(x, scale, shift, d=d, smooth=smooth, eps=eps)
         from . import rotation

@@ -334,6 +334,8 @@ _TOKEN = {"values": _family("fpq_adaln_rotate_quant_token_rows", max_c=2560, slo
 _FULL = _family("fpq_fullrot_quant_rows", full=True)
 _FULL_MX = _family("fpq_fullrot_quant_rows_codes_mx", km=True, table=False, seg=64, full=True)
 FULL_WIDTHS = (1920, 2304)             # the widths the library builds (include/fpq.h, fpq_fullrot_quant_rows)
+_FULL_ADALN = _family("fpq_fullrot_adaln_quant_rows", max_c=max(FULL_WIDTHS), slots=3, full=True)
+_FULL_ADALN_MX = _family("fpq_fullrot_adaln_quant_rows_codes_mx", km=True, table=False, max_c=max(FULL_WIDTHS), seg=64, full=True)
 _RESID = _family("fpq_resid_adaln_rotate_quant_rows", max_c=2560, slots=3)
 _RESID_MX = _family("fpq_resid_adaln_rotate_quant_rows_codes_mx", km=True, table=False, max_c=2560, seg=64)
 _RESID_TOKEN = {"values": _family("fpq_resid_adaln_rotate_quant_token_rows", max_c=2560, slots=4),
@@ -457,6 +459,40 @@ def rotate_quant_full_mx(x: torch.Tensor, d: Optional[torch.Tensor] = None, smoo
     rows: (codes uint8 [rows, C/2], scales fp16 [rows, C/128]), or (kmajor) the k-major images - codes [C/128, rows, 64], scales
     fp32 [C/128, rows rounded up to 4]."""
     return _rotate_full("rotate_quant_full_mx", _FULL_MX, x, None, d, smooth, kmajor)
+
+
+def _adaln_full_args(name: str, fam: _Family, x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor):
+    """_rotate_full's refusals, then _adaln_args' checks."""
+    if x.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError(f"{name}: x must be float16 or float32, got {x.dtype}")
+    if x.shape[-1] not in FULL_WIDTHS:
+        raise RuntimeError(f"{name}: the full-width rotation is built for the widths {FULL_WIDTHS}, got {x.shape[-1]}")
+    return _adaln_args(name, fam, x, scale, shift, None)
+
+
+def adaln_rotate_quant_full(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, table: str = "e2m1",
+                            d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                            return_intermediates: bool = False):
+    """act_quant( matmul( LN(x).mul(scale.add(1)).add_(shift).mul(smooth), Q ) ) in one launch, Q = get_orthogonal_matrix(C) - the
+    FULL-WIDTH matrix of rotate_quant_full: adaln_rotate_quant for the reference's `--rotate` without `--block_rotate`.
+
+    x: [B, L, C] fp16/fp32 on the GPU, C in FULL_WIDTHS; scale, shift: [B, 1, C] (or [B, C]), both fp16 or both fp32; d: the C signs
+    (default sign_vector(C, 42)).  Returns fp16 [B, L, C] (plus h and the rotated tensor when return_intermediates): h as
+    adaln_rotate_quant's, the rest rotate_quant_full(h) bit for bit."""
+    name = "adaln_rotate_quant_full"
+    c, seq, sc, sh, _ = _adaln_full_args(name, _FULL_ADALN, x, scale, shift)
+    return _produce(name, _FULL_ADALN, x, c, TABLE_IDS[table], d, smooth, False, 2 if return_intermediates else 0, sc, sh, seq, eps)
+
+
+def adaln_rotate_quant_full_mx(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, d: Optional[torch.Tensor] = None,
+                               smooth: Optional[torch.Tensor] = None, eps: float = 1e-6, kmajor: bool = False
+                               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """adaln_rotate_quant_full(x, scale, shift, "e2m1") emitting the FP4 GEMM's operands instead of values, byte for byte
+    gemm.quantize_mx of the rotated rows: (codes uint8 [B*L, C/2], scales fp16 [B*L, C/128]), or (kmajor) the k-major images - codes
+    [C/128, B*L, 64], scales fp32 [C/128, B*L rounded up to 4]."""
+    name = "adaln_rotate_quant_full_mx"
+    c, seq, sc, sh, _ = _adaln_full_args(name, _FULL_ADALN_MX, x, scale, shift)
+    return _produce(name, _FULL_ADALN_MX, x, c, 0, d, smooth, kmajor, 0, sc, sh, seq, eps)
 
 
 def adaln_rotate_quant_mx(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, d: Optional[torch.Tensor] = None,

@@ -1230,6 +1230,33 @@ int fpq_fullrot_quant_rows(const void* x, void* out, void* rotated_out, int64_t 
 int fpq_fullrot_quant_rows_codes_mx(const void* x, void* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
                                     const float* smooth, const uint32_t* sign_words_host, int kmajor, fpq_stream_t stream);
 
+/* The complete producer of tr/basic_var.py:263 / :266 in the FULL-WIDTH mode, one launch: fpq_adaln_rotate_quant_rows' LayerNorm and
+ * modulate in front of fpq_fullrot_quant_rows' rotation and quantizer (csrc/fpq_fulladaln.h):
+ *     h   = half( ((LayerNorm(x) * half(scale + 1)) + shift) * smooth )    (no affine, eps; the statistics of the raw x in fp32, always
+ *                                                                            centred; fp16 modulation adds the 1 in fp16)
+ *     y   = half( c_h * sum_j +-h_j )             (= h @ half(Q), Q the full-width matrix)
+ *     out = per-group(128) quant(y)
+ * x: [rows, cols] F16 / F32, cols == 1920 or 2304 (every other width: FPQ_ERR_SHAPE); scale, shift: [rows / rows_per_batch, cols] in
+ * mod_dtype (F16 or F32, both the same), row r takes entry r / rows_per_batch; smooth: device float[cols] or NULL;
+ * sign_words_host as in fpq_fullrot_quant_rows; h_out / rotated_out: NULL or fp16 [rows, cols] receiving h / y, each on its own;
+ * table_id: every symmetric table.
+ * Parity: y and out are fpq_fullrot_quant_rows(h) bit for bit; h is within tests/fulladaln_model.py's bound of the float64 chain (the
+ * bound of tests/adaln_model.py with this kernel's summation depth - 8 + 3 + 6 additions at 1920, 8 + 5 + 6 at 2304 - and no one-pass branch).
+ * Checks, in this order, before any launch: rows < 0, cols < 0, sign_words_host NULL, rows_per_batch <= 0 or rows not a multiple of
+ * rows_per_batch (FPQ_ERR_ARG); table_id (FPQ_ERR_TABLE); in_dtype, mod_dtype (FPQ_ERR_DTYPE); cols not a built width or
+ * rows >= 2^31 (FPQ_ERR_SHAPE); rows == 0 -> FPQ_OK, nothing is launched; x, out, scale or shift NULL, a pointer not 16-byte
+ * aligned (FPQ_ERR_ARG). */
+int fpq_fullrot_adaln_quant_rows(const void* x, void* out, void* h_out, void* rotated_out, int64_t rows, int64_t cols, int in_dtype,
+                                 const void* scale, const void* shift, int mod_dtype, int64_t rows_per_batch, float eps,
+                                 const float* smooth, const uint32_t* sign_words_host, int table_id, fpq_stream_t stream);
+/* The same launch emitting the FP4 GEMM's activation operands, as fpq_fullrot_quant_rows_codes_mx does for y (kmajor == 0: codes
+ * uint8 [rows, cols / 2], scales fp16 [rows, cols / 128]; kmajor != 0: the k-major images, the padding of the scale image is the
+ * caller's).  Checks: scales NULL with rows > 0 and a built width (FPQ_ERR_ARG), then those of fpq_fullrot_adaln_quant_rows (the
+ * table is FPQ_E2M1; FPQ_ERR_SHAPE also for a k-major image of 2 GiB or more). */
+int fpq_fullrot_adaln_quant_rows_codes_mx(const void* x, void* codes, void* scales, int64_t rows, int64_t cols, int in_dtype,
+                                          const void* scale, const void* shift, int mod_dtype, int64_t rows_per_batch, float eps,
+                                          const float* smooth, const uint32_t* sign_words_host, int kmajor, fpq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
