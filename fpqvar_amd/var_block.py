@@ -253,9 +253,14 @@ class GenerationBatch:
     def q_proj(self, t2d, gate, resid):       # x + proj(a).mul(gamma1), gate and residual applied in the GEMM epilogue
         return self.row.linear(*self.row.quantize(t2d, self.kmajor), *self.wop["proj"], None, gate, resid)
 
+    @property
+    def attn_scale(self):
+        """SelfAttention.scale (tr/basic_var.py:137-142): 1 under attn_l2_norm, else 0.25 / sqrt(head_dim) - not SDPA's head_dim ** -0.5"""
+        return 1.0 if self.attn_l2_norm else 0.25 * self.hd ** -0.5
+
     def attend(self, q, kc, vc, scale=None):   # q [B,L,H,c]; kc, vc [B,Ltot,H,c] (flash layout, as the KV runs use)
-        if scale is None and self.attn_l2_norm:
-            scale = 1.0
+        if scale is None:
+            scale = self.attn_scale
         o = Fn.scaled_dot_product_attention(q.transpose(1, 2), kc.transpose(1, 2), vc.transpose(1, 2), scale=scale)
         return o.transpose(1, 2).reshape(q.shape[0], q.shape[1], self.C)
 
@@ -328,7 +333,7 @@ class GenerationBatch:
                     h = Fn.gelu(Fn.linear(self.row.r_act(self, x2), self.wq["fc1"]), approximate="tanh")
                     x = x + Fn.linear(self.row.r_fc2(self, h), self.wq["fc2"]).mul(g2)
                 continue
-            scale = 1.0 if self.attn_l2_norm else hd ** -0.5
+            scale = self.attn_scale
             prod = None
             if pend is not None:   # the previous block's fc2 tail, applied by this block's first producer
                 x, prod = self.resid_producer(path, pend, x, sc1, sh1, self.s_qkv)
