@@ -256,6 +256,18 @@ _SIGS = {
     "fpq_fullrot_adaln_quant_rows_codes_mx": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
                                                           _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_void_p,
                                                           _c.POINTER(_c.c_uint32), _c.c_int, _c.c_void_p]),
+    # both full-width producers in front of the per-token FP6 quantizer (rotation.rotate_quant_full_token, adaln_rotate_quant_full_token):
+    # the per-group twins' lists with row_scales as the last output and, on the code forms, a table id in front of `int kmajor`
+    "fpq_fullrot_quant_token_rows": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
+                                                 _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_void_p]),
+    "fpq_fullrot_quant_token_rows_codes_f6": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
+                                                          _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int, _c.c_void_p]),
+    "fpq_fullrot_adaln_quant_token_rows": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
+                                                       _c.c_int64, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float,
+                                                       _c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_void_p]),
+    "fpq_fullrot_adaln_quant_token_rows_codes_f6": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
+                                                                _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_void_p,
+                                                                _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int, _c.c_void_p]),
     # the fc1 tail with its dual pair and the layout as arguments: the twin's list, then neg table, pos table, kmajor
     "fpq_gemm_a6w4_gelu_dual_pair": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
                                                  _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,

@@ -336,6 +336,11 @@ _FULL_MX = _family("fpq_fullrot_quant_rows_codes_mx", km=True, table=False, seg=
 FULL_WIDTHS = (1920, 2304)             # the widths the library builds (include/fpq.h, fpq_fullrot_quant_rows)
 _FULL_ADALN = _family("fpq_fullrot_adaln_quant_rows", max_c=max(FULL_WIDTHS), slots=3, full=True)
 _FULL_ADALN_MX = _family("fpq_fullrot_adaln_quant_rows_codes_mx", km=True, table=False, max_c=max(FULL_WIDTHS), seg=64, full=True)
+_FULL_TOKEN = {"values": _family("fpq_fullrot_quant_token_rows", slots=3, full=True),
+               "fp6": _family("fpq_fullrot_quant_token_rows_codes_f6", km=True, seg=96, row_scales=True, full=True)}
+_FULL_ADALN_TOKEN = {"values": _family("fpq_fullrot_adaln_quant_token_rows", max_c=max(FULL_WIDTHS), slots=4, full=True),
+                     "fp6": _family("fpq_fullrot_adaln_quant_token_rows_codes_f6", km=True, max_c=max(FULL_WIDTHS), seg=96, row_scales=True,
+                                    full=True)}
 _RESID = _family("fpq_resid_adaln_rotate_quant_rows", max_c=2560, slots=3)
 _RESID_MX = _family("fpq_resid_adaln_rotate_quant_rows_codes_mx", km=True, table=False, max_c=2560, seg=64)
 _RESID_TOKEN = {"values": _family("fpq_resid_adaln_rotate_quant_token_rows", max_c=2560, slots=4),
@@ -493,6 +498,54 @@ def adaln_rotate_quant_full_mx(x: torch.Tensor, scale: torch.Tensor, shift: torc
     name = "adaln_rotate_quant_full_mx"
     c, seq, sc, sh, _ = _adaln_full_args(name, _FULL_ADALN_MX, x, scale, shift)
     return _produce(name, _FULL_ADALN_MX, x, c, 0, d, smooth, kmajor, 0, sc, sh, seq, eps)
+
+
+def _full_token_form(name: str, forms, table: str, emit: str, kmajor: bool) -> _Family:
+    """adaln_rotate_quant_token's refusals - emit against table, kmajor only for the code forms - and the row of the form."""
+    if emit not in ("values", "fp6", "bf6"):
+        raise RuntimeError(f"{name}: unknown emit {emit!r}")
+    if table not in ("e2m3", "e3m2"):
+        raise RuntimeError(f"{name}: the per-token quantizer runs on the FP6 tables 'e2m3' / 'e3m2', got {table!r}")
+    if emit == "fp6" and table != "e2m3":
+        raise RuntimeError(f"{name}: emit='fp6' is the E2M3 operand format")
+    if emit == "bf6" and table != "e3m2":
+        raise RuntimeError(f"{name}: emit='bf6' is the E3M2 operand format")
+    if kmajor and emit == "values":
+        raise RuntimeError(f"{name}: kmajor is a layout of the FP6 operand codes (emit='fp6' / 'bf6')")
+    return forms["values" if emit == "values" else "fp6"]
+
+
+def rotate_quant_full_token(x: torch.Tensor, table: str = "e2m3", d: Optional[torch.Tensor] = None,
+                            smooth: Optional[torch.Tensor] = None, emit: str = "values", kmajor: bool = False,
+                            return_rotated: bool = False):
+    """rotate_quant_full for the per-token configurations (W6A6): out = fp6_quant_*_per_token_cuda( half(x*smooth) @ half(Q), 6 ) in
+    one launch, Q the FULL-WIDTH matrix, ONE scale per row.  x: [..., C] fp16 or fp32 on the GPU, C in FULL_WIDTHS; d: the C signs.
+    emit="values": fp16 of x's shape (and the rotated tensor with return_rotated - rotate_quant_full's bit for bit);
+    emit="fp6" (table e2m3) / "bf6" (table e3m2): (dense 6-bit codes uint8 [rows, C * 3 / 4], scales fp16 [rows]) - byte for byte
+    gemm.quantize_fp6 of the rotated rows, the operands of gemm.linear_fp6; kmajor: the codes as the activation side's k-major image
+    [C/128, rows, 96]."""
+    name = "rotate_quant_full_token"
+    fam = _full_token_form(name, _FULL_TOKEN, table, emit, kmajor)
+    if return_rotated and emit != "values":
+        raise RuntimeError(f"{name}: the rotated rows go out with emit='values' only")
+    return _rotate_full(name, fam, x, table, d, smooth, kmajor, 1 if return_rotated else 0)
+
+
+def adaln_rotate_quant_full_token(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, table: str = "e2m3",
+                                  d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                                  emit: str = "values", kmajor: bool = False, return_intermediates: bool = False):
+    """adaln_rotate_quant_token with the FULL-WIDTH matrix of rotate_quant_full: LayerNorm, modulate, smooth, x . Q, then
+    fp6_quant_*_per_token_cuda with one scale per token row - one launch (W6A6 under the reference's `--rotate` without
+    `--block_rotate`).  x: [B, L, C], C in FULL_WIDTHS; scale, shift: [B, 1, C] (or [B, C]), both fp16 or both fp32.
+    emit="values": fp16 [B, L, C] (plus h and the rotated tensor with return_intermediates: adaln_rotate_quant_full's bit for bit);
+    emit="fp6" / "bf6": (dense 6-bit codes uint8 [B*L, C * 3 / 4], scales fp16 [B*L]) for gemm.linear_fp6, kmajor: the k-major image
+    [C/128, B*L, 96]."""
+    name = "adaln_rotate_quant_full_token"
+    fam = _full_token_form(name, _FULL_ADALN_TOKEN, table, emit, kmajor)
+    if return_intermediates and emit != "values":
+        raise RuntimeError(f"{name}: the intermediates go out with emit='values' only")
+    c, seq, sc, sh, _ = _adaln_full_args(name, fam, x, scale, shift)
+    return _produce(name, fam, x, c, TABLE_IDS[table], d, smooth, kmajor, 2 if return_intermediates else 0, sc, sh, seq, eps)
 
 
 def adaln_rotate_quant_mx(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, d: Optional[torch.Tensor] = None,

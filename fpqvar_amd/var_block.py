@@ -145,6 +145,14 @@ ROWS = {
         linear_split=lambda *a, **kw: gemm.linear_fp6_qkv_to_cache(*a, **kw), linear_gelu_dual=None,
         weight=lambda w: qu.fp6_quant_e2m3_per_token_cuda(w, 6), weight_operands=_fp6_weight),
 }
+# rotation="full": Q is the dense randomized Hadamard matrix (the reference's `--rotate` without `--block_rotate`), so the two adaLN
+# producers of a config's row are the full-width ones; every other entry stays.  No gated-residual full-width producer exists.
+FULL_PRODUCERS = {
+    "w4a4": dict(values=lambda *a, sm: rot.adaln_rotate_quant_full(*a, "e2m1", smooth=sm),
+                 operands=lambda *a, sm, km: rot.adaln_rotate_quant_full_mx(*a, smooth=sm, kmajor=km)),
+    "w6a6": dict(values=lambda *a, sm: rot.adaln_rotate_quant_full_token(*a, "e2m3", smooth=sm),
+                 operands=lambda *a, sm, km: rot.adaln_rotate_quant_full_token(*a, "e2m3", smooth=sm, emit="fp6", kmajor=km)),
+}
 
 
 class GenerationBatch:
@@ -153,8 +161,12 @@ class GenerationBatch:
     def __init__(self, model: str = "d30-256", config: str = "w4a4", depth: Optional[int] = None,
                  batch_rows: Optional[int] = None, device=None, seed: int = 0, fused_fc1: bool = True, sdpa_in_f: bool = False,
                  kmajor: bool = True, qkv_to_cache: bool = True, attn_l2_norm: bool = False, qk_norm: str = "fused",
-                 kv_storage: str = "fp16", fuse_residual: bool = False):
+                 kv_storage: str = "fp16", fuse_residual: bool = False, rotation: str = "block"):
         assert model in MODELS and config in ("w4a4", "w6a6") and qk_norm in ("fused", "torch")
+        if rotation not in ("block", "full"):
+            raise ValueError(f"rotation must be 'block' or 'full', got {rotation!r}")
+        if rotation == "full" and fuse_residual:
+            raise ValueError("rotation='full' has no gated-residual producer: not with fuse_residual")
         if kv_storage not in ("fp16", "codes"):
             raise ValueError(f"kv_storage must be 'fp16' or 'codes', got {kv_storage!r}")
         if kv_storage == "codes" and sdpa_in_f:
@@ -170,6 +182,11 @@ class GenerationBatch:
         self.hd = self.C // self.H
         self.max_len = sum(p * p for p in self.patch_nums)
         self.W6, self.row = config == "w6a6", ROWS[config]
+        # "block": Q = 128-wide blocks (the run scripts' --block_rotate); "full": the dense randomized Hadamard matrix of size C,
+        # online through the full-width producers (C in rotation.FULL_WIDTHS)
+        self.rotation = rotation
+        if rotation == "full":
+            self.row = SimpleNamespace(**{**vars(self.row), **FULL_PRODUCERS[config], "resid_values": None, "resid_operands": None})
         self.fused_fc1 = fused_fc1 and self.row.linear_gelu_dual is not None
         self.sdpa_in_f = sdpa_in_f                              # path F with torch's SDPA instead of fpq_attention_blhc (rounds 1 - 4 timed it that way)
         self.fused_gelu_quant = fused_fc1                       # path F: GELU + fc2's input quantizer in one pass over the fc1 output
@@ -186,7 +203,7 @@ class GenerationBatch:
         self.gen = g
         self.s_qkv = torch.rand(C, device=dev, generator=g) + 0.5
         self.s_fc1 = torch.rand(C, device=dev, generator=g) + 0.5
-        q64 = rot.block_random_hadamard_matrix(C, 128, dev, 42)
+        q64 = rot.get_orthogonal_matrix(C, device=dev) if rotation == "full" else rot.block_random_hadamard_matrix(C, 128, dev, 42)
         self.q32 = q64.float()
 
         def lin_w(o, i, smooth=None, rotate=False):
@@ -415,6 +432,7 @@ class GenerationBatch:
     def describe(self) -> str:
         return (f"VAR-{self.model} transformer part, {self.depth} blocks x {len(self.patch_nums)} steps ({self.max_len} tokens), "
                 f"B={self.B} rows per token (CFG), {self.config.upper()} + FP6 KV cache, random weights"
+                + (", full-width rotation" if self.rotation == "full" else "")
                 + (f", attn_l2_norm (q / k norm: {self.qk_norm})" if self.attn_l2_norm else "")
                 + (", KV cache stored as FP6 codes + scales (PackedKVCache)" if self.kv_storage == "codes" else ""))
 

@@ -1257,6 +1257,45 @@ int fpq_fullrot_adaln_quant_rows_codes_mx(const void* x, void* codes, void* scal
                                           const void* scale, const void* shift, int mod_dtype, int64_t rows_per_batch, float eps,
                                           const float* smooth, const uint32_t* sign_words_host, int kmajor, fpq_stream_t stream);
 
+/* Both full-width producers in front of the PER-TOKEN quantizer (W6A6: per-token E2M3 / E3M2 activations, run.sh:7,10,22,25, under
+ * `--rotate` without `--block_rotate`): fpq_fullrot_quant_rows' / fpq_fullrot_adaln_quant_rows' launch with
+ *     out = fp6_quant_{e2m3,e3m2}_per_token_cuda(y, 6)      ONE scale per row of `cols` channels (tr/quant_utils.py:503-534)
+ * behind the rotation instead of the per-group quantizer (csrc/fpq_fulltoken.h).  The rotated row lies complete in the wavefront's
+ * LDS image when the quantizer starts: the row maximum is one pass over that image, no second pass over memory.
+ * Arguments as the per-group twins' (x, smooth, sign_words_host, the modulation block) and as the 128-block token forms'
+ * (fpq_adaln_rotate_quant_token_rows, _token_rows_codes_f6): row_scales is the last output pointer, fp16 [rows].
+ * cols == 1920 or 2304; EVERY other width is FPQ_ERR_SHAPE.  table_id: FPQ_E2M3 or FPQ_E3M2, everything else FPQ_ERR_TABLE.
+ * Values forms: out fp16 [rows, cols]; rotated_out, h_out, row_scales: NULL or fp16 [rows, cols] / [rows, cols] / [rows], each on its own.
+ * Code forms (the FP6 GEMM's activation operands, fpq_gemm_fp6_rows / fpq_gemm_f6_rows): codes = dense 6-bit codes of table_id,
+ * kmajor == 0: uint8 [rows, cols * 3 / 4]; kmajor != 0: the activation side's k-major image [cols / 128, rows, 96] (K-MAJOR OPERAND
+ * IMAGES above); row_scales fp16 [rows] in both layouts, required.  Every byte of the `rows` rows is written in either layout; a
+ * caller that pads the image's row count for a consumer owns the padding rows.
+ * Parity, all bit for bit: y (rotated_out) == fpq_fullrot_quant_rows' y for the same x, smooth and signs; h_out and y behind the
+ * adaLN front == fpq_fullrot_adaln_quant_rows' h and y (so both inherit the bounds of tests/fullrot_model.py / tests/fulladaln_model.py);
+ * out == fpq_quant_rows(y, cols = row length) and row_scales == that quantizer's scales; (codes, row_scales) ==
+ * fpq_quant_rows_codes_f6(y, table_id, kmajor) byte for byte, and level(code) * scale == out.  An all-zero y row gives scale 0 and
+ * +0 / code 0 everywhere; a row with a non-finite y gives what the stand-alone quantizer gives on that y; a row's scale depends on
+ * no other row.
+ * Checks, in this order, before any launch: rows < 0, cols < 0, sign_words_host NULL (adaLN forms: rows_per_batch <= 0 or rows not
+ * a multiple of rows_per_batch) (FPQ_ERR_ARG); table_id (FPQ_ERR_TABLE); in_dtype (adaLN forms: mod_dtype) (FPQ_ERR_DTYPE); cols not
+ * a built width, rows >= 2^31 or a k-major image of 2 GiB or more (FPQ_ERR_SHAPE); rows == 0 -> FPQ_OK, nothing is launched; x or
+ * out (adaLN forms: scale, shift) NULL, a pointer not 16-byte aligned (FPQ_ERR_ARG).  The code forms look at row_scales first: NULL
+ * with rows > 0 and a built width is FPQ_ERR_ARG.
+ * Additions that change no existing entry point: FPQ_VERSION stays, a caller looks the symbols up. */
+int fpq_fullrot_quant_token_rows(const void* x, void* out, void* rotated_out, void* row_scales, int64_t rows, int64_t cols, int in_dtype,
+                                 const float* smooth, const uint32_t* sign_words_host, int table_id, fpq_stream_t stream);
+int fpq_fullrot_quant_token_rows_codes_f6(const void* x, uint8_t* codes, void* row_scales, int64_t rows, int64_t cols, int in_dtype,
+                                          const float* smooth, const uint32_t* sign_words_host, int table_id, int kmajor,
+                                          fpq_stream_t stream);
+int fpq_fullrot_adaln_quant_token_rows(const void* x, void* out, void* h_out, void* rotated_out, void* row_scales, int64_t rows,
+                                       int64_t cols, int in_dtype, const void* scale, const void* shift, int mod_dtype,
+                                       int64_t rows_per_batch, float eps, const float* smooth, const uint32_t* sign_words_host,
+                                       int table_id, fpq_stream_t stream);
+int fpq_fullrot_adaln_quant_token_rows_codes_f6(const void* x, uint8_t* codes, void* row_scales, int64_t rows, int64_t cols, int in_dtype,
+                                                const void* scale, const void* shift, int mod_dtype, int64_t rows_per_batch, float eps,
+                                                const float* smooth, const uint32_t* sign_words_host, int table_id, int kmajor,
+                                                fpq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

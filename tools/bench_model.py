@@ -37,15 +37,18 @@ def main():
     ap.add_argument("--fuse-residual", action="store_true",
                     help="paths F / Q: every gated residual behind a torch GEMM is applied by the adaLN producer that follows it "
                          "(rotation.resid_adaln_rotate_quant*; GenerationBatch(fuse_residual=True)) - same results, fewer launches")
+    ap.add_argument("--rotation", default="block", choices=("block", "full"),
+                    help="block: Q of 128-wide blocks (the run scripts' --block_rotate); full: the dense randomized Hadamard matrix of size C "
+                         "through the full-width producers (GenerationBatch(rotation='full'); not with --fuse-residual)")
     ap.add_argument("--tuned-gemms", action="store_true", help="torch's own GEMMs with the recorded TunableOp selections (var_block.tuned_torch_gemms)")
     args = ap.parse_args()
     torch.manual_seed(0)
     gb = var_block.GenerationBatch(args.model, args.config, depth=args.depth, batch_rows=args.batch, device="cuda:0",
                                    fused_fc1=not args.unfused_fc1, sdpa_in_f=args.sdpa_in_f, kmajor=not args.row_major_operands,
                                    qkv_to_cache=not args.qkv_copy_in, attn_l2_norm=args.attn_l2_norm, qk_norm=args.qk_norm,
-                                   kv_storage="codes" if args.kv_codes else "fp16", fuse_residual=args.fuse_residual)
+                                   kv_storage="codes" if args.kv_codes else "fp16", fuse_residual=args.fuse_residual, rotation=args.rotation)
     res = {"workload": gb.describe(), "depth": gb.depth, "batch_rows": gb.B, "fc1_epilogue_fused": gb.fused_fc1, "kmajor_operands": gb.kmajor, "qkv_to_cache": gb.qkv_to_cache,
-           "attn_l2_norm": gb.attn_l2_norm, "qk_norm": gb.qk_norm, "kv_storage": gb.kv_storage, "fuse_residual": gb.fuse_residual, "library": _lib.build_tag()}
+           "attn_l2_norm": gb.attn_l2_norm, "qk_norm": gb.qk_norm, "kv_storage": gb.kv_storage, "fuse_residual": gb.fuse_residual, "rotation": gb.rotation, "library": _lib.build_tag()}
     paths = args.paths.split(",")
     import contextlib
     ctx = var_block.tuned_torch_gemms() if args.tuned_gemms else contextlib.nullcontext()
