@@ -161,7 +161,7 @@ class GenerationBatch:
     def __init__(self, model: str = "d30-256", config: str = "w4a4", depth: Optional[int] = None,
                  batch_rows: Optional[int] = None, device=None, seed: int = 0, fused_fc1: bool = True, sdpa_in_f: bool = False,
                  kmajor: bool = True, qkv_to_cache: bool = True, attn_l2_norm: bool = False, qk_norm: str = "fused",
-                 kv_storage: str = "fp16", fuse_residual: bool = False, rotation: str = "block"):
+                 kv_storage: str = "fp16", fuse_residual: bool = False, rotation: str = "block", tensors: Optional[dict] = None):
         assert model in MODELS and config in ("w4a4", "w6a6") and qk_norm in ("fused", "torch")
         if rotation not in ("block", "full"):
             raise ValueError(f"rotation must be 'block' or 'full', got {rotation!r}")
@@ -199,25 +199,39 @@ class GenerationBatch:
         # step ends with the plain gate_residual.  Same results, bit for bit.  Off by default.
         self.fuse_residual = bool(fuse_residual)
         C, HID, B = self.C, self.HID, self.B
+        # tensors: the batch's parameters from outside instead of the draws below (a recorded run of the reference, tests) - "w": the
+        # four UNQUANTIZED fp32 weights qkv [3C, C], proj [C, C], fc1 [4C, C], fc2 [C, 4C] before smoothing and rotation, "s_qkv" /
+        # "s_fc1" [C], "mods": per block the six [B, 1, C] fp16 tensors (gamma1, gamma2, scale1, scale2, shift1, shift2), and with
+        # attn_l2_norm "scale_mul": per block [1, H, 1, 1], "qkv_bias": per block [3C] = cat(q_bias, 0, v_bias).  All or nothing;
+        # without it every draw below happens as before, in the same order.
+        ext = self._check_tensors(tensors, attn_l2_norm)
         g = torch.Generator(device=dev).manual_seed(seed)
         self.gen = g
-        self.s_qkv = torch.rand(C, device=dev, generator=g) + 0.5
-        self.s_fc1 = torch.rand(C, device=dev, generator=g) + 0.5
+        if ext is None:
+            self.s_qkv = torch.rand(C, device=dev, generator=g) + 0.5
+            self.s_fc1 = torch.rand(C, device=dev, generator=g) + 0.5
+        else:
+            self.s_qkv, self.s_fc1 = (ext[n].detach().to(dev, torch.float32).contiguous() for n in ("s_qkv", "s_fc1"))
         q64 = rot.get_orthogonal_matrix(C, device=dev) if rotation == "full" else rot.block_random_hadamard_matrix(C, 128, dev, 42)
         self.q32 = q64.float()
 
-        def lin_w(o, i, smooth=None, rotate=False):
-            w = torch.randn(o, i, device=dev, generator=g) * 0.02
+        def lin_w(name, o, i, smooth=None, rotate=False):
+            w = torch.randn(o, i, device=dev, generator=g) * 0.02 if ext is None else ext["w"][name].detach().to(dev, torch.float32)
+            assert w.shape == (o, i), f"{name}: {tuple(w.shape)}, expected {(o, i)}"
             if smooth is not None:
                 w = rot.transform_weight(w, smooth)
             return rot.rotate_weight(w, q64) if rotate else w
 
-        w32 = {"qkv": lin_w(3 * C, C, self.s_qkv, True), "proj": lin_w(C, C), "fc1": lin_w(HID, C, self.s_fc1, True),
-               "fc2": lin_w(C, HID)}
+        w32 = {"qkv": lin_w("qkv", 3 * C, C, self.s_qkv, True), "proj": lin_w("proj", C, C), "fc1": lin_w("fc1", HID, C, self.s_fc1, True),
+               "fc2": lin_w("fc2", C, HID)}
         self.wq = {n: self.row.weight(w) for n, w in w32.items()}
         self.wop = {n: self.row.weight_operands(w32[n], kmajor) for n in ("qkv", "proj", "fc1")}   # operands of the matrix-core GEMMs
         del w32
-        self.mods = [[(torch.randn(B, 1, C, device=dev, generator=g) * 0.2).half() for _ in range(6)] for _ in range(self.depth)]
+        if ext is None:
+            self.mods = [[(torch.randn(B, 1, C, device=dev, generator=g) * 0.2).half() for _ in range(6)] for _ in range(self.depth)]
+        else:
+            self.mods = [[t.detach().to(dev, torch.float16).contiguous() for t in m] for m in ext["mods"]]
+            assert len(self.mods) == self.depth and all(len(m) == 6 and all(t.shape == (B, 1, C) for t in m) for m in self.mods)
         self.e2m1 = qu.fp4_e2m1_grid.to(dev)
         self.e2m3 = qu.fp6_e2m3_grid.to(dev)
         self.gneg = torch.tensor([-1.75, -1.5, -1.25, -1.0, -0.75, -0.5, -0.25, 0.0], device=dev)
@@ -228,7 +242,12 @@ class GenerationBatch:
         # a generator of their own: every other tensor is the same with and without the flag.  qk_norm: "fused" - paths F / Q
         # normalize inside the qkv-to-cache kernels; "torch" - the reference's lines between the existing kernels (A/B, tests).
         self.attn_l2_norm, self.qk_norm = attn_l2_norm, qk_norm
-        if attn_l2_norm:
+        if attn_l2_norm and ext is not None:
+            self.scale_mul = [t.detach().to(dev, torch.float32).reshape(1, heads, 1, 1).contiguous() for t in ext["scale_mul"]]
+            self.qkv_bias = [t.detach().to(dev, torch.float32).reshape(3 * C).contiguous() for t in ext["qkv_bias"]]
+            assert len(self.scale_mul) == self.depth == len(self.qkv_bias)
+            self.head_scale = [kv_cache.qk_norm_head_scale(sm) for sm in self.scale_mul]
+        elif attn_l2_norm:
             gn = torch.Generator(device=dev).manual_seed(seed + 7919)
             self.scale_mul = []
             for _ in range(self.depth):
@@ -238,6 +257,16 @@ class GenerationBatch:
             self.head_scale = [kv_cache.qk_norm_head_scale(sm) for sm in self.scale_mul]
             self.qkv_bias = [torch.cat((torch.randn(C, device=dev, generator=gn) * 0.1, torch.zeros(C, device=dev),
                                         torch.randn(C, device=dev, generator=gn) * 0.1)) for _ in range(self.depth)]
+
+    @staticmethod
+    def _check_tensors(tensors, attn_l2_norm):
+        """the `tensors` argument, complete, or None"""
+        if tensors is None:
+            return None
+        need = {"w", "s_qkv", "s_fc1", "mods"} | ({"scale_mul", "qkv_bias"} if attn_l2_norm else set())
+        if not need <= set(tensors) or set(tensors["w"]) != {"qkv", "proj", "fc1", "fc2"}:
+            raise ValueError(f"tensors must hold {sorted(need)}, and w the four weights qkv, proj, fc1, fc2")
+        return tensors
 
     # ---- the quantizers and Linears of paths F and Q, through the config's row --------------------------------------------------
     def act_then_fc2_quant(self, y):

@@ -1,7 +1,9 @@
 """A plain float64 model of one scale step of the reference's quantized AdaLN blocks: the independent statement that the three
 paths of GenerationBatch.step (R, F, Q) are held to.  CPU only.
 
-Written from the reference's text, not from fpqvar_amd/var_block.py (tr/ = models_fp_quant_transform_rotate/):
+Written from the reference's text, not from fpqvar_amd/var_block.py, and held to the reference's blocks RUNNING by
+tests/test_block_reference_host.py (tests/golden/reference_blocks*.npz: in fp32 the model reproduces the executed reference to
+float32 round-off).  tr/ = models_fp_quant_transform_rotate/:
   block      tr/basic_var.py:253-269   gamma1, gamma2, scale1, scale2, shift1, shift2;  x_1 = (LN(x) (1 + scale1) + shift1) s_qkv . Q,
                                        x = x + attn(x_1) gamma1;  x_2 = (LN(x) (1 + scale2) + shift2) s_fc1 . Q,  x = x + ffn(x_2) gamma2
   attention  tr/basic_var.py:136-142   softmax scale 0.25 / sqrt(head_dim); under attn_l2_norm 1, with scale_mul_1H11 clamped at log 100
@@ -69,7 +71,9 @@ class BlockParams:
     the fake-quantized weights (one set shared by every block, as GenerationBatch has it); mods: per block (gamma1, gamma2, scale1,
     scale2, shift1, shift2), each fp16 [B, 1, C]; s_qkv / s_fc1 [C] and Q [C, C]: activation-side smoothing and rotation (None: not
     applied); scale_mul (per block [1, H, 1, 1]) and qkv_bias (per block [3C]) select attn_l2_norm when given.  ideal: no quantizer
-    and no fp16 rounding anywhere - the block in exact arithmetic, for the compensation check."""
+    and no fp16 rounding anywhere - the block in exact arithmetic, for the compensation check.  fp32: the quantizers stay (on fp32
+    tensors) and the fp16 roundings go - what the reference holds when it runs without autocast on fp32 inputs; w is then the
+    weight quantizer's fp32 output (the KV quantizer's result is fp16 even so, tr/quant_utils.py:516)."""
     C: int
     H: int
     config: str
@@ -81,6 +85,7 @@ class BlockParams:
     scale_mul: Optional[List[torch.Tensor]] = None
     qkv_bias: Optional[List[torch.Tensor]] = None
     ideal: bool = False
+    fp32: bool = False
 
 
 def params_of(gb) -> BlockParams:
@@ -120,17 +125,19 @@ class BlockModel:
     # ---- roundings and quantizers ------------------------------------------------------------------------------------------------
     def _r(self, t: torch.Tensor) -> torch.Tensor:
         """where the reference holds an fp16 tensor"""
-        return t if self.p.ideal else t.half().double()
+        return t if self.p.ideal or self.p.fp32 else t.half().double()
 
     def _quant(self, which: str, t: torch.Tensor) -> torch.Tensor:
-        return t if self.p.ideal else CONFIGS[self.p.config][which](t.half()).double()
+        if self.p.ideal:
+            return t
+        return CONFIGS[self.p.config][which](t.float() if self.p.fp32 else t.half()).double()
 
     def quantize_cache(self, t: torch.Tensor) -> torch.Tensor:
         """fp6_quant_e2m3_per_token_cuda on a cached K or V [B, n, H, head_dim] (tr/basic_var.py:194-195): an fp16 cache in the plain
         regime, an fp32 one (here float64) under attn_l2_norm; the result is fp16 either way."""
         if self.p.ideal:
             return t
-        return orc.per_token_kernel_sem(t if self.l2 else t.half(), "e2m3").double()
+        return orc.per_token_kernel_sem(t if self.l2 else t.float() if self.p.fp32 else t.half(), "e2m3").double()
 
     def _linear(self, t: torch.Tensor, name: str) -> torch.Tensor:
         return self._r(t @ self.w[name].T)
@@ -140,7 +147,7 @@ class BlockModel:
         """(LN(x) (1 + scale) + shift) s . Q as the Linear's act_quant receives it"""
         mu = x.mean(dim=-1, keepdim=True)
         ln = (x - mu) / torch.sqrt(((x - mu) ** 2).mean(dim=-1, keepdim=True) + EPS)
-        one_plus = (scale.double() + 1.0) if self.p.ideal else (scale + 1).double()          # scale1.add(1): an fp16 add
+        one_plus = (scale.double() + 1.0) if self.p.ideal or self.p.fp32 else (scale + 1).double()   # scale1.add(1): an fp16 add
         h = ln * (scale.double() if m == "scale_without_one" else one_plus) + shift.double()
         h = self._r(h if s is None else h * s)
         return h if self.Q is None or m == "activation_not_rotated" else self._r(h @ self.Q)

@@ -47,6 +47,28 @@ def test_every_emulation_order_is_within_the_bound(C, x_dtype):
             assert worst <= 1.0 and where_ok, (order, mod_dtype, eps, worst, where_ok)
 
 
+LEARNED = ("var30/mat_qkv", "var30/fc1", "var36/mat_qkv", "var36/fc1")
+
+
+@pytest.mark.parametrize("x_dtype", (F16, F32))
+@pytest.mark.parametrize("vector", LEARNED)
+def test_every_emulation_order_is_within_the_bound_under_the_learned_vectors(vector, x_dtype):
+    """The smoothing vectors the reference ships (tests/golden/reference_blocks.npz: factors from 0.012 to 2.79, four of them
+    negative) instead of make_case's rand * 1.5 + 0.25, at their own widths, 17 rows (every family): the fp32 model stays within
+    bound() in each summation order.  Only because this holds is the bound a fair limit for the kernels under these vectors
+    (tests/test_gpu_learned_smoothing.py)."""
+    from tests import block_fixture as bf
+    smooth = bf.learned_vectors()[vector]
+    C = smooth.numel()
+    for mod_dtype in (F16, F32):
+        x, scale, shift, _ = am.make_case(1, 17, C, x_dtype, mod_dtype, False, 1e-6)
+        ref = am.reference(x, scale, shift, smooth, 1e-6, 17)
+        assert set(am.families(17, C)) == set(am.FAMILIES) and float(ref["h"][ref["finite"]].abs().max()) < 6.0e4
+        for order in _orders(C, x_dtype):
+            worst, where_ok = am.check(am.emulate(x, scale, shift, smooth, 1e-6, 17, order), ref, x_dtype, C)
+            assert worst <= 1.0 and where_ok, (order, mod_dtype, worst, where_ok)
+
+
 # mutation -> (C, x dtype, modulation dtype, eps, a family that must exceed the bound)
 CAUGHT_AT = {
     "one_pass_always": (1920, F32, F32, 1e-6, "rho_high"),                    # rho = 1000: E[x^2] - mean^2 cancels six digits

@@ -50,6 +50,23 @@ def test_the_emulation_is_within_the_bound(C, x_dtype):
     print(f"fulladaln model C={C} {x_dtype}: worst err / bound {worst_all:.4f}")
 
 
+@pytest.mark.parametrize("x_dtype", (F16, F32))
+@pytest.mark.parametrize("vector", ("var30/mat_qkv", "var30/fc1", "var36/mat_qkv", "var36/fc1"))
+def test_the_emulation_is_within_the_bound_under_the_learned_vectors(vector, x_dtype):
+    """The smoothing vectors the reference ships (tests/golden/reference_blocks.npz: factors from 0.012 to 2.79, four of them
+    negative) at their own widths, 17 rows (every family): the fp32 model stays within bound().  Only because this holds is the
+    bound a fair limit for the kernel under these vectors (tests/test_gpu_learned_smoothing.py)."""
+    from tests import block_fixture as bf
+    smooth = bf.learned_vectors()[vector]
+    C = smooth.numel()
+    for mod_dtype in (F16, F32):
+        x, scale, shift, _ = fa.make_case(1, 17, C, x_dtype, mod_dtype, False, 1e-6)
+        ref = fa.reference(x, scale, shift, smooth, 1e-6, 17)
+        assert set(am.families(17, C)) == set(fa.FAMILIES) and float(ref["h"][ref["finite"]].abs().max()) < 6.0e4
+        worst, where_ok = fa.check(fa.emulate(x, scale, shift, smooth, 1e-6, 17), ref, x_dtype, C)
+        assert worst <= 1.0 and where_ok, (mod_dtype, worst, where_ok)
+
+
 # mutation -> (C, x dtype, modulation dtype, a family that must exceed the bound).  Every mutant is caught on make_case's own rows.
 # batch_off_by_one moves only the last row of a batch entry to its neighbour's modulation: with (B, L) = (2, 13) that is row 12 - the
 # "var_eps" row at C = 1920, the "inf" row at C = 2304 (not a finite row) - hence C = 1920.  scale_plus_one_fp32 needs fp16 modulation.
