@@ -1,9 +1,9 @@
-// fpq_fulladaln.h - the FULL-WIDTH adaLN producer: LayerNorm + modulate in front of fpq_fullrot.h's rotation and quantizer, one launch:
+// fpq_fulladaln.h - the adaLN FRONT of the full-width producers: LayerNorm + modulate in front of fpq_fullrot.h's rotation, one launch:
 //     h = half( ((LayerNorm(x) * half(scale + 1)) + shift) * smooth ),  y = half(c_h * h . diag(D) . H_C^T),  out = per-group quant(y)
-// (tr/basic_var.py:263,266 in the reference's `--rotate` without `--block_rotate`).  Included by fpq_fulladaln.hip after fpq_adaln.h
-// (wave_sum_dpp) and fpq_fullrot.h.
+// (tr/basic_var.py:263,266 in the reference's `--rotate` without `--block_rotate`).  Included by fpq_fulladaln.hip and fpq_fulltoken.hip
+// after fpq_adaln.h (wave_sum_dpp) and fpq_fullrot.h.
 //
-// One wavefront owns a row at a time, as fullrot_quant_kernel's; what differs is in front of fullrot_transform_row:
+// FrAdalnFront is what fullrot_rows_kernel (fpq_fullrot.h) runs in front of fullrot_transform_row in place of FrPlainFront:
 //   1. The RAW row is loaded in the FrRow operand layout (fr_col0: 8 consecutive channels per lane and operand (T, s), a buffer
 //      resource of one row: the segments kj >= K read zeros) - 16 registers per lane for fp16 rows of 1920, 48 for fp32 rows of 2304.
 //   2. The statistics of the raw x in fp32, ALWAYS centred (the row is in registers: the second pass costs no memory traffic, so
@@ -19,21 +19,13 @@
 //      parameter would double the 24 kernels for the sake of 8 multiplies per operand.  Each operand's 8 (fp32 rows: 16) raw
 //      registers die as its 4 registers of h are made; the padding segments are set to zero, so fullrot_transform_row sees
 //      exactly what fr_load_row would have loaded from h: rotated and out are rotate_quant_full(h)'s bit for bit.
-//   4. fullrot_transform_row and fr_quant_image, unchanged and shared with fullrot_quant_kernel.
+//   4. The rest of the row loop - fullrot_transform_row, then the tail - is the one text every front shares.
 // tests/fulladaln_model.py carries the bound on h (depth 8 + KT KS - 1 + 6 additions) and a model of this arithmetic in source order.
 #pragma once
 
-// a raw row of at most this many registers per lane is prefetched under the quantizer: fp16 rows of 1920, as fullrot_quant_kernel's
+// a raw row of at most this many registers per lane is prefetched under the quantizer: fp16 rows of 1920, as FrPlainFront's
 // (at 32 - fp32 rows of 1920, fp16 rows of 2304 - each of the 12 forms it adds spills 1 - 22 registers at four wavefronts per SIMD)
 constexpr int kFaPrefetchRegs = 16;
-
-struct FullAdalnArgs {
-  const void* scale;          // [rows / rows_per_batch][C] in the modulation dtype
-  const void* shift;
-  uint16_t* h_out;            // MODE 1: fp16 [rows][C] receiving h, or nullptr
-  uint32_t rows_per_batch;
-  float eps;
-};
 
 // A raw row as it is loaded: the 8 channels of lane (i, q) and operand (T, s) in one (fp16 rows) or two (fp32) 16-byte vectors
 template <int K, int M, typename Tin>
@@ -180,53 +172,37 @@ __device__ __forceinline__ void fa_modulate(const FaRaw<K, M, Tin>& x, float rst
     }
 }
 
-// Wavefronts per SIMD the launch bounds ask for: fullrot_quant_kernel's four, but three where 48 raw registers (fp32 rows of 2304) meet
+// Wavefronts per SIMD the launch bounds ask for: the plain front's four, but three where 48 raw registers (fp32 rows of 2304) meet
 // 32 of modulation loads per operand (fp32 scale, shift and smooth): that one form spills 4 - 6 registers at four.
 template <int K, int M, typename Tin, typename Tmod>
 constexpr int kFaWaves = (FrGeom<K, M>::KT * FrGeom<K, M>::KS * 4 * (int)sizeof(Tin) / 2 > 32 && sizeof(Tmod) == 4) ? 3 : kFrWaves;
 
-// MODE: fr_quant_image's (1: h and the rotated rows go out where their pointers are not null)
-template <int K, int M, typename Tin, typename Tmod, int MODE>
-__global__ __launch_bounds__(kBlock, (kFaWaves<K, M, Tin, Tmod>)) void fullrot_adaln_kernel(const void* __restrict__ xv, void* __restrict__ outv,
-                                                                         u32x4* __restrict__ rot_out, int64_t rows, FullRotArgs r,
-                                                                         FullAdalnArgs ad, Lut16Args a, Lut16Tab tab) {
+// The adaLN front of fullrot_rows_kernel (FrPlainFront's members).  EMIT: the tail's (FrTail::EMIT) - h goes out where ad.h_out is
+// given; no bytes behind a null pointer: the stores are dropped
+template <int K_, int M_, typename Tin_, typename Tmod, bool EMIT>
+struct FrAdalnFront {
+  static constexpr int K = K_, M = M_, WAVES = kFaWaves<K, M, Tin_, Tmod>;
   using G = FrGeom<K, M>;
-  __shared__ __attribute__((aligned(16))) uint16_t lut[kLutLdsEntries];
-  __shared__ __attribute__((aligned(16))) char img_s[kBlock / 64][G::IMG];
-  __shared__ uint32_t sign_s[G::SIGNW];
-  __shared__ u32x4 had_s[G::KT * 2 * 64];
-  __shared__ u32x4 sgn_s[G::KT * G::KS * 64];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t step = (int64_t)gridDim.x * (kBlock / 64);
-  int64_t row = (int64_t)blockIdx.x * (kBlock / 64) + wave;
-  const bool has_smooth = r.smooth != nullptr;
-  const __amdgpu_buffer_rsrc_t smooth = rq_rsrc(r.smooth, has_smooth ? G::C * 4 : 0);
-  auto row_rsrc = [&](int64_t t) { return rq_rsrc((const char*)xv + t * (G::C * (int64_t)sizeof(Tin)), G::C * (int)sizeof(Tin)); };
-  // the next raw row's loads are issued under the quantizer where its registers fit beside it (the census: profiles/adaln_full_ab.txt)
-  constexpr bool PREFETCH = G::KT * G::KS * 4 * FaRaw<K, M, Tin>::W <= kFaPrefetchRegs;
-  FaRaw<K, M, Tin> x;
-  if (row < rows) fa_load_raw<K, M, Tin>(row_rsrc(row), lane, x);   // in flight while the tables are staged
-  fr_stage_tables<K, M>(r, a, tab, lut, sign_s, had_s, sgn_s);
-  char* img = img_s[wave];
-  const FrLane lc = fr_lane_consts(lane);
-  while (row < rows) {
+  using Tin = Tin_;
+  using Raw = FaRaw<K, M, Tin>;
+  static constexpr bool PREFETCH = G::KT * G::KS * 4 * Raw::W <= kFaPrefetchRegs;   // the census: profiles/adaln_full_ab.txt
+  const FullAdalnArgs& ad;
+  bool has_smooth;
+  __amdgpu_buffer_rsrc_t smooth;
+  __device__ __forceinline__ FrAdalnFront(const FullRotArgs& r, const FullAdalnArgs& ad_)
+      : ad(ad_), has_smooth(r.smooth != nullptr), smooth(rq_rsrc(r.smooth, r.smooth != nullptr ? G::C * 4 : 0)) {}
+  __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t src, int lane, Raw& x) const { fa_load_raw<K, M, Tin>(src, lane, x); }
+  __device__ __forceinline__ FrRow<K, M> row(const Raw& x, int64_t row, int lane) const {
     const uint32_t b = (uint32_t)row / ad.rows_per_batch;   // rows < 2^31
     const int64_t mod_at = (int64_t)b * (G::C * (int64_t)sizeof(Tmod));
-    const bool emit_h = MODE == 1 && ad.h_out != nullptr;
+    const bool emit_h = EMIT && ad.h_out != nullptr;
     FrRow<K, M> h;
     float rstd, nm;
     fa_stats<K, M, Tin>(x, lane, ad.eps, rstd, nm);
-    fa_modulate<K, M, Tin, Tmod, MODE == 1>(x, rstd, nm, rq_rsrc((const char*)ad.scale + mod_at, G::C * (int)sizeof(Tmod)),
-                                            rq_rsrc((const char*)ad.shift + mod_at, G::C * (int)sizeof(Tmod)), smooth, has_smooth,
-                                            rq_rsrc(emit_h ? ad.h_out + row * G::C : nullptr, emit_h ? G::C * 2 : 0), lane, h);
-    fullrot_transform_row<K, M>(h, sgn_s, had_s, lc, r.c_h, img, lane);
-    __builtin_amdgcn_wave_barrier();
-    const int64_t next = row + step;
-    if (PREFETCH && next < rows) fa_load_raw<K, M, Tin>(row_rsrc(next), lane, x);   // in flight under the quantizer
-    fr_quant_image<K, M, MODE, true>(img, lut, lane, row, outv, rot_out, r, a);
-    __builtin_amdgcn_wave_barrier();   // the image is rewritten by the next row
-    row = next;
-    if (!PREFETCH && row < rows) fa_load_raw<K, M, Tin>(row_rsrc(row), lane, x);
+    fa_modulate<K, M, Tin, Tmod, EMIT>(x, rstd, nm, rq_rsrc((const char*)ad.scale + mod_at, G::C * (int)sizeof(Tmod)),
+                                       rq_rsrc((const char*)ad.shift + mod_at, G::C * (int)sizeof(Tmod)), smooth, has_smooth,
+                                       rq_rsrc(emit_h ? ad.h_out + row * G::C : nullptr, emit_h ? G::C * 2 : 0), lane, h);
+    return h;
   }
-}
+};
+

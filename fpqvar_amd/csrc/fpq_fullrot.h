@@ -25,8 +25,10 @@
 //      out == fpq_quant_rows(y) / fpq_quant_rows_codes_mx[_km](y) by construction.
 // Numerics: +-1 operands; every rounding is an fp32 rounding of a partial sum inside an MFMA (at most m - 1 in stage 1, 3 K - 1 in
 // stage 2: K segments x three pieces), one of the product with c_h, one to fp16: tests/fullrot_model.py carries the bound.
-// Built widths: kFullRotWidths.  The transform (fullrot_transform_row), the table staging (fr_stage_tables) and the quantizer tail
-// (fr_quant_image) are device functions of their own: the full-width adaLN producer (fpq_fulladaln.h) calls them behind its LayerNorm.
+// Built widths: kFullRotWidths.  The row loop is written ONCE, fullrot_rows_kernel<Front, Tail> at the end of this file: every
+// full-width producer is an instantiation of it.  A FRONT makes a row's operands (FrPlainFront here: fr_load_row; FrAdalnFront in
+// fpq_fulladaln.h: LayerNorm + modulate), a TAIL (FrTail) names what runs on the rotated row's LDS image: fr_quant_image here, one
+// scale per 128 elements, or fr_token_image (fpq_fulltoken.h), one per row.  The host side of all of them: fpq_fullrot_launch.h.
 #pragma once
 
 typedef __bf16 fr_bf8_t __attribute__((ext_vector_type(8)));
@@ -38,10 +40,30 @@ constexpr int kFrCUs = 256;
 
 struct FullRotArgs {
   const float* smooth;      // device float[C] or nullptr
-  uint16_t* code_scales;    // codes form: the group scales (fp16 [rows][G], k-major: fp32 [G][rows rounded up to 4])
+  uint16_t* code_scales;    // per group, codes: the group scales (fp16 [rows][G], k-major: fp32 [G][rows rounded up to 4]); per token: fp16 [rows]
   uint32_t km_rows;         // codes into a k-major image of this many rows; 0: row-major
   float c_h;                // float(half(float32(1 / sqrt(C))))
   uint32_t sign[kFrMaxSignWords];   // bit j set <=> D[j] == -1
+};
+
+struct FullAdalnArgs {      // what FrAdalnFront (fpq_fulladaln.h) takes beside them; here because the one host path fills it
+  const void* scale;          // [rows / rows_per_batch][C] in the modulation dtype
+  const void* shift;
+  uint16_t* h_out;            // FrTail::EMIT: fp16 [rows][C] receiving h, or nullptr
+  uint32_t rows_per_batch;
+  float eps;
+};
+
+// What a tail writes.  kValues: fp16 values (the per-token tail: the rotated rows too where `rot_out` is given); kEmit, the per-group
+// tail only: values + the rotated rows; kCodes: operand codes + scales (`outv`: the codes, `lut` staged from the code table)
+enum class FrMode { kValues, kEmit, kCodes };
+
+// The tail of a kernel.  TOKEN: fr_token_image, else fr_quant_image; ROT_MAYBE (kEmit): `rot_out` may be null.  EMIT: the form whose
+// intermediates - the rotated rows, a front's h - go out where their pointers are given
+template <bool TOKEN_, FrMode MODE_, bool ROT_MAYBE_>
+struct FrTail {
+  static constexpr bool TOKEN = TOKEN_, ROT_MAYBE = ROT_MAYBE_, EMIT = MODE_ == (TOKEN_ ? FrMode::kValues : FrMode::kEmit);
+  static constexpr FrMode MODE = MODE_;
 };
 
 // hadK as stage 2's A operands: w[mo][tp][lane][.] = the 8 bf16 values hadK[16 mo + lane % 16][16 (2 tp + e / 4) + 4 (lane / 16) + e % 4],
@@ -280,12 +302,11 @@ __device__ __forceinline__ void fr_stage_tables(const FullRotArgs& r, const Lut1
   __syncthreads();   // the tables and the signs (workgroup-wide, once); everything behind it is private to the wavefront
 }
 
-// The stand-alone quantizer's lane code on the wavefront's row image: vector v of the row = ko v / (m / 8), chunk v % (m / 8).
-// MODE 0: values out; 1: values + the rotated rows (ROT_MAYBE: `rot_out` may be null); 2: E2M1 operand codes + group scales
-// (`outv`: the codes, `lut` staged from the code table)
-template <int K, int M, int MODE, bool ROT_MAYBE = false>
+// The per-group tail: the stand-alone quantizer's lane code on the wavefront's row image: vector v of the row = ko v / (m / 8), chunk
+// v % (m / 8).  MODE: FrMode's; ROT_MAYBE: FrTail's; code_scales, km_rows: FullRotArgs', by value (fullrot_rows_kernel's note)
+template <int K, int M, FrMode MODE, bool ROT_MAYBE>
 __device__ __forceinline__ void fr_quant_image(const char* img, const uint16_t* lut, int lane, int64_t row, void* __restrict__ outv,
-                                               u32x4* __restrict__ rot_out, const FullRotArgs& r, const Lut16Args& a) {
+                                               u32x4* __restrict__ rot_out, uint16_t* code_scales, uint32_t km_rows, const Lut16Args& a) {
   using G = FrGeom<K, M>;
 #pragma unroll 1   // (unrolled, the passes' quantizer chains interleave and the C = 2304 code form runs out of registers)
   for (int pv = 0; pv < G::NPASS; ++pv) {
@@ -296,15 +317,15 @@ __device__ __forceinline__ void fr_quant_image(const char* img, const uint16_t* 
     if (!live) w = u32x4{0, 0, 0, 0};
     const uint32_t m = row_max_dpp<16>(vec_absmax16(w));
     const RowScale16 s = row_scale16(m, a.fpos.gmax, a.inv_gpos);
-    if constexpr (MODE == 2) {
+    if constexpr (MODE == FrMode::kCodes) {
       const uint32_t codes = codes_vec16(w, lut, a.shift, s.inv, s.inv_lo);
       const uint32_t g = (uint32_t)v >> 4, l16 = (uint32_t)v & 15u, t = (uint32_t)row;
       if (live) {
-        if (r.km_rows) {   // the k-major images (include/fpq.h), as rows16_codes_mx_kernel writes them
-          if (l16 == 0) ((float*)r.code_scales)[(int64_t)g * ((r.km_rows + 3u) & ~3u) + t] = (float)__builtin_bit_cast(_Float16, (uint16_t)(s.s16x2 & 0xFFFFu));
-          ((uint32_t*)outv)[(km4_off(t, g, l16 >> 2, r.km_rows) >> 2) + (l16 & 3u)] = codes;
+        if (km_rows) {   // the k-major images (include/fpq.h), as rows16_codes_mx_kernel writes them
+          if (l16 == 0) ((float*)code_scales)[(int64_t)g * ((km_rows + 3u) & ~3u) + t] = (float)__builtin_bit_cast(_Float16, (uint16_t)(s.s16x2 & 0xFFFFu));
+          ((uint32_t*)outv)[(km4_off(t, g, l16 >> 2, km_rows) >> 2) + (l16 & 3u)] = codes;
         } else {
-          if (l16 == 0) r.code_scales[row * (G::C / 128) + g] = (uint16_t)(s.s16x2 & 0xFFFFu);
+          if (l16 == 0) code_scales[row * (G::C / 128) + g] = (uint16_t)(s.s16x2 & 0xFFFFu);
           __builtin_nontemporal_store(codes, (uint32_t*)outv + row * G::VPR + v);
         }
       }
@@ -312,19 +333,45 @@ __device__ __forceinline__ void fr_quant_image(const char* img, const uint16_t* 
       const u32x4 o = quant_vec16<false>(w, lut, a.shift, s.inv, s.inv_lo, s.s16x2, 0.f, 0.f, 0u);
       if (live) {
         __builtin_nontemporal_store(o, (u32x4*)outv + row * G::VPR + v);
-        if constexpr (MODE == 1)
+        if constexpr (MODE == FrMode::kEmit)
           if (!ROT_MAYBE || rot_out) __builtin_nontemporal_store(w, rot_out + row * G::VPR + v);
       }
     }
   }
 }
+// the per-token tail (fpq_fulltoken.h)
+template <int K, int M, FrMode MODE>
+__device__ __forceinline__ void fr_token_image(const char* img, const uint16_t* lut, int lane, int64_t row, void* __restrict__ outv,
+                                               u32x4* __restrict__ rot_out, uint16_t* code_scales, uint32_t km_rows, const Lut16Args& a);
 
-// MODE: fr_quant_image's
-template <int K, int M, typename Tin, bool SMOOTH, int MODE>
-__global__ __launch_bounds__(kBlock, kFrWaves) void fullrot_quant_kernel(const void* __restrict__ xv, void* __restrict__ outv,
-                                                                         u32x4* __restrict__ rot_out, int64_t rows, FullRotArgs r,
-                                                                         Lut16Args a, Lut16Tab tab) {
+// The plain front: the row is loaded as the operands themselves, h = half(x * smooth) (fr_load_row).  What a front owns: Raw, the
+// row as load() leaves it in registers; row(), Raw -> the FrRow of h; PREFETCH, whether the next row's load() is issued under the
+// tail - where Raw fits beside the quantizer's registers - or behind it; WAVES, the wavefronts per SIMD of the launch bounds.
+template <int K_, int M_, typename Tin_, bool SMOOTH>
+struct FrPlainFront {
+  static constexpr int K = K_, M = M_, WAVES = kFrWaves;
+  using Tin = Tin_;
+  using Raw = FrRow<K, M>;
+  // 16 registers at C = 1920; the 24 of C = 2304 spill at four wavefronts per SIMD
+  static constexpr bool PREFETCH = FrGeom<K, M>::KT * FrGeom<K, M>::KS * 4 <= 16;
+  __amdgpu_buffer_rsrc_t smooth;
+  __device__ __forceinline__ FrPlainFront(const FullRotArgs& r) : smooth(rq_rsrc(r.smooth, SMOOTH ? K * M * 4 : 0)) {}
+  __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t src, int lane, Raw& x) const { fr_load_row<K, M, Tin, SMOOTH>(src, smooth, lane, x); }
+  __device__ __forceinline__ const FrRow<K, M>& row(const Raw& x, int64_t, int) const { return x; }
+};
+
+// THE row loop of every full-width producer.  FrontArgs: the kernel arguments of the front beside FullRotArgs (none, or
+// FullAdalnArgs), given explicitly at the instantiation.  Four things keep the machine code what separate kernels had (DESIGN.md
+// 4g): the loop is the __global__ function itself, not a device function under per-family wrappers; a front without arguments
+// has NO parameter, not an empty one; the tail is called here, not through a member of the tag; and it takes the two fields of
+// FullRotArgs it reads by value, not the block by reference.
+template <typename Front, typename Tail, typename... FrontArgs>
+__global__ __launch_bounds__(kBlock, Front::WAVES) void fullrot_rows_kernel(const void* __restrict__ xv, void* __restrict__ outv,
+                                                                        u32x4* __restrict__ rot_out, int64_t rows, FullRotArgs r,
+                                                                        FrontArgs... fa, Lut16Args a, Lut16Tab tab) {
+  constexpr int K = Front::K, M = Front::M;
   using G = FrGeom<K, M>;
+  using Tin = typename Front::Tin;
   __shared__ __attribute__((aligned(16))) uint16_t lut[kLutLdsEntries];
   __shared__ __attribute__((aligned(16))) char img_s[kBlock / 64][G::IMG];
   __shared__ uint32_t sign_s[G::SIGNW];
@@ -334,29 +381,28 @@ __global__ __launch_bounds__(kBlock, kFrWaves) void fullrot_quant_kernel(const v
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t step = (int64_t)gridDim.x * (kBlock / 64);
   int64_t row = (int64_t)blockIdx.x * (kBlock / 64) + wave;
-  const __amdgpu_buffer_rsrc_t smooth = rq_rsrc(r.smooth, SMOOTH ? G::C * 4 : 0);
+  const Front front(r, fa...);
   auto row_rsrc = [&](int64_t t) { return rq_rsrc((const char*)xv + t * (G::C * (int64_t)sizeof(Tin)), G::C * (int)sizeof(Tin)); };
-  // the next row's loads are issued under the quantizer where its 16-byte vectors fit beside it: C = 1920 (16 registers; the 24 of
-  // C = 2304 spill at four wavefronts per SIMD)
-  constexpr bool PREFETCH = G::KT * G::KS * 4 <= 16;
-  FrRow<K, M> h;
-  if (row < rows) fr_load_row<K, M, Tin, SMOOTH>(row_rsrc(row), smooth, lane, h);   // in flight while the tables are staged
+  constexpr bool PREFETCH = Front::PREFETCH;
+  typename Front::Raw x;
+  if (row < rows) front.load(row_rsrc(row), lane, x);   // in flight while the tables are staged
   fr_stage_tables<K, M>(r, a, tab, lut, sign_s, had_s, sgn_s);
   char* img = img_s[wave];
   const FrLane lc = fr_lane_consts(lane);
   while (row < rows) {
-    fullrot_transform_row<K, M>(h, sgn_s, had_s, lc, r.c_h, img, lane);
+    fullrot_transform_row<K, M>(front.row(x, row, lane), sgn_s, had_s, lc, r.c_h, img, lane);
     __builtin_amdgcn_wave_barrier();
     const int64_t next = row + step;
-    if (PREFETCH && next < rows) fr_load_row<K, M, Tin, SMOOTH>(row_rsrc(next), smooth, lane, h);   // in flight under the quantizer
-    fr_quant_image<K, M, MODE>(img, lut, lane, row, outv, rot_out, r, a);
+    if (PREFETCH && next < rows) front.load(row_rsrc(next), lane, x);   // in flight under the quantizer
+    if constexpr (Tail::TOKEN) fr_token_image<K, M, Tail::MODE>(img, lut, lane, row, outv, rot_out, r.code_scales, r.km_rows, a);
+    else fr_quant_image<K, M, Tail::MODE, Tail::ROT_MAYBE>(img, lut, lane, row, outv, rot_out, r.code_scales, r.km_rows, a);
     __builtin_amdgcn_wave_barrier();   // the image is rewritten by the next row
     row = next;
-    if (!PREFETCH && row < rows) fr_load_row<K, M, Tin, SMOOTH>(row_rsrc(row), smooth, lane, h);
+    if (!PREFETCH && row < rows) front.load(row_rsrc(row), lane, x);
   }
 }
 
-// ---- the host side both launchers share ----
+// ---- the host side (fpq_fullrot_launch.h) ----
 // Persistent wavefronts, one row each at a time: the grid is what the chip holds resident - kFrCUs x kFrWaves workgroups of 4
 // wavefronts (the launch bounds' occupancy; LDS: 4 row images + the table, ~25 KiB per workgroup) - or one wavefront per row.
 inline int fullrot_grid(int64_t rows) { return grid_for((rows + kBlock / 64 - 1) / (kBlock / 64), (int64_t)kFrCUs * kFrWaves); }

@@ -1,17 +1,16 @@
-// fpq_fulltoken.h - the PER-TOKEN quantizer tail of the full-width rotation (W6A6: per-token E2M3 / E3M2 activations): a second
-// tail beside fr_quant_image on the wavefront's row image, and the two kernels that run it - behind the plain rotation
-// (fpq_fullrot.h) and behind the adaLN front (fpq_fulladaln.h).  Included by fpq_fulltoken.hip after those two.
+// fpq_fulltoken.h - the PER-TOKEN quantizer tail of the full-width rotation (W6A6: per-token E2M3 / E3M2 activations): the second
+// tail beside fr_quant_image on the wavefront's row image, run by fullrot_rows_kernel (fpq_fullrot.h) under FrTail<true, ..> behind
+// either front.  Included by fpq_fulltoken.hip after fpq_fullrot.h and fpq_fulladaln.h.
 //
-// Everything in front of the tail is the parents' code, called unchanged: fr_load_row / fa_load_raw, fa_stats, fa_modulate,
-// fr_stage_tables, fullrot_transform_row.  When the transform returns, the rotated fp16 row y sits complete in the wavefront's
-// LDS image, so ONE scale per row costs no second pass over memory:
+// When the transform returns, the rotated fp16 row y sits complete in the wavefront's LDS image, so ONE scale per row costs no
+// second pass over memory:
 //   1. The row maximum: every lane reads its vector v = 64 pass + lane of every pass (NPASS = 4 at C = 1920, 5 at 2304) and keeps
 //      the largest |pattern| (vec_absmax16); the dead vectors v >= VPR of the last pass (16 lanes at 1920, 32 at 2304) read
 //      nothing and contribute zero; row_max_dpp<64> joins the lanes.  row_scale16 makes the scale and its reciprocal exactly as
 //      rows16_lut_wave_kernel / rows16_codes6_wave_kernel do: an all-zero row, a row with an inf and a row with a NaN come out as
 //      the stand-alone per-token quantizer's on the same y.
 //   2. The second walk over the image, one 16-byte vector per lane and pass in row order, runs that quantizer's lane code with the
-//      row's scale.  MODE 0: quant_vec16 on the level table -> fp16 values (and y itself where `rot_out` is given).  MODE 1:
+//      row's scale.  kValues: quant_vec16 on the level table -> fp16 values (and y itself where `rot_out` is given).  kCodes:
 //      the 8 codes of the vector from the 6-bit code table (lut16_codes6: E2M3 or E3M2) as 48 bits; the four lanes of a quad
 //      own one 32-element block = 24 contiguous bytes of the row, and lane q of the quad takes the (3 - q) upper 16-bit words of
 //      its own string and the q + 1 lower words of its right neighbour's (one quad_perm DPP move each half), so lanes 0 .. 2 store 8
@@ -26,11 +25,11 @@
 template <int K, int M>
 __device__ __forceinline__ int fr_image_at(int v) { return (v / (M / 8)) * FrGeom<K, M>::STRIDE + (v % (M / 8)) * 16; }
 
-// MODE 0: values out (`rot_out`: the rotated rows too, or null); 1: dense 6-bit operand codes (`outv`: row-major [rows][C * 3 / 4] or
-// the k-major image of r.km_rows rows; `lut` staged from the code table).  r.code_scales: the row scales (fp16 [rows]; MODE 0: or null)
-template <int K, int M, int MODE>
+// kValues: values out (`rot_out`: the rotated rows too, or null); kCodes: dense 6-bit operand codes (`outv`: row-major [rows][C * 3 / 4]
+// or the k-major image of km_rows rows; `lut` staged from the code table).  code_scales: the row scales (fp16 [rows]; kValues: or null)
+template <int K, int M, FrMode MODE>
 __device__ __forceinline__ void fr_token_image(const char* img, const uint16_t* lut, int lane, int64_t row, void* __restrict__ outv,
-                                               u32x4* __restrict__ rot_out, const FullRotArgs& r, const Lut16Args& a) {
+                                               u32x4* __restrict__ rot_out, uint16_t* code_scales, uint32_t km_rows, const Lut16Args& a) {
   using G = FrGeom<K, M>;
   static_assert(G::VPR % 4 == 0, "a quad of lanes is live or dead as a whole");
   uint32_t m = 0;
@@ -45,14 +44,14 @@ __device__ __forceinline__ void fr_token_image(const char* img, const uint16_t* 
   }
   m = row_max_dpp<64>(m);
   const RowScale16 s = row_scale16(m, a.fpos.gmax, a.inv_gpos);
-  if ((MODE == 1 || r.code_scales) && lane == 0) r.code_scales[row] = (uint16_t)(s.s16x2 & 0xFFFFu);
+  if ((MODE == FrMode::kCodes || code_scales) && lane == 0) code_scales[row] = (uint16_t)(s.s16x2 & 0xFFFFu);
 #pragma unroll 1   // (as fr_quant_image's: unrolled, the passes' quantizer chains interleave and cost registers)
   for (int pv = 0; pv < G::NPASS; ++pv) {
     const int v = pv * 64 + lane;
     const bool live = v < G::VPR;
     u32x4 w = *(const u32x4*)(img + (live ? fr_image_at<K, M>(v) : 0));
     if (!live) w = u32x4{0, 0, 0, 0};
-    if constexpr (MODE == 1) {
+    if constexpr (MODE == FrMode::kCodes) {
       uint32_t lo4, hi4;   // eight 6-bit codes, one per byte
       codes8_vec16(w, lut, a.shift, s.inv, s.inv_lo, lo4, hi4);
       const uint64_t own = (uint64_t)((lo4 & 0x3Fu) | ((lo4 >> 2) & 0xFC0u) | ((lo4 >> 4) & 0x3F000u) | ((lo4 >> 6) & 0xFC0000u)) |
@@ -64,9 +63,9 @@ __device__ __forceinline__ void fr_token_image(const char* img, const uint16_t* 
       const uint64_t w6 = (own >> sr) | (nb << (48u - sr));
       if (live && qp < 3u) {
         const u32x2 o2 = {(uint32_t)w6, (uint32_t)(w6 >> 32)};
-        if (r.km_rows) {   // plain stores: the rows of a workgroup fill whole lines of a plane between them (fpq_codes_fp6.h)
+        if (km_rows) {   // plain stores: the rows of a workgroup fill whole lines of a plane between them (fpq_codes_fp6.h)
           const uint32_t wb = 24u * (b & 3u) + 8u * qp;
-          *(u32x2*)((uint8_t*)outv + km6_off((uint32_t)row, b >> 2, wb >> 4, r.km_rows) + (wb & 15u)) = o2;
+          *(u32x2*)((uint8_t*)outv + km6_off((uint32_t)row, b >> 2, wb >> 4, km_rows) + (wb & 15u)) = o2;
         } else {
           __builtin_nontemporal_store(o2, (u32x2*)((uint8_t*)outv + row * (G::C / 4 * 3) + 24u * b + 8u * qp));
         }
@@ -78,86 +77,5 @@ __device__ __forceinline__ void fr_token_image(const char* img, const uint16_t* 
         if (rot_out) __builtin_nontemporal_store(w, rot_out + row * G::VPR + v);
       }
     }
-  }
-}
-
-// fullrot_quant_kernel with the per-token tail.  MODE: fr_token_image's
-template <int K, int M, typename Tin, bool SMOOTH, int MODE>
-__global__ __launch_bounds__(kBlock, kFrWaves) void fulltok_quant_kernel(const void* __restrict__ xv, void* __restrict__ outv,
-                                                                         u32x4* __restrict__ rot_out, int64_t rows, FullRotArgs r,
-                                                                         Lut16Args a, Lut16Tab tab) {
-  using G = FrGeom<K, M>;
-  __shared__ __attribute__((aligned(16))) uint16_t lut[kLutLdsEntries];
-  __shared__ __attribute__((aligned(16))) char img_s[kBlock / 64][G::IMG];
-  __shared__ uint32_t sign_s[G::SIGNW];
-  __shared__ u32x4 had_s[G::KT * 2 * 64];
-  __shared__ u32x4 sgn_s[G::KT * G::KS * 64];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t step = (int64_t)gridDim.x * (kBlock / 64);
-  int64_t row = (int64_t)blockIdx.x * (kBlock / 64) + wave;
-  const __amdgpu_buffer_rsrc_t smooth = rq_rsrc(r.smooth, SMOOTH ? G::C * 4 : 0);
-  auto row_rsrc = [&](int64_t t) { return rq_rsrc((const char*)xv + t * (G::C * (int64_t)sizeof(Tin)), G::C * (int)sizeof(Tin)); };
-  constexpr bool PREFETCH = G::KT * G::KS * 4 <= 16;   // fullrot_quant_kernel's rule
-  FrRow<K, M> h;
-  if (row < rows) fr_load_row<K, M, Tin, SMOOTH>(row_rsrc(row), smooth, lane, h);   // in flight while the tables are staged
-  fr_stage_tables<K, M>(r, a, tab, lut, sign_s, had_s, sgn_s);
-  char* img = img_s[wave];
-  const FrLane lc = fr_lane_consts(lane);
-  while (row < rows) {
-    fullrot_transform_row<K, M>(h, sgn_s, had_s, lc, r.c_h, img, lane);
-    __builtin_amdgcn_wave_barrier();
-    const int64_t next = row + step;
-    if (PREFETCH && next < rows) fr_load_row<K, M, Tin, SMOOTH>(row_rsrc(next), smooth, lane, h);   // in flight under the quantizer
-    fr_token_image<K, M, MODE>(img, lut, lane, row, outv, rot_out, r, a);
-    __builtin_amdgcn_wave_barrier();   // the image is rewritten by the next row
-    row = next;
-    if (!PREFETCH && row < rows) fr_load_row<K, M, Tin, SMOOTH>(row_rsrc(row), smooth, lane, h);
-  }
-}
-
-// fullrot_adaln_kernel with the per-token tail.  MODE 0: h goes out where ad.h_out is given (no bytes behind a null pointer: the
-// stores are dropped), the rotated rows where rot_out is; 1: operand codes only
-template <int K, int M, typename Tin, typename Tmod, int MODE>
-__global__ __launch_bounds__(kBlock, (kFaWaves<K, M, Tin, Tmod>)) void fulltok_adaln_kernel(const void* __restrict__ xv, void* __restrict__ outv,
-                                                                         u32x4* __restrict__ rot_out, int64_t rows, FullRotArgs r,
-                                                                         FullAdalnArgs ad, Lut16Args a, Lut16Tab tab) {
-  using G = FrGeom<K, M>;
-  __shared__ __attribute__((aligned(16))) uint16_t lut[kLutLdsEntries];
-  __shared__ __attribute__((aligned(16))) char img_s[kBlock / 64][G::IMG];
-  __shared__ uint32_t sign_s[G::SIGNW];
-  __shared__ u32x4 had_s[G::KT * 2 * 64];
-  __shared__ u32x4 sgn_s[G::KT * G::KS * 64];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t step = (int64_t)gridDim.x * (kBlock / 64);
-  int64_t row = (int64_t)blockIdx.x * (kBlock / 64) + wave;
-  const bool has_smooth = r.smooth != nullptr;
-  const __amdgpu_buffer_rsrc_t smooth = rq_rsrc(r.smooth, has_smooth ? G::C * 4 : 0);
-  auto row_rsrc = [&](int64_t t) { return rq_rsrc((const char*)xv + t * (G::C * (int64_t)sizeof(Tin)), G::C * (int)sizeof(Tin)); };
-  constexpr bool PREFETCH = G::KT * G::KS * 4 * FaRaw<K, M, Tin>::W <= kFaPrefetchRegs;   // fullrot_adaln_kernel's rule
-  FaRaw<K, M, Tin> x;
-  if (row < rows) fa_load_raw<K, M, Tin>(row_rsrc(row), lane, x);   // in flight while the tables are staged
-  fr_stage_tables<K, M>(r, a, tab, lut, sign_s, had_s, sgn_s);
-  char* img = img_s[wave];
-  const FrLane lc = fr_lane_consts(lane);
-  while (row < rows) {
-    const uint32_t b = (uint32_t)row / ad.rows_per_batch;   // rows < 2^31
-    const int64_t mod_at = (int64_t)b * (G::C * (int64_t)sizeof(Tmod));
-    const bool emit_h = MODE == 0 && ad.h_out != nullptr;
-    FrRow<K, M> h;
-    float rstd, nm;
-    fa_stats<K, M, Tin>(x, lane, ad.eps, rstd, nm);
-    fa_modulate<K, M, Tin, Tmod, MODE == 0>(x, rstd, nm, rq_rsrc((const char*)ad.scale + mod_at, G::C * (int)sizeof(Tmod)),
-                                            rq_rsrc((const char*)ad.shift + mod_at, G::C * (int)sizeof(Tmod)), smooth, has_smooth,
-                                            rq_rsrc(emit_h ? ad.h_out + row * G::C : nullptr, emit_h ? G::C * 2 : 0), lane, h);
-    fullrot_transform_row<K, M>(h, sgn_s, had_s, lc, r.c_h, img, lane);
-    __builtin_amdgcn_wave_barrier();
-    const int64_t next = row + step;
-    if (PREFETCH && next < rows) fa_load_raw<K, M, Tin>(row_rsrc(next), lane, x);   // in flight under the quantizer
-    fr_token_image<K, M, MODE>(img, lut, lane, row, outv, rot_out, r, a);
-    __builtin_amdgcn_wave_barrier();   // the image is rewritten by the next row
-    row = next;
-    if (!PREFETCH && row < rows) fa_load_raw<K, M, Tin>(row_rsrc(row), lane, x);
   }
 }

@@ -396,10 +396,13 @@ def _rotate(name: str, fam: _Family, x: torch.Tensor, table, d, smooth, kmajor=F
     """The producers of plain rows, x [..., C]: their checks, then the call."""
     require_gpu(x, name)
     c = x.shape[-1]
-    if fam is _ROTATE:
+    if fam is _ROTATE or fam.full:
         if x.dtype not in (torch.float16, torch.float32):
             raise RuntimeError(f"{name}: x must be float16 or float32, got {x.dtype}")
-        if c % 128 != 0:
+        if fam.full:
+            if c not in FULL_WIDTHS:
+                raise RuntimeError(f"{name}: the full-width rotation is built for the widths {FULL_WIDTHS}, got {c}")
+        elif c % 128 != 0:
             raise RuntimeError(f"{name}: the last dimension must be a multiple of 128")
     elif x.dtype not in (torch.float16, torch.float32) or c % 128 != 0:
         raise RuntimeError(f"{name}: x must be float16/float32 with a last dimension that is a multiple of 128")
@@ -409,7 +412,12 @@ def _rotate(name: str, fam: _Family, x: torch.Tensor, table, d, smooth, kmajor=F
 
 def _adaln_args(name: str, fam: _Family, x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, table):
     """The checks of the producers with an adaLN front, x [B, L, C]; returns (C, L, scale rows, shift rows, the table id where the
-    family takes few tables - it is refused here - or None)."""
+    family takes few tables - it is refused here - or None).  The full-width families refuse x's dtype and width first, as `_rotate` does."""
+    if fam.full:
+        if x.dtype not in (torch.float16, torch.float32):
+            raise RuntimeError(f"{name}: x must be float16 or float32, got {x.dtype}")
+        if x.shape[-1] not in FULL_WIDTHS:
+            raise RuntimeError(f"{name}: the full-width rotation is built for the widths {FULL_WIDTHS}, got {x.shape[-1]}")
     require_gpu(x, name)
     if x.dim() != 3:
         raise RuntimeError(f"{name}: x must be [B, L, C]")
@@ -439,23 +447,13 @@ def rotate_quant_mx(x: torch.Tensor, d: Optional[torch.Tensor] = None, smooth: O
     return _rotate("rotate_quant_mx", _ROTATE_MX, x, None, d, smooth, kmajor)
 
 
-def _rotate_full(name: str, fam: _Family, x: torch.Tensor, table, d, smooth, kmajor=False, extra: int = 0):
-    require_gpu(x, name)
-    c = x.shape[-1]
-    if x.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError(f"{name}: x must be float16 or float32, got {x.dtype}")
-    if c not in FULL_WIDTHS:
-        raise RuntimeError(f"{name}: the full-width rotation is built for the widths {FULL_WIDTHS}, got {c}")
-    return _produce(name, fam, x, c, TABLE_IDS[table] if fam.table else 0, d, smooth, kmajor, extra)
-
-
 def rotate_quant_full(x: torch.Tensor, table: str = "e2m1", d: Optional[torch.Tensor] = None,
                       smooth: Optional[torch.Tensor] = None, return_rotated: bool = False):
     """out = fp_quant_*_per_group_cuda( half(x*smooth) @ half(Q) , 128 ) in one launch, Q = get_orthogonal_matrix(C) - the
     FULL-WIDTH randomized Hadamard matrix (the reference's `--rotate` without `--block_rotate`; rotate_model(block_rotate=False)
     is the weight side).  x: [..., C] fp16 or fp32 on the GPU, C in FULL_WIDTHS; d: the C signs (default sign_vector(C, 42)).
     Returns fp16 (and the rotated fp16 tensor when return_rotated)."""
-    return _rotate_full("rotate_quant_full", _FULL, x, table, d, smooth, extra=1 if return_rotated else 0)
+    return _rotate("rotate_quant_full", _FULL, x, table, d, smooth, extra=1 if return_rotated else 0)
 
 
 def rotate_quant_full_mx(x: torch.Tensor, d: Optional[torch.Tensor] = None, smooth: Optional[torch.Tensor] = None,
@@ -463,16 +461,7 @@ def rotate_quant_full_mx(x: torch.Tensor, d: Optional[torch.Tensor] = None, smoo
     """rotate_quant_full(x, "e2m1") emitting the FP4 GEMM's operands instead of values, byte for byte gemm.quantize_mx of the rotated
     rows: (codes uint8 [rows, C/2], scales fp16 [rows, C/128]), or (kmajor) the k-major images - codes [C/128, rows, 64], scales
     fp32 [C/128, rows rounded up to 4]."""
-    return _rotate_full("rotate_quant_full_mx", _FULL_MX, x, None, d, smooth, kmajor)
-
-
-def _adaln_full_args(name: str, fam: _Family, x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor):
-    """_rotate_full's refusals, then _adaln_args' checks."""
-    if x.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError(f"{name}: x must be float16 or float32, got {x.dtype}")
-    if x.shape[-1] not in FULL_WIDTHS:
-        raise RuntimeError(f"{name}: the full-width rotation is built for the widths {FULL_WIDTHS}, got {x.shape[-1]}")
-    return _adaln_args(name, fam, x, scale, shift, None)
+    return _rotate("rotate_quant_full_mx", _FULL_MX, x, None, d, smooth, kmajor)
 
 
 def adaln_rotate_quant_full(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, table: str = "e2m1",
@@ -485,7 +474,7 @@ def adaln_rotate_quant_full(x: torch.Tensor, scale: torch.Tensor, shift: torch.T
     (default sign_vector(C, 42)).  Returns fp16 [B, L, C] (plus h and the rotated tensor when return_intermediates): h as
     adaln_rotate_quant's, the rest rotate_quant_full(h) bit for bit."""
     name = "adaln_rotate_quant_full"
-    c, seq, sc, sh, _ = _adaln_full_args(name, _FULL_ADALN, x, scale, shift)
+    c, seq, sc, sh, _ = _adaln_args(name, _FULL_ADALN, x, scale, shift, None)
     return _produce(name, _FULL_ADALN, x, c, TABLE_IDS[table], d, smooth, False, 2 if return_intermediates else 0, sc, sh, seq, eps)
 
 
@@ -496,7 +485,7 @@ def adaln_rotate_quant_full_mx(x: torch.Tensor, scale: torch.Tensor, shift: torc
     gemm.quantize_mx of the rotated rows: (codes uint8 [B*L, C/2], scales fp16 [B*L, C/128]), or (kmajor) the k-major images - codes
     [C/128, B*L, 64], scales fp32 [C/128, B*L rounded up to 4]."""
     name = "adaln_rotate_quant_full_mx"
-    c, seq, sc, sh, _ = _adaln_full_args(name, _FULL_ADALN_MX, x, scale, shift)
+    c, seq, sc, sh, _ = _adaln_args(name, _FULL_ADALN_MX, x, scale, shift, None)
     return _produce(name, _FULL_ADALN_MX, x, c, 0, d, smooth, kmajor, 0, sc, sh, seq, eps)
 
 
@@ -528,7 +517,7 @@ def rotate_quant_full_token(x: torch.Tensor, table: str = "e2m3", d: Optional[to
     fam = _full_token_form(name, _FULL_TOKEN, table, emit, kmajor)
     if return_rotated and emit != "values":
         raise RuntimeError(f"{name}: the rotated rows go out with emit='values' only")
-    return _rotate_full(name, fam, x, table, d, smooth, kmajor, 1 if return_rotated else 0)
+    return _rotate(name, fam, x, table, d, smooth, kmajor, 1 if return_rotated else 0)
 
 
 def adaln_rotate_quant_full_token(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, table: str = "e2m3",
@@ -544,7 +533,7 @@ def adaln_rotate_quant_full_token(x: torch.Tensor, scale: torch.Tensor, shift: t
     fam = _full_token_form(name, _FULL_ADALN_TOKEN, table, emit, kmajor)
     if return_intermediates and emit != "values":
         raise RuntimeError(f"{name}: the intermediates go out with emit='values' only")
-    c, seq, sc, sh, _ = _adaln_full_args(name, fam, x, scale, shift)
+    c, seq, sc, sh, _ = _adaln_args(name, fam, x, scale, shift, None)
     return _produce(name, fam, x, c, TABLE_IDS[table], d, smooth, kmajor, 2 if return_intermediates else 0, sc, sh, seq, eps)
 
 

@@ -1205,7 +1205,8 @@ int fpq_dequant_rows_codes_segments(const fpq_decode_segment_t* segments_device,
  *     q  = fp_quant_e{1,2,3}_per_group_cuda(x1, 4, 128) / fp6_quant_*_per_group_cuda
  * becomes one launch:  h = half(x * s);  y = half(c_h * sum_j +-h_j) with the signs of diag(D) . H_cols^T and
  * c_h = float(half(float32(1 / sqrt(cols)))), the one magnitude of half(float32(Q));  out = per-group(128) quant(y).
- * Both Hadamard factors run on the matrix cores, 2 cols (K + cols / K) FLOP per row (csrc/fpq_fullrot.h).
+ * Both Hadamard factors run on the matrix cores, 2 cols (K + cols / K) FLOP per row (csrc/fpq_fullrot.h: the one row loop of every
+ * fpq_fullrot_* entry point; csrc/fpq_fullrot_launch.h: their checks and the launch).
  * Built widths: cols == 1920 (had60 x 2^5) and cols == 2304 (had36 x 2^6).  EVERY other width - the powers of two, 1280 and 1536
  * included - is FPQ_ERR_SHAPE.
  * x: [rows, cols] F16 or F32; smooth: device float[cols] or NULL;
@@ -1231,7 +1232,7 @@ int fpq_fullrot_quant_rows_codes_mx(const void* x, void* codes, void* scales, in
                                     const float* smooth, const uint32_t* sign_words_host, int kmajor, fpq_stream_t stream);
 
 /* The complete producer of tr/basic_var.py:263 / :266 in the FULL-WIDTH mode, one launch: fpq_adaln_rotate_quant_rows' LayerNorm and
- * modulate in front of fpq_fullrot_quant_rows' rotation and quantizer (csrc/fpq_fulladaln.h):
+ * modulate in front of fpq_fullrot_quant_rows' rotation and quantizer (csrc/fpq_fulladaln.h: the adaLN front of that row loop):
  *     h   = half( ((LayerNorm(x) * half(scale + 1)) + shift) * smooth )    (no affine, eps; the statistics of the raw x in fp32, always
  *                                                                            centred; fp16 modulation adds the 1 in fp16)
  *     y   = half( c_h * sum_j +-h_j )             (= h @ half(Q), Q the full-width matrix)
@@ -1260,7 +1261,7 @@ int fpq_fullrot_adaln_quant_rows_codes_mx(const void* x, void* codes, void* scal
 /* Both full-width producers in front of the PER-TOKEN quantizer (W6A6: per-token E2M3 / E3M2 activations, run.sh:7,10,22,25, under
  * `--rotate` without `--block_rotate`): fpq_fullrot_quant_rows' / fpq_fullrot_adaln_quant_rows' launch with
  *     out = fp6_quant_{e2m3,e3m2}_per_token_cuda(y, 6)      ONE scale per row of `cols` channels (tr/quant_utils.py:503-534)
- * behind the rotation instead of the per-group quantizer (csrc/fpq_fulltoken.h).  The rotated row lies complete in the wavefront's
+ * behind the rotation instead of the per-group quantizer (csrc/fpq_fulltoken.h: the second tail of that row loop).  The rotated row lies complete in the wavefront's
  * LDS image when the quantizer starts: the row maximum is one pass over that image, no second pass over memory.
  * Arguments as the per-group twins' (x, smooth, sign_words_host, the modulation block) and as the 128-block token forms'
  * (fpq_adaln_rotate_quant_token_rows, _token_rows_codes_f6): row_scales is the last output pointer, fp16 [rows].

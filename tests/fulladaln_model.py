@@ -38,7 +38,7 @@ def padded(C: int) -> int:
 
 
 def depth(x_dtype, C: int) -> int:
-    """Sequential fp32 additions between an element and the row's sum in fullrot_adaln_kernel (fa_stats), counted from the source:
+    """Sequential fp32 additions between an element and the row's sum in the full-width adaLN front (csrc/fpq_fulladaln.h, fa_stats), counted from the source:
     8 into the operand's accumulator (fp32 rows: 8 v_add_f32; fp16 rows: 4 v_dot2_f32_f16 of 2 additions each; the centred pass: 8
     v_fma_f32), KT KS - 1 to join the operands' accumulators in turn, 6 levels of wave_sum_dpp.
     C = 1920: 8 + 3 + 6 = 17;  C = 2304: 8 + 5 + 6 = 19 - the same for both row dtypes."""
@@ -128,7 +128,7 @@ def _stats(xf: torch.Tensor, C: int, mutation: Optional[str]):
 
 def emulate(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, smooth: Optional[torch.Tensor], eps: float, L: int,
             mutation: Optional[str] = None) -> torch.Tensor:
-    """h (fp16 [R, C]) as fullrot_adaln_kernel computes it, in fp32 on the CPU, in source order (fa_stats, fa_modulate)."""
+    """h (fp16 [R, C]) as the full-width adaLN front computes it, in fp32 on the CPU, in source order (fa_stats, fa_modulate)."""
     assert mutation is None or mutation in MUTATIONS
     R, C = x.shape
     sm = smooth.float() if smooth is not None else None

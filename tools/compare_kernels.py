@@ -1,16 +1,19 @@
 """Machine-code identity of two builds of libfpq_hip.so, on the CPU: every kernel of the second build must carry the same
 instruction stream and the same register / LDS / scratch figures as in the first.
 
-usage: compare_kernels.py BEFORE.so AFTER.so [--rename 'REGEX=>REPLACEMENT' ...]
+usage: compare_kernels.py BEFORE.so AFTER.so [--rename 'REGEX=>REPLACEMENT' ...] [--allow-reorder]
 
 The gfx950 code objects are taken out of each library's .hip_fatbin section as tests/test_no_spill.py does
 (llvm-objcopy, clang-offload-bundler), every kernel symbol is disassembled (llvm-objdump -d --no-show-raw-insn) with
 addresses, branch-target comments and symbol offsets stripped, and kernels are matched by their demangled names.  A
 --rename rule maps a demangled name of BEFORE to the name the kernel carries in AFTER (a template parameter dropped).
 Prints the kernel counts, the kernels that disappeared or appeared (by template name), and every kernel whose code or
-figures differ; exit status 1 if any do."""
+figures differ; exit status 1 if any do.  --allow-reorder: a kernel with equal figures whose instructions are the same
+multiset in another order (the scheduler's answer to a moved source line) is reported as REORDERED with the size of its
+diff and does not fail the run."""
 import argparse
 import collections
+import difflib
 import os
 import re
 import shutil
@@ -160,6 +163,7 @@ def main():
     ap.add_argument("after")
     ap.add_argument("--rename", action="append", default=[], help="'REGEX=>REPLACEMENT' on the demangled names of BEFORE")
     ap.add_argument("--list", action="store_true", help="print every kernel that disappeared or appeared")
+    ap.add_argument("--allow-reorder", action="store_true", help="equal figures and equal sorted instructions: REORDERED, not a failure")
     args = ap.parse_args()
     rules = [(re.compile(r.split("=>")[0]), r.split("=>")[1]) for r in args.rename]
     with tempfile.TemporaryDirectory() as tb, tempfile.TemporaryDirectory() as ta:
@@ -186,7 +190,7 @@ def main():
         print(f"renamed: {len(moved)}")
         for o, n in sorted(moved):
             print(f"  {o}\n    -> {n}")
-    bad = 0
+    bad = reordered = 0
     for old, name in sorted(renamed.items()):
         if name not in after:
             continue
@@ -194,11 +198,16 @@ def main():
         if fb != fa:
             bad += 1
             print(f"FIGURES DIFFER {name}: {fb} -> {fa}")
-        if db is None or da is None or db != da:
+        if args.allow_reorder and fb == fa and db and da and db != da and sorted(db) == sorted(da):
+            reordered += 1
+            moved_lines = [d for d in difflib.unified_diff(db, da, lineterm="", n=0) if d[:1] in "+-" and d[:3] not in ("+++", "---")]
+            print(f"REORDERED {name}: {len(db)} instructions, {len(moved_lines)} diff lines: " + "; ".join(sorted(set(d[1:] for d in moved_lines))))
+        elif db is None or da is None or db != da:
             bad += 1
             print(f"CODE DIFFERS {name}: {len(db or [])} -> {len(da or [])} instructions")
     kept = len(before) - len(gone)
-    print(f"identical: {kept - bad} of {kept} kept kernels" if not bad else f"{bad} differences among {kept} kept kernels")
+    print((f"identical: {kept - bad - reordered} of {kept} kept kernels" if not bad else f"{bad} differences among {kept} kept kernels") +
+          (f", reordered: {reordered}" if args.allow_reorder else ""))
     return 1 if bad else 0
 
 
