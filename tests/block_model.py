@@ -33,6 +33,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from oracle import fpq_oracle as orc
+from tests.gelu_model import reference as gelu_tanh          # the one float64 GELU(tanh) the kernel tests are held to as well
 
 MUTANTS = (
     "swap_sc_sh",                    # 1  (scale1, shift1) <-> (scale2, shift2)
@@ -96,10 +97,6 @@ def params_of(gb) -> BlockParams:
                        mods=[[cpu(t) for t in m] for m in gb.mods], s_qkv=cpu(gb.s_qkv), s_fc1=cpu(gb.s_fc1), Q=cpu(gb.q32),
                        scale_mul=[cpu(t) for t in gb.scale_mul] if l2 else None,
                        qkv_bias=[cpu(t) for t in gb.qkv_bias] if l2 else None)
-
-
-def gelu_tanh(x: torch.Tensor) -> torch.Tensor:
-    return 0.5 * x * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (x + 0.044715 * x ** 3)))
 
 
 def deviation(y, y_model, x) -> float:
